@@ -17,7 +17,10 @@ every rank its own 1e6-cell slice of the (infinite, counter-based) seeded surfac
 the 1e5-cell 2+1D case, `--workload config5` the smooth leg of BASELINE config 5: the anisotropic-hydro (VAH) kernel on a 1e6-cell
 surface with its 14-moment coefficients interpolated on the device from the deltaf_coefficients/vah tables.
 
-One JSON line on stdout (rank 0).  Besides the contract's fields it carries
+One JSON line on stdout (rank 0).  A plain run sets up, warms up, times `--steps` steps, writes the last step's output with
+`--dump-outputs DIR` and prints the contract's fields (metric, value, unit, higher_is_better, dtype, ms_per_step = wall time of one
+timed step, ...), the workload's config and the kernel times of the timed steps.  Everything else it measures or checks runs after
+that with `--full` only, and the line then also carries
   roofline        the contract's object for the dominant kernel, HBM view: algorithmic bytes / kernel time
   roofline_valu   the roofline that actually binds this kernel: fp64 VALU
   cpu_baseline    the CPU oracle (a port of the reference loop) timed on this host's cores (all of them: `cores`, `cores_available`, `cpu_model`),
@@ -56,6 +59,26 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 FP64_VALU_PEAK_TF = 78.6   # 256 CU x 4 SIMD x 16 lanes x 2 flop x 2.4 GHz
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # all files of one dump, .npy headers included
+DUMP_SAMPLE_SEED = 20260003
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> array; all of one length along axis 0 when they are rows of one list) as path/<name>.npy in float64
+    (integer fields are exact below 2**53).  Over DUMP_LIMIT_BYTES in all, a fixed seeded sample of rows is written instead, its row numbers
+    as path/row_index.npy: the same rows for the same row count, so two builds' files compare entry for entry."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    headers = 256 * (len(arrays) + 1)   # an .npy header of these arrays is 128 bytes
+    if total + headers > DUMP_LIMIT_BYTES:
+        n = len(next(iter(arrays.values())))
+        assert all(len(v) == n for v in arrays.values())
+        keep = int((DUMP_LIMIT_BYTES - headers) // (total / n + 8))
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+        arrays = dict({k: v[idx] for k, v in arrays.items()}, row_index=idx.astype(np.float64))
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def workload(name):
@@ -304,9 +327,18 @@ def main():
                          "barriers, MAX over ranks) with a single rank")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend; gloo lets several ranks share one GPU (rehearsal on a 1-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else this script measures or checks: the CPU baseline, the shader clock probe, the steps with "
+                         "transfers, the host entry, the culling checks, roofline / roofline_valu and the per-rank entries (without it: set-up, warm-up, "
+                         "the timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0: the spectrum; the sampler: its particle list, a seeded sample of rows "
+                         "beyond 64 MB) as DIR/<name>.npy in float64")
     a = ap.parse_args()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a.gpus, sys.argv[1:]))   # before torch is imported or HIP touched in this process
 
@@ -478,13 +510,44 @@ def main():
         plan.check(stream)   # the timed steps ran without status read-back: any cell outside the coefficient table surfaces here
     if comm is not None and not vah:
         comm.check(stream)   # ... and so does any rank whose execute failed before a collective (the error word summed beside the spectrum)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"dN_pTdpTdphidy": out.cpu().numpy()})   # flat, as is3d_smooth_spectra returns it; N > 1: the summed spectrum
+    nbins = len(grid["pT"]) * len(grid["phi"]) * (len(grid["y"]) if wl["dimension"] == 3 else 1)
+    nsp = len(sp["mass"])
+    evals_step = float(n_total) * nbins * nsp
+    head = dict(metric="FO-cell x momentum-bin x species evals/sec", value=evals_step * a.steps / elapsed, unit="evals/s", n_gpus=world, steps=a.steps,
+                warmup=a.warmup, ms_per_step=elapsed / a.steps * 1e3, higher_is_better=True, scaling=a.scaling, vs_baseline=None, dtype="f64", data="synthetic")
+    value_note = ("reference-equivalent evals (cells x bins x all %d species, every row) per second, cell arrays resident in HBM when the "
+                  "timed region starts (the bench contract)" % nsp)
+    config = dict(workload=wl["text"], cells_total=n_total, cells_per_gpu=n_loc, species=nsp, bins=nbins, evals_per_step=evals_step, kernel=plan.main_kernel_name,
+                  parallelism=("cell-axis shards x%d of %s, one all-reduce of the spectrum" % (
+                      world, "one surface (BASELINE config 4 at 8)" if a.scaling == "strong" else "a surface that grows with N")) if world > 1 else "1 GPU",
+                  workspace_GB=plan.workspace_bytes / 1e9, workspace_bytes_per_cell=plan.workspace_bytes / float(max(n_loc, 1)))
+    kernel_ms = dict(prep=float(np.mean(ms["prep"])), main=float(np.mean(ms["main"])), finalize=float(np.mean(ms["finalize"])))   # HIP events of the timed steps
+
+    def finish():
+        plan.close()
+        if comm is not None:
+            comm.close()
+        if multi:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not a.full:
+        if rank == 0:
+            res = dict(head, value_note=value_note, transfers_included=False, allreduce=allreduce_by,
+                       config=dict(config, spectrum_finite=bool(torch.isfinite(out).all().item())), kernel_ms=kernel_ms)
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(res) + "\n").encode())
+        finish()
+        return
+
     st = plan.execute(n_loc, ptrs, out.data_ptr(), stream)   # untimed: status (classes, skipped cells) + sanity
     torch.cuda.synchronize()
-    nbins = len(grid["pT"]) * len(grid["phi"]) * (len(grid["y"]) if wl["dimension"] == 3 else 1)
     culled = (st["n_wave_rows_culled"] / st["n_wave_rows"]) if st.get("n_wave_rows") else 0.0
     unique_evals = float(n_loc) * nbins * st["n_classes"] * (len(grid["eta"]) if wl["dimension"] == 2 else 1)
     executed_evals = unique_evals * (1.0 - culled)   # rows the kernel proved unable to change a bit for a whole wave are not executed
-    ms_main = float(np.mean(ms["main"]))
+    ms_main = kernel_ms["main"]
     # ---- the binding roofline, per rank: fp64 VALU (flops and instructions per integrand from the emitted ISA, this rank's own culled fraction and kernel time)
     ic = isa_counts(plan.main_kernel_name, wl, plan.tile_shape, st["kernel_variant"], baryon=bool(wl.get("baryon")))
 
@@ -526,7 +589,7 @@ def main():
     ranks = None
     if multi:
         mine = dict(rank=rank, device=local, cells=n_loc, first_cell=lo,
-                    kernel_ms=dict(prep=float(np.mean(ms["prep"])), main=ms_main, finalize=float(np.mean(ms["finalize"]))),
+                    kernel_ms=kernel_ms,
                     allreduce_ms=float(np.mean(ms["allreduce"])) if ms["allreduce"] else None,
                     comm_rank_seen=list(comm.rank_seen()) if comm is not None else None,
                     wave_rows_culled_frac=culled, integrands_executed=executed_evals, roofline_valu=rv)
@@ -602,9 +665,7 @@ def main():
     spectrum_ok = bool(torch.isfinite(out).all().item())
 
     if rank == 0:
-        nsp = len(sp["mass"])
-        evals_step = float(n_total) * nbins * nsp
-        value = evals_step * a.steps / elapsed
+        value = head["value"]
         # ---- roofline (contract form, HBM): algorithmic bytes of the launch = cell arrays read once + spectrum written once
         ncell_arrays = len(cell_fields) - (0 if wl["dimension"] == 3 else 1)   # 18 (17 in 2+1D: no eta; 23 / 22 with the baryon arrays); VAH: 24
         b_alg = 8.0 * (ncell_arrays * n_loc + nsp * nbins)
@@ -619,14 +680,11 @@ def main():
         executed_all = sum(r["integrands_executed"] for r in ranks) if ranks else executed_evals
         executed_per_s = executed_all * a.steps / elapsed
         inner = len(grid["eta"]) if wl["dimension"] == 2 else 1   # 2+1D: an eval is a sum over the eta table; integrands are its terms
-        res = dict(metric="FO-cell x momentum-bin x species evals/sec", value=value, unit="evals/s", n_gpus=world, steps=a.steps,
-                   warmup=a.warmup, ms_per_step=elapsed / a.steps * 1e3, higher_is_better=True, scaling=a.scaling, vs_baseline=None,
-                   dtype="f64", data="synthetic",
-                   value_note="reference-equivalent evals (cells x bins x all %d species, every row) per second, cell arrays resident in HBM when the "
-                              "timed region starts (the bench contract); SURVEY.md 8d's t_kernel also contains the H->D upload of the cell arrays and the "
+        res = dict(head,
+                   value_note=value_note + "; SURVEY.md 8d's t_kernel also contains the H->D upload of the cell arrays and the "
                               "D->H download of the spectrum: value_incl_transfers / ms_per_step_incl_transfers.  The kernel executes %d species "
                               "classes and %.1f %% of their rows: executed_evals_per_s (2+1D: integrands = evals x %d eta nodes)" % (
-                                  nsp, st["n_classes"], 100.0 * (1.0 - culled), inner),
+                                  st["n_classes"], 100.0 * (1.0 - culled), inner),
                    executed_evals_per_s=executed_per_s, executed_fraction_of_value=executed_per_s / (value * inner),
                    transfers_included=False,
                    value_incl_transfers=evals_step / incl,
@@ -636,14 +694,9 @@ def main():
                    allreduce_ms=(max(r["allreduce_ms"] for r in ranks) if ranks and all(r["allreduce_ms"] is not None for r in ranks) else None),
                    ranks_seen=(sorted(r["comm_rank_seen"][0] for r in ranks) if ranks and all(r["comm_rank_seen"] for r in ranks) else None),
                    ranks=ranks,
-                   config=dict(workload=wl["text"], cells_total=n_total, cells_per_gpu=n_loc, species=nsp, species_classes_evaluated=st["n_classes"],
-                               bins=nbins, evals_per_step=evals_step, kernel=plan.main_kernel_name, kernel_variant=st["kernel_variant"],
-                               parallelism=("cell-axis shards x%d of %s, one all-reduce of the spectrum" % (
-                                   world, "one surface (BASELINE config 4 at 8)" if a.scaling == "strong" else "a surface that grows with N")) if world > 1 else "1 GPU",
-                               workspace_GB=plan.workspace_bytes / 1e9, workspace_bytes_per_cell=plan.workspace_bytes / float(max(n_loc, 1)),
-                               spectrum_finite=spectrum_ok,
+                   config=dict(config, species_classes_evaluated=st["n_classes"], kernel_variant=st["kernel_variant"], spectrum_finite=spectrum_ok,
                                culled_rows_change_no_bit=cull_identical),
-                   kernel_ms=dict(prep=float(np.mean(ms["prep"])), main=ms_main, finalize=float(np.mean(ms["finalize"])), main_no_cull=ms_no_cull, surface_cull=surf_cull),
+                   kernel_ms=dict(kernel_ms, main_no_cull=ms_no_cull, surface_cull=surf_cull),
                    roofline=roofline, roofline_valu=rv)
         if clock_err:
             res["clock_probe_error"] = clock_err
@@ -657,12 +710,7 @@ def main():
             res["gpu_over_cpu"] = value / res["cpu_baseline"]["value"]
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(res) + "\n").encode())
-    plan.close()
-    if comm is not None:
-        comm.close()
-    if multi:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 def sampler_cpu_baseline(cells, sp, df, gla, opts, n_events, seed, seconds_budget):
@@ -745,9 +793,12 @@ def bench_sampler(a, rank, world, local, dev, multi, json_fd):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if a.dump_outputs and rank == 0:
+        got = np.frombuffer(buf.cpu().numpy().tobytes(), dtype=api.PARTICLE_DTYPE)[:count]
+        dump_outputs(a.dump_outputs, {"particles_" + f: got[f] for f in got.dtype.names})   # N > 1: rank 0's list, the particles of its shard
     # the one-shot host entry (pageable arrays in, particle list out, plan + workspaces created inside): what operation = 2 of the driver calls
     host_entry = None
-    if world == 1:
+    if world == 1 and a.full:
         t1 = time.perf_counter()
         plist, sth = api.sample_particles(cells, sp, df, gla, opts, n_events=a.events, seed=seed, fq=fq)
         host_entry = dict(ms=(time.perf_counter() - t1) * 1e3, ms_h2d=sth["ms_h2d"], ms_device=sth["ms_prep"] + sth["ms_count"] + sth["ms_fill"],
@@ -770,6 +821,28 @@ def bench_sampler(a, rank, world, local, dev, multi, json_fd):
     kms["cells_records"] = kms["prep"] - kms["density"]
     kms["count_and_scan"] = kms["count"] - kms["poisson"]
     value = float(n_total) * a.events * a.steps / elapsed
+    res = dict(metric="FO-cell x event samples/sec (Monte Carlo particle sampler, the second leg of BASELINE config 5)", value=value, unit="cell-events/s",
+               n_gpus=world, steps=a.steps, warmup=a.warmup, ms_per_step=elapsed / a.steps * 1e3, higher_is_better=True, scaling=a.scaling, vs_baseline=None,
+               dtype="f64", data="synthetic",
+               particles_per_s=float(particles_all) * a.steps / elapsed, particles_per_step=particles_all,
+               hadrons_drawn_per_step=int(last["n_hadrons_drawn"]) if not ranks else sum(r["hadrons_drawn"] for r in ranks),
+               momentum_sampling_efficiency=last["n_acceptances"] / max(last["n_momentum_samples"], 1),
+               device_ms_per_step=dev_ms, device_allocations_during_timed_steps=allocs_in_steps,
+               value_note="(cell, event) pairs sampled per second, wall clock of the steps; cell arrays and the particle buffer resident in HBM; a step also "
+                          "reads back two counters per event batch (the number of emitting pairs, the batch's particle count), nothing else crosses PCIe",
+               ranks=ranks,
+               config=dict(workload="BASELINE config 5, sampler leg: 1e6-cell synthetic 3+1D surface (seed 20260002), %s, 305-species pdg-urqmd_v3.3+ list, "
+                                    "%d events per step, regular (not fast) mode; the reference's VAH sampler is an empty stub "
+                                    "(emissionfunction_sampling_kernels.cpp:1231-1239), so the viscous-hydro sampler is what exists to be measured" % (
+                                        {1: "14-moment delta-f", 2: "Chapman-Enskog delta-f", 3: "modified equilibrium (Mike)", 4: "modified equilibrium (Jonah)"}[df_mode], a.events),
+                           cells_total=n_total, cells_per_gpu=n_loc, species=len(sp["mass"]), species_classes_evaluated=last["n_classes"], events=a.events,
+                           df_mode=df_mode, parallelism=("cell-axis shards x%d, no collective" % world) if world > 1 else "1 GPU"),
+               kernel_ms=kms)
+    if not a.full:
+        sys.stdout.flush()
+        os.write(json_fd, (json.dumps(res) + "\n").encode())
+        plan.close()
+        return
     n_used_arrays = 18
     b_alg = 8.0 * n_used_arrays * n_loc + 96.0 * count
     # fp64-VALU view of the Gauss-Laguerre density kernel (flops per node from the emitted ISA, tools/count_isa.py)
@@ -788,23 +861,7 @@ def bench_sampler(a, rank, world, local, dev, multi, json_fd):
     if pps:
         div = json.load(open(pps[-1]))
         div.setdefault("file", "profiles/" + os.path.basename(pps[-1]))
-    res = dict(metric="FO-cell x event samples/sec (Monte Carlo particle sampler, the second leg of BASELINE config 5)", value=value, unit="cell-events/s",
-               n_gpus=world, steps=a.steps, warmup=a.warmup, ms_per_step=elapsed / a.steps * 1e3, higher_is_better=True, scaling=a.scaling, vs_baseline=None,
-               dtype="f64", data="synthetic",
-               particles_per_s=float(particles_all) * a.steps / elapsed, particles_per_step=particles_all,
-               hadrons_drawn_per_step=int(last["n_hadrons_drawn"]) if not ranks else sum(r["hadrons_drawn"] for r in ranks),
-               momentum_sampling_efficiency=last["n_acceptances"] / max(last["n_momentum_samples"], 1),
-               device_ms_per_step=dev_ms, device_allocations_during_timed_steps=allocs_in_steps,
-               value_note="(cell, event) pairs sampled per second, wall clock of the steps; cell arrays and the particle buffer resident in HBM; a step also "
-                          "reads back two counters per event batch (the number of emitting pairs, the batch's particle count), nothing else crosses PCIe",
-               host_entry=host_entry, same_list_as_host_entry=(same_as_host_entry if world == 1 else None), ranks=ranks,
-               config=dict(workload="BASELINE config 5, sampler leg: 1e6-cell synthetic 3+1D surface (seed 20260002), %s, 305-species pdg-urqmd_v3.3+ list, "
-                                    "%d events per step, regular (not fast) mode; the reference's VAH sampler is an empty stub "
-                                    "(emissionfunction_sampling_kernels.cpp:1231-1239), so the viscous-hydro sampler is what exists to be measured" % (
-                                        {1: "14-moment delta-f", 2: "Chapman-Enskog delta-f", 3: "modified equilibrium (Mike)", 4: "modified equilibrium (Jonah)"}[df_mode], a.events),
-                           cells_total=n_total, cells_per_gpu=n_loc, species=len(sp["mass"]), species_classes_evaluated=last["n_classes"], events=a.events,
-                           df_mode=df_mode, parallelism=("cell-axis shards x%d, no collective" % world) if world > 1 else "1 GPU"),
-               kernel_ms=kms,
+    res.update(host_entry=host_entry, same_list_as_host_entry=(same_as_host_entry if world == 1 else None),
                roofline=dict(bound="hbm", achieved=b_alg / (dev_ms * 1e-3) / 1e9, peak=HBM_PEAK_GBS, unit="GB/s", frac=b_alg / (dev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                              traffic=(div or {}).get("hbm_bytes_per_step"), traffic_source=(div or {}).get("source"),
                              kernel="the sampler's kernels of one step (density, cell records, Poisson, compaction, count, scan, fill)", kernel_ms=dev_ms,

@@ -8,12 +8,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REFERENCE = "/root/reference"   # present only in the build container; never read by -m gpu tests
+# data files of the original iS3D distribution, unchanged and at their paths there, that the reader tests parse: particle lists
+# (PDG/), delta-f coefficient tables (deltaf_coefficients/), the generator's particle list and Gauss-Laguerre nodes
+# (generate_delta_f_coefficients/), momentum / eta tables (tables/), input/surface.dat and iS3D_parameters.dat
+REFERENCE_DATA = os.path.join(ROOT, "tests", "golden", "reference_data.tar.xz")
 
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-    config.addinivalue_line("markers", "reference: reads data files under /root/reference (container only)")
     config.addinivalue_line("markers", "devlib: has work for the developer build of the library too (A/B kernel variants): tests/test_gpu_devlib.py re-runs it there")
     # a fresh checkout has no built library (build products are git-ignored): build it once, as __graft_entry__.build() does
     lib = os.path.join(ROOT, "is3d_amd", "lib", "libis3d_amd.so")
@@ -22,11 +24,17 @@ def pytest_configure(config):
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "is3d_amd", "csrc"), "-j4"], stdout=subprocess.DEVNULL)
 
 
-def pytest_collection_modifyitems(config, items):
-    skip_ref = pytest.mark.skip(reason="/root/reference not present")
-    for item in items:
-        if "reference" in item.keywords and not os.path.isdir(REFERENCE):
-            item.add_marker(skip_ref)
+def unpack_reference_data(dest):
+    """REFERENCE_DATA unpacked under `dest`; returns `dest`, the root the archive's relative paths start from."""
+    import tarfile
+    with tarfile.open(REFERENCE_DATA) as t:
+        t.extractall(dest, **({"filter": "data"} if hasattr(tarfile, "data_filter") else {}))
+    return dest
+
+
+@pytest.fixture(scope="session")
+def reference(tmp_path_factory):
+    return unpack_reference_data(str(tmp_path_factory.mktemp("reference")))
 
 
 def honoured(kind, dim, variants, baryon=False):

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -20,7 +21,7 @@ pytestmark = pytest.mark.gpu
                                                    ("config2", "cf_main_tile", ["--include-baryon"])])
 def test_bench_line(workload, kernel, extra):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--cells", "6000", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", workload, "--cells", "6000", "--steps", "2", "--warmup", "1",
                         "--cpu-baseline-seconds", "1", "--no-clock-probe"] + extra, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -59,7 +60,7 @@ def test_bench_line_sampler_leg():
     contract's fields, per-kernel device times, the HBM-form roofline, the fp64-VALU roofline of the density kernel, a serial CPU baseline on a
     slice whose list is the device's, and a second execute of the same shape that allocates nothing."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "config5-sampler", "--cells", "20000", "--events", "5", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "config5-sampler", "--cells", "20000", "--events", "5", "--steps", "2",
                         "--warmup", "1", "--cpu-baseline-seconds", "1"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -78,3 +79,47 @@ def test_bench_line_sampler_leg():
     ro, rv = d["roofline"], d["roofline_valu"]
     assert ro["bound"] == "hbm" and abs(ro["frac"] - ro["achieved"] / ro["peak"]) < 1e-12 and ro["algorithmic_bytes"] == 8.0 * 18 * 20000 + 96.0 * d["particles_per_step"]
     assert rv["bound"] == "fp64_valu" and rv["kernel"] == "cf_sampler_density" and 0 < rv["frac"] < 1
+
+
+def test_plain_bench_line_and_its_outputs(tmp_path, fx):
+    """A plain run (no --full): exactly --steps timed steps, the contract's fields and nothing the full run adds; --dump-outputs holds the
+    spectrum of the last timed step, the one the host entry computes for the same seeded surface."""
+    from conftest import relerr
+    from is3d_amd import api, synth
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cells", "6000", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config", "kernel_ms"):
+        assert key in d, key
+    for key in ("cpu_baseline", "roofline", "roofline_valu", "host_entry", "value_incl_transfers", "executed_evals_per_s"):
+        assert key not in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "evals/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["value"] == pytest.approx(6000.0 * d["config"]["bins"] * d["config"]["species"] / (d["ms_per_step"] * 1e-3), rel=1e-9)
+    assert d["config"]["spectrum_finite"] and d["kernel_ms"]["main"] > 0
+    got = np.load(str(tmp_path / "dN_pTdpTdphidy.npy"))
+    assert got.dtype == np.float64 and got.size == d["config"]["species"] * d["config"]["bins"]
+    want, _ = api.smooth_spectra(synth.synth_surface(6000, 3), fx["urqmd"], fx["grid"], fx["df"], dict(dimension=3, df_mode=2))
+    assert relerr(got, want) < 1e-12
+
+
+def test_plain_sampler_line_and_its_particle_list(tmp_path, fx):
+    """The sampler leg without --full: the particle list of the last timed step in --dump-outputs, field for field the host entry's list."""
+    from is3d_amd import api, inputs, synth
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "config5-sampler", "--cells", "20000", "--events", "5", "--steps", "2",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["unit"] == "cell-events/s" and d["ms_per_step"] > 0 and "cpu_baseline" not in d and "host_entry" not in d
+    want, _ = api.sample_particles(synth.synth_surface(20000, 3), fx["urqmd"], fx["df"], inputs.feqmod_tables(0.15), dict(dimension=3, df_mode=2),
+                                   n_events=5, seed=20260002)
+    assert len(want) == d["particles_per_step"] and not os.path.exists(str(tmp_path / "row_index.npy"))
+    for f in want.dtype.names:
+        got = np.load(str(tmp_path / ("particles_%s.npy" % f)))
+        assert got.dtype == np.float64 and np.array_equal(got, want[f].astype(np.float64)), f

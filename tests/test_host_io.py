@@ -6,7 +6,6 @@ import numpy as np
 import pytest
 
 import refformat
-from conftest import REFERENCE
 from is3d_amd import api, inputs, synth
 
 
@@ -366,26 +365,25 @@ def test_writer_is_byte_for_byte_the_iostream_text(tmp_path):
     assert open(os.path.join(res, "dN_pTdpTdphidy.dat")).read() == "".join(want_all)
 
 
-@pytest.mark.reference
-def test_readers_on_the_reference_files():
+def test_readers_on_the_reference_files(reference):
     """The shipped data files parse to the fixture the GPU box uses (is3d_amd/data/inputs_urqmd.json)."""
     g = inputs.grid()
     for key, rel in [("pT", "tables/pT_gauss_legendre_table.dat"), ("phi", "tables/phi_gauss_legendre_table.dat"),
                      ("y", "tables/y_trapezoid_table_21pt.dat"), ("eta", "tables/eta/eta_trapezoid_table_241pt.dat")]:
-        t = api.table_read(os.path.join(REFERENCE, rel))
+        t = api.table_read(os.path.join(reference, rel))
         assert np.array_equal(t[:, 0], g[key]) and np.array_equal(t[:, 1], g[key + "_w"])
     df = inputs.df_tables()
     for name in ("c0", "c2", "F", "betabulk", "betapi"):
-        T, v = api.df_table_read(os.path.join(REFERENCE, "deltaf_coefficients/vh/urqmd", name + ".dat"))
+        T, v = api.df_table_read(os.path.join(reference, "deltaf_coefficients/vh/urqmd", name + ".dat"))
         assert np.array_equal(T, df["T"]) and np.array_equal(v, df[name])
-    pdg = api.pdg_read(os.path.join(REFERENCE, "PDG/pdg-urqmd_v3.3+.dat"))
+    pdg = api.pdg_read(os.path.join(reference, "PDG/pdg-urqmd_v3.3+.dat"))
     ref = np.array(inputs.load_fixture()["pdg_urqmd"], dtype=np.float64)
     assert np.array_equal(pdg["mc_id"], ref[:, 0].astype(np.int64)) and np.array_equal(pdg["mass"], ref[:, 1])
-    chosen = api.table_read(os.path.join(REFERENCE, "PDG/chosen_particles_urqmd_v3.3+.dat"))
+    chosen = api.table_read(os.path.join(reference, "PDG/chosen_particles_urqmd_v3.3+.dat"))
     assert chosen.shape == (305, 1) and np.array_equal(chosen[:, 0], inputs.load_fixture()["chosen_urqmd"])
-    surf, _ = api.surface_read_vh(os.path.join(REFERENCE, "input/surface.dat"))
+    surf, _ = api.surface_read_vh(os.path.join(reference, "input/surface.dat"))
     assert len(surf["tau"]) == 1 and surf["P"][0] == 0.270 * 0.197327053
-    assert api.param_get(os.path.join(REFERENCE, "iS3D_parameters.dat"), "df_mode") == 4.0
+    assert api.param_get(os.path.join(reference, "iS3D_parameters.dat"), "df_mode") == 4.0
 
 
 def test_pdg_box_reader(tmp_path):
@@ -406,12 +404,11 @@ def test_pdg_box_reader(tmp_path):
     assert e.value.code == api.IS3D_EIO and "1000010020" in str(e.value)
 
 
-@pytest.mark.reference
-def test_smash_particle_lists_of_the_reference():
+def test_smash_particle_lists_of_the_reference(reference):
     """hrg_eos = 2 (the reference's shipped default) reads PDG/pdg_smash.dat with the conventional reader: against an independent token parse here;
     hrg_eos = 3 reads PDG/pdg_box.dat with the line reader: against refformat.box_entries on an independent line parse.  Both chosen lists are
     subsets of what is read (the reference requires it, iS3D_parameters.dat:18)."""
-    tok = open(os.path.join(REFERENCE, "PDG/pdg_smash.dat"), encoding="utf-8").read().split()
+    tok = open(os.path.join(reference, "PDG/pdg_smash.dat"), encoding="utf-8").read().split()
     want, i = [], 0
     while i < len(tok):
         mc, mass, g, b, nd = int(tok[i]), float(tok[i + 2]), int(tok[i + 4]), int(tok[i + 5]), int(tok[i + 11])
@@ -419,28 +416,28 @@ def test_smash_particle_lists_of_the_reference():
         if b > 0:
             want.append((-mc, mass, g, -b))
         i += 12 + 8 * nd
-    got = api.pdg_read(os.path.join(REFERENCE, "PDG/pdg_smash.dat"))
+    got = api.pdg_read(os.path.join(reference, "PDG/pdg_smash.dat"))
     assert len(got["mc_id"]) == len(want) == 493
     assert [(int(a), float(m), int(g), int(b)) for a, m, g, b in zip(got["mc_id"], got["mass"], got["gspin"], got["baryon"])] == want
-    chosen = api.table_read(os.path.join(REFERENCE, "PDG/chosen_particles_smash.dat"))[:, 0]
+    chosen = api.table_read(os.path.join(reference, "PDG/chosen_particles_smash.dat"))[:, 0]
     assert len(chosen) == 444 and set(chosen.astype(np.int64)) <= set(got["mc_id"])
     rows = []
-    for line in open(os.path.join(REFERENCE, "PDG/pdg_box.dat"), encoding="utf-8"):
+    for line in open(os.path.join(reference, "PDG/pdg_box.dat"), encoding="utf-8"):
         if not line.strip() or line.startswith("#"):
             continue
         f = line.split("#")[0].split()
         rows.append((f[0], float(f[1]), [int(x) for x in f[4:8]]))
-    box = api.pdg_read(os.path.join(REFERENCE, "PDG/pdg_box.dat"), box=True)
+    box = api.pdg_read(os.path.join(reference, "PDG/pdg_box.dat"), box=True)
     wantb = refformat.box_entries(rows)
     assert len(box["mc_id"]) == len(wantb) == 400
     assert [(int(a), float(m), float(g), float(b), float(s)) for a, m, g, b, s in
             zip(box["mc_id"], box["mass"], box["gspin"], box["baryon"], box["sign"])] == wantb
-    chosen = api.table_read(os.path.join(REFERENCE, "PDG/chosen_particles_box.dat"))[:, 0]
+    chosen = api.table_read(os.path.join(reference, "PDG/chosen_particles_box.dat"))[:, 0]
     assert len(chosen) == 399 and set(chosen.astype(np.int64)) <= set(box["mc_id"])
     # ... and their coefficient tables (deltafReader.h:27-29): the mu_B = 0 rows against numpy's own parse
     for d in ("smash", "smash_box"):
         for name in ("c0", "c2", "F", "betabulk", "betapi"):
-            path = os.path.join(REFERENCE, "deltaf_coefficients/vh", d, name + ".dat")
+            path = os.path.join(reference, "deltaf_coefficients/vh", d, name + ".dat")
             T, v = api.df_table_read(path)
             raw = np.loadtxt(path, skiprows=3)
             assert len(T) == 101 and np.array_equal(T, raw[:101, 0]) and np.array_equal(v, raw[:101, 2]) and np.all(raw[:101, 1] == 0.0)
@@ -515,9 +512,8 @@ def test_surface_reader_mode2(tmp_path):
     assert e.value.code == api.IS3D_EIO
 
 
-@pytest.mark.reference
-def test_vah_tables_of_the_reference_parse_to_the_fixture():
-    got = api.vah_df_read(os.path.join(REFERENCE, "deltaf_coefficients/vah"))
+def test_vah_tables_of_the_reference_parse_to_the_fixture(reference):
+    got = api.vah_df_read(os.path.join(reference, "deltaf_coefficients/vah"))
     tab = inputs.vah_df_tables()
     for k in ("L", "aL", "c0", "c1", "c2", "c3", "c4"):
         assert np.array_equal(got[k], tab[k]), k

@@ -25,8 +25,7 @@ from is3d_amd import api, inputs
 from oracle import oracle
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REFERENCE = "/root/reference"
-GEN = os.path.join(REFERENCE, "generate_delta_f_coefficients/urqmd/df_vh_dimensionless")
+GEN = "generate_delta_f_coefficients/urqmd/df_vh_dimensionless"
 HBARC = 0.197327053
 
 
@@ -127,27 +126,26 @@ def test_generator_integrals_are_the_yield_restatements_densities():
     assert abs(out0[8] * T ** 3 / i0[19] - 1) < 1e-12
 
 
-@pytest.mark.reference
-def test_readers_and_oracle_on_the_references_own_files():
-    """Container only: the same comparison with every input read through the LIBRARY's readers from the reference's files -- is3d_pdg_read on
+def test_readers_and_oracle_on_the_references_own_files(reference):
+    """The same comparison with every input read through the LIBRARY's readers from the reference's files -- is3d_pdg_read on
     PDG/pdg-urqmd_v3.3+.dat and on the generator's own pdg.dat (one more blank line: the same 327 entries), is3d_gla_read on the generator's
     64-point file (21 alphas), is3d_df_table_read_full on the ten shipped tables -- on every 4th temperature x every 5th chemical potential;
     and the fixtures are what those readers return."""
-    pdg = api.pdg_read(os.path.join(REFERENCE, "PDG/pdg-urqmd_v3.3+.dat"))
-    gen = api.pdg_read(os.path.join(GEN, "pdg.dat"))
+    pdg = api.pdg_read(os.path.join(reference, "PDG/pdg-urqmd_v3.3+.dat"))
+    gen = api.pdg_read(os.path.join(reference, GEN, "pdg.dat"))
     assert len(pdg["mass"]) == 327
     for k in pdg:
         assert np.array_equal(pdg[k], gen[k]), k
     pf = pdg_fixture()
     for k in pf:
         assert np.array_equal(pf[k], pdg[k]), k
-    root, weight = api.gla_read(os.path.join(GEN, "gauss_laguerre/gla_roots_weights_64_points.txt"))
+    root, weight = api.gla_read(os.path.join(reference, GEN, "gauss_laguerre/gla_roots_weights_64_points.txt"))
     assert root.shape == (21, 64)
     fx = fixture()
     assert np.array_equal(root[:5], fx["root"]) and np.array_equal(weight[:5], fx["weight"])
     tabs = {}
     for n in oracle.DF_NAMES_2D:
-        T, B, v = api.df_table_read_full(os.path.join(REFERENCE, "deltaf_coefficients/vh/urqmd", n + ".dat"))
+        T, B, v = api.df_table_read_full(os.path.join(reference, "deltaf_coefficients/vh/urqmd", n + ".dat"))
         assert v.shape == (81, 101) and np.array_equal(T, fx["T"]) and np.array_equal(B, fx["muB"])
         assert np.array_equal(v[np.ix_(fx["iB"], fx["iT"])], fx["shipped"][oracle.DF_NAMES_2D.index(n)])
         tabs[n] = v
@@ -161,21 +159,20 @@ def test_readers_and_oracle_on_the_references_own_files():
     assert not bad, bad[:5]
 
 
-@pytest.mark.reference
 @pytest.mark.parametrize("which", ["smash", "smash_box"])
-def test_smash_tables_of_the_reference_pin_the_other_two_particle_list_readers(which):
+def test_smash_tables_of_the_reference_pin_the_other_two_particle_list_readers(which, reference):
     """hrg_eos = 2 (the reference's shipped default: PDG/pdg_smash.dat through read_resonances_conventional, 493 entries) and hrg_eos = 3
     (PDG/pdg_box.dat through read_resonances_smash_box / read_mcid, 400 entries): deltaf_coefficients/vh/{smash, smash_box}/*.dat are the same
     generator's output for those lists (generate_delta_f_coefficients/{smash, smash_box}/df_vh_dimensionless/src: deltaf_table.cpp differs from the
     urqmd one in file names only).  The lists as is3d_pdg_read / is3d_pdg_read_box return them reproduce every sampled printed value."""
     if which == "smash":
-        pdg = api.pdg_read(os.path.join(REFERENCE, "PDG/pdg_smash.dat"))
+        pdg = api.pdg_read(os.path.join(reference, "PDG/pdg_smash.dat"))
         assert len(pdg["mass"]) == 493
     else:
-        pdg = api.pdg_read(os.path.join(REFERENCE, "PDG/pdg_box.dat"), box=True)
+        pdg = api.pdg_read(os.path.join(reference, "PDG/pdg_box.dat"), box=True)
         assert len(pdg["mass"]) == 400
-    root, weight = api.gla_read(os.path.join(REFERENCE, "generate_delta_f_coefficients", which, "df_vh_dimensionless/gauss_laguerre/gla_roots_weights_64_points.txt"))
-    tabs = {n: api.df_table_read_full(os.path.join(REFERENCE, "deltaf_coefficients/vh", which, n + ".dat")) for n in oracle.DF_NAMES_2D}
+    root, weight = api.gla_read(os.path.join(reference, "generate_delta_f_coefficients", which, "df_vh_dimensionless/gauss_laguerre/gla_roots_weights_64_points.txt"))
+    tabs = {n: api.df_table_read_full(os.path.join(reference, "deltaf_coefficients/vh", which, n + ".dat")) for n in oracle.DF_NAMES_2D}
     T, B, _ = tabs["c0"]
     bad = []
     for iB in range(0, len(B), 8):
@@ -188,10 +185,13 @@ def test_smash_tables_of_the_reference_pin_the_other_two_particle_list_readers(w
 
 
 if __name__ == "__main__" and "--all" in sys.argv:
-    # every row of every shipped table (container only, ~35 s)
-    pdg = api.pdg_read(os.path.join(REFERENCE, "PDG/pdg-urqmd_v3.3+.dat"))
-    root, weight = api.gla_read(os.path.join(GEN, "gauss_laguerre/gla_roots_weights_64_points.txt"))
-    tabs = {n: api.df_table_read_full(os.path.join(REFERENCE, "deltaf_coefficients/vh/urqmd", n + ".dat")) for n in oracle.DF_NAMES_2D}
+    # every row of every shipped table (~35 s)
+    import tempfile
+    from conftest import unpack_reference_data
+    reference = unpack_reference_data(tempfile.mkdtemp())
+    pdg = api.pdg_read(os.path.join(reference, "PDG/pdg-urqmd_v3.3+.dat"))
+    root, weight = api.gla_read(os.path.join(reference, GEN, "gauss_laguerre/gla_roots_weights_64_points.txt"))
+    tabs = {n: api.df_table_read_full(os.path.join(reference, "deltaf_coefficients/vh/urqmd", n + ".dat")) for n in oracle.DF_NAMES_2D}
     T, B, _ = tabs["c0"]
     n_bad, worst = 0, 0.0
     for iB in range(81):

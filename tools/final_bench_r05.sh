@@ -2,7 +2,7 @@
 # round 5, closing run: the bench lines of every workload with the final build -> gpurun_out/r05/final_*.json (copied to profiles/r05_bench*.json)
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r05; mkdir -p $O; cd $R
-run() { local n=$1; shift; python bench.py "$@" > $O/final_$n.json 2> $O/final_$n.err || { echo "$n failed"; tail -5 $O/final_$n.err; exit 1; }; python - "$O/final_$n.json" <<'PY'
+run() { local n=$1; shift; python bench.py --full "$@" > $O/final_$n.json 2> $O/final_$n.err || { echo "$n failed"; tail -5 $O/final_$n.err; exit 1; }; python - "$O/final_$n.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 rv = d.get("roofline_valu") or {}

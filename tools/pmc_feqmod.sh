@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/pmc_feqmod
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --df-mode 4 --steps 1 --warmup 0 --no-cpu-baseline --no-clock-probe --no-cull-check"
+B="python3 $R/bench.py --full --df-mode 4 --steps 1 --warmup 0 --no-cpu-baseline --no-clock-probe --no-cull-check"
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $OUT/sq -- $B > $OUT/sq.json 2> $OUT/sq.err || exit 1
 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INST_CYCLES_VMEM SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d $OUT/misc -- $B > $OUT/misc.json 2> $OUT/misc.err || exit 2
 python3 - <<PY

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/prof_r04_shards
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for n in 1000000 500000 250000 125000; do
-  B="python3 $R/bench.py --cells $n --steps 1 --warmup 0 --no-cpu-baseline --no-clock-probe --no-cull-check"
+  B="python3 $R/bench.py --full --cells $n --steps 1 --warmup 0 --no-cpu-baseline --no-clock-probe --no-cull-check"
   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch_$n -- $B > $OUT/fetch_$n.json 2> $OUT/fetch_$n.err || exit 2
   rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write_$n -- $B > $OUT/write_$n.json 2> $OUT/write_$n.err || exit 3
   echo "shard $n done"
