@@ -7,6 +7,7 @@
 //   - lives in namespace is3d_amd;
 //   - errors throw std::runtime_error(is3d_last_error()) instead of printf + exit(-1);
 //   - operation = 1 additionally leaves the spectrum in dN_pTdpTdphidy_ (the reference only writes files);
+//   - operation = 0 writes results/spacetime_distribution/ as the reference does and leaves both members empty; it needs x and y;
 //   - pinn is accepted and ignored, as in the reference (iS3D.cpp:100-134 never copies it; the kernels reconstruct it).
 #pragma once
 #include <stdexcept>

@@ -562,6 +562,62 @@ int is3d_write_sampler_tests(const char *results_dir, const is3d_sampler_test_bi
                              const int64_t *mc_id, int64_t n_particles, const is3d_particle *particles, double mean_yield);
 
 /* ---------------------------------------------------------------------------------------------
+ * Operation 0: smooth Cooper-Frye spacetime distributions, df_mode 1 / 2 -- the drop-in for calculate_dN_dX
+ * (emissionfunction_smooth_kernels.cpp:1000-1446, dispatched at emissionfunction.cpp:1510-1516).  Per cell
+ *   dN_dy_cell = sum_pT sum_phi sum_(y | eta) w_pT w_phi prefactor g p.dsigma f        (:1370; the 3+1D y sum has NO weights)
+ * with the spectra path's integrand, cell skipping and coefficients (the same cf_prep records); then per species
+ *   dN_dy = the sum over all cells, dN_taudtaudy[itau], dN_twopirdrdy[ir], dN_twopitaurdtaudrdy[itau][ir] = the sums over the cells of a bin,
+ *   itau = floor((tau - tau_min) / dtau), ir = floor((r - r_min) / dr), r = sqrt(x^2 + y^2), dtau = (tau_max - tau_min) / tau_bins (:1382-1398);
+ *   a cell outside [0, bins) of one index counts toward dN_dy and the other histogram only.
+ * Every sum is left to right over the cells in ascending index, each term pg_s * D_class(s)(cell) with pg_s = prefactor * g_s (one rounding
+ * each): bitwise reproducible, and a bin equals the running sum of dN_dy_cell over its cells.  The values are RAW sums (not divided by bin
+ * widths; is3d_write_spacetime normalises).  dN_dydeta: 2+1D, per eta node k of the eta table, sum w_pT w_phi prefactor g p.dsigma f / w_k (:1365);
+ * 3+1D one point (n_eta_eff = 1): the species' total (the reference's etaValues[0] is eta_fo of the LAST cell, :1155).  pT_w, phi_w: the
+ * weights of pT_tab, phi_tab (column 2), HOST memory.  df_mode 3 / 4 (calculate_dN_dX_feqmod) is not built: IS3D_EINVAL.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct {
+    double tau_min, tau_max, r_min, r_max;  /* parameters tau_min ... r_bins (emissionfunction.cpp:216-222) */
+    int32_t tau_bins, r_bins;
+} is3d_spacetime_bins;
+
+typedef struct {                        /* S = number of species; device pointers for the plan entry, host pointers for the one-shot */
+    double *dN_dy;                      /* [S]                         */
+    double *dN_taudtaudy;               /* [S][tau_bins]               */
+    double *dN_twopirdrdy;              /* [S][r_bins]                 */
+    double *dN_twopitaurdtaudrdy;       /* [S][tau_bins][r_bins]       */
+    double *dN_dydeta;                  /* [S][n_eta_eff], n_eta_eff = n_eta (2+1D) | 1 (3+1D) */
+    double *dN_dy_cell;                 /* [S][n_cells], may be NULL   */
+} is3d_spacetime_out;
+
+typedef struct {
+    int32_t code;
+    int32_t n_classes;
+    int64_t n_cells_skipped;            /* u.dsigma <= 0 (:1170): contribute 0 */
+    int64_t n_tau_outside, n_r_outside; /* non-skipped cells whose tau (r) bin index is outside [0, bins) */
+    int64_t n_tau_negative, n_r_negative; /* ... of them below 0 (the reference prints an error line per such cell) */
+    int64_t bad_cell;                   /* first cell with T outside the table, or -1 */
+    int32_t n_passes, reserved;
+    double ms_prep, ms_cells, ms_bins;  /* device time of the record writer, the per-cell kernel, the binning (keys, sort, sums) */
+    double ms_h2d, ms_d2h;              /* one-shot entry only */
+} is3d_spacetime_stats;
+
+/* one-shot host entry; the argument checks (df_mode 3 / 4, NULL x or y, bins < 1, tau_max <= tau_min, r_max <= r_min) precede any device use */
+int is3d_spacetime_distributions(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species, const is3d_grid *grid,
+                                 const double *pT_w, const double *phi_w, const is3d_df_tables *df, const is3d_options *opts,
+                                 const is3d_spacetime_bins *bins, is3d_spacetime_out *out, is3d_spacetime_stats *stats);
+/* the same on an existing plan (species classes, grids, splines shared with is3d_plan_execute): cells, x, y and out are DEVICE pointers;
+ * the plan's workspace_bytes cap bounds the passes.  stats != NULL synchronises the stream and reports IS3D_EDOMAIN as is3d_plan_execute does */
+int is3d_plan_execute_spacetime(is3d_plan *plan, const is3d_cells *cells, const double *x, const double *y, const double *pT_w,
+                                const double *phi_w, const is3d_spacetime_bins *bins, const is3d_spacetime_out *out, void *hip_stream,
+                                is3d_spacetime_stats *stats);
+/* the four files per species under <results_dir> (emissionfunction_smooth_kernels.cpp:1100-1127, :1403-1434), "%.6e" as the reference's
+ * setprecision(6) << scientific: dN_taudtaudy_<id>.dat (tau_mid, v / (tau_mid dtau)), dN_twopirdrdy_<id>.dat (r_mid, v / (2 pi r_mid dr)),
+ * dN_twopitaurdtaudrdy_<id>.dat (tau_mid, r_mid, v / (2 pi tau_mid r_mid dtau dr), r outer, tau inner), dN_dydeta_<id>_<n_eta_eff>pt.dat
+ * (eta_values[k], v).  IS3D_EIO if the directory is missing. */
+int is3d_write_spacetime(const char *results_dir, const is3d_spacetime_bins *bins, int32_t n_species, const int64_t *mc_id, int32_t n_eta_eff,
+                         const double *eta_values, const is3d_spacetime_out *out);
+
+/* ---------------------------------------------------------------------------------------------
  * Driver: IS3D::run_particlization (src/cpp/iS3D.cpp:74-192; class IS3D, src/cpp/iS3D.h:19-96).  Reads iS3D_parameters.dat,
  * PDG/, tables/, deltaf_coefficients/ from the current directory and writes results/ exactly as the command line tool does
  * (which is this call with surface = NULL).  surface != NULL is the embedding path (read_fo_surf_from_memory +

@@ -108,7 +108,42 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_multi_plan_shards", "is3d_multi_plan_output_size", "is3d_multi_plan_destroy",
            "is3d_vah_df_read", "is3d_vah_coefficients", "is3d_smooth_spectra_vah_df", "is3d_vah_plan_create", "is3d_vah_plan_output_size",
            "is3d_vah_plan_workspace_bytes", "is3d_vah_plan_execute", "is3d_vah_plan_set_timing", "is3d_vah_plan_timings",
-           "is3d_vah_plan_tile_shape", "is3d_vah_plan_destroy", "is3d_surface_read_vah", "is3d_vah_plan_main_kernel_name", "is3d_math_probe", "is3d_resource_counters"]
+           "is3d_vah_plan_tile_shape", "is3d_vah_plan_destroy", "is3d_surface_read_vah", "is3d_vah_plan_main_kernel_name", "is3d_math_probe", "is3d_resource_counters",
+           "is3d_spacetime_distributions", "is3d_plan_execute_spacetime", "is3d_write_spacetime"]
+
+class SpacetimeBins(C.Structure):
+    _fields_ = [("tau_min", C.c_double), ("tau_max", C.c_double), ("r_min", C.c_double), ("r_max", C.c_double),
+                ("tau_bins", C.c_int32), ("r_bins", C.c_int32)]
+
+
+class SpacetimeOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ["dN_dy", "dN_taudtaudy", "dN_twopirdrdy", "dN_twopitaurdtaudrdy", "dN_dydeta", "dN_dy_cell"]]
+
+
+class SpacetimeStats(C.Structure):
+    _fields_ = [("code", C.c_int32), ("n_classes", C.c_int32), ("n_cells_skipped", C.c_int64), ("n_tau_outside", C.c_int64),
+                ("n_r_outside", C.c_int64), ("n_tau_negative", C.c_int64), ("n_r_negative", C.c_int64), ("bad_cell", C.c_int64),
+                ("n_passes", C.c_int32), ("reserved", C.c_int32), ("ms_prep", C.c_double), ("ms_cells", C.c_double), ("ms_bins", C.c_double),
+                ("ms_h2d", C.c_double), ("ms_d2h", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
+SPACETIME_OUTPUTS = ["dN_dy", "dN_taudtaudy", "dN_twopirdrdy", "dN_twopitaurdtaudrdy", "dN_dydeta", "dN_dy_cell"]
+
+
+def _spacetime_bins(bins):
+    return SpacetimeBins(float(bins["tau_min"]), float(bins["tau_max"]), float(bins["r_min"]), float(bins["r_max"]), int(bins["tau_bins"]),
+                         int(bins["r_bins"]))
+
+
+def spacetime_shapes(n_species, n_cells, bins, dimension, n_eta):
+    """Shapes of the operation-0 outputs (include/is3d_amd.h, is3d_spacetime_out)."""
+    tb, rb = int(bins["tau_bins"]), int(bins["r_bins"])
+    return dict(dN_dy=(n_species,), dN_taudtaudy=(n_species, tb), dN_twopirdrdy=(n_species, rb), dN_twopitaurdtaudrdy=(n_species, tb, rb),
+                dN_dydeta=(n_species, 1 if dimension == 3 else n_eta), dN_dy_cell=(n_species, n_cells))
+
 
 REDUCE_ORDERED, REDUCE_RCCL = 0, 1
 IS3D_EPEER = -6
@@ -209,6 +244,12 @@ def load():
     L.is3d_multi_plan_output_size.restype = C.c_int64
     L.is3d_multi_plan_destroy.argtypes = [C.c_void_p]
     L.is3d_multi_plan_destroy.restype = None
+    L.is3d_spacetime_distributions.argtypes = [C.POINTER(Cells), _dp, _dp, C.POINTER(Species), C.POINTER(Grid), _dp, _dp, C.POINTER(DfTables),
+                                               C.POINTER(Options), C.POINTER(SpacetimeBins), C.POINTER(SpacetimeOut), C.POINTER(SpacetimeStats)]
+    L.is3d_plan_execute_spacetime.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_void_p, C.c_void_p, _dp, _dp, C.POINTER(SpacetimeBins),
+                                              C.POINTER(SpacetimeOut), C.c_void_p, C.POINTER(SpacetimeStats)]
+    L.is3d_write_spacetime.argtypes = [C.c_char_p, C.POINTER(SpacetimeBins), C.c_int32, C.POINTER(C.c_int64), C.c_int32, _dp,
+                                       C.POINTER(SpacetimeOut)]
     _LIB = L
     return L
 
@@ -487,6 +528,54 @@ def smooth_spectra(cells, species, grid, df, opts=None, out=None, fq=None):
     return out, st.as_dict()
 
 
+def spacetime_distributions(cells, species, grid, df, bins, opts=None, per_cell=False, x=None, y=None):
+    """Operation 0 (is3d_spacetime_distributions, the drop-in for calculate_dN_dX): host arrays in, a dict of numpy arrays out -- the RAW bin
+    sums dN_dy [S], dN_taudtaudy [S][tau_bins], dN_twopirdrdy [S][r_bins], dN_twopitaurdtaudrdy [S][tau_bins][r_bins], dN_dydeta
+    [S][n_eta | 1], with per_cell also dN_dy_cell [S][n_cells] -- and "stats".  grid needs pT_w and phi_w; x, y default to cells["x"], cells["y"];
+    bins: dict tau_min, tau_max, tau_bins, r_min, r_max, r_bins."""
+    L = load()
+    sps, gs, ds, os_, _, keep = _pack_common(species, grid, df, opts)
+    n = len(cells["tau"])
+    cs = Cells()
+    cs.n_cells = n
+    held = []
+    for f in CELL_FIELDS:
+        a = cells.get(f)
+        if a is not None:
+            a = _f64(a)
+            assert a.shape == (n,), f
+            held.append(a)
+            setattr(cs, f, a.ctypes.data)
+    x = cells.get("x") if x is None else x
+    y = cells.get("y") if y is None else y
+    xa = None if x is None else _f64(x)
+    ya = None if y is None else _f64(y)
+    pw, fw = _f64(grid["pT_w"]), _f64(grid["phi_w"])
+    dim = os_.dimension
+    shapes = spacetime_shapes(len(keep["sp"]["mass"]), n, bins, dim, len(keep["g"]["eta"]))
+    res = {k: np.zeros(v) for k, v in shapes.items() if k != "dN_dy_cell" or per_cell}
+    so = SpacetimeOut(*[res[k].ctypes.data if k in res else None for k in SPACETIME_OUTPUTS])
+    b = _spacetime_bins(bins)
+    st = SpacetimeStats()
+    rc = L.is3d_spacetime_distributions(C.byref(cs), _p(xa) if xa is not None else None, _p(ya) if ya is not None else None, C.byref(sps),
+                                        C.byref(gs), _p(pw), _p(fw), C.byref(ds), C.byref(os_), C.byref(b), C.byref(so), C.byref(st))
+    _check(rc)
+    res["stats"] = st.as_dict()
+    return res
+
+
+def write_spacetime(results_dir, bins, mc_id, eta_values, res):
+    """is3d_write_spacetime: the four files per species of calculate_dN_dX from the raw sums of spacetime_distributions."""
+    L = load()
+    mc = np.ascontiguousarray(mc_id, dtype=np.int64)
+    ev = _f64(np.atleast_1d(eta_values))
+    arrs = {k: _f64(res[k]) for k in SPACETIME_OUTPUTS[1:5]}
+    so = SpacetimeOut(*[arrs[k].ctypes.data if k in arrs else None for k in SPACETIME_OUTPUTS])
+    b = _spacetime_bins(bins)
+    _check(L.is3d_write_spacetime(results_dir.encode(), C.byref(b), len(mc), mc.ctypes.data_as(C.POINTER(C.c_int64)), len(ev), _p(ev),
+                                  C.byref(so)))
+
+
 def shard_bounds(n_cells, rank, n_ranks):
     """is3d_shard_bounds: the contiguous cell shard [lo, hi) of `rank` (what is3d_smooth_spectra_multi uses)."""
     lo, hi = C.c_int64(), C.c_int64()
@@ -728,6 +817,24 @@ class Plan:
         pw, fw = _f64(pT_w), _f64(phi_w)
         _check(load().is3d_plan_observables(self._h, C.c_void_p(int(dN_ptr)), _p(pw), _p(fw), C.c_void_p(int(dndy_ptr or 0)),
                                             C.c_void_p(int(spec2pi_ptr or 0)), C.c_void_p(int(vn_ptr or 0)), C.c_void_p(int(stream or 0))))
+
+    def execute_spacetime(self, n_cells, cell_ptrs, x_ptr, y_ptr, pT_w, phi_w, bins, out_ptrs, stream=0, want_stats=True):
+        """is3d_plan_execute_spacetime (operation 0): cell_ptrs, x_ptr, y_ptr and out_ptrs (dict name -> device pointer, SPACETIME_OUTPUTS;
+        dN_dy_cell optional) are device pointers, pT_w / phi_w host weight arrays."""
+        cs = Cells()
+        cs.n_cells = int(n_cells)
+        for f in CELL_FIELDS:
+            p = cell_ptrs.get(f)
+            if p:
+                setattr(cs, f, int(p))
+        pw, fw = _f64(pT_w), _f64(phi_w)
+        so = SpacetimeOut(*[int(out_ptrs[k]) if out_ptrs.get(k) else None for k in SPACETIME_OUTPUTS])
+        b = _spacetime_bins(bins)
+        st = SpacetimeStats()
+        rc = load().is3d_plan_execute_spacetime(self._h, C.byref(cs), C.c_void_p(int(x_ptr or 0)), C.c_void_p(int(y_ptr or 0)), _p(pw), _p(fw),
+                                                C.byref(b), C.byref(so), C.c_void_p(int(stream or 0)), C.byref(st) if want_stats else None)
+        _check(rc)
+        return st.as_dict() if want_stats else None
 
     def check(self, stream=0):
         """is3d_plan_check: raises Is3dError(IS3D_EDOMAIN) if an execute since the last check (status-less ones included) met a

@@ -19,6 +19,7 @@
 #include "../../include/is3d_amd.h"
 #include "cf_feqmod.h"
 #include "cf_launch.h"
+#include "cf_spacetime.h"
 #include "errors.h"
 #include "jonah.h"
 #include "spline.h"
@@ -103,6 +104,19 @@ struct is3d_plan {
     double bp_max = 0.0, detA_min = 0.0, mass_pion0 = 0.0;
     DevBuf<double> d_gl, d_jonah, d_cls_mass, d_cls_sign, d_cls_baryon, d_lane_mass, d_RN, d_CR, d_FB;
     DevBuf<int32_t> d_lane_cls, d_flag, d_list, d_count;
+
+    // operation 0 (is3d_plan_execute_spacetime): host copies of the species classes, the lane tables of cf_st_cells and its workspaces,
+    // made on the first such execute
+    std::vector<int32_t> sp_cls;
+    std::vector<double> cls_mass, cls_sign, cls_bar, pT_grid, sp_deg;
+    std::vector<double> st_hwpT, st_hwphi;   // the weights now on the device (d_st_wpT, d_st_wphi)
+    bool st_ready = false;
+    int st_npTp = 0, st_nlw = 0;
+    int64_t st_pass = 0, st_cap = 0;
+    DevBuf<double> d_st_mT, d_st_pT, d_st_sign, d_st_b, d_st_wpT, d_st_wphi, d_st_pg, d_st_D, d_st_slab, d_st_eta;
+    DevBuf<int32_t> d_st_cls, d_st_keys, d_st_cnt, d_st_tot, d_st_list;
+    DevBuf<int64_t> d_st_start;
+    DevBuf<unsigned long long> d_st_counters;
 
     bool timing = false;
     std::vector<hipEvent_t> ev_list;  // [pass][0..3]: start, after prep, after main; last: after finalize
@@ -252,6 +266,10 @@ static int plan_create_impl(is3d_plan **out, const is3d_species *sp, const is3d_
         cls[s] = found;
     }
     P->ncls = (int)cmass.size();
+    P->sp_cls.assign(cls.begin(), cls.end());
+    P->cls_mass = cmass; P->cls_sign = csign; P->cls_bar = cbar;
+    P->pT_grid.assign(g->pT, g->pT + g->n_pT);
+    P->sp_deg.assign(sp->degeneracy, sp->degeneracy + sp->n);
     P->Lbins = P->ncls * P->npT;
     // unit-strided lanes (variant 7, 2+1D): S lane slots per bin so that the slots fill whole waves (96 bins: 128 slots = 25 %
     // idle lanes with S = 1, 384 = 6 full waves with S = 4); S must divide the units per cell and the units per LDS batch (4)
@@ -1015,4 +1033,348 @@ extern "C" int is3d_smooth_spectra_feqmod(const is3d_cells *cells, const is3d_sp
 {
     if (!fq) return fail(IS3D_EINVAL, "null feqmod tables");
     return smooth_spectra_impl(cells, species, grid, df, fq, opts, dN_out, status);
+}
+
+// ---------------------------------------------------------------------------------------------
+// operation 0: smooth spacetime distributions (calculate_dN_dX, emissionfunction_smooth_kernels.cpp:1000-1446), cf_spacetime.hip
+// ---------------------------------------------------------------------------------------------
+static int st_check(const is3d_spacetime_bins *b, const double *x, const double *y, int df_mode)
+{
+    if (df_mode == 3 || df_mode == 4)
+        return fail(IS3D_EINVAL, "operation 0 with df_mode %d needs calculate_dN_dX_feqmod, which is not built yet (df_mode 1 or 2)", df_mode);
+    if (!x || !y) return fail(IS3D_EINVAL, "operation 0 needs the cells' x and y positions (NULL given)");
+    if (!b) return fail(IS3D_EINVAL, "null spacetime bins");
+    if (b->tau_bins < 1 || b->r_bins < 1) return fail(IS3D_EINVAL, "tau_bins and r_bins must be >= 1 (got %d, %d)", b->tau_bins, b->r_bins);
+    if (!(b->tau_max > b->tau_min) || !(b->r_max > b->r_min))
+        return fail(IS3D_EINVAL, "the bin ranges need tau_max > tau_min and r_max > r_min (got [%g, %g], [%g, %g])", b->tau_min, b->tau_max, b->r_min,
+                    b->r_max);
+    if ((int64_t)b->tau_bins * b->r_bins > ((int64_t)1 << 28)) return fail(IS3D_EINVAL, "tau_bins x r_bins too large");
+    return IS3D_OK;
+}
+
+// the spacetime lane tables and the per-pass workspace of a plan, made once
+static int st_setup(is3d_plan *P)
+{
+    if (P->st_ready) return IS3D_OK;
+    int npTp = 1;
+    while (npTp < P->npT) npTp <<= 1;
+    P->st_npTp = npTp;
+    P->st_nlw = (P->ncls * npTp + 63) / 64;
+    const int nl = P->st_nlw * 64;
+    std::vector<double> mT(nl, 1.0), pT(nl, 0.0), sg(nl, 1.0), b(nl, 0.0);
+    for (int l = 0; l < nl; l++) {
+        const int c = l / npTp, i = l % npTp;
+        if (c >= P->ncls || i >= P->npT) continue;   // padded lanes: finite operands, w_pT = 0
+        const double m = P->cls_mass[c], p = P->pT_grid[i];
+        mT[l] = std::sqrt(m * m + p * p);
+        pT[l] = p;
+        sg[l] = P->cls_sign[c];
+        b[l] = P->cls_bar[c];
+    }
+    HIP_TRY(P->d_st_mT.upload(mT));
+    HIP_TRY(P->d_st_pT.upload(pT));
+    HIP_TRY(P->d_st_sign.upload(sg));
+    HIP_TRY(P->d_st_b.upload(b));
+    HIP_TRY(P->d_st_wpT.alloc(nl));
+    HIP_TRY(P->d_st_wphi.alloc((size_t)P->jtiles * P->JT));
+    HIP_TRY(P->d_st_cls.upload(P->sp_cls));
+    std::vector<double> pg(P->npart);
+    for (int s = 0; s < P->npart; s++) pg[s] = P->prefactor * P->sp_deg[s];
+    HIP_TRY(P->d_st_pg.upload(pg));
+    // passes: the plan's record stream plus D (8 B per class and cell) within the same cap as the spectra path
+    const int64_t ws = is3d::default_stream_cap_bytes(P->opts.workspace_bytes);
+    const int64_t per_cell = (int64_t)P->bytes_per_cell + 8 * (int64_t)P->ncls;
+    P->st_pass = std::max<int64_t>(1, std::min<int64_t>(P->pass_cells, ws / per_cell));
+    hipError_t e = P->d_st_D.alloc((size_t)P->ncls * P->st_pass);
+    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(IS3D_ENOMEM, "out of device memory allocating the per-cell workspace D"); }
+    HIP_TRY(e);
+    if (!P->dim3) HIP_TRY(P->d_st_eta.alloc((size_t)P->ncls * P->K));
+    HIP_TRY(P->d_st_counters.alloc(4));
+    P->st_ready = true;
+    return IS3D_OK;
+}
+
+template <class T>
+static hipError_t st_grow(DevBuf<T> &buf, size_t n)
+{
+    if (buf.n >= n && buf.p) return hipSuccess;
+    return buf.alloc(std::max<size_t>(n, 1));
+}
+
+extern "C" int is3d_plan_execute_spacetime(is3d_plan *P, const is3d_cells *cells, const double *x, const double *y, const double *pT_w,
+                                           const double *phi_w, const is3d_spacetime_bins *bins, const is3d_spacetime_out *out, void *hip_stream,
+                                           is3d_spacetime_stats *stats)
+{
+    if (stats) { memset(stats, 0, sizeof *stats); stats->bad_cell = -1; }
+    if (!P || !cells || !out || !pT_w || !phi_w) return fail(IS3D_EINVAL, "null argument");
+    int rc = st_check(bins, x, y, P->opts.df_mode);
+    if (rc) return rc;
+    if (P->feqmod) return fail(IS3D_EINVAL, "operation 0 with df_mode %d needs calculate_dN_dX_feqmod, which is not built yet", P->opts.df_mode);
+    if (!is3d::spacetime_shape_supported(P->dim3, P->JT, P->KT))
+        return fail(IS3D_EINVAL, "operation 0 runs on the plan's unit records of the default tile shapes (this plan: kernel variant %d, %d x %d)",
+                    P->variant, P->JT, P->KT);
+    if (P->npT > 64) return fail(IS3D_EINVAL, "operation 0 takes pT grids of up to 64 values (got %d)", P->npT);
+    {
+        int npTp = 1;
+        while (npTp < P->npT) npTp <<= 1;
+        if (!P->dim3 && sizeof(double) * 4 * (64 / npTp) * (size_t)P->K > 64 * 1024)
+            return fail(IS3D_EINVAL, "operation 0 in 2+1D: %d pT values x %d eta nodes need more LDS than the per-cell kernel has", P->npT, P->K);
+    }
+    if (!out->dN_dy || !out->dN_taudtaudy || !out->dN_twopirdrdy || !out->dN_twopitaurdtaudrdy || !out->dN_dydeta)
+        return fail(IS3D_EINVAL, "a required output array is NULL");
+    const int64_t n = cells->n_cells;
+    if (n < 0 || n > P->max_cells) return fail(IS3D_EINVAL, "n_cells = %lld exceeds the plan's max_cells = %lld", (long long)n, (long long)P->max_cells);
+    if (n > 0x7fff0000LL) return fail(IS3D_EINVAL, "operation 0 takes up to 2^31 cells");
+    const is3d_options &o = P->opts;
+    if (n > 0) {
+        if (!cells->tau || !cells->dat || !cells->dax || !cells->day || !cells->dan || !cells->ux || !cells->uy || !cells->un ||
+            !cells->T || !cells->P || !cells->E || (P->dim3 && !cells->eta))
+            return fail(IS3D_EINVAL, "a required cell array is NULL");
+        if (o.include_shear_deltaf && (!cells->pixx || !cells->pixy || !cells->pixn || !cells->piyy || !cells->piyn))
+            return fail(IS3D_EINVAL, "include_shear_deltaf needs pixx, pixy, pixn, piyy, piyn");
+        if (o.include_bulk_deltaf && !cells->bulkPi) return fail(IS3D_EINVAL, "include_bulk_deltaf needs bulkPi");
+        if (P->baryondiff && (!cells->muB || !cells->nB || !cells->Vx || !cells->Vy || !cells->Vn))
+            return fail(IS3D_EINVAL, "include_baryon && include_baryondiff_deltaf need muB, nB, Vx, Vy, Vn");
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIP_TRY(hipSetDevice(P->device));
+    rc = st_setup(P);
+    if (rc) return rc;
+    const int S = P->npart, K = P->K;
+    const int64_t tb = bins->tau_bins, rbn = bins->r_bins, trb = tb * rbn;
+    const int n_eta_eff = P->dim3 ? 1 : K;
+
+    // momentum weights of the reduction (pT_tab, phi_tab column 2): uploaded when they differ from the plan's copy (the first execute, or new
+    // weights); an execute with the same weights and stats == NULL does not block the host
+    if (P->st_hwpT.size() != (size_t)P->npT || P->st_hwphi.size() != (size_t)P->J || !std::equal(P->st_hwpT.begin(), P->st_hwpT.end(), pT_w) ||
+        !std::equal(P->st_hwphi.begin(), P->st_hwphi.end(), phi_w)) {
+        std::vector<double> wl((size_t)P->st_nlw * 64, 0.0), wp((size_t)P->jtiles * P->JT, 0.0);
+        for (size_t l = 0; l < wl.size(); l++) {
+            const int c = (int)(l / P->st_npTp), i = (int)(l % P->st_npTp);
+            if (c < P->ncls && i < P->npT) wl[l] = pT_w[i];
+        }
+        for (int j = 0; j < P->J; j++) wp[j] = phi_w[j];
+        HIP_TRY(hipMemcpyAsync(P->d_st_wpT.p, wl.data(), wl.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(P->d_st_wphi.p, wp.data(), wp.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));   // the host vectors go out of scope
+        P->st_hwpT.assign(pT_w, pT_w + P->npT);
+        P->st_hwphi.assign(phi_w, phi_w + P->J);
+    }
+    std::vector<hipEvent_t> ev;
+    struct EvGuard { std::vector<hipEvent_t> &e; ~EvGuard() { for (auto x : e) (void)hipEventDestroy(x); } } evg{ev};
+    auto mark = [&](void) -> hipError_t {
+        if (!stats) return hipSuccess;
+        hipEvent_t e;
+        hipError_t r = hipEventCreate(&e);
+        if (r != hipSuccess) return r;
+        ev.push_back(e);
+        return hipEventRecord(e, st);
+    };
+    std::vector<int> stage;   // stage of the interval that ends at event i: 0 prep, 1 cells, 2 bins
+    unsigned long long init[8] = {~0ULL, 0ULL, 0ULL, 0ULL, 0ULL, 0ULL, 0ULL, ~0ULL};
+    HIP_TRY(hipMemcpyAsync(P->d_status.p, init, sizeof init, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(P->d_st_counters.p, 0, 4 * sizeof(unsigned long long), st));
+    HIP_TRY(mark());
+
+    // ---- bin stage, part 1: keys and the stable counting sort of every histogram (once per execute) ----
+    HIP_TRY(st_grow(P->d_st_keys, (size_t)3 * n));
+    HIP_TRY(st_grow(P->d_st_list, (size_t)3 * n));
+    HIP_TRY(st_grow(P->d_st_start, (size_t)(tb + 1) + (rbn + 1) + (trb + 1)));
+    const int64_t Bs[3] = {tb, rbn, trb};
+    int ntile[3];
+    size_t cnt_need = 1, tot_need = 1;
+    for (int h = 0; h < 3; h++) {
+        ntile[h] = is3d::spacetime_sort_tiles(n, Bs[h]);
+        cnt_need = std::max(cnt_need, (size_t)ntile[h] * Bs[h]);
+        tot_need = std::max(tot_need, (size_t)Bs[h]);
+    }
+    HIP_TRY(st_grow(P->d_st_cnt, cnt_need));
+    HIP_TRY(st_grow(P->d_st_tot, tot_need));
+    int32_t *keys[3] = {P->d_st_keys.p, P->d_st_keys.p + n, P->d_st_keys.p + 2 * n};
+    int32_t *lists[3] = {P->d_st_list.p, P->d_st_list.p + n, P->d_st_list.p + 2 * n};
+    int64_t *starts[3] = {P->d_st_start.p, P->d_st_start.p + tb + 1, P->d_st_start.p + tb + 1 + rbn + 1};
+    double *hout[3] = {out->dN_taudtaudy, out->dN_twopirdrdy, out->dN_twopitaurdtaudrdy};
+    const double dtau = (bins->tau_max - bins->tau_min) / (double)bins->tau_bins, dr = (bins->r_max - bins->r_min) / (double)bins->r_bins;
+    HIP_TRY(is3d::launch_spacetime_keys(cells->tau, cells->ux, cells->uy, cells->un, cells->dat, cells->dax, cells->day, cells->dan, x, y, n, bins->tau_min, dtau, bins->tau_bins, bins->r_min, dr, bins->r_bins, keys[0], keys[1],
+                                        keys[2], P->d_st_counters.p, st));
+    for (int h = 0; h < 3; h++)
+        HIP_TRY(is3d::launch_spacetime_sort(keys[h], n, Bs[h], ntile[h], P->d_st_cnt.p, P->d_st_tot.p, starts[h], lists[h], st));
+    HIP_TRY(mark()); stage.push_back(2);
+
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(out->dN_dy, 0, sizeof(double) * S, st));
+        for (int h = 0; h < 3; h++) HIP_TRY(hipMemsetAsync(hout[h], 0, sizeof(double) * S * Bs[h], st));
+        HIP_TRY(hipMemsetAsync(out->dN_dydeta, 0, sizeof(double) * S * n_eta_eff, st));
+    } else {
+        is3d::CellPtrs cp{};
+        cp.tau = cells->tau; cp.eta = cells->eta; cp.dat = cells->dat; cp.dax = cells->dax; cp.day = cells->day; cp.dan = cells->dan;
+        HIP_TRY(is3d::launch_pds_bound(cp, n, P->dim3, P->kmin, P->kmax, P->gw2d, P->mTmax, P->pTmax, P->d_status.p + 6, st));
+        const int64_t pc = P->st_pass;
+        const int G = (P->st_nlw + 3) / 4;
+        int nch = (int)std::min<int64_t>(pc, std::max<int64_t>(1, 16384 / G));
+        if (!P->dim3) nch = (int)std::max<int64_t>(1, std::min<int64_t>(nch, ((int64_t)256 << 20) / (8 * (int64_t)P->ncls * K)));
+        if (!P->dim3) HIP_TRY(st_grow(P->d_st_slab, (size_t)nch * P->ncls * K));
+        const int npasses = (int)((n + pc - 1) / pc);
+        for (int pass = 0; pass < npasses; pass++) {
+            const int64_t c0 = (int64_t)pass * pc;
+            const int32_t nc = (int32_t)std::min<int64_t>(pc, n - c0);
+            is3d::PrepParams pp{};
+            pp.cells = {cells->tau, cells->eta, cells->dat, cells->dax, cells->day, cells->dan, cells->ux, cells->uy, cells->un,
+                        cells->T, cells->P, cells->E, cells->pixx, cells->pixy, cells->pixn, cells->piyy, cells->piyn, cells->bulkPi,
+                        cells->muB, cells->nB, cells->Vx, cells->Vy, cells->Vn};
+            pp.cell0 = c0;
+            pp.n_cells = nc;
+            pp.J = P->J; pp.K = P->K;
+            pp.dim3 = P->dim3; pp.ce = P->ce;
+            pp.include_bulk = o.include_bulk_deltaf != 0;
+            pp.include_shear = o.include_shear_deltaf != 0;
+            pp.baryon = P->baryon; pp.baryondiff = P->baryondiff;
+            pp.bil = P->bil;
+            pp.cosphi = P->d_cosphi.p; pp.sinphi = P->d_sinphi.p;
+            pp.kgrid = P->d_kgrid.p; pp.kweight = P->d_kweight.p; pp.kch = P->d_kch.p; pp.ksh = P->d_ksh.p;
+            pp.spl = P->spl;
+            pp.tiled = 1;
+            pp.JT = P->JT; pp.R = P->KT; pp.jtiles = P->jtiles; pp.rblocks = P->rblocks;
+            pp.TS = P->d_TS.p;
+            pp.pds_bound = P->d_status.p + 6;
+            pp.mTmax = P->mTmax; pp.kmin = P->kmin; pp.kmax = P->kmax;
+            pp.status = P->d_status.p;
+            pp.TE = nullptr;   // the E2 tables of cf_main_tile3e are not needed here
+            pp.pTgrid = P->d_pTgrid.p; pp.npT = P->npT;
+            HIP_TRY(is3d::launch_prep(pp, st));
+            HIP_TRY(mark()); stage.push_back(0);
+
+            is3d::StCellArgs a{};
+            a.TS = P->d_TS.p; a.nc = nc; a.J = P->J; a.K = K; a.jtiles = P->jtiles; a.rblocks = P->rblocks;
+            a.ncls = P->ncls; a.npTp = P->st_npTp; a.nlw = P->st_nlw; a.G = G; a.nch = (int)std::min<int64_t>(nch, nc);
+            a.outflow = o.outflow != 0; a.regulate = o.regulate_deltaf != 0; a.zskip = o.zero_skip != 2;
+            a.lane_mT = P->d_st_mT.p; a.lane_pT = P->d_st_pT.p; a.lane_sign = P->d_st_sign.p; a.lane_b = P->d_st_b.p; a.lane_wpT = P->d_st_wpT.p;
+            a.wphi = P->d_st_wphi.p; a.pds_bound = P->d_status.p + 6;
+            a.D = P->d_st_D.p; a.eta_slab = P->dim3 ? nullptr : P->d_st_slab.p;
+            HIP_TRY(is3d::launch_spacetime_cells(a, P->ce, P->dim3, P->baryon, P->JT, P->KT, st));
+            if (!P->dim3) HIP_TRY(is3d::launch_spacetime_eta_reduce(P->d_st_slab.p, a.nch, (int64_t)P->ncls * K, pass == 0, P->d_st_eta.p, st));
+            HIP_TRY(mark()); stage.push_back(1);
+
+            // ---- bin stage, part 2: this pass's cells, in ascending order, onto the running sums ----
+            HIP_TRY(is3d::launch_spacetime_segsum(P->d_st_D.p, nc, c0, P->d_st_cls.p, P->d_st_pg.p, S, nullptr, nullptr, 1, pass == 0, out->dN_dy, st));
+            for (int h = 0; h < 3; h++)
+                HIP_TRY(is3d::launch_spacetime_segsum(P->d_st_D.p, nc, c0, P->d_st_cls.p, P->d_st_pg.p, S, starts[h], lists[h], Bs[h], pass == 0, hout[h],
+                                                      st));
+            if (out->dN_dy_cell)
+                HIP_TRY(is3d::launch_spacetime_per_cell(P->d_st_D.p, nc, c0, n, P->d_st_cls.p, P->d_st_pg.p, S, out->dN_dy_cell, st));
+            HIP_TRY(mark()); stage.push_back(2);
+        }
+        // dN/dy deta: 2+1D one value per eta node (:1365); 3+1D the single point of the species' total (quirk 2)
+        if (P->dim3) HIP_TRY(hipMemcpyAsync(out->dN_dydeta, out->dN_dy, sizeof(double) * S, hipMemcpyDeviceToDevice, st));
+        else HIP_TRY(is3d::launch_spacetime_eta_final(P->d_st_eta.p, P->d_st_cls.p, P->d_st_pg.p, P->d_kweight.p, S, K, out->dN_dydeta, st));
+        HIP_TRY(mark()); stage.push_back(2);
+        if (!stats) HIP_TRY(is3d::launch_fold_status(P->d_status.p, P->d_sticky.p, st));
+    }
+    if (stats) {
+        unsigned long long h[8], cn[4];
+        HIP_TRY(hipMemcpyAsync(h, P->d_status.p, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(cn, P->d_st_counters.p, sizeof cn, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t i = 1; i < ev.size(); i++) {
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[i - 1], ev[i]));
+            (stage[i - 1] == 0 ? stats->ms_prep : stage[i - 1] == 1 ? stats->ms_cells : stats->ms_bins) += ms;
+        }
+        stats->n_classes = P->ncls;
+        stats->n_passes = n == 0 ? 0 : (int32_t)((n + P->st_pass - 1) / P->st_pass);
+        stats->n_cells_skipped = n == 0 ? 0 : (int64_t)h[1];
+        stats->n_tau_outside = (int64_t)cn[0];
+        stats->n_r_outside = (int64_t)cn[1];
+        stats->n_tau_negative = (int64_t)cn[2];
+        stats->n_r_negative = (int64_t)cn[3];
+        if (n > 0) {
+            stats->bad_cell = (h[0] == ~0ULL) ? -1 : (int64_t)h[0];
+            if (h[7] != ~0ULL && (stats->bad_cell < 0 || (int64_t)h[7] < stats->bad_cell)) {
+                stats->bad_cell = (int64_t)h[7];
+                stats->code = IS3D_EDOMAIN;
+                return fail(IS3D_EDOMAIN, "cell %lld: p.u/T can exceed 1e9 for the momentum grid", (long long)stats->bad_cell);
+            }
+            if (stats->bad_cell >= 0) {
+                stats->code = IS3D_EDOMAIN;
+                return fail(IS3D_EDOMAIN, "cell %lld: T outside the coefficient table (the reference aborts in gsl_spline_eval here)",
+                            (long long)stats->bad_cell);
+            }
+        }
+    }
+    return IS3D_OK;
+}
+
+extern "C" int is3d_spacetime_distributions(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species,
+                                            const is3d_grid *grid, const double *pT_w, const double *phi_w, const is3d_df_tables *df,
+                                            const is3d_options *opts, const is3d_spacetime_bins *bins, is3d_spacetime_out *out,
+                                            is3d_spacetime_stats *stats)
+{
+    if (stats) { memset(stats, 0, sizeof *stats); stats->bad_cell = -1; }
+    if (!cells || !out || !opts || !pT_w || !phi_w) return fail(IS3D_EINVAL, "null argument");
+    int rc = st_check(bins, x, y, opts->df_mode);
+    if (rc) { if (stats) stats->code = rc; return rc; }
+    is3d_plan *P = nullptr;
+    rc = plan_create_impl(&P, species, grid, df, nullptr, opts, std::max<int64_t>(cells->n_cells, 1));
+    if (rc) { if (stats) stats->code = rc; return rc; }
+    struct Guard { is3d_plan *p; ~Guard() { is3d_plan_destroy(p); } } guard{P};
+    const int64_t n = cells->n_cells;
+    const int S = P->npart, n_eta_eff = P->dim3 ? 1 : P->K;
+    const int64_t tb = bins->tau_bins, rbn = bins->r_bins;
+    const bool diff = opts->include_baryon && opts->include_baryondiff_deltaf;
+    const double *src[25] = {cells->tau, cells->eta, cells->dat, cells->dax, cells->day, cells->dan, cells->ux, cells->uy, cells->un,
+                             cells->T, cells->P, cells->E, cells->pixx, cells->pixy, cells->pixn, cells->piyy, cells->piyn, cells->bulkPi,
+                             diff ? cells->muB : nullptr, diff ? cells->nB : nullptr, diff ? cells->Vx : nullptr,
+                             diff ? cells->Vy : nullptr, diff ? cells->Vn : nullptr, x, y};
+    const size_t sizes[6] = {(size_t)S, (size_t)(S * tb), (size_t)(S * rbn), (size_t)(S * tb * rbn), (size_t)S * n_eta_eff,
+                             out->dN_dy_cell ? (size_t)S * n : 0};
+    double *host_out[6] = {out->dN_dy, out->dN_taudtaudy, out->dN_twopirdrdy, out->dN_twopitaurdtaudrdy, out->dN_dydeta, out->dN_dy_cell};
+    for (int i = 0; i < 5; i++)
+        if (!host_out[i]) return fail(IS3D_EINVAL, "a required output array is NULL");
+    size_t total = 0;
+    for (size_t s : sizes) total += s;
+    DevBuf<double> dcell, dout;
+    HIP_TRY(dcell.alloc((size_t)std::max<int64_t>(n, 1) * 25));
+    HIP_TRY(dout.alloc(total));
+    hipEvent_t e0, e1, e2, e3;
+    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventCreate(&e2)); HIP_TRY(hipEventCreate(&e3));
+    struct EvGuard { hipEvent_t e[4]; ~EvGuard() { for (auto v : e) (void)hipEventDestroy(v); } } evg{{e0, e1, e2, e3}};
+    HIP_TRY(hipEventRecord(e0, nullptr));
+    const double *dptr[25];
+    for (int a = 0; a < 25; a++) {
+        dptr[a] = nullptr;
+        if (src[a] && n > 0) {
+            HIP_TRY(hipMemcpyAsync(dcell.p + (size_t)a * n, src[a], (size_t)n * sizeof(double), hipMemcpyHostToDevice, nullptr));
+            dptr[a] = dcell.p + (size_t)a * n;
+        }
+    }
+    HIP_TRY(hipEventRecord(e1, nullptr));
+    is3d_cells dc{};
+    dc.n_cells = n;
+    dc.tau = dptr[0]; dc.eta = dptr[1]; dc.dat = dptr[2]; dc.dax = dptr[3]; dc.day = dptr[4]; dc.dan = dptr[5];
+    dc.ux = dptr[6]; dc.uy = dptr[7]; dc.un = dptr[8]; dc.T = dptr[9]; dc.P = dptr[10]; dc.E = dptr[11];
+    dc.pixx = dptr[12]; dc.pixy = dptr[13]; dc.pixn = dptr[14]; dc.piyy = dptr[15]; dc.piyn = dptr[16]; dc.bulkPi = dptr[17];
+    dc.muB = dptr[18]; dc.nB = dptr[19]; dc.Vx = dptr[20]; dc.Vy = dptr[21]; dc.Vn = dptr[22];
+    const double *dx = n > 0 ? dptr[23] : dcell.p, *dy = n > 0 ? dptr[24] : dcell.p;
+    is3d_spacetime_out dev{};
+    double *dev_out[6];
+    size_t off = 0;
+    for (int i = 0; i < 6; i++) { dev_out[i] = sizes[i] ? dout.p + off : nullptr; off += sizes[i]; }
+    dev.dN_dy = dev_out[0]; dev.dN_taudtaudy = dev_out[1]; dev.dN_twopirdrdy = dev_out[2]; dev.dN_twopitaurdtaudrdy = dev_out[3];
+    dev.dN_dydeta = dev_out[4]; dev.dN_dy_cell = dev_out[5];
+    is3d_spacetime_stats stt{};
+    rc = is3d_plan_execute_spacetime(P, &dc, dx, dy, pT_w, phi_w, bins, &dev, nullptr, &stt);
+    if (rc) { if (stats) *stats = stt; return rc; }
+    HIP_TRY(hipEventRecord(e2, nullptr));
+    for (int i = 0; i < 6; i++)
+        if (sizes[i]) HIP_TRY(hipMemcpyAsync(host_out[i], dev_out[i], sizes[i] * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipEventRecord(e3, nullptr));
+    HIP_TRY(hipEventSynchronize(e3));
+    float h2d = 0, d2h = 0;
+    HIP_TRY(hipEventElapsedTime(&h2d, e0, e1));
+    HIP_TRY(hipEventElapsedTime(&d2h, e2, e3));
+    stt.ms_h2d = h2d;
+    stt.ms_d2h = d2h;
+    stt.code = IS3D_OK;
+    if (stats) *stats = stt;
+    return IS3D_OK;
 }

@@ -1,0 +1,48 @@
+// cf_spacetime.h -- launch entry points of cf_spacetime.hip (operation 0: smooth Cooper-Frye spacetime distributions).
+#pragma once
+#include "cf_device.h"
+#include <hip/hip_runtime_api.h>
+#include <cstdint>
+namespace is3d {
+
+// per-cell stage: lanes <-> (class, pT) with npTp (a power of two <= 64) lane slots per class; reads the unit-record stream TS that cf_prep
+// wrote for one pass of nc cells and writes D[cls * nc + cell] = unscale * sum_pT w_pT sum_phi w_phi sum_(y | eta) p.dsigma f
+// (prefactor and degeneracy not applied).  2+1D: eta_slab[chunk][cls][k] receives the chunk's (cls, eta node) partials.
+struct StCellArgs {
+    const double *TS;
+    int32_t nc, J, K, jtiles, rblocks;
+    int32_t ncls, npTp, nlw, G, nch;
+    int32_t outflow, regulate, zskip;
+    const double *lane_mT, *lane_pT, *lane_sign, *lane_b, *lane_wpT;   // [nlw * 64]
+    const double *wphi;                                                // [jtiles * JT], 0 past J
+    const unsigned long long *pds_bound;                               // bits of the stream's p.dsigma bound (cf_pds_bound)
+    double *D;                                                         // [ncls][nc]
+    double *eta_slab;                                                  // 2+1D: [nch][ncls][K]
+};
+bool spacetime_shape_supported(int dim3, int JT, int R);
+hipError_t launch_spacetime_cells(const StCellArgs &a, int ce, int dim3, int baryon, int JT, int R, hipStream_t st);
+// 2+1D: eta_cls[cls][k] (+)= sum over the nch chunks of eta_slab, in chunk order
+hipError_t launch_spacetime_eta_reduce(const double *eta_slab, int nch, int64_t n_per_chunk, int first_pass, double *eta_cls, hipStream_t st);
+// dN_dydeta[s][k] = (pg[s] * eta_cls[cls[s]][k]) / w[k]
+hipError_t launch_spacetime_eta_final(const double *eta_cls, const int32_t *cls, const double *pg, const double *w, int S, int K, double *out,
+                                      hipStream_t st);
+
+// bin stage: keys of every cell (tau bin, r bin, (tau, r) bin; -1 outside), counters[0..3] += live cells (u.dsigma > 0, the reference's
+// test at :1170) with tau bin outside [0, bins), r bin outside, tau bin < 0, r bin < 0
+hipError_t launch_spacetime_keys(const double *tau, const double *ux, const double *uy, const double *un, const double *dat, const double *dax,
+                                 const double *day, const double *dan, const double *x, const double *y, int64_t n, double tau_min, double dtau, int tau_bins,
+                                 double r_min, double dr, int r_bins, int32_t *key_tau, int32_t *key_r, int32_t *key_tr,
+                                 unsigned long long *counters, hipStream_t st);
+// stable counting sort of the cells by key: list[start[b] .. start[b + 1]) = the cells of bin b in ascending index order.
+// cnt: [ntile][B] ints of scratch, tot: [B], start: [B + 1]
+int spacetime_sort_tiles(int64_t n, int64_t B);
+hipError_t launch_spacetime_sort(const int32_t *key, int64_t n, int64_t B, int ntile, int32_t *cnt, int32_t *tot, int64_t *start, int32_t *list,
+                                 hipStream_t st);
+// out[s * nseg + seg] (first_pass ? 0 : out) + sum, left to right over the segment's cells c in [c0, c0 + nc) in ascending order, of
+// pg[s] * D[cls[s] * nc + (c - c0)], each product one rounding, each sum one rounding.  list == nullptr: one segment, all cells.
+hipError_t launch_spacetime_segsum(const double *D, int64_t nc, int64_t c0, const int32_t *cls, const double *pg, int S, const int64_t *start,
+                                   const int32_t *list, int64_t nseg, int first_pass, double *out, hipStream_t st);
+// per_cell[s * n_total + c0 + i] = pg[s] * D[cls[s] * nc + i]
+hipError_t launch_spacetime_per_cell(const double *D, int64_t nc, int64_t c0, int64_t n_total, const int32_t *cls, const double *pg, int S,
+                                     double *per_cell, hipStream_t st);
+}  // namespace is3d

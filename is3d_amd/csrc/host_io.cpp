@@ -1432,3 +1432,49 @@ extern "C" int is3d_write_sampler_tests(const char *results_dir, const is3d_samp
     for (int e = 0; e < n_events; e++) fl << yield[e] << std::endl;
     return IS3D_OK;
 }
+
+// operation 0: the smooth spacetime distributions of calculate_dN_dX (emissionfunction_smooth_kernels.cpp:1100-1127, :1403-1434) from the raw
+// bin sums of is3d_spacetime_distributions: per species dN_taudtaudy_<id>.dat, dN_twopirdrdy_<id>.dat, dN_twopitaurdtaudrdy_<id>.dat (written
+// inside the r loop: r outer, tau inner) and dN_dydeta_<id>_<n>pt.dat, setprecision(6) << scientific as the reference's streams.
+extern "C" int is3d_write_spacetime(const char *results_dir, const is3d_spacetime_bins *b, int32_t n_species, const int64_t *mc_id,
+                                    int32_t n_eta_eff, const double *eta_values, const is3d_spacetime_out *out)
+{
+    if (!results_dir || !b || !mc_id || !eta_values || !out || !out->dN_taudtaudy || !out->dN_twopirdrdy || !out->dN_twopitaurdtaudrdy ||
+        !out->dN_dydeta)
+        return io_fail(IS3D_EINVAL, "null argument");
+    if (b->tau_bins < 1 || b->r_bins < 1 || n_species < 0 || n_eta_eff < 1 || !(b->tau_max > b->tau_min) || !(b->r_max > b->r_min))
+        return io_fail(IS3D_EINVAL, "spacetime bins must be positive and tau_max > tau_min, r_max > r_min");
+    struct stat sb;
+    if (stat(results_dir, &sb) != 0 || !S_ISDIR(sb.st_mode)) return io_fail(IS3D_EIO, "%s is not a directory", results_dir);
+    const int TB = b->tau_bins, RB = b->r_bins;
+    const double tw = (b->tau_max - b->tau_min) / (double)TB, rw = (b->r_max - b->r_min) / (double)RB;   // :1075, :1084
+    const std::string root(results_dir);
+    for (int ip = 0; ip < n_species; ip++) {
+        const std::string id = std::to_string((long long)mc_id[ip]);
+        const std::string ft = root + "/dN_taudtaudy_" + id + ".dat", fr = root + "/dN_twopirdrdy_" + id + ".dat";
+        const std::string ftr = root + "/dN_twopitaurdtaudrdy_" + id + ".dat";
+        const std::string fe = root + "/dN_dydeta_" + id + "_" + std::to_string(n_eta_eff) + "pt.dat";
+        std::ofstream time_d(ft), radial_d(fr), timeradial_d(ftr), rapidity_d(fe);
+        if (!time_d || !radial_d || !timeradial_d || !rapidity_d) return io_fail(IS3D_EIO, "couldn't open the spacetime files under %s", results_dir);
+        const double *vt = out->dN_taudtaudy + (size_t)ip * TB, *vr = out->dN_twopirdrdy + (size_t)ip * RB;
+        const double *vtr = out->dN_twopitaurdtaudrdy + (size_t)ip * TB * RB;
+        for (int ir = 0; ir < RB; ir++) {                                        // :1403-1416
+            const double r_mid = b->r_min + rw * ((double)ir + 0.5);
+            radial_d << std::setprecision(6) << std::scientific << r_mid << "\t" << vr[ir] / (2.0 * M_PI * r_mid * rw) << "\n";
+            for (int it = 0; it < TB; it++) {
+                const double tau_mid = b->tau_min + tw * ((double)it + 0.5);
+                timeradial_d << std::setprecision(6) << std::scientific << tau_mid << "\t" << r_mid << "\t"
+                             << vtr[(size_t)it * RB + ir] / (2.0 * M_PI * tau_mid * r_mid * tw * rw) << "\n";
+            }
+        }
+        for (int it = 0; it < TB; it++) {                                        // :1418-1423
+            const double tau_mid = b->tau_min + tw * ((double)it + 0.5);
+            time_d << std::setprecision(6) << std::scientific << tau_mid << "\t" << vt[it] / (tau_mid * tw) << "\n";
+        }
+        for (int k = 0; k < n_eta_eff; k++)                                      // :1431-1434
+            rapidity_d << std::setprecision(6) << std::scientific << eta_values[k] << "\t" << out->dN_dydeta[(size_t)ip * n_eta_eff + k] << "\n";
+        time_d.close(); radial_d.close(); timeradial_d.close(); rapidity_d.close();
+        if (!time_d || !radial_d || !timeradial_d || !rapidity_d) return io_fail(IS3D_EIO, "write error under %s", results_dir);
+    }
+    return IS3D_OK;
+}

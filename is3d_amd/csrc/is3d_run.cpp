@@ -16,7 +16,12 @@
 // reference allocates the per-cell c0..c4 (emissionfunction.cpp:1397-1418) and the CUDA tree loads the VAH tables
 // (src/cuda/deltafReader.cu:74-81) -- reads input/surface.dat with read_surf_VAH_PLMatch and deltaf_coefficients/vah/c{0..4}_vah1.dat,
 // runs what the commented-out call site would (emissionfunction.cpp:1650-1654) and writes the same three result files.
-// Scope: operation in {1, 2}, mode in {0, 1, 4, 5, 6, 7}, df_mode in {1, 2, 3} with include_baryon in {0, 1}, df_mode 4
+// operation = 0 (smooth spacetime distributions, calculate_dN_dX; emissionfunction.cpp:1510-1516): mode in {0, 1, 4, 5, 6, 7}, df_mode in
+// {1, 2}, include_baryon in {0, 1}, dimension 2 or 3, on the first device of the run's list; reads tau_min ... r_bins (:216-222), writes
+// results/spacetime_distribution/{dN_taudtaudy, dN_twopirdrdy, dN_twopitaurdtaudrdy}_<id>.dat and dN_dydeta_<id>_<n>pt.dat (the directory must
+// exist) and prints one "dN_dy = %lf" line per species; no momentum-spectra file (those are written for operation = 1 only, :1678).  df_mode 3 / 4
+// (calculate_dN_dX_feqmod) and mode 2 are refused before anything is written.
+// Scope: operation in {0, 1, 2}, mode in {0, 1, 4, 5, 6, 7}, df_mode in {1, 2, 3} with include_baryon in {0, 1}, df_mode 4
 // (modified equilibrium; also reads tables/gla_roots_weights_32_points.txt, deta_min, mass_pion0 and the surface
 // averages it has just written, as the reference does) with include_baryon = 0.  Anything else is refused
 // with a message instead of silently doing something different from the reference.
@@ -158,7 +163,14 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
     GET(regulate, "regulate_deltaf");
     GET(outflow, "outflow");
 #undef GET
-    if (operation != 1 && operation != 2) DIE("operation = %d: only operation = 1 (smooth momentum spectra) and 2 (particle sampler) are on this path", operation);
+    if (operation != 0 && operation != 1 && operation != 2)
+        DIE("operation = %d: operation = 0 (smooth spacetime distributions), 1 (smooth momentum spectra) and 2 (particle sampler) are on this path", operation);
+    if (operation == 0) {
+        if (df_mode == 3 || df_mode == 4)
+            DIE("operation = 0 with df_mode = %d needs calculate_dN_dX_feqmod, which is not built yet: set df_mode = 1 or 2", df_mode);
+        if (!mem && mode == 2) DIE("operation = 0 with mode = 2: the reference has no spacetime distribution for anisotropic hydro");
+        if (mem && (!mem_x || !mem_y)) DIE("operation = 0 needs the cells' x and y positions (NULL given)");
+    }
     {
         double decays = 0.0;   // optional key here; the reference runs do_resonance_decays() after the spectra (emissionfunction.cpp:1689-1698)
         if (get_param("do_resonance_decays", &decays, false) == IS3D_OK && (int)decays)
@@ -439,6 +451,51 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
             memcpy(res->mass, mass.data(), sizeof(double) * (size_t)sp.n);
         }
         printf("Done sampling particles. Output stored in results folder. Goodbye!\n");
+        return IS3D_OK;
+    }
+    if (operation == 0) {
+        // ---- emissionfunction.cpp:1510-1516 -> calculate_dN_dX (smooth_kernels.cpp:1000-1446) ----
+        double t0b, t1b, tb, r0b, r1b, rb;
+        if (get_param("tau_min", &t0b) || get_param("tau_max", &t1b) || get_param("tau_bins", &tb) || get_param("r_min", &r0b) ||
+            get_param("r_max", &r1b) || get_param("r_bins", &rb))
+            return IS3D_EINVAL;
+        is3d_spacetime_bins bins{t0b, t1b, r0b, r1b, (int32_t)tb, (int32_t)rb};
+        const double *xp = mem ? mem_x : sa[23], *yp = mem ? mem_y : sa[24];
+        std::vector<double> zero(1, 0.0);
+        if (n_cells == 0) xp = yp = zero.data();
+        const int S = sp.n, n_eta_eff = dimension == 3 ? 1 : (int)eta.size();
+        std::vector<double> o_dy((size_t)S), o_t((size_t)S * bins.tau_bins), o_r((size_t)S * bins.r_bins),
+            o_tr((size_t)S * bins.tau_bins * bins.r_bins), o_eta((size_t)S * n_eta_eff);
+        is3d_spacetime_out out{o_dy.data(), o_t.data(), o_r.data(), o_tr.data(), o_eta.data(), nullptr};
+        for (int ip = 0; ip < S; ip++) printf("Starting spacetime distribution %lld\n", (long long)mcid[ip]);   // :1100
+        is3d_spacetime_stats sst{};
+        const int rc0 = is3d_spacetime_distributions(&cells, xp, yp, &sp, &grid, pTw.data(), phiw.data(), &df, &opts, &bins, &out, &sst);
+        if (rc0) {
+            const std::string msg = is3d_last_error();
+            DIE("is3d_spacetime_distributions failed (%d): %s", rc0, msg.c_str());
+        }
+        // the reference prints an error line per cell with a negative bin index (:1391-1392); one line with the counts here
+        if (sst.n_tau_negative || sst.n_r_negative)
+            printf("Error: %lld cells with a negative tau bin index, %lld with a negative r bin index. Adjust the tau_min / r_min parameters\n",
+                   (long long)sst.n_tau_negative, (long long)sst.n_r_negative);
+        // 3+1D: the single eta point is eta_fo of the surface's last cell (etaValues[0], assigned at :1155 before the skip test)
+        std::vector<double> eta_vals = dimension == 3 ? std::vector<double>(1, n_cells > 0 ? cells.eta[n_cells - 1] : 0.0) : eta;
+        if (is3d_write_spacetime("results/spacetime_distribution", &bins, S, mcid.data(), n_eta_eff, eta_vals.data(), &out))
+            DIE("%s", is3d_last_error());
+        for (int ip = 0; ip < S; ip++) printf("dN_dy = %lf\n", o_dy[ip]);   // :1438-1441
+        printf("species classes evaluated: %d of %d; cells skipped (u.dsigma <= 0): %lld; outside the tau / r bins: %lld / %lld\n", sst.n_classes, S,
+               (long long)sst.n_cells_skipped, (long long)sst.n_tau_outside, (long long)sst.n_r_outside);
+        printf("device time: prep %.3f ms, per-cell %.3f ms, bins %.3f ms; h2d %.3f ms, d2h %.3f ms\n", sst.ms_prep, sst.ms_cells, sst.ms_bins,
+               sst.ms_h2d, sst.ms_d2h);
+        if (res) {
+            res->operation = 0; res->n_species = S;
+            res->mc_id = (int64_t *)malloc(sizeof(int64_t) * (size_t)S);
+            res->mass = (double *)malloc(sizeof(double) * (size_t)S);
+            if (!res->mc_id || !res->mass) return is3d::set_error(IS3D_ENOMEM, "out of memory");
+            memcpy(res->mc_id, mcid.data(), sizeof(int64_t) * (size_t)S);
+            memcpy(res->mass, mass.data(), sizeof(double) * (size_t)S);
+        }
+        printf("Done calculating spacetime distributions. Output stored in results/spacetime_distribution. Goodbye!\n");
         return IS3D_OK;
     }
     is3d_status st{};
