@@ -25,17 +25,12 @@
 #include <vector>
 
 #include "../../include/is3d_amd.h"
+#include "cf_host.h"
 #include "errors.h"
 
 #define fail is3d::set_error
 
 namespace {
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(IS3D_ENODEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 // ---- RCCL, bound lazily ----
 struct Rccl {
@@ -492,8 +487,6 @@ extern "C" int is3d_plan_execute_allreduce(is3d_plan *plan, const is3d_cells *sh
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-constexpr int kCellArrays = 23;
-
 // everything a shard owns for the life of a multi-device plan
 struct Shard {
     int device = 0;
@@ -580,7 +573,7 @@ int shard_create(Shard &s, const is3d_species *sp, const is3d_grid *grid, const 
     (void)is3d_plan_set_timing(s.plan, 1);
     const int64_t nout = is3d_plan_output_size(s.plan);
     HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc((void **)&s.d_cells, sizeof(double) * kCellArrays * (size_t)s.cap));
+    HIP_TRY(hipMalloc((void **)&s.d_cells, sizeof(double) * is3d::kCellArrays * (size_t)s.cap));
     HIP_TRY(hipMalloc((void **)&s.d_out, sizeof(double) * (size_t)nout));
     if (need_tmp) HIP_TRY(hipMalloc((void **)&s.d_tmp, sizeof(double) * (size_t)nout));
     for (int k = 0; k < (need_tmp ? 3 : 2); k++) is3d::count_resource(1);
@@ -597,26 +590,10 @@ int shard_run(Shard &s, const is3d_cells *cells, bool diff)
 {
     HIP_TRY(hipSetDevice(s.device));
     const int64_t n = s.hi - s.lo;
-    const double *src[kCellArrays] = {cells->tau, cells->eta, cells->dat, cells->dax, cells->day, cells->dan, cells->ux, cells->uy, cells->un,
-                                      cells->T, cells->P, cells->E, cells->pixx, cells->pixy, cells->pixn, cells->piyy, cells->piyn, cells->bulkPi,
-                                      diff ? cells->muB : nullptr, diff ? cells->nB : nullptr, diff ? cells->Vx : nullptr,
-                                      diff ? cells->Vy : nullptr, diff ? cells->Vn : nullptr};
-    const double *dptr[kCellArrays];
     HIP_TRY(hipEventRecord(s.e0, s.stream));
-    for (int a = 0; a < kCellArrays; a++) {
-        dptr[a] = nullptr;
-        if (src[a] && n > 0) {
-            HIP_TRY(hipMemcpyAsync(s.d_cells + (size_t)a * n, src[a] + s.lo, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s.stream));
-            dptr[a] = s.d_cells + (size_t)a * n;
-        }
-    }
+    is3d_cells dc;
+    HIP_TRY(is3d::stage_cells(*cells, [diff](int a) { return a < 18 || diff; }, s.lo, n, s.d_cells, s.stream, &dc));
     HIP_TRY(hipEventRecord(s.e1, s.stream));
-    is3d_cells dc{};
-    dc.n_cells = n;
-    dc.tau = dptr[0]; dc.eta = dptr[1]; dc.dat = dptr[2]; dc.dax = dptr[3]; dc.day = dptr[4]; dc.dan = dptr[5];
-    dc.ux = dptr[6]; dc.uy = dptr[7]; dc.un = dptr[8]; dc.T = dptr[9]; dc.P = dptr[10]; dc.E = dptr[11];
-    dc.pixx = dptr[12]; dc.pixy = dptr[13]; dc.pixn = dptr[14]; dc.piyy = dptr[15]; dc.piyn = dptr[16]; dc.bulkPi = dptr[17];
-    dc.muB = dptr[18]; dc.nB = dptr[19]; dc.Vx = dptr[20]; dc.Vy = dptr[21]; dc.Vn = dptr[22];
     const int rc = is3d_plan_execute(s.plan, &dc, s.d_out, s.stream, &s.st);
     if (rc) return rc;
     is3d_status t{};

@@ -18,6 +18,7 @@
 
 #include "../../include/is3d_amd.h"
 #include "cf_feqmod.h"
+#include "cf_host.h"
 #include "cf_launch.h"
 #include "cf_spacetime.h"
 #include "errors.h"
@@ -26,42 +27,7 @@
 
 #define fail is3d::set_error
 
-namespace {
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(IS3D_ENODEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    hipError_t alloc(size_t count)
-    {
-        release();
-        n = count;
-        if (!count) return hipSuccess;
-        is3d::count_resource(1);
-        return hipMalloc((void **)&p, count * sizeof(T));
-    }
-    hipError_t upload(const std::vector<T> &h)
-    {
-        hipError_t e = alloc(h.size());
-        if (e != hipSuccess || h.empty()) return e;
-        return hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    ~DevBuf() { release(); }
-};
-
-}  // namespace
+using is3d::DevBuf;
 
 struct is3d_plan {
     is3d_options opts{};
@@ -695,6 +661,57 @@ static void chunk_plan(const is3d_plan *P, int64_t n, int &nch, int &nsmall)
     nsmall = is3d::chunk_taper(n, P->opts.cell_chunks, nch);
 }
 
+// cf_prep's parameters for the cells [c0, c0 + nc) of a pass; the caller sets tiled, pds_bound and TE
+static is3d::PrepParams fill_prep(const is3d_plan *P, const is3d_cells *cells, int64_t c0, int32_t nc)
+{
+    const is3d_options &o = P->opts;
+    is3d::PrepParams pp{};
+    pp.cells = is3d::cell_ptrs(*cells);
+    pp.cell0 = c0;
+    pp.n_cells = nc;
+    pp.J = P->J; pp.K = P->K;
+    pp.dim3 = P->dim3; pp.ce = P->ce;
+    pp.include_bulk = o.include_bulk_deltaf != 0;
+    pp.include_shear = o.include_shear_deltaf != 0;
+    pp.baryon = P->baryon; pp.baryondiff = P->baryondiff;
+    pp.bil = P->bil;
+    pp.cosphi = P->d_cosphi.p; pp.sinphi = P->d_sinphi.p;
+    pp.kgrid = P->d_kgrid.p; pp.kweight = P->d_kweight.p; pp.kch = P->d_kch.p; pp.ksh = P->d_ksh.p;
+    pp.spl = P->spl;
+    pp.S1 = P->d_S1.p; pp.S2 = P->d_S2.p; pp.S3 = P->d_S3.p;
+    pp.JT = P->JT; pp.R = P->KT; pp.jtiles = P->jtiles; pp.rblocks = P->rblocks;
+    pp.TS = P->d_TS.p;
+    pp.mTmax = P->mTmax; pp.kmin = P->kmin; pp.kmax = P->kmax;
+    pp.status = P->d_status.p;
+    pp.pTgrid = P->d_pTgrid.p; pp.npT = P->npT;
+    return pp;
+}
+
+// the status words of an execute (cf_device.h): [0] min bad cell, [1..5] counters, [6] the |p.dsigma| bound, [7] min cell whose p.u/T can exceed 1e9
+static hipError_t status_begin(is3d_plan *P, hipStream_t st)
+{
+    static const unsigned long long init[8] = {~0ULL, 0ULL, 0ULL, 0ULL, 0ULL, 0ULL, 0ULL, ~0ULL};
+    return hipMemcpyAsync(P->d_status.p, init, sizeof init, hipMemcpyHostToDevice, st);
+}
+
+// the words read back after the execute: *bad_cell, and IS3D_EDOMAIN (also in *code) for a cell out of the table or of the exponent range
+static int status_finish(const is3d_plan *P, const unsigned long long h[8], int64_t *bad_cell, int32_t *code)
+{
+    *bad_cell = (h[0] == ~0ULL) ? -1 : (int64_t)h[0];
+    if (h[7] != ~0ULL && (*bad_cell < 0 || (int64_t)h[7] < *bad_cell)) {
+        *bad_cell = (int64_t)h[7];
+        *code = IS3D_EDOMAIN;
+        return fail(IS3D_EDOMAIN, "cell %lld: p.u/T can exceed 1e9 for the momentum grid (flow velocity / temperature outside the "
+                    "kernel's exponent range; the reference's exp() overflows to inf there)", (long long)*bad_cell);
+    }
+    if (*bad_cell >= 0) {
+        *code = IS3D_EDOMAIN;
+        return fail(IS3D_EDOMAIN, "cell %lld: T%s outside the coefficient table (the reference aborts in gsl_spline_eval here)",
+                    (long long)*bad_cell, (P->feqmod && P->opts.df_mode == 4) ? " (or bulkPi/P)" : "");
+    }
+    return IS3D_OK;
+}
+
 extern "C" int is3d_plan_execute(is3d_plan *P, const is3d_cells *cells, double *dN_out, void *hip_stream, is3d_status *status)
 {
     if (!P || !cells || !dN_out) return fail(IS3D_EINVAL, "null argument");
@@ -702,17 +719,7 @@ extern "C" int is3d_plan_execute(is3d_plan *P, const is3d_cells *cells, double *
     const int64_t n = cells->n_cells;
     if (n < 0 || n > P->max_cells) return fail(IS3D_EINVAL, "n_cells = %lld exceeds the plan's max_cells = %lld", (long long)n, (long long)P->max_cells);
     const is3d_options &o = P->opts;
-    const bool need_eta = P->dim3;
-    if (n > 0) {
-        if (!cells->tau || !cells->dat || !cells->dax || !cells->day || !cells->dan || !cells->ux || !cells->uy || !cells->un ||
-            !cells->T || !cells->P || !cells->E || (need_eta && !cells->eta))
-            return fail(IS3D_EINVAL, "a required cell array is NULL");
-        if (o.include_shear_deltaf && (!cells->pixx || !cells->pixy || !cells->pixn || !cells->piyy || !cells->piyn))
-            return fail(IS3D_EINVAL, "include_shear_deltaf needs pixx, pixy, pixn, piyy, piyn");
-        if (o.include_bulk_deltaf && !cells->bulkPi) return fail(IS3D_EINVAL, "include_bulk_deltaf needs bulkPi");
-        if (P->baryondiff && (!cells->muB || !cells->nB || !cells->Vx || !cells->Vy || !cells->Vn))
-            return fail(IS3D_EINVAL, "include_baryon && include_baryondiff_deltaf need muB, nB, Vx, Vy, Vn");
-    }
+    if (int rc = is3d::check_cells(cells, P->dim3, o, P->baryondiff)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     HIP_TRY(hipSetDevice(P->device));
 
@@ -726,8 +733,7 @@ extern "C" int is3d_plan_execute(is3d_plan *P, const is3d_cells *cells, double *
         }
     }
     P->last_passes = npasses;
-    unsigned long long init[8] = {~0ULL, 0ULL, 0ULL, 0ULL, 0ULL, 0ULL, 0ULL, ~0ULL};
-    HIP_TRY(hipMemcpyAsync(P->d_status.p, init, sizeof init, hipMemcpyHostToDevice, st));
+    HIP_TRY(status_begin(P, st));
 
     int nch_used = 1, nch_small = 0;
     // tiled delta-f stream: p.dsigma travels times 2^-e (status[6] = bits of the bound, cf_device.h)
@@ -739,18 +745,14 @@ extern "C" int is3d_plan_execute(is3d_plan *P, const is3d_cells *cells, double *
         // all passes use the chunk count of the first (largest) pass so that partial slots line up
         chunk_plan(P, std::min<int64_t>(n, P->pass_cells), nch_used, nch_small);
         if (use_scale) {
-            is3d::CellPtrs cp{};
-            cp.tau = cells->tau; cp.eta = cells->eta; cp.dat = cells->dat; cp.dax = cells->dax; cp.day = cells->day; cp.dan = cells->dan;
-            HIP_TRY(is3d::launch_pds_bound(cp, n, P->dim3, P->kmin, P->kmax, P->gw2d, P->mTmax, P->pTmax, P->d_status.p + 6, st));
+            HIP_TRY(is3d::launch_pds_bound(is3d::cell_ptrs(*cells), n, P->dim3, P->kmin, P->kmax, P->gw2d, P->mTmax, P->pTmax, P->d_status.p + 6, st));
         }
         for (int pass = 0; pass < npasses; pass++) {
             const int64_t c0 = (int64_t)pass * P->pass_cells;
             const int32_t nc = (int32_t)std::min<int64_t>(P->pass_cells, n - c0);
             if (P->feqmod) {
                 is3d::FqPrepParams fp{};
-                fp.cells = {cells->tau, cells->eta, cells->dat, cells->dax, cells->day, cells->dan, cells->ux, cells->uy, cells->un,
-                            cells->T, cells->P, cells->E, cells->pixx, cells->pixy, cells->pixn, cells->piyy, cells->piyn, cells->bulkPi,
-                            cells->muB, cells->nB, cells->Vx, cells->Vy, cells->Vn};
+                fp.cells = is3d::cell_ptrs(*cells);
                 fp.baryon = P->baryon; fp.baryondiff = P->baryondiff; fp.bil = P->bil;
                 fp.cell0 = c0; fp.n_cells = nc; fp.J = P->J; fp.K = P->K;
                 fp.dim3 = P->dim3; fp.mode = o.df_mode;
@@ -800,29 +802,10 @@ extern "C" int is3d_plan_execute(is3d_plan *P, const is3d_cells *cells, double *
                 if (P->timing) HIP_TRY(hipEventRecord(P->ev_list[pass * 3 + 2], st));
                 continue;
             }
-            is3d::PrepParams pp{};
-            pp.cells = {cells->tau, cells->eta, cells->dat, cells->dax, cells->day, cells->dan, cells->ux, cells->uy, cells->un,
-                        cells->T, cells->P, cells->E, cells->pixx, cells->pixy, cells->pixn, cells->piyy, cells->piyn, cells->bulkPi};
-            pp.cell0 = c0;
-            pp.n_cells = nc;
-            pp.J = P->J; pp.K = P->K;
-            pp.dim3 = P->dim3; pp.ce = P->ce;
-            pp.include_bulk = o.include_bulk_deltaf != 0;
-            pp.include_shear = o.include_shear_deltaf != 0;
-            pp.baryon = P->baryon; pp.baryondiff = P->baryondiff;
-            pp.bil = P->bil;
-            pp.cells.muB = cells->muB; pp.cells.nB = cells->nB; pp.cells.Vx = cells->Vx; pp.cells.Vy = cells->Vy; pp.cells.Vn = cells->Vn;
-            pp.cosphi = P->d_cosphi.p; pp.sinphi = P->d_sinphi.p;
-            pp.kgrid = P->d_kgrid.p; pp.kweight = P->d_kweight.p; pp.kch = P->d_kch.p; pp.ksh = P->d_ksh.p;
-            pp.spl = P->spl;
-            pp.S1 = P->d_S1.p; pp.S2 = P->d_S2.p; pp.S3 = P->d_S3.p;
+            is3d::PrepParams pp = fill_prep(P, cells, c0, nc);
             pp.tiled = (P->variant != 1);
-            pp.JT = P->JT; pp.R = P->KT; pp.jtiles = P->jtiles; pp.rblocks = P->rblocks;
-            pp.TS = P->d_TS.p;
             pp.pds_bound = use_scale ? P->d_status.p + 6 : nullptr;
-            pp.mTmax = P->mTmax; pp.kmin = P->kmin; pp.kmax = P->kmax;
-            pp.status = P->d_status.p;
-            pp.TE = P->e2tab ? P->d_TE.p : nullptr; pp.pTgrid = P->d_pTgrid.p; pp.npT = P->npT;
+            pp.TE = P->e2tab ? P->d_TE.p : nullptr;
             if (P->timing) HIP_TRY(hipEventRecord(P->ev_list[pass * 3 + 0], st));
             HIP_TRY(is3d::launch_prep(pp, st));
             if (P->timing) HIP_TRY(hipEventRecord(P->ev_list[pass * 3 + 1], st));
@@ -887,18 +870,7 @@ extern "C" int is3d_plan_execute(is3d_plan *P, const is3d_cells *cells, double *
         status->n_wave_rows_culled = (int64_t)h[3];
         status->n_cells_breakdown = (int64_t)h[4];
         status->n_cells_narrow = (int64_t)h[5];
-        status->bad_cell = (h[0] == ~0ULL) ? -1 : (int64_t)h[0];
-        if (h[7] != ~0ULL && (status->bad_cell < 0 || (int64_t)h[7] < status->bad_cell)) {
-            status->bad_cell = (int64_t)h[7];
-            status->code = IS3D_EDOMAIN;
-            return fail(IS3D_EDOMAIN, "cell %lld: p.u/T can exceed 1e9 for the momentum grid (flow velocity / temperature outside the "
-                        "kernel's exponent range; the reference's exp() overflows to inf there)", (long long)status->bad_cell);
-        }
-        if (status->bad_cell >= 0) {
-            status->code = IS3D_EDOMAIN;
-            return fail(IS3D_EDOMAIN, "cell %lld: T%s outside the coefficient table (the reference aborts in gsl_spline_eval here)",
-                        (long long)status->bad_cell, (P->feqmod && o.df_mode == 4) ? " (or bulkPi/P)" : "");
-        }
+        return status_finish(P, h, &status->bad_cell, &status->code);
     }
     return IS3D_OK;
 }
@@ -976,33 +948,18 @@ static int smooth_spectra_impl(const is3d_cells *cells, const is3d_species *spec
 
     const int64_t n = cells->n_cells;
     const bool diff = opts->include_baryon && opts->include_baryondiff_deltaf;
-    const double *src[23] = {cells->tau, cells->eta, cells->dat, cells->dax, cells->day, cells->dan, cells->ux, cells->uy, cells->un,
-                             cells->T, cells->P, cells->E, cells->pixx, cells->pixy, cells->pixn, cells->piyy, cells->piyn, cells->bulkPi,
-                             diff ? cells->muB : nullptr, diff ? cells->nB : nullptr, diff ? cells->Vx : nullptr,
-                             diff ? cells->Vy : nullptr, diff ? cells->Vn : nullptr};
+    const auto keep = [diff](int a) { return a < 18 || diff; };   // the diffusion arrays only when they are read
     DevBuf<double> dcell, dout;
-    HIP_TRY(dcell.alloc((size_t)std::max<int64_t>(n, 1) * 23));
+    HIP_TRY(dcell.alloc((size_t)std::max<int64_t>(n, 1) * is3d::kCellArrays));
     HIP_TRY(dout.alloc((size_t)P->nout));
     hipEvent_t e0, e1, e2, e3;
     HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventCreate(&e2)); HIP_TRY(hipEventCreate(&e3));
     struct EvGuard { hipEvent_t e[4]; ~EvGuard() { for (auto x : e) (void)hipEventDestroy(x); } } evg{{e0, e1, e2, e3}};
     HIP_TRY(hipEventRecord(e0, nullptr));
-    const double *dptr[23];
-    for (int a = 0; a < 23; a++) {
-        dptr[a] = nullptr;
-        if (src[a] && n > 0) {
-            HIP_TRY(hipMemcpyAsync(dcell.p + (size_t)a * n, src[a], (size_t)n * sizeof(double), hipMemcpyHostToDevice, nullptr));
-            dptr[a] = dcell.p + (size_t)a * n;
-        }
-    }
+    is3d_cells dc;
+    HIP_TRY(is3d::stage_cells(*cells, keep, 0, n, dcell.p, nullptr, &dc));
     if (opts->accumulate) HIP_TRY(hipMemcpyAsync(dout.p, dN_out, (size_t)P->nout * sizeof(double), hipMemcpyHostToDevice, nullptr));
     HIP_TRY(hipEventRecord(e1, nullptr));
-    is3d_cells dc{};
-    dc.n_cells = n;
-    dc.tau = dptr[0]; dc.eta = dptr[1]; dc.dat = dptr[2]; dc.dax = dptr[3]; dc.day = dptr[4]; dc.dan = dptr[5];
-    dc.ux = dptr[6]; dc.uy = dptr[7]; dc.un = dptr[8]; dc.T = dptr[9]; dc.P = dptr[10]; dc.E = dptr[11];
-    dc.pixx = dptr[12]; dc.pixy = dptr[13]; dc.pixn = dptr[14]; dc.piyy = dptr[15]; dc.piyn = dptr[16]; dc.bulkPi = dptr[17];
-    dc.muB = dptr[18]; dc.nB = dptr[19]; dc.Vx = dptr[20]; dc.Vy = dptr[21]; dc.Vn = dptr[22];
     is3d_status st{};
     rc = is3d_plan_execute(P, &dc, dout.p, nullptr, &st);
     if (rc) { if (status) *status = st; return rc; }
@@ -1126,16 +1083,8 @@ extern "C" int is3d_plan_execute_spacetime(is3d_plan *P, const is3d_cells *cells
     if (n < 0 || n > P->max_cells) return fail(IS3D_EINVAL, "n_cells = %lld exceeds the plan's max_cells = %lld", (long long)n, (long long)P->max_cells);
     if (n > 0x7fff0000LL) return fail(IS3D_EINVAL, "operation 0 takes up to 2^31 cells");
     const is3d_options &o = P->opts;
-    if (n > 0) {
-        if (!cells->tau || !cells->dat || !cells->dax || !cells->day || !cells->dan || !cells->ux || !cells->uy || !cells->un ||
-            !cells->T || !cells->P || !cells->E || (P->dim3 && !cells->eta))
-            return fail(IS3D_EINVAL, "a required cell array is NULL");
-        if (o.include_shear_deltaf && (!cells->pixx || !cells->pixy || !cells->pixn || !cells->piyy || !cells->piyn))
-            return fail(IS3D_EINVAL, "include_shear_deltaf needs pixx, pixy, pixn, piyy, piyn");
-        if (o.include_bulk_deltaf && !cells->bulkPi) return fail(IS3D_EINVAL, "include_bulk_deltaf needs bulkPi");
-        if (P->baryondiff && (!cells->muB || !cells->nB || !cells->Vx || !cells->Vy || !cells->Vn))
-            return fail(IS3D_EINVAL, "include_baryon && include_baryondiff_deltaf need muB, nB, Vx, Vy, Vn");
-    }
+    rc = is3d::check_cells(cells, P->dim3, o, P->baryondiff);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     HIP_TRY(hipSetDevice(P->device));
     rc = st_setup(P);
@@ -1171,8 +1120,7 @@ extern "C" int is3d_plan_execute_spacetime(is3d_plan *P, const is3d_cells *cells
         return hipEventRecord(e, st);
     };
     std::vector<int> stage;   // stage of the interval that ends at event i: 0 prep, 1 cells, 2 bins
-    unsigned long long init[8] = {~0ULL, 0ULL, 0ULL, 0ULL, 0ULL, 0ULL, 0ULL, ~0ULL};
-    HIP_TRY(hipMemcpyAsync(P->d_status.p, init, sizeof init, hipMemcpyHostToDevice, st));
+    HIP_TRY(status_begin(P, st));
     HIP_TRY(hipMemsetAsync(P->d_st_counters.p, 0, 4 * sizeof(unsigned long long), st));
     HIP_TRY(mark());
 
@@ -1206,9 +1154,7 @@ extern "C" int is3d_plan_execute_spacetime(is3d_plan *P, const is3d_cells *cells
         for (int h = 0; h < 3; h++) HIP_TRY(hipMemsetAsync(hout[h], 0, sizeof(double) * S * Bs[h], st));
         HIP_TRY(hipMemsetAsync(out->dN_dydeta, 0, sizeof(double) * S * n_eta_eff, st));
     } else {
-        is3d::CellPtrs cp{};
-        cp.tau = cells->tau; cp.eta = cells->eta; cp.dat = cells->dat; cp.dax = cells->dax; cp.day = cells->day; cp.dan = cells->dan;
-        HIP_TRY(is3d::launch_pds_bound(cp, n, P->dim3, P->kmin, P->kmax, P->gw2d, P->mTmax, P->pTmax, P->d_status.p + 6, st));
+        HIP_TRY(is3d::launch_pds_bound(is3d::cell_ptrs(*cells), n, P->dim3, P->kmin, P->kmax, P->gw2d, P->mTmax, P->pTmax, P->d_status.p + 6, st));
         const int64_t pc = P->st_pass;
         const int G = (P->st_nlw + 3) / 4;
         int nch = (int)std::min<int64_t>(pc, std::max<int64_t>(1, 16384 / G));
@@ -1218,29 +1164,10 @@ extern "C" int is3d_plan_execute_spacetime(is3d_plan *P, const is3d_cells *cells
         for (int pass = 0; pass < npasses; pass++) {
             const int64_t c0 = (int64_t)pass * pc;
             const int32_t nc = (int32_t)std::min<int64_t>(pc, n - c0);
-            is3d::PrepParams pp{};
-            pp.cells = {cells->tau, cells->eta, cells->dat, cells->dax, cells->day, cells->dan, cells->ux, cells->uy, cells->un,
-                        cells->T, cells->P, cells->E, cells->pixx, cells->pixy, cells->pixn, cells->piyy, cells->piyn, cells->bulkPi,
-                        cells->muB, cells->nB, cells->Vx, cells->Vy, cells->Vn};
-            pp.cell0 = c0;
-            pp.n_cells = nc;
-            pp.J = P->J; pp.K = P->K;
-            pp.dim3 = P->dim3; pp.ce = P->ce;
-            pp.include_bulk = o.include_bulk_deltaf != 0;
-            pp.include_shear = o.include_shear_deltaf != 0;
-            pp.baryon = P->baryon; pp.baryondiff = P->baryondiff;
-            pp.bil = P->bil;
-            pp.cosphi = P->d_cosphi.p; pp.sinphi = P->d_sinphi.p;
-            pp.kgrid = P->d_kgrid.p; pp.kweight = P->d_kweight.p; pp.kch = P->d_kch.p; pp.ksh = P->d_ksh.p;
-            pp.spl = P->spl;
+            is3d::PrepParams pp = fill_prep(P, cells, c0, nc);
             pp.tiled = 1;
-            pp.JT = P->JT; pp.R = P->KT; pp.jtiles = P->jtiles; pp.rblocks = P->rblocks;
-            pp.TS = P->d_TS.p;
             pp.pds_bound = P->d_status.p + 6;
-            pp.mTmax = P->mTmax; pp.kmin = P->kmin; pp.kmax = P->kmax;
-            pp.status = P->d_status.p;
             pp.TE = nullptr;   // the E2 tables of cf_main_tile3e are not needed here
-            pp.pTgrid = P->d_pTgrid.p; pp.npT = P->npT;
             HIP_TRY(is3d::launch_prep(pp, st));
             HIP_TRY(mark()); stage.push_back(0);
 
@@ -1287,19 +1214,7 @@ extern "C" int is3d_plan_execute_spacetime(is3d_plan *P, const is3d_cells *cells
         stats->n_r_outside = (int64_t)cn[1];
         stats->n_tau_negative = (int64_t)cn[2];
         stats->n_r_negative = (int64_t)cn[3];
-        if (n > 0) {
-            stats->bad_cell = (h[0] == ~0ULL) ? -1 : (int64_t)h[0];
-            if (h[7] != ~0ULL && (stats->bad_cell < 0 || (int64_t)h[7] < stats->bad_cell)) {
-                stats->bad_cell = (int64_t)h[7];
-                stats->code = IS3D_EDOMAIN;
-                return fail(IS3D_EDOMAIN, "cell %lld: p.u/T can exceed 1e9 for the momentum grid", (long long)stats->bad_cell);
-            }
-            if (stats->bad_cell >= 0) {
-                stats->code = IS3D_EDOMAIN;
-                return fail(IS3D_EDOMAIN, "cell %lld: T outside the coefficient table (the reference aborts in gsl_spline_eval here)",
-                            (long long)stats->bad_cell);
-            }
-        }
+        return status_finish(P, h, &stats->bad_cell, &stats->code);
     }
     return IS3D_OK;
 }
@@ -1321,10 +1236,7 @@ extern "C" int is3d_spacetime_distributions(const is3d_cells *cells, const doubl
     const int S = P->npart, n_eta_eff = P->dim3 ? 1 : P->K;
     const int64_t tb = bins->tau_bins, rbn = bins->r_bins;
     const bool diff = opts->include_baryon && opts->include_baryondiff_deltaf;
-    const double *src[25] = {cells->tau, cells->eta, cells->dat, cells->dax, cells->day, cells->dan, cells->ux, cells->uy, cells->un,
-                             cells->T, cells->P, cells->E, cells->pixx, cells->pixy, cells->pixn, cells->piyy, cells->piyn, cells->bulkPi,
-                             diff ? cells->muB : nullptr, diff ? cells->nB : nullptr, diff ? cells->Vx : nullptr,
-                             diff ? cells->Vy : nullptr, diff ? cells->Vn : nullptr, x, y};
+    const auto keep = [diff](int a) { return a < 18 || diff; };
     const size_t sizes[6] = {(size_t)S, (size_t)(S * tb), (size_t)(S * rbn), (size_t)(S * tb * rbn), (size_t)S * n_eta_eff,
                              out->dN_dy_cell ? (size_t)S * n : 0};
     double *host_out[6] = {out->dN_dy, out->dN_taudtaudy, out->dN_twopirdrdy, out->dN_twopitaurdtaudrdy, out->dN_dydeta, out->dN_dy_cell};
@@ -1333,28 +1245,18 @@ extern "C" int is3d_spacetime_distributions(const is3d_cells *cells, const doubl
     size_t total = 0;
     for (size_t s : sizes) total += s;
     DevBuf<double> dcell, dout;
-    HIP_TRY(dcell.alloc((size_t)std::max<int64_t>(n, 1) * 25));
+    HIP_TRY(dcell.alloc((size_t)std::max<int64_t>(n, 1) * (is3d::kCellArrays + 2)));   // the cell arrays, then x and y
     HIP_TRY(dout.alloc(total));
     hipEvent_t e0, e1, e2, e3;
     HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventCreate(&e2)); HIP_TRY(hipEventCreate(&e3));
     struct EvGuard { hipEvent_t e[4]; ~EvGuard() { for (auto v : e) (void)hipEventDestroy(v); } } evg{{e0, e1, e2, e3}};
     HIP_TRY(hipEventRecord(e0, nullptr));
-    const double *dptr[25];
-    for (int a = 0; a < 25; a++) {
-        dptr[a] = nullptr;
-        if (src[a] && n > 0) {
-            HIP_TRY(hipMemcpyAsync(dcell.p + (size_t)a * n, src[a], (size_t)n * sizeof(double), hipMemcpyHostToDevice, nullptr));
-            dptr[a] = dcell.p + (size_t)a * n;
-        }
-    }
+    is3d_cells dc;
+    HIP_TRY(is3d::stage_cells(*cells, keep, 0, n, dcell.p, nullptr, &dc));
+    std::array<const double *, 2> xy = {x, y};
+    HIP_TRY(is3d::stage_arrays(xy, 0, n, dcell.p + (size_t)is3d::kCellArrays * n, nullptr));
     HIP_TRY(hipEventRecord(e1, nullptr));
-    is3d_cells dc{};
-    dc.n_cells = n;
-    dc.tau = dptr[0]; dc.eta = dptr[1]; dc.dat = dptr[2]; dc.dax = dptr[3]; dc.day = dptr[4]; dc.dan = dptr[5];
-    dc.ux = dptr[6]; dc.uy = dptr[7]; dc.un = dptr[8]; dc.T = dptr[9]; dc.P = dptr[10]; dc.E = dptr[11];
-    dc.pixx = dptr[12]; dc.pixy = dptr[13]; dc.pixn = dptr[14]; dc.piyy = dptr[15]; dc.piyn = dptr[16]; dc.bulkPi = dptr[17];
-    dc.muB = dptr[18]; dc.nB = dptr[19]; dc.Vx = dptr[20]; dc.Vy = dptr[21]; dc.Vn = dptr[22];
-    const double *dx = n > 0 ? dptr[23] : dcell.p, *dy = n > 0 ? dptr[24] : dcell.p;
+    const double *dx = n > 0 ? xy[0] : dcell.p, *dy = n > 0 ? xy[1] : dcell.p;
     is3d_spacetime_out dev{};
     double *dev_out[6];
     size_t off = 0;

@@ -38,6 +38,7 @@
 
 #include "../../include/is3d_amd.h"
 #include "cf_device.h"
+#include "cf_host.h"
 #include "cf_math.h"
 #include "errors.h"
 #include "jonah.h"
@@ -636,36 +637,7 @@ cf_sampler_run(SamplerParams p, SamplerSpecies sp, const SamplerCell *__restrict
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-#define SMP_TRY(expr)                                                                                            \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) return is3d::set_error(IS3D_ENODEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevMem {
-    void *p = nullptr;
-    hipError_t alloc(size_t bytes)
-    {
-        release();
-        if (!bytes) return hipSuccess;
-        is3d::count_resource(1);
-        return hipMalloc(&p, bytes);
-    }
-    template <class T>
-    hipError_t upload(const std::vector<T> &h)
-    {
-        hipError_t e = alloc(h.size() * sizeof(T));
-        if (e != hipSuccess || h.empty()) return e;
-        return hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    ~DevMem() { release(); }
-    template <class T> T *as() const { return (T *)p; }
-};
+using DevMem = is3d::DevBuf<unsigned char>;
 
 }  // namespace
 
@@ -729,8 +701,8 @@ extern "C" int is3d_sampler_plan_create(is3d_sampler_plan **out, const is3d_spec
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return set_error(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
     std::unique_ptr<is3d_sampler_plan> P(new is3d_sampler_plan);
     is3d::count_resource(0);
-    if (opts->device >= 0) SMP_TRY(hipSetDevice(opts->device));
-    SMP_TRY(hipGetDevice(&P->device));
+    if (opts->device >= 0) HIP_TRY(hipSetDevice(opts->device));
+    HIP_TRY(hipGetDevice(&P->device));
     P->max_cells = max_cells;
     P->o = *opts;
     P->three_d = opts->dimension == 3;
@@ -756,21 +728,21 @@ extern "C" int is3d_sampler_plan_create(is3d_sampler_plan **out, const is3d_spec
         cls[s] = found;
     }
     const int ncls = (int)cmass.size();
-    SMP_TRY(d_mass.upload(std::vector<double>(species->mass, species->mass + npart)));
-    SMP_TRY(d_sign.upload(std::vector<double>(species->sign, species->sign + npart)));
-    SMP_TRY(d_deg.upload(std::vector<double>(species->degeneracy, species->degeneracy + npart)));
-    SMP_TRY(d_cls.upload(cls));
-    SMP_TRY(d_cmass.upload(cmass));
-    SMP_TRY(d_csign.upload(csign));
+    HIP_TRY(d_mass.upload(std::vector<double>(species->mass, species->mass + npart)));
+    HIP_TRY(d_sign.upload(std::vector<double>(species->sign, species->sign + npart)));
+    HIP_TRY(d_deg.upload(std::vector<double>(species->degeneracy, species->degeneracy + npart)));
+    HIP_TRY(d_cls.upload(cls));
+    HIP_TRY(d_cmass.upload(cmass));
+    HIP_TRY(d_csign.upload(csign));
     std::vector<double> gl((size_t)4 * in->n_gla, 0.0);
     for (int k = 0; k < in->n_gla; k++) {
         gl[k] = in->root1[k]; gl[in->n_gla + k] = in->weight1[k];
         if (fq) { gl[2 * in->n_gla + k] = fq->root2[k]; gl[3 * in->n_gla + k] = fq->weight2[k]; }
     }
-    SMP_TRY(d_gl.upload(gl));
+    HIP_TRY(d_gl.upload(gl));
     if (baryon) {
-        SMP_TRY(d_bar.upload(std::vector<double>(species->baryon, species->baryon + npart)));
-        SMP_TRY(d_cbar.upload(cbar));
+        HIP_TRY(d_bar.upload(std::vector<double>(species->baryon, species->baryon + npart)));
+        HIP_TRY(d_cbar.upload(cbar));
     }
     sp = is3d::SamplerSpecies{d_mass.as<double>(), d_sign.as<double>(), d_deg.as<double>(), d_cls.as<int32_t>(),
                               d_cmass.as<double>(), d_csign.as<double>(), npart, ncls, d_bar.as<double>(), d_cbar.as<double>()};
@@ -779,7 +751,7 @@ extern "C" int is3d_sampler_plan_create(is3d_sampler_plan **out, const is3d_spec
     std::vector<double> xs(df->T, df->T + df->n_T);
     for (int i = 1; i < df->n_T; i++)
         if (!(xs[i] > xs[i - 1])) return set_error(IS3D_EINVAL, "coefficient table temperatures must ascend");
-    SMP_TRY(d_splx.upload(xs));
+    HIP_TRY(d_splx.upload(xs));
     const double *tabs[3] = {nullptr, nullptr, nullptr};
     int nspl;
     if (opts->df_mode == 1) { tabs[0] = df->c0; tabs[1] = df->c2; nspl = 2; }
@@ -789,8 +761,8 @@ extern "C" int is3d_sampler_plan_create(is3d_sampler_plan **out, const is3d_spec
     for (int s = 0; s < nspl; s++) {
         std::vector<double> ys(tabs[s], tabs[s] + df->n_T), cc;
         if (!is3d::natural_cspline_init(xs, ys, cc)) return set_error(IS3D_EINVAL, "spline construction failed");
-        SMP_TRY(d_sply[s].upload(ys));
-        SMP_TRY(d_splc[s].upload(cc));
+        HIP_TRY(d_sply[s].upload(ys));
+        HIP_TRY(d_splc[s].upload(cc));
         p.spl.y[s] = d_sply[s].as<double>();
         p.spl.c[s] = d_splc[s].as<double>();
     }
@@ -798,13 +770,13 @@ extern "C" int is3d_sampler_plan_create(is3d_sampler_plan **out, const is3d_spec
         const double *t5[5];
         if (opts->df_mode == 1) { t5[0] = df->c0; t5[1] = df->c1; t5[2] = df->c2; t5[3] = df->c3; t5[4] = df->c4; }
         else { t5[0] = df->F; t5[1] = df->G; t5[2] = df->betabulk; t5[3] = df->betaV; t5[4] = df->betapi; }
-        SMP_TRY(d_bilT.upload(xs));
-        SMP_TRY(d_bilB.upload(std::vector<double>(df->muB, df->muB + df->n_muB)));
+        HIP_TRY(d_bilT.upload(xs));
+        HIP_TRY(d_bilB.upload(std::vector<double>(df->muB, df->muB + df->n_muB)));
         p.bil.nT = df->n_T; p.bil.nB = df->n_muB;
         p.bil.swap = opts->reference_bilinear_indexing != 0;
         p.bil.T = d_bilT.as<double>(); p.bil.muB = d_bilB.as<double>();
         for (int k = 0; k < 5; k++) {
-            SMP_TRY(d_biltab[k].upload(std::vector<double>(t5[k], t5[k] + (size_t)df->n_T * df->n_muB)));
+            HIP_TRY(d_biltab[k].upload(std::vector<double>(t5[k], t5[k] + (size_t)df->n_T * df->n_muB)));
             p.bil.tab[k] = d_biltab[k].as<double>();
         }
     }
@@ -820,7 +792,7 @@ extern "C" int is3d_sampler_plan_create(is3d_sampler_plan **out, const is3d_spec
             return set_error(IS3D_EINVAL, "df_mode 4: bulkPi/Peq(lambda) is not ascending at T_avg = %.6g GeV (GSL would abort here)", fq->T_avg);
         p.nj = (int)bp.size();
         for (const auto *v : {&bp, &l2, &zz, &cl, &cz}) jon.insert(jon.end(), v->begin(), v->end());
-        SMP_TRY(d_jonah.upload(jon));
+        HIP_TRY(d_jonah.upload(jon));
         p.jx = d_jonah.as<double>(); p.jl2 = p.jx + p.nj; p.jz = p.jx + 2 * p.nj; p.jcl = p.jx + 3 * p.nj; p.jcz = p.jx + 4 * p.nj;
     }
     if (fq) { p.detA_min = fq->deta_min; p.mass_pion0 = fq->mass_pion0; }
@@ -885,8 +857,8 @@ extern "C" int is3d_sampler_plan_create(is3d_sampler_plan **out, const is3d_spec
                 bkd[ip] = (neq + (bnum * J10 * G) + (J20 * F / std::pow(T, 2))) / betabulk;
             }
         }
-        SMP_TRY(d_eqd.upload(eqd));
-        SMP_TRY(d_bkd.upload(bkd));
+        HIP_TRY(d_eqd.upload(eqd));
+        HIP_TRY(d_bkd.upload(bkd));
         p.eqd = d_eqd.as<double>(); p.bkd = d_bkd.as<double>();
         p.T_sw = Tsw;
         if (opts->df_mode == 3 && baryon) {                                            // :862-867 at (Tavg with T_switch, muBavg)
@@ -896,9 +868,9 @@ extern "C" int is3d_sampler_plan_create(is3d_sampler_plan **out, const is3d_spec
         } else if (opts->df_mode == 3) { p.F_avg = spline_at(0, Tsw) * Tsw; p.betabulk_avg = spline_at(1, Tsw) * Tsw * Tsw * Tsw * Tsw; }
     }
     p.y_max = three_d ? 0.5 : in->y_cut;                                              // :837-838
-    SMP_TRY(P->d_status.alloc(8 * sizeof(unsigned long long)));
+    HIP_TRY(P->d_status.alloc(8 * sizeof(unsigned long long)));
     p.status = P->d_status.as<unsigned long long>();
-    for (auto &e : P->ev) SMP_TRY(hipEventCreate(&e));
+    for (auto &e : P->ev) HIP_TRY(hipEventCreate(&e));
     *out = P.release();
     return IS3D_OK;
 }
@@ -907,22 +879,9 @@ namespace {
 // cell-array checks shared by the host and the device entry (pointers are only tested for NULL here)
 int check_cells(const is3d_cells *cells, const is3d_options *o, int64_t first_cell)
 {
-    using is3d::set_error;
     const int64_t n = cells->n_cells;
-    if (n < 0 || n + first_cell > 0xffffffffLL) return set_error(IS3D_EINVAL, "cell indices must fit 32 bits for the counter-based streams");
-    const bool three_d = o->dimension == 3;
-    const bool baryondiff = o->include_baryon != 0 && o->include_baryondiff_deltaf != 0;
-    if (n > 0) {
-        if (!cells->tau || !cells->dat || !cells->dax || !cells->day || !cells->dan || !cells->ux || !cells->uy || !cells->un ||
-            !cells->T || !cells->P || !cells->E || (three_d && !cells->eta))
-            return set_error(IS3D_EINVAL, "a required cell array is NULL");
-        if (o->include_shear_deltaf && (!cells->pixx || !cells->pixy || !cells->pixn || !cells->piyy || !cells->piyn))
-            return set_error(IS3D_EINVAL, "include_shear_deltaf needs pixx, pixy, pixn, piyy, piyn");
-        if (o->include_bulk_deltaf && !cells->bulkPi) return set_error(IS3D_EINVAL, "include_bulk_deltaf needs bulkPi");
-        if (baryondiff && (!cells->muB || !cells->nB || !cells->Vx || !cells->Vy || !cells->Vn))
-            return set_error(IS3D_EINVAL, "include_baryon && include_baryondiff_deltaf need muB, nB, Vx, Vy, Vn");
-    }
-    return IS3D_OK;
+    if (n < 0 || n + first_cell > 0xffffffffLL) return is3d::set_error(IS3D_EINVAL, "cell indices must fit 32 bits for the counter-based streams");
+    return is3d::check_cells(cells, o->dimension == 3, *o, o->include_baryon != 0 && o->include_baryondiff_deltaf != 0);
 }
 // which of the 23 cell arrays (CellPtrs order) the kernels read under these options
 bool cell_array_needed(int a, const is3d_options *o)
@@ -956,118 +915,115 @@ extern "C" int is3d_sampler_plan_execute(is3d_sampler_plan *P, const is3d_cells 
     if (int rc = check_cells(cells, &P->o, first_cell)) return rc;
     const int64_t n = cells->n_cells;
     if (n > P->max_cells) return set_error(IS3D_EINVAL, "%lld cells, the sampler plan was created for %lld", (long long)n, (long long)P->max_cells);
-    SMP_TRY(hipSetDevice(P->device));
+    HIP_TRY(hipSetDevice(P->device));
     if (n == 0) return IS3D_OK;
     const int ncls = P->ncls;
     is3d::SamplerParams &p = P->p;
     const is3d::SamplerSpecies &sp = P->sp;
-    const double *src[23] = {cells->tau, cells->eta, cells->dat, cells->dax, cells->day, cells->dan, cells->ux, cells->uy, cells->un,
-                             cells->T, cells->P, cells->E, cells->pixx, cells->pixy, cells->pixn, cells->piyy, cells->piyn, cells->bulkPi,
-                             cells->muB, cells->nB, cells->Vx, cells->Vy, cells->Vn};
-    const double *dptr[23];
-    for (int a = 0; a < 23; a++) dptr[a] = (src[a] && cell_array_needed(a, &P->o)) ? src[a] : nullptr;
-    p.cells = {dptr[0], dptr[1], dptr[2], dptr[3], dptr[4], dptr[5], dptr[6], dptr[7], dptr[8], dptr[9], dptr[10], dptr[11],
-               dptr[12], dptr[13], dptr[14], dptr[15], dptr[16], dptr[17], dptr[18], dptr[19], dptr[20], dptr[21], dptr[22]};
+    auto arrays = is3d::cell_arrays(*cells);
+    for (int a = 0; a < is3d::kCellArrays; a++)
+        if (!cell_array_needed(a, &P->o)) arrays[a] = nullptr;
+    p.cells = is3d::cell_ptrs(is3d::cells_from_arrays(n, arrays));
     p.x = x_dev; p.y = y_dev;
     p.n_cells = n; p.first_cell = first_cell;
     p.seed = seed;
     p.cdf = nullptr;           // set below, once the workspaces exist
     hipEvent_t *ev = P->ev;
     unsigned long long init[8] = {~0ULL, 0, 0, 0, 0, 0, 0, 0};
-    SMP_TRY(hipMemcpyAsync(P->d_status.p, init, sizeof init, hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(P->d_status.p, init, sizeof init, hipMemcpyHostToDevice, nullptr));
     // ---- workspaces: sized by the largest (cells, event batch) seen so far; a second execute of the same shape allocates nothing ----
     const int64_t max_threads = (int64_t)1 << 25;
     int eb = (int)std::max<int64_t>(1, std::min<int64_t>(n_events, max_threads / n));
     if (batch_events > 0) eb = std::min(eb, batch_events);
     const int64_t bt = (int64_t)eb * n;
     if (n > P->cap_cells) {
-        SMP_TRY(P->d_GT.alloc((size_t)n * ncls * sizeof(double)));
-        if (P->o.df_mode == 3 && !p.fast) SMP_TRY(P->d_GT2.alloc((size_t)n * ncls * sizeof(double)));
-        if (P->o.df_mode == 3 && p.baryon) SMP_TRY(P->d_GT3.alloc((size_t)n * ncls * sizeof(double)));
-        SMP_TRY(P->d_rec.alloc((size_t)n * sizeof(is3d::SamplerCell)));
+        HIP_TRY(P->d_GT.alloc((size_t)n * ncls * sizeof(double)));
+        if (P->o.df_mode == 3 && !p.fast) HIP_TRY(P->d_GT2.alloc((size_t)n * ncls * sizeof(double)));
+        if (P->o.df_mode == 3 && p.baryon) HIP_TRY(P->d_GT3.alloc((size_t)n * ncls * sizeof(double)));
+        HIP_TRY(P->d_rec.alloc((size_t)n * sizeof(is3d::SamplerCell)));
         // running sums of the species weights per cell, one per block of 8 species (312 B per cell for 305 species): df_mode 3's weights may be negative (n_eq + Pi dn_bulk),
         // its sums are not monotone and the species is found by the linear inversion there
-        if (P->o.df_mode != 3) SMP_TRY(P->d_cdf.alloc((size_t)n * ((sp.npart + is3d::kCdfBlock - 1) / is3d::kCdfBlock) * sizeof(double)));
+        if (P->o.df_mode != 3) HIP_TRY(P->d_cdf.alloc((size_t)n * ((sp.npart + is3d::kCdfBlock - 1) / is3d::kCdfBlock) * sizeof(double)));
         P->cap_cells = n;
     }
     if (bt > P->cap_bt) {
-        SMP_TRY(P->d_drawn.alloc((size_t)bt * sizeof(int32_t)));
-        SMP_TRY(P->d_emits.alloc((size_t)bt));
-        SMP_TRY(P->d_active.alloc((size_t)bt * sizeof(int32_t)));
-        SMP_TRY(P->d_nactive.alloc(sizeof(int32_t)));
-        SMP_TRY(P->d_counts.alloc((size_t)(bt + 1) * sizeof(int64_t)));
-        SMP_TRY(P->d_offsets.alloc((size_t)(bt + 1) * sizeof(int64_t)));
+        HIP_TRY(P->d_drawn.alloc((size_t)bt * sizeof(int32_t)));
+        HIP_TRY(P->d_emits.alloc((size_t)bt));
+        HIP_TRY(P->d_active.alloc((size_t)bt * sizeof(int32_t)));
+        HIP_TRY(P->d_nactive.alloc(sizeof(int32_t)));
+        HIP_TRY(P->d_counts.alloc((size_t)(bt + 1) * sizeof(int64_t)));
+        HIP_TRY(P->d_offsets.alloc((size_t)(bt + 1) * sizeof(int64_t)));
         size_t tb = 0, tmp2 = 0;
-        SMP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, P->d_counts.as<int64_t>(), P->d_offsets.as<int64_t>(), (int)(bt + 1), nullptr));
-        SMP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tmp2, hipcub::CountingInputIterator<int32_t>(0), P->d_emits.as<uint8_t>(), P->d_active.as<int32_t>(),
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, P->d_counts.as<int64_t>(), P->d_offsets.as<int64_t>(), (int)(bt + 1), nullptr));
+        HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tmp2, hipcub::CountingInputIterator<int32_t>(0), P->d_emits.as<uint8_t>(), P->d_active.as<int32_t>(),
                                               P->d_nactive.as<int32_t>(), (int)bt, nullptr));
         P->tmp_bytes = std::max(tb, tmp2);
-        SMP_TRY(P->d_scan_tmp.alloc(P->tmp_bytes));
+        HIP_TRY(P->d_scan_tmp.alloc(P->tmp_bytes));
         P->cap_bt = bt;
     }
     p.cdf = P->d_cdf.as<double>();
     DevMem &d_GT = P->d_GT, &d_GT2 = P->d_GT2, &d_GT3 = P->d_GT3, &d_rec = P->d_rec, &d_counts = P->d_counts, &d_offsets = P->d_offsets, &d_scan_tmp = P->d_scan_tmp;
     DevMem &d_drawn = P->d_drawn, &d_emits = P->d_emits, &d_active = P->d_active, &d_nactive = P->d_nactive;
     size_t tmp_bytes = P->tmp_bytes;
-    SMP_TRY(hipEventRecord(ev[1], nullptr));
+    HIP_TRY(hipEventRecord(ev[1], nullptr));
     {
         const int64_t tot = n * ncls;
-        hipLaunchKernelGGL(is3d::cf_sampler_density, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, dptr[9], dptr[18], n, sp,
+        hipLaunchKernelGGL(is3d::cf_sampler_density, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, p.cells.T, p.cells.muB, n, sp,
                            P->d_gl.as<double>(), P->ngla, d_GT.as<double>(), d_GT2.as<double>(), d_GT3.as<double>());
-        SMP_TRY(hipEventRecord(ev[6], nullptr));
+        HIP_TRY(hipEventRecord(ev[6], nullptr));
         hipLaunchKernelGGL(is3d::cf_sampler_cells, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, nullptr, p, sp, d_GT.as<double>(),
                            d_GT2.as<double>(), d_GT3.as<double>(), d_rec.as<is3d::SamplerCell>());
-        SMP_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    SMP_TRY(hipEventRecord(ev[2], nullptr));
+    HIP_TRY(hipEventRecord(ev[2], nullptr));
     // ---- events in batches of <= 2^25 (event, cell) threads: count, scan, fill ----
     int64_t base = 0;
     double ms_count = 0.0, ms_fill = 0.0, ms_poisson = 0.0;
     for (int e0 = 0; e0 < n_events; e0 += eb) {
         const int ne = std::min(eb, n_events - e0);
         const int64_t nt = (int64_t)ne * n;
-        SMP_TRY(hipEventRecord(ev[5], nullptr));
+        HIP_TRY(hipEventRecord(ev[5], nullptr));
         // Poisson numbers of all pairs, then the ordered list of the pairs that emit
         hipLaunchKernelGGL(is3d::cf_sampler_poisson, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, nullptr, p, d_rec.as<is3d::SamplerCell>(), e0, ne,
                            d_drawn.as<int32_t>(), d_emits.as<uint8_t>());
-        SMP_TRY(hipGetLastError());
-        SMP_TRY(hipcub::DeviceSelect::Flagged(d_scan_tmp.p, tmp_bytes, hipcub::CountingInputIterator<int32_t>(0), d_emits.as<uint8_t>(),
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipcub::DeviceSelect::Flagged(d_scan_tmp.p, tmp_bytes, hipcub::CountingInputIterator<int32_t>(0), d_emits.as<uint8_t>(),
                                               d_active.as<int32_t>(), d_nactive.as<int32_t>(), (int)nt, nullptr));
-        SMP_TRY(hipEventRecord(ev[7], nullptr));
+        HIP_TRY(hipEventRecord(ev[7], nullptr));
         int32_t n_active = 0;
-        SMP_TRY(hipMemcpy(&n_active, d_nactive.p, sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&n_active, d_nactive.p, sizeof(int32_t), hipMemcpyDeviceToHost));
         int64_t batch_total = 0;
         if (n_active > 0) {
             const unsigned grid = (unsigned)(((int64_t)n_active + 127) / 128);
-            SMP_TRY(hipMemsetAsync(d_counts.as<int64_t>() + n_active, 0, sizeof(int64_t), nullptr));
+            HIP_TRY(hipMemsetAsync(d_counts.as<int64_t>() + n_active, 0, sizeof(int64_t), nullptr));
             hipLaunchKernelGGL((is3d::cf_sampler_run<false>), dim3(grid), dim3(128), 0, nullptr, p, sp, d_rec.as<is3d::SamplerCell>(),
                                d_GT.as<double>(), d_GT2.as<double>(), d_GT3.as<double>(), e0, d_active.as<int32_t>(), (int64_t)n_active,
                                d_drawn.as<int32_t>(), d_counts.as<int64_t>(), (const int64_t *)nullptr, (int64_t)0, (is3d_particle *)nullptr, (int64_t)0);
-            SMP_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             // element n_active of the scan (counts[n_active] = 0) is the batch total
-            SMP_TRY(hipcub::DeviceScan::ExclusiveSum(d_scan_tmp.p, tmp_bytes, d_counts.as<int64_t>(), d_offsets.as<int64_t>(), n_active + 1, nullptr));
-            SMP_TRY(hipEventRecord(ev[3], nullptr));
-            SMP_TRY(hipMemcpy(&batch_total, d_offsets.as<int64_t>() + n_active, sizeof(int64_t), hipMemcpyDeviceToHost));
+            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_scan_tmp.p, tmp_bytes, d_counts.as<int64_t>(), d_offsets.as<int64_t>(), n_active + 1, nullptr));
+            HIP_TRY(hipEventRecord(ev[3], nullptr));
+            HIP_TRY(hipMemcpy(&batch_total, d_offsets.as<int64_t>() + n_active, sizeof(int64_t), hipMemcpyDeviceToHost));
             if (capacity > 0 && base < capacity && batch_total > 0) {
                 hipLaunchKernelGGL((is3d::cf_sampler_run<true>), dim3(grid), dim3(128), 0, nullptr, p, sp, d_rec.as<is3d::SamplerCell>(),
                                    d_GT.as<double>(), d_GT2.as<double>(), d_GT3.as<double>(), e0, d_active.as<int32_t>(), (int64_t)n_active,
                                    d_drawn.as<int32_t>(), (int64_t *)nullptr, d_offsets.as<int64_t>(), base, particles_dev, capacity);
-                SMP_TRY(hipGetLastError());
+                HIP_TRY(hipGetLastError());
             }
         } else {
-            SMP_TRY(hipEventRecord(ev[3], nullptr));
+            HIP_TRY(hipEventRecord(ev[3], nullptr));
         }
-        SMP_TRY(hipEventRecord(ev[4], nullptr));
-        SMP_TRY(hipEventSynchronize(ev[4]));
+        HIP_TRY(hipEventRecord(ev[4], nullptr));
+        HIP_TRY(hipEventSynchronize(ev[4]));
         float a = 0, b = 0, c = 0;
-        SMP_TRY(hipEventElapsedTime(&a, ev[5], ev[3]));
-        SMP_TRY(hipEventElapsedTime(&b, ev[3], ev[4]));
-        SMP_TRY(hipEventElapsedTime(&c, ev[5], ev[7]));
+        HIP_TRY(hipEventElapsedTime(&a, ev[5], ev[3]));
+        HIP_TRY(hipEventElapsedTime(&b, ev[3], ev[4]));
+        HIP_TRY(hipEventElapsedTime(&c, ev[5], ev[7]));
         ms_count += a; ms_fill += b; ms_poisson += c;
         base += batch_total;
     }
     unsigned long long h[8];
-    SMP_TRY(hipMemcpy(h, P->d_status.p, sizeof h, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h, P->d_status.p, sizeof h, hipMemcpyDeviceToHost));
     *n_particles = base;
     if (stats) {
         float b = 0, dn = 0;
@@ -1118,35 +1074,22 @@ extern "C" int is3d_sample_particles(const is3d_cells *cells, const is3d_species
     if (int rc = check_cells(cells, opts, in->first_cell)) return rc;
     const int64_t n = cells->n_cells;
     if (n == 0) return IS3D_OK;
-    const double *src[23] = {cells->tau, cells->eta, cells->dat, cells->dax, cells->day, cells->dan, cells->ux, cells->uy, cells->un,
-                             cells->T, cells->P, cells->E, cells->pixx, cells->pixy, cells->pixn, cells->piyy, cells->piyn, cells->bulkPi,
-                             cells->muB, cells->nB, cells->Vx, cells->Vy, cells->Vn};
-    DevMem d_cell[23], d_x, d_y, d_particles;
-    const double *dptr[23];
+    is3d::DevBuf<double> d_cells;   // the needed cell arrays, then x and y
+    DevMem d_particles;
+    HIP_TRY(d_cells.alloc((size_t)n * (is3d::kCellArrays + 2)));
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    SMP_TRY(hipEventCreate(&e0));
-    SMP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
     struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{e0, e1};
-    SMP_TRY(hipEventRecord(e0, nullptr));
-    for (int a = 0; a < 23; a++) {
-        dptr[a] = nullptr;
-        if (src[a] && cell_array_needed(a, opts)) {
-            SMP_TRY(d_cell[a].alloc((size_t)n * sizeof(double)));
-            SMP_TRY(hipMemcpyAsync(d_cell[a].p, src[a], (size_t)n * sizeof(double), hipMemcpyHostToDevice, nullptr));
-            dptr[a] = d_cell[a].as<double>();
-        }
-    }
-    if (in->x) { SMP_TRY(d_x.alloc((size_t)n * sizeof(double))); SMP_TRY(hipMemcpyAsync(d_x.p, in->x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, nullptr)); }
-    if (in->y) { SMP_TRY(d_y.alloc((size_t)n * sizeof(double))); SMP_TRY(hipMemcpyAsync(d_y.p, in->y, (size_t)n * sizeof(double), hipMemcpyHostToDevice, nullptr)); }
-    SMP_TRY(hipEventRecord(e1, nullptr));
-    is3d_cells dc{};
-    dc.n_cells = n;
-    dc.tau = dptr[0]; dc.eta = dptr[1]; dc.dat = dptr[2]; dc.dax = dptr[3]; dc.day = dptr[4]; dc.dan = dptr[5]; dc.ux = dptr[6]; dc.uy = dptr[7]; dc.un = dptr[8];
-    dc.T = dptr[9]; dc.P = dptr[10]; dc.E = dptr[11]; dc.pixx = dptr[12]; dc.pixy = dptr[13]; dc.pixn = dptr[14]; dc.piyy = dptr[15]; dc.piyn = dptr[16];
-    dc.bulkPi = dptr[17]; dc.muB = dptr[18]; dc.nB = dptr[19]; dc.Vx = dptr[20]; dc.Vy = dptr[21]; dc.Vn = dptr[22];
-    if (capacity > 0) SMP_TRY(d_particles.alloc((size_t)capacity * sizeof(is3d_particle)));
+    HIP_TRY(hipEventRecord(e0, nullptr));
+    is3d_cells dc;
+    HIP_TRY(is3d::stage_cells(*cells, [opts](int a) { return cell_array_needed(a, opts); }, 0, n, d_cells.p, nullptr, &dc));
+    std::array<const double *, 2> xy = {in->x, in->y};
+    HIP_TRY(is3d::stage_arrays(xy, 0, n, d_cells.p + (size_t)is3d::kCellArrays * n, nullptr));
+    HIP_TRY(hipEventRecord(e1, nullptr));
+    if (capacity > 0) HIP_TRY(d_particles.alloc((size_t)capacity * sizeof(is3d_particle)));
     int64_t total = 0;
-    const int rc = is3d_sampler_plan_execute(P, &dc, d_x.as<double>(), d_y.as<double>(), in->n_events, in->seed, in->first_cell, in->batch_events,
+    const int rc = is3d_sampler_plan_execute(P, &dc, xy[0], xy[1], in->n_events, in->seed, in->first_cell, in->batch_events,
                                              d_particles.as<is3d_particle>(), capacity, &total, stats);
     *n_particles = total;
     if (stats) {
@@ -1157,7 +1100,7 @@ extern "C" int is3d_sample_particles(const is3d_cells *cells, const is3d_species
     if (rc && rc != IS3D_ENOMEM) return rc;
     const std::string kept = rc ? is3d_last_error() : "";
     const int64_t ncopy = std::min<int64_t>(total, capacity);
-    if (ncopy > 0) SMP_TRY(hipMemcpy(particles, d_particles.p, (size_t)ncopy * sizeof(is3d_particle), hipMemcpyDeviceToHost));
+    if (ncopy > 0) HIP_TRY(hipMemcpy(particles, d_particles.p, (size_t)ncopy * sizeof(is3d_particle), hipMemcpyDeviceToHost));
     if (rc) return set_error(rc, "%s", kept.c_str());
     return IS3D_OK;
 }

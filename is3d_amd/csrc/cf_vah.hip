@@ -30,6 +30,7 @@
 
 #include "../../include/is3d_amd.h"
 #include "cf_device.h"
+#include "cf_host.h"
 #include "cf_launch.h"
 #include "cf_math.h"
 #include "errors.h"
@@ -735,40 +736,7 @@ __global__ void __launch_bounds__(256) cf_vah_coeffs(VahCoefArgs a)
 
 namespace {
 
-#define VAH_TRY(expr)                                                                                            \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) return is3d::set_error(IS3D_ENODEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevMem {
-    void *p = nullptr;
-    size_t bytes = 0;
-    hipError_t alloc(size_t b)
-    {
-        release();
-        bytes = b;
-        if (!b) return hipSuccess;
-        is3d::count_resource(1);
-        return hipMalloc(&p, b);
-    }
-    template <class T>
-    hipError_t upload(const std::vector<T> &h)
-    {
-        hipError_t e = alloc(h.size() * sizeof(T));
-        if (e != hipSuccess || h.empty()) return e;
-        return hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-    }
-    hipError_t upload(const double *h, size_t n)
-    {
-        hipError_t e = alloc(n * sizeof(double));
-        if (e != hipSuccess || !n) return e;
-        return hipMemcpy(p, h, n * sizeof(double), hipMemcpyHostToDevice);
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    ~DevMem() { release(); }
-    template <class T> T *as() const { return (T *)p; }
-};
+using DevMem = is3d::DevBuf<unsigned char>;
 
 constexpr int kJT3 = 6, kR3 = 7, kJT2 = 8, kR2 = 61;   // the round-1 kernel's tile shapes (kernel variant 2; 2+1D always)
 constexpr int kJT3F = 8, kR3F = 7;                       // cf_main_vah3 (3+1D default, kernel variant 3)
@@ -824,9 +792,9 @@ struct TabDev {
         std::vector<double> all(5 * n);
         const double *src[5] = {t->c0, t->c1, t->c2, t->c3, t->c4};
         for (int k = 0; k < 5; k++) memcpy(all.data() + k * n, src[k], n * sizeof(double));
-        VAH_TRY(L.upload(t->L, (size_t)nL));
-        VAH_TRY(aL.upload(t->aL, (size_t)naL));
-        VAH_TRY(c.upload(all));
+        HIP_TRY(L.upload(t->L, (size_t)nL));
+        HIP_TRY(aL.upload(t->aL, (size_t)naL));
+        HIP_TRY(c.upload(all));
         return IS3D_OK;
     }
     void fill(is3d::VahCoefArgs &a) const
@@ -883,8 +851,8 @@ extern "C" int is3d_vah_plan_create(is3d_vah_plan **out, const is3d_species *sp,
     std::unique_ptr<is3d_vah_plan> P(new is3d_vah_plan);
     is3d::count_resource(0);
     P->o = *o;
-    if (o->device >= 0) VAH_TRY(hipSetDevice(o->device));
-    VAH_TRY(hipGetDevice(&P->device));
+    if (o->device >= 0) HIP_TRY(hipSetDevice(o->device));
+    HIP_TRY(hipGetDevice(&P->device));
     P->three_d = three_d;
     P->max_cells = max_cells;
 
@@ -941,19 +909,19 @@ extern "C" int is3d_vah_plan_create(is3d_vah_plan **out, const is3d_species *sp,
     }
     for (int s = 0; s < npart; s++)
         for (int i = 0; i < npT; i++) lane_sp[(size_t)s * npT + i] = slot_of[cls[s] * npT + i];
-    VAH_TRY(P->d_lane_sub.upload(lsub));
+    HIP_TRY(P->d_lane_sub.upload(lsub));
     std::vector<double> cosphi(J), sinphi(J), kgrid(K), kweight(K, 1.0), deg(sp->degeneracy, sp->degeneracy + npart);
     for (int j = 0; j < J; j++) { cosphi[j] = std::cos(gr->phi[j]); sinphi[j] = std::sin(gr->phi[j]); }
     for (int k = 0; k < K; k++) {
         kgrid[k] = three_d ? gr->y[k] : gr->eta[k];
         if (!three_d) kweight[k] = gr->eta_w[k] * (gr->eta[1] - gr->eta[0]);          // :2178-2187
     }
-    VAH_TRY(P->d_mT.upload(mT)); VAH_TRY(P->d_pT.upload(pT)); VAH_TRY(P->d_sg.upload(sg)); VAH_TRY(P->d_lane.upload(lane_sp)); VAH_TRY(P->d_deg.upload(deg));
-    VAH_TRY(P->d_cos.upload(cosphi)); VAH_TRY(P->d_sin.upload(sinphi)); VAH_TRY(P->d_kg.upload(kgrid)); VAH_TRY(P->d_kw.upload(kweight));
+    HIP_TRY(P->d_mT.upload(mT)); HIP_TRY(P->d_pT.upload(pT)); HIP_TRY(P->d_sg.upload(sg)); HIP_TRY(P->d_lane.upload(lane_sp)); HIP_TRY(P->d_deg.upload(deg));
+    HIP_TRY(P->d_cos.upload(cosphi)); HIP_TRY(P->d_sin.upload(sinphi)); HIP_TRY(P->d_kg.upload(kgrid)); HIP_TRY(P->d_kw.upload(kweight));
     if (tab) {
         if (int rc = P->tab.upload(tab)) return rc;
         P->tables = true;
-        VAH_TRY(P->d_coef.alloc(sizeof(double) * 5 * (size_t)max_cells));
+        HIP_TRY(P->d_coef.alloc(sizeof(double) * 5 * (size_t)max_cells));
     }
     for (int s2 = 0; s2 < L; s2++) { P->mTmax = std::max(P->mTmax, mT[s2]); P->pTmax = std::max(P->pTmax, pT[s2]); }
     P->ktiles = three_d ? P->rblocks : 1; P->upc = three_d ? 1 : P->rblocks;
@@ -992,13 +960,13 @@ extern "C" int is3d_vah_plan_create(is3d_vah_plan **out, const is3d_species *sp,
         }
         if (e != hipSuccess) return set_error(IS3D_ENODEVICE, "hipMalloc failed: %s", hipGetErrorString(e));
     }
-    VAH_TRY(P->d_status.alloc(8 * sizeof(unsigned long long)));
+    HIP_TRY(P->d_status.alloc(8 * sizeof(unsigned long long)));
     *out = P.release();
     return IS3D_OK;
 }
 
 extern "C" int64_t is3d_vah_plan_output_size(const is3d_vah_plan *P) { return P ? P->nout : 0; }
-extern "C" int64_t is3d_vah_plan_workspace_bytes(const is3d_vah_plan *P) { return P ? (int64_t)(P->d_TS.bytes + P->d_partial.bytes + P->d_coef.bytes) : 0; }
+extern "C" int64_t is3d_vah_plan_workspace_bytes(const is3d_vah_plan *P) { return P ? (int64_t)(P->d_TS.n + P->d_partial.n + P->d_coef.n) : 0; }
 extern "C" int is3d_vah_plan_set_timing(is3d_vah_plan *P, int32_t enable)
 {
     if (!P) return is3d::set_error(IS3D_EINVAL, "null plan");
@@ -1026,30 +994,24 @@ extern "C" int is3d_vah_plan_execute(is3d_vah_plan *P, const is3d_vah_cells *cel
     if (status) { memset(status, 0, sizeof *status); status->bad_cell = -1; status->n_classes = P->ncls; }
     const int64_t n = cells->n_cells;
     if (n < 0 || n > P->max_cells) return set_error(IS3D_EINVAL, "n_cells = %lld exceeds the plan's max_cells = %lld", (long long)n, (long long)P->max_cells);
-    const double *src[30] = {cells->tau, cells->eta, cells->ux, cells->uy, cells->un, cells->dat, cells->dax, cells->day, cells->dan, cells->T,
-                             cells->pitt, cells->pitx, cells->pity, cells->pitn, cells->pixx, cells->pixy, cells->pixn, cells->piyy, cells->piyn,
-                             cells->pinn, cells->bulkPi, cells->Wx, cells->Wy, cells->Lambda, cells->aL, cells->c0, cells->c1, cells->c2,
-                             cells->c3, cells->c4};
-    if (n > 0)
-        for (int a = 0; a < 30; a++)
-            if (!src[a] && !(a == 1 && !P->three_d) && a != 9 && !(a >= 25 && P->tables))
-                return set_error(IS3D_EINVAL, "a required VAH cell array is NULL (index %d)", a);
+    if (int rc = is3d::check_vah_cells(cells, P->three_d, P->tables)) return rc;
+    const auto src = is3d::cell_arrays(*cells);
     hipStream_t st = (hipStream_t)hip_stream;
-    VAH_TRY(hipSetDevice(P->device));
+    HIP_TRY(hipSetDevice(P->device));
     const is3d_options &o = P->o;
     const int npasses = n == 0 ? 0 : (int)((n + P->pass_cells - 1) / P->pass_cells);
     if (P->timing)
         while (P->ev.size() < (size_t)npasses * 3 + 1) {
             hipEvent_t e;
-            VAH_TRY(hipEventCreate(&e));
+            HIP_TRY(hipEventCreate(&e));
             P->ev.push_back(e);
         }
     P->last_passes = npasses;
     unsigned long long init[8] = {~0ULL, 0, 0, 0, 0, 0, 0, ~0ULL};
     unsigned long long *d_st = P->d_status.as<unsigned long long>();
-    VAH_TRY(hipMemcpyAsync(d_st, init, sizeof init, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_st, init, sizeof init, hipMemcpyHostToDevice, st));
     if (n == 0) {
-        if (!o.accumulate) VAH_TRY(hipMemsetAsync(dN_out, 0, (size_t)P->nout * sizeof(double), st));
+        if (!o.accumulate) HIP_TRY(hipMemsetAsync(dN_out, 0, (size_t)P->nout * sizeof(double), st));
     }
     int nch = (int)std::max<int64_t>(1, std::min<int64_t>(P->nch, std::min<int64_t>(n, P->pass_cells) / 64));
     // tapered tail of the cell partition as in cf_plan.cpp (cf_device.h: chunk_cells, chunk_taper)
@@ -1059,7 +1021,7 @@ extern "C" int is3d_vah_plan_execute(is3d_vah_plan *P, const is3d_vah_cells *cel
         const int32_t nc = (int32_t)std::min<int64_t>(P->pass_cells, n - c0);
         const double *q[30];
         for (int a = 0; a < 30; a++) q[a] = src[a] ? src[a] + c0 : nullptr;
-        if (P->timing) VAH_TRY(hipEventRecord(P->ev[pass * 3 + 0], st));
+        if (P->timing) HIP_TRY(hipEventRecord(P->ev[pass * 3 + 0], st));
         if (P->tables) {
             is3d::VahCoefArgs ca{};
             ca.n = nc; ca.Lambda = q[23]; ca.aL = q[24];
@@ -1068,7 +1030,7 @@ extern "C" int is3d_vah_plan_execute(is3d_vah_plan *P, const is3d_vah_cells *cel
             ca.status = d_st;
             ca.cell0 = c0;
             hipLaunchKernelGGL(is3d::cf_vah_coeffs, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, st, ca);
-            VAH_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
         is3d::VahPrepParams pp{};
         pp.cells = {q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8], q[10], q[11], q[12], q[13], q[14], q[15], q[16], q[17], q[18], q[19],
@@ -1082,8 +1044,8 @@ extern "C" int is3d_vah_plan_execute(is3d_vah_plan *P, const is3d_vah_cells *cel
         const int nbatch = (nc + cb - 1) / cb;
         if (cb == is3d::kVahCB3) hipLaunchKernelGGL(is3d::cf_prep_vah<is3d::kVahCB3>, dim3(std::min(nbatch, 4096)), dim3(is3d::kVahThreads), P->lds_prep, st, pp);
         else hipLaunchKernelGGL(is3d::cf_prep_vah<is3d::kVahCB>, dim3(std::min(nbatch, 4096)), dim3(is3d::kVahThreads), P->lds_prep, st, pp);
-        VAH_TRY(hipGetLastError());
-        if (P->timing) VAH_TRY(hipEventRecord(P->ev[pass * 3 + 1], st));
+        HIP_TRY(hipGetLastError());
+        if (P->timing) HIP_TRY(hipEventRecord(P->ev[pass * 3 + 1], st));
         is3d::MainGeom g{};
         g.n_cells = nc; g.J = P->J; g.K = P->K; g.Lpad = P->Lpad; g.wpb = P->wpb; g.G = (P->Lpad / 64 + P->wpb - 1) / P->wpb;
         g.jtiles = P->jtiles; g.ktiles = P->ktiles; g.nch = nch; g.nch_small = nch_small; g.NT = P->jtiles * P->ktiles * nch; g.Kacc = P->Kacc;
@@ -1094,18 +1056,18 @@ extern "C" int is3d_vah_plan_execute(is3d_vah_plan *P, const is3d_vah_cells *cel
         else if (P->three_d) launch_vah<true>(o.regulate_deltaf != 0, P->d_TS.as<double>(), P->d_mT.as<double>(), P->d_pT.as<double>(), P->d_sg.as<double>(), P->d_partial.as<double>(), d_st, g, st);
         else launch_vah<false>(o.regulate_deltaf != 0, P->d_TS.as<double>(), P->d_mT.as<double>(), P->d_pT.as<double>(), P->d_sg.as<double>(), P->d_partial.as<double>(), d_st, g, st);
 #endif
-        VAH_TRY(hipGetLastError());
-        if (P->timing) VAH_TRY(hipEventRecord(P->ev[pass * 3 + 2], st));
+        HIP_TRY(hipGetLastError());
+        if (P->timing) HIP_TRY(hipEventRecord(P->ev[pass * 3 + 2], st));
         // each pass finalises into the output (accumulating after the first): the partial slots are rewritten per pass
         const double prefactor = 1.0 / (8.0 * (M_PI * M_PI * M_PI)) / is3d::kHbarC / is3d::kHbarC / is3d::kHbarC;   // :2147
-        VAH_TRY(is3d::launch_finalize(P->d_partial.as<double>(), P->d_lane.as<int>(), P->d_deg.as<double>(), dN_out, P->nout, P->npart, P->npT, P->J,
+        HIP_TRY(is3d::launch_finalize(P->d_partial.as<double>(), P->d_lane.as<int>(), P->d_deg.as<double>(), dN_out, P->nout, P->npart, P->npT, P->J,
                                       P->Kacc, P->Lpad, nch, prefactor, (pass > 0 || o.accumulate) ? 1 : 0, nullptr, st, P->split, P->Lbins));
     }
-    if (P->timing && npasses) VAH_TRY(hipEventRecord(P->ev[npasses * 3], st));
+    if (P->timing && npasses) HIP_TRY(hipEventRecord(P->ev[npasses * 3], st));
     if (status) {
         unsigned long long h[8];
-        VAH_TRY(hipMemcpyAsync(h, d_st, sizeof h, hipMemcpyDeviceToHost, st));
-        VAH_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(h, d_st, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         status->n_passes = npasses;
         status->kernel_variant = P->fact ? 3 : 2;
         status->n_wave_rows = (int64_t)h[2];
@@ -1131,13 +1093,13 @@ extern "C" int is3d_vah_plan_timings(is3d_vah_plan *P, is3d_status *status)
     if (!P || !status) return is3d::set_error(IS3D_EINVAL, "null argument");
     status->ms_prep = status->ms_main = status->ms_finalize = 0.0;
     if (!P->timing || P->last_passes == 0) return IS3D_OK;
-    VAH_TRY(hipSetDevice(P->device));
-    VAH_TRY(hipEventSynchronize(P->ev[P->last_passes * 3]));
+    HIP_TRY(hipSetDevice(P->device));
+    HIP_TRY(hipEventSynchronize(P->ev[P->last_passes * 3]));
     for (int pass = 0; pass < P->last_passes; pass++) {
         float a = 0, b = 0, c = 0;
-        VAH_TRY(hipEventElapsedTime(&a, P->ev[pass * 3 + 0], P->ev[pass * 3 + 1]));
-        VAH_TRY(hipEventElapsedTime(&b, P->ev[pass * 3 + 1], P->ev[pass * 3 + 2]));
-        VAH_TRY(hipEventElapsedTime(&c, P->ev[pass * 3 + 2], P->ev[pass * 3 + 3]));   // the next pass's start, or the closing event
+        HIP_TRY(hipEventElapsedTime(&a, P->ev[pass * 3 + 0], P->ev[pass * 3 + 1]));
+        HIP_TRY(hipEventElapsedTime(&b, P->ev[pass * 3 + 1], P->ev[pass * 3 + 2]));
+        HIP_TRY(hipEventElapsedTime(&c, P->ev[pass * 3 + 2], P->ev[pass * 3 + 3]));   // the next pass's start, or the closing event
         status->ms_prep += a; status->ms_main += b; status->ms_finalize += c;
     }
     status->n_passes = P->last_passes;
@@ -1156,28 +1118,28 @@ extern "C" int is3d_vah_coefficients(const is3d_vah_df_tables *tab, int64_t n, c
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return set_error(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
     if (n == 0) return IS3D_OK;
-    if (device >= 0) VAH_TRY(hipSetDevice(device));
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
     TabDev td;
     if (int rc = td.upload(tab)) return rc;
     DevMem d_in, d_out, d_st;
-    VAH_TRY(d_in.alloc(sizeof(double) * 2 * (size_t)n));
-    VAH_TRY(d_out.alloc(sizeof(double) * 5 * (size_t)n));
-    VAH_TRY(d_st.alloc(sizeof(unsigned long long)));
+    HIP_TRY(d_in.alloc(sizeof(double) * 2 * (size_t)n));
+    HIP_TRY(d_out.alloc(sizeof(double) * 5 * (size_t)n));
+    HIP_TRY(d_st.alloc(sizeof(unsigned long long)));
     const unsigned long long init = ~0ULL;
-    VAH_TRY(hipMemcpy(d_st.p, &init, sizeof init, hipMemcpyHostToDevice));
-    VAH_TRY(hipMemcpy(d_in.p, Lambda, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    VAH_TRY(hipMemcpy(d_in.as<double>() + n, aL, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_st.p, &init, sizeof init, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_in.p, Lambda, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_in.as<double>() + n, aL, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
     is3d::VahCoefArgs ca{};
     ca.n = n; ca.Lambda = d_in.as<double>(); ca.aL = d_in.as<double>() + n;
     td.fill(ca);
     for (int k = 0; k < 5; k++) ca.out[k] = d_out.as<double>() + (size_t)k * n;
     ca.status = d_st.as<unsigned long long>();
     hipLaunchKernelGGL(is3d::cf_vah_coeffs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, ca);
-    VAH_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     double *dst[5] = {c0, c1, c2, c3, c4};
-    for (int k = 0; k < 5; k++) VAH_TRY(hipMemcpy(dst[k], ca.out[k], sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 5; k++) HIP_TRY(hipMemcpy(dst[k], ca.out[k], sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
     unsigned long long bad = ~0ULL;
-    VAH_TRY(hipMemcpy(&bad, d_st.p, sizeof bad, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&bad, d_st.p, sizeof bad, hipMemcpyDeviceToHost));
     if (bad != ~0ULL) {
         if (bad_cell) *bad_cell = (int64_t)bad;
         return set_error(IS3D_EDOMAIN, "cell %llu: (Lambda, alpha_L) beyond the last node of the VAH coefficient tables (the reference leaves the "
@@ -1198,35 +1160,17 @@ extern "C" int is3d_smooth_spectra_vah_df(const is3d_vah_cells *cells, const is3
     if (int rc = is3d_vah_plan_create(&P, sp, gr, tab, o, std::max<int64_t>(n, 1))) return rc;
     struct Guard { is3d_vah_plan *p; ~Guard() { is3d_vah_plan_destroy(p); } } guard{P};
     (void)is3d_vah_plan_set_timing(P, 1);
-    const double *src[30] = {cells->tau, cells->eta, cells->ux, cells->uy, cells->un, cells->dat, cells->dax, cells->day, cells->dan, cells->T,
-                             cells->pitt, cells->pitx, cells->pity, cells->pitn, cells->pixx, cells->pixy, cells->pixn, cells->piyy, cells->piyn,
-                             cells->pinn, cells->bulkPi, cells->Wx, cells->Wy, cells->Lambda, cells->aL, cells->c0, cells->c1, cells->c2,
-                             cells->c3, cells->c4};
-    if (n > 0)
-        for (int a = 0; a < 30; a++)
-            if (!src[a] && !(a == 1 && o->dimension == 2) && a != 9 && !(a >= 25 && tab)) return set_error(IS3D_EINVAL, "a required VAH cell array is NULL (index %d)", a);
+    if (int rc = is3d::check_vah_cells(cells, o->dimension != 2, tab != nullptr)) return rc;
     DevMem d_cell, d_out;
-    VAH_TRY(d_cell.alloc(sizeof(double) * 30 * (size_t)std::max<int64_t>(n, 1)));
-    VAH_TRY(d_out.alloc(sizeof(double) * (size_t)P->nout));
-    const double *dp[30];
-    for (int a = 0; a < 30; a++) {
-        dp[a] = nullptr;
-        if (src[a] && a != 9 && !(a >= 25 && tab) && n > 0) {
-            VAH_TRY(hipMemcpyAsync(d_cell.as<double>() + (size_t)a * n, src[a], (size_t)n * sizeof(double), hipMemcpyHostToDevice, nullptr));
-            dp[a] = d_cell.as<double>() + (size_t)a * n;
-        }
-    }
-    if (o->accumulate) VAH_TRY(hipMemcpyAsync(d_out.p, dN_out, (size_t)P->nout * sizeof(double), hipMemcpyHostToDevice, nullptr));
-    is3d_vah_cells dc{};
-    dc.n_cells = n;
-    dc.tau = dp[0]; dc.eta = dp[1]; dc.ux = dp[2]; dc.uy = dp[3]; dc.un = dp[4]; dc.dat = dp[5]; dc.dax = dp[6]; dc.day = dp[7]; dc.dan = dp[8];
-    dc.T = nullptr; dc.pitt = dp[10]; dc.pitx = dp[11]; dc.pity = dp[12]; dc.pitn = dp[13]; dc.pixx = dp[14]; dc.pixy = dp[15]; dc.pixn = dp[16];
-    dc.piyy = dp[17]; dc.piyn = dp[18]; dc.pinn = dp[19]; dc.bulkPi = dp[20]; dc.Wx = dp[21]; dc.Wy = dp[22]; dc.Lambda = dp[23]; dc.aL = dp[24];
-    dc.c0 = dp[25]; dc.c1 = dp[26]; dc.c2 = dp[27]; dc.c3 = dp[28]; dc.c4 = dp[29];
+    HIP_TRY(d_cell.alloc(sizeof(double) * is3d::kVahCellArrays * (size_t)std::max<int64_t>(n, 1)));
+    HIP_TRY(d_out.alloc(sizeof(double) * (size_t)P->nout));
+    is3d_vah_cells dc;   // T is not read; c0..c4 come from the tables when they are given
+    HIP_TRY(is3d::stage_cells(*cells, [tab](int a) { return a != 9 && !(a >= 25 && tab); }, 0, n, d_cell.as<double>(), nullptr, &dc));
+    if (o->accumulate) HIP_TRY(hipMemcpyAsync(d_out.p, dN_out, (size_t)P->nout * sizeof(double), hipMemcpyHostToDevice, nullptr));
     is3d_status st{};
     const int rc = is3d_vah_plan_execute(P, &dc, d_out.as<double>(), nullptr, &st);
     if (rc) { if (status) *status = st; return rc; }
-    VAH_TRY(hipMemcpy(dN_out, d_out.p, (size_t)P->nout * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dN_out, d_out.p, (size_t)P->nout * sizeof(double), hipMemcpyDeviceToHost));
     is3d_status t{};
     (void)is3d_vah_plan_timings(P, &t);
     st.ms_prep = t.ms_prep; st.ms_main = t.ms_main; st.ms_finalize = t.ms_finalize;

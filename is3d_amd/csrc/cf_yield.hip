@@ -18,6 +18,7 @@
 
 #include "../../include/is3d_amd.h"
 #include "cf_device.h"
+#include "cf_host.h"
 #include "cf_math.h"
 #include "errors.h"
 #include "jonah.h"
@@ -102,31 +103,7 @@ __global__ void __launch_bounds__(256) cf_yield_cells(YieldParams p)
 
 namespace {
 
-#define YLD_TRY(expr)                                                                                            \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) return is3d::set_error(IS3D_ENODEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevMem {
-    void *p = nullptr;
-    hipError_t alloc(size_t bytes)
-    {
-        release();
-        if (!bytes) return hipSuccess;
-        is3d::count_resource(1);
-        return hipMalloc(&p, bytes);
-    }
-    hipError_t upload(const void *h, size_t bytes)
-    {
-        hipError_t e = alloc(bytes);
-        if (e != hipSuccess || !bytes) return e;
-        return hipMemcpy(p, h, bytes, hipMemcpyHostToDevice);
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-    ~DevMem() { release(); }
-    template <class T> T *as() const { return (T *)p; }
-};
+using DevMem = is3d::DevBuf<unsigned char>;
 
 // gsl_spline_eval on a host table (the reference evaluates the df coefficients at the surface averages once per run)
 bool host_spline_at(const std::vector<double> &xs, const double *tab, double xq, double *out)
@@ -191,7 +168,7 @@ extern "C" int is3d_total_yield(const is3d_cells *cells, const is3d_species *spe
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return set_error(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
-    if (opts->device >= 0) YLD_TRY(hipSetDevice(opts->device));
+    if (opts->device >= 0) HIP_TRY(hipSetDevice(opts->device));
 
     // ---- Deltaf_Data::compute_particle_densities at the averages (deltafReader.cpp:536-650) ----
     const int npart = species->n;
@@ -278,18 +255,14 @@ extern "C" int is3d_total_yield(const is3d_cells *cells, const is3d_species *spe
     if (n == 0) return IS3D_OK;
 
     // ---- per-cell weights on the device ----
-    DevMem d_cell[16], d_jx, d_jz, d_jcz, d_partial, d_status;
-    const double *src[16] = {cells->tau, cells->dat, cells->dax, cells->day, cells->dan, cells->ux, cells->uy, cells->un, cells->T, cells->P,
-                             opts->include_bulk_deltaf ? cells->bulkPi : nullptr, baryondiff ? cells->muB : nullptr,
-                             baryondiff ? cells->Vx : nullptr, baryondiff ? cells->Vy : nullptr, baryondiff ? cells->Vn : nullptr, nullptr};
-    const double *dp[16];
-    for (int a = 0; a < 16; a++) {
-        dp[a] = nullptr;
-        if (src[a]) { YLD_TRY(d_cell[a].upload(src[a], (size_t)n * sizeof(double))); dp[a] = d_cell[a].as<double>(); }
-    }
-    p.cells.tau = dp[0]; p.cells.dat = dp[1]; p.cells.dax = dp[2]; p.cells.day = dp[3]; p.cells.dan = dp[4];
-    p.cells.ux = dp[5]; p.cells.uy = dp[6]; p.cells.un = dp[7]; p.cells.T = dp[8]; p.cells.P = dp[9]; p.cells.bulkPi = dp[10];
-    p.cells.muB = dp[11]; p.cells.Vx = dp[12]; p.cells.Vy = dp[13]; p.cells.Vn = dp[14];
+    is3d::DevBuf<double> d_cells;
+    DevMem d_jx, d_jz, d_jcz, d_partial, d_status;
+    HIP_TRY(d_cells.alloc((size_t)n * is3d::kCellArrays));
+    // tau, dsigma, u, T, P; bulkPi with include_bulk_deltaf; muB and V with baryon diffusion (include/is3d_amd.h order)
+    const auto keep = [&](int a) { return a == 0 || (a >= 2 && a <= 10) || (a == 17 && opts->include_bulk_deltaf) || (baryondiff && (a == 18 || a >= 20)); };
+    is3d_cells dc;
+    HIP_TRY(is3d::stage_cells(*cells, keep, 0, n, d_cells.p, nullptr, &dc));
+    p.cells = is3d::cell_ptrs(dc);
     p.n_cells = n; p.df_mode = mode; p.include_bulk = opts->include_bulk_deltaf != 0; p.baryon = baryon; p.baryondiff = baryondiff;
     p.T_lo = xs.front(); p.T_hi = xs.back(); p.dT = std::fabs(xs[1] - xs[0]); p.nT = df->n_T;
     if (baryon) { p.B_lo = df->muB[0]; p.dB = std::fabs(df->muB[1] - df->muB[0]); p.nB = df->n_muB; p.swap = opts->reference_bilinear_indexing != 0; }
@@ -299,21 +272,21 @@ extern "C" int is3d_total_yield(const is3d_cells *cells, const is3d_species *spe
         if (!is3d::natural_cspline_init(bp, zz, cz))
             return set_error(IS3D_EINVAL, "df_mode 4: bulkPi/Peq(lambda) is not ascending at T_avg = %.6g GeV (GSL would abort here)", fq->T_avg);
         p.nj = (int)bp.size();
-        YLD_TRY(d_jx.upload(bp.data(), bp.size() * sizeof(double)));
-        YLD_TRY(d_jz.upload(zz.data(), zz.size() * sizeof(double)));
-        YLD_TRY(d_jcz.upload(cz.data(), cz.size() * sizeof(double)));
+        HIP_TRY(d_jx.upload(bp));
+        HIP_TRY(d_jz.upload(zz));
+        HIP_TRY(d_jcz.upload(cz));
         p.jx = d_jx.as<double>(); p.jz = d_jz.as<double>(); p.jcz = d_jcz.as<double>();
     }
     const int grid = (int)std::min<int64_t>((n + 255) / 256, 1024);
-    YLD_TRY(d_partial.alloc((size_t)grid * sizeof(double)));
+    HIP_TRY(d_partial.alloc((size_t)grid * sizeof(double)));
     unsigned long long st0 = ~0ULL;
-    YLD_TRY(d_status.upload(&st0, sizeof st0));
+    HIP_TRY(d_status.upload(&st0, 1));
     p.partial = d_partial.as<double>(); p.status = d_status.as<unsigned long long>();
     hipLaunchKernelGGL(is3d::cf_yield_cells, dim3(grid), dim3(256), 0, nullptr, p);
-    YLD_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     std::vector<double> part(grid);
-    YLD_TRY(hipMemcpy(part.data(), d_partial.p, (size_t)grid * sizeof(double), hipMemcpyDeviceToHost));
-    YLD_TRY(hipMemcpy(&st0, d_status.p, sizeof st0, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(part.data(), d_partial.p, (size_t)grid * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&st0, d_status.p, sizeof st0, hipMemcpyDeviceToHost));
     if (st0 != ~0ULL)
         return set_error(IS3D_EDOMAIN, "cell %llu: T%s outside the coefficient table (the reference aborts in evaluate_df_coefficients here)", st0,
                          mode == 4 ? " (or bulkPi/P)" : (baryon ? " or muB" : ""));
