@@ -618,6 +618,60 @@ int is3d_write_spacetime(const char *results_dir, const is3d_spacetime_bins *bin
                          const double *eta_values, const is3d_spacetime_out *out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Spin polarization from thermal vorticity (mode 5) -- what EmissionFunctionArray::calculate_spin_polzn computes
+ * (src/cpp/emissionfunction_polzn_kernels.cpp:27-265; writer write_polzn_vector_toFile, emissionfunction.cpp:775-821).  For every species s
+ * and (pT, phi, y), summed over ALL cells (no u.dsigma test, no outflow cut, no degeneracy, no (2 pi hbar c)^-3):
+ *   pt = mT cosh(y - eta), pn = mT / tau sinh(y - eta), px = pT cos(phi), py = pT sin(phi), ut = sqrt(|1 + ux^2 + uy^2 + tau^2 un^2|),
+ *   f0 = 1 / (exp(p.u / T) + sign), pref = -(1 / (8 m)) (1 - sign f0),
+ *   spin_t = 2 pref (wxy pn - wxn py + wyn px),   spin_x = 2 pref (wyn pt - wtn py + wty pn),
+ *   spin_y = 2 pref (-wxn pt + wtn px - wtx pn),  spin_n = 2 pref (wtx py + wxy pt - wty px),
+ *   S_mu += w p.dsigma f0 spin_mu,  Snorm += w p.dsigma f0.
+ * T is ONE temperature for the whole surface (Plasma::temperature: the first line of average_thermodynamic_quantities.dat, or T_switch
+ * when set_FO_temperature = 1; emissionfunction.cpp:1318-1321).  3+1D: the y grid, eta = the cell's eta, w = 1.  2+1D: y = 0, the sum over
+ * the eta grid with w = eta_w[k] (eta[1] - eta[0]).  Outputs in the spectrum layout s + S (ipT + n_pT (iphi + n_phi iy)).
+ * The vorticity is indexed by the GLOBAL cell index (the reference reads wtx_fo[icell] with the index inside its 10 000-cell chunk, so every
+ * chunk after the first reuses the first chunk's vorticity).  Species of the same (mass, sign) share one evaluation;
+ * degeneracy and baryon number do not enter.  Deterministic: per-chunk partial sums reduced in a fixed order, no floating-point atomics.
+ * Options honoured: dimension, device, workspace_bytes (cap on the per-chunk partial sums; 0: 16 GiB).  The argument checks (a NULL
+ * vorticity or cell array the dimension needs, T <= 0 or not finite, a mass <= 0, fewer than 2 eta nodes in 2+1D) precede any device use.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct {                        /* thermal vorticity varpi_{mu nu} as read from a mode-5 surface (readindata.cpp:470-551), no unit conversion */
+    const double *wtx, *wty, *wtn, *wxy, *wxn, *wyn;
+} is3d_vorticity;
+
+typedef struct {                        /* each [n_species][n_pT][n_phi][n_y_eff] in the spectrum layout; host (one-shot) or device (plan) */
+    double *St, *Sx, *Sy, *Sn, *Snorm;
+} is3d_polarization_out;
+
+typedef struct {
+    int32_t code;
+    int32_t n_classes;                  /* distinct (mass, sign) classes evaluated */
+    int32_t n_chunks;                   /* cell chunks of the partial sums (reduced in chunk order) */
+    int32_t reserved;
+    double ms_cells, ms_reduce;         /* device time of the per-chunk kernel and of the chunk reduction */
+    double ms_h2d, ms_d2h;              /* one-shot entry only */
+} is3d_polarization_stats;
+
+/* one-shot host entry: cells (tau, eta in 3+1D, ux, uy, un, dat, dax, day, dan are read) and vorticity are HOST arrays of cells->n_cells */
+int is3d_spin_polarization(const is3d_cells *cells, const is3d_vorticity *vorticity, const is3d_species *species, const is3d_grid *grid,
+                           double T, const is3d_options *opts, is3d_polarization_out *out, is3d_polarization_stats *stats);
+/* device-resident form: species classes, grids and lane tables on the device at create; execute takes DEVICE cell and vorticity arrays and
+ * DEVICE outputs on hip_stream (a hipStream_t, NULL = default).  stats != NULL synchronises the stream and fills the times.  The one-shot is
+ * create + upload + execute + download, so the two agree bit for bit. */
+typedef struct is3d_polarization_plan is3d_polarization_plan;
+int is3d_polarization_plan_create(is3d_polarization_plan **plan, const is3d_species *species, const is3d_grid *grid, const is3d_options *opts,
+                                  int64_t max_cells);
+int is3d_polarization_plan_execute(is3d_polarization_plan *plan, const is3d_cells *cells, const is3d_vorticity *vorticity, double T,
+                                   const is3d_polarization_out *out, void *hip_stream, is3d_polarization_stats *stats);
+void is3d_polarization_plan_destroy(is3d_polarization_plan *plan);
+/* write_polzn_vector_toFile (emissionfunction.cpp:775-821): APPENDS to <results_dir>/St.dat, Sx.dat, Sy.dat, Sn.dat one line per point,
+ * "y\tphip\tpT\tS/Snorm" (scientific, setprecision(8), setw(5)), species outer, then y, phi, pT, a blank line after each phi block.  The
+ * ratio is formed here, in C++, so 0/0 and +-inf print as the reference's would.  2+1D: y = 0 (y may be NULL).  IS3D_EIO if a file cannot
+ * be opened. */
+int is3d_write_polarization(const char *results_dir, int32_t dimension, int32_t n_species, int32_t n_pT, const double *pT, int32_t n_phi,
+                            const double *phi, int32_t n_y, const double *y, const is3d_polarization_out *out);
+
+/* ---------------------------------------------------------------------------------------------
  * Driver: IS3D::run_particlization (src/cpp/iS3D.cpp:74-192; class IS3D, src/cpp/iS3D.h:19-96).  Reads iS3D_parameters.dat,
  * PDG/, tables/, deltaf_coefficients/ from the current directory and writes results/ exactly as the command line tool does
  * (which is this call with surface = NULL).  surface != NULL is the embedding path (read_fo_surf_from_memory +
@@ -702,6 +756,9 @@ int32_t is3d_surface_source(is3d_surface *surface);
 int32_t is3d_surface_from_sidecar(const is3d_surface *surface);
 int is3d_surface_arrays(const is3d_surface *surface, const double **arrays, int32_t n_arrays, double avg5[5]);
 void is3d_surface_close(is3d_surface *surface);
+/* the six thermal-vorticity arrays of a mode-5 surface (w: wtx wty wtn wxy wxn wyn, as read, no unit conversion; valid until
+ * is3d_surface_close).  A mode-5 sidecar carries them too (one written without them is re-parsed).  IS3D_EINVAL for any other mode. */
+int is3d_surface_vorticity(const is3d_surface *surface, const double *w[6]);
 
 /* PDG_Data::read_resonances_conventional (src/cpp/readindata.cpp:1440-1568), reduced to what the
  * smooth path uses.  Two-call pattern (mc_id == NULL -> only *n).  Arrays of capacity entries. */

@@ -109,7 +109,28 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_vah_df_read", "is3d_vah_coefficients", "is3d_smooth_spectra_vah_df", "is3d_vah_plan_create", "is3d_vah_plan_output_size",
            "is3d_vah_plan_workspace_bytes", "is3d_vah_plan_execute", "is3d_vah_plan_set_timing", "is3d_vah_plan_timings",
            "is3d_vah_plan_tile_shape", "is3d_vah_plan_destroy", "is3d_surface_read_vah", "is3d_vah_plan_main_kernel_name", "is3d_math_probe", "is3d_resource_counters",
-           "is3d_spacetime_distributions", "is3d_plan_execute_spacetime", "is3d_write_spacetime"]
+           "is3d_spacetime_distributions", "is3d_plan_execute_spacetime", "is3d_write_spacetime",
+           "is3d_spin_polarization", "is3d_polarization_plan_create", "is3d_polarization_plan_execute", "is3d_polarization_plan_destroy",
+           "is3d_write_polarization", "is3d_surface_vorticity"]
+
+VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
+POLARIZATION_OUTPUTS = ["St", "Sx", "Sy", "Sn", "Snorm"]
+
+
+class Vorticity(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in VORTICITY_FIELDS]
+
+
+class PolarizationOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in POLARIZATION_OUTPUTS]
+
+
+class PolarizationStats(C.Structure):
+    _fields_ = [("code", C.c_int32), ("n_classes", C.c_int32), ("n_chunks", C.c_int32), ("reserved", C.c_int32),
+                ("ms_cells", C.c_double), ("ms_reduce", C.c_double), ("ms_h2d", C.c_double), ("ms_d2h", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 class SpacetimeBins(C.Structure):
     _fields_ = [("tau_min", C.c_double), ("tau_max", C.c_double), ("r_min", C.c_double), ("r_max", C.c_double),
@@ -250,6 +271,16 @@ def load():
                                               C.POINTER(SpacetimeOut), C.c_void_p, C.POINTER(SpacetimeStats)]
     L.is3d_write_spacetime.argtypes = [C.c_char_p, C.POINTER(SpacetimeBins), C.c_int32, C.POINTER(C.c_int64), C.c_int32, _dp,
                                        C.POINTER(SpacetimeOut)]
+    L.is3d_spin_polarization.argtypes = [C.POINTER(Cells), C.POINTER(Vorticity), C.POINTER(Species), C.POINTER(Grid), C.c_double,
+                                         C.POINTER(Options), C.POINTER(PolarizationOut), C.POINTER(PolarizationStats)]
+    L.is3d_polarization_plan_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(Species), C.POINTER(Grid), C.POINTER(Options), C.c_int64]
+    L.is3d_polarization_plan_execute.argtypes = [C.c_void_p, C.POINTER(Cells), C.POINTER(Vorticity), C.c_double, C.POINTER(PolarizationOut),
+                                                 C.c_void_p, C.POINTER(PolarizationStats)]
+    L.is3d_polarization_plan_destroy.argtypes = [C.c_void_p]
+    L.is3d_polarization_plan_destroy.restype = None
+    L.is3d_write_polarization.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, _dp,
+                                          C.POINTER(PolarizationOut)]
+    L.is3d_surface_vorticity.argtypes = [C.c_void_p, C.POINTER(_dp)]
     _LIB = L
     return L
 
@@ -574,6 +605,119 @@ def write_spacetime(results_dir, bins, mc_id, eta_values, res):
     b = _spacetime_bins(bins)
     _check(L.is3d_write_spacetime(results_dir.encode(), C.byref(b), len(mc), mc.ctypes.data_as(C.POINTER(C.c_int64)), len(ev), _p(ev),
                                   C.byref(so)))
+
+
+def _polzn_pack(species, grid, opts):
+    o = dict(DEFAULT_OPTS)
+    o.update(opts or {})
+    keep = {}
+    sp = {k: _f64(species[k]) for k in ["mass", "sign", "degeneracy", "baryon"]}
+    g = {k: _f64(grid[k]) for k in ["pT", "phi", "y", "eta", "eta_w"]}
+    keep.update(sp=sp, g=g)
+    sps = Species(len(sp["mass"]), _p(sp["mass"]), _p(sp["sign"]), _p(sp["degeneracy"]), _p(sp["baryon"]))
+    gs = Grid(len(g["pT"]), _p(g["pT"]), len(g["phi"]), _p(g["phi"]), len(g["y"]), _p(g["y"]), len(g["eta"]), _p(g["eta"]), _p(g["eta_w"]))
+    os_ = Options()
+    for k, v in o.items():
+        setattr(os_, k, int(v))
+    ny_eff = 1 if o["dimension"] == 2 else len(g["y"])
+    nout = len(sp["mass"]) * len(g["pT"]) * len(g["phi"]) * ny_eff
+    return sps, gs, os_, nout, keep
+
+
+def _host_cells(cells, held):
+    n = len(next(v for f in CELL_FIELDS for v in [cells.get(f)] if v is not None))
+    cs = Cells()
+    cs.n_cells = n
+    for f in CELL_FIELDS:
+        a = cells.get(f)
+        if a is not None:
+            a = _f64(a)
+            assert a.shape == (n,), f
+            held.append(a)
+            setattr(cs, f, a.ctypes.data)
+    return cs
+
+
+def spin_polarization(cells, vorticity, species, grid, T, opts=None):
+    """is3d_spin_polarization (mode 5, the drop-in for calculate_spin_polzn with the vorticity read at the global cell index): host arrays
+    in -> dict St, Sx, Sy, Sn, Snorm (flat, spectrum layout) and "stats".  vorticity: dict of VORTICITY_FIELDS arrays (None: refused by the
+    library); T: the surface's single temperature; opts: dimension, device, workspace_bytes."""
+    L = load()
+    sps, gs, os_, nout, keep = _polzn_pack(species, grid, opts)
+    held = []
+    cs = _host_cells(cells, held)
+    vs = None
+    if vorticity is not None:
+        vs = Vorticity()
+        for f in VORTICITY_FIELDS:
+            a = vorticity.get(f)
+            if a is not None:
+                a = _f64(a)
+                assert a.shape == (cs.n_cells,), f
+                held.append(a)
+                setattr(vs, f, a.ctypes.data)
+    res = {k: np.zeros(nout) for k in POLARIZATION_OUTPUTS}
+    po = PolarizationOut(*[res[k].ctypes.data for k in POLARIZATION_OUTPUTS])
+    st = PolarizationStats()
+    _check(L.is3d_spin_polarization(C.byref(cs), C.byref(vs) if vs is not None else None, C.byref(sps), C.byref(gs), float(T), C.byref(os_),
+                                    C.byref(po), C.byref(st)))
+    res["stats"] = st.as_dict()
+    return res
+
+
+class PolarizationPlan:
+    """Device-resident spin polarization (is3d_polarization_plan_*): cell and vorticity arrays and the five outputs are device pointers (ints),
+    e.g. torch tensors' data_ptr(); `stream` a hipStream_t handle."""
+
+    def __init__(self, species, grid, opts=None, max_cells=1):
+        L = load()
+        sps, gs, os_, nout, _ = _polzn_pack(species, grid, opts)
+        self._h = C.c_void_p()
+        _check(L.is3d_polarization_plan_create(C.byref(self._h), C.byref(sps), C.byref(gs), C.byref(os_), int(max_cells)))
+        self.output_size = nout
+
+    def execute(self, n_cells, cell_ptrs, vort_ptrs, T, out_ptrs, stream=0, want_stats=True):
+        """cell_ptrs / vort_ptrs: dict field -> device pointer (vort_ptrs None: refused); out_ptrs: dict St, Sx, Sy, Sn, Snorm -> device pointer."""
+        cs = Cells()
+        cs.n_cells = int(n_cells)
+        for f in CELL_FIELDS:
+            p = cell_ptrs.get(f)
+            if p:
+                setattr(cs, f, int(p))
+        vs = None
+        if vort_ptrs is not None:
+            vs = Vorticity(*[int(vort_ptrs[f]) if vort_ptrs.get(f) else None for f in VORTICITY_FIELDS])
+        po = PolarizationOut(*[int(out_ptrs[k]) if out_ptrs.get(k) else None for k in POLARIZATION_OUTPUTS])
+        st = PolarizationStats()
+        _check(load().is3d_polarization_plan_execute(self._h, C.byref(cs), C.byref(vs) if vs is not None else None, float(T), C.byref(po),
+                                                     C.c_void_p(int(stream or 0)), C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
+    def close(self):
+        if self._h:
+            load().is3d_polarization_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def write_polarization(results_dir, dimension, pT, phi, y, res, n_species=None):
+    """is3d_write_polarization: appends St.dat, Sx.dat, Sy.dat, Sn.dat under results_dir from the five arrays of spin_polarization (the
+    ratios S / Snorm are formed in the library).  y may be None in 2+1D."""
+    L = load()
+    pT, phi = _f64(pT), _f64(phi)
+    yv = _f64(y if y is not None else [0.0])
+    arrs = {k: _f64(res[k]) for k in POLARIZATION_OUTPUTS}
+    ny_eff = 1 if dimension == 2 else len(yv)
+    if n_species is None:
+        n_species = arrs["St"].size // (len(pT) * len(phi) * ny_eff)
+    po = PolarizationOut(*[arrs[k].ctypes.data for k in POLARIZATION_OUTPUTS])
+    _check(L.is3d_write_polarization(results_dir.encode(), int(dimension), int(n_species), len(pT), _p(pT), len(phi), _p(phi),
+                                     len(yv), _p(yv), C.byref(po)))
 
 
 def shard_bounds(n_cells, rank, n_ranks):
@@ -933,6 +1077,29 @@ def surface_open(path, mode=1, include_baryon=0, include_baryondiff_deltaf=0, di
     finally:
         L.is3d_surface_close(h)
     return arrs, (None if mode == 2 else avg), source
+
+
+def surface_vorticity(path, include_baryon=0, include_baryondiff_deltaf=0, dimension=3, cache=1):
+    """is3d_surface_open (mode 5) + is3d_surface_vorticity: the six thermal-vorticity arrays of a mode-5 surface (copies), dict
+    VORTICITY_FIELDS -> array, and the source (0 text parsed | 1 text parsed + sidecar written | 2 sidecar)."""
+    L = load()
+    L.is3d_surface_open.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.is3d_surface_cells.argtypes = [C.c_void_p]
+    L.is3d_surface_cells.restype = C.c_int64
+    L.is3d_surface_source.argtypes = [C.c_void_p]
+    L.is3d_surface_close.argtypes = [C.c_void_p]
+    L.is3d_surface_close.restype = None
+    h = C.c_void_p()
+    _check(L.is3d_surface_open(path.encode(), 5, int(include_baryon), int(include_baryondiff_deltaf), int(dimension), int(cache), C.byref(h)))
+    try:
+        n = L.is3d_surface_cells(h)
+        ptrs = (_dp * 6)()
+        _check(L.is3d_surface_vorticity(h, ptrs))
+        w = {f: (np.ctypeslib.as_array(ptrs[i], shape=(n,)).copy() if n > 0 else np.zeros(0)) for i, f in enumerate(VORTICITY_FIELDS)}
+        source = L.is3d_surface_source(h)
+    finally:
+        L.is3d_surface_close(h)
+    return w, source
 
 
 def pdg_read(path, box=False):

@@ -354,7 +354,7 @@ extern "C" int is3d_surface_read_vh(const char *path, int32_t include_baryon, in
 // read and dropped: the kernel reconstructs them (smooth_kernels.cpp:133, :166-170).
 // ---------------------------------------------------------------------------------------------
 static int surface_read_text(const std::string &text, const char *path, int32_t mode, int32_t include_baryon, int32_t include_baryondiff_deltaf,
-                             int32_t dimension, int64_t *n_cells, double *const *A, double *avg5, double *const *XY)
+                             int32_t dimension, int64_t *n_cells, double *const *A, double *avg5, double *const *XY, double *const *W = nullptr)
 {
     if (mode == 1) return surface_read_vh_text(text, path, include_baryon, include_baryondiff_deltaf, dimension, n_cells, A, avg5, XY);
     if (mode != 0 && mode != 4 && mode != 5 && mode != 6 && mode != 7)
@@ -414,7 +414,8 @@ static int surface_read_text(const std::string &text, const char *path, int32_t 
         } else if (mode == 5) {
             // read_surf_VH_Vorticity (readindata.cpp:470-551): the mode-1 columns -- with V^tau inside the baryon-diffusion block, as in
             // mode 0 -- then the six components of the thermal vorticity.  calculate_spectra runs the viscous-hydro kernels on such a
-            // surface (emissionfunction.cpp:1503, :1643; its calculate_spin_polzn branch at :1675 is unreachable), which do not read them.
+            // surface (emissionfunction.cpp:1503, :1643; its calculate_spin_polzn branch at :1675 is unreachable), which do not read them;
+            // is3d_surface_open keeps them for the spin polarization (is3d_surface_vorticity).
             dat = next(); dax = next(); day = next(); dan = next();
             ux = next(); uy = next(); un = next();
             E = next() * kHbarC; T = next() * kHbarC; P = next() * kHbarC;
@@ -427,7 +428,10 @@ static int surface_read_text(const std::string &text, const char *path, int32_t 
                 (void)next();  // Vt
                 Vx = next(); Vy = next(); Vn = next();
             }
-            for (int k = 0; k < 6; k++) (void)next();   // wtx wty wtn wxy wxn wyn
+            for (int k = 0; k < 6; k++) {   // wtx wty wtn wxy wxn wyn, as read (no unit conversion): the spin polarization's input
+                const double wk = next();
+                if (W) W[k][i] = wk;
+            }
         } else if (mode == 4 || mode == 6) {
             eta = 0.0;
             dat = next() * tau; dax = next() * tau; day = next() * tau;
@@ -619,6 +623,7 @@ extern "C" int is3d_surface_read_vah(const char *path, int32_t dimension, int64_
 namespace {
 
 constexpr int kSurfArraysVH = 25;    // cell_arrays23 + x, y
+constexpr int kSurfArraysVort = 31;  // mode 5: the 25, then wtx wty wtn wxy wxn wyn (array_mask bits 25-30: a sidecar without them does not match)
 constexpr int kSurfArraysVAH = 32;   // arrays32 of is3d_surface_read_vah
 
 struct CacheHeader {
@@ -738,7 +743,7 @@ extern "C" int is3d_surface_open(const char *path, int32_t mode, int32_t include
     const uint64_t tkey = mix64(mix64(mix64(0x1553D5ULL, (uint64_t)stt.st_ctim.tv_sec * 1000000000ULL + (uint64_t)stt.st_ctim.tv_nsec), (uint64_t)stt.st_ino), (uint64_t)stt.st_dev);
     std::unique_ptr<is3d_surface> S(new is3d_surface);
     S->mode = mode; S->include_baryon = include_baryon != 0; S->include_diff = include_baryondiff_deltaf != 0; S->dimension = dimension;
-    const int narr = vah ? kSurfArraysVAH : kSurfArraysVH;
+    const int narr = vah ? kSurfArraysVAH : mode == 5 ? kSurfArraysVort : kSurfArraysVH;
     S->a.resize((size_t)narr);
     uint64_t mask = 0;
     for (int k = 0; k < narr; k++) {
@@ -817,7 +822,8 @@ extern "C" int is3d_surface_open(const char *path, int32_t mode, int32_t include
     int64_t n = rows;
     int rc;
     if (vah) rc = surface_read_vah_text(text, path, dimension, &n, ptr.data());
-    else rc = surface_read_text(text, path, mode, include_baryon, include_baryondiff_deltaf, dimension, &n, ptr.data(), S->avg, ptr.data() + 23);
+    else rc = surface_read_text(text, path, mode, include_baryon, include_baryondiff_deltaf, dimension, &n, ptr.data(), S->avg, ptr.data() + 23,
+                                mode == 5 ? ptr.data() + kSurfArraysVH : nullptr);
     if (rc) return rc;
     S->n = n;
     if (n == 0)
@@ -855,10 +861,21 @@ extern "C" int32_t is3d_surface_from_sidecar(const is3d_surface *s) { return (s 
 extern "C" int is3d_surface_arrays(const is3d_surface *s, const double **arrays, int32_t n_arrays, double avg5[5])
 {
     if (!s || !arrays) return io_fail(IS3D_EINVAL, "null argument");
-    if (n_arrays != (int32_t)s->a.size())
-        return io_fail(IS3D_EINVAL, "is3d_surface_arrays: this surface (mode %d) has %zu arrays, %d asked for", s->mode, s->a.size(), n_arrays);
-    for (size_t k = 0; k < s->a.size(); k++) arrays[k] = s->a[k].empty() ? nullptr : s->a[k].data();
+    // mode 5 keeps the vorticity behind the 25 arrays of every viscous-hydro format: is3d_surface_vorticity hands it out
+    const size_t na = s->mode == 5 ? (size_t)kSurfArraysVH : s->a.size();
+    if (n_arrays != (int32_t)na)
+        return io_fail(IS3D_EINVAL, "is3d_surface_arrays: this surface (mode %d) has %zu arrays, %d asked for", s->mode, na, n_arrays);
+    for (size_t k = 0; k < na; k++) arrays[k] = s->a[k].empty() ? nullptr : s->a[k].data();
     if (avg5) memcpy(avg5, s->avg, sizeof s->avg);
+    return IS3D_OK;
+}
+
+extern "C" int is3d_surface_vorticity(const is3d_surface *s, const double *w[6])
+{
+    if (!s || !w) return io_fail(IS3D_EINVAL, "null argument");
+    if (s->mode != 5 || s->a.size() != (size_t)kSurfArraysVort)
+        return io_fail(IS3D_EINVAL, "is3d_surface_vorticity: only a mode-5 surface carries the thermal vorticity (this one is mode %d)", s->mode);
+    for (int k = 0; k < 6; k++) w[k] = s->a[(size_t)kSurfArraysVH + k].empty() ? nullptr : s->a[(size_t)kSurfArraysVH + k].data();
     return IS3D_OK;
 }
 
@@ -1475,6 +1492,43 @@ extern "C" int is3d_write_spacetime(const char *results_dir, const is3d_spacetim
             rapidity_d << std::setprecision(6) << std::scientific << eta_values[k] << "\t" << out->dN_dydeta[(size_t)ip * n_eta_eff + k] << "\n";
         time_d.close(); radial_d.close(); timeradial_d.close(); rapidity_d.close();
         if (!time_d || !radial_d || !timeradial_d || !rapidity_d) return io_fail(IS3D_EIO, "write error under %s", results_dir);
+    }
+    return IS3D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// EmissionFunctionArray::write_polzn_vector_toFile (src/cpp/emissionfunction.cpp:775-821): St.dat, Sx.dat, Sy.dat, Sn.dat opened with
+// ios_base::app; per point `scientific << setw(5) << setprecision(8) << y << "\t" << phip << "\t" << pT << "\t" << (S / Snorm)`, species
+// outer, then y, phi, pT, a blank line after each phi block.  The quotient is formed here, so 0/0 and +-inf print as the reference's do.
+// ---------------------------------------------------------------------------------------------
+extern "C" int is3d_write_polarization(const char *results_dir, int32_t dimension, int32_t n_species, int32_t n_pT, const double *pT,
+                                       int32_t n_phi, const double *phi, int32_t n_y, const double *y, const is3d_polarization_out *out)
+{
+    if (!results_dir || !pT || !phi || !out || !out->St || !out->Sx || !out->Sy || !out->Sn || !out->Snorm) return io_fail(IS3D_EINVAL, "null argument");
+    if (dimension != 2 && dimension != 3) return io_fail(IS3D_EINVAL, "dimension = %d: 2 or 3", dimension);
+    if (dimension == 3 && !y) return io_fail(IS3D_EINVAL, "3+1D needs the y grid");
+    if (n_species < 0 || n_pT < 0 || n_phi < 0 || n_y < 0) return io_fail(IS3D_EINVAL, "negative size");
+    const int y_pts = dimension == 2 ? 1 : n_y;
+    const char *names[4] = {"St.dat", "Sx.dat", "Sy.dat", "Sn.dat"};
+    const double *S[4] = {out->St, out->Sx, out->Sy, out->Sn};
+    for (int m = 0; m < 4; m++) {
+        const std::string path = std::string(results_dir) + "/" + names[m];
+        std::ofstream f(path, std::ios_base::app);
+        if (!f) return io_fail(IS3D_EIO, "cannot open %s", path.c_str());
+        for (int ipart = 0; ipart < n_species; ipart++)
+            for (int iy = 0; iy < y_pts; iy++) {
+                const double yv = dimension == 2 ? 0.0 : y[iy];
+                for (int iphip = 0; iphip < n_phi; iphip++) {
+                    for (int ipT = 0; ipT < n_pT; ipT++) {
+                        const long long i = (long long)ipart + (long long)n_species * ((long long)ipT + (long long)n_pT * ((long long)iphip + (long long)n_phi * iy));
+                        f << std::scientific << std::setw(5) << std::setprecision(8) << yv << "\t" << phi[iphip] << "\t" << pT[ipT] << "\t"
+                          << (S[m][i] / out->Snorm[i]) << "\n";
+                    }
+                    f << "\n";
+                }
+            }
+        f.close();
+        if (!f) return io_fail(IS3D_EIO, "write error on %s", path.c_str());
     }
     return IS3D_OK;
 }

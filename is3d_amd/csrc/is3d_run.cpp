@@ -21,6 +21,9 @@
 // results/spacetime_distribution/{dN_taudtaudy, dN_twopirdrdy, dN_twopitaurdtaudrdy}_<id>.dat and dN_dydeta_<id>_<n>pt.dat (the directory must
 // exist) and prints one "dN_dy = %lf" line per species; no momentum-spectra file (those are written for operation = 1 only, :1678).  df_mode 3 / 4
 // (calculate_dN_dX_feqmod) and mode 2 are refused before anything is written.
+// mode = 5: every run, whatever its operation, ends with the spin polarization from the surface's thermal vorticity (calculate_spin_polzn,
+// emissionfunction.cpp:1675) and appends results/St.dat, Sx.dat, Sy.dat, Sn.dat (write_polzn_vector_toFile, :1701), with T from the averages
+// file just written or T_switch when set_FO_temperature = 1; the embedding entry has no vorticity and says so.
 // Scope: operation in {0, 1, 2}, mode in {0, 1, 4, 5, 6, 7}, df_mode in {1, 2, 3} with include_baryon in {0, 1}, df_mode 4
 // (modified equilibrium; also reads tables/gla_roots_weights_32_points.txt, deta_min, mass_pion0 and the surface
 // averages it has just written, as the reference does) with include_baryon = 0.  Anything else is refused
@@ -316,6 +319,48 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
     opts.include_bulk_deltaf = include_bulk; opts.include_shear_deltaf = include_shear; opts.include_baryondiff_deltaf = include_diff;
     opts.regulate_deltaf = regulate; opts.outflow = outflow;
     opts.accumulate = 0; opts.device = rd.list.empty() ? -1 : rd.list[0]; opts.kernel_variant = variant;
+    // ---- mode 5: every run ends with the spin polarization from the surface's thermal vorticity (emissionfunction.cpp:1675, :1701) ----
+    auto polarization = [&]() -> int {
+        if (mode != 5 || vah) return IS3D_OK;
+        if (mem) {
+            printf("mode = 5: the spin polarization needs the thermal vorticity, which only the file reader (input/surface.dat) provides; no S*.dat written\n");
+            return IS3D_OK;
+        }
+        // Plasma::temperature: the first line of the averages file this run wrote, or T_switch (emissionfunction.cpp:1318-1321)
+        double Tp = 0.0, set_T = 0.0;
+        {
+            FILE *tf = fopen("average_thermodynamic_quantities.dat", "r");
+            if (!tf || fscanf(tf, "%lf", &Tp) != 1) {
+                if (tf) fclose(tf);
+                DIE("Error opening average thermodynamic file");
+            }
+            fclose(tf);
+        }
+        if (get_param("set_fo_temperature", &set_T, false) == IS3D_OK && (int)set_T && get_param("t_switch", &Tp)) return IS3D_EINVAL;
+        const double *w[6];
+        if (is3d_surface_vorticity(surf, w)) DIE("%s", is3d_last_error());
+        is3d_vorticity vort{w[0], w[1], w[2], w[3], w[4], w[5]};
+        is3d_options po{};
+        po.dimension = dimension;
+        po.device = rd.list.empty() ? -1 : rd.list[0];   // the first device of the run: polarization is not sharded
+        const size_t np = mcid.size() * pT.size() * phi.size() * (size_t)((dimension == 2) ? 1 : y.size());
+        std::vector<double> pS[5];
+        for (auto &v : pS) v.assign(np, 0.0);
+        is3d_polarization_out po_out{pS[0].data(), pS[1].data(), pS[2].data(), pS[3].data(), pS[4].data()};
+        is3d_polarization_stats pst{};
+        printf("Calculating spin polarization vector (T = %.6f GeV)...\n", Tp);
+        const int rcp = is3d_spin_polarization(&cells, &vort, &sp, &grid, Tp, &po, &po_out, &pst);
+        if (rcp) {
+            const std::string msg = is3d_last_error();
+            DIE("is3d_spin_polarization failed (%d): %s", rcp, msg.c_str());
+        }
+        printf("Writing polarization vector to file...\n");
+        if (is3d_write_polarization("results", dimension, sp.n, grid.n_pT, pT.data(), grid.n_phi, phi.data(), grid.n_y, y.data(), &po_out))
+            DIE("%s", is3d_last_error());
+        printf("polarization: species classes evaluated: %d of %d; device time: cells %.3f ms, reduce %.3f ms\n", pst.n_classes, sp.n,
+               pst.ms_cells, pst.ms_reduce);
+        return IS3D_OK;
+    };
     const int ny_eff = (dimension == 2) ? 1 : (int)y.size();
     std::vector<double> dN(mcid.size() * pT.size() * phi.size() * (size_t)ny_eff, 0.0);
     if (operation == 2) {
@@ -450,6 +495,7 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
             memcpy(res->mc_id, mcid.data(), sizeof(int64_t) * (size_t)sp.n);
             memcpy(res->mass, mass.data(), sizeof(double) * (size_t)sp.n);
         }
+        if (int rcp = polarization()) return rcp;
         printf("Done sampling particles. Output stored in results folder. Goodbye!\n");
         return IS3D_OK;
     }
@@ -495,6 +541,7 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
             memcpy(res->mc_id, mcid.data(), sizeof(int64_t) * (size_t)S);
             memcpy(res->mass, mass.data(), sizeof(double) * (size_t)S);
         }
+        if (int rcp = polarization()) return rcp;
         printf("Done calculating spacetime distributions. Output stored in results/spacetime_distribution. Goodbye!\n");
         return IS3D_OK;
     }
@@ -579,6 +626,7 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         memcpy(res->mc_id, mcid.data(), sizeof(int64_t) * (size_t)sp.n);
         memcpy(res->mass, mass.data(), sizeof(double) * (size_t)sp.n);
     }
+    if (int rcp = polarization()) return rcp;
     printf("Done calculating particle spectra. Output stored in results folder. Goodbye!\n");
     return IS3D_OK;
 }

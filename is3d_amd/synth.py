@@ -98,6 +98,18 @@ def synth_surface(n_cells, dimension, seed=None, first_cell=0, baryon=False):
     return {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in s.items()}
 
 
+VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
+SEED_VORTICITY = 20260005
+
+
+def synth_vorticity(n_cells, seed=SEED_VORTICITY, first_cell=0):
+    """Thermal vorticity varpi_{mu nu} of cells [first_cell, first_cell + n_cells) (the six columns of a mode-5 surface, wtx wty wtn wxy
+    wxn wyn): each component uniform in [-0.1, 0.1) from its own counter slot, so |varpi| <~ 0.1 and any slice equals the same cells of a
+    longer draw.  Independent of synth_surface (its own seed)."""
+    c = np.arange(first_cell, first_cell + n_cells, dtype=np.uint64) * np.uint64(8)
+    return {f: np.ascontiguousarray(0.2 * _uniform(seed, c + np.uint64(k)) - 0.1, dtype=np.float64) for k, f in enumerate(VORTICITY_FIELDS)}
+
+
 VAH_FIELDS = ["tau", "eta", "ux", "uy", "un", "dat", "dax", "day", "dan", "T", "pitt", "pitx", "pity", "pitn", "pixx", "pixy", "pixn",
               "piyy", "piyn", "pinn", "bulkPi", "Wx", "Wy", "Lambda", "aL", "c0", "c1", "c2", "c3", "c4"]
 

@@ -1,0 +1,286 @@
+"""GPU: the spin polarization from thermal vorticity (is3d_spin_polarization, is3d_polarization_plan_*, the command line tool on mode 5)
+against a numpy restatement of the reference loop (emissionfunction_polzn_kernels.cpp:27-265), evaluated directly -- independent of the
+kernel's factorisation."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import refformat
+from is3d_amd import api, inputs, synth
+from test_polarization_io import write_mode5
+
+pytestmark = pytest.mark.gpu
+
+OUTS = api.POLARIZATION_OUTPUTS
+
+
+def restate(cells, w, sp, grid, T, dim, chunk_local=False):
+    """calculate_spin_polzn in numpy, term by term (polzn_kernels.cpp:117-216).  chunk_local: the reference's indexing of the vorticity by
+    the cell index inside its 10 000-cell chunk (:149-154)."""
+    n = len(cells["tau"])
+    idx = np.arange(n) % 10000 if chunk_local else np.arange(n)
+    wtx, wty, wtn, wxy, wxn, wyn = (np.asarray(w[f])[idx] for f in synth.VORTICITY_FIELDS)
+    tau, ux, uy, un = cells["tau"], cells["ux"], cells["uy"], cells["un"]
+    dat, dax, day, dan = cells["dat"], cells["dax"], cells["day"], cells["dan"]
+    ut = np.sqrt(np.abs(1.0 + ux * ux + uy * uy + tau * tau * un * un))   # :137
+    pTv, phiv = np.asarray(grid["pT"]), np.asarray(grid["phi"])
+    if dim == 3:
+        yv, etav, wk = np.asarray(grid["y"]), None, None
+    else:
+        yv = np.zeros(1)
+        etav = np.asarray(grid["eta"])
+        wk = np.asarray(grid["eta_w"]) * (etav[1] - etav[0])                 # :69-70
+    S, npT, J, ny = len(sp["mass"]), len(pTv), len(phiv), len(yv)
+    out = {k: np.zeros((ny, J, npT, S)) for k in OUTS}
+    cp, spn = np.cos(phiv), np.sin(phiv)
+    # axes: cell, phi, (y | eta)
+    C = lambda a: a[:, None, None]                                           # noqa: E731
+    with np.errstate(over="ignore", invalid="ignore"):
+        for s in range(S):
+            m, sign = float(sp["mass"][s]), float(sp["sign"][s])
+            for ip, pT in enumerate(pTv):
+                mT = np.sqrt(m * m + pT * pT)
+                px, py = (pT * cp)[None, :, None], (pT * spn)[None, :, None]
+                if dim == 3:
+                    d = yv[None, None, :] - C(cells["eta"])
+                else:
+                    d = 0.0 - etav[None, None, :]
+                pt = mT * np.cosh(d)
+                pn = mT / C(tau) * np.sinh(d)
+                pds = pt * C(dat) + px * C(dax) + py * C(day) + pn * C(dan)
+                pu = pt * C(ut) - px * C(ux) - py * C(uy) - C(tau * tau) * pn * C(un)
+                f0 = 1.0 / (np.exp(pu / T) + sign)
+                pref = -(1.0 / 8.0 / m) * (1.0 - sign * f0)
+                st = pref * 2.0 * (C(wxy) * pn - C(wxn) * py + C(wyn) * px)
+                sx = pref * 2.0 * (C(wyn) * pt - C(wtn) * py + C(wty) * pn)
+                sy = pref * 2.0 * (-C(wxn) * pt + C(wtn) * px - C(wtx) * pn)
+                sn = pref * 2.0 * (C(wtx) * py + C(wxy) * pt - C(wty) * px)
+                wt = 1.0 if dim == 3 else wk[None, None, :]
+                base = wt * pds * f0
+                for k, v in (("St", base * st), ("Sx", base * sx), ("Sy", base * sy), ("Sn", base * sn), ("Snorm", base)):
+                    if dim == 3:
+                        out[k][:, :, ip, s] = v.sum(axis=0).T          # [y][phi]
+                    else:
+                        out[k][0, :, ip, s] = v.sum(axis=(0, 2))
+    return {k: v.reshape(-1) for k, v in out.items()}
+
+
+def assert_close(got, ref, tol=1e-10):
+    for k in OUTS:
+        assert np.all(np.isfinite(got[k])), k
+        assert np.all(np.isfinite(ref[k])), k
+        scale = np.max(np.abs(ref[k]))
+        assert scale > 0, k
+        err = np.max(np.abs(got[k] - ref[k])) / scale
+        assert err <= tol, (k, err)
+
+
+def pick_species(n, kinds):
+    """n urqmd species with the requested statistics (1 fermions, -1 bosons) and one Boltzmann copy (sign 0) of the first."""
+    u = inputs.species("urqmd")
+    idx = []
+    for want in kinds:
+        idx += [i for i in range(len(u["mass"])) if u["sign"][i] == want][:n]
+    sp = {k: np.asarray(u[k])[idx].copy() for k in ("mass", "sign", "degeneracy", "baryon")}
+    for k in sp:
+        sp[k] = np.append(sp[k], sp[k][0])
+    sp["sign"][-1] = 0.0
+    return sp
+
+
+def mixed_cells(n, dim, seed):
+    """synthetic cells with a few that the spectra path would skip (u.dsigma <= 0), and extreme ones: fast flow, eta at the y grid's edges."""
+    c = synth.synth_surface(n, dim, seed=seed)
+    c["dat"][::9] *= -1.0
+    c["dax"][1::11] *= 40.0
+    c["ux"][2::13] = 8.0
+    c["uy"][3::13] = -6.0
+    if dim == 3:
+        y = inputs.grid()["y"]
+        c["eta"][4::10] = float(y[0])
+        c["eta"][5::10] = float(y[-1])
+        c["un"][6::17] = 3.0 / c["tau"][6::17]
+    return c
+
+
+@pytest.mark.parametrize("dim,n,kinds", [(3, 200, (1, -1)), (3, 60, (-1,)), (2, 50, (1, -1)), (2, 120, (1,))])
+def test_parity_with_restatement(fx, dim, n, kinds):
+    sp = pick_species(3 if len(kinds) == 2 else 6, kinds)
+    assert 5 <= len(sp["mass"]) <= 8
+    cells = mixed_cells(n, dim, seed=300 + n + dim)
+    w = synth.synth_vorticity(n, seed=77 + n)
+    T = 0.1503
+    got = api.spin_polarization(cells, w, sp, fx["grid"], T, dict(dimension=dim))
+    ref = restate(cells, w, sp, fx["grid"], T, dim)
+    assert_close(got, ref)
+    assert 2 <= got["stats"]["n_classes"] <= len(sp["mass"])
+
+
+def test_vorticity_read_at_global_cell_index():
+    n = 10050
+    g = inputs.grid()
+    grid = dict(pT=g["pT"][[2, 11, 20]], phi=g["phi"][[0, 7, 13, 19]], y=g["y"][[3, 10, 17]], eta=g["eta"], eta_w=g["eta_w"])
+    sp = pick_species(1, (1, -1))
+    cells = synth.synth_surface(n, 3, seed=401)
+    w = synth.synth_vorticity(n, seed=402)
+    assert all(not np.array_equal(w[f][10000:], w[f][:50]) for f in synth.VORTICITY_FIELDS)
+    T = 0.148
+    got = api.spin_polarization(cells, w, sp, grid, T, dict(dimension=3))
+    ref = restate(cells, w, sp, grid, T, 3)
+    assert_close(got, ref)
+    local = restate(cells, w, sp, grid, T, 3, chunk_local=True)
+    for k in OUTS[:4]:
+        scale = np.max(np.abs(ref[k]))
+        assert np.max(np.abs(local[k] - ref[k])) / scale > 1e-6, k   # the chunk-local answer is a different one
+        assert np.max(np.abs(got[k] - local[k])) / scale > 1e-6, k
+    assert np.array_equal(got["Snorm"], api.spin_polarization(cells, w, sp, grid, T, dict(dimension=3))["Snorm"])
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_exact_properties(fx, dim):
+    n = 150
+    # species of one (mass, sign) with different degeneracy and baryon number, plus two others
+    sp = dict(mass=np.array([0.9383, 0.13957, 0.9383, 0.4937, 0.9383]), sign=np.array([1.0, -1.0, 1.0, -1.0, 1.0]),
+              degeneracy=np.array([2.0, 1.0, 4.0, 1.0, 2.0]), baryon=np.array([1.0, 0.0, -1.0, 0.0, 0.0]))
+    cells = mixed_cells(n, dim, seed=500 + dim)
+    w = synth.synth_vorticity(n, seed=501)
+    T = 0.152
+    o = dict(dimension=dim)
+    base = api.spin_polarization(cells, w, sp, fx["grid"], T, o)
+    assert base["stats"]["n_classes"] == 3
+    zero = api.spin_polarization(cells, {f: np.zeros(n) for f in synth.VORTICITY_FIELDS}, sp, fx["grid"], T, o)
+    for k in OUTS[:4]:
+        assert np.all(zero[k] == 0.0), k
+    assert np.array_equal(zero["Snorm"], base["Snorm"])
+    dbl = api.spin_polarization(cells, {f: 2.0 * w[f] for f in synth.VORTICITY_FIELDS}, sp, fx["grid"], T, o)
+    for k in OUTS[:4]:
+        assert np.array_equal(dbl[k], 2.0 * base[k]), k
+    assert dbl["Snorm"].tobytes() == base["Snorm"].tobytes()
+    S = len(sp["mass"])
+    for k in OUTS:
+        a = base[k].reshape(-1, S)
+        assert a[:, 0].tobytes() == a[:, 2].tobytes() == a[:, 4].tobytes(), k
+        assert np.any(a[:, 0] != 0.0)
+
+
+def test_tie_to_spectra_path(fx):
+    """Snorm is the thermal spectrum without prefactor and degeneracy: with every cell at the polarization T, shear and bulk delta-f off and
+    outflow off, (2 pi hbar c)^-3 g_s Snorm is the spectrum of the cells with u.dsigma > 0 (the spectra path skips the others)."""
+    n, T = 100000, 0.1507
+    cells = synth.synth_surface(n, 3, seed=20260002)
+    tau, ux, uy, un = cells["tau"], cells["ux"], cells["uy"], cells["un"]
+    ut = np.sqrt(1.0 + ux * ux + uy * uy + tau * tau * un * un)
+    live = ut * cells["dat"] + ux * cells["dax"] + uy * cells["day"] + un * cells["dan"] > 0.0
+    cells = {k: np.ascontiguousarray(v[live]) for k, v in cells.items()}
+    cells["T"] = np.full(len(cells["tau"]), T)
+    w = synth.synth_vorticity(len(cells["tau"]), seed=601)
+    sp = fx["urqmd"]
+    pol = api.spin_polarization(cells, w, sp, fx["grid"], T, dict(dimension=3))
+    spec, _ = api.smooth_spectra(cells, sp, fx["grid"], fx["df"], dict(dimension=3, df_mode=1, include_shear_deltaf=0, include_bulk_deltaf=0,
+                                                                       outflow=0))
+    S = len(sp["mass"])
+    pref = (2.0 * np.pi * synth.HBARC) ** -3
+    a = (pref * np.asarray(sp["degeneracy"])[None, :] * pol["Snorm"].reshape(-1, S))
+    b = spec.reshape(-1, S)
+    err = np.max(np.abs(a - b), axis=0) / np.max(np.abs(b), axis=0)
+    assert np.max(err) <= 1e-11, (int(np.argmax(err)), float(np.max(err)))
+
+
+def test_determinism_and_plan_entry(fx):
+    import torch
+    n = 100000
+    cells = synth.synth_surface(n, 3, seed=20260002)
+    w = synth.synth_vorticity(n, seed=701)
+    sp = fx["urqmd"]
+    T = 0.1504
+    a = api.spin_polarization(cells, w, sp, fx["grid"], T, dict(dimension=3))
+    b = api.spin_polarization(cells, w, sp, fx["grid"], T, dict(dimension=3))
+    for k in OUTS:
+        assert a[k].tobytes() == b[k].tobytes(), k
+    dev = torch.device("cuda:0")
+    tc = {k: torch.from_numpy(np.ascontiguousarray(cells[k])).to(dev) for k in api.CELL_FIELDS if k in cells}
+    tw = {k: torch.from_numpy(w[k]).to(dev) for k in synth.VORTICITY_FIELDS}
+    plan = api.PolarizationPlan(sp, fx["grid"], dict(dimension=3), max_cells=n)
+    outs = {k: torch.full((plan.output_size,), 7.0, dtype=torch.float64, device=dev) for k in OUTS}
+    stream = torch.cuda.current_stream().cuda_stream
+    try:
+        for _ in range(2):
+            st = plan.execute(n, {k: v.data_ptr() for k, v in tc.items()}, {k: v.data_ptr() for k, v in tw.items()}, T,
+                              {k: v.data_ptr() for k, v in outs.items()}, stream)
+            torch.cuda.synchronize()
+            for k in OUTS:
+                assert outs[k].cpu().numpy().tobytes() == a[k].tobytes(), k
+        assert st["n_chunks"] >= 1 and st["ms_cells"] > 0
+        with pytest.raises(api.Is3dError) as e:
+            plan.execute(n, {k: v.data_ptr() for k, v in tc.items()}, None, T, {k: v.data_ptr() for k, v in outs.items()}, stream)
+        assert e.value.code == -1
+    finally:
+        plan.close()
+
+
+# ---- the command line tool ------------------------------------------------------------------
+CLI_IDS = [211, -211, 321, 2212, 3122, -3122]
+
+
+def mode5_run(tmp_path, name, n, params, seed=811):
+    cells = synth.synth_surface(n, 3, seed=seed)
+    w = synth.synth_vorticity(n, seed=seed + 1)
+    root = refformat.make_run_dir(str(tmp_path / name), cells, CLI_IDS, dict(dict(mode=5, dimension=3), **params))
+    write_mode5(os.path.join(root, "input", "surface.dat"), cells, w)
+    return root, cells, w
+
+
+def run_cli(root):
+    env = dict(os.environ, IS3D_DEVICES="0")
+    r = subprocess.run([api.CLI_PATH], cwd=root, capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    return r
+
+
+def expected_files(tmp_path, root, T):
+    """what api.write_polarization writes from the library result on the surface as the reader returns it"""
+    arrs, _, _ = api.surface_open(os.path.join(root, "input", "surface.dat"), mode=5, cache=0)
+    w, _ = api.surface_vorticity(os.path.join(root, "input", "surface.dat"), cache=0)
+    cells = {k: arrs[k] for k in api.CELL_FIELDS if arrs.get(k) is not None}
+    pdg = api.pdg_read(os.path.join(root, "PDG", "pdg-urqmd_v3.3+.dat"))
+    pos = [int(np.nonzero(pdg["mc_id"] == i)[0][0]) for i in CLI_IDS]
+    sp = dict(mass=pdg["mass"][pos], sign=pdg["sign"][pos], degeneracy=pdg["gspin"][pos], baryon=pdg["baryon"][pos])
+    g = inputs.grid()
+    grid = dict(pT=g["pT"], phi=g["phi"], y=g["y"], eta=g["eta"], eta_w=g["eta_w"])
+    res = api.spin_polarization(cells, w, sp, grid, T, dict(dimension=3))
+    d = tmp_path / ("expected_%d" % len(os.listdir(tmp_path)))
+    d.mkdir()
+    api.write_polarization(str(d), 3, g["pT"], g["phi"], g["y"], res)
+    return {nm: (d / nm).read_bytes() for nm in ("St.dat", "Sx.dat", "Sy.dat", "Sn.dat")}
+
+
+def test_cli_mode5_writes_polarization(tmp_path):
+    root, _, _ = mode5_run(tmp_path, "run", 300, dict(operation=1, set_FO_temperature=0))
+    r = run_cli(root)
+    assert "spin polarization" in r.stdout
+    with open(os.path.join(root, "average_thermodynamic_quantities.dat")) as f:
+        T = float(f.readline())
+    exp = expected_files(tmp_path, root, T)
+    for nm, b in exp.items():
+        assert open(os.path.join(root, "results", nm), "rb").read() == b, nm
+    # the operation's own output: the same as the same surface written in mode 1 gives
+    spec5 = open(os.path.join(root, "results", "dN_pTdpTdphidy.dat"), "rb").read()
+    root1, _, _ = mode5_run(tmp_path, "run_mode1", 300, dict(operation=1, set_FO_temperature=0, mode=1))
+    synth.write_surface_dat(os.path.join(root1, "input", "surface.dat"), synth.synth_surface(300, 3, seed=811))
+    run_cli(root1)
+    assert open(os.path.join(root1, "results", "dN_pTdpTdphidy.dat"), "rb").read() == spec5
+    assert not any(os.path.exists(os.path.join(root1, "results", nm)) for nm in exp)
+    # a second run appends
+    run_cli(root)
+    for nm, b in exp.items():
+        assert open(os.path.join(root, "results", nm), "rb").read() == b * 2, nm
+
+
+def test_cli_mode5_T_switch(tmp_path):
+    root, _, _ = mode5_run(tmp_path, "run", 120, dict(operation=1, set_FO_temperature=1), seed=821)
+    run_cli(root)
+    exp = expected_files(tmp_path, root, api.param_get(os.path.join(root, "iS3D_parameters.dat"), "T_switch"))
+    for nm, b in exp.items():
+        assert open(os.path.join(root, "results", nm), "rb").read() == b, nm
