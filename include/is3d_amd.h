@@ -573,7 +573,8 @@ int is3d_write_sampler_tests(const char *results_dir, const is3d_sampler_test_bi
  * each): bitwise reproducible, and a bin equals the running sum of dN_dy_cell over its cells.  The values are RAW sums (not divided by bin
  * widths; is3d_write_spacetime normalises).  dN_dydeta: 2+1D, per eta node k of the eta table, sum w_pT w_phi prefactor g p.dsigma f / w_k (:1365);
  * 3+1D one point (n_eta_eff = 1): the species' total (the reference's etaValues[0] is eta_fo of the LAST cell, :1155).  pT_w, phi_w: the
- * weights of pT_tab, phi_tab (column 2), HOST memory.  df_mode 3 / 4 (calculate_dN_dX_feqmod) is not built: IS3D_EINVAL.
+ * weights of pT_tab, phi_tab (column 2), HOST memory.  df_mode 3 / 4 (calculate_dN_dX_feqmod) goes through the *_feqmod entries below;
+ * the entries without feqmod tables refuse it with IS3D_EINVAL.
  * --------------------------------------------------------------------------------------------- */
 typedef struct {
     double tau_min, tau_max, r_min, r_max;  /* parameters tau_min ... r_bins (emissionfunction.cpp:216-222) */
@@ -616,6 +617,33 @@ int is3d_plan_execute_spacetime(is3d_plan *plan, const is3d_cells *cells, const 
  * (eta_values[k], v).  IS3D_EIO if the directory is missing. */
 int is3d_write_spacetime(const char *results_dir, const is3d_spacetime_bins *bins, int32_t n_species, const int64_t *mc_id, int32_t n_eta_eff,
                          const double *eta_values, const is3d_spacetime_out *out);
+
+/* Operation 0 with the modified equilibrium, df_mode 3 / 4 -- the drop-in for calculate_dN_dX_feqmod (emissionfunction_smooth_kernels.cpp:1449-2135):
+ * the same outputs, binning and order of additions as above; the per-cell integrand is that of is3d_smooth_spectra_feqmod (the linearised
+ * delta-f where feqmod breaks down, df_mode 3) except in three places the routine differs from the spectra one:
+ *   1. 3+1D: no switch to the linear delta-f for the rows |y - eta| < detA of cells with detA < 0.01 (:1926-1934 is commented out);
+ *   2. 2+1D: the eta nodes are stretched by detA whenever detA > deta_min (:1847-1849; the spectra path also requires detA < 1); weights and
+ *      the eta values written to the file are unchanged;
+ *   3. the nan / inf test is on renorm / detA in both dimensions (:1881), before the breakdown branch: a (cell, species) that fails it adds 0,
+ *      broken down or not.  p.dsigma keeps dsigma_eta inside the eta weight (:1943, :2010).
+ * include_baryon = 1 with df_mode 3 only (df_mode 4 exits in the reference). */
+typedef struct {
+    int64_t n_cells_breakdown;          /* cells where feqmod breaks down (df_mode 3; the reference prints a running count over species x cells) */
+    int64_t n_renorm_skipped;           /* (cell, species class) pairs that failed the test of point 3: they add 0 */
+    int64_t first_cell_out_of_range;    /* first cell left out because E_mod / T_mod can exceed 1e9 (IS3D_EDOMAIN, as the spectra path), or -1 */
+    double ms_renorm, ms_linear;        /* device time of the df_mode 3 renormalisation and of the linearised delta-f of the breakdown cells */
+} is3d_spacetime_feqmod_stats;
+
+/* one-shot host entry, the arguments of is3d_spacetime_distributions plus the feqmod tables; every argument check (NULL fq, df_mode 1 / 2,
+ * df_mode 4 with include_baryon, the bins, NULL x or y) precedes any device use */
+int is3d_spacetime_distributions_feqmod(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species,
+                                        const is3d_grid *grid, const double *pT_w, const double *phi_w, const is3d_df_tables *df,
+                                        const is3d_feqmod_tables *fq, const is3d_options *opts, const is3d_spacetime_bins *bins,
+                                        is3d_spacetime_out *out, is3d_spacetime_stats *stats, is3d_spacetime_feqmod_stats *fstats);
+/* is3d_plan_execute_spacetime on a plan of is3d_plan_create_feqmod (which that entry also accepts), with the extra counters */
+int is3d_plan_execute_spacetime_feqmod(is3d_plan *plan, const is3d_cells *cells, const double *x, const double *y, const double *pT_w,
+                                       const double *phi_w, const is3d_spacetime_bins *bins, const is3d_spacetime_out *out, void *hip_stream,
+                                       is3d_spacetime_stats *stats, is3d_spacetime_feqmod_stats *fstats);
 
 /* ---------------------------------------------------------------------------------------------
  * Spin polarization from thermal vorticity (mode 5) -- what EmissionFunctionArray::calculate_spin_polzn computes

@@ -110,6 +110,7 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_vah_plan_workspace_bytes", "is3d_vah_plan_execute", "is3d_vah_plan_set_timing", "is3d_vah_plan_timings",
            "is3d_vah_plan_tile_shape", "is3d_vah_plan_destroy", "is3d_surface_read_vah", "is3d_vah_plan_main_kernel_name", "is3d_math_probe", "is3d_resource_counters",
            "is3d_spacetime_distributions", "is3d_plan_execute_spacetime", "is3d_write_spacetime",
+           "is3d_spacetime_distributions_feqmod", "is3d_plan_execute_spacetime_feqmod",
            "is3d_spin_polarization", "is3d_polarization_plan_create", "is3d_polarization_plan_execute", "is3d_polarization_plan_destroy",
            "is3d_write_polarization", "is3d_surface_vorticity"]
 
@@ -149,6 +150,14 @@ class SpacetimeStats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
+class SpacetimeFeqmodStats(C.Structure):
+    _fields_ = [("n_cells_breakdown", C.c_int64), ("n_renorm_skipped", C.c_int64), ("first_cell_out_of_range", C.c_int64),
+                ("ms_renorm", C.c_double), ("ms_linear", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 SPACETIME_OUTPUTS = ["dN_dy", "dN_taudtaudy", "dN_twopirdrdy", "dN_twopitaurdtaudrdy", "dN_dydeta", "dN_dy_cell"]
@@ -269,6 +278,11 @@ def load():
                                                C.POINTER(Options), C.POINTER(SpacetimeBins), C.POINTER(SpacetimeOut), C.POINTER(SpacetimeStats)]
     L.is3d_plan_execute_spacetime.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_void_p, C.c_void_p, _dp, _dp, C.POINTER(SpacetimeBins),
                                               C.POINTER(SpacetimeOut), C.c_void_p, C.POINTER(SpacetimeStats)]
+    L.is3d_spacetime_distributions_feqmod.argtypes = [C.POINTER(Cells), _dp, _dp, C.POINTER(Species), C.POINTER(Grid), _dp, _dp,
+                                                      C.POINTER(DfTables), C.POINTER(FeqmodTables), C.POINTER(Options), C.POINTER(SpacetimeBins),
+                                                      C.POINTER(SpacetimeOut), C.POINTER(SpacetimeStats), C.POINTER(SpacetimeFeqmodStats)]
+    L.is3d_plan_execute_spacetime_feqmod.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_void_p, C.c_void_p, _dp, _dp, C.POINTER(SpacetimeBins),
+                                                     C.POINTER(SpacetimeOut), C.c_void_p, C.POINTER(SpacetimeStats), C.POINTER(SpacetimeFeqmodStats)]
     L.is3d_write_spacetime.argtypes = [C.c_char_p, C.POINTER(SpacetimeBins), C.c_int32, C.POINTER(C.c_int64), C.c_int32, _dp,
                                        C.POINTER(SpacetimeOut)]
     L.is3d_spin_polarization.argtypes = [C.POINTER(Cells), C.POINTER(Vorticity), C.POINTER(Species), C.POINTER(Grid), C.c_double,
@@ -559,11 +573,12 @@ def smooth_spectra(cells, species, grid, df, opts=None, out=None, fq=None):
     return out, st.as_dict()
 
 
-def spacetime_distributions(cells, species, grid, df, bins, opts=None, per_cell=False, x=None, y=None):
+def spacetime_distributions(cells, species, grid, df, bins, opts=None, per_cell=False, x=None, y=None, fq=None):
     """Operation 0 (is3d_spacetime_distributions, the drop-in for calculate_dN_dX): host arrays in, a dict of numpy arrays out -- the RAW bin
     sums dN_dy [S], dN_taudtaudy [S][tau_bins], dN_twopirdrdy [S][r_bins], dN_twopitaurdtaudrdy [S][tau_bins][r_bins], dN_dydeta
     [S][n_eta | 1], with per_cell also dN_dy_cell [S][n_cells] -- and "stats".  grid needs pT_w and phi_w; x, y default to cells["x"], cells["y"];
-    bins: dict tau_min, tau_max, tau_bins, r_min, r_max, r_bins."""
+    bins: dict tau_min, tau_max, tau_bins, r_min, r_max, r_bins.  With fq (df_mode 3, 4): is3d_spacetime_distributions_feqmod (the drop-in for
+    calculate_dN_dX_feqmod), and "feqmod_stats" as well."""
     L = load()
     sps, gs, ds, os_, _, keep = _pack_common(species, grid, df, opts)
     n = len(cells["tau"])
@@ -588,9 +603,18 @@ def spacetime_distributions(cells, species, grid, df, bins, opts=None, per_cell=
     so = SpacetimeOut(*[res[k].ctypes.data if k in res else None for k in SPACETIME_OUTPUTS])
     b = _spacetime_bins(bins)
     st = SpacetimeStats()
-    rc = L.is3d_spacetime_distributions(C.byref(cs), _p(xa) if xa is not None else None, _p(ya) if ya is not None else None, C.byref(sps),
-                                        C.byref(gs), _p(pw), _p(fw), C.byref(ds), C.byref(os_), C.byref(b), C.byref(so), C.byref(st))
-    _check(rc)
+    xp, yp = (_p(xa) if xa is not None else None), (_p(ya) if ya is not None else None)
+    if fq is not None:
+        fqs = _pack_feqmod(fq, keep)
+        fst = SpacetimeFeqmodStats()
+        rc = L.is3d_spacetime_distributions_feqmod(C.byref(cs), xp, yp, C.byref(sps), C.byref(gs), _p(pw), _p(fw), C.byref(ds), C.byref(fqs),
+                                                   C.byref(os_), C.byref(b), C.byref(so), C.byref(st), C.byref(fst))
+        _check(rc)
+        res["feqmod_stats"] = fst.as_dict()
+    else:
+        rc = L.is3d_spacetime_distributions(C.byref(cs), xp, yp, C.byref(sps), C.byref(gs), _p(pw), _p(fw), C.byref(ds), C.byref(os_), C.byref(b),
+                                            C.byref(so), C.byref(st))
+        _check(rc)
     res["stats"] = st.as_dict()
     return res
 
@@ -914,7 +938,8 @@ class Plan:
         if fq is not None:
             fqs = _pack_feqmod(fq, keep)
             _check(L.is3d_plan_create_feqmod(C.byref(self._h), C.byref(sps), C.byref(gs), C.byref(ds), C.byref(fqs), C.byref(os_), int(max_cells)))
-        else:
+        self.feqmod = fq is not None
+        if fq is None:
             _check(L.is3d_plan_create(C.byref(self._h), C.byref(sps), C.byref(gs), C.byref(ds), C.byref(os_), int(max_cells)))
         self.output_size = int(L.is3d_plan_output_size(self._h))
         assert self.output_size == nout
@@ -964,7 +989,8 @@ class Plan:
 
     def execute_spacetime(self, n_cells, cell_ptrs, x_ptr, y_ptr, pT_w, phi_w, bins, out_ptrs, stream=0, want_stats=True):
         """is3d_plan_execute_spacetime (operation 0): cell_ptrs, x_ptr, y_ptr and out_ptrs (dict name -> device pointer, SPACETIME_OUTPUTS;
-        dN_dy_cell optional) are device pointers, pT_w / phi_w host weight arrays."""
+        dN_dy_cell optional) are device pointers, pT_w / phi_w host weight arrays.  On a plan made with fq (df_mode 3, 4):
+        is3d_plan_execute_spacetime_feqmod, whose counters come back under "feqmod" in the stats dict."""
         cs = Cells()
         cs.n_cells = int(n_cells)
         for f in CELL_FIELDS:
@@ -975,6 +1001,13 @@ class Plan:
         so = SpacetimeOut(*[int(out_ptrs[k]) if out_ptrs.get(k) else None for k in SPACETIME_OUTPUTS])
         b = _spacetime_bins(bins)
         st = SpacetimeStats()
+        if self.feqmod:
+            fst = SpacetimeFeqmodStats()
+            rc = load().is3d_plan_execute_spacetime_feqmod(self._h, C.byref(cs), C.c_void_p(int(x_ptr or 0)), C.c_void_p(int(y_ptr or 0)), _p(pw),
+                                                           _p(fw), C.byref(b), C.byref(so), C.c_void_p(int(stream or 0)),
+                                                           C.byref(st) if want_stats else None, C.byref(fst) if want_stats else None)
+            _check(rc)
+            return dict(st.as_dict(), feqmod=fst.as_dict()) if want_stats else None
         rc = load().is3d_plan_execute_spacetime(self._h, C.byref(cs), C.c_void_p(int(x_ptr or 0)), C.c_void_p(int(y_ptr or 0)), _p(pw), _p(fw),
                                                 C.byref(b), C.byref(so), C.c_void_p(int(stream or 0)), C.byref(st) if want_stats else None)
         _check(rc)

@@ -86,11 +86,13 @@ struct FqLinearArgs {
 };
 
 size_t prep_feqmod_lds_bytes(int nT, int nj, int ngl, int J, int K, int jtiles, int rblocks, int rec);
-hipError_t launch_prep_feqmod(const FqPrepParams &p, hipStream_t st);
-// RN[cell][cls] = |n_linear / n_mod| (/ detA in 3+1D), 0 where the reference skips the species (nan / inf) or the cell
+// op0: the records of operation 0 (cf_spacetime_feqmod.hip; its departures are listed at cf_prep_feqmod)
+hipError_t launch_prep_feqmod(const FqPrepParams &p, hipStream_t st, bool op0 = false);
+// RN[cell][cls] = |n_linear / n_mod| (/ detA in 3+1D), 0 where the reference skips the species (nan / inf) or the cell.
+// op0_nskip != NULL: operation 0's form (cf_feqmod.hip, OP0), *op0_nskip += the (cell, class) pairs that fail its test
 hipError_t launch_feqmod_renorm(const double *CR, const double *gl, int ngl, const double *cls_mass, const double *cls_sign,
                                 const double *cls_baryon /* NULL: include_baryon = 0 */, int ncls, int n_cells, int include_bulk,
-                                int is_dim3, double *RN, hipStream_t st);
+                                int is_dim3, double *RN, hipStream_t st, unsigned long long *op0_nskip = nullptr);
 hipError_t launch_main_feqmod(int variant, int dim3, int outflow, int mode3, int baryon, const FqMainArgs &a, hipStream_t st);
 // list = indices with flag != 0 in ascending order, *count = their number; status[4] += #flag 1, status[5] += #flag 2
 hipError_t launch_feqmod_compact(const int32_t *flag, int n, int32_t *list, int32_t *count, unsigned long long *status,

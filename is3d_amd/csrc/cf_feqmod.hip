@@ -89,7 +89,12 @@ __device__ __forceinline__ double fq_beta(double ax, double ay, double az, doubl
     return (2.0 * __builtin_fma(az, bz, __builtin_fma(ay, by, ax * bx))) * invTm2;
 }
 
-template <int CB>
+// OP0: the records of operation 0 (calculate_dN_dX_feqmod, smooth_kernels.cpp:1449-2135; cf_spacetime_feqmod.hip), which differs from the
+// spectra routine in three places: no narrow-row fallback in 3+1D (:1926-1934 commented out), the 2+1D eta scaling without the upper bound detA < 1
+// (:1847-1849), and the nan / inf test on renorm / detA in both dimensions (:1881; df_mode 4 here, df_mode 3 in cf_feqmod_renorm), before the
+// breakdown branch.  p.dsigma carries dsigma_eta inside the eta weight (:1943, :2010).  status[2] counts the cells of that test (df_mode 4);
+// CR slot 5 holds 2 for a breakdown cell, whose |renorm| is tested all the same.
+template <int CB, bool OP0>
 __global__ void __launch_bounds__(kFqThreads) cf_prep_feqmod(FqPrepParams p)
 {
     extern __shared__ double lds[];
@@ -204,8 +209,8 @@ __global__ void __launch_bounds__(kFqThreads) cf_prep_feqmod(FqPrepParams p)
             const double P = p.cells.P[gi], E = p.cells.E[gi];
             double bulkPi = (valid && p.include_bulk) ? p.cells.bulkPi[gi] : 0.0;
             if (valid && p.mode == 4) {                                               // :584-590
-                if (bulkPi < -P) bulkPi = -(1.0 - 1.e-5) * P;
-                else if (bulkPi / P > p.bp_max) bulkPi = P * (p.bp_max - 1.e-5);
+                if (OP0 ? bulkPi <= -P : bulkPi < -P) bulkPi = -(1.0 - 1.e-5) * P;   // operation 0: <= and >= (:1708-1712)
+                else if (OP0 ? bulkPi / P >= p.bp_max : bulkPi / P > p.bp_max) bulkPi = P * (p.bp_max - 1.e-5);
                 const double r = bulkPi / P;
                 if (!(r >= jx[0] && r <= jx[nj - 1])) {                               // outside the Jonah table (P <= 0, NaN)
                     atomicMin(&p.status[0], (unsigned long long)gi);
@@ -284,13 +289,19 @@ __global__ void __launch_bounds__(kFqThreads) cf_prep_feqmod(FqPrepParams p)
                     if (detA <= p.detA_min || (neq_pion0 + dn_pion0) < 0.0) breakdown = true;
                 }
                 double eta_scale = 1.0;
-                if (detA > p.detA_min && detA < 1.0 && !p.dim3) eta_scale = detA;     // :727-728
+                if (detA > p.detA_min && (OP0 || detA < 1.0) && !p.dim3) eta_scale = detA;   // :727-728 (operation 0: :1847-1849)
                 double rn = 1.0;
                 if (p.mode == 4) {                                                    // :761-777
                     if (p.include_bulk) rn = z;
-                    if (p.dim3) rn /= detA;
-                    rn = fabs(rn);
-                    if (isnan(rn) || isinf(rn)) rn = 0.0;                             // :768-772: every species skipped
+                    if (OP0) {                                                        // :1881-1891
+                        const double q = rn / detA;
+                        if (isnan(q) || isinf(q)) { rn = 0.0; atomicAdd(&p.status[2], 1ULL); }
+                        else rn = fabs(p.dim3 ? q : rn);
+                    } else {
+                        if (p.dim3) rn /= detA;
+                        rn = fabs(rn);
+                        if (isnan(rn) || isinf(rn)) rn = 0.0;                         // :768-772: every species skipped
+                    }
                 }
                 // Exponent range of the main kernel's exponential (exp_p9, |v| < 1.4e9): E_mod/T_mod <= (1 + ||A^-1||_F) E_LRF / T_mod with
                 // E_LRF = p.u <= mTmax (u^tau + |tau u^eta|) cosh(max |y - eta|).  A cell beyond it -- a singular or nearly singular A that the
@@ -309,7 +320,7 @@ __global__ void __launch_bounds__(kFqThreads) cf_prep_feqmod(FqPrepParams p)
                     }
                 }
                 if (leave_out) breakdown = false;
-                const bool narrow = p.dim3 && !breakdown && !leave_out && detA < 0.01;   // :807-813
+                const bool narrow = !OP0 && p.dim3 && !breakdown && !leave_out && detA < 0.01;   // :807-813
                 s.dat = dat; s.dax = dax; s.day = day; s.dan_tau = dan / tau;
                 s.eta = p.dim3 ? p.cells.eta[gi] : 0.0;
                 s.eta_scale = eta_scale;
@@ -324,7 +335,7 @@ __global__ void __launch_bounds__(kFqThreads) cf_prep_feqmod(FqPrepParams p)
                 flag = breakdown ? 1 : (narrow ? 2 : 0);
                 if (p.mode == 3) {
                     double *cr = p.CR + (int64_t)cell * kCrRec;
-                    cr[0] = T; cr[1] = T_mod; cr[2] = bulkPi / betabulk; cr[3] = F; cr[4] = detA; cr[5] = s.live;
+                    cr[0] = T; cr[1] = T_mod; cr[2] = bulkPi / betabulk; cr[3] = F; cr[4] = detA; cr[5] = (OP0 && breakdown) ? 2.0 : s.live;
                     cr[6] = alphaB; cr[7] = G;
                 }
                 if (flag) {
@@ -398,7 +409,8 @@ __global__ void __launch_bounds__(kFqThreads) cf_prep_feqmod(FqPrepParams p)
             const double ch = cosh(dlt), sh = sinh(dlt);
             const double a0 = -s.Xt * ch + s.tXn * sh, a2 = -s.Zt * ch + s.tZn * sh;  // p_LRF = mT a + pT b, :913
             const double ax = s.Ai[0] * a0 + s.Ai[2] * a2, ay = s.Ai[3] * a0 + s.Ai[5] * a2, az = s.Ai[6] * a0 + s.Ai[8] * a2;
-            l_A[idx] = (v * s.rn) * (w * ch * s.dat + sh * s.dan_tau);                // dsigma_eta outside the eta weight, :905
+            if (OP0) l_A[idx] = (v * s.rn) * (w * ch * s.dat + w * (sh * s.dan_tau));   // operation 0: inside it, :2010
+            else l_A[idx] = (v * s.rn) * (w * ch * s.dat + sh * s.dan_tau);           // dsigma_eta outside the eta weight, :905
             l_W[idx] = (v * s.rn) * w;
             l_al[idx] = (1.0 + (ax * ax + ay * ay + az * az)) * s.invTm2;
             l_ax[idx] = ax; l_ay[idx] = ay; l_az[idx] = az;
@@ -530,15 +542,18 @@ size_t prep_feqmod_lds_bytes(int nT, int nj, int ngl, int J, int K, int jtiles, 
     return sizeof(double) * ((size_t)nT * 7 + (size_t)nj * 5 + (size_t)ngl * 4 + (size_t)cb * (6 * K + 5 * J + K * jtiles) + bounds + (size_t)rec) + sizeof(FqScal) * cb;   // + one int2 per record element
 }
 
-hipError_t launch_prep_feqmod(const FqPrepParams &p, hipStream_t st)
+hipError_t launch_prep_feqmod(const FqPrepParams &p, hipStream_t st, bool op0)
 {
     if (p.n_cells <= 0) return hipSuccess;
     const int cb = fq_batch_cells(p.K);
     const int nbatch = (p.n_cells + cb - 1) / cb;
     const int grid = nbatch < 4096 ? nbatch : 4096;
     const size_t lds = prep_feqmod_lds_bytes(p.spl.n, p.nj, p.ngl, p.J, p.K, p.jtiles, p.rblocks, 4 * p.JT + p.R * (4 + p.JT));
-    if (cb == kFqCB3) hipLaunchKernelGGL(cf_prep_feqmod<kFqCB3>, dim3(grid), dim3(kFqThreads), lds, st, p);
-    else hipLaunchKernelGGL(cf_prep_feqmod<kFqCB>, dim3(grid), dim3(kFqThreads), lds, st, p);
+    if (op0) {
+        if (cb == kFqCB3) hipLaunchKernelGGL((cf_prep_feqmod<kFqCB3, true>), dim3(grid), dim3(kFqThreads), lds, st, p);
+        else hipLaunchKernelGGL((cf_prep_feqmod<kFqCB, true>), dim3(grid), dim3(kFqThreads), lds, st, p);
+    } else if (cb == kFqCB3) hipLaunchKernelGGL((cf_prep_feqmod<kFqCB3, false>), dim3(grid), dim3(kFqThreads), lds, st, p);
+    else hipLaunchKernelGGL((cf_prep_feqmod<kFqCB, false>), dim3(grid), dim3(kFqThreads), lds, st, p);
     return hipGetLastError();
 }
 
@@ -546,11 +561,14 @@ hipError_t launch_prep_feqmod(const FqPrepParams &p, hipStream_t st)
 // df_mode 3 renormalisation, smooth_kernels.cpp:747-777: renorm = n_linear / n_mod per (cell, species); the degeneracy
 // cancels in the ratio, so one value per (mass, sign) class serves all its species.
 // ------------------------------------------------------------------------------------------------
+// OP0 (operation 0, :1854-1891): breakdown cells (CR slot 5 = 2) are tested too; the test is on renorm / detA in both dimensions, a pair that
+// fails it gets 0 and is counted in *nskip; a breakdown cell that passes gets 1 (cf_st_fq_linear reads it as a switch).
 constexpr int kGlMax = 256;   // n_gla <= 256 (checked by the plan)
+template <bool OP0>
 __global__ void __launch_bounds__(256)
 cf_feqmod_renorm(const double *__restrict__ CR, const double *__restrict__ gl, int ngl, const double *__restrict__ cls_mass,
                  const double *__restrict__ cls_sign, const double *__restrict__ cls_baryon, int ncls, int n_cells, int include_bulk,
-                 int dim3, double *__restrict__ RN)
+                 int dim3, double *__restrict__ RN, unsigned long long *__restrict__ nskip)
 {
     // node constants once per workgroup: w p e^p (alpha = 1 nodes: neq_int, J10_int) and w e^p (alpha = 2 nodes: J20_int) -- the
     // integrands of gt_neq / gt_J10 / gt_J20 above with the node-only exponential taken out (one exp per node and integral
@@ -590,7 +608,9 @@ cf_feqmod_renorm(const double *__restrict__ CR, const double *__restrict__ gl, i
                 const double e = __builtin_fmin(exp_full(sqrt_nr(l_p1[k] + mb2) - chem), 1.0e300), r = rcp_nr(e + sign);
                 s_neq = __builtin_fma(c1, r, s_neq);
                 if (baryon != 0.0) s_n10 = __builtin_fma(c1, (e * r) * r, s_n10);
-                s_mod = __builtin_fma(c1, rcp_nr(__builtin_fmin(exp_full(sqrt_nr(l_p1[k] + mm2) - chem_mod), 1.0e300) + sign), s_mod);
+                const double em = exp_full(sqrt_nr(l_p1[k] + mm2) - chem_mod);
+                // operation 0 tests renorm for inf: a node whose exponential overflows adds exactly 0 there, as 1 / (exp() + sign) does
+                if (!(OP0 && isinf(em))) s_mod = __builtin_fma(c1, rcp_nr(__builtin_fmin(em, 1.0e300) + sign), s_mod);
                 const double E2 = sqrt_nr(l_p2[k] + mb2), e2 = __builtin_fmin(exp_full(E2 - chem), 1.0e300), r2 = rcp_nr(e2 + sign);
                 s_j20 = __builtin_fma(l_c2[k], E2 * ((e2 * r2) * r2), s_j20);
             }
@@ -601,7 +621,11 @@ cf_feqmod_renorm(const double *__restrict__ CR, const double *__restrict__ gl, i
             const double n_mod = nmod_fact * s_mod;
             renorm = n_linear / n_mod;
         }
-        if (isnan(renorm) || isinf(renorm)) renorm = 0.0;                             // :768-772: species skipped in this cell
+        if (OP0) {
+            const double q = renorm / detA;
+            if (isnan(q) || isinf(q)) { renorm = 0.0; atomicAdd(nskip, 1ULL); }
+            else renorm = cr[5] == 2.0 ? 1.0 : fabs(dim3 ? q : renorm);
+        } else if (isnan(renorm) || isinf(renorm)) renorm = 0.0;                      // :768-772: species skipped in this cell
         else {
             if (dim3) renorm /= detA;
             renorm = fabs(renorm);
@@ -612,12 +636,16 @@ cf_feqmod_renorm(const double *__restrict__ CR, const double *__restrict__ gl, i
 
 hipError_t launch_feqmod_renorm(const double *CR, const double *gl, int ngl, const double *cls_mass, const double *cls_sign,
                                 const double *cls_baryon, int ncls, int n_cells, int include_bulk, int is_dim3, double *RN,
-                                hipStream_t st)
+                                hipStream_t st, unsigned long long *op0_nskip)
 {
     if (n_cells <= 0) return hipSuccess;
     const int64_t n = (int64_t)n_cells * ncls;
-    hipLaunchKernelGGL(cf_feqmod_renorm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, CR, gl, ngl, cls_mass, cls_sign,
-                       cls_baryon, ncls, n_cells, include_bulk, is_dim3, RN);
+    if (op0_nskip)
+        hipLaunchKernelGGL(cf_feqmod_renorm<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, CR, gl, ngl, cls_mass, cls_sign,
+                           cls_baryon, ncls, n_cells, include_bulk, is_dim3, RN, op0_nskip);
+    else
+        hipLaunchKernelGGL(cf_feqmod_renorm<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, CR, gl, ngl, cls_mass, cls_sign,
+                           cls_baryon, ncls, n_cells, include_bulk, is_dim3, RN, nullptr);
     return hipGetLastError();
 }
 

@@ -80,6 +80,7 @@ struct is3d_plan {
     int st_npTp = 0, st_nlw = 0;
     int64_t st_pass = 0, st_cap = 0;
     DevBuf<double> d_st_mT, d_st_pT, d_st_sign, d_st_b, d_st_wpT, d_st_wphi, d_st_pg, d_st_D, d_st_slab, d_st_eta;
+    DevBuf<double> d_st_mass;   // feqmod: the lanes' masses (the linearised delta-f of the breakdown cells)
     DevBuf<int32_t> d_st_cls, d_st_keys, d_st_cnt, d_st_tot, d_st_list;
     DevBuf<int64_t> d_st_start;
     DevBuf<unsigned long long> d_st_counters;
@@ -995,10 +996,13 @@ extern "C" int is3d_smooth_spectra_feqmod(const is3d_cells *cells, const is3d_sp
 // ---------------------------------------------------------------------------------------------
 // operation 0: smooth spacetime distributions (calculate_dN_dX, emissionfunction_smooth_kernels.cpp:1000-1446), cf_spacetime.hip
 // ---------------------------------------------------------------------------------------------
-static int st_check(const is3d_spacetime_bins *b, const double *x, const double *y, int df_mode)
+static int st_check(const is3d_spacetime_bins *b, const double *x, const double *y, int df_mode, bool feqmod = false)
 {
-    if (df_mode == 3 || df_mode == 4)
-        return fail(IS3D_EINVAL, "operation 0 with df_mode %d needs calculate_dN_dX_feqmod, which is not built yet (df_mode 1 or 2)", df_mode);
+    if (!feqmod && (df_mode == 3 || df_mode == 4))
+        return fail(IS3D_EINVAL, "operation 0 with df_mode %d is calculate_dN_dX_feqmod: use is3d_spacetime_distributions_feqmod / "
+                    "is3d_plan_execute_spacetime_feqmod (this entry takes df_mode 1 or 2)", df_mode);
+    if (feqmod && df_mode != 3 && df_mode != 4)
+        return fail(IS3D_EINVAL, "the feqmod entries of operation 0 take df_mode 3 or 4 (got %d)", df_mode);
     if (!x || !y) return fail(IS3D_EINVAL, "operation 0 needs the cells' x and y positions (NULL given)");
     if (!b) return fail(IS3D_EINVAL, "null spacetime bins");
     if (b->tau_bins < 1 || b->r_bins < 1) return fail(IS3D_EINVAL, "tau_bins and r_bins must be >= 1 (got %d, %d)", b->tau_bins, b->r_bins);
@@ -1018,11 +1022,12 @@ static int st_setup(is3d_plan *P)
     P->st_npTp = npTp;
     P->st_nlw = (P->ncls * npTp + 63) / 64;
     const int nl = P->st_nlw * 64;
-    std::vector<double> mT(nl, 1.0), pT(nl, 0.0), sg(nl, 1.0), b(nl, 0.0);
+    std::vector<double> mT(nl, 1.0), pT(nl, 0.0), sg(nl, 1.0), b(nl, 0.0), ms(nl, 1.0);
     for (int l = 0; l < nl; l++) {
         const int c = l / npTp, i = l % npTp;
         if (c >= P->ncls || i >= P->npT) continue;   // padded lanes: finite operands, w_pT = 0
         const double m = P->cls_mass[c], p = P->pT_grid[i];
+        ms[l] = m;
         mT[l] = std::sqrt(m * m + p * p);
         pT[l] = p;
         sg[l] = P->cls_sign[c];
@@ -1032,6 +1037,7 @@ static int st_setup(is3d_plan *P)
     HIP_TRY(P->d_st_pT.upload(pT));
     HIP_TRY(P->d_st_sign.upload(sg));
     HIP_TRY(P->d_st_b.upload(b));
+    if (P->feqmod) HIP_TRY(P->d_st_mass.upload(ms));
     HIP_TRY(P->d_st_wpT.alloc(nl));
     HIP_TRY(P->d_st_wphi.alloc((size_t)P->jtiles * P->JT));
     HIP_TRY(P->d_st_cls.upload(P->sp_cls));
@@ -1058,23 +1064,28 @@ static hipError_t st_grow(DevBuf<T> &buf, size_t n)
     return buf.alloc(std::max<size_t>(n, 1));
 }
 
-extern "C" int is3d_plan_execute_spacetime(is3d_plan *P, const is3d_cells *cells, const double *x, const double *y, const double *pT_w,
-                                           const double *phi_w, const is3d_spacetime_bins *bins, const is3d_spacetime_out *out, void *hip_stream,
-                                           is3d_spacetime_stats *stats)
+// the breakdown cells' workgroup slots of cf_st_fq_linear (2+1D: eta partial slots after the chunks')
+static int st_linear_slots(int64_t nc) { return (int)std::max<int64_t>(1, std::min<int64_t>(64, nc)); }
+
+static int st_execute(is3d_plan *P, const is3d_cells *cells, const double *x, const double *y, const double *pT_w, const double *phi_w,
+                      const is3d_spacetime_bins *bins, const is3d_spacetime_out *out, void *hip_stream, is3d_spacetime_stats *stats,
+                      is3d_spacetime_feqmod_stats *fstats)
 {
     if (stats) { memset(stats, 0, sizeof *stats); stats->bad_cell = -1; }
+    if (fstats) { memset(fstats, 0, sizeof *fstats); fstats->first_cell_out_of_range = -1; }
     if (!P || !cells || !out || !pT_w || !phi_w) return fail(IS3D_EINVAL, "null argument");
-    int rc = st_check(bins, x, y, P->opts.df_mode);
+    int rc = st_check(bins, x, y, P->opts.df_mode, P->feqmod);
     if (rc) return rc;
-    if (P->feqmod) return fail(IS3D_EINVAL, "operation 0 with df_mode %d needs calculate_dN_dX_feqmod, which is not built yet", P->opts.df_mode);
-    if (!is3d::spacetime_shape_supported(P->dim3, P->JT, P->KT))
+    if (P->feqmod ? !is3d::spacetime_feqmod_shape_supported(P->dim3, P->JT, P->KT) : !is3d::spacetime_shape_supported(P->dim3, P->JT, P->KT))
         return fail(IS3D_EINVAL, "operation 0 runs on the plan's unit records of the default tile shapes (this plan: kernel variant %d, %d x %d)",
                     P->variant, P->JT, P->KT);
     if (P->npT > 64) return fail(IS3D_EINVAL, "operation 0 takes pT grids of up to 64 values (got %d)", P->npT);
     {
         int npTp = 1;
         while (npTp < P->npT) npTp <<= 1;
-        if (!P->dim3 && sizeof(double) * 4 * (64 / npTp) * (size_t)P->K > 64 * 1024)
+        // the feqmod kernel keeps 16 KiB of LDS for its staged records
+        const size_t cap = P->feqmod ? 48 * 1024 : 64 * 1024;
+        if (!P->dim3 && sizeof(double) * 4 * (64 / npTp) * (size_t)P->K > cap)
             return fail(IS3D_EINVAL, "operation 0 in 2+1D: %d pT values x %d eta nodes need more LDS than the per-cell kernel has", P->npT, P->K);
     }
     if (!out->dN_dy || !out->dN_taudtaudy || !out->dN_twopirdrdy || !out->dN_twopitaurdtaudrdy || !out->dN_dydeta)
@@ -1119,7 +1130,7 @@ extern "C" int is3d_plan_execute_spacetime(is3d_plan *P, const is3d_cells *cells
         ev.push_back(e);
         return hipEventRecord(e, st);
     };
-    std::vector<int> stage;   // stage of the interval that ends at event i: 0 prep, 1 cells, 2 bins
+    std::vector<int> stage;   // stage of the interval that ends at event i: 0 prep, 1 cells, 2 bins, 3 renormalisation, 4 linearised delta-f
     HIP_TRY(status_begin(P, st));
     HIP_TRY(hipMemsetAsync(P->d_st_counters.p, 0, 4 * sizeof(unsigned long long), st));
     HIP_TRY(mark());
@@ -1154,33 +1165,88 @@ extern "C" int is3d_plan_execute_spacetime(is3d_plan *P, const is3d_cells *cells
         for (int h = 0; h < 3; h++) HIP_TRY(hipMemsetAsync(hout[h], 0, sizeof(double) * S * Bs[h], st));
         HIP_TRY(hipMemsetAsync(out->dN_dydeta, 0, sizeof(double) * S * n_eta_eff, st));
     } else {
-        HIP_TRY(is3d::launch_pds_bound(is3d::cell_ptrs(*cells), n, P->dim3, P->kmin, P->kmax, P->gw2d, P->mTmax, P->pTmax, P->d_status.p + 6, st));
+        // (the feqmod records carry p.dsigma unscaled)
+        if (!P->feqmod)
+            HIP_TRY(is3d::launch_pds_bound(is3d::cell_ptrs(*cells), n, P->dim3, P->kmin, P->kmax, P->gw2d, P->mTmax, P->pTmax, P->d_status.p + 6, st));
         const int64_t pc = P->st_pass;
         const int G = (P->st_nlw + 3) / 4;
         int nch = (int)std::min<int64_t>(pc, std::max<int64_t>(1, 16384 / G));
         if (!P->dim3) nch = (int)std::max<int64_t>(1, std::min<int64_t>(nch, ((int64_t)256 << 20) / (8 * (int64_t)P->ncls * K)));
-        if (!P->dim3) HIP_TRY(st_grow(P->d_st_slab, (size_t)nch * P->ncls * K));
+        const int GL = P->feqmod ? st_linear_slots(pc) : 0;
+        if (!P->dim3) HIP_TRY(st_grow(P->d_st_slab, (size_t)(nch + GL) * P->ncls * K));
         const int npasses = (int)((n + pc - 1) / pc);
         for (int pass = 0; pass < npasses; pass++) {
             const int64_t c0 = (int64_t)pass * pc;
             const int32_t nc = (int32_t)std::min<int64_t>(pc, n - c0);
-            is3d::PrepParams pp = fill_prep(P, cells, c0, nc);
-            pp.tiled = 1;
-            pp.pds_bound = P->d_status.p + 6;
-            pp.TE = nullptr;   // the E2 tables of cf_main_tile3e are not needed here
-            HIP_TRY(is3d::launch_prep(pp, st));
-            HIP_TRY(mark()); stage.push_back(0);
+            if (P->feqmod) {
+                // ---- the feqmod records (operation 0's form), df_mode 3 renormalisation, per-cell stage, breakdown cells ----
+                is3d::FqPrepParams fp{};
+                fp.cells = is3d::cell_ptrs(*cells);
+                fp.baryon = P->baryon; fp.baryondiff = P->baryondiff; fp.bil = P->bil;
+                fp.cell0 = c0; fp.n_cells = nc; fp.J = P->J; fp.K = K;
+                fp.dim3 = P->dim3; fp.mode = o.df_mode;
+                fp.include_bulk = o.include_bulk_deltaf != 0; fp.include_shear = o.include_shear_deltaf != 0;
+                fp.cosphi = P->d_cosphi.p; fp.sinphi = P->d_sinphi.p; fp.kgrid = P->d_kgrid.p; fp.kweight = P->d_kweight.p;
+                fp.spl = P->spl;
+                fp.nj = P->nj;
+                fp.jx = P->d_jonah.p; fp.jl2 = fp.jx + P->nj; fp.jz = fp.jx + 2 * P->nj; fp.jcl = fp.jx + 3 * P->nj; fp.jcz = fp.jx + 4 * P->nj;
+                fp.bp_max = P->bp_max;
+                fp.mTmax = P->mTmax; fp.kmin = P->kmin; fp.kmax = P->kmax;
+                fp.pTmax = P->pTmax; fp.scale_rows = 0;   // D holds the unscaled value: no power-of-two row scale
+                fp.ngl = P->ngl; fp.gl = P->d_gl.p;
+                fp.detA_min = P->detA_min; fp.mass_pion0 = P->mass_pion0;
+                fp.JT = P->JT; fp.R = P->KT; fp.jtiles = P->jtiles; fp.rblocks = P->rblocks;
+                fp.TS = P->d_TS.p; fp.CR = P->d_CR.p; fp.FB = P->d_FB.p; fp.flag = P->d_flag.p;
+                fp.status = P->d_status.p;
+                HIP_TRY(is3d::launch_prep_feqmod(fp, st, true));
+                HIP_TRY(mark()); stage.push_back(0);
+                if (o.df_mode == 3) {
+                    HIP_TRY(is3d::launch_feqmod_renorm(P->d_CR.p, P->d_gl.p, P->ngl, P->d_cls_mass.p, P->d_cls_sign.p,
+                                                       P->baryon ? P->d_cls_baryon.p : nullptr, P->ncls, nc, fp.include_bulk, P->dim3,
+                                                       P->d_RN.p, st, P->d_status.p + 2));
+                    HIP_TRY(mark()); stage.push_back(3);
+                }
+                is3d::StFqCellArgs a{};
+                a.TS = P->d_TS.p; a.nc = nc; a.J = P->J; a.K = K; a.jtiles = P->jtiles; a.rblocks = P->rblocks;
+                a.ncls = P->ncls; a.npTp = P->st_npTp; a.nlw = P->st_nlw; a.G = G; a.nch = (int)std::min<int64_t>(nch, nc);
+                a.zskip = o.zero_skip != 2;
+                a.lane_mT = P->d_st_mT.p; a.lane_pT = P->d_st_pT.p; a.lane_sign = P->d_st_sign.p; a.lane_b = P->d_st_b.p; a.lane_wpT = P->d_st_wpT.p;
+                a.wphi = P->d_st_wphi.p; a.RN = o.df_mode == 3 ? P->d_RN.p : nullptr;
+                a.D = P->d_st_D.p; a.eta_slab = P->dim3 ? nullptr : P->d_st_slab.p;
+                HIP_TRY(is3d::launch_spacetime_feqmod_cells(a, P->dim3, o.df_mode == 3, P->baryon, o.outflow != 0, P->JT, P->KT, st));
+                HIP_TRY(mark()); stage.push_back(1);
+                HIP_TRY(is3d::launch_feqmod_compact(P->d_flag.p, nc, P->d_list.p, P->d_count.p, P->d_status.p, st));
+                is3d::StFqLinearArgs la{};
+                la.FB = P->d_FB.p; la.list = P->d_list.p; la.count = P->d_count.p;
+                la.lane_mT = P->d_st_mT.p; la.lane_pT = P->d_st_pT.p; la.lane_sign = P->d_st_sign.p; la.lane_mass = P->d_st_mass.p;
+                la.lane_b = P->baryon ? P->d_st_b.p : nullptr; la.lane_wpT = P->d_st_wpT.p;
+                la.cosphi = P->d_cosphi.p; la.sinphi = P->d_sinphi.p; la.wphi = P->d_st_wphi.p; la.kgrid = P->d_kgrid.p; la.kweight = P->d_kweight.p;
+                la.RN = o.df_mode == 3 ? P->d_RN.p : nullptr;
+                la.nc = nc; la.J = P->J; la.K = K; la.ncls = P->ncls; la.npTp = P->st_npTp; la.nlw = P->st_nlw; la.G = G; la.GL = GL; la.nch = a.nch;
+                la.dim3 = P->dim3; la.mode = o.df_mode; la.outflow = o.outflow != 0; la.regulate = o.regulate_deltaf != 0;
+                la.D = P->d_st_D.p; la.eta_slab = P->dim3 ? nullptr : P->d_st_slab.p;
+                HIP_TRY(is3d::launch_spacetime_feqmod_linear(la, st));
+                if (!P->dim3) HIP_TRY(is3d::launch_spacetime_eta_reduce(P->d_st_slab.p, a.nch + GL, (int64_t)P->ncls * K, pass == 0, P->d_st_eta.p, st));
+                HIP_TRY(mark()); stage.push_back(4);
+            } else {
+                is3d::PrepParams pp = fill_prep(P, cells, c0, nc);
+                pp.tiled = 1;
+                pp.pds_bound = P->d_status.p + 6;
+                pp.TE = nullptr;   // the E2 tables of cf_main_tile3e are not needed here
+                HIP_TRY(is3d::launch_prep(pp, st));
+                HIP_TRY(mark()); stage.push_back(0);
 
-            is3d::StCellArgs a{};
-            a.TS = P->d_TS.p; a.nc = nc; a.J = P->J; a.K = K; a.jtiles = P->jtiles; a.rblocks = P->rblocks;
-            a.ncls = P->ncls; a.npTp = P->st_npTp; a.nlw = P->st_nlw; a.G = G; a.nch = (int)std::min<int64_t>(nch, nc);
-            a.outflow = o.outflow != 0; a.regulate = o.regulate_deltaf != 0; a.zskip = o.zero_skip != 2;
-            a.lane_mT = P->d_st_mT.p; a.lane_pT = P->d_st_pT.p; a.lane_sign = P->d_st_sign.p; a.lane_b = P->d_st_b.p; a.lane_wpT = P->d_st_wpT.p;
-            a.wphi = P->d_st_wphi.p; a.pds_bound = P->d_status.p + 6;
-            a.D = P->d_st_D.p; a.eta_slab = P->dim3 ? nullptr : P->d_st_slab.p;
-            HIP_TRY(is3d::launch_spacetime_cells(a, P->ce, P->dim3, P->baryon, P->JT, P->KT, st));
-            if (!P->dim3) HIP_TRY(is3d::launch_spacetime_eta_reduce(P->d_st_slab.p, a.nch, (int64_t)P->ncls * K, pass == 0, P->d_st_eta.p, st));
-            HIP_TRY(mark()); stage.push_back(1);
+                is3d::StCellArgs a{};
+                a.TS = P->d_TS.p; a.nc = nc; a.J = P->J; a.K = K; a.jtiles = P->jtiles; a.rblocks = P->rblocks;
+                a.ncls = P->ncls; a.npTp = P->st_npTp; a.nlw = P->st_nlw; a.G = G; a.nch = (int)std::min<int64_t>(nch, nc);
+                a.outflow = o.outflow != 0; a.regulate = o.regulate_deltaf != 0; a.zskip = o.zero_skip != 2;
+                a.lane_mT = P->d_st_mT.p; a.lane_pT = P->d_st_pT.p; a.lane_sign = P->d_st_sign.p; a.lane_b = P->d_st_b.p; a.lane_wpT = P->d_st_wpT.p;
+                a.wphi = P->d_st_wphi.p; a.pds_bound = P->d_status.p + 6;
+                a.D = P->d_st_D.p; a.eta_slab = P->dim3 ? nullptr : P->d_st_slab.p;
+                HIP_TRY(is3d::launch_spacetime_cells(a, P->ce, P->dim3, P->baryon, P->JT, P->KT, st));
+                if (!P->dim3) HIP_TRY(is3d::launch_spacetime_eta_reduce(P->d_st_slab.p, a.nch, (int64_t)P->ncls * K, pass == 0, P->d_st_eta.p, st));
+                HIP_TRY(mark()); stage.push_back(1);
+            }
 
             // ---- bin stage, part 2: this pass's cells, in ascending order, onto the running sums ----
             HIP_TRY(is3d::launch_spacetime_segsum(P->d_st_D.p, nc, c0, P->d_st_cls.p, P->d_st_pg.p, S, nullptr, nullptr, 1, pass == 0, out->dN_dy, st));
@@ -1205,7 +1271,16 @@ extern "C" int is3d_plan_execute_spacetime(is3d_plan *P, const is3d_cells *cells
         for (size_t i = 1; i < ev.size(); i++) {
             float ms = 0;
             HIP_TRY(hipEventElapsedTime(&ms, ev[i - 1], ev[i]));
+            if (stage[i - 1] >= 3) {
+                if (fstats) (stage[i - 1] == 3 ? fstats->ms_renorm : fstats->ms_linear) += ms;
+                continue;
+            }
             (stage[i - 1] == 0 ? stats->ms_prep : stage[i - 1] == 1 ? stats->ms_cells : stats->ms_bins) += ms;
+        }
+        if (fstats && n > 0) {
+            fstats->n_cells_breakdown = (int64_t)h[4];
+            fstats->n_renorm_skipped = (int64_t)h[2] * (o.df_mode == 4 ? P->ncls : 1);   // df_mode 4: whole cells (cf_prep_feqmod)
+            fstats->first_cell_out_of_range = h[7] == ~0ULL ? -1 : (int64_t)h[7];
         }
         stats->n_classes = P->ncls;
         stats->n_passes = n == 0 ? 0 : (int32_t)((n + P->st_pass - 1) / P->st_pass);
@@ -1219,17 +1294,41 @@ extern "C" int is3d_plan_execute_spacetime(is3d_plan *P, const is3d_cells *cells
     return IS3D_OK;
 }
 
-extern "C" int is3d_spacetime_distributions(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species,
-                                            const is3d_grid *grid, const double *pT_w, const double *phi_w, const is3d_df_tables *df,
-                                            const is3d_options *opts, const is3d_spacetime_bins *bins, is3d_spacetime_out *out,
-                                            is3d_spacetime_stats *stats)
+extern "C" int is3d_plan_execute_spacetime(is3d_plan *P, const is3d_cells *cells, const double *x, const double *y, const double *pT_w,
+                                           const double *phi_w, const is3d_spacetime_bins *bins, const is3d_spacetime_out *out, void *hip_stream,
+                                           is3d_spacetime_stats *stats)
+{
+    return st_execute(P, cells, x, y, pT_w, phi_w, bins, out, hip_stream, stats, nullptr);
+}
+
+extern "C" int is3d_plan_execute_spacetime_feqmod(is3d_plan *P, const is3d_cells *cells, const double *x, const double *y, const double *pT_w,
+                                                  const double *phi_w, const is3d_spacetime_bins *bins, const is3d_spacetime_out *out,
+                                                  void *hip_stream, is3d_spacetime_stats *stats, is3d_spacetime_feqmod_stats *fstats)
+{
+    if (P && !P->feqmod) {
+        if (stats) { memset(stats, 0, sizeof *stats); stats->bad_cell = -1; }
+        if (fstats) { memset(fstats, 0, sizeof *fstats); fstats->first_cell_out_of_range = -1; }
+        return fail(IS3D_EINVAL, "is3d_plan_execute_spacetime_feqmod needs a plan of is3d_plan_create_feqmod (df_mode 3 or 4)");
+    }
+    // the counters need the stream's status words: an execute with fstats reports them as one with stats does
+    is3d_spacetime_stats local{};
+    return st_execute(P, cells, x, y, pT_w, phi_w, bins, out, hip_stream, stats ? stats : (fstats ? &local : nullptr), fstats);
+}
+
+static int st_oneshot(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species, const is3d_grid *grid,
+                      const double *pT_w, const double *phi_w, const is3d_df_tables *df, const is3d_feqmod_tables *fq, const is3d_options *opts,
+                      const is3d_spacetime_bins *bins, is3d_spacetime_out *out, is3d_spacetime_stats *stats, is3d_spacetime_feqmod_stats *fstats)
 {
     if (stats) { memset(stats, 0, sizeof *stats); stats->bad_cell = -1; }
+    if (fstats) { memset(fstats, 0, sizeof *fstats); fstats->first_cell_out_of_range = -1; }
     if (!cells || !out || !opts || !pT_w || !phi_w) return fail(IS3D_EINVAL, "null argument");
-    int rc = st_check(bins, x, y, opts->df_mode);
+    int rc = st_check(bins, x, y, opts->df_mode, fq != nullptr);
+    if (!rc && fq && opts->include_baryon && opts->df_mode == 4)
+        rc = fail(IS3D_EINVAL, "df_mode 4 does not work with include_baryon = 1 (the reference exits there too)");
+    if (!rc && fq) rc = validate(species, grid, df, fq, opts);   // every check before the plan touches the device
     if (rc) { if (stats) stats->code = rc; return rc; }
     is3d_plan *P = nullptr;
-    rc = plan_create_impl(&P, species, grid, df, nullptr, opts, std::max<int64_t>(cells->n_cells, 1));
+    rc = plan_create_impl(&P, species, grid, df, fq, opts, std::max<int64_t>(cells->n_cells, 1));
     if (rc) { if (stats) stats->code = rc; return rc; }
     struct Guard { is3d_plan *p; ~Guard() { is3d_plan_destroy(p); } } guard{P};
     const int64_t n = cells->n_cells;
@@ -1264,7 +1363,7 @@ extern "C" int is3d_spacetime_distributions(const is3d_cells *cells, const doubl
     dev.dN_dy = dev_out[0]; dev.dN_taudtaudy = dev_out[1]; dev.dN_twopirdrdy = dev_out[2]; dev.dN_twopitaurdtaudrdy = dev_out[3];
     dev.dN_dydeta = dev_out[4]; dev.dN_dy_cell = dev_out[5];
     is3d_spacetime_stats stt{};
-    rc = is3d_plan_execute_spacetime(P, &dc, dx, dy, pT_w, phi_w, bins, &dev, nullptr, &stt);
+    rc = st_execute(P, &dc, dx, dy, pT_w, phi_w, bins, &dev, nullptr, &stt, fstats);
     if (rc) { if (stats) *stats = stt; return rc; }
     HIP_TRY(hipEventRecord(e2, nullptr));
     for (int i = 0; i < 6; i++)
@@ -1279,4 +1378,25 @@ extern "C" int is3d_spacetime_distributions(const is3d_cells *cells, const doubl
     stt.code = IS3D_OK;
     if (stats) *stats = stt;
     return IS3D_OK;
+}
+
+extern "C" int is3d_spacetime_distributions(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species,
+                                            const is3d_grid *grid, const double *pT_w, const double *phi_w, const is3d_df_tables *df,
+                                            const is3d_options *opts, const is3d_spacetime_bins *bins, is3d_spacetime_out *out,
+                                            is3d_spacetime_stats *stats)
+{
+    return st_oneshot(cells, x, y, species, grid, pT_w, phi_w, df, nullptr, opts, bins, out, stats, nullptr);
+}
+
+extern "C" int is3d_spacetime_distributions_feqmod(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species,
+                                                   const is3d_grid *grid, const double *pT_w, const double *phi_w, const is3d_df_tables *df,
+                                                   const is3d_feqmod_tables *fq, const is3d_options *opts, const is3d_spacetime_bins *bins,
+                                                   is3d_spacetime_out *out, is3d_spacetime_stats *stats, is3d_spacetime_feqmod_stats *fstats)
+{
+    if (!fq) {
+        if (stats) { memset(stats, 0, sizeof *stats); stats->bad_cell = -1; stats->code = IS3D_EINVAL; }
+        if (fstats) { memset(fstats, 0, sizeof *fstats); fstats->first_cell_out_of_range = -1; }
+        return fail(IS3D_EINVAL, "null feqmod tables");
+    }
+    return st_oneshot(cells, x, y, species, grid, pT_w, phi_w, df, fq, opts, bins, out, stats, fstats);
 }

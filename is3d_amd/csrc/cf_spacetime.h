@@ -5,6 +5,35 @@
 #include <cstdint>
 namespace is3d {
 
+// operation 0 with the modified equilibrium (cf_spacetime_feqmod.hip): the per-cell stage on cf_prep_feqmod's OP0 records of one pass of nc
+// cells (3+1D 8 x 7, 2+1D 8 x 31), D[cls * nc + cell] = sum_pT w_pT sum_phi w_phi sum_(y | eta) p.dsigma f; 2+1D: eta_slab[chunk][cls][k]
+struct StFqCellArgs {
+    const double *TS;
+    int32_t nc, J, K, jtiles, rblocks;
+    int32_t ncls, npTp, nlw, G, nch;
+    int32_t zskip;
+    const double *lane_mT, *lane_pT, *lane_sign, *lane_b, *lane_wpT;   // [nlw * 64]
+    const double *wphi;                                                // [jtiles * JT], 0 past J
+    const double *RN;                                                  // df_mode 3: [nc][ncls] |renorm| (cf_feqmod_renorm<true>)
+    double *D;                                                         // [ncls][nc]
+    double *eta_slab;                                                  // 2+1D: [nch + GL][ncls][K]
+};
+// the breakdown cells of a pass (cf_feqmod_compact's list): D of those cells, 2+1D eta partials into slab slots nch .. nch + GL - 1
+struct StFqLinearArgs {
+    const double *FB;
+    const int32_t *list, *count;
+    const double *lane_mT, *lane_pT, *lane_sign, *lane_mass, *lane_b, *lane_wpT;   // lane_b: include_baryon, else NULL
+    const double *cosphi, *sinphi, *wphi, *kgrid, *kweight;
+    const double *RN;                                                  // df_mode 3
+    int32_t nc, J, K, ncls, npTp, nlw, G, GL, nch;
+    int32_t dim3, mode, outflow, regulate;
+    double *D, *eta_slab;
+};
+bool spacetime_feqmod_shape_supported(int dim3, int JT, int R);
+size_t spacetime_feqmod_eta_lds(int dim3, int npTp, int K);
+hipError_t launch_spacetime_feqmod_cells(const StFqCellArgs &a, int dim3, int mode3, int baryon, int outflow, int JT, int R, hipStream_t st);
+hipError_t launch_spacetime_feqmod_linear(const StFqLinearArgs &a, hipStream_t st);
+
 // per-cell stage: lanes <-> (class, pT) with npTp (a power of two <= 64) lane slots per class; reads the unit-record stream TS that cf_prep
 // wrote for one pass of nc cells and writes D[cls * nc + cell] = unscale * sum_pT w_pT sum_phi w_phi sum_(y | eta) p.dsigma f
 // (prefactor and degeneracy not applied).  2+1D: eta_slab[chunk][cls][k] receives the chunk's (cls, eta node) partials.

@@ -170,7 +170,7 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         DIE("operation = %d: operation = 0 (smooth spacetime distributions), 1 (smooth momentum spectra) and 2 (particle sampler) are on this path", operation);
     if (operation == 0) {
         if (df_mode == 3 || df_mode == 4)
-            DIE("operation = 0 with df_mode = %d needs calculate_dN_dX_feqmod, which is not built yet: set df_mode = 1 or 2", df_mode);
+            DIE("operation = 0 with df_mode = %d (calculate_dN_dX_feqmod) is not run by this driver yet (the library entry is3d_spacetime_distributions_feqmod has it): set df_mode = 1 or 2", df_mode);
         if (!mem && mode == 2) DIE("operation = 0 with mode = 2: the reference has no spacetime distribution for anisotropic hydro");
         if (mem && (!mem_x || !mem_y)) DIE("operation = 0 needs the cells' x and y positions (NULL given)");
     }
