@@ -700,6 +700,74 @@ int is3d_write_polarization(const char *results_dir, int32_t dimension, int32_t 
                             const double *phi, int32_t n_y, const double *y, const is3d_polarization_out *out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Resonance decay feed-down -- what EmissionFunctionArray::do_resonance_decays (src/cpp/emissionfunction_resonance_decays.cpp:124-2158)
+ * computes if its exit(-1) at entry (:128-129) is taken away.  Parents: the unstable chosen species, chosen-list order from the LAST to
+ * index 1; each parent's log dN is taken from the spectrum as it stands at its turn (so it holds the feed-down of every parent before it).
+ * Its 2-body (adjusted-mass loop :243-258) and 3-body (Q factor, 12-point s integral) channels, in file order, feed the daughters that are
+ * in the chosen list (same-type daughters grouped, multiplicity as weight); 1- and 4-body channels add nothing.  The (v, zeta) integrands
+ * use 12 x 12 Gauss-Legendre points and read the parent by bilinear interpolation of log dN in (Phi, M_T) (2+1D; 3+1D: also linear in Y)
+ * up to the M_T switch, and the exponential M_T fit of each (y, phi) row above it.  Divergences from the reference:
+ * the switch is the minimum over rows of M_T at the last pT index before the row's first non-positive value (the reference's MTmax, the
+ * last node, for a positive spectrum); the 2-body recoil mass is the partner's (the reference takes particle_2's for every group) and the
+ * channel's adjusted masses are used throughout; the acos argument is clamped to [-1, 1] (counted in n_clamps); what the reference exits
+ * on is a return code.  The spectrum is [n_chosen][n_pT][n_phi][n_y_eff] in the library's layout, species fastest (n_y_eff = 1 in 2+1D).
+ * Deterministic: each (daughter, bin) has one writer per parent that adds the parent's channels in channel order; no floating-point atomics.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct {                        /* is3d_pdg_read_decays' output: entries in file order with the synthesised antibaryon entries */
+    int32_t n;
+    const int64_t *mc_id;
+    const double *mass, *width;
+    const int32_t *stable;              /* decays_Npart[0] == 1 (readindata.cpp:1487) */
+    const int32_t *n_channels;          /* per entry; entry i's channels follow those of entries 0 .. i-1 */
+    const int32_t *npart;               /* per channel, as in the file (|npart| products; negative values occur) */
+    const double *branch_ratio;         /* per channel */
+    const int64_t *daughters;           /* [channel][5], 0 = none */
+} is3d_decay_table;
+
+typedef struct {
+    int32_t code;
+    int32_t n_parents;                  /* unstable chosen parents visited */
+    int32_t n_channels;                 /* 2- and 3-body channels with at least one chosen daughter (integrated) */
+    int32_t n_adjusted;                 /* ... of which 2-body channels whose masses the adjustment loop changed */
+    int64_t n_clamps;                   /* quadrature points whose cos(Phi~) was clamped to [-1, 1] */
+    int64_t n_points;                   /* quadrature points per execute: bins x (144 | 1728) summed over every (parent, daughter, channel group) */
+    double ms_tables, ms_feed;          /* device time of the per-parent table kernels (log, fit, switch) and of the feed-down kernels */
+    double ms_h2d, ms_d2h;              /* one-shot entry only */
+} is3d_decay_stats;
+
+/* PDG_Data::read_resonances_conventional (readindata.cpp:1440-1568) in full, for hrg_eos = 1, 2.  Two-call pattern: mc_id == NULL returns
+ * *n (the entries is3d_pdg_read counts) and *n_channels_total.  Antibaryon entries copy their baryon's channels with every daughter negated
+ * unless it has baryon = charge = strangeness = 0 (:1510-1535).  More than 50 channels or 5 products, a truncated or non-numeric record, or a
+ * daughter of an unstable antibaryon channel that cannot be found: IS3D_EIO. */
+int is3d_pdg_read_decays(const char *path, int32_t *n, int32_t *n_channels_total, int64_t *mc_id, double *mass, double *width,
+                         int32_t *stable, int32_t *n_channels, int32_t *npart, double *branch_ratio, int64_t *daughters, int32_t capacity,
+                         int32_t channel_capacity);
+/* calculate_Q_factor (:99-121): the 3-body phase-space normalisation, 24-point Gauss-Legendre.  Host only. */
+double is3d_decay_q_factor(double mass_parent, double mass_1, double mass_2, double mass_3);
+/* one-shot: dN_inout is a HOST spectrum, fed down in place.  chosen_mc_id: the chosen list in its order (each must be in the table).
+ * EINVAL: fewer than 2 chosen species, a chosen or daughter id missing from the table, a 5-body channel, a daughter mass driven negative by
+ * the adjustment.  EDOMAIN: a pT / phi (/ y) grid that does not ascend (or pT <= 0); a (y, phi) row of a parent with fewer than 2 points for
+ * the M_T fit (the message names the parent's mc_id and the row).  On EDOMAIN from the fit the device spectrum of the plan entry holds the
+ * feed-down of the parents before the failing one. */
+int is3d_resonance_decays(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id, const is3d_grid *grid,
+                          int32_t dimension, int32_t device, double *dN_inout, is3d_decay_stats *stats);
+/* device-resident form: the schedule, groups, E*, p*, Q, s nodes and M_T nodes go to the device at create; execute feeds down the DEVICE
+ * spectrum dN_inout on hip_stream (NULL = default) and synchronises it (a failed fit is reported by the return code).  stats != NULL times
+ * every kernel.  The one-shot is create + upload + execute + download: the two agree bit for bit. */
+typedef struct is3d_decay_plan is3d_decay_plan;
+int is3d_decay_plan_create(is3d_decay_plan **plan, const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
+                           const is3d_grid *grid, int32_t dimension, int32_t device);
+int64_t is3d_decay_plan_output_size(const is3d_decay_plan *plan);
+int is3d_decay_plan_execute(is3d_decay_plan *plan, double *dN_inout, void *hip_stream, is3d_decay_stats *stats);
+void is3d_decay_plan_destroy(is3d_decay_plan *plan);
+/* write_dN_pTdpTdphidy_with_resonance_decays_toFile and write_dN_dpTdphidy_with_resonance_decays_toFile (emissionfunction.cpp:452-488,
+ * :555-590): APPEND to <results_dir>/dN_pTdpTdphidy_resonance_decays.dat ("y\tphip\tpT\tdN", scientific, setprecision(8), species outer, then
+ * y, phi, pT, a blank line after each phi block) and <results_dir>/dN_dpTdphidy_resonance_decays.dat (a header line, then the same with
+ * dN x pT).  2+1D: y = 0 (y may be NULL).  IS3D_EIO if a file cannot be opened. */
+int is3d_write_results_decays(const char *results_dir, int32_t dimension, int32_t n_species, int32_t n_pT, const double *pT, int32_t n_phi,
+                              const double *phi, int32_t n_y, const double *y, const double *dN);
+
+/* ---------------------------------------------------------------------------------------------
  * Driver: IS3D::run_particlization (src/cpp/iS3D.cpp:74-192; class IS3D, src/cpp/iS3D.h:19-96).  Reads iS3D_parameters.dat,
  * PDG/, tables/, deltaf_coefficients/ from the current directory and writes results/ exactly as the command line tool does
  * (which is this call with surface = NULL).  surface != NULL is the embedding path (read_fo_surf_from_memory +

@@ -112,7 +112,9 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_spacetime_distributions", "is3d_plan_execute_spacetime", "is3d_write_spacetime",
            "is3d_spacetime_distributions_feqmod", "is3d_plan_execute_spacetime_feqmod",
            "is3d_spin_polarization", "is3d_polarization_plan_create", "is3d_polarization_plan_execute", "is3d_polarization_plan_destroy",
-           "is3d_write_polarization", "is3d_surface_vorticity"]
+           "is3d_write_polarization", "is3d_surface_vorticity",
+           "is3d_pdg_read_decays", "is3d_decay_q_factor", "is3d_resonance_decays", "is3d_decay_plan_create", "is3d_decay_plan_output_size",
+           "is3d_decay_plan_execute", "is3d_decay_plan_destroy", "is3d_write_results_decays"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 POLARIZATION_OUTPUTS = ["St", "Sx", "Sy", "Sn", "Snorm"]
@@ -132,6 +134,19 @@ class PolarizationStats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+class DecayTable(C.Structure):
+    _fields_ = [("n", C.c_int32), ("mc_id", C.c_void_p), ("mass", C.c_void_p), ("width", C.c_void_p), ("stable", C.c_void_p),
+                ("n_channels", C.c_void_p), ("npart", C.c_void_p), ("branch_ratio", C.c_void_p), ("daughters", C.c_void_p)]
+
+
+class DecayStats(C.Structure):
+    _fields_ = [("code", C.c_int32), ("n_parents", C.c_int32), ("n_channels", C.c_int32), ("n_adjusted", C.c_int32), ("n_clamps", C.c_int64), ("n_points", C.c_int64),
+                ("ms_tables", C.c_double), ("ms_feed", C.c_double), ("ms_h2d", C.c_double), ("ms_d2h", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
 
 class SpacetimeBins(C.Structure):
     _fields_ = [("tau_min", C.c_double), ("tau_max", C.c_double), ("r_min", C.c_double), ("r_max", C.c_double),
@@ -295,6 +310,19 @@ def load():
     L.is3d_write_polarization.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, _dp,
                                           C.POINTER(PolarizationOut)]
     L.is3d_surface_vorticity.argtypes = [C.c_void_p, C.POINTER(_dp)]
+    _i32p, _i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    L.is3d_pdg_read_decays.argtypes = [C.c_char_p, _i32p, _i32p, _i64p, _dp, _dp, _i32p, _i32p, _i32p, _dp, _i64p, C.c_int32, C.c_int32]
+    L.is3d_decay_q_factor.restype = C.c_double
+    L.is3d_decay_q_factor.argtypes = [C.c_double] * 4
+    L.is3d_resonance_decays.argtypes = [C.POINTER(DecayTable), C.c_int32, _i64p, C.POINTER(Grid), C.c_int32, C.c_int32, _dp,
+                                        C.POINTER(DecayStats)]
+    L.is3d_decay_plan_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(DecayTable), C.c_int32, _i64p, C.POINTER(Grid), C.c_int32, C.c_int32]
+    L.is3d_decay_plan_output_size.restype = C.c_int64
+    L.is3d_decay_plan_output_size.argtypes = [C.c_void_p]
+    L.is3d_decay_plan_execute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DecayStats)]
+    L.is3d_decay_plan_destroy.argtypes = [C.c_void_p]
+    L.is3d_decay_plan_destroy.restype = None
+    L.is3d_write_results_decays.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp]
     _LIB = L
     return L
 
@@ -742,6 +770,95 @@ def write_polarization(results_dir, dimension, pT, phi, y, res, n_species=None):
     po = PolarizationOut(*[arrs[k].ctypes.data for k in POLARIZATION_OUTPUTS])
     _check(L.is3d_write_polarization(results_dir.encode(), int(dimension), int(n_species), len(pT), _p(pT), len(phi), _p(phi),
                                      len(yv), _p(yv), C.byref(po)))
+
+
+def pdg_read_decays(path):
+    """is3d_pdg_read_decays (hrg_eos 1, 2): dict of per-entry mc_id, mass, width, stable, n_channels and per-channel npart, branch_ratio,
+    daughters [n_channels_total, 5] (entry i's channels follow those of the entries before it)."""
+    L = load()
+    n, nc = C.c_int32(0), C.c_int32(0)
+    _check(L.is3d_pdg_read_decays(path.encode(), C.byref(n), C.byref(nc), None, None, None, None, None, None, None, None, 0, 0))
+    t = dict(mc_id=np.zeros(n.value, np.int64), mass=np.zeros(n.value), width=np.zeros(n.value), stable=np.zeros(n.value, np.int32),
+             n_channels=np.zeros(n.value, np.int32), npart=np.zeros(nc.value, np.int32), branch_ratio=np.zeros(nc.value),
+             daughters=np.zeros((nc.value, 5), np.int64))
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+    i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))  # noqa: E731
+    _check(L.is3d_pdg_read_decays(path.encode(), C.byref(n), C.byref(nc), i64(t["mc_id"]), _p(t["mass"]), _p(t["width"]), i32(t["stable"]),
+                                  i32(t["n_channels"]), i32(t["npart"]), _p(t["branch_ratio"]), i64(t["daughters"]), n.value, nc.value))
+    return t
+
+
+def decay_q_factor(mass_parent, m1, m2, m3):
+    """is3d_decay_q_factor: calculate_Q_factor, the 3-body normalisation (host)."""
+    return load().is3d_decay_q_factor(float(mass_parent), float(m1), float(m2), float(m3))
+
+
+def _decay_pack(table, chosen_mc_id, grid):
+    keep = dict(mc_id=np.ascontiguousarray(table["mc_id"], np.int64), mass=_f64(table["mass"]), width=_f64(table["width"]),
+                stable=np.ascontiguousarray(table["stable"], np.int32), n_channels=np.ascontiguousarray(table["n_channels"], np.int32),
+                npart=np.ascontiguousarray(table["npart"], np.int32), branch_ratio=_f64(table["branch_ratio"]),
+                daughters=np.ascontiguousarray(table["daughters"], np.int64).reshape(-1))
+    ts = DecayTable(len(keep["mc_id"]), *[keep[k].ctypes.data for k in ["mc_id", "mass", "width", "stable", "n_channels", "npart",
+                                                                         "branch_ratio", "daughters"]])
+    ch = np.ascontiguousarray(chosen_mc_id, np.int64)
+    g = {k: _f64(grid[k]) if grid.get(k) is not None else _f64([0.0]) for k in ["pT", "phi", "y"]}
+    gs = Grid(len(g["pT"]), _p(g["pT"]), len(g["phi"]), _p(g["phi"]), len(g["y"]), _p(g["y"]), 0, None, None)
+    keep.update(ch=ch, g=g)
+    return ts, ch, gs, keep
+
+
+def resonance_decays(table, chosen_mc_id, grid, dN, dimension=2, device=-1):
+    """is3d_resonance_decays: the feed-down of a host spectrum (flat, species fastest, n_y_eff = 1 in 2+1D).  Returns (fed-down copy, stats).
+    table: pdg_read_decays' dict; chosen_mc_id: the chosen list in its order; grid: dict pT, phi (and y in 3+1D)."""
+    L = load()
+    ts, ch, gs, keep = _decay_pack(table, chosen_mc_id, grid)
+    out = np.array(dN, dtype=np.float64, copy=True).reshape(-1)
+    st = DecayStats()
+    _check(L.is3d_resonance_decays(C.byref(ts), len(ch), ch.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(gs), int(dimension), int(device),
+                                   _p(out), C.byref(st)))
+    return out, st.as_dict()
+
+
+class DecayPlan:
+    """Device-resident feed-down (is3d_decay_plan_*): execute(dN_ptr) feeds down a DEVICE spectrum in place, e.g. a torch tensor's data_ptr()."""
+
+    def __init__(self, table, chosen_mc_id, grid, dimension=2, device=-1):
+        L = load()
+        ts, ch, gs, _ = _decay_pack(table, chosen_mc_id, grid)
+        self._h = C.c_void_p()
+        _check(L.is3d_decay_plan_create(C.byref(self._h), C.byref(ts), len(ch), ch.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(gs),
+                                        int(dimension), int(device)))
+        self.output_size = L.is3d_decay_plan_output_size(self._h)
+
+    def execute(self, dN_ptr, stream=0, want_stats=True):
+        st = DecayStats()
+        _check(load().is3d_decay_plan_execute(self._h, C.c_void_p(int(dN_ptr)), C.c_void_p(int(stream or 0)),
+                                              C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
+    def close(self):
+        if self._h:
+            load().is3d_decay_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def write_results_decays(results_dir, dimension, pT, phi, y, dN, n_species=None):
+    """is3d_write_results_decays: appends dN_pTdpTdphidy_resonance_decays.dat and dN_dpTdphidy_resonance_decays.dat under results_dir."""
+    L = load()
+    pT, phi = _f64(pT), _f64(phi)
+    yv = _f64(y if y is not None else [0.0])
+    d = _f64(dN).reshape(-1)
+    ny_eff = 1 if dimension == 2 else len(yv)
+    if n_species is None:
+        n_species = d.size // (len(pT) * len(phi) * ny_eff)
+    _check(L.is3d_write_results_decays(results_dir.encode(), int(dimension), int(n_species), len(pT), _p(pT), len(phi), _p(phi), len(yv),
+                                       _p(yv), _p(d)))
 
 
 def shard_bounds(n_cells, rank, n_ranks):

@@ -988,6 +988,156 @@ extern "C" int is3d_pdg_read(const char *path, int32_t *n, int64_t *mc_id, doubl
 }
 
 // ---------------------------------------------------------------------------------------------
+// PDG_Data::read_resonances_conventional in full (readindata.cpp:1440-1568): the entries of is3d_pdg_read with their decay channels.
+//   Per channel "dummy Npart branch d0 d1 d2 d3 d4"; stable = Npart[0] == 1 (:1487).  An antibaryon entry copies its baryon's channels; a
+//   non-zero daughter is looked up among the entries read so far (first match, :1517-1519) and kept if that entry has baryon = charge =
+//   strangeness = 0, else negated (:1527-1528).  Not found: the reference exits when the baryon is unstable and the branch ratio exceeds
+//   1e-15 (IS3D_EIO here); otherwise it reads the antibaryon entry itself, whose quantum numbers are nonzero: negated.  The entry of the
+//   read that hits EOF is dropped as in is3d_pdg_read, with its channels.
+// ---------------------------------------------------------------------------------------------
+extern "C" int is3d_pdg_read_decays(const char *path, int32_t *n, int32_t *n_channels_total, int64_t *mc_id, double *mass, double *width,
+                                    int32_t *stable, int32_t *n_channels, int32_t *npart, double *branch_ratio, int64_t *daughters,
+                                    int32_t capacity, int32_t channel_capacity)
+{
+    if (!path || !n || !n_channels_total) return io_fail(IS3D_EINVAL, "null argument");
+    std::string text;
+    if (!slurp(path, text)) return io_fail(IS3D_EIO, "cannot open %s", path);
+    struct Ch { int np; double br; long d[5]; };
+    struct Ent { long id; double m, w; int b, s, q, stable; std::vector<Ch> ch; };
+    std::vector<Ent> v;
+    std::vector<std::string> tok;
+    {
+        std::istringstream ss(text);
+        std::string t;
+        while (ss >> t) tok.push_back(t);
+    }
+    const bool trailing_ws = !text.empty() && isspace((unsigned char)text.back());
+    auto num_l = [&](size_t k, long &out) {
+        char *e;
+        out = strtol(tok[k].c_str(), &e, 10);
+        return *e == '\0' && e != tok[k].c_str();
+    };
+    auto num_d = [&](size_t k, double &out) {
+        char *e;
+        out = strtod(tok[k].c_str(), &e);
+        return *e == '\0' && e != tok[k].c_str();
+    };
+    size_t i = 0;
+    while (i < tok.size()) {
+        if (i + 12 > tok.size()) return io_fail(IS3D_EIO, "%s: truncated particle record", path);
+        Ent e;
+        long b, s, q, decays;
+        if (!num_l(i, e.id) || !num_d(i + 2, e.m) || !num_d(i + 3, e.w) || !num_l(i + 5, b) || !num_l(i + 6, s) || !num_l(i + 10, q) ||
+            !num_l(i + 11, decays))
+            return io_fail(IS3D_EIO, "%s: non-numeric field in the record at token %zu", path, i);
+        e.b = (int)b; e.s = (int)s; e.q = (int)q;
+        if (decays < 0 || decays > 50) return io_fail(IS3D_EIO, "%s: particle %ld has %ld decay channels (max 50)", path, e.id, decays);
+        if (i + 12 + 8 * (size_t)decays > tok.size()) return io_fail(IS3D_EIO, "%s: truncated decay table of particle %ld", path, e.id);
+        for (long j = 0; j < decays; j++) {
+            const size_t k = i + 12 + 8 * (size_t)j;
+            Ch c;
+            long np;
+            if (!num_l(k + 1, np) || !num_d(k + 2, c.br)) return io_fail(IS3D_EIO, "%s: particle %ld channel %ld is not numeric", path, e.id, j);
+            if (np > 5 || np < -5) return io_fail(IS3D_EIO, "%s: particle %ld channel %ld has %ld products (max 5)", path, e.id, j, np);
+            c.np = (int)np;
+            for (int d = 0; d < 5; d++)
+                if (!num_l(k + 3 + d, c.d[d])) return io_fail(IS3D_EIO, "%s: particle %ld channel %ld: daughter %d is not numeric", path, e.id, j, d);
+            e.ch.push_back(c);
+        }
+        e.stable = (!e.ch.empty() && e.ch[0].np == 1) ? 1 : 0;
+        i += 12 + 8 * (size_t)decays;
+        v.push_back(e);
+        if (e.b > 0) {
+            Ent a = e;
+            a.id = -e.id; a.b = -e.b; a.s = -e.s; a.q = -e.q;
+            for (Ch &c : a.ch)
+                for (int d = 0; d < 5; d++) {
+                    if (c.d[d] == 0) continue;
+                    const Ent *f = nullptr;
+                    for (const Ent &x : v)
+                        if (x.id == c.d[d]) { f = &x; break; }
+                    if (!f && !e.stable && c.br > 1e-15)
+                        return io_fail(IS3D_EIO, "%s: can not find decay particle %ld of anti-baryon %ld", path, c.d[d], a.id);
+                    if (!f) f = &a;
+                    if (!(f->b == 0 && f->q == 0 && f->s == 0)) c.d[d] = -c.d[d];
+                }
+            v.push_back(a);
+        }
+    }
+    if (!trailing_ws && !v.empty()) v.pop_back();
+    size_t nch = 0;
+    for (const Ent &e : v) nch += e.ch.size();
+    *n = (int32_t)v.size();
+    *n_channels_total = (int32_t)nch;
+    if (!mc_id) return IS3D_OK;
+    if ((int32_t)v.size() > capacity || (int64_t)nch > channel_capacity)
+        return io_fail(IS3D_EINVAL, "%s: capacity %d / %d < %zu particles / %zu channels", path, capacity, channel_capacity, v.size(), nch);
+    size_t c0 = 0;
+    for (size_t k = 0; k < v.size(); k++) {
+        const Ent &e = v[k];
+        mc_id[k] = e.id;
+        if (mass) mass[k] = e.m;
+        if (width) width[k] = e.w;
+        if (stable) stable[k] = e.stable;
+        if (n_channels) n_channels[k] = (int32_t)e.ch.size();
+        for (const Ch &c : e.ch) {
+            if (npart) npart[c0] = c.np;
+            if (branch_ratio) branch_ratio[c0] = c.br;
+            if (daughters)
+                for (int d = 0; d < 5; d++) daughters[c0 * 5 + d] = c.d[d];
+            c0++;
+        }
+    }
+    return IS3D_OK;
+}
+
+// write_dN_pTdpTdphidy_with_resonance_decays_toFile, write_dN_dpTdphidy_with_resonance_decays_toFile (emissionfunction.cpp:452-488,
+// :555-590): row prefixes by the reference's own manipulators, values by std::to_chars as in is3d_write_results
+extern "C" int is3d_write_results_decays(const char *dir, int32_t dimension, int32_t npart, int32_t npT, const double *pT, int32_t nphi,
+                                         const double *phi, int32_t ny, const double *y, const double *dN)
+{
+    if (!dir || !pT || !phi || !dN) return io_fail(IS3D_EINVAL, "null argument");
+    if (dimension != 2 && dimension != 3) return io_fail(IS3D_EINVAL, "dimension = %d: 2 or 3", dimension);
+    if (dimension == 3 && !y) return io_fail(IS3D_EINVAL, "3+1D output needs the y grid");
+    if (npart < 0 || npT < 0 || nphi < 0 || (dimension == 3 && ny < 0)) return io_fail(IS3D_EINVAL, "negative grid or species count");
+    const int y_pts = (dimension == 2) ? 1 : ny;
+    std::vector<std::string> prefix((size_t)y_pts * nphi * npT);
+    for (int iy = 0; iy < y_pts; iy++)
+        for (int iphip = 0; iphip < nphi; iphip++)
+            for (int ipT = 0; ipT < npT; ipT++) {
+                std::ostringstream f;
+                f << std::scientific << std::setw(5) << std::setprecision(8) << ((dimension == 2) ? 0.0 : y[iy]) << "\t" << phi[iphip] << "\t"
+                  << pT[ipT] << "\t";
+                prefix[((size_t)iy * nphi + iphip) * npT + ipT] = f.str();
+            }
+    const char *names[2] = {"/dN_pTdpTdphidy_resonance_decays.dat", "/dN_dpTdphidy_resonance_decays.dat"};
+    for (int which = 0; which < 2; which++) {
+        std::string out;
+        if (which == 1) out = "y\tphip\tpT\tdN_dpTdphidy\n";
+        char num[40];
+        for (int ipart = 0; ipart < npart; ipart++)
+            for (int iy = 0; iy < y_pts; iy++)
+                for (int iphip = 0; iphip < nphi; iphip++) {
+                    for (int ipT = 0; ipT < npT; ipT++) {
+                        const long long iS3D = (long long)ipart + (long long)npart * ((long long)ipT + (long long)npT * ((long long)iphip + (long long)nphi * iy));
+                        const double value = which ? dN[iS3D] * pT[ipT] : dN[iS3D];
+                        out += prefix[((size_t)iy * nphi + iphip) * npT + ipT];
+                        const auto r = std::to_chars(num, num + sizeof num, value, std::chars_format::scientific, 8);
+                        out.append(num, (size_t)(r.ptr - num));
+                        out.push_back('\n');
+                    }
+                    out.push_back('\n');
+                }
+        const std::string p = std::string(dir) + names[which];
+        FILE *f = fopen(p.c_str(), "ab");
+        if (!f) return io_fail(IS3D_EIO, "cannot open %s (the results directory must exist)", p.c_str());
+        const bool ok = fwrite(out.data(), 1, out.size(), f) == out.size();
+        if (fclose(f) != 0 || !ok) return io_fail(IS3D_EIO, "cannot write %s", p.c_str());
+    }
+    return IS3D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // PDG_Data::read_resonances_smash_box  (src/cpp/readindata.cpp:1571-1685; hrg_eos = 3, PDG/pdg_box.dat) with read_mcid (:1201-1418).
 //   Line oriented: "name mass width parity id [id [id [id]]]", '#' starts a comment line (and ends a data line: the extraction of the ids
 //   stops at the first token that is not a number), blank lines skipped.  Every non-zero id gives an entry, followed by its antiparticle when

@@ -21,6 +21,10 @@
 // results/spacetime_distribution/{dN_taudtaudy, dN_twopirdrdy, dN_twopitaurdtaudrdy}_<id>.dat and dN_dydeta_<id>_<n>pt.dat (the directory must
 // exist) and prints one "dN_dy = %lf" line per species; no momentum-spectra file (those are written for operation = 1 only, :1678).  df_mode 3 / 4
 // (calculate_dN_dX_feqmod) and mode 2 are refused before anything is written.
+// do_resonance_decays = 1 (optional key): with operation = 1 and hrg_eos = 1 or 2, the thermal files are written as without it, then the
+// feed-down (is3d_resonance_decays) runs on the spectrum on the first device of the run's list and results/dN_pTdpTdphidy_resonance_decays.dat
+// and dN_dpTdphidy_resonance_decays.dat are appended (emissionfunction.cpp:1689-1698); the embedding result keeps the thermal spectrum.
+// Operations 0 and 2 and hrg_eos = 3 (no decay data) refuse the key.
 // mode = 5: every run, whatever its operation, ends with the spin polarization from the surface's thermal vorticity (calculate_spin_polzn,
 // emissionfunction.cpp:1675) and appends results/St.dat, Sx.dat, Sy.dat, Sn.dat (write_polzn_vector_toFile, :1701), with T from the averages
 // file just written or T_switch when set_FO_temperature = 1; the embedding entry has no vorticity and says so.
@@ -174,10 +178,16 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         if (!mem && mode == 2) DIE("operation = 0 with mode = 2: the reference has no spacetime distribution for anisotropic hydro");
         if (mem && (!mem_x || !mem_y)) DIE("operation = 0 needs the cells' x and y positions (NULL given)");
     }
+    bool do_decays = false;
     {
         double decays = 0.0;   // optional key here; the reference runs do_resonance_decays() after the spectra (emissionfunction.cpp:1689-1698)
-        if (get_param("do_resonance_decays", &decays, false) == IS3D_OK && (int)decays)
-            DIE("do_resonance_decays = 1: resonance decays are not on this path; set do_resonance_decays = 0");
+        if (get_param("do_resonance_decays", &decays, false) == IS3D_OK && (int)decays) {
+            if (operation != 1)
+                DIE("do_resonance_decays = 1 with operation = %d: the feed-down follows the momentum spectra (operation = 1) only; set do_resonance_decays = 0", operation);
+            if (hrg_eos == 3)
+                DIE("do_resonance_decays = 1 with hrg_eos = 3: PDG/pdg_box.dat carries no decay data (smash box: no decay info, iS3D_parameters.dat); use hrg_eos = 1 or 2");
+            do_decays = true;
+        }
     }
     const bool vah = !mem && mode == 2;
     if (vah) {
@@ -625,6 +635,32 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         memcpy(res->spectrum, dN.data(), sizeof(double) * dN.size());
         memcpy(res->mc_id, mcid.data(), sizeof(int64_t) * (size_t)sp.n);
         memcpy(res->mass, mass.data(), sizeof(double) * (size_t)sp.n);
+    }
+    if (do_decays) {
+        // emissionfunction.cpp:1689-1698: the feed-down of the thermal spectrum, then its two files; on the first device of the run's list
+        printf("Starting resonance decays...\n");
+        int32_t nd = 0, nc = 0;
+        if (is3d_pdg_read_decays(pdg_path, &nd, &nc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0)) DIE("%s", is3d_last_error());
+        std::vector<int64_t> did((size_t)nd), dau((size_t)nc * 5);
+        std::vector<double> dm((size_t)nd), dw((size_t)nd), dbr((size_t)nc);
+        std::vector<int32_t> dst((size_t)nd), dnc((size_t)nd), dnp((size_t)nc);
+        if (is3d_pdg_read_decays(pdg_path, &nd, &nc, did.data(), dm.data(), dw.data(), dst.data(), dnc.data(), dnp.data(), dbr.data(), dau.data(), nd, nc))
+            DIE("%s", is3d_last_error());
+        const is3d_decay_table tab{nd, did.data(), dm.data(), dw.data(), dst.data(), dnc.data(), dnp.data(), dbr.data(), dau.data()};
+        std::vector<double> fed(dN);
+        is3d_decay_stats dst_{};
+        const double t4 = now_s();
+        const int rcd = is3d_resonance_decays(&tab, sp.n, mcid.data(), &grid, dimension, rd.list.empty() ? -1 : rd.list[0], fed.data(), &dst_);
+        if (rcd) {
+            const std::string msg = is3d_last_error();
+            DIE("is3d_resonance_decays failed (%d): %s", rcd, msg.c_str());
+        }
+        printf("Writing thermal + resonance decays spectra to file...\n");
+        if (is3d_write_results_decays("results", dimension, sp.n, grid.n_pT, pT.data(), grid.n_phi, phi.data(), grid.n_y, y.data(), fed.data()))
+            DIE("%s", is3d_last_error());
+        printf("resonance decays: %d parents, %d channels integrated (%d with adjusted masses), %lld acos clamps; device time: tables %.3f ms, "
+               "feed-down %.3f ms; wall %.3f s\n", dst_.n_parents, dst_.n_channels, dst_.n_adjusted, (long long)dst_.n_clamps, dst_.ms_tables,
+               dst_.ms_feed, now_s() - t4);
     }
     if (int rcp = polarization()) return rcp;
     printf("Done calculating particle spectra. Output stored in results folder. Goodbye!\n");
