@@ -499,6 +499,8 @@ typedef struct {
     double ms_h2d, ms_prep, ms_count, ms_fill;   /* device time: upload, densities + cell records, count pass + scan, fill pass */
     double ms_density;                  /* part of ms_prep: cf_sampler_density (the Gauss-Laguerre density integrals per (cell, class)) */
     double ms_poisson;                  /* part of ms_count: cf_sampler_poisson + the compaction of the emitting (event, cell) pairs */
+    double ms_bin;                      /* is3d_sampler_plan_execute_binned: cf_sampler_bins over all batches (0 for the list entries) */
+    int64_t particle_workspace_bytes;   /* is3d_sampler_plan_execute_binned: the plan-owned particle workspace (one batch); 0 otherwise */
 } is3d_sampler_stats;
 
 /* All pointers HOST memory; opts: dimension, df_mode (1-4), include_bulk_deltaf, include_shear_deltaf, device.  Particles
@@ -556,10 +558,56 @@ int is3d_write_particle_list_osc(const char *path, int32_t n_events, int64_t n_p
  * pT_lower_cut, pT_upper_cut, pT_bins, tau_min, tau_max, tau_bins, r_min, r_max, r_bins (emissionfunction.cpp:205-222). */
 typedef struct {
     double y_cut, eta_cut, pT_lower_cut, pT_upper_cut, tau_min, tau_max, r_min, r_max;
-    int32_t y_bins, eta_bins, pT_bins, tau_bins, r_bins, reserved;
+    int32_t y_bins, eta_bins, pT_bins, tau_bins, r_bins;
+    int32_t kernel_form;                /* tuning, device binning only: 0 = the measured choice (workgroup-private histograms where they
+                                           fit the LDS, global atomics otherwise), 1 = global atomics, 2 = workgroup-private (IS3D_EINVAL
+                                           if they do not fit).  The histograms do not depend on it. */
 } is3d_sampler_test_bins;
 int is3d_write_sampler_tests(const char *results_dir, const is3d_sampler_test_bins *bins, int32_t n_events, int32_t n_species,
                              const int64_t *mc_id, int64_t n_particles, const is3d_particle *particles, double mean_yield);
+
+/* The same distributions as raw integer histograms, so that the sampler can bin on the device and never hold the list (S = number of
+ * species; every array caller-owned):
+ *   dN_dy [S * y_bins], dN_deta [S * eta_bins], dN_pT [S * pT_bins], dN_tau [S * tau_bins], dN_r [S * r_bins]   counts, [species][bin]
+ *   vn_re, vn_im [7 * S * pT_bins]     [k][species][bin]: the sums of cos((k+1) phi), sin((k+1) phi) over the hadrons of dN_pT's bin
+ *   yield [n_events]                   hadrons per event
+ * dN_pT is the one count that both sample_dN_2pipTdpTdy and sample_vn keep.  The harmonic sums are FIXED POINT: every term is added as
+ * llrint(term * 2^32) (IS3D_SAMPLER_VN_SCALE), so that all sums are integer sums -- independent of the order of arrival, and with it of
+ * launch geometry, event batching and cell sharding, bit for bit.  One term is off by at most 2^-33; a sum of N terms is below N 2^32 in
+ * magnitude, so no bin overflows up to IS3D_SAMPLER_VN_MAX_COUNT = 2^31 - 1 entries: the device entries check dN_pT afterwards and
+ * return IS3D_EDOMAIN beyond that.  The per-particle rule is csrc/cf_sampler_bins.h, shared by host and device. */
+#define IS3D_SAMPLER_VN_HARMONICS 7
+#define IS3D_SAMPLER_VN_SCALE 4294967296.0
+#define IS3D_SAMPLER_VN_MAX_COUNT 2147483647LL
+typedef struct {
+    int64_t *dN_dy, *dN_deta, *dN_pT, *dN_tau, *dN_r, *vn_re, *vn_im, *yield;
+} is3d_sampler_hist;
+/* list -> histograms on the host (step 1 of is3d_write_sampler_tests; the CPU yardstick of the device kernel).  hist is overwritten. */
+int is3d_sampler_bin_list(const is3d_sampler_test_bins *bins, int32_t n_events, int32_t n_species, int64_t n_particles,
+                          const is3d_particle *particles, const is3d_sampler_hist *hist);
+/* histograms -> the files of is3d_write_sampler_tests (step 2); every file but vn/ is byte for byte the list writer's, vn/ agrees to
+ * the fixed point (2^-32 absolute in v_n before the 7 printed digits). */
+int is3d_write_sampler_tests_binned(const char *results_dir, const is3d_sampler_test_bins *bins, int32_t n_events, int32_t n_species,
+                                    const int64_t *mc_id, const is3d_sampler_hist *hist, double mean_yield);
+/* is3d_sampler_plan_execute with the list binned per event batch on the device and discarded: fill into a plan-owned particle workspace
+ * (grown to the largest batch seen: stats->particle_workspace_bytes), cf_sampler_bins into device-resident histograms, and after the last
+ * batch one copy to hist_host (HOST arrays, overwritten).  No buffer is sized by the total number of hadrons, and the sampler runs once.
+ * The histograms are those of is3d_sampler_bin_list on the list of is3d_sampler_plan_execute: counts and yields exactly; vn_re, vn_im
+ * within one unit per entry of the bin (device and host libm).  Bad bins (a count < 1, pT_upper_cut <= pT_lower_cut, an empty y, eta,
+ * tau or r range): IS3D_EINVAL before any launch; a dN_pT bin above IS3D_SAMPLER_VN_MAX_COUNT: IS3D_EDOMAIN. */
+int is3d_sampler_plan_execute_binned(is3d_sampler_plan *plan, const is3d_cells *cells_dev, const double *x_dev, const double *y_dev,
+                                     int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
+                                     const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist_host, int64_t *n_particles,
+                                     is3d_sampler_stats *stats);
+/* host-pointer one-shot (create + upload + execute_binned + destroy; in->first_cell is honoured), and the same over the cell shards of
+ * is3d_sample_particles_multi, one per entry of devices, the integer histograms added on the host: equal to the single-device result
+ * bit for bit. */
+int is3d_sample_binned(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                       const is3d_options *opts, const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
+                       is3d_sampler_stats *stats);
+int is3d_sample_binned_multi(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                             const is3d_options *opts, const int32_t *devices, int32_t n_devices, const is3d_sampler_test_bins *bins,
+                             const is3d_sampler_hist *hist, int64_t *n_particles, is3d_sampler_stats *stats);
 
 /* ---------------------------------------------------------------------------------------------
  * Operation 0: smooth Cooper-Frye spacetime distributions, df_mode 1 / 2 -- the drop-in for calculate_dN_dX

@@ -70,7 +70,8 @@ class SamplerStats(C.Structure):
     _fields_ = [("n_cells_skipped", C.c_int64), ("n_hadrons_drawn", C.c_int64), ("n_momentum_samples", C.c_int64),
                 ("n_acceptances", C.c_int64), ("n_classes", C.c_int32), ("reserved", C.c_int32), ("n_cells_breakdown", C.c_int64),
                 ("ms_h2d", C.c_double),
-                ("ms_prep", C.c_double), ("ms_count", C.c_double), ("ms_fill", C.c_double), ("ms_density", C.c_double), ("ms_poisson", C.c_double)]
+                ("ms_prep", C.c_double), ("ms_count", C.c_double), ("ms_fill", C.c_double), ("ms_density", C.c_double), ("ms_poisson", C.c_double),
+                ("ms_bin", C.c_double), ("particle_workspace_bytes", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -114,7 +115,8 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_spin_polarization", "is3d_polarization_plan_create", "is3d_polarization_plan_execute", "is3d_polarization_plan_destroy",
            "is3d_write_polarization", "is3d_surface_vorticity",
            "is3d_pdg_read_decays", "is3d_decay_q_factor", "is3d_resonance_decays", "is3d_decay_plan_create", "is3d_decay_plan_output_size",
-           "is3d_decay_plan_execute", "is3d_decay_plan_destroy", "is3d_write_results_decays"]
+           "is3d_decay_plan_execute", "is3d_decay_plan_destroy", "is3d_write_results_decays",
+           "is3d_sampler_bin_list", "is3d_write_sampler_tests_binned", "is3d_sampler_plan_execute_binned", "is3d_sample_binned", "is3d_sample_binned_multi"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 POLARIZATION_OUTPUTS = ["St", "Sx", "Sy", "Sn", "Snorm"]
@@ -1282,18 +1284,14 @@ def df_table_read_full(path):
     return T, B, v
 
 
-def sample_particles(cells, species, df, gla, opts=None, n_events=1, seed=1, y_cut=0.5, first_cell=0, capacity=None, fq=None, fast=0,
-                     T_avg=0.0, T_avg_switch=0.0, batch_events=0, muB_avg=0.0, devices=None):
-    """is3d_sample_particles (the drop-in for sample_dN_pTdpTdphidy, df_mode 1-4).  cells: dict of host arrays (x, y optional);
-    gla: dict with root1, weight1; fq: the feqmod tables (df_mode 3, 4; fast mode with df_mode 2).  Returns (numpy structured array of PARTICLE_DTYPE, stats dict); capacity = None sizes the
-    buffer from a count-only first call."""
-    L = load()
+def _pack_sampler(cells, species, df, gla, opts, n_events, seed, y_cut, first_cell, fq, fast, T_avg, T_avg_switch, batch_events, muB_avg):
+    """The C structs of the host-pointer sampler entries: (Cells, Species, DfTables, SamplerInputs, Options, what must stay alive)."""
     grid_dummy = dict(pT=[1.0], phi=[0.0], y=[0.0], eta=[0.0], eta_w=[1.0])
     sps, _, ds, os_, _, keep = _pack_common(species, grid_dummy, df, opts)
     n = len(cells["tau"])
     cs = Cells()
     cs.n_cells = n
-    held = []
+    held = [keep]
     for f in CELL_FIELDS:
         a = cells.get(f)
         if a is not None:
@@ -1308,6 +1306,18 @@ def sample_particles(cells, species, df, gla, opts=None, n_events=1, seed=1, y_c
     si = SamplerInputs(int(n_events), len(r1), int(seed), float(y_cut), int(first_cell), _p(xs) if xs is not None else None,
                        _p(ys) if ys is not None else None, _p(r1), _p(w1), C.pointer(fqs) if fqs is not None else None, int(fast), int(batch_events),
                        float(T_avg), float(T_avg_switch), float(muB_avg))
+    held += [r1, w1, xs, ys, fqs]
+    return cs, sps, ds, si, os_, held
+
+
+def sample_particles(cells, species, df, gla, opts=None, n_events=1, seed=1, y_cut=0.5, first_cell=0, capacity=None, fq=None, fast=0,
+                     T_avg=0.0, T_avg_switch=0.0, batch_events=0, muB_avg=0.0, devices=None):
+    """is3d_sample_particles (the drop-in for sample_dN_pTdpTdphidy, df_mode 1-4).  cells: dict of host arrays (x, y optional);
+    gla: dict with root1, weight1; fq: the feqmod tables (df_mode 3, 4; fast mode with df_mode 2).  Returns (numpy structured array of PARTICLE_DTYPE, stats dict); capacity = None sizes the
+    buffer from a count-only first call."""
+    L = load()
+    cs, sps, ds, si, os_, _held = _pack_sampler(cells, species, df, gla, opts, n_events, seed, y_cut, first_cell, fq, fast, T_avg, T_avg_switch,
+                                                batch_events, muB_avg)
     st = SamplerStats()
     cnt = C.c_int64(0)
     if devices is not None:   # is3d_sample_particles_multi: one cell shard per listed device (an ordinal may repeat)
@@ -1369,6 +1379,25 @@ class SamplerPlan:
         d["n_particles"] = int(cnt.value)
         return int(cnt.value), d
 
+    def execute_binned(self, n_cells, dev_ptrs, n_events, seed, bins, n_species, x_ptr=0, y_ptr=0, first_cell=0, batch_events=0):
+        """is3d_sampler_plan_execute_binned: -> (dict of int64 histograms, stats); n_species: the length of the plan's species list."""
+        cs = Cells()
+        cs.n_cells = int(n_cells)
+        for f in CELL_FIELDS:
+            if dev_ptrs.get(f):
+                setattr(cs, f, int(dev_ptrs[f]))
+        b = _pack_bins(bins)
+        h, out = _hist_arrays(bins, n_events, n_species)
+        cnt, st = C.c_int64(0), SamplerStats()
+        L = load()
+        L.is3d_sampler_plan_execute_binned.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32,
+                                                       C.POINTER(SamplerTestBins), C.POINTER(SamplerHist), C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
+        _check(L.is3d_sampler_plan_execute_binned(self._h, C.byref(cs), C.c_void_p(int(x_ptr) or None), C.c_void_p(int(y_ptr) or None), int(n_events),
+                                                  int(seed), int(first_cell), int(batch_events), C.byref(b), C.byref(h), C.byref(cnt), C.byref(st)))
+        d = st.as_dict()
+        d["n_particles"] = int(cnt.value)
+        return out, d
+
     def close(self):
         if self._h:
             load().is3d_sampler_plan_destroy(self._h)
@@ -1428,7 +1457,7 @@ def write_particle_list_osc(path, n_events, particles, mc_id):
 
 class SamplerTestBins(C.Structure):
     _fields_ = [(n, C.c_double) for n in ["y_cut", "eta_cut", "pT_lower_cut", "pT_upper_cut", "tau_min", "tau_max", "r_min", "r_max"]] + \
-               [(n, C.c_int32) for n in ["y_bins", "eta_bins", "pT_bins", "tau_bins", "r_bins", "reserved"]]
+               [(n, C.c_int32) for n in ["y_bins", "eta_bins", "pT_bins", "tau_bins", "r_bins", "kernel_form"]]
 
 
 def write_sampler_tests(results_dir, bins, n_events, mc_id, particles, mean_yield=0.0):
@@ -1443,6 +1472,95 @@ def write_sampler_tests(results_dir, bins, n_events, mc_id, particles, mean_yiel
                                            C.c_void_p, C.c_double]
     _check(L.is3d_write_sampler_tests(results_dir.encode(), C.byref(b), int(n_events), len(ids), ids.ctypes.data_as(C.POINTER(C.c_int64)),
                                       len(particles), particles.ctypes.data, float(mean_yield)))
+
+
+class SamplerHist(C.Structure):
+    _fields_ = [(n, C.POINTER(C.c_int64)) for n in ["dN_dy", "dN_deta", "dN_pT", "dN_tau", "dN_r", "vn_re", "vn_im", "yield"]]
+
+
+VN_HARMONICS = 7          # IS3D_SAMPLER_VN_HARMONICS
+VN_SCALE = 2.0 ** 32      # IS3D_SAMPLER_VN_SCALE: vn_re, vn_im hold the sums of llrint(term * 2^32)
+
+
+def _pack_bins(bins):
+    b = SamplerTestBins()
+    for k, v in bins.items():
+        setattr(b, k, v)
+    return b
+
+
+def _hist_arrays(bins, n_events, n_species, hist=None):
+    """is3d_sampler_hist over numpy int64 arrays: (struct, dict).  hist = None: fresh zero arrays of the shapes [species][bin],
+    vn_re / vn_im [7][species][pT bin], yield [event]; otherwise the caller's arrays are checked and used."""
+    S, E, nb = int(n_species), int(n_events), {k: max(int(bins[k]), 0) for k in ("y_bins", "eta_bins", "pT_bins", "tau_bins", "r_bins")}
+    shapes = dict(dN_dy=(S, nb["y_bins"]), dN_deta=(S, nb["eta_bins"]), dN_pT=(S, nb["pT_bins"]), dN_tau=(S, nb["tau_bins"]), dN_r=(S, nb["r_bins"]),
+                  vn_re=(VN_HARMONICS, S, nb["pT_bins"]), vn_im=(VN_HARMONICS, S, nb["pT_bins"]))
+    shapes["yield"] = (max(E, 0),)
+    out = {}
+    for k, shp in shapes.items():
+        if hist is None:
+            out[k] = np.zeros(shp, dtype=np.int64)
+        else:
+            out[k] = np.ascontiguousarray(hist[k], dtype=np.int64)
+            assert out[k].shape == shp, (k, out[k].shape, shp)
+    h = SamplerHist(*[out[k].ctypes.data_as(C.POINTER(C.c_int64)) for k, _ in SamplerHist._fields_])
+    return h, out
+
+
+def sampler_bin_list(bins, n_events, n_species, particles):
+    """is3d_sampler_bin_list: a particle list -> dict of int64 histograms (the CPU yardstick of the device binning)."""
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    b = _pack_bins(bins)
+    h, out = _hist_arrays(bins, n_events, n_species)
+    L = load()
+    L.is3d_sampler_bin_list.argtypes = [C.POINTER(SamplerTestBins), C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(SamplerHist)]
+    _check(L.is3d_sampler_bin_list(C.byref(b), int(n_events), int(n_species), len(particles), particles.ctypes.data, C.byref(h)))
+    return out
+
+
+def write_sampler_tests_binned(results_dir, bins, n_events, mc_id, hist, mean_yield=0.0):
+    """is3d_write_sampler_tests_binned: the test_sampler = 1 files from a dict of int64 histograms."""
+    ids = np.ascontiguousarray(mc_id, dtype=np.int64)
+    b = _pack_bins(bins)
+    h, _keep = _hist_arrays(bins, n_events, len(ids), hist)
+    L = load()
+    L.is3d_write_sampler_tests_binned.argtypes = [C.c_char_p, C.POINTER(SamplerTestBins), C.c_int32, C.c_int32, C.POINTER(C.c_int64),
+                                                  C.POINTER(SamplerHist), C.c_double]
+    _check(L.is3d_write_sampler_tests_binned(results_dir.encode(), C.byref(b), int(n_events), len(ids), ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             C.byref(h), float(mean_yield)))
+
+
+def sample_binned(cells, species, df, gla, bins, opts=None, n_events=1, seed=1, y_cut=0.5, first_cell=0, fq=None, fast=0, T_avg=0.0,
+                  T_avg_switch=0.0, batch_events=0, muB_avg=0.0, devices=None):
+    """is3d_sample_binned (devices = None) | is3d_sample_binned_multi: the sampler with every event batch binned on the device and dropped.
+    Arguments as sample_particles; bins: dict of is3d_sampler_test_bins fields.  Returns (dict of int64 histograms, stats dict)."""
+    L = load()
+    cs, sps, ds, si, os_, _held = _pack_sampler(cells, species, df, gla, opts, n_events, seed, y_cut, first_cell, fq, fast, T_avg, T_avg_switch,
+                                                batch_events, muB_avg)
+    b = _pack_bins(bins)
+    h, out = _hist_arrays(bins, n_events, sps.n)
+    st = SamplerStats()
+    cnt = C.c_int64(0)
+    if devices is not None:
+        dv = (C.c_int32 * len(devices))(*[int(d) for d in devices])
+        L.is3d_sample_binned_multi.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options),
+                                               C.POINTER(C.c_int32), C.c_int32, C.POINTER(SamplerTestBins), C.POINTER(SamplerHist),
+                                               C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
+        rc = L.is3d_sample_binned_multi(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), dv, len(devices), C.byref(b), C.byref(h),
+                                        C.byref(cnt), C.byref(st))
+    else:
+        L.is3d_sample_binned.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options),
+                                         C.POINTER(SamplerTestBins), C.POINTER(SamplerHist), C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
+        rc = L.is3d_sample_binned(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), C.byref(b), C.byref(h), C.byref(cnt), C.byref(st))
+    _check(rc)
+    d = st.as_dict()
+    d["n_particles"] = int(cnt.value)
+    return out, d
+
+
+def sample_binned_multi(cells, species, df, gla, bins, opts=None, devices=(0,), **kw):
+    """is3d_sample_binned_multi: one cell shard per entry of devices (an ordinal may repeat); the result equals sample_binned's bit for bit."""
+    return sample_binned(cells, species, df, gla, bins, opts, devices=list(devices), **kw)
 
 
 def gla_read(path):

@@ -833,6 +833,51 @@ extern "C" int is3d_smooth_spectra_multi(const is3d_cells *cells, const is3d_spe
 // ------------------------------------------------------------------------------------------------
 // particle sampler over several devices
 // ------------------------------------------------------------------------------------------------
+namespace {
+// the device list of the sampler's multi entries: n_devices <= 0 = every visible device; an ordinal may repeat
+int sampler_devices(const int32_t *devices, int32_t n_devices, std::vector<int> &dev)
+{
+    const int visible = is3d_device_count();
+    if (visible < 1) return fail(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
+    if (n_devices <= 0) { n_devices = visible; devices = nullptr; }
+    if (n_devices > 1024) return fail(IS3D_EINVAL, "n_devices = %d", n_devices);
+    dev.resize(n_devices);
+    for (int i = 0; i < n_devices; i++) {
+        dev[i] = devices ? devices[i] : i;
+        if (dev[i] < 0 || dev[i] >= visible) return fail(IS3D_EINVAL, "device %d is not one of the %d visible HIP devices", dev[i], visible);
+    }
+    return IS3D_OK;
+}
+// shard [lo, hi) of a host surface on `device`: the cell arrays and x, y advanced to lo, first_cell with them
+void sampler_shard(const is3d_cells *cells, const is3d_sampler_inputs *in, const is3d_options *opts, int64_t lo, int64_t hi, int device,
+                   is3d_cells *c, is3d_sampler_inputs *si, is3d_options *o)
+{
+    *c = *cells;
+    c->n_cells = hi - lo;
+    const double **fields[] = {&c->tau, &c->eta, &c->dat, &c->dax, &c->day, &c->dan, &c->ux, &c->uy, &c->un, &c->T, &c->P, &c->E, &c->pixx, &c->pixy,
+                               &c->pixn, &c->piyy, &c->piyn, &c->bulkPi, &c->muB, &c->nB, &c->Vx, &c->Vy, &c->Vn};
+    for (auto f : fields)
+        if (*f) *f += lo;
+    *si = *in;
+    si->first_cell = in->first_cell + lo;
+    if (si->x) si->x += lo;
+    if (si->y) si->y += lo;
+    *o = *opts;
+    o->device = device;
+}
+// counts summed, times the slowest shard's
+void sampler_stats_add(is3d_sampler_stats &agg, const is3d_sampler_stats &t)
+{
+    agg.n_cells_skipped += t.n_cells_skipped; agg.n_hadrons_drawn += t.n_hadrons_drawn;
+    agg.n_momentum_samples += t.n_momentum_samples; agg.n_acceptances += t.n_acceptances;
+    agg.n_classes = std::max(agg.n_classes, t.n_classes); agg.n_cells_breakdown += t.n_cells_breakdown;
+    agg.ms_h2d = std::max(agg.ms_h2d, t.ms_h2d); agg.ms_prep = std::max(agg.ms_prep, t.ms_prep);
+    agg.ms_count = std::max(agg.ms_count, t.ms_count); agg.ms_fill = std::max(agg.ms_fill, t.ms_fill);
+    agg.ms_bin = std::max(agg.ms_bin, t.ms_bin);
+    agg.particle_workspace_bytes = std::max(agg.particle_workspace_bytes, t.particle_workspace_bytes);
+}
+}  // namespace
+
 extern "C" int is3d_sample_particles_multi(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df,
                                            const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices,
                                            int32_t n_devices, is3d_particle *particles, int64_t capacity, int64_t *n_particles,
@@ -842,15 +887,9 @@ extern "C" int is3d_sample_particles_multi(const is3d_cells *cells, const is3d_s
     *n_particles = 0;
     if (stats) memset(stats, 0, sizeof *stats);
     if (cells->n_cells < 0) return fail(IS3D_EINVAL, "n_cells < 0");
-    const int visible = is3d_device_count();
-    if (visible < 1) return fail(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
-    if (n_devices <= 0) { n_devices = visible; devices = nullptr; }
-    if (n_devices > 1024) return fail(IS3D_EINVAL, "n_devices = %d", n_devices);
-    std::vector<int> dev(n_devices);
-    for (int i = 0; i < n_devices; i++) {
-        dev[i] = devices ? devices[i] : i;
-        if (dev[i] < 0 || dev[i] >= visible) return fail(IS3D_EINVAL, "device %d is not one of the %d visible HIP devices", dev[i], visible);
-    }
+    std::vector<int> dev;
+    if (int rc = sampler_devices(devices, n_devices, dev)) return rc;
+    n_devices = (int32_t)dev.size();
     if (particles == nullptr) capacity = 0;
     if (n_devices == 1) {
         is3d_options o = *opts;
@@ -874,18 +913,10 @@ extern "C" int is3d_sample_particles_multi(const is3d_cells *cells, const is3d_s
             (void)is3d_shard_bounds(cells->n_cells, i, n_devices, &sh[i].lo, &sh[i].hi);
             th.emplace_back([&, i] {
                 SShard &s = sh[i];
-                is3d_cells c = *cells;
-                c.n_cells = s.hi - s.lo;
-                const double **fields[] = {&c.tau, &c.eta, &c.dat, &c.dax, &c.day, &c.dan, &c.ux, &c.uy, &c.un, &c.T, &c.P, &c.E, &c.pixx, &c.pixy,
-                                           &c.pixn, &c.piyy, &c.piyn, &c.bulkPi, &c.muB, &c.nB, &c.Vx, &c.Vy, &c.Vn};
-                for (auto f : fields)
-                    if (*f) *f += s.lo;
-                is3d_sampler_inputs si = *in;
-                si.first_cell = in->first_cell + s.lo;
-                if (si.x) si.x += s.lo;
-                if (si.y) si.y += s.lo;
-                is3d_options o = *opts;
-                o.device = s.device;
+                is3d_cells c;
+                is3d_sampler_inputs si;
+                is3d_options o;
+                sampler_shard(cells, in, opts, s.lo, s.hi, s.device, &c, &si, &o);
                 s.rc = is3d_sample_particles(&c, species, df, &si, &o, nullptr, 0, &s.count, &s.st);
                 if (!s.rc && fill && s.count > 0) {
                     s.list.resize((size_t)s.count);
@@ -901,12 +932,7 @@ extern "C" int is3d_sample_particles_multi(const is3d_cells *cells, const is3d_s
     for (int i = 0; i < n_devices; i++) {
         if (sh[i].rc) return fail(sh[i].rc, "shard %d (device %d): %s", i, sh[i].device, sh[i].err.c_str());
         total += sh[i].count;
-        const is3d_sampler_stats &t = sh[i].st;
-        agg.n_cells_skipped += t.n_cells_skipped; agg.n_hadrons_drawn += t.n_hadrons_drawn;
-        agg.n_momentum_samples += t.n_momentum_samples; agg.n_acceptances += t.n_acceptances;
-        agg.n_classes = std::max(agg.n_classes, t.n_classes); agg.n_cells_breakdown += t.n_cells_breakdown;
-        agg.ms_h2d = std::max(agg.ms_h2d, t.ms_h2d); agg.ms_prep = std::max(agg.ms_prep, t.ms_prep);
-        agg.ms_count = std::max(agg.ms_count, t.ms_count); agg.ms_fill = std::max(agg.ms_fill, t.ms_fill);
+        sampler_stats_add(agg, sh[i].st);
     }
     *n_particles = total;
     if (stats) *stats = agg;
@@ -927,5 +953,87 @@ extern "C" int is3d_sample_particles_multi(const is3d_cells *cells, const is3d_s
             pos[i] = p;
         }
     if (total > capacity) return fail(IS3D_ENOMEM, "particle buffer too small: %lld particles, capacity %lld", (long long)total, (long long)capacity);
+    return IS3D_OK;
+}
+
+// is3d_sample_binned over the same shards: every shard bins its own hadrons on its device, the integer histograms are added here --
+// an exact sum, so the result is the single-device one bit for bit
+extern "C" int is3d_sample_binned_multi(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df,
+                                        const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices, int32_t n_devices,
+                                        const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
+                                        is3d_sampler_stats *stats)
+{
+    if (!cells || !species || !in || !opts || !bins || !hist || !n_particles) return fail(IS3D_EINVAL, "null argument");
+    *n_particles = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (cells->n_cells < 0) return fail(IS3D_EINVAL, "n_cells < 0");
+    std::vector<int> dev;
+    if (int rc = sampler_devices(devices, n_devices, dev)) return rc;
+    n_devices = (int32_t)dev.size();
+    if (n_devices == 1) {
+        is3d_options o = *opts;
+        o.device = dev[0];
+        return is3d_sample_binned(cells, species, df, in, &o, bins, hist, n_particles, stats);
+    }
+    if (in->n_events < 1 || species->n < 1 || bins->y_bins < 1 || bins->eta_bins < 1 || bins->pT_bins < 1 || bins->tau_bins < 1 || bins->r_bins < 1)
+        return fail(IS3D_EINVAL, "n_events, the species count and every bin count must be >= 1");
+    if (!hist->dN_dy || !hist->dN_deta || !hist->dN_pT || !hist->dN_tau || !hist->dN_r || !hist->vn_re || !hist->vn_im || !hist->yield)
+        return fail(IS3D_EINVAL, "null argument");
+    // the arrays of is3d_sampler_hist laid end to end, as one block per shard
+    const int64_t S = species->n, E = in->n_events, P = (int64_t)IS3D_SAMPLER_VN_HARMONICS * S * bins->pT_bins;
+    const int64_t len[8] = {S * bins->y_bins, S * bins->eta_bins, S * bins->pT_bins, S * bins->tau_bins, S * bins->r_bins, P, P, E};
+    int64_t *const out[8] = {hist->dN_dy, hist->dN_deta, hist->dN_pT, hist->dN_tau, hist->dN_r, hist->vn_re, hist->vn_im, hist->yield};
+    int64_t words = 0;
+    for (int a = 0; a < 8; a++) words += len[a];
+    struct BShard {
+        int device = 0;
+        int64_t lo = 0, hi = 0, count = 0;
+        std::vector<int64_t> h;
+        is3d_sampler_stats st{};
+        int rc = IS3D_OK;
+        std::string err;
+    };
+    std::vector<BShard> sh(n_devices);
+    {
+        std::vector<std::thread> th;
+        for (int i = 0; i < n_devices; i++) {
+            sh[i].device = dev[i];
+            (void)is3d_shard_bounds(cells->n_cells, i, n_devices, &sh[i].lo, &sh[i].hi);
+            sh[i].h.assign((size_t)words, 0);
+            th.emplace_back([&, i] {
+                BShard &s = sh[i];
+                is3d_cells c;
+                is3d_sampler_inputs si;
+                is3d_options o;
+                sampler_shard(cells, in, opts, s.lo, s.hi, s.device, &c, &si, &o);
+                int64_t *q = s.h.data();
+                int64_t *part[8];
+                for (int a = 0; a < 8; a++) { part[a] = q; q += len[a]; }
+                const is3d_sampler_hist hs{part[0], part[1], part[2], part[3], part[4], part[5], part[6], part[7]};
+                s.rc = is3d_sample_binned(&c, species, df, &si, &o, bins, &hs, &s.count, &s.st);
+                if (s.rc) s.err = is3d_last_error();
+            });
+        }
+        for (auto &t : th) t.join();
+    }
+    is3d_sampler_stats agg{};
+    int64_t total = 0;
+    for (int a = 0; a < 8; a++) memset(out[a], 0, (size_t)len[a] * sizeof(int64_t));
+    for (int i = 0; i < n_devices; i++) {
+        if (sh[i].rc) return fail(sh[i].rc, "shard %d (device %d): %s", i, sh[i].device, sh[i].err.c_str());
+        total += sh[i].count;
+        sampler_stats_add(agg, sh[i].st);
+        const int64_t *q = sh[i].h.data();
+        for (int a = 0; a < 8; a++) {
+            for (int64_t j = 0; j < len[a]; j++) out[a][j] += q[j];
+            q += len[a];
+        }
+    }
+    *n_particles = total;
+    if (stats) *stats = agg;
+    for (int64_t j = 0; j < len[2]; j++)
+        if (hist->dN_pT[j] > IS3D_SAMPLER_VN_MAX_COUNT)
+            return fail(IS3D_EDOMAIN, "dN_pT bin %lld holds %lld hadrons: the fixed-point harmonic sums are exact up to %lld per bin", (long long)j,
+                        (long long)hist->dN_pT[j], (long long)IS3D_SAMPLER_VN_MAX_COUNT);
     return IS3D_OK;
 }

@@ -40,6 +40,7 @@
 #include "cf_device.h"
 #include "cf_host.h"
 #include "cf_math.h"
+#include "cf_sampler_bins.h"
 #include "errors.h"
 #include "jonah.h"
 #include "spline.h"
@@ -654,9 +655,11 @@ struct is3d_sampler_plan {
     DevMem d_jonah, d_eqd, d_bkd;
     DevMem d_status, d_GT, d_GT2, d_GT3, d_rec, d_counts, d_offsets, d_scan_tmp;
     DevMem d_drawn, d_emits, d_active, d_nactive, d_cdf;
+    DevMem d_particles, d_hist;             // is3d_sampler_plan_execute_binned: one batch of particles; the histograms, then the yields
     int64_t cap_cells = 0, cap_bt = 0;      // what the workspaces above were sized for
+    int64_t cap_particles = 0, cap_hist = 0;
     size_t tmp_bytes = 0;
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
 extern "C" int is3d_sampler_plan_create(is3d_sampler_plan **out, const is3d_species *species, const is3d_df_tables *df,
@@ -890,6 +893,15 @@ bool cell_array_needed(int a, const is3d_options *o)
     const bool baryondiff = o->include_baryon != 0 && o->include_baryondiff_deltaf != 0;
     return a < 12 ? (a != 1 || three_d) : (a < 17 ? o->include_shear_deltaf != 0 : (a == 17 ? o->include_bulk_deltaf != 0 : baryondiff));
 }
+// what is3d_sampler_plan_execute_binned adds to the batch loop
+struct BinRun {
+    is3d_sampler_test_bins bins;
+    is3d::SamplerBinWidths widths;
+    is3d::SamplerHistLayout layout;
+};
+int sampler_execute(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev, int32_t n_events, uint64_t seed,
+                    int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
+                    int64_t *n_particles, is3d_sampler_stats *stats);
 }  // namespace
 
 extern "C" void is3d_sampler_plan_destroy(is3d_sampler_plan *P)
@@ -906,12 +918,22 @@ extern "C" int is3d_sampler_plan_execute(is3d_sampler_plan *P, const is3d_cells 
                                          uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity,
                                          int64_t *n_particles, is3d_sampler_stats *stats)
 {
+    return sampler_execute(P, cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, particles_dev, capacity, nullptr, n_particles, stats);
+}
+
+namespace {
+// the one batch loop: bin == NULL fills the caller's list (or only counts); bin != NULL fills each batch into the plan's particle workspace
+// at base 0, bins it into P->d_hist and drops it
+int sampler_execute(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev, int32_t n_events, uint64_t seed,
+                    int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
+                    int64_t *n_particles, is3d_sampler_stats *stats)
+{
     using is3d::set_error;
     if (!P || !cells || !n_particles) return set_error(IS3D_EINVAL, "null argument");
     *n_particles = 0;
     if (stats) memset(stats, 0, sizeof *stats);
     if (n_events < 1) return set_error(IS3D_EINVAL, "n_events must be >= 1");
-    if (particles_dev == nullptr) capacity = 0;
+    if (particles_dev == nullptr || bin) capacity = 0;
     if (int rc = check_cells(cells, &P->o, first_cell)) return rc;
     const int64_t n = cells->n_cells;
     if (n > P->max_cells) return set_error(IS3D_EINVAL, "%lld cells, the sampler plan was created for %lld", (long long)n, (long long)P->max_cells);
@@ -978,7 +1000,7 @@ extern "C" int is3d_sampler_plan_execute(is3d_sampler_plan *P, const is3d_cells 
     HIP_TRY(hipEventRecord(ev[2], nullptr));
     // ---- events in batches of <= 2^25 (event, cell) threads: count, scan, fill ----
     int64_t base = 0;
-    double ms_count = 0.0, ms_fill = 0.0, ms_poisson = 0.0;
+    double ms_count = 0.0, ms_fill = 0.0, ms_poisson = 0.0, ms_bin = 0.0;
     for (int e0 = 0; e0 < n_events; e0 += eb) {
         const int ne = std::min(eb, n_events - e0);
         const int64_t nt = (int64_t)ne * n;
@@ -1004,22 +1026,38 @@ extern "C" int is3d_sampler_plan_execute(is3d_sampler_plan *P, const is3d_cells 
             HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_scan_tmp.p, tmp_bytes, d_counts.as<int64_t>(), d_offsets.as<int64_t>(), n_active + 1, nullptr));
             HIP_TRY(hipEventRecord(ev[3], nullptr));
             HIP_TRY(hipMemcpy(&batch_total, d_offsets.as<int64_t>() + n_active, sizeof(int64_t), hipMemcpyDeviceToHost));
-            if (capacity > 0 && base < capacity && batch_total > 0) {
+            // the list: the caller's buffer at the running base; binned: the plan's workspace, grown to the largest batch seen, at base 0
+            is3d_particle *dst = particles_dev;
+            int64_t dst_base = base, dst_cap = capacity;
+            if (bin && batch_total > 0) {
+                if (batch_total > P->cap_particles) {
+                    HIP_TRY(P->d_particles.alloc((size_t)batch_total * sizeof(is3d_particle)));
+                    P->cap_particles = batch_total;
+                }
+                dst = P->d_particles.as<is3d_particle>(); dst_base = 0; dst_cap = batch_total;
+            }
+            if (dst_cap > 0 && dst_base < dst_cap && batch_total > 0) {
                 hipLaunchKernelGGL((is3d::cf_sampler_run<true>), dim3(grid), dim3(128), 0, nullptr, p, sp, d_rec.as<is3d::SamplerCell>(),
                                    d_GT.as<double>(), d_GT2.as<double>(), d_GT3.as<double>(), e0, d_active.as<int32_t>(), (int64_t)n_active,
-                                   d_drawn.as<int32_t>(), (int64_t *)nullptr, d_offsets.as<int64_t>(), base, particles_dev, capacity);
+                                   d_drawn.as<int32_t>(), (int64_t *)nullptr, d_offsets.as<int64_t>(), dst_base, dst, dst_cap);
                 HIP_TRY(hipGetLastError());
             }
         } else {
             HIP_TRY(hipEventRecord(ev[3], nullptr));
         }
+        HIP_TRY(hipEventRecord(ev[8], nullptr));
+        if (bin && batch_total > 0)
+            HIP_TRY(is3d::sampler_bins_launch(bin->bins, bin->widths, bin->layout, sp.npart, n_events, P->d_particles.as<is3d_particle>(), batch_total,
+                                              P->d_hist.as<unsigned long long>(), P->d_hist.as<unsigned long long>() + bin->layout.total,
+                                              bin->bins.kernel_form));
         HIP_TRY(hipEventRecord(ev[4], nullptr));
         HIP_TRY(hipEventSynchronize(ev[4]));
-        float a = 0, b = 0, c = 0;
+        float a = 0, b = 0, c = 0, d = 0;
         HIP_TRY(hipEventElapsedTime(&a, ev[5], ev[3]));
-        HIP_TRY(hipEventElapsedTime(&b, ev[3], ev[4]));
+        HIP_TRY(hipEventElapsedTime(&b, ev[3], ev[8]));
         HIP_TRY(hipEventElapsedTime(&c, ev[5], ev[7]));
-        ms_count += a; ms_fill += b; ms_poisson += c;
+        HIP_TRY(hipEventElapsedTime(&d, ev[8], ev[4]));
+        ms_count += a; ms_fill += b; ms_poisson += c; ms_bin += d;
         base += batch_total;
     }
     unsigned long long h[8];
@@ -1040,6 +1078,10 @@ extern "C" int is3d_sampler_plan_execute(is3d_sampler_plan *P, const is3d_cells 
         stats->n_cells_breakdown = (int64_t)h[5];
         stats->n_classes = ncls;
         stats->ms_count = ms_count; stats->ms_fill = ms_fill;
+        if (bin) {
+            stats->ms_bin = ms_bin;
+            stats->particle_workspace_bytes = P->cap_particles * (int64_t)sizeof(is3d_particle);
+        }
     }
     if (h[0] != ~0ULL)
         return set_error(IS3D_EDOMAIN, "cell %lld: T%s outside the coefficient table (the reference aborts in gsl_spline_eval here)", (long long)h[0],
@@ -1049,6 +1091,41 @@ extern "C" int is3d_sampler_plan_execute(is3d_sampler_plan *P, const is3d_cells 
                          (long long)base, (long long)capacity);
     return IS3D_OK;
 }
+}  // namespace
+
+namespace {
+// what the host-pointer entries share: a plan for this surface, and the needed cell arrays, x and y uploaded in one block
+struct StagedRun {
+    is3d_sampler_plan *P = nullptr;
+    is3d::DevBuf<double> d_cells;   // the needed cell arrays, then x and y
+    is3d_cells dc{};
+    std::array<const double *, 2> xy{};
+    float ms_h2d = 0;
+    ~StagedRun() { is3d_sampler_plan_destroy(P); }
+};
+// an empty surface stages nothing (r.dc.n_cells = 0)
+int stage_run(StagedRun &r, const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+              const is3d_options *opts)
+{
+    if (int rc = is3d_sampler_plan_create(&r.P, species, df, in, opts, std::max<int64_t>(cells->n_cells, 1))) return rc;
+    if (int rc = check_cells(cells, opts, in->first_cell)) return rc;
+    const int64_t n = cells->n_cells;
+    if (n == 0) return IS3D_OK;
+    HIP_TRY(r.d_cells.alloc((size_t)n * (is3d::kCellArrays + 2)));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{e0, e1};
+    HIP_TRY(hipEventRecord(e0, nullptr));
+    HIP_TRY(is3d::stage_cells(*cells, [opts](int a) { return cell_array_needed(a, opts); }, 0, n, r.d_cells.p, nullptr, &r.dc));
+    r.xy = {in->x, in->y};
+    HIP_TRY(is3d::stage_arrays(r.xy, 0, n, r.d_cells.p + (size_t)is3d::kCellArrays * n, nullptr));
+    HIP_TRY(hipEventRecord(e1, nullptr));
+    HIP_TRY(hipEventSynchronize(e1));
+    (void)hipEventElapsedTime(&r.ms_h2d, e0, e1);
+    return IS3D_OK;
+}
+}  // namespace
 
 // the host-pointer entry: plan + upload + execute + download (the particle list is the plan's, bit for bit)
 extern "C" int is3d_sample_particles(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df,
@@ -1068,39 +1145,109 @@ extern "C" int is3d_sample_particles(const is3d_cells *cells, const is3d_species
         return set_error(IS3D_EINVAL, "n_events must be >= 1");
     }
     if (particles == nullptr) capacity = 0;
-    is3d_sampler_plan *P = nullptr;
-    if (int rc = is3d_sampler_plan_create(&P, species, df, in, opts, std::max<int64_t>(cells->n_cells, 1))) return rc;
-    struct Guard { is3d_sampler_plan *p; ~Guard() { is3d_sampler_plan_destroy(p); } } guard{P};
-    if (int rc = check_cells(cells, opts, in->first_cell)) return rc;
-    const int64_t n = cells->n_cells;
-    if (n == 0) return IS3D_OK;
-    is3d::DevBuf<double> d_cells;   // the needed cell arrays, then x and y
+    StagedRun r;
+    if (int rc = stage_run(r, cells, species, df, in, opts)) return rc;
+    if (cells->n_cells == 0) return IS3D_OK;
+    is3d_sampler_plan *P = r.P;
     DevMem d_particles;
-    HIP_TRY(d_cells.alloc((size_t)n * (is3d::kCellArrays + 2)));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{e0, e1};
-    HIP_TRY(hipEventRecord(e0, nullptr));
-    is3d_cells dc;
-    HIP_TRY(is3d::stage_cells(*cells, [opts](int a) { return cell_array_needed(a, opts); }, 0, n, d_cells.p, nullptr, &dc));
-    std::array<const double *, 2> xy = {in->x, in->y};
-    HIP_TRY(is3d::stage_arrays(xy, 0, n, d_cells.p + (size_t)is3d::kCellArrays * n, nullptr));
-    HIP_TRY(hipEventRecord(e1, nullptr));
     if (capacity > 0) HIP_TRY(d_particles.alloc((size_t)capacity * sizeof(is3d_particle)));
     int64_t total = 0;
-    const int rc = is3d_sampler_plan_execute(P, &dc, xy[0], xy[1], in->n_events, in->seed, in->first_cell, in->batch_events,
+    const int rc = is3d_sampler_plan_execute(P, &r.dc, r.xy[0], r.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events,
                                              d_particles.as<is3d_particle>(), capacity, &total, stats);
     *n_particles = total;
-    if (stats) {
-        float a = 0;
-        (void)hipEventElapsedTime(&a, e0, e1);
-        stats->ms_h2d = a;
-    }
+    if (stats) stats->ms_h2d = r.ms_h2d;
     if (rc && rc != IS3D_ENOMEM) return rc;
     const std::string kept = rc ? is3d_last_error() : "";
     const int64_t ncopy = std::min<int64_t>(total, capacity);
     if (ncopy > 0) HIP_TRY(hipMemcpy(particles, d_particles.p, (size_t)ncopy * sizeof(is3d_particle), hipMemcpyDeviceToHost));
     if (rc) return set_error(rc, "%s", kept.c_str());
     return IS3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// binned on the device: the list of each event batch goes through cf_sampler_bins (cf_sampler_bins.hip) and is dropped
+// ------------------------------------------------------------------------------------------------
+namespace {
+int check_bin_args(const is3d_sampler_test_bins *bins, const is3d_sampler_hist *h, int32_t n_events)
+{
+    using is3d::set_error;
+    if (!bins || !h) return set_error(IS3D_EINVAL, "null argument");
+    if (n_events < 1) return set_error(IS3D_EINVAL, "n_events must be >= 1");
+    if (!is3d::sampler_bins_valid(*bins))
+        return set_error(IS3D_EINVAL, "sampler test bins: every bin count must be >= 1, y_cut and eta_cut > 0, pT_upper_cut > pT_lower_cut, tau_max > tau_min, r_max > r_min");
+    if (!h->dN_dy || !h->dN_deta || !h->dN_pT || !h->dN_tau || !h->dN_r || !h->vn_re || !h->vn_im || !h->yield) return set_error(IS3D_EINVAL, "null argument");
+    if (bins->kernel_form < 0 || bins->kernel_form > 2) return set_error(IS3D_EINVAL, "kernel_form = %d: 0, 1 or 2", bins->kernel_form);
+    return IS3D_OK;
+}
+// the arrays of a histogram set in the order of SamplerHistLayout, with their lengths
+struct HistParts {
+    int64_t *p[7];
+    int64_t n[7];
+};
+HistParts hist_parts(const is3d_sampler_hist &h, const is3d::SamplerHistLayout &l)
+{
+    return {{h.dN_dy, h.dN_deta, h.dN_pT, h.dN_tau, h.dN_r, h.vn_re, h.vn_im},
+            {l.de - l.dy, l.dp - l.de, l.dt - l.dp, l.dr - l.dt, l.vr - l.dr, l.vi - l.vr, l.total - l.vi}};
+}
+}  // namespace
+
+extern "C" int is3d_sampler_plan_execute_binned(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev,
+                                                int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
+                                                const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
+                                                is3d_sampler_stats *stats)
+{
+    using is3d::set_error;
+    if (!P || !cells || !n_particles) return set_error(IS3D_EINVAL, "null argument");
+    *n_particles = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (int rc = check_bin_args(bins, hist, n_events)) return rc;
+    const int S = P->sp.npart;
+    BinRun br{*bins, is3d::sampler_bin_widths(*bins), is3d::sampler_hist_layout(*bins, S)};
+    if (bins->kernel_form == 2 && !is3d::sampler_bins_lds_fits(br.layout))
+        return set_error(IS3D_EINVAL, "kernel_form = 2: %lld histogram words do not fit the LDS", (long long)br.layout.total);
+    const HistParts parts = hist_parts(*hist, br.layout);
+    for (int a = 0; a < 7; a++) memset(parts.p[a], 0, (size_t)parts.n[a] * sizeof(int64_t));
+    memset(hist->yield, 0, (size_t)n_events * sizeof(int64_t));
+    const int64_t words = br.layout.total + n_events;
+    if (cells->n_cells > 0) {
+        HIP_TRY(hipSetDevice(P->device));
+        if (words > P->cap_hist) {
+            HIP_TRY(P->d_hist.alloc((size_t)words * sizeof(int64_t)));
+            P->cap_hist = words;
+        }
+        HIP_TRY(hipMemsetAsync(P->d_hist.p, 0, (size_t)words * sizeof(int64_t), nullptr));
+    }
+    if (int rc = sampler_execute(P, cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, nullptr, 0, &br, n_particles, stats)) return rc;
+    if (cells->n_cells == 0) return IS3D_OK;
+    std::vector<int64_t> h((size_t)words);
+    HIP_TRY(hipMemcpy(h.data(), P->d_hist.p, (size_t)words * sizeof(int64_t), hipMemcpyDeviceToHost));
+    const int64_t *src = h.data();
+    for (int a = 0; a < 7; a++) {
+        memcpy(parts.p[a], src, (size_t)parts.n[a] * sizeof(int64_t));
+        src += parts.n[a];
+    }
+    memcpy(hist->yield, src, (size_t)n_events * sizeof(int64_t));
+    for (int64_t j = 0; j < parts.n[2]; j++)
+        if (hist->dN_pT[j] > IS3D_SAMPLER_VN_MAX_COUNT)
+            return set_error(IS3D_EDOMAIN, "dN_pT bin %lld holds %lld hadrons: the fixed-point harmonic sums are exact up to %lld per bin", (long long)j,
+                             (long long)hist->dN_pT[j], (long long)IS3D_SAMPLER_VN_MAX_COUNT);
+    return IS3D_OK;
+}
+
+// the host-pointer entry: plan + upload + execute_binned
+extern "C" int is3d_sample_binned(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                                  const is3d_options *opts, const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist,
+                                  int64_t *n_particles, is3d_sampler_stats *stats)
+{
+    using is3d::set_error;
+    if (!cells || !species || !df || !in || !opts || !n_particles) return set_error(IS3D_EINVAL, "null argument");
+    *n_particles = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (int rc = check_bin_args(bins, hist, in->n_events)) return rc;
+    StagedRun r;
+    if (int rc = stage_run(r, cells, species, df, in, opts)) return rc;
+    const int rc = is3d_sampler_plan_execute_binned(r.P, &r.dc, r.xy[0], r.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events, bins,
+                                                    hist, n_particles, stats);
+    if (stats) stats->ms_h2d = r.ms_h2d;
+    return rc;
 }

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/is3d_amd.h"
+#include "cf_sampler_bins.h"
 #include "errors.h"
 
 namespace {
@@ -1509,50 +1510,55 @@ extern "C" int is3d_write_particle_list_osc(const char *path, int32_t n_events, 
 // list on the host: results/dN_dy/dN_dy_<id>_test.dat (+ _average_test), dN_deta/dN_deta_<id>_test.dat,
 // momentum_distribution/dN_2pipTdpTdy_<id>_test.dat, vn/vn_<id>_test.dat, spacetime_distribution/dN_taudtaudy_sampled_<id>_test.dat
 // and dN_twopirdrdy_sampled_<id>_test.dat, mean_yield.dat, yield_list.dat.  The directories must exist, as for the reference.
-extern "C" int is3d_write_sampler_tests(const char *results_dir, const is3d_sampler_test_bins *b, int32_t n_events, int32_t n_species,
-                                        const int64_t *mc_id, int64_t n_particles, const is3d_particle *particles, double mean_yield)
+// Two steps: the list goes into the integer histograms of is3d_sampler_hist through the one bin rule of cf_sampler_bins.h (sampler_bin_list),
+// the histograms go into the files (sampler_write_hist).  The list writer also keeps the harmonic sums in double, as the reference does, and
+// prints those: its files are what they always were; the histogram writer has only the fixed-point sums (2^-32 absolute in v_n).
+namespace {
+constexpr int K_MAX = IS3D_SAMPLER_VN_HARMONICS;                             // emissionfunction.h:132
+
+// vr, vi (may be NULL): the double sums of cos((k+1) phi), sin((k+1) phi), [k][species][bin], added to in list order
+int sampler_bin_list(const is3d_sampler_test_bins *b, int32_t n_events, int32_t n_species, int64_t n_particles, const is3d_particle *particles,
+                     const is3d_sampler_hist *h, double *vr, double *vi)
 {
-    if (!results_dir || !b || !mc_id || (n_particles > 0 && !particles)) return io_fail(IS3D_EINVAL, "null argument");
-    if (b->y_bins < 1 || b->eta_bins < 1 || b->pT_bins < 1 || b->tau_bins < 1 || b->r_bins < 1 || n_events < 1 || n_species < 1)
-        return io_fail(IS3D_EINVAL, "sampler test bins must be positive");
-    const int K_MAX = 7;                                                     // emissionfunction.h:132
-    const double two_pi = 2.0 * M_PI;
-    const double yw = 2.0 * b->y_cut / (double)b->y_bins, ew = 2.0 * b->eta_cut / (double)b->eta_bins;
-    const double pw = (b->pT_upper_cut - b->pT_lower_cut) / (double)b->pT_bins;
-    const double tw = (b->tau_max - b->tau_min) / (double)b->tau_bins, rw = (b->r_max - b->r_min) / (double)b->r_bins;
-    std::vector<double> dy((size_t)n_species * b->y_bins, 0.0), de((size_t)n_species * b->eta_bins, 0.0), dp((size_t)n_species * b->pT_bins, 0.0);
-    std::vector<double> vc((size_t)n_species * b->pT_bins, 0.0), vr((size_t)K_MAX * n_species * b->pT_bins, 0.0), vi(vr.size(), 0.0);
-    std::vector<double> dt((size_t)n_species * b->tau_bins, 0.0), dr((size_t)n_species * b->r_bins, 0.0);
-    std::vector<int64_t> yield((size_t)n_events, 0);
+    const is3d::SamplerBinWidths w = is3d::sampler_bin_widths(*b);
+    const is3d::SamplerHistLayout l = is3d::sampler_hist_layout(*b, n_species);
+    int64_t *const arr[7] = {h->dN_dy, h->dN_deta, h->dN_pT, h->dN_tau, h->dN_r, h->vn_re, h->vn_im};
+    const int64_t len[7] = {l.de - l.dy, l.dp - l.de, l.dt - l.dp, l.dr - l.dt, l.vr - l.dr, l.vi - l.vr, l.total - l.vi};
+    for (int a = 0; a < 7; a++) std::fill(arr[a], arr[a] + len[a], (int64_t)0);
+    std::fill(h->yield, h->yield + n_events, (int64_t)0);
+    const size_t plane = (size_t)n_species * b->pT_bins;
     for (int64_t i = 0; i < n_particles; i++) {
         const is3d_particle &q = particles[i];
         if (q.species < 0 || q.species >= n_species || q.event < 0 || q.event >= n_events) return io_fail(IS3D_EINVAL, "particle %lld: species or event out of range", (long long)i);
-        const int ip = q.species;
-        yield[q.event] += 1;
-        const double yp = 0.5 * std::log((q.E + q.pz) / (q.E - q.pz));
-        const int iyp = (int)std::floor((yp + b->y_cut) / yw);                  // sample_dN_dy
-        if (iyp >= 0 && iyp < b->y_bins) dy[(size_t)ip * b->y_bins + iyp] += 1.0;
-        const int ieta = (int)std::floor((q.eta + b->eta_cut) / ew);            // sample_dN_deta
-        if (ieta >= 0 && ieta < b->eta_bins) de[(size_t)ip * b->eta_bins + ieta] += 1.0;
-        if (std::fabs(yp) <= b->y_cut) {
-            const double pT = std::sqrt(q.px * q.px + q.py * q.py);
-            const int ipT = (int)std::floor((pT - b->pT_lower_cut) / pw);       // sample_dN_2pipTdpTdy, sample_vn
-            if (ipT >= 0 && ipT < b->pT_bins) {
-                dp[(size_t)ip * b->pT_bins + ipT] += 1.0;
-                vc[(size_t)ip * b->pT_bins + ipT] += 1.0;
-                double phi = std::atan2(q.py, q.px);
-                if (phi < 0.0) phi += 2.0 * M_PI;
-                for (int k = 0; k < K_MAX; k++) {
-                    vr[((size_t)k * n_species + ip) * b->pT_bins + ipT] += std::cos(((double)k + 1.0) * phi);
-                    vi[((size_t)k * n_species + ip) * b->pT_bins + ipT] += std::sin(((double)k + 1.0) * phi);
-                }
+        const size_t ip = (size_t)q.species;
+        h->yield[q.event] += 1;
+        const is3d::SamplerBinIndex k = is3d::sampler_bin_particle(*b, w, q);
+        if (k.iyp >= 0) h->dN_dy[ip * b->y_bins + k.iyp] += 1;
+        if (k.ieta >= 0) h->dN_deta[ip * b->eta_bins + k.ieta] += 1;
+        if (k.itau >= 0) h->dN_tau[ip * b->tau_bins + k.itau] += 1;
+        if (k.ir >= 0) h->dN_r[ip * b->r_bins + k.ir] += 1;
+        if (k.ipT >= 0) {
+            const size_t j = ip * b->pT_bins + k.ipT;
+            h->dN_pT[j] += 1;
+            for (int m = 0; m < K_MAX; m++) {
+                const double c = std::cos(((double)m + 1.0) * k.phi), sn = std::sin(((double)m + 1.0) * k.phi);
+                h->vn_re[m * plane + j] += is3d::sampler_vn_fixed(c);
+                h->vn_im[m * plane + j] += is3d::sampler_vn_fixed(sn);
+                if (vr) { vr[m * plane + j] += c; vi[m * plane + j] += sn; }
             }
-            const double r = std::sqrt(q.x * q.x + q.y * q.y);                   // sample_dN_dX
-            const int itau = (int)std::floor((q.tau - b->tau_min) / tw), ir = (int)std::floor((r - b->r_min) / rw);
-            if (itau >= 0 && itau < b->tau_bins) dt[(size_t)ip * b->tau_bins + itau] += 1.0;
-            if (ir >= 0 && ir < b->r_bins) dr[(size_t)ip * b->r_bins + ir] += 1.0;
         }
     }
+    return IS3D_OK;
+}
+
+// vr, vi: the double harmonic sums of sampler_bin_list, or NULL: the fixed-point sums of the histograms
+int sampler_write_hist(const char *results_dir, const is3d_sampler_test_bins *b, int32_t n_events, int32_t n_species, const int64_t *mc_id,
+                       const is3d_sampler_hist *h, const double *vr, const double *vi, double mean_yield)
+{
+    const double two_pi = 2.0 * M_PI;
+    const is3d::SamplerBinWidths w = is3d::sampler_bin_widths(*b);
+    const double yw = w.yw, ew = w.ew, pw = w.pw, tw = w.tw, rw = w.rw;
+    const size_t plane = (size_t)n_species * b->pT_bins;
     const std::string root(results_dir);
     const double Nev = (double)n_events;
     for (int ip = 0; ip < n_species; ip++) {
@@ -1565,19 +1571,22 @@ extern "C" int is3d_write_sampler_tests(const char *results_dir, const is3d_samp
             return io_fail(IS3D_EIO, "couldn't open the sampler test files under %s (dN_dy/, dN_deta/, momentum_distribution/, vn/, spacetime_distribution/ must exist)", results_dir);
         double avg = 0.0;
         for (int i = 0; i < b->y_bins; i++) {                                    // :919-937
-            avg += dy[(size_t)ip * b->y_bins + i];
-            f1 << std::setprecision(6) << (-b->y_cut + yw * ((double)i + 0.5)) << "\t" << dy[(size_t)ip * b->y_bins + i] / (yw * Nev) << std::endl;
+            const double dy = (double)h->dN_dy[(size_t)ip * b->y_bins + i];
+            avg += dy;
+            f1 << std::setprecision(6) << (-b->y_cut + yw * ((double)i + 0.5)) << "\t" << dy / (yw * Nev) << std::endl;
         }
         f2 << std::setprecision(6) << avg / (2.0 * b->y_cut * Nev) << std::endl;
         for (int i = 0; i < b->eta_bins; i++)                                    // :961-972
-            f3 << std::setprecision(6) << (-b->eta_cut + ew * ((double)i + 0.5)) << "\t" << de[(size_t)ip * b->eta_bins + i] / (ew * Nev) << std::endl;
+            f3 << std::setprecision(6) << (-b->eta_cut + ew * ((double)i + 0.5)) << "\t" << (double)h->dN_deta[(size_t)ip * b->eta_bins + i] / (ew * Nev) << std::endl;
         for (int i = 0; i < b->pT_bins; i++) {                                   // :991-1001, :1156-1177
             const double pT_mid = b->pT_lower_cut + pw * ((double)i + 0.5);
-            f4 << std::setprecision(6) << std::scientific << pT_mid << "\t" << dp[(size_t)ip * b->pT_bins + i] / (two_pi * 2.0 * b->y_cut * pw * pT_mid * Nev) << "\n";
+            const double count = (double)h->dN_pT[(size_t)ip * b->pT_bins + i];
+            f4 << std::setprecision(6) << std::scientific << pT_mid << "\t" << count / (two_pi * 2.0 * b->y_cut * pw * pT_mid * Nev) << "\n";
             f5 << std::setprecision(6) << std::scientific << pT_mid;
             for (int k = 0; k < K_MAX; k++) {
-                const size_t j = ((size_t)k * n_species + ip) * b->pT_bins + i;
-                double vn_abs = std::sqrt(vr[j] * vr[j] + vi[j] * vi[j]) / vc[(size_t)ip * b->pT_bins + i];
+                const size_t j = (size_t)k * plane + (size_t)ip * b->pT_bins + i;
+                const double re = vr ? vr[j] : (double)h->vn_re[j] / IS3D_SAMPLER_VN_SCALE, im = vi ? vi[j] : (double)h->vn_im[j] / IS3D_SAMPLER_VN_SCALE;
+                double vn_abs = std::sqrt(re * re + im * im) / count;
                 if (std::isnan(vn_abs) || std::isinf(vn_abs)) vn_abs = 0.0;
                 f5 << "\t" << vn_abs;
             }
@@ -1585,19 +1594,59 @@ extern "C" int is3d_write_sampler_tests(const char *results_dir, const is3d_samp
         }
         for (int i = 0; i < b->r_bins; i++) {                                    // :1215-1221
             const double r_mid = b->r_min + rw * ((double)i + 0.5);
-            f7 << std::setprecision(6) << std::scientific << r_mid << "\t" << dr[(size_t)ip * b->r_bins + i] / (2.0 * M_PI * r_mid * rw * Nev * 2.0 * b->y_cut) << "\n";
+            f7 << std::setprecision(6) << std::scientific << r_mid << "\t" << (double)h->dN_r[(size_t)ip * b->r_bins + i] / (2.0 * M_PI * r_mid * rw * Nev * 2.0 * b->y_cut) << "\n";
         }
         for (int i = 0; i < b->tau_bins; i++) {                                  // :1223-1229
             const double tau_mid = b->tau_min + tw * ((double)i + 0.5);
-            f6 << std::setprecision(6) << std::scientific << tau_mid << "\t" << dt[(size_t)ip * b->tau_bins + i] / (tau_mid * tw * Nev * 2.0 * b->y_cut) << "\n";
+            f6 << std::setprecision(6) << std::scientific << tau_mid << "\t" << (double)h->dN_tau[(size_t)ip * b->tau_bins + i] / (tau_mid * tw * Nev * 2.0 * b->y_cut) << "\n";
         }
     }
     std::ofstream fm(root + "/mean_yield.dat"), fl(root + "/yield_list.dat");   // :1244-1257
     if (!fm || !fl) return io_fail(IS3D_EIO, "couldn't open %s/mean_yield.dat", results_dir);
     fm << mean_yield << std::endl;
     fl << "sampled particle yield\n";
-    for (int e = 0; e < n_events; e++) fl << yield[e] << std::endl;
+    for (int e = 0; e < n_events; e++) fl << h->yield[e] << std::endl;
     return IS3D_OK;
+}
+
+bool hist_has_null(const is3d_sampler_hist *h)
+{
+    return !h || !h->dN_dy || !h->dN_deta || !h->dN_pT || !h->dN_tau || !h->dN_r || !h->vn_re || !h->vn_im || !h->yield;
+}
+bool sampler_sizes_bad(const is3d_sampler_test_bins *b, int32_t n_events, int32_t n_species)
+{
+    return b->y_bins < 1 || b->eta_bins < 1 || b->pT_bins < 1 || b->tau_bins < 1 || b->r_bins < 1 || n_events < 1 || n_species < 1;
+}
+}  // namespace
+
+extern "C" int is3d_sampler_bin_list(const is3d_sampler_test_bins *b, int32_t n_events, int32_t n_species, int64_t n_particles,
+                                     const is3d_particle *particles, const is3d_sampler_hist *hist)
+{
+    if (!b || hist_has_null(hist) || (n_particles > 0 && !particles)) return io_fail(IS3D_EINVAL, "null argument");
+    if (sampler_sizes_bad(b, n_events, n_species)) return io_fail(IS3D_EINVAL, "sampler test bins must be positive");
+    return sampler_bin_list(b, n_events, n_species, n_particles, particles, hist, nullptr, nullptr);
+}
+
+extern "C" int is3d_write_sampler_tests_binned(const char *results_dir, const is3d_sampler_test_bins *b, int32_t n_events, int32_t n_species,
+                                               const int64_t *mc_id, const is3d_sampler_hist *hist, double mean_yield)
+{
+    if (!results_dir || !b || !mc_id || hist_has_null(hist)) return io_fail(IS3D_EINVAL, "null argument");
+    if (sampler_sizes_bad(b, n_events, n_species)) return io_fail(IS3D_EINVAL, "sampler test bins must be positive");
+    return sampler_write_hist(results_dir, b, n_events, n_species, mc_id, hist, nullptr, nullptr, mean_yield);
+}
+
+extern "C" int is3d_write_sampler_tests(const char *results_dir, const is3d_sampler_test_bins *b, int32_t n_events, int32_t n_species,
+                                        const int64_t *mc_id, int64_t n_particles, const is3d_particle *particles, double mean_yield)
+{
+    if (!results_dir || !b || !mc_id || (n_particles > 0 && !particles)) return io_fail(IS3D_EINVAL, "null argument");
+    if (sampler_sizes_bad(b, n_events, n_species)) return io_fail(IS3D_EINVAL, "sampler test bins must be positive");
+    const size_t S = (size_t)n_species, plane = S * b->pT_bins;
+    std::vector<int64_t> dy(S * b->y_bins), de(S * b->eta_bins), dp(plane), dt(S * b->tau_bins), dr(S * b->r_bins), fr(K_MAX * plane), fi(K_MAX * plane);
+    std::vector<int64_t> yield((size_t)n_events);
+    std::vector<double> vr(K_MAX * plane, 0.0), vi(K_MAX * plane, 0.0);
+    const is3d_sampler_hist h{dy.data(), de.data(), dp.data(), dt.data(), dr.data(), fr.data(), fi.data(), yield.data()};
+    if (int rc = sampler_bin_list(b, n_events, n_species, n_particles, particles, &h, vr.data(), vi.data())) return rc;
+    return sampler_write_hist(results_dir, b, n_events, n_species, mc_id, &h, vr.data(), vi.data(), mean_yield);
 }
 
 // operation 0: the smooth spacetime distributions of calculate_dN_dX (emissionfunction_smooth_kernels.cpp:1100-1127, :1403-1434) from the raw

@@ -25,6 +25,10 @@
 // feed-down (is3d_resonance_decays) runs on the spectrum on the first device of the run's list and results/dN_pTdpTdphidy_resonance_decays.dat
 // and dN_dpTdphidy_resonance_decays.dat are appended (emissionfunction.cpp:1689-1698); the embedding result keeps the thermal spectrum.
 // Operations 0 and 2 and hrg_eos = 3 (no decay data) refuse the key.
+// test_sampler_on_device = 1 (optional key, default 0): with operation = 2 and test_sampler = 1 the hadrons are sampled ONCE and binned per event
+// batch on the device (is3d_sample_binned_multi), never held as a list; the same files are written from the integer histograms
+// (is3d_write_sampler_tests_binned; vn/ to the fixed point) and the same lines printed, plus ms_bin.  test_sampler = 0, other operations and
+// the embedding entry (which returns the list) refuse the key.
 // mode = 5: every run, whatever its operation, ends with the spin polarization from the surface's thermal vorticity (calculate_spin_polzn,
 // emissionfunction.cpp:1675) and appends results/St.dat, Sx.dat, Sy.dat, Sn.dat (write_polzn_vector_toFile, :1701), with T from the averages
 // file just written or T_switch when set_FO_temperature = 1; the embedding entry has no vorticity and says so.
@@ -187,6 +191,20 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
             if (hrg_eos == 3)
                 DIE("do_resonance_decays = 1 with hrg_eos = 3: PDG/pdg_box.dat carries no decay data (smash box: no decay info, iS3D_parameters.dat); use hrg_eos = 1 or 2");
             do_decays = true;
+        }
+    }
+    bool bin_on_device = false;
+    {
+        double on_device = 0.0, test_sampler = 0.0;   // optional key: the test_sampler = 1 distributions binned on the device, no particle list
+        if (get_param("test_sampler_on_device", &on_device, false) == IS3D_OK && (int)on_device) {
+            if (operation != 2)
+                DIE("test_sampler_on_device = 1 with operation = %d: it bins the sampler's hadrons (operation = 2); set test_sampler_on_device = 0", operation);
+            if (get_param("test_sampler", &test_sampler)) return IS3D_EINVAL;
+            if (!(int)test_sampler)
+                DIE("test_sampler_on_device = 1 with test_sampler = 0: the particle list is the output of that run and is not kept on this path; set test_sampler_on_device = 0");
+            if (res)
+                DIE("test_sampler_on_device = 1: the embedding entry returns the particle list, which this path never holds; set test_sampler_on_device = 0");
+            bin_on_device = true;
         }
     }
     const bool vah = !mem && mode == 2;
@@ -474,6 +492,30 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         if (df_mode == 2) printf("Sampling particles with Chapman Enskog df...\n");
         if (df_mode == 3) printf("Sampling particles with Mike's modified distribution...\n");
         if (df_mode == 4) printf("Sampling particles with Jonah's modified distribution...\n");
+        if (bin_on_device) {
+            // one pass: every event batch is binned on its device and dropped; the integer histograms of the shards are added on the host
+            const size_t S = (size_t)sp.n, plane = (size_t)IS3D_SAMPLER_VN_HARMONICS * S * bins.pT_bins;
+            std::vector<int64_t> h_dy(S * bins.y_bins), h_de(S * bins.eta_bins), h_dp(S * bins.pT_bins), h_dt(S * bins.tau_bins), h_dr(S * bins.r_bins),
+                h_vr(plane), h_vi(plane), h_yield((size_t)si.n_events);
+            const is3d_sampler_hist hist{h_dy.data(), h_de.data(), h_dp.data(), h_dt.data(), h_dr.data(), h_vr.data(), h_vi.data(), h_yield.data()};
+            const int rcb = is3d_sample_binned_multi(&cells, &sp, &df, &si, &opts, rd.list.empty() ? nullptr : rd.list.data(), (int32_t)rd.list.size(), &bins,
+                                                     &hist, &count, &ss);
+            if (rcb) DIE("is3d_sample_binned failed (%d): %s", rcb, is3d_last_error());
+            double t2s = now_s();
+            printf("\nMomentum sampling efficiency = %f %%\n", 100.0 * (double)ss.n_acceptances / (double)std::max<int64_t>(ss.n_momentum_samples, 1));
+            if (feqmod) printf("feqmod breaks down for %lld cells\n", (long long)ss.n_cells_breakdown);
+            printf("Writing the binned sampler test distributions...\n");
+            if (is3d_write_sampler_tests_binned("results", &bins, si.n_events, sp.n, mcid.data(), &hist, mean_yield)) DIE("%s", is3d_last_error());
+            double t3s = now_s();
+            printf("particles: %lld in %d event(s); hadrons drawn %lld; cells skipped (u.dsigma <= 0): %lld\n", (long long)count, si.n_events,
+                   (long long)ss.n_hadrons_drawn, (long long)ss.n_cells_skipped);
+            printf("device time: prep %.3f ms, count %.3f ms, fill %.3f ms; h2d %.3f ms\n", ss.ms_prep, ss.ms_count, ss.ms_fill, ss.ms_h2d);
+            printf("binned on the device: ms_bin %.3f ms, particle workspace %lld bytes (one event batch)\n", ss.ms_bin, (long long)ss.particle_workspace_bytes);
+            printf("wall: read %.3f s, sampling %.3f s, write %.3f s\n", t1 - t0, t2s - t1, t3s - t2s);
+            if (int rcp = polarization()) return rcp;
+            printf("Done sampling particles. Output stored in results folder. Goodbye!\n");
+            return IS3D_OK;
+        }
         int rc2 = is3d_sample_particles_multi(&cells, &sp, &df, &si, &opts, rd.list.empty() ? nullptr : rd.list.data(), (int32_t)rd.list.size(), nullptr, 0, &count, &ss);
         if (rc2) DIE("is3d_sample_particles failed (%d): %s", rc2, is3d_last_error());
         std::vector<is3d_particle> plist((size_t)std::max<int64_t>(count, 1));
