@@ -1067,6 +1067,21 @@ static hipError_t st_grow(DevBuf<T> &buf, size_t n)
 // the breakdown cells' workgroup slots of cf_st_fq_linear (2+1D: eta partial slots after the chunks')
 static int st_linear_slots(int64_t nc) { return (int)std::max<int64_t>(1, std::min<int64_t>(64, nc)); }
 
+// what the per-cell kernels take of a grid: up to 64 pT values (one wave holds a class), and in 2+1D the workgroup's eta rows in LDS --
+// [4 waves][64 / npTp classes][K] doubles within 64 KiB (the feqmod kernel keeps 16 KiB of it for its staged records: 48 KiB).  A function of
+// the grid alone: the one-shot entries ask it before they create a plan
+static int st_check_grid(bool dim3, bool feqmod, int npT, int K)
+{
+    if (npT > 64) return fail(IS3D_EINVAL, "operation 0 takes pT grids of up to 64 values (got %d)", npT);
+    int npTp = 1;
+    while (npTp < npT) npTp <<= 1;
+    const size_t cap = feqmod ? 48 * 1024 : 64 * 1024, per_eta = sizeof(double) * 4 * (64 / npTp);
+    if (!dim3 && per_eta * (size_t)K > cap)
+        return fail(IS3D_EINVAL, "operation 0 in 2+1D: %d pT values x %d eta nodes need more LDS than the per-cell kernel has (up to %d eta nodes "
+                    "with this pT grid)", npT, K, (int)(cap / per_eta));
+    return IS3D_OK;
+}
+
 static int st_execute(is3d_plan *P, const is3d_cells *cells, const double *x, const double *y, const double *pT_w, const double *phi_w,
                       const is3d_spacetime_bins *bins, const is3d_spacetime_out *out, void *hip_stream, is3d_spacetime_stats *stats,
                       is3d_spacetime_feqmod_stats *fstats)
@@ -1077,17 +1092,10 @@ static int st_execute(is3d_plan *P, const is3d_cells *cells, const double *x, co
     int rc = st_check(bins, x, y, P->opts.df_mode, P->feqmod);
     if (rc) return rc;
     if (P->feqmod ? !is3d::spacetime_feqmod_shape_supported(P->dim3, P->JT, P->KT) : !is3d::spacetime_shape_supported(P->dim3, P->JT, P->KT))
-        return fail(IS3D_EINVAL, "operation 0 runs on the plan's unit records of the default tile shapes (this plan: kernel variant %d, %d x %d)",
-                    P->variant, P->JT, P->KT);
-    if (P->npT > 64) return fail(IS3D_EINVAL, "operation 0 takes pT grids of up to 64 values (got %d)", P->npT);
-    {
-        int npTp = 1;
-        while (npTp < P->npT) npTp <<= 1;
-        // the feqmod kernel keeps 16 KiB of LDS for its staged records
-        const size_t cap = P->feqmod ? 48 * 1024 : 64 * 1024;
-        if (!P->dim3 && sizeof(double) * 4 * (64 / npTp) * (size_t)P->K > cap)
-            return fail(IS3D_EINVAL, "operation 0 in 2+1D: %d pT values x %d eta nodes need more LDS than the per-cell kernel has", P->npT, P->K);
-    }
+        return fail(IS3D_EINVAL, "operation 0 runs on the plan's unit records of the default tile shapes (this plan: kernel variant %d, %d x %d "
+                    "records for %d %s nodes)", P->variant, P->JT, P->KT, P->K, P->dim3 ? "y" : "eta");
+    rc = st_check_grid(P->dim3, P->feqmod, P->npT, P->K);
+    if (rc) return rc;
     if (!out->dN_dy || !out->dN_taudtaudy || !out->dN_twopirdrdy || !out->dN_twopitaurdtaudrdy || !out->dN_dydeta)
         return fail(IS3D_EINVAL, "a required output array is NULL");
     const int64_t n = cells->n_cells;
@@ -1326,6 +1334,7 @@ static int st_oneshot(const is3d_cells *cells, const double *x, const double *y,
     if (!rc && fq && opts->include_baryon && opts->df_mode == 4)
         rc = fail(IS3D_EINVAL, "df_mode 4 does not work with include_baryon = 1 (the reference exits there too)");
     if (!rc && fq) rc = validate(species, grid, df, fq, opts);   // every check before the plan touches the device
+    if (!rc && grid && (opts->dimension == 2 || opts->dimension == 3)) rc = st_check_grid(opts->dimension == 3, fq != nullptr, grid->n_pT, grid->n_eta);
     if (rc) { if (stats) stats->code = rc; return rc; }
     is3d_plan *P = nullptr;
     rc = plan_create_impl(&P, species, grid, df, fq, opts, std::max<int64_t>(cells->n_cells, 1));

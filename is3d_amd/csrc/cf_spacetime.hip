@@ -39,7 +39,8 @@ __device__ __forceinline__ double st_unscale(const unsigned long long *bound_bit
 //   p.dsigma = mT A_k + W_k pT B_j;   x = p.u/T = mT Cp_k - pT Dp_j;   z = exp(-x + b alpha_B)
 //   br = mT^2 alpha_k + mT pT beta_jk + pT^2 gamma_j [+ b (mT L_k + pT L2_j)]
 //   14-moment: df = br / (1 + sign z);  Chapman-Enskog: df = br / ((1 + sign z) x);   f = z / (1 + sign z) (1 + df)
-// Phi entries past J (the last tile's clamped copies) carry w_phi = 0; rows past K are neutral padding (A = W = 0).
+// Phi entries past J (the last tile's clamped copies) carry w_phi = 0; rows past K are neutral padding (A = W = 0) in 2+1D, where W enters
+// p.dsigma; in 3+1D (W = 1, not read) the row loop stops at the y grid's last row.
 // ------------------------------------------------------------------------------------------------
 template <bool CE, bool DIM3, bool BARYON, int JT, int R>
 __global__ void __launch_bounds__(256) cf_st_cells(const StCellArgs a)
@@ -95,6 +96,7 @@ __global__ void __launch_bounds__(256) cf_st_cells(const StCellArgs a)
                 const double baB = BARYON ? bq * U[4 * JT] : 0.0;
                 const double *__restrict__ rows = U + HDR;
                 for (int r = 0; r < R; r++) {
+                    if (DIM3 && rb * R + r >= K) break;   // padding rows: W is not read in 3+1D, pT B_j f of row K - 1 would be added
                     const double *__restrict__ row = rows + r * RW;
                     const double mTC = mT * row[1];
                     const double earg = BARYON ? (bmax - mTC) + baB : bmax - mTC;
