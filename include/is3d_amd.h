@@ -585,6 +585,15 @@ typedef struct {
 /* list -> histograms on the host (step 1 of is3d_write_sampler_tests; the CPU yardstick of the device kernel).  hist is overwritten. */
 int is3d_sampler_bin_list(const is3d_sampler_test_bins *bins, int32_t n_events, int32_t n_species, int64_t n_particles,
                           const is3d_particle *particles, const is3d_sampler_hist *hist);
+/* list -> histograms on the DEVICE: a caller's HOST list (any order, any length) is uploaded, binned by cf_sampler_bins in the form
+ * bins->kernel_form, and the histograms copied to hist (HOST arrays, overwritten) as is3d_sampler_plan_execute_binned does.  A particle
+ * whose species is outside [0, n_species) or whose event is outside [0, n_events) adds nothing (is3d_sampler_bin_list refuses such a
+ * list): *n_skipped = n_particles - sum(yield) counts them.  Checked before any device use: the bins and kernel_form as for
+ * is3d_sampler_plan_execute_binned (kernel_form = 2 on a block that does not fit the LDS included), n_events >= 1, n_species >= 1,
+ * n_particles >= 0, particles non-null when n_particles > 0: IS3D_EINVAL.  n_particles = 0: zero histograms, no launch.  A dN_pT bin
+ * above IS3D_SAMPLER_VN_MAX_COUNT: IS3D_EDOMAIN.  device < 0: the current device. */
+int is3d_sampler_bin_list_device(const is3d_sampler_test_bins *bins, int32_t n_events, int32_t n_species, int64_t n_particles,
+                                 const is3d_particle *particles, const is3d_sampler_hist *hist, int64_t *n_skipped, int32_t device);
 /* histograms -> the files of is3d_write_sampler_tests (step 2); every file but vn/ is byte for byte the list writer's, vn/ agrees to
  * the fixed point (2^-32 absolute in v_n before the 7 printed digits). */
 int is3d_write_sampler_tests_binned(const char *results_dir, const is3d_sampler_test_bins *bins, int32_t n_events, int32_t n_species,

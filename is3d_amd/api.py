@@ -116,7 +116,8 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_write_polarization", "is3d_surface_vorticity",
            "is3d_pdg_read_decays", "is3d_decay_q_factor", "is3d_resonance_decays", "is3d_decay_plan_create", "is3d_decay_plan_output_size",
            "is3d_decay_plan_execute", "is3d_decay_plan_destroy", "is3d_write_results_decays",
-           "is3d_sampler_bin_list", "is3d_write_sampler_tests_binned", "is3d_sampler_plan_execute_binned", "is3d_sample_binned", "is3d_sample_binned_multi"]
+           "is3d_sampler_bin_list", "is3d_write_sampler_tests_binned", "is3d_sampler_plan_execute_binned", "is3d_sample_binned", "is3d_sample_binned_multi",
+           "is3d_sampler_bin_list_device"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 POLARIZATION_OUTPUTS = ["St", "Sx", "Sy", "Sn", "Snorm"]
@@ -1516,6 +1517,21 @@ def sampler_bin_list(bins, n_events, n_species, particles):
     L.is3d_sampler_bin_list.argtypes = [C.POINTER(SamplerTestBins), C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(SamplerHist)]
     _check(L.is3d_sampler_bin_list(C.byref(b), int(n_events), int(n_species), len(particles), particles.ctypes.data, C.byref(h)))
     return out
+
+
+def sampler_bin_list_device(bins, n_events, n_species, particles, device=0):
+    """is3d_sampler_bin_list_device: a host particle list binned by the device kernel (form bins["kernel_form"]).  Returns (dict of int64
+    histograms, n_skipped); n_skipped counts the particles whose species or event is out of range, which add nothing."""
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    b = _pack_bins(bins)
+    h, out = _hist_arrays(bins, n_events, n_species)
+    skipped = C.c_int64(0)
+    L = load()
+    L.is3d_sampler_bin_list_device.argtypes = [C.POINTER(SamplerTestBins), C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(SamplerHist),
+                                               C.POINTER(C.c_int64), C.c_int32]
+    _check(L.is3d_sampler_bin_list_device(C.byref(b), int(n_events), int(n_species), len(particles), particles.ctypes.data, C.byref(h),
+                                          C.byref(skipped), int(device)))
+    return out, int(skipped.value)
 
 
 def write_sampler_tests_binned(results_dir, bins, n_events, mc_id, hist, mean_yield=0.0):

@@ -1251,3 +1251,49 @@ extern "C" int is3d_sample_binned(const is3d_cells *cells, const is3d_species *s
     if (stats) stats->ms_h2d = r.ms_h2d;
     return rc;
 }
+
+// a caller's list through the same kernel: upload, sampler_bins_launch, download as is3d_sampler_plan_execute_binned does
+extern "C" int is3d_sampler_bin_list_device(const is3d_sampler_test_bins *bins, int32_t n_events, int32_t n_species, int64_t n_particles,
+                                            const is3d_particle *particles, const is3d_sampler_hist *hist, int64_t *n_skipped, int32_t device)
+{
+    using is3d::set_error;
+    if (!n_skipped) return set_error(IS3D_EINVAL, "null argument");
+    *n_skipped = 0;
+    if (int rc = check_bin_args(bins, hist, n_events)) return rc;
+    if (n_species < 1) return set_error(IS3D_EINVAL, "n_species must be >= 1");
+    if (n_particles < 0 || (n_particles > 0 && !particles)) return set_error(IS3D_EINVAL, "n_particles must be >= 0 and particles non-null");
+    const is3d::SamplerHistLayout l = is3d::sampler_hist_layout(*bins, n_species);
+    if (bins->kernel_form == 2 && !is3d::sampler_bins_lds_fits(l))
+        return set_error(IS3D_EINVAL, "kernel_form = 2: %lld histogram words do not fit the LDS", (long long)l.total);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return set_error(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
+    const HistParts parts = hist_parts(*hist, l);
+    for (int a = 0; a < 7; a++) memset(parts.p[a], 0, (size_t)parts.n[a] * sizeof(int64_t));
+    memset(hist->yield, 0, (size_t)n_events * sizeof(int64_t));
+    if (n_particles == 0) return IS3D_OK;
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    const int64_t words = l.total + n_events;
+    DevMem d_list, d_hist;
+    HIP_TRY(d_list.alloc((size_t)n_particles * sizeof(is3d_particle)));
+    HIP_TRY(d_hist.alloc((size_t)words * sizeof(int64_t)));
+    HIP_TRY(hipMemcpy(d_list.p, particles, (size_t)n_particles * sizeof(is3d_particle), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(d_hist.p, 0, (size_t)words * sizeof(int64_t), nullptr));
+    HIP_TRY(is3d::sampler_bins_launch(*bins, is3d::sampler_bin_widths(*bins), l, n_species, n_events, d_list.as<is3d_particle>(), n_particles,
+                                      d_hist.as<unsigned long long>(), d_hist.as<unsigned long long>() + l.total, bins->kernel_form));
+    std::vector<int64_t> h((size_t)words);
+    HIP_TRY(hipMemcpy(h.data(), d_hist.p, (size_t)words * sizeof(int64_t), hipMemcpyDeviceToHost));
+    const int64_t *src = h.data();
+    for (int a = 0; a < 7; a++) {
+        memcpy(parts.p[a], src, (size_t)parts.n[a] * sizeof(int64_t));
+        src += parts.n[a];
+    }
+    memcpy(hist->yield, src, (size_t)n_events * sizeof(int64_t));
+    int64_t counted = 0;
+    for (int32_t e = 0; e < n_events; e++) counted += hist->yield[e];
+    *n_skipped = n_particles - counted;
+    for (int64_t j = 0; j < parts.n[2]; j++)
+        if (hist->dN_pT[j] > IS3D_SAMPLER_VN_MAX_COUNT)
+            return set_error(IS3D_EDOMAIN, "dN_pT bin %lld holds %lld hadrons: the fixed-point harmonic sums are exact up to %lld per bin", (long long)j,
+                             (long long)hist->dN_pT[j], (long long)IS3D_SAMPLER_VN_MAX_COUNT);
+    return IS3D_OK;
+}

@@ -1613,9 +1613,10 @@ bool hist_has_null(const is3d_sampler_hist *h)
 {
     return !h || !h->dN_dy || !h->dN_deta || !h->dN_pT || !h->dN_tau || !h->dN_r || !h->vn_re || !h->vn_im || !h->yield;
 }
+// (an empty range would divide by zero in the bin rule and in the writers' normalisation)
 bool sampler_sizes_bad(const is3d_sampler_test_bins *b, int32_t n_events, int32_t n_species)
 {
-    return b->y_bins < 1 || b->eta_bins < 1 || b->pT_bins < 1 || b->tau_bins < 1 || b->r_bins < 1 || n_events < 1 || n_species < 1;
+    return !is3d::sampler_bins_valid(*b) || n_events < 1 || n_species < 1;
 }
 }  // namespace
 
@@ -1623,7 +1624,7 @@ extern "C" int is3d_sampler_bin_list(const is3d_sampler_test_bins *b, int32_t n_
                                      const is3d_particle *particles, const is3d_sampler_hist *hist)
 {
     if (!b || hist_has_null(hist) || (n_particles > 0 && !particles)) return io_fail(IS3D_EINVAL, "null argument");
-    if (sampler_sizes_bad(b, n_events, n_species)) return io_fail(IS3D_EINVAL, "sampler test bins must be positive");
+    if (sampler_sizes_bad(b, n_events, n_species)) return io_fail(IS3D_EINVAL, "sampler test bins: counts, n_events and n_species must be >= 1, y_cut and eta_cut > 0, every range non-empty");
     return sampler_bin_list(b, n_events, n_species, n_particles, particles, hist, nullptr, nullptr);
 }
 
@@ -1631,7 +1632,7 @@ extern "C" int is3d_write_sampler_tests_binned(const char *results_dir, const is
                                                const int64_t *mc_id, const is3d_sampler_hist *hist, double mean_yield)
 {
     if (!results_dir || !b || !mc_id || hist_has_null(hist)) return io_fail(IS3D_EINVAL, "null argument");
-    if (sampler_sizes_bad(b, n_events, n_species)) return io_fail(IS3D_EINVAL, "sampler test bins must be positive");
+    if (sampler_sizes_bad(b, n_events, n_species)) return io_fail(IS3D_EINVAL, "sampler test bins: counts, n_events and n_species must be >= 1, y_cut and eta_cut > 0, every range non-empty");
     return sampler_write_hist(results_dir, b, n_events, n_species, mc_id, hist, nullptr, nullptr, mean_yield);
 }
 
@@ -1639,7 +1640,7 @@ extern "C" int is3d_write_sampler_tests(const char *results_dir, const is3d_samp
                                         const int64_t *mc_id, int64_t n_particles, const is3d_particle *particles, double mean_yield)
 {
     if (!results_dir || !b || !mc_id || (n_particles > 0 && !particles)) return io_fail(IS3D_EINVAL, "null argument");
-    if (sampler_sizes_bad(b, n_events, n_species)) return io_fail(IS3D_EINVAL, "sampler test bins must be positive");
+    if (sampler_sizes_bad(b, n_events, n_species)) return io_fail(IS3D_EINVAL, "sampler test bins: counts, n_events and n_species must be >= 1, y_cut and eta_cut > 0, every range non-empty");
     const size_t S = (size_t)n_species, plane = S * b->pT_bins;
     std::vector<int64_t> dy(S * b->y_bins), de(S * b->eta_bins), dp(plane), dt(S * b->tau_bins), dr(S * b->r_bins), fr(K_MAX * plane), fi(K_MAX * plane);
     std::vector<int64_t> yield((size_t)n_events);

@@ -118,3 +118,34 @@ def test_shard_bounds_and_multi_entry_argument_checks(fx):
         with pytest.raises(api.Is3dError) as e:
             api.smooth_spectra_multi(cells, fx["pikp"], fx["grid"], fx["df"], dict(dimension=3, df_mode=1), devices=[0, 99])
         assert e.value.code == api.IS3D_EINVAL
+
+
+def test_sampler_bin_list_device_validates_before_device_use():
+    """is3d_sampler_bin_list_device: every refusal is IS3D_EINVAL with or without a device; a good call without one is IS3D_ENODEVICE."""
+    bins = dict(y_cut=1.5, eta_cut=4.0, pT_lower_cut=0.25, pT_upper_cut=2.75, tau_min=1.0, tau_max=9.0, r_min=0.5, r_max=8.0,
+                y_bins=12, eta_bins=16, pT_bins=10, tau_bins=8, r_bins=15)
+    p = np.zeros(3, dtype=api.PARTICLE_DTYPE)
+    p["E"], p["tau"] = 1.0, 2.0
+    p0, a0 = api.resource_counters()
+    for bad, ne, ns in ((dict(y_bins=0), 2, 3), (dict(tau_max=1.0), 2, 3), (dict(eta_cut=0.0), 2, 3), (dict(kernel_form=3), 2, 3), (dict(kernel_form=-1), 2, 3),
+                        ({}, 0, 3), ({}, 2, 0), (dict(kernel_form=2), 2, 305)):
+        with pytest.raises(api.Is3dError) as e:
+            api.sampler_bin_list_device(dict(bins, **bad), ne, ns, p)
+        assert e.value.code == api.IS3D_EINVAL, (bad, ne, ns)
+    assert "%d histogram words" % (305 * (12 + 16 + 8 + 15 + 15 * 10)) in str(e.value)        # the block that does not fit, by its size
+    L = api.load()
+    b = api._pack_bins(bins)
+    h, _keep = api._hist_arrays(bins, 2, 3)
+    skipped = ctypes.c_int64(0)
+    L.is3d_sampler_bin_list_device.argtypes = [ctypes.POINTER(api.SamplerTestBins), ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
+                                               ctypes.POINTER(api.SamplerHist), ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]
+    assert L.is3d_sampler_bin_list_device(ctypes.byref(b), 2, 3, -1, p.ctypes.data, ctypes.byref(h), ctypes.byref(skipped), 0) == api.IS3D_EINVAL
+    assert L.is3d_sampler_bin_list_device(ctypes.byref(b), 2, 3, 3, None, ctypes.byref(h), ctypes.byref(skipped), 0) == api.IS3D_EINVAL
+    assert L.is3d_sampler_bin_list_device(ctypes.byref(b), 2, 3, 3, p.ctypes.data, None, ctypes.byref(skipped), 0) == api.IS3D_EINVAL
+    assert L.is3d_sampler_bin_list_device(ctypes.byref(b), 2, 3, 3, p.ctypes.data, ctypes.byref(h), None, 0) == api.IS3D_EINVAL
+    assert L.is3d_sampler_bin_list_device(None, 2, 3, 3, p.ctypes.data, ctypes.byref(h), ctypes.byref(skipped), 0) == api.IS3D_EINVAL
+    assert api.resource_counters() == (p0, a0)
+    if L.is3d_device_count() == 0:
+        with pytest.raises(api.Is3dError) as e:
+            api.sampler_bin_list_device(bins, 2, 3, p)
+        assert e.value.code == api.IS3D_ENODEVICE and "no CPU path" in str(e.value)

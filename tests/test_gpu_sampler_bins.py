@@ -1,10 +1,13 @@
 """GPU (-m gpu): the sampler's test_sampler = 1 distributions binned on the device and list-free (is3d_sample_binned,
 is3d_sampler_plan_execute_binned, is3d_sample_binned_multi) against the host yardstick on the sampler's own list
-(is3d_sampler_bin_list(is3d_sample_particles)): parity, invariance under batching / sharding / devices, the memory bound, the refusals."""
+(is3d_sampler_bin_list(is3d_sample_particles)): parity, invariance under batching / sharding / devices, the memory bound, the refusals; and
+the same parity for the 305-species list (global atomics: the block does not fit the LDS), df_mode 3 / 4, fast = 1, include_baryon = 1, batches
+without a particle, more shards than cells and a single event."""
 import numpy as np
 import pytest
 
 from is3d_amd import api, inputs, synth
+from sampler_bins_ref import layout_total
 
 pytestmark = pytest.mark.gpu
 COUNTS = ("dN_dy", "dN_deta", "dN_pT", "dN_tau", "dN_r", "yield")
@@ -128,3 +131,101 @@ def test_refusals_and_the_empty_surface(runs, fx):
     assert api.resource_counters() == (p0, a0)              # refused before any plan or launch
     empty, st = api.sample_binned({k: v[:0] for k, v in r["cells"].items()}, *args, r["bins"], r["o"], n_events=3, seed=7)
     assert st["n_particles"] == 0 and all(not empty[k].any() for k in ALL) and empty["yield"].shape == (3,)
+
+
+# ---- more of the sampler through the same parity: the inputs are those tests/test_gpu_sampler.py builds for these modes ----
+SHIPPED_BINS = dict(y_cut=5.0, y_bins=50, eta_cut=7.0, eta_bins=70, pT_lower_cut=0.0, pT_upper_cut=3.0, pT_bins=100, tau_min=0.0, tau_max=12.0,
+                    tau_bins=120, r_min=0.0, r_max=12.0, r_bins=60)             # iS3D_parameters.dat as shipped
+
+
+def parity(cells, sp, df, gla, bins, o, kw, at_least):
+    """sample_binned against sampler_bin_list(sample_particles) of the same inputs: counts and yields exact, vn within one fixed-point step per
+    particle; no sampled particle within 1e-9 of a rapidity edge or of the gate (a property of the seed, asserted).  Returns (list, got, stats)."""
+    p, lst = api.sample_particles(cells, sp, df, gla, o, **kw)
+    print("hadrons:", len(p))
+    assert len(p) >= at_least
+    yp = 0.5 * np.log((p["E"] + p["pz"]) / (p["E"] - p["pz"]))
+    u = (yp + bins["y_cut"]) / (2.0 * bins["y_cut"] / bins["y_bins"])
+    assert np.abs(u - np.rint(u)).min() > 1e-9 and np.abs(np.abs(yp) - bins["y_cut"]).min() > 1e-9
+    want = api.sampler_bin_list(bins, kw["n_events"], len(sp["mass"]), p)
+    got, st = api.sample_binned(cells, sp, df, gla, bins, o, **kw)
+    for k in COUNTS:
+        assert got[k].dtype == np.int64 and np.array_equal(got[k], want[k]), k
+    for k in ("vn_re", "vn_im"):
+        assert np.all(np.abs(got[k] - want[k]) <= want["dN_pT"][None]), k
+    assert st["n_particles"] == len(p) == got["yield"].sum() and st["n_hadrons_drawn"] == lst["n_hadrons_drawn"]
+    return p, got, st
+
+
+def test_305_species_take_the_global_form(fx):
+    """The urqmd list at the shipped bin counts on the 3+1D surface: 305 * 1800 words do not fit the LDS, so form 0 must choose global atomics
+    (the same bits as form 1) and form 2 is refused."""
+    cells = synth.synth_surface(600, 3, seed=811)
+    sp, gla, o = fx["urqmd"], inputs.feqmod_tables(0.15), dict(dimension=3, df_mode=2)
+    assert len(sp["mass"]) == 305 and layout_total(SHIPPED_BINS, 305) == 305 * 1800 > 8192
+    kw = dict(n_events=400, seed=7, y_cut=0.5)
+    p, got, _ = parity(cells, sp, fx["df"], gla, SHIPPED_BINS, o, kw, 1001)
+    assert len(np.unique(p["species"])) > 100
+    h1, _ = api.sample_binned(cells, sp, fx["df"], gla, dict(SHIPPED_BINS, kernel_form=1), o, **kw)
+    assert same(h1, got)
+    with pytest.raises(api.Is3dError) as e:
+        api.sample_binned(cells, sp, fx["df"], gla, dict(SHIPPED_BINS, kernel_form=2), o, **kw)
+    assert e.value.code == api.IS3D_EINVAL and str(305 * 1800) in str(e.value)
+
+
+@pytest.mark.parametrize("mode", ["3d_feqmod4", "2d_feqmod3_fast", "3d_ce_baryon"])
+def test_other_modes_binned_on_device_equal_the_binned_list(fx, mode):
+    """df_mode 4, df_mode 3 with fast = 1 (2+1D) and include_baryon = 1 (six species, p / pbar and Lambda / Lambdabar apart)."""
+    if mode == "3d_ce_baryon":
+        cells = synth.synth_surface(300, 3, seed=850 + 3 + 2, baryon=True)
+        sp, df = inputs.species([211, 321, 2212, -2212, 3122, -3122]), inputs.df_tables_full()
+        gla = inputs.feqmod_tables(inputs.surface_average_T(cells))
+        o = dict(dimension=3, df_mode=2, include_baryon=1, include_baryondiff_deltaf=1)
+        kw = dict(n_events=800, seed=90210, y_cut=0.8)
+        bins = CASES["3d_ce"]["bins"]
+    else:
+        dim, df_mode, fast = (3, 4, 0) if mode == "3d_feqmod4" else (2, 3, 1)
+        cells = synth.synth_surface(400, dim, seed=830 + dim + df_mode)
+        cells = {k: v.copy() for k, v in cells.items()}
+        cells["bulkPi"][::9] = -5.0 * cells["P"][::9]          # df_mode 3: breakdown; df_mode 4: clamped
+        sp, df = fx["pikp"], fx["df"]
+        gla = inputs.feqmod_tables(inputs.surface_average_T(cells))
+        o = dict(dimension=dim, df_mode=df_mode)
+        kw = dict(n_events=800, seed=31337, y_cut=0.9, fq=gla, fast=fast, T_avg=gla["T_avg"], T_avg_switch=0.151)
+        bins = CASES["3d_ce" if dim == 3 else "2d_14m"]["bins"]
+    assert 300 <= len(cells["T"]) <= 600
+    p, got, st = parity(cells, sp, df, gla, bins, o, kw, 1001)
+    assert (st["n_cells_breakdown"] > 0) == (mode == "2d_feqmod3_fast")
+    assert all(0 < got[k].sum() < len(p) for k in ("dN_dy", "dN_deta", "dN_pT", "dN_tau", "dN_r"))
+
+
+def test_batches_without_a_particle(runs, fx):
+    """60 cells, 200 events, one event per batch: most batches hold no hadron (no fill, no bin launch for them) -- bit for bit the unbatched run."""
+    r = runs["3d_ce"]
+    cells = {k: v[:60] for k, v in r["cells"].items()}
+    kw = dict(r["kw"], n_events=200)
+    p, whole, _ = parity(cells, fx["pikp"], fx["df"], r["gla"], r["bins"], r["o"], kw, 20)
+    assert (whole["yield"] == 0).any() and (whole["yield"] > 0).any()
+    for form in (0, 1, 2):
+        h, st = api.sample_binned(cells, fx["pikp"], fx["df"], r["gla"], dict(r["bins"], kernel_form=form), r["o"], batch_events=1, **kw)
+        assert same(h, whole) and st["n_particles"] == len(p), form
+
+
+def test_more_shards_than_cells_and_a_single_event(runs, fx):
+    """Five shards of a 3-cell surface (two of them empty), and n_events = 1 over two shards: each equals the single-device result."""
+    r = runs["3d_ce"]
+    args = (fx["pikp"], fx["df"], r["gla"], r["bins"], r["o"])
+    cells = {k: v[:3] for k, v in r["cells"].items()}
+    kw = dict(r["kw"], n_events=3000)
+    p, whole, _ = parity(cells, *args[:3], r["bins"], r["o"], kw, 5)
+    multi, stm = api.sample_binned_multi(cells, *args, devices=[0] * 5, **kw)
+    assert same(multi, whole) and stm["n_particles"] == len(p)
+    kw1 = dict(r["kw"], n_events=1)
+    p1, one, _ = parity(r["cells"], fx["urqmd"], fx["df"], r["gla"], r["bins"], r["o"], kw1, 1)
+    assert one["yield"].shape == (1,) and one["yield"][0] == len(p1)
+    multi1, st1 = api.sample_binned_multi(r["cells"], fx["urqmd"], fx["df"], r["gla"], r["bins"], r["o"], devices=[0, 0], **kw1)
+    assert same(multi1, one) and st1["n_particles"] == len(p1)
+    ref, _ = api.sample_binned(r["cells"], *args, **kw1)       # pi/K/p: the block fits, so the private form runs on a handful of hadrons too
+    for form in (1, 2):
+        h, _ = api.sample_binned(r["cells"], *args[:3], dict(r["bins"], kernel_form=form), r["o"], **kw1)
+        assert same(h, ref), form

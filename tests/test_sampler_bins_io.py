@@ -1,109 +1,16 @@
 """CPU: the integer histograms of the test_sampler = 1 distributions (is3d_sampler_bin_list, the host side of the one bin rule in
 csrc/cf_sampler_bins.h) against a numpy restatement of sample_dN_dy ... sample_dN_dX (sampling_kernels.cpp:31-152), and the histogram
 writer (is3d_write_sampler_tests_binned) against the list writer, on a hand-made list with particles on and beside every kind of edge."""
-import math
 import os
 
 import numpy as np
+import pytest
 
 from is3d_amd import api
 
-BINS = dict(y_cut=1.5, eta_cut=4.0, pT_lower_cut=0.25, pT_upper_cut=2.75, tau_min=1.0, tau_max=9.0, r_min=0.5, r_max=8.0,
-            y_bins=12, eta_bins=16, pT_bins=10, tau_bins=8, r_bins=15)
-MASS = np.array([0.138, 0.494, 0.938])
-IDS = [211, 321, 2212]
-N_EVENTS = 5            # event 3 stays empty
+from sampler_bins_ref import BINS, IDS, K_NAN, K_Y, N_EVENTS, NAN_FIELDS, log_decided, make_list, numpy_hist
+
 DIRS = ("dN_dy", "dN_deta", "momentum_distribution", "vn", "spacetime_distribution")
-
-
-def _edge_particles():
-    """(y, pT, phi, eta, tau, r) by hand: on the edge, one step of the last bit to either side, and well inside."""
-    b = BINS
-    rows = []
-
-    def beside(v):
-        return [np.nextafter(v, -np.inf), v, np.nextafter(v, np.inf)]
-
-    for y in beside(b["y_cut"]) + beside(-b["y_cut"]) + beside(0.0) + [b["y_cut"] + 1e-12, -b["y_cut"] - 1e-12, 2 * b["y_cut"]]:
-        rows.append((y, 1.0, 0.3, 0.1, 4.0, 3.0))
-    pw = (b["pT_upper_cut"] - b["pT_lower_cut"]) / b["pT_bins"]
-    for pT in beside(b["pT_lower_cut"]) + beside(b["pT_upper_cut"]) + beside(b["pT_lower_cut"] + 3 * pw) + [0.0, 1e-300, 10.0]:
-        for phi in (0.0, -0.4, 2.5, -3.0, math.pi, -math.pi, -1e-17):     # phi < 0 is wrapped into [0, 2 pi)
-            rows.append((0.2, pT, phi, -0.7, 4.0, 3.0))
-    for tau in beside(b["tau_min"]) + beside(b["tau_max"]) + [0.5 * b["tau_min"], 2.0 * b["tau_max"], b["tau_min"] + 3.0]:
-        rows.append((-0.3, 0.8, 1.0, 0.0, tau, 3.0))
-    for r in beside(b["r_min"]) + beside(b["r_max"]) + [0.0, 0.5 * b["r_min"], 3.0 * b["r_max"]]:
-        rows.append((0.4, 0.8, -2.0, 0.0, 4.0, r))
-    for eta in beside(b["eta_cut"]) + beside(-b["eta_cut"]) + [0.0, 9.0, -9.0]:
-        rows.append((0.0, 0.9, 0.7, eta, 4.0, 3.0))
-    return np.array(rows)
-
-
-def make_list():
-    rng = np.random.default_rng(11)
-    edge = _edge_particles()
-    n_rand = 2000 - len(edge)
-    rand = np.stack([rng.normal(0, 1.2, n_rand), rng.gamma(2.0, 0.4, n_rand), rng.uniform(-math.pi, math.pi, n_rand), rng.normal(0, 2.5, n_rand),
-                     rng.uniform(0.2, 11.0, n_rand), np.abs(rng.normal(0, 4.0, n_rand))], axis=1)
-    rows = np.concatenate([edge, rand])
-    rows = rows[rng.permutation(len(rows))]
-    n = len(rows)
-    p = np.zeros(n, dtype=api.PARTICLE_DTYPE)
-    p["event"] = np.sort(rng.choice([0, 1, 2, 4], n))
-    p["species"] = rng.integers(0, 3, n)
-    y, pT, phi, eta, tau, r = rows.T
-    m = MASS[p["species"]]
-    p["px"], p["py"] = pT * np.cos(phi), pT * np.sin(phi)
-    p["px"][phi == 0.0] = pT[phi == 0.0]                  # pT lands on the cut exactly
-    mT = np.sqrt(m * m + pT * pT)
-    p["pz"], p["E"] = mT * np.sinh(y), mT * np.cosh(y)
-    p["eta"], p["tau"] = eta, tau
-    a = rng.uniform(-math.pi, math.pi, n)
-    p["x"], p["y"] = r * np.cos(a), r * np.sin(a)
-    on_axis = rng.random(n) < 0.3
-    p["x"][on_axis], p["y"][on_axis] = r[on_axis], 0.0    # r lands on its edges exactly
-    p["t"], p["z"] = tau * np.cosh(eta), tau * np.sinh(eta)
-    p["cell"] = np.arange(n)
-    return p
-
-
-def numpy_hist(p, b, n_events, n_species):
-    """The per-particle rule of the list writer (floor((v - lo) / width), the |yp| <= y_cut gate, phi in [0, 2 pi)), restated.  yp goes through
-    math.log -- the C library's log, as the host code's -- so that the bins of particles ON a rapidity edge are decided by the same function;
-    every other operation is correctly rounded in numpy as in C."""
-    S = n_species
-    yw, ew = 2.0 * b["y_cut"] / b["y_bins"], 2.0 * b["eta_cut"] / b["eta_bins"]
-    pw = (b["pT_upper_cut"] - b["pT_lower_cut"]) / b["pT_bins"]
-    tw, rw = (b["tau_max"] - b["tau_min"]) / b["tau_bins"], (b["r_max"] - b["r_min"]) / b["r_bins"]
-    yp = np.array([0.5 * math.log(q) for q in (p["E"] + p["pz"]) / (p["E"] - p["pz"])])
-    sp = p["species"].astype(np.int64)
-    out = dict(dN_dy=np.zeros((S, b["y_bins"]), np.int64), dN_deta=np.zeros((S, b["eta_bins"]), np.int64), dN_pT=np.zeros((S, b["pT_bins"]), np.int64),
-               dN_tau=np.zeros((S, b["tau_bins"]), np.int64), dN_r=np.zeros((S, b["r_bins"]), np.int64))
-    out["yield"] = np.bincount(p["event"], minlength=n_events).astype(np.int64)
-
-    def count(name, idx, nb, gate):
-        ok = gate & (idx >= 0) & (idx < nb)
-        np.add.at(out[name], (sp[ok], idx[ok].astype(np.int64)), 1)
-        return ok
-
-    everyone = np.ones(len(p), bool)
-    mid = np.abs(yp) <= b["y_cut"]
-    count("dN_dy", np.floor((yp + b["y_cut"]) / yw), b["y_bins"], everyone)
-    count("dN_deta", np.floor((p["eta"] + b["eta_cut"]) / ew), b["eta_bins"], everyone)
-    pT = np.sqrt(p["px"] * p["px"] + p["py"] * p["py"])
-    ipT = np.floor((pT - b["pT_lower_cut"]) / pw)
-    ok = count("dN_pT", ipT, b["pT_bins"], mid)
-    count("dN_tau", np.floor((p["tau"] - b["tau_min"]) / tw), b["tau_bins"], mid)
-    r = np.sqrt(p["x"] * p["x"] + p["y"] * p["y"])
-    count("dN_r", np.floor((r - b["r_min"]) / rw), b["r_bins"], mid)
-    phi = np.arctan2(p["py"], p["px"])
-    phi = np.where(phi < 0.0, phi + 2.0 * math.pi, phi)
-    out["vn_re"] = np.zeros((api.VN_HARMONICS, S, b["pT_bins"]), np.int64)
-    out["vn_im"] = np.zeros_like(out["vn_re"])
-    for k in range(api.VN_HARMONICS):
-        np.add.at(out["vn_re"][k], (sp[ok], ipT[ok].astype(np.int64)), np.rint(np.cos((k + 1.0) * phi[ok]) * api.VN_SCALE).astype(np.int64))
-        np.add.at(out["vn_im"][k], (sp[ok], ipT[ok].astype(np.int64)), np.rint(np.sin((k + 1.0) * phi[ok]) * api.VN_SCALE).astype(np.int64))
-    return out
 
 
 def _result_files(root):
@@ -154,3 +61,53 @@ def test_binned_writer_matches_the_list_writer(tmp_path):
         else:
             assert a[name] == b[name], name
     assert n_vn == 3
+
+
+def test_nan_rows_reach_no_bin_and_are_counted():
+    """Each of the five NaN rows (E, px, tau, x, eta) stays out of the histograms its NaN feeds, adds to the others, and to the yield."""
+    p, kinds = make_list(with_kinds=True)
+    for i, f in enumerate(NAN_FIELDS):
+        q = p[kinds == K_NAN + i]
+        assert len(q) == 1 and np.isnan(q[f][0])
+        got = api.sampler_bin_list(BINS, N_EVENTS, 3, q)
+        want = numpy_hist(q, BINS, N_EVENTS, 3)
+        sums = {k: int(got[k].sum()) for k in ("dN_dy", "dN_deta", "dN_pT", "dN_tau", "dN_r", "yield")}
+        empty = dict(E=("dN_dy", "dN_pT", "dN_tau", "dN_r"), px=("dN_pT",), tau=("dN_tau",), x=("dN_r",), eta=("dN_deta",))[f]
+        assert sums == {k: 0 if k in empty else 1 for k in sums}, (f, sums)
+        assert all(np.array_equal(got[k], want[k]) for k in sums), f
+        assert got["vn_re"].any() == ("dN_pT" not in empty)
+
+
+def test_log_decided_particles_are_few_and_hand_made():
+    """The split the device test makes (tests/test_gpu_sampler_bins_lists.py), checked where no device is needed: the particles whose rapidity
+    bin or gate lies within 1e-12 of an edge in long double are 19 of the 2000 -- at most 2 % -- and every one is a row whose rapidity was put
+    on or beside an edge by hand.  Away from them the long-double restatement and the C library's agree on every bin."""
+    p, kinds = make_list(with_kinds=True)
+    ref, u, d = numpy_hist(p, BINS, N_EVENTS, 3, longdouble=True)
+    hard = log_decided(u, d)
+    print("log-decided:", int(hard.sum()), "of", len(p))
+    assert 0 < hard.sum() <= 0.02 * len(p) and (kinds[hard] == K_Y).all()
+    assert hard.sum() == 19
+    easy = p[~hard]
+    a, b = numpy_hist(easy, BINS, N_EVENTS, 3), numpy_hist(easy, BINS, N_EVENTS, 3, longdouble=True)[0]
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    got = api.sampler_bin_list(BINS, N_EVENTS, 3, easy)
+    assert all(np.array_equal(got[k], a[k]) for k in ("dN_dy", "dN_deta", "dN_pT", "dN_tau", "dN_r", "yield"))
+
+
+def test_empty_ranges_and_bad_counts_are_refused(tmp_path):
+    """A zero-width or inverted range would divide by zero in the bin rule: IS3D_EINVAL from the host binning and from both writers."""
+    p = make_list()
+    hist = api.sampler_bin_list(BINS, N_EVENTS, 3, p)
+    for bad in (dict(y_cut=0.0), dict(y_cut=-1.0), dict(eta_cut=0.0), dict(pT_upper_cut=BINS["pT_lower_cut"]), dict(pT_upper_cut=0.1),
+                dict(tau_max=BINS["tau_min"]), dict(r_max=BINS["r_min"]), dict(r_max=0.0), dict(y_cut=float("nan")), dict(y_bins=0), dict(r_bins=-2)):
+        b = dict(BINS, **bad)
+        hb = hist if b["y_bins"] == BINS["y_bins"] and b["r_bins"] == BINS["r_bins"] else api._hist_arrays(b, N_EVENTS, 3)[1]
+        calls = (lambda: api.sampler_bin_list(b, N_EVENTS, 3, p),
+                 lambda: api.write_sampler_tests(str(tmp_path), b, N_EVENTS, IDS, p),
+                 lambda: api.write_sampler_tests_binned(str(tmp_path), b, N_EVENTS, IDS, hb))
+        for call in calls:
+            with pytest.raises(api.Is3dError) as e:
+                call()
+            assert e.value.code == api.IS3D_EINVAL, bad
+    assert not os.listdir(str(tmp_path))                     # refused before any file is opened
