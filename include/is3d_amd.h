@@ -702,6 +702,40 @@ int is3d_plan_execute_spacetime_feqmod(is3d_plan *plan, const is3d_cells *cells,
                                        const double *phi_w, const is3d_spacetime_bins *bins, const is3d_spacetime_out *out, void *hip_stream,
                                        is3d_spacetime_stats *stats, is3d_spacetime_feqmod_stats *fstats);
 
+/* Operation 0 over several devices (one process): the cells are cut into the contiguous blocks of is3d_shard_bounds, shard s runs on
+ * devices[s], all shards concurrently with one host thread and one stream each.  A shard uploads its cells, writes its records and runs the
+ * per-cell stage (df_mode 3 / 4: with the renormalisation and the linearised delta-f of its own breakdown cells) on a plan of its own; its
+ * D slice lands in one [class][n_cells] array on devices[0] at the shard's cell offset (a copy on the device, hipMemcpyPeer from another
+ * one).  devices[0] then runs the bin stage ONCE over the whole D and the whole surface's tau, x, y and skip flags -- keys, stable sort,
+ * left-to-right segment sums, the dN_dy walk -- exactly as the single-device entries do.  All pointers are HOST pointers.
+ *   fq:       NULL = df_mode 1 / 2 (is3d_spacetime_distributions), else df_mode 3 / 4 (is3d_spacetime_distributions_feqmod).
+ *   devices:  as is3d_smooth_spectra_multi: NULL = the ordinals 0 .. n_devices - 1, n_devices <= 0 = every visible device, an ordinal may
+ *             repeat; opts->device is ignored.  More shards than cells: the shards without cells contribute nothing (no error).
+ * Contract:
+ *   - one shard: the result is that of is3d_spacetime_distributions(_feqmod) on devices[0] bit for bit, dN_dydeta included;
+ *   - any shard count, any device list: dN_dy, dN_taudtaudy, dN_twopirdrdy, dN_twopitaurdtaudrdy, dN_dy_cell (the assembled D expanded to
+ *     species) and, in 3+1D, dN_dydeta are BITWISE the single-device result -- a cell's D depends on that cell alone, and every sum runs
+ *     over the assembled D in global cell order.  The df_mode 1 / 2 records carry a power-of-two p.dsigma scale taken over the execute: the
+ *     shards exchange their bounds before the records are written and all use the whole surface's, so the records themselves are the
+ *     single-device ones;
+ *   - 2+1D dN_dydeta: every shard reduces its per-chunk eta slabs in chunk order as a single device does, and a kernel on devices[0] adds the
+ *     shards' rows in shard order 0, 1, 2, ... (no floating-point atomics): bitwise reproducible for a given shard count whatever the devices;
+ *     it differs from the single-device value by the association of its additions only;
+ *   - the workspace_bytes passes inside a shard change nothing of the above.
+ * stats: the counters summed over the shards (n_tau_* / n_r_* come from the one bin stage), bad_cell the lowest GLOBAL cell index, ms_prep /
+ * ms_cells the slowest shard's, ms_bins the one bin stage's, ms_h2d the slowest shard's upload plus the bin stage's, ms_d2h the D placement
+ * (slowest shard) plus the read-back.  shard_stats: NULL or one entry per shard (n_devices of them; is3d_device_count() for n_devices <= 0),
+ * bad_cell shard-local.
+ * Errors: the argument checks of the two one-shot entries (NULL x or y, bins < 1, empty ranges, the grid bounds, an fq that contradicts
+ * df_mode), n_devices beyond the visible count with devices == NULL and a negative ordinal are refused with IS3D_EINVAL BEFORE any device
+ * is used or plan created (is3d_resource_counters is unchanged by them); a cell outside the coefficient table in any shard gives
+ * IS3D_EDOMAIN for the whole call. */
+int is3d_spacetime_distributions_multi(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species,
+                                       const is3d_grid *grid, const double *pT_w, const double *phi_w, const is3d_df_tables *df,
+                                       const is3d_feqmod_tables *fq, const is3d_options *opts, const int32_t *devices, int32_t n_devices,
+                                       const is3d_spacetime_bins *bins, is3d_spacetime_out *out, is3d_spacetime_stats *stats,
+                                       is3d_spacetime_stats *shard_stats);
+
 /* ---------------------------------------------------------------------------------------------
  * Spin polarization from thermal vorticity (mode 5) -- what EmissionFunctionArray::calculate_spin_polzn computes
  * (src/cpp/emissionfunction_polzn_kernels.cpp:27-265; writer write_polzn_vector_toFile, emissionfunction.cpp:775-821).  For every species s

@@ -111,7 +111,7 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_vah_plan_workspace_bytes", "is3d_vah_plan_execute", "is3d_vah_plan_set_timing", "is3d_vah_plan_timings",
            "is3d_vah_plan_tile_shape", "is3d_vah_plan_destroy", "is3d_surface_read_vah", "is3d_vah_plan_main_kernel_name", "is3d_math_probe", "is3d_resource_counters",
            "is3d_spacetime_distributions", "is3d_plan_execute_spacetime", "is3d_write_spacetime",
-           "is3d_spacetime_distributions_feqmod", "is3d_plan_execute_spacetime_feqmod",
+           "is3d_spacetime_distributions_feqmod", "is3d_plan_execute_spacetime_feqmod", "is3d_spacetime_distributions_multi",
            "is3d_spin_polarization", "is3d_polarization_plan_create", "is3d_polarization_plan_execute", "is3d_polarization_plan_destroy",
            "is3d_write_polarization", "is3d_surface_vorticity",
            "is3d_pdg_read_decays", "is3d_decay_q_factor", "is3d_resonance_decays", "is3d_decay_plan_create", "is3d_decay_plan_output_size",
@@ -299,6 +299,10 @@ def load():
     L.is3d_spacetime_distributions_feqmod.argtypes = [C.POINTER(Cells), _dp, _dp, C.POINTER(Species), C.POINTER(Grid), _dp, _dp,
                                                       C.POINTER(DfTables), C.POINTER(FeqmodTables), C.POINTER(Options), C.POINTER(SpacetimeBins),
                                                       C.POINTER(SpacetimeOut), C.POINTER(SpacetimeStats), C.POINTER(SpacetimeFeqmodStats)]
+    L.is3d_spacetime_distributions_multi.argtypes = [C.POINTER(Cells), _dp, _dp, C.POINTER(Species), C.POINTER(Grid), _dp, _dp,
+                                                     C.POINTER(DfTables), C.POINTER(FeqmodTables), C.POINTER(Options), C.POINTER(C.c_int32),
+                                                     C.c_int32, C.POINTER(SpacetimeBins), C.POINTER(SpacetimeOut), C.POINTER(SpacetimeStats),
+                                                     C.POINTER(SpacetimeStats)]
     L.is3d_plan_execute_spacetime_feqmod.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_void_p, C.c_void_p, _dp, _dp, C.POINTER(SpacetimeBins),
                                                      C.POINTER(SpacetimeOut), C.c_void_p, C.POINTER(SpacetimeStats), C.POINTER(SpacetimeFeqmodStats)]
     L.is3d_write_spacetime.argtypes = [C.c_char_p, C.POINTER(SpacetimeBins), C.c_int32, C.POINTER(C.c_int64), C.c_int32, _dp,
@@ -647,6 +651,57 @@ def spacetime_distributions(cells, species, grid, df, bins, opts=None, per_cell=
                                             C.byref(so), C.byref(st))
         _check(rc)
     res["stats"] = st.as_dict()
+    return res
+
+
+def spacetime_distributions_multi(cells, species, grid, df, bins, opts=None, devices=None, fq=None, per_cell=False, x=None, y=None):
+    """is3d_spacetime_distributions_multi: operation 0 with the per-cell stage on one contiguous cell shard per entry of devices (an ordinal may
+    repeat; an int n means the ordinals 0 .. n - 1; None or 0 every visible device) and ONE bin stage on devices[0].  Arguments and result as
+    spacetime_distributions (fq: df_mode 3, 4), plus "shard_stats", one dict per shard.  Everything but the 2+1D dN_dydeta is bitwise the
+    single-device result for any shard count; that one is reproducible for a given shard count.  An Is3dError raised here carries bad_cell
+    (global), stats and shard_stats."""
+    L = load()
+    sps, gs, ds, os_, _, keep = _pack_common(species, grid, df, opts)
+    n = len(cells["tau"])
+    cs = Cells()
+    cs.n_cells = n
+    held = []
+    for f in CELL_FIELDS:
+        a = cells.get(f)
+        if a is not None:
+            a = _f64(a)
+            assert a.shape == (n,), f
+            held.append(a)
+            setattr(cs, f, a.ctypes.data)
+    x = cells.get("x") if x is None else x
+    y = cells.get("y") if y is None else y
+    xa = None if x is None else _f64(x)
+    ya = None if y is None else _f64(y)
+    pw, fw = _f64(grid["pT_w"]), _f64(grid["phi_w"])
+    shapes = spacetime_shapes(len(keep["sp"]["mass"]), n, bins, os_.dimension, len(keep["g"]["eta"]))
+    res = {k: np.zeros(v) for k, v in shapes.items() if k != "dN_dy_cell" or per_cell}
+    so = SpacetimeOut(*[res[k].ctypes.data if k in res else None for k in SPACETIME_OUTPUTS])
+    b = _spacetime_bins(bins)
+    if devices is None or isinstance(devices, (int, np.integer)):
+        nd, dv = int(devices or 0), None
+    else:
+        nd = len(devices)
+        dv = (C.c_int32 * max(nd, 1))(*[int(d) for d in devices])
+    st = SpacetimeStats()
+    n_stats = nd if nd > 0 else max(L.is3d_device_count(), 1)
+    sst = (SpacetimeStats * max(n_stats, 1))()
+    fqs = _pack_feqmod(fq, keep) if fq is not None else None
+    xp, yp = (_p(xa) if xa is not None else None), (_p(ya) if ya is not None else None)
+    rc = L.is3d_spacetime_distributions_multi(C.byref(cs), xp, yp, C.byref(sps), C.byref(gs), _p(pw), _p(fw), C.byref(ds),
+                                              C.byref(fqs) if fqs is not None else None, C.byref(os_), dv, nd, C.byref(b), C.byref(so),
+                                              C.byref(st), sst)
+    stats, shard_stats = st.as_dict(), [sst[i].as_dict() for i in range(n_stats)]
+    if rc != 0:
+        err = Is3dError(rc, L.is3d_last_error().decode(), bad_cell=stats["bad_cell"])
+        err.stats, err.shard_stats = stats, shard_stats
+        raise err
+    res["stats"] = stats
+    res["shard_stats"] = shard_stats
     return res
 
 

@@ -14,6 +14,8 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <array>
+#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,6 +28,7 @@
 
 #include "../../include/is3d_amd.h"
 #include "cf_host.h"
+#include "cf_spacetime.h"
 #include "errors.h"
 
 #define fail is3d::set_error
@@ -1036,4 +1039,287 @@ extern "C" int is3d_sample_binned_multi(const is3d_cells *cells, const is3d_spec
             return fail(IS3D_EDOMAIN, "dN_pT bin %lld holds %lld hadrons: the fixed-point harmonic sums are exact up to %lld per bin", (long long)j,
                         (long long)hist->dN_pT[j], (long long)IS3D_SAMPLER_VN_MAX_COUNT);
     return IS3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// operation 0 over several devices: the per-cell stage (96 % of the step) on contiguous shards of the cells, one bin stage on devices[0]
+// ------------------------------------------------------------------------------------------------
+namespace {
+// every shard's |p.dsigma| bound in, the largest out: each shard arrives once and waits for the rest (a shard that fails before it reaches
+// its records still arrives, through leave(), so that nobody waits for it)
+struct BoundExchange {
+    std::mutex m;
+    std::condition_variable cv;
+    int expected = 0, arrived = 0;
+    unsigned long long bound = 0;   // bits of non-negative doubles order like unsigned integers (cf_pds_bound)
+    int exchange(unsigned long long mine, unsigned long long *all)
+    {
+        std::unique_lock<std::mutex> lock(m);
+        bound = std::max(bound, mine);
+        if (++arrived >= expected) cv.notify_all();
+        else cv.wait(lock, [this] { return arrived >= expected; });
+        *all = bound;
+        return IS3D_OK;
+    }
+    void leave()
+    {
+        std::lock_guard<std::mutex> lock(m);
+        if (++arrived >= expected) cv.notify_all();
+    }
+};
+
+struct StShard {
+    int device = 0;
+    int64_t lo = 0, hi = 0;
+    is3d_plan *plan = nullptr;
+    hipStream_t stream = nullptr;
+    is3d::DevBuf<double> d_cells;
+    is3d_spacetime_stats st{};
+    int rc = IS3D_OK;
+    std::string err;
+    bool exchanged = false;
+    ~StShard()
+    {
+        (void)hipSetDevice(device);
+        if (plan) is3d_plan_destroy(plan);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+// a shard's cells up, its records and per-cell stage, its D blocks into the assembled D; the stream is synchronised on return
+int st_shard_run(StShard &s, const is3d_cells *cells, const is3d_species *species, const is3d_grid *grid, const double *pT_w, const double *phi_w,
+                 const is3d_df_tables *df, const is3d_feqmod_tables *fq, const is3d_options *opts, is3d::StSplit &split)
+{
+    HIP_TRY(hipSetDevice(s.device));
+    const int64_t n = s.hi - s.lo;
+    if (!s.plan) {
+        is3d_options o = *opts;
+        o.device = s.device;
+        const int rc = fq ? is3d_plan_create_feqmod(&s.plan, species, grid, df, fq, &o, n) : is3d_plan_create(&s.plan, species, grid, df, &o, n);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+    HIP_TRY(s.d_cells.alloc((size_t)n * is3d::kCellArrays));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    struct EvGuard { hipEvent_t &a, &b; ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evg{e0, e1};
+    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    const bool diff = opts->include_baryon && opts->include_baryondiff_deltaf;
+    HIP_TRY(hipEventRecord(e0, s.stream));
+    is3d_cells dc;
+    HIP_TRY(is3d::stage_cells(*cells, [diff](int a) { return a < 18 || diff; }, s.lo, n, s.d_cells.p, s.stream, &dc));
+    HIP_TRY(hipEventRecord(e1, s.stream));
+    const int rc = is3d::spacetime_execute_split(s.plan, &dc, nullptr, nullptr, pT_w, phi_w, nullptr, nullptr, s.stream, &s.st, &split);
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) s.st.ms_h2d = ms;
+    else (void)hipGetLastError();
+    return rc;
+}
+}  // namespace
+
+namespace {
+int st_multi_impl(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species, const is3d_grid *grid,
+                  const double *pT_w, const double *phi_w, const is3d_df_tables *df, const is3d_feqmod_tables *fq, const is3d_options *opts,
+                  const int32_t *devices, int32_t n_devices, const is3d_spacetime_bins *bins, is3d_spacetime_out *out,
+                  is3d_spacetime_stats *stats, is3d_spacetime_stats *shard_stats)
+{
+    // ---- every refusal, before any device is used or a plan created ----
+    if (!opts) return fail(IS3D_EINVAL, "null argument");
+    if (!fq && (opts->df_mode == 3 || opts->df_mode == 4))
+        return fail(IS3D_EINVAL, "df_mode %d (calculate_dN_dX_feqmod) needs the feqmod tables: fq is NULL", opts->df_mode);
+    if (fq && opts->df_mode != 3 && opts->df_mode != 4)
+        return fail(IS3D_EINVAL, "fq is given but df_mode is %d: the feqmod tables go with df_mode 3 or 4, pass fq = NULL for df_mode 1 or 2", opts->df_mode);
+    if (int rc = is3d::spacetime_check_args(cells, x, y, species, grid, pT_w, phi_w, df, fq, opts, bins, out)) return rc;
+    if (n_devices > 1024) return fail(IS3D_EINVAL, "n_devices = %d (up to 1024 shards)", n_devices);
+    if (devices)
+        for (int i = 0; i < n_devices; i++)
+            if (devices[i] < 0) return fail(IS3D_EINVAL, "devices[%d] = %d: a device ordinal cannot be negative", i, devices[i]);
+    const int visible = is3d_device_count();
+    if (!devices && n_devices > visible)
+        return fail(IS3D_EINVAL, "n_devices = %d with devices == NULL asks for the ordinals 0..%d, but %d HIP device%s visible", n_devices,
+                    n_devices - 1, visible, visible == 1 ? " is" : "s are");
+    if (visible < 1) return fail(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
+    if (n_devices <= 0) { n_devices = visible; devices = nullptr; }
+    std::vector<int> dev(n_devices);
+    for (int i = 0; i < n_devices; i++) {
+        dev[i] = devices ? devices[i] : i;
+        if (dev[i] >= visible) return fail(IS3D_EINVAL, "devices[%d] = %d is not one of the %d visible HIP devices", i, dev[i], visible);
+    }
+    if (shard_stats) {
+        memset(shard_stats, 0, sizeof(is3d_spacetime_stats) * (size_t)n_devices);
+        for (int i = 0; i < n_devices; i++) shard_stats[i].bad_cell = -1;
+    }
+
+    if (n_devices == 1) {
+        // one shard IS the single-device call on devices[0]: no assembled D, no second upload of the surface
+        is3d_options o = *opts;
+        o.device = dev[0];
+        is3d_spacetime_stats st{};
+        const int rc = fq ? is3d_spacetime_distributions_feqmod(cells, x, y, species, grid, pT_w, phi_w, df, fq, &o, bins, out, &st, nullptr)
+                          : is3d_spacetime_distributions(cells, x, y, species, grid, pT_w, phi_w, df, &o, bins, out, &st);
+        st.code = rc;
+        if (stats) *stats = st;
+        if (shard_stats) shard_stats[0] = st;
+        return rc;
+    }
+
+    // ---- the shards; shard 0's plan lives on devices[0] and also serves the bin stage ----
+    // (declared ahead of the shards, so destroyed after them: the caller's thread gets its current device back)
+    struct DeviceRestore { int d = -1; ~DeviceRestore() { if (d >= 0) (void)hipSetDevice(d); } } restore;
+    if (hipGetDevice(&restore.d) != hipSuccess) { restore.d = -1; (void)hipGetLastError(); }
+    const int64_t n = cells->n_cells;
+    const bool dim3 = opts->dimension == 3;
+    std::vector<StShard> sh(n_devices);
+    int n_active = 0;
+    for (int i = 0; i < n_devices; i++) {
+        sh[i].device = dev[i];
+        sh[i].st.bad_cell = -1;
+        (void)is3d_shard_bounds(n, i, n_devices, &sh[i].lo, &sh[i].hi);
+        if (sh[i].hi > sh[i].lo) n_active++;
+    }
+    HIP_TRY(hipSetDevice(dev[0]));
+    {
+        is3d_options o = *opts;
+        o.device = dev[0];
+        const int64_t cap = std::max<int64_t>(sh[0].hi - sh[0].lo, 1);
+        const int rc = fq ? is3d_plan_create_feqmod(&sh[0].plan, species, grid, df, fq, &o, cap) : is3d_plan_create(&sh[0].plan, species, grid, df, &o, cap);
+        if (rc) return rc;
+    }
+    is3d_plan *P0 = sh[0].plan;
+    const int ncls = is3d::plan_classes(P0), S = species->n, K = dim3 ? 1 : grid->n_eta;
+    is3d::DevBuf<double> D_full;
+    {
+        const hipError_t e = D_full.alloc((size_t)ncls * (size_t)std::max<int64_t>(n, 1));
+        if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(IS3D_ENOMEM, "out of device memory allocating D for all cells on device %d", dev[0]); }
+        HIP_TRY(e);
+    }
+    BoundExchange bx;
+    bx.expected = n_active;
+    auto run = [&](int i) {
+        StShard &s = sh[i];
+        is3d::StSplit split;
+        split.role = is3d::ST_CELLS;
+        split.D_full = D_full.p; split.D_device = dev[0]; split.n_total = n; split.c_off = s.lo;
+        split.exchange = [&bx, &s](unsigned long long mine, unsigned long long *all) { s.exchanged = true; return bx.exchange(mine, all); };
+        s.rc = st_shard_run(s, cells, species, grid, pT_w, phi_w, df, fq, opts, split);
+        if (s.rc) s.err = is3d_last_error();   // the error text is thread-local
+        if (!s.exchanged) bx.leave();
+    };
+    if (n_active == 1) {   // on this thread; the one shard with cells, whichever rank the bounds rule gives them to
+        for (int i = 0; i < n_devices; i++)
+            if (sh[i].hi > sh[i].lo) run(i);
+    } else if (n_active > 1) {
+        std::vector<std::thread> th;
+        for (int i = 0; i < n_devices; i++)
+            if (sh[i].hi > sh[i].lo) th.emplace_back(run, i);
+        for (auto &t : th) t.join();
+    }
+    // ---- stats of the shards (also on failure, so that the caller sees which cell was bad) ----
+    is3d_spacetime_stats agg{};
+    agg.bad_cell = -1;
+    agg.n_classes = ncls;
+    int rc_first = IS3D_OK;
+    std::string err_first;
+    for (int i = 0; i < n_devices; i++) {
+        is3d_spacetime_stats &t = sh[i].st;
+        t.n_classes = ncls;   // a function of the species list alone: shards without cells report it too
+        t.code = sh[i].rc;
+        if (shard_stats) shard_stats[i] = t;
+        if (sh[i].rc && !rc_first) { rc_first = sh[i].rc; err_first = "shard " + std::to_string(i) + " (device " + std::to_string(sh[i].device) + "): " + sh[i].err; }
+        agg.n_cells_skipped += t.n_cells_skipped;
+        agg.n_passes = std::max(agg.n_passes, t.n_passes);
+        agg.ms_prep = std::max(agg.ms_prep, t.ms_prep);
+        agg.ms_cells = std::max(agg.ms_cells, t.ms_cells);
+        agg.ms_h2d = std::max(agg.ms_h2d, t.ms_h2d);
+        agg.ms_d2h = std::max(agg.ms_d2h, t.ms_d2h);   // the D placement
+        if (t.bad_cell >= 0 && (agg.bad_cell < 0 || sh[i].lo + t.bad_cell < agg.bad_cell)) agg.bad_cell = sh[i].lo + t.bad_cell;
+    }
+    agg.code = rc_first;
+    if (rc_first) {
+        if (stats) *stats = agg;
+        if (rc_first == IS3D_EDOMAIN && agg.bad_cell >= 0)
+            return fail(rc_first, "cell %lld of the surface: %s", (long long)agg.bad_cell, err_first.c_str());
+        return fail(rc_first, "%s", err_first.c_str());
+    }
+
+    // ---- the one bin stage, on devices[0], over the assembled D and the whole surface's tau, u, dsigma, x, y ----
+    HIP_TRY(hipSetDevice(dev[0]));
+    if (!sh[0].stream) HIP_TRY(hipStreamCreateWithFlags(&sh[0].stream, hipStreamNonBlocking));
+    hipStream_t st0 = sh[0].stream;
+    const int n_eta_eff = K;
+    const int64_t tb = bins->tau_bins, rbn = bins->r_bins;
+    const size_t sizes[6] = {(size_t)S, (size_t)(S * tb), (size_t)(S * rbn), (size_t)(S * tb * rbn), (size_t)S * n_eta_eff,
+                             out->dN_dy_cell ? (size_t)S * n : 0};
+    double *host_out[6] = {out->dN_dy, out->dN_taudtaudy, out->dN_twopirdrdy, out->dN_twopitaurdtaudrdy, out->dN_dydeta, out->dN_dy_cell};
+    size_t total = 0;
+    for (size_t z : sizes) total += z;
+    is3d::DevBuf<double> dsurf, dout, dparts;
+    HIP_TRY(dsurf.alloc((size_t)std::max<int64_t>(n, 1) * (is3d::kCellArrays + 2)));
+    HIP_TRY(dout.alloc(total));
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
+    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(ev[0], st0));
+    is3d_cells dc;
+    HIP_TRY(is3d::stage_cells(*cells, [](int a) { return a == 0 || (a >= 2 && a <= 8); }, 0, n, dsurf.p, st0, &dc));   // tau, dsigma, u
+    std::array<const double *, 2> xy = {x, y};
+    HIP_TRY(is3d::stage_arrays(xy, 0, n, dsurf.p + (size_t)is3d::kCellArrays * n, st0));
+    HIP_TRY(hipEventRecord(ev[1], st0));
+    const double *dx = n > 0 ? xy[0] : dsurf.p, *dy = n > 0 ? xy[1] : dsurf.p;
+    if (!dim3 && n_active > 0) {
+        // 2+1D dN/dy deta: the shards' class rows next to each other on devices[0], added in shard order into the plan's row
+        const int64_t per = (int64_t)ncls * K;
+        HIP_TRY(dparts.alloc((size_t)per * n_active));
+        int k = 0;
+        for (int i = 0; i < n_devices; i++) {
+            if (sh[i].hi <= sh[i].lo) continue;
+            double *dst = dparts.p + (size_t)per * k++;
+            if (sh[i].device == dev[0]) HIP_TRY(hipMemcpyAsync(dst, is3d::plan_st_eta(sh[i].plan), sizeof(double) * per, hipMemcpyDeviceToDevice, st0));
+            else HIP_TRY(hipMemcpyPeerAsync(dst, dev[0], is3d::plan_st_eta(sh[i].plan), sh[i].device, sizeof(double) * per, st0));
+        }
+        HIP_TRY(is3d::launch_spacetime_eta_shards(dparts.p, n_active, per, is3d::plan_st_eta(P0), st0));
+    }
+    is3d_spacetime_out dv{};
+    double *dev_out[6];
+    size_t off = 0;
+    for (int i = 0; i < 6; i++) { dev_out[i] = sizes[i] ? dout.p + off : nullptr; off += sizes[i]; }
+    dv.dN_dy = dev_out[0]; dv.dN_taudtaudy = dev_out[1]; dv.dN_twopirdrdy = dev_out[2]; dv.dN_twopitaurdtaudrdy = dev_out[3];
+    dv.dN_dydeta = dev_out[4]; dv.dN_dy_cell = dev_out[5];
+    is3d::StSplit split;
+    split.role = is3d::ST_BINS;
+    split.D_full = D_full.p; split.D_device = dev[0]; split.n_total = n; split.c_off = 0;
+    is3d_spacetime_stats bst{};
+    if (int rc = is3d::spacetime_execute_split(P0, &dc, dx, dy, pT_w, phi_w, bins, &dv, st0, &bst, &split)) {
+        agg.code = rc;
+        if (stats) *stats = agg;
+        return rc;
+    }
+    HIP_TRY(hipEventRecord(ev[2], st0));
+    for (int i = 0; i < 6; i++)
+        if (sizes[i]) HIP_TRY(hipMemcpyAsync(host_out[i], dev_out[i], sizes[i] * sizeof(double), hipMemcpyDeviceToHost, st0));
+    HIP_TRY(hipEventRecord(ev[3], st0));
+    HIP_TRY(hipEventSynchronize(ev[3]));
+    float h2d = 0, d2h = 0;
+    HIP_TRY(hipEventElapsedTime(&h2d, ev[0], ev[1]));
+    HIP_TRY(hipEventElapsedTime(&d2h, ev[2], ev[3]));
+    agg.ms_bins = bst.ms_bins;
+    agg.ms_h2d += h2d;
+    agg.ms_d2h += d2h;
+    agg.n_tau_outside = bst.n_tau_outside; agg.n_r_outside = bst.n_r_outside;
+    agg.n_tau_negative = bst.n_tau_negative; agg.n_r_negative = bst.n_r_negative;
+    agg.code = IS3D_OK;
+    if (stats) *stats = agg;
+    return IS3D_OK;
+}
+}  // namespace
+
+extern "C" int is3d_spacetime_distributions_multi(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species,
+                                                  const is3d_grid *grid, const double *pT_w, const double *phi_w, const is3d_df_tables *df,
+                                                  const is3d_feqmod_tables *fq, const is3d_options *opts, const int32_t *devices,
+                                                  int32_t n_devices, const is3d_spacetime_bins *bins, is3d_spacetime_out *out,
+                                                  is3d_spacetime_stats *stats, is3d_spacetime_stats *shard_stats)
+{
+    if (stats) { memset(stats, 0, sizeof *stats); stats->bad_cell = -1; }
+    const int rc = st_multi_impl(cells, x, y, species, grid, pT_w, phi_w, df, fq, opts, devices, n_devices, bins, out, stats, shard_stats);
+    if (stats) stats->code = rc;   // whatever the way out: a refusal, a HIP failure, a shard's error
+    return rc;
 }

@@ -1084,38 +1084,41 @@ static int st_check_grid(bool dim3, bool feqmod, int npT, int K)
 
 static int st_execute(is3d_plan *P, const is3d_cells *cells, const double *x, const double *y, const double *pT_w, const double *phi_w,
                       const is3d_spacetime_bins *bins, const is3d_spacetime_out *out, void *hip_stream, is3d_spacetime_stats *stats,
-                      is3d_spacetime_feqmod_stats *fstats)
+                      is3d_spacetime_feqmod_stats *fstats, is3d::StSplit *split = nullptr)
 {
     if (stats) { memset(stats, 0, sizeof *stats); stats->bad_cell = -1; }
     if (fstats) { memset(fstats, 0, sizeof *fstats); fstats->first_cell_out_of_range = -1; }
-    if (!P || !cells || !out || !pT_w || !phi_w) return fail(IS3D_EINVAL, "null argument");
-    int rc = st_check(bins, x, y, P->opts.df_mode, P->feqmod);
+    // the halves of an execute (cf_spacetime.h): a shard's per-cell stage into the assembled D, or the bin stage over it
+    const bool do_cells = !split || split->role == is3d::ST_CELLS, do_bins = !split || split->role == is3d::ST_BINS;
+    if (!P || !cells || (do_bins && !out) || (do_cells && (!pT_w || !phi_w))) return fail(IS3D_EINVAL, "null argument");
+    if (split && (!split->D_full || split->n_total < cells->n_cells + split->c_off || split->c_off < 0)) return fail(IS3D_EINVAL, "bad split");
+    int rc = do_bins ? st_check(bins, x, y, P->opts.df_mode, P->feqmod) : IS3D_OK;
     if (rc) return rc;
     if (P->feqmod ? !is3d::spacetime_feqmod_shape_supported(P->dim3, P->JT, P->KT) : !is3d::spacetime_shape_supported(P->dim3, P->JT, P->KT))
         return fail(IS3D_EINVAL, "operation 0 runs on the plan's unit records of the default tile shapes (this plan: kernel variant %d, %d x %d "
                     "records for %d %s nodes)", P->variant, P->JT, P->KT, P->K, P->dim3 ? "y" : "eta");
     rc = st_check_grid(P->dim3, P->feqmod, P->npT, P->K);
     if (rc) return rc;
-    if (!out->dN_dy || !out->dN_taudtaudy || !out->dN_twopirdrdy || !out->dN_twopitaurdtaudrdy || !out->dN_dydeta)
+    if (do_bins && (!out->dN_dy || !out->dN_taudtaudy || !out->dN_twopirdrdy || !out->dN_twopitaurdtaudrdy || !out->dN_dydeta))
         return fail(IS3D_EINVAL, "a required output array is NULL");
     const int64_t n = cells->n_cells;
-    if (n < 0 || n > P->max_cells) return fail(IS3D_EINVAL, "n_cells = %lld exceeds the plan's max_cells = %lld", (long long)n, (long long)P->max_cells);
+    if (n < 0 || (do_cells && n > P->max_cells)) return fail(IS3D_EINVAL, "n_cells = %lld exceeds the plan's max_cells = %lld", (long long)n, (long long)P->max_cells);
     if (n > 0x7fff0000LL) return fail(IS3D_EINVAL, "operation 0 takes up to 2^31 cells");
     const is3d_options &o = P->opts;
-    rc = is3d::check_cells(cells, P->dim3, o, P->baryondiff);
+    rc = do_cells ? is3d::check_cells(cells, P->dim3, o, P->baryondiff) : IS3D_OK;
     if (rc) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     HIP_TRY(hipSetDevice(P->device));
     rc = st_setup(P);
     if (rc) return rc;
     const int S = P->npart, K = P->K;
-    const int64_t tb = bins->tau_bins, rbn = bins->r_bins, trb = tb * rbn;
+    const int64_t tb = do_bins ? bins->tau_bins : 1, rbn = do_bins ? bins->r_bins : 1, trb = tb * rbn;
     const int n_eta_eff = P->dim3 ? 1 : K;
 
     // momentum weights of the reduction (pT_tab, phi_tab column 2): uploaded when they differ from the plan's copy (the first execute, or new
     // weights); an execute with the same weights and stats == NULL does not block the host
-    if (P->st_hwpT.size() != (size_t)P->npT || P->st_hwphi.size() != (size_t)P->J || !std::equal(P->st_hwpT.begin(), P->st_hwpT.end(), pT_w) ||
-        !std::equal(P->st_hwphi.begin(), P->st_hwphi.end(), phi_w)) {
+    if (do_cells && (P->st_hwpT.size() != (size_t)P->npT || P->st_hwphi.size() != (size_t)P->J ||
+                     !std::equal(P->st_hwpT.begin(), P->st_hwpT.end(), pT_w) || !std::equal(P->st_hwphi.begin(), P->st_hwphi.end(), phi_w))) {
         std::vector<double> wl((size_t)P->st_nlw * 64, 0.0), wp((size_t)P->jtiles * P->JT, 0.0);
         for (size_t l = 0; l < wl.size(); l++) {
             const int c = (int)(l / P->st_npTp), i = (int)(l % P->st_npTp);
@@ -1138,51 +1141,78 @@ static int st_execute(is3d_plan *P, const is3d_cells *cells, const double *x, co
         ev.push_back(e);
         return hipEventRecord(e, st);
     };
-    std::vector<int> stage;   // stage of the interval that ends at event i: 0 prep, 1 cells, 2 bins, 3 renormalisation, 4 linearised delta-f
+    std::vector<int> stage;   // stage of the interval that ends at event i: 0 prep, 1 cells, 2 bins, 3 renormalisation, 4 linearised delta-f,
+                              // 5 a shard's D blocks placed in the assembled D
     HIP_TRY(status_begin(P, st));
     HIP_TRY(hipMemsetAsync(P->d_st_counters.p, 0, 4 * sizeof(unsigned long long), st));
     HIP_TRY(mark());
 
     // ---- bin stage, part 1: keys and the stable counting sort of every histogram (once per execute) ----
-    HIP_TRY(st_grow(P->d_st_keys, (size_t)3 * n));
-    HIP_TRY(st_grow(P->d_st_list, (size_t)3 * n));
-    HIP_TRY(st_grow(P->d_st_start, (size_t)(tb + 1) + (rbn + 1) + (trb + 1)));
+    int32_t *keys[3] = {nullptr, nullptr, nullptr}, *lists[3] = {nullptr, nullptr, nullptr};
+    int64_t *starts[3] = {nullptr, nullptr, nullptr};
+    double *hout[3] = {nullptr, nullptr, nullptr};
     const int64_t Bs[3] = {tb, rbn, trb};
-    int ntile[3];
-    size_t cnt_need = 1, tot_need = 1;
-    for (int h = 0; h < 3; h++) {
-        ntile[h] = is3d::spacetime_sort_tiles(n, Bs[h]);
-        cnt_need = std::max(cnt_need, (size_t)ntile[h] * Bs[h]);
-        tot_need = std::max(tot_need, (size_t)Bs[h]);
+    if (do_bins) {
+        HIP_TRY(st_grow(P->d_st_keys, (size_t)3 * n));
+        HIP_TRY(st_grow(P->d_st_list, (size_t)3 * n));
+        HIP_TRY(st_grow(P->d_st_start, (size_t)(tb + 1) + (rbn + 1) + (trb + 1)));
+        int ntile[3];
+        size_t cnt_need = 1, tot_need = 1;
+        for (int h = 0; h < 3; h++) {
+            ntile[h] = is3d::spacetime_sort_tiles(n, Bs[h]);
+            cnt_need = std::max(cnt_need, (size_t)ntile[h] * Bs[h]);
+            tot_need = std::max(tot_need, (size_t)Bs[h]);
+        }
+        HIP_TRY(st_grow(P->d_st_cnt, cnt_need));
+        HIP_TRY(st_grow(P->d_st_tot, tot_need));
+        for (int h = 0; h < 3; h++) { keys[h] = P->d_st_keys.p + h * n; lists[h] = P->d_st_list.p + h * n; }
+        starts[0] = P->d_st_start.p; starts[1] = P->d_st_start.p + tb + 1; starts[2] = P->d_st_start.p + tb + 1 + rbn + 1;
+        hout[0] = out->dN_taudtaudy; hout[1] = out->dN_twopirdrdy; hout[2] = out->dN_twopitaurdtaudrdy;
+        const double dtau = (bins->tau_max - bins->tau_min) / (double)bins->tau_bins, dr = (bins->r_max - bins->r_min) / (double)bins->r_bins;
+        HIP_TRY(is3d::launch_spacetime_keys(cells->tau, cells->ux, cells->uy, cells->un, cells->dat, cells->dax, cells->day, cells->dan, x, y, n, bins->tau_min, dtau, bins->tau_bins, bins->r_min, dr, bins->r_bins, keys[0], keys[1],
+                                            keys[2], P->d_st_counters.p, st));
+        for (int h = 0; h < 3; h++)
+            HIP_TRY(is3d::launch_spacetime_sort(keys[h], n, Bs[h], ntile[h], P->d_st_cnt.p, P->d_st_tot.p, starts[h], lists[h], st));
+        HIP_TRY(mark()); stage.push_back(2);
     }
-    HIP_TRY(st_grow(P->d_st_cnt, cnt_need));
-    HIP_TRY(st_grow(P->d_st_tot, tot_need));
-    int32_t *keys[3] = {P->d_st_keys.p, P->d_st_keys.p + n, P->d_st_keys.p + 2 * n};
-    int32_t *lists[3] = {P->d_st_list.p, P->d_st_list.p + n, P->d_st_list.p + 2 * n};
-    int64_t *starts[3] = {P->d_st_start.p, P->d_st_start.p + tb + 1, P->d_st_start.p + tb + 1 + rbn + 1};
-    double *hout[3] = {out->dN_taudtaudy, out->dN_twopirdrdy, out->dN_twopitaurdtaudrdy};
-    const double dtau = (bins->tau_max - bins->tau_min) / (double)bins->tau_bins, dr = (bins->r_max - bins->r_min) / (double)bins->r_bins;
-    HIP_TRY(is3d::launch_spacetime_keys(cells->tau, cells->ux, cells->uy, cells->un, cells->dat, cells->dax, cells->day, cells->dan, x, y, n, bins->tau_min, dtau, bins->tau_bins, bins->r_min, dr, bins->r_bins, keys[0], keys[1],
-                                        keys[2], P->d_st_counters.p, st));
-    for (int h = 0; h < 3; h++)
-        HIP_TRY(is3d::launch_spacetime_sort(keys[h], n, Bs[h], ntile[h], P->d_st_cnt.p, P->d_st_tot.p, starts[h], lists[h], st));
-    HIP_TRY(mark()); stage.push_back(2);
+    // ---- bin stage, part 2: a block of D, cells [c0, c0 + nc) in ascending order, onto the running sums ----
+    auto sum_bins = [&](const double *D, int64_t nc, int64_t c0, int first) -> int {
+        HIP_TRY(is3d::launch_spacetime_segsum(D, nc, c0, P->d_st_cls.p, P->d_st_pg.p, S, nullptr, nullptr, 1, first, out->dN_dy, st));
+        for (int h = 0; h < 3; h++)
+            HIP_TRY(is3d::launch_spacetime_segsum(D, nc, c0, P->d_st_cls.p, P->d_st_pg.p, S, starts[h], lists[h], Bs[h], first, hout[h], st));
+        if (out->dN_dy_cell) HIP_TRY(is3d::launch_spacetime_per_cell(D, nc, c0, n, P->d_st_cls.p, P->d_st_pg.p, S, out->dN_dy_cell, st));
+        HIP_TRY(mark()); stage.push_back(2);
+        return IS3D_OK;
+    };
 
     if (n == 0) {
-        HIP_TRY(hipMemsetAsync(out->dN_dy, 0, sizeof(double) * S, st));
-        for (int h = 0; h < 3; h++) HIP_TRY(hipMemsetAsync(hout[h], 0, sizeof(double) * S * Bs[h], st));
-        HIP_TRY(hipMemsetAsync(out->dN_dydeta, 0, sizeof(double) * S * n_eta_eff, st));
+        if (do_bins) {
+            HIP_TRY(hipMemsetAsync(out->dN_dy, 0, sizeof(double) * S, st));
+            for (int h = 0; h < 3; h++) HIP_TRY(hipMemsetAsync(hout[h], 0, sizeof(double) * S * Bs[h], st));
+            HIP_TRY(hipMemsetAsync(out->dN_dydeta, 0, sizeof(double) * S * n_eta_eff, st));
+        }
     } else {
         // (the feqmod records carry p.dsigma unscaled)
-        if (!P->feqmod)
+        if (do_cells && !P->feqmod) {
             HIP_TRY(is3d::launch_pds_bound(is3d::cell_ptrs(*cells), n, P->dim3, P->kmin, P->kmax, P->gw2d, P->mTmax, P->pTmax, P->d_status.p + 6, st));
+            if (split && split->exchange) {
+                // a shard: the records take the scale of the WHOLE surface, so that they -- and D -- are the single-device ones bit for bit
+                unsigned long long mine = 0, all = 0;
+                HIP_TRY(hipMemcpyAsync(&mine, P->d_status.p + 6, sizeof mine, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                rc = split->exchange(mine, &all);
+                if (rc) return rc;
+                HIP_TRY(hipMemcpyAsync(P->d_status.p + 6, &all, sizeof all, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipStreamSynchronize(st));   // `all` goes out of scope
+            }
+        }
         const int64_t pc = P->st_pass;
         const int G = (P->st_nlw + 3) / 4;
         int nch = (int)std::min<int64_t>(pc, std::max<int64_t>(1, 16384 / G));
         if (!P->dim3) nch = (int)std::max<int64_t>(1, std::min<int64_t>(nch, ((int64_t)256 << 20) / (8 * (int64_t)P->ncls * K)));
         const int GL = P->feqmod ? st_linear_slots(pc) : 0;
-        if (!P->dim3) HIP_TRY(st_grow(P->d_st_slab, (size_t)(nch + GL) * P->ncls * K));
-        const int npasses = (int)((n + pc - 1) / pc);
+        if (!P->dim3 && do_cells) HIP_TRY(st_grow(P->d_st_slab, (size_t)(nch + GL) * P->ncls * K));
+        const int npasses = do_cells ? (int)((n + pc - 1) / pc) : 0;
         for (int pass = 0; pass < npasses; pass++) {
             const int64_t c0 = (int64_t)pass * pc;
             const int32_t nc = (int32_t)std::min<int64_t>(pc, n - c0);
@@ -1256,19 +1286,32 @@ static int st_execute(is3d_plan *P, const is3d_cells *cells, const double *x, co
                 HIP_TRY(mark()); stage.push_back(1);
             }
 
-            // ---- bin stage, part 2: this pass's cells, in ascending order, onto the running sums ----
-            HIP_TRY(is3d::launch_spacetime_segsum(P->d_st_D.p, nc, c0, P->d_st_cls.p, P->d_st_pg.p, S, nullptr, nullptr, 1, pass == 0, out->dN_dy, st));
-            for (int h = 0; h < 3; h++)
-                HIP_TRY(is3d::launch_spacetime_segsum(P->d_st_D.p, nc, c0, P->d_st_cls.p, P->d_st_pg.p, S, starts[h], lists[h], Bs[h], pass == 0, hout[h],
-                                                      st));
-            if (out->dN_dy_cell)
-                HIP_TRY(is3d::launch_spacetime_per_cell(P->d_st_D.p, nc, c0, n, P->d_st_cls.p, P->d_st_pg.p, S, out->dN_dy_cell, st));
+            if (split) {
+                // the pass's block [class][nc] into the assembled [class][n_total] at the shard's global cell offset
+                double *dst = split->D_full + split->c_off + c0;
+                if (split->D_device == P->device)
+                    HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double) * (size_t)split->n_total, P->d_st_D.p, sizeof(double) * (size_t)nc,
+                                             sizeof(double) * (size_t)nc, (size_t)P->ncls, hipMemcpyDeviceToDevice, st));
+                else
+                    for (int c = 0; c < P->ncls; c++)
+                        HIP_TRY(hipMemcpyPeerAsync(dst + (int64_t)c * split->n_total, split->D_device, P->d_st_D.p + (int64_t)c * nc, P->device,
+                                                   sizeof(double) * (size_t)nc, st));
+                HIP_TRY(mark()); stage.push_back(5);
+            } else {
+                rc = sum_bins(P->d_st_D.p, nc, c0, pass == 0);
+                if (rc) return rc;
+            }
+        }
+        if (do_bins) {
+            if (split) {   // the whole assembled D at once: the same left-to-right sums as pass after pass
+                rc = sum_bins(split->D_full, n, 0, 1);
+                if (rc) return rc;
+            }
+            // dN/dy deta: 2+1D one value per eta node (:1365); 3+1D the single point of the species' total (quirk 2)
+            if (P->dim3) HIP_TRY(hipMemcpyAsync(out->dN_dydeta, out->dN_dy, sizeof(double) * S, hipMemcpyDeviceToDevice, st));
+            else HIP_TRY(is3d::launch_spacetime_eta_final(P->d_st_eta.p, P->d_st_cls.p, P->d_st_pg.p, P->d_kweight.p, S, K, out->dN_dydeta, st));
             HIP_TRY(mark()); stage.push_back(2);
         }
-        // dN/dy deta: 2+1D one value per eta node (:1365); 3+1D the single point of the species' total (quirk 2)
-        if (P->dim3) HIP_TRY(hipMemcpyAsync(out->dN_dydeta, out->dN_dy, sizeof(double) * S, hipMemcpyDeviceToDevice, st));
-        else HIP_TRY(is3d::launch_spacetime_eta_final(P->d_st_eta.p, P->d_st_cls.p, P->d_st_pg.p, P->d_kweight.p, S, K, out->dN_dydeta, st));
-        HIP_TRY(mark()); stage.push_back(2);
         if (!stats) HIP_TRY(is3d::launch_fold_status(P->d_status.p, P->d_sticky.p, st));
     }
     if (stats) {
@@ -1279,6 +1322,7 @@ static int st_execute(is3d_plan *P, const is3d_cells *cells, const double *x, co
         for (size_t i = 1; i < ev.size(); i++) {
             float ms = 0;
             HIP_TRY(hipEventElapsedTime(&ms, ev[i - 1], ev[i]));
+            if (stage[i - 1] == 5) { stats->ms_d2h += ms; continue; }
             if (stage[i - 1] >= 3) {
                 if (fstats) (stage[i - 1] == 3 ? fstats->ms_renorm : fstats->ms_linear) += ms;
                 continue;
@@ -1291,7 +1335,7 @@ static int st_execute(is3d_plan *P, const is3d_cells *cells, const double *x, co
             fstats->first_cell_out_of_range = h[7] == ~0ULL ? -1 : (int64_t)h[7];
         }
         stats->n_classes = P->ncls;
-        stats->n_passes = n == 0 ? 0 : (int32_t)((n + P->st_pass - 1) / P->st_pass);
+        stats->n_passes = (n == 0 || !do_cells) ? 0 : (int32_t)((n + P->st_pass - 1) / P->st_pass);
         stats->n_cells_skipped = n == 0 ? 0 : (int64_t)h[1];
         stats->n_tau_outside = (int64_t)cn[0];
         stats->n_r_outside = (int64_t)cn[1];
@@ -1323,6 +1367,18 @@ extern "C" int is3d_plan_execute_spacetime_feqmod(is3d_plan *P, const is3d_cells
     return st_execute(P, cells, x, y, pT_w, phi_w, bins, out, hip_stream, stats ? stats : (fstats ? &local : nullptr), fstats);
 }
 
+// the argument checks of the one-shot entries (and of the entry that shards the cells over devices, cf_multi.hip): no device is touched
+static int st_check_args(const is3d_species *species, const is3d_grid *grid, const is3d_df_tables *df, const is3d_feqmod_tables *fq,
+                         const is3d_options *opts, const is3d_spacetime_bins *bins, const double *x, const double *y)
+{
+    int rc = st_check(bins, x, y, opts->df_mode, fq != nullptr);
+    if (!rc && fq && opts->include_baryon && opts->df_mode == 4)
+        rc = fail(IS3D_EINVAL, "df_mode 4 does not work with include_baryon = 1 (the reference exits there too)");
+    if (!rc && fq) rc = validate(species, grid, df, fq, opts);   // every check before the plan touches the device
+    if (!rc && grid && (opts->dimension == 2 || opts->dimension == 3)) rc = st_check_grid(opts->dimension == 3, fq != nullptr, grid->n_pT, grid->n_eta);
+    return rc;
+}
+
 static int st_oneshot(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species, const is3d_grid *grid,
                       const double *pT_w, const double *phi_w, const is3d_df_tables *df, const is3d_feqmod_tables *fq, const is3d_options *opts,
                       const is3d_spacetime_bins *bins, is3d_spacetime_out *out, is3d_spacetime_stats *stats, is3d_spacetime_feqmod_stats *fstats)
@@ -1330,11 +1386,7 @@ static int st_oneshot(const is3d_cells *cells, const double *x, const double *y,
     if (stats) { memset(stats, 0, sizeof *stats); stats->bad_cell = -1; }
     if (fstats) { memset(fstats, 0, sizeof *fstats); fstats->first_cell_out_of_range = -1; }
     if (!cells || !out || !opts || !pT_w || !phi_w) return fail(IS3D_EINVAL, "null argument");
-    int rc = st_check(bins, x, y, opts->df_mode, fq != nullptr);
-    if (!rc && fq && opts->include_baryon && opts->df_mode == 4)
-        rc = fail(IS3D_EINVAL, "df_mode 4 does not work with include_baryon = 1 (the reference exits there too)");
-    if (!rc && fq) rc = validate(species, grid, df, fq, opts);   // every check before the plan touches the device
-    if (!rc && grid && (opts->dimension == 2 || opts->dimension == 3)) rc = st_check_grid(opts->dimension == 3, fq != nullptr, grid->n_pT, grid->n_eta);
+    int rc = st_check_args(species, grid, df, fq, opts, bins, x, y);
     if (rc) { if (stats) stats->code = rc; return rc; }
     is3d_plan *P = nullptr;
     rc = plan_create_impl(&P, species, grid, df, fq, opts, std::max<int64_t>(cells->n_cells, 1));
@@ -1388,6 +1440,32 @@ static int st_oneshot(const is3d_cells *cells, const double *x, const double *y,
     if (stats) *stats = stt;
     return IS3D_OK;
 }
+
+namespace is3d {
+int spacetime_check_args(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species, const is3d_grid *grid,
+                         const double *pT_w, const double *phi_w, const is3d_df_tables *df, const is3d_feqmod_tables *fq, const is3d_options *opts,
+                         const is3d_spacetime_bins *bins, const is3d_spacetime_out *out)
+{
+    if (!cells || !out || !opts || !pT_w || !phi_w) return fail(IS3D_EINVAL, "null argument");
+    int rc = st_check_args(species, grid, df, fq, opts, bins, x, y);
+    if (!rc && !fq) rc = validate(species, grid, df, nullptr, opts);   // what plan creation would refuse, before any device sees a plan
+    if (rc) return rc;
+    if (!out->dN_dy || !out->dN_taudtaudy || !out->dN_twopirdrdy || !out->dN_twopitaurdtaudrdy || !out->dN_dydeta)
+        return fail(IS3D_EINVAL, "a required output array is NULL");
+    if (cells->n_cells < 0) return fail(IS3D_EINVAL, "n_cells < 0");
+    if (cells->n_cells > 0x7fff0000LL) return fail(IS3D_EINVAL, "operation 0 takes up to 2^31 cells");
+    return check_cells(cells, opts->dimension == 3, *opts, opts->include_baryon && opts->include_baryondiff_deltaf);
+}
+int spacetime_execute_split(is3d_plan *plan, const is3d_cells *cells, const double *x, const double *y, const double *pT_w, const double *phi_w,
+                            const is3d_spacetime_bins *bins, const is3d_spacetime_out *out, void *hip_stream, is3d_spacetime_stats *stats,
+                            StSplit *split)
+{
+    if (!split || (split->role != ST_CELLS && split->role != ST_BINS)) return fail(IS3D_EINVAL, "bad split");
+    return st_execute(plan, cells, x, y, pT_w, phi_w, bins, out, hip_stream, stats, nullptr, split);
+}
+int plan_classes(const is3d_plan *P) { return P ? P->ncls : 0; }
+double *plan_st_eta(const is3d_plan *P) { return P ? P->d_st_eta.p : nullptr; }
+}  // namespace is3d
 
 extern "C" int is3d_spacetime_distributions(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species,
                                             const is3d_grid *grid, const double *pT_w, const double *phi_w, const is3d_df_tables *df,

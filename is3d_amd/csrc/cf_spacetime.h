@@ -3,6 +3,8 @@
 #include "cf_device.h"
 #include <hip/hip_runtime_api.h>
 #include <cstdint>
+#include <functional>
+#include "../../include/is3d_amd.h"
 namespace is3d {
 
 // operation 0 with the modified equilibrium (cf_spacetime_feqmod.hip): the per-cell stage on cf_prep_feqmod's OP0 records of one pass of nc
@@ -52,6 +54,8 @@ bool spacetime_shape_supported(int dim3, int JT, int R);
 hipError_t launch_spacetime_cells(const StCellArgs &a, int ce, int dim3, int baryon, int JT, int R, hipStream_t st);
 // 2+1D: eta_cls[cls][k] (+)= sum over the nch chunks of eta_slab, in chunk order
 hipError_t launch_spacetime_eta_reduce(const double *eta_slab, int nch, int64_t n_per_chunk, int first_pass, double *eta_cls, hipStream_t st);
+// 2+1D, several shards: eta_cls[i] = parts[0][i] + parts[1][i] + ..., left to right in shard order
+hipError_t launch_spacetime_eta_shards(const double *parts, int nparts, int64_t n_per_part, double *eta_cls, hipStream_t st);
 // dN_dydeta[s][k] = (pg[s] * eta_cls[cls[s]][k]) / w[k]
 hipError_t launch_spacetime_eta_final(const double *eta_cls, const int32_t *cls, const double *pg, const double *w, int S, int K, double *out,
                                       hipStream_t st);
@@ -74,4 +78,29 @@ hipError_t launch_spacetime_segsum(const double *D, int64_t nc, int64_t c0, cons
 // per_cell[s * n_total + c0 + i] = pg[s] * D[cls[s] * nc + i]
 hipError_t launch_spacetime_per_cell(const double *D, int64_t nc, int64_t c0, int64_t n_total, const int32_t *cls, const double *pg, int S,
                                      double *per_cell, hipStream_t st);
+
+// ---- the two halves of an execute, for the cell-axis split over devices (cf_multi.hip; defined in cf_plan.cpp) ----
+// ST_CELLS: records and the per-cell stage of a shard's cells; every pass's D block [class][nc] lands in D_full[class][n_total] at cell
+//           c_off + c0 (a 2-D copy on D_device, row-wise hipMemcpyPeerAsync from another device); in 2+1D the shard's class rows of
+//           dN/dy deta stay in the plan (plan_st_eta).  No keys, no sort, no sums; bins, x, y and out are not read.
+// ST_BINS:  keys, sort, segment sums, dN_dy walk and dN_dy_cell over the assembled D_full of all n_total = cells->n_cells cells, which only
+//           need tau, u and dsigma; 2+1D: dN_dydeta from the plan's class rows as the caller left them (plan_st_eta).
+enum { ST_CELLS = 1, ST_BINS = 2 };
+struct StSplit {
+    int role = 0;
+    double *D_full = nullptr;
+    int D_device = 0;
+    int64_t n_total = 0, c_off = 0;
+    // df_mode 1 / 2: the shard's |p.dsigma| bound (bits) goes in, the bound of the whole surface comes out; called once, before the records
+    std::function<int(unsigned long long, unsigned long long *)> exchange;
+};
+int spacetime_execute_split(is3d_plan *plan, const is3d_cells *cells, const double *x, const double *y, const double *pT_w, const double *phi_w,
+                            const is3d_spacetime_bins *bins, const is3d_spacetime_out *out, void *hip_stream, is3d_spacetime_stats *stats,
+                            StSplit *split);
+// the argument checks of the one-shot entries of operation 0, none of which touches a device (fq == NULL: df_mode 1 / 2)
+int spacetime_check_args(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species, const is3d_grid *grid,
+                         const double *pT_w, const double *phi_w, const is3d_df_tables *df, const is3d_feqmod_tables *fq, const is3d_options *opts,
+                         const is3d_spacetime_bins *bins, const is3d_spacetime_out *out);
+int plan_classes(const is3d_plan *plan);      // species classes (rows of D)
+double *plan_st_eta(const is3d_plan *plan);   // 2+1D: [classes][n_eta] class rows of dN/dy deta on the plan's device (after a spacetime execute)
 }  // namespace is3d

@@ -201,6 +201,25 @@ hipError_t launch_spacetime_eta_reduce(const double *eta_slab, int nch, int64_t 
     return hipGetLastError();
 }
 
+// the multi-device entry: eta_cls[i] = parts[0][i] + parts[1][i] + ... left to right over the shards' class rows (one lane per element, a
+// fixed order for a given shard count; one part is copied bit for bit)
+__global__ void __launch_bounds__(256)
+cf_st_eta_shards(const double *__restrict__ parts, int nparts, int64_t n_per_part, double *__restrict__ eta_cls)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_per_part) return;
+    double s = parts[i];
+    for (int p = 1; p < nparts; p++) s += parts[p * n_per_part + i];
+    eta_cls[i] = s;
+}
+
+hipError_t launch_spacetime_eta_shards(const double *parts, int nparts, int64_t n_per_part, double *eta_cls, hipStream_t st)
+{
+    if (n_per_part <= 0 || nparts <= 0) return hipSuccess;
+    hipLaunchKernelGGL(cf_st_eta_shards, dim3((unsigned)((n_per_part + 255) / 256)), dim3(256), 0, st, parts, nparts, n_per_part, eta_cls);
+    return hipGetLastError();
+}
+
 __global__ void __launch_bounds__(256)
 cf_st_eta_final(const double *__restrict__ eta_cls, const int32_t *__restrict__ cls, const double *__restrict__ pg, const double *__restrict__ w,
                 int S, int K, double *__restrict__ out)

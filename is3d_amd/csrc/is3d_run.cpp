@@ -17,7 +17,8 @@
 // (src/cuda/deltafReader.cu:74-81) -- reads input/surface.dat with read_surf_VAH_PLMatch and deltaf_coefficients/vah/c{0..4}_vah1.dat,
 // runs what the commented-out call site would (emissionfunction.cpp:1650-1654) and writes the same three result files.
 // operation = 0 (smooth spacetime distributions, calculate_dN_dX; emissionfunction.cpp:1510-1516): mode in {0, 1, 4, 5, 6, 7}, df_mode in
-// {1, 2}, include_baryon in {0, 1}, dimension 2 or 3, on the first device of the run's list; reads tau_min ... r_bins (:216-222), writes
+// {1, 2}, include_baryon in {0, 1}, dimension 2 or 3, the per-cell stage sharded over the run's device list and one bin stage on its first
+// device (is3d_spacetime_distributions_multi); reads tau_min ... r_bins (:216-222), writes
 // results/spacetime_distribution/{dN_taudtaudy, dN_twopirdrdy, dN_twopitaurdtaudrdy}_<id>.dat and dN_dydeta_<id>_<n>pt.dat (the directory must
 // exist) and prints one "dN_dy = %lf" line per species; no momentum-spectra file (those are written for operation = 1 only, :1678).  df_mode 3 / 4
 // (calculate_dN_dX_feqmod) and mode 2 are refused before anything is written.
@@ -567,10 +568,18 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         is3d_spacetime_out out{o_dy.data(), o_t.data(), o_r.data(), o_tr.data(), o_eta.data(), nullptr};
         for (int ip = 0; ip < S; ip++) printf("Starting spacetime distribution %lld\n", (long long)mcid[ip]);   // :1100
         is3d_spacetime_stats sst{};
-        const int rc0 = is3d_spacetime_distributions(&cells, xp, yp, &sp, &grid, pTw.data(), phiw.data(), &df, &opts, &bins, &out, &sst);
+        // the per-cell stage on cell-axis shards over the run's devices, one bin stage on the first (is3d_spacetime_distributions_multi)
+        const int rc0 = is3d_spacetime_distributions_multi(&cells, xp, yp, &sp, &grid, pTw.data(), phiw.data(), &df, nullptr, &opts,
+                                                           rd.list.empty() ? nullptr : rd.list.data(), (int32_t)rd.list.size(), &bins, &out, &sst,
+                                                           nullptr);
+        {
+            const int nd = rd.list.empty() ? is3d_device_count() : (int)rd.list.size();
+            printf("devices: %d (cell-axis shards of ~%lld cells%s)\n", nd, (long long)((n_cells + nd - 1) / std::max(nd, 1)),
+                   nd > 1 ? ", one bin stage over the assembled per-cell values" : "");
+        }
         if (rc0) {
             const std::string msg = is3d_last_error();
-            DIE("is3d_spacetime_distributions failed (%d): %s", rc0, msg.c_str());
+            DIE("is3d_spacetime_distributions_multi failed (%d): %s", rc0, msg.c_str());
         }
         // the reference prints an error line per cell with a negative bin index (:1391-1392); one line with the counts here
         if (sst.n_tau_negative || sst.n_r_negative)
