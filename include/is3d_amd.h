@@ -783,6 +783,33 @@ int is3d_polarization_plan_create(is3d_polarization_plan **plan, const is3d_spec
 int is3d_polarization_plan_execute(is3d_polarization_plan *plan, const is3d_cells *cells, const is3d_vorticity *vorticity, double T,
                                    const is3d_polarization_out *out, void *hip_stream, is3d_polarization_stats *stats);
 void is3d_polarization_plan_destroy(is3d_polarization_plan *plan);
+/* The spin polarization over several devices (one process): the cells are cut into the contiguous blocks of is3d_shard_bounds, shard s runs
+ * on devices[s], all shards concurrently with one host thread, one is3d_polarization_plan and one stream each.  A shard uploads its own cell
+ * slice and the same slice of the six vorticity arrays (the vorticity stays indexed by the GLOBAL cell index), runs the per-chunk kernel with
+ * the chunk count of ITS cell count and adds its chunks in chunk order into one class-lane array V_s (not expanded to species, not scaled:
+ * the v of the single-device reduction before its scale).  The V_s of the shards that have cells are placed next to each other on devices[0]
+ * (a copy on the device, hipMemcpyPeer from another one) and one kernel there forms out = scale x ((V_0 + V_1) + V_2 ...) per (species, pT,
+ * bin), in shard order.  No floating-point atomics, no collective.  All pointers are HOST pointers.
+ *   devices:  as is3d_spacetime_distributions_multi: NULL = the ordinals 0 .. n_devices - 1, n_devices <= 0 = every visible device, an ordinal
+ *             may repeat; opts->device is ignored.  More shards than cells: the shards without cells contribute nothing; no cells at all:
+ *             the five outputs are zeros.
+ * Contract:
+ *   - one shard: the result is that of is3d_spin_polarization on devices[0] bit for bit;
+ *   - N shards: the result is bitwise scale x ((V_0 + V_1) + V_2 ...), so bitwise reproducible for a given shard count whatever the device
+ *     list; two calls give the same bits;
+ *   - against the single device it differs by the association of the additions only.  The single-device chunk partition is a function of
+ *     the whole surface's size, a shard's of the shard's size, so bitwise equality with the single device is NOT promised.
+ * stats: n_classes; n_chunks summed over the shards; ms_cells the slowest shard's; ms_reduce the slowest shard's class sums plus the
+ * combine on devices[0]; ms_h2d the slowest shard's upload; ms_d2h the placement of the class sums on devices[0] plus the read-back.
+ * shard_stats: NULL or one entry per shard (n_devices of them; is3d_device_count() for n_devices <= 0); ms_reduce its class sums, ms_d2h the
+ * placement of its class sums on devices[0].
+ * Errors: every argument check of is3d_spin_polarization, a negative ordinal and n_devices beyond the visible count with devices == NULL are
+ * refused with IS3D_EINVAL BEFORE any device is used or plan created (is3d_resource_counters is unchanged by them); with no device present
+ * IS3D_ENODEVICE.  A shard's failure is returned, with its message, after all threads have joined; the lowest failing shard wins. */
+int is3d_spin_polarization_multi(const is3d_cells *cells, const is3d_vorticity *vorticity, const is3d_species *species,
+                                 const is3d_grid *grid, double T, const is3d_options *opts,
+                                 const int32_t *devices, int32_t n_devices,
+                                 is3d_polarization_out *out, is3d_polarization_stats *stats, is3d_polarization_stats *shard_stats);
 /* write_polzn_vector_toFile (emissionfunction.cpp:775-821): APPENDS to <results_dir>/St.dat, Sx.dat, Sy.dat, Sn.dat one line per point,
  * "y\tphip\tpT\tS/Snorm" (scientific, setprecision(8), setw(5)), species outer, then y, phi, pT, a blank line after each phi block.  The
  * ratio is formed here, in C++, so 0/0 and +-inf print as the reference's would.  2+1D: y = 0 (y may be NULL).  IS3D_EIO if a file cannot
@@ -882,7 +909,9 @@ int is3d_run_particlization(const is3d_cells *surface, const double *x, const do
 /* The same on an explicit device list (operation 1: the cells are sharded over the devices as is3d_smooth_spectra_multi does;
  * operation 2 samples the shards on their devices and merges the lists, is3d_sample_particles_multi).  devices == NULL && n_devices > 0: ordinals 0 .. n_devices-1.  n_devices <= 0 is what
  * is3d_run_particlization and the command line tool do: the environment decides -- IS3D_DEVICES = "0,2,3" | "all" (default:
- * every visible device), IS3D_REDUCE = "ordered" (default) | "rccl". */
+ * every visible device), IS3D_REDUCE = "ordered" (default) | "rccl".  mode = 5: a list that was spelled out (devices != NULL here, or
+ * IS3D_DEVICES) also shards the spin polarization (is3d_spin_polarization_multi); a bare count (devices == NULL) or no list leaves it on the
+ * first device, so that the S files do not depend on how many devices a machine shows. */
 int is3d_run_particlization_on(const is3d_cells *surface, const double *x, const double *y, int32_t kernel_variant,
                                const int32_t *devices, int32_t n_devices, int32_t reduce, is3d_run_result *result);
 void is3d_run_result_free(is3d_run_result *result);

@@ -113,7 +113,7 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_spacetime_distributions", "is3d_plan_execute_spacetime", "is3d_write_spacetime",
            "is3d_spacetime_distributions_feqmod", "is3d_plan_execute_spacetime_feqmod", "is3d_spacetime_distributions_multi",
            "is3d_spin_polarization", "is3d_polarization_plan_create", "is3d_polarization_plan_execute", "is3d_polarization_plan_destroy",
-           "is3d_write_polarization", "is3d_surface_vorticity",
+           "is3d_write_polarization", "is3d_surface_vorticity", "is3d_spin_polarization_multi",
            "is3d_pdg_read_decays", "is3d_decay_q_factor", "is3d_resonance_decays", "is3d_decay_plan_create", "is3d_decay_plan_output_size",
            "is3d_decay_plan_execute", "is3d_decay_plan_destroy", "is3d_write_results_decays",
            "is3d_sampler_bin_list", "is3d_write_sampler_tests_binned", "is3d_sampler_plan_execute_binned", "is3d_sample_binned", "is3d_sample_binned_multi",
@@ -309,6 +309,9 @@ def load():
                                        C.POINTER(SpacetimeOut)]
     L.is3d_spin_polarization.argtypes = [C.POINTER(Cells), C.POINTER(Vorticity), C.POINTER(Species), C.POINTER(Grid), C.c_double,
                                          C.POINTER(Options), C.POINTER(PolarizationOut), C.POINTER(PolarizationStats)]
+    L.is3d_spin_polarization_multi.argtypes = [C.POINTER(Cells), C.POINTER(Vorticity), C.POINTER(Species), C.POINTER(Grid), C.c_double,
+                                               C.POINTER(Options), C.POINTER(C.c_int32), C.c_int32, C.POINTER(PolarizationOut),
+                                               C.POINTER(PolarizationStats), C.POINTER(PolarizationStats)]
     L.is3d_polarization_plan_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(Species), C.POINTER(Grid), C.POINTER(Options), C.c_int64]
     L.is3d_polarization_plan_execute.argtypes = [C.c_void_p, C.POINTER(Cells), C.POINTER(Vorticity), C.c_double, C.POINTER(PolarizationOut),
                                                  C.c_void_p, C.POINTER(PolarizationStats)]
@@ -748,6 +751,20 @@ def _host_cells(cells, held):
     return cs
 
 
+def _host_vorticity(vorticity, n_cells, held):
+    if vorticity is None:
+        return None
+    vs = Vorticity()
+    for f in VORTICITY_FIELDS:
+        a = vorticity.get(f)
+        if a is not None:
+            a = _f64(a)
+            assert a.shape == (n_cells,), f
+            held.append(a)
+            setattr(vs, f, a.ctypes.data)
+    return vs
+
+
 def spin_polarization(cells, vorticity, species, grid, T, opts=None):
     """is3d_spin_polarization (mode 5, the drop-in for calculate_spin_polzn with the vorticity read at the global cell index): host arrays
     in -> dict St, Sx, Sy, Sn, Snorm (flat, spectrum layout) and "stats".  vorticity: dict of VORTICITY_FIELDS arrays (None: refused by the
@@ -756,22 +773,46 @@ def spin_polarization(cells, vorticity, species, grid, T, opts=None):
     sps, gs, os_, nout, keep = _polzn_pack(species, grid, opts)
     held = []
     cs = _host_cells(cells, held)
-    vs = None
-    if vorticity is not None:
-        vs = Vorticity()
-        for f in VORTICITY_FIELDS:
-            a = vorticity.get(f)
-            if a is not None:
-                a = _f64(a)
-                assert a.shape == (cs.n_cells,), f
-                held.append(a)
-                setattr(vs, f, a.ctypes.data)
+    vs = _host_vorticity(vorticity, cs.n_cells, held)
     res = {k: np.zeros(nout) for k in POLARIZATION_OUTPUTS}
     po = PolarizationOut(*[res[k].ctypes.data for k in POLARIZATION_OUTPUTS])
     st = PolarizationStats()
     _check(L.is3d_spin_polarization(C.byref(cs), C.byref(vs) if vs is not None else None, C.byref(sps), C.byref(gs), float(T), C.byref(os_),
                                     C.byref(po), C.byref(st)))
     res["stats"] = st.as_dict()
+    return res
+
+
+def spin_polarization_multi(cells, vorticity, species, grid, T, opts=None, devices=None):
+    """is3d_spin_polarization_multi: the spin polarization with one contiguous cell shard per entry of devices (an ordinal may repeat; an int n
+    means the ordinals 0 .. n - 1; None or 0 every visible device), the shards' class sums added in shard order on devices[0].  Arguments and
+    result as spin_polarization, plus "shard_stats", one dict per shard.  One shard is spin_polarization on devices[0] bit for bit; N shards
+    are bitwise reproducible for that shard count and differ from the single device by the association of the additions only.  An Is3dError
+    raised here carries stats and shard_stats."""
+    L = load()
+    sps, gs, os_, nout, keep = _polzn_pack(species, grid, opts)
+    held = []
+    cs = _host_cells(cells, held)
+    vs = _host_vorticity(vorticity, cs.n_cells, held)
+    res = {k: np.zeros(nout) for k in POLARIZATION_OUTPUTS}
+    po = PolarizationOut(*[res[k].ctypes.data for k in POLARIZATION_OUTPUTS])
+    if devices is None or isinstance(devices, (int, np.integer)):
+        nd, dv = int(devices or 0), None
+    else:
+        nd = len(devices)
+        dv = (C.c_int32 * max(nd, 1))(*[int(d) for d in devices])
+    st = PolarizationStats()
+    n_stats = nd if nd > 0 else max(L.is3d_device_count(), 1)
+    sst = (PolarizationStats * max(n_stats, 1))()
+    rc = L.is3d_spin_polarization_multi(C.byref(cs), C.byref(vs) if vs is not None else None, C.byref(sps), C.byref(gs), float(T), C.byref(os_),
+                                        dv, nd, C.byref(po), C.byref(st), sst)
+    stats, shard_stats = st.as_dict(), [sst[i].as_dict() for i in range(n_stats)]
+    if rc != 0:
+        err = Is3dError(rc, L.is3d_last_error().decode())
+        err.stats, err.shard_stats = stats, shard_stats
+        raise err
+    res["stats"] = stats
+    res["shard_stats"] = shard_stats
     return res
 
 

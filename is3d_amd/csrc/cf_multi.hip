@@ -28,6 +28,7 @@
 
 #include "../../include/is3d_amd.h"
 #include "cf_host.h"
+#include "cf_polzn.h"
 #include "cf_spacetime.h"
 #include "errors.h"
 
@@ -1320,6 +1321,226 @@ extern "C" int is3d_spacetime_distributions_multi(const is3d_cells *cells, const
 {
     if (stats) { memset(stats, 0, sizeof *stats); stats->bad_cell = -1; }
     const int rc = st_multi_impl(cells, x, y, species, grid, pT_w, phi_w, df, fq, opts, devices, n_devices, bins, out, stats, shard_stats);
+    if (stats) stats->code = rc;   // whatever the way out: a refusal, a HIP failure, a shard's error
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// spin polarization (mode 5) over several devices: the per-chunk kernel and the chunk sums on contiguous shards of the cells, the shards'
+// class-lane sums placed on devices[0] and added there in shard order.  Cells are independent and none is skipped, so the shards exchange
+// nothing before the end: no thread waits for another
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct PzShard {
+    int device = 0;
+    int64_t lo = 0, hi = 0;
+    is3d_polarization_plan *plan = nullptr;
+    hipStream_t stream = nullptr;
+    is3d::DevBuf<double> d_in, V;   // d_in: 9 cell arrays + 6 vorticity arrays of the shard's cells
+    is3d_polarization_stats st{};
+    int rc = IS3D_OK;
+    std::string err;
+    ~PzShard()
+    {
+        (void)hipSetDevice(device);
+        if (plan) is3d_polarization_plan_destroy(plan);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+// a shard's cell slice and the same slice of the vorticity up, the per-chunk kernel, the class-lane sums into s.V; the stream is synchronised
+int pz_shard_run(PzShard &s, const is3d_cells *cells, const is3d_vorticity *w, const is3d_species *species, const is3d_grid *grid, double T,
+                 const is3d_options *opts)
+{
+    HIP_TRY(hipSetDevice(s.device));
+    const int64_t n = s.hi - s.lo;
+    const bool dim3 = opts->dimension == 3;
+    if (!s.plan) {
+        is3d_options o = *opts;
+        o.device = s.device;
+        if (int rc = is3d_polarization_plan_create(&s.plan, species, grid, &o, n)) return rc;
+    }
+    HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+    HIP_TRY(s.d_in.alloc((size_t)n * 15));
+    HIP_TRY(s.V.alloc((size_t)is3d::polzn_plan_class_sum_size(s.plan)));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    struct EvGuard { hipEvent_t &a, &b; ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evg{e0, e1};
+    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventRecord(e0, s.stream));
+    is3d_cells dc{};
+    HIP_TRY(is3d::stage_cells(*cells, [dim3](int i) { return i <= 8 && (i != 1 || dim3); }, s.lo, n, s.d_in.p, s.stream, &dc));
+    std::array<const double *, 6> wa{w->wtx, w->wty, w->wtn, w->wxy, w->wxn, w->wyn};
+    HIP_TRY(is3d::stage_arrays(wa, s.lo, n, s.d_in.p + 9 * (size_t)n, s.stream));   // the shard's own slice: global cell lo + c <-> local c
+    HIP_TRY(hipEventRecord(e1, s.stream));
+    const is3d_vorticity dw{wa[0], wa[1], wa[2], wa[3], wa[4], wa[5]};
+    const int rc = is3d::polzn_plan_class_sums(s.plan, &dc, &dw, T, s.V.p, s.stream, &s.st);
+    if (rc) return rc;
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    s.st.ms_h2d = ms;
+    return IS3D_OK;
+}
+
+int pz_multi_impl(const is3d_cells *cells, const is3d_vorticity *w, const is3d_species *species, const is3d_grid *grid, double T,
+                  const is3d_options *opts, const int32_t *devices, int32_t n_devices, is3d_polarization_out *out,
+                  is3d_polarization_stats *stats, is3d_polarization_stats *shard_stats)
+{
+    // ---- every refusal, before any device is used or a plan created ----
+    is3d_options dflt{};
+    dflt.dimension = 3;
+    if (!opts) opts = &dflt;   // as the single-device entries: 3+1D
+    if (int rc = is3d::polzn_check_args(cells, w, species, grid, T, opts, out)) return rc;
+    if (n_devices > 1024) return fail(IS3D_EINVAL, "n_devices = %d (up to 1024 shards)", n_devices);
+    if (devices)
+        for (int i = 0; i < n_devices; i++)
+            if (devices[i] < 0) return fail(IS3D_EINVAL, "devices[%d] = %d: a device ordinal cannot be negative", i, devices[i]);
+    const int visible = is3d_device_count();
+    if (!devices && n_devices > visible)
+        return fail(IS3D_EINVAL, "n_devices = %d with devices == NULL asks for the ordinals 0..%d, but %d HIP device%s visible", n_devices,
+                    n_devices - 1, visible, visible == 1 ? " is" : "s are");
+    if (visible < 1) return fail(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
+    if (n_devices <= 0) { n_devices = visible; devices = nullptr; }
+    std::vector<int> dev(n_devices);
+    for (int i = 0; i < n_devices; i++) {
+        dev[i] = devices ? devices[i] : i;
+        if (dev[i] >= visible) return fail(IS3D_EINVAL, "devices[%d] = %d is not one of the %d visible HIP devices", i, dev[i], visible);
+    }
+    if (shard_stats) memset(shard_stats, 0, sizeof(is3d_polarization_stats) * (size_t)n_devices);
+
+    if (n_devices == 1) {
+        // one shard IS the single-device call on devices[0]
+        is3d_options o = *opts;
+        o.device = dev[0];
+        is3d_polarization_stats st{};
+        const int rc = is3d_spin_polarization(cells, w, species, grid, T, &o, out, &st);
+        st.code = rc;
+        if (stats) *stats = st;
+        if (shard_stats) shard_stats[0] = st;
+        return rc;
+    }
+
+    // (declared ahead of the shards, so destroyed after them: the caller's thread gets its current device back)
+    struct DeviceRestore { int d = -1; ~DeviceRestore() { if (d >= 0) (void)hipSetDevice(d); } } restore;
+    if (hipGetDevice(&restore.d) != hipSuccess) { restore.d = -1; (void)hipGetLastError(); }
+    const int64_t n = cells->n_cells;
+    std::vector<PzShard> sh(n_devices);
+    int n_active = 0;
+    for (int i = 0; i < n_devices; i++) {
+        sh[i].device = dev[i];
+        (void)is3d_shard_bounds(n, i, n_devices, &sh[i].lo, &sh[i].hi);
+        if (sh[i].hi > sh[i].lo) n_active++;
+    }
+    // shard 0's plan lives on devices[0] and also holds the class index and scale tables of the combine (it has cells whenever any shard has)
+    HIP_TRY(hipSetDevice(dev[0]));
+    {
+        is3d_options o = *opts;
+        o.device = dev[0];
+        if (int rc = is3d_polarization_plan_create(&sh[0].plan, species, grid, &o, std::max<int64_t>(sh[0].hi - sh[0].lo, 1))) return rc;
+    }
+    is3d_polarization_plan *P0 = sh[0].plan;
+    auto run = [&](int i) {
+        sh[i].rc = pz_shard_run(sh[i], cells, w, species, grid, T, opts);
+        if (sh[i].rc) sh[i].err = is3d_last_error();   // the error text is thread-local
+    };
+    {
+        std::vector<std::thread> th;
+        for (int i = 0; i < n_devices; i++)
+            if (sh[i].hi > sh[i].lo) th.emplace_back(run, i);
+        for (auto &t : th) t.join();
+    }
+    is3d_polarization_stats agg{};
+    agg.n_classes = is3d::polzn_plan_classes(P0);
+    int rc_first = IS3D_OK;
+    std::string err_first;
+    double ms_sums = 0.0;
+    for (int i = 0; i < n_devices; i++) {
+        is3d_polarization_stats &t = sh[i].st;
+        t.n_classes = agg.n_classes;   // a function of the species list alone: shards without cells report it too
+        t.code = sh[i].rc;
+        if (shard_stats) shard_stats[i] = t;
+        if (sh[i].rc && !rc_first) { rc_first = sh[i].rc; err_first = "shard " + std::to_string(i) + " (device " + std::to_string(sh[i].device) + "): " + sh[i].err; }
+        agg.n_chunks += t.n_chunks;
+        agg.ms_cells = std::max(agg.ms_cells, t.ms_cells);
+        agg.ms_h2d = std::max(agg.ms_h2d, t.ms_h2d);
+        ms_sums = std::max(ms_sums, t.ms_reduce);
+    }
+    agg.ms_reduce = ms_sums;
+    agg.code = rc_first;
+    if (rc_first) {
+        if (stats) *stats = agg;
+        return fail(rc_first, "%s", err_first.c_str());
+    }
+
+    // ---- placement of the class sums on devices[0], the sum over the shards, the read-back ----
+    HIP_TRY(hipSetDevice(dev[0]));
+    if (!sh[0].stream) HIP_TRY(hipStreamCreateWithFlags(&sh[0].stream, hipStreamNonBlocking));
+    hipStream_t st0 = sh[0].stream;
+    const int64_t per = is3d::polzn_plan_class_sum_size(P0);
+    const size_t nout = (size_t)is3d::polzn_plan_output_size(P0);
+    is3d::DevBuf<double> stage, dout;
+    {
+        hipError_t e = stage.alloc((size_t)per * (size_t)n_active);
+        if (e == hipSuccess) e = dout.alloc(nout * 5);
+        if (e == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            return fail(IS3D_ENOMEM, "out of device memory for the class sums of %d shards (%.2f GB) on device %d", n_active, per * 8.0 * n_active / 1e9, dev[0]);
+        }
+        HIP_TRY(e);
+    }
+    // ev[0 .. n_active]: around each shard's placement; then the combine and the read-back
+    std::vector<hipEvent_t> ev((size_t)n_active + 3, nullptr);
+    struct EvGuard { std::vector<hipEvent_t> &e; ~EvGuard() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } evg{ev};
+    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(ev[0], st0));
+    int k = 0;
+    for (int i = 0; i < n_devices; i++) {   // every shard's stream is synchronised: its V is complete
+        if (sh[i].hi <= sh[i].lo) continue;
+        double *dst = stage.p + (size_t)per * k++;
+        if (sh[i].device == dev[0]) HIP_TRY(hipMemcpyAsync(dst, sh[i].V.p, sizeof(double) * (size_t)per, hipMemcpyDeviceToDevice, st0));
+        else HIP_TRY(hipMemcpyPeerAsync(dst, dev[0], sh[i].V.p, sh[i].device, sizeof(double) * (size_t)per, st0));
+        HIP_TRY(hipEventRecord(ev[k], st0));
+    }
+    const hipEvent_t e_placed = ev[n_active], e_combined = ev[n_active + 1], e_back = ev[n_active + 2];
+    const is3d_polarization_out dv{dout.p, dout.p + nout, dout.p + 2 * nout, dout.p + 3 * nout, dout.p + 4 * nout};
+    if (int rc = is3d::polzn_plan_combine(P0, stage.p, n_active, &dv, st0)) {
+        agg.code = rc;
+        if (stats) *stats = agg;
+        return rc;
+    }
+    HIP_TRY(hipEventRecord(e_combined, st0));
+    double *ho[5] = {out->St, out->Sx, out->Sy, out->Sn, out->Snorm};
+    for (int m = 0; m < 5; m++) HIP_TRY(hipMemcpyAsync(ho[m], dout.p + m * nout, sizeof(double) * nout, hipMemcpyDeviceToHost, st0));
+    HIP_TRY(hipEventRecord(e_back, st0));
+    HIP_TRY(hipEventSynchronize(e_back));
+    float place = 0.f, combine = 0.f, back = 0.f;
+    HIP_TRY(hipEventElapsedTime(&place, ev[0], e_placed));
+    HIP_TRY(hipEventElapsedTime(&combine, e_placed, e_combined));
+    HIP_TRY(hipEventElapsedTime(&back, e_combined, e_back));
+    if (shard_stats) {
+        k = 0;
+        for (int i = 0; i < n_devices; i++) {
+            if (sh[i].hi <= sh[i].lo) continue;
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+            shard_stats[i].ms_d2h = ms;   // the placement of this shard's class sums
+            k++;
+        }
+    }
+    agg.ms_reduce += combine;
+    agg.ms_d2h = (double)place + back;
+    agg.code = IS3D_OK;
+    if (stats) *stats = agg;
+    return IS3D_OK;
+}
+}  // namespace
+
+extern "C" int is3d_spin_polarization_multi(const is3d_cells *cells, const is3d_vorticity *vorticity, const is3d_species *species,
+                                            const is3d_grid *grid, double T, const is3d_options *opts, const int32_t *devices,
+                                            int32_t n_devices, is3d_polarization_out *out, is3d_polarization_stats *stats,
+                                            is3d_polarization_stats *shard_stats)
+{
+    if (stats) memset(stats, 0, sizeof *stats);
+    const int rc = pz_multi_impl(cells, vorticity, species, grid, T, opts, devices, n_devices, out, stats, shard_stats);
     if (stats) stats->code = rc;   // whatever the way out: a refusal, a HIP failure, a shard's error
     return rc;
 }

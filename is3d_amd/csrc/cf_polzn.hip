@@ -7,6 +7,9 @@
 //                   (3+1D 4 phi x 3 y, 2+1D 8 phi with the eta sum inside) and one chunk of the cells, and writes its five partial sums per
 //                   bin to the chunk's slab.
 //   cf_polzn_reduce the chunk slabs summed in chunk order per (species, pT, bin), the class's -1 / (4 m) applied once.
+// Over several devices (is3d_spin_polarization_multi, cf_multi.hip) the second stage is split in two:
+//   cf_polzn_class_sums  on each shard's device: its chunk slabs summed in chunk order per (class lane, bin), not expanded, not scaled.
+//   cf_polzn_shards      on the first device: the shards' class-lane sums added in shard order per (species, pT, bin), then the -1 / (4 m).
 // No floating-point atomics: the results are bitwise the same from run to run.
 //
 // Factorisation.  With A_k = cosh ut - sinh tau un, B_j = cos(phi) ux + sin(phi) uy and u_perp = sqrt(ux^2 + uy^2):
@@ -246,6 +249,61 @@ hipError_t launch_polzn_reduce(const double *slab, int nch, int64_t NB, int64_t 
     const int64_t n = (int64_t)S * npT * NB;
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(cf_polzn_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, slab, nch, NB, Lp, cls, scale, S, npT, npTp, St, Sx,
+                       Sy, Sn, Snorm);
+    return hipGetLastError();
+}
+
+// ---- several devices: a shard's class-lane sums, and their sum over the shards (is3d_spin_polarization_multi) ----
+// one thread per pair of class-lane elements (per = 5 NB Lp is even: Lp is a multiple of 64); the additions of cf_polzn_reduce, from the same 0.0
+__global__ void __launch_bounds__(256) cf_polzn_class_sums(const double *__restrict__ slab, int nch, int64_t per, double *__restrict__ V)
+{
+    const int64_t i = 2 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= per) return;
+    double2 v = {0.0, 0.0};
+    for (int ch = 0; ch < nch; ch++) {
+        const double2 a = *(const double2 *)(slab + (int64_t)ch * per + i);
+        v.x += a.x;
+        v.y += a.y;
+    }
+    *(double2 *)(V + i) = v;
+}
+
+hipError_t launch_polzn_class_sums(const double *slab, int nch, int64_t per, double *V, hipStream_t st)
+{
+    if (per <= 0) return hipSuccess;
+    hipLaunchKernelGGL(cf_polzn_class_sums, dim3((unsigned)((per / 2 + 255) / 256)), dim3(256), 0, st, slab, nch, per, V);
+    return hipGetLastError();
+}
+
+// one thread per output element (species, pT, bin), indexed as cf_polzn_reduce; the shards' sums added left to right in shard order
+__global__ void __launch_bounds__(256)
+cf_polzn_shards(const double *__restrict__ stage, int n_sh, int64_t NB, int64_t Lp, const int32_t *__restrict__ cls, const double *__restrict__ scale,
+                int S, int npT, int npTp, double *__restrict__ St, double *__restrict__ Sx, double *__restrict__ Sy, double *__restrict__ Sn,
+                double *__restrict__ Snorm)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)S * npT * NB) return;
+    const int s = (int)(i % S);
+    const int64_t r = i / S;
+    const int ipT = (int)(r % npT);
+    const int64_t bin = r / npT;
+    const int64_t l = (int64_t)cls[s] * npTp + ipT, per = 5 * NB * Lp;
+    double *outs[5] = {St, Sx, Sy, Sn, Snorm};
+#pragma unroll
+    for (int m = 0; m < 5; m++) {
+        const double *p = stage + ((int64_t)m * NB + bin) * Lp + l;
+        double v = n_sh > 0 ? p[0] : 0.0;
+        for (int k = 1; k < n_sh; k++) v = v + p[(int64_t)k * per];
+        outs[m][i] = m < 4 ? scale[s] * v : v;
+    }
+}
+
+hipError_t launch_polzn_shards(const double *stage, int n_sh, int64_t NB, int64_t Lp, const int32_t *cls, const double *scale, int S, int npT,
+                               int npTp, double *St, double *Sx, double *Sy, double *Sn, double *Snorm, hipStream_t st)
+{
+    const int64_t n = (int64_t)S * npT * NB;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(cf_polzn_shards, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, stage, n_sh, NB, Lp, cls, scale, S, npT, npTp, St, Sx,
                        Sy, Sn, Snorm);
     return hipGetLastError();
 }
@@ -513,3 +571,81 @@ extern "C" int is3d_spin_polarization(const is3d_cells *cells, const is3d_vortic
     }
     return IS3D_OK;
 }
+
+// =================================================================================================
+// what is3d_spin_polarization_multi (cf_multi.hip) takes from a plan: the checks, a shard's class-lane sums, the sum over the shards
+// =================================================================================================
+namespace is3d {
+
+int polzn_check_args(const is3d_cells *cells, const is3d_vorticity *w, const is3d_species *species, const is3d_grid *grid, double T,
+                     const is3d_options *opts, const is3d_polarization_out *out)
+{
+    int dim3;
+    if (int rc = dim_of(opts, &dim3)) return rc;
+    if (int rc = check_grid_species(species, grid, dim3)) return rc;
+    if (int rc = check_inputs(cells, w, T, dim3)) return rc;
+    if (!out || !out->St || !out->Sx || !out->Sy || !out->Sn || !out->Snorm) return set_error(IS3D_EINVAL, "the five output arrays are required");
+    return IS3D_OK;
+}
+
+int polzn_plan_classes(const is3d_polarization_plan *P) { return P->ncls; }
+int64_t polzn_plan_output_size(const is3d_polarization_plan *P) { return (int64_t)P->S * P->npT * P->NB; }
+int64_t polzn_plan_class_sum_size(const is3d_polarization_plan *P) { return 5 * P->NB * (int64_t)P->nlw * 64; }
+
+int polzn_plan_class_sums(is3d_polarization_plan *P, const is3d_cells *cells, const is3d_vorticity *w, double T, double *V, hipStream_t st,
+                          is3d_polarization_stats *stats)
+{
+    if (!P || !V || !stats) return set_error(IS3D_EINVAL, "plan, class sums or stats is NULL");
+    if (int rc = check_inputs(cells, w, T, P->dim3)) return rc;
+    const int64_t n = cells->n_cells;
+    if (n < 1) return set_error(IS3D_EINVAL, "a shard without cells has no class sums");
+    if (P->max_cells > 0 && n > P->max_cells)
+        return set_error(IS3D_EINVAL, "%lld cells > the plan's max_cells %lld", (long long)n, (long long)P->max_cells);
+    HIP_TRY(hipSetDevice(P->device));
+    const int nch = polzn_chunks(P, n);
+    const int64_t Lp = (int64_t)P->nlw * 64, per = 5 * P->NB * Lp;
+    const size_t need = (size_t)nch * (size_t)per;
+    if (P->slab.n < need) {
+        hipError_t e = P->slab.alloc(need);
+        if (e != hipSuccess) {
+            P->slab.release();
+            return set_error(IS3D_ENOMEM, "out of device memory for the polarization partial sums (%.2f GB: %d chunks x 5 x %lld bins x %lld lanes)",
+                             need * 8.0 / 1e9, nch, (long long)P->NB, (long long)Lp);
+        }
+    }
+    PolznArgs a{};
+    a.tau = cells->tau; a.eta = cells->eta; a.ux = cells->ux; a.uy = cells->uy; a.un = cells->un;
+    a.dat = cells->dat; a.dax = cells->dax; a.day = cells->day; a.dan = cells->dan;
+    a.wtx = w->wtx; a.wty = w->wty; a.wtn = w->wtn; a.wxy = w->wxy; a.wxn = w->wxn; a.wyn = w->wyn;
+    a.n_cells = (int32_t)n; a.nch = nch; a.nlw = P->nlw; a.ntj = P->ntj; a.ntk = P->ntk; a.J = P->J; a.K = P->K;
+    a.invT = 1.0 / T;
+    a.lane_mT = P->lane_mT.p; a.lane_pT = P->lane_pT.p; a.lane_sign = P->lane_sign.p;
+    a.cphi = P->cphi.p; a.sphi = P->sphi.p; a.ka = P->ka.p; a.kb = P->kb.p; a.kw = P->kw.p;
+    a.slab = P->slab.p; a.NB = P->NB;
+    HIP_TRY(hipEventRecord(P->ev[0], st));
+    HIP_TRY(launch_polzn_cells(a, P->dim3, st));
+    HIP_TRY(hipEventRecord(P->ev[1], st));
+    HIP_TRY(launch_polzn_class_sums(P->slab.p, nch, per, V, st));
+    HIP_TRY(hipEventRecord(P->ev[2], st));
+    HIP_TRY(hipEventSynchronize(P->ev[2]));
+    float t_cells = 0.f, t_sums = 0.f;
+    HIP_TRY(hipEventElapsedTime(&t_cells, P->ev[0], P->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&t_sums, P->ev[1], P->ev[2]));
+    stats->code = IS3D_OK;
+    stats->n_classes = P->ncls;
+    stats->n_chunks = nch;
+    stats->ms_cells = t_cells;
+    stats->ms_reduce = t_sums;
+    return IS3D_OK;
+}
+
+int polzn_plan_combine(is3d_polarization_plan *P, const double *stage, int n_sh, const is3d_polarization_out *out, hipStream_t st)
+{
+    if (!P || !out || n_sh < 0 || (n_sh > 0 && !stage)) return set_error(IS3D_EINVAL, "plan, staging array or outputs missing");
+    HIP_TRY(hipSetDevice(P->device));
+    HIP_TRY(launch_polzn_shards(stage, n_sh, P->NB, (int64_t)P->nlw * 64, P->cls.p, P->scale.p, P->S, P->npT, P->npTp, out->St, out->Sx, out->Sy,
+                                out->Sn, out->Snorm, st));
+    return IS3D_OK;
+}
+
+}  // namespace is3d

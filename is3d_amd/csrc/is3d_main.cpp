@@ -31,14 +31,15 @@ int main(int argc, char **argv)
             else { fprintf(stderr, "--reduce ordered|rccl\n"); return 2; }
         } else if (!strcmp(argv[i], "--help")) {
             printf("usage: %s [--variant 1|2|3|4] [--devices 0,1,...] [--reduce ordered|rccl]   (run inside an iS3D run directory)\n"
-                   "  operation = 1 shards the freezeout cells over the devices (default: every visible GPU; IS3D_DEVICES, IS3D_REDUCE)\n", argv[0]);
+                   "  operation = 1 shards the freezeout cells over the devices (default: every visible GPU; IS3D_DEVICES, IS3D_REDUCE)\n"
+                   "  mode = 5 shards the spin polarization over a device list given by --devices or IS3D_DEVICES (default: the first device alone)\n", argv[0]);
             return 0;
         }
     }
     if (devices.empty() && reduce < 0) return is3d_run_particlization(NULL, NULL, NULL, variant, NULL) == IS3D_OK ? 0 : 1;
-    if (devices.empty()) {   // --reduce alone: every visible device
-        for (int d = 0; d < is3d_device_count(); d++) devices.push_back(d);
-        if (devices.empty()) devices.push_back(0);
+    if (devices.empty()) {   // --reduce alone: every visible device, as a count -- no list was spelled out (mode 5: the polarization is not sharded)
+        const int n = is3d_device_count() > 0 ? is3d_device_count() : 1;
+        return is3d_run_particlization_on(NULL, NULL, NULL, variant, NULL, n, reduce, NULL) == IS3D_OK ? 0 : 1;
     }
     return is3d_run_particlization_on(NULL, NULL, NULL, variant, devices.data(), (int32_t)devices.size(),
                                       reduce < 0 ? IS3D_REDUCE_ORDERED : reduce, NULL) == IS3D_OK ? 0 : 1;

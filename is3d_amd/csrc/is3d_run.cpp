@@ -32,7 +32,10 @@
 // the embedding entry (which returns the list) refuse the key.
 // mode = 5: every run, whatever its operation, ends with the spin polarization from the surface's thermal vorticity (calculate_spin_polzn,
 // emissionfunction.cpp:1675) and appends results/St.dat, Sx.dat, Sy.dat, Sn.dat (write_polzn_vector_toFile, :1701), with T from the averages
-// file just written or T_switch when set_FO_temperature = 1; the embedding entry has no vorticity and says so.
+// file just written or T_switch when set_FO_temperature = 1; the embedding entry has no vorticity and says so.  With a device list that was
+// spelled out (the list of is3d_run_particlization_on, --devices, IS3D_DEVICES) the cells are sharded over it (is3d_spin_polarization_multi:
+// one shard per entry, the class sums added in shard order on the first device); without one, or with a bare device count, the first device
+// computes alone, so that the S files do not depend on how many devices a machine shows.
 // Scope: operation in {0, 1, 2}, mode in {0, 1, 4, 5, 6, 7}, df_mode in {1, 2, 3} with include_baryon in {0, 1}, df_mode 4
 // (modified equilibrium; also reads tables/gla_roots_weights_32_points.txt, deta_min, mass_pion0 and the surface
 // averages it has just written, as the reference does) with include_baryon = 0.  Anything else is refused
@@ -121,6 +124,7 @@ static void surface_averages(const is3d_cells *c, double avg[5])
 struct RunDevices {
     std::vector<int32_t> list;   // empty: all visible
     int32_t reduce = IS3D_REDUCE_ORDERED;
+    bool named = false;          // the list was spelled out (the entry's list, --devices, IS3D_DEVICES), not a bare count of ordinals
 };
 
 static int parse_run_devices(const int32_t *devices, int32_t n_devices, int32_t reduce, RunDevices &rd)
@@ -128,6 +132,7 @@ static int parse_run_devices(const int32_t *devices, int32_t n_devices, int32_t 
     rd.reduce = reduce;
     if (devices && n_devices > 0) {
         rd.list.assign(devices, devices + n_devices);
+        rd.named = true;
         return IS3D_OK;
     }
     if (n_devices > 0) {
@@ -150,6 +155,7 @@ static int parse_run_devices(const int32_t *devices, int32_t n_devices, int32_t 
                 p = (*end == ',') ? end + 1 : end;
                 if (*end && *end != ',') return die("IS3D_DEVICES = %s: a comma separated list of HIP device ordinals, or all", e);
             }
+            rd.named = !rd.list.empty();
         }
     }
     return IS3D_OK;
@@ -371,23 +377,29 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         is3d_vorticity vort{w[0], w[1], w[2], w[3], w[4], w[5]};
         is3d_options po{};
         po.dimension = dimension;
-        po.device = rd.list.empty() ? -1 : rd.list[0];   // the first device of the run: polarization is not sharded
+        po.device = rd.list.empty() ? -1 : rd.list[0];
         const size_t np = mcid.size() * pT.size() * phi.size() * (size_t)((dimension == 2) ? 1 : y.size());
         std::vector<double> pS[5];
         for (auto &v : pS) v.assign(np, 0.0);
         is3d_polarization_out po_out{pS[0].data(), pS[1].data(), pS[2].data(), pS[3].data(), pS[4].data()};
         is3d_polarization_stats pst{};
         printf("Calculating spin polarization vector (T = %.6f GeV)...\n", Tp);
-        const int rcp = is3d_spin_polarization(&cells, &vort, &sp, &grid, Tp, &po, &po_out, &pst);
+        // a device list the user spelled out shards the cells like the run's other cell sums do.  Without one the first device computes alone:
+        // the sum's association depends on the shard count, and the S files (eight digits) must not depend on how many cards a machine shows
+        std::vector<is3d_polarization_stats> pss(rd.named ? rd.list.size() : 0);
+        const int rcp = rd.named ? is3d_spin_polarization_multi(&cells, &vort, &sp, &grid, Tp, &po, rd.list.data(), (int32_t)rd.list.size(), &po_out,
+                                                                &pst, pss.data())
+                                 : is3d_spin_polarization(&cells, &vort, &sp, &grid, Tp, &po, &po_out, &pst);
         if (rcp) {
             const std::string msg = is3d_last_error();
-            DIE("is3d_spin_polarization failed (%d): %s", rcp, msg.c_str());
+            DIE("%s failed (%d): %s", rd.named ? "is3d_spin_polarization_multi" : "is3d_spin_polarization", rcp, msg.c_str());
         }
         printf("Writing polarization vector to file...\n");
         if (is3d_write_polarization("results", dimension, sp.n, grid.n_pT, pT.data(), grid.n_phi, phi.data(), grid.n_y, y.data(), &po_out))
             DIE("%s", is3d_last_error());
         printf("polarization: species classes evaluated: %d of %d; device time: cells %.3f ms, reduce %.3f ms\n", pst.n_classes, sp.n,
                pst.ms_cells, pst.ms_reduce);
+        if (rd.named) printf("polarization: %d shard%s; slowest shard's cells %.3f ms\n", (int)pss.size(), pss.size() == 1 ? "" : "s", pst.ms_cells);
         return IS3D_OK;
     };
     const int ny_eff = (dimension == 2) ? 1 : (int)y.size();
