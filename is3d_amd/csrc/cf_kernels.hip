@@ -1281,7 +1281,16 @@ __device__ unsigned long long g_prof3e[16];
 // E2L (variant 12, round 5, developer build): the E2 tables are neither streamed nor staged -- the workgroup BUILDS the tables of a batch in LDS from the
 // staged records' D'_j and Dmax (the expression of cf_prep's table writer, rounding for rounding: bitwise the same tables), one table region beside
 // the two record buffers, one more barrier per batch.
-template <bool CE, bool OUTFLOW, bool REG, int JT, int R, int MODE = 0, bool PROF = false, bool BARYON = false, bool E2G = false, bool RAWH = false, bool E2L = false>
+// SH8 (round 13; the default of the MODE 1 kernels without baryon slots, variants 6, 10 and 12 -- variant 13 of the developer build keeps the round-5 form): the header's wave-uniform D'_j and gamma_j leave the vector registers -- they go RAW
+// (the RAWH expressions) to SGPR pairs by v_readfirstlane once per live unit, one scalar operand per evaluation FMA; B_j stays raw in 16 VGPRs (with it
+// the SGPR file spills), and the C'_k leave their SGPRs: a live row reads its own again -- and the 32 VGPRs this frees hold
+// 8-wide reciprocal batches: ONE v_rcp_f64 per row of 8 phi values (rcp_batch<8>) instead of two.
+// Range of the shared reciprocal: q = (1 + sign z) x with x = p.u/T in (m/T, 1e9] (cf_prep refuses larger) and z = e^-(x - mu/T) <= 1, so q lies in
+// (1e-6, 2e9) for any surface (cf_main_tile states the same bound) and the product of 8 in (1e-48, 2.6e74): no overflow, underflow or zero.  The 8 q of a
+// batch belong to ONE lane and ONE row: a padded row (k >= K: A, alpha, beta zero, C' of row K-1) or a padded lane is dropped whole at the store, and a padded phi
+// (j >= J) is cf_prep's copy of phi J-1 (header, beta and E2 table alike), i.e. a q the live part of the batch already holds -- no new way to poison a live value.
+template <bool CE, bool OUTFLOW, bool REG, int JT, int R, int MODE = 0, bool PROF = false, bool BARYON = false, bool E2G = false, bool RAWH = false, bool E2L = false,
+          bool SH8 = false>
 __global__ void __launch_bounds__(512)
 cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, const double *__restrict__ lane_mT,
                const double *__restrict__ lane_pT, const double *__restrict__ lane_sign, const int32_t *__restrict__ lane_ipT,
@@ -1292,8 +1301,9 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
     // the header's x; the lane's baryon number b enters the exponent (b alpha_B) and the b-linear part of df (cf_main_tile)
     constexpr int HDR = 4 * JT + (BARYON ? 2 : 0), RS = BARYON ? 6 : 4, RW = RS + JT;
     constexpr int REC = HDR + R * RW;
-    constexpr int RB = JT % 4 == 0 ? 4 : (JT % 3 == 0 ? 3 : 2);
+    constexpr int RB = (SH8 && JT % 8 == 0) ? 8 : (JT % 4 == 0 ? 4 : (JT % 3 == 0 ? 3 : 2));
     static_assert(JT % RB == 0 && JT % 2 == 0, "phi tile: whole reciprocal batches, 16-byte records");
+    static_assert(!SH8 || (MODE >= 1 && !BARYON && !RAWH), "SH8: the row-mask kernel without baryon slots");
     // MODE 0 (variant 5): hand-pipelined rows; 1 (variant 6): the rows of a unit tested for liveness before their exponentials.
     // (Tried and dropped, round 2: the liveness of all rows of a BATCH of units in one pipelined pass before the batch, masks in
     // SGPRs -- 356.6 against 355.9 ms: the pass costs what it saves.)
@@ -1386,9 +1396,10 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
             const bool dead = __all(eu < cull_thr);
             if (g.zskip && dead) { n_rows += R; n_dead += R; return false; }
         }
-        if constexpr (ROWMASK) {
+        if constexpr (ROWMASK && !SH8) {
             // live unit: the C'_k are wave-uniform and stay live through the rows (each row's exponential starts from them before the
-            // row's own reads return): moved to SGPRs, no VGPR is free there
+            // row's own reads return): moved to SGPRs, no VGPR is free there.  (SH8: the 32 SGPRs of D'_j and gamma_j leave no room for these 14 --
+            // 26 v_writelane spills with them -- so a live row reads its C'_k again with its other operands.)
 #pragma unroll
             for (int r = 0; r < R; r++) {
                 const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)__double2loint(cn[r])), hi = __builtin_amdgcn_readfirstlane((unsigned)__double2hiint(cn[r]));
@@ -1398,7 +1409,11 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
         double pTB[JT], pTD[JT], pT2g[JT], E2[JT];
 #pragma unroll
         for (int jj = 0; jj < JT; jj++) {
-            if constexpr (RAWH) {   // raw header values (the names keep the products' roles)
+            if constexpr (SH8) {    // raw header values on the scalar side (wave-uniform: an LDS broadcast)
+                pTB[jj] = U[4 * jj + 0];            // (B_j too: 106 SGPRs and 43 v_writelane spills; D'_j and gamma_j alone fit)
+                pTD[jj] = to_sgpr(U[4 * jj + 1]);
+                pT2g[jj] = to_sgpr(U[4 * jj + 2]);
+            } else if constexpr (RAWH) {   // raw header values (the names keep the products' roles)
                 pTB[jj] = U[4 * jj + 0];
                 pTD[jj] = U[4 * jj + 1];
                 pT2g[jj] = U[4 * jj + 2];
@@ -1433,7 +1448,7 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
                 for (int i = 0; i < RB; i++) {
                     const double z = E1 * E2[j0 + i];
                     if (CE) {
-                        const double x = RAWH ? __builtin_fma(-pT, pTD[j0 + i], mTC) : mTC - pTD[j0 + i];
+                        const double x = (RAWH || SH8) ? __builtin_fma(-pT, pTD[j0 + i], mTC) : mTC - pTD[j0 + i];
                         zv[i] = z * x;
                         qq[i] = __builtin_fma(sign, zv[i], x);
                     } else {
@@ -1446,9 +1461,9 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
                 for (int i = 0; i < RB; i++) {
                     const int jj = j0 + i;
                     const double beta = rw.v[RS + jj];
-                    const double pds = RAWH ? (OUTFLOW ? fma_clamp01(pT, pTB[jj], mTA) : __builtin_fma(pT, pTB[jj], mTA))
-                                            : (OUTFLOW ? add_clamp01(mTA, pTB[jj]) : (mTA + pTB[jj]));
-                    const double br = RAWH ? __builtin_fma(mTpTs, beta, __builtin_fma(pT2s, pT2g[jj], mT2a)) : __builtin_fma(mTpTs, beta, mT2a + pT2g[jj]);
+                    const double pds = (RAWH || SH8) ? (OUTFLOW ? fma_clamp01(pT, pTB[jj], mTA) : __builtin_fma(pT, pTB[jj], mTA))
+                                                     : (OUTFLOW ? add_clamp01(mTA, pTB[jj]) : (mTA + pTB[jj]));
+                    const double br = (RAWH || SH8) ? __builtin_fma(mTpTs, beta, __builtin_fma(pT2s, pT2g[jj], mT2a)) : __builtin_fma(mTpTs, beta, mT2a + pT2g[jj]);
                     const double dfr = inv[i];
                     const double u = REG ? fma_clamp01_half(dfr, br) : __builtin_fma(dfr, br, 1.0);
                     const double w = (zv[i] * dfr) * u;
@@ -1478,7 +1493,9 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
                 if (live & (1u << r)) {
                     Row rw;
                     rw.v = rows + r * RW;
-                    rw.mTC = mT * cn[r];   // C'_k is already here (read with the unit bounds): the exponential starts before the row's own reads return
+                    // C'_k is already here (read with the unit bounds): the exponential starts before the row's own reads return.  SH8: cn[] served the row
+                    // tests only (no SGPRs left to keep it), the row reads its C'_k again with its other operands
+                    rw.mTC = mT * (SH8 ? rw.v[1] : cn[r]);
                     rw.E1 = exp_p9(BARYON ? (bmax - rw.mTC) + baB : bmax - rw.mTC);   // degree 9, one-fma reduction (cf_math.h): 7e-14
                     rw.live = true;
                     evals(rw, r);
@@ -2055,7 +2072,7 @@ constexpr int kTile7JT = 8, kTile7R = 31;   // variant 7 (2+1D)
 void main_tile_shape(int variant, int dim3, int *JT, int *KT)
 {
     if (variant == 1) { *JT = 1; *KT = dim3 ? kV1KT3 : kV1KT2; return; }
-    if (variant == 5 || variant == 6 || (variant >= 9 && variant <= 12)) variant = 3;   // same tile, E2 table stream
+    if (variant == 5 || variant == 6 || (variant >= 9 && variant <= 13)) variant = 3;   // same tile, E2 table stream
     if (variant == 7 || variant == 8) {
         if (!dim3) { *JT = kTile7JT; *KT = kTile7R; return; }
         variant = 3;
@@ -2065,7 +2082,7 @@ void main_tile_shape(int variant, int dim3, int *JT, int *KT)
     *KT = dim3 ? kTileR3[i] : kTileR2[i];
 }
 
-template <bool CE, bool OF, bool RG, int JT, int R, int MODE = 0, bool BARYON = false, bool E2G = false, bool RAWH = false, bool E2L = false>
+template <bool CE, bool OF, bool RG, int JT, int R, int MODE = 0, bool BARYON = false, bool E2G = false, bool RAWH = false, bool E2L = false, bool SH8 = false>
 static void launch_tile3e_t(const MainArgs &a_in, hipStream_t st)
 {
     MainArgs a = a_in;
@@ -2074,7 +2091,7 @@ static void launch_tile3e_t(const MainArgs &a_in, hipStream_t st)
     const int grid = ((pairs + 7) / 8) * 8 * a.g.ktiles * a.g.G;
     const size_t lds = tile3e_lds_bytes(JT, R, a.g.ub, 2, BARYON ? 1 : 0, E2L ? 2 : E2G ? 1 : 0);
     if constexpr (E2G || RAWH || E2L) {
-        hipLaunchKernelGGL((cf_main_tile3e<CE, OF, RG, JT, R, MODE, false, BARYON, E2G, RAWH, E2L>), dim3(grid), dim3(a.g.wpb * 64), lds, st, a.TS, a.TE, a.lane_mT,
+        hipLaunchKernelGGL((cf_main_tile3e<CE, OF, RG, JT, R, MODE, false, BARYON, E2G, RAWH, E2L, SH8>), dim3(grid), dim3(a.g.wpb * 64), lds, st, a.TS, a.TE, a.lane_mT,
                            a.lane_pT, a.lane_sign, a.lane_ipT, a.partial, a.stats, a.g, a.lane_pe, a.lane_b, a.cull_floor, a.pTgrid);
         return;
     }
@@ -2084,7 +2101,7 @@ static void launch_tile3e_t(const MainArgs &a_in, hipStream_t st)
         if (prof) {
             unsigned long long h[16] = {0};
             (void)hipMemcpyToSymbol(HIP_SYMBOL(g_prof3e), h, sizeof h);
-            hipLaunchKernelGGL((cf_main_tile3e<CE, OF, RG, JT, R, MODE, true>), dim3(grid), dim3(a.g.wpb * 64), lds, st, a.TS, a.TE, a.lane_mT,
+            hipLaunchKernelGGL((cf_main_tile3e<CE, OF, RG, JT, R, MODE, true, false, false, false, false, SH8>), dim3(grid), dim3(a.g.wpb * 64), lds, st, a.TS, a.TE, a.lane_mT,
                                a.lane_pT, a.lane_sign, a.lane_ipT, a.partial, a.stats, a.g, a.lane_pe, a.lane_b, a.cull_floor);
             (void)hipStreamSynchronize(st);
             (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_prof3e), sizeof h);
@@ -2096,7 +2113,7 @@ static void launch_tile3e_t(const MainArgs &a_in, hipStream_t st)
             return;
         }
     }
-    hipLaunchKernelGGL((cf_main_tile3e<CE, OF, RG, JT, R, MODE, false, BARYON>), dim3(grid), dim3(a.g.wpb * 64), lds, st, a.TS, a.TE, a.lane_mT,
+    hipLaunchKernelGGL((cf_main_tile3e<CE, OF, RG, JT, R, MODE, false, BARYON, false, false, false, SH8>), dim3(grid), dim3(a.g.wpb * 64), lds, st, a.TS, a.TE, a.lane_mT,
                        a.lane_pT, a.lane_sign, a.lane_ipT, a.partial, a.stats, a.g, a.lane_pe, a.lane_b, a.cull_floor);
 }
 
@@ -2113,15 +2130,18 @@ static void launch_variant(int variant, const MainArgs &a, hipStream_t st)
             // variant 5: the 8 x 7 tile with the E2 table stream, rows hand-pipelined (the plan only sets TE up for 3+1D)
             if (variant == 5 && a.TE && !a.g.baryon) { launch_tile3e_t<CE, OF, RG, kTileJT3[1], kTileR3[1]>(a, st); return; }
         }
-        if (variant == 6 && a.TE && !a.g.baryon) { launch_tile3e_t<CE, OF, RG, kTileJT3[1], kTileR3[1], 1>(a, st); return; }
+        // (D'_j and gamma_j in SGPRs, one reciprocal per row of 8: SH8 -- 322.8 against 328.2 ms on config 3, profiles/r13_ab_rcp8.log)
+        if (variant == 6 && a.TE && !a.g.baryon) { launch_tile3e_t<CE, OF, RG, kTileJT3[1], kTileR3[1], 1, false, false, false, false, true>(a, st); return; }
         if ((variant == 5 || variant == 6) && a.TE && a.g.baryon) { launch_tile3e_t<CE, OF, RG, kTileJT3[1], kTileR3[1], 1, true>(a, st); return; }
         if constexpr (kDevBuild) {
             // variant 10 (round 5): the E2 column straight from global memory into registers, records-only LDS batches
-            if (variant == 10 && a.TE && !a.g.baryon) { launch_tile3e_t<CE, OF, RG, kTileJT3[1], kTileR3[1], 1, false, true>(a, st); return; }
+            if (variant == 10 && a.TE && !a.g.baryon) { launch_tile3e_t<CE, OF, RG, kTileJT3[1], kTileR3[1], 1, false, true, false, false, true>(a, st); return; }
             // variant 11 (round 5): raw header values as FMA operands
             if (variant == 11 && a.TE && !a.g.baryon) { launch_tile3e_t<CE, OF, RG, kTileJT3[1], kTileR3[1], 1, false, false, true>(a, st); return; }
             // variant 12 (round 5): the E2 tables built per workgroup in LDS from the staged records
-            if (variant == 12 && a.TE && a.pTgrid && !a.g.baryon) { launch_tile3e_t<CE, OF, RG, kTileJT3[1], kTileR3[1], 1, false, false, false, true>(a, st); return; }
+            if (variant == 12 && a.TE && a.pTgrid && !a.g.baryon) { launch_tile3e_t<CE, OF, RG, kTileJT3[1], kTileR3[1], 1, false, false, false, true, true>(a, st); return; }
+            // variant 13: variant 6 as it was through round 5 -- the header times the lane's pT in 48 VGPRs, a reciprocal per 4 evaluations
+            if (variant == 13 && a.TE && !a.g.baryon) { launch_tile3e_t<CE, OF, RG, kTileJT3[1], kTileR3[1], 1>(a, st); return; }
         }
         if constexpr (kDevBuild)   // measured and dropped (profiles/r05_ab_tile3s.log: 120.4 against 100.2 ms)
         if (variant == 9 && a.TE && !a.g.baryon && a.g.wpb == 1) {   // cf_main_tile3s: one-wave workgroups, no LDS
@@ -2134,7 +2154,7 @@ static void launch_variant(int variant, const MainArgs &a, hipStream_t st)
             return;
         }
     }
-    if (variant == 5 || variant == 6 || (variant >= 9 && variant <= 12)) variant = 3;
+    if (variant == 5 || variant == 6 || (variant >= 9 && variant <= 13)) variant = 3;
     if constexpr (!DIM3) {
         // variant 7: 2+1D, 8 x 31 tile: units short enough for four of them per LDS buffer, i.e. for unit-strided lanes with S = 4
         if (variant == 7 || !kDevBuild) { launch_tile_t<CE, false, OF, RG, kTile7JT, kTile7R>(a, st); return; }
@@ -2220,7 +2240,7 @@ hipError_t launch_main(int variant, int ce, int dim3, int outflow, int reg, cons
 
 const char *main_kernel_name(int variant)
 {
-    return variant == 1 ? "cf_main_direct" : variant == 9 ? "cf_main_tile3s" : ((variant == 5 || variant == 6 || variant == 10 || variant == 11 || variant == 12) ? "cf_main_tile3e" : "cf_main_tile");
+    return variant == 1 ? "cf_main_direct" : variant == 9 ? "cf_main_tile3s" : ((variant == 5 || variant == 6 || variant == 10 || variant == 11 || variant == 12 || variant == 13) ? "cf_main_tile3e" : "cf_main_tile");
 }
 
 // ------------------------------------------------------------------------------------------------

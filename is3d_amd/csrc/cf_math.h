@@ -254,6 +254,13 @@ __device__ __forceinline__ double fma_clamp01(double a, double b, double c)
     return u;
 }
 
+// a wave-uniform double (an LDS broadcast, say) moved to an SGPR pair: two v_readfirstlane_b32
+__device__ __forceinline__ double to_sgpr(double v)
+{
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)__double2loint(v)), hi = __builtin_amdgcn_readfirstlane((unsigned)__double2hiint(v));
+    return __hiloint2double((int)hi, (int)lo);
+}
+
 // sqrt(x) for normal x > 0: v_rsq_f64 seed, one coupled Newton (Goldschmidt) step for sqrt and 1/(2 sqrt), then one
 // residual correction: relative error <= ~1.5e-16 for any seed better than 1e-5.  No range scaling: callers pass
 // x in [1e-280, 1e280].

@@ -45,7 +45,7 @@ def demangle_params(sym):
     if name == "cf_main_tile":
         keys = ["CE", "DIM3", "OUTFLOW", "REG", "BARYON", "JT", "R", "LAZY", "DMA"]
     elif name == "cf_main_tile3e":
-        keys = ["CE", "OUTFLOW", "REG", "JT", "R", "MODE", "PROF", "BARYON", "E2G", "RAWH", "E2L"]
+        keys = ["CE", "OUTFLOW", "REG", "JT", "R", "MODE", "PROF", "BARYON", "E2G", "RAWH", "E2L", "SH8"]
     elif name == "cf_main_tile3s":
         keys = ["CE", "OUTFLOW", "REG", "JT", "R"]
     elif name == "cf_main_feqmod":
@@ -212,6 +212,8 @@ def main():
         else:
             jt = params["JT"]
             rbatch_t = (4 if jt % 4 == 0 else (3 if jt % 3 == 0 else 2)) if params.get("DIM3", 1) else (8 if jt % 8 == 0 else 4)
+            if name == "cf_main_tile3e" and params.get("SH8") and jt % 8 == 0:
+                rbatch_t = 8
         n_eval = count_evaluations(hot_ins)
         from_isa = n_eval > 0 and n_eval % hot["v_rcp_f64"] == 0
         if not from_isa:   # accumulators spilled or renamed inside the loop: fall back to the template rule and say so
@@ -235,7 +237,13 @@ def main():
         if name == "cf_main_tile3e" and params.pop("E2L", 0):    # variant 12 (tables built per workgroup in LDS)
             name = "cf_main_tile3e_e2l"
         params.pop("E2L", None)
-        if name in ("cf_main_tile3e", "cf_main_tile3e_e2g", "cf_main_tile3e_rawh", "cf_main_tile3e_e2l") and params.pop("BARYON", 0):
+        # SH8 (D'_j, gamma_j in SGPRs, one reciprocal per row of 8: what variant 6 launches since round 13) has its own key; the plain key stays with the
+        # round-5 form (variant 13 of the developer build), whose figures tests/test_isa_counts.py pins
+        sh8 = name == "cf_main_tile3e" and params.pop("SH8", 0)
+        if sh8:
+            name = "cf_main_tile3e_sh8"
+        params.pop("SH8", None)
+        if name in ("cf_main_tile3e", "cf_main_tile3e_e2g", "cf_main_tile3e_rawh", "cf_main_tile3e_e2l", "cf_main_tile3e_sh8") and params.pop("BARYON", 0):
             name += "_baryon"
         key = "%s:%s" % (name, ",".join("%s=%d" % kv for kv in params.items()))
         if vah3_alt:
