@@ -999,6 +999,39 @@ int is3d_df_table_read_full(const char *path, int32_t *n_T, int32_t *n_muB, doub
  * Two-call pattern (root == NULL -> only the shape); root/weight[alpha * n_points + k], capacity in doubles each. */
 int is3d_gla_read(const char *path, int32_t *n_alpha, int32_t *n_points, double *root, double *weight, int64_t capacity);
 
+/* The df-coefficient generator (generate_delta_f_coefficients/<list>/df_vh_dimensionless/src/deltaf_table.cpp:137-248, :296-395) on the device:
+ * the ten tables of deltaf_coefficients/vh/<list>/ for any hadron list, Gauss-Laguerre rule and (T, mu_B) grid.
+ *   list      every entry as is3d_pdg_read / is3d_pdg_read_box return it; entries with mass == 0 (the photon) are skipped as in the reference
+ *   root, weight   [4][n_gla]: the Gauss-Laguerre rules for alpha = 1, 2, 3, 4 (rows 1..4 of is3d_gla_read's arrays), any n_gla >= 1
+ *   T, muB    [n_T], [n_muB] in GeV, any order; T > 0
+ *   tables    [10][n_muB][n_T]: c0 T^4, c1 T^3, c2 T^4, c3 T^4, c4 T^5, F / T, G, betabulk / T^4, betaV / T^3, betapi / T^4 -- the numbers the
+ *             generator prints (:240-244, :387-391)
+ *   integrals NULL, or [20][n_muB][n_T]: J20 J21 J40 J41 N10 N30 N31 M20 M21 A20 A21 B10 nB e p J30 J32 N20 M10 M11 in the generator's units
+ * Every sum has a fixed order that depends on n_gla and list->n alone (csrc/cf_dfgen.hip): a point's numbers are bitwise the same from run to
+ * run and in whatever grid the point is computed; `integrals` changes no bit of `tables`.
+ * Arguments are checked before any device use: null pointers, n <= 0, n_gla <= 0, n_T or n_muB <= 0, T <= 0, a root <= 0, a negative mass and
+ * non-finite values are IS3D_EINVAL; a good call without a device is IS3D_ENODEVICE (no CPU path).  Where the reference calls exit(-1) --
+ * exp(E/T - b muB/T) + sign <= 0 at a node (thermal_integrands.cpp:18-23), a zero bulk or diffusion denominator (deltaf_table.cpp:228-237), a
+ * zero betapi, betabulk or betaV (:370-384) -- and where an output is not finite, the call returns IS3D_EDOMAIN; is3d_last_error() names T, mu_B
+ * and the condition(s) of the first such point in grid order (and the list entry for the first case).  `tables` is filled nevertheless. */
+typedef struct {
+    int32_t n;
+    const double *mass, *gspin, *baryon, *sign;
+} is3d_hadron_list;
+typedef struct {
+    double ms_kernel, ms_h2d, ms_d2h;   /* device time of the kernel (events); wall time of the uploads and of the copies back */
+    int32_t n_massive;                  /* entries with mass != 0 */
+    int32_t reserved;
+} is3d_dfgen_stats;
+int is3d_df_generate(const is3d_hadron_list *list, int32_t n_gla, const double *const root[4], const double *const weight[4],
+                     int32_t n_T, const double *T, int32_t n_muB, const double *muB, int32_t device, double *tables,
+                     double *integrals, is3d_dfgen_stats *stats);
+/* Writes <dir>/{c0,c1,c2,c3,c4,F,G,betabulk,betaV,betapi}.dat in the generator's format (the two count lines, the label line of
+ * deltaf_table.cpp:129-133 / :288-292, then rows `fixed`, setw(8), mu_B outer, T inner), which is3d_df_table_read[_full] read back.  tables as
+ * is3d_df_generate fills it.  <dir> is created if missing (one level); an existing <dir>/c0.dat is never overwritten: IS3D_EINVAL.  A value
+ * that is not finite is IS3D_EINVAL; IS3D_EIO if a file cannot be written. */
+int is3d_df_tables_write(const char *dir, int32_t n_T, const double *T, int32_t n_muB, const double *muB, const double *tables);
+
 /* Writers (src/cpp/emissionfunction.cpp:381-450, :729-772, :1053-1136): append to
  * <dir>/dN_pTdpTdphidy.dat, <dir>/dN_pTdpTdphidy_<mcid>.dat, <dir>/dN_dy_<mcid>.dat,
  * <dir>/vn_continuous/vn_<mcid>.dat in the reference's formatting.  pT/phi/y carry nodes and

@@ -117,7 +117,7 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_pdg_read_decays", "is3d_decay_q_factor", "is3d_resonance_decays", "is3d_decay_plan_create", "is3d_decay_plan_output_size",
            "is3d_decay_plan_execute", "is3d_decay_plan_destroy", "is3d_write_results_decays",
            "is3d_sampler_bin_list", "is3d_write_sampler_tests_binned", "is3d_sampler_plan_execute_binned", "is3d_sample_binned", "is3d_sample_binned_multi",
-           "is3d_sampler_bin_list_device"]
+           "is3d_sampler_bin_list_device", "is3d_df_generate", "is3d_df_tables_write"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 POLARIZATION_OUTPUTS = ["St", "Sx", "Sy", "Sn", "Snorm"]
@@ -196,6 +196,17 @@ def spacetime_shapes(n_species, n_cells, bins, dimension, n_eta):
 REDUCE_ORDERED, REDUCE_RCCL = 0, 1
 IS3D_EPEER = -6
 COMM_ID_BYTES = 128
+
+
+class HadronList(C.Structure):
+    _fields_ = [("n", C.c_int32), ("mass", _dp), ("gspin", _dp), ("baryon", _dp), ("sign", _dp)]
+
+
+class DfgenStats(C.Structure):
+    _fields_ = [("ms_kernel", C.c_double), ("ms_h2d", C.c_double), ("ms_d2h", C.c_double), ("n_massive", C.c_int32), ("reserved", C.c_int32)]
+
+
+DFGEN_INTEGRALS = ["J20", "J21", "J40", "J41", "N10", "N30", "N31", "M20", "M21", "A20", "A21", "B10", "nB", "e", "p", "J30", "J32", "N20", "M10", "M11"]
 
 
 class Is3dError(RuntimeError):
@@ -333,6 +344,9 @@ def load():
     L.is3d_decay_plan_destroy.argtypes = [C.c_void_p]
     L.is3d_decay_plan_destroy.restype = None
     L.is3d_write_results_decays.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp]
+    L.is3d_df_generate.argtypes = [C.POINTER(HadronList), C.c_int32, C.POINTER(_dp), C.POINTER(_dp), C.c_int32, _dp, C.c_int32, _dp, C.c_int32,
+                                   _dp, _dp, C.POINTER(DfgenStats)]
+    L.is3d_df_tables_write.argtypes = [C.c_char_p, C.c_int32, _dp, C.c_int32, _dp, _dp]
     _LIB = L
     return L
 
@@ -1379,6 +1393,38 @@ def df_table_read_full(path):
     T, B, v = np.zeros(nT.value), np.zeros(nB.value), np.zeros((nB.value, nT.value))
     _check(L.is3d_df_table_read_full(path.encode(), C.byref(nT), C.byref(nB), _p(T), _p(B), _p(v), v.size))
     return T, B, v
+
+
+def df_generate(pdg, root, weight, T, muB, device=-1, with_integrals=False):
+    """is3d_df_generate: the ten coefficient tables of deltaf_coefficients/vh/<list>/ for the hadron list `pdg` (as pdg_read returns it) on the
+    (T, muB) grid, computed on the device.  root, weight: the Gauss-Laguerre arrays as gla_read returns them (row alpha; rows 1..4 are used).
+    Returns (tables [10][n_muB][n_T] in the order of DF_NAMES_2D, integrals [20][n_muB][n_T] in the order of DFGEN_INTEGRALS or None, stats)."""
+    L = load()
+    cols = [_f64(pdg[k]) for k in ("mass", "gspin", "baryon", "sign")]
+    n = len(cols[0])
+    if any(len(c) != n for c in cols):
+        raise ValueError("the hadron list's arrays differ in length")
+    root, weight = np.asarray(root, dtype=np.float64), np.asarray(weight, dtype=np.float64)
+    if root.ndim != 2 or root.shape != weight.shape or root.shape[0] < 5:
+        raise ValueError("root and weight must be [n_alpha >= 5][n_points] (alpha = 1..4 are used)")
+    rows = [_f64(root[a]) for a in range(1, 5)] + [_f64(weight[a]) for a in range(1, 5)]
+    r4, w4 = (_dp * 4)(*[_p(a) for a in rows[:4]]), (_dp * 4)(*[_p(a) for a in rows[4:]])
+    T, muB = _f64(np.atleast_1d(T)), _f64(np.atleast_1d(muB))
+    hl = HadronList(n, *[_p(c) for c in cols])
+    tables = np.zeros((10, len(muB), len(T)))
+    integrals = np.zeros((20, len(muB), len(T))) if with_integrals else None
+    st = DfgenStats()
+    _check(L.is3d_df_generate(C.byref(hl), root.shape[1], r4, w4, len(T), _p(T), len(muB), _p(muB), device, _p(tables),
+                              _p(integrals) if with_integrals else None, C.byref(st)))
+    return tables, integrals, dict(ms_kernel=st.ms_kernel, ms_h2d=st.ms_h2d, ms_d2h=st.ms_d2h, n_massive=st.n_massive)
+
+
+def df_tables_write(directory, T, muB, tables):
+    """is3d_df_tables_write: the ten files of a coefficient directory in the generator's format; refuses to overwrite an existing c0.dat."""
+    T, muB, tables = _f64(np.atleast_1d(T)), _f64(np.atleast_1d(muB)), _f64(tables)
+    if tables.shape != (10, len(muB), len(T)):
+        raise ValueError("tables must be [10][n_muB][n_T]")
+    _check(load().is3d_df_tables_write(str(directory).encode(), len(T), _p(T), len(muB), _p(muB), _p(tables)))
 
 
 def _pack_sampler(cells, species, df, gla, opts, n_events, seed, y_cut, first_cell, fq, fast, T_avg, T_avg_switch, batch_events, muB_avg):

@@ -1732,3 +1732,55 @@ extern "C" int is3d_write_polarization(const char *results_dir, int32_t dimensio
     }
     return IS3D_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The coefficient generator's output files (generate_delta_f_coefficients/*/df_vh_dimensionless/src/deltaf_table.cpp):
+//   "<n_T>\n<n_muB>\n", the label line (:129-133, :288-292), then per (mu_B outer, T inner) `fixed << setw(8) << T << "\t\t" << muB
+//   << "\t\t" << value` (:240-244, :387-391): setw holds for T alone, the precision is the stream's default 6.
+// ---------------------------------------------------------------------------------------------
+extern "C" int is3d_df_tables_write(const char *dir, int32_t n_T, const double *T, int32_t n_muB, const double *muB, const double *tables)
+{
+    if (!dir || !T || !muB || !tables) return io_fail(IS3D_EINVAL, "null argument");
+    if (n_T < 1 || n_muB < 1) return io_fail(IS3D_EINVAL, "n_T = %d, n_muB = %d: at least one of each", n_T, n_muB);
+    static const char *const names[10] = {"c0", "c1", "c2", "c3", "c4", "F", "G", "betabulk", "betaV", "betapi"};
+    static const char *const labels[10] = {"c0_T4 [fm^3/GeV^3 * GeV^4]", "c1_T3 [fm^3/GeV^2 * GeV^3]", "c2_T4 [fm^3/GeV^3 * GeV^4]", "c3_T4 [fm^3/GeV * GeV^4]",
+                                           "c4_T5 [fm^3/GeV^2 * GeV^5]", "F_over_T [fm^-1 / GeV]", "G [1]", "betabulk_over_T4 [fm^-4 / GeV^4]",
+                                           "betaV_over_T3 [fm^-3 / GeV^3]", "betapi_over_T4 [fm^-4 / GeV^4]"};
+    const size_t npt = (size_t)n_T * n_muB;
+    for (int i = 0; i < n_T; i++)
+        if (!std::isfinite(T[i])) return io_fail(IS3D_EINVAL, "T[%d] is not finite", i);
+    for (int i = 0; i < n_muB; i++)
+        if (!std::isfinite(muB[i])) return io_fail(IS3D_EINVAL, "muB[%d] is not finite", i);
+    for (size_t i = 0; i < 10 * npt; i++)
+        if (!std::isfinite(tables[i]))
+            return io_fail(IS3D_EINVAL, "%s at T = %.6g, muB = %.6g GeV is not finite", names[i / npt], T[(i % npt) % n_T], muB[(i % npt) / n_T]);
+    std::string base(dir);
+    while (base.size() > 1 && base.back() == '/') base.pop_back();
+    struct stat sb;
+    if (stat((base + "/c0.dat").c_str(), &sb) == 0)
+        return io_fail(IS3D_EINVAL, "%s/c0.dat exists: coefficient tables are never overwritten; choose another directory", base.c_str());
+    if (stat(base.c_str(), &sb) != 0 && mkdir(base.c_str(), 0777) != 0) return io_fail(IS3D_EIO, "cannot create the directory %s", base.c_str());
+    std::string text;
+    char line[160];
+    for (int t = 0; t < 10; t++) {
+        text.clear();
+        text.reserve(npt * 40 + 128);
+        snprintf(line, sizeof line, "%d\n%d\n", n_T, n_muB);
+        text += line;
+        text += "T [GeV]\t\tmuB [GeV]\t\t";
+        text += labels[t];
+        text += "\n";
+        const double *v = tables + (size_t)t * npt;
+        for (int ib = 0; ib < n_muB; ib++)
+            for (int i = 0; i < n_T; i++) {
+                snprintf(line, sizeof line, "%8.6f\t\t%.6f\t\t%.6f\n", T[i], muB[ib], v[(size_t)ib * n_T + i]);
+                text += line;
+            }
+        const std::string path = base + "/" + names[t] + ".dat";
+        FILE *f = fopen(path.c_str(), "w");
+        if (!f) return io_fail(IS3D_EIO, "cannot open %s for writing", path.c_str());
+        const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+        if (fclose(f) != 0 || !ok) return io_fail(IS3D_EIO, "short write to %s", path.c_str());
+    }
+    return IS3D_OK;
+}

@@ -26,6 +26,8 @@
 // feed-down (is3d_resonance_decays) runs on the spectrum on the first device of the run's list and results/dN_pTdpTdphidy_resonance_decays.dat
 // and dN_dpTdphidy_resonance_decays.dat are appended (emissionfunction.cpp:1689-1698); the embedding result keeps the thermal spectrum.
 // Operations 0 and 2 and hrg_eos = 3 (no decay data) refuse the key.
+// deltaf_dir = DIR (optional key, absent by default): the coefficient tables are read from DIR instead of deltaf_coefficients/vh/<eos>/ --
+// a directory written by `iS3D_amd --generate-df DIR` (is3d_main.cpp) for an edited list or another (T, mu_B) grid.
 // test_sampler_on_device = 1 (optional key, default 0): with operation = 2 and test_sampler = 1 the hadrons are sampled ONCE and binned per event
 // batch on the device (is3d_sample_binned_multi), never held as a list; the same files are written from the integer histograms
 // (is3d_write_sampler_tests_binned; vn/ to the fixed point) and the same lines printed, plus ms_bin.  test_sampler = 0, other operations and
@@ -82,6 +84,24 @@ static int get_param(const char *name, double *v, bool required = true)
     int rc = is3d_param_get("iS3D_parameters.dat", name, v);
     if (rc && required) fprintf(stderr, "iS3D-amd: %s\n", is3d_last_error());
     return rc;
+}
+
+// an optional key whose value is text (deltaf_dir): the line rules of is3d_param_get -- '#' starts a comment, blanks and tabs are removed, the
+// name is lower-cased, later lines overwrite -- with the right-hand side taken verbatim.  False when the key is absent.
+static bool get_param_text(const char *name, std::string &value)
+{
+    std::ifstream f("iS3D_parameters.dat");
+    bool found = false;
+    for (std::string line; std::getline(f, line);) {
+        line = line.substr(0, line.find('#'));
+        line.erase(std::remove_if(line.begin(), line.end(), [](char c) { return c == ' ' || c == '\t' || c == '\r'; }), line.end());
+        const size_t eq = line.find('=');
+        if (eq == std::string::npos) continue;
+        std::string lhs = line.substr(0, eq);
+        for (char &c : lhs) c = (char)tolower((unsigned char)c);
+        if (lhs == name) { value = line.substr(eq + 1); found = true; }
+    }
+    return found;
 }
 
 static int read_table(const char *path, std::vector<double> &col1, std::vector<double> &col2)
@@ -230,6 +250,14 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
     else if (hrg_eos == 2) { pdg_path = "PDG/pdg_smash.dat"; df_dir = "deltaf_coefficients/vh/smash/"; }
     else if (hrg_eos == 3) { pdg_path = "PDG/pdg_box.dat"; df_dir = "deltaf_coefficients/vh/smash_box/"; }   // readindata.h:219, deltafReader.h:29
     else DIE("hrg_eos = %d: please choose hrg_eos = (1,2,3)", hrg_eos);
+    // optional key deltaf_dir: the coefficient tables come from that directory (one written by `iS3D_amd --generate-df DIR`, say) instead
+    std::string df_dir_key;
+    if (get_param_text("deltaf_dir", df_dir_key)) {
+        if (df_dir_key.empty()) DIE("deltaf_dir is empty: name the directory that holds c0.dat ... betapi.dat, or remove the key");
+        if (df_dir_key.back() != '/') df_dir_key += '/';
+        df_dir = df_dir_key.c_str();
+        printf("df coefficient tables from %s (deltaf_dir)\n", df_dir);
+    }
 
     double t0 = now_s();
     // the device contexts are created while the surface is being parsed (joined before the first device call)
