@@ -294,6 +294,9 @@ void is3d_plan_destroy(is3d_plan *plan);
 /* Host entry over several devices: what is3d_smooth_spectra / is3d_smooth_spectra_feqmod (fq != NULL: df_mode 3, 4) compute,
  * with the cells split into n_devices contiguous shards (sizes differ by at most one cell), shard s on devices[s].
  *   devices == NULL: ordinals 0 .. n_devices-1;  n_devices <= 0: every visible device.  opts->device is ignored.
+ *   Every in-process multi-device entry reads its list by this one rule: more than 1024 shards, a negative ordinal and n_devices beyond the
+ *   visible count with devices == NULL are IS3D_EINVAL before any device is used (so with or without one), then no visible device is
+ *   IS3D_ENODEVICE, then an ordinal beyond the visible count IS3D_EINVAL; the message names devices[i] or n_devices.
  *   status (may be NULL): counters summed over the shards, bad_cell = lowest global cell index, ms_prep / ms_main / ms_finalize /
  *   ms_h2d = the slowest shard's, ms_d2h = reduction + download;  shard_status (may be NULL): n_devices entries, one per shard
  *   (bad_cell is shard-local there).

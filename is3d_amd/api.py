@@ -671,6 +671,17 @@ def spacetime_distributions(cells, species, grid, df, bins, opts=None, per_cell=
     return res
 
 
+def _pack_devices(devices):
+    """The devices argument of the multi-device wrappers -> (c_int32 array or None, n_devices, n_stats): None or an int n means no list and that
+    count (None or 0: every visible device; n: the ordinals 0 .. n - 1), a sequence its entries; n_stats: the shards the library reports on."""
+    if devices is None or isinstance(devices, (int, np.integer)):
+        nd, dv = int(devices or 0), None
+    else:
+        nd = len(devices)
+        dv = (C.c_int32 * max(nd, 1))(*[int(d) for d in devices])
+    return dv, nd, nd if nd > 0 else max(load().is3d_device_count(), 1)
+
+
 def spacetime_distributions_multi(cells, species, grid, df, bins, opts=None, devices=None, fq=None, per_cell=False, x=None, y=None):
     """is3d_spacetime_distributions_multi: operation 0 with the per-cell stage on one contiguous cell shard per entry of devices (an ordinal may
     repeat; an int n means the ordinals 0 .. n - 1; None or 0 every visible device) and ONE bin stage on devices[0].  Arguments and result as
@@ -699,14 +710,9 @@ def spacetime_distributions_multi(cells, species, grid, df, bins, opts=None, dev
     res = {k: np.zeros(v) for k, v in shapes.items() if k != "dN_dy_cell" or per_cell}
     so = SpacetimeOut(*[res[k].ctypes.data if k in res else None for k in SPACETIME_OUTPUTS])
     b = _spacetime_bins(bins)
-    if devices is None or isinstance(devices, (int, np.integer)):
-        nd, dv = int(devices or 0), None
-    else:
-        nd = len(devices)
-        dv = (C.c_int32 * max(nd, 1))(*[int(d) for d in devices])
+    dv, nd, n_stats = _pack_devices(devices)
     st = SpacetimeStats()
-    n_stats = nd if nd > 0 else max(L.is3d_device_count(), 1)
-    sst = (SpacetimeStats * max(n_stats, 1))()
+    sst = (SpacetimeStats * n_stats)()
     fqs = _pack_feqmod(fq, keep) if fq is not None else None
     xp, yp = (_p(xa) if xa is not None else None), (_p(ya) if ya is not None else None)
     rc = L.is3d_spacetime_distributions_multi(C.byref(cs), xp, yp, C.byref(sps), C.byref(gs), _p(pw), _p(fw), C.byref(ds),
@@ -810,14 +816,9 @@ def spin_polarization_multi(cells, vorticity, species, grid, T, opts=None, devic
     vs = _host_vorticity(vorticity, cs.n_cells, held)
     res = {k: np.zeros(nout) for k in POLARIZATION_OUTPUTS}
     po = PolarizationOut(*[res[k].ctypes.data for k in POLARIZATION_OUTPUTS])
-    if devices is None or isinstance(devices, (int, np.integer)):
-        nd, dv = int(devices or 0), None
-    else:
-        nd = len(devices)
-        dv = (C.c_int32 * max(nd, 1))(*[int(d) for d in devices])
+    dv, nd, n_stats = _pack_devices(devices)
     st = PolarizationStats()
-    n_stats = nd if nd > 0 else max(L.is3d_device_count(), 1)
-    sst = (PolarizationStats * max(n_stats, 1))()
+    sst = (PolarizationStats * n_stats)()
     rc = L.is3d_spin_polarization_multi(C.byref(cs), C.byref(vs) if vs is not None else None, C.byref(sps), C.byref(gs), float(T), C.byref(os_),
                                         dv, nd, C.byref(po), C.byref(st), sst)
     stats, shard_stats = st.as_dict(), [sst[i].as_dict() for i in range(n_stats)]
@@ -1000,15 +1001,14 @@ def smooth_spectra_multi(cells, species, grid, df, opts=None, devices=None, redu
     if out is None:
         out = np.zeros(nout)
     assert out.dtype == np.float64 and out.size == nout and out.flags.c_contiguous
-    nd = len(devices) if devices is not None else 0
-    dv = (C.c_int32 * nd)(*[int(d) for d in devices]) if nd else None
+    dv, nd, n_stats = _pack_devices(devices)
     st = Status()
-    sst = (Status * max(nd, L.is3d_device_count(), 1))()
+    sst = (Status * n_stats)()
     fqs = _pack_feqmod(fq, keep) if fq is not None else None
     rc = L.is3d_smooth_spectra_multi(C.byref(cs), C.byref(sps), C.byref(gs), C.byref(ds), C.byref(fqs) if fqs is not None else None,
                                      C.byref(os_), dv, nd, int(reduce), _p(out), C.byref(st), sst)
     _check(rc)
-    return out, st.as_dict(), [sst[i].as_dict() for i in range(nd or L.is3d_device_count())]
+    return out, st.as_dict(), [sst[i].as_dict() for i in range(n_stats)]
 
 
 class MultiPlan:
@@ -1018,8 +1018,7 @@ class MultiPlan:
     def __init__(self, species, grid, df, opts=None, devices=None, reduce=REDUCE_ORDERED, max_cells=1, fq=None):
         L = load()
         sps, gs, ds, os_, self.output_size, self._keep = _pack_common(species, grid, df, opts)
-        nd = len(devices) if devices is not None else 0
-        dv = (C.c_int32 * nd)(*[int(d) for d in devices]) if nd else None
+        dv, nd, _ = _pack_devices(devices)
         fqs = _pack_feqmod(fq, self._keep) if fq is not None else None
         self._h = C.c_void_p()
         _check(L.is3d_multi_plan_create(C.byref(self._h), C.byref(sps), C.byref(gs), C.byref(ds), C.byref(fqs) if fqs is not None else None,
@@ -1464,13 +1463,13 @@ def sample_particles(cells, species, df, gla, opts=None, n_events=1, seed=1, y_c
     st = SamplerStats()
     cnt = C.c_int64(0)
     if devices is not None:   # is3d_sample_particles_multi: one cell shard per listed device (an ordinal may repeat)
-        dv = (C.c_int32 * len(devices))(*[int(d) for d in devices])
+        dv, nd, _ = _pack_devices(devices)
         L.is3d_sample_particles_multi.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs),
                                                   C.POINTER(Options), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int64,
                                                   C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
 
         def call(buf, cap):
-            return L.is3d_sample_particles_multi(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), dv, len(devices), buf, cap,
+            return L.is3d_sample_particles_multi(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), dv, nd, buf, cap,
                                                  C.byref(cnt), C.byref(st))
     else:
         def call(buf, cap):
@@ -1700,11 +1699,11 @@ def sample_binned(cells, species, df, gla, bins, opts=None, n_events=1, seed=1, 
     st = SamplerStats()
     cnt = C.c_int64(0)
     if devices is not None:
-        dv = (C.c_int32 * len(devices))(*[int(d) for d in devices])
+        dv, nd, _ = _pack_devices(devices)
         L.is3d_sample_binned_multi.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options),
                                                C.POINTER(C.c_int32), C.c_int32, C.POINTER(SamplerTestBins), C.POINTER(SamplerHist),
                                                C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
-        rc = L.is3d_sample_binned_multi(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), dv, len(devices), C.byref(b), C.byref(h),
+        rc = L.is3d_sample_binned_multi(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), dv, nd, C.byref(b), C.byref(h),
                                         C.byref(cnt), C.byref(st))
     else:
         L.is3d_sample_binned.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options),

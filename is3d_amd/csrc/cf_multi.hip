@@ -491,32 +491,154 @@ extern "C" int is3d_plan_execute_allreduce(is3d_plan *plan, const is3d_cells *sh
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-// everything a shard owns for the life of a multi-device plan
-struct Shard {
+// ---- what the multi-device entries share: resolve_devices, assign_shards, run_shards, first_error, then each entry's own combine ----
+
+// The device list of a multi-device entry: devices == NULL stands for the ordinals 0 .. n_devices - 1, n_devices <= 0 for every visible
+// device; an ordinal may repeat.  What the list alone decides is refused first, so that it is IS3D_EINVAL with or without a device.
+int resolve_devices(const int32_t *devices, int32_t n_devices, std::vector<int> &dev)
+{
+    if (n_devices > 1024) return fail(IS3D_EINVAL, "n_devices = %d (up to 1024 shards)", n_devices);
+    if (devices)
+        for (int i = 0; i < n_devices; i++)
+            if (devices[i] < 0) return fail(IS3D_EINVAL, "devices[%d] = %d: a device ordinal cannot be negative", i, devices[i]);
+    const int visible = is3d_device_count();
+    if (!devices && n_devices > visible)
+        return fail(IS3D_EINVAL, "n_devices = %d with devices == NULL asks for the ordinals 0..%d, but %d HIP device%s visible", n_devices,
+                    n_devices - 1, visible, visible == 1 ? " is" : "s are");
+    if (visible < 1) return fail(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
+    if (n_devices <= 0) { n_devices = visible; devices = nullptr; }
+    dev.resize(n_devices);
+    for (int i = 0; i < n_devices; i++) {
+        dev[i] = devices ? devices[i] : i;
+        if (dev[i] >= visible) return fail(IS3D_EINVAL, "devices[%d] = %d is not one of the %d visible HIP devices", i, dev[i], visible);
+    }
+    return IS3D_OK;
+}
+
+// what every shard record starts with: its device, its cells [lo, hi) of the surface, how its run ended
+struct ShardBase {
     int device = 0;
-    int64_t cap = 0;                   // cells this shard's plan, device block and staging block are sized for
-    int64_t lo = 0, hi = 0;            // its cells in the current execute
-    is3d_plan *plan = nullptr;
-    double *d_cells = nullptr, *d_out = nullptr, *d_tmp = nullptr;   // d_tmp: the partner's spectrum in a round of the tree sum
-    hipStream_t stream = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr, e_sum = nullptr;
-    is3d_status st{};
+    int64_t lo = 0, hi = 0;
     int rc = IS3D_OK;
     std::string err;
 };
+bool every_shard(const ShardBase &) { return true; }
+bool has_cells(const ShardBase &s) { return s.hi > s.lo; }
 
-void shard_release(Shard &s)
+// shard i on dev[i] with the cells is3d_shard_bounds gives it; returns how many shards have cells
+template <class S>
+int assign_shards(std::vector<S> &sh, const std::vector<int> &dev, int64_t n_cells)
 {
-    (void)hipSetDevice(s.device);
-    if (s.plan) is3d_plan_destroy(s.plan);
-    if (s.d_cells) (void)hipFree(s.d_cells);
-    if (s.d_out) (void)hipFree(s.d_out);
-    if (s.d_tmp) (void)hipFree(s.d_tmp);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-    for (hipEvent_t e : {s.e0, s.e1, s.e_sum})
-        if (e) (void)hipEventDestroy(e);
-    s = Shard{};
+    int n_active = 0;
+    for (size_t i = 0; i < sh.size(); i++) {
+        sh[i].device = dev[i];
+        (void)is3d_shard_bounds(n_cells, (int32_t)i, (int32_t)sh.size(), &sh[i].lo, &sh[i].hi);
+        sh[i].rc = IS3D_OK;
+        sh[i].err.clear();
+        if (has_cells(sh[i])) n_active++;
+    }
+    return n_active;
 }
+
+// fn(i) for every shard that `pick` selects, concurrently on one host thread each (a lone one on the calling thread); a shard keeps its
+// return code and, the error text being thread-local, the text.  A failed shard does not stop the others
+template <class S, class Fn>
+void run_shards(std::vector<S> &sh, bool (*pick)(const ShardBase &), Fn fn)
+{
+    auto run = [&](int i) {
+        sh[i].rc = fn(i);
+        if (sh[i].rc) sh[i].err = is3d_last_error();
+    };
+    std::vector<int> picked;
+    for (size_t i = 0; i < sh.size(); i++)
+        if (pick(sh[i])) picked.push_back((int)i);
+    if (picked.size() == 1) {
+        run(picked[0]);
+        return;
+    }
+    std::vector<std::thread> th;
+    for (int i : picked) th.emplace_back(run, i);
+    for (auto &t : th) t.join();
+}
+
+// the first failed shard wins: its code and "shard i (device d): its text"; IS3D_OK when every shard succeeded
+template <class S>
+void first_error(const std::vector<S> &sh, int *rc, std::string *text)
+{
+    *rc = IS3D_OK;
+    for (size_t i = 0; i < sh.size() && !*rc; i++)
+        if (sh[i].rc) {
+            *rc = sh[i].rc;
+            *text = "shard " + std::to_string(i) + " (device " + std::to_string(sh[i].device) + "): " + sh[i].err;
+        }
+}
+
+// a shard's first bad cell (shard-local, -1: none) as an index of the whole surface; the lowest one is kept
+void keep_lowest_bad_cell(int64_t &global, const ShardBase &s, int64_t bad_cell)
+{
+    if (bad_cell >= 0 && (global < 0 || s.lo + bad_cell < global)) global = s.lo + bad_cell;
+}
+
+// the calling thread's current device, put back at the end of the scope (declared ahead of the shards, so restored after their release)
+struct DeviceRestore {
+    int d = -1;
+    DeviceRestore() { if (hipGetDevice(&d) != hipSuccess) { d = -1; (void)hipGetLastError(); } }
+    DeviceRestore(const DeviceRestore &) = delete;
+    ~DeviceRestore() { if (d >= 0) (void)hipSetDevice(d); }
+};
+
+// a non-blocking stream of `device` (current at create), destroyed there
+struct Stream {
+    hipStream_t s = nullptr;
+    int device = 0;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    hipError_t create(int dev) { device = dev; return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    ~Stream() { if (s) { (void)hipSetDevice(device); (void)hipStreamDestroy(s); } }
+    operator hipStream_t() const { return s; }
+};
+
+// events of the current device; add(n) appends n of them
+struct Events {
+    std::vector<hipEvent_t> e;
+    Events() = default;
+    Events(const Events &) = delete;
+    hipError_t add(size_t n, unsigned flags = hipEventDefault)
+    {
+        for (; n; n--) {
+            e.push_back(nullptr);
+            const hipError_t r = hipEventCreateWithFlags(&e.back(), flags);
+            if (r != hipSuccess) return r;
+        }
+        return hipSuccess;
+    }
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    hipEvent_t operator[](size_t i) const { return e[i]; }
+};
+
+// a shard's partial result to its place on the device that combines them, on a stream of that device: a copy inside one device, a peer copy
+// between two
+hipError_t place_on(double *dst, int dst_device, const double *src, int src_device, size_t count, hipStream_t stream)
+{
+    if (src_device == dst_device) return hipMemcpyAsync(dst, src, sizeof(double) * count, hipMemcpyDeviceToDevice, stream);
+    return hipMemcpyPeerAsync(dst, dst_device, src, src_device, sizeof(double) * count, stream);
+}
+
+// ---- the Cooper-Frye spectrum (is3d_multi_plan_*, is3d_smooth_spectra_multi) ----
+// everything a shard owns for the life of a multi-device plan
+struct Shard : ShardBase {
+    int64_t cap = 0;                   // cells this shard's plan and device block are sized for
+    is3d_plan *plan = nullptr;
+    is3d::DevBuf<double> d_cells, d_out, d_tmp;   // d_tmp: the partner's spectrum in a round of the tree sum
+    Stream stream;
+    Events ev;                         // [0], [1]: around an upload or the reduction; [2]: this shard's round of the tree sum is enqueued
+    is3d_status st{};
+    ~Shard()
+    {
+        (void)hipSetDevice(device);
+        if (plan) is3d_plan_destroy(plan);
+    }
+};
 
 // communicators of IS3D_REDUCE_RCCL are kept for the life of the process, keyed by the device list (creating one costs ~0.1-1 s)
 struct CommSet { std::vector<int> devices; std::vector<ncclComm_t> comms; };
@@ -549,18 +671,14 @@ int commset_for(const std::vector<int> &devs, CommSet **out)
 }  // namespace
 
 struct is3d_multi_plan {
-    std::vector<Shard> sh;
+    std::vector<int> dev;
+    std::vector<Shard> sh;             // sized once: a shard is neither copied nor moved
     int reduce = IS3D_REDUCE_ORDERED;
     int64_t max_cells = 0, nout = 0;
     bool diff = false, accumulate = false;
-    int n_arrays = 18;                 // cell arrays a shard uploads (23 with baryon diffusion)
     CommSet *comms = nullptr;
     std::vector<double> h_acc;         // accumulate: the device sum lands here first
-
-    ~is3d_multi_plan()
-    {
-        for (auto &s : sh) shard_release(s);
-    }
+    explicit is3d_multi_plan(const std::vector<int> &d) : dev(d), sh(d.size()) {}
 };
 
 namespace {
@@ -576,14 +694,12 @@ int shard_create(Shard &s, const is3d_species *sp, const is3d_grid *grid, const 
     if (rc) return rc;
     (void)is3d_plan_set_timing(s.plan, 1);
     const int64_t nout = is3d_plan_output_size(s.plan);
-    HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc((void **)&s.d_cells, sizeof(double) * is3d::kCellArrays * (size_t)s.cap));
-    HIP_TRY(hipMalloc((void **)&s.d_out, sizeof(double) * (size_t)nout));
-    if (need_tmp) HIP_TRY(hipMalloc((void **)&s.d_tmp, sizeof(double) * (size_t)nout));
-    for (int k = 0; k < (need_tmp ? 3 : 2); k++) is3d::count_resource(1);
-    HIP_TRY(hipEventCreate(&s.e0));
-    HIP_TRY(hipEventCreate(&s.e1));
-    HIP_TRY(hipEventCreateWithFlags(&s.e_sum, hipEventDisableTiming));
+    HIP_TRY(s.stream.create(s.device));
+    HIP_TRY(s.d_cells.alloc(is3d::kCellArrays * (size_t)s.cap));
+    HIP_TRY(s.d_out.alloc((size_t)nout));
+    if (need_tmp) HIP_TRY(s.d_tmp.alloc((size_t)nout));
+    HIP_TRY(s.ev.add(2));
+    HIP_TRY(s.ev.add(1, hipEventDisableTiming));
     return IS3D_OK;
 }
 
@@ -594,17 +710,17 @@ int shard_run(Shard &s, const is3d_cells *cells, bool diff)
 {
     HIP_TRY(hipSetDevice(s.device));
     const int64_t n = s.hi - s.lo;
-    HIP_TRY(hipEventRecord(s.e0, s.stream));
+    HIP_TRY(hipEventRecord(s.ev[0], s.stream));
     is3d_cells dc;
-    HIP_TRY(is3d::stage_cells(*cells, [diff](int a) { return a < 18 || diff; }, s.lo, n, s.d_cells, s.stream, &dc));
-    HIP_TRY(hipEventRecord(s.e1, s.stream));
-    const int rc = is3d_plan_execute(s.plan, &dc, s.d_out, s.stream, &s.st);
+    HIP_TRY(is3d::stage_cells(*cells, [diff](int a) { return a < 18 || diff; }, s.lo, n, s.d_cells.p, s.stream, &dc));
+    HIP_TRY(hipEventRecord(s.ev[1], s.stream));
+    const int rc = is3d_plan_execute(s.plan, &dc, s.d_out.p, s.stream, &s.st);
     if (rc) return rc;
     is3d_status t{};
     (void)is3d_plan_timings(s.plan, &t);
     s.st.ms_prep = t.ms_prep; s.st.ms_main = t.ms_main; s.st.ms_finalize = t.ms_finalize;
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, s.e0, s.e1));
+    HIP_TRY(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]));
     s.st.ms_h2d = ms;
     return IS3D_OK;
 }
@@ -614,7 +730,7 @@ int rccl_allreduce_shards(std::vector<Shard> &sh, CommSet *cs, int64_t nout)
     NCCL_TRY(rccl().GroupStart());
     for (size_t i = 0; i < sh.size(); i++) {
         (void)hipSetDevice(sh[i].device);
-        ncclResult_t r = rccl().AllReduce(sh[i].d_out, sh[i].d_out, (size_t)nout, ncclDouble, ncclSum, cs->comms[i], sh[i].stream);
+        ncclResult_t r = rccl().AllReduce(sh[i].d_out.p, sh[i].d_out.p, (size_t)nout, ncclDouble, ncclSum, cs->comms[i], sh[i].stream);
         if (r != ncclSuccess) {
             (void)rccl().GroupEnd();
             return fail(IS3D_ENODEVICE, "ncclAllReduce failed: %s", rccl().GetErrorString(r));
@@ -638,32 +754,18 @@ int tree_sum_shards(std::vector<Shard> &sh, int64_t nout)
         for (size_t i = 0; i + stride < n; i += 2 * stride) {
             Shard &dst = sh[i], &src = sh[i + stride];
             HIP_TRY(hipSetDevice(dst.device));
-            if (stride > 1) HIP_TRY(hipStreamWaitEvent(dst.stream, src.e_sum, 0));   // round 0: every shard's stream is already synchronised
-            const double *from = src.d_out;
-            if (src.device != dst.device) {
-                HIP_TRY(hipMemcpyPeerAsync(dst.d_tmp, dst.device, src.d_out, src.device, sizeof(double) * (size_t)nout, dst.stream));
-                from = dst.d_tmp;
+            if (stride > 1) HIP_TRY(hipStreamWaitEvent(dst.stream, src.ev[2], 0));   // round 0: every shard's stream is already synchronised
+            const double *from = src.d_out.p;
+            if (src.device != dst.device) {   // a partner on the same device is read where it lies
+                HIP_TRY(place_on(dst.d_tmp.p, dst.device, src.d_out.p, src.device, (size_t)nout, dst.stream));
+                from = dst.d_tmp.p;
             }
-            HIP_TRY(launch_add_spectrum(dst.d_out, from, nout, dst.stream));
-            HIP_TRY(hipEventRecord(dst.e_sum, dst.stream));
+            HIP_TRY(launch_add_spectrum(dst.d_out.p, from, nout, dst.stream));
+            HIP_TRY(hipEventRecord(dst.ev[2], dst.stream));
         }
     }
     HIP_TRY(hipSetDevice(sh[0].device));
     HIP_TRY(hipStreamSynchronize(sh[0].stream));
-    return IS3D_OK;
-}
-
-int check_devices(const int32_t *devices, int32_t &n_devices, std::vector<int> &dev)
-{
-    const int visible = is3d_device_count();
-    if (visible < 1) return fail(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
-    if (n_devices <= 0) { n_devices = visible; devices = nullptr; }
-    if (n_devices > 1024) return fail(IS3D_EINVAL, "n_devices = %d", n_devices);
-    dev.resize(n_devices);
-    for (int i = 0; i < n_devices; i++) {
-        dev[i] = devices ? devices[i] : i;
-        if (dev[i] < 0 || dev[i] >= visible) return fail(IS3D_EINVAL, "device %d is not one of the %d visible HIP devices", dev[i], visible);
-    }
     return IS3D_OK;
 }
 
@@ -678,19 +780,21 @@ extern "C" int is3d_multi_plan_create(is3d_multi_plan **out, const is3d_species 
     if (reduce != IS3D_REDUCE_ORDERED && reduce != IS3D_REDUCE_RCCL) return fail(IS3D_EINVAL, "reduce must be IS3D_REDUCE_ORDERED or IS3D_REDUCE_RCCL");
     if (max_cells < 0) return fail(IS3D_EINVAL, "max_cells < 0");
     std::vector<int> dev;
-    if (int rc = check_devices(devices, n_devices, dev)) return rc;
-    std::unique_ptr<is3d_multi_plan> M(new is3d_multi_plan);
+    if (int rc = resolve_devices(devices, n_devices, dev)) return rc;
+    n_devices = (int32_t)dev.size();
+    std::unique_ptr<is3d_multi_plan> M(new is3d_multi_plan(dev));
+    DeviceRestore restore;   // creating a plan leaves the caller's current device alone (a failed one is released after the restore, as ever)
     M->reduce = reduce;
     M->max_cells = max_cells;
     M->accumulate = opts->accumulate != 0;
     M->diff = opts->include_baryon && opts->include_baryondiff_deltaf;
-    M->sh.resize(n_devices);
     if (reduce == IS3D_REDUCE_RCCL && n_devices > 1)
         if (int rc = commset_for(dev, &M->comms)) return rc;
-    for (int i = 0; i < n_devices; i++) {
-        M->sh[i].device = dev[i];
-        M->sh[i].cap = std::max<int64_t>((max_cells + n_devices - 1) / n_devices, 1);
-        M->sh[i].st.bad_cell = -1;
+    std::vector<Shard> &sh = M->sh;
+    assign_shards(sh, dev, max_cells);
+    for (auto &s : sh) {
+        s.cap = std::max<int64_t>((max_cells + n_devices - 1) / n_devices, 1);
+        s.st.bad_cell = -1;
     }
     // a shard needs a receive buffer if it takes a partner from another device in some round of the tree
     std::vector<char> need_tmp(n_devices, 0);
@@ -698,19 +802,12 @@ extern "C" int is3d_multi_plan_create(is3d_multi_plan **out, const is3d_species 
         for (int stride = 1; stride < n_devices; stride *= 2)
             for (int i = 0; i + stride < n_devices; i += 2 * stride)
                 if (dev[i] != dev[i + stride]) need_tmp[i] = 1;
-    {
-        std::vector<std::thread> th;
-        for (int i = 0; i < n_devices; i++)
-            th.emplace_back([&, i] {
-                Shard &s = M->sh[i];
-                s.rc = shard_create(s, species, grid, df, fq, opts, need_tmp[i] != 0);
-                if (s.rc) s.err = is3d_last_error();
-            });
-        for (auto &t : th) t.join();
-    }
-    for (int i = 0; i < n_devices; i++)
-        if (M->sh[i].rc) return fail(M->sh[i].rc, "shard %d (device %d): %s", i, M->sh[i].device, M->sh[i].err.c_str());
-    M->nout = is3d_plan_output_size(M->sh[0].plan);
+    run_shards(sh, every_shard, [&](int i) { return shard_create(sh[i], species, grid, df, fq, opts, need_tmp[i] != 0); });
+    int rc;
+    std::string text;
+    first_error(sh, &rc, &text);
+    if (rc) return fail(rc, "%s", text.c_str());
+    M->nout = is3d_plan_output_size(sh[0].plan);
     *out = M.release();
     return IS3D_OK;
 }
@@ -729,34 +826,21 @@ extern "C" int is3d_multi_plan_execute(is3d_multi_plan *M, const is3d_cells *cel
     if (cells->n_cells < 0 || cells->n_cells > M->max_cells)
         return fail(IS3D_EINVAL, "n_cells = %lld outside the multi-device plan's max_cells = %lld", (long long)cells->n_cells, (long long)M->max_cells);
     std::vector<Shard> &sh = M->sh;
-    for (int i = 0; i < n_devices; i++) {
-        (void)is3d_shard_bounds(cells->n_cells, i, n_devices, &sh[i].lo, &sh[i].hi);
-        sh[i].st = is3d_status{};
-        sh[i].st.bad_cell = -1;
-        sh[i].rc = IS3D_OK;
-        sh[i].err.clear();
+    assign_shards(sh, M->dev, cells->n_cells);
+    for (auto &s : sh) {
+        s.st = is3d_status{};
+        s.st.bad_cell = -1;
     }
-    if (n_devices == 1) {
-        sh[0].rc = shard_run(sh[0], cells, M->diff);
-        if (sh[0].rc) sh[0].err = is3d_last_error();
-    } else {
-        std::vector<std::thread> th;
-        for (int i = 0; i < n_devices; i++)
-            th.emplace_back([&, i] {
-                sh[i].rc = shard_run(sh[i], cells, M->diff);
-                if (sh[i].rc) sh[i].err = is3d_last_error();   // the error text is thread-local
-            });
-        for (auto &t : th) t.join();
-    }
+    run_shards(sh, every_shard, [&](int i) { return shard_run(sh[i], cells, M->diff); });   // the sum reads every shard's spectrum
     // aggregate (also on failure, so that the caller sees which cell was bad)
-    int rc_first = IS3D_OK;
+    int rc_first;
     std::string err_first;
+    first_error(sh, &rc_first, &err_first);
     is3d_status agg{};
     agg.bad_cell = -1;
     for (int i = 0; i < n_devices; i++) {
         const is3d_status &t = sh[i].st;
         if (shard_status) { shard_status[i] = t; shard_status[i].code = sh[i].rc; }
-        if (sh[i].rc && !rc_first) { rc_first = sh[i].rc; err_first = "shard " + std::to_string(i) + " (device " + std::to_string(sh[i].device) + "): " + sh[i].err; }
         agg.n_classes = std::max(agg.n_classes, t.n_classes);
         agg.n_cells_skipped += t.n_cells_skipped;
         agg.n_passes = std::max(agg.n_passes, t.n_passes);
@@ -769,7 +853,7 @@ extern "C" int is3d_multi_plan_execute(is3d_multi_plan *M, const is3d_cells *cel
         agg.n_wave_rows_culled += t.n_wave_rows_culled;
         agg.n_cells_breakdown += t.n_cells_breakdown;
         agg.n_cells_narrow += t.n_cells_narrow;
-        if (t.bad_cell >= 0 && (agg.bad_cell < 0 || sh[i].lo + t.bad_cell < agg.bad_cell)) agg.bad_cell = sh[i].lo + t.bad_cell;
+        keep_lowest_bad_cell(agg.bad_cell, sh[i], t.bad_cell);
     }
     agg.code = rc_first;
     if (rc_first) {
@@ -777,24 +861,25 @@ extern "C" int is3d_multi_plan_execute(is3d_multi_plan *M, const is3d_cells *cel
         return fail(rc_first, "%s", err_first.c_str());
     }
     const int64_t nout = M->nout;
-    HIP_TRY(hipSetDevice(sh[0].device));
-    HIP_TRY(hipEventRecord(sh[0].e0, sh[0].stream));
+    Shard &s0 = sh[0];
+    HIP_TRY(hipSetDevice(s0.device));
+    HIP_TRY(hipEventRecord(s0.ev[0], s0.stream));
     int rc = IS3D_OK;
     if (n_devices > 1) rc = (M->reduce == IS3D_REDUCE_RCCL) ? rccl_allreduce_shards(sh, M->comms, nout) : tree_sum_shards(sh, nout);
     if (rc) { agg.code = rc; if (status) *status = agg; return rc; }
-    HIP_TRY(hipSetDevice(sh[0].device));
+    HIP_TRY(hipSetDevice(s0.device));
     if (M->accumulate) {   // reference semantics: dN += result (smooth_kernels.cpp:375)
         M->h_acc.resize((size_t)nout);
-        HIP_TRY(hipMemcpyAsync(M->h_acc.data(), sh[0].d_out, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, sh[0].stream));
-        HIP_TRY(hipStreamSynchronize(sh[0].stream));
+        HIP_TRY(hipMemcpyAsync(M->h_acc.data(), s0.d_out.p, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, s0.stream));
+        HIP_TRY(hipStreamSynchronize(s0.stream));
         for (int64_t i = 0; i < nout; i++) dN_out[i] += M->h_acc[(size_t)i];
     } else {
-        HIP_TRY(hipMemcpyAsync(dN_out, sh[0].d_out, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, sh[0].stream));
+        HIP_TRY(hipMemcpyAsync(dN_out, s0.d_out.p, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, s0.stream));
     }
-    HIP_TRY(hipEventRecord(sh[0].e1, sh[0].stream));
-    HIP_TRY(hipEventSynchronize(sh[0].e1));
+    HIP_TRY(hipEventRecord(s0.ev[1], s0.stream));
+    HIP_TRY(hipEventSynchronize(s0.ev[1]));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, sh[0].e0, sh[0].e1));
+    HIP_TRY(hipEventElapsedTime(&ms, s0.ev[0], s0.ev[1]));
     agg.ms_d2h = ms;
     if (status) *status = agg;
     return IS3D_OK;
@@ -809,7 +894,8 @@ extern "C" int is3d_smooth_spectra_multi(const is3d_cells *cells, const is3d_spe
     if (reduce != IS3D_REDUCE_ORDERED && reduce != IS3D_REDUCE_RCCL) return fail(IS3D_EINVAL, "reduce must be IS3D_REDUCE_ORDERED or IS3D_REDUCE_RCCL");
     if (cells->n_cells < 0) return fail(IS3D_EINVAL, "n_cells < 0");
     std::vector<int> dev;
-    if (int rc = check_devices(devices, n_devices, dev)) return rc;
+    if (int rc = resolve_devices(devices, n_devices, dev)) return rc;
+    n_devices = (int32_t)dev.size();
     if (status) { memset(status, 0, sizeof *status); status->bad_cell = -1; }
     if (shard_status) memset(shard_status, 0, sizeof(is3d_status) * (size_t)n_devices);
 
@@ -838,47 +924,53 @@ extern "C" int is3d_smooth_spectra_multi(const is3d_cells *cells, const is3d_spe
 // particle sampler over several devices
 // ------------------------------------------------------------------------------------------------
 namespace {
-// the device list of the sampler's multi entries: n_devices <= 0 = every visible device; an ordinal may repeat
-int sampler_devices(const int32_t *devices, int32_t n_devices, std::vector<int> &dev)
+// a shard of the sampler's multi entries: [lo, hi) of a host surface as the arguments of a single-device call on `device` -- the cell arrays
+// and x, y advanced to lo, first_cell with them -- and what that call reports
+struct SamplerShard : ShardBase {
+    is3d_cells c;
+    is3d_sampler_inputs si;
+    is3d_options o;
+    int64_t count = 0;
+    is3d_sampler_stats st{};
+};
+void sampler_shard(SamplerShard &s, const is3d_cells *cells, const is3d_sampler_inputs *in, const is3d_options *opts)
 {
-    const int visible = is3d_device_count();
-    if (visible < 1) return fail(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
-    if (n_devices <= 0) { n_devices = visible; devices = nullptr; }
-    if (n_devices > 1024) return fail(IS3D_EINVAL, "n_devices = %d", n_devices);
-    dev.resize(n_devices);
-    for (int i = 0; i < n_devices; i++) {
-        dev[i] = devices ? devices[i] : i;
-        if (dev[i] < 0 || dev[i] >= visible) return fail(IS3D_EINVAL, "device %d is not one of the %d visible HIP devices", dev[i], visible);
-    }
-    return IS3D_OK;
-}
-// shard [lo, hi) of a host surface on `device`: the cell arrays and x, y advanced to lo, first_cell with them
-void sampler_shard(const is3d_cells *cells, const is3d_sampler_inputs *in, const is3d_options *opts, int64_t lo, int64_t hi, int device,
-                   is3d_cells *c, is3d_sampler_inputs *si, is3d_options *o)
-{
-    *c = *cells;
-    c->n_cells = hi - lo;
-    const double **fields[] = {&c->tau, &c->eta, &c->dat, &c->dax, &c->day, &c->dan, &c->ux, &c->uy, &c->un, &c->T, &c->P, &c->E, &c->pixx, &c->pixy,
-                               &c->pixn, &c->piyy, &c->piyn, &c->bulkPi, &c->muB, &c->nB, &c->Vx, &c->Vy, &c->Vn};
+    s.c = *cells;
+    s.c.n_cells = s.hi - s.lo;
+    is3d_cells &c = s.c;
+    const double **fields[] = {&c.tau, &c.eta, &c.dat, &c.dax, &c.day, &c.dan, &c.ux, &c.uy, &c.un, &c.T, &c.P, &c.E, &c.pixx, &c.pixy,
+                               &c.pixn, &c.piyy, &c.piyn, &c.bulkPi, &c.muB, &c.nB, &c.Vx, &c.Vy, &c.Vn};
     for (auto f : fields)
-        if (*f) *f += lo;
-    *si = *in;
-    si->first_cell = in->first_cell + lo;
-    if (si->x) si->x += lo;
-    if (si->y) si->y += lo;
-    *o = *opts;
-    o->device = device;
+        if (*f) *f += s.lo;
+    s.si = *in;
+    s.si.first_cell = in->first_cell + s.lo;
+    if (s.si.x) s.si.x += s.lo;
+    if (s.si.y) s.si.y += s.lo;
+    s.o = *opts;
+    s.o.device = s.device;
 }
-// counts summed, times the slowest shard's
-void sampler_stats_add(is3d_sampler_stats &agg, const is3d_sampler_stats &t)
+// the first failed shard's error; else the hadron counts summed, the other counters summed and the times the slowest shard's
+template <class S>
+int sampler_totals(const std::vector<S> &sh, int64_t *n_particles, is3d_sampler_stats *stats)
 {
-    agg.n_cells_skipped += t.n_cells_skipped; agg.n_hadrons_drawn += t.n_hadrons_drawn;
-    agg.n_momentum_samples += t.n_momentum_samples; agg.n_acceptances += t.n_acceptances;
-    agg.n_classes = std::max(agg.n_classes, t.n_classes); agg.n_cells_breakdown += t.n_cells_breakdown;
-    agg.ms_h2d = std::max(agg.ms_h2d, t.ms_h2d); agg.ms_prep = std::max(agg.ms_prep, t.ms_prep);
-    agg.ms_count = std::max(agg.ms_count, t.ms_count); agg.ms_fill = std::max(agg.ms_fill, t.ms_fill);
-    agg.ms_bin = std::max(agg.ms_bin, t.ms_bin);
-    agg.particle_workspace_bytes = std::max(agg.particle_workspace_bytes, t.particle_workspace_bytes);
+    int rc;
+    std::string text;
+    first_error(sh, &rc, &text);
+    if (rc) return fail(rc, "%s", text.c_str());
+    is3d_sampler_stats agg{};
+    for (const S &s : sh) {
+        const is3d_sampler_stats &t = s.st;
+        *n_particles += s.count;
+        agg.n_cells_skipped += t.n_cells_skipped; agg.n_hadrons_drawn += t.n_hadrons_drawn;
+        agg.n_momentum_samples += t.n_momentum_samples; agg.n_acceptances += t.n_acceptances;
+        agg.n_classes = std::max(agg.n_classes, t.n_classes); agg.n_cells_breakdown += t.n_cells_breakdown;
+        agg.ms_h2d = std::max(agg.ms_h2d, t.ms_h2d); agg.ms_prep = std::max(agg.ms_prep, t.ms_prep);
+        agg.ms_count = std::max(agg.ms_count, t.ms_count); agg.ms_fill = std::max(agg.ms_fill, t.ms_fill);
+        agg.ms_bin = std::max(agg.ms_bin, t.ms_bin);
+        agg.particle_workspace_bytes = std::max(agg.particle_workspace_bytes, t.particle_workspace_bytes);
+    }
+    if (stats) *stats = agg;
+    return IS3D_OK;
 }
 }  // namespace
 
@@ -892,7 +984,7 @@ extern "C" int is3d_sample_particles_multi(const is3d_cells *cells, const is3d_s
     if (stats) memset(stats, 0, sizeof *stats);
     if (cells->n_cells < 0) return fail(IS3D_EINVAL, "n_cells < 0");
     std::vector<int> dev;
-    if (int rc = sampler_devices(devices, n_devices, dev)) return rc;
+    if (int rc = resolve_devices(devices, n_devices, dev)) return rc;
     n_devices = (int32_t)dev.size();
     if (particles == nullptr) capacity = 0;
     if (n_devices == 1) {
@@ -900,46 +992,23 @@ extern "C" int is3d_sample_particles_multi(const is3d_cells *cells, const is3d_s
         o.device = dev[0];
         return is3d_sample_particles(cells, species, df, in, &o, particles, capacity, n_particles, stats);
     }
-    struct SShard {
-        int device = 0;
-        int64_t lo = 0, hi = 0, count = 0;
-        std::vector<is3d_particle> list;
-        is3d_sampler_stats st{};
-        int rc = IS3D_OK;
-        std::string err;
-    };
+    struct SShard : SamplerShard { std::vector<is3d_particle> list; };
+    DeviceRestore restore;
     std::vector<SShard> sh(n_devices);
+    const int n_active = assign_shards(sh, dev, cells->n_cells);
     const bool fill = capacity > 0;
-    {
-        std::vector<std::thread> th;
-        for (int i = 0; i < n_devices; i++) {
-            sh[i].device = dev[i];
-            (void)is3d_shard_bounds(cells->n_cells, i, n_devices, &sh[i].lo, &sh[i].hi);
-            th.emplace_back([&, i] {
-                SShard &s = sh[i];
-                is3d_cells c;
-                is3d_sampler_inputs si;
-                is3d_options o;
-                sampler_shard(cells, in, opts, s.lo, s.hi, s.device, &c, &si, &o);
-                s.rc = is3d_sample_particles(&c, species, df, &si, &o, nullptr, 0, &s.count, &s.st);
-                if (!s.rc && fill && s.count > 0) {
-                    s.list.resize((size_t)s.count);
-                    s.rc = is3d_sample_particles(&c, species, df, &si, &o, s.list.data(), s.count, &s.count, &s.st);
-                }
-                if (s.rc) s.err = is3d_last_error();
-            });
+    // (an empty surface: every shard still makes its empty call, for the single-device entry's own checks and stats)
+    run_shards(sh, n_active ? has_cells : every_shard, [&](int i) {   // count, then fill a list of that size
+        SShard &s = sh[i];
+        sampler_shard(s, cells, in, opts);
+        int rc = is3d_sample_particles(&s.c, species, df, &s.si, &s.o, nullptr, 0, &s.count, &s.st);
+        if (!rc && fill && s.count > 0) {
+            s.list.resize((size_t)s.count);
+            rc = is3d_sample_particles(&s.c, species, df, &s.si, &s.o, s.list.data(), s.count, &s.count, &s.st);
         }
-        for (auto &t : th) t.join();
-    }
-    int64_t total = 0;
-    is3d_sampler_stats agg{};
-    for (int i = 0; i < n_devices; i++) {
-        if (sh[i].rc) return fail(sh[i].rc, "shard %d (device %d): %s", i, sh[i].device, sh[i].err.c_str());
-        total += sh[i].count;
-        sampler_stats_add(agg, sh[i].st);
-    }
-    *n_particles = total;
-    if (stats) *stats = agg;
+        return rc;
+    });
+    if (int rc = sampler_totals(sh, n_particles, stats)) return rc;
     if (!fill) return IS3D_OK;
     // merge: every shard list is ordered by (event, cell, draw) and the shards are ascending cell ranges, so the single-device order is,
     // event by event, shard 0's hadrons of that event, then shard 1's, ...
@@ -956,7 +1025,8 @@ extern "C" int is3d_sample_particles_multi(const is3d_cells *cells, const is3d_s
             }
             pos[i] = p;
         }
-    if (total > capacity) return fail(IS3D_ENOMEM, "particle buffer too small: %lld particles, capacity %lld", (long long)total, (long long)capacity);
+    if (*n_particles > capacity)
+        return fail(IS3D_ENOMEM, "particle buffer too small: %lld particles, capacity %lld", (long long)*n_particles, (long long)capacity);
     return IS3D_OK;
 }
 
@@ -972,7 +1042,7 @@ extern "C" int is3d_sample_binned_multi(const is3d_cells *cells, const is3d_spec
     if (stats) memset(stats, 0, sizeof *stats);
     if (cells->n_cells < 0) return fail(IS3D_EINVAL, "n_cells < 0");
     std::vector<int> dev;
-    if (int rc = sampler_devices(devices, n_devices, dev)) return rc;
+    if (int rc = resolve_devices(devices, n_devices, dev)) return rc;
     n_devices = (int32_t)dev.size();
     if (n_devices == 1) {
         is3d_options o = *opts;
@@ -989,52 +1059,30 @@ extern "C" int is3d_sample_binned_multi(const is3d_cells *cells, const is3d_spec
     int64_t *const out[8] = {hist->dN_dy, hist->dN_deta, hist->dN_pT, hist->dN_tau, hist->dN_r, hist->vn_re, hist->vn_im, hist->yield};
     int64_t words = 0;
     for (int a = 0; a < 8; a++) words += len[a];
-    struct BShard {
-        int device = 0;
-        int64_t lo = 0, hi = 0, count = 0;
-        std::vector<int64_t> h;
-        is3d_sampler_stats st{};
-        int rc = IS3D_OK;
-        std::string err;
-    };
+    struct BShard : SamplerShard { std::vector<int64_t> h; };
+    DeviceRestore restore;
     std::vector<BShard> sh(n_devices);
-    {
-        std::vector<std::thread> th;
-        for (int i = 0; i < n_devices; i++) {
-            sh[i].device = dev[i];
-            (void)is3d_shard_bounds(cells->n_cells, i, n_devices, &sh[i].lo, &sh[i].hi);
-            sh[i].h.assign((size_t)words, 0);
-            th.emplace_back([&, i] {
-                BShard &s = sh[i];
-                is3d_cells c;
-                is3d_sampler_inputs si;
-                is3d_options o;
-                sampler_shard(cells, in, opts, s.lo, s.hi, s.device, &c, &si, &o);
-                int64_t *q = s.h.data();
-                int64_t *part[8];
-                for (int a = 0; a < 8; a++) { part[a] = q; q += len[a]; }
-                const is3d_sampler_hist hs{part[0], part[1], part[2], part[3], part[4], part[5], part[6], part[7]};
-                s.rc = is3d_sample_binned(&c, species, df, &si, &o, bins, &hs, &s.count, &s.st);
-                if (s.rc) s.err = is3d_last_error();
-            });
-        }
-        for (auto &t : th) t.join();
-    }
-    is3d_sampler_stats agg{};
-    int64_t total = 0;
+    const int n_active = assign_shards(sh, dev, cells->n_cells);
+    run_shards(sh, n_active ? has_cells : every_shard, [&](int i) {   // (an empty surface: as in is3d_sample_particles_multi)
+        BShard &s = sh[i];
+        sampler_shard(s, cells, in, opts);
+        s.h.assign((size_t)words, 0);
+        int64_t *q = s.h.data();
+        int64_t *part[8];
+        for (int a = 0; a < 8; a++) { part[a] = q; q += len[a]; }
+        const is3d_sampler_hist hs{part[0], part[1], part[2], part[3], part[4], part[5], part[6], part[7]};
+        return is3d_sample_binned(&s.c, species, df, &s.si, &s.o, bins, &hs, &s.count, &s.st);
+    });
     for (int a = 0; a < 8; a++) memset(out[a], 0, (size_t)len[a] * sizeof(int64_t));
-    for (int i = 0; i < n_devices; i++) {
-        if (sh[i].rc) return fail(sh[i].rc, "shard %d (device %d): %s", i, sh[i].device, sh[i].err.c_str());
-        total += sh[i].count;
-        sampler_stats_add(agg, sh[i].st);
-        const int64_t *q = sh[i].h.data();
+    if (int rc = sampler_totals(sh, n_particles, stats)) return rc;
+    for (const BShard &s : sh) {
+        if (s.h.empty()) continue;   // a shard without cells made no call
+        const int64_t *q = s.h.data();
         for (int a = 0; a < 8; a++) {
             for (int64_t j = 0; j < len[a]; j++) out[a][j] += q[j];
             q += len[a];
         }
     }
-    *n_particles = total;
-    if (stats) *stats = agg;
     for (int64_t j = 0; j < len[2]; j++)
         if (hist->dN_pT[j] > IS3D_SAMPLER_VN_MAX_COUNT)
             return fail(IS3D_EDOMAIN, "dN_pT bin %lld holds %lld hadrons: the fixed-point harmonic sums are exact up to %lld per bin", (long long)j,
@@ -1069,21 +1117,16 @@ struct BoundExchange {
     }
 };
 
-struct StShard {
-    int device = 0;
-    int64_t lo = 0, hi = 0;
+struct StShard : ShardBase {
     is3d_plan *plan = nullptr;
-    hipStream_t stream = nullptr;
+    Stream stream;
     is3d::DevBuf<double> d_cells;
     is3d_spacetime_stats st{};
-    int rc = IS3D_OK;
-    std::string err;
     bool exchanged = false;
     ~StShard()
     {
         (void)hipSetDevice(device);
         if (plan) is3d_plan_destroy(plan);
-        if (stream) (void)hipStreamDestroy(stream);
     }
 };
 
@@ -1099,25 +1142,22 @@ int st_shard_run(StShard &s, const is3d_cells *cells, const is3d_species *specie
         const int rc = fq ? is3d_plan_create_feqmod(&s.plan, species, grid, df, fq, &o, n) : is3d_plan_create(&s.plan, species, grid, df, &o, n);
         if (rc) return rc;
     }
-    HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+    HIP_TRY(s.stream.create(s.device));
     HIP_TRY(s.d_cells.alloc((size_t)n * is3d::kCellArrays));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    struct EvGuard { hipEvent_t &a, &b; ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evg{e0, e1};
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    Events ev;
+    HIP_TRY(ev.add(2));
     const bool diff = opts->include_baryon && opts->include_baryondiff_deltaf;
-    HIP_TRY(hipEventRecord(e0, s.stream));
+    HIP_TRY(hipEventRecord(ev[0], s.stream));
     is3d_cells dc;
     HIP_TRY(is3d::stage_cells(*cells, [diff](int a) { return a < 18 || diff; }, s.lo, n, s.d_cells.p, s.stream, &dc));
-    HIP_TRY(hipEventRecord(e1, s.stream));
+    HIP_TRY(hipEventRecord(ev[1], s.stream));
     const int rc = is3d::spacetime_execute_split(s.plan, &dc, nullptr, nullptr, pT_w, phi_w, nullptr, nullptr, s.stream, &s.st, &split);
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) s.st.ms_h2d = ms;
+    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) s.st.ms_h2d = ms;
     else (void)hipGetLastError();
     return rc;
 }
-}  // namespace
 
-namespace {
 int st_multi_impl(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species, const is3d_grid *grid,
                   const double *pT_w, const double *phi_w, const is3d_df_tables *df, const is3d_feqmod_tables *fq, const is3d_options *opts,
                   const int32_t *devices, int32_t n_devices, const is3d_spacetime_bins *bins, is3d_spacetime_out *out,
@@ -1130,21 +1170,9 @@ int st_multi_impl(const is3d_cells *cells, const double *x, const double *y, con
     if (fq && opts->df_mode != 3 && opts->df_mode != 4)
         return fail(IS3D_EINVAL, "fq is given but df_mode is %d: the feqmod tables go with df_mode 3 or 4, pass fq = NULL for df_mode 1 or 2", opts->df_mode);
     if (int rc = is3d::spacetime_check_args(cells, x, y, species, grid, pT_w, phi_w, df, fq, opts, bins, out)) return rc;
-    if (n_devices > 1024) return fail(IS3D_EINVAL, "n_devices = %d (up to 1024 shards)", n_devices);
-    if (devices)
-        for (int i = 0; i < n_devices; i++)
-            if (devices[i] < 0) return fail(IS3D_EINVAL, "devices[%d] = %d: a device ordinal cannot be negative", i, devices[i]);
-    const int visible = is3d_device_count();
-    if (!devices && n_devices > visible)
-        return fail(IS3D_EINVAL, "n_devices = %d with devices == NULL asks for the ordinals 0..%d, but %d HIP device%s visible", n_devices,
-                    n_devices - 1, visible, visible == 1 ? " is" : "s are");
-    if (visible < 1) return fail(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
-    if (n_devices <= 0) { n_devices = visible; devices = nullptr; }
-    std::vector<int> dev(n_devices);
-    for (int i = 0; i < n_devices; i++) {
-        dev[i] = devices ? devices[i] : i;
-        if (dev[i] >= visible) return fail(IS3D_EINVAL, "devices[%d] = %d is not one of the %d visible HIP devices", i, dev[i], visible);
-    }
+    std::vector<int> dev;
+    if (int rc = resolve_devices(devices, n_devices, dev)) return rc;
+    n_devices = (int32_t)dev.size();
     if (shard_stats) {
         memset(shard_stats, 0, sizeof(is3d_spacetime_stats) * (size_t)n_devices);
         for (int i = 0; i < n_devices; i++) shard_stats[i].bad_cell = -1;
@@ -1164,19 +1192,12 @@ int st_multi_impl(const is3d_cells *cells, const double *x, const double *y, con
     }
 
     // ---- the shards; shard 0's plan lives on devices[0] and also serves the bin stage ----
-    // (declared ahead of the shards, so destroyed after them: the caller's thread gets its current device back)
-    struct DeviceRestore { int d = -1; ~DeviceRestore() { if (d >= 0) (void)hipSetDevice(d); } } restore;
-    if (hipGetDevice(&restore.d) != hipSuccess) { restore.d = -1; (void)hipGetLastError(); }
+    DeviceRestore restore;
     const int64_t n = cells->n_cells;
     const bool dim3 = opts->dimension == 3;
     std::vector<StShard> sh(n_devices);
-    int n_active = 0;
-    for (int i = 0; i < n_devices; i++) {
-        sh[i].device = dev[i];
-        sh[i].st.bad_cell = -1;
-        (void)is3d_shard_bounds(n, i, n_devices, &sh[i].lo, &sh[i].hi);
-        if (sh[i].hi > sh[i].lo) n_active++;
-    }
+    const int n_active = assign_shards(sh, dev, n);
+    for (auto &s : sh) s.st.bad_cell = -1;
     HIP_TRY(hipSetDevice(dev[0]));
     {
         is3d_options o = *opts;
@@ -1195,44 +1216,35 @@ int st_multi_impl(const is3d_cells *cells, const double *x, const double *y, con
     }
     BoundExchange bx;
     bx.expected = n_active;
-    auto run = [&](int i) {
+    run_shards(sh, has_cells, [&](int i) {
         StShard &s = sh[i];
         is3d::StSplit split;
         split.role = is3d::ST_CELLS;
         split.D_full = D_full.p; split.D_device = dev[0]; split.n_total = n; split.c_off = s.lo;
         split.exchange = [&bx, &s](unsigned long long mine, unsigned long long *all) { s.exchanged = true; return bx.exchange(mine, all); };
-        s.rc = st_shard_run(s, cells, species, grid, pT_w, phi_w, df, fq, opts, split);
-        if (s.rc) s.err = is3d_last_error();   // the error text is thread-local
+        const int rc = st_shard_run(s, cells, species, grid, pT_w, phi_w, df, fq, opts, split);
         if (!s.exchanged) bx.leave();
-    };
-    if (n_active == 1) {   // on this thread; the one shard with cells, whichever rank the bounds rule gives them to
-        for (int i = 0; i < n_devices; i++)
-            if (sh[i].hi > sh[i].lo) run(i);
-    } else if (n_active > 1) {
-        std::vector<std::thread> th;
-        for (int i = 0; i < n_devices; i++)
-            if (sh[i].hi > sh[i].lo) th.emplace_back(run, i);
-        for (auto &t : th) t.join();
-    }
+        return rc;
+    });
     // ---- stats of the shards (also on failure, so that the caller sees which cell was bad) ----
+    int rc_first;
+    std::string err_first;
+    first_error(sh, &rc_first, &err_first);
     is3d_spacetime_stats agg{};
     agg.bad_cell = -1;
     agg.n_classes = ncls;
-    int rc_first = IS3D_OK;
-    std::string err_first;
     for (int i = 0; i < n_devices; i++) {
         is3d_spacetime_stats &t = sh[i].st;
         t.n_classes = ncls;   // a function of the species list alone: shards without cells report it too
         t.code = sh[i].rc;
         if (shard_stats) shard_stats[i] = t;
-        if (sh[i].rc && !rc_first) { rc_first = sh[i].rc; err_first = "shard " + std::to_string(i) + " (device " + std::to_string(sh[i].device) + "): " + sh[i].err; }
         agg.n_cells_skipped += t.n_cells_skipped;
         agg.n_passes = std::max(agg.n_passes, t.n_passes);
         agg.ms_prep = std::max(agg.ms_prep, t.ms_prep);
         agg.ms_cells = std::max(agg.ms_cells, t.ms_cells);
         agg.ms_h2d = std::max(agg.ms_h2d, t.ms_h2d);
         agg.ms_d2h = std::max(agg.ms_d2h, t.ms_d2h);   // the D placement
-        if (t.bad_cell >= 0 && (agg.bad_cell < 0 || sh[i].lo + t.bad_cell < agg.bad_cell)) agg.bad_cell = sh[i].lo + t.bad_cell;
+        keep_lowest_bad_cell(agg.bad_cell, sh[i], t.bad_cell);
     }
     agg.code = rc_first;
     if (rc_first) {
@@ -1244,7 +1256,7 @@ int st_multi_impl(const is3d_cells *cells, const double *x, const double *y, con
 
     // ---- the one bin stage, on devices[0], over the assembled D and the whole surface's tau, u, dsigma, x, y ----
     HIP_TRY(hipSetDevice(dev[0]));
-    if (!sh[0].stream) HIP_TRY(hipStreamCreateWithFlags(&sh[0].stream, hipStreamNonBlocking));
+    HIP_TRY(sh[0].stream.create(dev[0]));
     hipStream_t st0 = sh[0].stream;
     const int n_eta_eff = K;
     const int64_t tb = bins->tau_bins, rbn = bins->r_bins;
@@ -1256,9 +1268,8 @@ int st_multi_impl(const is3d_cells *cells, const double *x, const double *y, con
     is3d::DevBuf<double> dsurf, dout, dparts;
     HIP_TRY(dsurf.alloc((size_t)std::max<int64_t>(n, 1) * (is3d::kCellArrays + 2)));
     HIP_TRY(dout.alloc(total));
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
-    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    Events ev;
+    HIP_TRY(ev.add(4));
     HIP_TRY(hipEventRecord(ev[0], st0));
     is3d_cells dc;
     HIP_TRY(is3d::stage_cells(*cells, [](int a) { return a == 0 || (a >= 2 && a <= 8); }, 0, n, dsurf.p, st0, &dc));   // tau, dsigma, u
@@ -1271,12 +1282,8 @@ int st_multi_impl(const is3d_cells *cells, const double *x, const double *y, con
         const int64_t per = (int64_t)ncls * K;
         HIP_TRY(dparts.alloc((size_t)per * n_active));
         int k = 0;
-        for (int i = 0; i < n_devices; i++) {
-            if (sh[i].hi <= sh[i].lo) continue;
-            double *dst = dparts.p + (size_t)per * k++;
-            if (sh[i].device == dev[0]) HIP_TRY(hipMemcpyAsync(dst, is3d::plan_st_eta(sh[i].plan), sizeof(double) * per, hipMemcpyDeviceToDevice, st0));
-            else HIP_TRY(hipMemcpyPeerAsync(dst, dev[0], is3d::plan_st_eta(sh[i].plan), sh[i].device, sizeof(double) * per, st0));
-        }
+        for (const StShard &s : sh)
+            if (has_cells(s)) HIP_TRY(place_on(dparts.p + (size_t)per * k++, dev[0], is3d::plan_st_eta(s.plan), s.device, (size_t)per, st0));
         HIP_TRY(is3d::launch_spacetime_eta_shards(dparts.p, n_active, per, is3d::plan_st_eta(P0), st0));
     }
     is3d_spacetime_out dv{};
@@ -1331,20 +1338,15 @@ extern "C" int is3d_spacetime_distributions_multi(const is3d_cells *cells, const
 // nothing before the end: no thread waits for another
 // ------------------------------------------------------------------------------------------------
 namespace {
-struct PzShard {
-    int device = 0;
-    int64_t lo = 0, hi = 0;
+struct PzShard : ShardBase {
     is3d_polarization_plan *plan = nullptr;
-    hipStream_t stream = nullptr;
+    Stream stream;
     is3d::DevBuf<double> d_in, V;   // d_in: 9 cell arrays + 6 vorticity arrays of the shard's cells
     is3d_polarization_stats st{};
-    int rc = IS3D_OK;
-    std::string err;
     ~PzShard()
     {
         (void)hipSetDevice(device);
         if (plan) is3d_polarization_plan_destroy(plan);
-        if (stream) (void)hipStreamDestroy(stream);
     }
 };
 
@@ -1360,23 +1362,22 @@ int pz_shard_run(PzShard &s, const is3d_cells *cells, const is3d_vorticity *w, c
         o.device = s.device;
         if (int rc = is3d_polarization_plan_create(&s.plan, species, grid, &o, n)) return rc;
     }
-    HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+    HIP_TRY(s.stream.create(s.device));
     HIP_TRY(s.d_in.alloc((size_t)n * 15));
     HIP_TRY(s.V.alloc((size_t)is3d::polzn_plan_class_sum_size(s.plan)));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    struct EvGuard { hipEvent_t &a, &b; ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evg{e0, e1};
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, s.stream));
+    Events ev;
+    HIP_TRY(ev.add(2));
+    HIP_TRY(hipEventRecord(ev[0], s.stream));
     is3d_cells dc{};
     HIP_TRY(is3d::stage_cells(*cells, [dim3](int i) { return i <= 8 && (i != 1 || dim3); }, s.lo, n, s.d_in.p, s.stream, &dc));
     std::array<const double *, 6> wa{w->wtx, w->wty, w->wtn, w->wxy, w->wxn, w->wyn};
     HIP_TRY(is3d::stage_arrays(wa, s.lo, n, s.d_in.p + 9 * (size_t)n, s.stream));   // the shard's own slice: global cell lo + c <-> local c
-    HIP_TRY(hipEventRecord(e1, s.stream));
+    HIP_TRY(hipEventRecord(ev[1], s.stream));
     const is3d_vorticity dw{wa[0], wa[1], wa[2], wa[3], wa[4], wa[5]};
     const int rc = is3d::polzn_plan_class_sums(s.plan, &dc, &dw, T, s.V.p, s.stream, &s.st);
     if (rc) return rc;
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
     s.st.ms_h2d = ms;
     return IS3D_OK;
 }
@@ -1390,21 +1391,9 @@ int pz_multi_impl(const is3d_cells *cells, const is3d_vorticity *w, const is3d_s
     dflt.dimension = 3;
     if (!opts) opts = &dflt;   // as the single-device entries: 3+1D
     if (int rc = is3d::polzn_check_args(cells, w, species, grid, T, opts, out)) return rc;
-    if (n_devices > 1024) return fail(IS3D_EINVAL, "n_devices = %d (up to 1024 shards)", n_devices);
-    if (devices)
-        for (int i = 0; i < n_devices; i++)
-            if (devices[i] < 0) return fail(IS3D_EINVAL, "devices[%d] = %d: a device ordinal cannot be negative", i, devices[i]);
-    const int visible = is3d_device_count();
-    if (!devices && n_devices > visible)
-        return fail(IS3D_EINVAL, "n_devices = %d with devices == NULL asks for the ordinals 0..%d, but %d HIP device%s visible", n_devices,
-                    n_devices - 1, visible, visible == 1 ? " is" : "s are");
-    if (visible < 1) return fail(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
-    if (n_devices <= 0) { n_devices = visible; devices = nullptr; }
-    std::vector<int> dev(n_devices);
-    for (int i = 0; i < n_devices; i++) {
-        dev[i] = devices ? devices[i] : i;
-        if (dev[i] >= visible) return fail(IS3D_EINVAL, "devices[%d] = %d is not one of the %d visible HIP devices", i, dev[i], visible);
-    }
+    std::vector<int> dev;
+    if (int rc = resolve_devices(devices, n_devices, dev)) return rc;
+    n_devices = (int32_t)dev.size();
     if (shard_stats) memset(shard_stats, 0, sizeof(is3d_polarization_stats) * (size_t)n_devices);
 
     if (n_devices == 1) {
@@ -1419,17 +1408,9 @@ int pz_multi_impl(const is3d_cells *cells, const is3d_vorticity *w, const is3d_s
         return rc;
     }
 
-    // (declared ahead of the shards, so destroyed after them: the caller's thread gets its current device back)
-    struct DeviceRestore { int d = -1; ~DeviceRestore() { if (d >= 0) (void)hipSetDevice(d); } } restore;
-    if (hipGetDevice(&restore.d) != hipSuccess) { restore.d = -1; (void)hipGetLastError(); }
-    const int64_t n = cells->n_cells;
+    DeviceRestore restore;
     std::vector<PzShard> sh(n_devices);
-    int n_active = 0;
-    for (int i = 0; i < n_devices; i++) {
-        sh[i].device = dev[i];
-        (void)is3d_shard_bounds(n, i, n_devices, &sh[i].lo, &sh[i].hi);
-        if (sh[i].hi > sh[i].lo) n_active++;
-    }
+    const int n_active = assign_shards(sh, dev, cells->n_cells);
     // shard 0's plan lives on devices[0] and also holds the class index and scale tables of the combine (it has cells whenever any shard has)
     HIP_TRY(hipSetDevice(dev[0]));
     {
@@ -1438,33 +1419,22 @@ int pz_multi_impl(const is3d_cells *cells, const is3d_vorticity *w, const is3d_s
         if (int rc = is3d_polarization_plan_create(&sh[0].plan, species, grid, &o, std::max<int64_t>(sh[0].hi - sh[0].lo, 1))) return rc;
     }
     is3d_polarization_plan *P0 = sh[0].plan;
-    auto run = [&](int i) {
-        sh[i].rc = pz_shard_run(sh[i], cells, w, species, grid, T, opts);
-        if (sh[i].rc) sh[i].err = is3d_last_error();   // the error text is thread-local
-    };
-    {
-        std::vector<std::thread> th;
-        for (int i = 0; i < n_devices; i++)
-            if (sh[i].hi > sh[i].lo) th.emplace_back(run, i);
-        for (auto &t : th) t.join();
-    }
+    run_shards(sh, has_cells, [&](int i) { return pz_shard_run(sh[i], cells, w, species, grid, T, opts); });
+    int rc_first;
+    std::string err_first;
+    first_error(sh, &rc_first, &err_first);
     is3d_polarization_stats agg{};
     agg.n_classes = is3d::polzn_plan_classes(P0);
-    int rc_first = IS3D_OK;
-    std::string err_first;
-    double ms_sums = 0.0;
     for (int i = 0; i < n_devices; i++) {
         is3d_polarization_stats &t = sh[i].st;
         t.n_classes = agg.n_classes;   // a function of the species list alone: shards without cells report it too
         t.code = sh[i].rc;
         if (shard_stats) shard_stats[i] = t;
-        if (sh[i].rc && !rc_first) { rc_first = sh[i].rc; err_first = "shard " + std::to_string(i) + " (device " + std::to_string(sh[i].device) + "): " + sh[i].err; }
         agg.n_chunks += t.n_chunks;
         agg.ms_cells = std::max(agg.ms_cells, t.ms_cells);
         agg.ms_h2d = std::max(agg.ms_h2d, t.ms_h2d);
-        ms_sums = std::max(ms_sums, t.ms_reduce);
+        agg.ms_reduce = std::max(agg.ms_reduce, t.ms_reduce);
     }
-    agg.ms_reduce = ms_sums;
     agg.code = rc_first;
     if (rc_first) {
         if (stats) *stats = agg;
@@ -1473,7 +1443,7 @@ int pz_multi_impl(const is3d_cells *cells, const is3d_vorticity *w, const is3d_s
 
     // ---- placement of the class sums on devices[0], the sum over the shards, the read-back ----
     HIP_TRY(hipSetDevice(dev[0]));
-    if (!sh[0].stream) HIP_TRY(hipStreamCreateWithFlags(&sh[0].stream, hipStreamNonBlocking));
+    HIP_TRY(sh[0].stream.create(dev[0]));
     hipStream_t st0 = sh[0].stream;
     const int64_t per = is3d::polzn_plan_class_sum_size(P0);
     const size_t nout = (size_t)is3d::polzn_plan_output_size(P0);
@@ -1488,16 +1458,13 @@ int pz_multi_impl(const is3d_cells *cells, const is3d_vorticity *w, const is3d_s
         HIP_TRY(e);
     }
     // ev[0 .. n_active]: around each shard's placement; then the combine and the read-back
-    std::vector<hipEvent_t> ev((size_t)n_active + 3, nullptr);
-    struct EvGuard { std::vector<hipEvent_t> &e; ~EvGuard() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } evg{ev};
-    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    Events ev;
+    HIP_TRY(ev.add((size_t)n_active + 3));
     HIP_TRY(hipEventRecord(ev[0], st0));
     int k = 0;
-    for (int i = 0; i < n_devices; i++) {   // every shard's stream is synchronised: its V is complete
-        if (sh[i].hi <= sh[i].lo) continue;
-        double *dst = stage.p + (size_t)per * k++;
-        if (sh[i].device == dev[0]) HIP_TRY(hipMemcpyAsync(dst, sh[i].V.p, sizeof(double) * (size_t)per, hipMemcpyDeviceToDevice, st0));
-        else HIP_TRY(hipMemcpyPeerAsync(dst, dev[0], sh[i].V.p, sh[i].device, sizeof(double) * (size_t)per, st0));
+    for (const PzShard &s : sh) {   // every shard's stream is synchronised: its V is complete
+        if (!has_cells(s)) continue;
+        HIP_TRY(place_on(stage.p + (size_t)per * k++, dev[0], s.V.p, s.device, (size_t)per, st0));
         HIP_TRY(hipEventRecord(ev[k], st0));
     }
     const hipEvent_t e_placed = ev[n_active], e_combined = ev[n_active + 1], e_back = ev[n_active + 2];
@@ -1519,7 +1486,7 @@ int pz_multi_impl(const is3d_cells *cells, const is3d_vorticity *w, const is3d_s
     if (shard_stats) {
         k = 0;
         for (int i = 0; i < n_devices; i++) {
-            if (sh[i].hi <= sh[i].lo) continue;
+            if (!has_cells(sh[i])) continue;
             float ms = 0.f;
             HIP_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
             shard_stats[i].ms_d2h = ms;   // the placement of this shard's class sums

@@ -149,3 +149,58 @@ def test_sampler_bin_list_device_validates_before_device_use():
         with pytest.raises(api.Is3dError) as e:
             api.sampler_bin_list_device(bins, 2, 3, p)
         assert e.value.code == api.IS3D_ENODEVICE and "no CPU path" in str(e.value)
+
+
+SAMPLER_BINS = dict(y_cut=1.5, eta_cut=4.0, pT_lower_cut=0.25, pT_upper_cut=2.75, tau_min=1.0, tau_max=9.0, r_min=0.5, r_max=8.0,
+                    y_bins=12, eta_bins=16, pT_bins=10, tau_bins=8, r_bins=15)
+MULTI_ENTRIES = ["smooth_spectra_multi", "multi_plan", "sample_particles_multi", "sample_binned_multi", "spacetime_distributions_multi",
+                 "spin_polarization_multi"]
+
+
+def multi_entry(fx, name):
+    """call(devices) of one in-process multi-device entry through its api wrapper: 4 cells, the pikp species, otherwise valid arguments"""
+    sp, grid, df = fx["pikp"], fx["grid"], fx["df"]
+    cells = synth.synth_surface(4, 3, seed=11)
+    o = dict(dimension=3, df_mode=1)
+    gla = inputs.feqmod_tables(0.15)
+    if name == "smooth_spectra_multi":
+        return lambda d: api.smooth_spectra_multi(cells, sp, grid, df, o, devices=d)
+    if name == "multi_plan":
+        return lambda d: api.MultiPlan(sp, grid, df, o, devices=d, max_cells=4).close()
+    if name == "sample_particles_multi":
+        return lambda d: api.sample_particles(cells, sp, df, gla, o, devices=d)
+    if name == "sample_binned_multi":
+        return lambda d: api.sample_binned(cells, sp, df, gla, SAMPLER_BINS, o, devices=d)
+    if name == "spacetime_distributions_multi":
+        bins = dict(tau_min=0.0, tau_max=20.0, tau_bins=3, r_min=0.0, r_max=20.0, r_bins=3)
+        return lambda d: api.spacetime_distributions_multi(cells, sp, fx["grid_w"], df, bins, o, d)
+    vort = synth.synth_vorticity(4, seed=12)
+    return lambda d: api.spin_polarization_multi(cells, vort, sp, grid, 0.15, dict(dimension=3), d)
+
+
+@pytest.mark.parametrize("devices,needle", [([0, -2], "devices[1] = -2"), ([0] * 1025, "n_devices = 1025"), (999, "n_devices = 999")],
+                         ids=["negative-ordinal", "1025-entries", "count-beyond-visible"])
+@pytest.mark.parametrize("name", MULTI_ENTRIES)
+def test_multi_entries_refuse_a_bad_device_list_alike(fx, name, devices, needle):
+    """One rule for the device list of every in-process multi-device entry: a negative ordinal, more than 1024 shards and a bare count beyond
+    the visible devices (devices = NULL, n_devices = 999) are IS3D_EINVAL with the same words, with or without a GPU, before any device is
+    used (the resource counters stand still)."""
+    call = multi_entry(fx, name)
+    before = api.resource_counters()
+    with pytest.raises(api.Is3dError) as e:
+        call(devices)
+    assert e.value.code == api.IS3D_EINVAL, str(e.value)
+    assert needle in str(e.value), str(e.value)
+    assert api.resource_counters() == before
+
+
+@pytest.mark.parametrize("name", MULTI_ENTRIES)
+def test_multi_entries_have_no_cpu_path(fx, name):
+    """devices = [0, 0] is a valid list: without a HIP device every multi-device entry answers IS3D_ENODEVICE (with one it computes)."""
+    call = multi_entry(fx, name)
+    if api.load().is3d_device_count() > 0:
+        call([0, 0])
+        return
+    with pytest.raises(api.Is3dError) as e:
+        call([0, 0])
+    assert e.value.code == api.IS3D_ENODEVICE and "no CPU path" in str(e.value)

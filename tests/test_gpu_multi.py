@@ -473,3 +473,37 @@ def test_bench_four_ranks_uneven_shards_through_the_library_communicator(tmp_pat
     assert all(x["allreduce_ms"] is not None and x["allreduce_ms"] >= 0 for x in d["ranks"]) and d["config"]["spectrum_finite"]
     assert d["value"] == pytest.approx(3001.0 * d["config"]["bins"] * d["config"]["species"] / (d["ms_per_step"] * 1e-3), rel=1e-9)
     _check_multi_rank_line(d)
+
+
+def test_a_lone_shard_with_cells_runs_on_the_calling_thread(fx):
+    """One cell over devices = [0, 0]: shard 0 holds the cell, shard 1 none, and the one shard with work runs on the caller's thread instead
+    of a thread of its own.  The spin polarization, the sampler's list and the sampler's histograms are the single-device ones bit for bit;
+    where the entry reports on its shards (the polarization), it reports on both, the second with nothing done."""
+    cells = synth.synth_surface(1, 3, seed=17)
+    sp, grid, df = fx["pikp"], fx["grid"], fx["df"]
+    assert [api.shard_bounds(1, r, 2) for r in range(2)] == [(0, 1), (1, 1)]
+    vort = synth.synth_vorticity(1, seed=18)
+    one = api.spin_polarization(cells, vort, sp, grid, 0.15, dict(dimension=3))
+    two = api.spin_polarization_multi(cells, vort, sp, grid, 0.15, dict(dimension=3), [0, 0])
+    for k in api.POLARIZATION_OUTPUTS:
+        assert np.array_equal(one[k], two[k]), k
+    assert np.abs(one["Snorm"]).max() > 0
+    sh = two["shard_stats"]
+    assert len(sh) == 2 and sh[0]["n_chunks"] == two["stats"]["n_chunks"] >= 1 and sh[1]["n_chunks"] == 0 and sh[1]["code"] == 0
+    assert sh[1]["ms_cells"] == 0 and sh[1]["ms_h2d"] == 0 and sh[1]["ms_d2h"] == 0
+    gla = inputs.feqmod_tables(0.15)
+    o = dict(dimension=3, df_mode=2)
+    kw = dict(n_events=512, seed=5)
+    plist, st1 = api.sample_particles(cells, sp, df, gla, o, **kw)
+    mlist, st2 = api.sample_particles(cells, sp, df, gla, o, devices=[0, 0], **kw)
+    print("one cell, %d events: %d hadrons" % (kw["n_events"], len(plist)))
+    assert len(plist) == len(mlist) and st2["n_particles"] == st1["n_particles"] and st2["n_hadrons_drawn"] == st1["n_hadrons_drawn"]
+    for f in plist.dtype.names:
+        assert np.array_equal(plist[f], mlist[f]), f
+    bins = dict(y_cut=1.5, eta_cut=4.0, pT_lower_cut=0.25, pT_upper_cut=2.75, tau_min=1.0, tau_max=9.0, r_min=0.5, r_max=8.0,
+                y_bins=12, eta_bins=16, pT_bins=10, tau_bins=8, r_bins=15)
+    h1, sb1 = api.sample_binned(cells, sp, df, gla, bins, o, **kw)
+    h2, sb2 = api.sample_binned(cells, sp, df, gla, bins, o, devices=[0, 0], **kw)
+    assert sorted(h1) == sorted(h2) and sb2["n_particles"] == sb1["n_particles"] == st1["n_particles"]
+    for k in h1:
+        assert np.array_equal(h1[k], h2[k]), k
