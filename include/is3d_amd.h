@@ -447,7 +447,24 @@ int is3d_vah_plan_tile_shape(const is3d_vah_plan *plan, int32_t *JT, int32_t *R)
 /* "cf_main_vah3" (3+1D, opts.kernel_variant 0 | 3: factored exponent, 8 x 7 tile) or "cf_main_vah" (2+1D; 3+1D with kernel_variant 2: the
  * round-1 kernel on the 6 x 7 tile, kept for A/B) as it appears in rocprofv3 traces */
 const char *is3d_vah_plan_main_kernel_name(const is3d_vah_plan *plan);
+/* is3d_plan_observables for a device-resident spectrum of this plan's shape (dN/dy, dN/2 pi pT dpT dy, v_n; the same arguments, the same
+ * kernels, this plan's species and grid): a VAH caller that wants a dN/dy does not take the spectrum to the host.  Asynchronous on hip_stream. */
+int is3d_vah_plan_observables(is3d_vah_plan *plan, const double *dN_dev, const double *pT_w, const double *phi_w, double *dNdy,
+                              double *dN2pipTdpTdy, double *vn, void *hip_stream);
 void is3d_vah_plan_destroy(is3d_vah_plan *plan);
+
+/* is3d_smooth_spectra_vah_df over several devices (tab == NULL: c0..c4 from the cells): the cells in n_devices contiguous shards
+ * (is3d_shard_bounds), shard s on devices[s] with a host thread, a non-blocking stream and an is3d_vah_plan of its own; the device list,
+ * reduce, status and shard_status as for is3d_smooth_spectra_multi (IS3D_REDUCE_ORDERED: the fixed binary tree, bitwise reproducible for a
+ * given shard count, an ordinal may repeat; IS3D_REDUCE_RCCL: distinct devices).  A shard uploads only its own cells; with tab its
+ * coefficients are interpolated on its own device.  One shard with IS3D_REDUCE_ORDERED is is3d_smooth_spectra_vah_df on devices[0].
+ * opts->accumulate = 1 adds the combined result to dN_out on the host.  Shards without cells contribute zeros.  A failed shard does not stop
+ * the others; the first failed shard's code comes back with "shard i (device d): ..." and, for IS3D_EDOMAIN, the cell's index in the whole
+ * surface (also status->bad_cell; shard_status[i].bad_cell is shard-local).  NULL arguments, n_cells < 0, a NULL cell array that is read, a bad
+ * reduce and what the list alone decides are IS3D_EINVAL before any device is used. */
+int is3d_smooth_spectra_vah_multi(const is3d_vah_cells *cells, const is3d_species *species, const is3d_grid *grid,
+                                  const is3d_vah_df_tables *tab, const is3d_options *opts, const int32_t *devices, int32_t n_devices,
+                                  int32_t reduce, double *dN_out, is3d_status *status, is3d_status *shard_status);
 
 /* FO_data_reader::read_surf_VAH_PLMatch (mode 2; src/cpp/readindata.cpp:813-928): 31 numbers per cell -- tau x y eta | dat dax day
  * dan | ut ux uy un | E T P PL | pitt pitx pity pitn pixx pixy pixn piyy piyn pinn | Wt Wx Wy Wn | bulkPi -- E, T, P, PL, pi, W and

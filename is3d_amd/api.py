@@ -117,7 +117,8 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_pdg_read_decays", "is3d_decay_q_factor", "is3d_resonance_decays", "is3d_decay_plan_create", "is3d_decay_plan_output_size",
            "is3d_decay_plan_execute", "is3d_decay_plan_destroy", "is3d_write_results_decays",
            "is3d_sampler_bin_list", "is3d_write_sampler_tests_binned", "is3d_sampler_plan_execute_binned", "is3d_sample_binned", "is3d_sample_binned_multi",
-           "is3d_sampler_bin_list_device", "is3d_df_generate", "is3d_df_tables_write"]
+           "is3d_sampler_bin_list_device", "is3d_df_generate", "is3d_df_tables_write",
+           "is3d_smooth_spectra_vah_multi", "is3d_vah_plan_observables"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 POLARIZATION_OUTPUTS = ["St", "Sx", "Sy", "Sn", "Snorm"]
@@ -347,6 +348,10 @@ def load():
     L.is3d_df_generate.argtypes = [C.POINTER(HadronList), C.c_int32, C.POINTER(_dp), C.POINTER(_dp), C.c_int32, _dp, C.c_int32, _dp, C.c_int32,
                                    _dp, _dp, C.POINTER(DfgenStats)]
     L.is3d_df_tables_write.argtypes = [C.c_char_p, C.c_int32, _dp, C.c_int32, _dp, _dp]
+    L.is3d_smooth_spectra_vah_multi.argtypes = [C.POINTER(VahCells), C.POINTER(Species), C.POINTER(Grid), C.POINTER(VahDfTables),
+                                                C.POINTER(Options), C.POINTER(C.c_int32), C.c_int32, C.c_int32, _dp, C.POINTER(Status),
+                                                C.POINTER(Status)]
+    L.is3d_vah_plan_observables.argtypes = [C.c_void_p, C.c_void_p, _dp, _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _LIB = L
     return L
 
@@ -568,6 +573,13 @@ class VahPlan:
         if rc != 0:
             raise Is3dError(rc, load().is3d_last_error().decode(), bad_cell=st.bad_cell)
         return st.as_dict() if want_status else None
+
+    def observables(self, dN_ptr, pT_w, phi_w, dndy_ptr=0, spec2pi_ptr=0, vn_ptr=0, stream=0):
+        """is3d_vah_plan_observables: as Plan.observables -- device pointers (ints) in and out, host weight arrays (pT_w may be None when
+        dN/dy is not asked for)."""
+        pw, fw = None if pT_w is None else _f64(pT_w), _f64(phi_w)
+        _check(load().is3d_vah_plan_observables(self._h, C.c_void_p(int(dN_ptr)), None if pw is None else _p(pw), _p(fw), C.c_void_p(int(dndy_ptr or 0)),
+                                                C.c_void_p(int(spec2pi_ptr or 0)), C.c_void_p(int(vn_ptr or 0)), C.c_void_p(int(stream or 0))))
 
     def timings(self):
         st = Status()
@@ -1009,6 +1021,35 @@ def smooth_spectra_multi(cells, species, grid, df, opts=None, devices=None, redu
                                      C.byref(os_), dv, nd, int(reduce), _p(out), C.byref(st), sst)
     _check(rc)
     return out, st.as_dict(), [sst[i].as_dict() for i in range(n_stats)]
+
+
+def smooth_spectra_vah_multi(cells, species, grid, opts=None, devices=None, reduce=REDUCE_ORDERED, out=None, tab=None):
+    """is3d_smooth_spectra_vah_multi: smooth_spectra_vah with the cells sharded over `devices` (as smooth_spectra_multi: a list of HIP
+    ordinals, one shard per entry, an ordinal may repeat; an int n means the ordinals 0 .. n - 1; None every visible device).  Returns
+    (dN, status dict); status["shards"] holds one status dict per shard (bad_cell shard-local there).  An Is3dError raised here carries
+    bad_cell (an index of the whole surface) and that status."""
+    L = load()
+    sps, gs, _, os_, nout, keep = _pack_common(species, grid, _VAH_DUMMY_DF, opts)
+    held = []
+    if tab is not None:
+        cells = {k: v for k, v in cells.items() if k not in ("c0", "c1", "c2", "c3", "c4")}
+    cs = _vah_cells_struct(cells, held)
+    if out is None:
+        out = np.zeros(nout)
+    assert out.dtype == np.float64 and out.size == nout and out.flags.c_contiguous
+    ts = _pack_vah_tables(tab, keep) if tab is not None else None
+    dv, nd, n_stats = _pack_devices(devices)
+    st = Status()
+    sst = (Status * n_stats)()
+    rc = L.is3d_smooth_spectra_vah_multi(C.byref(cs), C.byref(sps), C.byref(gs), C.byref(ts) if ts is not None else None, C.byref(os_),
+                                         dv, nd, int(reduce), _p(out), C.byref(st), sst)
+    status = st.as_dict()
+    status["shards"] = [sst[i].as_dict() for i in range(n_stats)]
+    if rc != 0:
+        err = Is3dError(rc, L.is3d_last_error().decode(), bad_cell=status["bad_cell"])
+        err.status = status
+        raise err
+    return out, status
 
 
 class MultiPlan:

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <array>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <type_traits>
@@ -137,6 +138,19 @@ hipError_t stage_cells(const Cells &h, Keep keep, int64_t lo, int64_t n, double 
     const hipError_t e = stage_arrays(a, lo, n, block, st);
     *dev = cells_from_arrays(n, a);
     return e;
+}
+
+// cos(k phi_j) and sin(k phi_j), k = 1..7, as [k - 1][j]: the harmonics of write_continuous_vn_toFile (emissionfunction.cpp:1106) that
+// launch_observables reads, for every plan that offers the derived observables
+inline void vn_harmonics(const double *phi, int J, std::vector<double> &ck, std::vector<double> &sk)
+{
+    ck.resize((size_t)7 * J);
+    sk.resize((size_t)7 * J);
+    for (int k = 0; k < 7; k++)
+        for (int j = 0; j < J; j++) {
+            ck[(size_t)k * J + j] = std::cos(((double)k + 1.0) * phi[j]);
+            sk[(size_t)k * J + j] = std::sin(((double)k + 1.0) * phi[j]);
+        }
 }
 
 }  // namespace is3d

@@ -624,6 +624,45 @@ hipError_t place_on(double *dst, int dst_device, const double *src, int src_devi
     return hipMemcpyPeerAsync(dst, dst_device, src, src_device, sizeof(double) * count, stream);
 }
 
+// which shards take a partner from another device in some round of the tree sum (tree_sum_shards) and so need a receive buffer
+std::vector<char> tree_receivers(const std::vector<int> &dev)
+{
+    const int n = (int)dev.size();
+    std::vector<char> need(dev.size(), 0);
+    for (int stride = 1; stride < n; stride *= 2)
+        for (int i = 0; i + stride < n; i += 2 * stride)
+            if (dev[i] != dev[i + stride]) need[i] = 1;
+    return need;
+}
+
+// the is3d_status of a sharded spectrum from its shards' (S: a shard with an is3d_status st): counters summed, the slowest shard's ms_prep /
+// ms_main / ms_finalize / ms_h2d, the most passes, the lowest bad cell as an index of the whole surface; shard_status[i] (may be NULL) is shard
+// i's own, with its return code
+template <class S>
+is3d_status aggregate_status(const std::vector<S> &sh, is3d_status *shard_status)
+{
+    is3d_status agg{};
+    agg.bad_cell = -1;
+    for (size_t i = 0; i < sh.size(); i++) {
+        const is3d_status &t = sh[i].st;
+        if (shard_status) { shard_status[i] = t; shard_status[i].code = sh[i].rc; }
+        agg.n_classes = std::max(agg.n_classes, t.n_classes);
+        agg.n_cells_skipped += t.n_cells_skipped;
+        agg.n_passes = std::max(agg.n_passes, t.n_passes);
+        agg.kernel_variant = t.kernel_variant ? t.kernel_variant : agg.kernel_variant;
+        agg.ms_prep = std::max(agg.ms_prep, t.ms_prep);
+        agg.ms_main = std::max(agg.ms_main, t.ms_main);
+        agg.ms_finalize = std::max(agg.ms_finalize, t.ms_finalize);
+        agg.ms_h2d = std::max(agg.ms_h2d, t.ms_h2d);
+        agg.n_wave_rows += t.n_wave_rows;
+        agg.n_wave_rows_culled += t.n_wave_rows_culled;
+        agg.n_cells_breakdown += t.n_cells_breakdown;
+        agg.n_cells_narrow += t.n_cells_narrow;
+        keep_lowest_bad_cell(agg.bad_cell, sh[i], t.bad_cell);
+    }
+    return agg;
+}
+
 // ---- the Cooper-Frye spectrum (is3d_multi_plan_*, is3d_smooth_spectra_multi) ----
 // everything a shard owns for the life of a multi-device plan
 struct Shard : ShardBase {
@@ -725,7 +764,9 @@ int shard_run(Shard &s, const is3d_cells *cells, bool diff)
     return IS3D_OK;
 }
 
-int rccl_allreduce_shards(std::vector<Shard> &sh, CommSet *cs, int64_t nout)
+// (S: a shard with its spectrum in d_out and a stream, Shard or VahShard)
+template <class S>
+int rccl_allreduce_shards(std::vector<S> &sh, CommSet *cs, int64_t nout)
 {
     NCCL_TRY(rccl().GroupStart());
     for (size_t i = 0; i < sh.size(); i++) {
@@ -746,13 +787,15 @@ int rccl_allreduce_shards(std::vector<Shard> &sh, CommSet *cs, int64_t nout)
 
 // Pairwise tree in a fixed order: round r adds shard i + 2^r into shard i for every i that is a multiple of 2^(r+1); the pairs of a
 // round run concurrently on the streams of their receiving shards, a receiver waits for its partner's previous round through an event.
-// The sum ends in shard 0; the order of the additions depends on the shard count only.
-int tree_sum_shards(std::vector<Shard> &sh, int64_t nout)
+// The sum ends in shard 0; the order of the additions depends on the shard count only.  S: a shard with d_out, d_tmp, stream and ev[2]
+// (Shard, VahShard).
+template <class S>
+int tree_sum_shards(std::vector<S> &sh, int64_t nout)
 {
     const size_t n = sh.size();
     for (size_t stride = 1; stride < n; stride *= 2) {
         for (size_t i = 0; i + stride < n; i += 2 * stride) {
-            Shard &dst = sh[i], &src = sh[i + stride];
+            S &dst = sh[i], &src = sh[i + stride];
             HIP_TRY(hipSetDevice(dst.device));
             if (stride > 1) HIP_TRY(hipStreamWaitEvent(dst.stream, src.ev[2], 0));   // round 0: every shard's stream is already synchronised
             const double *from = src.d_out.p;
@@ -796,12 +839,7 @@ extern "C" int is3d_multi_plan_create(is3d_multi_plan **out, const is3d_species 
         s.cap = std::max<int64_t>((max_cells + n_devices - 1) / n_devices, 1);
         s.st.bad_cell = -1;
     }
-    // a shard needs a receive buffer if it takes a partner from another device in some round of the tree
-    std::vector<char> need_tmp(n_devices, 0);
-    if (reduce == IS3D_REDUCE_ORDERED)
-        for (int stride = 1; stride < n_devices; stride *= 2)
-            for (int i = 0; i + stride < n_devices; i += 2 * stride)
-                if (dev[i] != dev[i + stride]) need_tmp[i] = 1;
+    const std::vector<char> need_tmp = reduce == IS3D_REDUCE_ORDERED ? tree_receivers(dev) : std::vector<char>(dev.size(), 0);
     run_shards(sh, every_shard, [&](int i) { return shard_create(sh[i], species, grid, df, fq, opts, need_tmp[i] != 0); });
     int rc;
     std::string text;
@@ -836,25 +874,7 @@ extern "C" int is3d_multi_plan_execute(is3d_multi_plan *M, const is3d_cells *cel
     int rc_first;
     std::string err_first;
     first_error(sh, &rc_first, &err_first);
-    is3d_status agg{};
-    agg.bad_cell = -1;
-    for (int i = 0; i < n_devices; i++) {
-        const is3d_status &t = sh[i].st;
-        if (shard_status) { shard_status[i] = t; shard_status[i].code = sh[i].rc; }
-        agg.n_classes = std::max(agg.n_classes, t.n_classes);
-        agg.n_cells_skipped += t.n_cells_skipped;
-        agg.n_passes = std::max(agg.n_passes, t.n_passes);
-        agg.kernel_variant = t.kernel_variant ? t.kernel_variant : agg.kernel_variant;
-        agg.ms_prep = std::max(agg.ms_prep, t.ms_prep);
-        agg.ms_main = std::max(agg.ms_main, t.ms_main);
-        agg.ms_finalize = std::max(agg.ms_finalize, t.ms_finalize);
-        agg.ms_h2d = std::max(agg.ms_h2d, t.ms_h2d);
-        agg.n_wave_rows += t.n_wave_rows;
-        agg.n_wave_rows_culled += t.n_wave_rows_culled;
-        agg.n_cells_breakdown += t.n_cells_breakdown;
-        agg.n_cells_narrow += t.n_cells_narrow;
-        keep_lowest_bad_cell(agg.bad_cell, sh[i], t.bad_cell);
-    }
+    is3d_status agg = aggregate_status(sh, shard_status);
     agg.code = rc_first;
     if (rc_first) {
         if (status) *status = agg;
@@ -918,6 +938,141 @@ extern "C" int is3d_smooth_spectra_multi(const is3d_cells *cells, const is3d_spe
     is3d_multi_plan_destroy(M);
     if (rc) return fail(rc, "%s", kept.c_str());
     return IS3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// anisotropic hydro (mode 2) over several devices: is3d_smooth_spectra_vah_df on contiguous shards of the cells, every shard with an
+// is3d_vah_plan of its own size, the shard spectra combined as the viscous ones are (tree_sum_shards / rccl_allreduce_shards)
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct VahShard : ShardBase {
+    is3d_vah_plan *plan = nullptr;
+    is3d::DevBuf<double> d_cells, d_out, d_tmp;   // d_tmp: the partner's spectrum in a round of the tree sum
+    Stream stream;
+    Events ev;                         // as Shard's: [0], [1] around the upload or the reduction; [2]: this shard's round of the tree sum is enqueued
+    is3d_status st{};
+    ~VahShard()
+    {
+        (void)hipSetDevice(device);
+        if (plan) is3d_vah_plan_destroy(plan);
+    }
+};
+
+// the shard's plan and buffers, its slices up, the plan run; the spectrum stays on the device (s.d_out), the stream is synchronised
+// (is3d_vah_plan_execute reads the status back).  A shard without cells leaves zeros
+int vah_shard_run(VahShard &s, const is3d_vah_cells *cells, const is3d_species *sp, const is3d_grid *grid, const is3d_vah_df_tables *tab,
+                  const is3d_options *opts, bool need_tmp)
+{
+    HIP_TRY(hipSetDevice(s.device));
+    const int64_t n = s.hi - s.lo;
+    is3d_options o = *opts;
+    o.device = s.device;
+    o.accumulate = 0;
+    if (int rc = is3d_vah_plan_create(&s.plan, sp, grid, tab, &o, std::max<int64_t>(n, 1))) return rc;
+    (void)is3d_vah_plan_set_timing(s.plan, 1);
+    const int64_t nout = is3d_vah_plan_output_size(s.plan);
+    HIP_TRY(s.stream.create(s.device));
+    HIP_TRY(s.d_cells.alloc(is3d::kVahCellArrays * (size_t)std::max<int64_t>(n, 1)));
+    HIP_TRY(s.d_out.alloc((size_t)nout));
+    if (need_tmp) HIP_TRY(s.d_tmp.alloc((size_t)nout));
+    HIP_TRY(s.ev.add(2));
+    HIP_TRY(s.ev.add(1, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(s.ev[0], s.stream));
+    is3d_vah_cells dc;   // the selection of is3d_smooth_spectra_vah_df: T is not read; c0..c4 come from the tables when they are given
+    HIP_TRY(is3d::stage_cells(*cells, [tab](int a) { return a != 9 && !(a >= 25 && tab); }, s.lo, n, s.d_cells.p, s.stream, &dc));
+    HIP_TRY(hipEventRecord(s.ev[1], s.stream));
+    if (int rc = is3d_vah_plan_execute(s.plan, &dc, s.d_out.p, s.stream, &s.st)) return rc;
+    is3d_status t{};
+    (void)is3d_vah_plan_timings(s.plan, &t);
+    s.st.ms_prep = t.ms_prep; s.st.ms_main = t.ms_main; s.st.ms_finalize = t.ms_finalize;
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]));
+    s.st.ms_h2d = ms;
+    return IS3D_OK;
+}
+
+int vah_multi_impl(const is3d_vah_cells *cells, const is3d_species *species, const is3d_grid *grid, const is3d_vah_df_tables *tab,
+                   const is3d_options *opts, const int32_t *devices, int32_t n_devices, int32_t reduce, double *dN_out, is3d_status *status,
+                   is3d_status *shard_status)
+{
+    // ---- every refusal, before any device is used or a plan created ----
+    if (!cells || !species || !grid || !opts || !dN_out) return fail(IS3D_EINVAL, "null argument");
+    if (reduce != IS3D_REDUCE_ORDERED && reduce != IS3D_REDUCE_RCCL) return fail(IS3D_EINVAL, "reduce must be IS3D_REDUCE_ORDERED or IS3D_REDUCE_RCCL");
+    if (cells->n_cells < 0) return fail(IS3D_EINVAL, "n_cells < 0");
+    if (int rc = is3d::check_vah_cells(cells, opts->dimension != 2, tab != nullptr)) return rc;
+    std::vector<int> dev;
+    if (int rc = resolve_devices(devices, n_devices, dev)) return rc;
+    n_devices = (int32_t)dev.size();
+    if (shard_status) memset(shard_status, 0, sizeof(is3d_status) * (size_t)n_devices);
+
+    if (n_devices == 1 && reduce == IS3D_REDUCE_ORDERED) {
+        // one shard IS the single-device call on devices[0]: no second upload of the surface
+        is3d_options o = *opts;
+        o.device = dev[0];
+        is3d_status st{};
+        const int rc = is3d_smooth_spectra_vah_df(cells, species, grid, tab, &o, dN_out, &st);
+        st.code = rc;
+        if (status) *status = st;
+        if (shard_status) shard_status[0] = st;
+        return rc;
+    }
+
+    DeviceRestore restore;
+    CommSet *comms = nullptr;
+    if (reduce == IS3D_REDUCE_RCCL && n_devices > 1)
+        if (int rc = commset_for(dev, &comms)) return rc;
+    std::vector<VahShard> sh(n_devices);
+    assign_shards(sh, dev, cells->n_cells);
+    for (auto &s : sh) s.st.bad_cell = -1;
+    const std::vector<char> need_tmp = reduce == IS3D_REDUCE_ORDERED ? tree_receivers(dev) : std::vector<char>(dev.size(), 0);
+    run_shards(sh, every_shard, [&](int i) { return vah_shard_run(sh[i], cells, species, grid, tab, opts, need_tmp[i] != 0); });   // the sum reads every shard's spectrum
+    // aggregate (also on failure, so that the caller sees which cell was bad)
+    int rc_first;
+    std::string err_first;
+    first_error(sh, &rc_first, &err_first);
+    is3d_status agg = aggregate_status(sh, shard_status);
+    agg.code = rc_first;
+    if (status) *status = agg;
+    if (rc_first) {
+        if (rc_first == IS3D_EDOMAIN && agg.bad_cell >= 0)
+            return fail(rc_first, "cell %lld of the surface: %s", (long long)agg.bad_cell, err_first.c_str());
+        return fail(rc_first, "%s", err_first.c_str());
+    }
+
+    // ---- the sum of the shard spectra into shard 0's, the read-back ----
+    VahShard &s0 = sh[0];
+    const int64_t nout = is3d_vah_plan_output_size(s0.plan);
+    HIP_TRY(hipSetDevice(s0.device));
+    HIP_TRY(hipEventRecord(s0.ev[0], s0.stream));
+    if (n_devices > 1)
+        if (int rc = comms ? rccl_allreduce_shards(sh, comms, nout) : tree_sum_shards(sh, nout)) return rc;
+    HIP_TRY(hipSetDevice(s0.device));
+    std::vector<double> h_acc;   // accumulate: the device sum lands here first
+    if (opts->accumulate) {      // dN += result, on the host as is3d_multi_plan_execute does
+        h_acc.resize((size_t)nout);
+        HIP_TRY(hipMemcpyAsync(h_acc.data(), s0.d_out.p, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, s0.stream));
+        HIP_TRY(hipStreamSynchronize(s0.stream));
+        for (int64_t i = 0; i < nout; i++) dN_out[i] += h_acc[(size_t)i];
+    } else {
+        HIP_TRY(hipMemcpyAsync(dN_out, s0.d_out.p, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, s0.stream));
+    }
+    HIP_TRY(hipEventRecord(s0.ev[1], s0.stream));
+    HIP_TRY(hipEventSynchronize(s0.ev[1]));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, s0.ev[0], s0.ev[1]));
+    if (status) status->ms_d2h = ms;
+    return IS3D_OK;
+}
+}  // namespace
+
+extern "C" int is3d_smooth_spectra_vah_multi(const is3d_vah_cells *cells, const is3d_species *species, const is3d_grid *grid,
+                                             const is3d_vah_df_tables *tab, const is3d_options *opts, const int32_t *devices,
+                                             int32_t n_devices, int32_t reduce, double *dN_out, is3d_status *status, is3d_status *shard_status)
+{
+    if (status) { memset(status, 0, sizeof *status); status->bad_cell = -1; }
+    const int rc = vah_multi_impl(cells, species, grid, tab, opts, devices, n_devices, reduce, dN_out, status, shard_status);
+    if (status) status->code = rc;   // whatever the way out: a refusal, a HIP failure, a shard's error
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -349,12 +349,8 @@ static int plan_create_impl(is3d_plan **out, const is3d_species *sp, const is3d_
         HIP_TRY(P->d_ksh.upload(ksh));
     }
     {
-        std::vector<double> ck((size_t)7 * P->J), sk((size_t)7 * P->J);
-        for (int k = 0; k < 7; k++)
-            for (int j = 0; j < P->J; j++) {
-                ck[(size_t)k * P->J + j] = std::cos(((double)k + 1.0) * g->phi[j]);   // emissionfunction.cpp:1106
-                sk[(size_t)k * P->J + j] = std::sin(((double)k + 1.0) * g->phi[j]);
-            }
+        std::vector<double> ck, sk;
+        is3d::vn_harmonics(g->phi, P->J, ck, sk);
         HIP_TRY(P->d_coskphi.upload(ck));
         HIP_TRY(P->d_sinkphi.upload(sk));
         HIP_TRY(P->d_phiw.alloc(P->J));

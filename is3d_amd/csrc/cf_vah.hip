@@ -818,6 +818,7 @@ struct is3d_vah_plan {
     int64_t nout = 0, max_cells = 0, pass_cells = 0;
     size_t lds_prep = 0;
     DevMem d_mT, d_pT, d_sg, d_lane, d_deg, d_cos, d_sin, d_kg, d_kw, d_TS, d_partial, d_coef, d_status, d_lane_sub;
+    is3d::DevBuf<double> d_coskphi, d_sinkphi, d_phiw, d_pTw;   // derived observables
     TabDev tab;
     std::vector<hipEvent_t> ev;   // [pass][0..2]: start, after coefficients + prep, after main; last: after finalize
     int last_passes = 0;
@@ -961,6 +962,14 @@ extern "C" int is3d_vah_plan_create(is3d_vah_plan **out, const is3d_species *sp,
         if (e != hipSuccess) return set_error(IS3D_ENODEVICE, "hipMalloc failed: %s", hipGetErrorString(e));
     }
     HIP_TRY(P->d_status.alloc(8 * sizeof(unsigned long long)));
+    {
+        std::vector<double> ck, sk;
+        is3d::vn_harmonics(gr->phi, J, ck, sk);
+        HIP_TRY(P->d_coskphi.upload(ck));
+        HIP_TRY(P->d_sinkphi.upload(sk));
+        HIP_TRY(P->d_phiw.alloc((size_t)J));
+        HIP_TRY(P->d_pTw.alloc((size_t)npT));
+    }
     *out = P.release();
     return IS3D_OK;
 }
@@ -1105,6 +1114,22 @@ extern "C" int is3d_vah_plan_timings(is3d_vah_plan *P, is3d_status *status)
     status->n_passes = P->last_passes;
     status->kernel_variant = P->fact ? 3 : 2;
     status->n_classes = P->ncls;
+    return IS3D_OK;
+}
+
+// the reductions of is3d_plan_observables (cf_plan.cpp) on a spectrum of this plan's shape: the same kernels, this plan's species and grid
+extern "C" int is3d_vah_plan_observables(is3d_vah_plan *P, const double *dN_dev, const double *pT_w, const double *phi_w, double *dNdy_dev,
+                                         double *dN2pipTdpTdy_dev, double *vn_dev, void *hip_stream)
+{
+    using is3d::set_error;
+    if (!P || !dN_dev || !phi_w) return set_error(IS3D_EINVAL, "null argument");
+    if (dNdy_dev && !pT_w) return set_error(IS3D_EINVAL, "dN/dy needs the pT weights");
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIP_TRY(hipSetDevice(P->device));
+    HIP_TRY(hipMemcpyAsync(P->d_phiw.p, phi_w, (size_t)P->J * sizeof(double), hipMemcpyHostToDevice, st));
+    if (pT_w) HIP_TRY(hipMemcpyAsync(P->d_pTw.p, pT_w, (size_t)P->npT * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(is3d::launch_observables(dN_dev, P->d_phiw.p, P->d_pTw.p, P->d_coskphi.p, P->d_sinkphi.p, dNdy_dev, dN2pipTdpTdy_dev, vn_dev,
+                                     P->npart, P->npT, P->J, P->Kacc, st));
     return IS3D_OK;
 }
 

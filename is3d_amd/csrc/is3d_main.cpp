@@ -119,7 +119,8 @@ int main(int argc, char **argv)
                    "  --generate-df writes the ten df coefficient tables of the hrg_eos list into DIR (default grid: T 0.1..0.2 GeV x 101,\n"
                    "  muB 0..0.8 GeV x 81, 64 Gauss-Laguerre nodes) and does nothing else; the optional parameter deltaf_dir = DIR makes a run read them\n"
                    "  operation = 1 shards the freezeout cells over the devices (default: every visible GPU; IS3D_DEVICES, IS3D_REDUCE)\n"
-                   "  mode = 5 shards the spin polarization over a device list given by --devices or IS3D_DEVICES (default: the first device alone)\n", argv[0], argv[0]);
+                   "  mode = 5 shards the spin polarization over a device list given by --devices or IS3D_DEVICES (default: the first device alone)\n"
+                   "  mode = 2 shards the anisotropic-hydro spectra over such a list in the same way (default: the first device alone)\n", argv[0], argv[0]);
             return 0;
         }
     }

@@ -15,7 +15,10 @@
 // mode = 2 (anisotropic hydro, P_L matching; BASELINE config 5): operation = 1 with df_mode = 4 -- the combination for which the
 // reference allocates the per-cell c0..c4 (emissionfunction.cpp:1397-1418) and the CUDA tree loads the VAH tables
 // (src/cuda/deltafReader.cu:74-81) -- reads input/surface.dat with read_surf_VAH_PLMatch and deltaf_coefficients/vah/c{0..4}_vah1.dat,
-// runs what the commented-out call site would (emissionfunction.cpp:1650-1654) and writes the same three result files.
+// runs what the commented-out call site would (emissionfunction.cpp:1650-1654) and writes the same three result files.  With a device list
+// that was spelled out (the list of is3d_run_particlization_on, --devices, IS3D_DEVICES) the cells are sharded over it
+// (is3d_smooth_spectra_vah_multi, the run's reduce); without one, or with a bare device count, the first device computes alone -- the rule of
+// mode 5 below -- so that a mode-2 run does not depend on how many devices a machine shows.
 // operation = 0 (smooth spacetime distributions, calculate_dN_dX; emissionfunction.cpp:1510-1516): mode in {0, 1, 4, 5, 6, 7}, df_mode in
 // {1, 2}, include_baryon in {0, 1}, dimension 2 or 3, the per-cell stage sharded over the run's device list and one bin stage on its first
 // device (is3d_spacetime_distributions_multi); reads tau_min ... r_bins (:216-222), writes
@@ -663,7 +666,15 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         const double **vf[25] = {&vc.tau, &vc.eta, &vc.ux, &vc.uy, &vc.un, &vc.dat, &vc.dax, &vc.day, &vc.dan, &vc.T, &vc.pitt, &vc.pitx, &vc.pity,
                                  &vc.pitn, &vc.pixx, &vc.pixy, &vc.pixn, &vc.piyy, &vc.piyn, &vc.pinn, &vc.bulkPi, &vc.Wx, &vc.Wy, &vc.Lambda, &vc.aL};
         for (int a = 0; a < 25; a++) *vf[a] = sa[a];
-        rc = is3d_smooth_spectra_vah_df(&vc, &sp, &grid, &vt, &opts, dN.data(), &st);
+        // a device list the user spelled out shards the cells; without one the first device computes alone, whatever the machine shows
+        if (rd.named) {
+            rc = is3d_smooth_spectra_vah_multi(&vc, &sp, &grid, &vt, &opts, rd.list.data(), (int32_t)rd.list.size(), rd.reduce, dN.data(), &st, nullptr);
+            const int nd = (int)rd.list.size();
+            printf("devices: %d (cell-axis shards of ~%lld cells%s)\n", nd, (long long)((n_cells + nd - 1) / std::max(nd, 1)),
+                   nd > 1 ? (rd.reduce == IS3D_REDUCE_RCCL ? ", RCCL all-reduce of the spectrum" : ", shard-ordered device sum of the spectrum") : "");
+        } else {
+            rc = is3d_smooth_spectra_vah_df(&vc, &sp, &grid, &vt, &opts, dN.data(), &st);
+        }
     } else if (feqmod) {
         printf("computing thermal spectra from vhydro with feqmod...\n");
         // emissionfunction.cpp:1309-1319: Gauss-Laguerre tables, Plasma::load_thermodynamic_averages (the file written
