@@ -722,6 +722,36 @@ int is3d_plan_execute_spacetime_feqmod(is3d_plan *plan, const is3d_cells *cells,
                                        const double *phi_w, const is3d_spacetime_bins *bins, const is3d_spacetime_out *out, void *hip_stream,
                                        is3d_spacetime_stats *stats, is3d_spacetime_feqmod_stats *fstats);
 
+/* Operation 0 for anisotropic hydro (mode 2, P_L matching).  The reference has no such routine -- calculate_dN_dX knows viscous hydro only --
+ * so THIS is the definition: the VAH analogue of calculate_dN_dX, with the integrand, the options and the domain rule of
+ * is3d_smooth_spectra_vah[_df] above: f_a (1 + fbar_a delta-f), include_bulk_deltaf, include_shear_deltaf, regulate_deltaf; NO outflow cut and
+ * NO skipped cells (a cell with u.dsigma <= 0 contributes its negative value and is binned); IS3D_EDOMAIN + stats->bad_cell for a cell whose
+ * E_a/Lambda can exceed 1e9 for the momentum grid or, with tables, whose (Lambda, alpha_L) lies beyond them.  Everything else is operation 0
+ * as stated above for df_mode 1 / 2:
+ *   dN_dy_cell[s][c] = pg_s D[class(s)][c],  D = sum_pT w_pT sum_phi w_phi sum_(y | eta) p.dsigma f;  the 3+1D y sum has no weights, the 2+1D eta
+ *   sum carries the VAH kernel's own weights eta_w[k] (eta[1] - eta[0]) (smooth_kernels.cpp:2175-2185);
+ *   dN_dy and the three histograms are the left-to-right sums of dN_dy_cell over the cells in ascending index (the same bin rule, RAW sums);
+ *   dN_dydeta: 3+1D one point, the species' total; 2+1D per eta node k that node's term of the sum divided by eta_w[k] (eta[1] - eta[0]).
+ * stats: n_cells_skipped is always 0; n_tau_outside, n_r_outside, n_tau_negative, n_r_negative count ALL cells outside a histogram (the
+ * df_mode 1 - 4 entries count the u.dsigma > 0 ones); bad_cell as above.  opts: dimension, include_bulk_deltaf, include_shear_deltaf,
+ * regulate_deltaf, device, workspace_bytes, collapse_species, zero_skip (exact zeros only: every value gives the same bits), kernel_variant 0 | 3
+ * (the per-cell kernel reads the default variant's records).  Several devices are not offered for this entry.
+ *
+ * One-shot, HOST pointers.  tab == NULL: c0..c4 come from the cells; otherwise they are interpolated on the device and cells->c0..c4 are ignored.
+ * Every argument check -- NULL x, y or weights, bins < 1, empty ranges, more than 64 pT values or an eta table beyond the per-cell kernel's LDS,
+ * kernel_variant other than 0 / 3, a NULL cell array that is read -- precedes any device use or plan creation (is3d_resource_counters is unchanged
+ * by a refusal); a good call without a device is IS3D_ENODEVICE. */
+int is3d_spacetime_distributions_vah(const is3d_vah_cells *cells, const double *x, const double *y, const is3d_species *species,
+                                     const is3d_grid *grid, const double *pT_w, const double *phi_w, const is3d_vah_df_tables *tab,
+                                     const is3d_options *opts, const is3d_spacetime_bins *bins, is3d_spacetime_out *out,
+                                     is3d_spacetime_stats *stats);
+/* the same on an is3d_vah_plan (with or without its coefficient tables; species classes, grids and the record stream shared with
+ * is3d_vah_plan_execute): cells, x, y and out are DEVICE pointers, pT_w and phi_w HOST memory; the plan's workspace_bytes cap bounds the passes
+ * (stats->n_passes).  Asynchronous on hip_stream; stats != NULL synchronises it and reports IS3D_EDOMAIN with stats->bad_cell. */
+int is3d_vah_plan_execute_spacetime(is3d_vah_plan *plan, const is3d_vah_cells *cells, const double *x, const double *y, const double *pT_w,
+                                    const double *phi_w, const is3d_spacetime_bins *bins, const is3d_spacetime_out *out, void *hip_stream,
+                                    is3d_spacetime_stats *stats);
+
 /* Operation 0 over several devices (one process): the cells are cut into the contiguous blocks of is3d_shard_bounds, shard s runs on
  * devices[s], all shards concurrently with one host thread and one stream each.  A shard uploads its cells, writes its records and runs the
  * per-cell stage (df_mode 3 / 4: with the renormalisation and the linearised delta-f of its own breakdown cells) on a plan of its own; its

@@ -118,7 +118,8 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_decay_plan_execute", "is3d_decay_plan_destroy", "is3d_write_results_decays",
            "is3d_sampler_bin_list", "is3d_write_sampler_tests_binned", "is3d_sampler_plan_execute_binned", "is3d_sample_binned", "is3d_sample_binned_multi",
            "is3d_sampler_bin_list_device", "is3d_df_generate", "is3d_df_tables_write",
-           "is3d_smooth_spectra_vah_multi", "is3d_vah_plan_observables"]
+           "is3d_smooth_spectra_vah_multi", "is3d_vah_plan_observables",
+           "is3d_spacetime_distributions_vah", "is3d_vah_plan_execute_spacetime"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 POLARIZATION_OUTPUTS = ["St", "Sx", "Sy", "Sn", "Snorm"]
@@ -352,6 +353,11 @@ def load():
                                                 C.POINTER(Options), C.POINTER(C.c_int32), C.c_int32, C.c_int32, _dp, C.POINTER(Status),
                                                 C.POINTER(Status)]
     L.is3d_vah_plan_observables.argtypes = [C.c_void_p, C.c_void_p, _dp, _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.is3d_spacetime_distributions_vah.argtypes = [C.POINTER(VahCells), _dp, _dp, C.POINTER(Species), C.POINTER(Grid), _dp, _dp,
+                                                   C.POINTER(VahDfTables), C.POINTER(Options), C.POINTER(SpacetimeBins), C.POINTER(SpacetimeOut),
+                                                   C.POINTER(SpacetimeStats)]
+    L.is3d_vah_plan_execute_spacetime.argtypes = [C.c_void_p, C.POINTER(VahCells), C.c_void_p, C.c_void_p, _dp, _dp, C.POINTER(SpacetimeBins),
+                                                  C.POINTER(SpacetimeOut), C.c_void_p, C.POINTER(SpacetimeStats)]
     _LIB = L
     return L
 
@@ -533,6 +539,35 @@ def surface_read_vah(path, dimension=3):
     return arrs
 
 
+def spacetime_distributions_vah(cells, species, grid, bins, opts=None, per_cell=False, tab=None):
+    """Operation 0 for anisotropic hydro (is3d_spacetime_distributions_vah): cells is a dict of host arrays per VAH_FIELDS plus "x" and "y";
+    grid needs pT_w and phi_w.  Returns the dict of spacetime_distributions -- the RAW bin sums dN_dy, dN_taudtaudy, dN_twopirdrdy,
+    dN_twopitaurdtaudrdy, dN_dydeta, with per_cell also dN_dy_cell -- and "stats".  tab (dict L, aL, c0..c4): the cells' c0..c4 are ignored,
+    the coefficients come from the (Lambda, alpha_L) tables.  Is3dError carries .bad_cell for IS3D_EDOMAIN."""
+    L = load()
+    sps, gs, _, os_, _, keep = _pack_common(species, grid, _VAH_DUMMY_DF, opts)
+    held = []
+    fields = {k: v for k, v in cells.items() if k in VAH_FIELDS and not (tab is not None and k in ("c0", "c1", "c2", "c3", "c4"))}
+    cs = _vah_cells_struct(fields, held)
+    n = cs.n_cells
+    xa = None if cells.get("x") is None else _f64(cells["x"])
+    ya = None if cells.get("y") is None else _f64(cells["y"])
+    pw, fw = _f64(grid["pT_w"]), _f64(grid["phi_w"])
+    shapes = spacetime_shapes(len(keep["sp"]["mass"]), n, bins, os_.dimension, len(keep["g"]["eta"]))
+    res = {k: np.zeros(v) for k, v in shapes.items() if k != "dN_dy_cell" or per_cell}
+    so = SpacetimeOut(*[res[k].ctypes.data if k in res else None for k in SPACETIME_OUTPUTS])
+    b = _spacetime_bins(bins)
+    st = SpacetimeStats()
+    ts = _pack_vah_tables(tab, keep) if tab is not None else None
+    rc = L.is3d_spacetime_distributions_vah(C.byref(cs), _p(xa) if xa is not None else None, _p(ya) if ya is not None else None, C.byref(sps),
+                                            C.byref(gs), _p(pw), _p(fw), C.byref(ts) if ts is not None else None, C.byref(os_), C.byref(b),
+                                            C.byref(so), C.byref(st))
+    if rc != 0:
+        raise Is3dError(rc, L.is3d_last_error().decode(), bad_cell=st.bad_cell)
+    res["stats"] = st.as_dict()
+    return res
+
+
 class VahPlan:
     """Device-resident VAH plan (is3d_vah_plan_*): cell arrays and the output are device pointers (ints); with `tab` the
     coefficients are interpolated on the device from (Lambda, aL) and c0..c4 need not be given."""
@@ -580,6 +615,20 @@ class VahPlan:
         pw, fw = None if pT_w is None else _f64(pT_w), _f64(phi_w)
         _check(load().is3d_vah_plan_observables(self._h, C.c_void_p(int(dN_ptr)), None if pw is None else _p(pw), _p(fw), C.c_void_p(int(dndy_ptr or 0)),
                                                 C.c_void_p(int(spec2pi_ptr or 0)), C.c_void_p(int(vn_ptr or 0)), C.c_void_p(int(stream or 0))))
+
+    def execute_spacetime(self, n_cells, cell_ptrs, x_ptr, y_ptr, pT_w, phi_w, bins, out_ptrs, stream=0, want_stats=True):
+        """is3d_vah_plan_execute_spacetime: as Plan.execute_spacetime -- cell arrays, x, y and the outputs (dict per SPACETIME_OUTPUTS,
+        dN_dy_cell optional) are device pointers (ints), the weights host arrays."""
+        cs = _vah_cells_struct(dict(cell_ptrs, n_cells=n_cells), None, device=True)
+        pw, fw = _f64(pT_w), _f64(phi_w)
+        so = SpacetimeOut(*[C.c_void_p(int(out_ptrs[k])) if out_ptrs.get(k) else None for k in SPACETIME_OUTPUTS])
+        b = _spacetime_bins(bins)
+        st = SpacetimeStats()
+        rc = load().is3d_vah_plan_execute_spacetime(self._h, C.byref(cs), C.c_void_p(int(x_ptr or 0)), C.c_void_p(int(y_ptr or 0)), _p(pw), _p(fw),
+                                                    C.byref(b), C.byref(so), C.c_void_p(int(stream or 0)), C.byref(st) if want_stats else None)
+        if rc != 0:
+            raise Is3dError(rc, load().is3d_last_error().decode(), bad_cell=st.bad_cell)
+        return st.as_dict() if want_stats else None
 
     def timings(self):
         st = Status()

@@ -81,8 +81,8 @@ struct is3d_plan {
     int64_t st_pass = 0, st_cap = 0;
     DevBuf<double> d_st_mT, d_st_pT, d_st_sign, d_st_b, d_st_wpT, d_st_wphi, d_st_pg, d_st_D, d_st_slab, d_st_eta;
     DevBuf<double> d_st_mass;   // feqmod: the lanes' masses (the linearised delta-f of the breakdown cells)
-    DevBuf<int32_t> d_st_cls, d_st_keys, d_st_cnt, d_st_tot, d_st_list;
-    DevBuf<int64_t> d_st_start;
+    DevBuf<int32_t> d_st_cls;
+    is3d::StBinWork st_bins;   // keys, lists and the scratch of the sorts (cf_spacetime.h)
     DevBuf<unsigned long long> d_st_counters;
 
     bool timing = false;
@@ -1143,40 +1143,23 @@ static int st_execute(is3d_plan *P, const is3d_cells *cells, const double *x, co
     HIP_TRY(hipMemsetAsync(P->d_st_counters.p, 0, 4 * sizeof(unsigned long long), st));
     HIP_TRY(mark());
 
-    // ---- bin stage, part 1: keys and the stable counting sort of every histogram (once per execute) ----
-    int32_t *keys[3] = {nullptr, nullptr, nullptr}, *lists[3] = {nullptr, nullptr, nullptr};
-    int64_t *starts[3] = {nullptr, nullptr, nullptr};
-    double *hout[3] = {nullptr, nullptr, nullptr};
+    // ---- bin stage (cf_spacetime.h), part 1: keys and the stable counting sort of every histogram (once per execute) ----
+    is3d::StBinStage bs{};
     const int64_t Bs[3] = {tb, rbn, trb};
+    double *hout[3] = {nullptr, nullptr, nullptr};
     if (do_bins) {
-        HIP_TRY(st_grow(P->d_st_keys, (size_t)3 * n));
-        HIP_TRY(st_grow(P->d_st_list, (size_t)3 * n));
-        HIP_TRY(st_grow(P->d_st_start, (size_t)(tb + 1) + (rbn + 1) + (trb + 1)));
-        int ntile[3];
-        size_t cnt_need = 1, tot_need = 1;
-        for (int h = 0; h < 3; h++) {
-            ntile[h] = is3d::spacetime_sort_tiles(n, Bs[h]);
-            cnt_need = std::max(cnt_need, (size_t)ntile[h] * Bs[h]);
-            tot_need = std::max(tot_need, (size_t)Bs[h]);
-        }
-        HIP_TRY(st_grow(P->d_st_cnt, cnt_need));
-        HIP_TRY(st_grow(P->d_st_tot, tot_need));
-        for (int h = 0; h < 3; h++) { keys[h] = P->d_st_keys.p + h * n; lists[h] = P->d_st_list.p + h * n; }
-        starts[0] = P->d_st_start.p; starts[1] = P->d_st_start.p + tb + 1; starts[2] = P->d_st_start.p + tb + 1 + rbn + 1;
-        hout[0] = out->dN_taudtaudy; hout[1] = out->dN_twopirdrdy; hout[2] = out->dN_twopitaurdtaudrdy;
-        const double dtau = (bins->tau_max - bins->tau_min) / (double)bins->tau_bins, dr = (bins->r_max - bins->r_min) / (double)bins->r_bins;
-        HIP_TRY(is3d::launch_spacetime_keys(cells->tau, cells->ux, cells->uy, cells->un, cells->dat, cells->dax, cells->day, cells->dan, x, y, n, bins->tau_min, dtau, bins->tau_bins, bins->r_min, dr, bins->r_bins, keys[0], keys[1],
-                                            keys[2], P->d_st_counters.p, st));
-        for (int h = 0; h < 3; h++)
-            HIP_TRY(is3d::launch_spacetime_sort(keys[h], n, Bs[h], ntile[h], P->d_st_cnt.p, P->d_st_tot.p, starts[h], lists[h], st));
+        bs.tau = cells->tau; bs.ux = cells->ux; bs.uy = cells->uy; bs.un = cells->un;
+        bs.dat = cells->dat; bs.dax = cells->dax; bs.day = cells->day; bs.dan = cells->dan; bs.x = x; bs.y = y;
+        bs.n = n; bs.cls = P->d_st_cls.p; bs.pg = P->d_st_pg.p; bs.S = S; bs.all_cells = 0;
+        bs.bins = bins; bs.out = out; bs.counters = P->d_st_counters.p;
+        rc = is3d::spacetime_bins_begin(P->st_bins, bs, st);
+        if (rc) return rc;
+        for (int h = 0; h < 3; h++) hout[h] = bs.hout[h];
         HIP_TRY(mark()); stage.push_back(2);
     }
     // ---- bin stage, part 2: a block of D, cells [c0, c0 + nc) in ascending order, onto the running sums ----
     auto sum_bins = [&](const double *D, int64_t nc, int64_t c0, int first) -> int {
-        HIP_TRY(is3d::launch_spacetime_segsum(D, nc, c0, P->d_st_cls.p, P->d_st_pg.p, S, nullptr, nullptr, 1, first, out->dN_dy, st));
-        for (int h = 0; h < 3; h++)
-            HIP_TRY(is3d::launch_spacetime_segsum(D, nc, c0, P->d_st_cls.p, P->d_st_pg.p, S, starts[h], lists[h], Bs[h], first, hout[h], st));
-        if (out->dN_dy_cell) HIP_TRY(is3d::launch_spacetime_per_cell(D, nc, c0, n, P->d_st_cls.p, P->d_st_pg.p, S, out->dN_dy_cell, st));
+        if (int r = is3d::spacetime_bins_add(bs, D, nc, c0, first, st)) return r;
         HIP_TRY(mark()); stage.push_back(2);
         return IS3D_OK;
     };

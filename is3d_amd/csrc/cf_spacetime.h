@@ -1,6 +1,7 @@
 // cf_spacetime.h -- launch entry points of cf_spacetime.hip (operation 0: smooth Cooper-Frye spacetime distributions).
 #pragma once
 #include "cf_device.h"
+#include "cf_host.h"
 #include <hip/hip_runtime_api.h>
 #include <cstdint>
 #include <functional>
@@ -60,12 +61,27 @@ hipError_t launch_spacetime_eta_shards(const double *parts, int nparts, int64_t 
 hipError_t launch_spacetime_eta_final(const double *eta_cls, const int32_t *cls, const double *pg, const double *w, int S, int K, double *out,
                                       hipStream_t st);
 
+// operation 0 for anisotropic hydro (cf_spacetime_vah.hip): the per-cell stage on cf_prep_vah's "F" records of one pass of nc cells (3+1D 8 x 7,
+// 2+1D 8 x 31), D[cls * nc + cell] = sum_pT w_pT sum_phi w_phi sum_(y | eta) p.dsigma f_a (1 + fbar_a df); 2+1D: eta_slab[chunk][cls][k]
+struct StVahCellArgs {
+    const double *TS;
+    int32_t nc, J, K, jtiles, rblocks;
+    int32_t ncls, npTp, nlw, G, nch;
+    int32_t zskip;
+    const double *lane_mT, *lane_pT, *lane_sign, *lane_wpT;            // [nlw * 64]
+    const double *wphi;                                                // [jtiles * JT], 0 past J
+    double *D;                                                         // [ncls][nc]
+    double *eta_slab;                                                  // 2+1D: [nch][ncls][K]
+};
+bool spacetime_vah_shape_supported(int dim3, int JT, int R);
+hipError_t launch_spacetime_vah_cells(const StVahCellArgs &a, int dim3, int regulate, int JT, int R, hipStream_t st);
+
 // bin stage: keys of every cell (tau bin, r bin, (tau, r) bin; -1 outside), counters[0..3] += live cells (u.dsigma > 0, the reference's
-// test at :1170) with tau bin outside [0, bins), r bin outside, tau bin < 0, r bin < 0
+// test at :1170; all_cells != 0: every cell -- anisotropic hydro skips none) with tau bin outside [0, bins), r bin outside, tau bin < 0, r bin < 0
 hipError_t launch_spacetime_keys(const double *tau, const double *ux, const double *uy, const double *un, const double *dat, const double *dax,
                                  const double *day, const double *dan, const double *x, const double *y, int64_t n, double tau_min, double dtau, int tau_bins,
                                  double r_min, double dr, int r_bins, int32_t *key_tau, int32_t *key_r, int32_t *key_tr,
-                                 unsigned long long *counters, hipStream_t st);
+                                 unsigned long long *counters, int all_cells, hipStream_t st);
 // stable counting sort of the cells by key: list[start[b] .. start[b + 1]) = the cells of bin b in ascending index order.
 // cnt: [ntile][B] ints of scratch, tot: [B], start: [B + 1]
 int spacetime_sort_tiles(int64_t n, int64_t B);
@@ -78,6 +94,30 @@ hipError_t launch_spacetime_segsum(const double *D, int64_t nc, int64_t c0, cons
 // per_cell[s * n_total + c0 + i] = pg[s] * D[cls[s] * nc + i]
 hipError_t launch_spacetime_per_cell(const double *D, int64_t nc, int64_t c0, int64_t n_total, const int32_t *cls, const double *pg, int S,
                                      double *per_cell, hipStream_t st);
+
+// ---- the bin stage over plain device arrays (is3d_plan and is3d_vah_plan alike): keys and the stable sort of every histogram once per
+// execute (begin), then blocks of D, cells [c0, c0 + nc) in ascending order, onto the running sums (add) ----
+struct StBinWork {   // scratch of the sorts, grown on demand and kept by the plan
+    DevBuf<int32_t> keys, cnt, tot, list;
+    DevBuf<int64_t> start;
+};
+struct StBinStage {
+    const double *tau, *ux, *uy, *un, *dat, *dax, *day, *dan, *x, *y;   // [n]: bin keys and the u.dsigma test of the counters
+    int64_t n;
+    const int32_t *cls;                                                 // [S] species -> class row of D
+    const double *pg;                                                   // [S] prefactor x degeneracy
+    int32_t S, all_cells;                                               // all_cells: see launch_spacetime_keys
+    const is3d_spacetime_bins *bins;
+    const is3d_spacetime_out *out;
+    unsigned long long *counters;                                       // [4], zeroed by the caller
+    // set by spacetime_bins_begin
+    int32_t *lists[3];
+    int64_t *starts[3], Bs[3];
+    double *hout[3];
+};
+int spacetime_bins_begin(StBinWork &w, StBinStage &s, hipStream_t st);
+// D: [class][nc]; first != 0 starts the sums, otherwise they continue from out
+int spacetime_bins_add(const StBinStage &s, const double *D, int64_t nc, int64_t c0, int first, hipStream_t st);
 
 // ---- the two halves of an execute, for the cell-axis split over devices (cf_multi.hip; defined in cf_plan.cpp) ----
 // ST_CELLS: records and the per-cell stage of a shard's cells; every pass's D block [class][nc] lands in D_full[class][n_total] at cell

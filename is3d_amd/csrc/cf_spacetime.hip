@@ -248,7 +248,7 @@ cf_st_keys(const double *__restrict__ tau, const double *__restrict__ ux, const 
            const double *__restrict__ dat, const double *__restrict__ dax, const double *__restrict__ day, const double *__restrict__ dan,
            const double *__restrict__ x, const double *__restrict__ y, int64_t n, double tau_min, double dtau,
            int tau_bins, double r_min, double dr, int r_bins, int32_t *__restrict__ key_tau, int32_t *__restrict__ key_r,
-           int32_t *__restrict__ key_tr, unsigned long long *__restrict__ counters)
+           int32_t *__restrict__ key_tr, unsigned long long *__restrict__ counters, int all_cells)
 {
 #pragma clang fp contract(off)
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -263,10 +263,10 @@ cf_st_keys(const double *__restrict__ tau, const double *__restrict__ ux, const 
         key_r[c] = ir;
         key_tr[c] = (in_t && in_r) ? it * r_bins + ir : -1;
         // the counts are over the cells the reference bins: it skips u.dsigma <= 0 before binning (:1160-1170, the same expression);
-        // a skipped cell is still listed in its bins, where it adds +0
+        // a skipped cell is still listed in its bins, where it adds +0.  all_cells: the anisotropic-hydro path skips no cell and counts every one
         const double tau2 = tau[c] * tau[c];
         const double ut = sqrt(1.0 + ux[c] * ux[c] + uy[c] * uy[c] + tau2 * un[c] * un[c]);
-        const bool live = ut * dat[c] + ux[c] * dax[c] + uy[c] * day[c] + un[c] * dan[c] > 0.0;
+        const bool live = all_cells || ut * dat[c] + ux[c] * dax[c] + uy[c] * day[c] + un[c] * dan[c] > 0.0;
         out_t = live && !in_t;
         out_r = live && !in_r;
         neg_t = live && qt < 0.0;
@@ -285,11 +285,11 @@ cf_st_keys(const double *__restrict__ tau, const double *__restrict__ ux, const 
 hipError_t launch_spacetime_keys(const double *tau, const double *ux, const double *uy, const double *un, const double *dat, const double *dax,
                                  const double *day, const double *dan, const double *x, const double *y, int64_t n, double tau_min, double dtau, int tau_bins,
                                  double r_min, double dr, int r_bins, int32_t *key_tau, int32_t *key_r, int32_t *key_tr,
-                                 unsigned long long *counters, hipStream_t st)
+                                 unsigned long long *counters, int all_cells, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(cf_st_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tau, ux, uy, un, dat, dax, day, dan, x, y, n, tau_min, dtau, tau_bins, r_min, dr, r_bins,
-                       key_tau, key_r, key_tr, counters);
+                       key_tau, key_r, key_tr, counters, all_cells);
     return hipGetLastError();
 }
 
@@ -475,6 +475,51 @@ hipError_t launch_spacetime_per_cell(const double *D, int64_t nc, int64_t c0, in
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(cf_st_per_cell, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, D, nc, c0, n_total, cls, pg, S, per_cell);
     return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// the bin stage over plain device arrays: what is3d_plan_execute_spacetime and is3d_vah_plan_execute_spacetime share
+// ------------------------------------------------------------------------------------------------
+template <class T>
+static hipError_t bins_grow(DevBuf<T> &buf, size_t n)
+{
+    if (buf.n >= n && buf.p) return hipSuccess;
+    return buf.alloc(std::max<size_t>(n, 1));
+}
+
+int spacetime_bins_begin(StBinWork &w, StBinStage &s, hipStream_t st)
+{
+    const int64_t n = s.n, tb = s.bins->tau_bins, rbn = s.bins->r_bins, trb = tb * rbn;
+    s.Bs[0] = tb; s.Bs[1] = rbn; s.Bs[2] = trb;
+    HIP_TRY(bins_grow(w.keys, (size_t)3 * n));
+    HIP_TRY(bins_grow(w.list, (size_t)3 * n));
+    HIP_TRY(bins_grow(w.start, (size_t)(tb + 1) + (rbn + 1) + (trb + 1)));
+    int ntile[3];
+    size_t cnt_need = 1, tot_need = 1;
+    for (int h = 0; h < 3; h++) {
+        ntile[h] = spacetime_sort_tiles(n, s.Bs[h]);
+        cnt_need = std::max(cnt_need, (size_t)ntile[h] * s.Bs[h]);
+        tot_need = std::max(tot_need, (size_t)s.Bs[h]);
+    }
+    HIP_TRY(bins_grow(w.cnt, cnt_need));
+    HIP_TRY(bins_grow(w.tot, tot_need));
+    int32_t *keys[3];
+    for (int h = 0; h < 3; h++) { keys[h] = w.keys.p + h * n; s.lists[h] = w.list.p + h * n; }
+    s.starts[0] = w.start.p; s.starts[1] = w.start.p + tb + 1; s.starts[2] = w.start.p + tb + 1 + rbn + 1;
+    s.hout[0] = s.out->dN_taudtaudy; s.hout[1] = s.out->dN_twopirdrdy; s.hout[2] = s.out->dN_twopitaurdtaudrdy;
+    const double dtau = (s.bins->tau_max - s.bins->tau_min) / (double)s.bins->tau_bins, dr = (s.bins->r_max - s.bins->r_min) / (double)s.bins->r_bins;
+    HIP_TRY(launch_spacetime_keys(s.tau, s.ux, s.uy, s.un, s.dat, s.dax, s.day, s.dan, s.x, s.y, n, s.bins->tau_min, dtau, s.bins->tau_bins, s.bins->r_min, dr,
+                                  s.bins->r_bins, keys[0], keys[1], keys[2], s.counters, s.all_cells, st));
+    for (int h = 0; h < 3; h++) HIP_TRY(launch_spacetime_sort(keys[h], n, s.Bs[h], ntile[h], w.cnt.p, w.tot.p, s.starts[h], s.lists[h], st));
+    return IS3D_OK;
+}
+
+int spacetime_bins_add(const StBinStage &s, const double *D, int64_t nc, int64_t c0, int first, hipStream_t st)
+{
+    HIP_TRY(launch_spacetime_segsum(D, nc, c0, s.cls, s.pg, s.S, nullptr, nullptr, 1, first, s.out->dN_dy, st));
+    for (int h = 0; h < 3; h++) HIP_TRY(launch_spacetime_segsum(D, nc, c0, s.cls, s.pg, s.S, s.starts[h], s.lists[h], s.Bs[h], first, s.hout[h], st));
+    if (s.out->dN_dy_cell) HIP_TRY(launch_spacetime_per_cell(D, nc, c0, s.n, s.cls, s.pg, s.S, s.out->dN_dy_cell, st));
+    return IS3D_OK;
 }
 
 }  // namespace is3d

@@ -12,7 +12,7 @@
 // average_thermodynamic_quantities.dat (readindata.cpp:464-466).
 // operation = 2 (particle sampler; df_mode 1-4, fast in {0, 1}, include_baryon = 1 with df_mode 1-3) writes
 // results/particle_list_osc.dat (write_particle_list_OSC, emissionfunction.cpp:863-901) and results/dN_dy_*.dat is skipped.
-// mode = 2 (anisotropic hydro, P_L matching; BASELINE config 5): operation = 1 with df_mode = 4 -- the combination for which the
+// mode = 2 (anisotropic hydro, P_L matching; BASELINE config 5): operation = 1 (or 0, below) with df_mode = 4 -- the combination for which the
 // reference allocates the per-cell c0..c4 (emissionfunction.cpp:1397-1418) and the CUDA tree loads the VAH tables
 // (src/cuda/deltafReader.cu:74-81) -- reads input/surface.dat with read_surf_VAH_PLMatch and deltaf_coefficients/vah/c{0..4}_vah1.dat,
 // runs what the commented-out call site would (emissionfunction.cpp:1650-1654) and writes the same three result files.  With a device list
@@ -24,7 +24,9 @@
 // device (is3d_spacetime_distributions_multi); reads tau_min ... r_bins (:216-222), writes
 // results/spacetime_distribution/{dN_taudtaudy, dN_twopirdrdy, dN_twopitaurdtaudrdy}_<id>.dat and dN_dydeta_<id>_<n>pt.dat (the directory must
 // exist) and prints one "dN_dy = %lf" line per species; no momentum-spectra file (those are written for operation = 1 only, :1678).  df_mode 3 / 4
-// (calculate_dN_dX_feqmod) and mode 2 are refused before anything is written.
+// (calculate_dN_dX_feqmod) with those modes is refused before anything is written.  mode = 2 with df_mode = 4 runs the anisotropic-hydro form
+// (is3d_spacetime_distributions_vah; the reference has none): the same parameters, files and lines from the mode-2 surface and the
+// deltaf_coefficients/vah tables, on the first device of the run's list.
 // do_resonance_decays = 1 (optional key): with operation = 1 and hrg_eos = 1 or 2, the thermal files are written as without it, then the
 // feed-down (is3d_resonance_decays) runs on the spectrum on the first device of the run's list and results/dN_pTdpTdphidy_resonance_decays.dat
 // and dN_dpTdphidy_resonance_decays.dat are appended (emissionfunction.cpp:1689-1698); the embedding result keeps the thermal spectrum.
@@ -207,9 +209,9 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
     if (operation != 0 && operation != 1 && operation != 2)
         DIE("operation = %d: operation = 0 (smooth spacetime distributions), 1 (smooth momentum spectra) and 2 (particle sampler) are on this path", operation);
     if (operation == 0) {
-        if (df_mode == 3 || df_mode == 4)
+        // mode = 2 (anisotropic hydro; df_mode = 4 is checked below) has its own routine, is3d_spacetime_distributions_vah
+        if ((df_mode == 3 || df_mode == 4) && !(!mem && mode == 2))
             DIE("operation = 0 with df_mode = %d (calculate_dN_dX_feqmod) is not run by this driver yet (the library entry is3d_spacetime_distributions_feqmod has it): set df_mode = 1 or 2", df_mode);
-        if (!mem && mode == 2) DIE("operation = 0 with mode = 2: the reference has no spacetime distribution for anisotropic hydro");
         if (mem && (!mem_x || !mem_y)) DIE("operation = 0 needs the cells' x and y positions (NULL given)");
     }
     bool do_decays = false;
@@ -239,7 +241,7 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
     }
     const bool vah = !mem && mode == 2;
     if (vah) {
-        if (operation != 1) DIE("mode = 2 (anisotropic hydro): only operation = 1; the reference's VAH sampler is an empty stub (emissionfunction_sampling_kernels.cpp:1231-1239)");
+        if (operation == 2) DIE("mode = 2 (anisotropic hydro): operation = 0 or 1; the reference's VAH sampler is an empty stub (emissionfunction_sampling_kernels.cpp:1231-1239)");
         if (df_mode != 4) DIE("mode = 2 (anisotropic hydro) needs df_mode = 4: the per-cell 14-moment coefficients c0..c4 exist for that combination only (emissionfunction.cpp:1410-1418)");
     }
     if (!mem && !vah && mode != 0 && mode != 1 && mode != 4 && mode != 5 && mode != 6 && mode != 7)
@@ -433,6 +435,23 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         if (rd.named) printf("polarization: %d shard%s; slowest shard's cells %.3f ms\n", (int)pss.size(), pss.size() == 1 ? "" : "s", pst.ms_cells);
         return IS3D_OK;
     };
+    // ---- mode 2: the surface's cell arrays and the deltaf_coefficients/vah tables (what src/cuda/deltafReader.cu:224-278 would have put into the surface) ----
+    std::vector<double> vah_L, vah_aL, vah_c;
+    is3d_vah_df_tables vt{};
+    is3d_vah_cells vc{};
+    if (vah) {
+        int32_t nL = 0, naL = 0;
+        if (is3d_vah_df_read("deltaf_coefficients/vah", &nL, &naL, nullptr, nullptr, nullptr, 0)) DIE("%s", is3d_last_error());
+        vah_L.resize((size_t)nL); vah_aL.resize((size_t)naL); vah_c.resize((size_t)5 * nL * naL);
+        if (is3d_vah_df_read("deltaf_coefficients/vah", &nL, &naL, vah_L.data(), vah_aL.data(), vah_c.data(), (int64_t)vah_c.size())) DIE("%s", is3d_last_error());
+        const size_t tn = (size_t)nL * naL;
+        vt = is3d_vah_df_tables{nL, naL, vah_L.data(), vah_aL.data(), vah_c.data(), vah_c.data() + tn, vah_c.data() + 2 * tn, vah_c.data() + 3 * tn,
+                                vah_c.data() + 4 * tn};
+        vc.n_cells = n_cells;
+        const double **vf[25] = {&vc.tau, &vc.eta, &vc.ux, &vc.uy, &vc.un, &vc.dat, &vc.dax, &vc.day, &vc.dan, &vc.T, &vc.pitt, &vc.pitx, &vc.pity,
+                                 &vc.pitn, &vc.pixx, &vc.pixy, &vc.pixn, &vc.piyy, &vc.piyn, &vc.pinn, &vc.bulkPi, &vc.Wx, &vc.Wy, &vc.Lambda, &vc.aL};
+        for (int a = 0; a < 25; a++) *vf[a] = sa[a];
+    }
     const int ny_eff = (dimension == 2) ? 1 : (int)y.size();
     std::vector<double> dN(mcid.size() * pT.size() * phi.size() * (size_t)ny_eff, 0.0);
     if (operation == 2) {
@@ -602,7 +621,8 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
             get_param("r_max", &r1b) || get_param("r_bins", &rb))
             return IS3D_EINVAL;
         is3d_spacetime_bins bins{t0b, t1b, r0b, r1b, (int32_t)tb, (int32_t)rb};
-        const double *xp = mem ? mem_x : sa[23], *yp = mem ? mem_y : sa[24];
+        // x and y: arrays 23, 24 of the viscous-hydro surfaces, the last two of is3d_surface_read_vah's 32
+        const double *xp = mem ? mem_x : sa[vah ? 30 : 23], *yp = mem ? mem_y : sa[vah ? 31 : 24];
         std::vector<double> zero(1, 0.0);
         if (n_cells == 0) xp = yp = zero.data();
         const int S = sp.n, n_eta_eff = dimension == 3 ? 1 : (int)eta.size();
@@ -611,25 +631,30 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         is3d_spacetime_out out{o_dy.data(), o_t.data(), o_r.data(), o_tr.data(), o_eta.data(), nullptr};
         for (int ip = 0; ip < S; ip++) printf("Starting spacetime distribution %lld\n", (long long)mcid[ip]);   // :1100
         is3d_spacetime_stats sst{};
-        // the per-cell stage on cell-axis shards over the run's devices, one bin stage on the first (is3d_spacetime_distributions_multi)
-        const int rc0 = is3d_spacetime_distributions_multi(&cells, xp, yp, &sp, &grid, pTw.data(), phiw.data(), &df, nullptr, &opts,
-                                                           rd.list.empty() ? nullptr : rd.list.data(), (int32_t)rd.list.size(), &bins, &out, &sst,
-                                                           nullptr);
-        {
+        int rc0;
+        if (vah) {
+            // anisotropic hydro: the first device of the run's list computes alone (opts.device), whatever the list holds
+            printf("computing spacetime distributions from vahydro (P_L matching) with df...\n");
+            rc0 = is3d_spacetime_distributions_vah(&vc, xp, yp, &sp, &grid, pTw.data(), phiw.data(), &vt, &opts, &bins, &out, &sst);
+        } else {
+            // the per-cell stage on cell-axis shards over the run's devices, one bin stage on the first (is3d_spacetime_distributions_multi)
+            rc0 = is3d_spacetime_distributions_multi(&cells, xp, yp, &sp, &grid, pTw.data(), phiw.data(), &df, nullptr, &opts,
+                                                     rd.list.empty() ? nullptr : rd.list.data(), (int32_t)rd.list.size(), &bins, &out, &sst, nullptr);
             const int nd = rd.list.empty() ? is3d_device_count() : (int)rd.list.size();
             printf("devices: %d (cell-axis shards of ~%lld cells%s)\n", nd, (long long)((n_cells + nd - 1) / std::max(nd, 1)),
                    nd > 1 ? ", one bin stage over the assembled per-cell values" : "");
         }
         if (rc0) {
             const std::string msg = is3d_last_error();
-            DIE("is3d_spacetime_distributions_multi failed (%d): %s", rc0, msg.c_str());
+            DIE("%s failed (%d): %s", vah ? "is3d_spacetime_distributions_vah" : "is3d_spacetime_distributions_multi", rc0, msg.c_str());
         }
         // the reference prints an error line per cell with a negative bin index (:1391-1392); one line with the counts here
         if (sst.n_tau_negative || sst.n_r_negative)
             printf("Error: %lld cells with a negative tau bin index, %lld with a negative r bin index. Adjust the tau_min / r_min parameters\n",
                    (long long)sst.n_tau_negative, (long long)sst.n_r_negative);
         // 3+1D: the single eta point is eta_fo of the surface's last cell (etaValues[0], assigned at :1155 before the skip test)
-        std::vector<double> eta_vals = dimension == 3 ? std::vector<double>(1, n_cells > 0 ? cells.eta[n_cells - 1] : 0.0) : eta;
+        const double *eta_fo = vah ? vc.eta : cells.eta;
+        std::vector<double> eta_vals = dimension == 3 ? std::vector<double>(1, n_cells > 0 ? eta_fo[n_cells - 1] : 0.0) : eta;
         if (is3d_write_spacetime("results/spacetime_distribution", &bins, S, mcid.data(), n_eta_eff, eta_vals.data(), &out))
             DIE("%s", is3d_last_error());
         for (int ip = 0; ip < S; ip++) printf("dN_dy = %lf\n", o_dy[ip]);   // :1438-1441
@@ -655,17 +680,6 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         // the call the reference has commented out (emissionfunction.cpp:1650-1654), with the coefficients the CUDA tree's reader
         // would have put into the surface (src/cuda/deltafReader.cu:224-278)
         printf("computing thermal spectra from vahydro (P_L matching) with df...\n");
-        int32_t nL = 0, naL = 0;
-        if (is3d_vah_df_read("deltaf_coefficients/vah", &nL, &naL, nullptr, nullptr, nullptr, 0)) DIE("%s", is3d_last_error());
-        std::vector<double> Lg((size_t)nL), ag((size_t)naL), ct((size_t)5 * nL * naL);
-        if (is3d_vah_df_read("deltaf_coefficients/vah", &nL, &naL, Lg.data(), ag.data(), ct.data(), (int64_t)ct.size())) DIE("%s", is3d_last_error());
-        const size_t tn = (size_t)nL * naL;
-        is3d_vah_df_tables vt{nL, naL, Lg.data(), ag.data(), ct.data(), ct.data() + tn, ct.data() + 2 * tn, ct.data() + 3 * tn, ct.data() + 4 * tn};
-        is3d_vah_cells vc{};
-        vc.n_cells = n_cells;
-        const double **vf[25] = {&vc.tau, &vc.eta, &vc.ux, &vc.uy, &vc.un, &vc.dat, &vc.dax, &vc.day, &vc.dan, &vc.T, &vc.pitt, &vc.pitx, &vc.pity,
-                                 &vc.pitn, &vc.pixx, &vc.pixy, &vc.pixn, &vc.piyy, &vc.piyn, &vc.pinn, &vc.bulkPi, &vc.Wx, &vc.Wy, &vc.Lambda, &vc.aL};
-        for (int a = 0; a < 25; a++) *vf[a] = sa[a];
         // a device list the user spelled out shards the cells; without one the first device computes alone, whatever the machine shows
         if (rd.named) {
             rc = is3d_smooth_spectra_vah_multi(&vc, &sp, &grid, &vt, &opts, rd.list.data(), (int32_t)rd.list.size(), rd.reduce, dN.data(), &st, nullptr);

@@ -21,6 +21,6 @@ echo "== library host code: hipcc -x c++ -fsanitize=address (device objects unch
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 C="$R/is3d_amd/csrc"; L="$R/is3d_amd/lib"
 for f in host_io is3d_run; do $HIPCC -O1 -g -std=c++17 -fPIC -fsanitize=address -fno-omit-frame-pointer -x c++ -c "$C/$f.cpp" -o "$T/$f.o"; done
-$HIPCC --offload-arch=gfx950 -shared -pthread -fsanitize=address -shared-libasan -o "$L/libis3d_amd.so" "$L/cf_kernels.o" "$L/cf_feqmod.o" "$L/cf_sampler.o" "$L/cf_sampler_bins.o" "$L/cf_vah.o" "$L/cf_multi.o" "$L/cf_yield.o" "$L/cf_spacetime.o" "$L/cf_spacetime_feqmod.o" "$L/cf_polzn.o" "$L/cf_decays.o" "$L/cf_dfgen.o" "$L/cf_plan.o" "$T/host_io.o" "$T/is3d_run.o" -ldl
+$HIPCC --offload-arch=gfx950 -shared -pthread -fsanitize=address -shared-libasan -o "$L/libis3d_amd.so" "$L/cf_kernels.o" "$L/cf_feqmod.o" "$L/cf_sampler.o" "$L/cf_sampler_bins.o" "$L/cf_vah.o" "$L/cf_multi.o" "$L/cf_yield.o" "$L/cf_spacetime.o" "$L/cf_spacetime_feqmod.o" "$L/cf_spacetime_vah.o" "$L/cf_polzn.o" "$L/cf_decays.o" "$L/cf_dfgen.o" "$L/cf_plan.o" "$T/host_io.o" "$T/is3d_run.o" -ldl
 RT=$(find /opt/rocm/lib/llvm -name "libclang_rt.asan*x86_64*.so" | head -1)
 ASAN_OPTIONS=detect_leaks=0:halt_on_error=1:verify_asan_link_order=0 LD_PRELOAD=$RT python -m pytest tests/test_host_io.py tests/test_sampler_bins_io.py tests/test_abi.py -x -q
