@@ -138,6 +138,8 @@ def test_order_of_additions_and_counters(fx, dim):
 def test_bitwise_invariances(fx, dim):
     cells, res = run(fx, dim)
     sp, g, bins = species(fx, dim), wgrid(fx), surface_bins(cells)
+    # cell_chunks is not read on this path (the chunk count comes from the lane waves: is3d_vah_plan_execute_spacetime): that entry only proves
+    # the option harmless.  Chunks of more than one cell run in tests/test_gpu_spacetime_vah_offtile.py.
     for extra in (dict(), dict(workspace_bytes=SMALL_WS), dict(cell_chunks=3), dict(zero_skip=2)):
         got = api.spacetime_distributions_vah(cells, sp, g, bins, dict(dimension=dim, **extra), per_cell=True)
         if "workspace_bytes" in extra:
