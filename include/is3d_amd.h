@@ -552,6 +552,42 @@ int is3d_sample_particles_multi(const is3d_cells *cells, const is3d_species *spe
                                 const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices, int32_t n_devices,
                                 is3d_particle *particles, int64_t capacity, int64_t *n_particles, is3d_sampler_stats *stats);
 
+/* Particle sampler for anisotropic hydro (mode 2, operation 2).  The reference's sample_dN_pTdpTdphidy_VAH_PL is an empty stub, so THIS is
+ * the definition: the VAH analogue of sample_dN_pTdpTdphidy in regular mode (fast = 0).  The leading-order distribution f_a is an equilibrium
+ * distribution at the stretched momentum p' = (p_x, p_y, p_z / alpha_L) of the local rest frame, so the sampler is the reference's df_mode-4
+ * construction -- sample isotropically, map the momentum linearly -- with the residual delta-f of is3d_smooth_spectra_vah as a viscous weight.
+ * Per cell, with the basis, the dsigma boost and ds_max = |dsigma_t| + |dsigma_space| (local rest frame) of is3d_sample_particles:
+ *   - u.dsigma <= 0: skipped, counted in stats->n_cells_skipped.
+ *   - Lambda or alpha_L not finite and > 0, or (with tab) a cell beyond the last node of the tables: a bad cell (so are a Lambda above 1e4
+ *     times a boson's mass, where the momentum sampler's rejection bound ends, and a mean hadron number >= 2^31).  IS3D_EDOMAIN naming the
+ *     lowest global index ("cell N: ..."); the other cells are sampled all the same and the list, *n_particles and stats are returned with
+ *     the error.  No rejection loop is entered with such a scale.
+ *   - bound density per species dn_s = 2 alpha_L g_s Lambda^3 / (2 pi^2 hbarc^3) GaussThermal(neq_int; m_s / Lambda, sign_s): the 14-moment
+ *     bound 2 n_eq with T -> Lambda, alpha_L the Jacobian d^3p = alpha_L d^3p'; species added in list order;
+ *     dn_tot = (sum_s dn_s) 2 y_max ds_max, y_max = y_cut (2+1D) | 0.5 (3+1D).
+ *   - draws: the Poisson number, the species and the momentum from the counter-based streams of is3d_sample_particles (same key, same five
+ *     roles); p' = sample_momentum(m, sign, T = Lambda, chem = 0); local-rest-frame momentum (p'_x, p'_y, alpha_L p'_z), E = sqrt(m^2 + p^2),
+ *     boosted to the lab frame as there.
+ *   - weights: w_flux = max(0, E dsigma_t - p.dsigma_space) / (E ds_max) with the stretched momentum; w_visc = (1 + clamp(fbar_a df, -1, 1)) / 2
+ *     with df = c3 (p.z)(W.p) + c4 pi_perp^{mu nu} p_mu p_nu (include_shear_deltaf) + (c0 m^2 + c1 (p.z)^2 + c2 (p.u)^2) Pi
+ *     (include_bulk_deltaf) at the hadron's momentum and fbar_a = 1 - sign f_a, E_a = E' (the energy of p'); kept when u_keep < w_flux w_visc.
+ *   - the 2+1D rapidity draw, eta, t, z, x, y and the is3d_particle fields: as is3d_sample_particles.
+ * The expected number of kept hadrons of species s is the integral of d^3p / E max(p.dsigma, 0) f_a (1 + clamp(fbar_a df)): the smooth VAH
+ * spectrum with regulate_deltaf = 1 and an outflow cut, integrated over momentum.
+ * HOST pointers.  tab == NULL: c0..c4 from the cells; else they are interpolated on the device (is3d_vah_coefficients) and cells->c0..c4 may be
+ * NULL.  cells->T is not read; eta only in 3+1D; pi_perp, Wx, Wy only with include_shear_deltaf; bulkPi only with include_bulk_deltaf.
+ * Calling pattern, ordering (event, cell, draw), IS3D_ENOMEM rule and stats: is3d_sample_particles.  in->fast != 0, a non-NULL in->feqmod,
+ * a NULL cell array that would be read, n_events < 1 and n_gla outside 1..256 are IS3D_EINVAL before any device use; a good call without a
+ * device is IS3D_ENODEVICE. */
+int is3d_sample_particles_vah(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab,
+                              const is3d_sampler_inputs *in, const is3d_options *opts, is3d_particle *particles, int64_t capacity,
+                              int64_t *n_particles, is3d_sampler_stats *stats);
+/* is3d_sample_particles_vah over several devices, as is3d_sample_particles_multi: contiguous cell shards, first_cell advanced per shard, the
+ * lists merged into the single-device order; no collective.  The same refusals, before any device use; opts->device is ignored. */
+int is3d_sample_particles_vah_multi(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab,
+                                    const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices, int32_t n_devices,
+                                    is3d_particle *particles, int64_t capacity, int64_t *n_particles, is3d_sampler_stats *stats);
+
 /* EmissionFunctionArray::calculate_total_yield (src/cpp/emissionfunction_sampling_kernels.cpp:653-830; call sites
  * emissionfunction.cpp:1527, :1591): the mean particle yield of the surface, from which an oversampled run takes its number of
  * events, Nevents = min(ceil(min_num_hadrons / |yield|), max_num_samples) (emissionfunction.cpp:1524-1533).  Species densities

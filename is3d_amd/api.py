@@ -6,6 +6,7 @@ PyTorch is used by callers for device memory and streams; this module itself nee
 """
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -119,7 +120,8 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_sampler_bin_list", "is3d_write_sampler_tests_binned", "is3d_sampler_plan_execute_binned", "is3d_sample_binned", "is3d_sample_binned_multi",
            "is3d_sampler_bin_list_device", "is3d_df_generate", "is3d_df_tables_write",
            "is3d_smooth_spectra_vah_multi", "is3d_vah_plan_observables",
-           "is3d_spacetime_distributions_vah", "is3d_vah_plan_execute_spacetime"]
+           "is3d_spacetime_distributions_vah", "is3d_vah_plan_execute_spacetime",
+           "is3d_sample_particles_vah", "is3d_sample_particles_vah_multi"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 POLARIZATION_OUTPUTS = ["St", "Sx", "Sy", "Sn", "Snorm"]
@@ -1574,6 +1576,69 @@ def sample_particles(cells, species, df, gla, opts=None, n_events=1, seed=1, y_c
     d = st.as_dict()
     d["n_particles"] = int(cnt.value)
     return out[:min(int(cnt.value), int(capacity))], d
+
+
+def sample_particles_vah(cells, species, gla, opts=None, tab=None, n_events=1, seed=1, y_cut=0.5, first_cell=0, capacity=None, batch_events=0,
+                         devices=None, fast=0, fq=None):
+    """is3d_sample_particles_vah: the particle sampler for anisotropic hydro (mode 2, operation 2).  cells: dict of host arrays per VAH_FIELDS
+    (x, y optional); gla: dict with root1, weight1; tab (dict L, aL, c0..c4): the coefficients come from the (Lambda, alpha_L) tables and the
+    cells' c0..c4 are ignored.  devices: is3d_sample_particles_vah_multi, one cell shard per listed device (an ordinal may repeat).  Returns
+    (numpy structured array of PARTICLE_DTYPE, stats dict); capacity = None sizes the buffer from a count-only first call.  A bad cell raises
+    Is3dError(IS3D_EDOMAIN) with .bad_cell (the lowest global index), .particles and .stats: the other cells are sampled all the same.
+    fast, fq: passed on only so that the entry's refusals can be reached."""
+    L = load()
+    sps, _, _, os_, _, keep = _pack_common(species, dict(pT=[1.0], phi=[0.0], y=[0.0], eta=[0.0], eta_w=[1.0]), _VAH_DUMMY_DF, opts)
+    held = [keep]
+    if tab is not None:
+        cells = {k: v for k, v in cells.items() if k not in ("c0", "c1", "c2", "c3", "c4")}
+    cs = _vah_cells_struct(cells, held)
+    ts = _pack_vah_tables(tab, keep) if tab is not None else None
+    r1, w1 = _f64(gla["root1"]), _f64(gla["weight1"])
+    xs = _f64(cells["x"]) if cells.get("x") is not None else None
+    ys = _f64(cells["y"]) if cells.get("y") is not None else None
+    fqs = _pack_feqmod(fq, keep) if fq is not None else None
+    si = SamplerInputs(int(n_events), len(r1), int(seed), float(y_cut), int(first_cell), _p(xs) if xs is not None else None,
+                       _p(ys) if ys is not None else None, _p(r1), _p(w1), C.pointer(fqs) if fqs is not None else None, int(fast), int(batch_events),
+                       0.0, 0.0, 0.0)
+    st = SamplerStats()
+    cnt = C.c_int64(0)
+    tp = C.byref(ts) if ts is not None else None
+    head = [C.POINTER(VahCells), C.POINTER(Species), C.POINTER(VahDfTables), C.POINTER(SamplerInputs), C.POINTER(Options)]
+    tail = [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
+    L.is3d_sample_particles_vah.argtypes = head + tail
+    L.is3d_sample_particles_vah_multi.argtypes = head + [C.POINTER(C.c_int32), C.c_int32] + tail
+    if devices is not None:
+        dv, nd, _ = _pack_devices(devices)
+
+        def call(buf, cap):
+            return L.is3d_sample_particles_vah_multi(C.byref(cs), C.byref(sps), tp, C.byref(si), C.byref(os_), dv, nd, buf, cap, C.byref(cnt), C.byref(st))
+    else:
+        def call(buf, cap):
+            return L.is3d_sample_particles_vah(C.byref(cs), C.byref(sps), tp, C.byref(si), C.byref(os_), buf, cap, C.byref(cnt), C.byref(st))
+    if capacity is None:
+        rc = call(None, 0)
+        if rc != IS3D_EDOMAIN:
+            _check(rc)
+        capacity = int(cnt.value)
+    out = np.zeros(max(int(capacity), 1), dtype=PARTICLE_DTYPE)
+    assert out.dtype.itemsize == C.sizeof(Particle)
+    rc = call(out.ctypes.data, int(capacity))
+    d = st.as_dict()
+    d["n_particles"] = int(cnt.value)
+    out = out[:min(int(cnt.value), int(capacity))]
+    if rc == IS3D_EDOMAIN:
+        msg = L.is3d_last_error().decode()
+        m = re.search(r"cell (\d+):", msg)
+        e = Is3dError(rc, msg, bad_cell=int(m.group(1)) if m else None)
+        e.particles, e.stats = out, d
+        raise e
+    _check(rc)
+    return out, d
+
+
+def sample_particles_vah_multi(cells, species, gla, opts=None, devices=(0,), **kw):
+    """is3d_sample_particles_vah_multi: one cell shard per entry of devices (an ordinal may repeat); the list equals sample_particles_vah's."""
+    return sample_particles_vah(cells, species, gla, opts, devices=list(devices), **kw)
 
 
 class SamplerPlan:

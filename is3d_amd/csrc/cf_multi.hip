@@ -29,6 +29,7 @@
 #include "../../include/is3d_amd.h"
 #include "cf_host.h"
 #include "cf_polzn.h"
+#include "cf_sampler_common.h"
 #include "cf_spacetime.h"
 #include "errors.h"
 
@@ -1127,6 +1128,25 @@ int sampler_totals(const std::vector<S> &sh, int64_t *n_particles, is3d_sampler_
     if (stats) *stats = agg;
     return IS3D_OK;
 }
+// every shard list is ordered by (event, cell, draw) and the shards are ascending cell ranges, so the single-device order is, event by
+// event, shard 0's hadrons of that event, then shard 1's, ...
+template <class S>
+void merge_shard_lists(const std::vector<S> &sh, int32_t n_events, is3d_particle *particles, int64_t capacity)
+{
+    std::vector<size_t> pos(sh.size(), 0);
+    int64_t out = 0;
+    for (int32_t ev = 0; ev < n_events; ev++)
+        for (size_t i = 0; i < sh.size(); i++) {
+            const std::vector<is3d_particle> &l = sh[i].list;
+            size_t p = pos[i];
+            while (p < l.size() && l[p].event == ev) {
+                if (out < capacity) particles[out] = l[p];
+                out++;
+                p++;
+            }
+            pos[i] = p;
+        }
+}
 }  // namespace
 
 extern "C" int is3d_sample_particles_multi(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df,
@@ -1165,22 +1185,78 @@ extern "C" int is3d_sample_particles_multi(const is3d_cells *cells, const is3d_s
     });
     if (int rc = sampler_totals(sh, n_particles, stats)) return rc;
     if (!fill) return IS3D_OK;
-    // merge: every shard list is ordered by (event, cell, draw) and the shards are ascending cell ranges, so the single-device order is,
-    // event by event, shard 0's hadrons of that event, then shard 1's, ...
-    std::vector<size_t> pos(n_devices, 0);
-    int64_t out = 0;
-    for (int32_t ev = 0; ev < in->n_events; ev++)
-        for (int i = 0; i < n_devices; i++) {
-            const std::vector<is3d_particle> &l = sh[i].list;
-            size_t p = pos[i];
-            while (p < l.size() && l[p].event == ev) {
-                if (out < capacity) particles[out] = l[p];
-                out++;
-                p++;
-            }
-            pos[i] = p;
-        }
+    merge_shard_lists(sh, in->n_events, particles, capacity);
     if (*n_particles > capacity)
+        return fail(IS3D_ENOMEM, "particle buffer too small: %lld particles, capacity %lld", (long long)*n_particles, (long long)capacity);
+    return IS3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// anisotropic-hydro particle sampler (is3d_sample_particles_vah) over several devices: the same shards, first_cell advanced, the same merge
+// ------------------------------------------------------------------------------------------------
+extern "C" int is3d_sample_particles_vah_multi(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab,
+                                               const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices,
+                                               int32_t n_devices, is3d_particle *particles, int64_t capacity, int64_t *n_particles,
+                                               is3d_sampler_stats *stats)
+{
+    if (!n_particles) return fail(IS3D_EINVAL, "null argument");
+    *n_particles = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (int rc = is3d::sampler_vah_check(cells, species, tab, in, opts)) return rc;
+    std::vector<int> dev;
+    if (int rc = resolve_devices(devices, n_devices, dev)) return rc;
+    n_devices = (int32_t)dev.size();
+    if (particles == nullptr) capacity = 0;
+    if (n_devices == 1) {
+        is3d_options o = *opts;
+        o.device = dev[0];
+        return is3d_sample_particles_vah(cells, species, tab, in, &o, particles, capacity, n_particles, stats);
+    }
+    struct VShard : ShardBase {
+        is3d_vah_cells c;
+        is3d_sampler_inputs si;
+        is3d_options o;
+        int64_t count = 0;
+        is3d_sampler_stats st{};
+        std::vector<is3d_particle> list;
+    };
+    DeviceRestore restore;
+    std::vector<VShard> sh(n_devices);
+    const int n_active = assign_shards(sh, dev, cells->n_cells);
+    const bool fill = capacity > 0;
+    run_shards(sh, n_active ? has_cells : every_shard, [&](int i) {   // count, then fill a list of that size
+        VShard &s = sh[i];
+        auto a = is3d::cell_arrays(*cells);
+        for (auto &f : a)
+            if (f) f += s.lo;
+        s.c = is3d::cells_from_arrays(s.hi - s.lo, a);
+        s.si = *in;
+        s.si.first_cell = in->first_cell + s.lo;
+        if (s.si.x) s.si.x += s.lo;
+        if (s.si.y) s.si.y += s.lo;
+        s.o = *opts;
+        s.o.device = s.device;
+        int rc = is3d_sample_particles_vah(&s.c, species, tab, &s.si, &s.o, nullptr, 0, &s.count, &s.st);
+        if ((!rc || rc == IS3D_EDOMAIN) && fill && s.count > 0) {    // (a bad cell leaves the shard's other hadrons sampled)
+            s.list.resize((size_t)s.count);
+            rc = is3d_sample_particles_vah(&s.c, species, tab, &s.si, &s.o, s.list.data(), s.count, &s.count, &s.st);
+        }
+        return rc;
+    });
+    // a bad cell is reported (the first failed shard holds the lowest global index) after the merge: the list is returned with the error
+    int rc0;
+    std::string text;
+    first_error(sh, &rc0, &text);
+    bool only_domain = rc0 == IS3D_EDOMAIN;
+    for (const VShard &s : sh)
+        if (s.rc && s.rc != IS3D_EDOMAIN) only_domain = false;
+    if (rc0 && !only_domain) return fail(rc0, "%s", text.c_str());
+    if (only_domain)
+        for (VShard &s : sh) s.rc = IS3D_OK;
+    if (int rc = sampler_totals(sh, n_particles, stats)) return rc;
+    if (fill) merge_shard_lists(sh, in->n_events, particles, capacity);
+    if (only_domain) return fail(IS3D_EDOMAIN, "%s", text.c_str());
+    if (fill && *n_particles > capacity)
         return fail(IS3D_ENOMEM, "particle buffer too small: %lld particles, capacity %lld", (long long)*n_particles, (long long)capacity);
     return IS3D_OK;
 }

@@ -41,132 +41,12 @@
 #include "cf_host.h"
 #include "cf_math.h"
 #include "cf_sampler_bins.h"
+#include "cf_sampler_common.h"
 #include "errors.h"
 #include "jonah.h"
 #include "spline.h"
 
 namespace is3d {
-
-struct SamplerCell {
-    double live, breakdown;
-    double T_mod, shear_mod, bulk_mod, z;          // df_mode 3, 4
-    double tau, x, y, eta, ut, ux, uy, un, T;
-    double Xt, Xx, Xy, Xn, Yx, Yy, Zt, Zn;
-    double dst, dsx, dsy, dsz, ds_max;
-    double pixx, pixy, pixz, piyy, piyz, pizz;     // LRF
-    double bulkPi, dn_tot, dn_sum, neq_fact;
-    double c0, c2, F, betabulk, betapi, shear14;
-    // include_baryon: alpha_B (:962), alpha_B,mod (:1022), n_B/(E+P), T/betaV (:1026), V^i in the LRF (boost_Vmu_to_lrf), c1 c3 c4 | G betaV
-    double alphaB, alphaB_mod, ber, diff_mod, Vx, Vy, Vz, c1, c3, c4, G, betaV;
-};
-
-struct SamplerSpecies {       // device arrays, length npart / ncls
-    const double *mass, *sign, *degeneracy;
-    const int32_t *cls;
-    const double *cls_mass, *cls_sign;
-    int32_t npart, ncls;
-    const double *baryon, *cls_baryon;   // include_baryon, else NULL (the baryon number is part of the class key then)
-};
-
-struct SamplerParams {
-    CellPtrs cells;
-    const double *x, *y;
-    int64_t n_cells, first_cell;
-    int32_t dim3, df_mode, include_bulk, include_shear;
-    int32_t baryon, baryondiff;  // include_baryon; && include_baryondiff_deltaf: mu_B, n_B, V^mu are read (:953-964)
-    BilinearDev bil;             // baryon: c0..c4 (df_mode 1) | F G betabulk betaV betapi (df_mode 2, 3) on the (mu_B, T) grid
-    SplineDev spl;              // 14-moment: c0, c2; Chapman-Enskog: F, betabulk, betapi
-    int32_t ngl;
-    const double *gl;           // [4][ngl]: root1, weight1, root2, weight2 (alpha = 2 only for df_mode 3)
-    int32_t fast;               // species densities at the surface-average temperature (host arrays eqd, bkd)
-    const double *eqd, *bkd;    // [npart] Equilibrium_Density, Bulk_Density (deltafReader.cpp:536-650)
-    double T_sw, F_avg, betabulk_avg;   // fast breakdown test (emissionfunction.cpp:114-119)
-    int32_t nj;                 // Jonah tables (df_mode 4): abscissa, lambda^2, z and their spline c's
-    const double *jx, *jl2, *jz, *jcl, *jcz;
-    double bp_max, detA_min, mass_pion0;
-    double y_max;
-    uint64_t seed;
-    unsigned long long *status; // [0] min bad cell, [1] skipped, [2] momentum samples, [3] acceptances, [4] hadrons drawn, [5] breakdown cells
-    double *cdf;                // [ceil(npart / kCdfBlock)][n_cells]: the running sum of a cell's species weights after every kCdfBlock-th species, as
-                                // cf_sampler_cells adds them (NULL: df_mode 3)
-};
-
-// ---- Philox4x32-10 streams ----
-struct Rng {
-    uint32_t k0, k1, stream, cell, event, blk, buf[4];
-    int pos;
-    __device__ void init(uint64_t seed, uint32_t s, uint32_t c, uint32_t e)
-    {
-        k0 = (uint32_t)seed; k1 = (uint32_t)(seed >> 32);
-        stream = s; cell = c; event = e; blk = 0; pos = 4;
-    }
-    __device__ double uniform()
-    {
-        if (pos >= 4) {
-            uint32_t c0 = blk++, c1 = stream, c2 = cell, c3 = event, a = k0, b = k1;
-#pragma unroll
-            for (int r = 0; r < 10; r++) {
-                const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-                const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-                c0 = hi1 ^ c1 ^ a; c1 = lo1; c2 = hi0 ^ c3 ^ b; c3 = lo0;
-                a += 0x9E3779B9u; b += 0xBB67AE85u;
-            }
-            buf[0] = c0; buf[1] = c1; buf[2] = c2; buf[3] = c3;
-            pos = 0;
-        }
-        const uint32_t a = buf[pos], b = buf[pos + 1];
-        pos += 2;
-        return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);
-    }
-    __device__ long poisson(double mean)
-    {
-        long N = 0;
-        double remaining = mean;
-        while (remaining > 0.0) {
-            const double l = remaining < 256.0 ? remaining : 256.0;
-            remaining -= l;
-            const double u = uniform();
-            double p = exp(-l), F = p;
-            long k = 0;
-            while (u >= F && k < 4096) { k++; p *= l / (double)k; F += p; }
-            N += k;
-        }
-        return N;
-    }
-};
-
-// GaussThermal(neq_int | J10_int | J20_int, ...) (gaussThermal.cpp); chem = baryon * alpha_B
-__device__ __forceinline__ double gt_neq(const double *root, const double *weight, int n, double mbar, double sign, double chem = 0.0)
-{
-    double s = 0.0;
-    for (int k = 0; k < n; k++) {
-        const double pbar = root[k], Ebar = sqrt(pbar * pbar + mbar * mbar);
-        s += weight[k] * (pbar * exp(pbar) / (exp(Ebar - chem) + sign));
-    }
-    return s;
-}
-
-__device__ __forceinline__ double gt_J10(const double *root, const double *weight, int n, double mbar, double sign, double chem)
-{
-    double s = 0.0;
-    for (int k = 0; k < n; k++) {
-        const double pbar = root[k], Ebar = sqrt(pbar * pbar + mbar * mbar);
-        const double qstat = exp(Ebar - chem) + sign;
-        s += weight[k] * (pbar * exp(pbar + Ebar - chem) / (qstat * qstat));
-    }
-    return s;
-}
-
-__device__ __forceinline__ double gt_J20(const double *root, const double *weight, int n, double mbar, double sign, double chem = 0.0)
-{
-    double s = 0.0;
-    for (int k = 0; k < n; k++) {
-        const double pbar = root[k], Ebar = sqrt(pbar * pbar + mbar * mbar);
-        const double qstat = exp(Ebar - chem) + sign;
-        s += weight[k] * (Ebar * exp(pbar + Ebar - chem) / (qstat * qstat));
-    }
-    return s;
-}
 
 // GT[cell][class] = the n_eq integral; GT2 (df_mode 3, regular mode) = the J20 integral of n_linear, GT3 (with include_baryon) its
 // J10 integral; muB_fo != NULL (include_baryon && include_baryondiff_deltaf): chem = baryon mu_B / T
@@ -175,7 +55,6 @@ __device__ __forceinline__ double gt_J20(const double *root, const double *weigh
 // exp_full / sqrt_nr / rcp_nr of cf_math.h (1e-15 relative; arguments of order 1 .. 1e3) in place of libm's exp, sqrt and the division -- as
 // cf_feqmod_renorm does since round 3: 3.3 -> ~1 ms per 1e6 cells x 75 classes.  An exponential that overflowed is held at 1e300 so that its
 // node adds < 1e-300 of its weight instead of a division by inf.
-constexpr int kSmpGlMax = 256;   // n_gla <= 256 (is3d_sampler_plan_create checks)
 __global__ void __launch_bounds__(256)
 cf_sampler_density(const double *__restrict__ T_fo, const double *__restrict__ muB_fo, int64_t n_cells, SamplerSpecies sp,
                    const double *__restrict__ gl, int ngl, double *__restrict__ GT, double *__restrict__ GT2, double *__restrict__ GT3)
@@ -212,35 +91,6 @@ cf_sampler_density(const double *__restrict__ T_fo, const double *__restrict__ m
         }
         GT2[idx] = s_j20;
     }
-}
-
-// mean-number weight of species ip in a cell: fast_max_particle_number (:239-280) / max_particle_number (:282-359)
-// gt, gt2, gt3: the cell's column of the class-major integral tables (GT + cell), element of class k at [k * p.n_cells]
-// The running sums are kept for every kCdfBlock-th species only (round 5: 39 planes instead of 305 -- cf_sampler_cells was bound by these stores, 2.4 GB
-// per 1e6 cells): a hadron's species is the bisection of the block sums followed by the producer's own additions inside one block, continued from the stored
-// sum in front of it -- the same doubles in the same order, so the same species as the bisection of all 305 sums.
-constexpr int kCdfBlock = 8;
-
-__device__ __forceinline__ double species_dn(const SamplerParams &p, const SamplerSpecies &sp, const SamplerCell &c, const double *gt,
-                                             const double *gt2, const double *gt3, int ip)
-{
-    const bool linear = p.df_mode <= 2 || c.breakdown != 0.0;
-    if (p.fast) {
-        if (linear) return 2.0 * p.eqd[ip];
-        if (p.df_mode == 3) return p.eqd[ip] + c.bulkPi * p.bkd[ip];
-        return c.z * p.eqd[ip];
-    }
-    const int64_t kk = (int64_t)sp.cls[ip] * p.n_cells;
-    const double equilibrium_density = c.neq_fact * sp.degeneracy[ip] * gt[kk];
-    if (linear) return 2.0 * equilibrium_density;
-    if (p.df_mode == 3) {
-        const double J20 = (c.T * c.neq_fact) * sp.degeneracy[ip] * gt2[kk];
-        double bJ10G = 0.0;                                                             // baryon * J10 * G, :319-325
-        if (gt3) bJ10G = sp.baryon[ip] * (c.neq_fact * sp.degeneracy[ip] * gt3[kk]) * c.G;
-        const double bulk_density = (equilibrium_density + bJ10G + (J20 * c.F / c.T / c.T)) / c.betabulk;
-        return equilibrium_density + c.bulkPi * bulk_density;
-    }
-    return c.z * equilibrium_density;
 }
 
 // The cell's n_eq integrals are summed over the SPECIES in list order (the order the reference adds them in).  With GT[cell][class] that was 305
@@ -377,91 +227,11 @@ cf_sampler_cells(SamplerParams p, SamplerSpecies sp, const double *__restrict__ 
     const double *gt = GT + ic, *gt2 = GT2 ? GT2 + ic : nullptr, *gt3 = GT3 ? GT3 + ic : nullptr;
     // the running sums are kept (species-major, so that the lanes of a wave -- consecutive cells -- store adjacent words): the sampling kernels
     // then find a hadron's species by bisection of exactly these sums instead of re-adding up to 305 gathered weights per hadron
-    double dn = 0.0;
-    if (p.cdf) {
-        // (the stores never alias the tables read: said so, and the loop unrolled, so that four species' loads are in flight per trip)
-        double *__restrict__ cdf = p.cdf + ic;
-        const double *__restrict__ gtr = gt;
-#pragma unroll 4
-        for (int ip = 0; ip < sp.npart; ip++) {
-            dn += species_dn(p, sp, c, gtr, gt2, gt3, ip);
-            if ((ip & (kCdfBlock - 1)) == kCdfBlock - 1 || ip == sp.npart - 1) cdf[(int64_t)(ip / kCdfBlock) * p.n_cells] = dn;
-        }
-    } else {
-        for (int ip = 0; ip < sp.npart; ip++) dn += species_dn(p, sp, c, gt, gt2, gt3, ip);
-    }
+    const double dn = species_running_sums(p, sp, c, gt, gt2, gt3, ic);
     c.dn_sum = dn;
     c.dn_tot = dn * (2.0 * p.y_max * c.ds_max);
     c.live = (c.dn_tot > 0.0) ? 1.0 : 0.0;                                          // :1079
     out[ic] = c;
-}
-
-// :172-196
-__device__ __forceinline__ double pion_thermal_weight_max(double x)
-{
-    const double x2 = x * x, x3 = x2 * x, x4 = x3 * x;
-    const double max = (143206.88623164667 - 95956.76008684626 * x - 21341.937407169076 * x2 + 14388.446116867359 * x3 - 6083.775788504437 * x4) /
-                       (-0.3541350577684533 + 143218.69233952634 * x - 24516.803600065778 * x2 - 115811.59391199696 * x3 + 35814.36403387459 * x4);
-    return 1.00001 * max;
-}
-
-struct LrfMom { double E, px, py, pz; };
-
-// sample_momentum (:456-617); chem = baryon * alpha_B enters the heavy-hadron weight only (:588)
-__device__ LrfMom sample_momentum(Rng &g, long &acceptances, long &samples, double mass, double sign, double T, double chem)
-{
-    const double two_pi = 2.0 * M_PI;
-    const double mbar = mass / T, mbar_squared = mbar * mbar;
-    double pbar, Ebar, phi_over_2pi, costheta;
-    if (mbar < 1.008) {
-        double weq_max = 1.0;
-        if (mbar < 0.8554 && sign == -1.0) weq_max = pion_thermal_weight_max(mbar);
-        for (;;) {
-            samples += 1;
-            const double r1 = 1.0 - g.uniform(), r2 = 1.0 - g.uniform(), r3 = 1.0 - g.uniform();
-            const double l1 = log(r1), l2 = log(r2), l3 = log(r3);
-            const double l1_plus_l2 = l1 + l2;
-            pbar = -(l1 + l2 + l3);
-            Ebar = sqrt(pbar * pbar + mbar_squared);
-            phi_over_2pi = l1_plus_l2 * l1_plus_l2 / (pbar * pbar);
-            costheta = (l1 - l2) / l1_plus_l2;
-            const double weight = 1.0 / (exp(Ebar) + sign) / weq_max / (r1 * r2 * r3);
-            if (g.uniform() < weight) break;
-        }
-    } else {
-        const double K0 = mbar_squared, K1 = 2.0 * mbar, K2 = 2.0, Ksum = K0 + K1 + K2;
-        double kbar;
-        for (;;) {
-            samples += 1;
-            const double uk = g.uniform() * Ksum;
-            if (uk < K0) {
-                kbar = -log(1.0 - g.uniform());
-                phi_over_2pi = g.uniform();
-                costheta = 2.0 * g.uniform() - 1.0;
-            } else if (uk < K0 + K1) {
-                const double l1 = log(1.0 - g.uniform()), l2 = log(1.0 - g.uniform());
-                kbar = -(l1 + l2);
-                phi_over_2pi = -l1 / kbar;
-                costheta = 2.0 * g.uniform() - 1.0;
-            } else {
-                const double l1 = log(1.0 - g.uniform()), l2 = log(1.0 - g.uniform()), l3 = log(1.0 - g.uniform());
-                const double l1_plus_l2 = l1 + l2;
-                kbar = -(l1 + l2 + l3);
-                phi_over_2pi = l1_plus_l2 * l1_plus_l2 / (kbar * kbar);
-                costheta = (l1 - l2) / l1_plus_l2;
-            }
-            Ebar = kbar + mbar;
-            pbar = sqrt(Ebar * Ebar - mbar_squared);
-            const double exponent = exp(Ebar - chem);
-            const double weight = pbar / Ebar * exponent / (exponent + sign);
-            if (g.uniform() < weight) break;
-        }
-    }
-    acceptances += 1;
-    const double E = Ebar * T, pm = pbar * T, phi = phi_over_2pi * two_pi;
-    const double sintheta = sqrt(1.0 - costheta * costheta);
-    LrfMom q = {E, pm * sintheta * cos(phi), pm * sintheta * sin(phi), pm * costheta};
-    return q;
 }
 
 // stream 0 of every (event, cell) pair of the batch: the Poisson number of hadrons (std::poisson_distribution(dn_tot), :1085-1090)
@@ -511,32 +281,7 @@ __device__ __forceinline__ void sampler_thread(const SamplerParams &p, const Sam
     int64_t slot = FILL ? base + offsets[ia] : 0;
     for (long ih = 0; ih < N_hadrons; ih++) {
         const double ut_ = g_type.uniform() * c.dn_sum;
-        int chosen = sp.npart - 1;
-        if (p.cdf) {
-            // first species whose running sum exceeds ut_ (the last one if none does): bisection of the sums cf_sampler_cells stored -- the
-            // weights are >= 0 for df_mode 1, 2, 4, so the sums are non-decreasing and this IS the linear inversion below, in 9 reads
-            // (round 5) ... of the sums at the block ends: the first block whose end sum exceeds ut_ (the last block if none does), then the producer's
-            // additions inside it, continued from the sum stored in front of it
-            int lo = 0, hi = (sp.npart + kCdfBlock - 1) / kCdfBlock - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (ut_ < p.cdf[(int64_t)mid * p.n_cells + ic]) hi = mid;
-                else lo = mid + 1;
-            }
-            double cum = lo ? p.cdf[(int64_t)(lo - 1) * p.n_cells + ic] : 0.0;
-            const int ip1 = min((lo + 1) * kCdfBlock, sp.npart);
-            chosen = ip1 - 1;
-            for (int ip = lo * kCdfBlock; ip < ip1; ip++) {
-                cum += species_dn(p, sp, c, gt, gt2, gt3, ip);
-                if (ut_ < cum) { chosen = ip; break; }
-            }
-        } else {
-            double cum = 0.0;
-            for (int ip = 0; ip < sp.npart; ip++) {
-                cum += species_dn(p, sp, c, gt, gt2, gt3, ip);
-                if (ut_ < cum) { chosen = ip; break; }
-            }
-        }
+        const int chosen = choose_species(p, sp, c, gt, gt2, gt3, ic, ut_);
         const double mass = sp.mass[chosen], mass_squared = mass * mass, sign = sp.sign[chosen];
         const double baryon = sp.baryon ? sp.baryon[chosen] : 0.0;
         LrfMom q;
@@ -619,16 +364,7 @@ cf_sampler_run(SamplerParams p, SamplerSpecies sp, const SamplerCell *__restrict
 {
     unsigned long long tally[3] = {0ULL, 0ULL, 0ULL};
     sampler_thread<FILL>(p, sp, cellrec, GT, GT2, GT3, event0, active, n_active, n_drawn, counts, offsets, base, particles, capacity, tally);
-    if (!FILL) {
-        // the run-wide tallies: one global atomic per counter and workgroup instead of three per sampling thread
-        __shared__ unsigned long long blk[3];
-        if (threadIdx.x < 3) blk[threadIdx.x] = 0ULL;
-        __syncthreads();
-        for (int k = 0; k < 3; k++)
-            if (tally[k]) atomicAdd(&blk[k], tally[k]);
-        __syncthreads();
-        if (threadIdx.x < 3 && blk[threadIdx.x]) atomicAdd(&p.status[2 + threadIdx.x], blk[threadIdx.x]);
-    }
+    if (!FILL) sampler_tally(p, tally);
 }
 
 }  // namespace is3d
@@ -662,47 +398,26 @@ struct is3d_sampler_plan {
     hipEvent_t ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
-extern "C" int is3d_sampler_plan_create(is3d_sampler_plan **out, const is3d_species *species, const is3d_df_tables *df,
-                                        const is3d_sampler_inputs *in, const is3d_options *opts, int64_t max_cells)
+namespace {
+// what every sampler plan checks of its species list and Gauss-Laguerre nodes
+int check_species_nodes(const is3d_species *species, const is3d_sampler_inputs *in)
 {
     using is3d::set_error;
-    if (!out || !species || !df || !in || !opts) return set_error(IS3D_EINVAL, "null argument");
-    *out = nullptr;
-    if (max_cells < 1) max_cells = 1;
-    if (opts->dimension != 2 && opts->dimension != 3) return set_error(IS3D_EINVAL, "dimension must be 2 or 3 (got %d)", opts->dimension);
-    if (opts->df_mode < 1 || opts->df_mode > 4) return set_error(IS3D_EINVAL, "the sampler takes df_mode 1, 2, 3 or 4 (got %d)", opts->df_mode);
-    const is3d_feqmod_tables *fq = in->feqmod;
-    const bool need_alpha2 = opts->df_mode == 3 || (in->fast && opts->df_mode == 2);
-    if ((opts->df_mode >= 3 || need_alpha2) && !fq) return set_error(IS3D_EINVAL, "df_mode 3 / 4 (and fast mode with df_mode 2) need in->feqmod");
-    if (fq && (fq->n_gla != in->n_gla || !fq->root2 || !fq->weight2)) return set_error(IS3D_EINVAL, "in->feqmod: Gauss-Laguerre alpha = 2 nodes missing or of another size");
-    if (opts->df_mode == 4 && (fq->n_pdg < 1 || !fq->pdg_mass || !fq->pdg_degeneracy || !fq->pdg_sign || !(fq->T_avg > 0.0)))
-        return set_error(IS3D_EINVAL, "df_mode 4 needs the full PDG list and the surface-averaged temperature");
-    if (in->fast && !(in->T_avg > 0.0)) return set_error(IS3D_EINVAL, "fast = 1 needs the surface-averaged temperature");
-    const bool baryon = opts->include_baryon != 0, baryondiff = baryon && opts->include_baryondiff_deltaf != 0;
-    if (baryon) {
-        if (opts->df_mode == 4)   // deltafReader.cpp:470-474: "Jonah df doesn't work for nonzero muB. Exiting.."
-            return set_error(IS3D_EINVAL, "df_mode 4 does not work with include_baryon = 1 (the reference exits there too)");
-        if (!species->baryon) return set_error(IS3D_EINVAL, "include_baryon = 1 needs the species' baryon numbers");
-        if (df->n_muB < 2 || !df->muB) return set_error(IS3D_EINVAL, "include_baryon = 1 needs the full (T, muB) coefficient tables");
-        for (int i = 1; i < df->n_muB; i++)
-            if (!(df->muB[i] > df->muB[i - 1])) return set_error(IS3D_EINVAL, "coefficient table muB values must ascend");
-        if (opts->df_mode == 1 && (!df->c0 || !df->c1 || !df->c2 || !df->c3 || !df->c4)) return set_error(IS3D_EINVAL, "include_baryon = 1, df_mode 1 needs c0..c4 tables");
-        if (opts->df_mode != 1 && (!df->F || !df->G || !df->betabulk || !df->betaV || !df->betapi))
-            return set_error(IS3D_EINVAL, "include_baryon = 1, df_mode 2 / 3 need F, G, betabulk, betaV, betapi tables");
-    }
     if (species->n < 1 || !species->mass || !species->sign || !species->degeneracy) return set_error(IS3D_EINVAL, "empty species list");
     for (int s = 0; s < species->n; s++)
         if (!(species->mass[s] > 0.0)) return set_error(IS3D_EINVAL, "species %d has mass 0: photons cannot be sampled with this method (reference: exit, sampling_kernels.cpp:478-482)", s);
     if (in->n_gla < 1 || in->n_gla > is3d::kSmpGlMax || !in->root1 || !in->weight1)
         return set_error(IS3D_EINVAL, "the sampler needs the Gauss-Laguerre roots and weights for alpha = 1 (1 to %d nodes)", is3d::kSmpGlMax);
-    if (df->n_T < 3 || !df->T) return set_error(IS3D_EINVAL, "coefficient table needs >= 3 temperatures");
-    if (opts->df_mode == 1 && (!df->c0 || !df->c2)) return set_error(IS3D_EINVAL, "df_mode 1 needs c0 and c2 tables");
-    if ((opts->df_mode == 2 || opts->df_mode == 3) && (!df->F || !df->betabulk || !df->betapi))
-        return set_error(IS3D_EINVAL, "df_mode 2 / 3 need F, betabulk, betapi tables");
-    if (opts->df_mode == 4 && !df->betapi) return set_error(IS3D_EINVAL, "df_mode 4 needs the betapi table");
+    return IS3D_OK;
+}
+// the part of a plan that takes no coefficient tables: the device, the species classes (mass, sign[, baryon number]) and the Gauss-Laguerre nodes
+int plan_base(std::unique_ptr<is3d_sampler_plan> &P, const is3d_species *species, const is3d_sampler_inputs *in, const is3d_options *opts,
+              int64_t max_cells, const is3d_feqmod_tables *fq, bool baryon)
+{
+    using is3d::set_error;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return set_error(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
-    std::unique_ptr<is3d_sampler_plan> P(new is3d_sampler_plan);
+    P.reset(new is3d_sampler_plan);
     is3d::count_resource(0);
     if (opts->device >= 0) HIP_TRY(hipSetDevice(opts->device));
     HIP_TRY(hipGetDevice(&P->device));
@@ -710,14 +425,9 @@ extern "C" int is3d_sampler_plan_create(is3d_sampler_plan **out, const is3d_spec
     P->o = *opts;
     P->three_d = opts->dimension == 3;
     P->ngla = in->n_gla;
-    const bool three_d = P->three_d;
     auto &d_mass = P->d_mass; auto &d_sign = P->d_sign; auto &d_deg = P->d_deg; auto &d_cls = P->d_cls; auto &d_cmass = P->d_cmass; auto &d_csign = P->d_csign;
-    auto &d_gl = P->d_gl; auto &d_splx = P->d_splx; auto &d_sply = P->d_sply; auto &d_splc = P->d_splc;
-    auto &d_bar = P->d_bar; auto &d_cbar = P->d_cbar; auto &d_bilT = P->d_bilT; auto &d_bilB = P->d_bilB; auto &d_biltab = P->d_biltab;
-    auto &d_jonah = P->d_jonah; auto &d_eqd = P->d_eqd; auto &d_bkd = P->d_bkd;
-    is3d::SamplerParams &p = P->p;
+    auto &d_gl = P->d_gl; auto &d_bar = P->d_bar; auto &d_cbar = P->d_cbar;
     is3d::SamplerSpecies &sp = P->sp;
-
     // ---- species classes (mass, sign[, baryon number]): the density integral is per class ----
     const int npart = species->n;
     std::vector<int32_t> cls(npart);
@@ -750,6 +460,64 @@ extern "C" int is3d_sampler_plan_create(is3d_sampler_plan **out, const is3d_spec
     sp = is3d::SamplerSpecies{d_mass.as<double>(), d_sign.as<double>(), d_deg.as<double>(), d_cls.as<int32_t>(),
                               d_cmass.as<double>(), d_csign.as<double>(), npart, ncls, d_bar.as<double>(), d_cbar.as<double>()};
     P->ncls = ncls;
+    return IS3D_OK;
+}
+// the rapidity range, the status words and the events
+int plan_finish(is3d_sampler_plan *P, const is3d_sampler_inputs *in)
+{
+    is3d::SamplerParams &p = P->p;
+    const bool three_d = P->three_d;
+    p.y_max = three_d ? 0.5 : in->y_cut;                                              // :837-838
+    HIP_TRY(P->d_status.alloc(8 * sizeof(unsigned long long)));
+    p.status = P->d_status.as<unsigned long long>();
+    for (auto &e : P->ev) HIP_TRY(hipEventCreate(&e));
+    return IS3D_OK;
+}
+}  // namespace
+
+extern "C" int is3d_sampler_plan_create(is3d_sampler_plan **out, const is3d_species *species, const is3d_df_tables *df,
+                                        const is3d_sampler_inputs *in, const is3d_options *opts, int64_t max_cells)
+{
+    using is3d::set_error;
+    if (!out || !species || !df || !in || !opts) return set_error(IS3D_EINVAL, "null argument");
+    *out = nullptr;
+    if (max_cells < 1) max_cells = 1;
+    if (opts->dimension != 2 && opts->dimension != 3) return set_error(IS3D_EINVAL, "dimension must be 2 or 3 (got %d)", opts->dimension);
+    if (opts->df_mode < 1 || opts->df_mode > 4) return set_error(IS3D_EINVAL, "the sampler takes df_mode 1, 2, 3 or 4 (got %d)", opts->df_mode);
+    const is3d_feqmod_tables *fq = in->feqmod;
+    const bool need_alpha2 = opts->df_mode == 3 || (in->fast && opts->df_mode == 2);
+    if ((opts->df_mode >= 3 || need_alpha2) && !fq) return set_error(IS3D_EINVAL, "df_mode 3 / 4 (and fast mode with df_mode 2) need in->feqmod");
+    if (fq && (fq->n_gla != in->n_gla || !fq->root2 || !fq->weight2)) return set_error(IS3D_EINVAL, "in->feqmod: Gauss-Laguerre alpha = 2 nodes missing or of another size");
+    if (opts->df_mode == 4 && (fq->n_pdg < 1 || !fq->pdg_mass || !fq->pdg_degeneracy || !fq->pdg_sign || !(fq->T_avg > 0.0)))
+        return set_error(IS3D_EINVAL, "df_mode 4 needs the full PDG list and the surface-averaged temperature");
+    if (in->fast && !(in->T_avg > 0.0)) return set_error(IS3D_EINVAL, "fast = 1 needs the surface-averaged temperature");
+    const bool baryon = opts->include_baryon != 0, baryondiff = baryon && opts->include_baryondiff_deltaf != 0;
+    if (baryon) {
+        if (opts->df_mode == 4)   // deltafReader.cpp:470-474: "Jonah df doesn't work for nonzero muB. Exiting.."
+            return set_error(IS3D_EINVAL, "df_mode 4 does not work with include_baryon = 1 (the reference exits there too)");
+        if (!species->baryon) return set_error(IS3D_EINVAL, "include_baryon = 1 needs the species' baryon numbers");
+        if (df->n_muB < 2 || !df->muB) return set_error(IS3D_EINVAL, "include_baryon = 1 needs the full (T, muB) coefficient tables");
+        for (int i = 1; i < df->n_muB; i++)
+            if (!(df->muB[i] > df->muB[i - 1])) return set_error(IS3D_EINVAL, "coefficient table muB values must ascend");
+        if (opts->df_mode == 1 && (!df->c0 || !df->c1 || !df->c2 || !df->c3 || !df->c4)) return set_error(IS3D_EINVAL, "include_baryon = 1, df_mode 1 needs c0..c4 tables");
+        if (opts->df_mode != 1 && (!df->F || !df->G || !df->betabulk || !df->betaV || !df->betapi))
+            return set_error(IS3D_EINVAL, "include_baryon = 1, df_mode 2 / 3 need F, G, betabulk, betaV, betapi tables");
+    }
+    if (int rc = check_species_nodes(species, in)) return rc;
+    if (df->n_T < 3 || !df->T) return set_error(IS3D_EINVAL, "coefficient table needs >= 3 temperatures");
+    if (opts->df_mode == 1 && (!df->c0 || !df->c2)) return set_error(IS3D_EINVAL, "df_mode 1 needs c0 and c2 tables");
+    if ((opts->df_mode == 2 || opts->df_mode == 3) && (!df->F || !df->betabulk || !df->betapi))
+        return set_error(IS3D_EINVAL, "df_mode 2 / 3 need F, betabulk, betapi tables");
+    if (opts->df_mode == 4 && !df->betapi) return set_error(IS3D_EINVAL, "df_mode 4 needs the betapi table");
+    std::unique_ptr<is3d_sampler_plan> P;
+    if (int rc = plan_base(P, species, in, opts, max_cells, fq, baryon)) return rc;
+    const bool three_d = P->three_d;
+    auto &d_gl = P->d_gl; auto &d_splx = P->d_splx; auto &d_sply = P->d_sply; auto &d_splc = P->d_splc;
+    auto &d_bilT = P->d_bilT; auto &d_bilB = P->d_bilB; auto &d_biltab = P->d_biltab;
+    auto &d_jonah = P->d_jonah; auto &d_eqd = P->d_eqd; auto &d_bkd = P->d_bkd;
+    is3d::SamplerParams &p = P->p;
+    const int npart = species->n;
+
     // ---- splines (deltafReader.cpp:300-322) ----
     std::vector<double> xs(df->T, df->T + df->n_T);
     for (int i = 1; i < df->n_T; i++)
@@ -870,10 +638,7 @@ extern "C" int is3d_sampler_plan_create(is3d_sampler_plan **out, const is3d_spec
             p.F_avg = bl[0] * Tsw; p.betabulk_avg = bl[2] * (Tsw * Tsw * Tsw * Tsw);
         } else if (opts->df_mode == 3) { p.F_avg = spline_at(0, Tsw) * Tsw; p.betabulk_avg = spline_at(1, Tsw) * Tsw * Tsw * Tsw * Tsw; }
     }
-    p.y_max = three_d ? 0.5 : in->y_cut;                                              // :837-838
-    HIP_TRY(P->d_status.alloc(8 * sizeof(unsigned long long)));
-    p.status = P->d_status.as<unsigned long long>();
-    for (auto &e : P->ev) HIP_TRY(hipEventCreate(&e));
+    if (int rc = plan_finish(P.get(), in)) return rc;
     *out = P.release();
     return IS3D_OK;
 }
@@ -901,6 +666,9 @@ struct BinRun {
 };
 int sampler_execute(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev, int32_t n_events, uint64_t seed,
                     int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
+                    int64_t *n_particles, is3d_sampler_stats *stats);
+int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t n, const double *x_dev, const double *y_dev, int32_t n_events,
+                    uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
                     int64_t *n_particles, is3d_sampler_stats *stats);
 }  // namespace
 
@@ -933,19 +701,30 @@ int sampler_execute(is3d_sampler_plan *P, const is3d_cells *cells, const double 
     *n_particles = 0;
     if (stats) memset(stats, 0, sizeof *stats);
     if (n_events < 1) return set_error(IS3D_EINVAL, "n_events must be >= 1");
-    if (particles_dev == nullptr || bin) capacity = 0;
     if (int rc = check_cells(cells, &P->o, first_cell)) return rc;
     const int64_t n = cells->n_cells;
+    if (n > 0) {
+        auto arrays = is3d::cell_arrays(*cells);
+        for (int a = 0; a < is3d::kCellArrays; a++)
+            if (!cell_array_needed(a, &P->o)) arrays[a] = nullptr;
+        P->p.cells = is3d::cell_ptrs(is3d::cells_from_arrays(n, arrays));
+    }
+    return sampler_batches(P, nullptr, n, x_dev, y_dev, n_events, seed, first_cell, batch_events, particles_dev, capacity, bin, n_particles, stats);
+}
+
+// v == NULL: cf_sampler_cells and cf_sampler_run on P->p.cells; else the variant's kernels (cf_sampler_common.h)
+int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t n, const double *x_dev, const double *y_dev, int32_t n_events,
+                    uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
+                    int64_t *n_particles, is3d_sampler_stats *stats)
+{
+    using is3d::set_error;
+    if (particles_dev == nullptr || bin) capacity = 0;
     if (n > P->max_cells) return set_error(IS3D_EINVAL, "%lld cells, the sampler plan was created for %lld", (long long)n, (long long)P->max_cells);
     HIP_TRY(hipSetDevice(P->device));
     if (n == 0) return IS3D_OK;
     const int ncls = P->ncls;
     is3d::SamplerParams &p = P->p;
     const is3d::SamplerSpecies &sp = P->sp;
-    auto arrays = is3d::cell_arrays(*cells);
-    for (int a = 0; a < is3d::kCellArrays; a++)
-        if (!cell_array_needed(a, &P->o)) arrays[a] = nullptr;
-    p.cells = is3d::cell_ptrs(is3d::cells_from_arrays(n, arrays));
     p.x = x_dev; p.y = y_dev;
     p.n_cells = n; p.first_cell = first_cell;
     p.seed = seed;
@@ -990,11 +769,15 @@ int sampler_execute(is3d_sampler_plan *P, const is3d_cells *cells, const double 
     HIP_TRY(hipEventRecord(ev[1], nullptr));
     {
         const int64_t tot = n * ncls;
-        hipLaunchKernelGGL(is3d::cf_sampler_density, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, p.cells.T, p.cells.muB, n, sp,
-                           P->d_gl.as<double>(), P->ngla, d_GT.as<double>(), d_GT2.as<double>(), d_GT3.as<double>());
+        hipLaunchKernelGGL(is3d::cf_sampler_density, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, v ? v->T : p.cells.T,
+                           v ? nullptr : p.cells.muB, n, sp, P->d_gl.as<double>(), P->ngla, d_GT.as<double>(), d_GT2.as<double>(), d_GT3.as<double>());
         HIP_TRY(hipEventRecord(ev[6], nullptr));
-        hipLaunchKernelGGL(is3d::cf_sampler_cells, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, nullptr, p, sp, d_GT.as<double>(),
-                           d_GT2.as<double>(), d_GT3.as<double>(), d_rec.as<is3d::SamplerCell>());
+        if (v) {
+            if (int rc = v->cells(v->ctx, p, sp, d_GT.as<double>(), d_rec.as<is3d::SamplerCell>())) return rc;
+        } else {
+            hipLaunchKernelGGL(is3d::cf_sampler_cells, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, nullptr, p, sp, d_GT.as<double>(),
+                               d_GT2.as<double>(), d_GT3.as<double>(), d_rec.as<is3d::SamplerCell>());
+        }
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(ev[2], nullptr));
@@ -1018,9 +801,13 @@ int sampler_execute(is3d_sampler_plan *P, const is3d_cells *cells, const double 
         if (n_active > 0) {
             const unsigned grid = (unsigned)(((int64_t)n_active + 127) / 128);
             HIP_TRY(hipMemsetAsync(d_counts.as<int64_t>() + n_active, 0, sizeof(int64_t), nullptr));
-            hipLaunchKernelGGL((is3d::cf_sampler_run<false>), dim3(grid), dim3(128), 0, nullptr, p, sp, d_rec.as<is3d::SamplerCell>(),
-                               d_GT.as<double>(), d_GT2.as<double>(), d_GT3.as<double>(), e0, d_active.as<int32_t>(), (int64_t)n_active,
-                               d_drawn.as<int32_t>(), d_counts.as<int64_t>(), (const int64_t *)nullptr, (int64_t)0, (is3d_particle *)nullptr, (int64_t)0);
+            if (v)
+                v->run(v->ctx, false, grid, p, sp, is3d::SamplerRunArgs{d_rec.as<is3d::SamplerCell>(), d_GT.as<double>(), e0, d_active.as<int32_t>(),
+                                                                       (int64_t)n_active, d_drawn.as<int32_t>(), d_counts.as<int64_t>(), nullptr, 0, nullptr, 0});
+            else
+                hipLaunchKernelGGL((is3d::cf_sampler_run<false>), dim3(grid), dim3(128), 0, nullptr, p, sp, d_rec.as<is3d::SamplerCell>(),
+                                   d_GT.as<double>(), d_GT2.as<double>(), d_GT3.as<double>(), e0, d_active.as<int32_t>(), (int64_t)n_active,
+                                   d_drawn.as<int32_t>(), d_counts.as<int64_t>(), (const int64_t *)nullptr, (int64_t)0, (is3d_particle *)nullptr, (int64_t)0);
             HIP_TRY(hipGetLastError());
             // element n_active of the scan (counts[n_active] = 0) is the batch total
             HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_scan_tmp.p, tmp_bytes, d_counts.as<int64_t>(), d_offsets.as<int64_t>(), n_active + 1, nullptr));
@@ -1037,9 +824,13 @@ int sampler_execute(is3d_sampler_plan *P, const is3d_cells *cells, const double 
                 dst = P->d_particles.as<is3d_particle>(); dst_base = 0; dst_cap = batch_total;
             }
             if (dst_cap > 0 && dst_base < dst_cap && batch_total > 0) {
-                hipLaunchKernelGGL((is3d::cf_sampler_run<true>), dim3(grid), dim3(128), 0, nullptr, p, sp, d_rec.as<is3d::SamplerCell>(),
-                                   d_GT.as<double>(), d_GT2.as<double>(), d_GT3.as<double>(), e0, d_active.as<int32_t>(), (int64_t)n_active,
-                                   d_drawn.as<int32_t>(), (int64_t *)nullptr, d_offsets.as<int64_t>(), dst_base, dst, dst_cap);
+                if (v)
+                    v->run(v->ctx, true, grid, p, sp, is3d::SamplerRunArgs{d_rec.as<is3d::SamplerCell>(), d_GT.as<double>(), e0, d_active.as<int32_t>(),
+                                                                          (int64_t)n_active, d_drawn.as<int32_t>(), nullptr, d_offsets.as<int64_t>(), dst_base, dst, dst_cap});
+                else
+                    hipLaunchKernelGGL((is3d::cf_sampler_run<true>), dim3(grid), dim3(128), 0, nullptr, p, sp, d_rec.as<is3d::SamplerCell>(),
+                                       d_GT.as<double>(), d_GT2.as<double>(), d_GT3.as<double>(), e0, d_active.as<int32_t>(), (int64_t)n_active,
+                                       d_drawn.as<int32_t>(), (int64_t *)nullptr, d_offsets.as<int64_t>(), dst_base, dst, dst_cap);
                 HIP_TRY(hipGetLastError());
             }
         } else {
@@ -1083,6 +874,7 @@ int sampler_execute(is3d_sampler_plan *P, const is3d_cells *cells, const double 
             stats->particle_workspace_bytes = P->cap_particles * (int64_t)sizeof(is3d_particle);
         }
     }
+    if (h[0] != ~0ULL && v) return set_error(IS3D_EDOMAIN, "cell %lld: %s", (long long)h[0], v->domain_text);
     if (h[0] != ~0ULL)
         return set_error(IS3D_EDOMAIN, "cell %lld: T%s outside the coefficient table (the reference aborts in gsl_spline_eval here)", (long long)h[0],
                          P->o.df_mode == 4 ? " (or bulkPi/P)" : (p.baryon ? " or (T, muB)" : ""));
@@ -1092,6 +884,38 @@ int sampler_execute(is3d_sampler_plan *P, const is3d_cells *cells, const double 
     return IS3D_OK;
 }
 }  // namespace
+
+// ---- a sampler variant on this plan and batch loop (cf_sampler_common.h) ----
+int is3d::sampler_variant_plan_create(is3d_sampler_plan **out, const is3d_species *species, const is3d_sampler_inputs *in, const is3d_options *opts,
+                                      int64_t max_cells)
+{
+    *out = nullptr;
+    if (opts->dimension != 2 && opts->dimension != 3) return set_error(IS3D_EINVAL, "dimension must be 2 or 3 (got %d)", opts->dimension);
+    if (int rc = check_species_nodes(species, in)) return rc;
+    std::unique_ptr<is3d_sampler_plan> P;
+    if (int rc = plan_base(P, species, in, opts, std::max<int64_t>(max_cells, 1), nullptr, false)) return rc;
+    P->o.df_mode = 1;              // species_dn: 2 neq_fact g GT; the blocked running sums are kept
+    P->o.include_baryon = 0;
+    is3d::SamplerParams &p = P->p;
+    p.dim3 = P->three_d; p.df_mode = 1;
+    p.include_bulk = opts->include_bulk_deltaf != 0; p.include_shear = opts->include_shear_deltaf != 0;
+    p.ngl = in->n_gla; p.gl = P->d_gl.as<double>();
+    if (int rc = plan_finish(P.get(), in)) return rc;
+    *out = P.release();
+    return IS3D_OK;
+}
+
+int is3d::sampler_variant_execute(is3d_sampler_plan *P, const SamplerVariant &v, int64_t n_cells, const double *x_dev, const double *y_dev,
+                                  int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev,
+                                  int64_t capacity, int64_t *n_particles, is3d_sampler_stats *stats)
+{
+    *n_particles = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n_events < 1) return set_error(IS3D_EINVAL, "n_events must be >= 1");
+    if (n_cells < 0 || n_cells + first_cell > 0xffffffffLL) return set_error(IS3D_EINVAL, "cell indices must fit 32 bits for the counter-based streams");
+    P->p.cells = CellPtrs{};
+    return sampler_batches(P, &v, n_cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, particles_dev, capacity, nullptr, n_particles, stats);
+}
 
 namespace {
 // what the host-pointer entries share: a plan for this surface, and the needed cell arrays, x and y uploaded in one block

@@ -34,6 +34,7 @@
 #include "cf_launch.h"
 #include "cf_math.h"
 #include "cf_spacetime.h"
+#include "cf_vah_coef.h"
 #include "errors.h"
 
 namespace is3d {
@@ -1158,6 +1159,25 @@ extern "C" int is3d_vah_plan_observables(is3d_vah_plan *P, const double *dN_dev,
     if (pT_w) HIP_TRY(hipMemcpyAsync(P->d_pTw.p, pT_w, (size_t)P->npT * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(is3d::launch_observables(dN_dev, P->d_phiw.p, P->d_pTw.p, P->d_coskphi.p, P->d_sinkphi.p, dNdy_dev, dN2pipTdpTdy_dev, vn_dev,
                                      P->npart, P->npT, P->J, P->Kacc, st));
+    return IS3D_OK;
+}
+
+int is3d::vah_tables_check(const is3d_vah_df_tables *tab) { return check_tables(tab); }
+
+int is3d::vah_coeffs_device(const is3d_vah_df_tables *tab, int64_t n, int64_t cell0, const double *Lambda, const double *aL, double *const out[5],
+                            unsigned long long *status)
+{
+    if (n <= 0) return IS3D_OK;
+    TabDev td;
+    if (int rc = td.upload(tab)) return rc;
+    is3d::VahCoefArgs ca{};
+    ca.n = n; ca.cell0 = cell0; ca.Lambda = Lambda; ca.aL = aL;
+    td.fill(ca);
+    for (int k = 0; k < 5; k++) ca.out[k] = out[k];
+    ca.status = status;
+    hipLaunchKernelGGL(is3d::cf_vah_coeffs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, ca);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(nullptr));   // the tables are freed on return
     return IS3D_OK;
 }
 

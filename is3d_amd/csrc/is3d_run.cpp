@@ -241,7 +241,19 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
     }
     const bool vah = !mem && mode == 2;
     if (vah) {
-        if (operation == 2) DIE("mode = 2 (anisotropic hydro): operation = 0 or 1; the reference's VAH sampler is an empty stub (emissionfunction_sampling_kernels.cpp:1231-1239)");
+        if (operation == 2) {
+            // optional key vah_sampler = 1: this library's own VAH sampler (is3d_sample_particles_vah; the reference has none)
+            double vah_sampler = 0.0, oversample = 0.0;
+            if (!(get_param("vah_sampler", &vah_sampler, false) == IS3D_OK && (int)vah_sampler))
+                DIE("mode = 2 (anisotropic hydro): operation = 0 or 1; the reference's VAH sampler is an empty stub (emissionfunction_sampling_kernels.cpp:1231-1239); "
+                    "set vah_sampler = 1 for this library's own anisotropic-hydro sampler (is3d_sample_particles_vah)");
+            if (bin_on_device)
+                DIE("test_sampler_on_device = 1 with mode = 2: the anisotropic-hydro sampler's hadrons are binned on the host (test_sampler = 1); set test_sampler_on_device = 0");
+            if (get_param("oversample", &oversample)) return IS3D_EINVAL;
+            if ((int)oversample)
+                DIE("oversample = 1 with mode = 2: the mean yield that sizes an oversampled run (calculate_total_yield) is viscous-hydro only; set oversample = 0 "
+                    "(max_num_samples events are sampled)");
+        }
         if (df_mode != 4) DIE("mode = 2 (anisotropic hydro) needs df_mode = 4: the per-cell 14-moment coefficients c0..c4 exist for that combination only (emissionfunction.cpp:1410-1418)");
     }
     if (!mem && !vah && mode != 0 && mode != 1 && mode != 4 && mode != 5 && mode != 6 && mode != 7)
@@ -478,9 +490,9 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         if (mem) {
             if (mem_x) xs.assign(mem_x, mem_x + n_cells);
             if (mem_y) ys.assign(mem_y, mem_y + n_cells);
-        } else if (n_cells > 0) {   // they came with the surface (is3d_surface_arrays: arrays 23, 24)
-            xs.assign(sa[23], sa[23] + n_cells);
-            ys.assign(sa[24], sa[24] + n_cells);
+        } else if (n_cells > 0) {   // they came with the surface (is3d_surface_arrays: arrays 23, 24; mode 2: 30, 31)
+            xs.assign(sa[vah ? 30 : 23], sa[vah ? 30 : 23] + n_cells);
+            ys.assign(sa[vah ? 31 : 24], sa[vah ? 31 : 24] + n_cells);
         }
         int32_t n_alpha = 0, n_pts = 0;
         const char *gla_path = "tables/gla_roots_weights_32_points.txt";
@@ -495,7 +507,7 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         si.root1 = groot.data() + n_pts; si.weight1 = gweight.data() + n_pts;
         // df_mode 3 / 4 and fast mode: emissionfunction.cpp:1309-1321, sampling_kernels.cpp:852-869
         double T_avg_file = 0.0, E_avg_file = 0.0, P_avg_file = 0.0, muB_avg_file = 0.0;   // Plasma::load_thermodynamic_averages
-        {
+        if (!vah) {   // (the mode-2 reader writes no averages and the anisotropic-hydro sampler takes none)
             FILE *tf = fopen("average_thermodynamic_quantities.dat", "r");
             if (!tf || fscanf(tf, "%lf %lf %lf %lf", &T_avg_file, &E_avg_file, &P_avg_file, &muB_avg_file) != 4) DIE("Error opening average thermodynamic file");
             fclose(tf);
@@ -550,11 +562,13 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
             // Nevents = min((int)ceil(MIN_NUM_HADRONS / Ntotal), MAX_NUM_SAMPLES); at least one event is sampled here
             si.n_events = (int32_t)std::max(1.0, std::min(std::ceil(min_num_hadrons / Ntotal), (double)(int)max_num_samples));
         }
+        if (vah) si.n_events = (int32_t)std::max(1.0, (double)(int)max_num_samples);   // no mean yield to size the run: MAX_NUM_SAMPLES events
         printf("Sampling %d event(s)\n", si.n_events);
         if (df_mode == 1) printf("Sampling particles with Grad 14 moment df...\n");                    // emissionfunction.cpp:1540-1541, :1602-1603
         if (df_mode == 2) printf("Sampling particles with Chapman Enskog df...\n");
         if (df_mode == 3) printf("Sampling particles with Mike's modified distribution...\n");
-        if (df_mode == 4) printf("Sampling particles with Jonah's modified distribution...\n");
+        if (df_mode == 4 && !vah) printf("Sampling particles with Jonah's modified distribution...\n");
+        if (vah) printf("Sampling particles from vahydro (P_L matching) with df...\n");
         if (bin_on_device) {
             // one pass: every event batch is binned on its device and dropped; the integer histograms of the shards are added on the host
             const size_t S = (size_t)sp.n, plane = (size_t)IS3D_SAMPLER_VN_HARMONICS * S * bins.pT_bins;
@@ -579,11 +593,18 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
             printf("Done sampling particles. Output stored in results folder. Goodbye!\n");
             return IS3D_OK;
         }
-        int rc2 = is3d_sample_particles_multi(&cells, &sp, &df, &si, &opts, rd.list.empty() ? nullptr : rd.list.data(), (int32_t)rd.list.size(), nullptr, 0, &count, &ss);
-        if (rc2) DIE("is3d_sample_particles failed (%d): %s", rc2, is3d_last_error());
+        // count, then fill a list of that size: the viscous-hydro sampler, or (mode 2) the anisotropic-hydro one on the mode-2 cells and tables
+        auto sample = [&](is3d_particle *list, int64_t capacity) {
+            const int32_t *dl = rd.list.empty() ? nullptr : rd.list.data();
+            if (vah) return is3d_sample_particles_vah_multi(&vc, &sp, &vt, &si, &opts, dl, (int32_t)rd.list.size(), list, capacity, &count, &ss);
+            return is3d_sample_particles_multi(&cells, &sp, &df, &si, &opts, dl, (int32_t)rd.list.size(), list, capacity, &count, &ss);
+        };
+        const char *sampler_name = vah ? "is3d_sample_particles_vah" : "is3d_sample_particles";
+        int rc2 = sample(nullptr, 0);
+        if (rc2) DIE("%s failed (%d): %s", sampler_name, rc2, is3d_last_error());
         std::vector<is3d_particle> plist((size_t)std::max<int64_t>(count, 1));
-        rc2 = is3d_sample_particles_multi(&cells, &sp, &df, &si, &opts, rd.list.empty() ? nullptr : rd.list.data(), (int32_t)rd.list.size(), plist.data(), count, &count, &ss);
-        if (rc2) DIE("is3d_sample_particles failed (%d): %s", rc2, is3d_last_error());
+        rc2 = sample(plist.data(), count);
+        if (rc2) DIE("%s failed (%d): %s", sampler_name, rc2, is3d_last_error());
         double t2s = now_s();
         printf("\nMomentum sampling efficiency = %f %%\n", 100.0 * (double)ss.n_acceptances / (double)std::max<int64_t>(ss.n_momentum_samples, 1));
         if (feqmod) printf("feqmod breaks down for %lld cells\n", (long long)ss.n_cells_breakdown);
