@@ -75,15 +75,7 @@ struct is3d_plan {
     // made on the first such execute
     std::vector<int32_t> sp_cls;
     std::vector<double> cls_mass, cls_sign, cls_bar, pT_grid, sp_deg;
-    std::vector<double> st_hwpT, st_hwphi;   // the weights now on the device (d_st_wpT, d_st_wphi)
-    bool st_ready = false;
-    int st_npTp = 0, st_nlw = 0;
-    int64_t st_pass = 0, st_cap = 0;
-    DevBuf<double> d_st_mT, d_st_pT, d_st_sign, d_st_b, d_st_wpT, d_st_wphi, d_st_pg, d_st_D, d_st_slab, d_st_eta;
-    DevBuf<double> d_st_mass;   // feqmod: the lanes' masses (the linearised delta-f of the breakdown cells)
-    DevBuf<int32_t> d_st_cls;
-    is3d::StBinWork st_bins;   // keys, lists and the scratch of the sorts (cf_spacetime.h)
-    DevBuf<unsigned long long> d_st_counters;
+    is3d::StState st;   // lane tables, weights and workspaces (cf_spacetime.h)
 
     bool timing = false;
     std::vector<hipEvent_t> ev_list;  // [pass][0..3]: start, after prep, after main; last: after finalize
@@ -999,82 +991,110 @@ static int st_check(const is3d_spacetime_bins *b, const double *x, const double 
                     "is3d_plan_execute_spacetime_feqmod (this entry takes df_mode 1 or 2)", df_mode);
     if (feqmod && df_mode != 3 && df_mode != 4)
         return fail(IS3D_EINVAL, "the feqmod entries of operation 0 take df_mode 3 or 4 (got %d)", df_mode);
-    if (!x || !y) return fail(IS3D_EINVAL, "operation 0 needs the cells' x and y positions (NULL given)");
-    if (!b) return fail(IS3D_EINVAL, "null spacetime bins");
-    if (b->tau_bins < 1 || b->r_bins < 1) return fail(IS3D_EINVAL, "tau_bins and r_bins must be >= 1 (got %d, %d)", b->tau_bins, b->r_bins);
-    if (!(b->tau_max > b->tau_min) || !(b->r_max > b->r_min))
-        return fail(IS3D_EINVAL, "the bin ranges need tau_max > tau_min and r_max > r_min (got [%g, %g], [%g, %g])", b->tau_min, b->tau_max, b->r_min,
-                    b->r_max);
-    if ((int64_t)b->tau_bins * b->r_bins > ((int64_t)1 << 28)) return fail(IS3D_EINVAL, "tau_bins x r_bins too large");
-    return IS3D_OK;
+    return is3d::spacetime_check_bins(b, x, y);
 }
 
-// the spacetime lane tables and the per-pass workspace of a plan, made once
-static int st_setup(is3d_plan *P)
-{
-    if (P->st_ready) return IS3D_OK;
-    int npTp = 1;
-    while (npTp < P->npT) npTp <<= 1;
-    P->st_npTp = npTp;
-    P->st_nlw = (P->ncls * npTp + 63) / 64;
-    const int nl = P->st_nlw * 64;
-    std::vector<double> mT(nl, 1.0), pT(nl, 0.0), sg(nl, 1.0), b(nl, 0.0), ms(nl, 1.0);
-    for (int l = 0; l < nl; l++) {
-        const int c = l / npTp, i = l % npTp;
-        if (c >= P->ncls || i >= P->npT) continue;   // padded lanes: finite operands, w_pT = 0
-        const double m = P->cls_mass[c], p = P->pT_grid[i];
-        ms[l] = m;
-        mT[l] = std::sqrt(m * m + p * p);
-        pT[l] = p;
-        sg[l] = P->cls_sign[c];
-        b[l] = P->cls_bar[c];
-    }
-    HIP_TRY(P->d_st_mT.upload(mT));
-    HIP_TRY(P->d_st_pT.upload(pT));
-    HIP_TRY(P->d_st_sign.upload(sg));
-    HIP_TRY(P->d_st_b.upload(b));
-    if (P->feqmod) HIP_TRY(P->d_st_mass.upload(ms));
-    HIP_TRY(P->d_st_wpT.alloc(nl));
-    HIP_TRY(P->d_st_wphi.alloc((size_t)P->jtiles * P->JT));
-    HIP_TRY(P->d_st_cls.upload(P->sp_cls));
-    std::vector<double> pg(P->npart);
-    for (int s = 0; s < P->npart; s++) pg[s] = P->prefactor * P->sp_deg[s];
-    HIP_TRY(P->d_st_pg.upload(pg));
-    // passes: the plan's record stream plus D (8 B per class and cell) within the same cap as the spectra path
-    const int64_t ws = is3d::default_stream_cap_bytes(P->opts.workspace_bytes);
-    const int64_t per_cell = (int64_t)P->bytes_per_cell + 8 * (int64_t)P->ncls;
-    P->st_pass = std::max<int64_t>(1, std::min<int64_t>(P->pass_cells, ws / per_cell));
-    hipError_t e = P->d_st_D.alloc((size_t)P->ncls * P->st_pass);
-    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(IS3D_ENOMEM, "out of device memory allocating the per-cell workspace D"); }
-    HIP_TRY(e);
-    if (!P->dim3) HIP_TRY(P->d_st_eta.alloc((size_t)P->ncls * P->K));
-    HIP_TRY(P->d_st_counters.alloc(4));
-    P->st_ready = true;
-    return IS3D_OK;
-}
-
-template <class T>
-static hipError_t st_grow(DevBuf<T> &buf, size_t n)
-{
-    if (buf.n >= n && buf.p) return hipSuccess;
-    return buf.alloc(std::max<size_t>(n, 1));
-}
+// the 2+1D eta rows' share of LDS: the feqmod kernel keeps 16 KiB of the 64 for its staged records
+static size_t st_lds_cap(bool feqmod) { return (feqmod ? 48 : 64) * 1024; }
 
 // the breakdown cells' workgroup slots of cf_st_fq_linear (2+1D: eta partial slots after the chunks')
 static int st_linear_slots(int64_t nc) { return (int)std::max<int64_t>(1, std::min<int64_t>(64, nc)); }
 
-// what the per-cell kernels take of a grid: up to 64 pT values (one wave holds a class), and in 2+1D the workgroup's eta rows in LDS --
-// [4 waves][64 / npTp classes][K] doubles within 64 KiB (the feqmod kernel keeps 16 KiB of it for its staged records: 48 KiB).  A function of
-// the grid alone: the one-shot entries ask it before they create a plan
-static int st_check_grid(bool dim3, bool feqmod, int npT, int K)
+// one pass of df_mode 1 / 2: before the first, the |p.dsigma| bound of the surface; the records; the per-cell stage
+static int st_pass_viscous(is3d_plan *P, const is3d_cells *cells, is3d::StSplit *split, hipStream_t st, int pass, int64_t c0, int32_t nc, int nch,
+                           const is3d::StMark &mark)
 {
-    if (npT > 64) return fail(IS3D_EINVAL, "operation 0 takes pT grids of up to 64 values (got %d)", npT);
-    int npTp = 1;
-    while (npTp < npT) npTp <<= 1;
-    const size_t cap = feqmod ? 48 * 1024 : 64 * 1024, per_eta = sizeof(double) * 4 * (64 / npTp);
-    if (!dim3 && per_eta * (size_t)K > cap)
-        return fail(IS3D_EINVAL, "operation 0 in 2+1D: %d pT values x %d eta nodes need more LDS than the per-cell kernel has (up to %d eta nodes "
-                    "with this pT grid)", npT, K, (int)(cap / per_eta));
+    const is3d_options &o = P->opts;
+    const is3d::StState &S = P->st;
+    const int K = P->K;
+    if (pass == 0) {
+        HIP_TRY(is3d::launch_pds_bound(is3d::cell_ptrs(*cells), cells->n_cells, P->dim3, P->kmin, P->kmax, P->gw2d, P->mTmax, P->pTmax,
+                                       P->d_status.p + 6, st));
+        if (split && split->exchange) {
+            // a shard: the records take the scale of the WHOLE surface, so that they -- and D -- are the single-device ones bit for bit
+            unsigned long long mine = 0, all = 0;
+            HIP_TRY(hipMemcpyAsync(&mine, P->d_status.p + 6, sizeof mine, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (int rc = split->exchange(mine, &all)) return rc;
+            HIP_TRY(hipMemcpyAsync(P->d_status.p + 6, &all, sizeof all, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipStreamSynchronize(st));   // `all` goes out of scope
+        }
+    }
+    is3d::PrepParams pp = fill_prep(P, cells, c0, nc);
+    pp.tiled = 1;
+    pp.pds_bound = P->d_status.p + 6;
+    pp.TE = nullptr;   // the E2 tables of cf_main_tile3e are not needed here
+    HIP_TRY(is3d::launch_prep(pp, st));
+    HIP_TRY(mark(0));
+
+    is3d::StCellArgs a{};
+    a.TS = P->d_TS.p; a.nc = nc; a.J = P->J; a.K = K; a.jtiles = P->jtiles; a.rblocks = P->rblocks;
+    a.ncls = P->ncls; a.npTp = S.npTp; a.nlw = S.nlw; a.G = (S.nlw + 3) / 4; a.nch = (int)std::min<int64_t>(nch, nc);
+    a.outflow = o.outflow != 0; a.regulate = o.regulate_deltaf != 0; a.zskip = o.zero_skip != 2;
+    a.lane_mT = S.d_mT.p; a.lane_pT = S.d_pT.p; a.lane_sign = S.d_sign.p; a.lane_b = S.d_b.p; a.lane_wpT = S.d_wpT.p;
+    a.wphi = S.d_wphi.p; a.pds_bound = P->d_status.p + 6;
+    a.D = S.d_D.p; a.eta_slab = P->dim3 ? nullptr : S.d_slab.p;
+    HIP_TRY(is3d::launch_spacetime_cells(a, P->ce, P->dim3, P->baryon, P->JT, P->KT, st));
+    if (!P->dim3) HIP_TRY(is3d::launch_spacetime_eta_reduce(S.d_slab.p, a.nch, (int64_t)P->ncls * K, pass == 0, S.d_eta.p, st));
+    HIP_TRY(mark(1));
+    return IS3D_OK;
+}
+
+// one pass of df_mode 3 / 4: the feqmod records (operation 0's form; they carry p.dsigma unscaled), df_mode 3 renormalisation, per-cell stage,
+// breakdown cells
+static int st_pass_feqmod(is3d_plan *P, const is3d_cells *cells, hipStream_t st, int pass, int64_t c0, int32_t nc, int nch, const is3d::StMark &mark)
+{
+    const is3d_options &o = P->opts;
+    const is3d::StState &S = P->st;
+    const int K = P->K, G = (S.nlw + 3) / 4, GL = st_linear_slots(S.pass);
+    is3d::FqPrepParams fp{};
+    fp.cells = is3d::cell_ptrs(*cells);
+    fp.baryon = P->baryon; fp.baryondiff = P->baryondiff; fp.bil = P->bil;
+    fp.cell0 = c0; fp.n_cells = nc; fp.J = P->J; fp.K = K;
+    fp.dim3 = P->dim3; fp.mode = o.df_mode;
+    fp.include_bulk = o.include_bulk_deltaf != 0; fp.include_shear = o.include_shear_deltaf != 0;
+    fp.cosphi = P->d_cosphi.p; fp.sinphi = P->d_sinphi.p; fp.kgrid = P->d_kgrid.p; fp.kweight = P->d_kweight.p;
+    fp.spl = P->spl;
+    fp.nj = P->nj;
+    fp.jx = P->d_jonah.p; fp.jl2 = fp.jx + P->nj; fp.jz = fp.jx + 2 * P->nj; fp.jcl = fp.jx + 3 * P->nj; fp.jcz = fp.jx + 4 * P->nj;
+    fp.bp_max = P->bp_max;
+    fp.mTmax = P->mTmax; fp.kmin = P->kmin; fp.kmax = P->kmax;
+    fp.pTmax = P->pTmax; fp.scale_rows = 0;   // D holds the unscaled value: no power-of-two row scale
+    fp.ngl = P->ngl; fp.gl = P->d_gl.p;
+    fp.detA_min = P->detA_min; fp.mass_pion0 = P->mass_pion0;
+    fp.JT = P->JT; fp.R = P->KT; fp.jtiles = P->jtiles; fp.rblocks = P->rblocks;
+    fp.TS = P->d_TS.p; fp.CR = P->d_CR.p; fp.FB = P->d_FB.p; fp.flag = P->d_flag.p;
+    fp.status = P->d_status.p;
+    HIP_TRY(is3d::launch_prep_feqmod(fp, st, true));
+    HIP_TRY(mark(0));
+    if (o.df_mode == 3) {
+        HIP_TRY(is3d::launch_feqmod_renorm(P->d_CR.p, P->d_gl.p, P->ngl, P->d_cls_mass.p, P->d_cls_sign.p,
+                                           P->baryon ? P->d_cls_baryon.p : nullptr, P->ncls, nc, fp.include_bulk, P->dim3,
+                                           P->d_RN.p, st, P->d_status.p + 2));
+        HIP_TRY(mark(3));
+    }
+    is3d::StFqCellArgs a{};
+    a.TS = P->d_TS.p; a.nc = nc; a.J = P->J; a.K = K; a.jtiles = P->jtiles; a.rblocks = P->rblocks;
+    a.ncls = P->ncls; a.npTp = S.npTp; a.nlw = S.nlw; a.G = G; a.nch = (int)std::min<int64_t>(nch, nc);
+    a.zskip = o.zero_skip != 2;
+    a.lane_mT = S.d_mT.p; a.lane_pT = S.d_pT.p; a.lane_sign = S.d_sign.p; a.lane_b = S.d_b.p; a.lane_wpT = S.d_wpT.p;
+    a.wphi = S.d_wphi.p; a.RN = o.df_mode == 3 ? P->d_RN.p : nullptr;
+    a.D = S.d_D.p; a.eta_slab = P->dim3 ? nullptr : S.d_slab.p;
+    HIP_TRY(is3d::launch_spacetime_feqmod_cells(a, P->dim3, o.df_mode == 3, P->baryon, o.outflow != 0, P->JT, P->KT, st));
+    HIP_TRY(mark(1));
+    HIP_TRY(is3d::launch_feqmod_compact(P->d_flag.p, nc, P->d_list.p, P->d_count.p, P->d_status.p, st));
+    is3d::StFqLinearArgs la{};
+    la.FB = P->d_FB.p; la.list = P->d_list.p; la.count = P->d_count.p;
+    la.lane_mT = S.d_mT.p; la.lane_pT = S.d_pT.p; la.lane_sign = S.d_sign.p; la.lane_mass = S.d_mass.p;
+    la.lane_b = P->baryon ? S.d_b.p : nullptr; la.lane_wpT = S.d_wpT.p;
+    la.cosphi = P->d_cosphi.p; la.sinphi = P->d_sinphi.p; la.wphi = S.d_wphi.p; la.kgrid = P->d_kgrid.p; la.kweight = P->d_kweight.p;
+    la.RN = o.df_mode == 3 ? P->d_RN.p : nullptr;
+    la.nc = nc; la.J = P->J; la.K = K; la.ncls = P->ncls; la.npTp = S.npTp; la.nlw = S.nlw; la.G = G; la.GL = GL; la.nch = a.nch;
+    la.dim3 = P->dim3; la.mode = o.df_mode; la.outflow = o.outflow != 0; la.regulate = o.regulate_deltaf != 0;
+    la.D = S.d_D.p; la.eta_slab = P->dim3 ? nullptr : S.d_slab.p;
+    HIP_TRY(is3d::launch_spacetime_feqmod_linear(la, st));
+    if (!P->dim3) HIP_TRY(is3d::launch_spacetime_eta_reduce(S.d_slab.p, a.nch + GL, (int64_t)P->ncls * K, pass == 0, S.d_eta.p, st));
+    HIP_TRY(mark(4));
     return IS3D_OK;
 }
 
@@ -1093,10 +1113,9 @@ static int st_execute(is3d_plan *P, const is3d_cells *cells, const double *x, co
     if (P->feqmod ? !is3d::spacetime_feqmod_shape_supported(P->dim3, P->JT, P->KT) : !is3d::spacetime_shape_supported(P->dim3, P->JT, P->KT))
         return fail(IS3D_EINVAL, "operation 0 runs on the plan's unit records of the default tile shapes (this plan: kernel variant %d, %d x %d "
                     "records for %d %s nodes)", P->variant, P->JT, P->KT, P->K, P->dim3 ? "y" : "eta");
-    rc = st_check_grid(P->dim3, P->feqmod, P->npT, P->K);
+    rc = is3d::spacetime_check_grid(P->dim3, st_lds_cap(P->feqmod), P->npT, P->K);
+    if (!rc && do_bins) rc = is3d::spacetime_check_out(out);
     if (rc) return rc;
-    if (do_bins && (!out->dN_dy || !out->dN_taudtaudy || !out->dN_twopirdrdy || !out->dN_twopitaurdtaudrdy || !out->dN_dydeta))
-        return fail(IS3D_EINVAL, "a required output array is NULL");
     const int64_t n = cells->n_cells;
     if (n < 0 || (do_cells && n > P->max_cells)) return fail(IS3D_EINVAL, "n_cells = %lld exceeds the plan's max_cells = %lld", (long long)n, (long long)P->max_cells);
     if (n > 0x7fff0000LL) return fail(IS3D_EINVAL, "operation 0 takes up to 2^31 cells");
@@ -1105,224 +1124,39 @@ static int st_execute(is3d_plan *P, const is3d_cells *cells, const double *x, co
     if (rc) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     HIP_TRY(hipSetDevice(P->device));
-    rc = st_setup(P);
+    is3d::StSetup su{};
+    su.ncls = P->ncls; su.npT = P->npT; su.J = P->J; su.K = P->K; su.dim3 = P->dim3; su.jtiles = P->jtiles; su.JT = P->JT; su.npart = P->npart;
+    su.cls_mass = P->cls_mass.data(); su.cls_sign = P->cls_sign.data(); su.cls_bar = P->cls_bar.data();
+    su.pT_grid = P->pT_grid.data(); su.sp_deg = P->sp_deg.data(); su.sp_cls = P->sp_cls.data();
+    su.prefactor = P->prefactor;
+    su.bytes_per_cell = (int64_t)P->bytes_per_cell; su.pass_cells = P->pass_cells; su.workspace_bytes = o.workspace_bytes;
+    su.mass_lanes = P->feqmod; su.b_lanes = true; su.pad = is3d::ST_PAD_UNIT;
+    rc = is3d::spacetime_setup(P->st, su);
+    // an execute with the same weights and stats == NULL does not block the host
+    if (!rc && do_cells) rc = is3d::spacetime_upload_weights(P->st, pT_w, phi_w, st);
     if (rc) return rc;
-    const int S = P->npart, K = P->K;
-    const int64_t tb = do_bins ? bins->tau_bins : 1, rbn = do_bins ? bins->r_bins : 1, trb = tb * rbn;
-    const int n_eta_eff = P->dim3 ? 1 : K;
 
-    // momentum weights of the reduction (pT_tab, phi_tab column 2): uploaded when they differ from the plan's copy (the first execute, or new
-    // weights); an execute with the same weights and stats == NULL does not block the host
-    if (do_cells && (P->st_hwpT.size() != (size_t)P->npT || P->st_hwphi.size() != (size_t)P->J ||
-                     !std::equal(P->st_hwpT.begin(), P->st_hwpT.end(), pT_w) || !std::equal(P->st_hwphi.begin(), P->st_hwphi.end(), phi_w))) {
-        std::vector<double> wl((size_t)P->st_nlw * 64, 0.0), wp((size_t)P->jtiles * P->JT, 0.0);
-        for (size_t l = 0; l < wl.size(); l++) {
-            const int c = (int)(l / P->st_npTp), i = (int)(l % P->st_npTp);
-            if (c < P->ncls && i < P->npT) wl[l] = pT_w[i];
-        }
-        for (int j = 0; j < P->J; j++) wp[j] = phi_w[j];
-        HIP_TRY(hipMemcpyAsync(P->d_st_wpT.p, wl.data(), wl.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(P->d_st_wphi.p, wp.data(), wp.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));   // the host vectors go out of scope
-        P->st_hwpT.assign(pT_w, pT_w + P->npT);
-        P->st_hwphi.assign(phi_w, phi_w + P->J);
-    }
-    std::vector<hipEvent_t> ev;
-    struct EvGuard { std::vector<hipEvent_t> &e; ~EvGuard() { for (auto x : e) (void)hipEventDestroy(x); } } evg{ev};
-    auto mark = [&](void) -> hipError_t {
-        if (!stats) return hipSuccess;
-        hipEvent_t e;
-        hipError_t r = hipEventCreate(&e);
-        if (r != hipSuccess) return r;
-        ev.push_back(e);
-        return hipEventRecord(e, st);
+    unsigned long long h[8];
+    is3d::StRun r{};
+    r.bs.tau = cells->tau; r.bs.ux = cells->ux; r.bs.uy = cells->uy; r.bs.un = cells->un;
+    r.bs.dat = cells->dat; r.bs.dax = cells->dax; r.bs.day = cells->day; r.bs.dan = cells->dan; r.bs.x = x; r.bs.y = y;
+    r.bs.n = n; r.bs.bins = bins; r.bs.out = out; r.bs.all_cells = 0;
+    r.linear_slots = P->feqmod ? st_linear_slots(P->st.pass) : 0;
+    r.kweight = P->d_kweight.p; r.device = P->device; r.split = split; r.stream = st;
+    r.d_status = P->d_status.p; r.d_sticky = P->d_sticky.p; r.status = h; r.stats = stats;
+    if (fstats) { r.ms_renorm = &fstats->ms_renorm; r.ms_linear = &fstats->ms_linear; }
+    r.pass = [=](int pass, int64_t c0, int32_t nc, int nch, const is3d::StMark &mark) {
+        return P->feqmod ? st_pass_feqmod(P, cells, st, pass, c0, nc, nch, mark) : st_pass_viscous(P, cells, split, st, pass, c0, nc, nch, mark);
     };
-    std::vector<int> stage;   // stage of the interval that ends at event i: 0 prep, 1 cells, 2 bins, 3 renormalisation, 4 linearised delta-f,
-                              // 5 a shard's D blocks placed in the assembled D
-    HIP_TRY(status_begin(P, st));
-    HIP_TRY(hipMemsetAsync(P->d_st_counters.p, 0, 4 * sizeof(unsigned long long), st));
-    HIP_TRY(mark());
-
-    // ---- bin stage (cf_spacetime.h), part 1: keys and the stable counting sort of every histogram (once per execute) ----
-    is3d::StBinStage bs{};
-    const int64_t Bs[3] = {tb, rbn, trb};
-    double *hout[3] = {nullptr, nullptr, nullptr};
-    if (do_bins) {
-        bs.tau = cells->tau; bs.ux = cells->ux; bs.uy = cells->uy; bs.un = cells->un;
-        bs.dat = cells->dat; bs.dax = cells->dax; bs.day = cells->day; bs.dan = cells->dan; bs.x = x; bs.y = y;
-        bs.n = n; bs.cls = P->d_st_cls.p; bs.pg = P->d_st_pg.p; bs.S = S; bs.all_cells = 0;
-        bs.bins = bins; bs.out = out; bs.counters = P->d_st_counters.p;
-        rc = is3d::spacetime_bins_begin(P->st_bins, bs, st);
-        if (rc) return rc;
-        for (int h = 0; h < 3; h++) hout[h] = bs.hout[h];
-        HIP_TRY(mark()); stage.push_back(2);
+    rc = is3d::spacetime_run(P->st, r);
+    if (rc || !stats) return rc;
+    if (fstats && n > 0) {
+        fstats->n_cells_breakdown = (int64_t)h[4];
+        fstats->n_renorm_skipped = (int64_t)h[2] * (o.df_mode == 4 ? P->ncls : 1);   // df_mode 4: whole cells (cf_prep_feqmod)
+        fstats->first_cell_out_of_range = h[7] == ~0ULL ? -1 : (int64_t)h[7];
     }
-    // ---- bin stage, part 2: a block of D, cells [c0, c0 + nc) in ascending order, onto the running sums ----
-    auto sum_bins = [&](const double *D, int64_t nc, int64_t c0, int first) -> int {
-        if (int r = is3d::spacetime_bins_add(bs, D, nc, c0, first, st)) return r;
-        HIP_TRY(mark()); stage.push_back(2);
-        return IS3D_OK;
-    };
-
-    if (n == 0) {
-        if (do_bins) {
-            HIP_TRY(hipMemsetAsync(out->dN_dy, 0, sizeof(double) * S, st));
-            for (int h = 0; h < 3; h++) HIP_TRY(hipMemsetAsync(hout[h], 0, sizeof(double) * S * Bs[h], st));
-            HIP_TRY(hipMemsetAsync(out->dN_dydeta, 0, sizeof(double) * S * n_eta_eff, st));
-        }
-    } else {
-        // (the feqmod records carry p.dsigma unscaled)
-        if (do_cells && !P->feqmod) {
-            HIP_TRY(is3d::launch_pds_bound(is3d::cell_ptrs(*cells), n, P->dim3, P->kmin, P->kmax, P->gw2d, P->mTmax, P->pTmax, P->d_status.p + 6, st));
-            if (split && split->exchange) {
-                // a shard: the records take the scale of the WHOLE surface, so that they -- and D -- are the single-device ones bit for bit
-                unsigned long long mine = 0, all = 0;
-                HIP_TRY(hipMemcpyAsync(&mine, P->d_status.p + 6, sizeof mine, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                rc = split->exchange(mine, &all);
-                if (rc) return rc;
-                HIP_TRY(hipMemcpyAsync(P->d_status.p + 6, &all, sizeof all, hipMemcpyHostToDevice, st));
-                HIP_TRY(hipStreamSynchronize(st));   // `all` goes out of scope
-            }
-        }
-        const int64_t pc = P->st_pass;
-        const int G = (P->st_nlw + 3) / 4;
-        int nch = (int)std::min<int64_t>(pc, std::max<int64_t>(1, 16384 / G));
-        if (!P->dim3) nch = (int)std::max<int64_t>(1, std::min<int64_t>(nch, ((int64_t)256 << 20) / (8 * (int64_t)P->ncls * K)));
-        const int GL = P->feqmod ? st_linear_slots(pc) : 0;
-        if (!P->dim3 && do_cells) HIP_TRY(st_grow(P->d_st_slab, (size_t)(nch + GL) * P->ncls * K));
-        const int npasses = do_cells ? (int)((n + pc - 1) / pc) : 0;
-        for (int pass = 0; pass < npasses; pass++) {
-            const int64_t c0 = (int64_t)pass * pc;
-            const int32_t nc = (int32_t)std::min<int64_t>(pc, n - c0);
-            if (P->feqmod) {
-                // ---- the feqmod records (operation 0's form), df_mode 3 renormalisation, per-cell stage, breakdown cells ----
-                is3d::FqPrepParams fp{};
-                fp.cells = is3d::cell_ptrs(*cells);
-                fp.baryon = P->baryon; fp.baryondiff = P->baryondiff; fp.bil = P->bil;
-                fp.cell0 = c0; fp.n_cells = nc; fp.J = P->J; fp.K = K;
-                fp.dim3 = P->dim3; fp.mode = o.df_mode;
-                fp.include_bulk = o.include_bulk_deltaf != 0; fp.include_shear = o.include_shear_deltaf != 0;
-                fp.cosphi = P->d_cosphi.p; fp.sinphi = P->d_sinphi.p; fp.kgrid = P->d_kgrid.p; fp.kweight = P->d_kweight.p;
-                fp.spl = P->spl;
-                fp.nj = P->nj;
-                fp.jx = P->d_jonah.p; fp.jl2 = fp.jx + P->nj; fp.jz = fp.jx + 2 * P->nj; fp.jcl = fp.jx + 3 * P->nj; fp.jcz = fp.jx + 4 * P->nj;
-                fp.bp_max = P->bp_max;
-                fp.mTmax = P->mTmax; fp.kmin = P->kmin; fp.kmax = P->kmax;
-                fp.pTmax = P->pTmax; fp.scale_rows = 0;   // D holds the unscaled value: no power-of-two row scale
-                fp.ngl = P->ngl; fp.gl = P->d_gl.p;
-                fp.detA_min = P->detA_min; fp.mass_pion0 = P->mass_pion0;
-                fp.JT = P->JT; fp.R = P->KT; fp.jtiles = P->jtiles; fp.rblocks = P->rblocks;
-                fp.TS = P->d_TS.p; fp.CR = P->d_CR.p; fp.FB = P->d_FB.p; fp.flag = P->d_flag.p;
-                fp.status = P->d_status.p;
-                HIP_TRY(is3d::launch_prep_feqmod(fp, st, true));
-                HIP_TRY(mark()); stage.push_back(0);
-                if (o.df_mode == 3) {
-                    HIP_TRY(is3d::launch_feqmod_renorm(P->d_CR.p, P->d_gl.p, P->ngl, P->d_cls_mass.p, P->d_cls_sign.p,
-                                                       P->baryon ? P->d_cls_baryon.p : nullptr, P->ncls, nc, fp.include_bulk, P->dim3,
-                                                       P->d_RN.p, st, P->d_status.p + 2));
-                    HIP_TRY(mark()); stage.push_back(3);
-                }
-                is3d::StFqCellArgs a{};
-                a.TS = P->d_TS.p; a.nc = nc; a.J = P->J; a.K = K; a.jtiles = P->jtiles; a.rblocks = P->rblocks;
-                a.ncls = P->ncls; a.npTp = P->st_npTp; a.nlw = P->st_nlw; a.G = G; a.nch = (int)std::min<int64_t>(nch, nc);
-                a.zskip = o.zero_skip != 2;
-                a.lane_mT = P->d_st_mT.p; a.lane_pT = P->d_st_pT.p; a.lane_sign = P->d_st_sign.p; a.lane_b = P->d_st_b.p; a.lane_wpT = P->d_st_wpT.p;
-                a.wphi = P->d_st_wphi.p; a.RN = o.df_mode == 3 ? P->d_RN.p : nullptr;
-                a.D = P->d_st_D.p; a.eta_slab = P->dim3 ? nullptr : P->d_st_slab.p;
-                HIP_TRY(is3d::launch_spacetime_feqmod_cells(a, P->dim3, o.df_mode == 3, P->baryon, o.outflow != 0, P->JT, P->KT, st));
-                HIP_TRY(mark()); stage.push_back(1);
-                HIP_TRY(is3d::launch_feqmod_compact(P->d_flag.p, nc, P->d_list.p, P->d_count.p, P->d_status.p, st));
-                is3d::StFqLinearArgs la{};
-                la.FB = P->d_FB.p; la.list = P->d_list.p; la.count = P->d_count.p;
-                la.lane_mT = P->d_st_mT.p; la.lane_pT = P->d_st_pT.p; la.lane_sign = P->d_st_sign.p; la.lane_mass = P->d_st_mass.p;
-                la.lane_b = P->baryon ? P->d_st_b.p : nullptr; la.lane_wpT = P->d_st_wpT.p;
-                la.cosphi = P->d_cosphi.p; la.sinphi = P->d_sinphi.p; la.wphi = P->d_st_wphi.p; la.kgrid = P->d_kgrid.p; la.kweight = P->d_kweight.p;
-                la.RN = o.df_mode == 3 ? P->d_RN.p : nullptr;
-                la.nc = nc; la.J = P->J; la.K = K; la.ncls = P->ncls; la.npTp = P->st_npTp; la.nlw = P->st_nlw; la.G = G; la.GL = GL; la.nch = a.nch;
-                la.dim3 = P->dim3; la.mode = o.df_mode; la.outflow = o.outflow != 0; la.regulate = o.regulate_deltaf != 0;
-                la.D = P->d_st_D.p; la.eta_slab = P->dim3 ? nullptr : P->d_st_slab.p;
-                HIP_TRY(is3d::launch_spacetime_feqmod_linear(la, st));
-                if (!P->dim3) HIP_TRY(is3d::launch_spacetime_eta_reduce(P->d_st_slab.p, a.nch + GL, (int64_t)P->ncls * K, pass == 0, P->d_st_eta.p, st));
-                HIP_TRY(mark()); stage.push_back(4);
-            } else {
-                is3d::PrepParams pp = fill_prep(P, cells, c0, nc);
-                pp.tiled = 1;
-                pp.pds_bound = P->d_status.p + 6;
-                pp.TE = nullptr;   // the E2 tables of cf_main_tile3e are not needed here
-                HIP_TRY(is3d::launch_prep(pp, st));
-                HIP_TRY(mark()); stage.push_back(0);
-
-                is3d::StCellArgs a{};
-                a.TS = P->d_TS.p; a.nc = nc; a.J = P->J; a.K = K; a.jtiles = P->jtiles; a.rblocks = P->rblocks;
-                a.ncls = P->ncls; a.npTp = P->st_npTp; a.nlw = P->st_nlw; a.G = G; a.nch = (int)std::min<int64_t>(nch, nc);
-                a.outflow = o.outflow != 0; a.regulate = o.regulate_deltaf != 0; a.zskip = o.zero_skip != 2;
-                a.lane_mT = P->d_st_mT.p; a.lane_pT = P->d_st_pT.p; a.lane_sign = P->d_st_sign.p; a.lane_b = P->d_st_b.p; a.lane_wpT = P->d_st_wpT.p;
-                a.wphi = P->d_st_wphi.p; a.pds_bound = P->d_status.p + 6;
-                a.D = P->d_st_D.p; a.eta_slab = P->dim3 ? nullptr : P->d_st_slab.p;
-                HIP_TRY(is3d::launch_spacetime_cells(a, P->ce, P->dim3, P->baryon, P->JT, P->KT, st));
-                if (!P->dim3) HIP_TRY(is3d::launch_spacetime_eta_reduce(P->d_st_slab.p, a.nch, (int64_t)P->ncls * K, pass == 0, P->d_st_eta.p, st));
-                HIP_TRY(mark()); stage.push_back(1);
-            }
-
-            if (split) {
-                // the pass's block [class][nc] into the assembled [class][n_total] at the shard's global cell offset
-                double *dst = split->D_full + split->c_off + c0;
-                if (split->D_device == P->device)
-                    HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double) * (size_t)split->n_total, P->d_st_D.p, sizeof(double) * (size_t)nc,
-                                             sizeof(double) * (size_t)nc, (size_t)P->ncls, hipMemcpyDeviceToDevice, st));
-                else
-                    for (int c = 0; c < P->ncls; c++)
-                        HIP_TRY(hipMemcpyPeerAsync(dst + (int64_t)c * split->n_total, split->D_device, P->d_st_D.p + (int64_t)c * nc, P->device,
-                                                   sizeof(double) * (size_t)nc, st));
-                HIP_TRY(mark()); stage.push_back(5);
-            } else {
-                rc = sum_bins(P->d_st_D.p, nc, c0, pass == 0);
-                if (rc) return rc;
-            }
-        }
-        if (do_bins) {
-            if (split) {   // the whole assembled D at once: the same left-to-right sums as pass after pass
-                rc = sum_bins(split->D_full, n, 0, 1);
-                if (rc) return rc;
-            }
-            // dN/dy deta: 2+1D one value per eta node (:1365); 3+1D the single point of the species' total (quirk 2)
-            if (P->dim3) HIP_TRY(hipMemcpyAsync(out->dN_dydeta, out->dN_dy, sizeof(double) * S, hipMemcpyDeviceToDevice, st));
-            else HIP_TRY(is3d::launch_spacetime_eta_final(P->d_st_eta.p, P->d_st_cls.p, P->d_st_pg.p, P->d_kweight.p, S, K, out->dN_dydeta, st));
-            HIP_TRY(mark()); stage.push_back(2);
-        }
-        if (!stats) HIP_TRY(is3d::launch_fold_status(P->d_status.p, P->d_sticky.p, st));
-    }
-    if (stats) {
-        unsigned long long h[8], cn[4];
-        HIP_TRY(hipMemcpyAsync(h, P->d_status.p, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(cn, P->d_st_counters.p, sizeof cn, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (size_t i = 1; i < ev.size(); i++) {
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ev[i - 1], ev[i]));
-            if (stage[i - 1] == 5) { stats->ms_d2h += ms; continue; }
-            if (stage[i - 1] >= 3) {
-                if (fstats) (stage[i - 1] == 3 ? fstats->ms_renorm : fstats->ms_linear) += ms;
-                continue;
-            }
-            (stage[i - 1] == 0 ? stats->ms_prep : stage[i - 1] == 1 ? stats->ms_cells : stats->ms_bins) += ms;
-        }
-        if (fstats && n > 0) {
-            fstats->n_cells_breakdown = (int64_t)h[4];
-            fstats->n_renorm_skipped = (int64_t)h[2] * (o.df_mode == 4 ? P->ncls : 1);   // df_mode 4: whole cells (cf_prep_feqmod)
-            fstats->first_cell_out_of_range = h[7] == ~0ULL ? -1 : (int64_t)h[7];
-        }
-        stats->n_classes = P->ncls;
-        stats->n_passes = (n == 0 || !do_cells) ? 0 : (int32_t)((n + P->st_pass - 1) / P->st_pass);
-        stats->n_cells_skipped = n == 0 ? 0 : (int64_t)h[1];
-        stats->n_tau_outside = (int64_t)cn[0];
-        stats->n_r_outside = (int64_t)cn[1];
-        stats->n_tau_negative = (int64_t)cn[2];
-        stats->n_r_negative = (int64_t)cn[3];
-        return status_finish(P, h, &stats->bad_cell, &stats->code);
-    }
-    return IS3D_OK;
+    stats->n_cells_skipped = n == 0 ? 0 : (int64_t)h[1];
+    return status_finish(P, h, &stats->bad_cell, &stats->code);
 }
 
 extern "C" int is3d_plan_execute_spacetime(is3d_plan *P, const is3d_cells *cells, const double *x, const double *y, const double *pT_w,
@@ -1346,16 +1180,19 @@ extern "C" int is3d_plan_execute_spacetime_feqmod(is3d_plan *P, const is3d_cells
     return st_execute(P, cells, x, y, pT_w, phi_w, bins, out, hip_stream, stats ? stats : (fstats ? &local : nullptr), fstats);
 }
 
-// the argument checks of the one-shot entries (and of the entry that shards the cells over devices, cf_multi.hip): no device is touched
+// the argument checks of the one-shot entries (and of the entry that shards the cells over devices, cf_multi.hip) that need no plan, in the
+// order of their refusals: bins, grid, what plan creation would refuse, outputs.  No device is touched
 static int st_check_args(const is3d_species *species, const is3d_grid *grid, const is3d_df_tables *df, const is3d_feqmod_tables *fq,
-                         const is3d_options *opts, const is3d_spacetime_bins *bins, const double *x, const double *y)
+                         const is3d_options *opts, const is3d_spacetime_bins *bins, const double *x, const double *y, const is3d_spacetime_out *out)
 {
     int rc = st_check(bins, x, y, opts->df_mode, fq != nullptr);
     if (!rc && fq && opts->include_baryon && opts->df_mode == 4)
         rc = fail(IS3D_EINVAL, "df_mode 4 does not work with include_baryon = 1 (the reference exits there too)");
-    if (!rc && fq) rc = validate(species, grid, df, fq, opts);   // every check before the plan touches the device
-    if (!rc && grid && (opts->dimension == 2 || opts->dimension == 3)) rc = st_check_grid(opts->dimension == 3, fq != nullptr, grid->n_pT, grid->n_eta);
-    return rc;
+    if (!rc && fq) rc = validate(species, grid, df, fq, opts);
+    if (!rc && grid && (opts->dimension == 2 || opts->dimension == 3))
+        rc = is3d::spacetime_check_grid(opts->dimension == 3, st_lds_cap(fq != nullptr), grid->n_pT, grid->n_eta);
+    if (!rc && !fq) rc = validate(species, grid, df, nullptr, opts);
+    return rc ? rc : is3d::spacetime_check_out(out);
 }
 
 static int st_oneshot(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species, const is3d_grid *grid,
@@ -1365,59 +1202,16 @@ static int st_oneshot(const is3d_cells *cells, const double *x, const double *y,
     if (stats) { memset(stats, 0, sizeof *stats); stats->bad_cell = -1; }
     if (fstats) { memset(fstats, 0, sizeof *fstats); fstats->first_cell_out_of_range = -1; }
     if (!cells || !out || !opts || !pT_w || !phi_w) return fail(IS3D_EINVAL, "null argument");
-    int rc = st_check_args(species, grid, df, fq, opts, bins, x, y);
+    int rc = st_check_args(species, grid, df, fq, opts, bins, x, y, out);
     if (rc) { if (stats) stats->code = rc; return rc; }
     is3d_plan *P = nullptr;
     rc = plan_create_impl(&P, species, grid, df, fq, opts, std::max<int64_t>(cells->n_cells, 1));
     if (rc) { if (stats) stats->code = rc; return rc; }
     struct Guard { is3d_plan *p; ~Guard() { is3d_plan_destroy(p); } } guard{P};
-    const int64_t n = cells->n_cells;
-    const int S = P->npart, n_eta_eff = P->dim3 ? 1 : P->K;
-    const int64_t tb = bins->tau_bins, rbn = bins->r_bins;
     const bool diff = opts->include_baryon && opts->include_baryondiff_deltaf;
-    const auto keep = [diff](int a) { return a < 18 || diff; };
-    const size_t sizes[6] = {(size_t)S, (size_t)(S * tb), (size_t)(S * rbn), (size_t)(S * tb * rbn), (size_t)S * n_eta_eff,
-                             out->dN_dy_cell ? (size_t)S * n : 0};
-    double *host_out[6] = {out->dN_dy, out->dN_taudtaudy, out->dN_twopirdrdy, out->dN_twopitaurdtaudrdy, out->dN_dydeta, out->dN_dy_cell};
-    for (int i = 0; i < 5; i++)
-        if (!host_out[i]) return fail(IS3D_EINVAL, "a required output array is NULL");
-    size_t total = 0;
-    for (size_t s : sizes) total += s;
-    DevBuf<double> dcell, dout;
-    HIP_TRY(dcell.alloc((size_t)std::max<int64_t>(n, 1) * (is3d::kCellArrays + 2)));   // the cell arrays, then x and y
-    HIP_TRY(dout.alloc(total));
-    hipEvent_t e0, e1, e2, e3;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventCreate(&e2)); HIP_TRY(hipEventCreate(&e3));
-    struct EvGuard { hipEvent_t e[4]; ~EvGuard() { for (auto v : e) (void)hipEventDestroy(v); } } evg{{e0, e1, e2, e3}};
-    HIP_TRY(hipEventRecord(e0, nullptr));
-    is3d_cells dc;
-    HIP_TRY(is3d::stage_cells(*cells, keep, 0, n, dcell.p, nullptr, &dc));
-    std::array<const double *, 2> xy = {x, y};
-    HIP_TRY(is3d::stage_arrays(xy, 0, n, dcell.p + (size_t)is3d::kCellArrays * n, nullptr));
-    HIP_TRY(hipEventRecord(e1, nullptr));
-    const double *dx = n > 0 ? xy[0] : dcell.p, *dy = n > 0 ? xy[1] : dcell.p;
-    is3d_spacetime_out dev{};
-    double *dev_out[6];
-    size_t off = 0;
-    for (int i = 0; i < 6; i++) { dev_out[i] = sizes[i] ? dout.p + off : nullptr; off += sizes[i]; }
-    dev.dN_dy = dev_out[0]; dev.dN_taudtaudy = dev_out[1]; dev.dN_twopirdrdy = dev_out[2]; dev.dN_twopitaurdtaudrdy = dev_out[3];
-    dev.dN_dydeta = dev_out[4]; dev.dN_dy_cell = dev_out[5];
-    is3d_spacetime_stats stt{};
-    rc = st_execute(P, &dc, dx, dy, pT_w, phi_w, bins, &dev, nullptr, &stt, fstats);
-    if (rc) { if (stats) *stats = stt; return rc; }
-    HIP_TRY(hipEventRecord(e2, nullptr));
-    for (int i = 0; i < 6; i++)
-        if (sizes[i]) HIP_TRY(hipMemcpyAsync(host_out[i], dev_out[i], sizes[i] * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipEventRecord(e3, nullptr));
-    HIP_TRY(hipEventSynchronize(e3));
-    float h2d = 0, d2h = 0;
-    HIP_TRY(hipEventElapsedTime(&h2d, e0, e1));
-    HIP_TRY(hipEventElapsedTime(&d2h, e2, e3));
-    stt.ms_h2d = h2d;
-    stt.ms_d2h = d2h;
-    stt.code = IS3D_OK;
-    if (stats) *stats = stt;
-    return IS3D_OK;
+    return is3d::spacetime_oneshot(*cells, x, y, [diff](int a) { return a < 18 || diff; }, P->npart, P->dim3 ? 1 : P->K, bins, out, stats,
+                                   [&](const is3d_cells &dc, const double *dx, const double *dy, const is3d_spacetime_out &dev,
+                                       is3d_spacetime_stats *stt) { return st_execute(P, &dc, dx, dy, pT_w, phi_w, bins, &dev, nullptr, stt, fstats); });
 }
 
 namespace is3d {
@@ -1426,11 +1220,7 @@ int spacetime_check_args(const is3d_cells *cells, const double *x, const double 
                          const is3d_spacetime_bins *bins, const is3d_spacetime_out *out)
 {
     if (!cells || !out || !opts || !pT_w || !phi_w) return fail(IS3D_EINVAL, "null argument");
-    int rc = st_check_args(species, grid, df, fq, opts, bins, x, y);
-    if (!rc && !fq) rc = validate(species, grid, df, nullptr, opts);   // what plan creation would refuse, before any device sees a plan
-    if (rc) return rc;
-    if (!out->dN_dy || !out->dN_taudtaudy || !out->dN_twopirdrdy || !out->dN_twopitaurdtaudrdy || !out->dN_dydeta)
-        return fail(IS3D_EINVAL, "a required output array is NULL");
+    if (int rc = st_check_args(species, grid, df, fq, opts, bins, x, y, out)) return rc;
     if (cells->n_cells < 0) return fail(IS3D_EINVAL, "n_cells < 0");
     if (cells->n_cells > 0x7fff0000LL) return fail(IS3D_EINVAL, "operation 0 takes up to 2^31 cells");
     return check_cells(cells, opts->dimension == 3, *opts, opts->include_baryon && opts->include_baryondiff_deltaf);
@@ -1443,7 +1233,7 @@ int spacetime_execute_split(is3d_plan *plan, const is3d_cells *cells, const doub
     return st_execute(plan, cells, x, y, pT_w, phi_w, bins, out, hip_stream, stats, nullptr, split);
 }
 int plan_classes(const is3d_plan *P) { return P ? P->ncls : 0; }
-double *plan_st_eta(const is3d_plan *P) { return P ? P->d_st_eta.p : nullptr; }
+double *plan_st_eta(const is3d_plan *P) { return P ? P->st.d_eta.p : nullptr; }
 }  // namespace is3d
 
 extern "C" int is3d_spacetime_distributions(const is3d_cells *cells, const double *x, const double *y, const is3d_species *species,

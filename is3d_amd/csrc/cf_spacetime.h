@@ -1,10 +1,15 @@
-// cf_spacetime.h -- launch entry points of cf_spacetime.hip (operation 0: smooth Cooper-Frye spacetime distributions).
+// cf_spacetime.h -- operation 0 (smooth Cooper-Frye spacetime distributions): the launch entry points of cf_spacetime.hip,
+// cf_spacetime_feqmod.hip and cf_spacetime_vah.hip, and the host driver that is3d_plan (cf_plan.cpp) and is3d_vah_plan (cf_vah.hip) share
+// (cf_spacetime_host.cpp: state, setup, checks, weights, the pass loop around the plans' own records and per-cell launches, the one-shot wrapper).
 #pragma once
 #include "cf_device.h"
 #include "cf_host.h"
 #include <hip/hip_runtime_api.h>
+#include <algorithm>
+#include <array>
 #include <cstdint>
 #include <functional>
+#include <vector>
 #include "../../include/is3d_amd.h"
 namespace is3d {
 
@@ -119,7 +124,7 @@ int spacetime_bins_begin(StBinWork &w, StBinStage &s, hipStream_t st);
 // D: [class][nc]; first != 0 starts the sums, otherwise they continue from out
 int spacetime_bins_add(const StBinStage &s, const double *D, int64_t nc, int64_t c0, int first, hipStream_t st);
 
-// ---- the two halves of an execute, for the cell-axis split over devices (cf_multi.hip; defined in cf_plan.cpp) ----
+// ---- the two halves of an execute, for the cell-axis split over devices (cf_multi.hip) ----
 // ST_CELLS: records and the per-cell stage of a shard's cells; every pass's D block [class][nc] lands in D_full[class][n_total] at cell
 //           c_off + c0 (a 2-D copy on D_device, row-wise hipMemcpyPeerAsync from another device); in 2+1D the shard's class rows of
 //           dN/dy deta stay in the plan (plan_st_eta).  No keys, no sort, no sums; bins, x, y and out are not read.
@@ -134,6 +139,111 @@ struct StSplit {
     // df_mode 1 / 2: the shard's |p.dsigma| bound (bits) goes in, the bound of the whole surface comes out; called once, before the records
     std::function<int(unsigned long long, unsigned long long *)> exchange;
 };
+
+// ---- the host driver of operation 0 (cf_spacetime_host.cpp), whichever plan it serves ----
+// what a plan keeps for operation 0: the shape, the lane tables of the per-cell kernels (class-major, npTp lane slots per class, nlw waves),
+// the weights now on the device and their host copies, and the workspaces; made by spacetime_setup on the first such execute
+struct StState {
+    bool ready = false;
+    int ncls = 0, npT = 0, J = 0, K = 0, S = 0, dim3 = 1, nphi = 0;   // nphi = jtiles * JT slots of d_wphi
+    int npTp = 0, nlw = 0;
+    int64_t pass = 0;                                                  // cells per pass
+    std::vector<double> hwpT, hwphi;                                   // the weights now on the device (d_wpT, d_wphi)
+    DevBuf<double> d_mT, d_pT, d_sign, d_b, d_mass, d_wpT, d_wphi, d_pg, d_D, d_slab, d_eta;
+    DevBuf<int32_t> d_cls;
+    DevBuf<unsigned long long> d_counters;
+    StBinWork bins;
+};
+// the lanes past the classes and past the pT grid (w_pT = 0) take part in the kernels' wave-wide tests:
+// ST_PAD_UNIT: mT = 1, pT = 0, sign = 1, b = 0, mass = 1;  ST_PAD_REPEAT: class 0 / pT index 0 stand in for whichever of the two is past its end
+enum StPad { ST_PAD_UNIT, ST_PAD_REPEAT };
+struct StSetup {
+    int ncls, npT, J, K, dim3, jtiles, JT, npart;
+    const double *cls_mass, *cls_sign, *cls_bar;   // [ncls]; cls_bar may be NULL
+    const double *pT_grid, *sp_deg;                // [npT], [npart]
+    const int32_t *sp_cls;                         // [npart]
+    double prefactor;
+    int64_t bytes_per_cell, pass_cells, workspace_bytes;   // the plan's record stream; D (8 B per class and cell) shares its cap
+    bool mass_lanes, b_lanes;                      // upload d_mass, d_b
+    StPad pad;
+};
+int spacetime_setup(StState &s, const StSetup &a);
+// the checks, none of which touches a device.  lds_cap_bytes: what the per-cell kernel has for its 2+1D eta rows
+int spacetime_check_bins(const is3d_spacetime_bins *b, const double *x, const double *y);
+int spacetime_check_grid(bool dim3, size_t lds_cap_bytes, int npT, int K);
+int spacetime_check_out(const is3d_spacetime_out *out);
+// the momentum weights of the reduction, uploaded when they differ from the state's copy (the first execute, or new weights; only then does
+// the host wait for the stream)
+int spacetime_upload_weights(StState &s, const double *pT_w, const double *phi_w, hipStream_t st);
+
+// one execute.  Stage tags of the timer: 0 prep, 1 cells, 2 bins, 3 renormalisation, 4 linearised delta-f, 5 a shard's D blocks placed
+using StMark = std::function<hipError_t(int)>;   // ends a timed interval of the given stage (nothing without stats)
+struct StRun {
+    StBinStage bs;                       // the caller's part: the device arrays of the n cells, x, y, n, bins, out, all_cells
+    int linear_slots;                    // 2+1D: slab slots past the chunks' (cf_st_fq_linear), else 0
+    const double *kweight;               // 2+1D: [K] effective eta weights
+    int device;
+    StSplit *split;                      // the halves of an execute; NULL: both
+    hipStream_t stream;
+    unsigned long long *d_status;        // the plan's 8 status words (cf_device.h), started here
+    unsigned long long *d_sticky;        // may be NULL: launch_fold_status after an execute of n > 0 cells without stats
+    unsigned long long *status;          // [8]: the status words, read back when stats != NULL
+    is3d_spacetime_stats *stats;         // NULL: no timer, no read-back, the host does not wait
+    double *ms_renorm, *ms_linear;       // stages 3 and 4 (may be NULL)
+    // records and per-cell launch(es) of pass `pass`, cells [c0, c0 + nc), into d_D (2+1D: nch chunks' eta partials in d_slab, reduced into d_eta)
+    std::function<int(int pass, int64_t c0, int32_t nc, int nch, const StMark &mark)> pass;
+};
+// fills stats' times, n_classes, n_passes and the four bin counters; bad_cell, code and n_cells_skipped are the caller's to decode from status
+int spacetime_run(StState &s, const StRun &r);
+
+// the one-shot entries: host cells, x, y and outputs through one device block each around `exec` (plan execute on the device copies, its
+// stats into *stt); H2D and D2H times into stats.  keep(i): cell array i is staged.  S species, n_eta_eff eta points of dN_dydeta
+template <class Cells, class Keep, class Exec>
+int spacetime_oneshot(const Cells &cells, const double *x, const double *y, Keep keep, int S, int n_eta_eff, const is3d_spacetime_bins *bins,
+                      const is3d_spacetime_out *out, is3d_spacetime_stats *stats, Exec exec)
+{
+    const int64_t n = cells.n_cells, tb = bins->tau_bins, rbn = bins->r_bins;
+    const size_t narr = cell_arrays(cells).size();
+    const size_t sizes[6] = {(size_t)S, (size_t)(S * tb), (size_t)(S * rbn), (size_t)(S * tb * rbn), (size_t)S * n_eta_eff,
+                             out->dN_dy_cell ? (size_t)S * n : 0};
+    double *host_out[6] = {out->dN_dy, out->dN_taudtaudy, out->dN_twopirdrdy, out->dN_twopitaurdtaudrdy, out->dN_dydeta, out->dN_dy_cell};
+    size_t total = 0;
+    for (size_t s : sizes) total += s;
+    DevBuf<double> dcell, dout;
+    HIP_TRY(dcell.alloc((size_t)std::max<int64_t>(n, 1) * (narr + 2)));   // the cell arrays, then x and y
+    HIP_TRY(dout.alloc(total));
+    hipEvent_t e[4] = {};
+    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{e};
+    for (auto &v : e) HIP_TRY(hipEventCreate(&v));
+    HIP_TRY(hipEventRecord(e[0], nullptr));
+    Cells dc;
+    HIP_TRY(stage_cells(cells, keep, 0, n, dcell.p, nullptr, &dc));
+    std::array<const double *, 2> xy = {x, y};
+    HIP_TRY(stage_arrays(xy, 0, n, dcell.p + narr * (size_t)n, nullptr));
+    HIP_TRY(hipEventRecord(e[1], nullptr));
+    const double *dx = n > 0 ? xy[0] : dcell.p, *dy = n > 0 ? xy[1] : dcell.p;
+    double *dev_out[6];
+    size_t off = 0;
+    for (int i = 0; i < 6; i++) { dev_out[i] = sizes[i] ? dout.p + off : nullptr; off += sizes[i]; }
+    const is3d_spacetime_out dev{dev_out[0], dev_out[1], dev_out[2], dev_out[3], dev_out[4], dev_out[5]};
+    is3d_spacetime_stats stt{};
+    const int rc = exec(dc, dx, dy, dev, &stt);
+    if (rc) { if (stats) *stats = stt; return rc; }
+    HIP_TRY(hipEventRecord(e[2], nullptr));
+    for (int i = 0; i < 6; i++)
+        if (sizes[i]) HIP_TRY(hipMemcpyAsync(host_out[i], dev_out[i], sizes[i] * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipEventRecord(e[3], nullptr));
+    HIP_TRY(hipEventSynchronize(e[3]));
+    float h2d = 0, d2h = 0;
+    HIP_TRY(hipEventElapsedTime(&h2d, e[0], e[1]));
+    HIP_TRY(hipEventElapsedTime(&d2h, e[2], e[3]));
+    stt.ms_h2d = h2d;
+    stt.ms_d2h = d2h;
+    stt.code = IS3D_OK;
+    if (stats) *stats = stt;
+    return IS3D_OK;
+}
+
 int spacetime_execute_split(is3d_plan *plan, const is3d_cells *cells, const double *x, const double *y, const double *pT_w, const double *phi_w,
                             const is3d_spacetime_bins *bins, const is3d_spacetime_out *out, void *hip_stream, is3d_spacetime_stats *stats,
                             StSplit *split);

@@ -829,14 +829,7 @@ struct is3d_vah_plan {
     // lane slots per class -- not the mT-sorted lanes of the spectra kernel) and its workspaces, made on the first such execute
     std::vector<int32_t> sp_cls;
     std::vector<double> cls_mass, cls_sign, pT_grid, sp_deg;
-    std::vector<double> st_hwpT, st_hwphi;   // the weights now on the device (d_st_wpT, d_st_wphi)
-    bool st_ready = false;
-    int st_npTp = 0, st_nlw = 0;
-    int64_t st_pass = 0;
-    is3d::DevBuf<double> d_st_mT, d_st_pT, d_st_sign, d_st_wpT, d_st_wphi, d_st_pg, d_st_D, d_st_slab, d_st_eta;
-    is3d::DevBuf<int32_t> d_st_cls;
-    is3d::DevBuf<unsigned long long> d_st_counters;
-    is3d::StBinWork st_bins;
+    is3d::StState st;
 
     ~is3d_vah_plan()
     {
@@ -1263,75 +1256,28 @@ extern "C" int is3d_smooth_spectra_vah(const is3d_vah_cells *cells, const is3d_s
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-int vah_st_check_bins(const is3d_spacetime_bins *b, const double *x, const double *y)
+// one pass: coefficients and "F" records, the per-cell stage
+int vah_st_pass(is3d_vah_plan *P, const std::array<const double *, is3d::kVahCellArrays> &src, hipStream_t st, int pass, int64_t c0, int32_t nc,
+                int nch, const is3d::StMark &mark)
 {
-    using is3d::set_error;
-    if (!x || !y) return set_error(IS3D_EINVAL, "operation 0 needs the cells' x and y positions (NULL given)");
-    if (!b) return set_error(IS3D_EINVAL, "null spacetime bins");
-    if (b->tau_bins < 1 || b->r_bins < 1) return set_error(IS3D_EINVAL, "tau_bins and r_bins must be >= 1 (got %d, %d)", b->tau_bins, b->r_bins);
-    if (!(b->tau_max > b->tau_min) || !(b->r_max > b->r_min))
-        return set_error(IS3D_EINVAL, "the bin ranges need tau_max > tau_min and r_max > r_min (got [%g, %g], [%g, %g])", b->tau_min, b->tau_max,
-                         b->r_min, b->r_max);
-    if ((int64_t)b->tau_bins * b->r_bins > ((int64_t)1 << 28)) return set_error(IS3D_EINVAL, "tau_bins x r_bins too large");
+    const is3d::StState &S = P->st;
+    const int K = P->K;
+    if (int rc = vah_records(P, src, c0, nc, st)) return rc;
+    HIP_TRY(mark(0));
+    is3d::StVahCellArgs a{};
+    a.TS = P->d_TS.as<double>(); a.nc = nc; a.J = P->J; a.K = K; a.jtiles = P->jtiles; a.rblocks = P->rblocks;
+    a.ncls = P->ncls; a.npTp = S.npTp; a.nlw = S.nlw; a.G = (S.nlw + 3) / 4; a.nch = (int)std::min<int64_t>(nch, nc);
+    a.zskip = P->o.zero_skip != 2;
+    a.lane_mT = S.d_mT.p; a.lane_pT = S.d_pT.p; a.lane_sign = S.d_sign.p; a.lane_wpT = S.d_wpT.p;
+    a.wphi = S.d_wphi.p;
+    a.D = S.d_D.p; a.eta_slab = P->three_d ? nullptr : S.d_slab.p;
+    HIP_TRY(is3d::launch_spacetime_vah_cells(a, P->three_d, P->o.regulate_deltaf != 0, P->JT, P->R, st));
+    if (!P->three_d) HIP_TRY(is3d::launch_spacetime_eta_reduce(S.d_slab.p, a.nch, (int64_t)P->ncls * K, pass == 0, S.d_eta.p, st));
+    HIP_TRY(mark(1));
     return IS3D_OK;
 }
 
-// what cf_st_vah_cells takes of a grid (the rule of cf_plan.cpp's st_check_grid): up to 64 pT values (one wave holds a class), and in 2+1D the
-// workgroup's eta rows in LDS -- [4 waves][64 / npTp classes][K] doubles within 64 KiB
-int vah_st_check_grid(bool dim3, int npT, int K)
-{
-    using is3d::set_error;
-    if (npT > 64) return set_error(IS3D_EINVAL, "operation 0 takes pT grids of up to 64 values (got %d)", npT);
-    int npTp = 1;
-    while (npTp < npT) npTp <<= 1;
-    const size_t cap = 64 * 1024, per_eta = sizeof(double) * 4 * (64 / npTp);
-    if (!dim3 && per_eta * (size_t)K > cap)
-        return set_error(IS3D_EINVAL, "operation 0 in 2+1D: %d pT values x %d eta nodes need more LDS than the per-cell kernel has (up to %d eta "
-                         "nodes with this pT grid)", npT, K, (int)(cap / per_eta));
-    return IS3D_OK;
-}
-
-// the spacetime lane tables and the per-pass workspace of a plan, made once
-int vah_st_setup(is3d_vah_plan *P)
-{
-    using is3d::set_error;
-    if (P->st_ready) return IS3D_OK;
-    int npTp = 1;
-    while (npTp < P->npT) npTp <<= 1;
-    P->st_npTp = npTp;
-    P->st_nlw = (P->ncls * npTp + 63) / 64;
-    const int nl = P->st_nlw * 64;
-    std::vector<double> mT(nl), pT(nl), sg(nl);
-    for (int l = 0; l < nl; l++) {
-        // padded lanes (w_pT = 0) repeat a lane of the grid: whatever cf_prep_vah's domain test admits for the grid is in range for them too
-        const int c = l / npTp < P->ncls ? l / npTp : 0, i = l % npTp < P->npT ? l % npTp : 0;
-        const double m = P->cls_mass[c], p = P->pT_grid[i];
-        mT[l] = std::sqrt(m * m + p * p);
-        pT[l] = p;
-        sg[l] = P->cls_sign[c];
-    }
-    HIP_TRY(P->d_st_mT.upload(mT));
-    HIP_TRY(P->d_st_pT.upload(pT));
-    HIP_TRY(P->d_st_sign.upload(sg));
-    HIP_TRY(P->d_st_wpT.alloc(nl));
-    HIP_TRY(P->d_st_wphi.alloc((size_t)P->jtiles * P->JT));
-    HIP_TRY(P->d_st_cls.upload(P->sp_cls));
-    const double prefactor = 1.0 / (8.0 * (M_PI * M_PI * M_PI)) / is3d::kHbarC / is3d::kHbarC / is3d::kHbarC;   // as is3d_vah_plan_execute
-    std::vector<double> pg(P->npart);
-    for (int s = 0; s < P->npart; s++) pg[s] = prefactor * P->sp_deg[s];
-    HIP_TRY(P->d_st_pg.upload(pg));
-    // passes: the plan's record stream plus D (8 B per class and cell) within the same cap as the spectra path
-    const int64_t ws = is3d::default_stream_cap_bytes(P->o.workspace_bytes);
-    const int64_t per_cell = (int64_t)sizeof(double) * P->jtiles * P->rblocks * P->REC + 8 * (int64_t)P->ncls;
-    P->st_pass = std::max<int64_t>(1, std::min<int64_t>(P->pass_cells, ws / per_cell));
-    const hipError_t e = P->d_st_D.alloc((size_t)P->ncls * P->st_pass);
-    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return set_error(IS3D_ENOMEM, "out of device memory allocating the per-cell workspace D"); }
-    HIP_TRY(e);
-    if (!P->three_d) HIP_TRY(P->d_st_eta.alloc((size_t)P->ncls * P->K));
-    HIP_TRY(P->d_st_counters.alloc(4));
-    P->st_ready = true;
-    return IS3D_OK;
-}
+constexpr size_t kVahStLds = 64 * 1024;   // cf_st_vah_cells' LDS for the 2+1D eta rows
 
 }  // namespace
 
@@ -1342,130 +1288,53 @@ extern "C" int is3d_vah_plan_execute_spacetime(is3d_vah_plan *P, const is3d_vah_
     using is3d::set_error;
     if (stats) { memset(stats, 0, sizeof *stats); stats->bad_cell = -1; }
     if (!P || !cells || !out || !pT_w || !phi_w) return set_error(IS3D_EINVAL, "null argument");
-    if (int rc = vah_st_check_bins(bins, x, y)) return rc;
+    if (int rc = is3d::spacetime_check_bins(bins, x, y)) return rc;
     if (!P->fact || !is3d::spacetime_vah_shape_supported(P->three_d, P->JT, P->R))
         return set_error(IS3D_EINVAL, "operation 0 runs on the plan's \"F\" unit records of the default kernel variant (this plan: %d x %d records, "
                          "kernel_variant %d)", P->JT, P->R, P->o.kernel_variant);
-    if (int rc = vah_st_check_grid(P->three_d, P->npT, P->K)) return rc;
-    if (!out->dN_dy || !out->dN_taudtaudy || !out->dN_twopirdrdy || !out->dN_twopitaurdtaudrdy || !out->dN_dydeta)
-        return set_error(IS3D_EINVAL, "a required output array is NULL");
+    if (int rc = is3d::spacetime_check_grid(P->three_d, kVahStLds, P->npT, P->K)) return rc;
+    if (int rc = is3d::spacetime_check_out(out)) return rc;
     const int64_t n = cells->n_cells;
     if (n < 0 || n > P->max_cells) return set_error(IS3D_EINVAL, "n_cells = %lld exceeds the plan's max_cells = %lld", (long long)n, (long long)P->max_cells);
+    if (n > 0x7fff0000LL) return set_error(IS3D_EINVAL, "operation 0 takes up to 2^31 cells");
     if (int rc = is3d::check_vah_cells(cells, P->three_d, P->tables)) return rc;
     const auto src = is3d::cell_arrays(*cells);
     hipStream_t st = (hipStream_t)hip_stream;
     HIP_TRY(hipSetDevice(P->device));
-    if (int rc = vah_st_setup(P)) return rc;
-    const is3d_options &o = P->o;
-    const int S = P->npart, K = P->K;
-    const int n_eta_eff = P->three_d ? 1 : K;
+    is3d::StSetup su{};
+    su.ncls = P->ncls; su.npT = P->npT; su.J = P->J; su.K = P->K; su.dim3 = P->three_d; su.jtiles = P->jtiles; su.JT = P->JT; su.npart = P->npart;
+    su.cls_mass = P->cls_mass.data(); su.cls_sign = P->cls_sign.data(); su.cls_bar = nullptr;
+    su.pT_grid = P->pT_grid.data(); su.sp_deg = P->sp_deg.data(); su.sp_cls = P->sp_cls.data();
+    su.prefactor = 1.0 / (8.0 * (M_PI * M_PI * M_PI)) / is3d::kHbarC / is3d::kHbarC / is3d::kHbarC;   // as is3d_vah_plan_execute
+    su.bytes_per_cell = (int64_t)sizeof(double) * P->jtiles * P->rblocks * P->REC;
+    su.pass_cells = P->pass_cells; su.workspace_bytes = P->o.workspace_bytes;
+    // padded lanes repeat a lane of the grid: whatever cf_prep_vah's domain test admits for the grid is in range for them too
+    su.mass_lanes = false; su.b_lanes = false; su.pad = is3d::ST_PAD_REPEAT;
+    if (int rc = is3d::spacetime_setup(P->st, su)) return rc;
+    if (int rc = is3d::spacetime_upload_weights(P->st, pT_w, phi_w, st)) return rc;
 
-    // momentum weights of the reduction: uploaded when they differ from the plan's copy (the first execute, or new weights)
-    if (P->st_hwpT.size() != (size_t)P->npT || P->st_hwphi.size() != (size_t)P->J || !std::equal(P->st_hwpT.begin(), P->st_hwpT.end(), pT_w) ||
-        !std::equal(P->st_hwphi.begin(), P->st_hwphi.end(), phi_w)) {
-        std::vector<double> wl((size_t)P->st_nlw * 64, 0.0), wp((size_t)P->jtiles * P->JT, 0.0);
-        for (size_t l = 0; l < wl.size(); l++) {
-            const int c = (int)(l / P->st_npTp), i = (int)(l % P->st_npTp);
-            if (c < P->ncls && i < P->npT) wl[l] = pT_w[i];
-        }
-        for (int j = 0; j < P->J; j++) wp[j] = phi_w[j];
-        HIP_TRY(hipMemcpyAsync(P->d_st_wpT.p, wl.data(), wl.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(P->d_st_wphi.p, wp.data(), wp.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));   // the host vectors go out of scope
-        P->st_hwpT.assign(pT_w, pT_w + P->npT);
-        P->st_hwphi.assign(phi_w, phi_w + P->J);
+    unsigned long long h[8];
+    is3d::StRun r{};
+    r.bs.tau = cells->tau; r.bs.ux = cells->ux; r.bs.uy = cells->uy; r.bs.un = cells->un;
+    r.bs.dat = cells->dat; r.bs.dax = cells->dax; r.bs.day = cells->day; r.bs.dan = cells->dan; r.bs.x = x; r.bs.y = y;
+    r.bs.n = n; r.bs.bins = bins; r.bs.out = out; r.bs.all_cells = 1;   // every cell counts (no cell is skipped here)
+    r.kweight = P->d_kw.as<double>(); r.device = P->device; r.stream = st;
+    r.d_status = P->d_status.as<unsigned long long>(); r.status = h; r.stats = stats;
+    r.pass = [&](int pass, int64_t c0, int32_t nc, int nch, const is3d::StMark &mark) { return vah_st_pass(P, src, st, pass, c0, nc, nch, mark); };
+    if (int rc = is3d::spacetime_run(P->st, r)) return rc;
+    if (!stats) return IS3D_OK;
+    stats->n_cells_skipped = 0;   // no cell is skipped on this path
+    if (n > 0 && h[7] != ~0ULL && (h[0] == ~0ULL || h[7] < h[0])) {
+        stats->bad_cell = (int64_t)h[7];
+        stats->code = IS3D_EDOMAIN;
+        return set_error(IS3D_EDOMAIN, "cell %lld: E_a/Lambda can exceed 1e9 for the momentum grid (flow, Lambda or alpha_L outside the kernel's "
+                         "exponent range; the reference's exp() overflows to inf there)", (long long)stats->bad_cell);
     }
-    std::vector<hipEvent_t> ev;
-    struct EvGuard { std::vector<hipEvent_t> &e; ~EvGuard() { for (auto v : e) (void)hipEventDestroy(v); } } evg{ev};
-    std::vector<int> stage;   // stage of the interval that ends at event i + 1: 0 coefficients + prep, 1 cells, 2 bins
-    auto mark = [&](int what) -> hipError_t {
-        if (!stats) return hipSuccess;
-        hipEvent_t e;
-        const hipError_t r = hipEventCreate(&e);
-        if (r != hipSuccess) return r;
-        if (!ev.empty()) stage.push_back(what);
-        ev.push_back(e);
-        return hipEventRecord(e, st);
-    };
-    const unsigned long long init[8] = {~0ULL, 0, 0, 0, 0, 0, 0, ~0ULL};
-    unsigned long long *d_st = P->d_status.as<unsigned long long>();
-    HIP_TRY(hipMemcpyAsync(d_st, init, sizeof init, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(P->d_st_counters.p, 0, 4 * sizeof(unsigned long long), st));
-    HIP_TRY(mark(0));
-
-    // ---- bin stage (cf_spacetime.h), part 1: keys and the stable sort of every histogram; every cell counts (no cell is skipped here) ----
-    is3d::StBinStage bs{};
-    bs.tau = cells->tau; bs.ux = cells->ux; bs.uy = cells->uy; bs.un = cells->un;
-    bs.dat = cells->dat; bs.dax = cells->dax; bs.day = cells->day; bs.dan = cells->dan; bs.x = x; bs.y = y;
-    bs.n = n; bs.cls = P->d_st_cls.p; bs.pg = P->d_st_pg.p; bs.S = S; bs.all_cells = 1;
-    bs.bins = bins; bs.out = out; bs.counters = P->d_st_counters.p;
-    if (int rc = is3d::spacetime_bins_begin(P->st_bins, bs, st)) return rc;
-    HIP_TRY(mark(2));
-
-    int npasses = 0;
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(out->dN_dy, 0, sizeof(double) * S, st));
-        for (int h = 0; h < 3; h++) HIP_TRY(hipMemsetAsync(bs.hout[h], 0, sizeof(double) * S * bs.Bs[h], st));
-        HIP_TRY(hipMemsetAsync(out->dN_dydeta, 0, sizeof(double) * S * n_eta_eff, st));
-    } else {
-        const int64_t pc = P->st_pass;
-        const int G = (P->st_nlw + 3) / 4;
-        int nch = (int)std::min<int64_t>(pc, std::max<int64_t>(1, 16384 / G));
-        if (!P->three_d) nch = (int)std::max<int64_t>(1, std::min<int64_t>(nch, ((int64_t)256 << 20) / (8 * (int64_t)P->ncls * K)));
-        if (!P->three_d && P->d_st_slab.n < (size_t)nch * P->ncls * K) HIP_TRY(P->d_st_slab.alloc((size_t)nch * P->ncls * K));
-        npasses = (int)((n + pc - 1) / pc);
-        for (int pass = 0; pass < npasses; pass++) {
-            const int64_t c0 = (int64_t)pass * pc;
-            const int32_t nc = (int32_t)std::min<int64_t>(pc, n - c0);
-            if (int rc = vah_records(P, src, c0, nc, st)) return rc;
-            HIP_TRY(mark(0));
-            is3d::StVahCellArgs a{};
-            a.TS = P->d_TS.as<double>(); a.nc = nc; a.J = P->J; a.K = K; a.jtiles = P->jtiles; a.rblocks = P->rblocks;
-            a.ncls = P->ncls; a.npTp = P->st_npTp; a.nlw = P->st_nlw; a.G = G; a.nch = (int)std::min<int64_t>(nch, nc);
-            a.zskip = o.zero_skip != 2;
-            a.lane_mT = P->d_st_mT.p; a.lane_pT = P->d_st_pT.p; a.lane_sign = P->d_st_sign.p; a.lane_wpT = P->d_st_wpT.p;
-            a.wphi = P->d_st_wphi.p;
-            a.D = P->d_st_D.p; a.eta_slab = P->three_d ? nullptr : P->d_st_slab.p;
-            HIP_TRY(is3d::launch_spacetime_vah_cells(a, P->three_d, o.regulate_deltaf != 0, P->JT, P->R, st));
-            if (!P->three_d) HIP_TRY(is3d::launch_spacetime_eta_reduce(P->d_st_slab.p, a.nch, (int64_t)P->ncls * K, pass == 0, P->d_st_eta.p, st));
-            HIP_TRY(mark(1));
-            if (int rc = is3d::spacetime_bins_add(bs, P->d_st_D.p, nc, c0, pass == 0, st)) return rc;
-            HIP_TRY(mark(2));
-        }
-        // dN/dy deta: 3+1D the single point of the species' total; 2+1D per eta node, the node's term over its effective weight w_k deta
-        if (P->three_d) HIP_TRY(hipMemcpyAsync(out->dN_dydeta, out->dN_dy, sizeof(double) * S, hipMemcpyDeviceToDevice, st));
-        else HIP_TRY(is3d::launch_spacetime_eta_final(P->d_st_eta.p, P->d_st_cls.p, P->d_st_pg.p, P->d_kw.as<double>(), S, K, out->dN_dydeta, st));
-        HIP_TRY(mark(2));
-    }
-    if (stats) {
-        unsigned long long h[8], cn[4];
-        HIP_TRY(hipMemcpyAsync(h, d_st, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(cn, P->d_st_counters.p, sizeof cn, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (size_t i = 1; i < ev.size(); i++) {
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ev[i - 1], ev[i]));
-            (stage[i - 1] == 0 ? stats->ms_prep : stage[i - 1] == 1 ? stats->ms_cells : stats->ms_bins) += ms;
-        }
-        stats->n_classes = P->ncls;
-        stats->n_passes = npasses;
-        stats->n_cells_skipped = 0;   // no cell is skipped on this path
-        stats->n_tau_outside = (int64_t)cn[0];
-        stats->n_r_outside = (int64_t)cn[1];
-        stats->n_tau_negative = (int64_t)cn[2];
-        stats->n_r_negative = (int64_t)cn[3];
-        if (n > 0 && h[7] != ~0ULL && (h[0] == ~0ULL || h[7] < h[0])) {
-            stats->bad_cell = (int64_t)h[7];
-            stats->code = IS3D_EDOMAIN;
-            return set_error(IS3D_EDOMAIN, "cell %lld: E_a/Lambda can exceed 1e9 for the momentum grid (flow, Lambda or alpha_L outside the kernel's "
-                             "exponent range; the reference's exp() overflows to inf there)", (long long)stats->bad_cell);
-        }
-        if (n > 0 && h[0] != ~0ULL) {
-            stats->bad_cell = (int64_t)h[0];
-            stats->code = IS3D_EDOMAIN;
-            return set_error(IS3D_EDOMAIN, "cell %lld: (Lambda, alpha_L) beyond the last node of the VAH coefficient tables (the reference leaves the "
-                             "cell's c0..c4 unset there, src/cuda/deltafReader.cu:237-276)", (long long)stats->bad_cell);
-        }
+    if (n > 0 && h[0] != ~0ULL) {
+        stats->bad_cell = (int64_t)h[0];
+        stats->code = IS3D_EDOMAIN;
+        return set_error(IS3D_EDOMAIN, "cell %lld: (Lambda, alpha_L) beyond the last node of the VAH coefficient tables (the reference leaves the "
+                         "cell's c0..c4 unset there, src/cuda/deltafReader.cu:237-276)", (long long)stats->bad_cell);
     }
     return IS3D_OK;
 }
@@ -1480,58 +1349,23 @@ extern "C" int is3d_spacetime_distributions_vah(const is3d_vah_cells *cells, con
     // every argument check before a device is used or a plan created
     const auto refuse = [stats](int rc) { if (stats) stats->code = rc; return rc; };
     if (!cells || !sp || !gr || !o || !out || !pT_w || !phi_w) return refuse(set_error(IS3D_EINVAL, "null argument"));
-    if (int rc = vah_st_check_bins(bins, x, y)) return refuse(rc);
+    if (int rc = is3d::spacetime_check_bins(bins, x, y)) return refuse(rc);
     if (o->dimension != 2 && o->dimension != 3) return refuse(set_error(IS3D_EINVAL, "dimension must be 2 or 3 (got %d)", o->dimension));
     if (o->kernel_variant != 0 && o->kernel_variant != 3)
         return refuse(set_error(IS3D_EINVAL, "operation 0 for anisotropic hydro runs on the default records: kernel_variant 0 or 3 (got %d)", o->kernel_variant));
     if (gr->n_pT < 1 || gr->n_phi < 1 || !gr->pT || !gr->phi) return refuse(set_error(IS3D_EINVAL, "empty pT/phi grid"));
-    if (int rc = vah_st_check_grid(o->dimension == 3, gr->n_pT, gr->n_eta)) return refuse(rc);
-    if (!out->dN_dy || !out->dN_taudtaudy || !out->dN_twopirdrdy || !out->dN_twopitaurdtaudrdy || !out->dN_dydeta)
-        return refuse(set_error(IS3D_EINVAL, "a required output array is NULL"));
+    if (int rc = is3d::spacetime_check_grid(o->dimension == 3, kVahStLds, gr->n_pT, gr->n_eta)) return refuse(rc);
+    if (int rc = is3d::spacetime_check_out(out)) return refuse(rc);
     const int64_t n = cells->n_cells;
     if (n < 0 || n > 0x7fff0000LL) return refuse(set_error(IS3D_EINVAL, "n_cells out of range"));
     if (int rc = is3d::check_vah_cells(cells, o->dimension != 2, tab != nullptr)) return refuse(rc);
     is3d_vah_plan *P = nullptr;
     if (int rc = is3d_vah_plan_create(&P, sp, gr, tab, o, std::max<int64_t>(n, 1))) return refuse(rc);
     struct Guard { is3d_vah_plan *p; ~Guard() { is3d_vah_plan_destroy(p); } } guard{P};
-    const int S = P->npart, n_eta_eff = P->three_d ? 1 : P->K;
-    const int64_t tb = bins->tau_bins, rbn = bins->r_bins;
-    const size_t sizes[6] = {(size_t)S, (size_t)(S * tb), (size_t)(S * rbn), (size_t)(S * tb * rbn), (size_t)S * n_eta_eff,
-                             out->dN_dy_cell ? (size_t)S * n : 0};
-    double *host_out[6] = {out->dN_dy, out->dN_taudtaudy, out->dN_twopirdrdy, out->dN_twopitaurdtaudrdy, out->dN_dydeta, out->dN_dy_cell};
-    size_t total = 0;
-    for (size_t s : sizes) total += s;
-    is3d::DevBuf<double> dcell, dout;
-    HIP_TRY(dcell.alloc((size_t)std::max<int64_t>(n, 1) * (is3d::kVahCellArrays + 2)));   // the cell arrays, then x and y
-    HIP_TRY(dout.alloc(total));
-    hipEvent_t e[4];
-    for (auto &v : e) HIP_TRY(hipEventCreate(&v));
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; i++) (void)hipEventDestroy(e[i]); } } evg{e};
-    HIP_TRY(hipEventRecord(e[0], nullptr));
-    is3d_vah_cells dc;   // T is not read; c0..c4 come from the tables when they are given
-    HIP_TRY(is3d::stage_cells(*cells, [tab](int a) { return a != 9 && !(a >= 25 && tab); }, 0, n, dcell.p, nullptr, &dc));
-    std::array<const double *, 2> xy = {x, y};
-    HIP_TRY(is3d::stage_arrays(xy, 0, n, dcell.p + (size_t)is3d::kVahCellArrays * n, nullptr));
-    HIP_TRY(hipEventRecord(e[1], nullptr));
-    const double *dx = n > 0 ? xy[0] : dcell.p, *dy = n > 0 ? xy[1] : dcell.p;
-    double *dev_out[6];
-    size_t off = 0;
-    for (int i = 0; i < 6; i++) { dev_out[i] = sizes[i] ? dout.p + off : nullptr; off += sizes[i]; }
-    const is3d_spacetime_out dev{dev_out[0], dev_out[1], dev_out[2], dev_out[3], dev_out[4], dev_out[5]};
-    is3d_spacetime_stats stt{};
-    const int rc = is3d_vah_plan_execute_spacetime(P, &dc, dx, dy, pT_w, phi_w, bins, &dev, nullptr, &stt);
-    if (rc) { if (stats) *stats = stt; return rc; }
-    HIP_TRY(hipEventRecord(e[2], nullptr));
-    for (int i = 0; i < 6; i++)
-        if (sizes[i]) HIP_TRY(hipMemcpyAsync(host_out[i], dev_out[i], sizes[i] * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipEventRecord(e[3], nullptr));
-    HIP_TRY(hipEventSynchronize(e[3]));
-    float h2d = 0, d2h = 0;
-    HIP_TRY(hipEventElapsedTime(&h2d, e[0], e[1]));
-    HIP_TRY(hipEventElapsedTime(&d2h, e[2], e[3]));
-    stt.ms_h2d = h2d;
-    stt.ms_d2h = d2h;
-    stt.code = IS3D_OK;
-    if (stats) *stats = stt;
-    return IS3D_OK;
+    // T is not read; c0..c4 come from the tables when they are given
+    return is3d::spacetime_oneshot(*cells, x, y, [tab](int a) { return a != 9 && !(a >= 25 && tab); }, P->npart, P->three_d ? 1 : P->K, bins, out,
+                                   stats, [&](const is3d_vah_cells &dc, const double *dx, const double *dy, const is3d_spacetime_out &dev,
+                                              is3d_spacetime_stats *stt) {
+                                       return is3d_vah_plan_execute_spacetime(P, &dc, dx, dy, pT_w, phi_w, bins, &dev, nullptr, stt);
+                                   });
 }

@@ -34,7 +34,7 @@ def plain(grid):
     return {k: grid[k] for k in ("pT", "phi", "y", "eta", "eta_w")}
 
 
-# ---- what the kernels derive from a shape (cf_plan.cpp: st_setup, st_check_grid, the plan's tile choice; cf_polzn.hip) ----
+# ---- what the kernels derive from a shape (cf_spacetime_host.cpp: spacetime_setup, spacetime_check_grid; the plan's tile choice; cf_polzn.hip) ----
 def npTp_of(npT):
     p = 1
     while p < npT:
@@ -60,7 +60,7 @@ def op0_tile(dim, npT, baryon, feqmod):
 
 
 def op0_lds_max_eta(npT, feqmod):
-    """the largest 2+1D eta count of st_check_grid: 4 waves x (64 / npTp) classes x K doubles within 64 KiB (feqmod: 48 KiB)"""
+    """the largest 2+1D eta count of spacetime_check_grid: 4 waves x (64 / npTp) classes x K doubles within 64 KiB (feqmod: 48 KiB)"""
     return ((48 if feqmod else 64) * 1024) // (8 * 4 * (64 // npTp_of(npT)))
 
 
@@ -125,7 +125,7 @@ OP0_FQ = [
     Op0("2d-npT2-phi3-eta%d-lds-max" % op0_lds_max_eta(2, True), 2, (2, 3, op0_lds_max_eta(2, True)), 3, THREE, 2, {}, True),
 ]
 
-# refused by st_check_grid before a plan exists: (name, dim, shape, df_mode)
+# refused by spacetime_check_grid before a plan exists: (name, dim, shape, df_mode)
 OP0_REFUSED = [
     ("2d-npT1-eta%d-df" % (op0_lds_max_eta(1, False) + 1), 2, (1, 3, op0_lds_max_eta(1, False) + 1), 1),
     ("2d-npT2-eta%d-df" % (op0_lds_max_eta(2, False) + 1), 2, (2, 3, op0_lds_max_eta(2, False) + 1), 2),
@@ -181,12 +181,12 @@ def op0_derived(case):
     return dict(npTp=npTp_of(npT), nlw=nlw_of(n_classes(inputs.species(case.species), baryon), npT), phi=(nphi % jt, jt), rows=(nk % r, r))
 
 
-# ---- operation 0 for anisotropic hydro (cf_spacetime_vah.hip; host side in cf_vah.hip: vah_st_check_grid, vah_st_setup, the chunk rule) ----
+# ---- operation 0 for anisotropic hydro (cf_spacetime_vah.hip; host side: cf_vah.hip on cf_spacetime_host.cpp's grid check, setup and chunk rule) ----
 VAH_TILE = {3: (8, 7), 2: (8, 31)}   # (phi tile, row block) of the "F" unit records the per-cell kernel reads
 
 
 def vah_lds_max_eta(npT):
-    """the largest 2+1D eta count of vah_st_check_grid: 4 waves x (64 / npTp) classes x K doubles within 64 KiB"""
+    """the largest 2+1D eta count of spacetime_check_grid for this path: 4 waves x (64 / npTp) classes x K doubles within 64 KiB"""
     return (64 * 1024) // (8 * 4 * (64 // npTp_of(npT)))
 
 
@@ -197,7 +197,7 @@ def vah_record_doubles(dim):
 
 
 def vah_pass_cells(ncls, nphi, nk, n, dim, workspace_bytes):
-    """cells per pass of vah_st_setup: the plan's record stream plus D (8 bytes per class and cell) within opts.workspace_bytes; without that
+    """cells per pass of spacetime_setup: the plan's record stream plus D (8 bytes per class and cell) within opts.workspace_bytes; without that
     option the cap is 16 GiB or more, which every surface here fits into"""
     if not workspace_bytes:
         return n
@@ -263,7 +263,7 @@ OP0_VAH_MANY = [
     _vah("2d-npT33-phi1-eta33-75classes-1000cells", 2, (33, 1, 33), "classes", VAH_MANY),
 ]
 
-# refused by vah_st_check_grid before a plan exists (the one-shot entry) or before anything is allocated (the plan entry): (name, dim, shape)
+# refused by spacetime_check_grid before a plan exists (the one-shot entry) or before anything is allocated (the plan entry): (name, dim, shape)
 OP0_VAH_REFUSED = [
     ("2d-npT1-eta%d" % (vah_lds_max_eta(1) + 1), 2, (1, 3, vah_lds_max_eta(1) + 1)),
     ("2d-npT2-eta%d" % (vah_lds_max_eta(2) + 1), 2, (2, 3, vah_lds_max_eta(2) + 1)),

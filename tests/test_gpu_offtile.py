@@ -5,7 +5,7 @@ the checker the subsystem already has, with that checker's metric and tolerance.
 What these cases found: cf_st_cells summed the padding rows of a 3+1D y grid that is no multiple of 7 (p.dsigma of a 3+1D row does not read
 W, so a padding row added pT B_j f of the last y row: dN_dy_cell off by up to 9 % on 15 y nodes, non-zero where the oracle has 0 on a single
 one); its row loop now stops at the last y row.  The one-shot entries refused a grid past the 64-pT / LDS bounds only after creating a
-plan; they ask st_check_grid first.  Worst errors on an MI355X after the fix: operation 0 df_mode 1 / 2 3.8e-14 (held to 1e-10), df_mode
+plan; they ask the grid check first.  Worst errors on an MI355X after the fix: operation 0 df_mode 1 / 2 3.8e-14 (held to 1e-10), df_mode
 3 / 4 4.2e-14 (1e-9), mode 5 8.3e-14 (1e-10), feed-down 1.7e-13 (1e-10)."""
 import os
 from functools import lru_cache

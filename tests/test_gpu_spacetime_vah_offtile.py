@@ -1,4 +1,4 @@
-"""GPU: operation 0 for anisotropic hydro (cf_spacetime_vah.hip; vah_st_setup and is3d_vah_plan_execute_spacetime in cf_vah.hip) on the
+"""GPU: operation 0 for anisotropic hydro (cf_spacetime_vah.hip; is3d_vah_plan_execute_spacetime on cf_spacetime_host.cpp's driver) on the
 off-tile cases of tests/offtile_cases.py (OP0_VAH, OP0_VAH_MANY, OP0_VAH_REFUSED): npTp = 1 and 64, partly filled workgroups, a single y
 node or phi, full and padded row blocks, the 2+1D LDS bound and its refusal, row blocks and rows that the exact-zero culls skip, several
 passes, two cells in one chunk, and a plan executed with changed weights.  tests/test_offtile_cases.py proves on the CPU that the table
