@@ -603,6 +603,51 @@ typedef struct {
 int is3d_total_yield(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
                      const is3d_yield_inputs *avg, const is3d_options *opts, double *mean_yield, double *densities);
 
+/* The mean yield of an anisotropic-hydro surface: what sizes an oversampled run of is3d_sample_particles_vah.  The reference has nothing to
+ * match (calculate_total_yield is viscous-hydro only and works at the surface-average temperature; there is no surface average of
+ * (Lambda, alpha_L) and mode 2 writes no averages file), so THIS is the definition.
+ * *mean_yield is the mean number of hadrons the surface emits: the momentum integral of the smooth VAH integrand (is3d_smooth_spectra_vah) with
+ * the LINEAR residual delta-f (regulate_deltaf = 0) and no outflow cut, over the cells with u.dsigma > 0 -- the cells the sampler does not
+ * skip -- in the convention of calculate_total_yield: backflow included; 3+1D: the whole rapidity range; 2+1D: times 2 y_cut.
+ * f_a is an equilibrium distribution at the stretched momentum p' = (p_x, p_y, p_z / alpha_L), so in the local rest frame the integral reduces
+ * to three radial ones.  For a cell with Lambda, alpha = alpha_L and a species (m, sign, g), mbar = m / Lambda, on the alpha = 1 Gauss-Laguerre
+ * nodes (r_k, w_k) = (in->root1, in->weight1), E_k = sqrt(r_k^2 + mbar^2):
+ *     N0 = sum_k w_k r_k   e^{r_k}       / (e^{E_k} + sign)
+ *     A0 = sum_k w_k r_k   e^{r_k + E_k} / (e^{E_k} + sign)^2
+ *     A2 = sum_k w_k r_k^3 e^{r_k + E_k} / (e^{E_k} + sign)^2
+ *     K_m = [include_bulk_deltaf] Pi (c0 + c2)
+ *     K_p = ([include_bulk_deltaf] Pi (c1 alpha^2 + c2 (2 + alpha^2)) + [include_shear_deltaf] c4 (pi_XX + pi_YY + alpha^2 pi_ZZ)) / 3
+ *     N_{cell,s} = (u.dsigma) alpha g Lambda^3 / (2 pi^2 hbarc^3) (N0 + K_m m^2 A0 + K_p Lambda^2 A2)
+ * with pi_AB = A_mu B_nu pi_perp^{mu nu} on the basis (X, Y, Z) of is3d_sample_particles_vah (covariant basis components, metric
+ * (+, -, -, -tau^2)).  yield_by_species[s] = sum_cells N_{cell,s} (times 2 y_cut in 2+1D); *mean_yield = their sum in list order.
+ * Where the terms come from: the angular averages <p_z^2> = alpha^2 p'^2 / 3, <p_x^2> = <p_y^2> = p'^2 / 3, <E^2> = m^2 + p'^2 (2 + alpha^2) / 3;
+ * every term odd in a momentum component integrates to zero -- the c3 (p.z)(W.p) term (W.z = 0 by the way W^tau and W^eta are reconstructed)
+ * and the spatial flux p^i dsigma_i.  The components of pi_perp along u are NOT read: they vanish on every surface whose pi_perp is orthogonal
+ * to u (file surfaces, synthetic ones); on any other input tensor the yield differs from the smooth spectrum's integral by those terms.  For
+ * alpha_L = 1 and a traceless pi_perp the shear term vanishes; for alpha_L != 1 it does not ((alpha^2 - 1) pi_ZZ).  With a large residual bulk
+ * pressure the linear delta-f can drive a yield negative: the caller decides what that means (is3d_oversample_events takes the magnitude).
+ * Bad cells: Lambda or alpha_L not finite and > 0, or (tab != NULL) a cell beyond the last node of the tables -- IS3D_EDOMAIN naming
+ * in->first_cell + the lowest index ("cell N: ..."), the outputs holding the sum over the other cells.  u.dsigma <= 0: skipped, counted.
+ * HOST pointers.  in: n_gla (1..256), root1, weight1, y_cut (2+1D: > 0), first_cell; fast must be 0 and feqmod NULL.  opts: dimension,
+ * include_bulk_deltaf, include_shear_deltaf, device.  tab == NULL: the coefficients from the cells.  Arrays read: tau, u, dsigma, Lambda, aL;
+ * pi_perp (and c4 without tab) only with include_shear_deltaf; bulkPi (and c0..c2 without tab) only with include_bulk_deltaf; never T, eta,
+ * Wx, Wy, c3.  A NULL argument, a NULL array that would be read and the values above are IS3D_EINVAL before any device use; a good call
+ * without a device is IS3D_ENODEVICE; n_cells = 0 gives 0.  Deterministic: per-(cell tile, class) partial sums added in a fixed order (no
+ * floating-point atomics), the tiling a function of n_cells only -- the same bits from run to run and device to device.
+ * stats: device time of the upload, of the per-cell kernel (with the coefficient interpolation) and of the per-(cell, class) integrals. */
+typedef struct {
+    int64_t n_cells_skipped;            /* u.dsigma <= 0 */
+    int32_t n_classes, reserved;        /* species classes (mass, sign) the radial integrals were done for */
+    double ms_h2d, ms_cells, ms_classes;
+} is3d_yield_vah_stats;
+int is3d_total_yield_vah(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab /* NULL: c0..c4 from the cells */,
+                         const is3d_sampler_inputs *in /* n_gla, root1, weight1, y_cut, first_cell */, const is3d_options *opts,
+                         double *mean_yield, double *yield_by_species /* may be NULL */, is3d_yield_vah_stats *stats /* may be NULL */);
+/* The number of events of an oversampled run (emissionfunction.cpp:1524-1533, with at least one event):
+ * max(1, min(ceil(min_num_hadrons / |(float) mean_yield|), max_num_samples)).  min_num_hadrons not > 0 or max_num_samples < 1: IS3D_EINVAL;
+ * a yield that is 0 or not finite: IS3D_EDOMAIN. */
+int is3d_oversample_events(double min_num_hadrons, double mean_yield, int32_t max_num_samples, int32_t *n_events);
+
 /* write_particle_list_OSC (src/cpp/emissionfunction.cpp:863-901): results/particle_list_osc.dat, "# N" per non-empty event
  * then "mcid t x y z E px py pz" rows; particles ordered by event. */
 int is3d_write_particle_list_osc(const char *path, int32_t n_events, int64_t n_particles, const is3d_particle *particles,

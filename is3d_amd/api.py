@@ -121,7 +121,8 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_sampler_bin_list_device", "is3d_df_generate", "is3d_df_tables_write",
            "is3d_smooth_spectra_vah_multi", "is3d_vah_plan_observables",
            "is3d_spacetime_distributions_vah", "is3d_vah_plan_execute_spacetime",
-           "is3d_sample_particles_vah", "is3d_sample_particles_vah_multi"]
+           "is3d_sample_particles_vah", "is3d_sample_particles_vah_multi",
+           "is3d_total_yield_vah", "is3d_oversample_events"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
 POLARIZATION_OUTPUTS = ["St", "Sx", "Sy", "Sn", "Snorm"]
@@ -1743,6 +1744,59 @@ def total_yield(cells, species, df, gla, avg5, opts=None, y_cut=0.5, fq=None):
                                    C.POINTER(Options), C.POINTER(C.c_double), _dp]
     _check(L.is3d_total_yield(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(yi), C.byref(os_), C.byref(out), _p(dens)))
     return out.value, dens
+
+
+class YieldVahStats(C.Structure):
+    _fields_ = [("n_cells_skipped", C.c_int64), ("n_classes", C.c_int32), ("reserved", C.c_int32), ("ms_h2d", C.c_double), ("ms_cells", C.c_double),
+                ("ms_classes", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def total_yield_vah(cells, species, gla, opts=None, tab=None, y_cut=0.5, first_cell=0, fast=0, fq=None):
+    """is3d_total_yield_vah: the mean number of hadrons an anisotropic-hydro surface emits (linear delta-f, no outflow cut, the cells with
+    u.dsigma > 0), which sizes an oversampled run of sample_particles_vah.  cells: dict of host arrays per VAH_FIELDS; gla: dict with root1,
+    weight1; tab (dict L, aL, c0..c4): the coefficients come from the (Lambda, alpha_L) tables and the cells' c0..c4 are ignored.  Returns
+    (mean_yield, yield_by_species, stats dict).  A bad cell raises Is3dError(IS3D_EDOMAIN) with .bad_cell (the lowest global index),
+    .mean_yield, .yield_by_species and .stats: the sums over the other cells.  fast, fq: passed on only so that the entry's refusals can be
+    reached."""
+    L = load()
+    sps, _, _, os_, _, keep = _pack_common(species, dict(pT=[1.0], phi=[0.0], y=[0.0], eta=[0.0], eta_w=[1.0]), _VAH_DUMMY_DF, opts)
+    held = [keep]
+    if tab is not None:
+        cells = {k: v for k, v in cells.items() if k not in ("c0", "c1", "c2", "c3", "c4")}
+    cs = _vah_cells_struct(cells, held)
+    ts = _pack_vah_tables(tab, keep) if tab is not None else None
+    r1, w1 = _f64(gla["root1"]), _f64(gla["weight1"])
+    fqs = _pack_feqmod(fq, keep) if fq is not None else None
+    si = SamplerInputs(1, len(r1), 0, float(y_cut), int(first_cell), None, None, _p(r1), _p(w1), C.pointer(fqs) if fqs is not None else None,
+                       int(fast), 0, 0.0, 0.0, 0.0)
+    st = YieldVahStats()
+    out = C.c_double(0.0)
+    by = np.zeros(sps.n)
+    L.is3d_total_yield_vah.argtypes = [C.POINTER(VahCells), C.POINTER(Species), C.POINTER(VahDfTables), C.POINTER(SamplerInputs), C.POINTER(Options),
+                                       C.POINTER(C.c_double), _dp, C.POINTER(YieldVahStats)]
+    rc = L.is3d_total_yield_vah(C.byref(cs), C.byref(sps), C.byref(ts) if ts is not None else None, C.byref(si), C.byref(os_), C.byref(out), _p(by),
+                                C.byref(st))
+    if rc == IS3D_EDOMAIN:
+        msg = L.is3d_last_error().decode()
+        m = re.search(r"cell (\d+):", msg)
+        e = Is3dError(rc, msg, bad_cell=int(m.group(1)) if m else None)
+        e.mean_yield, e.yield_by_species, e.stats = out.value, by, st.as_dict()
+        raise e
+    _check(rc)
+    return out.value, by, st.as_dict()
+
+
+def oversample_events(min_num_hadrons, mean_yield, max_num_samples):
+    """is3d_oversample_events: max(1, min(ceil(min_num_hadrons / |(float) mean_yield|), max_num_samples)), the number of events of an
+    oversampled run (emissionfunction.cpp:1524-1533)."""
+    L = load()
+    L.is3d_oversample_events.argtypes = [C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_int32)]
+    n = C.c_int32(0)
+    _check(L.is3d_oversample_events(float(min_num_hadrons), float(mean_yield), int(max_num_samples), C.byref(n)))
+    return int(n.value)
 
 
 def write_particle_list_osc(path, n_events, particles, mc_id):

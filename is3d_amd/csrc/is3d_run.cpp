@@ -37,6 +37,11 @@
 // batch on the device (is3d_sample_binned_multi), never held as a list; the same files are written from the integer histograms
 // (is3d_write_sampler_tests_binned; vn/ to the fixed point) and the same lines printed, plus ms_bin.  test_sampler = 0, other operations and
 // the embedding entry (which returns the list) refuse the key.
+// vah_oversample = 1 (optional key, default 0): with mode = 2, operation = 2, df_mode = 4 and vah_sampler = 1 the anisotropic-hydro mean yield
+// (is3d_total_yield_vah: first device of the run's list, the file's y_cut, the deltaf_coefficients/vah tables, the sampler's Gauss-Laguerre file)
+// is printed as the viscous path prints its own and sizes the run, Nevents = is3d_oversample_events(min_num_hadrons, yield, max_num_samples); a
+// yield <= 0 (the linear delta-f of a large residual bulk pressure) stops the run before anything is written.  Every other combination refuses
+// the key; oversample = 1 stays refused with mode = 2.
 // mode = 5: every run, whatever its operation, ends with the spin polarization from the surface's thermal vorticity (calculate_spin_polzn,
 // emissionfunction.cpp:1675) and appends results/St.dat, Sx.dat, Sy.dat, Sn.dat (write_polzn_vector_toFile, :1701), with T from the averages
 // file just written or T_switch when set_FO_temperature = 1; the embedding entry has no vorticity and says so.  With a device list that was
@@ -240,6 +245,19 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         }
     }
     const bool vah = !mem && mode == 2;
+    // optional key vah_oversample = 1: the anisotropic-hydro mean yield (is3d_total_yield_vah) sizes the run of this library's own VAH sampler
+    bool vah_oversample = false;
+    {
+        double key = 0.0, sampler = 0.0;
+        if (get_param("vah_oversample", &key, false) == IS3D_OK && (int)key) {
+            const bool own_sampler = get_param("vah_sampler", &sampler, false) == IS3D_OK && (int)sampler;
+            if (!(vah && operation == 2 && df_mode == 4 && own_sampler))
+                DIE("vah_oversample = 1 with mode = %d, operation = %d, df_mode = %d, vah_sampler = %d: the anisotropic-hydro mean yield sizes this library's own "
+                    "anisotropic-hydro sampler only (mode = 2, operation = 2, df_mode = 4, vah_sampler = 1); set vah_oversample = 0", mode, operation, df_mode,
+                    (int)own_sampler);
+            vah_oversample = true;
+        }
+    }
     if (vah) {
         if (operation == 2) {
             // optional key vah_sampler = 1: this library's own VAH sampler (is3d_sample_particles_vah; the reference has none)
@@ -252,7 +270,7 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
             if (get_param("oversample", &oversample)) return IS3D_EINVAL;
             if ((int)oversample)
                 DIE("oversample = 1 with mode = 2: the mean yield that sizes an oversampled run (calculate_total_yield) is viscous-hydro only; set oversample = 0 "
-                    "(max_num_samples events are sampled)");
+                    "(max_num_samples events are sampled), and vah_oversample = 1 for the anisotropic-hydro mean yield (is3d_total_yield_vah) to size the run");
         }
         if (df_mode != 4) DIE("mode = 2 (anisotropic hydro) needs df_mode = 4: the per-cell 14-moment coefficients c0..c4 exist for that combination only (emissionfunction.cpp:1410-1418)");
     }
@@ -562,7 +580,21 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
             // Nevents = min((int)ceil(MIN_NUM_HADRONS / Ntotal), MAX_NUM_SAMPLES); at least one event is sampled here
             si.n_events = (int32_t)std::max(1.0, std::min(std::ceil(min_num_hadrons / Ntotal), (double)(int)max_num_samples));
         }
-        if (vah) si.n_events = (int32_t)std::max(1.0, (double)(int)max_num_samples);   // no mean yield to size the run: MAX_NUM_SAMPLES events
+        if (vah) si.n_events = (int32_t)std::max(1.0, (double)(int)max_num_samples);   // without vah_oversample no mean yield sizes the run: MAX_NUM_SAMPLES events
+        if (vah_oversample) {
+            // the anisotropic-hydro mean yield on the first device of the run's list (opts.device), with the sampler's tables, nodes and y_cut
+            double Ntotal = 0.0;
+            printf("Total particle yield: ");
+            const int rc1 = is3d_total_yield_vah(&vc, &sp, &vt, &si, &opts, &Ntotal, nullptr, nullptr);
+            if (rc1) DIE("is3d_total_yield_vah failed (%d): %s", rc1, is3d_last_error());
+            if (dimension == 2) printf("dN_dy ~ %lf\n\n", Ntotal / (2.0 * y_cut));
+            printf("%lf\n", Ntotal);
+            if (!(Ntotal > 0.0))
+                DIE("vah_oversample = 1: the linear delta-f has driven the mean yield of the surface non-positive (%g), which sizes no run (the residual bulk "
+                    "pressure is outside the range of the linear correction); set vah_oversample = 0 (max_num_samples events are sampled)", Ntotal);
+            mean_yield = Ntotal;
+            if (is3d_oversample_events(min_num_hadrons, Ntotal, (int32_t)max_num_samples, &si.n_events)) DIE("%s", is3d_last_error());
+        }
         printf("Sampling %d event(s)\n", si.n_events);
         if (df_mode == 1) printf("Sampling particles with Grad 14 moment df...\n");                    // emissionfunction.cpp:1540-1541, :1602-1603
         if (df_mode == 2) printf("Sampling particles with Chapman Enskog df...\n");
