@@ -519,7 +519,8 @@ typedef struct {
     double ms_h2d, ms_prep, ms_count, ms_fill;   /* device time: upload, densities + cell records, count pass + scan, fill pass */
     double ms_density;                  /* part of ms_prep: cf_sampler_density (the Gauss-Laguerre density integrals per (cell, class)) */
     double ms_poisson;                  /* part of ms_count: cf_sampler_poisson + the compaction of the emitting (event, cell) pairs */
-    double ms_bin;                      /* is3d_sampler_plan_execute_binned: cf_sampler_bins over all batches (0 for the list entries) */
+    double ms_bin;                      /* is3d_sampler_plan_execute_binned: cf_sampler_bins over all batches (0 for the list entries);
+                                           is3d_sample_binned_vah: the fused sample-and-bin passes (ms_count = ms_fill = 0 there) */
     int64_t particle_workspace_bytes;   /* is3d_sampler_plan_execute_binned: the plan-owned particle workspace (one batch); 0 otherwise */
 } is3d_sampler_stats;
 
@@ -718,6 +719,39 @@ int is3d_sample_binned(const is3d_cells *cells, const is3d_species *species, con
 int is3d_sample_binned_multi(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
                              const is3d_options *opts, const int32_t *devices, int32_t n_devices, const is3d_sampler_test_bins *bins,
                              const is3d_sampler_hist *hist, int64_t *n_particles, is3d_sampler_stats *stats);
+/* The anisotropic-hydro sampler with its hadrons binned where they are sampled (cf_sampler_vah_bin), in one pass and without a list.  As for
+ * is3d_sample_particles_vah the reference has nothing to match, so THIS is the definition:
+ *   the histograms are those of is3d_sampler_bin_list on the list that is3d_sample_particles_vah returns for the same arguments -- counts
+ *   and yields exactly; vn_re, vn_im within one unit per entry of the dN_pT bin (device and host libm; against is3d_sampler_bin_list_device
+ *   of that list, which runs the same device arithmetic, they are expected to be identical).  *n_particles = the sum of the yields = the
+ *   length of that list.
+ * How: per event batch the Poisson numbers and the compaction of the emitting (event, cell) pairs as in the list route, then ONE pass, thread
+ * <-> pair, that replays the list route's streams and loop and gives every kept hadron's is3d_particle (built in registers) to the rule of
+ * csrc/cf_sampler_bins.h; the adds are the 64-bit integer adds of cf_sampler_bins, so the result depends neither on the order of arrival
+ * nor on bins->kernel_form (0 = workgroup-private histograms in LDS where they fit 64 KiB, 1 = global atomics, 2 = private or IS3D_EINVAL),
+ * in->batch_events, in->first_cell sharding or the device count, bit for bit.
+ * Device memory: the histograms (8 B per word of is3d_sampler_hist), the per-cell records of is3d_sample_particles_vah and 9 B per
+ * (event, cell) pair of ONE batch (Poisson number, emit flag, pair list; batches of <= 2^25 pairs, or in->batch_events events) with the
+ * compaction's temporary storage -- nothing is sized by the number of hadrons: no particle workspace, no counts, no offsets, no scan.
+ * stats: ms_bin is the time of the fused sample-and-bin passes; ms_count, ms_fill and particle_workspace_bytes are 0; ms_h2d, ms_prep,
+ * ms_density, ms_poisson, n_momentum_samples, n_acceptances, n_hadrons_drawn and n_cells_skipped are those of is3d_sample_particles_vah.
+ * HOST pointers; hist is overwritten.  Refused with IS3D_EINVAL before any device use, in this order: everything is3d_sample_particles_vah
+ * refuses, then what is3d_sample_binned refuses of bins and hist (a NULL, bad bins, kernel_form outside 0..2, kernel_form = 2 on a block
+ * that does not fit the LDS).  A good call without a device is IS3D_ENODEVICE, an empty surface included (the plan comes first, as for
+ * is3d_sample_particles_vah); with a device n_cells = 0 gives zero histograms, *n_particles = 0 and IS3D_OK without a launch.
+ * A bad cell (is3d_sample_particles_vah): IS3D_EDOMAIN naming the lowest global index, with the histograms of the other cells, *n_particles
+ * and stats returned.  A dN_pT bin above IS3D_SAMPLER_VN_MAX_COUNT: IS3D_EDOMAIN. */
+int is3d_sample_binned_vah(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab /* NULL: c0..c4 from the cells */,
+                           const is3d_sampler_inputs *in, const is3d_options *opts, const is3d_sampler_test_bins *bins,
+                           const is3d_sampler_hist *hist, int64_t *n_particles, is3d_sampler_stats *stats /* may be NULL */);
+/* is3d_sample_binned_vah over contiguous cell shards, shard s on devices[s] with first_cell advanced to the shard's first cell (the shard
+ * scaffold of is3d_sample_particles_vah_multi); the shards' integer histograms are added on the host, so the result equals the single-device
+ * one bit for bit.  The same refusals, before any device use; opts->device is ignored; a bad cell is named by its index in the whole
+ * surface (the lowest one), with the sum of all shards' histograms returned.  stats are summed (times: the slowest shard's). */
+int is3d_sample_binned_vah_multi(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab,
+                                 const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices, int32_t n_devices,
+                                 const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
+                                 is3d_sampler_stats *stats);
 
 /* ---------------------------------------------------------------------------------------------
  * Operation 0: smooth Cooper-Frye spacetime distributions, df_mode 1 / 2 -- the drop-in for calculate_dN_dX

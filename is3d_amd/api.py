@@ -121,7 +121,7 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_sampler_bin_list_device", "is3d_df_generate", "is3d_df_tables_write",
            "is3d_smooth_spectra_vah_multi", "is3d_vah_plan_observables",
            "is3d_spacetime_distributions_vah", "is3d_vah_plan_execute_spacetime",
-           "is3d_sample_particles_vah", "is3d_sample_particles_vah_multi",
+           "is3d_sample_particles_vah", "is3d_sample_particles_vah_multi", "is3d_sample_binned_vah", "is3d_sample_binned_vah_multi",
            "is3d_total_yield_vah", "is3d_oversample_events"]
 
 VORTICITY_FIELDS = ["wtx", "wty", "wtn", "wxy", "wxn", "wyn"]
@@ -1579,15 +1579,8 @@ def sample_particles(cells, species, df, gla, opts=None, n_events=1, seed=1, y_c
     return out[:min(int(cnt.value), int(capacity))], d
 
 
-def sample_particles_vah(cells, species, gla, opts=None, tab=None, n_events=1, seed=1, y_cut=0.5, first_cell=0, capacity=None, batch_events=0,
-                         devices=None, fast=0, fq=None):
-    """is3d_sample_particles_vah: the particle sampler for anisotropic hydro (mode 2, operation 2).  cells: dict of host arrays per VAH_FIELDS
-    (x, y optional); gla: dict with root1, weight1; tab (dict L, aL, c0..c4): the coefficients come from the (Lambda, alpha_L) tables and the
-    cells' c0..c4 are ignored.  devices: is3d_sample_particles_vah_multi, one cell shard per listed device (an ordinal may repeat).  Returns
-    (numpy structured array of PARTICLE_DTYPE, stats dict); capacity = None sizes the buffer from a count-only first call.  A bad cell raises
-    Is3dError(IS3D_EDOMAIN) with .bad_cell (the lowest global index), .particles and .stats: the other cells are sampled all the same.
-    fast, fq: passed on only so that the entry's refusals can be reached."""
-    L = load()
+def _pack_sampler_vah(cells, species, gla, opts, tab, n_events, seed, y_cut, first_cell, batch_events, fast, fq):
+    """The arguments the anisotropic-hydro sampler entries share: (VahCells, Species, tables pointer | None, SamplerInputs, Options, held)."""
     sps, _, _, os_, _, keep = _pack_common(species, dict(pT=[1.0], phi=[0.0], y=[0.0], eta=[0.0], eta_w=[1.0]), _VAH_DUMMY_DF, opts)
     held = [keep]
     if tab is not None:
@@ -1601,9 +1594,22 @@ def sample_particles_vah(cells, species, gla, opts=None, tab=None, n_events=1, s
     si = SamplerInputs(int(n_events), len(r1), int(seed), float(y_cut), int(first_cell), _p(xs) if xs is not None else None,
                        _p(ys) if ys is not None else None, _p(r1), _p(w1), C.pointer(fqs) if fqs is not None else None, int(fast), int(batch_events),
                        0.0, 0.0, 0.0)
+    held += [ts, r1, w1, xs, ys, fqs]
+    return cs, sps, (C.byref(ts) if ts is not None else None), si, os_, held
+
+
+def sample_particles_vah(cells, species, gla, opts=None, tab=None, n_events=1, seed=1, y_cut=0.5, first_cell=0, capacity=None, batch_events=0,
+                         devices=None, fast=0, fq=None):
+    """is3d_sample_particles_vah: the particle sampler for anisotropic hydro (mode 2, operation 2).  cells: dict of host arrays per VAH_FIELDS
+    (x, y optional); gla: dict with root1, weight1; tab (dict L, aL, c0..c4): the coefficients come from the (Lambda, alpha_L) tables and the
+    cells' c0..c4 are ignored.  devices: is3d_sample_particles_vah_multi, one cell shard per listed device (an ordinal may repeat).  Returns
+    (numpy structured array of PARTICLE_DTYPE, stats dict); capacity = None sizes the buffer from a count-only first call.  A bad cell raises
+    Is3dError(IS3D_EDOMAIN) with .bad_cell (the lowest global index), .particles and .stats: the other cells are sampled all the same.
+    fast, fq: passed on only so that the entry's refusals can be reached."""
+    L = load()
+    cs, sps, tp, si, os_, _held = _pack_sampler_vah(cells, species, gla, opts, tab, n_events, seed, y_cut, first_cell, batch_events, fast, fq)
     st = SamplerStats()
     cnt = C.c_int64(0)
-    tp = C.byref(ts) if ts is not None else None
     head = [C.POINTER(VahCells), C.POINTER(Species), C.POINTER(VahDfTables), C.POINTER(SamplerInputs), C.POINTER(Options)]
     tail = [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
     L.is3d_sample_particles_vah.argtypes = head + tail
@@ -1927,6 +1933,46 @@ def sample_binned(cells, species, df, gla, bins, opts=None, n_events=1, seed=1, 
 def sample_binned_multi(cells, species, df, gla, bins, opts=None, devices=(0,), **kw):
     """is3d_sample_binned_multi: one cell shard per entry of devices (an ordinal may repeat); the result equals sample_binned's bit for bit."""
     return sample_binned(cells, species, df, gla, bins, opts, devices=list(devices), **kw)
+
+
+def sample_binned_vah(cells, species, gla, bins, opts=None, tab=None, n_events=1, seed=1, y_cut=0.5, first_cell=0, batch_events=0, devices=None,
+                      fast=0, fq=None):
+    """is3d_sample_binned_vah (devices = None) | is3d_sample_binned_vah_multi: the anisotropic-hydro sampler with every hadron binned where it
+    is sampled, in one pass and without a list.  Arguments as sample_particles_vah; bins: dict of is3d_sampler_test_bins fields.  Returns
+    (dict of int64 histograms, stats dict): the histograms of sampler_bin_list on sample_particles_vah's list.  A bad cell raises
+    Is3dError(IS3D_EDOMAIN) with .bad_cell (the lowest global index), .hist and .stats: the other cells are binned all the same."""
+    L = load()
+    cs, sps, tp, si, os_, _held = _pack_sampler_vah(cells, species, gla, opts, tab, n_events, seed, y_cut, first_cell, batch_events, fast, fq)
+    b = _pack_bins(bins)
+    h, out = _hist_arrays(bins, n_events, sps.n)
+    st = SamplerStats()
+    cnt = C.c_int64(0)
+    head = [C.POINTER(VahCells), C.POINTER(Species), C.POINTER(VahDfTables), C.POINTER(SamplerInputs), C.POINTER(Options)]
+    tail = [C.POINTER(SamplerTestBins), C.POINTER(SamplerHist), C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
+    L.is3d_sample_binned_vah.argtypes = head + tail
+    L.is3d_sample_binned_vah_multi.argtypes = head + [C.POINTER(C.c_int32), C.c_int32] + tail
+    if devices is not None:
+        dv, nd, _ = _pack_devices(devices)
+        rc = L.is3d_sample_binned_vah_multi(C.byref(cs), C.byref(sps), tp, C.byref(si), C.byref(os_), dv, nd, C.byref(b), C.byref(h), C.byref(cnt),
+                                            C.byref(st))
+    else:
+        rc = L.is3d_sample_binned_vah(C.byref(cs), C.byref(sps), tp, C.byref(si), C.byref(os_), C.byref(b), C.byref(h), C.byref(cnt), C.byref(st))
+    d = st.as_dict()
+    d["n_particles"] = int(cnt.value)
+    if rc == IS3D_EDOMAIN:
+        msg = L.is3d_last_error().decode()
+        m = re.search(r"cell (\d+):", msg)
+        e = Is3dError(rc, msg, bad_cell=int(m.group(1)) if m else None)
+        e.hist, e.stats = out, d
+        raise e
+    _check(rc)
+    return out, d
+
+
+def sample_binned_vah_multi(cells, species, gla, bins, opts=None, devices=(0,), **kw):
+    """is3d_sample_binned_vah_multi: one cell shard per entry of devices (an ordinal may repeat); the result equals sample_binned_vah's bit
+    for bit."""
+    return sample_binned_vah(cells, species, gla, bins, opts, devices=list(devices), **kw)
 
 
 def gla_read(path):

@@ -1261,6 +1261,90 @@ extern "C" int is3d_sample_particles_vah_multi(const is3d_vah_cells *cells, cons
     return IS3D_OK;
 }
 
+// is3d_sample_binned_vah over the same shards: every shard samples and bins its own cells on its device, the integer histograms are added
+// here -- an exact sum, so the result is the single-device one bit for bit.  A bad cell leaves the other cells binned, in every shard.
+extern "C" int is3d_sample_binned_vah_multi(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab,
+                                            const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices, int32_t n_devices,
+                                            const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
+                                            is3d_sampler_stats *stats)
+{
+    if (!n_particles) return fail(IS3D_EINVAL, "null argument");
+    *n_particles = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (int rc = is3d::sampler_vah_check(cells, species, tab, in, opts)) return rc;
+    if (int rc = is3d::sampler_check_bin_args(bins, hist, in->n_events, species->n)) return rc;
+    std::vector<int> dev;
+    if (int rc = resolve_devices(devices, n_devices, dev)) return rc;
+    n_devices = (int32_t)dev.size();
+    if (n_devices == 1) {
+        is3d_options o = *opts;
+        o.device = dev[0];
+        return is3d_sample_binned_vah(cells, species, tab, in, &o, bins, hist, n_particles, stats);
+    }
+    // the arrays of is3d_sampler_hist laid end to end, as one block per shard
+    const int64_t S = species->n, E = in->n_events, P = (int64_t)IS3D_SAMPLER_VN_HARMONICS * S * bins->pT_bins;
+    const int64_t len[8] = {S * bins->y_bins, S * bins->eta_bins, S * bins->pT_bins, S * bins->tau_bins, S * bins->r_bins, P, P, E};
+    int64_t *const out[8] = {hist->dN_dy, hist->dN_deta, hist->dN_pT, hist->dN_tau, hist->dN_r, hist->vn_re, hist->vn_im, hist->yield};
+    int64_t words = 0;
+    for (int a = 0; a < 8; a++) words += len[a];
+    struct VBShard : ShardBase {
+        is3d_vah_cells c;
+        is3d_sampler_inputs si;
+        is3d_options o;
+        int64_t count = 0;
+        is3d_sampler_stats st{};
+        std::vector<int64_t> h;
+    };
+    DeviceRestore restore;
+    std::vector<VBShard> sh(n_devices);
+    const int n_active = assign_shards(sh, dev, cells->n_cells);
+    run_shards(sh, n_active ? has_cells : every_shard, [&](int i) {
+        VBShard &s = sh[i];
+        auto a = is3d::cell_arrays(*cells);
+        for (auto &f : a)
+            if (f) f += s.lo;
+        s.c = is3d::cells_from_arrays(s.hi - s.lo, a);
+        s.si = *in;
+        s.si.first_cell = in->first_cell + s.lo;
+        if (s.si.x) s.si.x += s.lo;
+        if (s.si.y) s.si.y += s.lo;
+        s.o = *opts;
+        s.o.device = s.device;
+        s.h.assign((size_t)words, 0);
+        int64_t *q = s.h.data();
+        int64_t *part[8];
+        for (int k = 0; k < 8; k++) { part[k] = q; q += len[k]; }
+        const is3d_sampler_hist hs{part[0], part[1], part[2], part[3], part[4], part[5], part[6], part[7]};
+        return is3d_sample_binned_vah(&s.c, species, tab, &s.si, &s.o, bins, &hs, &s.count, &s.st);
+    });
+    for (int a = 0; a < 8; a++) memset(out[a], 0, (size_t)len[a] * sizeof(int64_t));
+    // a bad cell is reported (the first failed shard holds the lowest global index) after the sum: the histograms are returned with the error
+    int rc0;
+    std::string text;
+    first_error(sh, &rc0, &text);
+    bool only_domain = rc0 == IS3D_EDOMAIN;
+    for (const VBShard &s : sh)
+        if (s.rc && s.rc != IS3D_EDOMAIN) only_domain = false;
+    if (rc0 && !only_domain) return fail(rc0, "%s", text.c_str());
+    if (only_domain)
+        for (VBShard &s : sh) s.rc = IS3D_OK;
+    if (int rc = sampler_totals(sh, n_particles, stats)) return rc;
+    for (const VBShard &s : sh) {
+        if (s.h.empty()) continue;   // a shard without cells made no call
+        const int64_t *q = s.h.data();
+        for (int a = 0; a < 8; a++) {
+            for (int64_t j = 0; j < len[a]; j++) out[a][j] += q[j];
+            q += len[a];
+        }
+    }
+    if (only_domain) return fail(IS3D_EDOMAIN, "%s", text.c_str());
+    for (int64_t j = 0; j < len[2]; j++)
+        if (hist->dN_pT[j] > IS3D_SAMPLER_VN_MAX_COUNT)
+            return fail(IS3D_EDOMAIN, "dN_pT bin %lld holds %lld hadrons: the fixed-point harmonic sums are exact up to %lld per bin", (long long)j,
+                        (long long)hist->dN_pT[j], (long long)IS3D_SAMPLER_VN_MAX_COUNT);
+    return IS3D_OK;
+}
+
 // is3d_sample_binned over the same shards: every shard bins its own hadrons on its device, the integer histograms are added here --
 // an exact sum, so the result is the single-device one bit for bit
 extern "C" int is3d_sample_binned_multi(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df,

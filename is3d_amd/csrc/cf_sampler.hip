@@ -393,6 +393,8 @@ struct is3d_sampler_plan {
     DevMem d_drawn, d_emits, d_active, d_nactive, d_cdf;
     DevMem d_particles, d_hist;             // is3d_sampler_plan_execute_binned: one batch of particles; the histograms, then the yields
     int64_t cap_cells = 0, cap_bt = 0;      // what the workspaces above were sized for
+    int64_t cap_list = 0;                   // ... d_counts and d_offsets, which a fused binned run (SamplerVariant::bin) never has
+    size_t tmp_select = 0, tmp_scan = 0;
     int64_t cap_particles = 0, cap_hist = 0;
     size_t tmp_bytes = 0;
     hipEvent_t ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -659,11 +661,7 @@ bool cell_array_needed(int a, const is3d_options *o)
     return a < 12 ? (a != 1 || three_d) : (a < 17 ? o->include_shear_deltaf != 0 : (a == 17 ? o->include_bulk_deltaf != 0 : baryondiff));
 }
 // what is3d_sampler_plan_execute_binned adds to the batch loop
-struct BinRun {
-    is3d_sampler_test_bins bins;
-    is3d::SamplerBinWidths widths;
-    is3d::SamplerHistLayout layout;
-};
+using BinRun = is3d::SamplerBinRun;
 int sampler_execute(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev, int32_t n_events, uint64_t seed,
                     int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
                     int64_t *n_particles, is3d_sampler_stats *stats);
@@ -691,7 +689,7 @@ extern "C" int is3d_sampler_plan_execute(is3d_sampler_plan *P, const is3d_cells 
 
 namespace {
 // the one batch loop: bin == NULL fills the caller's list (or only counts); bin != NULL fills each batch into the plan's particle workspace
-// at base 0, bins it into P->d_hist and drops it
+// at base 0, bins it into P->d_hist and drops it -- or, for a variant with a bin hook, samples each batch straight into P->d_hist
 int sampler_execute(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev, int32_t n_events, uint64_t seed,
                     int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
                     int64_t *n_particles, is3d_sampler_stats *stats)
@@ -747,20 +745,26 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t
         if (P->o.df_mode != 3) HIP_TRY(P->d_cdf.alloc((size_t)n * ((sp.npart + is3d::kCdfBlock - 1) / is3d::kCdfBlock) * sizeof(double)));
         P->cap_cells = n;
     }
+    // fused: one pass per batch samples and bins; the counts, the offsets and the scan exist only to put a list in order
+    const bool fused = v && v->bin && bin;
     if (bt > P->cap_bt) {
         HIP_TRY(P->d_drawn.alloc((size_t)bt * sizeof(int32_t)));
         HIP_TRY(P->d_emits.alloc((size_t)bt));
         HIP_TRY(P->d_active.alloc((size_t)bt * sizeof(int32_t)));
         HIP_TRY(P->d_nactive.alloc(sizeof(int32_t)));
+        HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, P->tmp_select, hipcub::CountingInputIterator<int32_t>(0), P->d_emits.as<uint8_t>(),
+                                              P->d_active.as<int32_t>(), P->d_nactive.as<int32_t>(), (int)bt, nullptr));
+        P->cap_bt = bt;
+    }
+    if (!fused && bt > P->cap_list) {
         HIP_TRY(P->d_counts.alloc((size_t)(bt + 1) * sizeof(int64_t)));
         HIP_TRY(P->d_offsets.alloc((size_t)(bt + 1) * sizeof(int64_t)));
-        size_t tb = 0, tmp2 = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, P->d_counts.as<int64_t>(), P->d_offsets.as<int64_t>(), (int)(bt + 1), nullptr));
-        HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tmp2, hipcub::CountingInputIterator<int32_t>(0), P->d_emits.as<uint8_t>(), P->d_active.as<int32_t>(),
-                                              P->d_nactive.as<int32_t>(), (int)bt, nullptr));
-        P->tmp_bytes = std::max(tb, tmp2);
-        HIP_TRY(P->d_scan_tmp.alloc(P->tmp_bytes));
-        P->cap_bt = bt;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, P->tmp_scan, P->d_counts.as<int64_t>(), P->d_offsets.as<int64_t>(), (int)(bt + 1), nullptr));
+        P->cap_list = bt;
+    }
+    if (const size_t need = std::max(P->tmp_select, fused ? (size_t)0 : P->tmp_scan); need > P->tmp_bytes) {
+        HIP_TRY(P->d_scan_tmp.alloc(need));
+        P->tmp_bytes = need;
     }
     p.cdf = P->d_cdf.as<double>();
     DevMem &d_GT = P->d_GT, &d_GT2 = P->d_GT2, &d_GT3 = P->d_GT3, &d_rec = P->d_rec, &d_counts = P->d_counts, &d_offsets = P->d_offsets, &d_scan_tmp = P->d_scan_tmp;
@@ -798,7 +802,17 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t
         int32_t n_active = 0;
         HIP_TRY(hipMemcpy(&n_active, d_nactive.p, sizeof(int32_t), hipMemcpyDeviceToHost));
         int64_t batch_total = 0;
-        if (n_active > 0) {
+        if (fused) {
+            HIP_TRY(hipEventRecord(ev[3], nullptr));
+            HIP_TRY(hipEventRecord(ev[8], nullptr));
+            if (n_active > 0) {
+                unsigned long long *hist_dev = P->d_hist.as<unsigned long long>();
+                v->bin(v->ctx, p, sp, is3d::SamplerRunArgs{d_rec.as<is3d::SamplerCell>(), d_GT.as<double>(), e0, d_active.as<int32_t>(), (int64_t)n_active,
+                                                            d_drawn.as<int32_t>(), nullptr, nullptr, 0, nullptr, 0},
+                       *bin, hist_dev, hist_dev + bin->layout.total);
+                HIP_TRY(hipGetLastError());
+            }
+        } else if (n_active > 0) {
             const unsigned grid = (unsigned)(((int64_t)n_active + 127) / 128);
             HIP_TRY(hipMemsetAsync(d_counts.as<int64_t>() + n_active, 0, sizeof(int64_t), nullptr));
             if (v)
@@ -836,7 +850,7 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t
         } else {
             HIP_TRY(hipEventRecord(ev[3], nullptr));
         }
-        HIP_TRY(hipEventRecord(ev[8], nullptr));
+        if (!fused) HIP_TRY(hipEventRecord(ev[8], nullptr));
         if (bin && batch_total > 0)
             HIP_TRY(is3d::sampler_bins_launch(bin->bins, bin->widths, bin->layout, sp.npart, n_events, P->d_particles.as<is3d_particle>(), batch_total,
                                               P->d_hist.as<unsigned long long>(), P->d_hist.as<unsigned long long>() + bin->layout.total,
@@ -868,11 +882,9 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t
         stats->n_hadrons_drawn = (int64_t)h[4];
         stats->n_cells_breakdown = (int64_t)h[5];
         stats->n_classes = ncls;
-        stats->ms_count = ms_count; stats->ms_fill = ms_fill;
-        if (bin) {
-            stats->ms_bin = ms_bin;
-            stats->particle_workspace_bytes = P->cap_particles * (int64_t)sizeof(is3d_particle);
-        }
+        stats->ms_count = fused ? 0.0 : ms_count; stats->ms_fill = fused ? 0.0 : ms_fill;
+        if (bin) stats->ms_bin = ms_bin;
+        if (bin && !fused) stats->particle_workspace_bytes = P->cap_particles * (int64_t)sizeof(is3d_particle);
     }
     if (h[0] != ~0ULL && v) return set_error(IS3D_EDOMAIN, "cell %lld: %s", (long long)h[0], v->domain_text);
     if (h[0] != ~0ULL)
@@ -1013,7 +1025,77 @@ HistParts hist_parts(const is3d_sampler_hist &h, const is3d::SamplerHistLayout &
     return {{h.dN_dy, h.dN_deta, h.dN_pT, h.dN_tau, h.dN_r, h.vn_re, h.vn_im},
             {l.de - l.dy, l.dp - l.de, l.dt - l.dp, l.dr - l.dt, l.vr - l.dr, l.vi - l.vr, l.total - l.vi}};
 }
+// a binned run's histograms: the caller's arrays zeroed and, for a surface with cells, the plan's device block (histograms, then yields) sized and zeroed ...
+int hist_begin(is3d_sampler_plan *P, const HistParts &parts, const is3d_sampler_hist *hist, int32_t n_events, int64_t words, bool device)
+{
+    for (int a = 0; a < 7; a++) memset(parts.p[a], 0, (size_t)parts.n[a] * sizeof(int64_t));
+    memset(hist->yield, 0, (size_t)n_events * sizeof(int64_t));
+    if (!device) return IS3D_OK;
+    HIP_TRY(hipSetDevice(P->device));
+    if (words > P->cap_hist) {
+        HIP_TRY(P->d_hist.alloc((size_t)words * sizeof(int64_t)));
+        P->cap_hist = words;
+    }
+    HIP_TRY(hipMemsetAsync(P->d_hist.p, 0, (size_t)words * sizeof(int64_t), nullptr));
+    return IS3D_OK;
+}
+// ... and after the last batch the one copy to the caller's arrays
+int hist_end(is3d_sampler_plan *P, const HistParts &parts, const is3d_sampler_hist *hist, int32_t n_events, int64_t words)
+{
+    std::vector<int64_t> h((size_t)words);
+    HIP_TRY(hipMemcpy(h.data(), P->d_hist.p, (size_t)words * sizeof(int64_t), hipMemcpyDeviceToHost));
+    const int64_t *src = h.data();
+    for (int a = 0; a < 7; a++) {
+        memcpy(parts.p[a], src, (size_t)parts.n[a] * sizeof(int64_t));
+        src += parts.n[a];
+    }
+    memcpy(hist->yield, src, (size_t)n_events * sizeof(int64_t));
+    return IS3D_OK;
+}
+int hist_check_counts(const HistParts &parts, const is3d_sampler_hist *hist)
+{
+    for (int64_t j = 0; j < parts.n[2]; j++)
+        if (hist->dN_pT[j] > IS3D_SAMPLER_VN_MAX_COUNT)
+            return is3d::set_error(IS3D_EDOMAIN, "dN_pT bin %lld holds %lld hadrons: the fixed-point harmonic sums are exact up to %lld per bin", (long long)j,
+                                   (long long)hist->dN_pT[j], (long long)IS3D_SAMPLER_VN_MAX_COUNT);
+    return IS3D_OK;
+}
 }  // namespace
+
+int is3d::sampler_check_bin_args(const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int32_t n_events, int32_t n_species)
+{
+    if (int rc = check_bin_args(bins, hist, n_events)) return rc;
+    const SamplerHistLayout l = sampler_hist_layout(*bins, n_species);
+    if (bins->kernel_form == 2 && !sampler_bins_lds_fits(l))
+        return set_error(IS3D_EINVAL, "kernel_form = 2: %lld histogram words do not fit the LDS", (long long)l.total);
+    return IS3D_OK;
+}
+
+int is3d::sampler_variant_execute_binned(is3d_sampler_plan *P, const SamplerVariant &v, int64_t n_cells, const double *x_dev, const double *y_dev,
+                                         int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
+                                         const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
+                                         is3d_sampler_stats *stats)
+{
+    *n_particles = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (!v.bin) return set_error(IS3D_EINVAL, "this sampler variant has no fused bin pass");
+    if (n_cells < 0 || n_cells + first_cell > 0xffffffffLL) return set_error(IS3D_EINVAL, "cell indices must fit 32 bits for the counter-based streams");
+    const BinRun br{*bins, sampler_bin_widths(*bins), sampler_hist_layout(*bins, P->sp.npart)};
+    const HistParts parts = hist_parts(*hist, br.layout);
+    const int64_t words = br.layout.total + n_events;
+    if (int rc = hist_begin(P, parts, hist, n_events, words, n_cells > 0)) return rc;
+    P->p.cells = CellPtrs{};
+    int64_t unused = 0;
+    const int rc = sampler_batches(P, &v, n_cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, nullptr, 0, &br, &unused, stats);
+    // a bad cell (IS3D_EDOMAIN) leaves the other cells' hadrons binned: the histograms are returned with the error
+    if (rc && rc != IS3D_EDOMAIN) return rc;
+    if (n_cells == 0) return IS3D_OK;
+    const std::string kept = rc ? is3d_last_error() : "";
+    if (int rc2 = hist_end(P, parts, hist, n_events, words)) return rc2;
+    for (int32_t e = 0; e < n_events; e++) *n_particles += hist->yield[e];
+    if (rc) return set_error(rc, "%s", kept.c_str());
+    return hist_check_counts(parts, hist);
+}
 
 extern "C" int is3d_sampler_plan_execute_binned(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev,
                                                 int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
@@ -1030,32 +1112,12 @@ extern "C" int is3d_sampler_plan_execute_binned(is3d_sampler_plan *P, const is3d
     if (bins->kernel_form == 2 && !is3d::sampler_bins_lds_fits(br.layout))
         return set_error(IS3D_EINVAL, "kernel_form = 2: %lld histogram words do not fit the LDS", (long long)br.layout.total);
     const HistParts parts = hist_parts(*hist, br.layout);
-    for (int a = 0; a < 7; a++) memset(parts.p[a], 0, (size_t)parts.n[a] * sizeof(int64_t));
-    memset(hist->yield, 0, (size_t)n_events * sizeof(int64_t));
     const int64_t words = br.layout.total + n_events;
-    if (cells->n_cells > 0) {
-        HIP_TRY(hipSetDevice(P->device));
-        if (words > P->cap_hist) {
-            HIP_TRY(P->d_hist.alloc((size_t)words * sizeof(int64_t)));
-            P->cap_hist = words;
-        }
-        HIP_TRY(hipMemsetAsync(P->d_hist.p, 0, (size_t)words * sizeof(int64_t), nullptr));
-    }
+    if (int rc = hist_begin(P, parts, hist, n_events, words, cells->n_cells > 0)) return rc;
     if (int rc = sampler_execute(P, cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, nullptr, 0, &br, n_particles, stats)) return rc;
     if (cells->n_cells == 0) return IS3D_OK;
-    std::vector<int64_t> h((size_t)words);
-    HIP_TRY(hipMemcpy(h.data(), P->d_hist.p, (size_t)words * sizeof(int64_t), hipMemcpyDeviceToHost));
-    const int64_t *src = h.data();
-    for (int a = 0; a < 7; a++) {
-        memcpy(parts.p[a], src, (size_t)parts.n[a] * sizeof(int64_t));
-        src += parts.n[a];
-    }
-    memcpy(hist->yield, src, (size_t)n_events * sizeof(int64_t));
-    for (int64_t j = 0; j < parts.n[2]; j++)
-        if (hist->dN_pT[j] > IS3D_SAMPLER_VN_MAX_COUNT)
-            return set_error(IS3D_EDOMAIN, "dN_pT bin %lld holds %lld hadrons: the fixed-point harmonic sums are exact up to %lld per bin", (long long)j,
-                             (long long)hist->dN_pT[j], (long long)IS3D_SAMPLER_VN_MAX_COUNT);
-    return IS3D_OK;
+    if (int rc = hist_end(P, parts, hist, n_events, words)) return rc;
+    return hist_check_counts(parts, hist);
 }
 
 // the host-pointer entry: plan + upload + execute_binned

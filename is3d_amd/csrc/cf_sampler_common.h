@@ -13,6 +13,7 @@
 #include "../../include/is3d_amd.h"
 #include "cf_device.h"
 #include "cf_math.h"
+#include "cf_sampler_bins.h"
 
 namespace is3d {
 
@@ -316,15 +317,25 @@ struct SamplerRunArgs {
     is3d_particle *particles;
     int64_t capacity;
 };
+// the bins of a binned run with what follows from them (is3d_sampler_plan_execute_binned, sampler_variant_execute_binned)
+struct SamplerBinRun {
+    is3d_sampler_test_bins bins;
+    SamplerBinWidths widths;
+    SamplerHistLayout layout;
+};
 // T: the DEVICE array the density integrals take as temperature; cells: writes the records (live, dn_sum, dn_tot and the running sums as
 // cf_sampler_cells does; status[0], [1]) after the density kernel, returns an IS3D code; run: the count (fill = false) or fill pass on `grid`
-// workgroups of 128; domain_text: what IS3D_EDOMAIN says after "cell N: "
+// workgroups of 128; domain_text: what IS3D_EDOMAIN says after "cell N: ".
+// bin (optional): the fused pass of a binned run -- the emitting pairs of a.active sampled once and every kept hadron added straight into
+// hist_dev (layout b.layout) and yield_dev (one word per event of the run); of a, only rec, GT, event0, active, n_active and n_drawn are set
 struct SamplerVariant {
     const double *T;
     const char *domain_text;
     void *ctx;
     int (*cells)(void *ctx, const SamplerParams &p, const SamplerSpecies &sp, const double *GT, SamplerCell *rec);
     void (*run)(void *ctx, bool fill, unsigned grid, const SamplerParams &p, const SamplerSpecies &sp, const SamplerRunArgs &a);
+    void (*bin)(void *ctx, const SamplerParams &p, const SamplerSpecies &sp, const SamplerRunArgs &a, const SamplerBinRun &b,
+                unsigned long long *hist_dev, unsigned long long *yield_dev);
 };
 // a plan with the species classes, the alpha = 1 Gauss-Laguerre nodes and the workspaces, without coefficient tables: df_mode 1 weights
 // (2 neq_fact g GT), regular mode.  The argument checks come before any device use.
@@ -334,6 +345,17 @@ int sampler_variant_plan_create(is3d_sampler_plan **out, const is3d_species *spe
 int sampler_variant_execute(is3d_sampler_plan *P, const SamplerVariant &v, int64_t n_cells, const double *x_dev, const double *y_dev,
                             int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev,
                             int64_t capacity, int64_t *n_particles, is3d_sampler_stats *stats);
+// a binned run of a variant that has a bin hook: per event batch Poisson, select and ONE launch of the hook -- no counts, offsets, scan or
+// particle workspace exist on this path.  The histograms live in the plan (zeroed before the first batch) and are copied to hist_host
+// (HOST arrays, overwritten) once after the last batch, also when a bad cell gives IS3D_EDOMAIN; *n_particles is the sum of the yields.
+// stats: ms_bin is the time of the fused passes; ms_count, ms_fill and particle_workspace_bytes are 0.  The caller has checked bins and
+// hist (sampler_check_bin_args).
+int sampler_variant_execute_binned(is3d_sampler_plan *P, const SamplerVariant &v, int64_t n_cells, const double *x_dev, const double *y_dev,
+                                   int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events, const is3d_sampler_test_bins *bins,
+                                   const is3d_sampler_hist *hist_host, int64_t *n_particles, is3d_sampler_stats *stats);
+// the bin checks of is3d_sample_binned (IS3D_EINVAL, no device use): null, bad bins, kernel_form outside 0..2, and kernel_form = 2 on a
+// histogram block of n_species species that does not fit the LDS
+int sampler_check_bin_args(const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int32_t n_events, int32_t n_species);
 
 // is3d_sample_particles_vah's refusals (IS3D_EINVAL), all before any device use: also what is3d_sample_particles_vah_multi checks first
 int sampler_vah_check(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab, const is3d_sampler_inputs *in,

@@ -27,7 +27,9 @@
 //   cf_sampler_vah_cells  thread <-> cell: the record (SamplerCell: T = Lambda, pi.. = pi_perp in the LRF, V. = W in the LRF, bulkPi = the residual
 //                         bulk pressure, c0..c4; VahCellExtra: alpha_L and the tensor components along u), the running sums, dn_tot
 //   cf_sampler_vah_run    thread <-> emitting (event, cell) pair: count pass and fill pass, as cf_sampler_run
+//   cf_sampler_vah_bin    the same pairs sampled once and binned as cf_sampler_bins does, without a list (is3d_sample_binned_vah)
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -154,7 +156,122 @@ cf_sampler_vah_cells(SamplerParams p, SamplerSpecies sp, VahSamplerCells v, cons
     out[ic] = c; extra[ic] = x;
 }
 
-// one emitting (event, cell) pair, as sampler_thread of cf_sampler.hip with the VAH momentum map and weight
+// ---- what a pass does with a kept hadron: the one thing in which count, fill and bin differ ----
+struct VahKeepCount {
+    __device__ __forceinline__ void operator()(const is3d_particle &) {}
+};
+struct VahKeepFill {
+    is3d_particle *__restrict__ particles;
+    int64_t slot, capacity;
+    __device__ __forceinline__ void operator()(const is3d_particle &o)
+    {
+        if (slot < capacity) particles[slot] = o;
+        slot++;
+    }
+};
+struct VahBinArgs {
+    is3d_sampler_test_bins b;
+    SamplerBinWidths w;
+    SamplerHistLayout l;
+    int n_species;
+};
+// the adds of cf_sampler_bins (cf_sampler_bins.hip) for one particle, into the workgroup's LDS block or the global one: 64-bit integer atomics
+struct VahKeepBin {
+    const VahBinArgs &a;
+    unsigned long long *h;
+    __device__ __forceinline__ void operator()(const is3d_particle &q)
+    {
+        const SamplerBinIndex k = sampler_bin_particle(a.b, a.w, q);
+        const int64_t s = q.species;
+        if (k.iyp >= 0) atomicAdd(&h[a.l.dy + s * a.b.y_bins + k.iyp], 1ULL);
+        if (k.ieta >= 0) atomicAdd(&h[a.l.de + s * a.b.eta_bins + k.ieta], 1ULL);
+        if (k.itau >= 0) atomicAdd(&h[a.l.dt + s * a.b.tau_bins + k.itau], 1ULL);
+        if (k.ir >= 0) atomicAdd(&h[a.l.dr + s * a.b.r_bins + k.ir], 1ULL);
+        if (k.ipT >= 0) {
+            const int64_t j = s * a.b.pT_bins + k.ipT, plane = (int64_t)a.n_species * a.b.pT_bins;
+            atomicAdd(&h[a.l.dp + j], 1ULL);
+            for (int m = 0; m < IS3D_SAMPLER_VN_HARMONICS; m++) {
+                double sn, cs;
+                sincos(((double)m + 1.0) * k.phi, &sn, &cs);
+                atomicAdd(&h[a.l.vr + m * plane + j], (unsigned long long)sampler_vn_fixed(cs));   // two's complement: signed sums
+                atomicAdd(&h[a.l.vi + m * plane + j], (unsigned long long)sampler_vn_fixed(sn));
+            }
+        }
+    }
+};
+
+// one emitting (event, cell) pair, as sampler_thread of cf_sampler.hip with the VAH momentum map and weight: the ONE piece of source the
+// count, the fill and the bin pass run.  idx is the pair's event-major index (event - event0) * n_cells + cell; every kept hadron goes to
+// keep() as the is3d_particle of the list.  Returns the number kept; tally[] gets the pair's momentum samples, acceptances and hadrons drawn.
+template <class Keep>
+__device__ __forceinline__ long vah_sample_pair(const SamplerParams &p, const SamplerSpecies &sp, const SamplerCell *__restrict__ cellrec,
+                                                const VahCellExtra *__restrict__ extra, const double *__restrict__ GT, int ievent, int64_t ic,
+                                                long N_hadrons, Keep &keep, unsigned long long (&tally)[3])
+{
+    const SamplerCell &c = cellrec[ic];
+    const VahCellExtra x = extra[ic];
+    const uint32_t gcell = (uint32_t)(p.first_cell + ic);
+    Rng g_type, g_momentum, g_keep, g_rapidity;
+    g_type.init(p.seed, 1, gcell, (uint32_t)ievent);
+    g_momentum.init(p.seed, 2, gcell, (uint32_t)ievent);
+    g_keep.init(p.seed, 3, gcell, (uint32_t)ievent);
+    g_rapidity.init(p.seed, 4, gcell, (uint32_t)ievent);
+    const double *gt = GT + ic;
+    const double sinheta = sinh(c.eta), cosheta = sqrt(1.0 + sinheta * sinheta);
+    long kept = 0, samples = 0, acceptances = 0;
+    for (long ih = 0; ih < N_hadrons; ih++) {
+        const double ut_ = g_type.uniform() * c.dn_sum;
+        const int chosen = choose_species(p, sp, c, gt, nullptr, nullptr, ic, ut_);
+        const double mass = sp.mass[chosen], mass_squared = mass * mass, sign = sp.sign[chosen];
+        const LrfMom m = sample_momentum(g_momentum, acceptances, samples, mass, sign, c.T, 0.0);
+        LrfMom q;
+        q.px = m.px; q.py = m.py; q.pz = x.aL * m.pz;
+        q.E = sqrt(mass_squared + q.px * q.px + q.py * q.py + q.pz * q.pz);
+        // the residual delta-f (smooth_kernels.cpp:2323-2342) at this momentum; E_a = m.E
+        double df = 0.0;
+        if (p.include_shear) {
+            const double pimunu_pmu_pnu = q.E * (q.E * x.piuu + 2.0 * (q.px * x.piux + q.py * x.piuy + q.pz * x.piuz))
+                                        + q.px * q.px * c.pixx + q.py * q.py * c.piyy + q.pz * q.pz * c.pizz
+                                        + 2.0 * (q.px * q.py * c.pixy + q.px * q.pz * c.pixz + q.py * q.pz * c.piyz);
+            const double Wmu_pmu_pz = q.pz * (q.px * c.Vx + q.py * c.Vy + q.pz * c.Vz);   // (p.z)(W.p) = (-p_z)(-W_i p_i)
+            df = c.c3 * Wmu_pmu_pz + c.c4 * pimunu_pmu_pnu;
+        }
+        if (p.include_bulk) df += (c.c0 * mass_squared + c.c1 * q.pz * q.pz + c.c2 * q.E * q.E) * c.bulkPi;
+        const double fabar = 1.0 - sign / (exp(m.E / c.T) + sign);
+        const double w_visc = (1.0 + fmax(-1.0, fmin(fabar * df, 1.0))) / 2.0;
+        // boost_pLRF_to_lab_frame (emissionfunction.cpp:40-51)
+        const double ptau = q.E * c.ut + q.px * c.Xt + q.pz * c.Zt;
+        const double plx = q.E * c.ux + q.px * c.Xx + q.py * c.Yx;
+        const double ply = q.E * c.uy + q.px * c.Xy + q.py * c.Yy;
+        const double pn = q.E * c.un + q.px * c.Xn + q.pz * c.Zn;
+        const double w_flux = fmax(0.0, q.E * c.dst - q.px * c.dsx - q.py * c.dsy - q.pz * c.dsz) / (q.E * c.ds_max);   // :1148
+        if (!(g_keep.uniform() < (w_flux * w_visc))) continue;
+        double Elab, pz, eta = c.eta, sh = sinheta, ch = cosheta;
+        if (!p.dim3) {                                                          // :1168-1186
+            const double yp = p.y_max * (2.0 * g_rapidity.uniform() - 1.0);
+            const double sinhy = sinh(yp), coshy = sqrt(1.0 + sinhy * sinhy);
+            const double tau_pn = c.tau * pn, mT = sqrt(mass_squared + plx * plx + ply * ply);
+            sh = (ptau * sinhy - tau_pn * coshy) / mT;
+            eta = asinh(sh);
+            ch = sqrt(1.0 + sh * sh);
+            pz = mT * sinhy;
+            Elab = mT * coshy;
+        } else {
+            pz = c.tau * pn * ch + ptau * sh;
+            Elab = sqrt(mass_squared + plx * plx + ply * ply + pz * pz);
+        }
+        is3d_particle o;
+        o.cell = p.first_cell + ic; o.event = ievent; o.species = chosen;
+        o.tau = c.tau; o.x = c.x; o.y = c.y; o.eta = eta; o.t = c.tau * ch; o.z = c.tau * sh;
+        o.E = Elab; o.px = plx; o.py = ply; o.pz = pz;
+        keep(o);
+        kept++;
+    }
+    tally[0] += (unsigned long long)samples; tally[1] += (unsigned long long)acceptances; tally[2] += (unsigned long long)N_hadrons;
+    return kept;
+}
+
+// thread <-> emitting (event, cell) pair: the count pass (counts[] and the run-wide tallies) and the fill pass of the list route
 template <bool FILL>
 __global__ void __launch_bounds__(128)
 cf_sampler_vah_run(SamplerParams p, SamplerSpecies sp, const SamplerCell *__restrict__ cellrec, const VahCellExtra *__restrict__ extra,
@@ -168,76 +285,77 @@ cf_sampler_vah_run(SamplerParams p, SamplerSpecies sp, const SamplerCell *__rest
         const int64_t idx = active[ia];                                     // event-major: (event - event0) * n_cells + cell
         const int ievent = event0 + (int)(idx / p.n_cells);
         const int64_t ic = idx % p.n_cells;
-        const SamplerCell &c = cellrec[ic];
-        const VahCellExtra x = extra[ic];
-        const uint32_t gcell = (uint32_t)(p.first_cell + ic);
         const long N_hadrons = n_drawn[idx];                                // cf_sampler_poisson (stream 0)
-        Rng g_type, g_momentum, g_keep, g_rapidity;
-        g_type.init(p.seed, 1, gcell, (uint32_t)ievent);
-        g_momentum.init(p.seed, 2, gcell, (uint32_t)ievent);
-        g_keep.init(p.seed, 3, gcell, (uint32_t)ievent);
-        g_rapidity.init(p.seed, 4, gcell, (uint32_t)ievent);
-        const double *gt = GT + ic;
-        const double sinheta = sinh(c.eta), cosheta = sqrt(1.0 + sinheta * sinheta);
-        long kept = 0, samples = 0, acceptances = 0;
-        int64_t slot = FILL ? base + offsets[ia] : 0;
-        for (long ih = 0; ih < N_hadrons; ih++) {
-            const double ut_ = g_type.uniform() * c.dn_sum;
-            const int chosen = choose_species(p, sp, c, gt, nullptr, nullptr, ic, ut_);
-            const double mass = sp.mass[chosen], mass_squared = mass * mass, sign = sp.sign[chosen];
-            const LrfMom m = sample_momentum(g_momentum, acceptances, samples, mass, sign, c.T, 0.0);
-            LrfMom q;
-            q.px = m.px; q.py = m.py; q.pz = x.aL * m.pz;
-            q.E = sqrt(mass_squared + q.px * q.px + q.py * q.py + q.pz * q.pz);
-            // the residual delta-f (smooth_kernels.cpp:2323-2342) at this momentum; E_a = m.E
-            double df = 0.0;
-            if (p.include_shear) {
-                const double pimunu_pmu_pnu = q.E * (q.E * x.piuu + 2.0 * (q.px * x.piux + q.py * x.piuy + q.pz * x.piuz))
-                                            + q.px * q.px * c.pixx + q.py * q.py * c.piyy + q.pz * q.pz * c.pizz
-                                            + 2.0 * (q.px * q.py * c.pixy + q.px * q.pz * c.pixz + q.py * q.pz * c.piyz);
-                const double Wmu_pmu_pz = q.pz * (q.px * c.Vx + q.py * c.Vy + q.pz * c.Vz);   // (p.z)(W.p) = (-p_z)(-W_i p_i)
-                df = c.c3 * Wmu_pmu_pz + c.c4 * pimunu_pmu_pnu;
-            }
-            if (p.include_bulk) df += (c.c0 * mass_squared + c.c1 * q.pz * q.pz + c.c2 * q.E * q.E) * c.bulkPi;
-            const double fabar = 1.0 - sign / (exp(m.E / c.T) + sign);
-            const double w_visc = (1.0 + fmax(-1.0, fmin(fabar * df, 1.0))) / 2.0;
-            // boost_pLRF_to_lab_frame (emissionfunction.cpp:40-51)
-            const double ptau = q.E * c.ut + q.px * c.Xt + q.pz * c.Zt;
-            const double plx = q.E * c.ux + q.px * c.Xx + q.py * c.Yx;
-            const double ply = q.E * c.uy + q.px * c.Xy + q.py * c.Yy;
-            const double pn = q.E * c.un + q.px * c.Xn + q.pz * c.Zn;
-            const double w_flux = fmax(0.0, q.E * c.dst - q.px * c.dsx - q.py * c.dsy - q.pz * c.dsz) / (q.E * c.ds_max);   // :1148
-            if (!(g_keep.uniform() < (w_flux * w_visc))) continue;
-            double Elab, pz, eta = c.eta, sh = sinheta, ch = cosheta;
-            if (!p.dim3) {                                                          // :1168-1186
-                const double yp = p.y_max * (2.0 * g_rapidity.uniform() - 1.0);
-                const double sinhy = sinh(yp), coshy = sqrt(1.0 + sinhy * sinhy);
-                const double tau_pn = c.tau * pn, mT = sqrt(mass_squared + plx * plx + ply * ply);
-                sh = (ptau * sinhy - tau_pn * coshy) / mT;
-                eta = asinh(sh);
-                ch = sqrt(1.0 + sh * sh);
-                pz = mT * sinhy;
-                Elab = mT * coshy;
-            } else {
-                pz = c.tau * pn * ch + ptau * sh;
-                Elab = sqrt(mass_squared + plx * plx + ply * ply + pz * pz);
-            }
-            if (FILL && slot < capacity) {
-                is3d_particle o;
-                o.cell = p.first_cell + ic; o.event = ievent; o.species = chosen;
-                o.tau = c.tau; o.x = c.x; o.y = c.y; o.eta = eta; o.t = c.tau * ch; o.z = c.tau * sh;
-                o.E = Elab; o.px = plx; o.py = ply; o.pz = pz;
-                particles[slot] = o;
-            }
-            slot++;
-            kept++;
-        }
-        if (!FILL) {
-            counts[ia] = kept;
-            tally[0] = (unsigned long long)samples; tally[1] = (unsigned long long)acceptances; tally[2] = (unsigned long long)N_hadrons;
+        if (FILL) {
+            VahKeepFill keep{particles, base + offsets[ia], capacity};
+            vah_sample_pair(p, sp, cellrec, extra, GT, ievent, ic, N_hadrons, keep, tally);
+        } else {
+            VahKeepCount keep;
+            counts[ia] = vah_sample_pair(p, sp, cellrec, extra, GT, ievent, ic, N_hadrons, keep, tally);
         }
     }
     if (!FILL) sampler_tally(p, tally);
+}
+
+// The bin pass: the count pass's threads, streams and loop, every kept hadron added straight into the histograms of cf_sampler_bins
+// (the same rule, cf_sampler_bins.h, on the same is3d_particle the fill pass would store) -- no list, so no counts, offsets or scan.
+// Every add is a 64-bit integer, so the histograms are those of the list route bit for bit whatever the order of arrival.
+//   PRIVATE: the whole block lives in dynamic LDS (ds_add_u64), a bounded number of workgroups walks the pair list grid-stride and each
+//            flushes its non-zero words once with global adds
+//   else:    every add goes straight to the global block
+// Per-event yields: the pairs are event-major, so the lanes of a wave see runs of equal events; after the rejection loop, with the wave
+// reconverged, the first lane of a run adds the run's kept hadrons (a segmented sum over an inclusive wave scan) -- one add per distinct
+// event per wave and trip.  Lanes past n_active take part with event INT_MAX and kept = 0.  The trip count is the same for every thread
+// of a workgroup: the wave operations see whole waves and the barriers every thread.
+constexpr int kVahBinThreads = 256;
+constexpr int kVahBinPrivateBlocks = 768;     // workgroup-private form: at most this many flushes (three 43 KiB blocks per CU of 160 KiB LDS)
+
+template <bool PRIVATE>
+__global__ void __launch_bounds__(kVahBinThreads, 2)
+cf_sampler_vah_bin(SamplerParams p, SamplerSpecies sp, const SamplerCell *__restrict__ cellrec, const VahCellExtra *__restrict__ extra,
+                   const double *__restrict__ GT, int event0, const int32_t *__restrict__ active, int64_t n_active,
+                   const int32_t *__restrict__ n_drawn, VahBinArgs a, unsigned long long *__restrict__ hist,
+                   unsigned long long *__restrict__ yield)
+{
+    extern __shared__ unsigned long long priv[];
+    if (PRIVATE) {
+        for (int64_t j = threadIdx.x; j < a.l.total; j += kVahBinThreads) priv[j] = 0ULL;
+        __syncthreads();
+    }
+    VahKeepBin keep{a, PRIVATE ? priv : hist};
+    unsigned long long tally[3] = {0ULL, 0ULL, 0ULL};
+    const int lane = threadIdx.x & 63;
+    for (int64_t i0 = (int64_t)blockIdx.x * kVahBinThreads; i0 < n_active; i0 += (int64_t)gridDim.x * kVahBinThreads) {
+        const int64_t ia = i0 + threadIdx.x;
+        int ev = INT_MAX;
+        long long kept = 0;
+        if (ia < n_active) {
+            const int64_t idx = active[ia];
+            ev = event0 + (int)(idx / p.n_cells);
+            kept = vah_sample_pair(p, sp, cellrec, extra, GT, ev, idx % p.n_cells, (long)n_drawn[idx], keep, tally);
+        }
+        const int prev = __shfl_up(ev, 1);
+        const bool lead = lane == 0 || prev != ev;
+        const unsigned long long leaders = __ballot(lead);
+        long long incl = kept;                                               // inclusive scan of kept over the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const long long t = __shfl_up(incl, d);
+            if (lane >= d) incl += t;
+        }
+        const unsigned long long above = lane == 63 ? 0ULL : (leaders >> (lane + 1)) << (lane + 1);
+        const int last = (above ? __ffsll((long long)above) - 1 : 64) - 1;  // the last lane of the run that ends at the next leader
+        const long long run = __shfl(incl, last) - incl + kept;
+        if (lead && ev != INT_MAX && run) atomicAdd(&yield[ev], (unsigned long long)run);
+    }
+    sampler_tally(p, tally);
+    if (PRIVATE) {
+        __syncthreads();
+        for (int64_t j = threadIdx.x; j < a.l.total; j += kVahBinThreads) {
+            const unsigned long long v = priv[j];
+            if (v) atomicAdd(&hist[j], v);
+        }
+    }
 }
 
 }  // namespace is3d
@@ -282,6 +400,25 @@ void vah_run_hook(void *ctx, bool fill, unsigned grid, const is3d::SamplerParams
                            a.n_drawn, a.counts, a.offsets, a.base, a.particles, a.capacity);
 }
 
+// the fused pass of a binned run: one launch per event batch.  Private form: at most kVahBinPrivateBlocks workgroups, each walking the
+// pair list grid-stride; global form: one trip per thread
+void vah_bin_hook(void *ctx, const is3d::SamplerParams &p, const is3d::SamplerSpecies &sp, const is3d::SamplerRunArgs &a, const is3d::SamplerBinRun &b,
+                  unsigned long long *hist_dev, unsigned long long *yield_dev)
+{
+    const VahRun &r = *(const VahRun *)ctx;
+    const is3d::VahCellExtra *extra = r.d_extra.as<is3d::VahCellExtra>();
+    const is3d::VahBinArgs ba{b.bins, b.widths, b.layout, sp.npart};
+    const bool priv = b.bins.kernel_form == 2 || (b.bins.kernel_form == 0 && is3d::sampler_bins_lds_fits(b.layout));
+    const int64_t trips = (a.n_active + is3d::kVahBinThreads - 1) / is3d::kVahBinThreads;
+    if (priv)
+        hipLaunchKernelGGL((is3d::cf_sampler_vah_bin<true>), dim3((unsigned)std::min<int64_t>(trips, is3d::kVahBinPrivateBlocks)), dim3(is3d::kVahBinThreads),
+                           (size_t)b.layout.total * sizeof(unsigned long long), nullptr, p, sp, a.rec, extra, a.GT, a.event0, a.active, a.n_active, a.n_drawn,
+                           ba, hist_dev, yield_dev);
+    else
+        hipLaunchKernelGGL((is3d::cf_sampler_vah_bin<false>), dim3((unsigned)trips), dim3(is3d::kVahBinThreads), 0, nullptr, p, sp, a.rec, extra, a.GT,
+                           a.event0, a.active, a.n_active, a.n_drawn, ba, hist_dev, yield_dev);
+}
+
 // the arrays of is3d_vah_cells (cf_host.h order) the sampler reads: not T; eta in 3+1D; pi and W with shear, bulkPi with bulk; c0..c4 without tables
 bool vah_array_needed(int a, const is3d_options *o, bool tables)
 {
@@ -323,40 +460,46 @@ int is3d::sampler_vah_check(const is3d_vah_cells *cells, const is3d_species *spe
     return IS3D_OK;
 }
 
-extern "C" int is3d_sample_particles_vah(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab,
-                                         const is3d_sampler_inputs *in, const is3d_options *opts, is3d_particle *particles, int64_t capacity,
-                                         int64_t *n_particles, is3d_sampler_stats *stats)
-{
-    using is3d::set_error;
-    if (!n_particles) return set_error(IS3D_EINVAL, "null argument");
-    *n_particles = 0;
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (int rc = is3d::sampler_vah_check(cells, species, tab, in, opts)) return rc;
-    if (particles == nullptr) capacity = 0;
-    const int64_t n = cells->n_cells;
+namespace {
+// what the host-pointer entries share: a plan for this surface; the needed cell arrays, then x and y, uploaded in one block; the variant
+struct VahStaged {
     is3d_sampler_plan *P = nullptr;
-    if (int rc = is3d::sampler_variant_plan_create(&P, species, in, opts, n)) return rc;
-    struct PlanGuard { is3d_sampler_plan *p; ~PlanGuard() { is3d_sampler_plan_destroy(p); } } guard{P};
-    if (n == 0) return IS3D_OK;
-
-    // ---- the needed cell arrays, then x and y, in one block ----
     VahRun r;
-    r.tab = tab; r.n = n; r.first_cell = in->first_cell;
     is3d::DevBuf<double> d_cells;
-    HIP_TRY(d_cells.alloc((size_t)n * (is3d::kVahCellArrays + 2)));
+    std::array<const double *, 2> xy{};
+    float ms_h2d = 0;
+    is3d::SamplerVariant var{};
+    ~VahStaged() { is3d_sampler_plan_destroy(P); }
+};
+// an empty surface stages nothing
+int vah_stage(VahStaged &s, const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab, const is3d_sampler_inputs *in,
+              const is3d_options *opts)
+{
+    const int64_t n = cells->n_cells;
+    if (int rc = is3d::sampler_variant_plan_create(&s.P, species, in, opts, n)) return rc;
+    VahRun &r = s.r;
+    is3d::SamplerVariant &var = s.var;
+    var.domain_text = "Lambda or alpha_L is not finite and > 0 (or Lambda > 1e4 boson masses, or the cell's mean hadron number >= 2^31), or "
+                      "(Lambda, alpha_L) lies beyond the last node of the VAH coefficient tables";
+    var.ctx = &r;
+    var.cells = vah_cells_hook;
+    var.run = vah_run_hook;
+    var.bin = vah_bin_hook;
+    if (n == 0) return IS3D_OK;
+    r.tab = tab; r.n = n; r.first_cell = in->first_cell;
+    HIP_TRY(s.d_cells.alloc((size_t)n * (is3d::kVahCellArrays + 2)));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
     struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{e0, e1};
     HIP_TRY(hipEventRecord(e0, nullptr));
     is3d_vah_cells dc{};
-    HIP_TRY(is3d::stage_cells(*cells, [&](int a) { return vah_array_needed(a, opts, tab != nullptr); }, 0, n, d_cells.p, nullptr, &dc));
-    std::array<const double *, 2> xy{in->x, in->y};
-    HIP_TRY(is3d::stage_arrays(xy, 0, n, d_cells.p + (size_t)is3d::kVahCellArrays * n, nullptr));
+    HIP_TRY(is3d::stage_cells(*cells, [&](int a) { return vah_array_needed(a, opts, tab != nullptr); }, 0, n, s.d_cells.p, nullptr, &dc));
+    s.xy = {in->x, in->y};
+    HIP_TRY(is3d::stage_arrays(s.xy, 0, n, s.d_cells.p + (size_t)is3d::kVahCellArrays * n, nullptr));
     HIP_TRY(hipEventRecord(e1, nullptr));
     HIP_TRY(hipEventSynchronize(e1));
-    float ms_h2d = 0;
-    (void)hipEventElapsedTime(&ms_h2d, e0, e1);
+    (void)hipEventElapsedTime(&s.ms_h2d, e0, e1);
     is3d::VahSamplerCells &v = r.v;
     v.tau = dc.tau; v.eta = dc.eta; v.ux = dc.ux; v.uy = dc.uy; v.un = dc.un; v.dat = dc.dat; v.dax = dc.dax; v.day = dc.day; v.dan = dc.dan;
     const double *pi[10] = {dc.pitt, dc.pitx, dc.pity, dc.pitn, dc.pixx, dc.pixy, dc.pixn, dc.piyy, dc.piyn, dc.pinn};
@@ -368,21 +511,32 @@ extern "C" int is3d_sample_particles_vah(const is3d_vah_cells *cells, const is3d
     if (tab) { v.L_last = tab->L[tab->n_L - 1]; v.aL_last = tab->aL[tab->n_aL - 1]; }
     if (tab) HIP_TRY(r.d_coef.alloc((size_t)5 * n * sizeof(double)));
     HIP_TRY(r.d_extra.alloc((size_t)n * sizeof(is3d::VahCellExtra)));
-
-    is3d::SamplerVariant var{};
     var.T = dc.Lambda;
-    var.domain_text = "Lambda or alpha_L is not finite and > 0 (or Lambda > 1e4 boson masses, or the cell's mean hadron number >= 2^31), or "
-                      "(Lambda, alpha_L) lies beyond the last node of the VAH coefficient tables";
-    var.ctx = &r;
-    var.cells = vah_cells_hook;
-    var.run = vah_run_hook;
+    return IS3D_OK;
+}
+}  // namespace
+
+extern "C" int is3d_sample_particles_vah(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab,
+                                         const is3d_sampler_inputs *in, const is3d_options *opts, is3d_particle *particles, int64_t capacity,
+                                         int64_t *n_particles, is3d_sampler_stats *stats)
+{
+    using is3d::set_error;
+    if (!n_particles) return set_error(IS3D_EINVAL, "null argument");
+    *n_particles = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (int rc = is3d::sampler_vah_check(cells, species, tab, in, opts)) return rc;
+    if (particles == nullptr) capacity = 0;
+    const int64_t n = cells->n_cells;
+    VahStaged s;
+    if (int rc = vah_stage(s, cells, species, tab, in, opts)) return rc;
+    if (n == 0) return IS3D_OK;
     DevMem d_particles;
     if (capacity > 0) HIP_TRY(d_particles.alloc((size_t)capacity * sizeof(is3d_particle)));
     int64_t total = 0;
-    const int rc = is3d::sampler_variant_execute(P, var, n, xy[0], xy[1], in->n_events, in->seed, in->first_cell, in->batch_events, d_particles.as<is3d_particle>(), capacity,
-                                                 &total, stats);
+    const int rc = is3d::sampler_variant_execute(s.P, s.var, n, s.xy[0], s.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events,
+                                                 d_particles.as<is3d_particle>(), capacity, &total, stats);
     *n_particles = total;
-    if (stats) stats->ms_h2d = ms_h2d;
+    if (stats) stats->ms_h2d = s.ms_h2d;
     // a bad cell (IS3D_EDOMAIN) leaves the other cells' hadrons sampled: the list is returned with the error
     if (rc && rc != IS3D_ENOMEM && rc != IS3D_EDOMAIN) return rc;
     const std::string kept = rc ? is3d_last_error() : "";
@@ -390,4 +544,23 @@ extern "C" int is3d_sample_particles_vah(const is3d_vah_cells *cells, const is3d
     if (ncopy > 0) HIP_TRY(hipMemcpy(particles, d_particles.p, (size_t)ncopy * sizeof(is3d_particle), hipMemcpyDeviceToHost));
     if (rc) return set_error(rc, "%s", kept.c_str());
     return IS3D_OK;
+}
+
+// the sampler with every hadron binned where it is sampled (cf_sampler_vah_bin): no list on the device or the host
+extern "C" int is3d_sample_binned_vah(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab,
+                                      const is3d_sampler_inputs *in, const is3d_options *opts, const is3d_sampler_test_bins *bins,
+                                      const is3d_sampler_hist *hist, int64_t *n_particles, is3d_sampler_stats *stats)
+{
+    using is3d::set_error;
+    if (!n_particles) return set_error(IS3D_EINVAL, "null argument");
+    *n_particles = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (int rc = is3d::sampler_vah_check(cells, species, tab, in, opts)) return rc;
+    if (int rc = is3d::sampler_check_bin_args(bins, hist, in->n_events, species->n)) return rc;
+    VahStaged s;
+    if (int rc = vah_stage(s, cells, species, tab, in, opts)) return rc;
+    const int rc = is3d::sampler_variant_execute_binned(s.P, s.var, cells->n_cells, s.xy[0], s.xy[1], in->n_events, in->seed, in->first_cell,
+                                                        in->batch_events, bins, hist, n_particles, stats);
+    if (stats) stats->ms_h2d = s.ms_h2d;
+    return rc;
 }

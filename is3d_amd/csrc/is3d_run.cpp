@@ -42,6 +42,12 @@
 // is printed as the viscous path prints its own and sizes the run, Nevents = is3d_oversample_events(min_num_hadrons, yield, max_num_samples); a
 // yield <= 0 (the linear delta-f of a large residual bulk pressure) stops the run before anything is written.  Every other combination refuses
 // the key; oversample = 1 stays refused with mode = 2.
+// vah_sampler_on_device = 1 (optional key, default 0): with mode = 2, operation = 2, df_mode = 4, vah_sampler = 1 and test_sampler = 1 the
+// anisotropic-hydro sampler's hadrons are sampled ONCE and binned where they are sampled (is3d_sample_binned_vah; is3d_sample_binned_vah_multi over
+// a device list that was spelled out), never held as a list: the files of the host-binned run are written from the integer histograms
+// (is3d_write_sampler_tests_binned, with the same mean_yield; vn/ to the fixed point), the same lines printed plus ms_bin, no particle list.  Works
+// together with vah_oversample = 1.  Every other combination and the embedding entry (which returns the list) refuse the key before anything is
+// written; test_sampler_on_device = 1 stays refused with mode = 2 (it names the viscous route).
 // mode = 5: every run, whatever its operation, ends with the spin polarization from the surface's thermal vorticity (calculate_spin_polzn,
 // emissionfunction.cpp:1675) and appends results/St.dat, Sx.dat, Sy.dat, Sn.dat (write_polzn_vector_toFile, :1701), with T from the averages
 // file just written or T_switch when set_FO_temperature = 1; the embedding entry has no vorticity and says so.  With a device list that was
@@ -256,6 +262,23 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
                     "anisotropic-hydro sampler only (mode = 2, operation = 2, df_mode = 4, vah_sampler = 1); set vah_oversample = 0", mode, operation, df_mode,
                     (int)own_sampler);
             vah_oversample = true;
+        }
+    }
+    // optional key vah_sampler_on_device = 1: the VAH sampler's hadrons binned where they are sampled (is3d_sample_binned_vah), no particle list
+    bool vah_bin_on_device = false;
+    {
+        double key = 0.0, sampler = 0.0, test_sampler = 0.0;
+        if (get_param("vah_sampler_on_device", &key, false) == IS3D_OK && (int)key) {
+            const bool own_sampler = get_param("vah_sampler", &sampler, false) == IS3D_OK && (int)sampler;
+            const bool tests = get_param("test_sampler", &test_sampler, false) == IS3D_OK && (int)test_sampler;
+            if (!(vah && operation == 2 && df_mode == 4 && own_sampler && tests))
+                DIE("vah_sampler_on_device = 1 with mode = %d, operation = %d, df_mode = %d, vah_sampler = %d, test_sampler = %d: it bins the hadrons of this "
+                    "library's own anisotropic-hydro sampler on the device and keeps no particle list (mode = 2, operation = 2, df_mode = 4, vah_sampler = 1, "
+                    "test_sampler = 1; the viscous-hydro route has test_sampler_on_device); set vah_sampler_on_device = 0", mode, operation, df_mode,
+                    (int)own_sampler, (int)tests);
+            if (res)
+                DIE("vah_sampler_on_device = 1: the embedding entry returns the particle list, which this path never holds; set vah_sampler_on_device = 0");
+            vah_bin_on_device = true;
         }
     }
     if (vah) {
@@ -601,15 +624,20 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         if (df_mode == 3) printf("Sampling particles with Mike's modified distribution...\n");
         if (df_mode == 4 && !vah) printf("Sampling particles with Jonah's modified distribution...\n");
         if (vah) printf("Sampling particles from vahydro (P_L matching) with df...\n");
-        if (bin_on_device) {
-            // one pass: every event batch is binned on its device and dropped; the integer histograms of the shards are added on the host
+        if (bin_on_device || vah_bin_on_device) {
+            // one pass: every event batch is binned on its device and dropped (anisotropic hydro: every hadron binned where it is sampled); the
+            // integer histograms of the shards are added on the host
             const size_t S = (size_t)sp.n, plane = (size_t)IS3D_SAMPLER_VN_HARMONICS * S * bins.pT_bins;
             std::vector<int64_t> h_dy(S * bins.y_bins), h_de(S * bins.eta_bins), h_dp(S * bins.pT_bins), h_dt(S * bins.tau_bins), h_dr(S * bins.r_bins),
                 h_vr(plane), h_vi(plane), h_yield((size_t)si.n_events);
             const is3d_sampler_hist hist{h_dy.data(), h_de.data(), h_dp.data(), h_dt.data(), h_dr.data(), h_vr.data(), h_vi.data(), h_yield.data()};
-            const int rcb = is3d_sample_binned_multi(&cells, &sp, &df, &si, &opts, rd.list.empty() ? nullptr : rd.list.data(), (int32_t)rd.list.size(), &bins,
-                                                     &hist, &count, &ss);
-            if (rcb) DIE("is3d_sample_binned failed (%d): %s", rcb, is3d_last_error());
+            // anisotropic hydro: a device list the user spelled out shards the cells; without one the first device samples alone
+            const int rcb = vah_bin_on_device
+                                ? (rd.named ? is3d_sample_binned_vah_multi(&vc, &sp, &vt, &si, &opts, rd.list.data(), (int32_t)rd.list.size(), &bins, &hist, &count, &ss)
+                                            : is3d_sample_binned_vah(&vc, &sp, &vt, &si, &opts, &bins, &hist, &count, &ss))
+                                : is3d_sample_binned_multi(&cells, &sp, &df, &si, &opts, rd.list.empty() ? nullptr : rd.list.data(), (int32_t)rd.list.size(),
+                                                           &bins, &hist, &count, &ss);
+            if (rcb) DIE("%s failed (%d): %s", vah_bin_on_device ? "is3d_sample_binned_vah" : "is3d_sample_binned", rcb, is3d_last_error());
             double t2s = now_s();
             printf("\nMomentum sampling efficiency = %f %%\n", 100.0 * (double)ss.n_acceptances / (double)std::max<int64_t>(ss.n_momentum_samples, 1));
             if (feqmod) printf("feqmod breaks down for %lld cells\n", (long long)ss.n_cells_breakdown);
@@ -619,7 +647,8 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
             printf("particles: %lld in %d event(s); hadrons drawn %lld; cells skipped (u.dsigma <= 0): %lld\n", (long long)count, si.n_events,
                    (long long)ss.n_hadrons_drawn, (long long)ss.n_cells_skipped);
             printf("device time: prep %.3f ms, count %.3f ms, fill %.3f ms; h2d %.3f ms\n", ss.ms_prep, ss.ms_count, ss.ms_fill, ss.ms_h2d);
-            printf("binned on the device: ms_bin %.3f ms, particle workspace %lld bytes (one event batch)\n", ss.ms_bin, (long long)ss.particle_workspace_bytes);
+            if (vah_bin_on_device) printf("binned where sampled on the device: ms_bin %.3f ms (sampling and binning, one pass), no particle workspace\n", ss.ms_bin);
+            else printf("binned on the device: ms_bin %.3f ms, particle workspace %lld bytes (one event batch)\n", ss.ms_bin, (long long)ss.particle_workspace_bytes);
             printf("wall: read %.3f s, sampling %.3f s, write %.3f s\n", t1 - t0, t2s - t1, t3s - t2s);
             if (int rcp = polarization()) return rcp;
             printf("Done sampling particles. Output stored in results folder. Goodbye!\n");
