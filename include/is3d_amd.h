@@ -520,7 +520,8 @@ typedef struct {
     double ms_density;                  /* part of ms_prep: cf_sampler_density (the Gauss-Laguerre density integrals per (cell, class)) */
     double ms_poisson;                  /* part of ms_count: cf_sampler_poisson + the compaction of the emitting (event, cell) pairs */
     double ms_bin;                      /* is3d_sampler_plan_execute_binned: cf_sampler_bins over all batches (0 for the list entries);
-                                           is3d_sample_binned_vah: the fused sample-and-bin passes (ms_count = ms_fill = 0 there) */
+                                           is3d_sample_binned_vah, is3d_sample_fused: the fused sample-and-bin passes (ms_count = ms_fill = 0
+                                           there) */
     int64_t particle_workspace_bytes;   /* is3d_sampler_plan_execute_binned: the plan-owned particle workspace (one batch); 0 otherwise */
 } is3d_sampler_stats;
 
@@ -719,6 +720,36 @@ int is3d_sample_binned(const is3d_cells *cells, const is3d_species *species, con
 int is3d_sample_binned_multi(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
                              const is3d_options *opts, const int32_t *devices, int32_t n_devices, const is3d_sampler_test_bins *bins,
                              const is3d_sampler_hist *hist, int64_t *n_particles, is3d_sampler_stats *stats);
+/* The viscous sampler with its hadrons binned where they are sampled (cf_sampler_fused), in one pass and without a list: the arguments,
+ * the persistent plan and the refusals of the binned entries above.  Definition:
+ *   the histograms are those of is3d_sampler_bin_list on the list that is3d_sample_particles (is3d_sampler_plan_execute) returns for the
+ *   same arguments -- counts and yields exactly; vn_re, vn_im within one unit per entry of the dN_pT bin (device and host libm).
+ *   *n_particles = the sum of the yields = the length of that list.
+ * How: per event batch the Poisson numbers and the compaction of the emitting (event, cell) pairs as in the list route, then ONE pass,
+ * thread <-> pair, that replays the list route's streams and loop (df_mode 1-4, fast, include_baryon) and gives every kept hadron's
+ * is3d_particle, built in registers, to the rule of csrc/cf_sampler_bins.h.  The adds are the 64-bit integer adds of cf_sampler_bins, so the
+ * result depends neither on the order of arrival nor on bins->kernel_form (0 = workgroup-private histograms in LDS where they fit 64 KiB,
+ * 1 = global atomics, 2 = private or IS3D_EINVAL), batch_events, first_cell sharding or the device count, bit for bit.
+ * Device memory: the histograms (8 B per word of is3d_sampler_hist), the per-cell records and tables of the plan, and 9 B per (event, cell)
+ * pair of ONE batch (Poisson number, emit flag, pair list; batches of <= 2^25 pairs, or batch_events events) with the compaction's temporary
+ * storage.  Nothing is sized by the number of hadrons: no particle workspace, no counts, no offsets, no scan.
+ * stats: ms_bin is the time of the fused passes; ms_count, ms_fill and particle_workspace_bytes are 0; the rest is the list route's.
+ * A plan may serve is3d_sampler_plan_execute, _execute_binned and _execute_fused in any order.  Refused with IS3D_EINVAL before any device
+ * use, in the order of the binned entries: a NULL, n_events < 1, bad bins, a NULL histogram array, kernel_form outside 0..2, kernel_form = 2
+ * on a block that does not fit the LDS (beside the three words of the run-wide tallies).  IS3D_EDOMAIN: a cell outside the coefficient
+ * table (named by its global index, as is3d_sample_binned does), a dN_pT bin above IS3D_SAMPLER_VN_MAX_COUNT. */
+int is3d_sampler_plan_execute_fused(is3d_sampler_plan *plan, const is3d_cells *cells_dev, const double *x_dev, const double *y_dev,
+                                    int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
+                                    const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist_host, int64_t *n_particles,
+                                    is3d_sampler_stats *stats);
+/* host-pointer one-shot (create + upload + execute_fused + destroy), and the same on the shard scaffold of is3d_sample_binned_multi: the
+ * integer histograms are added on the host, so the result equals the single-device one bit for bit. */
+int is3d_sample_fused(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                      const is3d_options *opts, const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
+                      is3d_sampler_stats *stats);
+int is3d_sample_fused_multi(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                            const is3d_options *opts, const int32_t *devices, int32_t n_devices, const is3d_sampler_test_bins *bins,
+                            const is3d_sampler_hist *hist, int64_t *n_particles, is3d_sampler_stats *stats);
 /* The anisotropic-hydro sampler with its hadrons binned where they are sampled (cf_sampler_vah_bin), in one pass and without a list.  As for
  * is3d_sample_particles_vah the reference has nothing to match, so THIS is the definition:
  *   the histograms are those of is3d_sampler_bin_list on the list that is3d_sample_particles_vah returns for the same arguments -- counts

@@ -118,6 +118,7 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_pdg_read_decays", "is3d_decay_q_factor", "is3d_resonance_decays", "is3d_decay_plan_create", "is3d_decay_plan_output_size",
            "is3d_decay_plan_execute", "is3d_decay_plan_destroy", "is3d_write_results_decays",
            "is3d_sampler_bin_list", "is3d_write_sampler_tests_binned", "is3d_sampler_plan_execute_binned", "is3d_sample_binned", "is3d_sample_binned_multi",
+           "is3d_sampler_plan_execute_fused", "is3d_sample_fused", "is3d_sample_fused_multi",
            "is3d_sampler_bin_list_device", "is3d_df_generate", "is3d_df_tables_write",
            "is3d_smooth_spectra_vah_multi", "is3d_vah_plan_observables",
            "is3d_spacetime_distributions_vah", "is3d_vah_plan_execute_spacetime",
@@ -1683,7 +1684,7 @@ class SamplerPlan:
         d["n_particles"] = int(cnt.value)
         return int(cnt.value), d
 
-    def execute_binned(self, n_cells, dev_ptrs, n_events, seed, bins, n_species, x_ptr=0, y_ptr=0, first_cell=0, batch_events=0):
+    def execute_binned(self, n_cells, dev_ptrs, n_events, seed, bins, n_species, x_ptr=0, y_ptr=0, first_cell=0, batch_events=0, _fused=False):
         """is3d_sampler_plan_execute_binned: -> (dict of int64 histograms, stats); n_species: the length of the plan's species list."""
         cs = Cells()
         cs.n_cells = int(n_cells)
@@ -1694,13 +1695,19 @@ class SamplerPlan:
         h, out = _hist_arrays(bins, n_events, n_species)
         cnt, st = C.c_int64(0), SamplerStats()
         L = load()
-        L.is3d_sampler_plan_execute_binned.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32,
-                                                       C.POINTER(SamplerTestBins), C.POINTER(SamplerHist), C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
-        _check(L.is3d_sampler_plan_execute_binned(self._h, C.byref(cs), C.c_void_p(int(x_ptr) or None), C.c_void_p(int(y_ptr) or None), int(n_events),
-                                                  int(seed), int(first_cell), int(batch_events), C.byref(b), C.byref(h), C.byref(cnt), C.byref(st)))
+        fn = L.is3d_sampler_plan_execute_fused if _fused else L.is3d_sampler_plan_execute_binned
+        fn.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32,
+                       C.POINTER(SamplerTestBins), C.POINTER(SamplerHist), C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
+        _check(fn(self._h, C.byref(cs), C.c_void_p(int(x_ptr) or None), C.c_void_p(int(y_ptr) or None), int(n_events),
+                  int(seed), int(first_cell), int(batch_events), C.byref(b), C.byref(h), C.byref(cnt), C.byref(st)))
         d = st.as_dict()
         d["n_particles"] = int(cnt.value)
         return out, d
+
+    def execute_fused(self, n_cells, dev_ptrs, n_events, seed, bins, n_species, x_ptr=0, y_ptr=0, first_cell=0, batch_events=0):
+        """is3d_sampler_plan_execute_fused: execute_binned's arguments and result, every hadron binned where it is sampled (no list, no
+        particle workspace: stats["particle_workspace_bytes"] == 0)."""
+        return self.execute_binned(n_cells, dev_ptrs, n_events, seed, bins, n_species, x_ptr, y_ptr, first_cell, batch_events, _fused=True)
 
     def close(self):
         if self._h:
@@ -1903,10 +1910,11 @@ def write_sampler_tests_binned(results_dir, bins, n_events, mc_id, hist, mean_yi
 
 
 def sample_binned(cells, species, df, gla, bins, opts=None, n_events=1, seed=1, y_cut=0.5, first_cell=0, fq=None, fast=0, T_avg=0.0,
-                  T_avg_switch=0.0, batch_events=0, muB_avg=0.0, devices=None):
+                  T_avg_switch=0.0, batch_events=0, muB_avg=0.0, devices=None, _fused=False):
     """is3d_sample_binned (devices = None) | is3d_sample_binned_multi: the sampler with every event batch binned on the device and dropped.
     Arguments as sample_particles; bins: dict of is3d_sampler_test_bins fields.  Returns (dict of int64 histograms, stats dict)."""
     L = load()
+    one, multi = (L.is3d_sample_fused, L.is3d_sample_fused_multi) if _fused else (L.is3d_sample_binned, L.is3d_sample_binned_multi)
     cs, sps, ds, si, os_, _held = _pack_sampler(cells, species, df, gla, opts, n_events, seed, y_cut, first_cell, fq, fast, T_avg, T_avg_switch,
                                                 batch_events, muB_avg)
     b = _pack_bins(bins)
@@ -1915,15 +1923,15 @@ def sample_binned(cells, species, df, gla, bins, opts=None, n_events=1, seed=1, 
     cnt = C.c_int64(0)
     if devices is not None:
         dv, nd, _ = _pack_devices(devices)
-        L.is3d_sample_binned_multi.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options),
+        multi.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options),
                                                C.POINTER(C.c_int32), C.c_int32, C.POINTER(SamplerTestBins), C.POINTER(SamplerHist),
                                                C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
-        rc = L.is3d_sample_binned_multi(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), dv, nd, C.byref(b), C.byref(h),
+        rc = multi(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), dv, nd, C.byref(b), C.byref(h),
                                         C.byref(cnt), C.byref(st))
     else:
-        L.is3d_sample_binned.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options),
+        one.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options),
                                          C.POINTER(SamplerTestBins), C.POINTER(SamplerHist), C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
-        rc = L.is3d_sample_binned(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), C.byref(b), C.byref(h), C.byref(cnt), C.byref(st))
+        rc = one(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), C.byref(b), C.byref(h), C.byref(cnt), C.byref(st))
     _check(rc)
     d = st.as_dict()
     d["n_particles"] = int(cnt.value)
@@ -1933,6 +1941,17 @@ def sample_binned(cells, species, df, gla, bins, opts=None, n_events=1, seed=1, 
 def sample_binned_multi(cells, species, df, gla, bins, opts=None, devices=(0,), **kw):
     """is3d_sample_binned_multi: one cell shard per entry of devices (an ordinal may repeat); the result equals sample_binned's bit for bit."""
     return sample_binned(cells, species, df, gla, bins, opts, devices=list(devices), **kw)
+
+
+def sample_fused(cells, species, df, gla, bins, opts=None, **kw):
+    """is3d_sample_fused (devices = None) | is3d_sample_fused_multi: sample_binned's arguments and result with every hadron binned where it
+    is sampled -- one pass per event batch, no list, no particle workspace.  Counts and yields equal sample_binned's; so do the harmonics."""
+    return sample_binned(cells, species, df, gla, bins, opts, _fused=True, **kw)
+
+
+def sample_fused_multi(cells, species, df, gla, bins, opts=None, devices=(0,), **kw):
+    """is3d_sample_fused_multi: one cell shard per entry of devices (an ordinal may repeat); the result equals sample_fused's bit for bit."""
+    return sample_fused(cells, species, df, gla, bins, opts, devices=list(devices), **kw)
 
 
 def sample_binned_vah(cells, species, gla, bins, opts=None, tab=None, n_events=1, seed=1, y_cut=0.5, first_cell=0, batch_events=0, devices=None,

@@ -1345,12 +1345,15 @@ extern "C" int is3d_sample_binned_vah_multi(const is3d_vah_cells *cells, const i
     return IS3D_OK;
 }
 
-// is3d_sample_binned over the same shards: every shard bins its own hadrons on its device, the integer histograms are added here --
-// an exact sum, so the result is the single-device one bit for bit
-extern "C" int is3d_sample_binned_multi(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df,
-                                        const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices, int32_t n_devices,
-                                        const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
-                                        is3d_sampler_stats *stats)
+// is3d_sample_binned | is3d_sample_fused over the same shards: every shard bins its own hadrons on its device, the integer histograms are
+// added here -- an exact sum, so the result is the single-device one bit for bit
+namespace {
+// one: is3d_sample_binned | is3d_sample_fused
+using BinnedOneShot = int (*)(const is3d_cells *, const is3d_species *, const is3d_df_tables *, const is3d_sampler_inputs *, const is3d_options *,
+                              const is3d_sampler_test_bins *, const is3d_sampler_hist *, int64_t *, is3d_sampler_stats *);
+int sample_binned_shards(BinnedOneShot one, const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df,
+                         const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices, int32_t n_devices,
+                         const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles, is3d_sampler_stats *stats)
 {
     if (!cells || !species || !in || !opts || !bins || !hist || !n_particles) return fail(IS3D_EINVAL, "null argument");
     *n_particles = 0;
@@ -1362,7 +1365,7 @@ extern "C" int is3d_sample_binned_multi(const is3d_cells *cells, const is3d_spec
     if (n_devices == 1) {
         is3d_options o = *opts;
         o.device = dev[0];
-        return is3d_sample_binned(cells, species, df, in, &o, bins, hist, n_particles, stats);
+        return one(cells, species, df, in, &o, bins, hist, n_particles, stats);
     }
     if (in->n_events < 1 || species->n < 1 || bins->y_bins < 1 || bins->eta_bins < 1 || bins->pT_bins < 1 || bins->tau_bins < 1 || bins->r_bins < 1)
         return fail(IS3D_EINVAL, "n_events, the species count and every bin count must be >= 1");
@@ -1386,7 +1389,7 @@ extern "C" int is3d_sample_binned_multi(const is3d_cells *cells, const is3d_spec
         int64_t *part[8];
         for (int a = 0; a < 8; a++) { part[a] = q; q += len[a]; }
         const is3d_sampler_hist hs{part[0], part[1], part[2], part[3], part[4], part[5], part[6], part[7]};
-        return is3d_sample_binned(&s.c, species, df, &s.si, &s.o, bins, &hs, &s.count, &s.st);
+        return one(&s.c, species, df, &s.si, &s.o, bins, &hs, &s.count, &s.st);
     });
     for (int a = 0; a < 8; a++) memset(out[a], 0, (size_t)len[a] * sizeof(int64_t));
     if (int rc = sampler_totals(sh, n_particles, stats)) return rc;
@@ -1403,6 +1406,29 @@ extern "C" int is3d_sample_binned_multi(const is3d_cells *cells, const is3d_spec
             return fail(IS3D_EDOMAIN, "dN_pT bin %lld holds %lld hadrons: the fixed-point harmonic sums are exact up to %lld per bin", (long long)j,
                         (long long)hist->dN_pT[j], (long long)IS3D_SAMPLER_VN_MAX_COUNT);
     return IS3D_OK;
+}
+}  // namespace
+
+extern "C" int is3d_sample_binned_multi(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df,
+                                        const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices, int32_t n_devices,
+                                        const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
+                                        is3d_sampler_stats *stats)
+{
+    return sample_binned_shards(is3d_sample_binned, cells, species, df, in, opts, devices, n_devices, bins, hist, n_particles, stats);
+}
+
+// is3d_sample_fused over the same shards: the same exact sum of integer histograms
+extern "C" int is3d_sample_fused_multi(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df,
+                                       const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices, int32_t n_devices,
+                                       const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
+                                       is3d_sampler_stats *stats)
+{
+    // (every refusal of the bins before the device list is looked at: none of them needs a device)
+    if (!cells || !species || !in || !opts || !bins || !hist || !n_particles) return fail(IS3D_EINVAL, "null argument");
+    *n_particles = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (int rc = is3d::sampler_check_fused_args(bins, hist, in->n_events, std::max<int32_t>(species->n, 1))) return rc;
+    return sample_binned_shards(is3d_sample_fused, cells, species, df, in, opts, devices, n_devices, bins, hist, n_particles, stats);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -27,6 +27,7 @@
 //                       writes the particles -- the list comes out ordered by (event, cell, draw), no atomics, no sort.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
+#include <limits.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -252,23 +253,16 @@ cf_sampler_poisson(SamplerParams p, const SamplerCell *__restrict__ cellrec, int
     emits[idx] = N > 0;
 }
 
-// one emitting (event, cell) pair; tallies = {momentum samples, acceptances, hadrons drawn} of this thread (count pass)
-template <bool FILL>
-__device__ __forceinline__ void sampler_thread(const SamplerParams &p, const SamplerSpecies &sp, const SamplerCell *__restrict__ cellrec,
-                                               const double *__restrict__ GT, const double *__restrict__ GT2,
-                                               const double *__restrict__ GT3, int event0, const int32_t *__restrict__ active, int64_t n_active, const int32_t *__restrict__ n_drawn,
-                                               int64_t *__restrict__ counts, const int64_t *__restrict__ offsets, int64_t base,
-                                               is3d_particle *__restrict__ particles, int64_t capacity, unsigned long long (&tally)[3])
+// one emitting (event, cell) pair: the ONE piece of source the count, the fill and the fused bin pass run.  ic is the pair's cell, ievent its
+// event; every kept hadron goes to keep() as the is3d_particle of the list.  Returns the number kept; tally[] gets the pair's momentum
+// samples, acceptances and hadrons drawn.
+template <class Keep>
+__device__ __forceinline__ long sample_pair(const SamplerParams &p, const SamplerSpecies &sp, const SamplerCell *__restrict__ cellrec,
+                                            const double *__restrict__ GT, const double *__restrict__ GT2, const double *__restrict__ GT3,
+                                            int ievent, int64_t ic, long N_hadrons, Keep &keep, unsigned long long (&tally)[3])
 {
-    const int64_t ia = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // position in the list of emitting (event, cell) pairs
-    if (ia >= n_active) return;
-    if (FILL && offsets[ia + 1] == offsets[ia]) return;                    // pass 1 kept nothing here: nothing to replay
-    const int64_t idx = active[ia];                                         // event-major: (event - event0) * n_cells + cell
-    const int ievent = event0 + (int)(idx / p.n_cells);
-    const int64_t ic = idx % p.n_cells;
     const SamplerCell &c = cellrec[ic];
     const uint32_t gcell = (uint32_t)(p.first_cell + ic);
-    const long N_hadrons = n_drawn[idx];                                    // cf_sampler_poisson (stream 0)
     Rng g_type, g_momentum, g_keep, g_rapidity;
     g_type.init(p.seed, 1, gcell, (uint32_t)ievent);
     g_momentum.init(p.seed, 2, gcell, (uint32_t)ievent);
@@ -278,7 +272,6 @@ __device__ __forceinline__ void sampler_thread(const SamplerParams &p, const Sam
     const bool linear = p.df_mode <= 2 || c.breakdown != 0.0;
     const double sinheta = sinh(c.eta), cosheta = sqrt(1.0 + sinheta * sinheta);   // :888-889
     long kept = 0, samples = 0, acceptances = 0;
-    int64_t slot = FILL ? base + offsets[ia] : 0;
     for (long ih = 0; ih < N_hadrons; ih++) {
         const double ut_ = g_type.uniform() * c.dn_sum;
         const int chosen = choose_species(p, sp, c, gt, gt2, gt3, ic, ut_);
@@ -339,22 +332,18 @@ __device__ __forceinline__ void sampler_thread(const SamplerParams &p, const Sam
             pz = c.tau * pn * ch + ptau * sh;
             Elab = sqrt(mass_squared + plx * plx + ply * ply + pz * pz);
         }
-        if (FILL && slot < capacity) {
-            is3d_particle o;
-            o.cell = p.first_cell + ic; o.event = ievent; o.species = chosen;
-            o.tau = c.tau; o.x = c.x; o.y = c.y; o.eta = eta; o.t = c.tau * ch; o.z = c.tau * sh;
-            o.E = Elab; o.px = plx; o.py = ply; o.pz = pz;
-            particles[slot] = o;
-        }
-        slot++;
+        is3d_particle o;
+        o.cell = p.first_cell + ic; o.event = ievent; o.species = chosen;
+        o.tau = c.tau; o.x = c.x; o.y = c.y; o.eta = eta; o.t = c.tau * ch; o.z = c.tau * sh;
+        o.E = Elab; o.px = plx; o.py = ply; o.pz = pz;
+        keep(o);
         kept++;
     }
-    if (!FILL) {
-        counts[ia] = kept;
-        tally[0] = (unsigned long long)samples; tally[1] = (unsigned long long)acceptances; tally[2] = (unsigned long long)N_hadrons;
-    }
+    tally[0] += (unsigned long long)samples; tally[1] += (unsigned long long)acceptances; tally[2] += (unsigned long long)N_hadrons;
+    return kept;
 }
 
+// thread <-> emitting (event, cell) pair: the count pass (counts[] and the run-wide tallies) and the fill pass of the list route
 template <bool FILL>
 __global__ void __launch_bounds__(128)
 cf_sampler_run(SamplerParams p, SamplerSpecies sp, const SamplerCell *__restrict__ cellrec, const double *__restrict__ GT,
@@ -363,8 +352,66 @@ cf_sampler_run(SamplerParams p, SamplerSpecies sp, const SamplerCell *__restrict
                is3d_particle *__restrict__ particles, int64_t capacity)
 {
     unsigned long long tally[3] = {0ULL, 0ULL, 0ULL};
-    sampler_thread<FILL>(p, sp, cellrec, GT, GT2, GT3, event0, active, n_active, n_drawn, counts, offsets, base, particles, capacity, tally);
+    const int64_t ia = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // position in the list of emitting (event, cell) pairs
+    if (ia < n_active && !(FILL && offsets[ia + 1] == offsets[ia])) {       // (fill: pass 1 kept nothing here, nothing to replay)
+        const int64_t idx = active[ia];                                     // event-major: (event - event0) * n_cells + cell
+        const int ievent = event0 + (int)(idx / p.n_cells);
+        const int64_t ic = idx % p.n_cells;
+        const long N_hadrons = n_drawn[idx];                                // cf_sampler_poisson (stream 0)
+        if (FILL) {
+            SamplerKeepFill keep{particles, base + offsets[ia], capacity};
+            sample_pair(p, sp, cellrec, GT, GT2, GT3, ievent, ic, N_hadrons, keep, tally);
+        } else {
+            SamplerKeepCount keep;
+            counts[ia] = sample_pair(p, sp, cellrec, GT, GT2, GT3, ievent, ic, N_hadrons, keep, tally);
+        }
+    }
     if (!FILL) sampler_tally(p, tally);
+}
+
+// The fused pass (is3d_sampler_plan_execute_fused): the count pass's threads, streams and loop, every kept hadron added straight into the
+// histograms of cf_sampler_bins (the same rule, cf_sampler_bins.h, on the same is3d_particle the fill pass would store) -- no list, so no
+// counts, offsets, scan or particle workspace.  Every add is a 64-bit integer, so the histograms are those of the list route bit for bit
+// whatever the order of arrival.
+//   PRIVATE: the whole block lives in dynamic LDS (ds_add_u64), at most kFusedBinPrivateBlocks workgroups walk the pair list grid-stride
+//            and each flushes its non-zero words once with global adds
+//   else:    every add goes straight to the global block (305 species: 305 x 1800 words)
+// Per-event yields: sampler_yield_runs after the rejection loop, with the wave reconverged; lanes past n_active take part with event
+// INT_MAX and kept = 0.  The trip count is the same for every thread of a workgroup: the wave operations see whole waves and the barriers
+// every thread; none of either sits inside the per-hadron loop.
+template <bool PRIVATE>
+__global__ void __launch_bounds__(kFusedBinThreads, 2)
+cf_sampler_fused(SamplerParams p, SamplerSpecies sp, const SamplerCell *__restrict__ cellrec, const double *__restrict__ GT,
+                 const double *__restrict__ GT2, const double *__restrict__ GT3, int event0, const int32_t *__restrict__ active, int64_t n_active,
+                 const int32_t *__restrict__ n_drawn, SamplerBinArgs a, unsigned long long *__restrict__ hist,
+                 unsigned long long *__restrict__ yield)
+{
+    extern __shared__ unsigned long long priv[];
+    if (PRIVATE) {
+        for (int64_t j = threadIdx.x; j < a.l.total; j += kFusedBinThreads) priv[j] = 0ULL;
+        __syncthreads();
+    }
+    SamplerKeepBin keep{a, PRIVATE ? priv : hist};
+    unsigned long long tally[3] = {0ULL, 0ULL, 0ULL};
+    for (int64_t i0 = (int64_t)blockIdx.x * kFusedBinThreads; i0 < n_active; i0 += (int64_t)gridDim.x * kFusedBinThreads) {
+        const int64_t ia = i0 + threadIdx.x;
+        int ev = INT_MAX;
+        long long kept = 0;
+        if (ia < n_active) {
+            const int64_t idx = active[ia];
+            ev = event0 + (int)(idx / p.n_cells);
+            kept = sample_pair(p, sp, cellrec, GT, GT2, GT3, ev, idx % p.n_cells, (long)n_drawn[idx], keep, tally);
+        }
+        sampler_yield_runs(ev, kept, yield);
+    }
+    sampler_tally(p, tally);
+    if (PRIVATE) {
+        __syncthreads();
+        for (int64_t j = threadIdx.x; j < a.l.total; j += kFusedBinThreads) {
+            const unsigned long long v = priv[j];
+            if (v) atomicAdd(&hist[j], v);
+        }
+    }
 }
 
 }  // namespace is3d
@@ -393,7 +440,7 @@ struct is3d_sampler_plan {
     DevMem d_drawn, d_emits, d_active, d_nactive, d_cdf;
     DevMem d_particles, d_hist;             // is3d_sampler_plan_execute_binned: one batch of particles; the histograms, then the yields
     int64_t cap_cells = 0, cap_bt = 0;      // what the workspaces above were sized for
-    int64_t cap_list = 0;                   // ... d_counts and d_offsets, which a fused binned run (SamplerVariant::bin) never has
+    int64_t cap_list = 0;                   // ... d_counts and d_offsets, which a fused binned run (SamplerVariant::bin, BinRun::fused) never has
     size_t tmp_select = 0, tmp_scan = 0;
     int64_t cap_particles = 0, cap_hist = 0;
     size_t tmp_bytes = 0;
@@ -689,7 +736,8 @@ extern "C" int is3d_sampler_plan_execute(is3d_sampler_plan *P, const is3d_cells 
 
 namespace {
 // the one batch loop: bin == NULL fills the caller's list (or only counts); bin != NULL fills each batch into the plan's particle workspace
-// at base 0, bins it into P->d_hist and drops it -- or, for a variant with a bin hook, samples each batch straight into P->d_hist
+// at base 0, bins it into P->d_hist and drops it -- or, for a variant with a bin hook or with bin->fused, samples each batch straight into
+// P->d_hist
 int sampler_execute(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev, int32_t n_events, uint64_t seed,
                     int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
                     int64_t *n_particles, is3d_sampler_stats *stats)
@@ -710,7 +758,30 @@ int sampler_execute(is3d_sampler_plan *P, const is3d_cells *cells, const double 
     return sampler_batches(P, nullptr, n, x_dev, y_dev, n_events, seed, first_cell, batch_events, particles_dev, capacity, bin, n_particles, stats);
 }
 
-// v == NULL: cf_sampler_cells and cf_sampler_run on P->p.cells; else the variant's kernels (cf_sampler_common.h)
+// the fused pass of the viscous route: one launch per event batch.  Private form: at most kFusedBinPrivateBlocks workgroups, each walking
+// the pair list grid-stride; global form: one trip per thread.  (sampler_tally keeps three words of static LDS beside the block: form 0 on
+// a block that leaves no room for them takes the global form, and form 2 is refused there.)
+bool fused_lds_fits(const is3d::SamplerHistLayout &l)
+{
+    return is3d::sampler_bins_lds_fits(l) && (size_t)(l.total + 3) * sizeof(unsigned long long) <= 65536;
+}
+void fused_launch(const is3d::SamplerParams &p, const is3d::SamplerSpecies &sp, const is3d::SamplerRunArgs &a, const double *GT2, const double *GT3,
+                  const BinRun &b, unsigned long long *hist_dev, unsigned long long *yield_dev)
+{
+    const is3d::SamplerBinArgs ba{b.bins, b.widths, b.layout, sp.npart};
+    const bool priv = b.bins.kernel_form == 2 || (b.bins.kernel_form == 0 && fused_lds_fits(b.layout));
+    const int64_t trips = (a.n_active + is3d::kFusedBinThreads - 1) / is3d::kFusedBinThreads;
+    if (priv)
+        hipLaunchKernelGGL((is3d::cf_sampler_fused<true>), dim3((unsigned)std::min<int64_t>(trips, is3d::kFusedBinPrivateBlocks)),
+                           dim3(is3d::kFusedBinThreads), (size_t)b.layout.total * sizeof(unsigned long long), nullptr, p, sp, a.rec, a.GT, GT2, GT3,
+                           a.event0, a.active, a.n_active, a.n_drawn, ba, hist_dev, yield_dev);
+    else
+        hipLaunchKernelGGL((is3d::cf_sampler_fused<false>), dim3((unsigned)trips), dim3(is3d::kFusedBinThreads), 0, nullptr, p, sp, a.rec, a.GT, GT2,
+                           GT3, a.event0, a.active, a.n_active, a.n_drawn, ba, hist_dev, yield_dev);
+}
+
+// v == NULL: cf_sampler_cells and cf_sampler_run (or, for a fused binned run, cf_sampler_fused) on P->p.cells; else the variant's kernels
+// (cf_sampler_common.h)
 int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t n, const double *x_dev, const double *y_dev, int32_t n_events,
                     uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
                     int64_t *n_particles, is3d_sampler_stats *stats)
@@ -746,7 +817,7 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t
         P->cap_cells = n;
     }
     // fused: one pass per batch samples and bins; the counts, the offsets and the scan exist only to put a list in order
-    const bool fused = v && v->bin && bin;
+    const bool fused = bin && (v ? v->bin != nullptr : bin->fused != 0);
     if (bt > P->cap_bt) {
         HIP_TRY(P->d_drawn.alloc((size_t)bt * sizeof(int32_t)));
         HIP_TRY(P->d_emits.alloc((size_t)bt));
@@ -807,9 +878,10 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t
             HIP_TRY(hipEventRecord(ev[8], nullptr));
             if (n_active > 0) {
                 unsigned long long *hist_dev = P->d_hist.as<unsigned long long>();
-                v->bin(v->ctx, p, sp, is3d::SamplerRunArgs{d_rec.as<is3d::SamplerCell>(), d_GT.as<double>(), e0, d_active.as<int32_t>(), (int64_t)n_active,
-                                                            d_drawn.as<int32_t>(), nullptr, nullptr, 0, nullptr, 0},
-                       *bin, hist_dev, hist_dev + bin->layout.total);
+                const is3d::SamplerRunArgs a{d_rec.as<is3d::SamplerCell>(), d_GT.as<double>(), e0, d_active.as<int32_t>(), (int64_t)n_active,
+                                             d_drawn.as<int32_t>(), nullptr, nullptr, 0, nullptr, 0};
+                if (v) v->bin(v->ctx, p, sp, a, *bin, hist_dev, hist_dev + bin->layout.total);
+                else fused_launch(p, sp, a, d_GT2.as<double>(), d_GT3.as<double>(), *bin, hist_dev, hist_dev + bin->layout.total);
                 HIP_TRY(hipGetLastError());
             }
         } else if (n_active > 0) {
@@ -1071,6 +1143,15 @@ int is3d::sampler_check_bin_args(const is3d_sampler_test_bins *bins, const is3d_
     return IS3D_OK;
 }
 
+int is3d::sampler_check_fused_args(const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int32_t n_events, int32_t n_species)
+{
+    if (int rc = check_bin_args(bins, hist, n_events)) return rc;
+    const SamplerHistLayout l = sampler_hist_layout(*bins, n_species);
+    if (bins->kernel_form == 2 && !fused_lds_fits(l))
+        return set_error(IS3D_EINVAL, "kernel_form = 2: %lld histogram words do not fit the LDS", (long long)l.total);
+    return IS3D_OK;
+}
+
 int is3d::sampler_variant_execute_binned(is3d_sampler_plan *P, const SamplerVariant &v, int64_t n_cells, const double *x_dev, const double *y_dev,
                                          int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
                                          const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
@@ -1080,7 +1161,7 @@ int is3d::sampler_variant_execute_binned(is3d_sampler_plan *P, const SamplerVari
     if (stats) memset(stats, 0, sizeof *stats);
     if (!v.bin) return set_error(IS3D_EINVAL, "this sampler variant has no fused bin pass");
     if (n_cells < 0 || n_cells + first_cell > 0xffffffffLL) return set_error(IS3D_EINVAL, "cell indices must fit 32 bits for the counter-based streams");
-    const BinRun br{*bins, sampler_bin_widths(*bins), sampler_hist_layout(*bins, P->sp.npart)};
+    const BinRun br{*bins, sampler_bin_widths(*bins), sampler_hist_layout(*bins, P->sp.npart), 0};
     const HistParts parts = hist_parts(*hist, br.layout);
     const int64_t words = br.layout.total + n_events;
     if (int rc = hist_begin(P, parts, hist, n_events, words, n_cells > 0)) return rc;
@@ -1097,10 +1178,11 @@ int is3d::sampler_variant_execute_binned(is3d_sampler_plan *P, const SamplerVari
     return hist_check_counts(parts, hist);
 }
 
-extern "C" int is3d_sampler_plan_execute_binned(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev,
-                                                int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
-                                                const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
-                                                is3d_sampler_stats *stats)
+namespace {
+// is3d_sampler_plan_execute_binned (fused = false) | is3d_sampler_plan_execute_fused
+int plan_execute_binned(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev, int32_t n_events, uint64_t seed,
+                        int64_t first_cell, int32_t batch_events, const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist,
+                        int64_t *n_particles, is3d_sampler_stats *stats, bool fused)
 {
     using is3d::set_error;
     if (!P || !cells || !n_particles) return set_error(IS3D_EINVAL, "null argument");
@@ -1108,8 +1190,8 @@ extern "C" int is3d_sampler_plan_execute_binned(is3d_sampler_plan *P, const is3d
     if (stats) memset(stats, 0, sizeof *stats);
     if (int rc = check_bin_args(bins, hist, n_events)) return rc;
     const int S = P->sp.npart;
-    BinRun br{*bins, is3d::sampler_bin_widths(*bins), is3d::sampler_hist_layout(*bins, S)};
-    if (bins->kernel_form == 2 && !is3d::sampler_bins_lds_fits(br.layout))
+    BinRun br{*bins, is3d::sampler_bin_widths(*bins), is3d::sampler_hist_layout(*bins, S), fused ? 1 : 0};
+    if (bins->kernel_form == 2 && !(fused ? fused_lds_fits(br.layout) : is3d::sampler_bins_lds_fits(br.layout)))
         return set_error(IS3D_EINVAL, "kernel_form = 2: %lld histogram words do not fit the LDS", (long long)br.layout.total);
     const HistParts parts = hist_parts(*hist, br.layout);
     const int64_t words = br.layout.total + n_events;
@@ -1117,25 +1199,64 @@ extern "C" int is3d_sampler_plan_execute_binned(is3d_sampler_plan *P, const is3d
     if (int rc = sampler_execute(P, cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, nullptr, 0, &br, n_particles, stats)) return rc;
     if (cells->n_cells == 0) return IS3D_OK;
     if (int rc = hist_end(P, parts, hist, n_events, words)) return rc;
+    if (fused)   // no list was counted: the hadrons are the sum of the yields
+        for (int32_t e = 0; e < n_events; e++) *n_particles += hist->yield[e];
     return hist_check_counts(parts, hist);
 }
+}  // namespace
 
-// the host-pointer entry: plan + upload + execute_binned
-extern "C" int is3d_sample_binned(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
-                                  const is3d_options *opts, const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist,
-                                  int64_t *n_particles, is3d_sampler_stats *stats)
+extern "C" int is3d_sampler_plan_execute_binned(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev,
+                                                int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
+                                                const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
+                                                is3d_sampler_stats *stats)
+{
+    return plan_execute_binned(P, cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, bins, hist, n_particles, stats, false);
+}
+
+// every hadron binned where it is sampled (cf_sampler_fused): Poisson, select and one launch per event batch
+extern "C" int is3d_sampler_plan_execute_fused(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev,
+                                               int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
+                                               const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
+                                               is3d_sampler_stats *stats)
+{
+    return plan_execute_binned(P, cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, bins, hist, n_particles, stats, true);
+}
+
+namespace {
+// the host-pointer entries: plan + upload + execute_binned | execute_fused
+int sample_binned(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                  const is3d_options *opts, const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
+                  is3d_sampler_stats *stats, bool fused)
 {
     using is3d::set_error;
     if (!cells || !species || !df || !in || !opts || !n_particles) return set_error(IS3D_EINVAL, "null argument");
     *n_particles = 0;
     if (stats) memset(stats, 0, sizeof *stats);
     if (int rc = check_bin_args(bins, hist, in->n_events)) return rc;
+    // (the fused entry refuses a private form that cannot run with the bins, before the plan: no refusal of its own needs a device)
+    if (fused && species->n >= 1)
+        if (int rc = is3d::sampler_check_fused_args(bins, hist, in->n_events, species->n)) return rc;
     StagedRun r;
     if (int rc = stage_run(r, cells, species, df, in, opts)) return rc;
-    const int rc = is3d_sampler_plan_execute_binned(r.P, &r.dc, r.xy[0], r.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events, bins,
-                                                    hist, n_particles, stats);
+    const int rc = plan_execute_binned(r.P, &r.dc, r.xy[0], r.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events, bins, hist,
+                                       n_particles, stats, fused);
     if (stats) stats->ms_h2d = r.ms_h2d;
     return rc;
+}
+}  // namespace
+
+extern "C" int is3d_sample_binned(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                                  const is3d_options *opts, const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist,
+                                  int64_t *n_particles, is3d_sampler_stats *stats)
+{
+    return sample_binned(cells, species, df, in, opts, bins, hist, n_particles, stats, false);
+}
+
+extern "C" int is3d_sample_fused(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                                 const is3d_options *opts, const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist,
+                                 int64_t *n_particles, is3d_sampler_stats *stats)
+{
+    return sample_binned(cells, species, df, in, opts, bins, hist, n_particles, stats, true);
 }
 
 // a caller's list through the same kernel: upload, sampler_bins_launch, download as is3d_sampler_plan_execute_binned does

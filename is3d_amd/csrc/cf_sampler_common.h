@@ -5,6 +5,7 @@
 // hipCUB compaction and scan: cf_sampler.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 
 #include <cmath>
@@ -302,6 +303,76 @@ __device__ __forceinline__ void sampler_tally(const SamplerParams &p, const unsi
     if (threadIdx.x < 3 && blk[threadIdx.x]) atomicAdd(&p.status[2 + threadIdx.x], blk[threadIdx.x]);
 }
 
+// ---- what a pass does with a kept hadron: the one thing in which count, fill and bin differ (sample_pair of cf_sampler.hip,
+// vah_sample_pair of cf_sampler_vah.hip) ----
+struct SamplerKeepCount {
+    __device__ __forceinline__ void operator()(const is3d_particle &) {}
+};
+struct SamplerKeepFill {
+    is3d_particle *__restrict__ particles;
+    int64_t slot, capacity;
+    __device__ __forceinline__ void operator()(const is3d_particle &o)
+    {
+        if (slot < capacity) particles[slot] = o;
+        slot++;
+    }
+};
+struct SamplerBinArgs {
+    is3d_sampler_test_bins b;
+    SamplerBinWidths w;
+    SamplerHistLayout l;
+    int n_species;
+};
+// the adds of cf_sampler_bins (cf_sampler_bins.hip) for one particle, into the workgroup's LDS block or the global one: 64-bit integer atomics
+struct SamplerKeepBin {
+    const SamplerBinArgs &a;
+    unsigned long long *h;
+    __device__ __forceinline__ void operator()(const is3d_particle &q)
+    {
+        const SamplerBinIndex k = sampler_bin_particle(a.b, a.w, q);
+        const int64_t s = q.species;
+        if (k.iyp >= 0) atomicAdd(&h[a.l.dy + s * a.b.y_bins + k.iyp], 1ULL);
+        if (k.ieta >= 0) atomicAdd(&h[a.l.de + s * a.b.eta_bins + k.ieta], 1ULL);
+        if (k.itau >= 0) atomicAdd(&h[a.l.dt + s * a.b.tau_bins + k.itau], 1ULL);
+        if (k.ir >= 0) atomicAdd(&h[a.l.dr + s * a.b.r_bins + k.ir], 1ULL);
+        if (k.ipT >= 0) {
+            const int64_t j = s * a.b.pT_bins + k.ipT, plane = (int64_t)a.n_species * a.b.pT_bins;
+            atomicAdd(&h[a.l.dp + j], 1ULL);
+            for (int m = 0; m < IS3D_SAMPLER_VN_HARMONICS; m++) {
+                double sn, cs;
+                sincos(((double)m + 1.0) * k.phi, &sn, &cs);
+                atomicAdd(&h[a.l.vr + m * plane + j], (unsigned long long)sampler_vn_fixed(cs));   // two's complement: signed sums
+                atomicAdd(&h[a.l.vi + m * plane + j], (unsigned long long)sampler_vn_fixed(sn));
+            }
+        }
+    }
+};
+
+// The per-event yields of a fused bin pass.  The pairs are event-major, so the lanes of a wave see runs of equal events: the first lane of
+// a run (leader ballot) adds the run's kept hadrons, a segmented sum over an inclusive wave scan -- one add per distinct event per wave.
+// Called by EVERY lane of the wave, reconverged, outside any divergent loop; a lane without a pair comes with ev = INT_MAX and kept = 0.
+__device__ __forceinline__ void sampler_yield_runs(int ev, long long kept, unsigned long long *__restrict__ yield)
+{
+    const int lane = threadIdx.x & 63;
+    const int prev = __shfl_up(ev, 1);
+    const bool lead = lane == 0 || prev != ev;
+    const unsigned long long leaders = __ballot(lead);
+    long long incl = kept;                                               // inclusive scan of kept over the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const long long t = __shfl_up(incl, d);
+        if (lane >= d) incl += t;
+    }
+    const unsigned long long above = lane == 63 ? 0ULL : (leaders >> (lane + 1)) << (lane + 1);
+    const int last = (above ? __ffsll((long long)above) - 1 : 64) - 1;  // the last lane of the run that ends at the next leader
+    const long long run = __shfl(incl, last) - incl + kept;
+    if (lead && ev != INT_MAX && run) atomicAdd(&yield[ev], (unsigned long long)run);
+}
+
+// the geometry of a fused bin pass (cf_sampler_fused, cf_sampler_vah_bin)
+constexpr int kFusedBinThreads = 256;
+constexpr int kFusedBinPrivateBlocks = 768;   // workgroup-private form: at most this many flushes (three 43 KiB blocks per CU of 160 KiB LDS)
+
 // ---- host: a sampler variant inside the viscous sampler's plan and batch loop (cf_sampler.hip) ----
 // what one launch of a variant's run kernel gets: the arguments of cf_sampler_run
 struct SamplerRunArgs {
@@ -318,10 +389,13 @@ struct SamplerRunArgs {
     int64_t capacity;
 };
 // the bins of a binned run with what follows from them (is3d_sampler_plan_execute_binned, sampler_variant_execute_binned)
+// fused: the viscous route samples and bins in one pass too (cf_sampler_fused) instead of filling and binning a list per batch; a variant
+// with a bin hook always does
 struct SamplerBinRun {
     is3d_sampler_test_bins bins;
     SamplerBinWidths widths;
     SamplerHistLayout layout;
+    int fused;
 };
 // T: the DEVICE array the density integrals take as temperature; cells: writes the records (live, dn_sum, dn_tot and the running sums as
 // cf_sampler_cells does; status[0], [1]) after the density kernel, returns an IS3D code; run: the count (fill = false) or fill pass on `grid`
@@ -356,6 +430,9 @@ int sampler_variant_execute_binned(is3d_sampler_plan *P, const SamplerVariant &v
 // the bin checks of is3d_sample_binned (IS3D_EINVAL, no device use): null, bad bins, kernel_form outside 0..2, and kernel_form = 2 on a
 // histogram block of n_species species that does not fit the LDS
 int sampler_check_bin_args(const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int32_t n_events, int32_t n_species);
+// the same for the viscous fused entries (is3d_sample_fused): the private form needs room for the three tally words of sampler_tally beside
+// the block
+int sampler_check_fused_args(const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int32_t n_events, int32_t n_species);
 
 // is3d_sample_particles_vah's refusals (IS3D_EINVAL), all before any device use: also what is3d_sample_particles_vah_multi checks first
 int sampler_vah_check(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab, const is3d_sampler_inputs *in,

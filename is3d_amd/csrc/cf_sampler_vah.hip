@@ -156,51 +156,7 @@ cf_sampler_vah_cells(SamplerParams p, SamplerSpecies sp, VahSamplerCells v, cons
     out[ic] = c; extra[ic] = x;
 }
 
-// ---- what a pass does with a kept hadron: the one thing in which count, fill and bin differ ----
-struct VahKeepCount {
-    __device__ __forceinline__ void operator()(const is3d_particle &) {}
-};
-struct VahKeepFill {
-    is3d_particle *__restrict__ particles;
-    int64_t slot, capacity;
-    __device__ __forceinline__ void operator()(const is3d_particle &o)
-    {
-        if (slot < capacity) particles[slot] = o;
-        slot++;
-    }
-};
-struct VahBinArgs {
-    is3d_sampler_test_bins b;
-    SamplerBinWidths w;
-    SamplerHistLayout l;
-    int n_species;
-};
-// the adds of cf_sampler_bins (cf_sampler_bins.hip) for one particle, into the workgroup's LDS block or the global one: 64-bit integer atomics
-struct VahKeepBin {
-    const VahBinArgs &a;
-    unsigned long long *h;
-    __device__ __forceinline__ void operator()(const is3d_particle &q)
-    {
-        const SamplerBinIndex k = sampler_bin_particle(a.b, a.w, q);
-        const int64_t s = q.species;
-        if (k.iyp >= 0) atomicAdd(&h[a.l.dy + s * a.b.y_bins + k.iyp], 1ULL);
-        if (k.ieta >= 0) atomicAdd(&h[a.l.de + s * a.b.eta_bins + k.ieta], 1ULL);
-        if (k.itau >= 0) atomicAdd(&h[a.l.dt + s * a.b.tau_bins + k.itau], 1ULL);
-        if (k.ir >= 0) atomicAdd(&h[a.l.dr + s * a.b.r_bins + k.ir], 1ULL);
-        if (k.ipT >= 0) {
-            const int64_t j = s * a.b.pT_bins + k.ipT, plane = (int64_t)a.n_species * a.b.pT_bins;
-            atomicAdd(&h[a.l.dp + j], 1ULL);
-            for (int m = 0; m < IS3D_SAMPLER_VN_HARMONICS; m++) {
-                double sn, cs;
-                sincos(((double)m + 1.0) * k.phi, &sn, &cs);
-                atomicAdd(&h[a.l.vr + m * plane + j], (unsigned long long)sampler_vn_fixed(cs));   // two's complement: signed sums
-                atomicAdd(&h[a.l.vi + m * plane + j], (unsigned long long)sampler_vn_fixed(sn));
-            }
-        }
-    }
-};
-
-// one emitting (event, cell) pair, as sampler_thread of cf_sampler.hip with the VAH momentum map and weight: the ONE piece of source the
+// one emitting (event, cell) pair, as sample_pair of cf_sampler.hip with the VAH momentum map and weight: the ONE piece of source the
 // count, the fill and the bin pass run.  idx is the pair's event-major index (event - event0) * n_cells + cell; every kept hadron goes to
 // keep() as the is3d_particle of the list.  Returns the number kept; tally[] gets the pair's momentum samples, acceptances and hadrons drawn.
 template <class Keep>
@@ -287,10 +243,10 @@ cf_sampler_vah_run(SamplerParams p, SamplerSpecies sp, const SamplerCell *__rest
         const int64_t ic = idx % p.n_cells;
         const long N_hadrons = n_drawn[idx];                                // cf_sampler_poisson (stream 0)
         if (FILL) {
-            VahKeepFill keep{particles, base + offsets[ia], capacity};
+            SamplerKeepFill keep{particles, base + offsets[ia], capacity};
             vah_sample_pair(p, sp, cellrec, extra, GT, ievent, ic, N_hadrons, keep, tally);
         } else {
-            VahKeepCount keep;
+            SamplerKeepCount keep;
             counts[ia] = vah_sample_pair(p, sp, cellrec, extra, GT, ievent, ic, N_hadrons, keep, tally);
         }
     }
@@ -307,25 +263,21 @@ cf_sampler_vah_run(SamplerParams p, SamplerSpecies sp, const SamplerCell *__rest
 // reconverged, the first lane of a run adds the run's kept hadrons (a segmented sum over an inclusive wave scan) -- one add per distinct
 // event per wave and trip.  Lanes past n_active take part with event INT_MAX and kept = 0.  The trip count is the same for every thread
 // of a workgroup: the wave operations see whole waves and the barriers every thread.
-constexpr int kVahBinThreads = 256;
-constexpr int kVahBinPrivateBlocks = 768;     // workgroup-private form: at most this many flushes (three 43 KiB blocks per CU of 160 KiB LDS)
-
 template <bool PRIVATE>
-__global__ void __launch_bounds__(kVahBinThreads, 2)
+__global__ void __launch_bounds__(kFusedBinThreads, 2)
 cf_sampler_vah_bin(SamplerParams p, SamplerSpecies sp, const SamplerCell *__restrict__ cellrec, const VahCellExtra *__restrict__ extra,
                    const double *__restrict__ GT, int event0, const int32_t *__restrict__ active, int64_t n_active,
-                   const int32_t *__restrict__ n_drawn, VahBinArgs a, unsigned long long *__restrict__ hist,
+                   const int32_t *__restrict__ n_drawn, SamplerBinArgs a, unsigned long long *__restrict__ hist,
                    unsigned long long *__restrict__ yield)
 {
     extern __shared__ unsigned long long priv[];
     if (PRIVATE) {
-        for (int64_t j = threadIdx.x; j < a.l.total; j += kVahBinThreads) priv[j] = 0ULL;
+        for (int64_t j = threadIdx.x; j < a.l.total; j += kFusedBinThreads) priv[j] = 0ULL;
         __syncthreads();
     }
-    VahKeepBin keep{a, PRIVATE ? priv : hist};
+    SamplerKeepBin keep{a, PRIVATE ? priv : hist};
     unsigned long long tally[3] = {0ULL, 0ULL, 0ULL};
-    const int lane = threadIdx.x & 63;
-    for (int64_t i0 = (int64_t)blockIdx.x * kVahBinThreads; i0 < n_active; i0 += (int64_t)gridDim.x * kVahBinThreads) {
+    for (int64_t i0 = (int64_t)blockIdx.x * kFusedBinThreads; i0 < n_active; i0 += (int64_t)gridDim.x * kFusedBinThreads) {
         const int64_t ia = i0 + threadIdx.x;
         int ev = INT_MAX;
         long long kept = 0;
@@ -334,24 +286,12 @@ cf_sampler_vah_bin(SamplerParams p, SamplerSpecies sp, const SamplerCell *__rest
             ev = event0 + (int)(idx / p.n_cells);
             kept = vah_sample_pair(p, sp, cellrec, extra, GT, ev, idx % p.n_cells, (long)n_drawn[idx], keep, tally);
         }
-        const int prev = __shfl_up(ev, 1);
-        const bool lead = lane == 0 || prev != ev;
-        const unsigned long long leaders = __ballot(lead);
-        long long incl = kept;                                               // inclusive scan of kept over the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long t = __shfl_up(incl, d);
-            if (lane >= d) incl += t;
-        }
-        const unsigned long long above = lane == 63 ? 0ULL : (leaders >> (lane + 1)) << (lane + 1);
-        const int last = (above ? __ffsll((long long)above) - 1 : 64) - 1;  // the last lane of the run that ends at the next leader
-        const long long run = __shfl(incl, last) - incl + kept;
-        if (lead && ev != INT_MAX && run) atomicAdd(&yield[ev], (unsigned long long)run);
+        sampler_yield_runs(ev, kept, yield);
     }
     sampler_tally(p, tally);
     if (PRIVATE) {
         __syncthreads();
-        for (int64_t j = threadIdx.x; j < a.l.total; j += kVahBinThreads) {
+        for (int64_t j = threadIdx.x; j < a.l.total; j += kFusedBinThreads) {
             const unsigned long long v = priv[j];
             if (v) atomicAdd(&hist[j], v);
         }
@@ -400,22 +340,22 @@ void vah_run_hook(void *ctx, bool fill, unsigned grid, const is3d::SamplerParams
                            a.n_drawn, a.counts, a.offsets, a.base, a.particles, a.capacity);
 }
 
-// the fused pass of a binned run: one launch per event batch.  Private form: at most kVahBinPrivateBlocks workgroups, each walking the
+// the fused pass of a binned run: one launch per event batch.  Private form: at most kFusedBinPrivateBlocks workgroups, each walking the
 // pair list grid-stride; global form: one trip per thread
 void vah_bin_hook(void *ctx, const is3d::SamplerParams &p, const is3d::SamplerSpecies &sp, const is3d::SamplerRunArgs &a, const is3d::SamplerBinRun &b,
                   unsigned long long *hist_dev, unsigned long long *yield_dev)
 {
     const VahRun &r = *(const VahRun *)ctx;
     const is3d::VahCellExtra *extra = r.d_extra.as<is3d::VahCellExtra>();
-    const is3d::VahBinArgs ba{b.bins, b.widths, b.layout, sp.npart};
+    const is3d::SamplerBinArgs ba{b.bins, b.widths, b.layout, sp.npart};
     const bool priv = b.bins.kernel_form == 2 || (b.bins.kernel_form == 0 && is3d::sampler_bins_lds_fits(b.layout));
-    const int64_t trips = (a.n_active + is3d::kVahBinThreads - 1) / is3d::kVahBinThreads;
+    const int64_t trips = (a.n_active + is3d::kFusedBinThreads - 1) / is3d::kFusedBinThreads;
     if (priv)
-        hipLaunchKernelGGL((is3d::cf_sampler_vah_bin<true>), dim3((unsigned)std::min<int64_t>(trips, is3d::kVahBinPrivateBlocks)), dim3(is3d::kVahBinThreads),
+        hipLaunchKernelGGL((is3d::cf_sampler_vah_bin<true>), dim3((unsigned)std::min<int64_t>(trips, is3d::kFusedBinPrivateBlocks)), dim3(is3d::kFusedBinThreads),
                            (size_t)b.layout.total * sizeof(unsigned long long), nullptr, p, sp, a.rec, extra, a.GT, a.event0, a.active, a.n_active, a.n_drawn,
                            ba, hist_dev, yield_dev);
     else
-        hipLaunchKernelGGL((is3d::cf_sampler_vah_bin<false>), dim3((unsigned)trips), dim3(is3d::kVahBinThreads), 0, nullptr, p, sp, a.rec, extra, a.GT,
+        hipLaunchKernelGGL((is3d::cf_sampler_vah_bin<false>), dim3((unsigned)trips), dim3(is3d::kFusedBinThreads), 0, nullptr, p, sp, a.rec, extra, a.GT,
                            a.event0, a.active, a.n_active, a.n_drawn, ba, hist_dev, yield_dev);
 }
 

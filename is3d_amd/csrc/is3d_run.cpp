@@ -37,6 +37,11 @@
 // batch on the device (is3d_sample_binned_multi), never held as a list; the same files are written from the integer histograms
 // (is3d_write_sampler_tests_binned; vn/ to the fixed point) and the same lines printed, plus ms_bin.  test_sampler = 0, other operations and
 // the embedding entry (which returns the list) refuse the key.
+// test_sampler_fused = 1 (optional key, default 0): with operation = 2, test_sampler = 1 and a viscous mode every hadron is binned where it is
+// sampled (is3d_sample_fused; is3d_sample_fused_multi over a device list that was spelled out) -- one pass per event batch, no list and no
+// particle workspace.  The files of the test_sampler_on_device = 1 run are written (is3d_write_sampler_tests_binned, the same mean_yield) and
+// its lines printed, plus ms_bin; test_sampler_on_device may be 0 or 1 beside it, and oversample = 1 works.  Other operations,
+// test_sampler = 0, mode = 2 (it has vah_sampler_on_device) and the embedding entry refuse the key before anything is written.
 // vah_oversample = 1 (optional key, default 0): with mode = 2, operation = 2, df_mode = 4 and vah_sampler = 1 the anisotropic-hydro mean yield
 // (is3d_total_yield_vah: first device of the run's list, the file's y_cut, the deltaf_coefficients/vah tables, the sampler's Gauss-Laguerre file)
 // is printed as the viscous path prints its own and sizes the run, Nevents = is3d_oversample_events(min_num_hadrons, yield, max_num_samples); a
@@ -251,6 +256,23 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         }
     }
     const bool vah = !mem && mode == 2;
+    // optional key test_sampler_fused = 1: the viscous sampler's hadrons binned where they are sampled (is3d_sample_fused), no particle list
+    bool bin_fused = false;
+    {
+        double key = 0.0, test_sampler = 0.0;
+        if (get_param("test_sampler_fused", &key, false) == IS3D_OK && (int)key) {
+            if (operation != 2)
+                DIE("test_sampler_fused = 1 with operation = %d: it bins the sampler's hadrons (operation = 2); set test_sampler_fused = 0", operation);
+            if (get_param("test_sampler", &test_sampler)) return IS3D_EINVAL;
+            if (!(int)test_sampler)
+                DIE("test_sampler_fused = 1 with test_sampler = 0: the particle list is the output of that run and is never held on this path; set test_sampler_fused = 0");
+            if (vah)
+                DIE("test_sampler_fused = 1 with mode = 2: it names the viscous-hydro sampler; the anisotropic-hydro one has vah_sampler_on_device; set test_sampler_fused = 0");
+            if (res)
+                DIE("test_sampler_fused = 1: the embedding entry returns the particle list, which this path never holds; set test_sampler_fused = 0");
+            bin_fused = true;
+        }
+    }
     // optional key vah_oversample = 1: the anisotropic-hydro mean yield (is3d_total_yield_vah) sizes the run of this library's own VAH sampler
     bool vah_oversample = false;
     {
@@ -624,7 +646,7 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         if (df_mode == 3) printf("Sampling particles with Mike's modified distribution...\n");
         if (df_mode == 4 && !vah) printf("Sampling particles with Jonah's modified distribution...\n");
         if (vah) printf("Sampling particles from vahydro (P_L matching) with df...\n");
-        if (bin_on_device || vah_bin_on_device) {
+        if (bin_on_device || vah_bin_on_device || bin_fused) {
             // one pass: every event batch is binned on its device and dropped (anisotropic hydro: every hadron binned where it is sampled); the
             // integer histograms of the shards are added on the host
             const size_t S = (size_t)sp.n, plane = (size_t)IS3D_SAMPLER_VN_HARMONICS * S * bins.pT_bins;
@@ -632,12 +654,15 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
                 h_vr(plane), h_vi(plane), h_yield((size_t)si.n_events);
             const is3d_sampler_hist hist{h_dy.data(), h_de.data(), h_dp.data(), h_dt.data(), h_dr.data(), h_vr.data(), h_vi.data(), h_yield.data()};
             // anisotropic hydro: a device list the user spelled out shards the cells; without one the first device samples alone
-            const int rcb = vah_bin_on_device
+            const int rcb = bin_fused
+                                ? (rd.named ? is3d_sample_fused_multi(&cells, &sp, &df, &si, &opts, rd.list.data(), (int32_t)rd.list.size(), &bins, &hist, &count, &ss)
+                                            : is3d_sample_fused(&cells, &sp, &df, &si, &opts, &bins, &hist, &count, &ss))
+                            : vah_bin_on_device
                                 ? (rd.named ? is3d_sample_binned_vah_multi(&vc, &sp, &vt, &si, &opts, rd.list.data(), (int32_t)rd.list.size(), &bins, &hist, &count, &ss)
                                             : is3d_sample_binned_vah(&vc, &sp, &vt, &si, &opts, &bins, &hist, &count, &ss))
                                 : is3d_sample_binned_multi(&cells, &sp, &df, &si, &opts, rd.list.empty() ? nullptr : rd.list.data(), (int32_t)rd.list.size(),
                                                            &bins, &hist, &count, &ss);
-            if (rcb) DIE("%s failed (%d): %s", vah_bin_on_device ? "is3d_sample_binned_vah" : "is3d_sample_binned", rcb, is3d_last_error());
+            if (rcb) DIE("%s failed (%d): %s", bin_fused ? "is3d_sample_fused" : vah_bin_on_device ? "is3d_sample_binned_vah" : "is3d_sample_binned", rcb, is3d_last_error());
             double t2s = now_s();
             printf("\nMomentum sampling efficiency = %f %%\n", 100.0 * (double)ss.n_acceptances / (double)std::max<int64_t>(ss.n_momentum_samples, 1));
             if (feqmod) printf("feqmod breaks down for %lld cells\n", (long long)ss.n_cells_breakdown);
@@ -647,7 +672,7 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
             printf("particles: %lld in %d event(s); hadrons drawn %lld; cells skipped (u.dsigma <= 0): %lld\n", (long long)count, si.n_events,
                    (long long)ss.n_hadrons_drawn, (long long)ss.n_cells_skipped);
             printf("device time: prep %.3f ms, count %.3f ms, fill %.3f ms; h2d %.3f ms\n", ss.ms_prep, ss.ms_count, ss.ms_fill, ss.ms_h2d);
-            if (vah_bin_on_device) printf("binned where sampled on the device: ms_bin %.3f ms (sampling and binning, one pass), no particle workspace\n", ss.ms_bin);
+            if (vah_bin_on_device || bin_fused) printf("binned where sampled on the device: ms_bin %.3f ms (sampling and binning, one pass), no particle workspace\n", ss.ms_bin);
             else printf("binned on the device: ms_bin %.3f ms, particle workspace %lld bytes (one event batch)\n", ss.ms_bin, (long long)ss.particle_workspace_bytes);
             printf("wall: read %.3f s, sampling %.3f s, write %.3f s\n", t1 - t0, t2s - t1, t3s - t2s);
             if (int rcp = polarization()) return rcp;
