@@ -750,7 +750,7 @@ int is3d_sample_fused(const is3d_cells *cells, const is3d_species *species, cons
 int is3d_sample_fused_multi(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
                             const is3d_options *opts, const int32_t *devices, int32_t n_devices, const is3d_sampler_test_bins *bins,
                             const is3d_sampler_hist *hist, int64_t *n_particles, is3d_sampler_stats *stats);
-/* The anisotropic-hydro sampler with its hadrons binned where they are sampled (cf_sampler_vah_bin), in one pass and without a list.  As for
+/* The anisotropic-hydro sampler with its hadrons binned where they are sampled (cf_sampler_fused), in one pass and without a list.  As for
  * is3d_sample_particles_vah the reference has nothing to match, so THIS is the definition:
  *   the histograms are those of is3d_sampler_bin_list on the list that is3d_sample_particles_vah returns for the same arguments -- counts
  *   and yields exactly; vn_re, vn_im within one unit per entry of the dN_pT bin (device and host libm; against is3d_sampler_bin_list_device
@@ -760,15 +760,17 @@ int is3d_sample_fused_multi(const is3d_cells *cells, const is3d_species *species
  * <-> pair, that replays the list route's streams and loop and gives every kept hadron's is3d_particle (built in registers) to the rule of
  * csrc/cf_sampler_bins.h; the adds are the 64-bit integer adds of cf_sampler_bins, so the result depends neither on the order of arrival
  * nor on bins->kernel_form (0 = workgroup-private histograms in LDS where they fit 64 KiB, 1 = global atomics, 2 = private or IS3D_EINVAL),
- * in->batch_events, in->first_cell sharding or the device count, bit for bit.
+ * in->batch_events, in->first_cell sharding or the device count, bit for bit.  "Fit" is the rule of is3d_sample_fused: the kernel keeps the
+ * three words of the run-wide tallies in LDS beside the block, so a private block has at most 8189 words; on a block of 8190-8192 words
+ * kernel_form = 0 takes the global form and kernel_form = 2 is refused (the list kernel of is3d_sample_binned still holds 8192).
  * Device memory: the histograms (8 B per word of is3d_sampler_hist), the per-cell records of is3d_sample_particles_vah and 9 B per
  * (event, cell) pair of ONE batch (Poisson number, emit flag, pair list; batches of <= 2^25 pairs, or in->batch_events events) with the
  * compaction's temporary storage -- nothing is sized by the number of hadrons: no particle workspace, no counts, no offsets, no scan.
  * stats: ms_bin is the time of the fused sample-and-bin passes; ms_count, ms_fill and particle_workspace_bytes are 0; ms_h2d, ms_prep,
  * ms_density, ms_poisson, n_momentum_samples, n_acceptances, n_hadrons_drawn and n_cells_skipped are those of is3d_sample_particles_vah.
  * HOST pointers; hist is overwritten.  Refused with IS3D_EINVAL before any device use, in this order: everything is3d_sample_particles_vah
- * refuses, then what is3d_sample_binned refuses of bins and hist (a NULL, bad bins, kernel_form outside 0..2, kernel_form = 2 on a block
- * that does not fit the LDS).  A good call without a device is IS3D_ENODEVICE, an empty surface included (the plan comes first, as for
+ * refuses, then what is3d_sample_fused refuses of bins and hist (a NULL, bad bins, kernel_form outside 0..2, kernel_form = 2 on a block
+ * that does not fit the LDS beside the three tally words).  A good call without a device is IS3D_ENODEVICE, an empty surface included (the plan comes first, as for
  * is3d_sample_particles_vah); with a device n_cells = 0 gives zero histograms, *n_particles = 0 and IS3D_OK without a launch.
  * A bad cell (is3d_sample_particles_vah): IS3D_EDOMAIN naming the lowest global index, with the histograms of the other cells, *n_particles
  * and stats returned.  A dN_pT bin above IS3D_SAMPLER_VN_MAX_COUNT: IS3D_EDOMAIN. */

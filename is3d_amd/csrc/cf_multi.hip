@@ -1272,7 +1272,7 @@ extern "C" int is3d_sample_binned_vah_multi(const is3d_vah_cells *cells, const i
     *n_particles = 0;
     if (stats) memset(stats, 0, sizeof *stats);
     if (int rc = is3d::sampler_vah_check(cells, species, tab, in, opts)) return rc;
-    if (int rc = is3d::sampler_check_bin_args(bins, hist, in->n_events, species->n)) return rc;
+    if (int rc = is3d::sampler_check_fused_args(bins, hist, in->n_events, species->n)) return rc;
     std::vector<int> dev;
     if (int rc = resolve_devices(devices, n_devices, dev)) return rc;
     n_devices = (int32_t)dev.size();

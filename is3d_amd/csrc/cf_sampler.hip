@@ -25,6 +25,8 @@
 //   cf_sampler_run      thread <-> emitting (event, cell) pair: species, momentum rejection loop, viscous and flux weights, keep
 //                       test; pass 1 counts, an exclusive scan turns counts into offsets, pass 2 replays the same streams and
 //                       writes the particles -- the list comes out ordered by (event, cell, draw), no atomics, no sort.
+//   cf_sampler_fused    the same pairs sampled once and binned where they are sampled, without a list
+// The last two and the per-pair loop they run are cf_sampler_common.h's, instantiated here with ViscousModel.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <limits.h>
@@ -253,31 +255,17 @@ cf_sampler_poisson(SamplerParams p, const SamplerCell *__restrict__ cellrec, int
     emits[idx] = N > 0;
 }
 
-// one emitting (event, cell) pair: the ONE piece of source the count, the fill and the fused bin pass run.  ic is the pair's cell, ievent its
-// event; every kept hadron goes to keep() as the is3d_particle of the list.  Returns the number kept; tally[] gets the pair's momentum
-// samples, acceptances and hadrons drawn.
-template <class Keep>
-__device__ __forceinline__ long sample_pair(const SamplerParams &p, const SamplerSpecies &sp, const SamplerCell *__restrict__ cellrec,
-                                            const double *__restrict__ GT, const double *__restrict__ GT2, const double *__restrict__ GT3,
-                                            int ievent, int64_t ic, long N_hadrons, Keep &keep, unsigned long long (&tally)[3])
-{
-    const SamplerCell &c = cellrec[ic];
-    const uint32_t gcell = (uint32_t)(p.first_cell + ic);
-    Rng g_type, g_momentum, g_keep, g_rapidity;
-    g_type.init(p.seed, 1, gcell, (uint32_t)ievent);
-    g_momentum.init(p.seed, 2, gcell, (uint32_t)ievent);
-    g_keep.init(p.seed, 3, gcell, (uint32_t)ievent);
-    g_rapidity.init(p.seed, 4, gcell, (uint32_t)ievent);
-    const double *gt = GT + ic, *gt2 = GT2 ? GT2 + ic : nullptr, *gt3 = GT3 ? GT3 + ic : nullptr;
-    const bool linear = p.df_mode <= 2 || c.breakdown != 0.0;
-    const double sinheta = sinh(c.eta), cosheta = sqrt(1.0 + sinheta * sinheta);   // :888-889
-    long kept = 0, samples = 0, acceptances = 0;
-    for (long ih = 0; ih < N_hadrons; ih++) {
-        const double ut_ = g_type.uniform() * c.dn_sum;
-        const int chosen = choose_species(p, sp, c, gt, gt2, gt3, ic, ut_);
-        const double mass = sp.mass[chosen], mass_squared = mass * mass, sign = sp.sign[chosen];
+// the viscous route's Model (cf_sampler_common.h): the df_mode 3 integral tables beside GT, and per hadron the linear delta-f draw with its
+// viscous weight or, for modified equilibrium away from breakdown, the rescaled momentum with weight 1
+struct ViscousModel {
+    const double *gt2, *gt3;
+    using Pair = bool;      // linear: df_mode 1, 2, or a modified-equilibrium cell that broke down
+    __device__ __forceinline__ Pair pair(const SamplerParams &p, const SamplerCell &c, int64_t) const { return p.df_mode <= 2 || c.breakdown != 0.0; }
+    __device__ __forceinline__ double draw(const SamplerParams &p, const SamplerSpecies &sp, const SamplerCell &c, Pair linear, int chosen,
+                                           double mass, double mass_squared, double sign, Rng &g_momentum, long &acceptances, long &samples,
+                                           LrfMom &q) const
+    {
         const double baryon = sp.baryon ? sp.baryon[chosen] : 0.0;
-        LrfMom q;
         double w_visc = 1.0;
         if (linear) {                                                               // :1100-1110, switch_to_linear_df
             const double chem = baryon * c.alphaB;
@@ -311,108 +299,9 @@ __device__ __forceinline__ long sample_pair(const SamplerParams &p, const Sample
             q.pz = (1.0 + c.bulk_mod) * m.pz + c.shear_mod * (c.pixz * m.px + c.piyz * m.py + c.pizz * m.pz) + diff_mod * c.Vz;
             q.E = sqrt(mass_squared + q.px * q.px + q.py * q.py + q.pz * q.pz);
         }
-        // boost_pLRF_to_lab_frame (emissionfunction.cpp:40-51)
-        const double ptau = q.E * c.ut + q.px * c.Xt + q.pz * c.Zt;
-        const double plx = q.E * c.ux + q.px * c.Xx + q.py * c.Yx;
-        const double ply = q.E * c.uy + q.px * c.Xy + q.py * c.Yy;
-        const double pn = q.E * c.un + q.px * c.Xn + q.pz * c.Zn;
-        const double w_flux = fmax(0.0, q.E * c.dst - q.px * c.dsx - q.py * c.dsy - q.pz * c.dsz) / (q.E * c.ds_max);   // :1148
-        if (!(g_keep.uniform() < (w_flux * w_visc))) continue;
-        double Elab, pz, eta = c.eta, sh = sinheta, ch = cosheta;
-        if (!p.dim3) {                                                              // :1168-1186
-            const double yp = p.y_max * (2.0 * g_rapidity.uniform() - 1.0);
-            const double sinhy = sinh(yp), coshy = sqrt(1.0 + sinhy * sinhy);
-            const double tau_pn = c.tau * pn, mT = sqrt(mass_squared + plx * plx + ply * ply);
-            sh = (ptau * sinhy - tau_pn * coshy) / mT;
-            eta = asinh(sh);
-            ch = sqrt(1.0 + sh * sh);
-            pz = mT * sinhy;
-            Elab = mT * coshy;
-        } else {
-            pz = c.tau * pn * ch + ptau * sh;
-            Elab = sqrt(mass_squared + plx * plx + ply * ply + pz * pz);
-        }
-        is3d_particle o;
-        o.cell = p.first_cell + ic; o.event = ievent; o.species = chosen;
-        o.tau = c.tau; o.x = c.x; o.y = c.y; o.eta = eta; o.t = c.tau * ch; o.z = c.tau * sh;
-        o.E = Elab; o.px = plx; o.py = ply; o.pz = pz;
-        keep(o);
-        kept++;
+        return w_visc;
     }
-    tally[0] += (unsigned long long)samples; tally[1] += (unsigned long long)acceptances; tally[2] += (unsigned long long)N_hadrons;
-    return kept;
-}
-
-// thread <-> emitting (event, cell) pair: the count pass (counts[] and the run-wide tallies) and the fill pass of the list route
-template <bool FILL>
-__global__ void __launch_bounds__(128)
-cf_sampler_run(SamplerParams p, SamplerSpecies sp, const SamplerCell *__restrict__ cellrec, const double *__restrict__ GT,
-               const double *__restrict__ GT2, const double *__restrict__ GT3, int event0, const int32_t *__restrict__ active, int64_t n_active,
-               const int32_t *__restrict__ n_drawn, int64_t *__restrict__ counts, const int64_t *__restrict__ offsets, int64_t base,
-               is3d_particle *__restrict__ particles, int64_t capacity)
-{
-    unsigned long long tally[3] = {0ULL, 0ULL, 0ULL};
-    const int64_t ia = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // position in the list of emitting (event, cell) pairs
-    if (ia < n_active && !(FILL && offsets[ia + 1] == offsets[ia])) {       // (fill: pass 1 kept nothing here, nothing to replay)
-        const int64_t idx = active[ia];                                     // event-major: (event - event0) * n_cells + cell
-        const int ievent = event0 + (int)(idx / p.n_cells);
-        const int64_t ic = idx % p.n_cells;
-        const long N_hadrons = n_drawn[idx];                                // cf_sampler_poisson (stream 0)
-        if (FILL) {
-            SamplerKeepFill keep{particles, base + offsets[ia], capacity};
-            sample_pair(p, sp, cellrec, GT, GT2, GT3, ievent, ic, N_hadrons, keep, tally);
-        } else {
-            SamplerKeepCount keep;
-            counts[ia] = sample_pair(p, sp, cellrec, GT, GT2, GT3, ievent, ic, N_hadrons, keep, tally);
-        }
-    }
-    if (!FILL) sampler_tally(p, tally);
-}
-
-// The fused pass (is3d_sampler_plan_execute_fused): the count pass's threads, streams and loop, every kept hadron added straight into the
-// histograms of cf_sampler_bins (the same rule, cf_sampler_bins.h, on the same is3d_particle the fill pass would store) -- no list, so no
-// counts, offsets, scan or particle workspace.  Every add is a 64-bit integer, so the histograms are those of the list route bit for bit
-// whatever the order of arrival.
-//   PRIVATE: the whole block lives in dynamic LDS (ds_add_u64), at most kFusedBinPrivateBlocks workgroups walk the pair list grid-stride
-//            and each flushes its non-zero words once with global adds
-//   else:    every add goes straight to the global block (305 species: 305 x 1800 words)
-// Per-event yields: sampler_yield_runs after the rejection loop, with the wave reconverged; lanes past n_active take part with event
-// INT_MAX and kept = 0.  The trip count is the same for every thread of a workgroup: the wave operations see whole waves and the barriers
-// every thread; none of either sits inside the per-hadron loop.
-template <bool PRIVATE>
-__global__ void __launch_bounds__(kFusedBinThreads, 2)
-cf_sampler_fused(SamplerParams p, SamplerSpecies sp, const SamplerCell *__restrict__ cellrec, const double *__restrict__ GT,
-                 const double *__restrict__ GT2, const double *__restrict__ GT3, int event0, const int32_t *__restrict__ active, int64_t n_active,
-                 const int32_t *__restrict__ n_drawn, SamplerBinArgs a, unsigned long long *__restrict__ hist,
-                 unsigned long long *__restrict__ yield)
-{
-    extern __shared__ unsigned long long priv[];
-    if (PRIVATE) {
-        for (int64_t j = threadIdx.x; j < a.l.total; j += kFusedBinThreads) priv[j] = 0ULL;
-        __syncthreads();
-    }
-    SamplerKeepBin keep{a, PRIVATE ? priv : hist};
-    unsigned long long tally[3] = {0ULL, 0ULL, 0ULL};
-    for (int64_t i0 = (int64_t)blockIdx.x * kFusedBinThreads; i0 < n_active; i0 += (int64_t)gridDim.x * kFusedBinThreads) {
-        const int64_t ia = i0 + threadIdx.x;
-        int ev = INT_MAX;
-        long long kept = 0;
-        if (ia < n_active) {
-            const int64_t idx = active[ia];
-            ev = event0 + (int)(idx / p.n_cells);
-            kept = sample_pair(p, sp, cellrec, GT, GT2, GT3, ev, idx % p.n_cells, (long)n_drawn[idx], keep, tally);
-        }
-        sampler_yield_runs(ev, kept, yield);
-    }
-    sampler_tally(p, tally);
-    if (PRIVATE) {
-        __syncthreads();
-        for (int64_t j = threadIdx.x; j < a.l.total; j += kFusedBinThreads) {
-            const unsigned long long v = priv[j];
-            if (v) atomicAdd(&hist[j], v);
-        }
-    }
-}
+};
 
 }  // namespace is3d
 
@@ -438,13 +327,15 @@ struct is3d_sampler_plan {
     DevMem d_jonah, d_eqd, d_bkd;
     DevMem d_status, d_GT, d_GT2, d_GT3, d_rec, d_counts, d_offsets, d_scan_tmp;
     DevMem d_drawn, d_emits, d_active, d_nactive, d_cdf;
-    DevMem d_particles, d_hist;             // is3d_sampler_plan_execute_binned: one batch of particles; the histograms, then the yields
+    DevMem d_particles, d_hist;             // a binned run: one batch of particles (list-and-bin only); the histograms, then the yields
     int64_t cap_cells = 0, cap_bt = 0;      // what the workspaces above were sized for
-    int64_t cap_list = 0;                   // ... d_counts and d_offsets, which a fused binned run (SamplerVariant::bin, BinRun::fused) never has
+    int64_t cap_list = 0;                   // ... d_counts and d_offsets, which a fused binned run never has
     size_t tmp_select = 0, tmp_scan = 0;
-    int64_t cap_particles = 0, cap_hist = 0;
+    int64_t cap_particles = 0;
     size_t tmp_bytes = 0;
     hipEvent_t ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    is3d::ViscousModel model{};             // the viscous sampler as a variant of its own plan (is3d_sampler_plan_create; unused by other variants)
+    is3d::SamplerVariant viscous;
 };
 
 namespace {
@@ -520,6 +411,17 @@ int plan_finish(is3d_sampler_plan *P, const is3d_sampler_inputs *in)
     HIP_TRY(P->d_status.alloc(8 * sizeof(unsigned long long)));
     p.status = P->d_status.as<unsigned long long>();
     for (auto &e : P->ev) HIP_TRY(hipEventCreate(&e));
+    return IS3D_OK;
+}
+}  // namespace
+
+namespace {
+// SamplerVariant::cells of the viscous sampler: cf_sampler_cells on the cell arrays of P->p.cells
+int viscous_cells(void *ctx, const is3d::SamplerParams &p, const is3d::SamplerSpecies &sp, const double *GT, is3d::SamplerCell *rec)
+{
+    is3d_sampler_plan *P = (is3d_sampler_plan *)ctx;
+    P->model = is3d::ViscousModel{P->d_GT2.as<double>(), P->d_GT3.as<double>()};
+    hipLaunchKernelGGL(is3d::cf_sampler_cells, dim3((unsigned)((p.n_cells + 127) / 128)), dim3(128), 0, nullptr, p, sp, GT, P->model.gt2, P->model.gt3, rec);
     return IS3D_OK;
 }
 }  // namespace
@@ -688,6 +590,12 @@ extern "C" int is3d_sampler_plan_create(is3d_sampler_plan **out, const is3d_spec
         } else if (opts->df_mode == 3) { p.F_avg = spline_at(0, Tsw) * Tsw; p.betabulk_avg = spline_at(1, Tsw) * Tsw * Tsw * Tsw * Tsw; }
     }
     if (int rc = plan_finish(P.get(), in)) return rc;
+    is3d::SamplerVariant &v = P->viscous;
+    v.domain_text = std::string("T") + (opts->df_mode == 4 ? " (or bulkPi/P)" : (baryon ? " or (T, muB)" : "")) +
+                    " outside the coefficient table (the reference aborts in gsl_spline_eval here)";
+    v.ctx = P.get();
+    v.cells = viscous_cells;
+    v.set_model(&P->model);
     *out = P.release();
     return IS3D_OK;
 }
@@ -707,14 +615,24 @@ bool cell_array_needed(int a, const is3d_options *o)
     const bool baryondiff = o->include_baryon != 0 && o->include_baryondiff_deltaf != 0;
     return a < 12 ? (a != 1 || three_d) : (a < 17 ? o->include_shear_deltaf != 0 : (a == 17 ? o->include_bulk_deltaf != 0 : baryondiff));
 }
-// what is3d_sampler_plan_execute_binned adds to the batch loop
+// the needed cell arrays of a DEVICE surface become the plan's, and the viscous variant's temperature and chemical potential
+int bind_cells(is3d_sampler_plan *P, const is3d_cells *cells, int64_t first_cell)
+{
+    if (int rc = check_cells(cells, &P->o, first_cell)) return rc;
+    if (cells->n_cells > 0) {
+        auto arrays = is3d::cell_arrays(*cells);
+        for (int a = 0; a < is3d::kCellArrays; a++)
+            if (!cell_array_needed(a, &P->o)) arrays[a] = nullptr;
+        P->p.cells = is3d::cell_ptrs(is3d::cells_from_arrays(cells->n_cells, arrays));
+    }
+    P->viscous.T = P->p.cells.T;
+    P->viscous.muB = P->p.cells.muB;
+    return IS3D_OK;
+}
 using BinRun = is3d::SamplerBinRun;
-int sampler_execute(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev, int32_t n_events, uint64_t seed,
-                    int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
-                    int64_t *n_particles, is3d_sampler_stats *stats);
-int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t n, const double *x_dev, const double *y_dev, int32_t n_events,
+int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t n, const double *x_dev, const double *y_dev, int32_t n_events,
                     uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
-                    int64_t *n_particles, is3d_sampler_stats *stats);
+                    bool fuse, int64_t *n_particles, is3d_sampler_stats *stats);
 }  // namespace
 
 extern "C" void is3d_sampler_plan_destroy(is3d_sampler_plan *P)
@@ -731,60 +649,23 @@ extern "C" int is3d_sampler_plan_execute(is3d_sampler_plan *P, const is3d_cells 
                                          uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity,
                                          int64_t *n_particles, is3d_sampler_stats *stats)
 {
-    return sampler_execute(P, cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, particles_dev, capacity, nullptr, n_particles, stats);
-}
-
-namespace {
-// the one batch loop: bin == NULL fills the caller's list (or only counts); bin != NULL fills each batch into the plan's particle workspace
-// at base 0, bins it into P->d_hist and drops it -- or, for a variant with a bin hook or with bin->fused, samples each batch straight into
-// P->d_hist
-int sampler_execute(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev, int32_t n_events, uint64_t seed,
-                    int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
-                    int64_t *n_particles, is3d_sampler_stats *stats)
-{
     using is3d::set_error;
     if (!P || !cells || !n_particles) return set_error(IS3D_EINVAL, "null argument");
     *n_particles = 0;
     if (stats) memset(stats, 0, sizeof *stats);
     if (n_events < 1) return set_error(IS3D_EINVAL, "n_events must be >= 1");
-    if (int rc = check_cells(cells, &P->o, first_cell)) return rc;
-    const int64_t n = cells->n_cells;
-    if (n > 0) {
-        auto arrays = is3d::cell_arrays(*cells);
-        for (int a = 0; a < is3d::kCellArrays; a++)
-            if (!cell_array_needed(a, &P->o)) arrays[a] = nullptr;
-        P->p.cells = is3d::cell_ptrs(is3d::cells_from_arrays(n, arrays));
-    }
-    return sampler_batches(P, nullptr, n, x_dev, y_dev, n_events, seed, first_cell, batch_events, particles_dev, capacity, bin, n_particles, stats);
+    if (int rc = bind_cells(P, cells, first_cell)) return rc;
+    return is3d::sampler_variant_execute(P, P->viscous, cells->n_cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, particles_dev,
+                                         capacity, n_particles, stats);
 }
 
-// the fused pass of the viscous route: one launch per event batch.  Private form: at most kFusedBinPrivateBlocks workgroups, each walking
-// the pair list grid-stride; global form: one trip per thread.  (sampler_tally keeps three words of static LDS beside the block: form 0 on
-// a block that leaves no room for them takes the global form, and form 2 is refused there.)
-bool fused_lds_fits(const is3d::SamplerHistLayout &l)
-{
-    return is3d::sampler_bins_lds_fits(l) && (size_t)(l.total + 3) * sizeof(unsigned long long) <= 65536;
-}
-void fused_launch(const is3d::SamplerParams &p, const is3d::SamplerSpecies &sp, const is3d::SamplerRunArgs &a, const double *GT2, const double *GT3,
-                  const BinRun &b, unsigned long long *hist_dev, unsigned long long *yield_dev)
-{
-    const is3d::SamplerBinArgs ba{b.bins, b.widths, b.layout, sp.npart};
-    const bool priv = b.bins.kernel_form == 2 || (b.bins.kernel_form == 0 && fused_lds_fits(b.layout));
-    const int64_t trips = (a.n_active + is3d::kFusedBinThreads - 1) / is3d::kFusedBinThreads;
-    if (priv)
-        hipLaunchKernelGGL((is3d::cf_sampler_fused<true>), dim3((unsigned)std::min<int64_t>(trips, is3d::kFusedBinPrivateBlocks)),
-                           dim3(is3d::kFusedBinThreads), (size_t)b.layout.total * sizeof(unsigned long long), nullptr, p, sp, a.rec, a.GT, GT2, GT3,
-                           a.event0, a.active, a.n_active, a.n_drawn, ba, hist_dev, yield_dev);
-    else
-        hipLaunchKernelGGL((is3d::cf_sampler_fused<false>), dim3((unsigned)trips), dim3(is3d::kFusedBinThreads), 0, nullptr, p, sp, a.rec, a.GT, GT2,
-                           GT3, a.event0, a.active, a.n_active, a.n_drawn, ba, hist_dev, yield_dev);
-}
-
-// v == NULL: cf_sampler_cells and cf_sampler_run (or, for a fused binned run, cf_sampler_fused) on P->p.cells; else the variant's kernels
-// (cf_sampler_common.h)
-int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t n, const double *x_dev, const double *y_dev, int32_t n_events,
+namespace {
+// the one batch loop of every variant.  bin == NULL fills the caller's list (or only counts); bin != NULL with fuse samples each batch
+// straight into P->d_hist (cf_sampler_fused); bin != NULL without it fills each batch into the plan's particle workspace at base 0, bins it
+// into P->d_hist (cf_sampler_bins) and drops it
+int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t n, const double *x_dev, const double *y_dev, int32_t n_events,
                     uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
-                    int64_t *n_particles, is3d_sampler_stats *stats)
+                    bool fuse, int64_t *n_particles, is3d_sampler_stats *stats)
 {
     using is3d::set_error;
     if (particles_dev == nullptr || bin) capacity = 0;
@@ -817,7 +698,7 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t
         P->cap_cells = n;
     }
     // fused: one pass per batch samples and bins; the counts, the offsets and the scan exist only to put a list in order
-    const bool fused = bin && (v ? v->bin != nullptr : bin->fused != 0);
+    const bool fused = bin && fuse;
     if (bt > P->cap_bt) {
         HIP_TRY(P->d_drawn.alloc((size_t)bt * sizeof(int32_t)));
         HIP_TRY(P->d_emits.alloc((size_t)bt));
@@ -838,21 +719,16 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t
         P->tmp_bytes = need;
     }
     p.cdf = P->d_cdf.as<double>();
-    DevMem &d_GT = P->d_GT, &d_GT2 = P->d_GT2, &d_GT3 = P->d_GT3, &d_rec = P->d_rec, &d_counts = P->d_counts, &d_offsets = P->d_offsets, &d_scan_tmp = P->d_scan_tmp;
+    DevMem &d_GT = P->d_GT, &d_rec = P->d_rec, &d_counts = P->d_counts, &d_offsets = P->d_offsets, &d_scan_tmp = P->d_scan_tmp;
     DevMem &d_drawn = P->d_drawn, &d_emits = P->d_emits, &d_active = P->d_active, &d_nactive = P->d_nactive;
     size_t tmp_bytes = P->tmp_bytes;
     HIP_TRY(hipEventRecord(ev[1], nullptr));
     {
         const int64_t tot = n * ncls;
-        hipLaunchKernelGGL(is3d::cf_sampler_density, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, v ? v->T : p.cells.T,
-                           v ? nullptr : p.cells.muB, n, sp, P->d_gl.as<double>(), P->ngla, d_GT.as<double>(), d_GT2.as<double>(), d_GT3.as<double>());
+        hipLaunchKernelGGL(is3d::cf_sampler_density, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, v.T, v.muB, n, sp, P->d_gl.as<double>(),
+                           P->ngla, d_GT.as<double>(), P->d_GT2.as<double>(), P->d_GT3.as<double>());
         HIP_TRY(hipEventRecord(ev[6], nullptr));
-        if (v) {
-            if (int rc = v->cells(v->ctx, p, sp, d_GT.as<double>(), d_rec.as<is3d::SamplerCell>())) return rc;
-        } else {
-            hipLaunchKernelGGL(is3d::cf_sampler_cells, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, nullptr, p, sp, d_GT.as<double>(),
-                               d_GT2.as<double>(), d_GT3.as<double>(), d_rec.as<is3d::SamplerCell>());
-        }
+        if (int rc = v.cells(v.ctx, p, sp, d_GT.as<double>(), d_rec.as<is3d::SamplerCell>())) return rc;
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(ev[2], nullptr));
@@ -873,50 +749,38 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t
         int32_t n_active = 0;
         HIP_TRY(hipMemcpy(&n_active, d_nactive.p, sizeof(int32_t), hipMemcpyDeviceToHost));
         int64_t batch_total = 0;
+        // what every launch of the batch gets; the count pass adds counts, the fill pass offsets and the list
+        is3d::SamplerRunArgs a{d_rec.as<is3d::SamplerCell>(), d_GT.as<double>(), e0, d_active.as<int32_t>(), (int64_t)n_active, d_drawn.as<int32_t>(),
+                               nullptr, nullptr, 0, nullptr, 0};
         if (fused) {
             HIP_TRY(hipEventRecord(ev[3], nullptr));
             HIP_TRY(hipEventRecord(ev[8], nullptr));
             if (n_active > 0) {
                 unsigned long long *hist_dev = P->d_hist.as<unsigned long long>();
-                const is3d::SamplerRunArgs a{d_rec.as<is3d::SamplerCell>(), d_GT.as<double>(), e0, d_active.as<int32_t>(), (int64_t)n_active,
-                                             d_drawn.as<int32_t>(), nullptr, nullptr, 0, nullptr, 0};
-                if (v) v->bin(v->ctx, p, sp, a, *bin, hist_dev, hist_dev + bin->layout.total);
-                else fused_launch(p, sp, a, d_GT2.as<double>(), d_GT3.as<double>(), *bin, hist_dev, hist_dev + bin->layout.total);
+                v.fused(v.model, p, sp, a, *bin, hist_dev, hist_dev + bin->layout.total);
                 HIP_TRY(hipGetLastError());
             }
         } else if (n_active > 0) {
-            const unsigned grid = (unsigned)(((int64_t)n_active + 127) / 128);
             HIP_TRY(hipMemsetAsync(d_counts.as<int64_t>() + n_active, 0, sizeof(int64_t), nullptr));
-            if (v)
-                v->run(v->ctx, false, grid, p, sp, is3d::SamplerRunArgs{d_rec.as<is3d::SamplerCell>(), d_GT.as<double>(), e0, d_active.as<int32_t>(),
-                                                                       (int64_t)n_active, d_drawn.as<int32_t>(), d_counts.as<int64_t>(), nullptr, 0, nullptr, 0});
-            else
-                hipLaunchKernelGGL((is3d::cf_sampler_run<false>), dim3(grid), dim3(128), 0, nullptr, p, sp, d_rec.as<is3d::SamplerCell>(),
-                                   d_GT.as<double>(), d_GT2.as<double>(), d_GT3.as<double>(), e0, d_active.as<int32_t>(), (int64_t)n_active,
-                                   d_drawn.as<int32_t>(), d_counts.as<int64_t>(), (const int64_t *)nullptr, (int64_t)0, (is3d_particle *)nullptr, (int64_t)0);
+            a.counts = d_counts.as<int64_t>();
+            v.run(v.model, false, p, sp, a);
             HIP_TRY(hipGetLastError());
             // element n_active of the scan (counts[n_active] = 0) is the batch total
             HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_scan_tmp.p, tmp_bytes, d_counts.as<int64_t>(), d_offsets.as<int64_t>(), n_active + 1, nullptr));
             HIP_TRY(hipEventRecord(ev[3], nullptr));
             HIP_TRY(hipMemcpy(&batch_total, d_offsets.as<int64_t>() + n_active, sizeof(int64_t), hipMemcpyDeviceToHost));
             // the list: the caller's buffer at the running base; binned: the plan's workspace, grown to the largest batch seen, at base 0
-            is3d_particle *dst = particles_dev;
-            int64_t dst_base = base, dst_cap = capacity;
+            a.counts = nullptr; a.offsets = d_offsets.as<int64_t>();
+            a.particles = particles_dev; a.base = base; a.capacity = capacity;
             if (bin && batch_total > 0) {
                 if (batch_total > P->cap_particles) {
                     HIP_TRY(P->d_particles.alloc((size_t)batch_total * sizeof(is3d_particle)));
                     P->cap_particles = batch_total;
                 }
-                dst = P->d_particles.as<is3d_particle>(); dst_base = 0; dst_cap = batch_total;
+                a.particles = P->d_particles.as<is3d_particle>(); a.base = 0; a.capacity = batch_total;
             }
-            if (dst_cap > 0 && dst_base < dst_cap && batch_total > 0) {
-                if (v)
-                    v->run(v->ctx, true, grid, p, sp, is3d::SamplerRunArgs{d_rec.as<is3d::SamplerCell>(), d_GT.as<double>(), e0, d_active.as<int32_t>(),
-                                                                          (int64_t)n_active, d_drawn.as<int32_t>(), nullptr, d_offsets.as<int64_t>(), dst_base, dst, dst_cap});
-                else
-                    hipLaunchKernelGGL((is3d::cf_sampler_run<true>), dim3(grid), dim3(128), 0, nullptr, p, sp, d_rec.as<is3d::SamplerCell>(),
-                                       d_GT.as<double>(), d_GT2.as<double>(), d_GT3.as<double>(), e0, d_active.as<int32_t>(), (int64_t)n_active,
-                                       d_drawn.as<int32_t>(), (int64_t *)nullptr, d_offsets.as<int64_t>(), dst_base, dst, dst_cap);
+            if (a.capacity > 0 && a.base < a.capacity && batch_total > 0) {
+                v.run(v.model, true, p, sp, a);
                 HIP_TRY(hipGetLastError());
             }
         } else {
@@ -929,12 +793,12 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t
                                               bin->bins.kernel_form));
         HIP_TRY(hipEventRecord(ev[4], nullptr));
         HIP_TRY(hipEventSynchronize(ev[4]));
-        float a = 0, b = 0, c = 0, d = 0;
-        HIP_TRY(hipEventElapsedTime(&a, ev[5], ev[3]));
-        HIP_TRY(hipEventElapsedTime(&b, ev[3], ev[8]));
-        HIP_TRY(hipEventElapsedTime(&c, ev[5], ev[7]));
-        HIP_TRY(hipEventElapsedTime(&d, ev[8], ev[4]));
-        ms_count += a; ms_fill += b; ms_poisson += c; ms_bin += d;
+        float a_ms = 0, b_ms = 0, c_ms = 0, d_ms = 0;
+        HIP_TRY(hipEventElapsedTime(&a_ms, ev[5], ev[3]));
+        HIP_TRY(hipEventElapsedTime(&b_ms, ev[3], ev[8]));
+        HIP_TRY(hipEventElapsedTime(&c_ms, ev[5], ev[7]));
+        HIP_TRY(hipEventElapsedTime(&d_ms, ev[8], ev[4]));
+        ms_count += a_ms; ms_fill += b_ms; ms_poisson += c_ms; ms_bin += d_ms;
         base += batch_total;
     }
     unsigned long long h[8];
@@ -958,10 +822,7 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant *v, int64_t
         if (bin) stats->ms_bin = ms_bin;
         if (bin && !fused) stats->particle_workspace_bytes = P->cap_particles * (int64_t)sizeof(is3d_particle);
     }
-    if (h[0] != ~0ULL && v) return set_error(IS3D_EDOMAIN, "cell %lld: %s", (long long)h[0], v->domain_text);
-    if (h[0] != ~0ULL)
-        return set_error(IS3D_EDOMAIN, "cell %lld: T%s outside the coefficient table (the reference aborts in gsl_spline_eval here)", (long long)h[0],
-                         P->o.df_mode == 4 ? " (or bulkPi/P)" : (p.baryon ? " or (T, muB)" : ""));
+    if (h[0] != ~0ULL) return set_error(IS3D_EDOMAIN, "cell %lld: %s", (long long)h[0], v.domain_text.c_str());
     if (particles_dev && base > capacity)
         return set_error(IS3D_ENOMEM, "%lld particles sampled but the caller's buffer holds %lld (call with particles = NULL for the count)",
                          (long long)base, (long long)capacity);
@@ -997,8 +858,28 @@ int is3d::sampler_variant_execute(is3d_sampler_plan *P, const SamplerVariant &v,
     if (stats) memset(stats, 0, sizeof *stats);
     if (n_events < 1) return set_error(IS3D_EINVAL, "n_events must be >= 1");
     if (n_cells < 0 || n_cells + first_cell > 0xffffffffLL) return set_error(IS3D_EINVAL, "cell indices must fit 32 bits for the counter-based streams");
-    P->p.cells = CellPtrs{};
-    return sampler_batches(P, &v, n_cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, particles_dev, capacity, nullptr, n_particles, stats);
+    return sampler_batches(P, v, n_cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, particles_dev, capacity, nullptr, false, n_particles,
+                           stats);
+}
+
+int is3d::sampler_variant_sample_list(is3d_sampler_plan *P, const SamplerVariant &v, int64_t n_cells, const double *x_dev, const double *y_dev,
+                                      const is3d_sampler_inputs *in, float ms_h2d, is3d_particle *particles, int64_t capacity,
+                                      int64_t *n_particles, is3d_sampler_stats *stats)
+{
+    if (particles == nullptr) capacity = 0;
+    DevMem d_particles;
+    if (capacity > 0) HIP_TRY(d_particles.alloc((size_t)capacity * sizeof(is3d_particle)));
+    int64_t total = 0;
+    const int rc = sampler_variant_execute(P, v, n_cells, x_dev, y_dev, in->n_events, in->seed, in->first_cell, in->batch_events,
+                                           d_particles.as<is3d_particle>(), capacity, &total, stats);
+    *n_particles = total;
+    if (stats) stats->ms_h2d = ms_h2d;
+    if (rc && rc != IS3D_ENOMEM && !(rc == IS3D_EDOMAIN && v.edomain_keeps_rest)) return rc;
+    const std::string kept = rc ? is3d_last_error() : "";
+    const int64_t ncopy = std::min<int64_t>(total, capacity);
+    if (ncopy > 0) HIP_TRY(hipMemcpy(particles, d_particles.p, (size_t)ncopy * sizeof(is3d_particle), hipMemcpyDeviceToHost));
+    if (rc) return set_error(rc, "%s", kept.c_str());
+    return IS3D_OK;
 }
 
 namespace {
@@ -1052,28 +933,15 @@ extern "C" int is3d_sample_particles(const is3d_cells *cells, const is3d_species
         if (rc0 && rc0 != IS3D_ENODEVICE) return rc0;
         return set_error(IS3D_EINVAL, "n_events must be >= 1");
     }
-    if (particles == nullptr) capacity = 0;
     StagedRun r;
     if (int rc = stage_run(r, cells, species, df, in, opts)) return rc;
     if (cells->n_cells == 0) return IS3D_OK;
-    is3d_sampler_plan *P = r.P;
-    DevMem d_particles;
-    if (capacity > 0) HIP_TRY(d_particles.alloc((size_t)capacity * sizeof(is3d_particle)));
-    int64_t total = 0;
-    const int rc = is3d_sampler_plan_execute(P, &r.dc, r.xy[0], r.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events,
-                                             d_particles.as<is3d_particle>(), capacity, &total, stats);
-    *n_particles = total;
-    if (stats) stats->ms_h2d = r.ms_h2d;
-    if (rc && rc != IS3D_ENOMEM) return rc;
-    const std::string kept = rc ? is3d_last_error() : "";
-    const int64_t ncopy = std::min<int64_t>(total, capacity);
-    if (ncopy > 0) HIP_TRY(hipMemcpy(particles, d_particles.p, (size_t)ncopy * sizeof(is3d_particle), hipMemcpyDeviceToHost));
-    if (rc) return set_error(rc, "%s", kept.c_str());
-    return IS3D_OK;
+    if (int rc = bind_cells(r.P, &r.dc, in->first_cell)) return rc;
+    return is3d::sampler_variant_sample_list(r.P, r.P->viscous, r.dc.n_cells, r.xy[0], r.xy[1], in, r.ms_h2d, particles, capacity, n_particles, stats);
 }
 
 // ------------------------------------------------------------------------------------------------
-// binned on the device: the list of each event batch goes through cf_sampler_bins (cf_sampler_bins.hip) and is dropped
+// binned on the device: fused, or the list of each event batch through cf_sampler_bins (cf_sampler_bins.hip) and dropped
 // ------------------------------------------------------------------------------------------------
 namespace {
 int check_bin_args(const is3d_sampler_test_bins *bins, const is3d_sampler_hist *h, int32_t n_events)
@@ -1087,6 +955,15 @@ int check_bin_args(const is3d_sampler_test_bins *bins, const is3d_sampler_hist *
     if (bins->kernel_form < 0 || bins->kernel_form > 2) return set_error(IS3D_EINVAL, "kernel_form = %d: 0, 1 or 2", bins->kernel_form);
     return IS3D_OK;
 }
+// ... and kernel_form = 2 on a block that the private form of the kernel that would run cannot hold
+int check_bin_args_lds(const is3d_sampler_test_bins *bins, const is3d_sampler_hist *h, int32_t n_events, int32_t n_species, bool fuse)
+{
+    if (int rc = check_bin_args(bins, h, n_events)) return rc;
+    const is3d::SamplerHistLayout l = is3d::sampler_hist_layout(*bins, n_species);
+    if (bins->kernel_form == 2 && !(fuse ? is3d::sampler_fused_lds_fits(l) : is3d::sampler_bins_lds_fits(l)))
+        return is3d::set_error(IS3D_EINVAL, "kernel_form = 2: %lld histogram words do not fit the LDS", (long long)l.total);
+    return IS3D_OK;
+}
 // the arrays of a histogram set in the order of SamplerHistLayout, with their lengths
 struct HistParts {
     int64_t *p[7];
@@ -1097,25 +974,22 @@ HistParts hist_parts(const is3d_sampler_hist &h, const is3d::SamplerHistLayout &
     return {{h.dN_dy, h.dN_deta, h.dN_pT, h.dN_tau, h.dN_r, h.vn_re, h.vn_im},
             {l.de - l.dy, l.dp - l.de, l.dt - l.dp, l.dr - l.dt, l.vr - l.dr, l.vi - l.vr, l.total - l.vi}};
 }
-// a binned run's histograms: the caller's arrays zeroed and, for a surface with cells, the plan's device block (histograms, then yields) sized and zeroed ...
-int hist_begin(is3d_sampler_plan *P, const HistParts &parts, const is3d_sampler_hist *hist, int32_t n_events, int64_t words, bool device)
+// a binned run's histograms: the caller's arrays zeroed and, where anything will be binned, the device block d_hist (histograms, then yields)
+// grown to `words` on the current device and zeroed ...
+int hist_begin(DevMem &d_hist, const HistParts &parts, const is3d_sampler_hist *hist, int32_t n_events, int64_t words, bool device)
 {
     for (int a = 0; a < 7; a++) memset(parts.p[a], 0, (size_t)parts.n[a] * sizeof(int64_t));
     memset(hist->yield, 0, (size_t)n_events * sizeof(int64_t));
     if (!device) return IS3D_OK;
-    HIP_TRY(hipSetDevice(P->device));
-    if (words > P->cap_hist) {
-        HIP_TRY(P->d_hist.alloc((size_t)words * sizeof(int64_t)));
-        P->cap_hist = words;
-    }
-    HIP_TRY(hipMemsetAsync(P->d_hist.p, 0, (size_t)words * sizeof(int64_t), nullptr));
+    if ((size_t)words * sizeof(int64_t) > d_hist.n) HIP_TRY(d_hist.alloc((size_t)words * sizeof(int64_t)));
+    HIP_TRY(hipMemsetAsync(d_hist.p, 0, (size_t)words * sizeof(int64_t), nullptr));
     return IS3D_OK;
 }
 // ... and after the last batch the one copy to the caller's arrays
-int hist_end(is3d_sampler_plan *P, const HistParts &parts, const is3d_sampler_hist *hist, int32_t n_events, int64_t words)
+int hist_end(const DevMem &d_hist, const HistParts &parts, const is3d_sampler_hist *hist, int32_t n_events, int64_t words)
 {
     std::vector<int64_t> h((size_t)words);
-    HIP_TRY(hipMemcpy(h.data(), P->d_hist.p, (size_t)words * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h.data(), d_hist.p, (size_t)words * sizeof(int64_t), hipMemcpyDeviceToHost));
     const int64_t *src = h.data();
     for (int a = 0; a < 7; a++) {
         memcpy(parts.p[a], src, (size_t)parts.n[a] * sizeof(int64_t));
@@ -1136,72 +1010,54 @@ int hist_check_counts(const HistParts &parts, const is3d_sampler_hist *hist)
 
 int is3d::sampler_check_bin_args(const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int32_t n_events, int32_t n_species)
 {
-    if (int rc = check_bin_args(bins, hist, n_events)) return rc;
-    const SamplerHistLayout l = sampler_hist_layout(*bins, n_species);
-    if (bins->kernel_form == 2 && !sampler_bins_lds_fits(l))
-        return set_error(IS3D_EINVAL, "kernel_form = 2: %lld histogram words do not fit the LDS", (long long)l.total);
-    return IS3D_OK;
+    return check_bin_args_lds(bins, hist, n_events, n_species, false);
 }
 
 int is3d::sampler_check_fused_args(const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int32_t n_events, int32_t n_species)
 {
-    if (int rc = check_bin_args(bins, hist, n_events)) return rc;
-    const SamplerHistLayout l = sampler_hist_layout(*bins, n_species);
-    if (bins->kernel_form == 2 && !fused_lds_fits(l))
-        return set_error(IS3D_EINVAL, "kernel_form = 2: %lld histogram words do not fit the LDS", (long long)l.total);
-    return IS3D_OK;
+    return check_bin_args_lds(bins, hist, n_events, n_species, true);
 }
 
 int is3d::sampler_variant_execute_binned(is3d_sampler_plan *P, const SamplerVariant &v, int64_t n_cells, const double *x_dev, const double *y_dev,
                                          int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
-                                         const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
+                                         const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, bool fuse, int64_t *n_particles,
                                          is3d_sampler_stats *stats)
 {
     *n_particles = 0;
     if (stats) memset(stats, 0, sizeof *stats);
-    if (!v.bin) return set_error(IS3D_EINVAL, "this sampler variant has no fused bin pass");
     if (n_cells < 0 || n_cells + first_cell > 0xffffffffLL) return set_error(IS3D_EINVAL, "cell indices must fit 32 bits for the counter-based streams");
-    const BinRun br{*bins, sampler_bin_widths(*bins), sampler_hist_layout(*bins, P->sp.npart), 0};
+    const BinRun br{*bins, sampler_bin_widths(*bins), sampler_hist_layout(*bins, P->sp.npart)};
     const HistParts parts = hist_parts(*hist, br.layout);
     const int64_t words = br.layout.total + n_events;
-    if (int rc = hist_begin(P, parts, hist, n_events, words, n_cells > 0)) return rc;
-    P->p.cells = CellPtrs{};
-    int64_t unused = 0;
-    const int rc = sampler_batches(P, &v, n_cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, nullptr, 0, &br, &unused, stats);
-    // a bad cell (IS3D_EDOMAIN) leaves the other cells' hadrons binned: the histograms are returned with the error
-    if (rc && rc != IS3D_EDOMAIN) return rc;
+    if (n_cells > 0) HIP_TRY(hipSetDevice(P->device));
+    if (int rc = hist_begin(P->d_hist, parts, hist, n_events, words, n_cells > 0)) return rc;
+    int64_t listed = 0;
+    const int rc = sampler_batches(P, v, n_cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, nullptr, 0, &br, fuse, &listed, stats);
+    if (rc && !(rc == IS3D_EDOMAIN && v.edomain_keeps_rest)) return rc;
     if (n_cells == 0) return IS3D_OK;
     const std::string kept = rc ? is3d_last_error() : "";
-    if (int rc2 = hist_end(P, parts, hist, n_events, words)) return rc2;
-    for (int32_t e = 0; e < n_events; e++) *n_particles += hist->yield[e];
+    if (int rc2 = hist_end(P->d_hist, parts, hist, n_events, words)) return rc2;
+    *n_particles = listed;
+    if (fuse)   // no list was counted: the hadrons are the sum of the yields
+        for (int32_t e = 0; e < n_events; e++) *n_particles += hist->yield[e];
     if (rc) return set_error(rc, "%s", kept.c_str());
     return hist_check_counts(parts, hist);
 }
 
 namespace {
-// is3d_sampler_plan_execute_binned (fused = false) | is3d_sampler_plan_execute_fused
+// is3d_sampler_plan_execute_binned (fuse = false: the list-and-bin route, the yardstick of the fused one) | is3d_sampler_plan_execute_fused
 int plan_execute_binned(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev, int32_t n_events, uint64_t seed,
                         int64_t first_cell, int32_t batch_events, const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist,
-                        int64_t *n_particles, is3d_sampler_stats *stats, bool fused)
+                        int64_t *n_particles, is3d_sampler_stats *stats, bool fuse)
 {
     using is3d::set_error;
     if (!P || !cells || !n_particles) return set_error(IS3D_EINVAL, "null argument");
     *n_particles = 0;
     if (stats) memset(stats, 0, sizeof *stats);
-    if (int rc = check_bin_args(bins, hist, n_events)) return rc;
-    const int S = P->sp.npart;
-    BinRun br{*bins, is3d::sampler_bin_widths(*bins), is3d::sampler_hist_layout(*bins, S), fused ? 1 : 0};
-    if (bins->kernel_form == 2 && !(fused ? fused_lds_fits(br.layout) : is3d::sampler_bins_lds_fits(br.layout)))
-        return set_error(IS3D_EINVAL, "kernel_form = 2: %lld histogram words do not fit the LDS", (long long)br.layout.total);
-    const HistParts parts = hist_parts(*hist, br.layout);
-    const int64_t words = br.layout.total + n_events;
-    if (int rc = hist_begin(P, parts, hist, n_events, words, cells->n_cells > 0)) return rc;
-    if (int rc = sampler_execute(P, cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, nullptr, 0, &br, n_particles, stats)) return rc;
-    if (cells->n_cells == 0) return IS3D_OK;
-    if (int rc = hist_end(P, parts, hist, n_events, words)) return rc;
-    if (fused)   // no list was counted: the hadrons are the sum of the yields
-        for (int32_t e = 0; e < n_events; e++) *n_particles += hist->yield[e];
-    return hist_check_counts(parts, hist);
+    if (int rc = check_bin_args_lds(bins, hist, n_events, P->sp.npart, fuse)) return rc;
+    if (int rc = bind_cells(P, cells, first_cell)) return rc;
+    return is3d::sampler_variant_execute_binned(P, P->viscous, cells->n_cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, bins, hist, fuse,
+                                                n_particles, stats);
 }
 }  // namespace
 
@@ -1226,7 +1082,7 @@ namespace {
 // the host-pointer entries: plan + upload + execute_binned | execute_fused
 int sample_binned(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
                   const is3d_options *opts, const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
-                  is3d_sampler_stats *stats, bool fused)
+                  is3d_sampler_stats *stats, bool fuse)
 {
     using is3d::set_error;
     if (!cells || !species || !df || !in || !opts || !n_particles) return set_error(IS3D_EINVAL, "null argument");
@@ -1234,12 +1090,12 @@ int sample_binned(const is3d_cells *cells, const is3d_species *species, const is
     if (stats) memset(stats, 0, sizeof *stats);
     if (int rc = check_bin_args(bins, hist, in->n_events)) return rc;
     // (the fused entry refuses a private form that cannot run with the bins, before the plan: no refusal of its own needs a device)
-    if (fused && species->n >= 1)
+    if (fuse && species->n >= 1)
         if (int rc = is3d::sampler_check_fused_args(bins, hist, in->n_events, species->n)) return rc;
     StagedRun r;
     if (int rc = stage_run(r, cells, species, df, in, opts)) return rc;
     const int rc = plan_execute_binned(r.P, &r.dc, r.xy[0], r.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events, bins, hist,
-                                       n_particles, stats, fused);
+                                       n_particles, stats, fuse);
     if (stats) stats->ms_h2d = r.ms_h2d;
     return rc;
 }
@@ -1269,38 +1125,22 @@ extern "C" int is3d_sampler_bin_list_device(const is3d_sampler_test_bins *bins, 
     if (int rc = check_bin_args(bins, hist, n_events)) return rc;
     if (n_species < 1) return set_error(IS3D_EINVAL, "n_species must be >= 1");
     if (n_particles < 0 || (n_particles > 0 && !particles)) return set_error(IS3D_EINVAL, "n_particles must be >= 0 and particles non-null");
-    const is3d::SamplerHistLayout l = is3d::sampler_hist_layout(*bins, n_species);
-    if (bins->kernel_form == 2 && !is3d::sampler_bins_lds_fits(l))
-        return set_error(IS3D_EINVAL, "kernel_form = 2: %lld histogram words do not fit the LDS", (long long)l.total);
+    if (int rc = is3d::sampler_check_bin_args(bins, hist, n_events, n_species)) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return set_error(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
+    const is3d::SamplerHistLayout l = is3d::sampler_hist_layout(*bins, n_species);
     const HistParts parts = hist_parts(*hist, l);
-    for (int a = 0; a < 7; a++) memset(parts.p[a], 0, (size_t)parts.n[a] * sizeof(int64_t));
-    memset(hist->yield, 0, (size_t)n_events * sizeof(int64_t));
-    if (n_particles == 0) return IS3D_OK;
-    if (device >= 0) HIP_TRY(hipSetDevice(device));
     const int64_t words = l.total + n_events;
     DevMem d_list, d_hist;
-    HIP_TRY(d_list.alloc((size_t)n_particles * sizeof(is3d_particle)));
-    HIP_TRY(d_hist.alloc((size_t)words * sizeof(int64_t)));
-    HIP_TRY(hipMemcpy(d_list.p, particles, (size_t)n_particles * sizeof(is3d_particle), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(d_hist.p, 0, (size_t)words * sizeof(int64_t), nullptr));
+    if (n_particles > 0 && device >= 0) HIP_TRY(hipSetDevice(device));
+    if (int rc = hist_begin(d_hist, parts, hist, n_events, words, n_particles > 0)) return rc;
+    if (n_particles == 0) return IS3D_OK;
+    HIP_TRY(d_list.upload(particles, (size_t)n_particles));
     HIP_TRY(is3d::sampler_bins_launch(*bins, is3d::sampler_bin_widths(*bins), l, n_species, n_events, d_list.as<is3d_particle>(), n_particles,
                                       d_hist.as<unsigned long long>(), d_hist.as<unsigned long long>() + l.total, bins->kernel_form));
-    std::vector<int64_t> h((size_t)words);
-    HIP_TRY(hipMemcpy(h.data(), d_hist.p, (size_t)words * sizeof(int64_t), hipMemcpyDeviceToHost));
-    const int64_t *src = h.data();
-    for (int a = 0; a < 7; a++) {
-        memcpy(parts.p[a], src, (size_t)parts.n[a] * sizeof(int64_t));
-        src += parts.n[a];
-    }
-    memcpy(hist->yield, src, (size_t)n_events * sizeof(int64_t));
+    if (int rc = hist_end(d_hist, parts, hist, n_events, words)) return rc;
     int64_t counted = 0;
     for (int32_t e = 0; e < n_events; e++) counted += hist->yield[e];
     *n_skipped = n_particles - counted;
-    for (int64_t j = 0; j < parts.n[2]; j++)
-        if (hist->dN_pT[j] > IS3D_SAMPLER_VN_MAX_COUNT)
-            return set_error(IS3D_EDOMAIN, "dN_pT bin %lld holds %lld hadrons: the fixed-point harmonic sums are exact up to %lld per bin", (long long)j,
-                             (long long)hist->dN_pT[j], (long long)IS3D_SAMPLER_VN_MAX_COUNT);
-    return IS3D_OK;
+    return hist_check_counts(parts, hist);
 }

@@ -1,15 +1,18 @@
 // cf_sampler_common.h -- what the particle samplers share (cf_sampler.hip: viscous hydro; cf_sampler_vah.hip: anisotropic hydro): the per-cell
 // record, the species and parameter blocks, the Philox streams, the Gauss-Laguerre integrands, the species weights with their blocked
-// running sums, the momentum sampler -- device code, inlined into each file's kernels -- and the host entries through which the
-// anisotropic-hydro sampler runs its two kernels inside the viscous sampler's plan and batch loop (density integrals, Poisson numbers,
-// hipCUB compaction and scan: cf_sampler.hip).
+// running sums, the momentum sampler, the per-pair loop and the two kernels that run it (cf_sampler_run, cf_sampler_fused: templates over
+// the route's Model) -- device code, instantiated in each file -- and on the host the launch rule of each kernel and the entries through
+// which a route runs as a SamplerVariant of the one plan and batch loop (density integrals, Poisson numbers, hipCUB compaction and scan:
+// cf_sampler.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
 
 #include "../../include/is3d_amd.h"
 #include "cf_device.h"
@@ -303,8 +306,7 @@ __device__ __forceinline__ void sampler_tally(const SamplerParams &p, const unsi
     if (threadIdx.x < 3 && blk[threadIdx.x]) atomicAdd(&p.status[2 + threadIdx.x], blk[threadIdx.x]);
 }
 
-// ---- what a pass does with a kept hadron: the one thing in which count, fill and bin differ (sample_pair of cf_sampler.hip,
-// vah_sample_pair of cf_sampler_vah.hip) ----
+// ---- what a pass does with a kept hadron: the one thing in which count, fill and bin differ (sample_pair) ----
 struct SamplerKeepCount {
     __device__ __forceinline__ void operator()(const is3d_particle &) {}
 };
@@ -369,12 +371,149 @@ __device__ __forceinline__ void sampler_yield_runs(int ev, long long kept, unsig
     if (lead && ev != INT_MAX && run) atomicAdd(&yield[ev], (unsigned long long)run);
 }
 
-// the geometry of a fused bin pass (cf_sampler_fused, cf_sampler_vah_bin)
+// ---- the sampling kernels, written once for every route ----
+// A Model is the small struct, passed by value to the kernels, that holds what differs between the routes (ViscousModel of cf_sampler.hip,
+// VahModel of cf_sampler_vah.hip):
+//   gt2, gt3   the J20 / J10 integral tables choose_species reads beside GT (null where the route has none)
+//   Pair       what the route keeps per (event, cell) pair beside the cell record: Pair pair(p, c, ic)
+//   draw       one momentum of the chosen species in the LRF with its viscous weight, from the momentum stream:
+//              double draw(p, sp, c, pair, chosen, mass, mass_squared, sign, g_momentum, acceptances, samples, q) -> w_visc
+//
+// one emitting (event, cell) pair: the ONE piece of source the count, the fill and the fused bin pass of every route run.  ic is the pair's
+// cell, ievent its event; every kept hadron goes to keep() as the is3d_particle of the list.  Returns the number kept; tally[] gets the
+// pair's momentum samples, acceptances and hadrons drawn.
+template <class Model, class Keep>
+__device__ __forceinline__ long sample_pair(const SamplerParams &p, const SamplerSpecies &sp, const SamplerCell *__restrict__ cellrec,
+                                            const double *__restrict__ GT, const Model &model, int ievent, int64_t ic, long N_hadrons,
+                                            Keep &keep, unsigned long long (&tally)[3])
+{
+    const SamplerCell &c = cellrec[ic];
+    const typename Model::Pair pair = model.pair(p, c, ic);
+    const uint32_t gcell = (uint32_t)(p.first_cell + ic);
+    Rng g_type, g_momentum, g_keep, g_rapidity;
+    g_type.init(p.seed, 1, gcell, (uint32_t)ievent);
+    g_momentum.init(p.seed, 2, gcell, (uint32_t)ievent);
+    g_keep.init(p.seed, 3, gcell, (uint32_t)ievent);
+    g_rapidity.init(p.seed, 4, gcell, (uint32_t)ievent);
+    const double *gt = GT + ic, *gt2 = model.gt2 ? model.gt2 + ic : nullptr, *gt3 = model.gt3 ? model.gt3 + ic : nullptr;
+    const double sinheta = sinh(c.eta), cosheta = sqrt(1.0 + sinheta * sinheta);   // :888-889
+    long kept = 0, samples = 0, acceptances = 0;
+    for (long ih = 0; ih < N_hadrons; ih++) {
+        const double ut_ = g_type.uniform() * c.dn_sum;
+        const int chosen = choose_species(p, sp, c, gt, gt2, gt3, ic, ut_);
+        const double mass = sp.mass[chosen], mass_squared = mass * mass, sign = sp.sign[chosen];
+        LrfMom q;
+        const double w_visc = model.draw(p, sp, c, pair, chosen, mass, mass_squared, sign, g_momentum, acceptances, samples, q);
+        // boost_pLRF_to_lab_frame (emissionfunction.cpp:40-51)
+        const double ptau = q.E * c.ut + q.px * c.Xt + q.pz * c.Zt;
+        const double plx = q.E * c.ux + q.px * c.Xx + q.py * c.Yx;
+        const double ply = q.E * c.uy + q.px * c.Xy + q.py * c.Yy;
+        const double pn = q.E * c.un + q.px * c.Xn + q.pz * c.Zn;
+        const double w_flux = fmax(0.0, q.E * c.dst - q.px * c.dsx - q.py * c.dsy - q.pz * c.dsz) / (q.E * c.ds_max);   // :1148
+        if (!(g_keep.uniform() < (w_flux * w_visc))) continue;
+        double Elab, pz, eta = c.eta, sh = sinheta, ch = cosheta;
+        if (!p.dim3) {                                                              // :1168-1186
+            const double yp = p.y_max * (2.0 * g_rapidity.uniform() - 1.0);
+            const double sinhy = sinh(yp), coshy = sqrt(1.0 + sinhy * sinhy);
+            const double tau_pn = c.tau * pn, mT = sqrt(mass_squared + plx * plx + ply * ply);
+            sh = (ptau * sinhy - tau_pn * coshy) / mT;
+            eta = asinh(sh);
+            ch = sqrt(1.0 + sh * sh);
+            pz = mT * sinhy;
+            Elab = mT * coshy;
+        } else {
+            pz = c.tau * pn * ch + ptau * sh;
+            Elab = sqrt(mass_squared + plx * plx + ply * ply + pz * pz);
+        }
+        is3d_particle o;
+        o.cell = p.first_cell + ic; o.event = ievent; o.species = chosen;
+        o.tau = c.tau; o.x = c.x; o.y = c.y; o.eta = eta; o.t = c.tau * ch; o.z = c.tau * sh;
+        o.E = Elab; o.px = plx; o.py = ply; o.pz = pz;
+        keep(o);
+        kept++;
+    }
+    tally[0] += (unsigned long long)samples; tally[1] += (unsigned long long)acceptances; tally[2] += (unsigned long long)N_hadrons;
+    return kept;
+}
+
+// the geometry of the two kernels
+constexpr int kRunThreads = 128;
 constexpr int kFusedBinThreads = 256;
 constexpr int kFusedBinPrivateBlocks = 768;   // workgroup-private form: at most this many flushes (three 43 KiB blocks per CU of 160 KiB LDS)
 
-// ---- host: a sampler variant inside the viscous sampler's plan and batch loop (cf_sampler.hip) ----
-// what one launch of a variant's run kernel gets: the arguments of cf_sampler_run
+// thread <-> emitting (event, cell) pair: the count pass (counts[] and the run-wide tallies) and the fill pass of the list route
+template <class Model, bool FILL>
+__global__ void __launch_bounds__(kRunThreads)
+cf_sampler_run(SamplerParams p, SamplerSpecies sp, const SamplerCell *__restrict__ cellrec, const double *__restrict__ GT, Model model,
+               int event0, const int32_t *__restrict__ active, int64_t n_active, const int32_t *__restrict__ n_drawn,
+               int64_t *__restrict__ counts, const int64_t *__restrict__ offsets, int64_t base, is3d_particle *__restrict__ particles,
+               int64_t capacity)
+{
+    unsigned long long tally[3] = {0ULL, 0ULL, 0ULL};
+    const int64_t ia = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // position in the list of emitting (event, cell) pairs
+    if (ia < n_active && !(FILL && offsets[ia + 1] == offsets[ia])) {       // (fill: pass 1 kept nothing here, nothing to replay)
+        const int64_t idx = active[ia];                                     // event-major: (event - event0) * n_cells + cell
+        const int ievent = event0 + (int)(idx / p.n_cells);
+        const int64_t ic = idx % p.n_cells;
+        const long N_hadrons = n_drawn[idx];                                // cf_sampler_poisson (stream 0)
+        if (FILL) {
+            SamplerKeepFill keep{particles, base + offsets[ia], capacity};
+            sample_pair(p, sp, cellrec, GT, model, ievent, ic, N_hadrons, keep, tally);
+        } else {
+            SamplerKeepCount keep;
+            counts[ia] = sample_pair(p, sp, cellrec, GT, model, ievent, ic, N_hadrons, keep, tally);
+        }
+    }
+    if (!FILL) sampler_tally(p, tally);
+}
+
+// The fused pass of a binned run: the count pass's threads, streams and loop, every kept hadron added straight into the histograms of
+// cf_sampler_bins (the same rule, cf_sampler_bins.h, on the same is3d_particle the fill pass would store) -- no list, so no counts,
+// offsets, scan or particle workspace.  Every add is a 64-bit integer, so the histograms are those of the list route bit for bit
+// whatever the order of arrival.
+//   PRIVATE: the whole block lives in dynamic LDS (ds_add_u64), at most kFusedBinPrivateBlocks workgroups walk the pair list grid-stride
+//            and each flushes its non-zero words once with global adds
+//   else:    every add goes straight to the global block (305 species: 305 x 1800 words)
+// Per-event yields: sampler_yield_runs after the rejection loop, with the wave reconverged; lanes past n_active take part with event
+// INT_MAX and kept = 0.  The trip count is the same for every thread of a workgroup: the wave operations see whole waves and the barriers
+// every thread; none of either sits inside the per-hadron loop.
+template <class Model, bool PRIVATE>
+__global__ void __launch_bounds__(kFusedBinThreads, 2)
+cf_sampler_fused(SamplerParams p, SamplerSpecies sp, const SamplerCell *__restrict__ cellrec, const double *__restrict__ GT, Model model,
+                 int event0, const int32_t *__restrict__ active, int64_t n_active, const int32_t *__restrict__ n_drawn, SamplerBinArgs a,
+                 unsigned long long *__restrict__ hist, unsigned long long *__restrict__ yield)
+{
+    extern __shared__ unsigned long long priv[];
+    if (PRIVATE) {
+        for (int64_t j = threadIdx.x; j < a.l.total; j += kFusedBinThreads) priv[j] = 0ULL;
+        __syncthreads();
+    }
+    SamplerKeepBin keep{a, PRIVATE ? priv : hist};
+    unsigned long long tally[3] = {0ULL, 0ULL, 0ULL};
+    for (int64_t i0 = (int64_t)blockIdx.x * kFusedBinThreads; i0 < n_active; i0 += (int64_t)gridDim.x * kFusedBinThreads) {
+        const int64_t ia = i0 + threadIdx.x;
+        int ev = INT_MAX;
+        long long kept = 0;
+        if (ia < n_active) {
+            const int64_t idx = active[ia];
+            ev = event0 + (int)(idx / p.n_cells);
+            kept = sample_pair(p, sp, cellrec, GT, model, ev, idx % p.n_cells, (long)n_drawn[idx], keep, tally);
+        }
+        sampler_yield_runs(ev, kept, yield);
+    }
+    sampler_tally(p, tally);
+    if (PRIVATE) {
+        __syncthreads();
+        for (int64_t j = threadIdx.x; j < a.l.total; j += kFusedBinThreads) {
+            const unsigned long long v = priv[j];
+            if (v) atomicAdd(&hist[j], v);
+        }
+    }
+}
+
+// ---- host: the launch rule of each kernel, a sampler variant, and the plan and batch loop every variant runs in (cf_sampler.hip) ----
+// what one launch gets beside the plan's parameters and species: the arguments of cf_sampler_run; a fused pass reads rec, GT, event0,
+// active, n_active and n_drawn only
 struct SamplerRunArgs {
     const SamplerCell *rec;
     const double *GT;
@@ -388,50 +527,90 @@ struct SamplerRunArgs {
     is3d_particle *particles;
     int64_t capacity;
 };
-// the bins of a binned run with what follows from them (is3d_sampler_plan_execute_binned, sampler_variant_execute_binned)
-// fused: the viscous route samples and bins in one pass too (cf_sampler_fused) instead of filling and binning a list per batch; a variant
-// with a bin hook always does
+// the bins of a binned run with what follows from them
 struct SamplerBinRun {
     is3d_sampler_test_bins bins;
     SamplerBinWidths widths;
     SamplerHistLayout layout;
-    int fused;
 };
-// T: the DEVICE array the density integrals take as temperature; cells: writes the records (live, dn_sum, dn_tot and the running sums as
-// cf_sampler_cells does; status[0], [1]) after the density kernel, returns an IS3D code; run: the count (fill = false) or fill pass on `grid`
-// workgroups of 128; domain_text: what IS3D_EDOMAIN says after "cell N: ".
-// bin (optional): the fused pass of a binned run -- the emitting pairs of a.active sampled once and every kept hadron added straight into
-// hist_dev (layout b.layout) and yield_dev (one word per event of the run); of a, only rec, GT, event0, active, n_active and n_drawn are set
+
+// the count (fill = false) or fill pass: one thread per emitting pair
+template <class Model>
+void launch_run(const void *model, bool fill, const SamplerParams &p, const SamplerSpecies &sp, const SamplerRunArgs &a)
+{
+    const dim3 grid((unsigned)((a.n_active + kRunThreads - 1) / kRunThreads)), block(kRunThreads);
+    const auto kernel = fill ? cf_sampler_run<Model, true> : cf_sampler_run<Model, false>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, nullptr, p, sp, a.rec, a.GT, *(const Model *)model, a.event0, a.active, a.n_active, a.n_drawn,
+                       a.counts, a.offsets, a.base, a.particles, a.capacity);
+}
+
+// Both forms of cf_sampler_fused keep the three words of sampler_tally in static LDS beside the dynamic block, so a private block fits
+// when block + 3 words <= 64 KiB (8189 words): THE rule of every fused entry.  kernel_form 0 takes the global form on a block beyond it,
+// kernel_form 2 is refused there (sampler_check_fused_args).
+inline bool sampler_fused_lds_fits(const SamplerHistLayout &l) { return l.total + 3 <= (int64_t)(65536 / sizeof(unsigned long long)); }
+
+// the fused pass: one launch per event batch.  Private form: at most kFusedBinPrivateBlocks workgroups, each walking the pair list
+// grid-stride; global form: one trip per thread
+template <class Model>
+void launch_fused(const void *model, const SamplerParams &p, const SamplerSpecies &sp, const SamplerRunArgs &a, const SamplerBinRun &b,
+                  unsigned long long *hist_dev, unsigned long long *yield_dev)
+{
+    const bool priv = b.bins.kernel_form == 2 || (b.bins.kernel_form == 0 && sampler_fused_lds_fits(b.layout));
+    const int64_t trips = (a.n_active + kFusedBinThreads - 1) / kFusedBinThreads;
+    const dim3 grid((unsigned)(priv ? std::min<int64_t>(trips, kFusedBinPrivateBlocks) : trips)), block(kFusedBinThreads);
+    const auto kernel = priv ? cf_sampler_fused<Model, true> : cf_sampler_fused<Model, false>;
+    hipLaunchKernelGGL(kernel, grid, block, priv ? (size_t)b.layout.total * sizeof(unsigned long long) : 0, nullptr, p, sp, a.rec, a.GT,
+                       *(const Model *)model, a.event0, a.active, a.n_active, a.n_drawn, SamplerBinArgs{b.bins, b.widths, b.layout, sp.npart},
+                       hist_dev, yield_dev);
+}
+
+// A sampler route inside the plan and batch loop: the viscous sampler is the variant of its own plan (cf_sampler.hip), the anisotropic-hydro
+// sampler one on a plan without coefficient tables (cf_sampler_vah.hip).
+//   T, muB        the DEVICE arrays the density integrals take as temperature and chemical potential (muB NULL: none)
+//   cells         writes the records (live, dn_sum, dn_tot and the running sums as cf_sampler_cells does; status[0], [1]) after the density
+//                 kernel and readies *model; returns an IS3D code
+//   model         the route's Model with its two launch rules (set_model)
+//   domain_text   what IS3D_EDOMAIN says after "cell N: "
+//   edomain_keeps_rest   the one difference in behaviour between the families: after IS3D_EDOMAIN the list or the histograms of the good
+//                 cells are still returned with the error (anisotropic hydro) or the entry returns at once (viscous hydro)
 struct SamplerVariant {
-    const double *T;
-    const char *domain_text;
-    void *ctx;
-    int (*cells)(void *ctx, const SamplerParams &p, const SamplerSpecies &sp, const double *GT, SamplerCell *rec);
-    void (*run)(void *ctx, bool fill, unsigned grid, const SamplerParams &p, const SamplerSpecies &sp, const SamplerRunArgs &a);
-    void (*bin)(void *ctx, const SamplerParams &p, const SamplerSpecies &sp, const SamplerRunArgs &a, const SamplerBinRun &b,
-                unsigned long long *hist_dev, unsigned long long *yield_dev);
+    const double *T = nullptr, *muB = nullptr;
+    std::string domain_text;
+    bool edomain_keeps_rest = false;
+    void *ctx = nullptr;
+    int (*cells)(void *ctx, const SamplerParams &p, const SamplerSpecies &sp, const double *GT, SamplerCell *rec) = nullptr;
+    const void *model = nullptr;
+    void (*run)(const void *model, bool fill, const SamplerParams &p, const SamplerSpecies &sp, const SamplerRunArgs &a) = nullptr;
+    void (*fused)(const void *model, const SamplerParams &p, const SamplerSpecies &sp, const SamplerRunArgs &a, const SamplerBinRun &b,
+                  unsigned long long *hist_dev, unsigned long long *yield_dev) = nullptr;
+    template <class Model>
+    void set_model(const Model *m) { model = m; run = launch_run<Model>; fused = launch_fused<Model>; }
 };
 // a plan with the species classes, the alpha = 1 Gauss-Laguerre nodes and the workspaces, without coefficient tables: df_mode 1 weights
 // (2 neq_fact g GT), regular mode.  The argument checks come before any device use.
 int sampler_variant_plan_create(is3d_sampler_plan **out, const is3d_species *species, const is3d_sampler_inputs *in, const is3d_options *opts,
                                 int64_t max_cells);
-// is3d_sampler_plan_execute with the variant's kernels in place of cf_sampler_cells and cf_sampler_run; the caller has checked its cells
+// the list of a run (particles_dev: DEVICE buffer of `capacity` entries, or NULL for the count); the caller has checked its cells
 int sampler_variant_execute(is3d_sampler_plan *P, const SamplerVariant &v, int64_t n_cells, const double *x_dev, const double *y_dev,
                             int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev,
                             int64_t capacity, int64_t *n_particles, is3d_sampler_stats *stats);
-// a binned run of a variant that has a bin hook: per event batch Poisson, select and ONE launch of the hook -- no counts, offsets, scan or
-// particle workspace exist on this path.  The histograms live in the plan (zeroed before the first batch) and are copied to hist_host
-// (HOST arrays, overwritten) once after the last batch, also when a bad cell gives IS3D_EDOMAIN; *n_particles is the sum of the yields.
-// stats: ms_bin is the time of the fused passes; ms_count, ms_fill and particle_workspace_bytes are 0.  The caller has checked bins and
-// hist (sampler_check_bin_args).
+// ... and the tail of the host-pointer list entries: the device buffer, the run of `in`, and the copy to `particles` (HOST, or NULL for the
+// count) -- also after IS3D_ENOMEM and, for a variant with edomain_keeps_rest, IS3D_EDOMAIN, with the error's text kept
+int sampler_variant_sample_list(is3d_sampler_plan *P, const SamplerVariant &v, int64_t n_cells, const double *x_dev, const double *y_dev,
+                                const is3d_sampler_inputs *in, float ms_h2d, is3d_particle *particles, int64_t capacity, int64_t *n_particles,
+                                is3d_sampler_stats *stats);
+// A binned run.  fuse: per event batch Poisson, select and ONE launch of cf_sampler_fused -- no counts, offsets, scan or particle workspace
+// exist on this path (stats: ms_bin is the time of the fused passes; ms_count, ms_fill and particle_workspace_bytes are 0); else each
+// batch's list is counted, scanned, filled into the plan's workspace, binned by cf_sampler_bins and dropped.  The histograms live in the
+// plan (zeroed before the first batch) and are copied to hist_host (HOST arrays, overwritten) once after the last batch; *n_particles is
+// the number of hadrons binned.  The caller has checked bins and hist (sampler_check_bin_args | sampler_check_fused_args) and its cells.
 int sampler_variant_execute_binned(is3d_sampler_plan *P, const SamplerVariant &v, int64_t n_cells, const double *x_dev, const double *y_dev,
                                    int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events, const is3d_sampler_test_bins *bins,
-                                   const is3d_sampler_hist *hist_host, int64_t *n_particles, is3d_sampler_stats *stats);
-// the bin checks of is3d_sample_binned (IS3D_EINVAL, no device use): null, bad bins, kernel_form outside 0..2, and kernel_form = 2 on a
-// histogram block of n_species species that does not fit the LDS
+                                   const is3d_sampler_hist *hist_host, bool fuse, int64_t *n_particles, is3d_sampler_stats *stats);
+// the bin checks of the list kernel's entries (is3d_sample_binned, is3d_sampler_bin_list_device; IS3D_EINVAL, no device use): null, bad
+// bins, kernel_form outside 0..2, and kernel_form = 2 on a histogram block of n_species species beyond sampler_bins_lds_fits (8192 words)
 int sampler_check_bin_args(const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int32_t n_events, int32_t n_species);
-// the same for the viscous fused entries (is3d_sample_fused): the private form needs room for the three tally words of sampler_tally beside
-// the block
+// the same for every fused entry, viscous and anisotropic: kernel_form = 2 needs sampler_fused_lds_fits
 int sampler_check_fused_args(const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int32_t n_events, int32_t n_species);
 
 // is3d_sample_particles_vah's refusals (IS3D_EINVAL), all before any device use: also what is3d_sample_particles_vah_multi checks first

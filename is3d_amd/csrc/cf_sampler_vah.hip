@@ -26,8 +26,8 @@
 //
 //   cf_sampler_vah_cells  thread <-> cell: the record (SamplerCell: T = Lambda, pi.. = pi_perp in the LRF, V. = W in the LRF, bulkPi = the residual
 //                         bulk pressure, c0..c4; VahCellExtra: alpha_L and the tensor components along u), the running sums, dn_tot
-//   cf_sampler_vah_run    thread <-> emitting (event, cell) pair: count pass and fill pass, as cf_sampler_run
-//   cf_sampler_vah_bin    the same pairs sampled once and binned as cf_sampler_bins does, without a list (is3d_sample_binned_vah)
+//   cf_sampler_run        thread <-> emitting (event, cell) pair: count pass and fill pass (cf_sampler_common.h, with VahModel)
+//   cf_sampler_fused      the same pairs sampled once and binned as cf_sampler_bins does, without a list (is3d_sample_binned_vah)
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -156,34 +156,21 @@ cf_sampler_vah_cells(SamplerParams p, SamplerSpecies sp, VahSamplerCells v, cons
     out[ic] = c; extra[ic] = x;
 }
 
-// one emitting (event, cell) pair, as sample_pair of cf_sampler.hip with the VAH momentum map and weight: the ONE piece of source the
-// count, the fill and the bin pass run.  idx is the pair's event-major index (event - event0) * n_cells + cell; every kept hadron goes to
-// keep() as the is3d_particle of the list.  Returns the number kept; tally[] gets the pair's momentum samples, acceptances and hadrons drawn.
-template <class Keep>
-__device__ __forceinline__ long vah_sample_pair(const SamplerParams &p, const SamplerSpecies &sp, const SamplerCell *__restrict__ cellrec,
-                                                const VahCellExtra *__restrict__ extra, const double *__restrict__ GT, int ievent, int64_t ic,
-                                                long N_hadrons, Keep &keep, unsigned long long (&tally)[3])
-{
-    const SamplerCell &c = cellrec[ic];
-    const VahCellExtra x = extra[ic];
-    const uint32_t gcell = (uint32_t)(p.first_cell + ic);
-    Rng g_type, g_momentum, g_keep, g_rapidity;
-    g_type.init(p.seed, 1, gcell, (uint32_t)ievent);
-    g_momentum.init(p.seed, 2, gcell, (uint32_t)ievent);
-    g_keep.init(p.seed, 3, gcell, (uint32_t)ievent);
-    g_rapidity.init(p.seed, 4, gcell, (uint32_t)ievent);
-    const double *gt = GT + ic;
-    const double sinheta = sinh(c.eta), cosheta = sqrt(1.0 + sinheta * sinheta);
-    long kept = 0, samples = 0, acceptances = 0;
-    for (long ih = 0; ih < N_hadrons; ih++) {
-        const double ut_ = g_type.uniform() * c.dn_sum;
-        const int chosen = choose_species(p, sp, c, gt, nullptr, nullptr, ic, ut_);
-        const double mass = sp.mass[chosen], mass_squared = mass * mass, sign = sp.sign[chosen];
+// the anisotropic-hydro route's Model (cf_sampler_common.h): no tables beside GT; per pair the cell's VahCellExtra; per hadron an isotropic
+// draw at Lambda stretched by alpha_L along z, with the residual delta-f (smooth_kernels.cpp:2323-2342) as the viscous weight
+struct VahModel {
+    static constexpr const double *gt2 = nullptr, *gt3 = nullptr;
+    const VahCellExtra *extra;
+    using Pair = VahCellExtra;
+    __device__ __forceinline__ Pair pair(const SamplerParams &, const SamplerCell &, int64_t ic) const { return extra[ic]; }
+    __device__ __forceinline__ double draw(const SamplerParams &p, const SamplerSpecies &, const SamplerCell &c, Pair x, int,
+                                           double mass, double mass_squared, double sign, Rng &g_momentum, long &acceptances, long &samples,
+                                           LrfMom &q) const
+    {
         const LrfMom m = sample_momentum(g_momentum, acceptances, samples, mass, sign, c.T, 0.0);
-        LrfMom q;
         q.px = m.px; q.py = m.py; q.pz = x.aL * m.pz;
         q.E = sqrt(mass_squared + q.px * q.px + q.py * q.py + q.pz * q.pz);
-        // the residual delta-f (smooth_kernels.cpp:2323-2342) at this momentum; E_a = m.E
+        // the residual delta-f at this momentum; E_a = m.E
         double df = 0.0;
         if (p.include_shear) {
             const double pimunu_pmu_pnu = q.E * (q.E * x.piuu + 2.0 * (q.px * x.piux + q.py * x.piuy + q.pz * x.piuz))
@@ -194,109 +181,9 @@ __device__ __forceinline__ long vah_sample_pair(const SamplerParams &p, const Sa
         }
         if (p.include_bulk) df += (c.c0 * mass_squared + c.c1 * q.pz * q.pz + c.c2 * q.E * q.E) * c.bulkPi;
         const double fabar = 1.0 - sign / (exp(m.E / c.T) + sign);
-        const double w_visc = (1.0 + fmax(-1.0, fmin(fabar * df, 1.0))) / 2.0;
-        // boost_pLRF_to_lab_frame (emissionfunction.cpp:40-51)
-        const double ptau = q.E * c.ut + q.px * c.Xt + q.pz * c.Zt;
-        const double plx = q.E * c.ux + q.px * c.Xx + q.py * c.Yx;
-        const double ply = q.E * c.uy + q.px * c.Xy + q.py * c.Yy;
-        const double pn = q.E * c.un + q.px * c.Xn + q.pz * c.Zn;
-        const double w_flux = fmax(0.0, q.E * c.dst - q.px * c.dsx - q.py * c.dsy - q.pz * c.dsz) / (q.E * c.ds_max);   // :1148
-        if (!(g_keep.uniform() < (w_flux * w_visc))) continue;
-        double Elab, pz, eta = c.eta, sh = sinheta, ch = cosheta;
-        if (!p.dim3) {                                                          // :1168-1186
-            const double yp = p.y_max * (2.0 * g_rapidity.uniform() - 1.0);
-            const double sinhy = sinh(yp), coshy = sqrt(1.0 + sinhy * sinhy);
-            const double tau_pn = c.tau * pn, mT = sqrt(mass_squared + plx * plx + ply * ply);
-            sh = (ptau * sinhy - tau_pn * coshy) / mT;
-            eta = asinh(sh);
-            ch = sqrt(1.0 + sh * sh);
-            pz = mT * sinhy;
-            Elab = mT * coshy;
-        } else {
-            pz = c.tau * pn * ch + ptau * sh;
-            Elab = sqrt(mass_squared + plx * plx + ply * ply + pz * pz);
-        }
-        is3d_particle o;
-        o.cell = p.first_cell + ic; o.event = ievent; o.species = chosen;
-        o.tau = c.tau; o.x = c.x; o.y = c.y; o.eta = eta; o.t = c.tau * ch; o.z = c.tau * sh;
-        o.E = Elab; o.px = plx; o.py = ply; o.pz = pz;
-        keep(o);
-        kept++;
+        return (1.0 + fmax(-1.0, fmin(fabar * df, 1.0))) / 2.0;
     }
-    tally[0] += (unsigned long long)samples; tally[1] += (unsigned long long)acceptances; tally[2] += (unsigned long long)N_hadrons;
-    return kept;
-}
-
-// thread <-> emitting (event, cell) pair: the count pass (counts[] and the run-wide tallies) and the fill pass of the list route
-template <bool FILL>
-__global__ void __launch_bounds__(128)
-cf_sampler_vah_run(SamplerParams p, SamplerSpecies sp, const SamplerCell *__restrict__ cellrec, const VahCellExtra *__restrict__ extra,
-                   const double *__restrict__ GT, int event0, const int32_t *__restrict__ active, int64_t n_active,
-                   const int32_t *__restrict__ n_drawn, int64_t *__restrict__ counts, const int64_t *__restrict__ offsets, int64_t base,
-                   is3d_particle *__restrict__ particles, int64_t capacity)
-{
-    unsigned long long tally[3] = {0ULL, 0ULL, 0ULL};
-    const int64_t ia = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // position in the list of emitting (event, cell) pairs
-    if (ia < n_active && !(FILL && offsets[ia + 1] == offsets[ia])) {
-        const int64_t idx = active[ia];                                     // event-major: (event - event0) * n_cells + cell
-        const int ievent = event0 + (int)(idx / p.n_cells);
-        const int64_t ic = idx % p.n_cells;
-        const long N_hadrons = n_drawn[idx];                                // cf_sampler_poisson (stream 0)
-        if (FILL) {
-            SamplerKeepFill keep{particles, base + offsets[ia], capacity};
-            vah_sample_pair(p, sp, cellrec, extra, GT, ievent, ic, N_hadrons, keep, tally);
-        } else {
-            SamplerKeepCount keep;
-            counts[ia] = vah_sample_pair(p, sp, cellrec, extra, GT, ievent, ic, N_hadrons, keep, tally);
-        }
-    }
-    if (!FILL) sampler_tally(p, tally);
-}
-
-// The bin pass: the count pass's threads, streams and loop, every kept hadron added straight into the histograms of cf_sampler_bins
-// (the same rule, cf_sampler_bins.h, on the same is3d_particle the fill pass would store) -- no list, so no counts, offsets or scan.
-// Every add is a 64-bit integer, so the histograms are those of the list route bit for bit whatever the order of arrival.
-//   PRIVATE: the whole block lives in dynamic LDS (ds_add_u64), a bounded number of workgroups walks the pair list grid-stride and each
-//            flushes its non-zero words once with global adds
-//   else:    every add goes straight to the global block
-// Per-event yields: the pairs are event-major, so the lanes of a wave see runs of equal events; after the rejection loop, with the wave
-// reconverged, the first lane of a run adds the run's kept hadrons (a segmented sum over an inclusive wave scan) -- one add per distinct
-// event per wave and trip.  Lanes past n_active take part with event INT_MAX and kept = 0.  The trip count is the same for every thread
-// of a workgroup: the wave operations see whole waves and the barriers every thread.
-template <bool PRIVATE>
-__global__ void __launch_bounds__(kFusedBinThreads, 2)
-cf_sampler_vah_bin(SamplerParams p, SamplerSpecies sp, const SamplerCell *__restrict__ cellrec, const VahCellExtra *__restrict__ extra,
-                   const double *__restrict__ GT, int event0, const int32_t *__restrict__ active, int64_t n_active,
-                   const int32_t *__restrict__ n_drawn, SamplerBinArgs a, unsigned long long *__restrict__ hist,
-                   unsigned long long *__restrict__ yield)
-{
-    extern __shared__ unsigned long long priv[];
-    if (PRIVATE) {
-        for (int64_t j = threadIdx.x; j < a.l.total; j += kFusedBinThreads) priv[j] = 0ULL;
-        __syncthreads();
-    }
-    SamplerKeepBin keep{a, PRIVATE ? priv : hist};
-    unsigned long long tally[3] = {0ULL, 0ULL, 0ULL};
-    for (int64_t i0 = (int64_t)blockIdx.x * kFusedBinThreads; i0 < n_active; i0 += (int64_t)gridDim.x * kFusedBinThreads) {
-        const int64_t ia = i0 + threadIdx.x;
-        int ev = INT_MAX;
-        long long kept = 0;
-        if (ia < n_active) {
-            const int64_t idx = active[ia];
-            ev = event0 + (int)(idx / p.n_cells);
-            kept = vah_sample_pair(p, sp, cellrec, extra, GT, ev, idx % p.n_cells, (long)n_drawn[idx], keep, tally);
-        }
-        sampler_yield_runs(ev, kept, yield);
-    }
-    sampler_tally(p, tally);
-    if (PRIVATE) {
-        __syncthreads();
-        for (int64_t j = threadIdx.x; j < a.l.total; j += kFusedBinThreads) {
-            const unsigned long long v = priv[j];
-            if (v) atomicAdd(&hist[j], v);
-        }
-    }
-}
+};
 
 }  // namespace is3d
 
@@ -307,12 +194,13 @@ namespace {
 
 using DevMem = is3d::DevBuf<unsigned char>;
 
-// what the two hooks of the batch loop need
+// what the variant's cells hook needs, and the model its launches read
 struct VahRun {
     is3d::VahSamplerCells v{};
     const is3d_vah_df_tables *tab = nullptr;
     int64_t n = 0, first_cell = 0;
     DevMem d_coef, d_extra;
+    is3d::VahModel model{};
 };
 
 int vah_cells_hook(void *ctx, const is3d::SamplerParams &p, const is3d::SamplerSpecies &sp, const double *GT, is3d::SamplerCell *rec)
@@ -323,40 +211,10 @@ int vah_cells_hook(void *ctx, const is3d::SamplerParams &p, const is3d::SamplerS
         for (int k = 0; k < 5; k++) { out[k] = r.d_coef.as<double>() + (size_t)k * r.n; r.v.c[k] = out[k]; }
         if (int rc = is3d::vah_coeffs_device(r.tab, r.n, r.first_cell, r.v.Lambda, r.v.aL, out, p.status)) return rc;
     }
+    r.model.extra = r.d_extra.as<is3d::VahCellExtra>();
     hipLaunchKernelGGL(is3d::cf_sampler_vah_cells, dim3((unsigned)((r.n + 127) / 128)), dim3(128), 0, nullptr, p, sp, r.v, GT, rec,
                        r.d_extra.as<is3d::VahCellExtra>());
     return IS3D_OK;
-}
-
-void vah_run_hook(void *ctx, bool fill, unsigned grid, const is3d::SamplerParams &p, const is3d::SamplerSpecies &sp, const is3d::SamplerRunArgs &a)
-{
-    const VahRun &r = *(const VahRun *)ctx;
-    const is3d::VahCellExtra *extra = r.d_extra.as<is3d::VahCellExtra>();
-    if (fill)
-        hipLaunchKernelGGL((is3d::cf_sampler_vah_run<true>), dim3(grid), dim3(128), 0, nullptr, p, sp, a.rec, extra, a.GT, a.event0, a.active, a.n_active,
-                           a.n_drawn, a.counts, a.offsets, a.base, a.particles, a.capacity);
-    else
-        hipLaunchKernelGGL((is3d::cf_sampler_vah_run<false>), dim3(grid), dim3(128), 0, nullptr, p, sp, a.rec, extra, a.GT, a.event0, a.active, a.n_active,
-                           a.n_drawn, a.counts, a.offsets, a.base, a.particles, a.capacity);
-}
-
-// the fused pass of a binned run: one launch per event batch.  Private form: at most kFusedBinPrivateBlocks workgroups, each walking the
-// pair list grid-stride; global form: one trip per thread
-void vah_bin_hook(void *ctx, const is3d::SamplerParams &p, const is3d::SamplerSpecies &sp, const is3d::SamplerRunArgs &a, const is3d::SamplerBinRun &b,
-                  unsigned long long *hist_dev, unsigned long long *yield_dev)
-{
-    const VahRun &r = *(const VahRun *)ctx;
-    const is3d::VahCellExtra *extra = r.d_extra.as<is3d::VahCellExtra>();
-    const is3d::SamplerBinArgs ba{b.bins, b.widths, b.layout, sp.npart};
-    const bool priv = b.bins.kernel_form == 2 || (b.bins.kernel_form == 0 && is3d::sampler_bins_lds_fits(b.layout));
-    const int64_t trips = (a.n_active + is3d::kFusedBinThreads - 1) / is3d::kFusedBinThreads;
-    if (priv)
-        hipLaunchKernelGGL((is3d::cf_sampler_vah_bin<true>), dim3((unsigned)std::min<int64_t>(trips, is3d::kFusedBinPrivateBlocks)), dim3(is3d::kFusedBinThreads),
-                           (size_t)b.layout.total * sizeof(unsigned long long), nullptr, p, sp, a.rec, extra, a.GT, a.event0, a.active, a.n_active, a.n_drawn,
-                           ba, hist_dev, yield_dev);
-    else
-        hipLaunchKernelGGL((is3d::cf_sampler_vah_bin<false>), dim3((unsigned)trips), dim3(is3d::kFusedBinThreads), 0, nullptr, p, sp, a.rec, extra, a.GT,
-                           a.event0, a.active, a.n_active, a.n_drawn, ba, hist_dev, yield_dev);
 }
 
 // the arrays of is3d_vah_cells (cf_host.h order) the sampler reads: not T; eta in 3+1D; pi and W with shear, bulkPi with bulk; c0..c4 without tables
@@ -421,10 +279,10 @@ int vah_stage(VahStaged &s, const is3d_vah_cells *cells, const is3d_species *spe
     is3d::SamplerVariant &var = s.var;
     var.domain_text = "Lambda or alpha_L is not finite and > 0 (or Lambda > 1e4 boson masses, or the cell's mean hadron number >= 2^31), or "
                       "(Lambda, alpha_L) lies beyond the last node of the VAH coefficient tables";
+    var.edomain_keeps_rest = true;
     var.ctx = &r;
     var.cells = vah_cells_hook;
-    var.run = vah_run_hook;
-    var.bin = vah_bin_hook;
+    var.set_model(&r.model);
     if (n == 0) return IS3D_OK;
     r.tab = tab; r.n = n; r.first_cell = in->first_cell;
     HIP_TRY(s.d_cells.alloc((size_t)n * (is3d::kVahCellArrays + 2)));
@@ -465,28 +323,15 @@ extern "C" int is3d_sample_particles_vah(const is3d_vah_cells *cells, const is3d
     *n_particles = 0;
     if (stats) memset(stats, 0, sizeof *stats);
     if (int rc = is3d::sampler_vah_check(cells, species, tab, in, opts)) return rc;
-    if (particles == nullptr) capacity = 0;
-    const int64_t n = cells->n_cells;
     VahStaged s;
     if (int rc = vah_stage(s, cells, species, tab, in, opts)) return rc;
-    if (n == 0) return IS3D_OK;
-    DevMem d_particles;
-    if (capacity > 0) HIP_TRY(d_particles.alloc((size_t)capacity * sizeof(is3d_particle)));
-    int64_t total = 0;
-    const int rc = is3d::sampler_variant_execute(s.P, s.var, n, s.xy[0], s.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events,
-                                                 d_particles.as<is3d_particle>(), capacity, &total, stats);
-    *n_particles = total;
-    if (stats) stats->ms_h2d = s.ms_h2d;
-    // a bad cell (IS3D_EDOMAIN) leaves the other cells' hadrons sampled: the list is returned with the error
-    if (rc && rc != IS3D_ENOMEM && rc != IS3D_EDOMAIN) return rc;
-    const std::string kept = rc ? is3d_last_error() : "";
-    const int64_t ncopy = std::min<int64_t>(total, capacity);
-    if (ncopy > 0) HIP_TRY(hipMemcpy(particles, d_particles.p, (size_t)ncopy * sizeof(is3d_particle), hipMemcpyDeviceToHost));
-    if (rc) return set_error(rc, "%s", kept.c_str());
-    return IS3D_OK;
+    if (cells->n_cells == 0) return IS3D_OK;
+    // (a bad cell, IS3D_EDOMAIN, leaves the other cells' hadrons sampled: the list is returned with the error -- edomain_keeps_rest)
+    return is3d::sampler_variant_sample_list(s.P, s.var, cells->n_cells, s.xy[0], s.xy[1], in, s.ms_h2d, particles, capacity, n_particles, stats);
 }
 
-// the sampler with every hadron binned where it is sampled (cf_sampler_vah_bin): no list on the device or the host
+// the sampler with every hadron binned where it is sampled (cf_sampler_fused): no list on the device or the host.  kernel_form = 2 needs
+// the block and the three tally words beside it in 64 KiB of LDS (sampler_fused_lds_fits: at most 8189 words), as for is3d_sample_fused
 extern "C" int is3d_sample_binned_vah(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab,
                                       const is3d_sampler_inputs *in, const is3d_options *opts, const is3d_sampler_test_bins *bins,
                                       const is3d_sampler_hist *hist, int64_t *n_particles, is3d_sampler_stats *stats)
@@ -496,11 +341,11 @@ extern "C" int is3d_sample_binned_vah(const is3d_vah_cells *cells, const is3d_sp
     *n_particles = 0;
     if (stats) memset(stats, 0, sizeof *stats);
     if (int rc = is3d::sampler_vah_check(cells, species, tab, in, opts)) return rc;
-    if (int rc = is3d::sampler_check_bin_args(bins, hist, in->n_events, species->n)) return rc;
+    if (int rc = is3d::sampler_check_fused_args(bins, hist, in->n_events, species->n)) return rc;
     VahStaged s;
     if (int rc = vah_stage(s, cells, species, tab, in, opts)) return rc;
     const int rc = is3d::sampler_variant_execute_binned(s.P, s.var, cells->n_cells, s.xy[0], s.xy[1], in->n_events, in->seed, in->first_cell,
-                                                        in->batch_events, bins, hist, n_particles, stats);
+                                                        in->batch_events, bins, hist, true, n_particles, stats);
     if (stats) stats->ms_h2d = s.ms_h2d;
     return rc;
 }

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from is3d_amd import api, inputs, synth
-from sampler_bins_ref import layout_total
+from sampler_bins_ref import BINS as REF_BINS, layout_total
 
 pytestmark = pytest.mark.gpu
 COUNTS = ("dN_dy", "dN_deta", "dN_pT", "dN_tau", "dN_r", "yield")
@@ -119,6 +119,45 @@ def test_305_species_take_the_global_form(runs):
         api.sample_fused(*args, dict(SHIPPED_BINS, kernel_form=2), r["o"], **r["kw"])
     assert e.value.code == api.IS3D_EINVAL and str(305 * 1800) in str(e.value)
     assert api.resource_counters() == before
+
+
+# the bins of LDS_FIT in tests/test_gpu_sampler_bins_lists.py: one species, 15 * 500 + 200 + 200 + 146 + 146 = 8192 words
+LDS_FIT = dict(REF_BINS, pT_bins=500, y_bins=200, eta_bins=200, tau_bins=146, r_bins=146)
+
+
+def test_the_private_form_ends_where_the_block_and_the_tally_words_fill_the_lds(fx):
+    """pi+ alone, a 400-cell surface (its volumes times 50, for a few thousand hadrons) x 30 events.  The fused kernel keeps three tally words
+    of static LDS beside the dynamic block, so tau_bins = 143 (8189 words) is the largest block of the private form and tau_bins = 146 (8192
+    words, which the list kernel still holds) the first that form 0 must send to the global form.  Forms 0 and 1 at both sizes, and form 2 at
+    8189, give the histograms of the host-binned list of the same call; form 2 at 8192 is refused."""
+    sp, gla, o = inputs.species([211]), inputs.feqmod_tables(0.15), dict(dimension=3, df_mode=2)
+    cells = {k: v.copy() for k, v in synth.synth_surface(400, 3, seed=861).items()}
+    for f in ("dat", "dax", "day", "dan"):
+        cells[f] *= 50.0
+    kw = dict(n_events=30, seed=19, y_cut=0.5)
+    plist, lst = api.sample_particles(cells, sp, fx["df"], gla, o, **kw)
+    print("hadrons", len(plist))
+    assert len(plist) >= 200
+    for tau_bins, words, forms in ((143, 8189, (0, 1, 2)), (146, 8192, (0, 1))):
+        bins = dict(LDS_FIT, tau_bins=tau_bins)
+        assert layout_total(bins, 1) == words
+        yp = 0.5 * np.log((plist["E"] + plist["pz"]) / (plist["E"] - plist["pz"]))
+        u = (yp + bins["y_cut"]) / (2.0 * bins["y_cut"] / bins["y_bins"])
+        assert np.abs(u - np.rint(u)).min() > 1e-9 and np.abs(np.abs(yp) - bins["y_cut"]).min() > 1e-9      # (a property of the fixture)
+        want = api.sampler_bin_list(bins, 30, 1, plist)
+        assert want["yield"].sum() == len(plist) and all(want[k].sum() > 0 for k in COUNTS)
+        for form in forms:
+            got, st = api.sample_fused(cells, sp, fx["df"], gla, dict(bins, kernel_form=form), o, **kw)
+            for k in COUNTS:
+                assert got[k].dtype == np.int64 and np.array_equal(got[k], want[k]), (words, form, k)
+            for k in ("vn_re", "vn_im"):
+                d = np.abs(got[k] - want[k])
+                print(words, "words, form", form, k, "against the host-binned list: max |delta|", int(d.max()))
+                assert np.all(d <= want["dN_pT"][None]), (words, form, k)
+            assert st["n_particles"] == len(plist) and all(st[k] == lst[k] for k in TALLIES), (words, form)
+    with pytest.raises(api.Is3dError) as e:
+        api.sample_fused(cells, sp, fx["df"], gla, dict(LDS_FIT, kernel_form=2), o, **kw)
+    assert e.value.code == api.IS3D_EINVAL and "kernel_form = 2" in str(e.value) and "8192" in str(e.value)
 
 
 def test_histograms_do_not_depend_on_geometry(runs):

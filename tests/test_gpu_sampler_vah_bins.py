@@ -1,5 +1,5 @@
 """GPU (-m gpu): the anisotropic-hydro sampler with its hadrons binned where they are sampled, in one pass and without a list
-(is3d_sample_binned_vah, is3d_sample_binned_vah_multi; cf_sampler_vah_bin).  The reference has no VAH sampler, so the yardstick is the
+(is3d_sample_binned_vah, is3d_sample_binned_vah_multi; cf_sampler_fused with the anisotropic-hydro model).  The reference has no VAH sampler, so the yardstick is the
 library's own list route: the histograms must be those of is3d_sampler_bin_list on the list is3d_sample_particles_vah returns for the same
 arguments.  Every comparison is between integers; the one tolerance is the project's rule for vn_re / vn_im against a HOST-binned list (one
 fixed-point unit per entry of the dN_pT bin: device and host libm differ).
@@ -10,6 +10,7 @@ drawn hadrons per call; every test asserts sum(yield) >= 2000 and that each of t
 import numpy as np
 import pytest
 
+import sampler_bins_ref as R
 from is3d_amd import api, inputs, synth
 
 pytestmark = pytest.mark.gpu
@@ -204,6 +205,44 @@ def test_stats_convention(cut):
     st = cut["stats"]
     assert st["particle_workspace_bytes"] == 0 and st["ms_count"] == 0 and st["ms_fill"] == 0 and st["ms_bin"] > 0
     assert st["n_particles"] == cut["whole"]["yield"].sum() and st["n_hadrons_drawn"] >= st["n_particles"]
+
+
+# ---- 3b. where the private form ends ----
+# the bins of LDS_FIT in tests/test_gpu_sampler_bins_lists.py: one species, 15 * 500 + 200 + 200 + 146 + 146 = 8192 words
+LDS_FIT = dict(R.BINS, pT_bins=500, y_bins=200, eta_bins=200, tau_bins=146, r_bins=146)
+
+
+def test_the_private_form_ends_where_the_block_and_the_tally_words_fill_the_lds(gla, tab):
+    """pi+ alone, 400 cells x 30 events.  The fused kernel keeps three tally words of static LDS beside the dynamic block, so tau_bins = 143
+    (8189 words) is the largest block of the private form and tau_bins = 146 (8192 words, which the list kernel still holds) the first that
+    form 0 must send to the global form.  Forms 0 and 1 at both sizes, and form 2 at 8189, give the histograms of the host-binned list of
+    the same call; form 2 at 8192 is refused."""
+    sp = inputs.species([211])
+    v = surface(400, 3, 9941, sp, gla, 30)
+    o = dict(dimension=3)
+    kw = dict(tab=tab, n_events=30, seed=61)
+    plist, lst = api.sample_particles_vah(v, sp, gla, o, **kw)
+    assert len(plist) >= 2000
+    for tau_bins, words, forms in ((143, 8189, (0, 1, 2)), (146, 8192, (0, 1))):
+        bins = dict(LDS_FIT, tau_bins=tau_bins)
+        assert R.layout_total(bins, 1) == words
+        yp = 0.5 * np.log((plist["E"] + plist["pz"]) / (plist["E"] - plist["pz"]))
+        u = (yp + bins["y_cut"]) / (2.0 * bins["y_cut"] / bins["y_bins"])
+        assert np.abs(u - np.rint(u)).min() > 1e-9 and np.abs(np.abs(yp) - bins["y_cut"]).min() > 1e-9      # (a property of the fixture)
+        want = api.sampler_bin_list(bins, 30, 1, plist)
+        assert want["yield"].sum() == len(plist) and all(want[k].sum() > 0 for k in COUNTS)
+        for form in forms:
+            got, st = api.sample_binned_vah(v, sp, gla, dict(bins, kernel_form=form), o, **kw)
+            for k in COUNTS + ("yield",):
+                assert got[k].dtype == np.int64 and np.array_equal(got[k], want[k]), (words, form, k)
+            for k in ("vn_re", "vn_im"):
+                d = np.abs(got[k] - want[k])
+                print(words, "words, form", form, k, "against the host-binned list: max |delta|", int(d.max()))
+                assert np.all(d <= want["dN_pT"][None]), (words, form, k)
+            assert st["n_particles"] == len(plist) and all(st[k] == lst[k] for k in TALLIES), (words, form)
+    with pytest.raises(api.Is3dError) as e:
+        api.sample_binned_vah(v, sp, gla, dict(LDS_FIT, kernel_form=2), o, **kw)
+    assert e.value.code == api.IS3D_EINVAL and "kernel_form = 2" in str(e.value) and "8192" in str(e.value)
 
 
 # ---- 4. nothing is allocated per event ----

@@ -84,6 +84,25 @@ def test_the_order_of_the_refusals(good, multi):
     assert "kernel_form = 2" in text and str(305 * 1800) in text
 
 
+@pytest.mark.parametrize("multi", [False, True], ids=["single", "multi"])
+def test_private_form_needs_room_for_the_tally_words_beside_the_block(good, multi):
+    """One species at the shipped bins with r_bins = 6450: 50 + 70 + 120 + 6450 + 15 * 100 = 8190 words fit the 64 KiB of LDS alone but not with
+    the three tally words of static LDS the fused kernel keeps beside the block: refused.  r_bins = 6449 gives 8189 words, the largest block
+    that fits, and is not refused for it."""
+    pion = inputs.species([211])
+    text = refused(good, multi, bins=dict(SHIPPED_BINS, r_bins=6450, kernel_form=2), sp=pion)
+    assert "kernel_form = 2" in text and "8190" in text
+    kw = dict(n_events=2, seed=3, **(dict(devices=[0, 0]) if multi else {}))
+    fits, o = dict(SHIPPED_BINS, r_bins=6449, kernel_form=2), dict(dimension=3, df_mode=2)
+    if api.load().is3d_device_count() > 0:
+        h, st = api.sample_fused(good["cells"], pion, good["df"], good["gla"], fits, o, **kw)
+        assert h["dN_r"].shape == (1, 6449) and st["n_particles"] == h["yield"].sum()
+        return
+    with pytest.raises(api.Is3dError) as e:
+        api.sample_fused(good["cells"], pion, good["df"], good["gla"], fits, o, **kw)
+    assert e.value.code == api.IS3D_ENODEVICE and "no CPU path" in str(e.value)
+
+
 def test_null_arguments_are_refused():
     lib = api.load()
     n = api.C.c_int64(7)

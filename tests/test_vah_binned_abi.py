@@ -104,6 +104,26 @@ def test_private_form_is_refused_where_the_block_does_not_fit(good, multi):
     assert e.value.code == api.IS3D_EINVAL and "fast" in str(e.value)
 
 
+@pytest.mark.parametrize("multi", [False, True], ids=["single", "multi"])
+def test_private_form_needs_room_for_the_tally_words_beside_the_block(good, multi):
+    """pi K p pbar at the shipped bins with tau_bins = 128, r_bins = 300: 4 * (50 + 70 + 128 + 300 + 15 * 100) = 8192 words fill the 64 KiB of
+    LDS, but the fused kernel keeps three tally words of static LDS beside the block: refused, as is3d_sample_fused refuses it.  r_bins = 298
+    gives 8184 words, which fit with the three words (8189 is the largest block that does) and are not refused for it."""
+    bins = dict(SHIPPED_BINS, tau_bins=128, r_bins=300, kernel_form=2)
+    assert len(good["sp"]["mass"]) == 4
+    text = refused(good, multi, bins=bins)
+    assert "kernel_form = 2" in text and "8192" in text
+    kw = dict(n_events=2, seed=3, **(dict(devices=[0, 0]) if multi else {}))
+    fits = dict(bins, r_bins=298)
+    if api.load().is3d_device_count() > 0:
+        h, st = api.sample_binned_vah(good["cells"], good["sp"], good["gla"], fits, dict(dimension=3), **kw)
+        assert h["dN_r"].shape == (4, 298) and h["dN_tau"].shape == (4, 128) and st["n_particles"] == h["yield"].sum()
+        return
+    with pytest.raises(api.Is3dError) as e:
+        api.sample_binned_vah(good["cells"], good["sp"], good["gla"], fits, dict(dimension=3), **kw)
+    assert e.value.code == api.IS3D_ENODEVICE and "no CPU path" in str(e.value)
+
+
 def test_null_arguments_are_refused():
     lib = api.load()
     n = api.C.c_int64(7)
