@@ -742,7 +742,7 @@ int is3d_sampler_plan_execute_fused(is3d_sampler_plan *plan, const is3d_cells *c
                                     int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
                                     const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist_host, int64_t *n_particles,
                                     is3d_sampler_stats *stats);
-/* host-pointer one-shot (create + upload + execute_fused + destroy), and the same on the shard scaffold of is3d_sample_binned_multi: the
+/* host-pointer one-shot (create + upload + execute_fused + destroy), and the same over the cell shards of is3d_sample_binned_multi: the
  * integer histograms are added on the host, so the result equals the single-device one bit for bit. */
 int is3d_sample_fused(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
                       const is3d_options *opts, const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
@@ -777,8 +777,8 @@ int is3d_sample_fused_multi(const is3d_cells *cells, const is3d_species *species
 int is3d_sample_binned_vah(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab /* NULL: c0..c4 from the cells */,
                            const is3d_sampler_inputs *in, const is3d_options *opts, const is3d_sampler_test_bins *bins,
                            const is3d_sampler_hist *hist, int64_t *n_particles, is3d_sampler_stats *stats /* may be NULL */);
-/* is3d_sample_binned_vah over contiguous cell shards, shard s on devices[s] with first_cell advanced to the shard's first cell (the shard
- * scaffold of is3d_sample_particles_vah_multi); the shards' integer histograms are added on the host, so the result equals the single-device
+/* is3d_sample_binned_vah over contiguous cell shards, shard s on devices[s] with first_cell advanced to the shard's first cell (the
+ * shards of is3d_sample_particles_vah_multi); the shards' integer histograms are added on the host, so the result equals the single-device
  * one bit for bit.  The same refusals, before any device use; opts->device is ignored; a bad cell is named by its index in the whole
  * surface (the lowest one), with the sum of all shards' histograms returned.  stats are summed (times: the slowest shard's). */
 int is3d_sample_binned_vah_multi(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab,

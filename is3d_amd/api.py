@@ -280,8 +280,14 @@ def load():
     L.is3d_pdg_read.argtypes = [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _dp, _dp, _dp, _dp, C.c_int32]
     L.is3d_df_table_read.argtypes = [C.c_char_p, C.POINTER(C.c_int32), _dp, _dp, C.c_int32]
     L.is3d_df_table_read_full.argtypes = [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp, _dp, C.c_int64]
-    L.is3d_sample_particles.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs),
-                                        C.POINTER(Options), C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
+    # the host-pointer sampler entries: a head per family, a tail per kind, the device list between them in the _multi form
+    heads = dict(viscous=[C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options)],
+                 vah=[C.POINTER(VahCells), C.POINTER(Species), C.POINTER(VahDfTables), C.POINTER(SamplerInputs), C.POINTER(Options)])
+    tails = dict(list=[C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(SamplerStats)],
+                 binned=[C.POINTER(SamplerTestBins), C.POINTER(SamplerHist), C.POINTER(C.c_int64), C.POINTER(SamplerStats)])
+    for name, (family, kind) in SAMPLER_ENTRIES.items():
+        getattr(L, name).argtypes = heads[family] + tails[kind]
+        getattr(L, name + "_multi").argtypes = heads[family] + [C.POINTER(C.c_int32), C.c_int32] + tails[kind]
     L.is3d_write_particle_list_osc.argtypes = [C.c_char_p, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
     L.is3d_gla_read.argtypes = [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp, C.c_int64]
     L.is3d_write_results.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, _dp, _dp,
@@ -1535,49 +1541,88 @@ def _pack_sampler(cells, species, df, gla, opts, n_events, seed, y_cut, first_ce
             assert a.shape == (n,), f
             held.append(a)
             setattr(cs, f, a.ctypes.data)
+    si = _sampler_inputs(cells, gla, n_events, seed, y_cut, first_cell, fq, fast, batch_events, held, T_avg, T_avg_switch, muB_avg)
+    return cs, sps, ds, si, os_, held
+
+
+def _sampler_inputs(cells, gla, n_events, seed, y_cut, first_cell, fq, fast, batch_events, held, T_avg=0.0, T_avg_switch=0.0, muB_avg=0.0):
+    """SamplerInputs for both sampler families (anisotropic hydro has no averages: 0.0).  held: what must stay alive, appended to; held[0] is
+    the list _pack_common keeps."""
     r1, w1 = _f64(gla["root1"]), _f64(gla["weight1"])
     xs = _f64(cells["x"]) if cells.get("x") is not None else None
     ys = _f64(cells["y"]) if cells.get("y") is not None else None
-    fqs = _pack_feqmod(fq, keep) if fq is not None else None
-    si = SamplerInputs(int(n_events), len(r1), int(seed), float(y_cut), int(first_cell), _p(xs) if xs is not None else None,
-                       _p(ys) if ys is not None else None, _p(r1), _p(w1), C.pointer(fqs) if fqs is not None else None, int(fast), int(batch_events),
-                       float(T_avg), float(T_avg_switch), float(muB_avg))
+    fqs = _pack_feqmod(fq, held[0]) if fq is not None else None
     held += [r1, w1, xs, ys, fqs]
-    return cs, sps, ds, si, os_, held
+    return SamplerInputs(int(n_events), len(r1), int(seed), float(y_cut), int(first_cell), _p(xs) if xs is not None else None,
+                         _p(ys) if ys is not None else None, _p(r1), _p(w1), C.pointer(fqs) if fqs is not None else None, int(fast), int(batch_events),
+                         float(T_avg), float(T_avg_switch), float(muB_avg))
+
+
+# the host-pointer sampler entries, each with a _multi form: name -> (family, kind); load() builds their argtypes from this
+SAMPLER_ENTRIES = dict(is3d_sample_particles=("viscous", "list"), is3d_sample_binned=("viscous", "binned"), is3d_sample_fused=("viscous", "binned"),
+                       is3d_sample_particles_vah=("vah", "list"), is3d_sample_binned_vah=("vah", "binned"))
+
+
+def _sampler_call(name, head, devices, edomain_keeps_rest, *tail):
+    """One call of the entry `name` (devices = None) or of name_multi (one cell shard per listed device; an ordinal may repeat).  An error
+    raises; with edomain_keeps_rest IS3D_EDOMAIN, which comes with the other cells' result, is returned instead."""
+    if devices is None:
+        rc = getattr(load(), name)(*head, *tail)
+    else:
+        dv, nd, _ = _pack_devices(devices)
+        rc = getattr(load(), name + "_multi")(*head, dv, nd, *tail)
+    if not (edomain_keeps_rest and rc == IS3D_EDOMAIN):
+        _check(rc)
+    return rc
+
+
+def _sampler_result(rc, st, cnt, **result):
+    """(result, stats dict with n_particles) of a sampler call; rc = IS3D_EDOMAIN, bad cells: Is3dError with .bad_cell (the index the text
+    names), .stats and the partial result under its keyword."""
+    (key, value), = result.items()
+    d = st.as_dict()
+    d["n_particles"] = int(cnt.value)
+    if rc:
+        msg = load().is3d_last_error().decode()
+        m = re.search(r"cell (\d+):", msg)
+        e = Is3dError(rc, msg, bad_cell=int(m.group(1)) if m else None)
+        setattr(e, key, value)
+        e.stats = d
+        raise e
+    return value, d
+
+
+def _sample_list(name, head, devices, capacity, edomain_keeps_rest):
+    """The list entries' protocol: capacity = None sizes the buffer from a count-only first call; -> (the list, stats dict).
+    edomain_keeps_rest: IS3D_EDOMAIN carries the other cells' hadrons (.particles, .stats)."""
+    st, cnt = SamplerStats(), C.c_int64(0)
+    if capacity is None:
+        _sampler_call(name, head, devices, edomain_keeps_rest, None, 0, C.byref(cnt), C.byref(st))
+        capacity = int(cnt.value)
+    out = np.zeros(max(int(capacity), 1), dtype=PARTICLE_DTYPE)
+    assert out.dtype.itemsize == C.sizeof(Particle)
+    rc = _sampler_call(name, head, devices, edomain_keeps_rest, out.ctypes.data, int(capacity), C.byref(cnt), C.byref(st))
+    return _sampler_result(rc, st, cnt, particles=out[:min(int(cnt.value), int(capacity))])
+
+
+def _sample_binned(name, head, devices, bins, n_events, n_species, edomain_keeps_rest):
+    """The binned entries: -> (dict of int64 histograms, stats dict).  edomain_keeps_rest: IS3D_EDOMAIN carries the other cells' histograms
+    (.hist, .stats)."""
+    b = _pack_bins(bins)
+    h, out = _hist_arrays(bins, n_events, n_species)
+    st, cnt = SamplerStats(), C.c_int64(0)
+    rc = _sampler_call(name, head, devices, edomain_keeps_rest, C.byref(b), C.byref(h), C.byref(cnt), C.byref(st))
+    return _sampler_result(rc, st, cnt, hist=out)
 
 
 def sample_particles(cells, species, df, gla, opts=None, n_events=1, seed=1, y_cut=0.5, first_cell=0, capacity=None, fq=None, fast=0,
                      T_avg=0.0, T_avg_switch=0.0, batch_events=0, muB_avg=0.0, devices=None):
     """is3d_sample_particles (the drop-in for sample_dN_pTdpTdphidy, df_mode 1-4).  cells: dict of host arrays (x, y optional);
     gla: dict with root1, weight1; fq: the feqmod tables (df_mode 3, 4; fast mode with df_mode 2).  Returns (numpy structured array of PARTICLE_DTYPE, stats dict); capacity = None sizes the
-    buffer from a count-only first call."""
-    L = load()
+    buffer from a count-only first call.  devices: is3d_sample_particles_multi, one cell shard per listed device (an ordinal may repeat)."""
     cs, sps, ds, si, os_, _held = _pack_sampler(cells, species, df, gla, opts, n_events, seed, y_cut, first_cell, fq, fast, T_avg, T_avg_switch,
                                                 batch_events, muB_avg)
-    st = SamplerStats()
-    cnt = C.c_int64(0)
-    if devices is not None:   # is3d_sample_particles_multi: one cell shard per listed device (an ordinal may repeat)
-        dv, nd, _ = _pack_devices(devices)
-        L.is3d_sample_particles_multi.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs),
-                                                  C.POINTER(Options), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int64,
-                                                  C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
-
-        def call(buf, cap):
-            return L.is3d_sample_particles_multi(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), dv, nd, buf, cap,
-                                                 C.byref(cnt), C.byref(st))
-    else:
-        def call(buf, cap):
-            return L.is3d_sample_particles(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), buf, cap, C.byref(cnt), C.byref(st))
-    if capacity is None:
-        _check(call(None, 0))
-        capacity = int(cnt.value)
-    out = np.zeros(max(int(capacity), 1), dtype=PARTICLE_DTYPE)
-    assert out.dtype.itemsize == C.sizeof(Particle)
-    rc = call(out.ctypes.data, int(capacity))
-    _check(rc)
-    d = st.as_dict()
-    d["n_particles"] = int(cnt.value)
-    return out[:min(int(cnt.value), int(capacity))], d
+    return _sample_list("is3d_sample_particles", (C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_)), devices, capacity, False)
 
 
 def _pack_sampler_vah(cells, species, gla, opts, tab, n_events, seed, y_cut, first_cell, batch_events, fast, fq):
@@ -1588,14 +1633,8 @@ def _pack_sampler_vah(cells, species, gla, opts, tab, n_events, seed, y_cut, fir
         cells = {k: v for k, v in cells.items() if k not in ("c0", "c1", "c2", "c3", "c4")}
     cs = _vah_cells_struct(cells, held)
     ts = _pack_vah_tables(tab, keep) if tab is not None else None
-    r1, w1 = _f64(gla["root1"]), _f64(gla["weight1"])
-    xs = _f64(cells["x"]) if cells.get("x") is not None else None
-    ys = _f64(cells["y"]) if cells.get("y") is not None else None
-    fqs = _pack_feqmod(fq, keep) if fq is not None else None
-    si = SamplerInputs(int(n_events), len(r1), int(seed), float(y_cut), int(first_cell), _p(xs) if xs is not None else None,
-                       _p(ys) if ys is not None else None, _p(r1), _p(w1), C.pointer(fqs) if fqs is not None else None, int(fast), int(batch_events),
-                       0.0, 0.0, 0.0)
-    held += [ts, r1, w1, xs, ys, fqs]
+    held.append(ts)
+    si = _sampler_inputs(cells, gla, n_events, seed, y_cut, first_cell, fq, fast, batch_events, held)
     return cs, sps, (C.byref(ts) if ts is not None else None), si, os_, held
 
 
@@ -1607,41 +1646,8 @@ def sample_particles_vah(cells, species, gla, opts=None, tab=None, n_events=1, s
     (numpy structured array of PARTICLE_DTYPE, stats dict); capacity = None sizes the buffer from a count-only first call.  A bad cell raises
     Is3dError(IS3D_EDOMAIN) with .bad_cell (the lowest global index), .particles and .stats: the other cells are sampled all the same.
     fast, fq: passed on only so that the entry's refusals can be reached."""
-    L = load()
     cs, sps, tp, si, os_, _held = _pack_sampler_vah(cells, species, gla, opts, tab, n_events, seed, y_cut, first_cell, batch_events, fast, fq)
-    st = SamplerStats()
-    cnt = C.c_int64(0)
-    head = [C.POINTER(VahCells), C.POINTER(Species), C.POINTER(VahDfTables), C.POINTER(SamplerInputs), C.POINTER(Options)]
-    tail = [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
-    L.is3d_sample_particles_vah.argtypes = head + tail
-    L.is3d_sample_particles_vah_multi.argtypes = head + [C.POINTER(C.c_int32), C.c_int32] + tail
-    if devices is not None:
-        dv, nd, _ = _pack_devices(devices)
-
-        def call(buf, cap):
-            return L.is3d_sample_particles_vah_multi(C.byref(cs), C.byref(sps), tp, C.byref(si), C.byref(os_), dv, nd, buf, cap, C.byref(cnt), C.byref(st))
-    else:
-        def call(buf, cap):
-            return L.is3d_sample_particles_vah(C.byref(cs), C.byref(sps), tp, C.byref(si), C.byref(os_), buf, cap, C.byref(cnt), C.byref(st))
-    if capacity is None:
-        rc = call(None, 0)
-        if rc != IS3D_EDOMAIN:
-            _check(rc)
-        capacity = int(cnt.value)
-    out = np.zeros(max(int(capacity), 1), dtype=PARTICLE_DTYPE)
-    assert out.dtype.itemsize == C.sizeof(Particle)
-    rc = call(out.ctypes.data, int(capacity))
-    d = st.as_dict()
-    d["n_particles"] = int(cnt.value)
-    out = out[:min(int(cnt.value), int(capacity))]
-    if rc == IS3D_EDOMAIN:
-        msg = L.is3d_last_error().decode()
-        m = re.search(r"cell (\d+):", msg)
-        e = Is3dError(rc, msg, bad_cell=int(m.group(1)) if m else None)
-        e.particles, e.stats = out, d
-        raise e
-    _check(rc)
-    return out, d
+    return _sample_list("is3d_sample_particles_vah", (C.byref(cs), C.byref(sps), tp, C.byref(si), C.byref(os_)), devices, capacity, True)
 
 
 def sample_particles_vah_multi(cells, species, gla, opts=None, devices=(0,), **kw):
@@ -1913,29 +1919,10 @@ def sample_binned(cells, species, df, gla, bins, opts=None, n_events=1, seed=1, 
                   T_avg_switch=0.0, batch_events=0, muB_avg=0.0, devices=None, _fused=False):
     """is3d_sample_binned (devices = None) | is3d_sample_binned_multi: the sampler with every event batch binned on the device and dropped.
     Arguments as sample_particles; bins: dict of is3d_sampler_test_bins fields.  Returns (dict of int64 histograms, stats dict)."""
-    L = load()
-    one, multi = (L.is3d_sample_fused, L.is3d_sample_fused_multi) if _fused else (L.is3d_sample_binned, L.is3d_sample_binned_multi)
     cs, sps, ds, si, os_, _held = _pack_sampler(cells, species, df, gla, opts, n_events, seed, y_cut, first_cell, fq, fast, T_avg, T_avg_switch,
                                                 batch_events, muB_avg)
-    b = _pack_bins(bins)
-    h, out = _hist_arrays(bins, n_events, sps.n)
-    st = SamplerStats()
-    cnt = C.c_int64(0)
-    if devices is not None:
-        dv, nd, _ = _pack_devices(devices)
-        multi.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options),
-                                               C.POINTER(C.c_int32), C.c_int32, C.POINTER(SamplerTestBins), C.POINTER(SamplerHist),
-                                               C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
-        rc = multi(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), dv, nd, C.byref(b), C.byref(h),
-                                        C.byref(cnt), C.byref(st))
-    else:
-        one.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options),
-                                         C.POINTER(SamplerTestBins), C.POINTER(SamplerHist), C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
-        rc = one(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), C.byref(b), C.byref(h), C.byref(cnt), C.byref(st))
-    _check(rc)
-    d = st.as_dict()
-    d["n_particles"] = int(cnt.value)
-    return out, d
+    return _sample_binned("is3d_sample_fused" if _fused else "is3d_sample_binned", (C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_)),
+                          devices, bins, n_events, sps.n, False)
 
 
 def sample_binned_multi(cells, species, df, gla, bins, opts=None, devices=(0,), **kw):
@@ -1960,32 +1947,8 @@ def sample_binned_vah(cells, species, gla, bins, opts=None, tab=None, n_events=1
     is sampled, in one pass and without a list.  Arguments as sample_particles_vah; bins: dict of is3d_sampler_test_bins fields.  Returns
     (dict of int64 histograms, stats dict): the histograms of sampler_bin_list on sample_particles_vah's list.  A bad cell raises
     Is3dError(IS3D_EDOMAIN) with .bad_cell (the lowest global index), .hist and .stats: the other cells are binned all the same."""
-    L = load()
     cs, sps, tp, si, os_, _held = _pack_sampler_vah(cells, species, gla, opts, tab, n_events, seed, y_cut, first_cell, batch_events, fast, fq)
-    b = _pack_bins(bins)
-    h, out = _hist_arrays(bins, n_events, sps.n)
-    st = SamplerStats()
-    cnt = C.c_int64(0)
-    head = [C.POINTER(VahCells), C.POINTER(Species), C.POINTER(VahDfTables), C.POINTER(SamplerInputs), C.POINTER(Options)]
-    tail = [C.POINTER(SamplerTestBins), C.POINTER(SamplerHist), C.POINTER(C.c_int64), C.POINTER(SamplerStats)]
-    L.is3d_sample_binned_vah.argtypes = head + tail
-    L.is3d_sample_binned_vah_multi.argtypes = head + [C.POINTER(C.c_int32), C.c_int32] + tail
-    if devices is not None:
-        dv, nd, _ = _pack_devices(devices)
-        rc = L.is3d_sample_binned_vah_multi(C.byref(cs), C.byref(sps), tp, C.byref(si), C.byref(os_), dv, nd, C.byref(b), C.byref(h), C.byref(cnt),
-                                            C.byref(st))
-    else:
-        rc = L.is3d_sample_binned_vah(C.byref(cs), C.byref(sps), tp, C.byref(si), C.byref(os_), C.byref(b), C.byref(h), C.byref(cnt), C.byref(st))
-    d = st.as_dict()
-    d["n_particles"] = int(cnt.value)
-    if rc == IS3D_EDOMAIN:
-        msg = L.is3d_last_error().decode()
-        m = re.search(r"cell (\d+):", msg)
-        e = Is3dError(rc, msg, bad_cell=int(m.group(1)) if m else None)
-        e.hist, e.stats = out, d
-        raise e
-    _check(rc)
-    return out, d
+    return _sample_binned("is3d_sample_binned_vah", (C.byref(cs), C.byref(sps), tp, C.byref(si), C.byref(os_)), devices, bins, n_events, sps.n, True)
 
 
 def sample_binned_vah_multi(cells, species, gla, bins, opts=None, devices=(0,), **kw):

@@ -1077,42 +1077,68 @@ extern "C" int is3d_smooth_spectra_vah_multi(const is3d_vah_cells *cells, const 
 }
 
 // ------------------------------------------------------------------------------------------------
-// particle sampler over several devices
+// particle sampler over several devices: the viscous entries (is3d_sample_particles | is3d_sample_binned | is3d_sample_fused) and the
+// anisotropic-hydro ones (is3d_sample_particles_vah | is3d_sample_binned_vah) on one shard record, one slice and two drivers -- a list
+// driver (count, fill, merge) and a binned driver (a histogram block per shard, an exact integer sum).  What differs between the families is
+// the cell struct, the single-device call and edomain_keeps_rest (SamplerVariant's fact, one level up): whether IS3D_EDOMAIN, a bad cell,
+// leaves the other cells sampled and is reported beside their result (anisotropic hydro) or is an error like any other (viscous).
 // ------------------------------------------------------------------------------------------------
 namespace {
-// a shard of the sampler's multi entries: [lo, hi) of a host surface as the arguments of a single-device call on `device` -- the cell arrays
-// and x, y advanced to lo, first_cell with them -- and what that call reports
-struct SamplerShard : ShardBase {
-    is3d_cells c;
+// a shard of the sampler's multi entries: [lo, hi) of a host surface as the arguments of a single-device call on `device`, what that call
+// reports, and its result (list: the list entries; h: the binned ones, the arrays of is3d_sampler_hist end to end)
+template <class Cells>
+struct SamplerShardT : ShardBase {
+    Cells c;
     is3d_sampler_inputs si;
     is3d_options o;
     int64_t count = 0;
     is3d_sampler_stats st{};
+    std::vector<is3d_particle> list;
+    std::vector<int64_t> h;
 };
-void sampler_shard(SamplerShard &s, const is3d_cells *cells, const is3d_sampler_inputs *in, const is3d_options *opts)
+// the cell arrays and x, y advanced to lo, first_cell with them
+template <class Cells>
+void slice_shard(SamplerShardT<Cells> &s, const Cells &cells, const is3d_sampler_inputs &in, const is3d_options &opts)
 {
-    s.c = *cells;
-    s.c.n_cells = s.hi - s.lo;
-    is3d_cells &c = s.c;
-    const double **fields[] = {&c.tau, &c.eta, &c.dat, &c.dax, &c.day, &c.dan, &c.ux, &c.uy, &c.un, &c.T, &c.P, &c.E, &c.pixx, &c.pixy,
-                               &c.pixn, &c.piyy, &c.piyn, &c.bulkPi, &c.muB, &c.nB, &c.Vx, &c.Vy, &c.Vn};
-    for (auto f : fields)
-        if (*f) *f += s.lo;
-    s.si = *in;
-    s.si.first_cell = in->first_cell + s.lo;
+    auto a = is3d::cell_arrays(cells);
+    for (auto &f : a)
+        if (f) f += s.lo;
+    s.c = is3d::cells_from_arrays(s.hi - s.lo, a);
+    s.si = in;
+    s.si.first_cell = in.first_cell + s.lo;
     if (s.si.x) s.si.x += s.lo;
     if (s.si.y) s.si.y += s.lo;
-    s.o = *opts;
+    s.o = opts;
     s.o.device = s.device;
 }
-// the first failed shard's error; else the hadron counts summed, the other counters summed and the times the slowest shard's
+// a one-entry device list is the single-device entry with these options
+is3d_options on_device(const is3d_options &opts, int device)
+{
+    is3d_options o = opts;
+    o.device = device;
+    return o;
+}
+// at entry, so that every refusal after the NULL checks leaves zeros
+void zero_outputs(int64_t *n_particles, is3d_sampler_stats *stats)
+{
+    *n_particles = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+}
+// the first failed shard's error; else the hadron counts summed, the other counters summed and the times the slowest shard's.  With
+// edomain_keeps_rest, where IS3D_EDOMAIN (a bad cell) is the shards' only error, the totals are taken all the same and *bad_cell gets the
+// text to return with IS3D_EDOMAIN once the caller has combined the shards' results: the first failed shard's, which names the lowest global
+// index, the shards being ascending cell ranges
 template <class S>
-int sampler_totals(const std::vector<S> &sh, int64_t *n_particles, is3d_sampler_stats *stats)
+int sampler_totals(const std::vector<S> &sh, bool edomain_keeps_rest, int64_t *n_particles, is3d_sampler_stats *stats, std::string *bad_cell)
 {
     int rc;
     std::string text;
     first_error(sh, &rc, &text);
-    if (rc) return fail(rc, "%s", text.c_str());
+    bool only_domain = edomain_keeps_rest && rc == IS3D_EDOMAIN;
+    for (const S &s : sh)
+        if (s.rc && s.rc != IS3D_EDOMAIN) only_domain = false;
+    if (rc && !only_domain) return fail(rc, "%s", text.c_str());
+    if (only_domain) *bad_cell = text;
     is3d_sampler_stats agg{};
     for (const S &s : sh) {
         const is3d_sampler_stats &t = s.st;
@@ -1147,6 +1173,129 @@ void merge_shard_lists(const std::vector<S> &sh, int32_t n_events, is3d_particle
             pos[i] = p;
         }
 }
+// The list driver.  one(shard, particles, capacity): the family's single-device list entry on the shard's slice, into s.count and s.st.
+// Every shard counts, then fills a list of that size; the lists are merged into the caller's.
+// (an empty surface: every shard still makes its empty call, for the single-device entry's own checks and stats)
+template <class Cells, class One>
+int sample_list_shards(const Cells *cells, const is3d_sampler_inputs *in, const is3d_options *opts, const std::vector<int> &dev,
+                       bool edomain_keeps_rest, is3d_particle *particles, int64_t capacity, int64_t *n_particles, is3d_sampler_stats *stats, One one)
+{
+    DeviceRestore restore;
+    std::vector<SamplerShardT<Cells>> sh(dev.size());
+    const int n_active = assign_shards(sh, dev, cells->n_cells);
+    const bool fill = capacity > 0;
+    run_shards(sh, n_active ? has_cells : every_shard, [&](int i) {
+        SamplerShardT<Cells> &s = sh[i];
+        slice_shard(s, *cells, *in, *opts);
+        int rc = one(s, nullptr, 0);
+        if ((!rc || (edomain_keeps_rest && rc == IS3D_EDOMAIN)) && fill && s.count > 0) {   // (a bad cell leaves the shard's other hadrons sampled)
+            s.list.resize((size_t)s.count);
+            rc = one(s, s.list.data(), s.count);
+        }
+        return rc;
+    });
+    std::string bad_cell;
+    if (int rc = sampler_totals(sh, edomain_keeps_rest, n_particles, stats, &bad_cell)) return rc;
+    if (fill) merge_shard_lists(sh, in->n_events, particles, capacity);
+    if (!bad_cell.empty()) return fail(IS3D_EDOMAIN, "%s", bad_cell.c_str());   // after the merge: the list is returned with the error
+    if (fill && *n_particles > capacity)
+        return fail(IS3D_ENOMEM, "particle buffer too small: %lld particles, capacity %lld", (long long)*n_particles, (long long)capacity);
+    return IS3D_OK;
+}
+
+// the eight arrays of an is3d_sampler_hist laid end to end as one block of int64_t: a shard's histograms
+struct HistBlock {
+    int64_t len[8], words = 0;
+    HistBlock(const is3d_sampler_test_bins &b, int64_t n_species, int64_t n_events)
+    {
+        const int64_t S = n_species, P = (int64_t)IS3D_SAMPLER_VN_HARMONICS * S * b.pT_bins;
+        const int64_t l[8] = {S * b.y_bins, S * b.eta_bins, S * b.pT_bins, S * b.tau_bins, S * b.r_bins, P, P, n_events};
+        for (int a = 0; a < 8; a++) words += len[a] = l[a];
+    }
+    static std::array<int64_t *, 8> arrays(const is3d_sampler_hist &h) { return {h.dN_dy, h.dN_deta, h.dN_pT, h.dN_tau, h.dN_r, h.vn_re, h.vn_im, h.yield}; }
+    is3d_sampler_hist view(int64_t *block) const
+    {
+        int64_t *p[8];
+        for (int a = 0; a < 8; a++) { p[a] = block; block += len[a]; }
+        return {p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7]};
+    }
+    void zero(const is3d_sampler_hist &h) const
+    {
+        const auto out = arrays(h);
+        for (int a = 0; a < 8; a++) memset(out[a], 0, (size_t)len[a] * sizeof(int64_t));
+    }
+    void add(const is3d_sampler_hist &h, const int64_t *block) const
+    {
+        const auto out = arrays(h);
+        for (int a = 0; a < 8; a++) {
+            for (int64_t j = 0; j < len[a]; j++) out[a][j] += block[j];
+            block += len[a];
+        }
+    }
+    int check_counts(const is3d_sampler_hist &h) const
+    {
+        for (int64_t j = 0; j < len[2]; j++)
+            if (h.dN_pT[j] > IS3D_SAMPLER_VN_MAX_COUNT)
+                return fail(IS3D_EDOMAIN, "dN_pT bin %lld holds %lld hadrons: the fixed-point harmonic sums are exact up to %lld per bin", (long long)j,
+                            (long long)h.dN_pT[j], (long long)IS3D_SAMPLER_VN_MAX_COUNT);
+        return IS3D_OK;
+    }
+};
+// The binned driver.  one(shard, hist): the family's single-device binned entry on the shard's slice, into s.count and s.st.  Every shard
+// samples and bins its own cells on its device into its own block; the integer histograms are added here -- an exact sum, so the result is
+// the single-device one bit for bit.  The caller's arrays are zeroed whatever the shards return.  bins and hist have been checked
+template <class Cells, class One>
+int sample_binned_shards(const Cells *cells, const is3d_sampler_inputs *in, const is3d_options *opts, const std::vector<int> &dev,
+                         bool edomain_keeps_rest, const is3d_sampler_test_bins *bins, int32_t n_species, const is3d_sampler_hist *hist,
+                         int64_t *n_particles, is3d_sampler_stats *stats, One one)
+{
+    const HistBlock hb(*bins, n_species, in->n_events);
+    DeviceRestore restore;
+    std::vector<SamplerShardT<Cells>> sh(dev.size());
+    const int n_active = assign_shards(sh, dev, cells->n_cells);
+    run_shards(sh, n_active ? has_cells : every_shard, [&](int i) {   // (an empty surface: as in sample_list_shards)
+        SamplerShardT<Cells> &s = sh[i];
+        slice_shard(s, *cells, *in, *opts);
+        s.h.assign((size_t)hb.words, 0);
+        const is3d_sampler_hist hs = hb.view(s.h.data());
+        return one(s, &hs);
+    });
+    hb.zero(*hist);
+    std::string bad_cell;
+    if (int rc = sampler_totals(sh, edomain_keeps_rest, n_particles, stats, &bad_cell)) return rc;
+    for (const SamplerShardT<Cells> &s : sh)
+        if (!s.h.empty()) hb.add(*hist, s.h.data());   // (a shard without cells made no call)
+    if (!bad_cell.empty()) return fail(IS3D_EDOMAIN, "%s", bad_cell.c_str());   // after the sum: the histograms are returned with the error
+    return hb.check_counts(*hist);
+}
+
+// is3d_sample_binned_multi (fuse = false) | is3d_sample_fused_multi
+int viscous_binned_multi(bool fuse, const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                         const is3d_options *opts, const int32_t *devices, int32_t n_devices, const is3d_sampler_test_bins *bins,
+                         const is3d_sampler_hist *hist, int64_t *n_particles, is3d_sampler_stats *stats)
+{
+    if (!cells || !species || !in || !opts || !bins || !hist || !n_particles) return fail(IS3D_EINVAL, "null argument");
+    zero_outputs(n_particles, stats);
+    // (the fused entry: every refusal of the bins before the device list is looked at: none of them needs a device)
+    if (fuse)
+        if (int rc = is3d::sampler_check_fused_args(bins, hist, in->n_events, std::max<int32_t>(species->n, 1))) return rc;
+    if (cells->n_cells < 0) return fail(IS3D_EINVAL, "n_cells < 0");
+    std::vector<int> dev;
+    if (int rc = resolve_devices(devices, n_devices, dev)) return rc;
+    const auto single = fuse ? is3d_sample_fused : is3d_sample_binned;
+    if (dev.size() == 1) {
+        const is3d_options o = on_device(*opts, dev[0]);
+        return single(cells, species, df, in, &o, bins, hist, n_particles, stats);
+    }
+    if (in->n_events < 1 || species->n < 1 || bins->y_bins < 1 || bins->eta_bins < 1 || bins->pT_bins < 1 || bins->tau_bins < 1 || bins->r_bins < 1)
+        return fail(IS3D_EINVAL, "n_events, the species count and every bin count must be >= 1");
+    if (!hist->dN_dy || !hist->dN_deta || !hist->dN_pT || !hist->dN_tau || !hist->dN_r || !hist->vn_re || !hist->vn_im || !hist->yield)
+        return fail(IS3D_EINVAL, "null argument");
+    return sample_binned_shards(cells, in, opts, dev, false, bins, species->n, hist, n_particles, stats,
+                                [&](SamplerShardT<is3d_cells> &s, const is3d_sampler_hist *h) {
+                                    return single(&s.c, species, df, &s.si, &s.o, bins, h, &s.count, &s.st);
+                                });
+}
 }  // namespace
 
 extern "C" int is3d_sample_particles_multi(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df,
@@ -1155,280 +1304,77 @@ extern "C" int is3d_sample_particles_multi(const is3d_cells *cells, const is3d_s
                                            is3d_sampler_stats *stats)
 {
     if (!cells || !in || !opts || !n_particles) return fail(IS3D_EINVAL, "null argument");
-    *n_particles = 0;
-    if (stats) memset(stats, 0, sizeof *stats);
+    zero_outputs(n_particles, stats);
     if (cells->n_cells < 0) return fail(IS3D_EINVAL, "n_cells < 0");
     std::vector<int> dev;
     if (int rc = resolve_devices(devices, n_devices, dev)) return rc;
-    n_devices = (int32_t)dev.size();
     if (particles == nullptr) capacity = 0;
-    if (n_devices == 1) {
-        is3d_options o = *opts;
-        o.device = dev[0];
+    if (dev.size() == 1) {
+        const is3d_options o = on_device(*opts, dev[0]);
         return is3d_sample_particles(cells, species, df, in, &o, particles, capacity, n_particles, stats);
     }
-    struct SShard : SamplerShard { std::vector<is3d_particle> list; };
-    DeviceRestore restore;
-    std::vector<SShard> sh(n_devices);
-    const int n_active = assign_shards(sh, dev, cells->n_cells);
-    const bool fill = capacity > 0;
-    // (an empty surface: every shard still makes its empty call, for the single-device entry's own checks and stats)
-    run_shards(sh, n_active ? has_cells : every_shard, [&](int i) {   // count, then fill a list of that size
-        SShard &s = sh[i];
-        sampler_shard(s, cells, in, opts);
-        int rc = is3d_sample_particles(&s.c, species, df, &s.si, &s.o, nullptr, 0, &s.count, &s.st);
-        if (!rc && fill && s.count > 0) {
-            s.list.resize((size_t)s.count);
-            rc = is3d_sample_particles(&s.c, species, df, &s.si, &s.o, s.list.data(), s.count, &s.count, &s.st);
-        }
-        return rc;
-    });
-    if (int rc = sampler_totals(sh, n_particles, stats)) return rc;
-    if (!fill) return IS3D_OK;
-    merge_shard_lists(sh, in->n_events, particles, capacity);
-    if (*n_particles > capacity)
-        return fail(IS3D_ENOMEM, "particle buffer too small: %lld particles, capacity %lld", (long long)*n_particles, (long long)capacity);
-    return IS3D_OK;
+    return sample_list_shards(cells, in, opts, dev, false, particles, capacity, n_particles, stats,
+                              [&](SamplerShardT<is3d_cells> &s, is3d_particle *p, int64_t cap) {
+                                  return is3d_sample_particles(&s.c, species, df, &s.si, &s.o, p, cap, &s.count, &s.st);
+                              });
 }
 
-// ------------------------------------------------------------------------------------------------
-// anisotropic-hydro particle sampler (is3d_sample_particles_vah) over several devices: the same shards, first_cell advanced, the same merge
-// ------------------------------------------------------------------------------------------------
 extern "C" int is3d_sample_particles_vah_multi(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab,
                                                const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices,
                                                int32_t n_devices, is3d_particle *particles, int64_t capacity, int64_t *n_particles,
                                                is3d_sampler_stats *stats)
 {
     if (!n_particles) return fail(IS3D_EINVAL, "null argument");
-    *n_particles = 0;
-    if (stats) memset(stats, 0, sizeof *stats);
+    zero_outputs(n_particles, stats);
     if (int rc = is3d::sampler_vah_check(cells, species, tab, in, opts)) return rc;
     std::vector<int> dev;
     if (int rc = resolve_devices(devices, n_devices, dev)) return rc;
-    n_devices = (int32_t)dev.size();
     if (particles == nullptr) capacity = 0;
-    if (n_devices == 1) {
-        is3d_options o = *opts;
-        o.device = dev[0];
+    if (dev.size() == 1) {
+        const is3d_options o = on_device(*opts, dev[0]);
         return is3d_sample_particles_vah(cells, species, tab, in, &o, particles, capacity, n_particles, stats);
     }
-    struct VShard : ShardBase {
-        is3d_vah_cells c;
-        is3d_sampler_inputs si;
-        is3d_options o;
-        int64_t count = 0;
-        is3d_sampler_stats st{};
-        std::vector<is3d_particle> list;
-    };
-    DeviceRestore restore;
-    std::vector<VShard> sh(n_devices);
-    const int n_active = assign_shards(sh, dev, cells->n_cells);
-    const bool fill = capacity > 0;
-    run_shards(sh, n_active ? has_cells : every_shard, [&](int i) {   // count, then fill a list of that size
-        VShard &s = sh[i];
-        auto a = is3d::cell_arrays(*cells);
-        for (auto &f : a)
-            if (f) f += s.lo;
-        s.c = is3d::cells_from_arrays(s.hi - s.lo, a);
-        s.si = *in;
-        s.si.first_cell = in->first_cell + s.lo;
-        if (s.si.x) s.si.x += s.lo;
-        if (s.si.y) s.si.y += s.lo;
-        s.o = *opts;
-        s.o.device = s.device;
-        int rc = is3d_sample_particles_vah(&s.c, species, tab, &s.si, &s.o, nullptr, 0, &s.count, &s.st);
-        if ((!rc || rc == IS3D_EDOMAIN) && fill && s.count > 0) {    // (a bad cell leaves the shard's other hadrons sampled)
-            s.list.resize((size_t)s.count);
-            rc = is3d_sample_particles_vah(&s.c, species, tab, &s.si, &s.o, s.list.data(), s.count, &s.count, &s.st);
-        }
-        return rc;
-    });
-    // a bad cell is reported (the first failed shard holds the lowest global index) after the merge: the list is returned with the error
-    int rc0;
-    std::string text;
-    first_error(sh, &rc0, &text);
-    bool only_domain = rc0 == IS3D_EDOMAIN;
-    for (const VShard &s : sh)
-        if (s.rc && s.rc != IS3D_EDOMAIN) only_domain = false;
-    if (rc0 && !only_domain) return fail(rc0, "%s", text.c_str());
-    if (only_domain)
-        for (VShard &s : sh) s.rc = IS3D_OK;
-    if (int rc = sampler_totals(sh, n_particles, stats)) return rc;
-    if (fill) merge_shard_lists(sh, in->n_events, particles, capacity);
-    if (only_domain) return fail(IS3D_EDOMAIN, "%s", text.c_str());
-    if (fill && *n_particles > capacity)
-        return fail(IS3D_ENOMEM, "particle buffer too small: %lld particles, capacity %lld", (long long)*n_particles, (long long)capacity);
-    return IS3D_OK;
+    return sample_list_shards(cells, in, opts, dev, true, particles, capacity, n_particles, stats,
+                              [&](SamplerShardT<is3d_vah_cells> &s, is3d_particle *p, int64_t cap) {
+                                  return is3d_sample_particles_vah(&s.c, species, tab, &s.si, &s.o, p, cap, &s.count, &s.st);
+                              });
 }
 
-// is3d_sample_binned_vah over the same shards: every shard samples and bins its own cells on its device, the integer histograms are added
-// here -- an exact sum, so the result is the single-device one bit for bit.  A bad cell leaves the other cells binned, in every shard.
 extern "C" int is3d_sample_binned_vah_multi(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab,
                                             const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices, int32_t n_devices,
                                             const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
                                             is3d_sampler_stats *stats)
 {
     if (!n_particles) return fail(IS3D_EINVAL, "null argument");
-    *n_particles = 0;
-    if (stats) memset(stats, 0, sizeof *stats);
+    zero_outputs(n_particles, stats);
     if (int rc = is3d::sampler_vah_check(cells, species, tab, in, opts)) return rc;
     if (int rc = is3d::sampler_check_fused_args(bins, hist, in->n_events, species->n)) return rc;
     std::vector<int> dev;
     if (int rc = resolve_devices(devices, n_devices, dev)) return rc;
-    n_devices = (int32_t)dev.size();
-    if (n_devices == 1) {
-        is3d_options o = *opts;
-        o.device = dev[0];
+    if (dev.size() == 1) {
+        const is3d_options o = on_device(*opts, dev[0]);
         return is3d_sample_binned_vah(cells, species, tab, in, &o, bins, hist, n_particles, stats);
     }
-    // the arrays of is3d_sampler_hist laid end to end, as one block per shard
-    const int64_t S = species->n, E = in->n_events, P = (int64_t)IS3D_SAMPLER_VN_HARMONICS * S * bins->pT_bins;
-    const int64_t len[8] = {S * bins->y_bins, S * bins->eta_bins, S * bins->pT_bins, S * bins->tau_bins, S * bins->r_bins, P, P, E};
-    int64_t *const out[8] = {hist->dN_dy, hist->dN_deta, hist->dN_pT, hist->dN_tau, hist->dN_r, hist->vn_re, hist->vn_im, hist->yield};
-    int64_t words = 0;
-    for (int a = 0; a < 8; a++) words += len[a];
-    struct VBShard : ShardBase {
-        is3d_vah_cells c;
-        is3d_sampler_inputs si;
-        is3d_options o;
-        int64_t count = 0;
-        is3d_sampler_stats st{};
-        std::vector<int64_t> h;
-    };
-    DeviceRestore restore;
-    std::vector<VBShard> sh(n_devices);
-    const int n_active = assign_shards(sh, dev, cells->n_cells);
-    run_shards(sh, n_active ? has_cells : every_shard, [&](int i) {
-        VBShard &s = sh[i];
-        auto a = is3d::cell_arrays(*cells);
-        for (auto &f : a)
-            if (f) f += s.lo;
-        s.c = is3d::cells_from_arrays(s.hi - s.lo, a);
-        s.si = *in;
-        s.si.first_cell = in->first_cell + s.lo;
-        if (s.si.x) s.si.x += s.lo;
-        if (s.si.y) s.si.y += s.lo;
-        s.o = *opts;
-        s.o.device = s.device;
-        s.h.assign((size_t)words, 0);
-        int64_t *q = s.h.data();
-        int64_t *part[8];
-        for (int k = 0; k < 8; k++) { part[k] = q; q += len[k]; }
-        const is3d_sampler_hist hs{part[0], part[1], part[2], part[3], part[4], part[5], part[6], part[7]};
-        return is3d_sample_binned_vah(&s.c, species, tab, &s.si, &s.o, bins, &hs, &s.count, &s.st);
-    });
-    for (int a = 0; a < 8; a++) memset(out[a], 0, (size_t)len[a] * sizeof(int64_t));
-    // a bad cell is reported (the first failed shard holds the lowest global index) after the sum: the histograms are returned with the error
-    int rc0;
-    std::string text;
-    first_error(sh, &rc0, &text);
-    bool only_domain = rc0 == IS3D_EDOMAIN;
-    for (const VBShard &s : sh)
-        if (s.rc && s.rc != IS3D_EDOMAIN) only_domain = false;
-    if (rc0 && !only_domain) return fail(rc0, "%s", text.c_str());
-    if (only_domain)
-        for (VBShard &s : sh) s.rc = IS3D_OK;
-    if (int rc = sampler_totals(sh, n_particles, stats)) return rc;
-    for (const VBShard &s : sh) {
-        if (s.h.empty()) continue;   // a shard without cells made no call
-        const int64_t *q = s.h.data();
-        for (int a = 0; a < 8; a++) {
-            for (int64_t j = 0; j < len[a]; j++) out[a][j] += q[j];
-            q += len[a];
-        }
-    }
-    if (only_domain) return fail(IS3D_EDOMAIN, "%s", text.c_str());
-    for (int64_t j = 0; j < len[2]; j++)
-        if (hist->dN_pT[j] > IS3D_SAMPLER_VN_MAX_COUNT)
-            return fail(IS3D_EDOMAIN, "dN_pT bin %lld holds %lld hadrons: the fixed-point harmonic sums are exact up to %lld per bin", (long long)j,
-                        (long long)hist->dN_pT[j], (long long)IS3D_SAMPLER_VN_MAX_COUNT);
-    return IS3D_OK;
+    return sample_binned_shards(cells, in, opts, dev, true, bins, species->n, hist, n_particles, stats,
+                                [&](SamplerShardT<is3d_vah_cells> &s, const is3d_sampler_hist *h) {
+                                    return is3d_sample_binned_vah(&s.c, species, tab, &s.si, &s.o, bins, h, &s.count, &s.st);
+                                });
 }
-
-// is3d_sample_binned | is3d_sample_fused over the same shards: every shard bins its own hadrons on its device, the integer histograms are
-// added here -- an exact sum, so the result is the single-device one bit for bit
-namespace {
-// one: is3d_sample_binned | is3d_sample_fused
-using BinnedOneShot = int (*)(const is3d_cells *, const is3d_species *, const is3d_df_tables *, const is3d_sampler_inputs *, const is3d_options *,
-                              const is3d_sampler_test_bins *, const is3d_sampler_hist *, int64_t *, is3d_sampler_stats *);
-int sample_binned_shards(BinnedOneShot one, const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df,
-                         const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices, int32_t n_devices,
-                         const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles, is3d_sampler_stats *stats)
-{
-    if (!cells || !species || !in || !opts || !bins || !hist || !n_particles) return fail(IS3D_EINVAL, "null argument");
-    *n_particles = 0;
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (cells->n_cells < 0) return fail(IS3D_EINVAL, "n_cells < 0");
-    std::vector<int> dev;
-    if (int rc = resolve_devices(devices, n_devices, dev)) return rc;
-    n_devices = (int32_t)dev.size();
-    if (n_devices == 1) {
-        is3d_options o = *opts;
-        o.device = dev[0];
-        return one(cells, species, df, in, &o, bins, hist, n_particles, stats);
-    }
-    if (in->n_events < 1 || species->n < 1 || bins->y_bins < 1 || bins->eta_bins < 1 || bins->pT_bins < 1 || bins->tau_bins < 1 || bins->r_bins < 1)
-        return fail(IS3D_EINVAL, "n_events, the species count and every bin count must be >= 1");
-    if (!hist->dN_dy || !hist->dN_deta || !hist->dN_pT || !hist->dN_tau || !hist->dN_r || !hist->vn_re || !hist->vn_im || !hist->yield)
-        return fail(IS3D_EINVAL, "null argument");
-    // the arrays of is3d_sampler_hist laid end to end, as one block per shard
-    const int64_t S = species->n, E = in->n_events, P = (int64_t)IS3D_SAMPLER_VN_HARMONICS * S * bins->pT_bins;
-    const int64_t len[8] = {S * bins->y_bins, S * bins->eta_bins, S * bins->pT_bins, S * bins->tau_bins, S * bins->r_bins, P, P, E};
-    int64_t *const out[8] = {hist->dN_dy, hist->dN_deta, hist->dN_pT, hist->dN_tau, hist->dN_r, hist->vn_re, hist->vn_im, hist->yield};
-    int64_t words = 0;
-    for (int a = 0; a < 8; a++) words += len[a];
-    struct BShard : SamplerShard { std::vector<int64_t> h; };
-    DeviceRestore restore;
-    std::vector<BShard> sh(n_devices);
-    const int n_active = assign_shards(sh, dev, cells->n_cells);
-    run_shards(sh, n_active ? has_cells : every_shard, [&](int i) {   // (an empty surface: as in is3d_sample_particles_multi)
-        BShard &s = sh[i];
-        sampler_shard(s, cells, in, opts);
-        s.h.assign((size_t)words, 0);
-        int64_t *q = s.h.data();
-        int64_t *part[8];
-        for (int a = 0; a < 8; a++) { part[a] = q; q += len[a]; }
-        const is3d_sampler_hist hs{part[0], part[1], part[2], part[3], part[4], part[5], part[6], part[7]};
-        return one(&s.c, species, df, &s.si, &s.o, bins, &hs, &s.count, &s.st);
-    });
-    for (int a = 0; a < 8; a++) memset(out[a], 0, (size_t)len[a] * sizeof(int64_t));
-    if (int rc = sampler_totals(sh, n_particles, stats)) return rc;
-    for (const BShard &s : sh) {
-        if (s.h.empty()) continue;   // a shard without cells made no call
-        const int64_t *q = s.h.data();
-        for (int a = 0; a < 8; a++) {
-            for (int64_t j = 0; j < len[a]; j++) out[a][j] += q[j];
-            q += len[a];
-        }
-    }
-    for (int64_t j = 0; j < len[2]; j++)
-        if (hist->dN_pT[j] > IS3D_SAMPLER_VN_MAX_COUNT)
-            return fail(IS3D_EDOMAIN, "dN_pT bin %lld holds %lld hadrons: the fixed-point harmonic sums are exact up to %lld per bin", (long long)j,
-                        (long long)hist->dN_pT[j], (long long)IS3D_SAMPLER_VN_MAX_COUNT);
-    return IS3D_OK;
-}
-}  // namespace
 
 extern "C" int is3d_sample_binned_multi(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df,
                                         const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices, int32_t n_devices,
                                         const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
                                         is3d_sampler_stats *stats)
 {
-    return sample_binned_shards(is3d_sample_binned, cells, species, df, in, opts, devices, n_devices, bins, hist, n_particles, stats);
+    return viscous_binned_multi(false, cells, species, df, in, opts, devices, n_devices, bins, hist, n_particles, stats);
 }
 
-// is3d_sample_fused over the same shards: the same exact sum of integer histograms
 extern "C" int is3d_sample_fused_multi(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df,
                                        const is3d_sampler_inputs *in, const is3d_options *opts, const int32_t *devices, int32_t n_devices,
                                        const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int64_t *n_particles,
                                        is3d_sampler_stats *stats)
 {
-    // (every refusal of the bins before the device list is looked at: none of them needs a device)
-    if (!cells || !species || !in || !opts || !bins || !hist || !n_particles) return fail(IS3D_EINVAL, "null argument");
-    *n_particles = 0;
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (int rc = is3d::sampler_check_fused_args(bins, hist, in->n_events, std::max<int32_t>(species->n, 1))) return rc;
-    return sample_binned_shards(is3d_sample_fused, cells, species, df, in, opts, devices, n_devices, bins, hist, n_particles, stats);
+    return viscous_binned_multi(true, cells, species, df, in, opts, devices, n_devices, bins, hist, n_particles, stats);
 }
 
 // ------------------------------------------------------------------------------------------------
