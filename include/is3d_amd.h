@@ -260,7 +260,12 @@ int is3d_probe_shader_clock(int32_t device, double seconds, double *ghz);
  * device, y[i] = f(x[i]) for HOST arrays of n doubles -- so that their accuracy is a tested number, not a comment.  which: 0 exp_full
  * (Cody-Waite, degree 10) | 1 exp_p9 (one-fma reduction, degree 9; |x| < 1.4e9) | 2 exp_p9_sat | 3 exp_full_sat (|x| up to ~1e45) | 4 sqrt_g1 (v_rsq_f64 +
  * one Goldschmidt step) | 5 sqrt_nr | 6 rcp_nr1 (v_rcp_f64 + one Newton step) | 7 rcp_nr (two steps) | 8 exp_p9_scaled with e = 5 (32 e^x: the
- * power-of-two factor cf_main_feqmod takes out of p.dsigma comes back through the exponential's shift constant). */
+ * power-of-two factor cf_main_feqmod takes out of p.dsigma comes back through the exponential's shift constant).
+ * Functions of several arguments read records of `arity` consecutive doubles from x and write one result per record slot; n must be a
+ * multiple of the arity (IS3D_EINVAL otherwise).  9 add_clamp01 (a, b) | 10 fma_clamp01 (a, b, c) | 11 fma_clamp01_half (a, b): the add / fma
+ * with the VOP3 clamp modifier that forms max(p.dsigma 2^-e, 0), min(max(fl(a b + c), 0), 1) with NaN -> 0, the value repeated over the
+ * record | 12 exp_p9_scaled (v, e): 2^e exp_p9(v) for an integer e, repeated over the record | 13, 14, 15, 16 rcp_batch<RB> with RB = 2, 3,
+ * 4, 8: slot i of a record gets 1 / x_i from the batch's one shared reciprocal. */
 int is3d_math_probe(int32_t which, int64_t n, const double *x, double *y, int32_t device);
 /* Diagnostic (no reference counterpart): process-wide counts of the plans this library has created (is3d_plan_create*, the per-shard plans of
  * is3d_multi_plan_create and of the one-shot entries) and of the device allocations (hipMalloc) it has made, since the library was loaded.  What a

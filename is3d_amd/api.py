@@ -1226,7 +1226,10 @@ class Comm:
             pass
 
 
-MATH_FUNCS = dict(exp_full=0, exp_p9=1, exp_p9_sat=2, exp_full_sat=3, sqrt_g1=4, sqrt_nr=5, rcp_nr1=6, rcp_nr=7, exp_p9_x32=8)
+MATH_FUNCS = dict(exp_full=0, exp_p9=1, exp_p9_sat=2, exp_full_sat=3, sqrt_g1=4, sqrt_nr=5, rcp_nr1=6, rcp_nr=7, exp_p9_x32=8,
+                  add_clamp01=9, fma_clamp01=10, fma_clamp01_half=11, exp_p9_scaled=12, rcp_batch2=13, rcp_batch3=14, rcp_batch4=15, rcp_batch8=16)
+# functions of several arguments: doubles per record (is3d_amd.h); the others take one
+MATH_ARITY = dict(add_clamp01=2, fma_clamp01=3, fma_clamp01_half=2, exp_p9_scaled=2, rcp_batch2=2, rcp_batch3=3, rcp_batch4=4, rcp_batch8=8)
 
 
 def resource_counters():
@@ -1239,12 +1242,18 @@ def resource_counters():
 
 
 def math_probe(which, x, device=-1):
-    """is3d_math_probe: the device's elementary function `which` (a key of MATH_FUNCS) at the host array x."""
+    """is3d_math_probe: the device's elementary function `which` (a key of MATH_FUNCS) at the host array x.  A function of several arguments
+    (MATH_ARITY) takes x as [records][arity] and returns [records] -- the rcp_batch functions [records][arity], one quotient per slot."""
     xs = _f64(x)
     y = np.zeros_like(xs)
     L = load()
     L.is3d_math_probe.argtypes = [C.c_int32, C.c_int64, _dp, _dp, C.c_int32]
     _check(L.is3d_math_probe(MATH_FUNCS[which], xs.size, _p(xs), _p(y), int(device)))
+    arity = MATH_ARITY.get(which, 1)
+    if arity > 1:
+        y = y.reshape(-1, arity)
+        if not which.startswith("rcp_batch"):
+            y = np.ascontiguousarray(y[:, 0])
     return y
 
 

@@ -63,7 +63,8 @@ struct PrepParams {
     double *TS;
     const unsigned long long *pds_bound;   // tiled stream: bits of a bound on |p.dsigma| over all lanes and cells (cf_pds_bound)
     double mTmax, kmin, kmax;       // largest lane mT; range of the k grid (y in 3+1D, eta nodes in 2+1D): bound of p.u/T
-    unsigned long long *status;     // [0] min bad cell (global index), [1] skipped count, [7] min cell whose p.u/T can exceed 1e9
+    double pTmax, gw2d;             // largest lane pT, max_k w_k cosh(eta_k) (2+1D): with the above, the cell's term of cf_pds_bound
+    unsigned long long *status;     // [0] min bad cell (global index), [1] skipped count, [7] min cell whose p.u/T can exceed 1e9 or whose |p.dsigma| can exceed 1e300
     // E2 table stream (kernel variant 5, see "TE" below); TE == nullptr: not written
     int32_t w0_share;               // wave 0's share of a batch's units (% of another wave's) while it runs the next batch's phase 1
     int32_t pair_writer;            // tiled stream: the record writer handles two elements per lane and trip (set by launch_prep)

@@ -471,15 +471,21 @@ __global__ void __launch_bounds__(kFqThreads) cf_prep_feqmod(FqPrepParams p)
                     for (int jt = 0; jt < p.jtiles; jt++) Bmax = fmax(Bmax, ub[3 * p.rblocks + p.rblocks * p.jtiles + 2 * jt + 1]);
                     const double bound = (p.mTmax * Amax + p.pTmax * Bmax * Wmax) * 1.0000001;
                     if (bound >= 1.0 && bound < 1.0e300) ec = __builtin_amdgcn_frexp_exp(bound);   // bound < 2^ec
+                    // a bound of 1e300 or more (or none: inf, NaN) has no scale, and unscaled the clamp would return 1 -- a finite, wrong
+                    // spectrum: the cell is reported (status[7]) and left out, its rows zeroed below (e_c = -1 says so until then)
+                    else if (!(bound < 1.0)) { ec = -1; atomicMin(&p.status[7], (unsigned long long)(p.cell0 + cbase + tid)); }
                 }
                 cs[tid].shiftc = kExpShift + (double)ec;
             }
             __syncthreads();
             if (p.scale_rows) {
                 for (int idx = tid; idx < ncb * K; idx += kFqThreads) {
-                    const double sc = ldexp_fast(1.0, -(int)(cs[idx / K].shiftc - kExpShift));
-                    l_A[idx] *= sc; l_W[idx] *= sc;
+                    const int ec = (int)(cs[idx / K].shiftc - kExpShift);
+                    const double sc = ldexp_fast(1.0, -ec);
+                    l_A[idx] = ec < 0 ? 0.0 : l_A[idx] * sc; l_W[idx] = ec < 0 ? 0.0 : l_W[idx] * sc;
                 }
+                __syncthreads();
+                if (tid < ncb && cs[tid].shiftc < kExpShift) cs[tid].shiftc = kExpShift;
                 __syncthreads();
             }
         }

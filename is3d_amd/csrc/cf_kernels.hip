@@ -68,8 +68,15 @@ __device__ __forceinline__ double eval_tail(double z, double x, double br, doubl
 // cells of an execute, for the power-of-two scale of the tiled stream (cf_device.h):
 //   mTmax (|dat| + |dan|/tau) cosh(max_k |y_k - eta|) + pTmax (|dax| + |day|)     (x max eta weight in 2+1D)
 // Bits of a non-negative double order like unsigned integers, so atomicMax on the bit pattern is a float max.
-// Non-finite cells are ignored (they are skipped or reported by cf_prep).
+// Cells whose term is not below 1e300 (non-finite ones among them) are ignored here: cf_prep skips them (u.dsigma <= 0) or leaves them out
+// and reports them (status[7]) by the same term, pds_cell_bound -- with a scale taken from the other cells their clamp would return 1.
 // ------------------------------------------------------------------------------------------------
+// g: cosh(max_k |y_k - eta|) in 3+1D, max_k w_k cosh(eta_k) in 2+1D
+__device__ __forceinline__ double pds_cell_bound(double dat, double dax, double day, double dan, double tau, double g, double mTmax, double pTmax)
+{
+    return (mTmax * (fabs(dat) + fabs(dan / tau)) + pTmax * (fabs(dax) + fabs(day))) * g;
+}
+
 __global__ void __launch_bounds__(256)
 cf_pds_bound(CellPtrs cells, int64_t n_cells, int dim3, double kmin, double kmax, double gw2d, double mTmax, double pTmax,
              unsigned long long *__restrict__ out)
@@ -81,7 +88,7 @@ cf_pds_bound(CellPtrs cells, int64_t n_cells, int dim3, double kmin, double kmax
             const double eta = cells.eta[i];
             g = cosh(fmax(fabs(kmin - eta), fabs(kmax - eta)));
         }
-        const double b = (mTmax * (fabs(cells.dat[i]) + fabs(cells.dan[i] / cells.tau[i])) + pTmax * (fabs(cells.dax[i]) + fabs(cells.day[i]))) * g;
+        const double b = pds_cell_bound(cells.dat[i], cells.dax[i], cells.day[i], cells.dan[i], cells.tau[i], g, mTmax, pTmax);
         if (b < 1.0e300) m = fmax(m, b);   // false for NaN
     }
     for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
@@ -243,8 +250,12 @@ __global__ void __launch_bounds__(kPrepThreads) cf_prep(PrepParams p)
                 // exponent range of exp_core: p.u/T <= mTmax (u^tau + |tau u^eta|) cosh(max |y - eta|) / T must stay below 1e9
                 // (a Lorentz factor of several hundred at T = 0.1 GeV; the reference's exp() would return inf there)
                 const double eta0 = p.dim3 ? p.cells.eta[gi] : 0.0;
-                const double xb = p.mTmax * (ut + fabs(tau * un)) * cosh(fmax(fabs(p.kmin - eta0), fabs(p.kmax - eta0))) / T;
-                if (!(xb < 1.0e9)) {
+                const double chmax = cosh(fmax(fabs(p.kmin - eta0), fabs(p.kmax - eta0)));
+                const double xb = p.mTmax * (ut + fabs(tau * un)) * chmax / T;
+                // range of the stream's power-of-two scale: cf_pds_bound takes no cell whose term is 1e300 or more, so the scale would come
+                // from the other cells and this cell's clamped p.dsigma 2^-e would read 1 -- a finite, wrong spectrum.  Left out and reported.
+                const bool pds_ok = !p.pds_bound || pds_cell_bound(dat, dax, day, dan, tau, p.dim3 ? chmax : p.gw2d, p.mTmax, p.pTmax) < 1.0e300;
+                if (!(xb < 1.0e9) || !pds_ok) {
                     atomicMin(&p.status[7], (unsigned long long)gi);
                     valid = false;
                 }
@@ -2322,9 +2333,53 @@ hipError_t launch_observables(const double *dN, const double *phi_w, const doubl
 // ------------------------------------------------------------------------------------------------
 // Diagnostic: the elementary functions of cf_math.h, one evaluation per element (is3d_math_probe, include/is3d_amd.h).  The kernels'
 // accuracy claims -- exp_full 1.4e-15, exp_p9 7e-14, the one-step square root 3e-15, rcp_nr1 2e-15 -- are checked against glibc / numpy
-// through this entry in tests/test_gpu_math.py instead of being taken from the comments.
+// through this entry in tests/test_gpu_math.py instead of being taken from the comments; so are the helpers the p.dsigma clamp rests on
+// (add_clamp01, fma_clamp01, fma_clamp01_half, exp_p9_scaled with any integer e) and rcp_batch<2, 3, 4, 8>.
 // ------------------------------------------------------------------------------------------------
+// Functions of several arguments (which >= 9) read records of `arity` consecutive doubles and write one result per record slot: the
+// clamp helpers and exp_p9_scaled (v, e) repeat their value over the record, rcp_batch<RB> writes 1 / q_i into slot i.
 namespace is3d {
+int math_probe_arity(int which)
+{
+    switch (which) {
+    case 9: case 11: case 12: case 13: return 2;   // add_clamp01 (a, b), fma_clamp01_half (a, b), exp_p9_scaled (v, e), rcp_batch<2>
+    case 10: case 14: return 3;                    // fma_clamp01 (a, b, c), rcp_batch<3>
+    case 15: return 4;                             // rcp_batch<4>
+    case 16: return 8;                             // rcp_batch<8>
+    default: return (which >= 0 && which <= 8) ? 1 : 0;
+    }
+}
+
+template <int RB>
+__device__ __forceinline__ void probe_rcp_batch(const double *__restrict__ x, double *__restrict__ y)
+{
+    double q[RB], inv[RB];
+#pragma unroll
+    for (int i = 0; i < RB; i++) q[i] = x[i];
+    rcp_batch<RB>(q, inv);
+#pragma unroll
+    for (int i = 0; i < RB; i++) y[i] = inv[i];
+}
+
+__global__ void __launch_bounds__(256) cf_math_probe_rec(int which, int arity, int64_t nrec, const double *__restrict__ x, double *__restrict__ y)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nrec) return;
+    x += i * arity; y += i * arity;
+    double r;
+    switch (which) {
+    case 9: r = add_clamp01(x[0], x[1]); break;
+    case 10: r = fma_clamp01(x[0], x[1], x[2]); break;
+    case 11: r = fma_clamp01_half(x[0], x[1]); break;
+    case 12: r = exp_p9_scaled(x[0], kExpShift + x[1]); break;   // 2^e exp_p9(v), e an integer
+    case 13: probe_rcp_batch<2>(x, y); return;
+    case 14: probe_rcp_batch<3>(x, y); return;
+    case 15: probe_rcp_batch<4>(x, y); return;
+    default: probe_rcp_batch<8>(x, y); return;
+    }
+    for (int s = 0; s < arity; s++) y[s] = r;
+}
+
 __global__ void __launch_bounds__(256) cf_math_probe(int which, int64_t n, const double *__restrict__ x, double *__restrict__ y)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2348,6 +2403,12 @@ __global__ void __launch_bounds__(256) cf_math_probe(int which, int64_t n, const
 hipError_t launch_math_probe(int which, int64_t n, const double *x, double *y, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
+    const int arity = math_probe_arity(which);
+    if (arity > 1) {   // n is a multiple of the arity (is3d_math_probe)
+        const int64_t nrec = n / arity;
+        hipLaunchKernelGGL(cf_math_probe_rec, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, st, which, arity, nrec, x, y);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(cf_math_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, which, n, x, y);
     return hipGetLastError();
 }

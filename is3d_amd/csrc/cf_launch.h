@@ -40,7 +40,10 @@ int tile3e_stream_slack_doubles(int JT, int R);                  // variant 5: o
 hipError_t launch_observables(const double *dN, const double *phi_w, const double *pT_w, const double *coskphi,
                               const double *sinkphi, double *dndy, double *spec2pi, double *vn, int npart, int npT, int J,
                               int ny, hipStream_t st);
-// which: 0 exp_full | 1 exp_p9 | 2 exp_p9_sat | 3 exp_full_sat | 4 sqrt_g1 | 5 sqrt_nr | 6 rcp_nr1 | 7 rcp_nr  (cf_math.h), y[i] = f(x[i])
+// which: 0 exp_full | 1 exp_p9 | 2 exp_p9_sat | 3 exp_full_sat | 4 sqrt_g1 | 5 sqrt_nr | 6 rcp_nr1 | 7 rcp_nr | 8 exp_p9_scaled, e = 5  (cf_math.h),
+// y[i] = f(x[i]); 9 add_clamp01 | 10 fma_clamp01 | 11 fma_clamp01_half | 12 exp_p9_scaled (v, e) | 13 .. 16 rcp_batch<2, 3, 4, 8>: records of
+// math_probe_arity(which) doubles, one result per record slot (n a multiple of the arity)
+int math_probe_arity(int which);   // doubles per record; 0 for an unknown function
 hipError_t launch_math_probe(int which, int64_t n, const double *x, double *y, hipStream_t st);
 hipError_t launch_clock_probe(unsigned long long ref_ticks, unsigned long long *out /* 2 x 8 */, hipStream_t st);
 hipError_t launch_fold_status(const unsigned long long *status /* [8] */, unsigned long long *sticky /* [2] */, hipStream_t st);

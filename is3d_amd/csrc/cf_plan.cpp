@@ -591,7 +591,9 @@ extern "C" int is3d_probe_shader_clock(int32_t device, double seconds, double *g
 
 extern "C" int is3d_math_probe(int32_t which, int64_t n, const double *x, double *y, int32_t device)
 {
-    if (which < 0 || which > 8 || n < 0 || (n > 0 && (!x || !y))) return fail(IS3D_EINVAL, "is3d_math_probe: which in 0..8, n >= 0, non-null arrays");
+    const int arity = is3d::math_probe_arity(which);
+    if (arity < 1 || n < 0 || (n > 0 && (!x || !y))) return fail(IS3D_EINVAL, "is3d_math_probe: which in 0..16, n >= 0, non-null arrays");
+    if (n % arity) return fail(IS3D_EINVAL, "is3d_math_probe: function %d reads records of %d doubles, n = %lld is no multiple of that", (int)which, arity, (long long)n);
     if (is3d_device_count() < 1) return fail(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
     if (n == 0) return IS3D_OK;
     if (device >= 0) HIP_TRY(hipSetDevice(device));
@@ -671,6 +673,7 @@ static is3d::PrepParams fill_prep(const is3d_plan *P, const is3d_cells *cells, i
     pp.JT = P->JT; pp.R = P->KT; pp.jtiles = P->jtiles; pp.rblocks = P->rblocks;
     pp.TS = P->d_TS.p;
     pp.mTmax = P->mTmax; pp.kmin = P->kmin; pp.kmax = P->kmax;
+    pp.pTmax = P->pTmax; pp.gw2d = P->gw2d;
     pp.status = P->d_status.p;
     pp.pTgrid = P->d_pTgrid.p; pp.npT = P->npT;
     return pp;
@@ -691,7 +694,8 @@ static int status_finish(const is3d_plan *P, const unsigned long long h[8], int6
         *bad_cell = (int64_t)h[7];
         *code = IS3D_EDOMAIN;
         return fail(IS3D_EDOMAIN, "cell %lld: p.u/T can exceed 1e9 for the momentum grid (flow velocity / temperature outside the "
-                    "kernel's exponent range; the reference's exp() overflows to inf there)", (long long)*bad_cell);
+                    "kernel's exponent range; the reference's exp() overflows to inf there), or |p.dsigma| can exceed 1e300 (outside the range of "
+                    "the power-of-two scale behind the outflow cut)", (long long)*bad_cell);
     }
     if (*bad_cell >= 0) {
         *code = IS3D_EDOMAIN;
@@ -878,8 +882,8 @@ extern "C" int is3d_plan_check(is3d_plan *P, void *hip_stream, int64_t *bad_cell
     if (first == ~0ULL) return IS3D_OK;
     if (bad_cell) *bad_cell = (int64_t)first;
     if (h[1] <= h[0])
-        return fail(IS3D_EDOMAIN, "cell %llu (of an execute since the last check): p.u/T can exceed 1e9 for the momentum grid; the cell was left "
-                    "out of the spectrum (the reference's exp() overflows to inf there)", first);
+        return fail(IS3D_EDOMAIN, "cell %llu (of an execute since the last check): p.u/T can exceed 1e9 for the momentum grid (the reference's exp() "
+                    "overflows to inf there), or |p.dsigma| can exceed 1e300; the cell was left out of the spectrum", first);
     return fail(IS3D_EDOMAIN, "cell %llu (of an execute since the last check): T%s outside the coefficient table; the cell was left out of the "
                 "spectrum (the reference aborts in gsl_spline_eval here)", first, (P->feqmod && P->opts.df_mode == 4) ? " (or bulkPi/P)" : "");
 }
