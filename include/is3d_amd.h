@@ -1089,6 +1089,55 @@ int is3d_write_results_decays(const char *results_dir, int32_t dimension, int32_
                               const double *phi, int32_t n_y, const double *y, const double *dN);
 
 /* ---------------------------------------------------------------------------------------------
+ * Monte Carlo decays of a sampled particle list to stable particles (the reference has none: this comment is the definition; DESIGN.md
+ * section 3p).  Thread <-> primary; a primary's whole decay tree draws from ONE Philox stream, Rng(seed, 5, lo32(g), hi32(g)) with
+ * g = first_particle + i (streams 0-4 are the samplers'), so a list decayed in pieces gives the bits of the whole.
+ * Per particle of table entry e (lab momentum P, position (t, x, y, z), mass table->mass[e]), depth-first, first daughter next:
+ *   - stable[e]: final.  A channel has n = |npart| products and is OPEN when the left-to-right sum of its daughters' table masses is < the
+ *     parent's mass; no open channel: final as itself, counted in n_stuck.
+ *   - channel: u_ch; the first open channel j with u_ch * c_last < c_j, c_j the running sum of the open channels' branch_ratio in file order
+ *     (the last open channel otherwise): renormalised over the open channels.
+ *   - lifetime != 0: u_tau is drawn at every decay; width > 0: the parent moves by (P / m) tau*, tau* = -(hbarc / width) log1p(-u_tau), and
+ *     tau = sqrt(t^2 - z^2), eta = atanh(z / t) are recomputed; width <= 0: it decays where it is.
+ *   - cluster masses, flat n-body phase space by mass generation with rejection: T = M - sum m_i; n - 2 uniforms sorted ascending to
+ *     r_1 .. r_{n-2}; mu_k = sum_{i<=k} m_i + r_k T (r_0 = 0, r_{n-1} = 1); w = prod_{k=1}^{n-1} p*(mu_k; mu_{k-1}, m_k) with
+ *     p*(a; b, c) = sqrt(max((a-b-c)(a+b+c)(a+b-c)(a-b+c), 0)) / (2a); n > 2: u_acc, accepted when u_acc w_max < w, w_max =
+ *     prod_{k=1}^{n-1} p*(T + sum_{i<=k} m_i; sum_{i<k} m_i, m_k) (GENBOD's bound); after IS3D_DECAY_MC_MAX_TRIALS proposals the last one
+ *     is taken and counted in n_exhausted.  n = 2: no rejection, no draw.
+ *   - momenta, top-down from the cluster Pc = P: for k = n-1 .. 1, u_cos then u_phi (cos theta = 2 u_cos - 1, phi = 2 pi u_phi); in the
+ *     cluster's rest frame particle k gets (sqrt(p^2 + m_k^2), p d) and the remainder (sqrt(p^2 + mu_{k-1}^2), -p d), p = p*(mu_k; mu_{k-1}, m_k);
+ *     both go to the lab by one pure boost with beta = Pc_vec / Pc_0 (beta = 0: unchanged); the remainder becomes Pc, after k = 1 particle 0.
+ * All pointers HOST memory.  particles[i].species indexes chosen_mc_id (as the samplers return it); out[k].species indexes the TABLE
+ * (daughters need not be chosen species: table->mc_id is the mc_id argument of is3d_write_particle_list_osc); out[k].cell and .event are the
+ * primary's, origin[k] (may be NULL) its index in particles.  Order: primaries in input order, within one the final particles in depth-first
+ * pre-order over each channel's daughters in file order.  out == NULL counts only; with a list, capacity < *n_out returns IS3D_ENOMEM with
+ * the full count in *n_out and nothing written.  IS3D_EINVAL before any device use: a NULL argument, n_particles < 0, a species outside
+ * [0, n_chosen), a chosen or daughter id missing from the table, a channel of an unstable entry with more than IS3D_DECAY_MC_MAX_BODIES (or
+ * fewer than 2) products, a decay graph with a cycle, a worst-case pending stack beyond IS3D_DECAY_MC_MAX_STACK (need(e) = 1 for a final
+ * entry, else the maximum of need(d_i) + (n - 1 - i) over its channels' daughters d_i).  n_particles = 0: OK, *n_out = 0, no launch.  A good
+ * call without a device is IS3D_ENODEVICE (no CPU path).  Two runs agree bit for bit.
+ * --------------------------------------------------------------------------------------------- */
+#define IS3D_DECAY_MC_MAX_BODIES 5
+#define IS3D_DECAY_MC_MAX_STACK  16
+#define IS3D_DECAY_MC_MAX_TRIALS 4096
+typedef struct {
+    uint64_t seed;
+    int64_t  first_particle;  /* global index of particles[0]: a list decayed in pieces gives the bits of the whole */
+    int32_t  lifetime;        /* 0: daughters are born where the parent was; 1: the parent first flies a proper time drawn from exp(-t Gamma / hbarc) */
+    int32_t  device;          /* < 0: the current device */
+} is3d_decay_mc_inputs;
+typedef struct {
+    int64_t n_primaries, n_decays, n_final, n_stuck, n_trials, n_exhausted;
+    int32_t max_stack, max_depth;       /* static, from the table */
+    int32_t n_closed_channels, reserved;
+    double ms_h2d, ms_count, ms_fill, ms_d2h;
+} is3d_decay_mc_stats;
+int is3d_decay_particles(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
+                         const is3d_decay_mc_inputs *in, int64_t n_particles, const is3d_particle *particles,
+                         is3d_particle *out, int64_t *origin /* may be NULL */, int64_t capacity,
+                         int64_t *n_out, is3d_decay_mc_stats *stats /* may be NULL */);
+
+/* ---------------------------------------------------------------------------------------------
  * Driver: IS3D::run_particlization (src/cpp/iS3D.cpp:74-192; class IS3D, src/cpp/iS3D.h:19-96).  Reads iS3D_parameters.dat,
  * PDG/, tables/, deltaf_coefficients/ from the current directory and writes results/ exactly as the command line tool does
  * (which is this call with surface = NULL).  surface != NULL is the embedding path (read_fo_surf_from_memory +

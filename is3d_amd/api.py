@@ -116,7 +116,7 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_spin_polarization", "is3d_polarization_plan_create", "is3d_polarization_plan_execute", "is3d_polarization_plan_destroy",
            "is3d_write_polarization", "is3d_surface_vorticity", "is3d_spin_polarization_multi",
            "is3d_pdg_read_decays", "is3d_decay_q_factor", "is3d_resonance_decays", "is3d_decay_plan_create", "is3d_decay_plan_output_size",
-           "is3d_decay_plan_execute", "is3d_decay_plan_destroy", "is3d_write_results_decays",
+           "is3d_decay_plan_execute", "is3d_decay_plan_destroy", "is3d_write_results_decays", "is3d_decay_particles",
            "is3d_sampler_bin_list", "is3d_write_sampler_tests_binned", "is3d_sampler_plan_execute_binned", "is3d_sample_binned", "is3d_sample_binned_multi",
            "is3d_sampler_plan_execute_fused", "is3d_sample_fused", "is3d_sample_fused_multi",
            "is3d_sampler_bin_list_device", "is3d_df_generate", "is3d_df_tables_write",
@@ -155,6 +155,19 @@ class DecayStats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class DecayMcInputs(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("first_particle", C.c_int64), ("lifetime", C.c_int32), ("device", C.c_int32)]
+
+
+class DecayMcStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ["n_primaries", "n_decays", "n_final", "n_stuck", "n_trials", "n_exhausted"]] + \
+               [(n, C.c_int32) for n in ["max_stack", "max_depth", "n_closed_channels", "reserved"]] + \
+               [(n, C.c_double) for n in ["ms_h2d", "ms_count", "ms_fill", "ms_d2h"]]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
 class SpacetimeBins(C.Structure):
@@ -1044,6 +1057,28 @@ def write_results_decays(results_dir, dimension, pT, phi, y, dN, n_species=None)
         n_species = d.size // (len(pT) * len(phi) * ny_eff)
     _check(L.is3d_write_results_decays(results_dir.encode(), int(dimension), int(n_species), len(pT), _p(pT), len(phi), _p(phi), len(yv),
                                        _p(yv), _p(d)))
+
+
+def decay_particles(table, chosen_mc_id, particles, seed=1, first_particle=0, lifetime=0, device=-1, capacity=None):
+    """is3d_decay_particles: a sampled list (PARTICLE_DTYPE, species indexing chosen_mc_id) decayed to stable particles by Monte Carlo on the
+    device.  Returns (out, origin, stats): out[k]["species"] indexes the TABLE (table["mc_id"] is the id list of write_particle_list_osc),
+    origin[k] is the primary's index in `particles`.  capacity = None sizes the buffers from a count-only first call."""
+    L = load()
+    ts, ch, _, keep = _decay_pack(table, chosen_mc_id, dict(pT=[1.0], phi=[0.0], y=[0.0]))
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    inp = DecayMcInputs(int(seed), int(first_particle), int(lifetime), int(device))
+    st, cnt = DecayMcStats(), C.c_int64(0)
+    L.is3d_decay_particles.argtypes = [C.POINTER(DecayTable), C.c_int32, C.POINTER(C.c_int64), C.POINTER(DecayMcInputs), C.c_int64, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(DecayMcStats)]
+    head = (C.byref(ts), len(ch), ch.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(inp), len(particles), particles.ctypes.data)
+    if capacity is None:
+        _check(L.is3d_decay_particles(*head, None, None, 0, C.byref(cnt), C.byref(st)))
+        capacity = int(cnt.value)
+    out = np.zeros(max(int(capacity), 1), dtype=PARTICLE_DTYPE)
+    origin = np.zeros(max(int(capacity), 1), dtype=np.int64)
+    _check(L.is3d_decay_particles(*head, out.ctypes.data, origin.ctypes.data, int(capacity), C.byref(cnt), C.byref(st)))
+    n = int(cnt.value)
+    return out[:n], origin[:n], st.as_dict()
 
 
 def shard_bounds(n_cells, rank, n_ranks):

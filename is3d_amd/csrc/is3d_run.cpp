@@ -31,6 +31,11 @@
 // feed-down (is3d_resonance_decays) runs on the spectrum on the first device of the run's list and results/dN_pTdpTdphidy_resonance_decays.dat
 // and dN_dpTdphidy_resonance_decays.dat are appended (emissionfunction.cpp:1689-1698); the embedding result keeps the thermal spectrum.
 // Operations 0 and 2 and hrg_eos = 3 (no decay data) refuse the key.
+// decay_sampled_hadrons = 1 (optional key, default 0): with operation = 2, test_sampler = 0 and hrg_eos = 1 or 2 (either sampler family)
+// results/particle_list_osc.dat is written as without it, then the list is decayed to stable particles by Monte Carlo (is3d_decay_particles:
+// the sampler's seed, lifetime = 0, the first device of the run's list) and results/particle_list_osc_decayed.dat written with the decay
+// table's ids; one line of stats is printed and the embedding result keeps the thermal list.  Every other combination refuses the key before
+// anything is written (do_resonance_decays = 1 stays refused with operation = 2: it names the smooth feed-down).
 // deltaf_dir = DIR (optional key, absent by default): the coefficient tables are read from DIR instead of deltaf_coefficients/vh/<eos>/ --
 // a directory written by `iS3D_amd --generate-df DIR` (is3d_main.cpp) for an edited list or another (T, mu_B) grid.
 // test_sampler_on_device = 1 (optional key, default 0): with operation = 2 and test_sampler = 1 the hadrons are sampled ONCE and binned per event
@@ -239,6 +244,21 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
             if (hrg_eos == 3)
                 DIE("do_resonance_decays = 1 with hrg_eos = 3: PDG/pdg_box.dat carries no decay data (smash box: no decay info, iS3D_parameters.dat); use hrg_eos = 1 or 2");
             do_decays = true;
+        }
+    }
+    // optional key decay_sampled_hadrons = 1: the sampled list decayed to stable particles on the device (is3d_decay_particles)
+    bool decay_sampled = false;
+    {
+        double key = 0.0, test_sampler = 0.0;
+        if (get_param("decay_sampled_hadrons", &key, false) == IS3D_OK && (int)key) {
+            if (operation != 2)
+                DIE("decay_sampled_hadrons = 1 with operation = %d: it decays the sampler's particle list (operation = 2); set decay_sampled_hadrons = 0", operation);
+            if (hrg_eos != 1 && hrg_eos != 2)
+                DIE("decay_sampled_hadrons = 1 with hrg_eos = %d: PDG/pdg_box.dat carries no decay data (smash box: no decay info, iS3D_parameters.dat); use hrg_eos = 1 or 2", hrg_eos);
+            if (get_param("test_sampler", &test_sampler)) return IS3D_EINVAL;
+            if ((int)test_sampler)
+                DIE("decay_sampled_hadrons = 1 with test_sampler = 1: that run bins the thermal hadrons and writes no particle list to decay; set decay_sampled_hadrons = 0");
+            decay_sampled = true;
         }
     }
     bool bin_on_device = false;
@@ -700,6 +720,33 @@ static int run_impl(const is3d_cells *mem, const double *mem_x, const double *me
         } else {
             printf("Writing sampled particles list to OSCAR File...\n");
             if (is3d_write_particle_list_osc("results/particle_list_osc.dat", si.n_events, count, plist.data(), mcid.data())) DIE("%s", is3d_last_error());
+        }
+        if (decay_sampled) {
+            // the thermal list decayed to stable particles, on the first device of the run's list; its species index the decay table
+            printf("Decaying the sampled hadrons to stable particles...\n");
+            int32_t nd = 0, nc = 0;
+            if (is3d_pdg_read_decays(pdg_path, &nd, &nc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0)) DIE("%s", is3d_last_error());
+            std::vector<int64_t> did((size_t)nd), dau((size_t)nc * 5);
+            std::vector<double> dm((size_t)nd), dw((size_t)nd), dbr((size_t)nc);
+            std::vector<int32_t> dst((size_t)nd), dnc((size_t)nd), dnp((size_t)nc);
+            if (is3d_pdg_read_decays(pdg_path, &nd, &nc, did.data(), dm.data(), dw.data(), dst.data(), dnc.data(), dnp.data(), dbr.data(), dau.data(), nd, nc))
+                DIE("%s", is3d_last_error());
+            const is3d_decay_table tab{nd, did.data(), dm.data(), dw.data(), dst.data(), dnc.data(), dnp.data(), dbr.data(), dau.data()};
+            const is3d_decay_mc_inputs mi{si.seed, 0, 0, rd.list.empty() ? -1 : rd.list[0]};
+            is3d_decay_mc_stats ms{};
+            int64_t n_final = 0;
+            const double t4 = now_s();
+            int rcd = is3d_decay_particles(&tab, sp.n, mcid.data(), &mi, count, plist.data(), nullptr, nullptr, 0, &n_final, &ms);
+            std::vector<is3d_particle> decayed((size_t)std::max<int64_t>(n_final, 1));
+            if (!rcd) rcd = is3d_decay_particles(&tab, sp.n, mcid.data(), &mi, count, plist.data(), decayed.data(), nullptr, n_final, &n_final, &ms);
+            if (rcd) {
+                const std::string msg = is3d_last_error();
+                DIE("is3d_decay_particles failed (%d): %s", rcd, msg.c_str());
+            }
+            if (is3d_write_particle_list_osc("results/particle_list_osc_decayed.dat", si.n_events, n_final, decayed.data(), did.data())) DIE("%s", is3d_last_error());
+            printf("decays: %lld primaries, %lld decays, %lld final particles (%lld without an open channel), %lld phase-space proposals (%lld exhausted); "
+                   "device time: count %.3f ms, fill %.3f ms; wall %.3f s\n", (long long)ms.n_primaries, (long long)ms.n_decays, (long long)ms.n_final,
+                   (long long)ms.n_stuck, (long long)ms.n_trials, (long long)ms.n_exhausted, ms.ms_count, ms.ms_fill, now_s() - t4);
         }
         double t3s = now_s();
         printf("particles: %lld in %d event(s); hadrons drawn %lld; cells skipped (u.dsigma <= 0): %lld\n", (long long)count, si.n_events,
