@@ -1,7 +1,14 @@
 // errors.h -- one thread-local error string behind is3d_last_error() (include/is3d_amd.h).
 #pragma once
+#include <string>
+#include <utility>
+#include <vector>
 namespace is3d {
 int set_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+// The one parser of a parameter file (host_io.cpp), by ParameterReader's line rules: everything from '#' dropped, blanks and tabs removed, the
+// line split at its first '=', the name lower-cased.  The (name, right-hand side) pairs come in file order -- a later one overwrites an earlier
+// one for whoever looks a name up.  is3d_param_get and the run driver's RunParams are built on it; a line without '=' fails the whole file.
+int param_pairs(const char *path, std::vector<std::pair<std::string, std::string>> &pairs);
 // Create the HIP contexts of the listed devices (all visible ones for n == 0) ahead of their first use: the run driver calls it on
 // a thread of its own while it parses the surface file (a cold context costs a quarter of a second).  Errors are left to the real calls.
 void warm_devices(const int *devices, int n);

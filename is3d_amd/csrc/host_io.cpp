@@ -91,13 +91,11 @@ extern "C" const char *is3d_last_error(void) { return is3d::g_last_error.c_str()
 //   per line: drop everything from '#', remove all blanks/tabs, split at the first '=',
 //   name lower-cased, value = leading double of the right-hand side; later lines overwrite.
 // ---------------------------------------------------------------------------------------------
-extern "C" int is3d_param_get(const char *path, const char *name, double *value)
+int is3d::param_pairs(const char *path, std::vector<std::pair<std::string, std::string>> &pairs)
 {
-    if (!path || !name || !value) return io_fail(IS3D_EINVAL, "null argument");
     std::string text;
     if (!slurp(path, text)) return io_fail(IS3D_EIO, "parameter file %s does not exist", path);
-    const std::string want = lower(strip_blanks(name));
-    bool found = false;
+    pairs.clear();
     size_t pos = 0;
     while (pos <= text.size()) {
         size_t nl = text.find('\n', pos);
@@ -109,13 +107,23 @@ extern "C" int is3d_param_get(const char *path, const char *name, double *value)
         size_t eq = line.find('=');
         if (eq == std::string::npos)
             return io_fail(IS3D_EINVAL, "%s: \"=\" symbol not found in assignment \"%s\"", path, line.c_str());
-        std::string lhs = lower(strip_blanks(line.substr(0, eq)));
-        std::string rhs = strip_blanks(line.substr(eq + 1));
-        if (lhs == want) {
-            *value = strtod(rhs.c_str(), nullptr);
+        pairs.emplace_back(lower(strip_blanks(line.substr(0, eq))), strip_blanks(line.substr(eq + 1)));
+    }
+    return IS3D_OK;
+}
+
+extern "C" int is3d_param_get(const char *path, const char *name, double *value)
+{
+    if (!path || !name || !value) return io_fail(IS3D_EINVAL, "null argument");
+    std::vector<std::pair<std::string, std::string>> pairs;
+    if (int rc = is3d::param_pairs(path, pairs)) return rc;
+    const std::string want = lower(strip_blanks(name));
+    bool found = false;
+    for (const auto &p : pairs)
+        if (p.first == want) {
+            *value = strtod(p.second.c_str(), nullptr);
             found = true;
         }
-    }
     if (!found) return io_fail(IS3D_EINVAL, "parameter with name %s not found in %s", name, path);
     return IS3D_OK;
 }

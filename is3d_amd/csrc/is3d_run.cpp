@@ -1,86 +1,25 @@
-// is3d_run.cpp -- IS3D::run_particlization (/root/reference/src/cpp/iS3D.cpp:74-192) behind the C ABI: the driver layer
-// shared by the command line tool (is3d_main.cpp) and the embedding class (include/iS3D_amd.hpp).
-//
-// Runs in a directory laid out like the reference's run directory; it reads the same hard-coded
-// CWD-relative files IS3D::run_particlization reads (/root/reference/src/cpp/iS3D.cpp:74-192):
-//   iS3D_parameters.dat, input/surface.dat, PDG/pdg-urqmd_v3.3+.dat | PDG/pdg_smash.dat,
-//   PDG/chosen_particles.dat, deltaf_coefficients/vh/<eos>/{c0,c2,F,betabulk,betapi}.dat,
-//   tables/pT_gauss_legendre_table.dat, tables/phi_gauss_legendre_table.dat,
-//   tables/y_trapezoid_table_21pt.dat, tables/eta/eta_trapezoid_table_241pt.dat
-// and writes what EmissionFunctionArray::calculate_spectra writes for operation = 1
-// (emissionfunction.cpp:1678-1686) into results/ (which must exist, README.md:34) plus
-// average_thermodynamic_quantities.dat (readindata.cpp:464-466).
-// operation = 2 (particle sampler; df_mode 1-4, fast in {0, 1}, include_baryon = 1 with df_mode 1-3) writes
-// results/particle_list_osc.dat (write_particle_list_OSC, emissionfunction.cpp:863-901) and results/dN_dy_*.dat is skipped.
-// mode = 2 (anisotropic hydro, P_L matching; BASELINE config 5): operation = 1 (or 0, below) with df_mode = 4 -- the combination for which the
-// reference allocates the per-cell c0..c4 (emissionfunction.cpp:1397-1418) and the CUDA tree loads the VAH tables
-// (src/cuda/deltafReader.cu:74-81) -- reads input/surface.dat with read_surf_VAH_PLMatch and deltaf_coefficients/vah/c{0..4}_vah1.dat,
-// runs what the commented-out call site would (emissionfunction.cpp:1650-1654) and writes the same three result files.  With a device list
-// that was spelled out (the list of is3d_run_particlization_on, --devices, IS3D_DEVICES) the cells are sharded over it
-// (is3d_smooth_spectra_vah_multi, the run's reduce); without one, or with a bare device count, the first device computes alone -- the rule of
-// mode 5 below -- so that a mode-2 run does not depend on how many devices a machine shows.
-// operation = 0 (smooth spacetime distributions, calculate_dN_dX; emissionfunction.cpp:1510-1516): mode in {0, 1, 4, 5, 6, 7}, df_mode in
-// {1, 2}, include_baryon in {0, 1}, dimension 2 or 3, the per-cell stage sharded over the run's device list and one bin stage on its first
-// device (is3d_spacetime_distributions_multi); reads tau_min ... r_bins (:216-222), writes
-// results/spacetime_distribution/{dN_taudtaudy, dN_twopirdrdy, dN_twopitaurdtaudrdy}_<id>.dat and dN_dydeta_<id>_<n>pt.dat (the directory must
-// exist) and prints one "dN_dy = %lf" line per species; no momentum-spectra file (those are written for operation = 1 only, :1678).  df_mode 3 / 4
-// (calculate_dN_dX_feqmod) with those modes is refused before anything is written.  mode = 2 with df_mode = 4 runs the anisotropic-hydro form
-// (is3d_spacetime_distributions_vah; the reference has none): the same parameters, files and lines from the mode-2 surface and the
-// deltaf_coefficients/vah tables, on the first device of the run's list.
-// do_resonance_decays = 1 (optional key): with operation = 1 and hrg_eos = 1 or 2, the thermal files are written as without it, then the
-// feed-down (is3d_resonance_decays) runs on the spectrum on the first device of the run's list and results/dN_pTdpTdphidy_resonance_decays.dat
-// and dN_dpTdphidy_resonance_decays.dat are appended (emissionfunction.cpp:1689-1698); the embedding result keeps the thermal spectrum.
-// Operations 0 and 2 and hrg_eos = 3 (no decay data) refuse the key.
-// decay_sampled_hadrons = 1 (optional key, default 0): with operation = 2, test_sampler = 0 and hrg_eos = 1 or 2 (either sampler family)
-// results/particle_list_osc.dat is written as without it, then the list is decayed to stable particles by Monte Carlo (is3d_decay_particles:
-// the sampler's seed, lifetime = 0, the first device of the run's list) and results/particle_list_osc_decayed.dat written with the decay
-// table's ids; one line of stats is printed and the embedding result keeps the thermal list.  Every other combination refuses the key before
-// anything is written (do_resonance_decays = 1 stays refused with operation = 2: it names the smooth feed-down).
-// deltaf_dir = DIR (optional key, absent by default): the coefficient tables are read from DIR instead of deltaf_coefficients/vh/<eos>/ --
-// a directory written by `iS3D_amd --generate-df DIR` (is3d_main.cpp) for an edited list or another (T, mu_B) grid.
-// test_sampler_on_device = 1 (optional key, default 0): with operation = 2 and test_sampler = 1 the hadrons are sampled ONCE and binned per event
-// batch on the device (is3d_sample_binned_multi), never held as a list; the same files are written from the integer histograms
-// (is3d_write_sampler_tests_binned; vn/ to the fixed point) and the same lines printed, plus ms_bin.  test_sampler = 0, other operations and
-// the embedding entry (which returns the list) refuse the key.
-// test_sampler_fused = 1 (optional key, default 0): with operation = 2, test_sampler = 1 and a viscous mode every hadron is binned where it is
-// sampled (is3d_sample_fused; is3d_sample_fused_multi over a device list that was spelled out) -- one pass per event batch, no list and no
-// particle workspace.  The files of the test_sampler_on_device = 1 run are written (is3d_write_sampler_tests_binned, the same mean_yield) and
-// its lines printed, plus ms_bin; test_sampler_on_device may be 0 or 1 beside it, and oversample = 1 works.  Other operations,
-// test_sampler = 0, mode = 2 (it has vah_sampler_on_device) and the embedding entry refuse the key before anything is written.
-// vah_oversample = 1 (optional key, default 0): with mode = 2, operation = 2, df_mode = 4 and vah_sampler = 1 the anisotropic-hydro mean yield
-// (is3d_total_yield_vah: first device of the run's list, the file's y_cut, the deltaf_coefficients/vah tables, the sampler's Gauss-Laguerre file)
-// is printed as the viscous path prints its own and sizes the run, Nevents = is3d_oversample_events(min_num_hadrons, yield, max_num_samples); a
-// yield <= 0 (the linear delta-f of a large residual bulk pressure) stops the run before anything is written.  Every other combination refuses
-// the key; oversample = 1 stays refused with mode = 2.
-// vah_sampler_on_device = 1 (optional key, default 0): with mode = 2, operation = 2, df_mode = 4, vah_sampler = 1 and test_sampler = 1 the
-// anisotropic-hydro sampler's hadrons are sampled ONCE and binned where they are sampled (is3d_sample_binned_vah; is3d_sample_binned_vah_multi over
-// a device list that was spelled out), never held as a list: the files of the host-binned run are written from the integer histograms
-// (is3d_write_sampler_tests_binned, with the same mean_yield; vn/ to the fixed point), the same lines printed plus ms_bin, no particle list.  Works
-// together with vah_oversample = 1.  Every other combination and the embedding entry (which returns the list) refuse the key before anything is
-// written; test_sampler_on_device = 1 stays refused with mode = 2 (it names the viscous route).
-// mode = 5: every run, whatever its operation, ends with the spin polarization from the surface's thermal vorticity (calculate_spin_polzn,
-// emissionfunction.cpp:1675) and appends results/St.dat, Sx.dat, Sy.dat, Sn.dat (write_polzn_vector_toFile, :1701), with T from the averages
-// file just written or T_switch when set_FO_temperature = 1; the embedding entry has no vorticity and says so.  With a device list that was
-// spelled out (the list of is3d_run_particlization_on, --devices, IS3D_DEVICES) the cells are sharded over it (is3d_spin_polarization_multi:
-// one shard per entry, the class sums added in shard order on the first device); without one, or with a bare device count, the first device
-// computes alone, so that the S files do not depend on how many devices a machine shows.
-// Scope: operation in {0, 1, 2}, mode in {0, 1, 4, 5, 6, 7}, df_mode in {1, 2, 3} with include_baryon in {0, 1}, df_mode 4
-// (modified equilibrium; also reads tables/gla_roots_weights_32_points.txt, deta_min, mass_pion0 and the surface
-// averages it has just written, as the reference does) with include_baryon = 0.  Anything else is refused
-// with a message instead of silently doing something different from the reference.
+// is3d_run.cpp -- IS3D::run_particlization (src/cpp/iS3D.cpp:74-192 of the reference) behind the C ABI: the driver layer shared by the command
+// line tool (is3d_main.cpp) and the embedding class (include/iS3D_amd.hpp).  What every parameter and optional key selects, what is refused and
+// what each operation prints and writes: INTEGRATION.md, section 1 ("The driver's optional keys").  Runs in an iS3D run directory.
+// Reads: iS3D_parameters.dat; input/surface.dat (or its sidecar input/surface.dat.is3dcache); PDG/pdg-urqmd_v3.3+.dat | pdg_smash.dat | pdg_box.dat;
+//   PDG/chosen_particles.dat; tables/{pT,phi}_gauss_legendre_table.dat, tables/y_trapezoid_table_21pt.dat, tables/eta/eta_trapezoid_table_241pt.dat
+//   (operation 2: the 41pt one first); deltaf_coefficients/vh/<eos>/{c0..c4,F,G,betabulk,betaV,betapi}.dat, or those names under deltaf_dir;
+//   deltaf_coefficients/vah/c{0..4}_vah1.dat (mode 2); tables/gla_roots_weights_32_points.txt (df_mode 3 / 4, operation 2); its own averages file.
+// Writes: average_thermodynamic_quantities.dat (not in mode 2); input/surface.dat.is3dcache; in results/, which must exist -- operation 1:
+//   dN_pTdpTdphidy*.dat, dN_dpTdphidy.dat, dN_dy_*.dat, vn_continuous/vn_*.dat, *_resonance_decays.dat; operation 0: spacetime_distribution/*.dat;
+//   operation 2: particle_list_osc.dat, particle_list_osc_decayed.dat, or the binned test files (test_sampler = 1); mode 5: S{t,x,y,n}.dat.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <chrono>
 #include <fstream>
 #include <iomanip>
 #include <string>
 #include <thread>
 #include <vector>
-
-#include <cstdarg>
 
 #include "../../include/is3d_amd.h"
 #include "errors.h"
@@ -105,30 +44,44 @@ static int die(const char *fmt, ...)
 }
 #define DIE(...) return die(__VA_ARGS__)
 
-static int get_param(const char *name, double *v, bool required = true)
-{
-    int rc = is3d_param_get("iS3D_parameters.dat", name, v);
-    if (rc && required) fprintf(stderr, "iS3D-amd: %s\n", is3d_last_error());
-    return rc;
-}
-
-// an optional key whose value is text (deltaf_dir): the line rules of is3d_param_get -- '#' starts a comment, blanks and tabs are removed, the
-// name is lower-cased, later lines overwrite -- with the right-hand side taken verbatim.  False when the key is absent.
-static bool get_param_text(const char *name, std::string &value)
-{
-    std::ifstream f("iS3D_parameters.dat");
-    bool found = false;
-    for (std::string line; std::getline(f, line);) {
-        line = line.substr(0, line.find('#'));
-        line.erase(std::remove_if(line.begin(), line.end(), [](char c) { return c == ' ' || c == '\t' || c == '\r'; }), line.end());
-        const size_t eq = line.find('=');
-        if (eq == std::string::npos) continue;
-        std::string lhs = line.substr(0, eq);
-        for (char &c : lhs) c = (char)tolower((unsigned char)c);
-        if (lhs == name) { value = line.substr(eq + 1); found = true; }
+// The parameter file, read and parsed once (is3d::param_pairs: the line rules of is3d_param_get).  A later line overwrites an earlier one.
+class RunParams {
+public:
+    explicit RunParams(const char *path) : path_(path), rc_(is3d::param_pairs(path, pairs_)), error_(rc_ ? is3d_last_error() : "") {}
+    // a key the run cannot do without: is3d_param_get's message behind "iS3D-amd: " when it is absent or the file cannot be used
+    int required(const char *name, double *v) const
+    {
+        if (rc_) {
+            is3d::set_error(rc_, "%s", error_.c_str());
+            fprintf(stderr, "iS3D-amd: %s\n", error_.c_str());
+            return IS3D_EINVAL;
+        }
+        return optional(name, v) ? IS3D_OK : die("parameter with name %s not found in %s", name, path_.c_str());
     }
-    return found;
-}
+    // false, and *v untouched, when the key is absent; the value is strtod of the right-hand side
+    bool optional(const char *name, double *v) const
+    {
+        std::string rhs;
+        if (!text(name, &rhs)) return false;
+        *v = strtod(rhs.c_str(), nullptr);
+        return true;
+    }
+    // the right-hand side as text: blanks and tabs are gone already, '\r' goes here
+    bool text(const char *name, std::string *s) const
+    {
+        bool found = false;
+        for (const auto &p : pairs_)
+            if (p.first == name) { *s = p.second; found = true; }
+        s->erase(std::remove(s->begin(), s->end(), '\r'), s->end());
+        return found;
+    }
+
+private:
+    std::string path_;
+    std::vector<std::pair<std::string, std::string>> pairs_;
+    int rc_;
+    std::string error_;
+};
 
 static int read_table(const char *path, std::vector<double> &col1, std::vector<double> &col2)
 {
@@ -171,6 +124,9 @@ struct RunDevices {
     std::vector<int32_t> list;   // empty: all visible
     int32_t reduce = IS3D_REDUCE_ORDERED;
     bool named = false;          // the list was spelled out (the entry's list, --devices, IS3D_DEVICES), not a bare count of ordinals
+    const int32_t *data() const { return list.empty() ? nullptr : list.data(); }
+    int32_t size() const { return (int32_t)list.size(); }
+    int32_t first() const { return list.empty() ? -1 : list[0]; }
 };
 
 static int parse_run_devices(const int32_t *devices, int32_t n_devices, int32_t reduce, RunDevices &rd)
@@ -207,733 +163,776 @@ static int parse_run_devices(const int32_t *devices, int32_t n_devices, int32_t 
     return IS3D_OK;
 }
 
-static int run_impl(const is3d_cells *mem, const double *mem_x, const double *mem_y, int variant, const RunDevices &rd, is3d_run_result *res)
-{
-    printf("iS3D-amd: MI355X-native smooth Cooper-Frye spectra (%s)\n", is3d_version());
-    double v;
+// the embedding entry's surface: the caller's arrays, already in GeV / fm units, and the cells' positions (either may be NULL)
+struct MemSurface { const is3d_cells *cells; const double *x, *y; };
+
+// what iS3D_parameters.dat asks for, after every check that needs nothing but that file
+struct RunConfig {
     int operation, mode, hrg_eos, dimension, df_mode, include_baryon, include_bulk, include_shear, include_diff, regulate, outflow;
-#define GET(var, name)                           \
-    if (get_param(name, &v)) return IS3D_EINVAL; \
-    var = (int)v;
-    GET(operation, "operation");
-    GET(mode, "mode");
-    GET(hrg_eos, "hrg_eos");
-    GET(dimension, "dimension");
-    GET(df_mode, "df_mode");
-    GET(include_baryon, "include_baryon");
-    GET(include_bulk, "include_bulk_deltaf");
-    GET(include_shear, "include_shear_deltaf");
-    GET(include_diff, "include_baryondiff_deltaf");
-    GET(regulate, "regulate_deltaf");
-    GET(outflow, "outflow");
-#undef GET
+    // optional keys (absent: 0); an `is set` flag here has passed its checks
+    bool do_decays, decay_sampled, bin_on_device, bin_fused, vah_oversample, vah_bin_on_device, vah_sampler, test_sampler;
+    bool vah;               // mode 2 from files: the anisotropic-hydro surface, tables and routines
+    bool feqmod;            // df_mode 3 / 4 of viscous hydro: the modified-equilibrium kernels
+    const char *pdg_path;
+    std::string df_dir;     // with its trailing '/'
+};
+
+// Reads every key that decides whether the run is accepted and makes every refusal, in a fixed order: a file with two things wrong gets the
+// message of the earlier check.  Touches no device and writes no file (its one line on stdout names deltaf_dir).  mem: NULL for a run from files.
+static int parse_config(const RunParams &p, const MemSurface *mem, bool wants_result, RunConfig &c)
+{
+    double v = 0.0;
+    const struct { int *var; const char *name; } required[11] = {
+        {&c.operation, "operation"}, {&c.mode, "mode"}, {&c.hrg_eos, "hrg_eos"}, {&c.dimension, "dimension"}, {&c.df_mode, "df_mode"},
+        {&c.include_baryon, "include_baryon"}, {&c.include_bulk, "include_bulk_deltaf"}, {&c.include_shear, "include_shear_deltaf"},
+        {&c.include_diff, "include_baryondiff_deltaf"}, {&c.regulate, "regulate_deltaf"}, {&c.outflow, "outflow"}};
+    for (const auto &r : required) {
+        if (p.required(r.name, &v)) return IS3D_EINVAL;
+        *r.var = (int)v;
+    }
+    const auto is_set = [&p](const char *name) { double key = 0.0; return p.optional(name, &key) && (int)key != 0; };
+    c.do_decays = is_set("do_resonance_decays"); c.decay_sampled = is_set("decay_sampled_hadrons"); c.bin_on_device = is_set("test_sampler_on_device");
+    c.bin_fused = is_set("test_sampler_fused"); c.vah_sampler = is_set("vah_sampler"); c.vah_oversample = is_set("vah_oversample");
+    c.vah_bin_on_device = is_set("vah_sampler_on_device");
+    // test_sampler is a sampler key: optional where a check only looks at it, required (with the missing-key message) where a key depends on it
+    const bool has_test_sampler = p.optional("test_sampler", &v);
+    c.test_sampler = has_test_sampler && (int)v != 0;
+    const auto need_test_sampler = [&] { return has_test_sampler ? IS3D_OK : p.required("test_sampler", &v); };
+    const int operation = c.operation, mode = c.mode, df_mode = c.df_mode, hrg_eos = c.hrg_eos;
+    const bool vah = c.vah = !mem && mode == 2;
+    // operation: 0 smooth spacetime distributions, 1 smooth momentum spectra, 2 particle sampler
     if (operation != 0 && operation != 1 && operation != 2)
         DIE("operation = %d: operation = 0 (smooth spacetime distributions), 1 (smooth momentum spectra) and 2 (particle sampler) are on this path", operation);
     if (operation == 0) {
-        // mode = 2 (anisotropic hydro; df_mode = 4 is checked below) has its own routine, is3d_spacetime_distributions_vah
-        if ((df_mode == 3 || df_mode == 4) && !(!mem && mode == 2))
+        // df_mode 3 / 4 of viscous hydro (calculate_dN_dX_feqmod) is a library entry only; mode 2 with df_mode 4 has is3d_spacetime_distributions_vah
+        if ((df_mode == 3 || df_mode == 4) && !vah)
             DIE("operation = 0 with df_mode = %d (calculate_dN_dX_feqmod) is not run by this driver yet (the library entry is3d_spacetime_distributions_feqmod has it): set df_mode = 1 or 2", df_mode);
-        if (mem && (!mem_x || !mem_y)) DIE("operation = 0 needs the cells' x and y positions (NULL given)");
+        if (mem && (!mem->x || !mem->y)) DIE("operation = 0 needs the cells' x and y positions (NULL given)");
     }
-    bool do_decays = false;
-    {
-        double decays = 0.0;   // optional key here; the reference runs do_resonance_decays() after the spectra (emissionfunction.cpp:1689-1698)
-        if (get_param("do_resonance_decays", &decays, false) == IS3D_OK && (int)decays) {
-            if (operation != 1)
-                DIE("do_resonance_decays = 1 with operation = %d: the feed-down follows the momentum spectra (operation = 1) only; set do_resonance_decays = 0", operation);
-            if (hrg_eos == 3)
-                DIE("do_resonance_decays = 1 with hrg_eos = 3: PDG/pdg_box.dat carries no decay data (smash box: no decay info, iS3D_parameters.dat); use hrg_eos = 1 or 2");
-            do_decays = true;
-        }
+    // do_resonance_decays = 1: the feed-down runs after the momentum spectra (emissionfunction.cpp:1689-1698) and needs a list with decay data
+    if (c.do_decays) {
+        if (operation != 1)
+            DIE("do_resonance_decays = 1 with operation = %d: the feed-down follows the momentum spectra (operation = 1) only; set do_resonance_decays = 0", operation);
+        if (hrg_eos == 3)
+            DIE("do_resonance_decays = 1 with hrg_eos = 3: PDG/pdg_box.dat carries no decay data (smash box: no decay info, iS3D_parameters.dat); use hrg_eos = 1 or 2");
     }
-    // optional key decay_sampled_hadrons = 1: the sampled list decayed to stable particles on the device (is3d_decay_particles)
-    bool decay_sampled = false;
-    {
-        double key = 0.0, test_sampler = 0.0;
-        if (get_param("decay_sampled_hadrons", &key, false) == IS3D_OK && (int)key) {
-            if (operation != 2)
-                DIE("decay_sampled_hadrons = 1 with operation = %d: it decays the sampler's particle list (operation = 2); set decay_sampled_hadrons = 0", operation);
-            if (hrg_eos != 1 && hrg_eos != 2)
-                DIE("decay_sampled_hadrons = 1 with hrg_eos = %d: PDG/pdg_box.dat carries no decay data (smash box: no decay info, iS3D_parameters.dat); use hrg_eos = 1 or 2", hrg_eos);
-            if (get_param("test_sampler", &test_sampler)) return IS3D_EINVAL;
-            if ((int)test_sampler)
-                DIE("decay_sampled_hadrons = 1 with test_sampler = 1: that run bins the thermal hadrons and writes no particle list to decay; set decay_sampled_hadrons = 0");
-            decay_sampled = true;
-        }
+    // decay_sampled_hadrons = 1: the sampled list decayed to stable particles (is3d_decay_particles): operation 2 writing its list, hrg_eos 1 | 2
+    if (c.decay_sampled) {
+        if (operation != 2)
+            DIE("decay_sampled_hadrons = 1 with operation = %d: it decays the sampler's particle list (operation = 2); set decay_sampled_hadrons = 0", operation);
+        if (hrg_eos != 1 && hrg_eos != 2)
+            DIE("decay_sampled_hadrons = 1 with hrg_eos = %d: PDG/pdg_box.dat carries no decay data (smash box: no decay info, iS3D_parameters.dat); use hrg_eos = 1 or 2", hrg_eos);
+        if (need_test_sampler()) return IS3D_EINVAL;
+        if (c.test_sampler)
+            DIE("decay_sampled_hadrons = 1 with test_sampler = 1: that run bins the thermal hadrons and writes no particle list to decay; set decay_sampled_hadrons = 0");
     }
-    bool bin_on_device = false;
-    {
-        double on_device = 0.0, test_sampler = 0.0;   // optional key: the test_sampler = 1 distributions binned on the device, no particle list
-        if (get_param("test_sampler_on_device", &on_device, false) == IS3D_OK && (int)on_device) {
-            if (operation != 2)
-                DIE("test_sampler_on_device = 1 with operation = %d: it bins the sampler's hadrons (operation = 2); set test_sampler_on_device = 0", operation);
-            if (get_param("test_sampler", &test_sampler)) return IS3D_EINVAL;
-            if (!(int)test_sampler)
-                DIE("test_sampler_on_device = 1 with test_sampler = 0: the particle list is the output of that run and is not kept on this path; set test_sampler_on_device = 0");
-            if (res)
-                DIE("test_sampler_on_device = 1: the embedding entry returns the particle list, which this path never holds; set test_sampler_on_device = 0");
-            bin_on_device = true;
-        }
+    // test_sampler_on_device = 1: the test_sampler = 1 distributions binned on the device, no particle list -- so not for the embedding entry
+    if (c.bin_on_device) {
+        if (operation != 2)
+            DIE("test_sampler_on_device = 1 with operation = %d: it bins the sampler's hadrons (operation = 2); set test_sampler_on_device = 0", operation);
+        if (need_test_sampler()) return IS3D_EINVAL;
+        if (!c.test_sampler)
+            DIE("test_sampler_on_device = 1 with test_sampler = 0: the particle list is the output of that run and is not kept on this path; set test_sampler_on_device = 0");
+        if (wants_result)
+            DIE("test_sampler_on_device = 1: the embedding entry returns the particle list, which this path never holds; set test_sampler_on_device = 0");
     }
-    const bool vah = !mem && mode == 2;
-    // optional key test_sampler_fused = 1: the viscous sampler's hadrons binned where they are sampled (is3d_sample_fused), no particle list
-    bool bin_fused = false;
-    {
-        double key = 0.0, test_sampler = 0.0;
-        if (get_param("test_sampler_fused", &key, false) == IS3D_OK && (int)key) {
-            if (operation != 2)
-                DIE("test_sampler_fused = 1 with operation = %d: it bins the sampler's hadrons (operation = 2); set test_sampler_fused = 0", operation);
-            if (get_param("test_sampler", &test_sampler)) return IS3D_EINVAL;
-            if (!(int)test_sampler)
-                DIE("test_sampler_fused = 1 with test_sampler = 0: the particle list is the output of that run and is never held on this path; set test_sampler_fused = 0");
-            if (vah)
-                DIE("test_sampler_fused = 1 with mode = 2: it names the viscous-hydro sampler; the anisotropic-hydro one has vah_sampler_on_device; set test_sampler_fused = 0");
-            if (res)
-                DIE("test_sampler_fused = 1: the embedding entry returns the particle list, which this path never holds; set test_sampler_fused = 0");
-            bin_fused = true;
-        }
+    // test_sampler_fused = 1: the viscous sampler's hadrons binned where they are sampled (is3d_sample_fused), no particle list
+    if (c.bin_fused) {
+        if (operation != 2)
+            DIE("test_sampler_fused = 1 with operation = %d: it bins the sampler's hadrons (operation = 2); set test_sampler_fused = 0", operation);
+        if (need_test_sampler()) return IS3D_EINVAL;
+        if (!c.test_sampler)
+            DIE("test_sampler_fused = 1 with test_sampler = 0: the particle list is the output of that run and is never held on this path; set test_sampler_fused = 0");
+        if (vah)
+            DIE("test_sampler_fused = 1 with mode = 2: it names the viscous-hydro sampler; the anisotropic-hydro one has vah_sampler_on_device; set test_sampler_fused = 0");
+        if (wants_result)
+            DIE("test_sampler_fused = 1: the embedding entry returns the particle list, which this path never holds; set test_sampler_fused = 0");
     }
-    // optional key vah_oversample = 1: the anisotropic-hydro mean yield (is3d_total_yield_vah) sizes the run of this library's own VAH sampler
-    bool vah_oversample = false;
-    {
-        double key = 0.0, sampler = 0.0;
-        if (get_param("vah_oversample", &key, false) == IS3D_OK && (int)key) {
-            const bool own_sampler = get_param("vah_sampler", &sampler, false) == IS3D_OK && (int)sampler;
-            if (!(vah && operation == 2 && df_mode == 4 && own_sampler))
-                DIE("vah_oversample = 1 with mode = %d, operation = %d, df_mode = %d, vah_sampler = %d: the anisotropic-hydro mean yield sizes this library's own "
-                    "anisotropic-hydro sampler only (mode = 2, operation = 2, df_mode = 4, vah_sampler = 1); set vah_oversample = 0", mode, operation, df_mode,
-                    (int)own_sampler);
-            vah_oversample = true;
-        }
-    }
-    // optional key vah_sampler_on_device = 1: the VAH sampler's hadrons binned where they are sampled (is3d_sample_binned_vah), no particle list
-    bool vah_bin_on_device = false;
-    {
-        double key = 0.0, sampler = 0.0, test_sampler = 0.0;
-        if (get_param("vah_sampler_on_device", &key, false) == IS3D_OK && (int)key) {
-            const bool own_sampler = get_param("vah_sampler", &sampler, false) == IS3D_OK && (int)sampler;
-            const bool tests = get_param("test_sampler", &test_sampler, false) == IS3D_OK && (int)test_sampler;
-            if (!(vah && operation == 2 && df_mode == 4 && own_sampler && tests))
-                DIE("vah_sampler_on_device = 1 with mode = %d, operation = %d, df_mode = %d, vah_sampler = %d, test_sampler = %d: it bins the hadrons of this "
-                    "library's own anisotropic-hydro sampler on the device and keeps no particle list (mode = 2, operation = 2, df_mode = 4, vah_sampler = 1, "
-                    "test_sampler = 1; the viscous-hydro route has test_sampler_on_device); set vah_sampler_on_device = 0", mode, operation, df_mode,
-                    (int)own_sampler, (int)tests);
-            if (res)
-                DIE("vah_sampler_on_device = 1: the embedding entry returns the particle list, which this path never holds; set vah_sampler_on_device = 0");
-            vah_bin_on_device = true;
-        }
+    // vah_oversample = 1: the anisotropic-hydro mean yield (is3d_total_yield_vah) sizes the run of this library's own VAH sampler, and no other
+    if (c.vah_oversample && !(vah && operation == 2 && df_mode == 4 && c.vah_sampler))
+        DIE("vah_oversample = 1 with mode = %d, operation = %d, df_mode = %d, vah_sampler = %d: the anisotropic-hydro mean yield sizes this library's own "
+            "anisotropic-hydro sampler only (mode = 2, operation = 2, df_mode = 4, vah_sampler = 1); set vah_oversample = 0", mode, operation, df_mode,
+            (int)c.vah_sampler);
+    // vah_sampler_on_device = 1: the VAH sampler's hadrons binned where they are sampled (is3d_sample_binned_vah), no particle list
+    if (c.vah_bin_on_device) {
+        if (!(vah && operation == 2 && df_mode == 4 && c.vah_sampler && c.test_sampler))
+            DIE("vah_sampler_on_device = 1 with mode = %d, operation = %d, df_mode = %d, vah_sampler = %d, test_sampler = %d: it bins the hadrons of this "
+                "library's own anisotropic-hydro sampler on the device and keeps no particle list (mode = 2, operation = 2, df_mode = 4, vah_sampler = 1, "
+                "test_sampler = 1; the viscous-hydro route has test_sampler_on_device); set vah_sampler_on_device = 0", mode, operation, df_mode,
+                (int)c.vah_sampler, (int)c.test_sampler);
+        if (wants_result)
+            DIE("vah_sampler_on_device = 1: the embedding entry returns the particle list, which this path never holds; set vah_sampler_on_device = 0");
     }
     if (vah) {
         if (operation == 2) {
-            // optional key vah_sampler = 1: this library's own VAH sampler (is3d_sample_particles_vah; the reference has none)
-            double vah_sampler = 0.0, oversample = 0.0;
-            if (!(get_param("vah_sampler", &vah_sampler, false) == IS3D_OK && (int)vah_sampler))
+            // vah_sampler = 1 selects this library's own VAH sampler (is3d_sample_particles_vah; the reference has none); it has keys of its own
+            if (!c.vah_sampler)
                 DIE("mode = 2 (anisotropic hydro): operation = 0 or 1; the reference's VAH sampler is an empty stub (emissionfunction_sampling_kernels.cpp:1231-1239); "
                     "set vah_sampler = 1 for this library's own anisotropic-hydro sampler (is3d_sample_particles_vah)");
-            if (bin_on_device)
+            if (c.bin_on_device)
                 DIE("test_sampler_on_device = 1 with mode = 2: the anisotropic-hydro sampler's hadrons are binned on the host (test_sampler = 1); set test_sampler_on_device = 0");
-            if (get_param("oversample", &oversample)) return IS3D_EINVAL;
-            if ((int)oversample)
+            if (p.required("oversample", &v)) return IS3D_EINVAL;
+            if ((int)v)
                 DIE("oversample = 1 with mode = 2: the mean yield that sizes an oversampled run (calculate_total_yield) is viscous-hydro only; set oversample = 0 "
                     "(max_num_samples events are sampled), and vah_oversample = 1 for the anisotropic-hydro mean yield (is3d_total_yield_vah) to size the run");
         }
+        // the per-cell c0..c4 exist for df_mode 4 only
         if (df_mode != 4) DIE("mode = 2 (anisotropic hydro) needs df_mode = 4: the per-cell 14-moment coefficients c0..c4 exist for that combination only (emissionfunction.cpp:1410-1418)");
     }
+    // mode: a surface format with a reader here (the embedding entry brings its own cells)
     if (!mem && !vah && mode != 0 && mode != 1 && mode != 4 && mode != 5 && mode != 6 && mode != 7)
         DIE("mode = %d: the smooth path reads the viscous-hydro surface formats 0, 1, 4, 5, 6, 7 and the anisotropic-hydro format 2 (3 = VAH P_L, P_T matching has no kernel in the reference: emissionfunction.cpp:1328-1681)", mode);
     if (df_mode < 1 || df_mode > 4) DIE("df_mode = %d: 1 (14-moment), 2 (Chapman-Enskog), 3 (modified equilibrium, Mike), 4 (Jonah)", df_mode);
-    const bool feqmod = !vah && (df_mode == 3 || df_mode == 4);
-    if (df_mode == 4 && include_baryon && !vah)   // deltafReader.cpp:470-474
+    c.feqmod = !vah && (df_mode == 3 || df_mode == 4);
+    if (df_mode == 4 && c.include_baryon && !vah)   // deltafReader.cpp:470-474
         DIE("Bilinear interpolation error: Jonah df doesn't work for nonzero muB (df_mode = 4 with include_baryon = 1)");
-    const char *pdg_path, *df_dir;
-    if (hrg_eos == 1) { pdg_path = "PDG/pdg-urqmd_v3.3+.dat"; df_dir = "deltaf_coefficients/vh/urqmd/"; }
-    else if (hrg_eos == 2) { pdg_path = "PDG/pdg_smash.dat"; df_dir = "deltaf_coefficients/vh/smash/"; }
-    else if (hrg_eos == 3) { pdg_path = "PDG/pdg_box.dat"; df_dir = "deltaf_coefficients/vh/smash_box/"; }   // readindata.h:219, deltafReader.h:29
+    // hrg_eos: the particle list and its coefficient directory (readindata.h:219, deltafReader.h:29)
+    if (hrg_eos == 1) { c.pdg_path = "PDG/pdg-urqmd_v3.3+.dat"; c.df_dir = "deltaf_coefficients/vh/urqmd/"; }
+    else if (hrg_eos == 2) { c.pdg_path = "PDG/pdg_smash.dat"; c.df_dir = "deltaf_coefficients/vh/smash/"; }
+    else if (hrg_eos == 3) { c.pdg_path = "PDG/pdg_box.dat"; c.df_dir = "deltaf_coefficients/vh/smash_box/"; }
     else DIE("hrg_eos = %d: please choose hrg_eos = (1,2,3)", hrg_eos);
-    // optional key deltaf_dir: the coefficient tables come from that directory (one written by `iS3D_amd --generate-df DIR`, say) instead
-    std::string df_dir_key;
-    if (get_param_text("deltaf_dir", df_dir_key)) {
-        if (df_dir_key.empty()) DIE("deltaf_dir is empty: name the directory that holds c0.dat ... betapi.dat, or remove the key");
-        if (df_dir_key.back() != '/') df_dir_key += '/';
-        df_dir = df_dir_key.c_str();
-        printf("df coefficient tables from %s (deltaf_dir)\n", df_dir);
+    // deltaf_dir: the coefficient tables come from that directory (one written by `iS3D_amd --generate-df DIR`, say) instead
+    std::string dir;
+    if (p.text("deltaf_dir", &dir)) {
+        if (dir.empty()) DIE("deltaf_dir is empty: name the directory that holds c0.dat ... betapi.dat, or remove the key");
+        if (dir.back() != '/') dir += '/';
+        c.df_dir = dir;
+        printf("df coefficient tables from %s (deltaf_dir)\n", c.df_dir.c_str());
     }
+    return IS3D_OK;
+}
 
-    double t0 = now_s();
-    // the device contexts are created while the surface is being parsed (joined before the first device call)
-    std::vector<int> warm_list(rd.list.begin(), rd.list.end());
-    std::thread warm([&warm_list] { is3d::warm_devices(warm_list.empty() ? nullptr : warm_list.data(), (int)warm_list.size()); });
-    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } warm_joiner{warm};
-    // ---- surface (iS3D.cpp:90-98) ----
+// Everything the run reads before it computes.  The structs the library takes point into the vectors and into the surface, which is the
+// library's (is3d_surface_open) until this object goes: it is neither copied nor moved.
+struct RunInputs {
+    RunInputs() = default;
+    RunInputs(const RunInputs &) = delete;
+    ~RunInputs() { if (surf) is3d_surface_close(surf); }
+    is3d_surface *surf = nullptr;              // NULL for the embedding entry's surface
+    bool from_memory = false;
     int64_t n_cells = 0;
-    double *ptr[23] = {nullptr};
-    double avg[5] = {0, 0, 0, 0, 0};
-    // the text surface: one read + one parse, or the binary sidecar input/surface.dat.is3dcache of an earlier run on the same file
-    // (is3d_surface_open; IS3D_NO_CACHE=1 disables); the arrays are the library's until the end of this function
-    is3d_surface *surf = nullptr;
-    struct SurfCloser { is3d_surface *&s; ~SurfCloser() { if (s) is3d_surface_close(s); } } surf_closer{surf};
-    const double *sa[32] = {nullptr};     // modes 0-7 except 2: cell_arrays23 + x, y; mode 2: arrays32
-    if (vah) {
-        if (is3d_surface_open("input/surface.dat", 2, 0, 0, dimension, 1, &surf)) DIE("%s", is3d_last_error());
-        n_cells = is3d_surface_cells(surf);
-        if (is3d_surface_arrays(surf, sa, 32, nullptr)) DIE("%s", is3d_last_error());
-        if (is3d_surface_from_sidecar(surf))
-            printf("surface: %lld cells from the binary sidecar input/surface.dat.is3dcache (IS3D_NO_CACHE=1 to re-parse the text)\n", (long long)n_cells);
-    } else if (mem) {
+    const double *x = nullptr, *y = nullptr;   // the cells' positions: with the surface file, or the caller's (which may be NULL)
+    is3d_cells cells{};                        // viscous hydro
+    is3d_vah_cells vc{};                       // mode 2
+    std::vector<int64_t> pdg_id, mcid;         // the whole particle list (the modified equilibrium needs it), then the chosen species
+    std::vector<double> pdg_mass, pdg_g, pdg_b, pdg_s, mass, sign, deg, bar;
+    std::vector<double> pT, pTw, phi, phiw, yv, yw, eta, etaw;
+    std::vector<double> Tk, Bk, tab[10], vah_L, vah_aL, vah_c;
+    is3d_species sp{};
+    is3d_grid grid{};
+    is3d_df_tables df{};
+    is3d_vah_df_tables vt{};
+    is3d_options opts{};
+    double t_start = 0.0, t_loaded = 0.0;      // wall clock around the reads
+};
+
+// ---- surface (iS3D.cpp:90-134): the text file (one read + one parse) or its binary sidecar of an earlier run, or the caller's vectors ----
+static int load_surface(const RunConfig &cfg, const MemSurface *mem, RunInputs &in, double avg[5])
+{
+    if (mem) {
         // iS3D.cpp:100-134: the surface comes from the caller's vectors, already in GeV / fm units (no hbar*c conversion)
         printf("Reading in freezeout surface from memory \n");
-        n_cells = mem->n_cells;
-        const double *src[23] = {mem->T, mem->P, mem->E, mem->tau, mem->eta, mem->ux, mem->uy, mem->un, mem->dat, mem->dax, mem->day, mem->dan,
-                                 mem->pixx, mem->pixy, mem->pixn, mem->piyy, mem->piyn, mem->bulkPi, mem->muB, mem->nB, mem->Vx, mem->Vy, mem->Vn};
-        for (int a = 0; a < 23; a++) ptr[a] = const_cast<double *>(src[a]);
+        in.from_memory = true;
+        in.cells = *mem->cells;
+        in.n_cells = in.cells.n_cells;
+        in.x = mem->x; in.y = mem->y;
+        const is3d_cells &m = in.cells;
+        const double *need[18] = {m.T, m.P, m.E, m.tau, m.eta, m.ux, m.uy, m.un, m.dat, m.dax, m.day, m.dan, m.pixx, m.pixy, m.pixn, m.piyy, m.piyn, m.bulkPi};
         for (int a = 0; a < 18; a++)
-            if (!ptr[a] && !(a == 4 && dimension == 2)) DIE("in-memory surface: a required array is NULL");
-        if (n_cells > 0) surface_averages(mem, avg);
+            if (!need[a] && !(a == 4 && cfg.dimension == 2)) DIE("in-memory surface: a required array is NULL");
+        if (in.n_cells > 0) surface_averages(&in.cells, avg);
     } else {
-        if (is3d_surface_open("input/surface.dat", mode, include_baryon, include_diff, dimension, 1, &surf)) DIE("%s", is3d_last_error());
-        n_cells = is3d_surface_cells(surf);
-        if (is3d_surface_arrays(surf, sa, 25, avg)) DIE("%s", is3d_last_error());
+        // modes 0-7 except 2: the 23 cell arrays, x, y and the averages; mode 2: is3d_surface_read_vah's 32 arrays, x and y last, no averages
+        const double *sa[32] = {nullptr};
+        const int n_arrays = cfg.vah ? 32 : 25;
+        if (is3d_surface_open("input/surface.dat", cfg.vah ? 2 : cfg.mode, cfg.vah ? 0 : cfg.include_baryon, cfg.vah ? 0 : cfg.include_diff, cfg.dimension, 1, &in.surf))
+            DIE("%s", is3d_last_error());
+        in.n_cells = is3d_surface_cells(in.surf);
+        if (is3d_surface_arrays(in.surf, sa, n_arrays, cfg.vah ? nullptr : avg)) DIE("%s", is3d_last_error());
         // said BEFORE the spectra are computed: a user who did not expect the cache sees it while the run can still be stopped
-        if (is3d_surface_from_sidecar(surf))
-            printf("surface: %lld cells from the binary sidecar input/surface.dat.is3dcache (its key -- size, mtime, ctime, inode, content hash -- matches "
-                   "input/surface.dat; IS3D_NO_CACHE=1 to re-parse the text)\n", (long long)n_cells);
-        for (int a = 0; a < 23; a++) ptr[a] = const_cast<double *>(sa[a]);   // read-only from here on
+        if (is3d_surface_from_sidecar(in.surf))
+            printf("surface: %lld cells from the binary sidecar input/surface.dat.is3dcache (%sIS3D_NO_CACHE=1 to re-parse the text)\n", (long long)in.n_cells,
+                   cfg.vah ? "" : "its key -- size, mtime, ctime, inode, content hash -- matches input/surface.dat; ");
+        is3d_cells &c = in.cells;
+        is3d_vah_cells &v = in.vc;   // both in the order of is3d_surface_arrays
+        const double **cf[23] = {&c.T, &c.P, &c.E, &c.tau, &c.eta, &c.ux, &c.uy, &c.un, &c.dat, &c.dax, &c.day, &c.dan, &c.pixx, &c.pixy, &c.pixn, &c.piyy,
+                                 &c.piyn, &c.bulkPi, &c.muB, &c.nB, &c.Vx, &c.Vy, &c.Vn};
+        const double **vf[25] = {&v.tau, &v.eta, &v.ux, &v.uy, &v.un, &v.dat, &v.dax, &v.day, &v.dan, &v.T, &v.pitt, &v.pitx, &v.pity, &v.pitn, &v.pixx, &v.pixy,
+                                 &v.pixn, &v.piyy, &v.piyn, &v.pinn, &v.bulkPi, &v.Wx, &v.Wy, &v.Lambda, &v.aL};
+        for (int a = 0; a < (cfg.vah ? 25 : 23); a++) *(cfg.vah ? vf[a] : cf[a]) = sa[a];
+        in.x = sa[n_arrays - 2]; in.y = sa[n_arrays - 1];
     }
-    if (!vah) {   // read_surf_VAH_PLMatch accumulates no averages (readindata.cpp:813-928)
+    in.cells.n_cells = in.vc.n_cells = in.n_cells;
+    return IS3D_OK;
+}
+
+// The reads, and the one write (the surface's averages), of a run before it computes; the warm-up is joined once the viscous-hydro inputs are in.
+static int load_inputs(const RunConfig &cfg, const RunDevices &rd, int variant, const MemSurface *mem, std::thread &warm, RunInputs &in)
+{
+    double avg[5] = {0, 0, 0, 0, 0};
+    if (int rc = load_surface(cfg, mem, in, avg)) return rc;
+    if (!cfg.vah) {   // read_surf_VAH_PLMatch accumulates no averages (readindata.cpp:813-928)
         std::ofstream f("average_thermodynamic_quantities.dat", std::ios_base::out);
         f << std::setprecision(15) << avg[0] << "\n" << avg[1] << "\n" << avg[2] << "\n" << avg[3] << "\n" << avg[4];
     }
     // ---- species (iS3D.cpp:138-140, 156; emissionfunction.cpp:336-351, 1293-1307) ----
     int32_t npdg = 0;
-    const auto pdg_read = (hrg_eos == 3) ? is3d_pdg_read_box : is3d_pdg_read;   // read_resonances: conventional | smash box (readindata.cpp:1687-1713)
-    if (pdg_read(pdg_path, &npdg, nullptr, nullptr, nullptr, nullptr, nullptr, 0)) DIE("%s", is3d_last_error());
-    std::vector<int64_t> pid(npdg);
-    std::vector<double> pmass(npdg), pg(npdg), pb(npdg), ps(npdg);
-    if (pdg_read(pdg_path, &npdg, pid.data(), pmass.data(), pg.data(), pb.data(), ps.data(), npdg)) DIE("%s", is3d_last_error());
+    const auto pdg_read = (cfg.hrg_eos == 3) ? is3d_pdg_read_box : is3d_pdg_read;   // read_resonances: conventional | smash box (readindata.cpp:1687-1713)
+    if (pdg_read(cfg.pdg_path, &npdg, nullptr, nullptr, nullptr, nullptr, nullptr, 0)) DIE("%s", is3d_last_error());
+    in.pdg_id.resize(npdg); in.pdg_mass.resize(npdg); in.pdg_g.resize(npdg); in.pdg_b.resize(npdg); in.pdg_s.resize(npdg);
+    if (pdg_read(cfg.pdg_path, &npdg, in.pdg_id.data(), in.pdg_mass.data(), in.pdg_g.data(), in.pdg_b.data(), in.pdg_s.data(), npdg)) DIE("%s", is3d_last_error());
     std::vector<double> chosen, dummy;
     if (read_table("PDG/chosen_particles.dat", chosen, dummy)) DIE("%s", is3d_last_error());
-    std::vector<int64_t> mcid;
-    std::vector<double> mass, sign, deg, bar;
     for (double c : chosen) {
-        int id = (int)c;
-        bool found = false;
-        for (int n = 0; n < npdg; n++)
-            if (pid[n] == id) {
-                mcid.push_back(pid[n]); mass.push_back(pmass[n]); sign.push_back(ps[n]); deg.push_back(pg[n]); bar.push_back(pb[n]);
-                found = true;
-                break;
-            }
-        if (!found) DIE("chosen particle %d is not in %s", id, pdg_path);
+        const int id = (int)c;
+        const auto at = std::find(in.pdg_id.begin(), in.pdg_id.end(), (int64_t)id);
+        if (at == in.pdg_id.end()) DIE("chosen particle %d is not in %s", id, cfg.pdg_path);
+        const size_t n = (size_t)(at - in.pdg_id.begin());
+        in.mcid.push_back(in.pdg_id[n]); in.mass.push_back(in.pdg_mass[n]); in.sign.push_back(in.pdg_s[n]); in.deg.push_back(in.pdg_g[n]); in.bar.push_back(in.pdg_b[n]);
     }
     // ---- grids (iS3D.cpp:161-167) ----
-    std::vector<double> pT, pTw, phi, phiw, y, yw, eta, etaw;
-    if (read_table("tables/pT_gauss_legendre_table.dat", pT, pTw) || read_table("tables/phi_gauss_legendre_table.dat", phi, phiw) ||
-        read_table("tables/y_trapezoid_table_21pt.dat", y, yw))
+    if (read_table("tables/pT_gauss_legendre_table.dat", in.pT, in.pTw) || read_table("tables/phi_gauss_legendre_table.dat", in.phi, in.phiw) ||
+        read_table("tables/y_trapezoid_table_21pt.dat", in.yv, in.yw))
         DIE("%s", is3d_last_error());
     // the eta table: 241 points for the smooth spectra; the reference opens the 41-point one when it samples (iS3D.cpp:164-167) and never uses it
     // there (nor does the sampler here): a run directory made for either operation is accepted
-    if (operation == 2) {
+    if (cfg.operation == 2) {
         // neither there: the reference fails on its missing table (readBlockData, arsenal.cpp:406-413) -- a mis-built run directory must not pass silently
-        if (read_table("tables/eta/eta_trapezoid_table_41pt.dat", eta, etaw) && read_table("tables/eta/eta_trapezoid_table_241pt.dat", eta, etaw))
+        if (read_table("tables/eta/eta_trapezoid_table_41pt.dat", in.eta, in.etaw) && read_table("tables/eta/eta_trapezoid_table_241pt.dat", in.eta, in.etaw))
             DIE("operation 2 opens tables/eta/eta_trapezoid_table_41pt.dat (or tables/eta/eta_trapezoid_table_241pt.dat): neither can be read (%s)", is3d_last_error());
-    } else if (read_table("tables/eta/eta_trapezoid_table_241pt.dat", eta, etaw))
+    } else if (read_table("tables/eta/eta_trapezoid_table_241pt.dat", in.eta, in.etaw))
         DIE("%s", is3d_last_error());
-    // ---- delta-f coefficient tables (iS3D.cpp:144-145) ----
-    //      include_baryon = 0: the mu_B = 0 rows; include_baryon = 1: the full (mu_B, T) grids (deltafReader.cpp:134)
+    // ---- delta-f coefficient tables (iS3D.cpp:144-145): include_baryon = 0: the mu_B = 0 rows; 1: the full (mu_B, T) grids (deltafReader.cpp:134) ----
     const char *names[10] = {"c0.dat", "c1.dat", "c2.dat", "c3.dat", "c4.dat", "F.dat", "G.dat", "betabulk.dat", "betaV.dat", "betapi.dat"};
-    std::vector<double> Tk, Bk, tab[10];
-    for (int t = 0; t < 10 && !vah; t++) {
-        std::string p = std::string(df_dir) + names[t];
+    std::vector<double> &Tk = in.Tk, &Bk = in.Bk, *tab = in.tab;
+    for (int t = 0; t < 10 && !cfg.vah; t++) {
+        std::string p = cfg.df_dir + names[t];
         int32_t nT = 0, nB = 0;
         const bool spline_table = (t == 0 || t == 2 || t == 5 || t == 7 || t == 9);   // c0 c2 F betabulk betapi
-        if (!include_baryon && !spline_table) continue;   // only the bilinear branch looks at c1 c3 c4 G betaV
+        if (!cfg.include_baryon && !spline_table) continue;   // only the bilinear branch looks at c1 c3 c4 G betaV
         if (is3d_df_table_read_full(p.c_str(), &nT, &nB, nullptr, nullptr, nullptr, 0)) DIE("%s", is3d_last_error());
-        if (!include_baryon) {
-            Tk.resize(nT);
+        Tk.resize(nT);
+        if (!cfg.include_baryon) {
             Bk.assign(1, 0.0);
             tab[t].resize(nT);
             if (is3d_df_table_read(p.c_str(), &nT, Tk.data(), tab[t].data(), nT)) DIE("%s", is3d_last_error());
         } else {
-            Tk.resize(nT);
             Bk.resize(nB);
             tab[t].resize((size_t)nT * nB);
             if (is3d_df_table_read_full(p.c_str(), &nT, &nB, Tk.data(), Bk.data(), tab[t].data(), (int64_t)tab[t].size())) DIE("%s", is3d_last_error());
         }
     }
+    in.df = is3d_df_tables{(int32_t)Tk.size(), Tk.data(), (int32_t)Bk.size(), Bk.data(), tab[0].data(), tab[1].data(), tab[2].data(),
+                           tab[3].data(), tab[4].data(), tab[5].data(), tab[6].data(), tab[7].data(), tab[8].data(), tab[9].data()};
     if (warm.joinable()) warm.join();
-    double t1 = now_s();
-    printf("Total number of freezeout cells: %lld\nNumber of chosen particles: %zu\n", (long long)n_cells, mcid.size());
-
-    is3d_cells cells{};
-    cells.n_cells = n_cells;
-    cells.T = ptr[0]; cells.P = ptr[1]; cells.E = ptr[2]; cells.tau = ptr[3]; cells.eta = ptr[4];
-    cells.ux = ptr[5]; cells.uy = ptr[6]; cells.un = ptr[7];
-    cells.dat = ptr[8]; cells.dax = ptr[9]; cells.day = ptr[10]; cells.dan = ptr[11];
-    cells.pixx = ptr[12]; cells.pixy = ptr[13]; cells.pixn = ptr[14]; cells.piyy = ptr[15]; cells.piyn = ptr[16];
-    cells.bulkPi = ptr[17];
-    cells.muB = ptr[18]; cells.nB = ptr[19]; cells.Vx = ptr[20]; cells.Vy = ptr[21]; cells.Vn = ptr[22];
-    is3d_species sp{(int32_t)mcid.size(), mass.data(), sign.data(), deg.data(), bar.data()};
-    is3d_grid grid{(int32_t)pT.size(), pT.data(), (int32_t)phi.size(), phi.data(), (int32_t)y.size(), y.data(),
-                   (int32_t)eta.size(), eta.data(), etaw.data()};
-    is3d_df_tables df{(int32_t)Tk.size(), Tk.data(), (int32_t)Bk.size(), Bk.data(), tab[0].data(), tab[1].data(), tab[2].data(),
-                      tab[3].data(), tab[4].data(), tab[5].data(), tab[6].data(), tab[7].data(), tab[8].data(), tab[9].data()};
-    is3d_options opts{};
-    opts.dimension = dimension; opts.df_mode = df_mode; opts.include_baryon = include_baryon;
-    opts.include_bulk_deltaf = include_bulk; opts.include_shear_deltaf = include_shear; opts.include_baryondiff_deltaf = include_diff;
-    opts.regulate_deltaf = regulate; opts.outflow = outflow;
-    opts.accumulate = 0; opts.device = rd.list.empty() ? -1 : rd.list[0]; opts.kernel_variant = variant;
-    // ---- mode 5: every run ends with the spin polarization from the surface's thermal vorticity (emissionfunction.cpp:1675, :1701) ----
-    auto polarization = [&]() -> int {
-        if (mode != 5 || vah) return IS3D_OK;
-        if (mem) {
-            printf("mode = 5: the spin polarization needs the thermal vorticity, which only the file reader (input/surface.dat) provides; no S*.dat written\n");
-            return IS3D_OK;
-        }
-        // Plasma::temperature: the first line of the averages file this run wrote, or T_switch (emissionfunction.cpp:1318-1321)
-        double Tp = 0.0, set_T = 0.0;
-        {
-            FILE *tf = fopen("average_thermodynamic_quantities.dat", "r");
-            if (!tf || fscanf(tf, "%lf", &Tp) != 1) {
-                if (tf) fclose(tf);
-                DIE("Error opening average thermodynamic file");
-            }
-            fclose(tf);
-        }
-        if (get_param("set_fo_temperature", &set_T, false) == IS3D_OK && (int)set_T && get_param("t_switch", &Tp)) return IS3D_EINVAL;
-        const double *w[6];
-        if (is3d_surface_vorticity(surf, w)) DIE("%s", is3d_last_error());
-        is3d_vorticity vort{w[0], w[1], w[2], w[3], w[4], w[5]};
-        is3d_options po{};
-        po.dimension = dimension;
-        po.device = rd.list.empty() ? -1 : rd.list[0];
-        const size_t np = mcid.size() * pT.size() * phi.size() * (size_t)((dimension == 2) ? 1 : y.size());
-        std::vector<double> pS[5];
-        for (auto &v : pS) v.assign(np, 0.0);
-        is3d_polarization_out po_out{pS[0].data(), pS[1].data(), pS[2].data(), pS[3].data(), pS[4].data()};
-        is3d_polarization_stats pst{};
-        printf("Calculating spin polarization vector (T = %.6f GeV)...\n", Tp);
-        // a device list the user spelled out shards the cells like the run's other cell sums do.  Without one the first device computes alone:
-        // the sum's association depends on the shard count, and the S files (eight digits) must not depend on how many cards a machine shows
-        std::vector<is3d_polarization_stats> pss(rd.named ? rd.list.size() : 0);
-        const int rcp = rd.named ? is3d_spin_polarization_multi(&cells, &vort, &sp, &grid, Tp, &po, rd.list.data(), (int32_t)rd.list.size(), &po_out,
-                                                                &pst, pss.data())
-                                 : is3d_spin_polarization(&cells, &vort, &sp, &grid, Tp, &po, &po_out, &pst);
-        if (rcp) {
-            const std::string msg = is3d_last_error();
-            DIE("%s failed (%d): %s", rd.named ? "is3d_spin_polarization_multi" : "is3d_spin_polarization", rcp, msg.c_str());
-        }
-        printf("Writing polarization vector to file...\n");
-        if (is3d_write_polarization("results", dimension, sp.n, grid.n_pT, pT.data(), grid.n_phi, phi.data(), grid.n_y, y.data(), &po_out))
-            DIE("%s", is3d_last_error());
-        printf("polarization: species classes evaluated: %d of %d; device time: cells %.3f ms, reduce %.3f ms\n", pst.n_classes, sp.n,
-               pst.ms_cells, pst.ms_reduce);
-        if (rd.named) printf("polarization: %d shard%s; slowest shard's cells %.3f ms\n", (int)pss.size(), pss.size() == 1 ? "" : "s", pst.ms_cells);
-        return IS3D_OK;
-    };
-    // ---- mode 2: the surface's cell arrays and the deltaf_coefficients/vah tables (what src/cuda/deltafReader.cu:224-278 would have put into the surface) ----
-    std::vector<double> vah_L, vah_aL, vah_c;
-    is3d_vah_df_tables vt{};
-    is3d_vah_cells vc{};
-    if (vah) {
+    in.t_loaded = now_s();
+    printf("Total number of freezeout cells: %lld\nNumber of chosen particles: %zu\n", (long long)in.n_cells, in.mcid.size());
+    in.sp = is3d_species{(int32_t)in.mcid.size(), in.mass.data(), in.sign.data(), in.deg.data(), in.bar.data()};
+    in.grid = is3d_grid{(int32_t)in.pT.size(), in.pT.data(), (int32_t)in.phi.size(), in.phi.data(), (int32_t)in.yv.size(), in.yv.data(),
+                        (int32_t)in.eta.size(), in.eta.data(), in.etaw.data()};
+    is3d_options &o = in.opts;
+    o.dimension = cfg.dimension; o.df_mode = cfg.df_mode; o.include_baryon = cfg.include_baryon;
+    o.include_bulk_deltaf = cfg.include_bulk; o.include_shear_deltaf = cfg.include_shear; o.include_baryondiff_deltaf = cfg.include_diff;
+    o.regulate_deltaf = cfg.regulate; o.outflow = cfg.outflow;
+    o.accumulate = 0; o.device = rd.first(); o.kernel_variant = variant;
+    // ---- mode 2: the deltaf_coefficients/vah tables (what src/cuda/deltafReader.cu:224-278 would have put into the surface) ----
+    if (cfg.vah) {
         int32_t nL = 0, naL = 0;
         if (is3d_vah_df_read("deltaf_coefficients/vah", &nL, &naL, nullptr, nullptr, nullptr, 0)) DIE("%s", is3d_last_error());
-        vah_L.resize((size_t)nL); vah_aL.resize((size_t)naL); vah_c.resize((size_t)5 * nL * naL);
-        if (is3d_vah_df_read("deltaf_coefficients/vah", &nL, &naL, vah_L.data(), vah_aL.data(), vah_c.data(), (int64_t)vah_c.size())) DIE("%s", is3d_last_error());
+        in.vah_L.resize((size_t)nL); in.vah_aL.resize((size_t)naL); in.vah_c.resize((size_t)5 * nL * naL);
+        if (is3d_vah_df_read("deltaf_coefficients/vah", &nL, &naL, in.vah_L.data(), in.vah_aL.data(), in.vah_c.data(), (int64_t)in.vah_c.size())) DIE("%s", is3d_last_error());
         const size_t tn = (size_t)nL * naL;
-        vt = is3d_vah_df_tables{nL, naL, vah_L.data(), vah_aL.data(), vah_c.data(), vah_c.data() + tn, vah_c.data() + 2 * tn, vah_c.data() + 3 * tn,
-                                vah_c.data() + 4 * tn};
-        vc.n_cells = n_cells;
-        const double **vf[25] = {&vc.tau, &vc.eta, &vc.ux, &vc.uy, &vc.un, &vc.dat, &vc.dax, &vc.day, &vc.dan, &vc.T, &vc.pitt, &vc.pitx, &vc.pity,
-                                 &vc.pitn, &vc.pixx, &vc.pixy, &vc.pixn, &vc.piyy, &vc.piyn, &vc.pinn, &vc.bulkPi, &vc.Wx, &vc.Wy, &vc.Lambda, &vc.aL};
-        for (int a = 0; a < 25; a++) *vf[a] = sa[a];
+        const double *c = in.vah_c.data();
+        in.vt = is3d_vah_df_tables{nL, naL, in.vah_L.data(), in.vah_aL.data(), c, c + tn, c + 2 * tn, c + 3 * tn, c + 4 * tn};
     }
-    const int ny_eff = (dimension == 2) ? 1 : (int)y.size();
-    std::vector<double> dN(mcid.size() * pT.size() * phi.size() * (size_t)ny_eff, 0.0);
-    if (operation == 2) {
-        // ---- emissionfunction.cpp:1522-1545: number of events, sampling, OSCAR list ----
-        double oversample, min_num_hadrons, max_num_samples, sampler_seed, y_cut, fast, test_sampler, set_T, T_switch = 0.0;
-        if (get_param("oversample", &oversample) || get_param("min_num_hadrons", &min_num_hadrons) || get_param("max_num_samples", &max_num_samples) ||
-            get_param("sampler_seed", &sampler_seed) || get_param("y_cut", &y_cut) || get_param("fast", &fast) || get_param("test_sampler", &test_sampler) ||
-            get_param("set_fo_temperature", &set_T))
+    return IS3D_OK;
+}
+
+// tables/gla_roots_weights_32_points.txt: the Gauss-Laguerre nodes, one row of n_pts per alpha
+struct GaussLaguerre {
+    const char *path = "tables/gla_roots_weights_32_points.txt";
+    int32_t n_alpha = 0, n_pts = 0;
+    std::vector<double> root, weight;
+    const double *r(int alpha) const { return root.data() + (size_t)alpha * n_pts; }
+    const double *w(int alpha) const { return weight.data() + (size_t)alpha * n_pts; }
+};
+
+// reads the table and points fq's alpha = 1 and alpha = 2 rules at it (emissionfunction.cpp:1309-1312)
+static int read_gauss_laguerre(GaussLaguerre &g, is3d_feqmod_tables &fq)
+{
+    if (is3d_gla_read(g.path, &g.n_alpha, &g.n_pts, nullptr, nullptr, 0)) DIE("%s", is3d_last_error());
+    if (g.n_alpha < 3) DIE("%s: needs alpha = 0, 1, 2", g.path);
+    g.root.resize((size_t)g.n_alpha * g.n_pts); g.weight.resize(g.root.size());
+    if (is3d_gla_read(g.path, &g.n_alpha, &g.n_pts, g.root.data(), g.weight.data(), (int64_t)g.root.size())) DIE("%s", is3d_last_error());
+    fq.n_gla = g.n_pts;
+    fq.root1 = g.r(1); fq.weight1 = g.w(1); fq.root2 = g.r(2); fq.weight2 = g.w(2);
+    return IS3D_OK;
+}
+
+// Plasma::load_thermodynamic_averages: the first n numbers (T, E, P, muB, nB) of the averages file this run wrote, read back as text
+static int read_averages(int n, double *v)
+{
+    FILE *tf = fopen("average_thermodynamic_quantities.dat", "r");
+    int got = 0;
+    while (tf && got < n && fscanf(tf, "%lf", &v[got]) == 1) got++;
+    if (tf) fclose(tf);
+    if (got != n) DIE("Error opening average thermodynamic file");
+    return IS3D_OK;
+}
+
+// the rest of what the modified equilibrium takes: the whole particle list, deta_min, mass_pion0 and the surface's average temperature
+static int fill_feqmod(const RunInputs &in, const RunParams &params, double T_avg, is3d_feqmod_tables &fq)
+{
+    if (params.required("deta_min", &fq.deta_min) || params.required("mass_pion0", &fq.mass_pion0)) return IS3D_EINVAL;
+    fq.n_pdg = (int32_t)in.pdg_id.size(); fq.pdg_mass = in.pdg_mass.data(); fq.pdg_degeneracy = in.pdg_g.data(); fq.pdg_sign = in.pdg_s.data();
+    fq.T_avg = T_avg;
+    return IS3D_OK;
+}
+
+// the decay table of a particle list, owning its arrays
+struct DecayTable {
+    std::vector<int64_t> id, daughters;
+    std::vector<double> mass, width, branch_ratio;
+    std::vector<int32_t> stable, n_channels, n_part;
+    is3d_decay_table view{};
+};
+
+static int read_decay_table(const char *path, DecayTable &t)
+{
+    int32_t nd = 0, nc = 0;
+    if (is3d_pdg_read_decays(path, &nd, &nc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0)) DIE("%s", is3d_last_error());
+    t.id.resize((size_t)nd); t.daughters.resize((size_t)nc * 5); t.mass.resize((size_t)nd); t.width.resize((size_t)nd); t.branch_ratio.resize((size_t)nc);
+    t.stable.resize((size_t)nd); t.n_channels.resize((size_t)nd); t.n_part.resize((size_t)nc);
+    if (is3d_pdg_read_decays(path, &nd, &nc, t.id.data(), t.mass.data(), t.width.data(), t.stable.data(), t.n_channels.data(), t.n_part.data(),
+                             t.branch_ratio.data(), t.daughters.data(), nd, nc))
+        DIE("%s", is3d_last_error());
+    t.view = is3d_decay_table{nd, t.id.data(), t.mass.data(), t.width.data(), t.stable.data(), t.n_channels.data(), t.n_part.data(), t.branch_ratio.data(),
+                              t.daughters.data()};
+    return IS3D_OK;
+}
+
+// What goes back to the embedding caller (iS3D.cpp:178-184): the species, and the operation's own product -- the spectrum or the particle list.
+static int copy_result(is3d_run_result *res, int operation, const RunInputs &in, const std::vector<double> *spectrum, const is3d_particle *list, int64_t count)
+{
+    if (!res) return IS3D_OK;
+    const size_t S = (size_t)in.sp.n;
+    res->operation = operation; res->n_species = in.sp.n;
+    if (list) { res->n_particles = count; res->particles = (is3d_particle *)malloc(sizeof(is3d_particle) * (size_t)std::max<int64_t>(count, 1)); }
+    if (spectrum) { res->n_spectrum = (int64_t)spectrum->size(); res->spectrum = (double *)malloc(sizeof(double) * spectrum->size()); }
+    res->mc_id = (int64_t *)malloc(sizeof(int64_t) * S);
+    res->mass = (double *)malloc(sizeof(double) * S);
+    if ((list && !res->particles) || (spectrum && !res->spectrum) || !res->mc_id || !res->mass)
+        return is3d::set_error(IS3D_ENOMEM, "out of memory%s", list ? " for the particle list" : spectrum ? " for the spectrum" : "");
+    if (list) memcpy(res->particles, list, sizeof(is3d_particle) * (size_t)count);
+    if (spectrum) memcpy(res->spectrum, spectrum->data(), sizeof(double) * spectrum->size());
+    memcpy(res->mc_id, in.mcid.data(), sizeof(int64_t) * S);
+    memcpy(res->mass, in.mass.data(), sizeof(double) * S);
+    return IS3D_OK;
+}
+
+// the line of a stage that shards the cells over the run's devices; `how` says what becomes of the shards' results (NULL: the run's reduce of the spectrum)
+static void print_devices(const RunDevices &rd, int64_t n_cells, const char *how)
+{
+    const int nd = rd.list.empty() ? is3d_device_count() : (int)rd.list.size();
+    if (!how) how = rd.reduce == IS3D_REDUCE_RCCL ? ", RCCL all-reduce of the spectrum" : ", shard-ordered device sum of the spectrum";
+    printf("devices: %d (cell-axis shards of ~%lld cells%s)\n", nd, (long long)((n_cells + nd - 1) / std::max(nd, 1)), nd > 1 ? how : "");
+}
+
+// a sampler run as set up from the parameter file and the tables, before anything is sampled
+struct SamplerRun {
+    is3d_sampler_inputs si{};
+    is3d_sampler_test_bins bins{};
+    GaussLaguerre gla;
+    is3d_feqmod_tables fq{};
+    std::vector<double> xs, ys;
+    double oversample = 0.0, min_num_hadrons = 0.0, max_num_samples = 0.0, y_cut = 0.0, avg[5] = {0, 0, 0, 0, 0};
+    double mean_yield = 0.0;   // calculate_total_yield's member mean_yield (:828), written by write_yield_list_toFile
+};
+
+// the sampler's lines after the sampling: what the momentum sampling accepted ...
+static void print_sampling_efficiency(const RunConfig &cfg, const is3d_sampler_stats &ss)
+{
+    printf("\nMomentum sampling efficiency = %f %%\n", 100.0 * (double)ss.n_acceptances / (double)std::max<int64_t>(ss.n_momentum_samples, 1));
+    if (cfg.feqmod) printf("feqmod breaks down for %lld cells\n", (long long)ss.n_cells_breakdown);
+}
+
+// ... and its closing lines, after the files are written; t_sampled and t_written are the clock at those two points
+static void print_sampler_summary(const RunConfig &cfg, const RunInputs &in, const SamplerRun &s, const is3d_sampler_stats &ss, int64_t count, double t_sampled,
+                                  double t_written)
+{
+    printf("particles: %lld in %d event(s); hadrons drawn %lld; cells skipped (u.dsigma <= 0): %lld\n", (long long)count, s.si.n_events,
+           (long long)ss.n_hadrons_drawn, (long long)ss.n_cells_skipped);
+    printf("device time: prep %.3f ms, count %.3f ms, fill %.3f ms; h2d %.3f ms\n", ss.ms_prep, ss.ms_count, ss.ms_fill, ss.ms_h2d);
+    if (cfg.vah_bin_on_device || cfg.bin_fused) printf("binned where sampled on the device: ms_bin %.3f ms (sampling and binning, one pass), no particle workspace\n", ss.ms_bin);
+    else if (cfg.bin_on_device) printf("binned on the device: ms_bin %.3f ms, particle workspace %lld bytes (one event batch)\n", ss.ms_bin, (long long)ss.particle_workspace_bytes);
+    printf("wall: read %.3f s, sampling %.3f s, write %.3f s\n", in.t_loaded - in.t_start, t_sampled - in.t_loaded, t_written - t_sampled);
+}
+
+// ---- emissionfunction.cpp:205-222, 1309-1321, sampling_kernels.cpp:842-869: the sampler's parameters, cell positions, nodes and averages ----
+static int setup_sampler(const RunConfig &cfg, const RunInputs &in, const RunParams &params, SamplerRun &s)
+{
+    double sampler_seed, fast, test_sampler, set_T, T_switch = 0.0;
+    if (params.required("oversample", &s.oversample) || params.required("min_num_hadrons", &s.min_num_hadrons) ||
+        params.required("max_num_samples", &s.max_num_samples) || params.required("sampler_seed", &sampler_seed) || params.required("y_cut", &s.y_cut) ||
+        params.required("fast", &fast) || params.required("test_sampler", &test_sampler) || params.required("set_fo_temperature", &set_T))
+        return IS3D_EINVAL;
+    if ((int)set_T && params.required("t_switch", &T_switch)) return IS3D_EINVAL;
+    is3d_sampler_test_bins &b = s.bins;
+    if (cfg.test_sampler) {                                                   // emissionfunction.cpp:205-222
+        double yb, eb, pb, tb, rb;
+        if (params.required("y_bins", &yb) || params.required("eta_cut", &b.eta_cut) || params.required("eta_bins", &eb) ||
+            params.required("pt_lower_cut", &b.pT_lower_cut) || params.required("pt_upper_cut", &b.pT_upper_cut) || params.required("pt_bins", &pb) ||
+            params.required("tau_min", &b.tau_min) || params.required("tau_max", &b.tau_max) || params.required("tau_bins", &tb) ||
+            params.required("r_min", &b.r_min) || params.required("r_max", &b.r_max) || params.required("r_bins", &rb))
             return IS3D_EINVAL;
-        if ((int)set_T && get_param("t_switch", &T_switch)) return IS3D_EINVAL;
-        is3d_sampler_test_bins bins{};
-        if ((int)test_sampler) {                                                  // emissionfunction.cpp:205-222
-            double yb, ec, eb, pl, pu, pb, t0b, t1b, tb, r0b, r1b, rb;
-            if (get_param("y_bins", &yb) || get_param("eta_cut", &ec) || get_param("eta_bins", &eb) || get_param("pt_lower_cut", &pl) ||
-                get_param("pt_upper_cut", &pu) || get_param("pt_bins", &pb) || get_param("tau_min", &t0b) || get_param("tau_max", &t1b) ||
-                get_param("tau_bins", &tb) || get_param("r_min", &r0b) || get_param("r_max", &r1b) || get_param("r_bins", &rb))
-                return IS3D_EINVAL;
-            bins.y_cut = y_cut; bins.eta_cut = ec; bins.pT_lower_cut = pl; bins.pT_upper_cut = pu; bins.tau_min = t0b; bins.tau_max = t1b;
-            bins.r_min = r0b; bins.r_max = r1b;
-            bins.y_bins = (int)yb; bins.eta_bins = (int)eb; bins.pT_bins = (int)pb; bins.tau_bins = (int)tb; bins.r_bins = (int)rb;
-        }
-        // cell positions: columns 1, 2 of every supported surface format (readindata.cpp:343-346 etc.)
-        std::vector<double> xs((size_t)n_cells, 0.0), ys((size_t)n_cells, 0.0);
-        if (mem) {
-            if (mem_x) xs.assign(mem_x, mem_x + n_cells);
-            if (mem_y) ys.assign(mem_y, mem_y + n_cells);
-        } else if (n_cells > 0) {   // they came with the surface (is3d_surface_arrays: arrays 23, 24; mode 2: 30, 31)
-            xs.assign(sa[vah ? 30 : 23], sa[vah ? 30 : 23] + n_cells);
-            ys.assign(sa[vah ? 31 : 24], sa[vah ? 31 : 24] + n_cells);
-        }
-        int32_t n_alpha = 0, n_pts = 0;
-        const char *gla_path = "tables/gla_roots_weights_32_points.txt";
-        if (is3d_gla_read(gla_path, &n_alpha, &n_pts, nullptr, nullptr, 0)) DIE("%s", is3d_last_error());
-        if (n_alpha < 3) DIE("%s: needs alpha = 0, 1, 2", gla_path);
-        std::vector<double> groot((size_t)n_alpha * n_pts), gweight((size_t)n_alpha * n_pts);
-        if (is3d_gla_read(gla_path, &n_alpha, &n_pts, groot.data(), gweight.data(), (int64_t)groot.size())) DIE("%s", is3d_last_error());
-        is3d_sampler_inputs si{};
-        si.n_events = 1; si.n_gla = n_pts;
-        si.seed = sampler_seed < 0 ? (uint64_t)std::chrono::system_clock::now().time_since_epoch().count() : (uint64_t)sampler_seed;   // :842-844
-        si.y_cut = y_cut; si.first_cell = 0; si.x = xs.data(); si.y = ys.data();
-        si.root1 = groot.data() + n_pts; si.weight1 = gweight.data() + n_pts;
-        // df_mode 3 / 4 and fast mode: emissionfunction.cpp:1309-1321, sampling_kernels.cpp:852-869
-        double T_avg_file = 0.0, E_avg_file = 0.0, P_avg_file = 0.0, muB_avg_file = 0.0;   // Plasma::load_thermodynamic_averages
-        if (!vah) {   // (the mode-2 reader writes no averages and the anisotropic-hydro sampler takes none)
-            FILE *tf = fopen("average_thermodynamic_quantities.dat", "r");
-            if (!tf || fscanf(tf, "%lf %lf %lf %lf", &T_avg_file, &E_avg_file, &P_avg_file, &muB_avg_file) != 4) DIE("Error opening average thermodynamic file");
-            fclose(tf);
-        }
-        is3d_feqmod_tables fqs{};
-        if (feqmod || (int)fast) {
-            double deta_min, mass_pion0;
-            if (get_param("deta_min", &deta_min) || get_param("mass_pion0", &mass_pion0)) return IS3D_EINVAL;
-            fqs.n_gla = n_pts;
-            fqs.root1 = si.root1; fqs.weight1 = si.weight1;
-            fqs.root2 = groot.data() + 2 * (size_t)n_pts; fqs.weight2 = gweight.data() + 2 * (size_t)n_pts;
-            fqs.n_pdg = npdg; fqs.pdg_mass = pmass.data(); fqs.pdg_degeneracy = pg.data(); fqs.pdg_sign = ps.data();
-            fqs.T_avg = T_avg_file; fqs.deta_min = deta_min; fqs.mass_pion0 = mass_pion0;
-            si.feqmod = &fqs;
-        }
-        si.fast = (int)fast != 0;
-        si.muB_avg = muB_avg_file;                                                // Plasma::baryon_chemical_potential, :858
-        si.T_avg = T_avg_file;
-        si.T_avg_switch = (int)set_T ? T_switch : T_avg_file;                     // :856
-        if (si.fast) printf("Using fast mode: (Tavg, muBavg) = (%lf, %lf)\n", si.T_avg_switch, muB_avg_file);
-        printf("iS3D Sampling Seed : %llu\n", (unsigned long long)si.seed);
-        is3d_sampler_stats ss{};
-        int64_t count = 0;
-        double mean_yield = 0.0;   // calculate_total_yield's member mean_yield (:828), written by write_yield_list_toFile
-        if ((int)oversample) {
-            // emissionfunction.cpp:1524-1533: the analytic mean yield (calculate_total_yield) sizes the run
-            double E_avg = 0.0, P_avg = 0.0, nB_avg = 0.0;
-            {
-                FILE *tf = fopen("average_thermodynamic_quantities.dat", "r");
-                double t_, m_;
-                if (!tf || fscanf(tf, "%lf %lf %lf %lf %lf", &t_, &E_avg, &P_avg, &m_, &nB_avg) != 5) DIE("Error opening average thermodynamic file");
-                fclose(tf);
-            }
-            if (n_alpha < 4) DIE("%s: the yield estimate needs alpha = 0, 1, 2, 3", gla_path);
-            is3d_feqmod_tables fqy = fqs;
-            if (!si.feqmod) {   // the alpha = 2 nodes enter every df_mode's bulk density (J20)
-                fqy.n_gla = n_pts;
-                fqy.root1 = si.root1; fqy.weight1 = si.weight1;
-                fqy.root2 = groot.data() + 2 * (size_t)n_pts; fqy.weight2 = gweight.data() + 2 * (size_t)n_pts;
-            }
-            is3d_sampler_inputs sy = si;
-            sy.feqmod = &fqy;
-            is3d_yield_inputs yi{T_avg_file, E_avg, P_avg, muB_avg_file, nB_avg, groot.data() + 3 * (size_t)n_pts, gweight.data() + 3 * (size_t)n_pts};
-            double Ntotal = 0.0;
-            printf("Total particle yield: ");
-            int rc1 = is3d_total_yield(&cells, &sp, &df, &sy, &yi, &opts, &Ntotal, nullptr);
-            if (rc1) DIE("is3d_total_yield failed (%d): %s", rc1, is3d_last_error());
-            if (dimension == 2) printf("dN_dy ~ %lf\n\n", Ntotal / (2.0 * y_cut));
-            printf("%lf\n", Ntotal);
-            mean_yield = Ntotal;
-            Ntotal = (double)fabsf((float)Ntotal);                                  // "prevent overflow", :1528
-            // Nevents = min((int)ceil(MIN_NUM_HADRONS / Ntotal), MAX_NUM_SAMPLES); at least one event is sampled here
-            si.n_events = (int32_t)std::max(1.0, std::min(std::ceil(min_num_hadrons / Ntotal), (double)(int)max_num_samples));
-        }
-        if (vah) si.n_events = (int32_t)std::max(1.0, (double)(int)max_num_samples);   // without vah_oversample no mean yield sizes the run: MAX_NUM_SAMPLES events
-        if (vah_oversample) {
-            // the anisotropic-hydro mean yield on the first device of the run's list (opts.device), with the sampler's tables, nodes and y_cut
-            double Ntotal = 0.0;
-            printf("Total particle yield: ");
-            const int rc1 = is3d_total_yield_vah(&vc, &sp, &vt, &si, &opts, &Ntotal, nullptr, nullptr);
-            if (rc1) DIE("is3d_total_yield_vah failed (%d): %s", rc1, is3d_last_error());
-            if (dimension == 2) printf("dN_dy ~ %lf\n\n", Ntotal / (2.0 * y_cut));
-            printf("%lf\n", Ntotal);
-            if (!(Ntotal > 0.0))
-                DIE("vah_oversample = 1: the linear delta-f has driven the mean yield of the surface non-positive (%g), which sizes no run (the residual bulk "
-                    "pressure is outside the range of the linear correction); set vah_oversample = 0 (max_num_samples events are sampled)", Ntotal);
-            mean_yield = Ntotal;
-            if (is3d_oversample_events(min_num_hadrons, Ntotal, (int32_t)max_num_samples, &si.n_events)) DIE("%s", is3d_last_error());
-        }
-        printf("Sampling %d event(s)\n", si.n_events);
-        if (df_mode == 1) printf("Sampling particles with Grad 14 moment df...\n");                    // emissionfunction.cpp:1540-1541, :1602-1603
-        if (df_mode == 2) printf("Sampling particles with Chapman Enskog df...\n");
-        if (df_mode == 3) printf("Sampling particles with Mike's modified distribution...\n");
-        if (df_mode == 4 && !vah) printf("Sampling particles with Jonah's modified distribution...\n");
-        if (vah) printf("Sampling particles from vahydro (P_L matching) with df...\n");
-        if (bin_on_device || vah_bin_on_device || bin_fused) {
-            // one pass: every event batch is binned on its device and dropped (anisotropic hydro: every hadron binned where it is sampled); the
-            // integer histograms of the shards are added on the host
-            const size_t S = (size_t)sp.n, plane = (size_t)IS3D_SAMPLER_VN_HARMONICS * S * bins.pT_bins;
-            std::vector<int64_t> h_dy(S * bins.y_bins), h_de(S * bins.eta_bins), h_dp(S * bins.pT_bins), h_dt(S * bins.tau_bins), h_dr(S * bins.r_bins),
-                h_vr(plane), h_vi(plane), h_yield((size_t)si.n_events);
-            const is3d_sampler_hist hist{h_dy.data(), h_de.data(), h_dp.data(), h_dt.data(), h_dr.data(), h_vr.data(), h_vi.data(), h_yield.data()};
-            // anisotropic hydro: a device list the user spelled out shards the cells; without one the first device samples alone
-            const int rcb = bin_fused
-                                ? (rd.named ? is3d_sample_fused_multi(&cells, &sp, &df, &si, &opts, rd.list.data(), (int32_t)rd.list.size(), &bins, &hist, &count, &ss)
-                                            : is3d_sample_fused(&cells, &sp, &df, &si, &opts, &bins, &hist, &count, &ss))
-                            : vah_bin_on_device
-                                ? (rd.named ? is3d_sample_binned_vah_multi(&vc, &sp, &vt, &si, &opts, rd.list.data(), (int32_t)rd.list.size(), &bins, &hist, &count, &ss)
-                                            : is3d_sample_binned_vah(&vc, &sp, &vt, &si, &opts, &bins, &hist, &count, &ss))
-                                : is3d_sample_binned_multi(&cells, &sp, &df, &si, &opts, rd.list.empty() ? nullptr : rd.list.data(), (int32_t)rd.list.size(),
-                                                           &bins, &hist, &count, &ss);
-            if (rcb) DIE("%s failed (%d): %s", bin_fused ? "is3d_sample_fused" : vah_bin_on_device ? "is3d_sample_binned_vah" : "is3d_sample_binned", rcb, is3d_last_error());
-            double t2s = now_s();
-            printf("\nMomentum sampling efficiency = %f %%\n", 100.0 * (double)ss.n_acceptances / (double)std::max<int64_t>(ss.n_momentum_samples, 1));
-            if (feqmod) printf("feqmod breaks down for %lld cells\n", (long long)ss.n_cells_breakdown);
-            printf("Writing the binned sampler test distributions...\n");
-            if (is3d_write_sampler_tests_binned("results", &bins, si.n_events, sp.n, mcid.data(), &hist, mean_yield)) DIE("%s", is3d_last_error());
-            double t3s = now_s();
-            printf("particles: %lld in %d event(s); hadrons drawn %lld; cells skipped (u.dsigma <= 0): %lld\n", (long long)count, si.n_events,
-                   (long long)ss.n_hadrons_drawn, (long long)ss.n_cells_skipped);
-            printf("device time: prep %.3f ms, count %.3f ms, fill %.3f ms; h2d %.3f ms\n", ss.ms_prep, ss.ms_count, ss.ms_fill, ss.ms_h2d);
-            if (vah_bin_on_device || bin_fused) printf("binned where sampled on the device: ms_bin %.3f ms (sampling and binning, one pass), no particle workspace\n", ss.ms_bin);
-            else printf("binned on the device: ms_bin %.3f ms, particle workspace %lld bytes (one event batch)\n", ss.ms_bin, (long long)ss.particle_workspace_bytes);
-            printf("wall: read %.3f s, sampling %.3f s, write %.3f s\n", t1 - t0, t2s - t1, t3s - t2s);
-            if (int rcp = polarization()) return rcp;
-            printf("Done sampling particles. Output stored in results folder. Goodbye!\n");
-            return IS3D_OK;
-        }
-        // count, then fill a list of that size: the viscous-hydro sampler, or (mode 2) the anisotropic-hydro one on the mode-2 cells and tables
-        auto sample = [&](is3d_particle *list, int64_t capacity) {
-            const int32_t *dl = rd.list.empty() ? nullptr : rd.list.data();
-            if (vah) return is3d_sample_particles_vah_multi(&vc, &sp, &vt, &si, &opts, dl, (int32_t)rd.list.size(), list, capacity, &count, &ss);
-            return is3d_sample_particles_multi(&cells, &sp, &df, &si, &opts, dl, (int32_t)rd.list.size(), list, capacity, &count, &ss);
-        };
-        const char *sampler_name = vah ? "is3d_sample_particles_vah" : "is3d_sample_particles";
-        int rc2 = sample(nullptr, 0);
-        if (rc2) DIE("%s failed (%d): %s", sampler_name, rc2, is3d_last_error());
-        std::vector<is3d_particle> plist((size_t)std::max<int64_t>(count, 1));
-        rc2 = sample(plist.data(), count);
-        if (rc2) DIE("%s failed (%d): %s", sampler_name, rc2, is3d_last_error());
-        double t2s = now_s();
-        printf("\nMomentum sampling efficiency = %f %%\n", 100.0 * (double)ss.n_acceptances / (double)std::max<int64_t>(ss.n_momentum_samples, 1));
-        if (feqmod) printf("feqmod breaks down for %lld cells\n", (long long)ss.n_cells_breakdown);
-        if ((int)test_sampler) {                                                  // emissionfunction.cpp:1545-1554
-            printf("Writing the binned sampler test distributions...\n");
-            if (is3d_write_sampler_tests("results", &bins, si.n_events, sp.n, mcid.data(), count, plist.data(), mean_yield)) DIE("%s", is3d_last_error());
-        } else {
-            printf("Writing sampled particles list to OSCAR File...\n");
-            if (is3d_write_particle_list_osc("results/particle_list_osc.dat", si.n_events, count, plist.data(), mcid.data())) DIE("%s", is3d_last_error());
-        }
-        if (decay_sampled) {
-            // the thermal list decayed to stable particles, on the first device of the run's list; its species index the decay table
-            printf("Decaying the sampled hadrons to stable particles...\n");
-            int32_t nd = 0, nc = 0;
-            if (is3d_pdg_read_decays(pdg_path, &nd, &nc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0)) DIE("%s", is3d_last_error());
-            std::vector<int64_t> did((size_t)nd), dau((size_t)nc * 5);
-            std::vector<double> dm((size_t)nd), dw((size_t)nd), dbr((size_t)nc);
-            std::vector<int32_t> dst((size_t)nd), dnc((size_t)nd), dnp((size_t)nc);
-            if (is3d_pdg_read_decays(pdg_path, &nd, &nc, did.data(), dm.data(), dw.data(), dst.data(), dnc.data(), dnp.data(), dbr.data(), dau.data(), nd, nc))
-                DIE("%s", is3d_last_error());
-            const is3d_decay_table tab{nd, did.data(), dm.data(), dw.data(), dst.data(), dnc.data(), dnp.data(), dbr.data(), dau.data()};
-            const is3d_decay_mc_inputs mi{si.seed, 0, 0, rd.list.empty() ? -1 : rd.list[0]};
-            is3d_decay_mc_stats ms{};
-            int64_t n_final = 0;
-            const double t4 = now_s();
-            int rcd = is3d_decay_particles(&tab, sp.n, mcid.data(), &mi, count, plist.data(), nullptr, nullptr, 0, &n_final, &ms);
-            std::vector<is3d_particle> decayed((size_t)std::max<int64_t>(n_final, 1));
-            if (!rcd) rcd = is3d_decay_particles(&tab, sp.n, mcid.data(), &mi, count, plist.data(), decayed.data(), nullptr, n_final, &n_final, &ms);
-            if (rcd) {
-                const std::string msg = is3d_last_error();
-                DIE("is3d_decay_particles failed (%d): %s", rcd, msg.c_str());
-            }
-            if (is3d_write_particle_list_osc("results/particle_list_osc_decayed.dat", si.n_events, n_final, decayed.data(), did.data())) DIE("%s", is3d_last_error());
-            printf("decays: %lld primaries, %lld decays, %lld final particles (%lld without an open channel), %lld phase-space proposals (%lld exhausted); "
-                   "device time: count %.3f ms, fill %.3f ms; wall %.3f s\n", (long long)ms.n_primaries, (long long)ms.n_decays, (long long)ms.n_final,
-                   (long long)ms.n_stuck, (long long)ms.n_trials, (long long)ms.n_exhausted, ms.ms_count, ms.ms_fill, now_s() - t4);
-        }
-        double t3s = now_s();
-        printf("particles: %lld in %d event(s); hadrons drawn %lld; cells skipped (u.dsigma <= 0): %lld\n", (long long)count, si.n_events,
-               (long long)ss.n_hadrons_drawn, (long long)ss.n_cells_skipped);
-        printf("device time: prep %.3f ms, count %.3f ms, fill %.3f ms; h2d %.3f ms\n", ss.ms_prep, ss.ms_count, ss.ms_fill, ss.ms_h2d);
-        printf("wall: read %.3f s, sampling %.3f s, write %.3f s\n", t1 - t0, t2s - t1, t3s - t2s);
-        if (res) {
-            // iS3D.cpp:178-184: the event lists go back to the caller (final_particles_)
-            res->operation = 2; res->n_events = si.n_events; res->n_species = sp.n; res->n_particles = count;
-            res->particles = (is3d_particle *)malloc(sizeof(is3d_particle) * (size_t)std::max<int64_t>(count, 1));
-            res->mc_id = (int64_t *)malloc(sizeof(int64_t) * (size_t)sp.n);
-            res->mass = (double *)malloc(sizeof(double) * (size_t)sp.n);
-            if (!res->particles || !res->mc_id || !res->mass) return is3d::set_error(IS3D_ENOMEM, "out of memory for the particle list");
-            memcpy(res->particles, plist.data(), sizeof(is3d_particle) * (size_t)count);
-            memcpy(res->mc_id, mcid.data(), sizeof(int64_t) * (size_t)sp.n);
-            memcpy(res->mass, mass.data(), sizeof(double) * (size_t)sp.n);
-        }
-        if (int rcp = polarization()) return rcp;
-        printf("Done sampling particles. Output stored in results folder. Goodbye!\n");
-        return IS3D_OK;
+        b.y_cut = s.y_cut;
+        b.y_bins = (int)yb; b.eta_bins = (int)eb; b.pT_bins = (int)pb; b.tau_bins = (int)tb; b.r_bins = (int)rb;
     }
-    if (operation == 0) {
-        // ---- emissionfunction.cpp:1510-1516 -> calculate_dN_dX (smooth_kernels.cpp:1000-1446) ----
-        double t0b, t1b, tb, r0b, r1b, rb;
-        if (get_param("tau_min", &t0b) || get_param("tau_max", &t1b) || get_param("tau_bins", &tb) || get_param("r_min", &r0b) ||
-            get_param("r_max", &r1b) || get_param("r_bins", &rb))
-            return IS3D_EINVAL;
-        is3d_spacetime_bins bins{t0b, t1b, r0b, r1b, (int32_t)tb, (int32_t)rb};
-        // x and y: arrays 23, 24 of the viscous-hydro surfaces, the last two of is3d_surface_read_vah's 32
-        const double *xp = mem ? mem_x : sa[vah ? 30 : 23], *yp = mem ? mem_y : sa[vah ? 31 : 24];
-        std::vector<double> zero(1, 0.0);
-        if (n_cells == 0) xp = yp = zero.data();
-        const int S = sp.n, n_eta_eff = dimension == 3 ? 1 : (int)eta.size();
-        std::vector<double> o_dy((size_t)S), o_t((size_t)S * bins.tau_bins), o_r((size_t)S * bins.r_bins),
-            o_tr((size_t)S * bins.tau_bins * bins.r_bins), o_eta((size_t)S * n_eta_eff);
-        is3d_spacetime_out out{o_dy.data(), o_t.data(), o_r.data(), o_tr.data(), o_eta.data(), nullptr};
-        for (int ip = 0; ip < S; ip++) printf("Starting spacetime distribution %lld\n", (long long)mcid[ip]);   // :1100
-        is3d_spacetime_stats sst{};
-        int rc0;
-        if (vah) {
-            // anisotropic hydro: the first device of the run's list computes alone (opts.device), whatever the list holds
-            printf("computing spacetime distributions from vahydro (P_L matching) with df...\n");
-            rc0 = is3d_spacetime_distributions_vah(&vc, xp, yp, &sp, &grid, pTw.data(), phiw.data(), &vt, &opts, &bins, &out, &sst);
-        } else {
-            // the per-cell stage on cell-axis shards over the run's devices, one bin stage on the first (is3d_spacetime_distributions_multi)
-            rc0 = is3d_spacetime_distributions_multi(&cells, xp, yp, &sp, &grid, pTw.data(), phiw.data(), &df, nullptr, &opts,
-                                                     rd.list.empty() ? nullptr : rd.list.data(), (int32_t)rd.list.size(), &bins, &out, &sst, nullptr);
-            const int nd = rd.list.empty() ? is3d_device_count() : (int)rd.list.size();
-            printf("devices: %d (cell-axis shards of ~%lld cells%s)\n", nd, (long long)((n_cells + nd - 1) / std::max(nd, 1)),
-                   nd > 1 ? ", one bin stage over the assembled per-cell values" : "");
-        }
-        if (rc0) {
-            const std::string msg = is3d_last_error();
-            DIE("%s failed (%d): %s", vah ? "is3d_spacetime_distributions_vah" : "is3d_spacetime_distributions_multi", rc0, msg.c_str());
-        }
-        // the reference prints an error line per cell with a negative bin index (:1391-1392); one line with the counts here
-        if (sst.n_tau_negative || sst.n_r_negative)
-            printf("Error: %lld cells with a negative tau bin index, %lld with a negative r bin index. Adjust the tau_min / r_min parameters\n",
-                   (long long)sst.n_tau_negative, (long long)sst.n_r_negative);
-        // 3+1D: the single eta point is eta_fo of the surface's last cell (etaValues[0], assigned at :1155 before the skip test)
-        const double *eta_fo = vah ? vc.eta : cells.eta;
-        std::vector<double> eta_vals = dimension == 3 ? std::vector<double>(1, n_cells > 0 ? eta_fo[n_cells - 1] : 0.0) : eta;
-        if (is3d_write_spacetime("results/spacetime_distribution", &bins, S, mcid.data(), n_eta_eff, eta_vals.data(), &out))
-            DIE("%s", is3d_last_error());
-        for (int ip = 0; ip < S; ip++) printf("dN_dy = %lf\n", o_dy[ip]);   // :1438-1441
-        printf("species classes evaluated: %d of %d; cells skipped (u.dsigma <= 0): %lld; outside the tau / r bins: %lld / %lld\n", sst.n_classes, S,
-               (long long)sst.n_cells_skipped, (long long)sst.n_tau_outside, (long long)sst.n_r_outside);
-        printf("device time: prep %.3f ms, per-cell %.3f ms, bins %.3f ms; h2d %.3f ms, d2h %.3f ms\n", sst.ms_prep, sst.ms_cells, sst.ms_bins,
-               sst.ms_h2d, sst.ms_d2h);
-        if (res) {
-            res->operation = 0; res->n_species = S;
-            res->mc_id = (int64_t *)malloc(sizeof(int64_t) * (size_t)S);
-            res->mass = (double *)malloc(sizeof(double) * (size_t)S);
-            if (!res->mc_id || !res->mass) return is3d::set_error(IS3D_ENOMEM, "out of memory");
-            memcpy(res->mc_id, mcid.data(), sizeof(int64_t) * (size_t)S);
-            memcpy(res->mass, mass.data(), sizeof(double) * (size_t)S);
-        }
-        if (int rcp = polarization()) return rcp;
-        printf("Done calculating spacetime distributions. Output stored in results/spacetime_distribution. Goodbye!\n");
-        return IS3D_OK;
+    // cell positions: columns 1, 2 of every supported surface format (readindata.cpp:343-346 etc.); zeros where the embedding caller gave none
+    s.xs.assign((size_t)in.n_cells, 0.0); s.ys.assign((size_t)in.n_cells, 0.0);
+    if (in.n_cells > 0 && in.x) s.xs.assign(in.x, in.x + in.n_cells);
+    if (in.n_cells > 0 && in.y) s.ys.assign(in.y, in.y + in.n_cells);
+    if (int rc = read_gauss_laguerre(s.gla, s.fq)) return rc;
+    is3d_sampler_inputs &si = s.si;
+    si.n_events = 1; si.n_gla = s.gla.n_pts;
+    si.seed = sampler_seed < 0 ? (uint64_t)std::chrono::system_clock::now().time_since_epoch().count() : (uint64_t)sampler_seed;   // :842-844
+    si.y_cut = s.y_cut; si.first_cell = 0; si.x = s.xs.data(); si.y = s.ys.data();
+    si.root1 = s.gla.r(1); si.weight1 = s.gla.w(1);
+    if (int rc = cfg.vah ? IS3D_OK : read_averages(4, s.avg)) return rc;   // (the mode-2 reader writes no averages and the VAH sampler takes none)
+    const double T_avg = s.avg[0], muB_avg = s.avg[3];
+    if (cfg.feqmod || (int)fast) {   // df_mode 3 / 4 and fast mode: emissionfunction.cpp:1309-1321, sampling_kernels.cpp:852-869
+        if (int rc = fill_feqmod(in, params, T_avg, s.fq)) return rc;
+        si.feqmod = &s.fq;
     }
+    si.fast = (int)fast != 0;
+    si.T_avg = T_avg; si.muB_avg = muB_avg;                                   // Plasma::baryon_chemical_potential, :858
+    si.T_avg_switch = (int)set_T ? T_switch : T_avg;                          // :856
+    if (si.fast) printf("Using fast mode: (Tavg, muBavg) = (%lf, %lf)\n", si.T_avg_switch, muB_avg);
+    printf("iS3D Sampling Seed : %llu\n", (unsigned long long)si.seed);
+    return IS3D_OK;
+}
+
+// ---- emissionfunction.cpp:1524-1533: the number of events, from the analytic mean yield where one sizes the run ----
+static int size_sampler_run(const RunConfig &cfg, RunInputs &in, SamplerRun &s)
+{
+    is3d_sampler_inputs &si = s.si;
+    const size_t n_pts = (size_t)s.gla.n_pts;
+    const auto print_yield = [&](double N) { if (cfg.dimension == 2) printf("dN_dy ~ %lf\n\n", N / (2.0 * s.y_cut)); printf("%lf\n", N); };
+    if ((int)s.oversample) {
+        if (int rc = read_averages(5, s.avg)) return rc;   // calculate_total_yield also takes E, P and nB
+        if (s.gla.n_alpha < 4) DIE("%s: the yield estimate needs alpha = 0, 1, 2, 3", s.gla.path);
+        is3d_feqmod_tables fqy = s.fq;   // the alpha = 2 nodes enter every df_mode's bulk density (J20)
+        is3d_sampler_inputs sy = si;
+        sy.feqmod = &fqy;
+        is3d_yield_inputs yi{s.avg[0], s.avg[1], s.avg[2], s.avg[3], s.avg[4], s.gla.root.data() + 3 * n_pts, s.gla.weight.data() + 3 * n_pts};
+        double Ntotal = 0.0;
+        printf("Total particle yield: ");
+        int rc1 = is3d_total_yield(&in.cells, &in.sp, &in.df, &sy, &yi, &in.opts, &Ntotal, nullptr);
+        if (rc1) DIE("is3d_total_yield failed (%d): %s", rc1, is3d_last_error());
+        print_yield(Ntotal);
+        s.mean_yield = Ntotal;
+        Ntotal = (double)fabsf((float)Ntotal);                                  // "prevent overflow", :1528
+        // Nevents = min((int)ceil(MIN_NUM_HADRONS / Ntotal), MAX_NUM_SAMPLES); at least one event is sampled here
+        si.n_events = (int32_t)std::max(1.0, std::min(std::ceil(s.min_num_hadrons / Ntotal), (double)(int)s.max_num_samples));
+    }
+    if (cfg.vah) si.n_events = (int32_t)std::max(1.0, (double)(int)s.max_num_samples);   // without vah_oversample no mean yield sizes the run: MAX_NUM_SAMPLES events
+    if (cfg.vah_oversample) {
+        // the anisotropic-hydro mean yield on the first device of the run's list (opts.device), with the sampler's tables, nodes and y_cut
+        double Ntotal = 0.0;
+        printf("Total particle yield: ");
+        const int rc1 = is3d_total_yield_vah(&in.vc, &in.sp, &in.vt, &si, &in.opts, &Ntotal, nullptr, nullptr);
+        if (rc1) DIE("is3d_total_yield_vah failed (%d): %s", rc1, is3d_last_error());
+        print_yield(Ntotal);
+        if (!(Ntotal > 0.0))
+            DIE("vah_oversample = 1: the linear delta-f has driven the mean yield of the surface non-positive (%g), which sizes no run (the residual bulk "
+                "pressure is outside the range of the linear correction); set vah_oversample = 0 (max_num_samples events are sampled)", Ntotal);
+        s.mean_yield = Ntotal;
+        if (is3d_oversample_events(s.min_num_hadrons, Ntotal, (int32_t)s.max_num_samples, &si.n_events)) DIE("%s", is3d_last_error());
+    }
+    printf("Sampling %d event(s)\n", si.n_events);
+    if (cfg.df_mode == 1) printf("Sampling particles with Grad 14 moment df...\n");                    // emissionfunction.cpp:1540-1541, :1602-1603
+    if (cfg.df_mode == 2) printf("Sampling particles with Chapman Enskog df...\n");
+    if (cfg.df_mode == 3) printf("Sampling particles with Mike's modified distribution...\n");
+    if (cfg.df_mode == 4 && !cfg.vah) printf("Sampling particles with Jonah's modified distribution...\n");
+    if (cfg.vah) printf("Sampling particles from vahydro (P_L matching) with df...\n");
+    return IS3D_OK;
+}
+
+// test_sampler_on_device | test_sampler_fused | vah_sampler_on_device: one pass, every event batch binned on its device and dropped (anisotropic
+// hydro and the fused route: every hadron binned where it is sampled); the integer histograms of the shards are added on the host
+static int run_sampler_binned(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, SamplerRun &s)
+{
+    const is3d_sampler_test_bins &bins = s.bins;
+    const size_t S = (size_t)in.sp.n, plane = (size_t)IS3D_SAMPLER_VN_HARMONICS * S * bins.pT_bins;
+    std::vector<int64_t> h_dy(S * bins.y_bins), h_de(S * bins.eta_bins), h_dp(S * bins.pT_bins), h_dt(S * bins.tau_bins), h_dr(S * bins.r_bins),
+        h_vr(plane), h_vi(plane), h_yield((size_t)s.si.n_events);
+    const is3d_sampler_hist hist{h_dy.data(), h_de.data(), h_dp.data(), h_dt.data(), h_dr.data(), h_vr.data(), h_vi.data(), h_yield.data()};
+    is3d_sampler_stats ss{};
+    int64_t count = 0;
+    // anisotropic hydro and the fused route: a device list the user spelled out shards the cells; without one the first device samples alone
+    const int rcb = cfg.bin_fused
+                        ? (rd.named ? is3d_sample_fused_multi(&in.cells, &in.sp, &in.df, &s.si, &in.opts, rd.list.data(), rd.size(), &bins, &hist, &count, &ss)
+                                    : is3d_sample_fused(&in.cells, &in.sp, &in.df, &s.si, &in.opts, &bins, &hist, &count, &ss))
+                    : cfg.vah_bin_on_device
+                        ? (rd.named ? is3d_sample_binned_vah_multi(&in.vc, &in.sp, &in.vt, &s.si, &in.opts, rd.list.data(), rd.size(), &bins, &hist, &count, &ss)
+                                    : is3d_sample_binned_vah(&in.vc, &in.sp, &in.vt, &s.si, &in.opts, &bins, &hist, &count, &ss))
+                        : is3d_sample_binned_multi(&in.cells, &in.sp, &in.df, &s.si, &in.opts, rd.data(), rd.size(), &bins, &hist, &count, &ss);
+    if (rcb) DIE("%s failed (%d): %s", cfg.bin_fused ? "is3d_sample_fused" : cfg.vah_bin_on_device ? "is3d_sample_binned_vah" : "is3d_sample_binned", rcb, is3d_last_error());
+    const double t_sampled = now_s();
+    print_sampling_efficiency(cfg, ss);
+    printf("Writing the binned sampler test distributions...\n");
+    if (is3d_write_sampler_tests_binned("results", &bins, s.si.n_events, in.sp.n, in.mcid.data(), &hist, s.mean_yield)) DIE("%s", is3d_last_error());
+    print_sampler_summary(cfg, in, s, ss, count, t_sampled, now_s());
+    return IS3D_OK;
+}
+
+// decay_sampled_hadrons = 1: the thermal list decayed to stable particles, on the first device of the run's list; its species index the decay table
+static int decay_sampled_list(const RunConfig &cfg, const RunInputs &in, const RunDevices &rd, const SamplerRun &s, const std::vector<is3d_particle> &plist, int64_t count)
+{
+    printf("Decaying the sampled hadrons to stable particles...\n");
+    DecayTable tab;
+    if (int rc = read_decay_table(cfg.pdg_path, tab)) return rc;
+    const is3d_decay_mc_inputs mi{s.si.seed, 0, 0, rd.first()};
+    is3d_decay_mc_stats ms{};
+    int64_t n_final = 0;
+    const double t4 = now_s();
+    int rcd = is3d_decay_particles(&tab.view, in.sp.n, in.mcid.data(), &mi, count, plist.data(), nullptr, nullptr, 0, &n_final, &ms);
+    std::vector<is3d_particle> decayed((size_t)std::max<int64_t>(n_final, 1));
+    if (!rcd) rcd = is3d_decay_particles(&tab.view, in.sp.n, in.mcid.data(), &mi, count, plist.data(), decayed.data(), nullptr, n_final, &n_final, &ms);
+    if (rcd) {
+        const std::string msg = is3d_last_error();
+        DIE("is3d_decay_particles failed (%d): %s", rcd, msg.c_str());
+    }
+    if (is3d_write_particle_list_osc("results/particle_list_osc_decayed.dat", s.si.n_events, n_final, decayed.data(), tab.id.data())) DIE("%s", is3d_last_error());
+    printf("decays: %lld primaries, %lld decays, %lld final particles (%lld without an open channel), %lld phase-space proposals (%lld exhausted); "
+           "device time: count %.3f ms, fill %.3f ms; wall %.3f s\n", (long long)ms.n_primaries, (long long)ms.n_decays, (long long)ms.n_final,
+           (long long)ms.n_stuck, (long long)ms.n_trials, (long long)ms.n_exhausted, ms.ms_count, ms.ms_fill, now_s() - t4);
+    return IS3D_OK;
+}
+
+// ---- operation 2 (emissionfunction.cpp:1522-1554): number of events, sampling, the OSCAR list or the binned test distributions ----
+static int run_sampler(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, RunParams &params, is3d_run_result *res)
+{
+    SamplerRun s;
+    if (int rc = setup_sampler(cfg, in, params, s)) return rc;
+    if (int rc = size_sampler_run(cfg, in, s)) return rc;
+    if (cfg.bin_on_device || cfg.vah_bin_on_device || cfg.bin_fused) return run_sampler_binned(cfg, in, rd, s);
+    // count, then fill a list of that size: the viscous-hydro sampler, or (mode 2) the anisotropic-hydro one on the mode-2 cells and tables
+    is3d_sampler_stats ss{};
+    int64_t count = 0;
+    auto sample = [&](is3d_particle *list, int64_t capacity) {
+        if (cfg.vah) return is3d_sample_particles_vah_multi(&in.vc, &in.sp, &in.vt, &s.si, &in.opts, rd.data(), rd.size(), list, capacity, &count, &ss);
+        return is3d_sample_particles_multi(&in.cells, &in.sp, &in.df, &s.si, &in.opts, rd.data(), rd.size(), list, capacity, &count, &ss);
+    };
+    const char *sampler_name = cfg.vah ? "is3d_sample_particles_vah" : "is3d_sample_particles";
+    int rc2 = sample(nullptr, 0);
+    if (rc2) DIE("%s failed (%d): %s", sampler_name, rc2, is3d_last_error());
+    std::vector<is3d_particle> plist((size_t)std::max<int64_t>(count, 1));
+    rc2 = sample(plist.data(), count);
+    if (rc2) DIE("%s failed (%d): %s", sampler_name, rc2, is3d_last_error());
+    const double t_sampled = now_s();
+    print_sampling_efficiency(cfg, ss);
+    if (cfg.test_sampler) {                                                   // emissionfunction.cpp:1545-1554
+        printf("Writing the binned sampler test distributions...\n");
+        if (is3d_write_sampler_tests("results", &s.bins, s.si.n_events, in.sp.n, in.mcid.data(), count, plist.data(), s.mean_yield)) DIE("%s", is3d_last_error());
+    } else {
+        printf("Writing sampled particles list to OSCAR File...\n");
+        if (is3d_write_particle_list_osc("results/particle_list_osc.dat", s.si.n_events, count, plist.data(), in.mcid.data())) DIE("%s", is3d_last_error());
+    }
+    if (int rc = cfg.decay_sampled ? decay_sampled_list(cfg, in, rd, s, plist, count) : IS3D_OK) return rc;
+    print_sampler_summary(cfg, in, s, ss, count, t_sampled, now_s());
+    if (res) res->n_events = s.si.n_events;   // iS3D.cpp:178-184: the event lists go back to the caller (final_particles_)
+    return copy_result(res, 2, in, nullptr, plist.data(), count);
+}
+
+// ---- operation 0 (emissionfunction.cpp:1510-1516 -> calculate_dN_dX, smooth_kernels.cpp:1000-1446) ----
+static int run_spacetime(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, RunParams &params, is3d_run_result *res)
+{
+    double t0b, t1b, tb, r0b, r1b, rb;
+    if (params.required("tau_min", &t0b) || params.required("tau_max", &t1b) || params.required("tau_bins", &tb) || params.required("r_min", &r0b) ||
+        params.required("r_max", &r1b) || params.required("r_bins", &rb))
+        return IS3D_EINVAL;
+    is3d_spacetime_bins bins{t0b, t1b, r0b, r1b, (int32_t)tb, (int32_t)rb};
+    const double *xp = in.x, *yp = in.y;
+    std::vector<double> zero(1, 0.0);
+    if (in.n_cells == 0) xp = yp = zero.data();
+    const int S = in.sp.n, n_eta_eff = cfg.dimension == 3 ? 1 : (int)in.eta.size();
+    std::vector<double> o_dy((size_t)S), o_t((size_t)S * bins.tau_bins), o_r((size_t)S * bins.r_bins),
+        o_tr((size_t)S * bins.tau_bins * bins.r_bins), o_eta((size_t)S * n_eta_eff);
+    is3d_spacetime_out out{o_dy.data(), o_t.data(), o_r.data(), o_tr.data(), o_eta.data(), nullptr};
+    for (int ip = 0; ip < S; ip++) printf("Starting spacetime distribution %lld\n", (long long)in.mcid[ip]);   // :1100
+    is3d_spacetime_stats sst{};
+    int rc0;
+    if (cfg.vah) {
+        // anisotropic hydro: the first device of the run's list computes alone (opts.device), whatever the list holds
+        printf("computing spacetime distributions from vahydro (P_L matching) with df...\n");
+        rc0 = is3d_spacetime_distributions_vah(&in.vc, xp, yp, &in.sp, &in.grid, in.pTw.data(), in.phiw.data(), &in.vt, &in.opts, &bins, &out, &sst);
+    } else {
+        // the per-cell stage on cell-axis shards over the run's devices, one bin stage on the first (is3d_spacetime_distributions_multi)
+        rc0 = is3d_spacetime_distributions_multi(&in.cells, xp, yp, &in.sp, &in.grid, in.pTw.data(), in.phiw.data(), &in.df, nullptr, &in.opts, rd.data(),
+                                                 rd.size(), &bins, &out, &sst, nullptr);
+        print_devices(rd, in.n_cells, ", one bin stage over the assembled per-cell values");
+    }
+    if (rc0) {
+        const std::string msg = is3d_last_error();
+        DIE("%s failed (%d): %s", cfg.vah ? "is3d_spacetime_distributions_vah" : "is3d_spacetime_distributions_multi", rc0, msg.c_str());
+    }
+    // the reference prints an error line per cell with a negative bin index (:1391-1392); one line with the counts here
+    if (sst.n_tau_negative || sst.n_r_negative)
+        printf("Error: %lld cells with a negative tau bin index, %lld with a negative r bin index. Adjust the tau_min / r_min parameters\n",
+               (long long)sst.n_tau_negative, (long long)sst.n_r_negative);
+    // 3+1D: the single eta point is eta_fo of the surface's last cell (etaValues[0], assigned at :1155 before the skip test)
+    const double *eta_fo = cfg.vah ? in.vc.eta : in.cells.eta;
+    std::vector<double> eta_vals = cfg.dimension == 3 ? std::vector<double>(1, in.n_cells > 0 ? eta_fo[in.n_cells - 1] : 0.0) : in.eta;
+    if (is3d_write_spacetime("results/spacetime_distribution", &bins, S, in.mcid.data(), n_eta_eff, eta_vals.data(), &out))
+        DIE("%s", is3d_last_error());
+    for (int ip = 0; ip < S; ip++) printf("dN_dy = %lf\n", o_dy[ip]);   // :1438-1441
+    printf("species classes evaluated: %d of %d; cells skipped (u.dsigma <= 0): %lld; outside the tau / r bins: %lld / %lld\n", sst.n_classes, S,
+           (long long)sst.n_cells_skipped, (long long)sst.n_tau_outside, (long long)sst.n_r_outside);
+    printf("device time: prep %.3f ms, per-cell %.3f ms, bins %.3f ms; h2d %.3f ms, d2h %.3f ms\n", sst.ms_prep, sst.ms_cells, sst.ms_bins,
+           sst.ms_h2d, sst.ms_d2h);
+    return copy_result(res, 0, in, nullptr, nullptr, 0);
+}
+
+// do_resonance_decays = 1 (emissionfunction.cpp:1689-1698): the feed-down of the thermal spectrum, then its two files; on the first device of the run's list
+static int feed_down(const RunConfig &cfg, const RunInputs &in, const RunDevices &rd, const std::vector<double> &dN)
+{
+    printf("Starting resonance decays...\n");
+    DecayTable tab;
+    if (int rc = read_decay_table(cfg.pdg_path, tab)) return rc;
+    std::vector<double> fed(dN);
+    is3d_decay_stats ds{};
+    const double t4 = now_s();
+    const int rcd = is3d_resonance_decays(&tab.view, in.sp.n, in.mcid.data(), &in.grid, cfg.dimension, rd.first(), fed.data(), &ds);
+    if (rcd) {
+        const std::string msg = is3d_last_error();
+        DIE("is3d_resonance_decays failed (%d): %s", rcd, msg.c_str());
+    }
+    printf("Writing thermal + resonance decays spectra to file...\n");
+    if (is3d_write_results_decays("results", cfg.dimension, in.sp.n, in.grid.n_pT, in.pT.data(), in.grid.n_phi, in.phi.data(), in.grid.n_y, in.yv.data(), fed.data()))
+        DIE("%s", is3d_last_error());
+    printf("resonance decays: %d parents, %d channels integrated (%d with adjusted masses), %lld acos clamps; device time: tables %.3f ms, "
+           "feed-down %.3f ms; wall %.3f s\n", ds.n_parents, ds.n_channels, ds.n_adjusted, (long long)ds.n_clamps, ds.ms_tables, ds.ms_feed, now_s() - t4);
+    return IS3D_OK;
+}
+
+// ---- operation 1 (emissionfunction.cpp:1556-1698): the smooth momentum spectra, their files, the decay feed-down ----
+static int run_spectra(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, RunParams &params, is3d_run_result *res)
+{
+    const int ny_eff = (cfg.dimension == 2) ? 1 : (int)in.yv.size();
+    std::vector<double> dN(in.mcid.size() * in.pT.size() * in.phi.size() * (size_t)ny_eff, 0.0);
     is3d_status st{};
     int rc;
-    if (vah) {
+    if (cfg.vah) {
         // the call the reference has commented out (emissionfunction.cpp:1650-1654), with the coefficients the CUDA tree's reader
         // would have put into the surface (src/cuda/deltafReader.cu:224-278)
         printf("computing thermal spectra from vahydro (P_L matching) with df...\n");
         // a device list the user spelled out shards the cells; without one the first device computes alone, whatever the machine shows
         if (rd.named) {
-            rc = is3d_smooth_spectra_vah_multi(&vc, &sp, &grid, &vt, &opts, rd.list.data(), (int32_t)rd.list.size(), rd.reduce, dN.data(), &st, nullptr);
-            const int nd = (int)rd.list.size();
-            printf("devices: %d (cell-axis shards of ~%lld cells%s)\n", nd, (long long)((n_cells + nd - 1) / std::max(nd, 1)),
-                   nd > 1 ? (rd.reduce == IS3D_REDUCE_RCCL ? ", RCCL all-reduce of the spectrum" : ", shard-ordered device sum of the spectrum") : "");
+            rc = is3d_smooth_spectra_vah_multi(&in.vc, &in.sp, &in.grid, &in.vt, &in.opts, rd.list.data(), rd.size(), rd.reduce, dN.data(), &st, nullptr);
+            print_devices(rd, in.n_cells, nullptr);
         } else {
-            rc = is3d_smooth_spectra_vah_df(&vc, &sp, &grid, &vt, &opts, dN.data(), &st);
+            rc = is3d_smooth_spectra_vah_df(&in.vc, &in.sp, &in.grid, &in.vt, &in.opts, dN.data(), &st);
         }
-    } else if (feqmod) {
-        printf("computing thermal spectra from vhydro with feqmod...\n");
-        // emissionfunction.cpp:1309-1319: Gauss-Laguerre tables, Plasma::load_thermodynamic_averages (the file written
-        // above, read back as text), parameters deta_min and mass_pion0 (:184, :188)
-        int32_t n_alpha = 0, n_pts = 0;
-        const char *gla_path = "tables/gla_roots_weights_32_points.txt";
-        if (is3d_gla_read(gla_path, &n_alpha, &n_pts, nullptr, nullptr, 0)) DIE("%s", is3d_last_error());
-        if (n_alpha < 3) DIE("%s: needs alpha = 0, 1, 2", gla_path);
-        std::vector<double> groot((size_t)n_alpha * n_pts), gweight((size_t)n_alpha * n_pts);
-        if (is3d_gla_read(gla_path, &n_alpha, &n_pts, groot.data(), gweight.data(), (int64_t)groot.size())) DIE("%s", is3d_last_error());
-        double deta_min, mass_pion0, T_avg = 0.0;
-        if (get_param("deta_min", &deta_min) || get_param("mass_pion0", &mass_pion0)) return IS3D_EINVAL;
-        {
-            FILE *tf = fopen("average_thermodynamic_quantities.dat", "r");
-            if (!tf || fscanf(tf, "%lf", &T_avg) != 1) DIE("Error opening average thermodynamic file");
-            fclose(tf);
-        }
-        is3d_feqmod_tables fq{};
-        fq.n_gla = n_pts;
-        fq.root1 = groot.data() + n_pts; fq.weight1 = gweight.data() + n_pts;
-        fq.root2 = groot.data() + 2 * (size_t)n_pts; fq.weight2 = gweight.data() + 2 * (size_t)n_pts;
-        fq.n_pdg = npdg; fq.pdg_mass = pmass.data(); fq.pdg_degeneracy = pg.data(); fq.pdg_sign = ps.data();
-        fq.T_avg = T_avg; fq.deta_min = deta_min; fq.mass_pion0 = mass_pion0;
-        rc = is3d_smooth_spectra_multi(&cells, &sp, &grid, &df, &fq, &opts, rd.list.empty() ? nullptr : rd.list.data(), (int32_t)rd.list.size(),
-                                       rd.reduce, dN.data(), &st, nullptr);
     } else {
-        printf("computing thermal spectra from vhydro with df...\n");
-        rc = is3d_smooth_spectra_multi(&cells, &sp, &grid, &df, nullptr, &opts, rd.list.empty() ? nullptr : rd.list.data(), (int32_t)rd.list.size(),
-                                       rd.reduce, dN.data(), &st, nullptr);
-    }
-    if (!vah) {
-        const int nd = rd.list.empty() ? is3d_device_count() : (int)rd.list.size();
-        printf("devices: %d (cell-axis shards of ~%lld cells%s)\n", nd, (long long)((n_cells + nd - 1) / std::max(nd, 1)),
-               nd > 1 ? (rd.reduce == IS3D_REDUCE_RCCL ? ", RCCL all-reduce of the spectrum" : ", shard-ordered device sum of the spectrum") : "");
+        GaussLaguerre gla;
+        is3d_feqmod_tables fq{};
+        fputs(cfg.feqmod ? "computing thermal spectra from vhydro with feqmod...\n" : "computing thermal spectra from vhydro with df...\n", stdout);
+        if (cfg.feqmod) {
+            // emissionfunction.cpp:1309-1319: Gauss-Laguerre tables, parameters deta_min and mass_pion0 (:184, :188), Plasma::load_thermodynamic_averages
+            double T_avg = 0.0;
+            if (int rcg = read_gauss_laguerre(gla, fq)) return rcg;
+            if (fill_feqmod(in, params, 0.0, fq)) return IS3D_EINVAL;
+            if (int rca = read_averages(1, &T_avg)) return rca;
+            fq.T_avg = T_avg;
+        }
+        rc = is3d_smooth_spectra_multi(&in.cells, &in.sp, &in.grid, &in.df, cfg.feqmod ? &fq : nullptr, &in.opts, rd.data(), rd.size(), rd.reduce, dN.data(),
+                                       &st, nullptr);
+        print_devices(rd, in.n_cells, nullptr);
     }
     if (rc) {
         const std::string msg = is3d_last_error();
         DIE("is3d_smooth_spectra failed (%d): %s", rc, msg.c_str());
     }
-    if (feqmod && !vah) printf("\nfeqmod breaks down for %lld cells\n\n", (long long)st.n_cells_breakdown);   // smooth_kernels.cpp:989
-    double t2 = now_s();
-    if (is3d_write_results("results", dimension, sp.n, mcid.data(), grid.n_pT, pT.data(), pTw.data(), grid.n_phi, phi.data(),
-                           phiw.data(), grid.n_y, y.data(), dN.data()))
+    if (cfg.feqmod) printf("\nfeqmod breaks down for %lld cells\n\n", (long long)st.n_cells_breakdown);   // smooth_kernels.cpp:989
+    const double t2 = now_s();
+    if (is3d_write_results("results", cfg.dimension, in.sp.n, in.mcid.data(), in.grid.n_pT, in.pT.data(), in.pTw.data(), in.grid.n_phi, in.phi.data(),
+                           in.phiw.data(), in.grid.n_y, in.yv.data(), dN.data()))
         DIE("%s", is3d_last_error());
-    double t3 = now_s();
-    printf("species classes evaluated: %d of %d; cells skipped (u.dsigma <= 0): %lld\n", st.n_classes, sp.n, (long long)st.n_cells_skipped);
+    const double t3 = now_s();
+    printf("species classes evaluated: %d of %d; cells skipped (u.dsigma <= 0): %lld\n", st.n_classes, in.sp.n, (long long)st.n_cells_skipped);
     printf("device time: prep %.3f ms, main %.3f ms (kernel variant %d), finalize %.3f ms; h2d %.3f ms, d2h %.3f ms\n", st.ms_prep,
            st.ms_main, st.kernel_variant, st.ms_finalize, st.ms_h2d, st.ms_d2h);
-    const int src_kind = surf ? is3d_surface_source(surf) : -1;
-    printf("wall: read %.3f s, spectra %.3f s, write %.3f s\n", t1 - t0, t2 - t1, t3 - t2);
+    const int src_kind = in.surf ? is3d_surface_source(in.surf) : -1;
+    printf("wall: read %.3f s, spectra %.3f s, write %.3f s\n", in.t_loaded - in.t_start, t2 - in.t_loaded, t3 - t2);
     if (src_kind >= 0)
         printf("surface: %s\n", src_kind == 2 ? "binary sidecar input/surface.dat.is3dcache (matches the text file; IS3D_NO_CACHE=1 to ignore)"
                                  : src_kind == 1 ? "text parsed, sidecar input/surface.dat.is3dcache written for the next run" : "text parsed");
-    if (res) {
-        res->operation = 1; res->n_species = sp.n; res->n_spectrum = (int64_t)dN.size();
-        res->spectrum = (double *)malloc(sizeof(double) * dN.size());
-        res->mc_id = (int64_t *)malloc(sizeof(int64_t) * (size_t)sp.n);
-        res->mass = (double *)malloc(sizeof(double) * (size_t)sp.n);
-        if (!res->spectrum || !res->mc_id || !res->mass) return is3d::set_error(IS3D_ENOMEM, "out of memory for the spectrum");
-        memcpy(res->spectrum, dN.data(), sizeof(double) * dN.size());
-        memcpy(res->mc_id, mcid.data(), sizeof(int64_t) * (size_t)sp.n);
-        memcpy(res->mass, mass.data(), sizeof(double) * (size_t)sp.n);
+    if (int rcr = copy_result(res, 1, in, &dN, nullptr, 0)) return rcr;   // the embedding result keeps the thermal spectrum
+    return cfg.do_decays ? feed_down(cfg, in, rd, dN) : IS3D_OK;
+}
+
+// ---- mode 5: every run ends with the spin polarization from the surface's thermal vorticity (emissionfunction.cpp:1675, :1701) ----
+static int run_polarization(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, RunParams &params, is3d_run_result *)
+{
+    if (cfg.mode != 5 || cfg.vah) return IS3D_OK;
+    if (in.from_memory) {
+        printf("mode = 5: the spin polarization needs the thermal vorticity, which only the file reader (input/surface.dat) provides; no S*.dat written\n");
+        return IS3D_OK;
     }
-    if (do_decays) {
-        // emissionfunction.cpp:1689-1698: the feed-down of the thermal spectrum, then its two files; on the first device of the run's list
-        printf("Starting resonance decays...\n");
-        int32_t nd = 0, nc = 0;
-        if (is3d_pdg_read_decays(pdg_path, &nd, &nc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0)) DIE("%s", is3d_last_error());
-        std::vector<int64_t> did((size_t)nd), dau((size_t)nc * 5);
-        std::vector<double> dm((size_t)nd), dw((size_t)nd), dbr((size_t)nc);
-        std::vector<int32_t> dst((size_t)nd), dnc((size_t)nd), dnp((size_t)nc);
-        if (is3d_pdg_read_decays(pdg_path, &nd, &nc, did.data(), dm.data(), dw.data(), dst.data(), dnc.data(), dnp.data(), dbr.data(), dau.data(), nd, nc))
-            DIE("%s", is3d_last_error());
-        const is3d_decay_table tab{nd, did.data(), dm.data(), dw.data(), dst.data(), dnc.data(), dnp.data(), dbr.data(), dau.data()};
-        std::vector<double> fed(dN);
-        is3d_decay_stats dst_{};
-        const double t4 = now_s();
-        const int rcd = is3d_resonance_decays(&tab, sp.n, mcid.data(), &grid, dimension, rd.list.empty() ? -1 : rd.list[0], fed.data(), &dst_);
-        if (rcd) {
-            const std::string msg = is3d_last_error();
-            DIE("is3d_resonance_decays failed (%d): %s", rcd, msg.c_str());
-        }
-        printf("Writing thermal + resonance decays spectra to file...\n");
-        if (is3d_write_results_decays("results", dimension, sp.n, grid.n_pT, pT.data(), grid.n_phi, phi.data(), grid.n_y, y.data(), fed.data()))
-            DIE("%s", is3d_last_error());
-        printf("resonance decays: %d parents, %d channels integrated (%d with adjusted masses), %lld acos clamps; device time: tables %.3f ms, "
-               "feed-down %.3f ms; wall %.3f s\n", dst_.n_parents, dst_.n_channels, dst_.n_adjusted, (long long)dst_.n_clamps, dst_.ms_tables,
-               dst_.ms_feed, now_s() - t4);
+    // Plasma::temperature: the first line of the averages file this run wrote, or T_switch (emissionfunction.cpp:1318-1321)
+    double Tp = 0.0, set_T = 0.0;
+    if (int rc = read_averages(1, &Tp)) return rc;
+    if (params.optional("set_fo_temperature", &set_T) && (int)set_T && params.required("t_switch", &Tp)) return IS3D_EINVAL;
+    const double *w[6];
+    if (is3d_surface_vorticity(in.surf, w)) DIE("%s", is3d_last_error());
+    is3d_vorticity vort{w[0], w[1], w[2], w[3], w[4], w[5]};
+    is3d_options po{};
+    po.dimension = cfg.dimension;
+    po.device = rd.first();
+    const size_t np = in.mcid.size() * in.pT.size() * in.phi.size() * (size_t)((cfg.dimension == 2) ? 1 : in.yv.size());
+    std::vector<double> pS[5];
+    for (auto &v : pS) v.assign(np, 0.0);
+    is3d_polarization_out po_out{pS[0].data(), pS[1].data(), pS[2].data(), pS[3].data(), pS[4].data()};
+    is3d_polarization_stats pst{};
+    printf("Calculating spin polarization vector (T = %.6f GeV)...\n", Tp);
+    // a device list the user spelled out shards the cells like the run's other cell sums do.  Without one the first device computes alone:
+    // the sum's association depends on the shard count, and the S files (eight digits) must not depend on how many cards a machine shows
+    std::vector<is3d_polarization_stats> pss(rd.named ? rd.list.size() : 0);
+    const int rcp = rd.named ? is3d_spin_polarization_multi(&in.cells, &vort, &in.sp, &in.grid, Tp, &po, rd.list.data(), rd.size(), &po_out, &pst, pss.data())
+                             : is3d_spin_polarization(&in.cells, &vort, &in.sp, &in.grid, Tp, &po, &po_out, &pst);
+    if (rcp) {
+        const std::string msg = is3d_last_error();
+        DIE("%s failed (%d): %s", rd.named ? "is3d_spin_polarization_multi" : "is3d_spin_polarization", rcp, msg.c_str());
     }
-    if (int rcp = polarization()) return rcp;
-    printf("Done calculating particle spectra. Output stored in results folder. Goodbye!\n");
+    printf("Writing polarization vector to file...\n");
+    if (is3d_write_polarization("results", cfg.dimension, in.sp.n, in.grid.n_pT, in.pT.data(), in.grid.n_phi, in.phi.data(), in.grid.n_y, in.yv.data(), &po_out))
+        DIE("%s", is3d_last_error());
+    printf("polarization: species classes evaluated: %d of %d; device time: cells %.3f ms, reduce %.3f ms\n", pst.n_classes, in.sp.n,
+           pst.ms_cells, pst.ms_reduce);
+    if (rd.named) printf("polarization: %d shard%s; slowest shard's cells %.3f ms\n", (int)pss.size(), pss.size() == 1 ? "" : "s", pst.ms_cells);
+    return IS3D_OK;
+}
+
+static int run_impl(const MemSurface *mem, int variant, const RunDevices &rd, is3d_run_result *res)
+{
+    printf("iS3D-amd: MI355X-native smooth Cooper-Frye spectra (%s)\n", is3d_version());
+    RunParams params("iS3D_parameters.dat");
+    RunConfig cfg{};
+    if (int rc = parse_config(params, mem, res != nullptr, cfg)) return rc;
+    RunInputs in;
+    in.t_start = now_s();
+    // the device contexts are created while the surface is being parsed (load_inputs joins before the first device call)
+    std::vector<int> warm_list(rd.list.begin(), rd.list.end());
+    std::thread warm([&warm_list] { is3d::warm_devices(warm_list.empty() ? nullptr : warm_list.data(), (int)warm_list.size()); });
+    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } warm_joiner{warm};
+    if (int rc = load_inputs(cfg, rd, variant, mem, warm, in)) return rc;
+    const auto stage = cfg.operation == 2 ? run_sampler : cfg.operation == 0 ? run_spacetime : run_spectra;
+    if (int rc = stage(cfg, in, rd, params, res)) return rc;
+    if (int rc = run_polarization(cfg, in, rd, params, res)) return rc;
+    fputs(cfg.operation == 2   ? "Done sampling particles. Output stored in results folder. Goodbye!\n"
+          : cfg.operation == 0 ? "Done calculating spacetime distributions. Output stored in results/spacetime_distribution. Goodbye!\n"
+                               : "Done calculating particle spectra. Output stored in results folder. Goodbye!\n", stdout);
     return IS3D_OK;
 }
 
@@ -949,7 +948,8 @@ extern "C" int is3d_run_particlization_on(const is3d_cells *surface, const doubl
     if (result) memset(result, 0, sizeof *result);
     RunDevices rd;
     if (int rc = parse_run_devices(devices, n_devices, reduce, rd)) return rc;
-    return run_impl(surface, x, y, kernel_variant, rd, result);
+    const MemSurface mem{surface, x, y};
+    return run_impl(surface ? &mem : nullptr, kernel_variant, rd, result);
 }
 
 extern "C" void is3d_run_result_free(is3d_run_result *r)
