@@ -912,6 +912,38 @@ cf_main_direct(const double *__restrict__ S1, const double *__restrict__ S2, con
 }
 
 // ------------------------------------------------------------------------------------------------
+// Row groups of the accumulator-relative cull (3+1D 8 x 7 tiles without baryon slots: variants 3, 5 and 6).  A term below
+// half an ulp of THE ACCUMULATOR IT IS ADDED TO cannot change it, so a row needs to be weighed against its own JT accumulators only -- not against the
+// smallest of the tile's JT x R, which in the two edge row blocks (|y| up to 5) belongs to the far-rapidity rows and keeps the near rows alive for
+// nothing.  One threshold per row would cost 12 VGPRs the SH8 kernel does not have; the rows {0,1} {2,3,4} {5,6} share one each (tools/cull_model.py:
+// 0.3939 live wave-rows against 0.3919 per row and 0.4065 per tile).  The rows of a unit are unrolled: a row test names its group's register at
+// compile time, no instruction is added.  kRowGroupCull = false puts every kernel back on the one threshold per (lane, tile).
+// ------------------------------------------------------------------------------------------------
+constexpr bool kRowGroupCull = true;
+constexpr int kCullGroups = 3;
+__host__ __device__ constexpr int cull_row_group(int r) { return r < 2 ? 0 : (r < 5 ? 1 : 2); }   // R = 7
+// thr[g] from the minimum over group g's accumulators (acc[jj * R + r]; NG == 1: over all NACC), never below `floor`; a group whose minimum is 0
+// (padded rows k >= K, nothing added yet) keeps the floor.  thr_min: the smallest of them, what the unit-level bound is held against.
+template <int NG, int NACC, int R>
+__device__ __forceinline__ void cull_refresh(const double (&acc)[NACC], int pe, double floor, double (&thr)[NG], double &thr_min)
+{
+    double m[NG];
+    bool seen[NG] = {};
+#pragma unroll
+    for (int i = 0; i < NACC; i++) {
+        const int gi = NG > 1 ? cull_row_group(i % R) : 0;
+        m[gi] = seen[gi] ? __builtin_fmin(m[gi], acc[i]) : acc[i];
+        seen[gi] = true;
+    }
+#pragma unroll
+    for (int gi = 0; gi < NG; gi++) {
+        const int e = __builtin_amdgcn_frexp_exp(m[gi]);                     // m = f 2^e, f in [0.5, 1)
+        thr[gi] = (m[gi] > 1.0e-290) ? __builtin_fmax(floor, (double)(e - 58 - pe) * 0.6931471805599453) : floor;
+        thr_min = gi ? __builtin_fmin(thr_min, thr[gi]) : thr[gi];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // cf_main_tile (variant 2, default): factorised exponential on a JT x KT tile of (phi, y) bins.
 //
 //   exp(-p.u/T) = exp(-(mT Cp_k - bmax)) * exp(pT Dp_j - bmax),   bmax = max_j pT Dp_j  (per lane, cell)
@@ -1014,7 +1046,11 @@ cf_main_tile(const double *__restrict__ TS, const double *__restrict__ lane_mT, 
     // accumulator and is skipped; min(acc) >= 2^(e-1) with e the frexp exponent of a (stale, hence still valid) minimum over
     // the lane's accumulators, refreshed once per batch.  On config 3 this culls 62 % of the wave-rows instead of 27 %.
     constexpr bool RELCULL = OUTFLOW && REG;
-    double cull_thr = -745.2;
+    // 3+1D, rows read when evaluated (variant 3): one threshold per row group (cull_refresh); every other instantiation one per (lane, tile)
+    constexpr int NG = (kRowGroupCull && RELCULL && DIM3 && LAZY && !BARYON && R == 7) ? kCullGroups : 1;
+    double cull_thr[NG], cull_min = -745.2;   // cull_min: the smallest of the group thresholds (unit-level test)
+#pragma unroll
+    for (int i = 0; i < NG; i++) cull_thr[i] = -745.2;
     // the lane's own bound on the scaled p.dsigma: pds <= max(mT/mTmax, pT/pTmax) < 2^pe (pe <= 0, from the plan), in place of pds <= 1
     const int pe = (RELCULL && lane_pe) ? lane_pe[l] : 0;
     auto process_unit = [&](const double *U) {
@@ -1023,7 +1059,7 @@ cf_main_tile(const double *__restrict__ TS, const double *__restrict__ lane_mT, 
             // roundings are monotone), so if that bound is below the threshold for the whole wave every row would be culled:
             // skip the unit's header work (JT exponentials) and its R row exponentials as well
             const double eu = __dsub_rn(__dmul_rn(pT, U[3]), __dmul_rn(mT, U[7]));   // the roundings of the row test, no contraction
-            if (g.zskip && __all(eu < cull_thr)) { n_rows += R; n_dead += R; return; }
+            if (g.zskip && __all(eu < cull_min)) { n_rows += R; n_dead += R; return; }
         }
         double pTB[JT], pTD[JT], pT2g[JT], E2[JT];
         double bmax = -1.0e300;
@@ -1050,7 +1086,7 @@ cf_main_tile(const double *__restrict__ TS, const double *__restrict__ lane_mT, 
         struct RowE { double v[RW]; double mTC, E1; bool live; };
         struct RowL { const double *v; double mTC, E1; bool live; };
         using Row = typename std::conditional<LAZY, RowL, RowE>::type;
-        auto fetch = [&](Row &rw, const double *row) {
+        auto fetch = [&](Row &rw, const double *row, int r) {   // r: the row's index in the tile (3+1D; a constant once the rows are unrolled)
             if constexpr (LAZY) rw.v = row;
             else {
 #pragma unroll
@@ -1058,7 +1094,7 @@ cf_main_tile(const double *__restrict__ TS, const double *__restrict__ lane_mT, 
             }
             rw.mTC = mT * row[1];
             const double earg = BARYON ? (bmax - rw.mTC) + baB : bmax - rw.mTC;
-            rw.live = !(g.zskip && __all(earg < cull_thr));
+            rw.live = !(g.zskip && __all(earg < cull_thr[NG > 1 ? cull_row_group(r) : 0]));
             n_rows += 1;
             n_dead += rw.live ? 0 : 1;
             rw.E1 = exp_p9(earg);
@@ -1104,11 +1140,11 @@ cf_main_tile(const double *__restrict__ TS, const double *__restrict__ lane_mT, 
         };
         const double *rows = U + HDR;
         Row cur, nxt;
-        if constexpr (DIM3 || R > 32) fetch(cur, rows);
+        if constexpr (DIM3 || R > 32) fetch(cur, rows, 0);
         if (DIM3) {
 #pragma unroll
             for (int r = 0; r < R; r++) {
-                if (r + 1 < R) fetch(nxt, rows + (r + 1) * RW);
+                if (r + 1 < R) fetch(nxt, rows + (r + 1) * RW, r + 1);
                 if (cur.live) evals(cur, r);
                 if (r + 1 < R) cur = nxt;
             }
@@ -1128,7 +1164,7 @@ cf_main_tile(const double *__restrict__ TS, const double *__restrict__ lane_mT, 
                 rw.mTC = mT * row[1];
                 const double earg = BARYON ? (bmax - rw.mTC) + baB : bmax - rw.mTC;
                 n_rows += 1;
-                if (g.zskip && __all(earg < cull_thr)) { n_dead += 1; continue; }
+                if (g.zskip && __all(earg < cull_thr[0])) { n_dead += 1; continue; }
                 rw.live = true;
                 rw.E1 = exp_p9(earg);
                 evals(rw, 0);
@@ -1140,9 +1176,9 @@ cf_main_tile(const double *__restrict__ TS, const double *__restrict__ lane_mT, 
             // behind the buffer); it is never evaluated.
 #pragma clang loop unroll(disable)
             for (int r = 0; r + 1 < R; r += 2) {
-                fetch(nxt, rows + (r + 1) * RW);
+                fetch(nxt, rows + (r + 1) * RW, 0);
                 if (cur.live) evals(cur, 0);
-                fetch(cur, rows + (r + 2) * RW);
+                fetch(cur, rows + (r + 2) * RW, 0);
                 if (nxt.live) evals(nxt, 0);
             }
             if (R & 1) {
@@ -1173,13 +1209,7 @@ cf_main_tile(const double *__restrict__ TS, const double *__restrict__ lane_mT, 
                     const int nu = min(UB, n_units - ib * UB);
                     const double *base = (const double *)lbuf[ib & 1] + sub_off;
                     for (int u = 0; u < nu; u += S) { process_unit(base + u * REC); n_calls++; }
-                    if (RELCULL && g.zskip == 2 && (((ib + 1) & ib) == 0 || (ib & 31) == 31)) {
-                        double m = acc[0];
-#pragma unroll
-                        for (int i = 1; i < NACC; i++) m = __builtin_fmin(m, acc[i]);
-                        const int e = __builtin_amdgcn_frexp_exp(m);
-                        cull_thr = (m > 1.0e-290) ? __builtin_fmax(-745.2, (double)(e - 58 - pe) * 0.6931471805599453) : -745.2;
-                    }
+                    if (RELCULL && g.zskip == 2 && (((ib + 1) & ib) == 0 || (ib & 31) == 31)) cull_refresh<NG, NACC, R>(acc, pe, -745.2, cull_thr, cull_min);
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
@@ -1220,13 +1250,7 @@ cf_main_tile(const double *__restrict__ TS, const double *__restrict__ lane_mT, 
                 for (int u = 0; u < nu; u += S) { process_unit(base + u * REC); n_calls++; }   // nu is a multiple of S (plan)
                 // the threshold follows log2 of the accumulators, which grow about linearly with the cells seen: refresh after batches
                 // 0, 1, 3, 7, 15, ... and every 32nd
-                if (RELCULL && g.zskip == 2 && (((ib + 1) & ib) == 0 || (ib & 31) == 31)) {
-                    double m = acc[0];
-#pragma unroll
-                    for (int i = 1; i < NACC; i++) m = __builtin_fmin(m, acc[i]);
-                    const int e = __builtin_amdgcn_frexp_exp(m);                     // m = f 2^e, f in [0.5, 1)
-                    cull_thr = (m > 1.0e-290) ? __builtin_fmax(-745.2, (double)(e - 58 - pe) * 0.6931471805599453) : -745.2;
-                }
+                if (RELCULL && g.zskip == 2 && (((ib + 1) & ib) == 0 || (ib & 31) == 31)) cull_refresh<NG, NACC, R>(acc, pe, -745.2, cull_thr, cull_min);
             }
             if (!EARLY) {
 #pragma unroll
@@ -1381,7 +1405,13 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
     constexpr bool RELCULL = OUTFLOW && REG;      // accumulator-relative culling, see cf_main_tile
     // surface-relative cull: the threshold never falls below what the partial spectrum of the chunks that ran first allows (cf_cull_floor)
     const double thr_floor = (RELCULL && cull_floor && g.zskip == 2) ? cull_floor[(int64_t)s_tile * g.Lpad + l] : -745.2;
-    double cull_thr = thr_floor;
+    // One threshold per row group (cull_refresh) in the SH8 kernels (variants 6, 10, 12) and the hand-pipelined variant 5; the round-5 form (variant 13,
+    // with it variant 11) and the baryon records keep one per (lane, tile): the in-tree baseline of the rule, and 256 VGPRs with none to spare.
+    // The floor is per (lane, tile) in either case and holds for every group.
+    constexpr int NG = (kRowGroupCull && RELCULL && !BARYON && !RAWH && R == 7 && (SH8 || MODE == 0)) ? kCullGroups : 1;
+    double cull_thr[NG], cull_min = thr_floor;    // cull_min: the smallest of the group thresholds (unit-level test)
+#pragma unroll
+    for (int i = 0; i < NG; i++) cull_thr[i] = thr_floor;
     const int pe = (RELCULL && lane_pe) ? lane_pe[l] : 0;
 
     unsigned long long pf_stage = 0, pf_wait = 0, pf_dead = 0, pf_live = 0, pf_hdr = 0, pf_nd = 0, pf_nl = 0, pf_thr = 0, pf_t0 = 0, pf_u0 = 0, pf_vm = 0, pf_pro = 0, pf_mid = 0, pf_ts = 0;
@@ -1404,9 +1434,22 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
         {
             double eu = __dsub_rn(bmax, __dmul_rn(mT, cminv));                           // unit-level cull, as in cf_main_tile
             if (BARYON) eu += baB;
-            const bool dead = __all(eu < cull_thr);
+            const bool dead = __all(eu < cull_min);   // a unit dead under the smallest group threshold has every row dead
             if (g.zskip && dead) { n_rows += R; n_dead += R; return false; }
         }
+        // MODE 1: liveness of the R rows (3 instructions a row), each against its own group's threshold
+        auto row_mask = [&]() -> unsigned {
+            unsigned live = (1u << R) - 1u;
+            if (g.zskip) {
+                live = 0;
+#pragma unroll
+                for (int r = 0; r < R; r++) {
+                    const double earg = BARYON ? (bmax - mT * cn[r]) + baB : bmax - mT * cn[r];
+                    live |= __all(earg < cull_thr[NG > 1 ? cull_row_group(r) : 0]) ? 0u : (1u << r);
+                }
+            }
+            return live;
+        };
         if constexpr (ROWMASK && !SH8) {
             // live unit: the C'_k are wave-uniform and stay live through the rows (each row's exponential starts from them before the
             // row's own reads return): moved to SGPRs, no VGPR is free there.  (SH8: the 32 SGPRs of D'_j and gamma_j leave no room for these 14 --
@@ -1437,11 +1480,11 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
             E2[jj] = E2G ? e2cur[jj] : tab[jj * kE2Stride];
         }
         struct Row { const double *v; double mTC, E1; bool live; };
-        auto fetch = [&](Row &rw, const double *row) {
+        auto fetch = [&](Row &rw, const double *row, int r) {
             rw.v = row;
             rw.mTC = mT * row[1];
             const double earg = BARYON ? (bmax - rw.mTC) + baB : bmax - rw.mTC;
-            rw.live = !(g.zskip && __all(earg < cull_thr));
+            rw.live = !(g.zskip && __all(earg < cull_thr[NG > 1 ? cull_row_group(r) : 0]));
             n_rows += 1;
             n_dead += rw.live ? 0 : 1;
             rw.E1 = exp_p9(earg);   // degree 9, one-fma reduction (cf_math.h): 7e-14, two instructions fewer per row
@@ -1487,15 +1530,11 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
             // Liveness of the R rows first (3 instructions a row), then only the live rows pay their exponential: a dead row inside
             // a live unit costs its test, not the 15-instruction exponential the row pipeline below computes for every row.
             // Within a live row the exponential's dependent chain overlaps the row's E1-independent work (x, p.dsigma, br).
-            unsigned live = (1u << R) - 1u;
-            if (g.zskip) {
-                live = 0;
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    const double earg = BARYON ? (bmax - mT * cn[r]) + baB : bmax - mT * cn[r];
-                    live |= __all(earg < cull_thr) ? 0u : (1u << r);
-                }
-            }
+            const unsigned live = row_mask();
+            // Row groups: a unit passes the unit bound against the SMALLEST group threshold, its rows are each held to their own group's -- the mask can
+            // come out empty; such a unit leaves here, its rows counted as below.  (Leaving in front of the header -- mask first, the 32 v_readfirstlane
+            // behind the exit -- was measured: the same time with culling on, 1.9 % slower with culling off, LABBOOK round 24.)
+            if (NG > 1 && live == 0) { n_rows += R; n_dead += R; return false; }
             n_rows += R;
             n_dead += R - __builtin_popcount(live);
             if constexpr (PROF) pf_hdr += clock64() - pf_u0;
@@ -1514,10 +1553,10 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
             }
         } else {
             Row cur, nxt;
-            fetch(cur, rows);
+            fetch(cur, rows, 0);
 #pragma unroll
             for (int r = 0; r < R; r++) {
-                if (r + 1 < R) fetch(nxt, rows + (r + 1) * RW);
+                if (r + 1 < R) fetch(nxt, rows + (r + 1) * RW, r + 1);
                 if (cur.live) evals(cur, r);
                 if (r + 1 < R) cur = nxt;
             }
@@ -1588,13 +1627,7 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
         if constexpr (PROF) pa = clock64();
         // the threshold follows log2 of the accumulators, which grow about linearly with the cells seen: refresh after batches
         // 0, 1, 3, 7, 15, ... and every 64th
-        if (RELCULL && g.zskip == 2 && (((ib + 1) & ib) == 0 || (ib & 63) == 63)) {
-            double m = acc[0];
-#pragma unroll
-            for (int i = 1; i < NACC; i++) m = __builtin_fmin(m, acc[i]);
-            const int e = __builtin_amdgcn_frexp_exp(m);
-            cull_thr = (m > 1.0e-290) ? __builtin_fmax(thr_floor, (double)(e - 58 - pe) * 0.6931471805599453) : thr_floor;
-        }
+        if (RELCULL && g.zskip == 2 && (((ib + 1) & ib) == 0 || (ib & 63) == 63)) cull_refresh<NG, NACC, R>(acc, pe, thr_floor, cull_thr, cull_min);
         if constexpr (PROF) pf_thr += clock64() - pa;
     };
     {

@@ -8,6 +8,12 @@ acc[lane][j][k] (equilibrium integrand, u = 1/2), and counts the (wave, cell, ti
   A  the kernel's rule: one threshold per (lane, tile) from the minimum over the tile's JT x R accumulators
   B  one threshold per (lane, tile, row): minimum over the row's JT accumulators
   C  per (lane, j, k): a row is live if any of its JT terms can reach half an ulp of ITS accumulator (needs E2_j per lane)
+  G  (--row-groups 2,3,2) one threshold per (lane, tile, group of consecutive rows): minimum over the group's accumulators -- the rule of the
+     kernels since round 24 (cull_refresh, cf_kernels.hip).  The unit-level test of the kernel is held against the smallest group threshold; the
+     model's "live units" are units with at least one live row, which is what the empty-mask exit of the kernel makes of them.
+
+--seed / --chunks: another seeded surface, cut into equal consecutive cell chunks with accumulators of their own (the counts are summed) -- e.g. the
+surface tests/test_gpu_parity.py::test_row_culling_changes_no_bit pins its cross-variant counts on: --cells 2000 --seed 80 --chunks 3.
 
 Thresholds use the final accumulators of the chunk (the best any stale running minimum can do), so the live fractions are
 lower bounds; rule A's number is compared with what the device reports (status.n_wave_rows_culled).
@@ -67,7 +73,13 @@ def main():
                          "would hold if cf_prep binned the cells by eta")
     ap.add_argument("--origin", default="0", help="row-block origin: an integer row, or 'eta': the row nearest the bin's eta minus R // 2, so that the "
                                                   "live window of the chunk's cells sits in one block (blocks then cover rows origin + R m, clipped to the grid)")
+    ap.add_argument("--row-groups", default=None, help="rule G: sizes of the groups of consecutive rows of a row block that share a threshold, e.g. 2,3,2")
+    ap.add_argument("--seed", type=int, default=None, help="seed of the surface (default: the config-3 seed)")
+    ap.add_argument("--chunks", type=int, default=1, help="cut the cells into this many equal consecutive chunks, each with its own accumulators")
     a = ap.parse_args()
+    groups = [int(x) for x in a.row_groups.split(",")] if a.row_groups else None
+    if groups and sum(groups) != a.R:
+        ap.error("--row-groups must add up to R")
     g = inputs.grid()
     sp = inputs.species("urqmd")
     pT, phi, yv = g["pT"], g["phi"], g["y"]
@@ -98,10 +110,10 @@ def main():
     pe = np.minimum(pe, 0)
 
     if a.eta_bin is None:
-        s = synth.synth_surface(a.cells, 3, first_cell=a.first)
+        s = synth.synth_surface(a.cells, 3, seed=a.seed, first_cell=a.first)
     else:
         hw = 0.5 * (yv[1] - yv[0])
-        big = synth.synth_surface(a.cells * 24, 3, first_cell=a.first)
+        big = synth.synth_surface(a.cells * 24, 3, seed=a.seed, first_cell=a.first)
         sel = np.nonzero(np.abs(big["eta"] - a.eta_bin) < hw)[0][:a.cells]
         s = {k: v[sel] for k, v in big.items()}
         a.cells = len(sel)
@@ -129,57 +141,69 @@ def main():
     jt_n, kt_n = (J + JT - 1) // JT, len(blocks)
     C = a.cells
 
-    # accumulators acc[l][j][k] (equilibrium, u = 1/2) and the exponent bounds
-    acc = np.zeros((L, J, K))
-    cb = 64
-    for c0 in range(0, C, cb):
-        c1 = min(C, c0 + cb)
-        x = mT[:, None, None, None] * Cp[None, c0:c1, None, :] - pTl[:, None, None, None] * Dp[None, c0:c1, :, None]   # [l][c][j][k]
-        pds = np.maximum(mT[:, None, None, None] * Ak[None, c0:c1, None, :] + pTl[:, None, None, None] * Bj[None, c0:c1, :, None], 0.0) * psc
-        acc += (pds * np.exp(-x)).sum(axis=1) * 0.5
-    with np.errstate(divide="ignore"):
-        e_acc = np.where(acc > 1e-290, np.floor(np.log2(np.maximum(acc, 1e-300))) + 1, -np.inf)    # frexp exponent
-    ln2 = 0.6931471805599453
-
-    def thr_from(e):   # e: frexp exponent(s) of a lower bound on the accumulators a row adds to
-        return np.maximum(-745.2, (e - 58 - pe.reshape((-1,) + (1,) * (e.ndim - 1))) * ln2)
-
-    live = {k: 0 for k in "ABC"}
-    unit_live = {k: 0 for k in "ABC"}
-    lane_live = {k: 0 for k in "AB"}
-    per_kt = {k: np.zeros(kt_n) for k in "AB"}
+    rules = "ABCG" if groups else "ABC"
+    live = {k: 0 for k in rules}
+    unit_live = {k: 0 for k in rules}
+    lane_live = {k: 0 for k in rules if k != "C"}
+    per_kt = {k: np.zeros(kt_n) for k in rules if k != "C"}
     total_rows = 0
-    for jt in range(jt_n):
-        js = slice(jt * JT, min(J, (jt + 1) * JT))
-        Dmax = Dp[:, js].max(axis=1)                                     # [c]
-        for kt in range(kt_n):
-            ks = slice(blocks[kt][0], blocks[kt][1])
-            earg = pTl[:, None, None] * Dmax[None, :, None] - mT[:, None, None] * Cp[None, :, ks]      # [l][c][r]
-            eA = e_acc[:, js, ks].min(axis=(1, 2))                        # [l]
-            eB = e_acc[:, js, ks].min(axis=1)                             # [l][r]
-            thrA = thr_from(eA)[:, None, None]
-            thrB = thr_from(eB)[:, None, :]
-            lvA = earg >= thrA
-            lvB = earg >= thrB
-            # C: exists j: earg + log E2_j >= thr(acc[j][k]);  log E2_j = pT (Dp_j - Dmax)
-            lvC = np.zeros_like(lvA)
-            for j in range(js.start, js.stop):
-                thrC = thr_from(e_acc[:, j, ks])[:, None, :]
-                lE2 = pTl[:, None] * (Dp[None, :, j] - Dmax[None, :])
-                lvC |= (earg + lE2[:, :, None]) >= thrC
-            nr = ks.stop - ks.start
-            total_rows += nw * C * nr
-            for key, lv in (("A", lvA), ("B", lvB), ("C", lvC)):
-                pad = np.zeros((nw * 64 - L,) + lv.shape[1:], dtype=bool)
-                w = np.concatenate([lv, pad]).reshape(nw, 64, C, nr).any(axis=1)    # [w][c][r]
-                live[key] += int(w.sum())
-                unit_live[key] += int(w.any(axis=2).sum())
-                if key in per_kt:
-                    per_kt[key][kt] += w.sum() * R / nr
-                    lane_live[key] += int(lv.sum())
+    for ich in range(a.chunks):
+        lo, hi = C * ich // a.chunks, C * (ich + 1) // a.chunks
+        Cc = hi - lo
+        # accumulators acc[l][j][k] (equilibrium, u = 1/2) and the exponent bounds
+        acc = np.zeros((L, J, K))
+        cb = 64
+        for c0 in range(lo, hi, cb):
+            c1 = min(hi, c0 + cb)
+            x = mT[:, None, None, None] * Cp[None, c0:c1, None, :] - pTl[:, None, None, None] * Dp[None, c0:c1, :, None]   # [l][c][j][k]
+            pds = np.maximum(mT[:, None, None, None] * Ak[None, c0:c1, None, :] + pTl[:, None, None, None] * Bj[None, c0:c1, :, None], 0.0) * psc
+            acc += (pds * np.exp(-x)).sum(axis=1) * 0.5
+        with np.errstate(divide="ignore"):
+            e_acc = np.where(acc > 1e-290, np.floor(np.log2(np.maximum(acc, 1e-300))) + 1, -np.inf)    # frexp exponent
+        ln2 = 0.6931471805599453
+
+        def thr_from(e):   # e: frexp exponent(s) of a lower bound on the accumulators a row adds to
+            return np.maximum(-745.2, (e - 58 - pe.reshape((-1,) + (1,) * (e.ndim - 1))) * ln2)
+
+        for jt in range(jt_n):
+            js = slice(jt * JT, min(J, (jt + 1) * JT))
+            Dmax = Dp[lo:hi, js].max(axis=1)                                   # [c]
+            for kt in range(kt_n):
+                ks = slice(blocks[kt][0], blocks[kt][1])
+                earg = pTl[:, None, None] * Dmax[None, :, None] - mT[:, None, None] * Cp[None, lo:hi, ks]     # [l][c][r]
+                eA = e_acc[:, js, ks].min(axis=(1, 2))                        # [l]
+                eB = e_acc[:, js, ks].min(axis=1)                             # [l][r]
+                thrA = thr_from(eA)[:, None, None]
+                thrB = thr_from(eB)[:, None, :]
+                lvA = earg >= thrA
+                lvB = earg >= thrB
+                if groups:   # G: the rows of the block in consecutive groups, a threshold each (a clipped block keeps the groups' positions)
+                    eG = np.empty_like(eB)
+                    r0 = 0
+                    for gs in groups:
+                        if r0 < eB.shape[1]:
+                            eG[:, r0:r0 + gs] = eB[:, r0:r0 + gs].min(axis=1, keepdims=True)
+                        r0 += gs
+                    lvG = earg >= thr_from(eG)[:, None, :]
+                # C: exists j: earg + log E2_j >= thr(acc[j][k]);  log E2_j = pT (Dp_j - Dmax)
+                lvC = np.zeros_like(lvA)
+                for j in range(js.start, js.stop):
+                    thrC = thr_from(e_acc[:, j, ks])[:, None, :]
+                    lE2 = pTl[:, None] * (Dp[None, lo:hi, j] - Dmax[None, :])
+                    lvC |= (earg + lE2[:, :, None]) >= thrC
+                nr = ks.stop - ks.start
+                total_rows += nw * Cc * nr
+                for key, lv in (("A", lvA), ("B", lvB), ("C", lvC)) + ((("G", lvG),) if groups else ()):
+                    pad = np.zeros((nw * 64 - L,) + lv.shape[1:], dtype=bool)
+                    w = np.concatenate([lv, pad]).reshape(nw, 64, Cc, nr).any(axis=1)    # [w][c][r]
+                    live[key] += int(w.sum())
+                    unit_live[key] += int(w.any(axis=2).sum())
+                    if key in per_kt:
+                        per_kt[key][kt] += w.sum() * R / nr
+                        lane_live[key] += int(lv.sum())
     units = nw * C * jt_n * kt_n
-    print("cells %d  lanes %d (%d waves)  tiles %d x %d  row blocks %s  scale 2^-%d" % (C, L, nw, jt_n, kt_n, blocks, e_sc))
-    for key in "ABC":
+    print("cells %d in %d chunk(s)  lanes %d (%d waves)  tiles %d x %d  row blocks %s  scale 2^-%d" % (C, a.chunks, L, nw, jt_n, kt_n, blocks, e_sc))
+    for key in rules:
         print("rule %s: live wave-rows %.4f  live units %.4f  rows per live unit %.2f" % (
             key, live[key] / total_rows, unit_live[key] / units, live[key] / max(unit_live[key], 1)))
     # issued fp64-VALU instructions per (wave, cell, phi tile) under rule A, priced with the instruction counts of cf_main_tile3e (DESIGN.md
@@ -189,7 +213,10 @@ def main():
     dead_rows_in_live_units = lu * R - lr
     instr = lr * (8 * 14 + 25) + lu * 59 + max(dead_rows_in_live_units, 0) * 3 + (units - lu) * 3
     print("rule A: modelled issued instructions per (wave, cell, phi tile): %.1f   (units per cell and tile: %d)" % (instr / (nw * C * jt_n), kt_n))
-    for key in "AB":
+    if groups:
+        ca, cg = 1.0 - live["A"] / total_rows, 1.0 - live["G"] / total_rows
+        print("rule G (row groups %s): culled wave-rows %.4f against A's %.4f: %+.2f %% relative" % (a.row_groups, cg, ca, 100.0 * (cg - ca) / ca))
+    for key in per_kt:
         print("rule %s: live (lane, row) pairs %.4f;  live wave-rows by row block: %s" % (
             key, lane_live[key] / (L * C * jt_n * K), np.round(per_kt[key] / (nw * C * jt_n * R), 4)))
 
