@@ -77,7 +77,10 @@ struct PrepParams {
 // ---- tiled stream TS (variants >= 2): what one workgroup of the main kernel streams through LDS ----
 // unit record (REC = 4*JT + R*(4+JT) doubles) for tile (jt, rb) of one cell:
 //   header  jj < JT : {B_j, Dp_j, gamma_j, x}                     j = jt*JT + jj (clamped to J-1); x: 3+1D records without baryon
-//                     slots carry max_j Dp_j of the tile in x of jj = 0 and min_k Cp_k of the unit's rows in x of jj = 1 (unit-level cull)
+//                     slots carry max_j Dp_j of the tile in x of jj = 0 and min_k Cp_k of the unit's rows in x of jj = 1 (unit-level cull),
+//                     and (JT >= 3) in x of jj = 2 lambda_u = log(mTmax max_k |A_k| + pTmax max_j |B_j|) of the unit's own scaled A_k, B_j,
+//                     rounded up and clamped to [-kPdsLambdaMax, 0]: |p.dsigma| <= max(mT/mTmax, pT/pTmax) e^lambda_u in this unit (the
+//                     accumulator-relative row cull adds it to the exponent it tests); x of jj >= 3 is zero
 //   row     r  < R  : {A_k, Cp_k, alpha_k, W_k, beta_{j0..j0+JT-1,k}}   k = rb*R + r; rows past K are
 //                     neutral padding (A = W = 0, Cp copied from row K-1, alpha = beta = 0)
 // 3+1D: stream s = jt*rblocks + rb, one unit per cell:        TS[(s*n_cells + cell)*REC]
@@ -97,6 +100,8 @@ struct PrepParams {
 //   TE[((jt*n_cells + cell)*JT + jj)*kE2Stride + ipT]   (pT fastest: the lanes' LDS reads of one jj hit consecutive words;
 //                                                        grids of up to kE2Stride pT values, else the plan falls back to variant 3)
 constexpr int kE2Stride = 32;
+// Range of lambda_u (above): 40 ln 2, more than any surface can use (a term 2^-40 of the bound is below every ulp the cull weighs) and finite for S_u = 0.
+constexpr double kPdsLambdaMax = 27.725887222397812;
 inline int unit_rec_doubles(int JT, int R, int baryon = 0) { return baryon ? 4 * JT + 2 + R * (6 + JT) : 4 * JT + R * (4 + JT); }
 
 // ---- main kernel geometry ----

@@ -160,11 +160,12 @@ __global__ void __launch_bounds__(kPrepThreads) cf_prep(PrepParams p)
     double *l_V1 = lk + 7 * CK, *l_Lk = lk + 8 * CK, *l_V2 = lj + 6 * CJ, *l_L2 = lj + 7 * CJ;   // include_baryon only
     double *l_bD = lj + NJA * CJ;              // [CB][jtiles] max_j Dp_j of a phi tile   (unit-level cull bounds, 3+1D)
     double *l_bC = l_bD + CB * ((J + 1) / 2);  // [CB][rblocks] min_k Cp_k of a row block
+    double *l_bL = l_bC + CB * K;              // [CB][jtiles][rblocks] lambda_u: log of the unit's own bound on the scaled p.dsigma (tiled 3+1D)
     // element descriptors of a unit record (tiled stream), one int2 per record element, filled once per workgroup (below)
     // 16-byte aligned (two descriptors per read): an even double offset from the block's base -- NOT a round trip through uintptr_t, which
     // loses the LDS address space: the descriptor reads became flat_load + s_waitcnt vmcnt(0), i.e. every trip of the writer waited for
     // all of the wave's outstanding stores (gfx9 counts stores in vmcnt)
-    int2 *desc = (int2 *)(lds + (((int)((p.dim3 ? l_bC + CB * K : l_bD) - lds) + 1) & ~1));
+    int2 *desc = (int2 *)(lds + (((int)((p.dim3 ? l_bL + (p.tiled ? CB * p.jtiles * p.rblocks : 0) : l_bD) - lds) + 1) & ~1));
 
     const int tid = threadIdx.x;
     for (int i = tid; i < nT; i += kPrepThreads) {
@@ -179,7 +180,7 @@ __global__ void __launch_bounds__(kPrepThreads) cf_prep(PrepParams p)
     // Record-element descriptors (tiled stream).  Every element of a unit record is a copy of one LDS double (possibly times the
     // p.dsigma scale), an exact zero, or a beta_jk; WHICH is the same for every unit, so the decode is done once:
     //   x: bits 0-15 offset of the source array in the LDS block | 16-18 how the index continues (0: c J + j, 1: c K + k, 2: c jtiles + jt,
-    //      3: c rblocks + rb, 4: c sizeof(CellScal)/8) | 19 scaled | 20 beta | 21 zero when the row is padding (k >= K) | 22 always zero
+    //      3: c rblocks + rb, 4: c sizeof(CellScal)/8, 5: (c jtiles + jt) rblocks + rb) | 19 scaled | 20 beta | 21 zero when the row is padding (k >= K) | 22 always zero
     //   y: jj (header entry / beta column) | r << 16 (row)
     // (As nested conditionals inside the writer loop the decode compiled to ~30 exec-masked branches with an LDS round trip in each arm:
     // 1 400 cycles per 64 elements, 91 % of the 2+1D prep kernel.)
@@ -189,7 +190,7 @@ __global__ void __launch_bounds__(kPrepThreads) cf_prep(PrepParams p)
         const int HDR = 4 * JT + (p.baryon ? 2 : 0), RS = p.baryon ? 6 : 4, RWD = RS + JT, REC = HDR + R * RWD;
         const int o_A = (int)(l_A - lds), o_Cp = (int)(l_Cp - lds), o_al = (int)(l_al - lds), o_W = (int)(l_W - lds), o_Lk = (int)(l_Lk - lds);
         const int o_B = (int)(l_B - lds), o_Dp = (int)(l_Dp - lds), o_ga = (int)(l_ga - lds), o_L2 = (int)(l_L2 - lds);
-        const int o_bD = (int)(l_bD - lds), o_bC = (int)(l_bC - lds);
+        const int o_bD = (int)(l_bD - lds), o_bC = (int)(l_bC - lds), o_bL = (int)(l_bL - lds);
         const int o_alphaB = (int)(&cs[0].alphaB - lds);
         constexpr int ZERO = 1 << 22, PADZ = 1 << 21, BETA = 1 << 20, SCALED = 1 << 19;
         for (int e = tid; e < REC; e += kPrepThreads) {
@@ -200,6 +201,7 @@ __global__ void __launch_bounds__(kPrepThreads) cf_prep(PrepParams p)
                 x = f == 0 ? (o_B | SCALED) : f == 1 ? o_Dp : f == 2 ? o_ga : (p.baryon ? o_L2 : ZERO);
                 if (unit_bounds && !p.baryon && e == 3) x = o_bD | (2 << 16);         // max_j D'_j of the tile: bmax = pT Dmax
                 else if (unit_bounds && !p.baryon && e == 7) x = o_bC | (3 << 16);    // min_k C'_k of the unit's rows
+                else if (unit_bounds && !p.baryon && e == 11) x = o_bL | (5 << 16);   // lambda_u: the unit's own p.dsigma bound (JT >= 3)
             } else if (e < HDR) {
                 x = (e == 4 * JT) ? (o_alphaB | (4 << 16)) : ((unit_bounds && e == 4 * JT + 1) ? (o_bD | (2 << 16)) : ZERO);
             } else {
@@ -417,6 +419,24 @@ __global__ void __launch_bounds__(kPrepThreads) cf_prep(PrepParams p)
                 for (int q2 = 0; q2 < R; q2++) v = fmin(v, l_Cp[c * K + min(rb * R + q2, K - 1)]);   // padding rows repeat row K-1
                 l_bC[idx] = v;
             }
+            // lambda_u = log of S_u = mTmax max_k |A_k| + pTmax max_j |B_j| (scaled as the record holds them), the unit's own bound on the
+            // scaled p.dsigma: |p.dsigma| <= max(mT/mTmax, pT/pTmax) S_u.  Rounded up, clamped to [-kPdsLambdaMax, 0]; S_u = 0 gives the lower end,
+            // a NaN or S_u >= 1 gives 0 (the surface-wide bound the row tests had before).  "B" records have no slot for it.
+            if (!p.baryon && JT >= 3) {
+                const int upc = p.jtiles * p.rblocks;
+                const double psc_u = pds_scale(p.pds_bound, nullptr);
+                for (int idx = tid; idx < ncb * upc; idx += kPrepThreads) {
+                    const int c = idx / upc, u = idx - c * upc, jt = u / p.rblocks, rb = u - jt * p.rblocks;
+                    double a = 0.0, b = 0.0;
+                    for (int q2 = 0; q2 < R; q2++) a = fmax(a, fabs(l_A[c * K + min(rb * R + q2, K - 1)]));
+                    for (int q2 = 0; q2 < JT; q2++) b = fmax(b, fabs(l_B[c * J + min(jt * JT + q2, J - 1)]));
+                    const double S = (p.mTmax * a + p.pTmax * b) * psc_u;
+                    double lam = 0.0;
+                    if (S == 0.0) lam = -kPdsLambdaMax;
+                    else if (S > 0.0 && S < 1.0) lam = fmin(fmax(log(S) + 2.0e-9, -kPdsLambdaMax), 0.0);
+                    l_bL[idx] = lam;
+                }
+            }
             __syncthreads();
         }
         // phase 1 of the workgroup's next batch, on wave 0, under the other waves' record writing
@@ -490,9 +510,9 @@ __global__ void __launch_bounds__(kPrepThreads) cf_prep(PrepParams p)
                 RawRule u;
                 const int jj = d.y & 0xffff, r = d.y >> 16, msel = (d.x >> 16) & 7;
                 u.off = (d.x & 0xffff) + (msel == 4 ? cs_cur : 0); u.r = r;
-                u.mc = msel == 0 ? J : msel == 1 ? K : msel == 2 ? p.jtiles : msel == 3 ? p.rblocks : (int)(sizeof(CellScal) / sizeof(double));
-                u.a = msel == 0 ? JT : msel == 2 ? 1 : 0;
-                u.b = msel == 1 ? R : msel == 3 ? 1 : 0;
+                u.mc = msel == 0 ? J : msel == 1 ? K : msel == 2 ? p.jtiles : msel == 3 ? p.rblocks : msel == 5 ? p.jtiles * p.rblocks : (int)(sizeof(CellScal) / sizeof(double));
+                u.a = msel == 0 ? JT : msel == 2 ? 1 : msel == 5 ? p.rblocks : 0;
+                u.b = msel == 1 ? R : (msel == 3 || msel == 5) ? 1 : 0;
                 u.q = msel == 0 ? jj : msel == 1 ? r : 0;
                 u.lim = msel == 0 ? J - 1 : msel == 1 ? K - 1 : 0x7fffffff;
                 u.zero = (d.x >> 22) & 1; u.padz = (d.x >> 21) & 1;
@@ -674,7 +694,7 @@ __global__ void __launch_bounds__(kPrepThreads) cf_prep(PrepParams p)
                         double *o = p.TS + unit * REC;
                         // one LDS round trip per 64 elements: the descriptor, then the source double next to the six reads of a
                         // (clamped) beta_of; no divergent branch
-                        const int cJ = c * J, cK = c * K, cT = c * p.jtiles + jt, cR = c * p.rblocks + rb, cS = cs_cur + c * (int)(sizeof(CellScal) / sizeof(double));
+                        const int cJ = c * J, cK = c * K, cT = c * p.jtiles + jt, cR = c * p.rblocks + rb, cU = cT * p.rblocks + rb, cS = cs_cur + c * (int)(sizeof(CellScal) / sizeof(double));
                         // two consecutive elements per lane: one 16-byte descriptor read, one 16-byte store (records are 16-byte
                         // multiples, cf_device.h), the two elements' LDS reads in flight together -- half the trips per record
                         auto element = [&](const int2 d) {
@@ -682,7 +702,7 @@ __global__ void __launch_bounds__(kPrepThreads) cf_prep(PrepParams p)
                             const int jcl = min(jt * JT + jj, J - 1);
                             const int k = rb * R + r, kcl = min(k, K - 1);
                             const int msel = (d.x >> 16) & 7;
-                            const int add = msel == 0 ? cJ + jcl : msel == 1 ? cK + kcl : msel == 2 ? cT : msel == 3 ? cR : cS;
+                            const int add = msel == 0 ? cJ + jcl : msel == 1 ? cK + kcl : msel == 2 ? cT : msel == 3 ? cR : msel == 5 ? cU : cS;
                             const bool zero = ((d.x >> 22) & 1) | (((d.x >> 21) & 1) & (k >= K));
                             const double raw = lds[zero ? 0 : (d.x & 0xffff) + add];
                             const double bet = beta_of(c, jcl, kcl);
@@ -752,13 +772,14 @@ static int prep_batch_cells(int K)
     return env ? env : kPrepCB3;
 }
 
-size_t prep_lds_bytes(int nT, int nspl, int J, int K, int baryon, int rec, int dim3)
+size_t prep_lds_bytes(int nT, int nspl, int J, int K, int baryon, int rec, int dim3, int units)
 {
     const int cb = prep_batch_cells(K);
     const int nka = baryon ? 9 : 7, nja = baryon ? 8 : 6;
     // the unit-level cull bounds ([cb][jtiles] + [cb][rblocks] <= cb ((J + 1) / 2 + K) doubles) exist for 3+1D grids only -- the kernel's
     // own predicate (p.dim3), whatever K is; a 2+1D eta table of 241 rows must not pay 8 KB for them (two workgroups per CU need <= 80 KB each)
-    const size_t bounds = dim3 ? (size_t)cb * ((J + 1) / 2 + K) : 0;
+    // + lambda_u, one double per unit of a cell (units = jtiles * rblocks of the tiled stream; 0 for the flat streams)
+    const size_t bounds = dim3 ? (size_t)cb * ((J + 1) / 2 + K + units) : 0;
     // + one int2 per element of a unit record (rec doubles; 0 for the flat streams of variant 1)
     return sizeof(double) * ((size_t)nT * (1 + 2 * nspl) + (size_t)cb * (nka * K + nja * J) + bounds + (size_t)rec + 2) + sizeof(CellScal) * cb * 2;   // + 2: descriptor alignment; two CellScal buffers
 }
@@ -780,7 +801,8 @@ hipError_t launch_prep(const PrepParams &p_in, hipStream_t stream)
         p.w0_share = w ? atoi(w) : 0;
         if (p.w0_share < 1 || p.w0_share > 100) p.w0_share = p.dim3 ? kPrepW0Share3 : kPrepW0Share2;
     }
-    size_t lds = prep_lds_bytes(p.spl.n, p.spl.nspl, p.J, p.K, p.baryon, p.tiled ? unit_rec_doubles(p.JT, p.R, p.baryon) : 0, p.dim3 ? 1 : 0);
+    size_t lds = prep_lds_bytes(p.spl.n, p.spl.nspl, p.J, p.K, p.baryon, p.tiled ? unit_rec_doubles(p.JT, p.R, p.baryon) : 0, p.dim3 ? 1 : 0,
+                                (p.tiled && p.dim3) ? p.jtiles * p.rblocks : 0);
     const bool nt = (p.dev_skip & 16) != 0;     // dev A/B (IS3D_PREP_SKIP bit 4): record stores non-temporal; default plain, see cf_prep
     if (nt) {
         if (cb == 16) hipLaunchKernelGGL((cf_prep<16, true>), dim3(grid), dim3(kPrepThreads), lds, stream, p);
@@ -920,6 +942,18 @@ cf_main_direct(const double *__restrict__ S1, const double *__restrict__ S2, con
 // compile time, no instruction is added.  kRowGroupCull = false puts every kernel back on the one threshold per (lane, tile).
 // ------------------------------------------------------------------------------------------------
 constexpr bool kRowGroupCull = true;
+// The unit's own p.dsigma bound in the tested exponent (the same kernels): the relative rule assumes pds < 2^pe, true of the
+// surface's worst cell and bin; inside one unit |pds| <= max(mT/mTmax, pT/pTmax) S_u < 2^pe e^lambda_u with lambda_u <= 0 from cf_prep (header
+// slot 11, cf_device.h), so a row is dead when earg + lambda_u is below its group's threshold.  lambda_u enters the TESTED exponent only, the
+// row exponential keeps earg: no rounding of the spectrum changes.  The exact-zero floor is no relative bound -- exp(earg) is +0 below -745.2
+// whatever pds is, and a group at the floor adds to accumulators that may be 0 -- so lambda_u must never meet a threshold that is the floor: a LANE
+// adds it (lamb, a lane mask: no VGPR) only while every one of its group thresholds is a relative bound, i.e. cull_min > -745.2; a relative bound is >= -708
+// (cull_refresh), so with lambda_u <= 0 a row that is exactly zero stays dead for that lane, and a lane outside the mask votes as before: the rule
+// culls at least the rows of the exact-zero rule and of the rule without lambda_u held to the same thresholds.  Exact-only runs (g.zskip == 1, or
+// no outflow clamp / regulate_deltaf) never leave the floor and add no lambda_u.  kPdsBoundCull = false restores pds < 2^pe everywhere.
+constexpr bool kPdsBoundCull = true;
+// the lane's vote where lambda_u (wave-uniform, an SGPR pair) is added per test: e + lam <= e, so the second test contains the first
+__device__ __forceinline__ bool cull_below(double e, double lam, bool lamb, double thr) { return (e < thr) | (lamb & (e + lam < thr)); }
 constexpr int kCullGroups = 3;
 __host__ __device__ constexpr int cull_row_group(int r) { return r < 2 ? 0 : (r < 5 ? 1 : 2); }   // R = 7
 // thr[g] from the minimum over group g's accumulators (acc[jj * R + r]; NG == 1: over all NACC), never below `floor`; a group whose minimum is 0
@@ -1048,18 +1082,24 @@ cf_main_tile(const double *__restrict__ TS, const double *__restrict__ lane_mT, 
     constexpr bool RELCULL = OUTFLOW && REG;
     // 3+1D, rows read when evaluated (variant 3): one threshold per row group (cull_refresh); every other instantiation one per (lane, tile)
     constexpr int NG = (kRowGroupCull && RELCULL && DIM3 && LAZY && !BARYON && R == 7) ? kCullGroups : 1;
-    double cull_thr[NG], cull_min = -745.2;   // cull_min: the smallest of the group thresholds (unit-level test)
+    // the same kernels add the unit's lambda_u to the exponent they test (kPdsBoundCull), per lane and only while all its thresholds are relative
+    constexpr bool PDSB = kPdsBoundCull && RELCULL && DIM3 && LAZY && !BARYON && R == 7 && JT >= 3;
+    constexpr double thr_floor = -745.2;
+    bool lamb = false;
+    double cull_thr[NG], cull_min = thr_floor;   // cull_min: the smallest of the group thresholds (unit-level test)
 #pragma unroll
-    for (int i = 0; i < NG; i++) cull_thr[i] = -745.2;
+    for (int i = 0; i < NG; i++) cull_thr[i] = thr_floor;
     // the lane's own bound on the scaled p.dsigma: pds <= max(mT/mTmax, pT/pTmax) < 2^pe (pe <= 0, from the plan), in place of pds <= 1
     const int pe = (RELCULL && lane_pe) ? lane_pe[l] : 0;
     auto process_unit = [&](const double *U) {
+        double lam = 0.0;   // wave-uniform, kept on the scalar side: the kernel has no VGPR to spare
+        if constexpr (PDSB) lam = to_sgpr(U[11]);
         if constexpr (!BARYON && DIM3 && JT >= 2) {
             // unit-level cull: earg_k = bmax - mT C'_k <= pT Dmax - mT Cmin for every row of the unit (both from cf_prep; the
             // roundings are monotone), so if that bound is below the threshold for the whole wave every row would be culled:
             // skip the unit's header work (JT exponentials) and its R row exponentials as well
             const double eu = __dsub_rn(__dmul_rn(pT, U[3]), __dmul_rn(mT, U[7]));   // the roundings of the row test, no contraction
-            if (g.zskip && __all(eu < cull_min)) { n_rows += R; n_dead += R; return; }
+            if (g.zskip && __all(PDSB ? cull_below(eu, lam, lamb, cull_min) : eu < cull_min)) { n_rows += R; n_dead += R; return; }
         }
         double pTB[JT], pTD[JT], pT2g[JT], E2[JT];
         double bmax = -1.0e300;
@@ -1094,7 +1134,7 @@ cf_main_tile(const double *__restrict__ TS, const double *__restrict__ lane_mT, 
             }
             rw.mTC = mT * row[1];
             const double earg = BARYON ? (bmax - rw.mTC) + baB : bmax - rw.mTC;
-            rw.live = !(g.zskip && __all(earg < cull_thr[NG > 1 ? cull_row_group(r) : 0]));
+            rw.live = !(g.zskip && __all(PDSB ? cull_below(earg, lam, lamb, cull_thr[NG > 1 ? cull_row_group(r) : 0]) : earg < cull_thr[NG > 1 ? cull_row_group(r) : 0]));   // lambda_u in the test, never in E1
             n_rows += 1;
             n_dead += rw.live ? 0 : 1;
             rw.E1 = exp_p9(earg);
@@ -1209,7 +1249,10 @@ cf_main_tile(const double *__restrict__ TS, const double *__restrict__ lane_mT, 
                     const int nu = min(UB, n_units - ib * UB);
                     const double *base = (const double *)lbuf[ib & 1] + sub_off;
                     for (int u = 0; u < nu; u += S) { process_unit(base + u * REC); n_calls++; }
-                    if (RELCULL && g.zskip == 2 && (((ib + 1) & ib) == 0 || (ib & 31) == 31)) cull_refresh<NG, NACC, R>(acc, pe, -745.2, cull_thr, cull_min);
+                    if (RELCULL && g.zskip == 2 && (((ib + 1) & ib) == 0 || (ib & 31) == 31)) {
+                        cull_refresh<NG, NACC, R>(acc, pe, thr_floor, cull_thr, cull_min);
+                        if (PDSB) lamb = cull_min > -745.2;   // every group threshold relative: the lane adds lambda_u from here on
+                    }
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
@@ -1250,7 +1293,10 @@ cf_main_tile(const double *__restrict__ TS, const double *__restrict__ lane_mT, 
                 for (int u = 0; u < nu; u += S) { process_unit(base + u * REC); n_calls++; }   // nu is a multiple of S (plan)
                 // the threshold follows log2 of the accumulators, which grow about linearly with the cells seen: refresh after batches
                 // 0, 1, 3, 7, 15, ... and every 32nd
-                if (RELCULL && g.zskip == 2 && (((ib + 1) & ib) == 0 || (ib & 31) == 31)) cull_refresh<NG, NACC, R>(acc, pe, -745.2, cull_thr, cull_min);
+                if (RELCULL && g.zskip == 2 && (((ib + 1) & ib) == 0 || (ib & 31) == 31)) {
+                    cull_refresh<NG, NACC, R>(acc, pe, thr_floor, cull_thr, cull_min);
+                    if (PDSB) lamb = cull_min > -745.2;
+                }
             }
             if (!EARLY) {
 #pragma unroll
@@ -1405,10 +1451,15 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
     constexpr bool RELCULL = OUTFLOW && REG;      // accumulator-relative culling, see cf_main_tile
     // surface-relative cull: the threshold never falls below what the partial spectrum of the chunks that ran first allows (cf_cull_floor)
     const double thr_floor = (RELCULL && cull_floor && g.zskip == 2) ? cull_floor[(int64_t)s_tile * g.Lpad + l] : -745.2;
+    constexpr bool GRP = RELCULL && !BARYON && !RAWH && R == 7 && (SH8 || MODE == 0);
+    constexpr bool PDSB = kPdsBoundCull && GRP && JT >= 3;      // the unit's lambda_u enters the tested exponent (kPdsBoundCull)
+    // per lane (a lane mask in an SGPR pair), set while every group threshold of the lane is a relative bound (a floor above -745.2 is one,
+    // cf_cull_floor): lambda_u never meets the exact-zero floor
+    bool lamb = PDSB && thr_floor > -745.2;
     // One threshold per row group (cull_refresh) in the SH8 kernels (variants 6, 10, 12) and the hand-pipelined variant 5; the round-5 form (variant 13,
     // with it variant 11) and the baryon records keep one per (lane, tile): the in-tree baseline of the rule, and 256 VGPRs with none to spare.
     // The floor is per (lane, tile) in either case and holds for every group.
-    constexpr int NG = (kRowGroupCull && RELCULL && !BARYON && !RAWH && R == 7 && (SH8 || MODE == 0)) ? kCullGroups : 1;
+    constexpr int NG = (kRowGroupCull && GRP) ? kCullGroups : 1;
     double cull_thr[NG], cull_min = thr_floor;    // cull_min: the smallest of the group thresholds (unit-level test)
 #pragma unroll
     for (int i = 0; i < NG; i++) cull_thr[i] = thr_floor;
@@ -1421,6 +1472,7 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
     auto process_unit = [&](const double *U, const double *tab) -> bool {
         // (both bounds in ONE LDS round trip: read before the test is formed, not under its g.zskip short-circuit)
         const double dmaxv = BARYON ? U[4 * JT + 1] : U[3], cminv = BARYON ? U[HDR + 5] : U[7];
+        const double lamv = PDSB ? U[11] : 0.0;                                          // lambda_u, in the same round trip
         // ... and, in the same round trip, the operands of the row tests (MODE 1): a live unit then forms its row mask while its header
         // is arriving instead of paying two more round trips for the C'_k; a dead unit drops four reads
         double cn[R];
@@ -1431,10 +1483,15 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
         }
         const double bmax = __dmul_rn(pT, dmaxv);                                        // pT Dmax == max_j pT Dp_j (pT >= 0)
         const double baB = BARYON ? bq * U[4 * JT] : 0.0;                                // b mu_B / T: f_eq = 1/(exp(x - b alpha_B) + sign)
+        // bl: what the tests subtract mT C' from (bmax + lambda_u; one addition per unit).  The row exponentials keep bmax.  MODE 0 has no VGPR pair for
+        // it: there lambda_u stays on the scalar side and is added per test.
+        double bl = bmax, lam_s = 0.0;
+        if constexpr (PDSB && ROWMASK) bl = bmax + (lamb ? lamv : 0.0);
+        if constexpr (PDSB && !ROWMASK) lam_s = to_sgpr(lamv);
         {
-            double eu = __dsub_rn(bmax, __dmul_rn(mT, cminv));                           // unit-level cull, as in cf_main_tile
+            double eu = __dsub_rn(bl, __dmul_rn(mT, cminv));                             // unit-level cull, as in cf_main_tile
             if (BARYON) eu += baB;
-            const bool dead = __all(eu < cull_min);   // a unit dead under the smallest group threshold has every row dead
+            const bool dead = __all((PDSB && !ROWMASK) ? cull_below(eu, lam_s, lamb, cull_min) : eu < cull_min);   // a unit dead under the smallest group threshold has every row dead
             if (g.zskip && dead) { n_rows += R; n_dead += R; return false; }
         }
         // MODE 1: liveness of the R rows (3 instructions a row), each against its own group's threshold
@@ -1444,7 +1501,7 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
                 live = 0;
 #pragma unroll
                 for (int r = 0; r < R; r++) {
-                    const double earg = BARYON ? (bmax - mT * cn[r]) + baB : bmax - mT * cn[r];
+                    const double earg = BARYON ? (bmax - mT * cn[r]) + baB : bl - mT * cn[r];   // the TESTED exponent: with lambda_u
                     live |= __all(earg < cull_thr[NG > 1 ? cull_row_group(r) : 0]) ? 0u : (1u << r);
                 }
             }
@@ -1484,7 +1541,7 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
             rw.v = row;
             rw.mTC = mT * row[1];
             const double earg = BARYON ? (bmax - rw.mTC) + baB : bmax - rw.mTC;
-            rw.live = !(g.zskip && __all(earg < cull_thr[NG > 1 ? cull_row_group(r) : 0]));
+            rw.live = !(g.zskip && __all(PDSB ? cull_below(earg, lam_s, lamb, cull_thr[NG > 1 ? cull_row_group(r) : 0]) : earg < cull_thr[NG > 1 ? cull_row_group(r) : 0]));   // lambda_u in the test, never in E1
             n_rows += 1;
             n_dead += rw.live ? 0 : 1;
             rw.E1 = exp_p9(earg);   // degree 9, one-fma reduction (cf_math.h): 7e-14, two instructions fewer per row
@@ -1534,7 +1591,7 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
             // Row groups: a unit passes the unit bound against the SMALLEST group threshold, its rows are each held to their own group's -- the mask can
             // come out empty; such a unit leaves here, its rows counted as below.  (Leaving in front of the header -- mask first, the 32 v_readfirstlane
             // behind the exit -- was measured: the same time with culling on, 1.9 % slower with culling off, LABBOOK round 24.)
-            if (NG > 1 && live == 0) { n_rows += R; n_dead += R; return false; }
+            if ((NG > 1 || PDSB) && live == 0) { n_rows += R; n_dead += R; return false; }
             n_rows += R;
             n_dead += R - __builtin_popcount(live);
             if constexpr (PROF) pf_hdr += clock64() - pf_u0;
@@ -1627,7 +1684,10 @@ cf_main_tile3e(const double *__restrict__ TS, const double *__restrict__ TE, con
         if constexpr (PROF) pa = clock64();
         // the threshold follows log2 of the accumulators, which grow about linearly with the cells seen: refresh after batches
         // 0, 1, 3, 7, 15, ... and every 64th
-        if (RELCULL && g.zskip == 2 && (((ib + 1) & ib) == 0 || (ib & 63) == 63)) cull_refresh<NG, NACC, R>(acc, pe, thr_floor, cull_thr, cull_min);
+        if (RELCULL && g.zskip == 2 && (((ib + 1) & ib) == 0 || (ib & 63) == 63)) {
+            cull_refresh<NG, NACC, R>(acc, pe, thr_floor, cull_thr, cull_min);
+            if (PDSB) lamb = cull_min > -745.2;     // every group threshold relative: the lane adds lambda_u from here on
+        }
         if constexpr (PROF) pf_thr += clock64() - pa;
     };
     {

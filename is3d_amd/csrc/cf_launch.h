@@ -22,7 +22,7 @@ inline int64_t default_stream_cap_bytes(int64_t requested)
     }
     return ws;
 }
-size_t prep_lds_bytes(int nT, int nspl, int J, int K, int baryon, int rec, int dim3);
+size_t prep_lds_bytes(int nT, int nspl, int J, int K, int baryon, int rec, int dim3, int units /* jtiles * rblocks of a tiled 3+1D stream, else 0 */);
 hipError_t launch_prep(const PrepParams &p, hipStream_t stream);
 void main_tile_shape(int variant, int dim3, int *JT, int *KT);
 hipError_t launch_main(int variant, int ce, int dim3, int outflow, int reg, const MainArgs &a, hipStream_t st);  // a.g.baryon selects the B kernels

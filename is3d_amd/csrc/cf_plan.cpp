@@ -430,7 +430,8 @@ static int plan_create_impl(is3d_plan **out, const is3d_species *sp, const is3d_
     is3d::main_tile_shape(P->variant, P->dim3 ? 1 : 0, &P->JT, &P->KT);
     P->jtiles = (P->J + P->JT - 1) / P->JT;
     const bool tiled = P->variant != 1;
-    if (!fq && is3d::prep_lds_bytes(df->n_T, nspl, P->J, P->K, P->baryon ? 1 : 0, tiled ? is3d::unit_rec_doubles(P->JT, P->KT, P->baryon ? 1 : 0) : 0, P->dim3 ? 1 : 0) > 160 * 1024)
+    if (!fq && is3d::prep_lds_bytes(df->n_T, nspl, P->J, P->K, P->baryon ? 1 : 0, tiled ? is3d::unit_rec_doubles(P->JT, P->KT, P->baryon ? 1 : 0) : 0, P->dim3 ? 1 : 0,
+                                    (tiled && P->dim3) ? P->jtiles * ((P->K + P->KT - 1) / P->KT) : 0) > 160 * 1024)
         return fail(IS3D_EINVAL, "grids too large for the prep kernel's LDS staging");
     P->rblocks = tiled ? (P->K + P->KT - 1) / P->KT : 1;
     P->ktiles = P->dim3 ? (P->K + P->KT - 1) / P->KT : 1;   // k tiles are separate tasks only in 3+1D

@@ -11,6 +11,9 @@ acc[lane][j][k] (equilibrium integrand, u = 1/2), and counts the (wave, cell, ti
   G  (--row-groups 2,3,2) one threshold per (lane, tile, group of consecutive rows): minimum over the group's accumulators -- the rule of the
      kernels since round 24 (cull_refresh, cf_kernels.hip).  The unit-level test of the kernel is held against the smallest group threshold; the
      model's "live units" are units with at least one live row, which is what the empty-mask exit of the kernel makes of them.
+  P  (--pds-bound unit|group|row) rule G (rule A without --row-groups) with lambda added to the tested exponent: earg + lambda >= thr, where
+     lambda = clamp(log((mTmax max_k |A_k| + pTmax max_j |B_j|) psc), -LAMBDA_MAX, 0) is the bound of the scaled p.dsigma over the unit's rows and
+     phi (unit: what cf_prep writes into header slot 11, the kernels' rule since round 25), over a row group's rows, or over one row.
 
 --seed / --chunks: another seeded surface, cut into equal consecutive cell chunks with accumulators of their own (the counts are summed) -- e.g. the
 surface tests/test_gpu_parity.py::test_row_culling_changes_no_bit pins its cross-variant counts on: --cells 2000 --seed 80 --chunks 3.
@@ -74,6 +77,8 @@ def main():
     ap.add_argument("--origin", default="0", help="row-block origin: an integer row, or 'eta': the row nearest the bin's eta minus R // 2, so that the "
                                                   "live window of the chunk's cells sits in one block (blocks then cover rows origin + R m, clipped to the grid)")
     ap.add_argument("--row-groups", default=None, help="rule G: sizes of the groups of consecutive rows of a row block that share a threshold, e.g. 2,3,2")
+    ap.add_argument("--pds-bound", default="none", choices=["none", "unit", "group", "row"],
+                    help="rule P: the bound of the scaled p.dsigma over the unit / the row group / the row, in place of the surface-wide 2^pe alone")
     ap.add_argument("--seed", type=int, default=None, help="seed of the surface (default: the config-3 seed)")
     ap.add_argument("--chunks", type=int, default=1, help="cut the cells into this many equal consecutive chunks, each with its own accumulators")
     a = ap.parse_args()
@@ -141,11 +146,15 @@ def main():
     jt_n, kt_n = (J + JT - 1) // JT, len(blocks)
     C = a.cells
 
-    rules = "ABCG" if groups else "ABC"
+    if a.pds_bound == "group" and not groups:
+        ap.error("--pds-bound group needs --row-groups")
+    rules = ("ABCG" if groups else "ABC") + ("P" if a.pds_bound != "none" else "")
+    LAMBDA_MAX = 40 * 0.6931471805599453          # kPdsLambdaMax, cf_device.h
+    lam_all = []
     live = {k: 0 for k in rules}
     unit_live = {k: 0 for k in rules}
-    lane_live = {k: 0 for k in rules if k != "C"}
-    per_kt = {k: np.zeros(kt_n) for k in rules if k != "C"}
+    lane_live = {k: 0 for k in rules if k not in "CP"}
+    per_kt = {k: np.zeros(kt_n) for k in rules if k not in "CP"}
     total_rows = 0
     for ich in range(a.chunks):
         lo, hi = C * ich // a.chunks, C * (ich + 1) // a.chunks
@@ -185,6 +194,27 @@ def main():
                             eG[:, r0:r0 + gs] = eB[:, r0:r0 + gs].min(axis=1, keepdims=True)
                         r0 += gs
                     lvG = earg >= thr_from(eG)[:, None, :]
+                if a.pds_bound != "none":
+                    absA = np.abs(Ak[lo:hi, ks])                               # [c][r]
+                    bB = np.abs(Bj[lo:hi, js]).max(axis=1)                    # [c]
+                    if a.pds_bound == "unit":
+                        aA = np.broadcast_to(absA.max(axis=1, keepdims=True), absA.shape)
+                    elif a.pds_bound == "row":
+                        aA = absA
+                    else:
+                        aA = np.empty_like(absA)
+                        r0 = 0
+                        for gs in groups:
+                            if r0 < absA.shape[1]:
+                                aA[:, r0:r0 + gs] = absA[:, r0:r0 + gs].max(axis=1, keepdims=True)
+                            r0 += gs
+                    with np.errstate(divide="ignore"):
+                        lam = np.clip(np.log((mTmax * aA + pTmax * bB[:, None]) * psc), -LAMBDA_MAX, 0.0)      # [c][r]
+                    lam_all.append(lam[:, 0] if a.pds_bound == "unit" else lam.ravel())
+                    thrP = thr_from(eG)[:, None, :] if groups else thrA
+                    # a lane adds lambda only while all its group thresholds are relative bounds (no group at the floor: a padded row, a zero accumulator)
+                    lamk = (np.isfinite(eG).all(axis=1) if groups else np.isfinite(eA)).astype(float)            # [l]
+                    lvP = (earg + lamk[:, None, None] * lam[None, :, :]) >= thrP
                 # C: exists j: earg + log E2_j >= thr(acc[j][k]);  log E2_j = pT (Dp_j - Dmax)
                 lvC = np.zeros_like(lvA)
                 for j in range(js.start, js.stop):
@@ -193,7 +223,7 @@ def main():
                     lvC |= (earg + lE2[:, :, None]) >= thrC
                 nr = ks.stop - ks.start
                 total_rows += nw * Cc * nr
-                for key, lv in (("A", lvA), ("B", lvB), ("C", lvC)) + ((("G", lvG),) if groups else ()):
+                for key, lv in (("A", lvA), ("B", lvB), ("C", lvC)) + ((("G", lvG),) if groups else ()) + ((("P", lvP),) if a.pds_bound != "none" else ()):
                     pad = np.zeros((nw * 64 - L,) + lv.shape[1:], dtype=bool)
                     w = np.concatenate([lv, pad]).reshape(nw, 64, Cc, nr).any(axis=1)    # [w][c][r]
                     live[key] += int(w.sum())
@@ -216,6 +246,12 @@ def main():
     if groups:
         ca, cg = 1.0 - live["A"] / total_rows, 1.0 - live["G"] / total_rows
         print("rule G (row groups %s): culled wave-rows %.4f against A's %.4f: %+.2f %% relative" % (a.row_groups, cg, ca, 100.0 * (cg - ca) / ca))
+    if a.pds_bound != "none":
+        lam = np.concatenate(lam_all)
+        base = "G" if groups else "A"
+        print("rule P (lambda per %s): mean %.2f median %.2f min %.2f max %.2f;  live wave-rows %.4f against %s's %.4f: %+.2f %%;  live units %+.2f %%" % (
+            a.pds_bound, lam.mean(), np.median(lam), lam.min(), lam.max(), live["P"] / total_rows, base, live[base] / total_rows,
+            100.0 * (live["P"] - live[base]) / live[base], 100.0 * (unit_live["P"] - unit_live[base]) / unit_live[base]))
     for key in per_kt:
         print("rule %s: live (lane, row) pairs %.4f;  live wave-rows by row block: %s" % (
             key, lane_live[key] / (L * C * jt_n * K), np.round(per_kt[key] / (nw * C * jt_n * R), 4)))
