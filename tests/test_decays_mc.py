@@ -67,18 +67,8 @@ def test_rounding_floor(tabs):
     assert 0.0 < worst <= cases.FLOOR
 
 
-def hand_table(entries):
-    """entries: [(mc_id, mass, width, stable, [(npart, branch_ratio, [daughter ids])])] -> pdg_read_decays' dict"""
-    ch = [c for e in entries for c in e[4]]
-    return dict(mc_id=np.array([e[0] for e in entries], np.int64), mass=np.array([e[1] for e in entries], np.float64),
-                width=np.array([e[2] for e in entries], np.float64), stable=np.array([e[3] for e in entries], np.int32),
-                n_channels=np.array([len(e[4]) for e in entries], np.int32), npart=np.array([c[0] for c in ch], np.int32),
-                branch_ratio=np.array([c[1] for c in ch], np.float64),
-                daughters=np.array([list(c[2]) + [0] * (5 - len(c[2])) for c in ch], np.int64).reshape(-1, 5))
-
-
 PI = [(211, 0.13957, 0.0, 1, [(1, 1.0, [211])]), (-211, 0.13957, 0.0, 1, [(1, 1.0, [-211])]), (111, 0.13498, 0.0, 1, [(1, 1.0, [111])])]
-OMEGA_3PI = hand_table(PI + [(223, 0.78265, 0.00849, 0, [(3, 0.89, [211, -211, 111])])])
+OMEGA_3PI = cases.hand_table(PI + [(223, 0.78265, 0.00849, 0, [(3, 0.89, [211, -211, 111])])])
 
 
 def test_three_body_phase_space_is_flat():
@@ -113,7 +103,7 @@ def chain_table(top_bodies):
     for k in range(1, 4):
         e.append((100 + k, 0.3 + 0.5 * k, 0.1, 0, [(5, 1.0, [100 + k - 1, 1, 1, 1, 1])]))
     e.append((104, 2.4, 0.1, 0, [(top_bodies, 1.0, [103] + [1] * (top_bodies - 1))]))
-    return hand_table(e)
+    return cases.hand_table(e)
 
 
 def test_table_analysis(tabs):
@@ -127,7 +117,7 @@ def test_table_analysis(tabs):
     with pytest.raises(api.Is3dError) as e:
         analysed(chain_table(4))
     assert e.value.code == api.IS3D_EINVAL and "17" in str(e.value)
-    cyc = hand_table(PI + [(9001, 1.0, 0.1, 0, [(2, 1.0, [9002, 111])]), (9002, 1.1, 0.1, 0, [(2, 1.0, [9001, 111])])])
+    cyc = cases.hand_table(PI + [(9001, 1.0, 0.1, 0, [(2, 1.0, [9002, 111])]), (9002, 1.1, 0.1, 0, [(2, 1.0, [9001, 111])])])
     with pytest.raises(api.Is3dError) as e:
         analysed(cyc)
     assert e.value.code == api.IS3D_EINVAL and "cycle" in str(e.value)
