@@ -57,8 +57,10 @@ def coefficients_bilinear_scipy(dff, df_mode, T, muB):
     return dict(F=S("F") * T, G=S("G"), betabulk=S("betabulk") * T4, betaV=S("betaV") * T3, betapi=S("betapi") * T4)
 
 
-def highprec_spectrum(cells, sp, grid, df, opts):
-    """Appendix A of SURVEY.md, long double, loops over cells only."""
+def highprec_spectrum(cells, sp, grid, df, opts, stats=None):
+    """Appendix A of SURVEY.md, long double, loops over cells only.  stats (a dict, optional) receives counts over the (cell, eta, bin) terms
+    that a double would see as nonzero past the outflow cut: `terms`, and those whose delta-f lies at or past the clamp, `clamp_hi` (>= 1) and
+    `clamp_lo` (<= -1)."""
     dim, dfm = opts["dimension"], opts["df_mode"]
     outflow, reg = opts.get("outflow", 1), opts.get("regulate_deltaf", 1)
     inc_bulk, inc_shear = opts.get("include_bulk_deltaf", 1), opts.get("include_shear_deltaf", 1)
@@ -145,6 +147,10 @@ def highprec_spectrum(cells, sp, grid, df, opts):
             dfc = feqbar * (shear * pipp + (b0 * m2 + (b1 * bb + b2 * pu) * pu) * bulkPi + (c3 * bb + c4 * pu) * Vp)
         else:
             dfc = feqbar * (shear * pipp / pu + (b0 * pu + b1 * bb + b2 * (pu - m2 / pu)) * bulkPi + (rho - bb / pu) * Vp / betaV)
+        if stats is not None:
+            on = ((pds * feq).astype(np.float64) != 0) & ((pds > 0) | (not outflow))
+            for k, m in (("terms", on), ("clamp_hi", on & (dfc >= 1)), ("clamp_lo", on & (dfc <= -1))):
+                stats[k] = stats.get(k, 0) + int(np.sum(m & (g != 0)[None, None, None, None, :]))
         if reg:
             dfc = np.clip(dfc, -1, 1)
         term = pds * feq * (1 + dfc)
@@ -181,15 +187,25 @@ def jonah_tables_ld(fq):
 
 def highprec_feqmod(cells, sp, grid, df, fq, opts):
     """calculate_dN_ptdptdphidy_feqmod (smooth_kernels.cpp:396-996), include_baryon = 0, in long double with numpy linear
-    algebra and scipy splines -- independent of the oracle's C.  Cells whose feqmod breaks down (df_mode 3) or rows in the
-    narrow window (3+1D, detA < 0.01) are NOT handled: the generator asserts that none occurs in the chosen cells."""
+    algebra and scipy splines -- independent of the oracle's C.  Returns (spectrum, counts).  The branches, each from the reference's text:
+      skipped      u.dsigma <= 0 (:523)
+      breakdown    df_mode 3 only (does_feqmod_breakdown, emissionfunction.cpp:109-150): detA <= deta_min, or the linearised pi0 density
+                   neq + Pi (neq + J20 F / T^2) / beta_Pi negative; every row of the cell takes the linear Chapman-Enskog delta-f (:825-857) at
+                   the UNSCALED eta, while the species' renormalisation is still formed and a NaN / infinite one drops the species (:773-778)
+      narrow rows  3+1D, not a breakdown cell, detA < 0.01: the rows with |y - eta| < detA take the linear delta-f, df_mode 3 as above,
+                   df_mode 4 with delta_z - 3 delta_lambda + feqbar delta_lambda (p.u - m^2 / p.u) / T (:811-819, :858-876)
+      small detA   no positivity is asked of detA: eta is rescaled only for deta_min < detA < 1 (2+1D, :729), the 3+1D renormalisation is
+                   |renorm / detA| (:783, :927), and df_mode 4 has no breakdown at all
+    counts: skipped, breakdown, narrow_cells (live cells that are no breakdown cells with detA < 0.01 in 3+1D), narrow_rows ((cell, y) pairs
+    inside the window), renorm_dropped ((cell, species) pairs)."""
     dim, dfm = opts["dimension"], opts["df_mode"]
-    outflow = opts.get("outflow", 1)
+    outflow, reg = opts.get("outflow", 1), opts.get("regulate_deltaf", 1)
     pT = grid["pT"].astype(LD)
     cosphi, sinphi = np.cos(grid["phi"]).astype(LD), np.sin(grid["phi"]).astype(LD)
     mass, sign, gdeg = sp["mass"].astype(LD), sp["sign"].astype(LD), sp["degeneracy"].astype(LD)
     ny = len(grid["y"]) if dim == 3 else 1
     out = np.zeros((ny, len(cosphi), len(pT), len(mass)), dtype=LD)
+    counts = dict(skipped=0, breakdown=0, narrow_cells=0, narrow_rows=0, renorm_dropped=0)
     pref = LD(float(2.0 * np.pi * 0.197327053)) ** -3
     two_pi2_hbarC3 = LD(float(2.0 * np.pi ** 2 * 0.197327053 ** 3))
     mT = np.sqrt(mass[:, None] ** 2 + pT[None, :] ** 2)
@@ -198,13 +214,22 @@ def highprec_feqmod(cells, sp, grid, df, fq, opts):
         S_l2, S_z = CubicSpline(bpt, l2, bc_type="natural"), CubicSpline(bpt, zt, bc_type="natural")
         bp_max = float(np.max(bpt))
     r1, w1, r2, w2 = (fq[k].astype(LD) for k in ("root1", "weight1", "root2", "weight2"))
+
+    def gt(kind, mb, r, wq, sg):
+        Eb = np.sqrt(r[None, :] ** 2 + mb[:, None] ** 2)
+        q = np.exp(Eb) + sg[:, None]
+        if kind == "neq":
+            return np.sum(wq * r * np.exp(r) / q, axis=1)
+        return np.sum(wq * Eb * np.exp(r + Eb) / (q * q), axis=1)
     for c in range(len(cells["tau"])):
         f = {k: LD(cells[k][c]) for k in synth.CELL_FIELDS}
         tau, tau2 = f["tau"], f["tau"] ** 2
         ux, uy, un = f["ux"], f["uy"], f["un"]
         ut = np.sqrt(1 + ux * ux + uy * uy + tau2 * un * un)
         dat, dax, day, dan = f["dat"], f["dax"], f["day"], f["dan"]
-        assert ut * dat + ux * dax + uy * day + un * dan > 0
+        if ut * dat + ux * dax + uy * day + un * dan <= 0:
+            counts["skipped"] += 1
+            continue
         T, P, E = f["T"], f["P"], f["E"]
         pixx, pixy, pixn, piyy, piyn = f["pixx"], f["pixy"], f["pixn"], f["piyy"], f["piyn"]
         uperp, utperp = np.sqrt(ux * ux + uy * uy), np.sqrt(1 + ux * ux + uy * uy)
@@ -240,46 +265,83 @@ def highprec_feqmod(cells, sp, grid, df, fq, opts):
         Ainv = np.linalg.inv(A.astype(np.float64)).astype(LD)
         for _ in range(3):                                                        # Newton-Schulz polish in long double
             Ainv = Ainv @ (2 * np.eye(3, dtype=LD) - A @ Ainv)
-        assert detA > 0.02, "generator cells must stay away from the breakdown branches"
+        breakdown = False
+        if dfm == 3:                                                              # emissionfunction.cpp:96-138: the pi0 with sign -1, no degeneracy
+            one, mpi = np.array([-1], dtype=LD), np.array([LD(fq["mass_pion0"]) / T])
+            nf = T ** 3 / two_pi2_hbarC3
+            neq0, J200 = nf * gt("neq", mpi, r1, w1, one)[0], T * nf * gt("J20", mpi, r2, w2, one)[0]
+            breakdown = bool(detA <= fq["deta_min"] or neq0 + bulkPi * (neq0 + J200 * F / T / T) / betabulk < 0)
+        counts["breakdown"] += breakdown
         eta_scale = LD(detA) if (dim == 2 and fq["deta_min"] < detA < 1.0) else LD(1)
         if dim == 3:
             ys, etas, ws = grid["y"].astype(LD), np.array([f["eta"]], dtype=LD), np.array([1], dtype=LD)
         else:
             ys, etas, ws = np.array([0], dtype=LD), grid["eta"].astype(LD), grid["eta_w"].astype(LD)
-        d = ys[:, None] - eta_scale * etas[None, :]
-        ch, sh = np.cosh(d)[:, :, None, None, None], np.sinh(d)[:, :, None, None, None]
         w = ws[None, :, None, None, None]
         mTb = mT.T[None, None, None, :, :]
+        m2 = (mass ** 2)[None, None, None, None, :]
+        sg = sign[None, None, None, None, :]
         px = (pT[None, :] * cosphi[:, None])[None, None, :, :, None]
         py = (pT[None, :] * sinphi[:, None])[None, None, :, :, None]
-        pt, t2pn = mTb * ch, tau * mTb * sh
-        pn = t2pn / tau2
-        pds = w * (pt * dat + px * dax + py * day) + pn * dan                      # dsigma_eta outside the weight, :905
-        pL = [-(e[0] * pt) + e[1] * px + e[2] * py + e[3] * t2pn for e in (X, Y, Z)]     # -X.p etc with p_mu lowered: :907-909
-        pm = [Ainv[i, 0] * pL[0] + Ainv[i, 1] * pL[1] + Ainv[i, 2] * pL[2] for i in range(3)]
-        Emod = np.sqrt((mass ** 2)[None, None, None, None, :] + pm[0] ** 2 + pm[1] ** 2 + pm[2] ** 2)
         if dfm == 3:
             mbar, mbm = mass / T, mass / T_mod
             neqf = T ** 3 / two_pi2_hbarC3
-
-            def gt(kind, mb, r, wq):
-                Eb = np.sqrt(r[None, :] ** 2 + mb[:, None] ** 2)
-                q = np.exp(Eb) + sign[:, None]
-                if kind == "neq":
-                    return np.sum(wq * r * np.exp(r) / q, axis=1)
-                return np.sum(wq * Eb * np.exp(r + Eb) / (q * q), axis=1)
-            neq = neqf * gdeg * gt("neq", mbar, r1, w1)
-            J20 = T * neqf * gdeg * gt("J20", mbar, r2, w2)
+            neq = neqf * gdeg * gt("neq", mbar, r1, w1, sign)
+            J20 = T * neqf * gdeg * gt("J20", mbar, r2, w2, sign)
             n_lin = neq + (bulkPi / betabulk) * (neq + J20 * F / T / T)
-            n_mod = (T_mod ** 3 / two_pi2_hbarC3) * gdeg * gt("neq", mbm, r1, w1)
-            renorm = (n_lin / n_mod)[None, None, None, None, :]
-        ren = np.abs(renorm) / (LD(detA) if dim == 3 else LD(1))
-        fm = ren / (np.exp(Emod / T_mod) + sign[None, None, None, None, :])
-        term = pds * fm
-        if outflow:
-            term = np.where(pds <= 0, LD(0), term)
+            n_mod = (T_mod ** 3 / two_pi2_hbarC3) * gdeg * gt("neq", mbm, r1, w1, sign)
+            with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+                kept = np.isfinite(n_lin.astype(np.float64) / n_mod.astype(np.float64))      # the reference's test is on a double
+                renorm = np.where(kept, n_lin / np.where(kept, n_mod, 1), 0)[None, None, None, None, :]
+        else:
+            kept = np.ones(len(mass), dtype=bool) if np.isfinite(float(renorm)) else np.zeros(len(mass), dtype=bool)
+        counts["renorm_dropped"] += int((~kept).sum())
+        narrow = np.zeros(len(ys), dtype=bool)
+        if dim == 3 and not breakdown and detA < 0.01:
+            counts["narrow_cells"] += 1
+            narrow = np.abs(ys - etas[0]) < LD(detA)
+            counts["narrow_rows"] += int(narrow.sum())
+        term = None
+        if not breakdown and not narrow.all():
+            d = ys[:, None] - eta_scale * etas[None, :]
+            ch, sh = np.cosh(d)[:, :, None, None, None], np.sinh(d)[:, :, None, None, None]
+            pt, t2pn = mTb * ch, tau * mTb * sh
+            pn = t2pn / tau2
+            pds = w * (pt * dat + px * dax + py * day) + pn * dan                      # dsigma_eta outside the weight, :905
+            pL = [-(e[0] * pt) + e[1] * px + e[2] * py + e[3] * t2pn for e in (X, Y, Z)]     # -X.p etc with p_mu lowered: :907-909
+            pm = [Ainv[i, 0] * pL[0] + Ainv[i, 1] * pL[1] + Ainv[i, 2] * pL[2] for i in range(3)]
+            Emod = np.sqrt((mass ** 2)[None, None, None, None, :] + pm[0] ** 2 + pm[1] ** 2 + pm[2] ** 2)
+            ren = np.abs(renorm / (LD(detA) if dim == 3 else LD(1)))
+            fm = ren / (np.exp(Emod / T_mod) + sign[None, None, None, None, :])
+            term = pds * fm
+            if outflow:
+                term = np.where(pds <= 0, LD(0), term)
+        if breakdown or narrow.any():
+            d = ys[:, None] - etas[None, :]
+            ch, sh = np.cosh(d)[:, :, None, None, None], np.sinh(d)[:, :, None, None, None]
+            pt, t2pn = mTb * ch, tau * mTb * sh
+            pn = t2pn / tau2
+            pds = w * (pt * dat + px * dax + py * day) + pn * dan
+            pu = pt * ut - px * ux - py * uy - t2pn * un
+            feq = 1 / (np.exp(pu / T) + sg)
+            feqbar = 1 - sg * feq
+            pipp = pitt * pt * pt + pixx * px * px + piyy * py * py + pinn * t2pn * t2pn + 2 * (
+                -(pitx * px + pity * py) * pt + pixy * px * py + t2pn * (pixn * px + piyn * py - pitn * pt))
+            shear = LD(0.5) / (betapi * T)
+            if dfm == 3:
+                dfc = feqbar * (shear * pipp / pu + (F / (T * T * betabulk) * pu + (pu - m2 / pu) / (3 * T * betabulk)) * bulkPi)
+            else:
+                dlam = bulkPi / (5 * betapi - 3 * P * (E + P) / E)
+                dfc = feqbar * shear * pipp / pu + (-3 * dlam * P / E - 3 * dlam + feqbar * dlam * (pu - m2 / pu) / T)
+            if reg:
+                dfc = np.clip(dfc, -1, 1)
+            lin = pds * feq * (1 + dfc)
+            if outflow:
+                lin = np.where(pds <= 0, LD(0), lin)
+            term = lin if term is None else np.where(narrow[:, None, None, None, None], lin, term)
+        term = np.where(kept[None, None, None, None, :], term, LD(0))
         out += pref * gdeg[None, None, None, :] * term.sum(axis=1)
-    return out.reshape(-1)
+    return out.reshape(-1), counts
 
 
 def hand_cells():
@@ -347,7 +409,7 @@ def main():
         for dfm in (4, 3):
             o = dict(dimension=dim, df_mode=dfm)
             key = "%s_feqmod%d" % (name, dfm)
-            hp[key] = highprec_feqmod(cells, sp, grid, df, fq, o).astype(np.float64)
+            hp[key] = highprec_feqmod(cells, sp, grid, df, fq, o)[0].astype(np.float64)
             cases.append(dict(key=key, cells=name, opts=o, feqmod=True))
             chk, nb = oracle.dN_pTdpTdphidy_feqmod(cells, sp, grid, df, fq, o)
             assert nb == 0
