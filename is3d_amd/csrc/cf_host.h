@@ -57,6 +57,18 @@ struct DevBuf {
     template <class U> U *as() const { return (U *)p; }
 };
 
+// IS3D_ENOMEM for a plan's stream or slab allocation that came back hipErrorOutOfMemory, with the sizes that decide it: `bytes` of `what`,
+// the cells per pass and their bytes of streams, and the partial slabs the plan asked for
+inline int oom_report(const char *what, size_t bytes, int64_t pass_cells, size_t bytes_per_cell, int slabs)
+{
+    (void)hipGetLastError();
+    size_t fr = 0, to = 0;
+    (void)hipMemGetInfo(&fr, &to);
+    return set_error(IS3D_ENOMEM, "out of device memory allocating %s (%.2f GB; %.2f GB free of %.2f GB): %lld cells per pass x %zu B of streams, "
+                     "%d partial slabs -- lower opts.workspace_bytes (more passes) or opts.cell_chunks", what, bytes / 1e9, fr / 1e9, to / 1e9,
+                     (long long)pass_cells, bytes_per_cell, slabs);
+}
+
 // ---- the cell structs of include/is3d_amd.h as arrays, in declaration order ----
 constexpr int kCellArrays = 23, kVahCellArrays = 30;
 static_assert(sizeof(is3d_cells) == sizeof(int64_t) + kCellArrays * sizeof(const double *), "is3d_cells: n_cells and 23 arrays");

@@ -20,6 +20,7 @@
 #include "cf_feqmod.h"
 #include "cf_host.h"
 #include "cf_launch.h"
+#include "cf_plan_geometry.h"
 #include "cf_spacetime.h"
 #include "errors.h"
 #include "jonah.h"
@@ -136,6 +137,301 @@ extern "C" int is3d_device_count(void)
     return n;
 }
 
+// The stages of plan_create_impl, in its order.  What they decide without the device is in cf_plan_geometry.h.
+
+// ---- choose kernel: the variant, whether it reads the E2 table stream, lane slots per momentum bin ----
+// Defaults per mode (A/B on MI355X):
+//   3+1D delta-f, pT grid <= 32: variant 6 -- 8 x 7 tile, phi-side exponentials from the E2 table stream, rows tested for liveness before
+//     their exponential (config 3: 354 ms against 404 ms for variant 3), with or without baryon slots;
+//   3+1D otherwise: 8 x 7 (modified equilibrium, with or without the baryon slots -- its records do not grow with them: 1005 vs 1028 ms for
+//     6 x 7; 247.1 against 260.5 ms per 3e5 cells), 6 x 7 for delta-f with the baryon slots;
+//   2+1D: variant 7 -- 8 x 31 tile with unit-strided lanes (delta-f, config 2, 96 bins: 31.4 ms against 38.7 ms for 8 x 61; 305 species, one
+//     slot per bin: 96.0 against 101.0 ms per 2e4 cells; modified equilibrium: rows tested against the unit's threshold from the beta minimum
+//     they carry, the default since round 4).
+// The shipped library holds the kernels these defaults reach (cf_kernels.hip::launch_variant, cf_feqmod.hip) and one explicit choice, the 8 x 7
+// tile without the E2 table stream (3) for a 3+1D delta-f surface without baryon slots; any other request runs the default.  The A/B forms of
+// rounds 1-5 exist in the developer build (make DEV=1), where tests/test_gpu_devlib.py runs their parity tests.
+static void plan_choose_kernel(is3d_plan &P, const is3d_grid *g, const is3d_options *o)
+{
+    const bool fq = P.feqmod;
+    const is3d::VariantChoice vc = is3d::choose_variant(o->dimension, fq, o->include_baryon != 0, g->n_pT <= is3d::kE2Stride, o->kernel_variant, is3d::kDevBuild);
+    P.variant = vc.variant;
+    P.e2tab = vc.e2tab;
+    // unit-strided lanes (2+1D, variants 7 and 8): S lane slots per bin so that the slots fill whole waves; S divides the units per cell
+    P.split = 1;
+    if (P.variant == 7 || P.variant == 8) {
+        int JT7 = 0, R7 = 0;
+        is3d::main_tile_shape(7, 0, &JT7, &R7);
+        P.split = is3d::lane_split(P.Lbins, (g->n_eta + R7 - 1) / R7);
+    }
+    if (fq && o->dimension == 2 && P.variant != 7) {
+        // modified equilibrium, 2+1D, the 61-row tiles (A/B): the same lane slots on the kernel's own tile -- S = 2 when it divides the units per cell and
+        // the units per LDS batch (cf_main_feqmod stages 1536 / REC units) and fills the two-wave workgroups better
+        int JTf = 0, Rf = 0;
+        is3d::main_tile_shape(P.variant, 0, &JTf, &Rf);
+        const int recf = 4 * JTf + Rf * (4 + JTf), ubf = std::max(1, 1536 / recf), rblocksf = (g->n_eta + Rf - 1) / Rf;
+        const int nb = P.Lbins;
+        const double waste1 = 1.0 - (double)nb / (double)(((nb + 63) / 64) * 64);
+        const double waste2 = 1.0 - (double)(2 * nb) / (double)(((2 * nb + 63) / 64) * 64);
+        if (rblocksf % 2 == 0 && ubf % 2 == 0 && waste2 < waste1 - 0.05) P.split = 2;
+    }
+}
+
+// ---- lanes and grids: the lane table, the species map, the phi and y / eta grids, uploaded ----
+static int plan_lanes_and_grids(is3d_plan &P, const is3d_grid *g, const is3d_options *o, const is3d::SpeciesClasses &k, is3d::LaneTable &lt)
+{
+    // dev A/B (IS3D_LANE_INTERLEAVE=1, developer build): the two waves of a workgroup take the even and the odd slots of their 128-slot span of
+    // the mT order instead of its lower and upper half -- both then cover the same mT range, cull the same units and rows, and meet at the
+    // per-batch barrier with (nearly) the same work done
+    static const bool inter = is3d::dev_env("IS3D_LANE_INTERLEAVE") != nullptr;
+    lt = is3d::lane_table(k, g->pT, P.npT, P.split, inter && o->dimension == 3 && !P.feqmod);
+    P.L = lt.L;
+    P.Lpad = lt.Lpad;
+    for (int s = 0; s < P.L; s++) { P.mTmax = std::max(P.mTmax, lt.mT[s]); P.pTmax = std::max(P.pTmax, std::fabs(lt.pT[s])); }
+    std::vector<double> cosphi(P.J), sinphi(P.J);
+    for (int j = 0; j < P.J; j++) { cosphi[j] = std::cos(g->phi[j]); sinphi[j] = std::sin(g->phi[j]); }  // :43-48
+    std::vector<double> kgrid(P.K), kweight(P.K, 1.0);
+    for (int k2 = 0; k2 < P.K; k2++) {
+        kgrid[k2] = P.dim3 ? g->y[k2] : g->eta[k2];
+        if (!P.dim3) kweight[k2] = g->eta_w[k2];
+    }
+    P.kmin = *std::min_element(kgrid.begin(), kgrid.end());
+    P.kmax = *std::max_element(kgrid.begin(), kgrid.end());
+    if (!P.dim3) {
+        P.gw2d = 0.0;
+        for (int k2 = 0; k2 < P.K; k2++) P.gw2d = std::max(P.gw2d, std::fabs(kweight[k2]) * std::cosh(kgrid[k2]));
+    }
+    HIP_TRY(P.d_mT.upload(lt.mT));
+    HIP_TRY(P.d_pT.upload(lt.pT));
+    HIP_TRY(P.d_sign.upload(lt.sign));
+    HIP_TRY(P.d_lane_b.upload(lt.b));
+    HIP_TRY(P.d_lane_sub.upload(lt.sub));
+    if (P.e2tab) {
+        std::vector<int32_t> ipT(P.Lpad, 0);
+        for (int s = 0; s < P.Lbins; s++) ipT[s] = lt.order[s] % P.npT;
+        HIP_TRY(P.d_lane_ipT.upload(ipT));
+        HIP_TRY(P.d_pTgrid.upload(P.pT_grid));
+        for (int i = 0; i < P.npT; i++)
+            if (!(g->pT[i] >= 0.0)) return fail(IS3D_EINVAL, "kernel_variant 5 needs pT >= 0 (pT Dmax must be the maximum of pT D_j)");
+    }
+    HIP_TRY(P.d_degeneracy.upload(P.sp_deg));
+    HIP_TRY(P.d_cls.upload(lt.lane_of));
+    {
+        // scaled p.dsigma of a lane: mT |A| + pT |B W| <= max(mT/mTmax, pT/pTmax) (mTmax |A| + pTmax |B W|) <= that factor (cf_pds_bound)
+        std::vector<int32_t> pe(P.Lpad, 0);
+        for (int s = 0; s < P.L; s++) {
+            const double f = std::max(P.mTmax > 0.0 ? lt.mT[s] / P.mTmax : 1.0, P.pTmax > 0.0 ? std::fabs(lt.pT[s]) / P.pTmax : 0.0);
+            int e = 0;
+            (void)std::frexp(f * (1.0 + 1.0e-12), &e);     // f (1 + eps) = m 2^e, m in [0.5, 1): f < 2^e with room for the roundings
+            pe[s] = std::min(e, 0);                        // the clamp keeps the scaled p.dsigma in [0, 1] whatever the lane
+        }
+        HIP_TRY(P.d_lane_pe.upload(pe));
+    }
+    HIP_TRY(P.d_cosphi.upload(cosphi));
+    HIP_TRY(P.d_sinphi.upload(sinphi));
+    HIP_TRY(P.d_kgrid.upload(kgrid));
+    HIP_TRY(P.d_kweight.upload(kweight));
+    {
+        std::vector<double> kch(P.K), ksh(P.K);
+        for (int k2 = 0; k2 < P.K; k2++) { kch[k2] = std::cosh(0.0 - kgrid[k2]); ksh[k2] = std::sinh(0.0 - kgrid[k2]); }   // smooth_kernels.cpp:279-280 with y = 0
+        HIP_TRY(P.d_kch.upload(kch));
+        HIP_TRY(P.d_ksh.upload(ksh));
+    }
+    std::vector<double> ck, sk;
+    is3d::vn_harmonics(g->phi, P.J, ck, sk);
+    HIP_TRY(P.d_coskphi.upload(ck));
+    HIP_TRY(P.d_sinkphi.upload(sk));
+    HIP_TRY(P.d_phiw.alloc(P.J));
+    HIP_TRY(P.d_pTw.alloc(P.npT));
+    return IS3D_OK;
+}
+
+// ---- coefficient tables: splines in T (deltafReader.cpp:300-322), and with baryon slots the full (mu_B, T) grids of the bilinear branch ----
+static int plan_coefficient_tables(is3d_plan &P, const is3d_df_tables *df, const is3d_options *o)
+{
+    const double *tabs[3] = {nullptr, nullptr, nullptr};
+    int nspl;
+    if (P.feqmod) {
+        // df_mode 3: F, betabulk, betapi; df_mode 4 reads betapi only (the other two slots mirror it, unused)
+        tabs[0] = (o->df_mode == 3) ? df->F : df->betapi;
+        tabs[1] = (o->df_mode == 3) ? df->betabulk : df->betapi;
+        tabs[2] = df->betapi;
+        nspl = 3;
+    } else if (!P.ce) { tabs[0] = df->c0; tabs[1] = df->c2; nspl = 2; }
+    else { tabs[0] = df->F; tabs[1] = df->betabulk; tabs[2] = df->betapi; nspl = 3; }
+    std::vector<double> xs(df->T, df->T + df->n_T);
+    HIP_TRY(P.d_splx.upload(xs));
+    P.spl.n = df->n_T;
+    P.spl.x = P.d_splx.p;
+    P.spl.nspl = nspl;
+    for (int s = 0; s < 3; s++) { P.spl.y[s] = nullptr; P.spl.c[s] = nullptr; }
+    for (int s = 0; s < nspl; s++) {
+        std::vector<double> ys(tabs[s], tabs[s] + df->n_T), cs;
+        if (!is3d::natural_cspline_init(xs, ys, cs)) return fail(IS3D_EINVAL, "spline construction failed");
+        HIP_TRY(P.d_sply[s].upload(ys));
+        HIP_TRY(P.d_splc[s].upload(cs));
+        P.spl.y[s] = P.d_sply[s].p;
+        P.spl.c[s] = P.d_splc[s].p;
+    }
+    if (P.baryon) {
+        // full (mu_B, T) grids for the bilinear branch (deltafReader.cpp:412-484)
+        const double *t5[5];
+        if (!P.ce && !P.feqmod) { t5[0] = df->c0; t5[1] = df->c1; t5[2] = df->c2; t5[3] = df->c3; t5[4] = df->c4; }
+        else { t5[0] = df->F; t5[1] = df->G; t5[2] = df->betabulk; t5[3] = df->betaV; t5[4] = df->betapi; }
+        std::vector<double> bs(df->muB, df->muB + df->n_muB);
+        HIP_TRY(P.d_bilT.upload(xs));
+        HIP_TRY(P.d_bilB.upload(bs));
+        P.bil.nT = df->n_T; P.bil.nB = df->n_muB;
+        P.bil.swap = o->reference_bilinear_indexing != 0;
+        P.bil.T = P.d_bilT.p; P.bil.muB = P.d_bilB.p;
+        for (int k = 0; k < 5; k++) {
+            std::vector<double> tv(t5[k], t5[k] + (size_t)df->n_T * df->n_muB);
+            HIP_TRY(P.d_biltab[k].upload(tv));
+            P.bil.tab[k] = P.d_biltab[k].p;
+        }
+    }
+    return IS3D_OK;
+}
+
+// ---- modified-equilibrium tables: Gauss-Laguerre nodes, the df_mode 4 splines in bulkPi/Peq, the lane -> class tables ----
+static int plan_feqmod_tables(is3d_plan &P, const is3d_feqmod_tables *fq, const is3d_options *o, const is3d::SpeciesClasses &k, const is3d::LaneTable &lt)
+{
+    P.ngl = fq->n_gla;
+    P.detA_min = fq->deta_min;
+    P.mass_pion0 = fq->mass_pion0;
+    std::vector<double> gl((size_t)4 * P.ngl);
+    for (int i = 0; i < P.ngl; i++) {
+        gl[i] = fq->root1[i]; gl[P.ngl + i] = fq->weight1[i]; gl[2 * P.ngl + i] = fq->root2[i]; gl[3 * P.ngl + i] = fq->weight2[i];
+    }
+    HIP_TRY(P.d_gl.upload(gl));
+    std::vector<double> jon;
+    if (o->df_mode == 4) {
+        std::vector<double> bp, l2, zz, cl, cz;
+        is3d::jonah_tables(fq, bp, l2, zz, P.bp_max);
+        // gsl_spline_init on (bulkPi_over_Peq, lambda_squared) and (bulkPi_over_Peq, z), deltafReader.cpp:311-320
+        if (!is3d::natural_cspline_init(bp, l2, cl) || !is3d::natural_cspline_init(bp, zz, cz))
+            return fail(IS3D_EINVAL, "df_mode 4: bulkPi/Peq(lambda) is not ascending at T_avg = %.6g GeV (GSL would abort here)", fq->T_avg);
+        P.nj = (int)bp.size();
+        for (const auto *v : {&bp, &l2, &zz, &cl, &cz}) jon.insert(jon.end(), v->begin(), v->end());
+    } else {
+        P.nj = 2;   // unused placeholder so that the prep kernel's LDS layout stays valid
+        jon.assign(10, 0.0);
+        jon[1] = 1.0;
+    }
+    HIP_TRY(P.d_jonah.upload(jon));
+    std::vector<double> lane_mass(P.Lpad, 1.0);
+    std::vector<int32_t> lane_cls(P.Lpad, 0);
+    for (int sl = 0; sl < P.split; sl++)   // every slot of a bin carries the bin's class
+        for (int s = 0; s < P.Lbins; s++) { lane_mass[sl * P.Lbins + s] = k.cmass[lt.order[s] / P.npT]; lane_cls[sl * P.Lbins + s] = lt.order[s] / P.npT; }
+    HIP_TRY(P.d_lane_mass.upload(lane_mass));
+    HIP_TRY(P.d_lane_cls.upload(lane_cls));
+    HIP_TRY(P.d_cls_mass.upload(k.cmass));
+    HIP_TRY(P.d_cls_sign.upload(k.csign));
+    if (P.baryon) HIP_TRY(P.d_cls_baryon.upload(k.cbar));
+    return IS3D_OK;
+}
+
+// ---- tiling and pass / chunk sizing: the tile grid, bytes of streams per cell, cells per pass, waves per workgroup, chunks ----
+static int plan_tiling_and_sizing(is3d_plan &P, const is3d_df_tables *df, const is3d_options *o, int64_t max_cells)
+{
+    is3d::main_tile_shape(P.variant, P.dim3 ? 1 : 0, &P.JT, &P.KT);
+    P.jtiles = (P.J + P.JT - 1) / P.JT;
+    const bool tiled = P.variant != 1;
+    if (!P.feqmod && is3d::prep_lds_bytes(df->n_T, P.spl.nspl, P.J, P.K, P.baryon ? 1 : 0, tiled ? is3d::unit_rec_doubles(P.JT, P.KT, P.baryon ? 1 : 0) : 0, P.dim3 ? 1 : 0,
+                                    (tiled && P.dim3) ? P.jtiles * ((P.K + P.KT - 1) / P.KT) : 0) > 160 * 1024)
+        return fail(IS3D_EINVAL, "grids too large for the prep kernel's LDS staging");
+    P.rblocks = tiled ? (P.K + P.KT - 1) / P.KT : 1;
+    P.ktiles = P.dim3 ? (P.K + P.KT - 1) / P.KT : 1;   // k tiles are separate tasks only in 3+1D
+    P.upc = (tiled && !P.dim3) ? P.rblocks : 1;            // 2+1D: eta blocks are consecutive units of one stream
+    if (P.feqmod && is3d::prep_feqmod_lds_bytes(df->n_T, P.nj, P.ngl, P.J, P.K, P.jtiles, P.rblocks, is3d::unit_rec_doubles(P.JT, P.KT, 0)) > 160 * 1024)
+        return fail(IS3D_EINVAL, "grids too large for the prep kernel's LDS staging");
+    if (tiled)
+        P.bytes_per_cell = sizeof(double) * (size_t)P.jtiles * P.rblocks * is3d::unit_rec_doubles(P.JT, P.KT, (P.baryon && !P.feqmod) ? 1 : 0);
+    else
+        P.bytes_per_cell = sizeof(double) * ((size_t)P.K * is3d::kS1Rec + (size_t)P.J * is3d::kS2Rec + (size_t)P.J * P.K);
+    if (P.e2tab) P.bytes_per_cell += sizeof(double) * (size_t)P.jtiles * is3d::kE2Stride * P.JT;
+    if (P.feqmod)   // fallback record, flag, list entry; df_mode 3: cell record + |renorm| per class
+        P.bytes_per_cell += sizeof(double) * is3d::kFbRec + 2 * sizeof(int32_t) +
+                             (o->df_mode == 3 ? sizeof(double) * ((size_t)is3d::kCrRec + P.ncls) : 0);
+    // cap on the derived streams of one pass: the caller's, else 16 GiB or 45 % of the device's TOTAL memory, whichever is larger (288 GB of
+    // HBM: a 1e6-cell surface with baryon slots -- 20.6 KB per cell -- stays a single pass; only what max_cells needs is allocated).  The
+    // total, not what happens to be free: the pass count, the chunk count and with them the summation order of a surface that needs several
+    // passes must not depend on what else occupies the GPU at the moment (the partial slab below adds up to 12 GiB on top; an allocation that
+    // does not fit is reported as IS3D_ENOMEM with the sizes, and opts.workspace_bytes sets the cap explicitly)
+    const int64_t ws = is3d::default_stream_cap_bytes(o->workspace_bytes);   // cf_launch.h: one rule for every plan
+    int64_t pc = ws / (int64_t)P.bytes_per_cell;
+    if (pc < 1) pc = 1;
+    if (pc > max_cells) pc = max_cells;
+    if (pc > 0x7fff0000LL) pc = 0x7fff0000LL;
+    P.pass_cells = pc;
+    P.max_cells = max_cells;
+
+    const int lane_waves = P.Lpad / 64;
+    P.wpb = 4;
+    if (tiled) {
+        P.wpb = is3d::waves_per_group(lane_waves, o->waves_per_group);
+        if (o->waves_per_group == 1 && P.e2tab) P.wpb = 1;   // cf_main_tile3e: one-wave workgroups (no barrier partner)
+        if (P.variant == 9) P.wpb = 1;                       // cf_main_tile3s: a workgroup IS one wave
+        // cf_main_feqmod, 3+1D 8 x 7 without baryon slots: one-wave workgroups (cf_feqmod.hip, LDSD); the pipelined A/B form (variant 5) keeps two
+        // -- the default there since round 4 (486 against 501 ms on the config-3 surface, profiles/r04_ab_feqmod.log); waves_per_group = 2 keeps the pair
+        if (P.feqmod && P.dim3 && (P.variant == 3 || P.variant == 6) && (o->waves_per_group == 1 || o->waves_per_group == 0)) P.wpb = 1;
+    }
+    // Chunk count (is3d::chunk_count): ~12 rounds of the chip (24 until the end of round 3 -- on a 125 000-cell shard 144 instead of 288 chunks run
+    // the same 43.1 ms and reduce 0.3 ms less) and chunks of at most ~1152 cells: the fabric / HBM-side traffic of the main kernel drops 3x (config 3:
+    // FETCH_SIZE 1.82e8 -> 5.99e7 KiB per launch) at an unchanged step time (the main kernel gains what the 1.3 ms of extra partial-slab reduction
+    // cost; 1.0 point less culling because every chunk warms its thresholds up anew).  Partial slabs: one 9.8 MB slab per chunk on config 3,
+    // 869 chunks = 8.5 GB under the 12 GiB cap (it was 2 GiB = 219 chunks until round 3).
+    static const int64_t kChunkRounds = [] { const char *e = is3d::dev_env("IS3D_CHUNK_ROUNDS"); const int v = e ? atoi(e) : 0; return (int64_t)(v > 0 ? v : 12); }();   // dev A/B
+    P.nch_max = is3d::chunk_count(kChunkRounds, (int64_t)lane_waves * P.jtiles * P.ktiles, pc, o->cell_chunks, (int64_t)P.J * P.Kacc * P.Lpad * (int64_t)sizeof(double));
+    return IS3D_OK;
+}
+
+// one stream or slab of the plan: out of device memory is reported with the sizes that decide it
+static int plan_big_alloc(is3d_plan &P, DevBuf<double> &buf, size_t count, const char *what)
+{
+    const hipError_t e = buf.alloc(count);
+    if (e == hipErrorOutOfMemory) return is3d::oom_report(what, count * sizeof(double), P.pass_cells, P.bytes_per_cell, P.nch_max);
+    if (e != hipSuccess) return fail(IS3D_ENODEVICE, "hipMalloc(%s) failed: %s", what, hipGetErrorString(e));
+    return IS3D_OK;
+}
+
+// ---- allocation: the streams of one pass, the partial slabs, the status words, the modified-equilibrium workspaces ----
+static int plan_allocate(is3d_plan &P, const is3d_options *o)
+{
+    const size_t pc = (size_t)P.pass_cells;
+    if (P.variant != 1) {
+        // unpredicated direct-to-LDS staging over-reads a short last batch (cf_main_tile3e, cf_main_tile variant 8)
+        const size_t slack = (size_t)is3d::tile3e_stream_slack_doubles(P.JT, P.KT) + 16 * (size_t)is3d::unit_rec_doubles(P.JT, P.KT, 1);
+        if (int rc = plan_big_alloc(P, P.d_TS, pc * P.jtiles * P.rblocks * is3d::unit_rec_doubles(P.JT, P.KT, (P.baryon && !P.feqmod) ? 1 : 0) + slack, "the unit-record stream")) return rc;
+        if (P.e2tab) {
+            if (int rc = plan_big_alloc(P, P.d_TE, pc * P.jtiles * is3d::kE2Stride * P.JT + slack, "the E2 table stream")) return rc;
+            P.ub3e = is3d::tile3e_units_per_batch(P.JT, P.KT, P.npT, P.wpb, P.baryon ? 1 : 0, P.variant == 10 ? 1 : P.variant == 12 ? 2 : 0);
+            if (P.ub3e < 1) return fail(IS3D_EINVAL, "kernel_variant 5: a unit record plus its %d x %d E2 table does not fit the LDS budget", P.npT, P.JT);
+        }
+    } else {
+        HIP_TRY(P.d_S1.alloc(pc * P.K * is3d::kS1Rec));
+        HIP_TRY(P.d_S2.alloc(pc * P.J * is3d::kS2Rec));
+        HIP_TRY(P.d_S3.alloc(pc * P.J * P.K));
+    }
+    if (int rc = plan_big_alloc(P, P.d_partial, (size_t)(P.nch_max + is3d::kTaperExtra /* the tapered tail: chunk_plan */) * P.J * P.Kacc * P.Lpad, "the per-chunk partial spectra")) return rc;
+    if (P.e2tab) HIP_TRY(P.d_cull_floor.alloc((size_t)P.jtiles * P.ktiles * P.Lpad));
+    HIP_TRY(P.d_status.alloc(8));
+    HIP_TRY(P.d_sticky.upload(std::vector<unsigned long long>{~0ULL, ~0ULL}));
+    if (P.feqmod) {
+        HIP_TRY(P.d_FB.alloc(pc * is3d::kFbRec));
+        HIP_TRY(P.d_flag.alloc(pc));
+        HIP_TRY(P.d_list.alloc(pc));
+        HIP_TRY(P.d_count.alloc(1));
+        if (o->df_mode == 3) {
+            HIP_TRY(P.d_CR.alloc(pc * is3d::kCrRec));
+            HIP_TRY(P.d_RN.alloc(pc * P.ncls));
+        }
+    }
+    P.workspace = (int64_t)(P.d_S1.n + P.d_S2.n + P.d_S3.n + P.d_TS.n + P.d_TE.n + P.d_partial.n + P.d_FB.n + P.d_CR.n + P.d_RN.n) * (int64_t)sizeof(double) +
+                  (int64_t)(P.d_flag.n + P.d_list.n) * (int64_t)sizeof(int32_t);
+    return IS3D_OK;
+}
+
 static int plan_create_impl(is3d_plan **out, const is3d_species *sp, const is3d_grid *g, const is3d_df_tables *df,
                             const is3d_feqmod_tables *fq, const is3d_options *o, int64_t max_cells)
 {
@@ -163,387 +459,25 @@ static int plan_create_impl(is3d_plan **out, const is3d_species *sp, const is3d_
     P->ny_eff = P->Kacc;
     P->nout = (int64_t)P->npart * P->npT * P->J * P->ny_eff;
     P->prefactor = std::pow(2.0 * M_PI * is3d::kHbarC, -3);  // smooth_kernels.cpp:36
-    // Default kernel per mode (A/B on MI355X):
-    //   3+1D delta-f without baryon slots, pT grid <= 32: variant 6 -- 8 x 7 tile, phi-side exponentials from the E2 table stream,
-    //     rows tested for liveness before their exponential (config 3: 354 ms against 404 ms for variant 3);
-    //   3+1D otherwise: 8 x 7 (modified equilibrium: 1005 vs 1028 ms for 6 x 7), 6 x 7 with the baryon slots;
-    //   2+1D delta-f: 8 x 61; with few momentum bins variant 7 -- 8 x 31 tile with unit-strided lanes, when that fills the waves
-    //     (config 2, 96 bins: 31.4 ms against 38.7 ms).
-    auto split_for = [&](int n_bins) {   // lane slots per bin for variant 7: S in {1, 2, 4} dividing the units per cell
-        int JT7 = 0, R7 = 0, S_best = 1;
-        is3d::main_tile_shape(7, 0, &JT7, &R7);
-        const int rblocks7 = (g->n_eta + R7 - 1) / R7;
-        double best = 1.0 - (double)n_bins / (double)(((n_bins + 63) / 64) * 64);
-        for (int S : {2, 4}) {
-            if (rblocks7 % S) continue;
-            const int tot = n_bins * S, pad = ((tot + 127) / 128) * 128;   // whole 2-wave workgroups
-            const double waste = 1.0 - (double)tot / (double)pad;
-            if (waste < best - 0.05) { best = waste; S_best = S; }
-        }
-        return S_best;
-    };
-    const bool plain3 = o->dimension == 3 && !o->include_baryon;
-    // (modified equilibrium in 3+1D: 8 x 7 with or without the baryon slots -- its records do not grow with them; 247.1 against 260.5 ms for 6 x 7 per 3e5 cells)
-    int default_variant = (plain3 || (fq && o->dimension == 3)) ? 3 : 2;
-    if (!fq && o->dimension == 3 && g->n_pT <= is3d::kE2Stride) default_variant = 6;   // with or without baryon slots
-    P->variant = (o->kernel_variant >= 1 && o->kernel_variant <= 13) ? o->kernel_variant : default_variant;
-    // The shipped library holds the kernels the defaults reach (cf_kernels.hip::launch_variant, cf_feqmod.hip): any other request runs the default --
-    // status.kernel_variant says which one ran.  One explicit choice is honoured: the 8 x 7 tile without the E2 table stream (3) for a 3+1D delta-f
-    // surface without baryon slots, which is also the default for pT grids of more than 32 values.  The A/B forms of rounds 1-5 (1, 2, 4, 5, 8, 9; the
-    // modified-equilibrium row walks 5, 6 and 61-row tiles) exist in the developer build (make DEV=1), where tests/test_gpu_devlib.py runs their parity tests.
-    const bool ab_variants = is3d::kDevBuild;
-    if (!ab_variants && !(!fq && plain3 && P->variant == 3)) P->variant = default_variant;
-    // modified equilibrium in 2+1D: variant 7 (8 x 31 tile, unit-strided lanes, rows tested against the unit's threshold from the beta minimum
-    // they carry) is the default since round 4; variants 2-4 keep the round-1 row walk on the 61-row tiles for A/B
-    if (fq && o->dimension == 2 && !(ab_variants && o->kernel_variant >= 2 && o->kernel_variant <= 4)) P->variant = 7;
-    if ((P->variant == 7 || P->variant == 8) && o->dimension == 3) P->variant = default_variant;
-    if (P->variant == 8 && fq) P->variant = 7;
-    if (P->variant == 8 && o->include_baryon) P->variant = 7;   // variant 8 = variant 7 with the register-staged copy (A/B), without baryon slots only   // unit-strided lanes: the 2+1D delta-f tile kernel
-    const bool e2ok = o->dimension == 3 && !fq && g->n_pT <= is3d::kE2Stride;   // the E2 table stream exists for the 3+1D delta-f kernels
-    // (modified equilibrium in 3+1D: variants 5 and 6 are A/B forms of its 8 x 7 kernel -- rows pipelined as in round 1 / row mask with the exact
-    // per-row thresholds, cf_feqmod.hip -- without baryon slots)
-    const bool fq56 = fq && plain3;
-    // variant 9 (round 5, developer build): cf_main_tile3s, the E2-table kernel with its unit records on the scalar path -- 3+1D delta-f without baryon slots only
-    if (P->variant >= 9 && P->variant <= 13 && !(e2ok && plain3 && is3d::kDevBuild)) P->variant = default_variant;   // measured and dropped: the developer build keeps them for A/B
-    if ((P->variant == 5 || P->variant == 6) && !e2ok && !fq56) P->variant = (fq || !plain3) ? default_variant : 3;
-    P->e2tab = (P->variant == 5 || P->variant == 6 || (P->variant >= 9 && P->variant <= 13)) && e2ok;
-
-    // ---- species classes: identical (mass, sign) => identical integrand up to the degeneracy ----
-    std::vector<int> cls(P->npart);
-    // (with include_baryon the baryon number enters f_eq and delta-f, so it is part of the class key)
+    // species classes: identical (mass, sign) => identical integrand up to the degeneracy; with include_baryon the baryon number enters f_eq
+    // and delta-f, so it is part of the class key
     P->baryon = o->include_baryon != 0;
     P->baryondiff = P->baryon && o->include_baryondiff_deltaf != 0;
-    std::vector<double> cmass, csign, cbar;
-    const bool collapse = (o->collapse_species != 2);
-    for (int s = 0; s < P->npart; s++) {
-        int found = -1;
-        const double bs = P->baryon ? sp->baryon[s] : 0.0;
-        if (collapse)
-            for (size_t c = 0; c < cmass.size(); c++)
-                if (cmass[c] == sp->mass[s] && csign[c] == sp->sign[s] && cbar[c] == bs) { found = (int)c; break; }
-        if (found < 0) { found = (int)cmass.size(); cmass.push_back(sp->mass[s]); csign.push_back(sp->sign[s]); cbar.push_back(bs); }
-        cls[s] = found;
-    }
-    P->ncls = (int)cmass.size();
-    P->sp_cls.assign(cls.begin(), cls.end());
-    P->cls_mass = cmass; P->cls_sign = csign; P->cls_bar = cbar;
+    const is3d::SpeciesClasses k = is3d::species_classes(sp->mass, sp->sign, P->baryon ? sp->baryon : nullptr, sp->n, o->collapse_species != 2);
+    P->ncls = (int)k.cmass.size();
+    P->sp_cls = k.cls;
+    P->cls_mass = k.cmass; P->cls_sign = k.csign; P->cls_bar = k.cbar;
     P->pT_grid.assign(g->pT, g->pT + g->n_pT);
     P->sp_deg.assign(sp->degeneracy, sp->degeneracy + sp->n);
     P->Lbins = P->ncls * P->npT;
-    // unit-strided lanes (variant 7, 2+1D): S lane slots per bin so that the slots fill whole waves (96 bins: 128 slots = 25 %
-    // idle lanes with S = 1, 384 = 6 full waves with S = 4); S must divide the units per cell and the units per LDS batch (4)
-    P->split = 1;
-    // default in 2+1D: the 8 x 31 tile, with or without extra lane slots (305 species, one slot per bin: 96.0 against 101.0 ms for 8 x 61 per 2e4 cells)
-    if (!fq && o->dimension == 2 && !(ab_variants && o->kernel_variant >= 1 && o->kernel_variant <= 8)) P->variant = 7;   // (9 is 3+1D only)
-    if (P->variant == 7 || P->variant == 8) P->split = split_for(P->Lbins);
-    if (fq && o->dimension == 2 && P->variant != 7) {
-        // modified equilibrium, 2+1D, the 61-row tiles (A/B): the same lane slots on the kernel's own tile -- S = 2 when it divides the units per cell and
-        // the units per LDS batch (cf_main_feqmod stages 1536 / REC units) and fills the two-wave workgroups better
-        int JTf = 0, Rf = 0;
-        is3d::main_tile_shape(P->variant, 0, &JTf, &Rf);
-        const int recf = 4 * JTf + Rf * (4 + JTf), ubf = std::max(1, 1536 / recf), rblocksf = (g->n_eta + Rf - 1) / Rf;
-        const int nb = P->Lbins;
-        const double waste1 = 1.0 - (double)nb / (double)(((nb + 63) / 64) * 64);
-        const double waste2 = 1.0 - (double)(2 * nb) / (double)(((2 * nb + 63) / 64) * 64);
-        if (rblocksf % 2 == 0 && ubf % 2 == 0 && waste2 < waste1 - 0.05) P->split = 2;
-    }
-    P->L = P->Lbins * P->split;
-    P->Lpad = ((P->L + 63) / 64) * 64;
-    // lane slots sorted by mT: a wave then holds momenta of similar energy, which is what makes the exact-zero
-    // row culling of the main kernel wave-uniform more often (and keeps exp arguments of a wave close together)
-    std::vector<double> mT(P->Lpad, 1.0), pT(P->Lpad, 0.0), sg(P->Lpad, 1.0), lb(P->Lpad, 0.0);
-    std::vector<int32_t> lsub(P->Lpad, 0);
-    std::vector<int> order(P->Lbins), slot_of(P->Lbins);
-    std::vector<double> mT_nat(P->Lbins);
-    for (int c = 0; c < P->ncls; c++)
-        for (int i = 0; i < P->npT; i++) {
-            double m = cmass[c], p = g->pT[i];
-            mT_nat[c * P->npT + i] = std::sqrt(m * m + p * p);  // :259
-            order[c * P->npT + i] = c * P->npT + i;
-        }
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return mT_nat[a] < mT_nat[b]; });
-    {
-        // dev A/B (IS3D_LANE_INTERLEAVE=1, developer build): the two waves of a workgroup take the even and the odd slots of their 128-slot span of
-        // the mT order instead of its lower and upper half -- both then cover the same mT range, cull the same units and rows, and meet at the
-        // per-batch barrier with (nearly) the same work done
-        static const bool inter = is3d::dev_env("IS3D_LANE_INTERLEAVE") != nullptr;
-        if (inter && o->dimension == 3 && !fq) {
-            std::vector<int> o2(order);
-            for (int b = 0; b + 128 <= P->Lbins; b += 128)
-                for (int i = 0; i < 64; i++) { o2[b + i] = order[b + 2 * i]; o2[b + 64 + i] = order[b + 2 * i + 1]; }
-            order.swap(o2);
-        }
-    }
-    for (int s = 0; s < P->Lbins; s++) {
-        const int nat = order[s], c = nat / P->npT, i = nat % P->npT;
-        slot_of[nat] = s;
-        for (int sl = 0; sl < P->split; sl++) {   // slot (bin s, sub sl) = sl * Lbins + s
-            const int t = sl * P->Lbins + s;
-            mT[t] = mT_nat[nat];
-            pT[t] = g->pT[i];
-            sg[t] = csign[c];
-            lb[t] = cbar[c];
-            lsub[t] = sl;
-        }
-    }
-    for (int s = 0; s < P->L; s++) { P->mTmax = std::max(P->mTmax, mT[s]); P->pTmax = std::max(P->pTmax, std::fabs(pT[s])); }
-    std::vector<int> lane_sp((size_t)P->npart * P->npT);
-    for (int s = 0; s < P->npart; s++)
-        for (int i = 0; i < P->npT; i++) lane_sp[(size_t)s * P->npT + i] = slot_of[cls[s] * P->npT + i];
-    std::vector<double> deg(sp->degeneracy, sp->degeneracy + P->npart);
-    std::vector<double> cosphi(P->J), sinphi(P->J);
-    for (int j = 0; j < P->J; j++) { cosphi[j] = std::cos(g->phi[j]); sinphi[j] = std::sin(g->phi[j]); }  // :43-48
-    std::vector<double> kgrid(P->K), kweight(P->K, 1.0);
-    for (int k = 0; k < P->K; k++) {
-        kgrid[k] = P->dim3 ? g->y[k] : g->eta[k];
-        if (!P->dim3) kweight[k] = g->eta_w[k];
-    }
-    P->kmin = *std::min_element(kgrid.begin(), kgrid.end());
-    P->kmax = *std::max_element(kgrid.begin(), kgrid.end());
-    if (!P->dim3) {
-        P->gw2d = 0.0;
-        for (int k = 0; k < P->K; k++) P->gw2d = std::max(P->gw2d, std::fabs(kweight[k]) * std::cosh(kgrid[k]));
-    }
-    HIP_TRY(P->d_mT.upload(mT));
-    HIP_TRY(P->d_pT.upload(pT));
-    HIP_TRY(P->d_sign.upload(sg));
-    HIP_TRY(P->d_lane_b.upload(lb));
-    HIP_TRY(P->d_lane_sub.upload(lsub));
-    if (P->e2tab) {
-        std::vector<int32_t> ipT(P->Lpad, 0);
-        for (int s = 0; s < P->Lbins; s++) ipT[s] = order[s] % P->npT;
-        HIP_TRY(P->d_lane_ipT.upload(ipT));
-        HIP_TRY(P->d_pTgrid.upload(std::vector<double>(g->pT, g->pT + P->npT)));
-        for (int i = 0; i < P->npT; i++)
-            if (!(g->pT[i] >= 0.0)) return fail(IS3D_EINVAL, "kernel_variant 5 needs pT >= 0 (pT Dmax must be the maximum of pT D_j)");
-    }
-    HIP_TRY(P->d_degeneracy.upload(deg));
-    HIP_TRY(P->d_cls.upload(lane_sp));
-    {
-        // scaled p.dsigma of a lane: mT |A| + pT |B W| <= max(mT/mTmax, pT/pTmax) (mTmax |A| + pTmax |B W|) <= that factor (cf_pds_bound)
-        std::vector<int32_t> pe(P->Lpad, 0);
-        for (int s = 0; s < P->L; s++) {
-            const double f = std::max(P->mTmax > 0.0 ? mT[s] / P->mTmax : 1.0, P->pTmax > 0.0 ? std::fabs(pT[s]) / P->pTmax : 0.0);
-            int e = 0;
-            (void)std::frexp(f * (1.0 + 1.0e-12), &e);     // f (1 + eps) = m 2^e, m in [0.5, 1): f < 2^e with room for the roundings
-            pe[s] = std::min(e, 0);                        // the clamp keeps the scaled p.dsigma in [0, 1] whatever the lane
-        }
-        HIP_TRY(P->d_lane_pe.upload(pe));
-    }
-    HIP_TRY(P->d_cosphi.upload(cosphi));
-    HIP_TRY(P->d_sinphi.upload(sinphi));
-    HIP_TRY(P->d_kgrid.upload(kgrid));
-    HIP_TRY(P->d_kweight.upload(kweight));
-    {
-        std::vector<double> kch(P->K), ksh(P->K);
-        for (int k = 0; k < P->K; k++) { kch[k] = std::cosh(0.0 - kgrid[k]); ksh[k] = std::sinh(0.0 - kgrid[k]); }   // smooth_kernels.cpp:279-280 with y = 0
-        HIP_TRY(P->d_kch.upload(kch));
-        HIP_TRY(P->d_ksh.upload(ksh));
-    }
-    {
-        std::vector<double> ck, sk;
-        is3d::vn_harmonics(g->phi, P->J, ck, sk);
-        HIP_TRY(P->d_coskphi.upload(ck));
-        HIP_TRY(P->d_sinkphi.upload(sk));
-        HIP_TRY(P->d_phiw.alloc(P->J));
-        HIP_TRY(P->d_pTw.alloc(P->npT));
-    }
 
-    // ---- splines (deltafReader.cpp:300-322) ----
-    const double *tabs[3] = {nullptr, nullptr, nullptr};
-    int nspl;
-    if (P->feqmod) {
-        // df_mode 3: F, betabulk, betapi; df_mode 4 reads betapi only (the other two slots mirror it, unused)
-        tabs[0] = (o->df_mode == 3) ? df->F : df->betapi;
-        tabs[1] = (o->df_mode == 3) ? df->betabulk : df->betapi;
-        tabs[2] = df->betapi;
-        nspl = 3;
-    } else if (!P->ce) { tabs[0] = df->c0; tabs[1] = df->c2; nspl = 2; }
-    else { tabs[0] = df->F; tabs[1] = df->betabulk; tabs[2] = df->betapi; nspl = 3; }
-    std::vector<double> xs(df->T, df->T + df->n_T);
-    HIP_TRY(P->d_splx.upload(xs));
-    P->spl.n = df->n_T;
-    P->spl.x = P->d_splx.p;
-    P->spl.nspl = nspl;
-    for (int s = 0; s < 3; s++) { P->spl.y[s] = nullptr; P->spl.c[s] = nullptr; }
-    for (int s = 0; s < nspl; s++) {
-        std::vector<double> ys(tabs[s], tabs[s] + df->n_T), cs;
-        if (!is3d::natural_cspline_init(xs, ys, cs)) return fail(IS3D_EINVAL, "spline construction failed");
-        HIP_TRY(P->d_sply[s].upload(ys));
-        HIP_TRY(P->d_splc[s].upload(cs));
-        P->spl.y[s] = P->d_sply[s].p;
-        P->spl.c[s] = P->d_splc[s].p;
-    }
-    if (P->baryon) {
-        // full (mu_B, T) grids for the bilinear branch (deltafReader.cpp:412-484)
-        const double *t5[5];
-        if (!P->ce && !fq) { t5[0] = df->c0; t5[1] = df->c1; t5[2] = df->c2; t5[3] = df->c3; t5[4] = df->c4; }
-        else { t5[0] = df->F; t5[1] = df->G; t5[2] = df->betabulk; t5[3] = df->betaV; t5[4] = df->betapi; }
-        std::vector<double> bs(df->muB, df->muB + df->n_muB);
-        HIP_TRY(P->d_bilT.upload(xs));
-        HIP_TRY(P->d_bilB.upload(bs));
-        P->bil.nT = df->n_T; P->bil.nB = df->n_muB;
-        P->bil.swap = o->reference_bilinear_indexing != 0;
-        P->bil.T = P->d_bilT.p; P->bil.muB = P->d_bilB.p;
-        for (int k = 0; k < 5; k++) {
-            std::vector<double> tv(t5[k], t5[k] + (size_t)df->n_T * df->n_muB);
-            HIP_TRY(P->d_biltab[k].upload(tv));
-            P->bil.tab[k] = P->d_biltab[k].p;
-        }
-    }
-    if (P->feqmod) {
-        P->ngl = fq->n_gla;
-        P->detA_min = fq->deta_min;
-        P->mass_pion0 = fq->mass_pion0;
-        std::vector<double> gl((size_t)4 * P->ngl);
-        for (int k = 0; k < P->ngl; k++) {
-            gl[k] = fq->root1[k]; gl[P->ngl + k] = fq->weight1[k]; gl[2 * P->ngl + k] = fq->root2[k]; gl[3 * P->ngl + k] = fq->weight2[k];
-        }
-        HIP_TRY(P->d_gl.upload(gl));
-        std::vector<double> jon;
-        if (o->df_mode == 4) {
-            std::vector<double> bp, l2, zz, cl, cz;
-            is3d::jonah_tables(fq, bp, l2, zz, P->bp_max);
-            // gsl_spline_init on (bulkPi_over_Peq, lambda_squared) and (bulkPi_over_Peq, z), deltafReader.cpp:311-320
-            if (!is3d::natural_cspline_init(bp, l2, cl) || !is3d::natural_cspline_init(bp, zz, cz))
-                return fail(IS3D_EINVAL, "df_mode 4: bulkPi/Peq(lambda) is not ascending at T_avg = %.6g GeV (GSL would abort here)", fq->T_avg);
-            P->nj = (int)bp.size();
-            for (const auto *v : {&bp, &l2, &zz, &cl, &cz}) jon.insert(jon.end(), v->begin(), v->end());
-        } else {
-            P->nj = 2;   // unused placeholder so that the prep kernel's LDS layout stays valid
-            jon.assign(10, 0.0);
-            jon[1] = 1.0;
-        }
-        HIP_TRY(P->d_jonah.upload(jon));
-        std::vector<double> lane_mass(P->Lpad, 1.0);
-        std::vector<int32_t> lane_cls(P->Lpad, 0);
-        for (int sl = 0; sl < P->split; sl++)   // every slot of a bin carries the bin's class
-            for (int s = 0; s < P->Lbins; s++) { lane_mass[sl * P->Lbins + s] = cmass[order[s] / P->npT]; lane_cls[sl * P->Lbins + s] = order[s] / P->npT; }
-        HIP_TRY(P->d_lane_mass.upload(lane_mass));
-        HIP_TRY(P->d_lane_cls.upload(lane_cls));
-        HIP_TRY(P->d_cls_mass.upload(cmass));
-        HIP_TRY(P->d_cls_sign.upload(csign));
-        if (P->baryon) HIP_TRY(P->d_cls_baryon.upload(cbar));
-    }
-
-    // ---- tiling / workspace ----
-    is3d::main_tile_shape(P->variant, P->dim3 ? 1 : 0, &P->JT, &P->KT);
-    P->jtiles = (P->J + P->JT - 1) / P->JT;
-    const bool tiled = P->variant != 1;
-    if (!fq && is3d::prep_lds_bytes(df->n_T, nspl, P->J, P->K, P->baryon ? 1 : 0, tiled ? is3d::unit_rec_doubles(P->JT, P->KT, P->baryon ? 1 : 0) : 0, P->dim3 ? 1 : 0,
-                                    (tiled && P->dim3) ? P->jtiles * ((P->K + P->KT - 1) / P->KT) : 0) > 160 * 1024)
-        return fail(IS3D_EINVAL, "grids too large for the prep kernel's LDS staging");
-    P->rblocks = tiled ? (P->K + P->KT - 1) / P->KT : 1;
-    P->ktiles = P->dim3 ? (P->K + P->KT - 1) / P->KT : 1;   // k tiles are separate tasks only in 3+1D
-    P->upc = (tiled && !P->dim3) ? P->rblocks : 1;            // 2+1D: eta blocks are consecutive units of one stream
-    if (fq && is3d::prep_feqmod_lds_bytes(df->n_T, P->nj, P->ngl, P->J, P->K, P->jtiles, P->rblocks, is3d::unit_rec_doubles(P->JT, P->KT, 0)) > 160 * 1024)
-        return fail(IS3D_EINVAL, "grids too large for the prep kernel's LDS staging");
-    if (tiled)
-        P->bytes_per_cell = sizeof(double) * (size_t)P->jtiles * P->rblocks * is3d::unit_rec_doubles(P->JT, P->KT, (P->baryon && !P->feqmod) ? 1 : 0);
-    else
-        P->bytes_per_cell = sizeof(double) * ((size_t)P->K * is3d::kS1Rec + (size_t)P->J * is3d::kS2Rec + (size_t)P->J * P->K);
-    if (P->e2tab) P->bytes_per_cell += sizeof(double) * (size_t)P->jtiles * is3d::kE2Stride * P->JT;
-    if (P->feqmod)   // fallback record, flag, list entry; df_mode 3: cell record + |renorm| per class
-        P->bytes_per_cell += sizeof(double) * is3d::kFbRec + 2 * sizeof(int32_t) +
-                             (o->df_mode == 3 ? sizeof(double) * ((size_t)is3d::kCrRec + P->ncls) : 0);
-    // cap on the derived streams of one pass: the caller's, else 16 GiB or 45 % of the device's TOTAL memory, whichever is larger (288 GB of
-    // HBM: a 1e6-cell surface with baryon slots -- 20.6 KB per cell -- stays a single pass; only what max_cells needs is allocated).  The
-    // total, not what happens to be free: the pass count, the chunk count and with them the summation order of a surface that needs several
-    // passes must not depend on what else occupies the GPU at the moment (the partial slab below adds up to 12 GiB on top; an allocation that
-    // does not fit is reported as IS3D_ENOMEM with the sizes, and opts.workspace_bytes sets the cap explicitly)
-    const int64_t ws = is3d::default_stream_cap_bytes(o->workspace_bytes);   // cf_launch.h: one rule for every plan
-    int64_t pc = ws / (int64_t)P->bytes_per_cell;
-    if (pc < 1) pc = 1;
-    if (pc > max_cells) pc = max_cells;
-    if (pc > 0x7fff0000LL) pc = 0x7fff0000LL;
-    P->pass_cells = pc;
-    P->max_cells = max_cells;
-
-    // cell chunks: enough wave-tasks for >= ~24 rounds of the chip, chunks of >= 64 cells,
-    // partial buffer <= 2 GiB
-    {
-        const int lane_waves = P->Lpad / 64;
-        // waves per workgroup: all waves of a workgroup stream the same records; idle waves (lane-wave count not a
-        // multiple) still occupy their SIMD slots, so take the size that wastes fewest, the larger one on ties
-        P->wpb = 4;
-        if (P->variant != 1) {
-            int best_waste = 1 << 30;
-            for (int w : {8, 4, 2}) {
-                int waste = ((lane_waves + w - 1) / w) * w - lane_waves;
-                if (waste * 64 < best_waste * 64 && waste < best_waste) { best_waste = waste; P->wpb = w; }
-            }
-            if (o->waves_per_group == 2 || o->waves_per_group == 4 || o->waves_per_group == 8) P->wpb = o->waves_per_group;
-            if (o->waves_per_group == 1 && P->e2tab) P->wpb = 1;   // cf_main_tile3e: one-wave workgroups (no barrier partner)
-            if (P->variant == 9) P->wpb = 1;                       // cf_main_tile3s: a workgroup IS one wave
-            // cf_main_feqmod, 3+1D 8 x 7 without baryon slots: one-wave workgroups (cf_feqmod.hip, LDSD); the pipelined A/B form (variant 5) keeps two
-            // -- the default there since round 4 (486 against 501 ms on the config-3 surface, profiles/r04_ab_feqmod.log); waves_per_group = 2 keeps the pair
-            if (P->feqmod && P->dim3 && (P->variant == 3 || P->variant == 6) && (o->waves_per_group == 1 || o->waves_per_group == 0)) P->wpb = 1;
-        }
-        const int64_t tasks_per_chunk = (int64_t)lane_waves * P->jtiles * P->ktiles;
-        const int64_t capacity = 256LL * 4 * 4;  // CUs x SIMDs x ~4 waves
-        static const int64_t kChunkRounds = [] { const char *e = is3d::dev_env("IS3D_CHUNK_ROUNDS"); const int v = e ? atoi(e) : 0; return (int64_t)(v > 0 ? v : 12); }();   // dev A/B
-        // Chunk count.  Two floors: enough tasks for ~12 rounds of the chip (load balance: lane-wave groups cull differently; 24 until the end of
-        // round 3 -- on a 125 000-cell shard 144 instead of 288 chunks run the same 43.1 ms and reduce 0.3 ms less), and chunks of at
-        // most ~1152 cells -- the streams of one (phi tile, chunk) pair are then ~5 MB, the readers' drift along them stays about the size of an
-        // XCD's 4 MB L2, and the fabric / HBM-side traffic of the main kernel drops 3x (config 3: FETCH_SIZE 1.82e8 -> 5.99e7 KiB per launch)
-        // at an unchanged step time (the main kernel gains what the 1.3 ms of extra partial-slab reduction cost; 1.0 point less culling because
-        // every chunk warms its thresholds up anew).  profiles/r03_chunks.log
-        int64_t nch = o->cell_chunks > 0 ? o->cell_chunks
-                                         : std::max<int64_t>((kChunkRounds * capacity + tasks_per_chunk - 1) / tasks_per_chunk, (pc + 1151) / 1152);
-        int64_t by_cells = std::max<int64_t>(1, pc / 64);
-        nch = std::min(nch, by_cells);
-        int64_t part_bytes_per_chunk = (int64_t)P->J * P->Kacc * P->Lpad * (int64_t)sizeof(double);
-        // partial buffer: <= 12 GiB by default (one 9.8 MB slab per chunk on config 3: 869 chunks = 8.5 GB; it was 2 GiB = 219 chunks until round 3);
-        // an explicit cell_chunks request may take up to 32 GiB
-        int64_t by_mem = std::max<int64_t>(1, ((int64_t)(o->cell_chunks > 0 ? 32 : 12) << 30) / part_bytes_per_chunk);
-        nch = std::max<int64_t>(1, std::min(nch, by_mem));
-        P->nch_max = (int)nch;
-    }
-#define BIG_ALLOC(buf, count, what)                                                                                                  \
-    do {                                                                                                                              \
-        const size_t n_ = (count);                                                                                                    \
-        hipError_t e_ = (buf).alloc(n_);                                                                                              \
-        if (e_ == hipErrorOutOfMemory) {                                                                                              \
-            (void)hipGetLastError();                                                                                                  \
-            size_t fr_ = 0, to_ = 0;                                                                                                  \
-            (void)hipMemGetInfo(&fr_, &to_);                                                                                          \
-            return fail(IS3D_ENOMEM, "out of device memory allocating %s (%.2f GB; %.2f GB free of %.2f GB): %lld cells per pass x %zu B of streams, " \
-                        "%d partial slabs -- lower opts.workspace_bytes (more passes) or opts.cell_chunks", what, n_ * sizeof(*(buf).p) / 1e9, \
-                        fr_ / 1e9, to_ / 1e9, (long long)pc, P->bytes_per_cell, P->nch_max);                                          \
-        }                                                                                                                             \
-        if (e_ != hipSuccess) return fail(IS3D_ENODEVICE, "hipMalloc(%s) failed: %s", what, hipGetErrorString(e_));                  \
-    } while (0)
-    if (tiled) {
-        // unpredicated direct-to-LDS staging over-reads a short last batch (cf_main_tile3e, cf_main_tile variant 8)
-        const size_t slack = (size_t)is3d::tile3e_stream_slack_doubles(P->JT, P->KT) + 16 * (size_t)is3d::unit_rec_doubles(P->JT, P->KT, 1);
-        BIG_ALLOC(P->d_TS, (size_t)pc * P->jtiles * P->rblocks * is3d::unit_rec_doubles(P->JT, P->KT, (P->baryon && !P->feqmod) ? 1 : 0) + slack, "the unit-record stream");
-        if (P->e2tab) {
-            BIG_ALLOC(P->d_TE, (size_t)pc * P->jtiles * is3d::kE2Stride * P->JT + slack, "the E2 table stream");
-            P->ub3e = is3d::tile3e_units_per_batch(P->JT, P->KT, P->npT, P->wpb, P->baryon ? 1 : 0, P->variant == 10 ? 1 : P->variant == 12 ? 2 : 0);
-            if (P->ub3e < 1) return fail(IS3D_EINVAL, "kernel_variant 5: a unit record plus its %d x %d E2 table does not fit the LDS budget", P->npT, P->JT);
-        }
-    } else {
-        HIP_TRY(P->d_S1.alloc((size_t)pc * P->K * is3d::kS1Rec));
-        HIP_TRY(P->d_S2.alloc((size_t)pc * P->J * is3d::kS2Rec));
-        HIP_TRY(P->d_S3.alloc((size_t)pc * P->J * P->K));
-    }
-    BIG_ALLOC(P->d_partial, (size_t)(P->nch_max + is3d::kTaperExtra /* the tapered tail: chunk_plan */) * P->J * P->Kacc * P->Lpad, "the per-chunk partial spectra");
-#undef BIG_ALLOC
-    if (P->e2tab) HIP_TRY(P->d_cull_floor.alloc((size_t)P->jtiles * P->ktiles * P->Lpad));
-    HIP_TRY(P->d_status.alloc(8));
-    HIP_TRY(P->d_sticky.upload(std::vector<unsigned long long>{~0ULL, ~0ULL}));
-    if (P->feqmod) {
-        HIP_TRY(P->d_FB.alloc((size_t)pc * is3d::kFbRec));
-        HIP_TRY(P->d_flag.alloc((size_t)pc));
-        HIP_TRY(P->d_list.alloc((size_t)pc));
-        HIP_TRY(P->d_count.alloc(1));
-        if (o->df_mode == 3) {
-            HIP_TRY(P->d_CR.alloc((size_t)pc * is3d::kCrRec));
-            HIP_TRY(P->d_RN.alloc((size_t)pc * P->ncls));
-        }
-    }
-    P->workspace = (int64_t)(P->d_S1.n + P->d_S2.n + P->d_S3.n + P->d_TS.n + P->d_TE.n + P->d_partial.n + P->d_FB.n + P->d_CR.n + P->d_RN.n) * (int64_t)sizeof(double) +
-                   (int64_t)(P->d_flag.n + P->d_list.n) * (int64_t)sizeof(int32_t);
+    is3d::LaneTable lt;
+    plan_choose_kernel(*P, g, o);
+    if ((rc = plan_lanes_and_grids(*P, g, o, k, lt))) return rc;
+    if ((rc = plan_coefficient_tables(*P, df, o))) return rc;
+    if (fq && (rc = plan_feqmod_tables(*P, fq, o, k, lt))) return rc;
+    if ((rc = plan_tiling_and_sizing(*P, df, o, max_cells))) return rc;
+    if ((rc = plan_allocate(*P, o))) return rc;
     *out = P.release();
     return IS3D_OK;
 }
@@ -706,6 +640,117 @@ static int status_finish(const is3d_plan *P, const unsigned long long h[8], int6
     return IS3D_OK;
 }
 
+// one pass of is3d_plan_execute over the cells [c0, c0 + nc), modified equilibrium: prep (+ renormalisation in df_mode 3), the main kernel, then the
+// flagged cells with the linearised delta-f; nch / nch_small: the chunk partition of the first pass (chunk_plan)
+static int exec_pass_feqmod(is3d_plan *P, const is3d_cells *cells, hipStream_t st, int pass, int64_t c0, int32_t nc, int nch_used, int nch_small)
+{
+    const is3d_options &o = P->opts;
+    is3d::FqPrepParams fp{};
+    fp.cells = is3d::cell_ptrs(*cells);
+    fp.baryon = P->baryon; fp.baryondiff = P->baryondiff; fp.bil = P->bil;
+    fp.cell0 = c0; fp.n_cells = nc; fp.J = P->J; fp.K = P->K;
+    fp.dim3 = P->dim3; fp.mode = o.df_mode;
+    fp.include_bulk = o.include_bulk_deltaf != 0; fp.include_shear = o.include_shear_deltaf != 0;
+    fp.cosphi = P->d_cosphi.p; fp.sinphi = P->d_sinphi.p; fp.kgrid = P->d_kgrid.p; fp.kweight = P->d_kweight.p;
+    fp.spl = P->spl;
+    fp.nj = P->nj;
+    fp.jx = P->d_jonah.p; fp.jl2 = fp.jx + P->nj; fp.jz = fp.jx + 2 * P->nj; fp.jcl = fp.jx + 3 * P->nj; fp.jcz = fp.jx + 4 * P->nj;
+    fp.bp_max = P->bp_max;
+    fp.mTmax = P->mTmax; fp.kmin = P->kmin; fp.kmax = P->kmax;
+    fp.pTmax = P->pTmax; fp.scale_rows = (o.df_mode == 4 && o.outflow != 0) ? 1 : 0;   // cf_main_feqmod's CLAMP instantiations
+    fp.ngl = P->ngl; fp.gl = P->d_gl.p;
+    fp.detA_min = P->detA_min; fp.mass_pion0 = P->mass_pion0;
+    fp.JT = P->JT; fp.R = P->KT; fp.jtiles = P->jtiles; fp.rblocks = P->rblocks;
+    fp.TS = P->d_TS.p; fp.CR = P->d_CR.p; fp.FB = P->d_FB.p; fp.flag = P->d_flag.p;
+    fp.status = P->d_status.p;
+    if (P->timing) HIP_TRY(hipEventRecord(P->ev_list[pass * 3 + 0], st));
+    HIP_TRY(is3d::launch_prep_feqmod(fp, st));
+    if (o.df_mode == 3)
+        HIP_TRY(is3d::launch_feqmod_renorm(P->d_CR.p, P->d_gl.p, P->ngl, P->d_cls_mass.p, P->d_cls_sign.p,
+                                           P->baryon ? P->d_cls_baryon.p : nullptr, P->ncls, nc, fp.include_bulk, P->dim3,
+                                           P->d_RN.p, st));
+    if (P->timing) HIP_TRY(hipEventRecord(P->ev_list[pass * 3 + 1], st));
+    is3d::FqMainArgs a{};
+    a.TS = P->d_TS.p; a.lane_mT = P->d_mT.p; a.lane_pT = P->d_pT.p; a.lane_sign = P->d_sign.p;
+    a.RN = P->d_RN.p; a.lane_cls = P->d_lane_cls.p; a.ncls = P->ncls;
+    a.lane_sub = P->d_lane_sub.p; a.g.split = P->split;
+    a.lane_b = P->baryon ? P->d_lane_b.p : nullptr;
+    a.partial = P->d_partial.p; a.stats = P->d_status.p;
+    a.g.upc = P->upc; a.g.zskip = (o.zero_skip == 2) ? 0 : (o.zero_skip == 1 ? 1 : 2); a.g.baryon = 0;
+    a.g.n_cells = nc; a.g.J = P->J; a.g.K = P->K; a.g.Lpad = P->Lpad; a.g.wpb = P->wpb;
+    a.g.G = (P->Lpad / 64 + P->wpb - 1) / P->wpb;
+    a.g.jtiles = P->jtiles; a.g.ktiles = P->ktiles; a.g.nch = nch_used; a.g.nch_small = nch_small;
+    a.g.NT = P->jtiles * P->ktiles * nch_used; a.g.Kacc = P->Kacc; a.g.first_pass = (pass == 0);
+    HIP_TRY(is3d::launch_main_feqmod(P->variant, P->dim3, o.outflow != 0, o.df_mode == 3, P->baryon ? 1 : 0, a, st));
+    // flagged cells (breakdown, narrow rows): ordered list, then the linearised delta-f on top of chunk 0
+    HIP_TRY(is3d::launch_feqmod_compact(P->d_flag.p, nc, P->d_list.p, P->d_count.p, P->d_status.p, st));
+    is3d::FqLinearArgs la{};
+    la.FB = P->d_FB.p; la.list = P->d_list.p; la.count = P->d_count.p;
+    la.lane_mT = P->d_mT.p; la.lane_pT = P->d_pT.p; la.lane_sign = P->d_sign.p; la.lane_mass = P->d_lane_mass.p;
+    la.lane_b = P->baryon ? P->d_lane_b.p : nullptr;
+    la.cosphi = P->d_cosphi.p; la.sinphi = P->d_sinphi.p; la.kgrid = P->d_kgrid.p; la.kweight = P->d_kweight.p;
+    la.partial = P->d_partial.p;
+    la.J = P->J; la.K = P->K; la.Kacc = P->Kacc; la.Lpad = P->Lpad; la.dim3 = P->dim3; la.mode = o.df_mode; la.Lbins = P->Lbins;
+    la.outflow = o.outflow != 0; la.regulate = o.regulate_deltaf != 0;
+    HIP_TRY(is3d::launch_feqmod_linear(la, st));
+    if (P->timing) HIP_TRY(hipEventRecord(P->ev_list[pass * 3 + 2], st));
+    return IS3D_OK;
+}
+
+// the same pass for delta-f (df_mode 1, 2): prep, the main kernel -- in two launches around the cull floors with zero_skip 3
+static int exec_pass_deltaf(is3d_plan *P, const is3d_cells *cells, hipStream_t st, int pass, int64_t c0, int32_t nc, int nch_used, int nch_small, bool use_scale)
+{
+    const is3d_options &o = P->opts;
+    is3d::PrepParams pp = fill_prep(P, cells, c0, nc);
+    pp.tiled = (P->variant != 1);
+    pp.pds_bound = use_scale ? P->d_status.p + 6 : nullptr;
+    pp.TE = P->e2tab ? P->d_TE.p : nullptr;
+    if (P->timing) HIP_TRY(hipEventRecord(P->ev_list[pass * 3 + 0], st));
+    HIP_TRY(is3d::launch_prep(pp, st));
+    if (P->timing) HIP_TRY(hipEventRecord(P->ev_list[pass * 3 + 1], st));
+
+    is3d::MainArgs a{};
+    a.S1 = P->d_S1.p; a.S2 = P->d_S2.p; a.S3 = P->d_S3.p; a.TS = P->d_TS.p;
+    a.g.upc = P->upc;
+    a.g.zskip = (o.zero_skip == 2) ? 0 : (o.zero_skip == 1 ? 1 : 2);   // 0 default: exact-zero + accumulator-relative culling; 3: + surface-relative floors (below)
+    a.lane_mT = P->d_mT.p; a.lane_pT = P->d_pT.p; a.lane_sign = P->d_sign.p; a.lane_b = P->d_lane_b.p;
+    a.g.baryon = P->baryon;
+    a.lane_pe = P->d_lane_pe.p;
+    a.partial = P->d_partial.p;
+    a.stats = P->d_status.p;
+    a.g.n_cells = nc;
+    a.g.J = P->J; a.g.K = P->K;
+    a.g.Lpad = P->Lpad;
+    a.g.wpb = P->wpb;
+    a.g.G = (P->Lpad / 64 + P->wpb - 1) / P->wpb;
+    a.g.jtiles = P->jtiles; a.g.ktiles = P->ktiles;
+    a.g.nch = nch_used; a.g.nch_small = nch_small;
+    a.g.NT = P->jtiles * P->ktiles * nch_used;
+    a.g.Kacc = P->Kacc;
+    a.g.first_pass = (pass == 0);
+    a.TE = P->e2tab ? P->d_TE.p : nullptr; a.lane_ipT = P->d_lane_ipT.p; a.g.npT = P->npT; a.g.ub = P->ub3e; a.pTgrid = P->e2tab ? P->d_pTgrid.p : nullptr;
+    a.g.split = P->split; a.lane_sub = P->d_lane_sub.p;
+    // zero_skip 3, surface-relative cull (cf_main_tile3e with outflow && regulate_deltaf; include/is3d_amd.h): an eighth of the chunks
+    // runs first with the accumulator-relative rule; their partial spectrum is a lower bound of the final one (all terms >= 0) and
+    // floors the row-cull thresholds of the other chunks, which would otherwise each start from an empty accumulator
+    static const int surf_den = [] { const char *e = is3d::dev_env("IS3D_SURFCULL_DEN"); const int v = e ? atoi(e) : 0; return v >= 2 ? v : 8; }();
+    const bool surf = o.zero_skip == 3 && P->e2tab && o.outflow != 0 && o.regulate_deltaf != 0 && nch_used >= 2 * surf_den;
+    if (surf) {
+        const int nA = nch_used / surf_den;
+        a.g.ch0 = 0; a.g.nch_run = nA;
+        HIP_TRY(is3d::launch_main(P->variant, P->ce, P->dim3, true, true, a, st));
+        HIP_TRY(is3d::launch_cull_floor(P->d_partial.p, nA, P->J, P->K, P->Kacc, P->Lpad, P->JT, P->KT, P->jtiles, P->ktiles, P->d_lane_pe.p,
+                                        2.0, P->d_cull_floor.p, st));
+        a.g.ch0 = nA; a.g.nch_run = nch_used - nA;
+        a.cull_floor = P->d_cull_floor.p;
+        HIP_TRY(is3d::launch_main(P->variant, P->ce, P->dim3, true, true, a, st));
+    } else {
+        HIP_TRY(is3d::launch_main(P->variant, P->ce, P->dim3, o.outflow != 0, o.regulate_deltaf != 0, a, st));
+    }
+    if (P->timing) HIP_TRY(hipEventRecord(P->ev_list[pass * 3 + 2], st));
+    return IS3D_OK;
+}
+
 extern "C" int is3d_plan_execute(is3d_plan *P, const is3d_cells *cells, double *dN_out, void *hip_stream, is3d_status *status)
 {
     if (!P || !cells || !dN_out) return fail(IS3D_EINVAL, "null argument");
@@ -744,105 +789,9 @@ extern "C" int is3d_plan_execute(is3d_plan *P, const is3d_cells *cells, double *
         for (int pass = 0; pass < npasses; pass++) {
             const int64_t c0 = (int64_t)pass * P->pass_cells;
             const int32_t nc = (int32_t)std::min<int64_t>(P->pass_cells, n - c0);
-            if (P->feqmod) {
-                is3d::FqPrepParams fp{};
-                fp.cells = is3d::cell_ptrs(*cells);
-                fp.baryon = P->baryon; fp.baryondiff = P->baryondiff; fp.bil = P->bil;
-                fp.cell0 = c0; fp.n_cells = nc; fp.J = P->J; fp.K = P->K;
-                fp.dim3 = P->dim3; fp.mode = o.df_mode;
-                fp.include_bulk = o.include_bulk_deltaf != 0; fp.include_shear = o.include_shear_deltaf != 0;
-                fp.cosphi = P->d_cosphi.p; fp.sinphi = P->d_sinphi.p; fp.kgrid = P->d_kgrid.p; fp.kweight = P->d_kweight.p;
-                fp.spl = P->spl;
-                fp.nj = P->nj;
-                fp.jx = P->d_jonah.p; fp.jl2 = fp.jx + P->nj; fp.jz = fp.jx + 2 * P->nj; fp.jcl = fp.jx + 3 * P->nj; fp.jcz = fp.jx + 4 * P->nj;
-                fp.bp_max = P->bp_max;
-                fp.mTmax = P->mTmax; fp.kmin = P->kmin; fp.kmax = P->kmax;
-                fp.pTmax = P->pTmax; fp.scale_rows = (o.df_mode == 4 && o.outflow != 0) ? 1 : 0;   // cf_main_feqmod's CLAMP instantiations
-                fp.ngl = P->ngl; fp.gl = P->d_gl.p;
-                fp.detA_min = P->detA_min; fp.mass_pion0 = P->mass_pion0;
-                fp.JT = P->JT; fp.R = P->KT; fp.jtiles = P->jtiles; fp.rblocks = P->rblocks;
-                fp.TS = P->d_TS.p; fp.CR = P->d_CR.p; fp.FB = P->d_FB.p; fp.flag = P->d_flag.p;
-                fp.status = P->d_status.p;
-                if (P->timing) HIP_TRY(hipEventRecord(P->ev_list[pass * 3 + 0], st));
-                HIP_TRY(is3d::launch_prep_feqmod(fp, st));
-                if (o.df_mode == 3)
-                    HIP_TRY(is3d::launch_feqmod_renorm(P->d_CR.p, P->d_gl.p, P->ngl, P->d_cls_mass.p, P->d_cls_sign.p,
-                                                       P->baryon ? P->d_cls_baryon.p : nullptr, P->ncls, nc, fp.include_bulk, P->dim3,
-                                                       P->d_RN.p, st));
-                if (P->timing) HIP_TRY(hipEventRecord(P->ev_list[pass * 3 + 1], st));
-                is3d::FqMainArgs a{};
-                a.TS = P->d_TS.p; a.lane_mT = P->d_mT.p; a.lane_pT = P->d_pT.p; a.lane_sign = P->d_sign.p;
-                a.RN = P->d_RN.p; a.lane_cls = P->d_lane_cls.p; a.ncls = P->ncls;
-                a.lane_sub = P->d_lane_sub.p; a.g.split = P->split;
-                a.lane_b = P->baryon ? P->d_lane_b.p : nullptr;
-                a.partial = P->d_partial.p; a.stats = P->d_status.p;
-                a.g.upc = P->upc; a.g.zskip = (o.zero_skip == 2) ? 0 : (o.zero_skip == 1 ? 1 : 2); a.g.baryon = 0;
-                a.g.n_cells = nc; a.g.J = P->J; a.g.K = P->K; a.g.Lpad = P->Lpad; a.g.wpb = P->wpb;
-                a.g.G = (P->Lpad / 64 + P->wpb - 1) / P->wpb;
-                a.g.jtiles = P->jtiles; a.g.ktiles = P->ktiles; a.g.nch = nch_used; a.g.nch_small = nch_small;
-                a.g.NT = P->jtiles * P->ktiles * nch_used; a.g.Kacc = P->Kacc; a.g.first_pass = (pass == 0);
-                HIP_TRY(is3d::launch_main_feqmod(P->variant, P->dim3, o.outflow != 0, o.df_mode == 3, P->baryon ? 1 : 0, a, st));
-                // flagged cells (breakdown, narrow rows): ordered list, then the linearised delta-f on top of chunk 0
-                HIP_TRY(is3d::launch_feqmod_compact(P->d_flag.p, nc, P->d_list.p, P->d_count.p, P->d_status.p, st));
-                is3d::FqLinearArgs la{};
-                la.FB = P->d_FB.p; la.list = P->d_list.p; la.count = P->d_count.p;
-                la.lane_mT = P->d_mT.p; la.lane_pT = P->d_pT.p; la.lane_sign = P->d_sign.p; la.lane_mass = P->d_lane_mass.p;
-                la.lane_b = P->baryon ? P->d_lane_b.p : nullptr;
-                la.cosphi = P->d_cosphi.p; la.sinphi = P->d_sinphi.p; la.kgrid = P->d_kgrid.p; la.kweight = P->d_kweight.p;
-                la.partial = P->d_partial.p;
-                la.J = P->J; la.K = P->K; la.Kacc = P->Kacc; la.Lpad = P->Lpad; la.dim3 = P->dim3; la.mode = o.df_mode; la.Lbins = P->Lbins;
-                la.outflow = o.outflow != 0; la.regulate = o.regulate_deltaf != 0;
-                HIP_TRY(is3d::launch_feqmod_linear(la, st));
-                if (P->timing) HIP_TRY(hipEventRecord(P->ev_list[pass * 3 + 2], st));
-                continue;
-            }
-            is3d::PrepParams pp = fill_prep(P, cells, c0, nc);
-            pp.tiled = (P->variant != 1);
-            pp.pds_bound = use_scale ? P->d_status.p + 6 : nullptr;
-            pp.TE = P->e2tab ? P->d_TE.p : nullptr;
-            if (P->timing) HIP_TRY(hipEventRecord(P->ev_list[pass * 3 + 0], st));
-            HIP_TRY(is3d::launch_prep(pp, st));
-            if (P->timing) HIP_TRY(hipEventRecord(P->ev_list[pass * 3 + 1], st));
-
-            is3d::MainArgs a{};
-            a.S1 = P->d_S1.p; a.S2 = P->d_S2.p; a.S3 = P->d_S3.p; a.TS = P->d_TS.p;
-            a.g.upc = P->upc;
-            a.g.zskip = (o.zero_skip == 2) ? 0 : (o.zero_skip == 1 ? 1 : 2);   // 0 default: exact-zero + accumulator-relative culling; 3: + surface-relative floors (below)
-            a.lane_mT = P->d_mT.p; a.lane_pT = P->d_pT.p; a.lane_sign = P->d_sign.p; a.lane_b = P->d_lane_b.p;
-            a.g.baryon = P->baryon;
-            a.lane_pe = P->d_lane_pe.p;
-            a.partial = P->d_partial.p;
-            a.stats = P->d_status.p;
-            a.g.n_cells = nc;
-            a.g.J = P->J; a.g.K = P->K;
-            a.g.Lpad = P->Lpad;
-            a.g.wpb = P->wpb;
-            a.g.G = (P->Lpad / 64 + P->wpb - 1) / P->wpb;
-            a.g.jtiles = P->jtiles; a.g.ktiles = P->ktiles;
-            a.g.nch = nch_used; a.g.nch_small = nch_small;
-            a.g.NT = P->jtiles * P->ktiles * nch_used;
-            a.g.Kacc = P->Kacc;
-            a.g.first_pass = (pass == 0);
-            a.TE = P->e2tab ? P->d_TE.p : nullptr; a.lane_ipT = P->d_lane_ipT.p; a.g.npT = P->npT; a.g.ub = P->ub3e; a.pTgrid = P->e2tab ? P->d_pTgrid.p : nullptr;
-            a.g.split = P->split; a.lane_sub = P->d_lane_sub.p;
-            // zero_skip 3, surface-relative cull (cf_main_tile3e with outflow && regulate_deltaf; include/is3d_amd.h): an eighth of the chunks
-            // runs first with the accumulator-relative rule; their partial spectrum is a lower bound of the final one (all terms >= 0) and
-            // floors the row-cull thresholds of the other chunks, which would otherwise each start from an empty accumulator
-            static const int surf_den = [] { const char *e = is3d::dev_env("IS3D_SURFCULL_DEN"); const int v = e ? atoi(e) : 0; return v >= 2 ? v : 8; }();
-            const bool surf = o.zero_skip == 3 && P->e2tab && o.outflow != 0 && o.regulate_deltaf != 0 && nch_used >= 2 * surf_den;
-            if (surf) {
-                const int nA = nch_used / surf_den;
-                a.g.ch0 = 0; a.g.nch_run = nA;
-                HIP_TRY(is3d::launch_main(P->variant, P->ce, P->dim3, true, true, a, st));
-                HIP_TRY(is3d::launch_cull_floor(P->d_partial.p, nA, P->J, P->K, P->Kacc, P->Lpad, P->JT, P->KT, P->jtiles, P->ktiles, P->d_lane_pe.p,
-                                                2.0, P->d_cull_floor.p, st));
-                a.g.ch0 = nA; a.g.nch_run = nch_used - nA;
-                a.cull_floor = P->d_cull_floor.p;
-                HIP_TRY(is3d::launch_main(P->variant, P->ce, P->dim3, true, true, a, st));
-            } else {
-                HIP_TRY(is3d::launch_main(P->variant, P->ce, P->dim3, o.outflow != 0, o.regulate_deltaf != 0, a, st));
-            }
-            if (P->timing) HIP_TRY(hipEventRecord(P->ev_list[pass * 3 + 2], st));
+            const int rc = P->feqmod ? exec_pass_feqmod(P, cells, st, pass, c0, nc, nch_used, nch_small)
+                                     : exec_pass_deltaf(P, cells, st, pass, c0, nc, nch_used, nch_small, use_scale);
+            if (rc) return rc;
         }
         HIP_TRY(is3d::launch_finalize(P->d_partial.p, P->d_cls.p, P->d_degeneracy.p, dN_out, P->nout, P->npart, P->npT, P->J,
                                       P->Kacc, P->Lpad, nch_used, P->prefactor, o.accumulate != 0,

@@ -28,12 +28,12 @@
 #include <chrono>
 #include <cmath>
 #include <memory>
-#include <map>
 #include <utility>
 #include <vector>
 
 #include "cf_host.h"
 #include "cf_math.h"
+#include "cf_plan_geometry.h"
 #include "cf_polzn.h"
 
 namespace is3d {
@@ -403,20 +403,11 @@ extern "C" int is3d_polarization_plan_create(is3d_polarization_plan **plan, cons
     P->max_cells = max_cells;
     P->ws_cap = (opts && opts->workspace_bytes > 0) ? opts->workspace_bytes : ((int64_t)16 << 30);
     // classes: one per distinct (mass, sign), in order of first appearance
-    std::map<std::pair<double, double>, int> key;
-    std::vector<int32_t> cls((size_t)P->S);
-    std::vector<double> cmass, csign, scale((size_t)P->S);
-    for (int s = 0; s < P->S; s++) {
-        auto k = std::make_pair(species->mass[s], species->sign[s]);
-        auto it = key.find(k);
-        if (it == key.end()) {
-            it = key.emplace(k, (int)cmass.size()).first;
-            cmass.push_back(species->mass[s]);
-            csign.push_back(species->sign[s]);
-        }
-        cls[(size_t)s] = it->second;
-        scale[(size_t)s] = -1.0 / (4.0 * species->mass[s]);   // 2 x -(1 / (8 m))
-    }
+    const SpeciesClasses kc = species_classes(species->mass, species->sign, nullptr, P->S, true);
+    const std::vector<int32_t> &cls = kc.cls;
+    const std::vector<double> &cmass = kc.cmass, &csign = kc.csign;
+    std::vector<double> scale((size_t)P->S);
+    for (int s = 0; s < P->S; s++) scale[(size_t)s] = -1.0 / (4.0 * species->mass[s]);   // 2 x -(1 / (8 m))
     P->ncls = (int)cmass.size();
     while (P->npTp < P->npT) P->npTp *= 2;
     P->nlw = (int)(((int64_t)P->ncls * P->npTp + 63) / 64);

@@ -43,6 +43,7 @@
 #include "cf_device.h"
 #include "cf_host.h"
 #include "cf_math.h"
+#include "cf_plan_geometry.h"
 #include "cf_sampler_bins.h"
 #include "cf_sampler_common.h"
 #include "errors.h"
@@ -370,16 +371,9 @@ int plan_base(std::unique_ptr<is3d_sampler_plan> &P, const is3d_species *species
     is3d::SamplerSpecies &sp = P->sp;
     // ---- species classes (mass, sign[, baryon number]): the density integral is per class ----
     const int npart = species->n;
-    std::vector<int32_t> cls(npart);
-    std::vector<double> cmass, csign, cbar;
-    for (int s = 0; s < npart; s++) {
-        int found = -1;
-        const double bs = baryon ? species->baryon[s] : 0.0;
-        for (size_t c = 0; c < cmass.size(); c++)
-            if (cmass[c] == species->mass[s] && csign[c] == species->sign[s] && cbar[c] == bs) { found = (int)c; break; }
-        if (found < 0) { found = (int)cmass.size(); cmass.push_back(species->mass[s]); csign.push_back(species->sign[s]); cbar.push_back(bs); }
-        cls[s] = found;
-    }
+    const is3d::SpeciesClasses kc = is3d::species_classes(species->mass, species->sign, baryon ? species->baryon : nullptr, npart, true);
+    const std::vector<int32_t> &cls = kc.cls;
+    const std::vector<double> &cmass = kc.cmass, &csign = kc.csign, &cbar = kc.cbar;
     const int ncls = (int)cmass.size();
     HIP_TRY(d_mass.upload(std::vector<double>(species->mass, species->mass + npart)));
     HIP_TRY(d_sign.upload(std::vector<double>(species->sign, species->sign + npart)));

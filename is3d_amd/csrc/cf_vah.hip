@@ -33,6 +33,7 @@
 #include "cf_host.h"
 #include "cf_launch.h"
 #include "cf_math.h"
+#include "cf_plan_geometry.h"
 #include "cf_spacetime.h"
 #include "cf_vah_coef.h"
 #include "errors.h"
@@ -838,6 +839,83 @@ struct is3d_vah_plan {
     }
 };
 
+// The stages of is3d_vah_plan_create, in its order.  What they decide without the device is in cf_plan_geometry.h, shared with cf_plan.cpp;
+// what differs between the two plans is an argument at the call.
+
+// ---- choose kernel: the factored-exponent kernel or the round-1 one, its tile, lane slots per momentum bin ----
+static int vah_choose_kernel(is3d_vah_plan &P, const is3d_options *o)
+{
+    if (o->kernel_variant != 0 && o->kernel_variant != 2 && o->kernel_variant != 3)
+        return is3d::set_error(IS3D_EINVAL, "VAH kernel_variant %d: 0 (default), 2 (round-1 kernel: 6 x 7 tile in 3+1D, 8 x 61 in 2+1D) or 3 (factored exponent: "
+                               "8 x 7 tile in 3+1D, 8 x 31 with unit-strided lanes in 2+1D)", o->kernel_variant);
+    // kernel_variant 2 (the round-1 kernel, expanded quadratic form) exists in the developer build for A/B; the shipped library runs cf_main_vah3
+    P.fact = !(is3d::kDevBuild && o->kernel_variant == 2);
+    P.JT = P.three_d ? (P.fact ? kJT3F : kJT3) : (P.fact ? kJT2F : kJT2); P.R = P.three_d ? (P.fact ? kR3F : kR3) : (P.fact ? kR2F : kR2);
+    P.jtiles = (P.J + P.JT - 1) / P.JT; P.rblocks = (P.K + P.R - 1) / P.R;
+    // unit-strided lanes (2+1D F records, as cf_plan.cpp's variant 7): S lane slots per momentum bin when that fills the waves better; S divides
+    // the units per cell (the eta table's row blocks) and the four units of an LDS buffer
+    P.split = (!P.three_d && P.fact) ? is3d::lane_split(P.Lbins, P.rblocks) : 1;
+    return IS3D_OK;
+}
+
+// ---- lanes and grids: the lane table (no baryon slots, never interleaved), the species map, the phi and y / eta grids, uploaded ----
+static int vah_lanes_and_grids(is3d_vah_plan &P, const is3d_grid *gr, const is3d::SpeciesClasses &k)
+{
+    const is3d::LaneTable lt = is3d::lane_table(k, gr->pT, P.npT, P.split, false);
+    P.Lpad = lt.Lpad;
+    HIP_TRY(P.d_lane_sub.upload(lt.sub));
+    std::vector<double> cosphi(P.J), sinphi(P.J), kgrid(P.K), kweight(P.K, 1.0);
+    for (int j = 0; j < P.J; j++) { cosphi[j] = std::cos(gr->phi[j]); sinphi[j] = std::sin(gr->phi[j]); }
+    for (int k2 = 0; k2 < P.K; k2++) {
+        kgrid[k2] = P.three_d ? gr->y[k2] : gr->eta[k2];
+        if (!P.three_d) kweight[k2] = gr->eta_w[k2] * (gr->eta[1] - gr->eta[0]);          // :2178-2187
+    }
+    HIP_TRY(P.d_mT.upload(lt.mT)); HIP_TRY(P.d_pT.upload(lt.pT)); HIP_TRY(P.d_sg.upload(lt.sign)); HIP_TRY(P.d_lane.upload(lt.lane_of)); HIP_TRY(P.d_deg.upload(P.sp_deg));
+    HIP_TRY(P.d_cos.upload(cosphi)); HIP_TRY(P.d_sin.upload(sinphi)); HIP_TRY(P.d_kg.upload(kgrid)); HIP_TRY(P.d_kw.upload(kweight));
+    // bound of |p.dsigma| over the lanes; pT as it is, where cf_plan.cpp takes |pT| (the same for the pT >= 0 grids both are given)
+    for (int s = 0; s < lt.L; s++) { P.mTmax = std::max(P.mTmax, lt.mT[s]); P.pTmax = std::max(P.pTmax, lt.pT[s]); }
+    return IS3D_OK;
+}
+
+// ---- tiling and pass / chunk sizing; returns the bytes of streams per cell ----
+static int vah_tiling_and_sizing(is3d_vah_plan &P, const is3d_options *o, size_t *bytes_per_cell)
+{
+    const bool three_d = P.three_d;
+    P.ktiles = three_d ? P.rblocks : 1; P.upc = three_d ? 1 : P.rblocks;
+    P.REC = P.fact ? 4 * P.JT + P.R * ((three_d ? 4 : 6) + P.JT) : 4 * P.JT + P.R * (4 + 2 * P.JT);
+    P.lds_prep = sizeof(is3d::VahScal) * is3d::vah_batch_cells(P.K) + sizeof(double) * ((size_t)is3d::vah_batch_cells(P.K) * (10 * P.K + 8 * P.J + 2 * P.rblocks) + (size_t)P.REC);   // + [CB][jtiles <= J] tile maxima, [CB][2 rblocks] row-block minima and the REC-entry descriptor table of the F records
+    if (P.lds_prep > 160 * 1024) return is3d::set_error(IS3D_EINVAL, "grids too large for the prep kernel's LDS staging");
+    // passes over the cell axis bounded by the workspace (default 16 GB)
+    *bytes_per_cell = sizeof(double) * (size_t)P.jtiles * P.rblocks * P.REC;
+    const int64_t ws = is3d::default_stream_cap_bytes(o->workspace_bytes);   // cf_launch.h: the rule of cf_plan.cpp, its clamp beside the partial slab included
+    P.pass_cells = std::max<int64_t>(1, std::min<int64_t>(P.max_cells, ws / (int64_t)*bytes_per_cell));
+    const int lane_waves = P.Lpad / 64;
+    P.wpb = is3d::waves_per_group(lane_waves, o->waves_per_group);
+    // cf_main_vah3, 3+1D: one-wave workgroups by default (no barrier partner; 962.2 against 974.6 ms on the config-5 surface, bitwise the same spectrum:
+    // profiles/r04_ab_vah_wpb.log); waves_per_group = 2 keeps the pair
+    if ((o->waves_per_group == 1 || o->waves_per_group == 0) && P.fact && three_d) P.wpb = 1;
+    // chunk count by the rule of cf_plan.cpp, but with 24 rounds of the chip where that plan has used 12 since round 3 (DESIGN.md lists this as an
+    // open question; the count fixes the summation order); chunks of at most ~1152 cells, partials <= 12 GiB
+    P.nch = is3d::chunk_count(24, (int64_t)lane_waves * P.jtiles * P.ktiles, P.pass_cells, o->cell_chunks, (int64_t)P.J * P.Kacc * P.Lpad * 8);
+    return IS3D_OK;
+}
+
+// ---- allocation: the unit-record stream of one pass, the partial slabs, the status words ----
+static int vah_allocate(is3d_vah_plan &P, size_t bytes_per_cell)
+{
+    const int slabs = P.nch + is3d::kTaperExtra;   // + the tapered tail of the partition (chunk_taper, at the execute)
+    for (int which = 0; which < 2; which++) {
+        const size_t bytes = which == 0 ? (size_t)P.pass_cells * bytes_per_cell + 64 * 1024   // + slack: the staging pieces of the last batch over-read the stream
+                                        : (size_t)slabs * P.J * P.Kacc * P.Lpad * sizeof(double);
+        const hipError_t e = (which == 0 ? P.d_TS : P.d_partial).alloc(bytes);
+        if (e == hipErrorOutOfMemory)
+            return is3d::oom_report(which == 0 ? "the unit-record stream" : "the per-chunk partial spectra", bytes, P.pass_cells, bytes_per_cell, slabs);
+        if (e != hipSuccess) return is3d::set_error(IS3D_ENODEVICE, "hipMalloc failed: %s", hipGetErrorString(e));
+    }
+    HIP_TRY(P.d_status.alloc(8 * sizeof(unsigned long long)));
+    return IS3D_OK;
+}
+
 extern "C" int is3d_vah_plan_create(is3d_vah_plan **out, const is3d_species *sp, const is3d_grid *gr, const is3d_vah_df_tables *tab,
                                     const is3d_options *o, int64_t max_cells)
 {
@@ -864,124 +942,34 @@ extern "C" int is3d_vah_plan_create(is3d_vah_plan **out, const is3d_species *sp,
     HIP_TRY(hipGetDevice(&P->device));
     P->three_d = three_d;
     P->max_cells = max_cells;
+    P->npart = sp->n; P->npT = gr->n_pT; P->J = gr->n_phi; P->K = three_d ? gr->n_y : gr->n_eta; P->Kacc = three_d ? P->K : 1;
+    P->nout = (int64_t)P->npart * P->npT * P->J * P->Kacc;
+    // species classes: identical (mass, sign) => identical integrand up to the degeneracy
+    const is3d::SpeciesClasses k = is3d::species_classes(sp->mass, sp->sign, nullptr, sp->n, o->collapse_species != 2);
+    P->ncls = (int)k.cmass.size();
+    P->Lbins = P->ncls * P->npT;
+    P->sp_cls = k.cls;
+    P->cls_mass = k.cmass; P->cls_sign = k.csign;
+    P->pT_grid.assign(gr->pT, gr->pT + P->npT);
+    P->sp_deg.assign(sp->degeneracy, sp->degeneracy + P->npart);
 
-    // ---- species classes and lanes sorted by mT (as cf_plan.cpp) ----
-    const int npart = sp->n, npT = gr->n_pT, J = gr->n_phi, K = three_d ? gr->n_y : gr->n_eta, Kacc = three_d ? K : 1;
-    P->npart = npart; P->npT = npT; P->J = J; P->K = K; P->Kacc = Kacc;
-    P->nout = (int64_t)npart * npT * J * Kacc;
-    std::vector<int> cls(npart);
-    std::vector<double> cmass, csign;
-    for (int s = 0; s < npart; s++) {
-        int found = -1;
-        if (o->collapse_species != 2)
-            for (size_t c = 0; c < cmass.size(); c++)
-                if (cmass[c] == sp->mass[s] && csign[c] == sp->sign[s]) { found = (int)c; break; }
-        if (found < 0) { found = (int)cmass.size(); cmass.push_back(sp->mass[s]); csign.push_back(sp->sign[s]); }
-        cls[s] = found;
-    }
-    P->sp_cls.assign(cls.begin(), cls.end());
-    P->cls_mass = cmass; P->cls_sign = csign;
-    P->pT_grid.assign(gr->pT, gr->pT + npT);
-    P->sp_deg.assign(sp->degeneracy, sp->degeneracy + npart);
-    if (o->kernel_variant != 0 && o->kernel_variant != 2 && o->kernel_variant != 3)
-        return set_error(IS3D_EINVAL, "VAH kernel_variant %d: 0 (default), 2 (round-1 kernel: 6 x 7 tile in 3+1D, 8 x 61 in 2+1D) or 3 (factored exponent: "
-                         "8 x 7 tile in 3+1D, 8 x 31 with unit-strided lanes in 2+1D)", o->kernel_variant);
-    // kernel_variant 2 (the round-1 kernel, expanded quadratic form) exists in the developer build for A/B; the shipped library runs cf_main_vah3
-    P->fact = !(is3d::kDevBuild && o->kernel_variant == 2);
-    P->JT = three_d ? (P->fact ? kJT3F : kJT3) : (P->fact ? kJT2F : kJT2); P->R = three_d ? (P->fact ? kR3F : kR3) : (P->fact ? kR2F : kR2);
-    P->jtiles = (J + P->JT - 1) / P->JT; P->rblocks = (K + P->R - 1) / P->R;
-    const int ncls = (int)cmass.size(), Lbins = ncls * npT;
-    // unit-strided lanes (2+1D F records, as cf_plan.cpp's variant 7): S lane slots per momentum bin when that fills the waves better -- S in
-    // {1, 2, 4} must divide the units per cell (the eta table's row blocks) and the four units of an LDS buffer
-    int split = 1;
-    if (!three_d && P->fact) {
-        double best = 1.0 - (double)Lbins / (double)(((Lbins + 63) / 64) * 64);
-        for (int S : {2, 4}) {
-            if (P->rblocks % S) continue;
-            const int tot = Lbins * S, pad = ((tot + 127) / 128) * 128;   // whole 2-wave workgroups
-            const double waste = 1.0 - (double)tot / (double)pad;
-            if (waste < best - 0.05) { best = waste; split = S; }
-        }
-    }
-    P->Lbins = Lbins; P->split = split;
-    const int L = Lbins * split, Lpad = ((L + 63) / 64) * 64;
-    P->ncls = ncls; P->Lpad = Lpad;
-    std::vector<double> mT(Lpad, 1.0), pT(Lpad, 0.0), sg(Lpad, 1.0), mT_nat(Lbins);
-    std::vector<int32_t> lsub(Lpad, 0);
-    std::vector<int> order(Lbins), slot_of(Lbins), lane_sp((size_t)npart * npT);
-    for (int c = 0; c < ncls; c++)
-        for (int i = 0; i < npT; i++) { mT_nat[c * npT + i] = std::sqrt(cmass[c] * cmass[c] + gr->pT[i] * gr->pT[i]); order[c * npT + i] = c * npT + i; }
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return mT_nat[a] < mT_nat[b]; });
-    for (int s = 0; s < Lbins; s++) {
-        const int nat = order[s];
-        slot_of[nat] = s;
-        for (int sl = 0; sl < split; sl++) {   // slot (bin s, sub sl) = sl * Lbins + s (cf_finalize adds a bin's slots in this order)
-            const int t = sl * Lbins + s;
-            mT[t] = mT_nat[nat]; pT[t] = gr->pT[nat % npT]; sg[t] = csign[nat / npT]; lsub[t] = sl;
-        }
-    }
-    for (int s = 0; s < npart; s++)
-        for (int i = 0; i < npT; i++) lane_sp[(size_t)s * npT + i] = slot_of[cls[s] * npT + i];
-    HIP_TRY(P->d_lane_sub.upload(lsub));
-    std::vector<double> cosphi(J), sinphi(J), kgrid(K), kweight(K, 1.0), deg(sp->degeneracy, sp->degeneracy + npart);
-    for (int j = 0; j < J; j++) { cosphi[j] = std::cos(gr->phi[j]); sinphi[j] = std::sin(gr->phi[j]); }
-    for (int k = 0; k < K; k++) {
-        kgrid[k] = three_d ? gr->y[k] : gr->eta[k];
-        if (!three_d) kweight[k] = gr->eta_w[k] * (gr->eta[1] - gr->eta[0]);          // :2178-2187
-    }
-    HIP_TRY(P->d_mT.upload(mT)); HIP_TRY(P->d_pT.upload(pT)); HIP_TRY(P->d_sg.upload(sg)); HIP_TRY(P->d_lane.upload(lane_sp)); HIP_TRY(P->d_deg.upload(deg));
-    HIP_TRY(P->d_cos.upload(cosphi)); HIP_TRY(P->d_sin.upload(sinphi)); HIP_TRY(P->d_kg.upload(kgrid)); HIP_TRY(P->d_kw.upload(kweight));
+    int rc;
+    size_t bytes_per_cell = 0;
+    if ((rc = vah_choose_kernel(*P, o))) return rc;
+    if ((rc = vah_lanes_and_grids(*P, gr, k))) return rc;
     if (tab) {
-        if (int rc = P->tab.upload(tab)) return rc;
+        if ((rc = P->tab.upload(tab))) return rc;
         P->tables = true;
         HIP_TRY(P->d_coef.alloc(sizeof(double) * 5 * (size_t)max_cells));
     }
-    for (int s2 = 0; s2 < L; s2++) { P->mTmax = std::max(P->mTmax, mT[s2]); P->pTmax = std::max(P->pTmax, pT[s2]); }
-    P->ktiles = three_d ? P->rblocks : 1; P->upc = three_d ? 1 : P->rblocks;
-    P->REC = P->fact ? 4 * P->JT + P->R * ((three_d ? 4 : 6) + P->JT) : 4 * P->JT + P->R * (4 + 2 * P->JT);
-    P->lds_prep = sizeof(is3d::VahScal) * is3d::vah_batch_cells(K) + sizeof(double) * ((size_t)is3d::vah_batch_cells(K) * (10 * K + 8 * J + 2 * P->rblocks) + (size_t)P->REC);   // + [CB][jtiles <= J] tile maxima, [CB][2 rblocks] row-block minima and the REC-entry descriptor table of the F records
-    if (P->lds_prep > 160 * 1024) return set_error(IS3D_EINVAL, "grids too large for the prep kernel's LDS staging");
-    // passes over the cell axis bounded by the workspace (default 16 GB), chunks as in cf_plan.cpp
-    const size_t bytes_per_cell = sizeof(double) * (size_t)P->jtiles * P->rblocks * P->REC;
-    const int64_t ws = is3d::default_stream_cap_bytes(o->workspace_bytes);   // cf_launch.h: the rule of cf_plan.cpp, its clamp beside the partial slab included
-    P->pass_cells = std::max<int64_t>(1, std::min<int64_t>(max_cells, ws / (int64_t)bytes_per_cell));
-    const int lane_waves = Lpad / 64;
-    int best = 1 << 30;
-    for (int w : {8, 4, 2}) { const int waste = ((lane_waves + w - 1) / w) * w - lane_waves; if (waste < best) { best = waste; P->wpb = w; } }
-    if (o->waves_per_group == 2 || o->waves_per_group == 4 || o->waves_per_group == 8) P->wpb = o->waves_per_group;
-    // cf_main_vah3, 3+1D: one-wave workgroups by default (no barrier partner; 962.2 against 974.6 ms on the config-5 surface, bitwise the same spectrum:
-    // profiles/r04_ab_vah_wpb.log); waves_per_group = 2 keeps the pair
-    if ((o->waves_per_group == 1 || o->waves_per_group == 0) && P->fact && three_d) P->wpb = 1;
-    // chunk count as in cf_plan.cpp: ~24 rounds of the chip, chunks of at most ~1152 cells (the streams of a chunk stay near the XCD's L2), partials <= 12 GiB
-    const int64_t tasks_per_chunk = (int64_t)lane_waves * P->jtiles * P->ktiles;
-    int64_t nch = o->cell_chunks > 0 ? o->cell_chunks : std::max<int64_t>((24LL * 4096 + tasks_per_chunk - 1) / tasks_per_chunk, (P->pass_cells + 1151) / 1152);
-    nch = std::min<int64_t>(nch, std::max<int64_t>(1, P->pass_cells / 64));
-    nch = std::max<int64_t>(1, std::min<int64_t>(nch, ((int64_t)(o->cell_chunks > 0 ? 32 : 12) << 30) / ((int64_t)J * Kacc * Lpad * 8)));
-    P->nch = (int)nch;
-    for (int which = 0; which < 2; which++) {
-        const size_t bytes = which == 0 ? (size_t)P->pass_cells * bytes_per_cell + 64 * 1024   // + slack: the staging pieces of the last batch over-read the stream
-                                        : (size_t)(nch + is3d::kTaperExtra /* the tapered tail of the partition, below */) * J * Kacc * Lpad * sizeof(double);
-        const hipError_t e = (which == 0 ? P->d_TS : P->d_partial).alloc(bytes);
-        if (e == hipErrorOutOfMemory) {
-            (void)hipGetLastError();
-            size_t fr = 0, to = 0;
-            (void)hipMemGetInfo(&fr, &to);
-            return set_error(IS3D_ENOMEM, "out of device memory allocating %s (%.2f GB; %.2f GB free of %.2f GB): %lld cells per pass x %zu B of streams, "
-                             "%d partial slabs -- lower opts.workspace_bytes (more passes) or opts.cell_chunks",
-                             which == 0 ? "the unit-record stream" : "the per-chunk partial spectra", bytes / 1e9, fr / 1e9, to / 1e9, (long long)P->pass_cells,
-                             bytes_per_cell, (int)(nch + is3d::kTaperExtra));
-        }
-        if (e != hipSuccess) return set_error(IS3D_ENODEVICE, "hipMalloc failed: %s", hipGetErrorString(e));
-    }
-    HIP_TRY(P->d_status.alloc(8 * sizeof(unsigned long long)));
-    {
-        std::vector<double> ck, sk;
-        is3d::vn_harmonics(gr->phi, J, ck, sk);
-        HIP_TRY(P->d_coskphi.upload(ck));
-        HIP_TRY(P->d_sinkphi.upload(sk));
-        HIP_TRY(P->d_phiw.alloc((size_t)J));
-        HIP_TRY(P->d_pTw.alloc((size_t)npT));
-    }
+    if ((rc = vah_tiling_and_sizing(*P, o, &bytes_per_cell))) return rc;
+    if ((rc = vah_allocate(*P, bytes_per_cell))) return rc;
+    std::vector<double> ck, sk;
+    is3d::vn_harmonics(gr->phi, P->J, ck, sk);
+    HIP_TRY(P->d_coskphi.upload(ck));
+    HIP_TRY(P->d_sinkphi.upload(sk));
+    HIP_TRY(P->d_phiw.alloc((size_t)P->J));
+    HIP_TRY(P->d_pTw.alloc((size_t)P->npT));
     *out = P.release();
     return IS3D_OK;
 }

@@ -33,6 +33,7 @@
 #include "cf_device.h"
 #include "cf_host.h"
 #include "cf_math.h"
+#include "cf_plan_geometry.h"
 #include "cf_vah_coef.h"
 #include "errors.h"
 
@@ -218,15 +219,9 @@ extern "C" int is3d_total_yield_vah(const is3d_vah_cells *cells, const is3d_spec
     }
     // species classes (mass, sign): the radial integrals are per class
     const int npart = species->n;
-    std::vector<int32_t> cls(npart);
-    std::vector<double> cmass, csign;
-    for (int s = 0; s < npart; s++) {
-        int found = -1;
-        for (size_t c = 0; c < cmass.size(); c++)
-            if (cmass[c] == species->mass[s] && csign[c] == species->sign[s]) { found = (int)c; break; }
-        if (found < 0) { found = (int)cmass.size(); cmass.push_back(species->mass[s]); csign.push_back(species->sign[s]); }
-        cls[s] = found;
-    }
+    const is3d::SpeciesClasses kc = is3d::species_classes(species->mass, species->sign, nullptr, npart, true);
+    const std::vector<int32_t> &cls = kc.cls;
+    const std::vector<double> &cmass = kc.cmass, &csign = kc.csign;
     const int ncls = (int)cmass.size();
     if (ncls > 65535) return set_error(IS3D_EINVAL, "%d species classes: the launch grid holds 65535", ncls);
     if (yield_by_species) memset(yield_by_species, 0, sizeof(double) * (size_t)npart);
