@@ -178,16 +178,19 @@ static void plan_choose_kernel(is3d_plan &P, const is3d_grid *g, const is3d_opti
 }
 
 // ---- lanes and grids: the lane table, the species map, the phi and y / eta grids, uploaded ----
-static int plan_lanes_and_grids(is3d_plan &P, const is3d_grid *g, const is3d_options *o, const is3d::SpeciesClasses &k, is3d::LaneTable &lt)
+static int plan_lanes_and_grids(is3d_plan &P, const is3d_grid *g, const is3d_options *o, const is3d::SpeciesClasses &k)
 {
     // dev A/B (IS3D_LANE_INTERLEAVE=1, developer build): the two waves of a workgroup take the even and the odd slots of their 128-slot span of
     // the mT order instead of its lower and upper half -- both then cover the same mT range, cull the same units and rows, and meet at the
     // per-batch barrier with (nearly) the same work done
     static const bool inter = is3d::dev_env("IS3D_LANE_INTERLEAVE") != nullptr;
-    lt = is3d::lane_table(k, g->pT, P.npT, P.split, inter && o->dimension == 3 && !P.feqmod);
+    const is3d::LaneTable lt = is3d::lane_table(k, g->pT, P.npT, P.split, inter && o->dimension == 3 && !P.feqmod);
     P.L = lt.L;
     P.Lpad = lt.Lpad;
-    for (int s = 0; s < P.L; s++) { P.mTmax = std::max(P.mTmax, lt.mT[s]); P.pTmax = std::max(P.pTmax, std::fabs(lt.pT[s])); }
+    // what is uploaded: the table's slots in use, the padding slots as copies of the last of them (they never change a cull vote of their wave)
+    const is3d::LaneArrays la = is3d::lane_arrays(lt, k, P.npT);
+    P.mTmax = la.mTmax;
+    P.pTmax = la.pTmax;
     std::vector<double> cosphi(P.J), sinphi(P.J);
     for (int j = 0; j < P.J; j++) { cosphi[j] = std::cos(g->phi[j]); sinphi[j] = std::sin(g->phi[j]); }  // :43-48
     std::vector<double> kgrid(P.K), kweight(P.K, 1.0);
@@ -201,31 +204,23 @@ static int plan_lanes_and_grids(is3d_plan &P, const is3d_grid *g, const is3d_opt
         P.gw2d = 0.0;
         for (int k2 = 0; k2 < P.K; k2++) P.gw2d = std::max(P.gw2d, std::fabs(kweight[k2]) * std::cosh(kgrid[k2]));
     }
-    HIP_TRY(P.d_mT.upload(lt.mT));
-    HIP_TRY(P.d_pT.upload(lt.pT));
-    HIP_TRY(P.d_sign.upload(lt.sign));
-    HIP_TRY(P.d_lane_b.upload(lt.b));
-    HIP_TRY(P.d_lane_sub.upload(lt.sub));
+    HIP_TRY(P.d_mT.upload(la.mT));
+    HIP_TRY(P.d_pT.upload(la.pT));
+    HIP_TRY(P.d_sign.upload(la.sign));
+    HIP_TRY(P.d_lane_b.upload(la.b));
+    HIP_TRY(P.d_lane_sub.upload(la.sub));
     if (P.e2tab) {
-        std::vector<int32_t> ipT(P.Lpad, 0);
-        for (int s = 0; s < P.Lbins; s++) ipT[s] = lt.order[s] % P.npT;
-        HIP_TRY(P.d_lane_ipT.upload(ipT));
+        HIP_TRY(P.d_lane_ipT.upload(la.ipT));
         HIP_TRY(P.d_pTgrid.upload(P.pT_grid));
         for (int i = 0; i < P.npT; i++)
             if (!(g->pT[i] >= 0.0)) return fail(IS3D_EINVAL, "kernel_variant 5 needs pT >= 0 (pT Dmax must be the maximum of pT D_j)");
     }
     HIP_TRY(P.d_degeneracy.upload(P.sp_deg));
     HIP_TRY(P.d_cls.upload(lt.lane_of));
-    {
-        // scaled p.dsigma of a lane: mT |A| + pT |B W| <= max(mT/mTmax, pT/pTmax) (mTmax |A| + pTmax |B W|) <= that factor (cf_pds_bound)
-        std::vector<int32_t> pe(P.Lpad, 0);
-        for (int s = 0; s < P.L; s++) {
-            const double f = std::max(P.mTmax > 0.0 ? lt.mT[s] / P.mTmax : 1.0, P.pTmax > 0.0 ? std::fabs(lt.pT[s]) / P.pTmax : 0.0);
-            int e = 0;
-            (void)std::frexp(f * (1.0 + 1.0e-12), &e);     // f (1 + eps) = m 2^e, m in [0.5, 1): f < 2^e with room for the roundings
-            pe[s] = std::min(e, 0);                        // the clamp keeps the scaled p.dsigma in [0, 1] whatever the lane
-        }
-        HIP_TRY(P.d_lane_pe.upload(pe));
+    HIP_TRY(P.d_lane_pe.upload(la.pe));
+    if (P.feqmod) {   // modified equilibrium: the slots' class and its mass
+        HIP_TRY(P.d_lane_mass.upload(la.mass));
+        HIP_TRY(P.d_lane_cls.upload(la.cls));
     }
     HIP_TRY(P.d_cosphi.upload(cosphi));
     HIP_TRY(P.d_sinphi.upload(sinphi));
@@ -293,8 +288,8 @@ static int plan_coefficient_tables(is3d_plan &P, const is3d_df_tables *df, const
     return IS3D_OK;
 }
 
-// ---- modified-equilibrium tables: Gauss-Laguerre nodes, the df_mode 4 splines in bulkPi/Peq, the lane -> class tables ----
-static int plan_feqmod_tables(is3d_plan &P, const is3d_feqmod_tables *fq, const is3d_options *o, const is3d::SpeciesClasses &k, const is3d::LaneTable &lt)
+// ---- modified-equilibrium tables: Gauss-Laguerre nodes, the df_mode 4 splines in bulkPi/Peq, the class tables (the lane -> class tables go up with the lanes) ----
+static int plan_feqmod_tables(is3d_plan &P, const is3d_feqmod_tables *fq, const is3d_options *o, const is3d::SpeciesClasses &k)
 {
     P.ngl = fq->n_gla;
     P.detA_min = fq->deta_min;
@@ -319,12 +314,6 @@ static int plan_feqmod_tables(is3d_plan &P, const is3d_feqmod_tables *fq, const 
         jon[1] = 1.0;
     }
     HIP_TRY(P.d_jonah.upload(jon));
-    std::vector<double> lane_mass(P.Lpad, 1.0);
-    std::vector<int32_t> lane_cls(P.Lpad, 0);
-    for (int sl = 0; sl < P.split; sl++)   // every slot of a bin carries the bin's class
-        for (int s = 0; s < P.Lbins; s++) { lane_mass[sl * P.Lbins + s] = k.cmass[lt.order[s] / P.npT]; lane_cls[sl * P.Lbins + s] = lt.order[s] / P.npT; }
-    HIP_TRY(P.d_lane_mass.upload(lane_mass));
-    HIP_TRY(P.d_lane_cls.upload(lane_cls));
     HIP_TRY(P.d_cls_mass.upload(k.cmass));
     HIP_TRY(P.d_cls_sign.upload(k.csign));
     if (P.baryon) HIP_TRY(P.d_cls_baryon.upload(k.cbar));
@@ -471,11 +460,10 @@ static int plan_create_impl(is3d_plan **out, const is3d_species *sp, const is3d_
     P->sp_deg.assign(sp->degeneracy, sp->degeneracy + sp->n);
     P->Lbins = P->ncls * P->npT;
 
-    is3d::LaneTable lt;
     plan_choose_kernel(*P, g, o);
-    if ((rc = plan_lanes_and_grids(*P, g, o, k, lt))) return rc;
+    if ((rc = plan_lanes_and_grids(*P, g, o, k))) return rc;
     if ((rc = plan_coefficient_tables(*P, df, o))) return rc;
-    if (fq && (rc = plan_feqmod_tables(*P, fq, o, k, lt))) return rc;
+    if (fq && (rc = plan_feqmod_tables(*P, fq, o, k))) return rc;
     if ((rc = plan_tiling_and_sizing(*P, df, o, max_cells))) return rc;
     if ((rc = plan_allocate(*P, o))) return rc;
     *out = P.release();

@@ -58,7 +58,7 @@ inline int lane_split(int n_bins, int rblocks)
 struct LaneTable {
     int Lbins = 0, L = 0, Lpad = 0;    // bins; slots in use (bins x split); slots padded to whole waves
     std::vector<int> order, slot_of;   // [Lbins] slot -> natural bin (class * n_pT + i) and back; E2 lane -> pT index is order % n_pT, lane -> class order / n_pT
-    std::vector<double> mT, pT, sign, b;   // [Lpad]; padding lanes hold 1, 0, 1, 0
+    std::vector<double> mT, pT, sign, b;   // [Lpad]; padding lanes hold 1, 0, 1, 0 HERE, in the host table; what a plan uploads is lane_arrays()
     std::vector<int32_t> sub;              // [Lpad] sub-lane of the slot within its bin; padding 0
     std::vector<int> lane_of;              // [species x n_pT] -> slot of the class's bin
 };
@@ -104,6 +104,48 @@ inline LaneTable lane_table(const SpeciesClasses &k, const double *pT, int n_pT,
     for (int s = 0; s < npart; s++)
         for (int i = 0; i < n_pT; i++) t.lane_of[(size_t)s * n_pT + i] = t.slot_of[k.cls[s] * n_pT + i];
     return t;
+}
+
+// ---- lane arrays: what a plan uploads of a lane table, one value per slot ----
+// Slots [0, L) hold the table's values and what the plans derive from them.  A padding slot [L, Lpad) is a copy of slot L - 1 in every array: the
+// heaviest bin of the last sub-lane, which always sits in the padding's own wave.  A copy reads the same operands, does the same arithmetic, holds the same
+// accumulators and thresholds and casts the same vote as its source, so it never changes a wave-wide cull vote; the table's own padding (1, 0, 1, 0 with
+// pe = 0: a light boson at rest) was alive in several times as many (unit, row) pairs as the real lanes of its wave and kept their rows running.  Every
+// index a copy carries (sub, ipT, cls) is one a real lane carries, hence in range wherever slot L - 1 is.  Nothing reads a padding slot's sums: lane_of
+// and the slots sl * Lbins + s that cf_finalize adds are all below L.
+struct LaneArrays {
+    int Lpad = 0;
+    std::vector<double> mT, pT, sign, b, mass;   // [Lpad]; mass: of the slot's class (modified equilibrium)
+    std::vector<int32_t> sub, ipT, pe, cls;      // [Lpad]; ipT: index of the slot's pT in the grid (E2 table column); cls: the slot's class;
+                                                 // pe: max(mT/mTmax, |pT|/pTmax) < 2^pe, pe <= 0 (the lane's share of the p.dsigma bound, cf_pds_bound)
+    double mTmax = 0.0, pTmax = 0.0;             // over the slots in use: max mT, max |pT|
+};
+inline LaneArrays lane_arrays(const LaneTable &t, const SpeciesClasses &k, int n_pT)
+{
+    LaneArrays a;
+    a.Lpad = t.Lpad;
+    a.mT = t.mT; a.pT = t.pT; a.sign = t.sign; a.b = t.b; a.sub = t.sub;
+    a.mass.assign(t.Lpad, 1.0);
+    a.ipT.assign(t.Lpad, 0); a.pe.assign(t.Lpad, 0); a.cls.assign(t.Lpad, 0);
+    for (int s = 0; s < t.L; s++) { a.mTmax = std::max(a.mTmax, t.mT[s]); a.pTmax = std::max(a.pTmax, std::fabs(t.pT[s])); }
+    for (int l = 0; l < t.L; l++) {
+        const int nat = t.order[l % t.Lbins];   // every slot of a bin carries the bin's class and pT index
+        a.cls[l] = nat / n_pT;
+        a.ipT[l] = nat % n_pT;
+        a.mass[l] = k.cmass[nat / n_pT];
+        // scaled p.dsigma of a lane: mT |A| + pT |B W| <= max(mT/mTmax, pT/pTmax) (mTmax |A| + pTmax |B W|) <= that factor (cf_pds_bound)
+        const double f = std::max(a.mTmax > 0.0 ? t.mT[l] / a.mTmax : 1.0, a.pTmax > 0.0 ? std::fabs(t.pT[l]) / a.pTmax : 0.0);
+        int e = 0;
+        (void)std::frexp(f * (1.0 + 1.0e-12), &e);     // f (1 + eps) = m 2^e, m in [0.5, 1): f < 2^e with room for the roundings
+        a.pe[l] = std::min(e, 0);                      // the clamp keeps the scaled p.dsigma in [0, 1] whatever the lane
+    }
+    if (t.L > 0)
+        for (int l = t.L; l < t.Lpad; l++) {
+            const int c = t.L - 1;
+            a.mT[l] = a.mT[c]; a.pT[l] = a.pT[c]; a.sign[l] = a.sign[c]; a.b[l] = a.b[c]; a.mass[l] = a.mass[c];
+            a.sub[l] = a.sub[c]; a.ipT[l] = a.ipT[c]; a.pe[l] = a.pe[c]; a.cls[l] = a.cls[c];
+        }
+    return a;
 }
 
 // ---- waves per workgroup of a tile kernel ----

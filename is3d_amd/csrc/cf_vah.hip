@@ -863,14 +863,16 @@ static int vah_lanes_and_grids(is3d_vah_plan &P, const is3d_grid *gr, const is3d
 {
     const is3d::LaneTable lt = is3d::lane_table(k, gr->pT, P.npT, P.split, false);
     P.Lpad = lt.Lpad;
-    HIP_TRY(P.d_lane_sub.upload(lt.sub));
+    // what is uploaded: the padding slots as copies of the last slot in use (lane_arrays: they never change a cull vote of their wave)
+    const is3d::LaneArrays la = is3d::lane_arrays(lt, k, P.npT);
+    HIP_TRY(P.d_lane_sub.upload(la.sub));
     std::vector<double> cosphi(P.J), sinphi(P.J), kgrid(P.K), kweight(P.K, 1.0);
     for (int j = 0; j < P.J; j++) { cosphi[j] = std::cos(gr->phi[j]); sinphi[j] = std::sin(gr->phi[j]); }
     for (int k2 = 0; k2 < P.K; k2++) {
         kgrid[k2] = P.three_d ? gr->y[k2] : gr->eta[k2];
         if (!P.three_d) kweight[k2] = gr->eta_w[k2] * (gr->eta[1] - gr->eta[0]);          // :2178-2187
     }
-    HIP_TRY(P.d_mT.upload(lt.mT)); HIP_TRY(P.d_pT.upload(lt.pT)); HIP_TRY(P.d_sg.upload(lt.sign)); HIP_TRY(P.d_lane.upload(lt.lane_of)); HIP_TRY(P.d_deg.upload(P.sp_deg));
+    HIP_TRY(P.d_mT.upload(la.mT)); HIP_TRY(P.d_pT.upload(la.pT)); HIP_TRY(P.d_sg.upload(la.sign)); HIP_TRY(P.d_lane.upload(lt.lane_of)); HIP_TRY(P.d_deg.upload(P.sp_deg));
     HIP_TRY(P.d_cos.upload(cosphi)); HIP_TRY(P.d_sin.upload(sinphi)); HIP_TRY(P.d_kg.upload(kgrid)); HIP_TRY(P.d_kw.upload(kweight));
     // bound of |p.dsigma| over the lanes; pT as it is, where cf_plan.cpp takes |pT| (the same for the pT >= 0 grids both are given)
     for (int s = 0; s < lt.L; s++) { P.mTmax = std::max(P.mTmax, lt.mT[s]); P.pTmax = std::max(P.pTmax, lt.pT[s]); }

@@ -15,6 +15,10 @@ acc[lane][j][k] (equilibrium integrand, u = 1/2), and counts the (wave, cell, ti
      lambda = clamp(log((mTmax max_k |A_k| + pTmax max_j |B_j|) psc), -LAMBDA_MAX, 0) is the bound of the scaled p.dsigma over the unit's rows and
      phi (unit: what cf_prep writes into header slot 11, the kernels' rule since round 25), over a row group's rows, or over one row.
 
+--pad none|legacy|copy: what the slots that pad the lanes to whole waves do.  none: they never vote (the tool's rule until round 26, and what the
+plans' copies of the last lane amount to: copy gives the same counts); legacy: 32 slots mT = 1, pT = 0, pe = 0 with accumulators, thresholds and votes
+of their own, which is what the plans uploaded until round 26 (+3.1 % live wave-rows on the config-3 chunks, LABBOOK round 26).
+
 --seed / --chunks: another seeded surface, cut into equal consecutive cell chunks with accumulators of their own (the counts are summed) -- e.g. the
 surface tests/test_gpu_parity.py::test_row_culling_changes_no_bit pins its cross-variant counts on: --cells 2000 --seed 80 --chunks 3.
 
@@ -80,6 +84,10 @@ def main():
     ap.add_argument("--pds-bound", default="none", choices=["none", "unit", "group", "row"],
                     help="rule P: the bound of the scaled p.dsigma over the unit / the row group / the row, in place of the surface-wide 2^pe alone")
     ap.add_argument("--seed", type=int, default=None, help="seed of the surface (default: the config-3 seed)")
+    ap.add_argument("--pad", default="none", choices=["none", "legacy", "copy"],
+                    help="the slots that pad the lanes to whole waves: never vote (none); the lane table's own padding mT = 1, pT = 0 with pe = 0, with "
+                         "accumulators, thresholds and votes of its own (legacy: what the plans uploaded before round 26); copies of the last lane "
+                         "(copy: what they upload now -- the votes of 'none')")
     ap.add_argument("--chunks", type=int, default=1, help="cut the cells into this many equal consecutive chunks, each with its own accumulators")
     a = ap.parse_args()
     groups = [int(x) for x in a.row_groups.split(",")] if a.row_groups else None
@@ -108,11 +116,17 @@ def main():
         m2[:, :ncl] = mT.reshape(len(pT), ncl); p2[:, :ncl] = pTl.reshape(len(pT), ncl)
         m2[:, ncl:] = m2[:, ncl - 1:ncl]; p2[:, ncl:] = p2[:, ncl - 1:ncl]      # duplicates of the heaviest class: never change a vote
         mT, pTl = m2.ravel(), p2.ravel()
-    L = len(mT)
-    nw = (L + 63) // 64
-    mTmax, pTmax = mT.max(), pTl.max()
+    mTmax, pTmax = mT.max(), pTl.max()           # over the real lanes, as in the plan
     pe = np.ceil(np.log2(np.maximum(mT / mTmax, pTl / pTmax))).astype(int)
     pe = np.minimum(pe, 0)
+    npad = -len(mT) % 64
+    if a.pad != "none" and npad:
+        legacy = a.pad == "legacy"
+        mT = np.concatenate([mT, np.full(npad, 1.0 if legacy else mT[-1])])
+        pTl = np.concatenate([pTl, np.full(npad, 0.0 if legacy else pTl[-1])])
+        pe = np.concatenate([pe, np.full(npad, 0 if legacy else pe[-1], dtype=int)])
+    L = len(mT)
+    nw = (L + 63) // 64
 
     if a.eta_bin is None:
         s = synth.synth_surface(a.cells, 3, seed=a.seed, first_cell=a.first)
