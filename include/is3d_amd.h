@@ -1131,11 +1131,67 @@ typedef struct {
     int32_t max_stack, max_depth;       /* static, from the table */
     int32_t n_closed_channels, reserved;
     double ms_h2d, ms_count, ms_fill, ms_d2h;
+    double ms_bin;                      /* the binned entries below: the one decay-and-bin pass (ms_count = ms_fill = 0 there); 0 for the list entry */
 } is3d_decay_mc_stats;
 int is3d_decay_particles(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
                          const is3d_decay_mc_inputs *in, int64_t n_particles, const is3d_particle *particles,
                          is3d_particle *out, int64_t *origin /* may be NULL */, int64_t capacity,
                          int64_t *n_out, is3d_decay_mc_stats *stats /* may be NULL */);
+
+/* The table as the decay kernels read it, resident on one device (device < 0: the current one): the host analysis and the upload that
+ * is3d_decay_particles performs on every call -- the open channels with their running sums, the chosen -> entry map, the cycle check,
+ * max_stack and max_depth -- done once for a caller that keeps its primaries on the device.  Every refusal of the table that
+ * is3d_decay_particles makes (IS3D_EINVAL, same messages) is made here before any device use; a good table without a device is
+ * IS3D_ENODEVICE.  A table serves any number of calls and may outlive them; destroy(NULL) is allowed. */
+typedef struct is3d_decay_mc_table is3d_decay_mc_table;
+int is3d_decay_mc_table_create(is3d_decay_mc_table **table_dev, const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
+                               int32_t device);
+void is3d_decay_mc_table_destroy(is3d_decay_mc_table *table_dev);
+
+/* The test_sampler distributions of a list AFTER its Monte Carlo decays, without the decayed list.  Definition:
+ *   the histograms are those of is3d_sampler_bin_list(bins, n_events, n_slots, ...) on the list that is3d_decay_particles returns for the
+ *   same (table, chosen_mc_id, in, particles), with every particle's species (a TABLE entry e) replaced by slot[e] and the particles with
+ *   slot[e] = -1 dropped -- counts and yields exactly; vn_re, vn_im within one unit per entry of the dN_pT bin (device and host libm).
+ *   *n_final is the length of that list before the drop, *n_unbinned = *n_final - sum(yield) the number dropped.
+ * How: ONE pass, thread <-> primary, over the same decay loop and stream (Rng(seed, 5, first_particle + i)): every final particle is built
+ * in registers as the fill pass stores it and goes to the rule of csrc/cf_sampler_bins.h at once -- no counts, offsets, scan or output
+ * list; device memory holds the primaries and the histograms.  The adds are the 64-bit integer adds of cf_sampler_bins, so the histograms
+ * do not depend on bins->kernel_form (0 = workgroup-private histograms in LDS where the block and six tally words fit 64 KiB, 1 = global
+ * atomics, 2 = private or IS3D_EINVAL), on the launch geometry, or on the pieces a list is decayed in (first_particle; integer histograms
+ * added by the caller), bit for bit.  slot: int32[table->n].  All pointers HOST memory; hist is overwritten.
+ * stats: the tallies and static fields of is3d_decay_particles; ms_count = ms_fill = 0, ms_bin is the pass.
+ * IS3D_EINVAL before any device use: every refusal of is3d_decay_particles; n_slots < 1; the bins, NULL histogram arrays and kernel_form
+ * as for is3d_sampler_bin_list_device; a NULL slot map or a slot outside [-1, n_slots); kernel_form = 2 on a block that does not fit; a
+ * primary whose event is outside [0, n_events).  n_particles = 0: zero histograms, no launch.  A dN_pT bin above
+ * IS3D_SAMPLER_VN_MAX_COUNT: IS3D_EDOMAIN.  A good call without a device: IS3D_ENODEVICE. */
+int is3d_decay_particles_binned(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
+                                const is3d_decay_mc_inputs *in, int64_t n_particles, const is3d_particle *particles,
+                                const int32_t *slot, int32_t n_slots, const is3d_sampler_test_bins *bins, int32_t n_events,
+                                const is3d_sampler_hist *hist, int64_t *n_final, int64_t *n_unbinned,
+                                is3d_decay_mc_stats *stats /* may be NULL */);
+/* is3d_sampler_plan_execute_binned with every event batch decayed and binned a second time from the plan's particle workspace: after a
+ * batch's fill, cf_sampler_bins bins the thermal hadrons into hist_host exactly as _execute_binned does (the same bits), then
+ * cf_decay_mc_bins decays the batch with first_particle = the number of hadrons of the batches before it and bins the products into
+ * hist_decayed (n_slots species).  hist_decayed is what is3d_decay_particles_binned gives for the whole list of is3d_sampler_plan_execute
+ * with first_particle = 0, seed = decay_seed: independent of batch_events, kernel_form and launch geometry, bit for bit.  table_dev: on
+ * the plan's device, created for the plan's species list as chosen list.  Device memory beyond _execute_binned's: the second histogram
+ * block and the slot map, sized at first use and kept by the plan; nothing is sized by the number of final particles or of events' hadrons.
+ * *n_particles: thermal hadrons; *n_final, *n_unbinned, decay_stats (may be NULL; n_primaries = *n_particles, ms_bin = the decay passes):
+ * as above.  IS3D_EINVAL before any device use: the refusals of _execute_binned, n_slots < 1, a NULL array of hist_decayed, a bad slot map,
+ * kernel_form = 2 on a decayed block that does not fit, a table of another chosen count or device. */
+int is3d_sampler_plan_execute_decayed_binned(is3d_sampler_plan *plan, const is3d_cells *cells_dev, const double *x_dev, const double *y_dev,
+                                             int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
+                                             const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist_host,
+                                             const is3d_decay_mc_table *table_dev, const int32_t *slot, int32_t n_slots, uint64_t decay_seed,
+                                             int32_t lifetime, const is3d_sampler_hist *hist_decayed, int64_t *n_particles, int64_t *n_final,
+                                             int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats);
+/* host-pointer one-shot for the viscous sampler (df_mode 1-4, fast, include_baryon): plan and table create, upload, execute, destroy.
+ * chosen_mc_id: the mc_id of species[0 .. n), which the table must hold.  The table's refusals come first, then is3d_sample_binned's. */
+int is3d_sample_decayed_binned(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                               const is3d_options *opts, const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist,
+                               const is3d_decay_table *table, const int64_t *chosen_mc_id, const int32_t *slot, int32_t n_slots,
+                               uint64_t decay_seed, int32_t lifetime, const is3d_sampler_hist *hist_decayed, int64_t *n_particles,
+                               int64_t *n_final, int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats);
 
 /* ---------------------------------------------------------------------------------------------
  * Driver: IS3D::run_particlization (src/cpp/iS3D.cpp:74-192; class IS3D, src/cpp/iS3D.h:19-96).  Reads iS3D_parameters.dat,

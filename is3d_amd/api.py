@@ -117,6 +117,8 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_write_polarization", "is3d_surface_vorticity", "is3d_spin_polarization_multi",
            "is3d_pdg_read_decays", "is3d_decay_q_factor", "is3d_resonance_decays", "is3d_decay_plan_create", "is3d_decay_plan_output_size",
            "is3d_decay_plan_execute", "is3d_decay_plan_destroy", "is3d_write_results_decays", "is3d_decay_particles",
+           "is3d_decay_mc_table_create", "is3d_decay_mc_table_destroy", "is3d_decay_particles_binned", "is3d_sampler_plan_execute_decayed_binned",
+           "is3d_sample_decayed_binned",
            "is3d_sampler_bin_list", "is3d_write_sampler_tests_binned", "is3d_sampler_plan_execute_binned", "is3d_sample_binned", "is3d_sample_binned_multi",
            "is3d_sampler_plan_execute_fused", "is3d_sample_fused", "is3d_sample_fused_multi",
            "is3d_sampler_bin_list_device", "is3d_df_generate", "is3d_df_tables_write",
@@ -164,7 +166,7 @@ class DecayMcInputs(C.Structure):
 class DecayMcStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ["n_primaries", "n_decays", "n_final", "n_stuck", "n_trials", "n_exhausted"]] + \
                [(n, C.c_int32) for n in ["max_stack", "max_depth", "n_closed_channels", "reserved"]] + \
-               [(n, C.c_double) for n in ["ms_h2d", "ms_count", "ms_fill", "ms_d2h"]]
+               [(n, C.c_double) for n in ["ms_h2d", "ms_count", "ms_fill", "ms_d2h", "ms_bin"]]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
@@ -1081,6 +1083,89 @@ def decay_particles(table, chosen_mc_id, particles, seed=1, first_particle=0, li
     return out[:n], origin[:n], st.as_dict()
 
 
+def _check_decayed(rc, st, nf, nu, **extra):
+    """A decayed-and-binned entry's return code: an Is3dError carries the decay stats (.stats) and whatever else the entry had in hand."""
+    d = st.as_dict()
+    d["n_final"], d["n_unbinned"] = int(nf.value), int(nu.value)
+    if rc != 0:
+        e = Is3dError(rc, load().is3d_last_error().decode())
+        e.stats = d
+        for k, v in extra.items():
+            setattr(e, k, v)
+        raise e
+    return d
+
+
+def _slot_map(table, slot):
+    slot = np.ascontiguousarray(slot, dtype=np.int32)
+    assert slot.shape == (len(table["mc_id"]),), (slot.shape, len(table["mc_id"]))
+    return slot
+
+
+def stable_slots(table, mc_ids=None):
+    """The slot map of a decayed-and-binned run: (int32[table entries], the slots' mc_id).  mc_ids = None: every stable entry of the table in
+    table order; otherwise those of mc_ids that are stable in the table, in the order given (the run driver's rule for its chosen list)."""
+    ids, stable = np.asarray(table["mc_id"], np.int64), np.asarray(table["stable"]) != 0
+    slot = np.full(len(ids), -1, np.int32)
+    if mc_ids is None:
+        keep = np.nonzero(stable)[0]
+    else:
+        first = {}
+        for e, i in enumerate(ids):
+            first.setdefault(int(i), e)
+        keep = [first[int(i)] for i in mc_ids if int(i) in first and stable[first[int(i)]]]
+    for k, e in enumerate(keep):
+        slot[e] = k
+    return slot, ids[np.asarray(keep, np.int64)] if len(keep) else np.zeros(0, np.int64)
+
+
+class DecayMcTable:
+    """is3d_decay_mc_table_*: the decay table as the Monte Carlo kernels read it, analysed once and resident on `device`.  Every refusal of the
+    table is raised here (Is3dError, IS3D_EINVAL) before any device use.  .stats: max_stack, max_depth, n_closed_channels come with a run."""
+
+    def __init__(self, table, chosen_mc_id, device=-1):
+        L = load()
+        ts, ch, _, self._keep = _decay_pack(table, chosen_mc_id, dict(pT=[1.0], phi=[0.0], y=[0.0]))
+        self.table, self.n_entries, self.n_chosen = table, len(table["mc_id"]), len(ch)
+        L.is3d_decay_mc_table_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(DecayTable), C.c_int32, C.POINTER(C.c_int64), C.c_int32]
+        L.is3d_decay_mc_table_destroy.argtypes = [C.c_void_p]
+        L.is3d_decay_mc_table_destroy.restype = None
+        self._h = C.c_void_p()
+        _check(L.is3d_decay_mc_table_create(C.byref(self._h), C.byref(ts), len(ch), ch.ctypes.data_as(C.POINTER(C.c_int64)), int(device)))
+
+    def close(self):
+        if self._h:
+            load().is3d_decay_mc_table_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def decay_particles_binned(table, chosen_mc_id, particles, slot, n_slots, bins, n_events, seed=1, first_particle=0, lifetime=0, device=-1):
+    """is3d_decay_particles_binned: a sampled list decayed on the device with every final particle binned at once -- the histograms of
+    sampler_bin_list on decay_particles' list with species -> slot[species], slot -1 dropped.  slot: int32 per table entry.  Returns
+    (dict of int64 histograms of n_slots species, stats dict with n_final, n_unbinned and the tallies of decay_particles)."""
+    L = load()
+    ts, ch, _, keep = _decay_pack(table, chosen_mc_id, dict(pT=[1.0], phi=[0.0], y=[0.0]))
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    slot = _slot_map(table, slot)
+    inp = DecayMcInputs(int(seed), int(first_particle), int(lifetime), int(device))
+    b = _pack_bins(bins)
+    h, out = _hist_arrays(bins, n_events, n_slots)
+    st, nf, nu = DecayMcStats(), C.c_int64(0), C.c_int64(0)
+    L.is3d_decay_particles_binned.argtypes = [C.POINTER(DecayTable), C.c_int32, C.POINTER(C.c_int64), C.POINTER(DecayMcInputs), C.c_int64, C.c_void_p,
+                                              C.c_void_p, C.c_int32, C.POINTER(SamplerTestBins), C.c_int32, C.POINTER(SamplerHist),
+                                              C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(DecayMcStats)]
+    rc = L.is3d_decay_particles_binned(C.byref(ts), len(ch), ch.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(inp), len(particles),
+                                       particles.ctypes.data, slot.ctypes.data, int(n_slots), C.byref(b), int(n_events), C.byref(h), C.byref(nf),
+                                       C.byref(nu), C.byref(st))
+    return out, _check_decayed(rc, st, nf, nu, hist=out)
+
+
 def shard_bounds(n_cells, rank, n_ranks):
     """is3d_shard_bounds: the contiguous cell shard [lo, hi) of `rank` (what is3d_smooth_spectra_multi uses)."""
     lo, hi = C.c_int64(), C.c_int64()
@@ -1754,6 +1839,34 @@ class SamplerPlan:
         d["n_particles"] = int(cnt.value)
         return out, d
 
+    def execute_decayed_binned(self, n_cells, dev_ptrs, n_events, seed, bins, n_species, table, slot, n_slots, decay_seed=None, lifetime=0,
+                               x_ptr=0, y_ptr=0, first_cell=0, batch_events=0):
+        """is3d_sampler_plan_execute_decayed_binned: execute_binned with every event batch also decayed (table: a DecayMcTable on the plan's
+        device, created for the plan's species list) and its final particles binned by slot.  decay_seed = None: the sampler's seed.
+        -> (thermal histograms, decayed histograms of n_slots species, sampler stats, decay stats with n_final and n_unbinned)."""
+        cs = Cells()
+        cs.n_cells = int(n_cells)
+        for f in CELL_FIELDS:
+            if dev_ptrs.get(f):
+                setattr(cs, f, int(dev_ptrs[f]))
+        b = _pack_bins(bins)
+        h, out = _hist_arrays(bins, n_events, n_species)
+        hd, outd = _hist_arrays(bins, n_events, n_slots)
+        slot = _slot_map(table.table, slot)
+        cnt, st, dst, nf, nu = C.c_int64(0), SamplerStats(), DecayMcStats(), C.c_int64(0), C.c_int64(0)
+        fn = load().is3d_sampler_plan_execute_decayed_binned
+        fn.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32,
+                       C.POINTER(SamplerTestBins), C.POINTER(SamplerHist), C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int32,
+                       C.POINTER(SamplerHist), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(SamplerStats),
+                       C.POINTER(DecayMcStats)]
+        rc = fn(self._h, C.byref(cs), C.c_void_p(int(x_ptr) or None), C.c_void_p(int(y_ptr) or None), int(n_events), int(seed), int(first_cell),
+                int(batch_events), C.byref(b), C.byref(h), table._h, slot.ctypes.data, int(n_slots), int(seed if decay_seed is None else decay_seed),
+                int(lifetime), C.byref(hd), C.byref(cnt), C.byref(nf), C.byref(nu), C.byref(st), C.byref(dst))
+        d = st.as_dict()
+        d["n_particles"] = int(cnt.value)
+        dd = _check_decayed(rc, dst, nf, nu, hist=out, hist_decayed=outd, sampler_stats=d)
+        return out, outd, d, dd
+
     def execute_fused(self, n_cells, dev_ptrs, n_events, seed, bins, n_species, x_ptr=0, y_ptr=0, first_cell=0, batch_events=0):
         """is3d_sampler_plan_execute_fused: execute_binned's arguments and result, every hadron binned where it is sampled (no list, no
         particle workspace: stats["particle_workspace_bytes"] == 0)."""
@@ -1967,6 +2080,34 @@ def sample_binned(cells, species, df, gla, bins, opts=None, n_events=1, seed=1, 
                                                 batch_events, muB_avg)
     return _sample_binned("is3d_sample_fused" if _fused else "is3d_sample_binned", (C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_)),
                           devices, bins, n_events, sps.n, False)
+
+
+def sample_decayed_binned(cells, species, df, gla, bins, table, chosen_mc_id, slot, n_slots, opts=None, n_events=1, seed=1, decay_seed=None,
+                          lifetime=0, y_cut=0.5, first_cell=0, fq=None, fast=0, T_avg=0.0, T_avg_switch=0.0, batch_events=0, muB_avg=0.0):
+    """is3d_sample_decayed_binned: the viscous sampler with every event batch binned (as sample_binned) and, decayed on the device, binned
+    again by slot.  chosen_mc_id: the mc_id of the species list.  Returns (thermal histograms, decayed histograms, sampler stats, decay stats
+    with n_final and n_unbinned)."""
+    cs, sps, ds, si, os_, _held = _pack_sampler(cells, species, df, gla, opts, n_events, seed, y_cut, first_cell, fq, fast, T_avg, T_avg_switch,
+                                                batch_events, muB_avg)
+    ts, ch, _, keep = _decay_pack(table, chosen_mc_id, dict(pT=[1.0], phi=[0.0], y=[0.0]))
+    assert len(ch) == sps.n, (len(ch), sps.n)
+    b = _pack_bins(bins)
+    h, out = _hist_arrays(bins, n_events, sps.n)
+    hd, outd = _hist_arrays(bins, n_events, n_slots)
+    slot = _slot_map(table, slot)
+    cnt, st, dst, nf, nu = C.c_int64(0), SamplerStats(), DecayMcStats(), C.c_int64(0), C.c_int64(0)
+    fn = load().is3d_sample_decayed_binned
+    fn.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options),
+                   C.POINTER(SamplerTestBins), C.POINTER(SamplerHist), C.POINTER(DecayTable), C.POINTER(C.c_int64), C.c_void_p, C.c_int32,
+                   C.c_uint64, C.c_int32, C.POINTER(SamplerHist), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                   C.POINTER(SamplerStats), C.POINTER(DecayMcStats)]
+    rc = fn(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), C.byref(b), C.byref(h), C.byref(ts),
+            ch.ctypes.data_as(C.POINTER(C.c_int64)), slot.ctypes.data, int(n_slots), int(seed if decay_seed is None else decay_seed), int(lifetime),
+            C.byref(hd), C.byref(cnt), C.byref(nf), C.byref(nu), C.byref(st), C.byref(dst))
+    d = st.as_dict()
+    d["n_particles"] = int(cnt.value)
+    dd = _check_decayed(rc, dst, nf, nu, hist=out, hist_decayed=outd, sampler_stats=d)
+    return out, outd, d, dd
 
 
 def sample_binned_multi(cells, species, df, gla, bins, opts=None, devices=(0,), **kw):

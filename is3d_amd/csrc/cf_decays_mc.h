@@ -1,0 +1,48 @@
+// cf_decays_mc.h -- what the sampler's batch loop (cf_sampler.hip) needs of the Monte Carlo decays (cf_decays_mc.hip): the one-pass
+// decay-and-bin launch on a device-resident table (is3d_decay_mc_table), and the checks both of its entries make before any device use.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/is3d_amd.h"
+#include "cf_sampler_bins.h"
+
+namespace is3d {
+
+// the run-wide words of cf_decay_mc_bins: decays, stuck, trials, exhausted, stack overflows (never), final particles
+constexpr int kDecayMcBinTallies = 6;
+
+// A decayed-and-binned run on the device: the table, the slot map (DEVICE, one int32 per table entry, -1 = not binned), the bins with what
+// follows from them for n_slots species, and the device block  hist [layout.total] | yield [n_events] | tally [kDecayMcBinTallies].
+struct DecayMcBinRun {
+    const is3d_decay_mc_table *table;
+    const int32_t *slot_dev;
+    int32_t n_slots, n_events;
+    uint64_t seed;
+    int32_t lifetime;
+    is3d_sampler_test_bins bins;
+    SamplerBinWidths widths;
+    SamplerHistLayout layout;
+    unsigned long long *block_dev;
+};
+
+// the private form keeps its tally words in static LDS beside the dynamic block: it fits when block + kDecayMcBinTallies words <= 64 KiB
+inline bool decay_mc_bins_lds_fits(const SamplerHistLayout &l) { return l.total + kDecayMcBinTallies <= (int64_t)(65536 / sizeof(unsigned long long)); }
+
+// IS3D_EINVAL, no device use: n_slots < 1, a NULL map, a slot outside [-1, n_slots), bins->kernel_form = 2 on a block of n_slots species
+// that does not fit (bins and hist themselves: sampler_check_bin_args)
+int decay_mc_check_slots(int32_t n_entries, const int32_t *slot, int32_t n_slots, const is3d_sampler_test_bins *bins);
+// every refusal of is3d_decay_mc_table_create, and nothing else: the host analysis of a table without a device
+int decay_mc_table_check(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id);
+int32_t decay_mc_table_entries(const is3d_decay_mc_table *t);
+int32_t decay_mc_table_chosen(const is3d_decay_mc_table *t);
+int decay_mc_table_device(const is3d_decay_mc_table *t);
+// n primaries of a DEVICE list (species indexing the table's chosen list, ordered by event), primary i drawing from stream first_particle + i,
+// decayed and binned into r.block_dev on the null stream in the form r.bins.kernel_form (0 = private where it fits, 1 = global, 2 = private)
+hipError_t decay_mc_bins_launch(const DecayMcBinRun &r, const is3d_particle *primaries_dev, int64_t n, int64_t first_particle);
+// the tallies of a finished run (HOST copy of the tally words) into stats; IS3D_EINVAL if a pending stack overflowed
+int decay_mc_bins_tallies(const unsigned long long *tally, is3d_decay_mc_stats *stats);
+// the static part of the stats: what the table analysis found
+void decay_mc_table_stats(const is3d_decay_mc_table *t, is3d_decay_mc_stats *stats);
+
+}  // namespace is3d

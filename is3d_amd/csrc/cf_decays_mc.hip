@@ -6,6 +6,10 @@
 //   cf_decay_mc<false>  counts the final particles of every primary (int32) and adds the run-wide tallies
 //   hipCUB exclusive scan of the counts (as the samplers')
 //   cf_decay_mc<true>   the same loop body, every final particle stored at the primary's offset
+// and, for a caller that wants the test_sampler distributions of the decayed list and not the list (is3d_decay_particles_binned, the batch
+// loop of cf_sampler.hip), ONE pass without counts, offsets or scan:
+//   cf_decay_mc_bins    the same loop body, every final particle built in registers and given to the bin rule of cf_sampler_bins.h at once
+// What a pass does with a final particle is its sink (SinkCount, SinkStore, SinkBin): the one thing in which the three differ.
 // The particle in hand lives in registers; its pending siblings wait on a stack in private memory (kStack entries of 88 bytes: the
 // table analysis on the host proves the need before any launch).  The table goes to the device flat, OPEN channels only, with the
 // running sums of their branching ratios, so the channel of a decay is the first whose sum exceeds u * (last sum).
@@ -17,12 +21,15 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
+#include <memory>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/is3d_amd.h"
 #include "cf_host.h"
 #include "cf_sampler_common.h"
+#include "cf_decays_mc.h"
 #include "errors.h"
 
 namespace {
@@ -35,6 +42,10 @@ using is3d::set_error;
 constexpr int kBodies = IS3D_DECAY_MC_MAX_BODIES, kStack = IS3D_DECAY_MC_MAX_STACK, kTrials = IS3D_DECAY_MC_MAX_TRIALS;
 constexpr int kThreads = 128;
 constexpr int kTallies = 5;   // decays, stuck, trials, exhausted, primaries whose stack would have overflowed (never: the host proves it)
+constexpr int kBinThreads = 256;                         // cf_decay_mc_bins
+constexpr int kBinTallies = is3d::kDecayMcBinTallies;    // ... which has no count pass to learn the number of final particles from: word kTallies
+constexpr int kBinPrivateBlocks = 512;                   // private form: at most this many flushes (its VGPRs let two workgroups share a CU: one round on 256 CUs)
+static_assert(kBinTallies == kTallies + 1, "the bin pass adds the final particles to the tallies of the count pass");
 
 struct McTable {              // device arrays: per entry | per open channel
     const double *mass, *width;
@@ -81,10 +92,64 @@ __device__ __forceinline__ void boost(double bx, double by, double bz, double b2
     }
 }
 
+// ---- what a pass does with a final particle (decay_tree): kMomenta tells whether the pass needs the products' momenta at all ----
+struct SinkCount {
+    static constexpr bool kMomenta = false;
+    __device__ __forceinline__ void operator()(int, const Pending &, const is3d_particle &) {}
+};
+// the fill pass: final particle number nfinal of the primary at its offset, no more than the count pass counted
+struct SinkStore {
+    static constexpr bool kMomenta = true;
+    const McArgs &a;
+    int64_t i, slot0;
+    int counted;
+    __device__ __forceinline__ void operator()(int nfinal, const Pending &c, const is3d_particle &q)
+    {
+        if (nfinal < counted) {
+            is3d_particle o;
+            o.cell = q.cell; o.event = q.event; o.species = c.e;
+            o.tau = c.tau; o.x = c.x; o.y = c.y; o.eta = c.eta; o.t = c.t; o.z = c.z;
+            o.E = c.E; o.px = c.px; o.py = c.py; o.pz = c.pz;
+            a.out[slot0 + nfinal] = o;
+            if (a.origin) a.origin[slot0 + nfinal] = i;
+        }
+    }
+};
+// the bin pass: the same is3d_particle, built in registers, goes to the rule of cf_sampler_bins.h with slot[entry] as its species; slot -1
+// (or a primary whose event has no yield word) adds nothing.  kept counts what was binned: the primary's share of its event's yield.
+struct McBinArgs {
+    is3d_sampler_test_bins b;
+    is3d::SamplerBinWidths w;
+    is3d::SamplerHistLayout l;        // of n_slots species
+    int32_t n_slots, n_events;
+    const int32_t *slot;              // [table entries]
+    unsigned long long *hist, *yield, *tally;   // tally[kBinTallies]
+};
+struct SinkBin {
+    static constexpr bool kMomenta = true;
+    const McBinArgs &b;
+    unsigned long long *h;            // the workgroup's LDS block, or the global one
+    bool live;
+    long long kept;
+    __device__ __forceinline__ void operator()(int, const Pending &c, const is3d_particle &q)
+    {
+        const int s = b.slot[c.e];
+        if (!live || s < 0 || s >= b.n_slots) return;
+        is3d_particle o;
+        o.cell = q.cell; o.event = q.event; o.species = s;
+        o.tau = c.tau; o.x = c.x; o.y = c.y; o.eta = c.eta; o.t = c.t; o.z = c.z;
+        o.E = c.E; o.px = c.px; o.py = c.py; o.pz = c.pz;
+        const is3d::SamplerBinIndex k = is3d::sampler_bin_particle(b.b, b.w, o);
+        is3d::sampler_bin_add(b.b, b.l, b.n_slots, k, s, h);
+        kept++;
+    }
+};
+
 // the decay tree of primary i; returns its number of final particles
-template <bool KEEP>
-__device__ __forceinline__ int decay_tree(const McArgs &a, int64_t i, unsigned long long (&tally)[kTallies])
+template <class Sink>
+__device__ __forceinline__ int decay_tree(const McArgs &a, int64_t i, unsigned long long (&tally)[kTallies], Sink &sink)
 {
+    constexpr bool KEEP = Sink::kMomenta;
     const is3d_particle q = a.in[i];
     const uint64_t gi = (uint64_t)(a.first + i);
     Rng g;
@@ -94,21 +159,12 @@ __device__ __forceinline__ int decay_tree(const McArgs &a, int64_t i, unsigned l
     Pending c;
     c.E = q.E; c.px = q.px; c.py = q.py; c.pz = q.pz; c.t = q.t; c.x = q.x; c.y = q.y; c.z = q.z; c.tau = q.tau; c.eta = q.eta;
     c.e = a.chosen_entry[q.species];
-    const int64_t slot0 = KEEP ? a.offsets[i] : 0;
-    const int counted = KEEP ? a.counts[i] : 0;
     for (;;) {
         const int c0 = a.t.ch0[c.e], c1 = a.t.ch0[c.e + 1];
         const bool stable = a.t.stable[c.e] != 0;
         if (stable || c0 == c1) {                       // final: stable, or stuck without an open channel
             if (!stable) tally[1]++;
-            if (KEEP && nfinal < counted) {
-                is3d_particle o;
-                o.cell = q.cell; o.event = q.event; o.species = c.e;
-                o.tau = c.tau; o.x = c.x; o.y = c.y; o.eta = c.eta; o.t = c.t; o.z = c.z;
-                o.E = c.E; o.px = c.px; o.py = c.py; o.pz = c.pz;
-                a.out[slot0 + nfinal] = o;
-                if (a.origin) a.origin[slot0 + nfinal] = i;
-            }
+            sink(nfinal, c, q);
             nfinal++;
             if (sp == 0) break;
             c = stack[--sp];
@@ -195,8 +251,13 @@ __global__ void __launch_bounds__(kThreads) cf_decay_mc(const McArgs a)
     unsigned long long tally[kTallies] = {0ULL, 0ULL, 0ULL, 0ULL, 0ULL};
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i < a.n) {
-        const int nf = decay_tree<KEEP>(a, i, tally);
-        if (!KEEP) a.counts[i] = nf;
+        if (KEEP) {
+            SinkStore sink{a, i, a.offsets[i], a.counts[i]};
+            decay_tree(a, i, tally, sink);
+        } else {
+            SinkCount sink;
+            a.counts[i] = decay_tree(a, i, tally, sink);
+        }
     }
     if (!KEEP) {   // one global add per counter and workgroup
         __shared__ unsigned long long blk[kTallies];
@@ -207,6 +268,46 @@ __global__ void __launch_bounds__(kThreads) cf_decay_mc(const McArgs a)
         __syncthreads();
         if (threadIdx.x < kTallies && blk[threadIdx.x]) atomicAdd(&a.tally[threadIdx.x], blk[threadIdx.x]);
     }
+}
+
+// The one-pass bin kernel.  Every workgroup walks a grid-stride slice of the primaries (the trip count is the same for every thread of the
+// workgroup, so the wave operations of sampler_yield_runs see whole waves).  PRIVATE: the histogram block lives in LDS (dynamic, l.total
+// words, beside the static tally words) and is flushed once, non-zero words only; otherwise every add is a global 64-bit atomic.  The
+// pending stack stays in private memory in both forms.  Yields: a primary's binned finals share its event, and the primaries come ordered
+// by event, so the first lane of a run of equal events adds the run's sum -- one add per distinct event per wave.
+template <bool PRIVATE>
+__global__ void __launch_bounds__(kBinThreads) cf_decay_mc_bins(const McArgs a, const McBinArgs b)
+{
+    extern __shared__ unsigned long long priv[];
+    __shared__ unsigned long long blk[kBinTallies];
+    if (threadIdx.x < kBinTallies) blk[threadIdx.x] = 0ULL;
+    if (PRIVATE)
+        for (int64_t j = threadIdx.x; j < b.l.total; j += kBinThreads) priv[j] = 0ULL;
+    __syncthreads();
+    unsigned long long tally[kTallies] = {0ULL, 0ULL, 0ULL, 0ULL, 0ULL}, finals = 0ULL;
+    for (int64_t i0 = (int64_t)blockIdx.x * kBinThreads; i0 < a.n; i0 += (int64_t)gridDim.x * kBinThreads) {
+        const int64_t i = i0 + threadIdx.x;
+        int ev = INT_MAX;                                  // lanes past the end, or with an event outside the yields: no add at all
+        long long kept = 0;
+        if (i < a.n) {
+            const int event = a.in[i].event;
+            const bool live = event >= 0 && event < b.n_events;
+            SinkBin sink{b, PRIVATE ? priv : b.hist, live, 0};
+            finals += (unsigned long long)decay_tree(a, i, tally, sink);
+            if (live) { ev = event; kept = sink.kept; }
+        }
+        is3d::sampler_yield_runs(ev, kept, b.yield);
+    }
+    for (int k = 0; k < kTallies; k++)
+        if (tally[k]) atomicAdd(&blk[k], tally[k]);
+    if (finals) atomicAdd(&blk[kTallies], finals);
+    __syncthreads();
+    if (threadIdx.x < kBinTallies && blk[threadIdx.x]) atomicAdd(&b.tally[threadIdx.x], blk[threadIdx.x]);
+    if (PRIVATE)
+        for (int64_t j = threadIdx.x; j < b.l.total; j += kBinThreads) {
+            const unsigned long long v = priv[j];
+            if (v) atomicAdd(&b.hist[j], v);
+        }
 }
 
 struct Widen {
@@ -331,49 +432,135 @@ struct Events {
 
 }  // namespace
 
+// The table as the kernels read it, resident on one device: the analysis (every table refusal) happens on the host before any device use,
+// the upload once.  is3d_decay_particles builds one per call; a caller that keeps its primaries on the device keeps the table there too.
+struct is3d_decay_mc_table {
+    int device = -1;                  // where the arrays live; -1: analysed only
+    int32_t n = 0, n_chosen = 0;
+    McHostTable H;
+    DevBuf<double> d_mass, d_width, d_cum;
+    DevBuf<int32_t> d_stable, d_ch0, d_nbody, d_dau, d_chosen;
+    McTable dev() const { return McTable{d_mass.p, d_width.p, d_stable.p, d_ch0.p, d_cum.p, d_nbody.p, d_dau.p}; }
+};
+
+namespace {
+
+// the arrays of an analysed table to the current device
+int table_upload(is3d_decay_mc_table &t, const is3d_decay_table &table)
+{
+    HIP_TRY(hipGetDevice(&t.device));
+    HIP_TRY(t.d_mass.upload(table.mass, (size_t)table.n));
+    HIP_TRY(t.d_width.upload(table.width, (size_t)table.n));
+    HIP_TRY(t.d_stable.upload(table.stable, (size_t)table.n));
+    HIP_TRY(t.d_ch0.upload(t.H.ch0));
+    HIP_TRY(t.d_cum.upload(t.H.cum));
+    HIP_TRY(t.d_nbody.upload(t.H.nbody));
+    HIP_TRY(t.d_dau.upload(t.H.dau));
+    HIP_TRY(t.d_chosen.upload(t.H.chosen_entry));
+    return IS3D_OK;
+}
+
+// what both host-list entries check of their list before the table is looked at ...
+int check_list_head(int32_t n_chosen, int64_t n_particles, const is3d_particle *particles)
+{
+    if (n_chosen < 1) return set_error(IS3D_EINVAL, "n_chosen = %d: the list's species index a chosen list of at least one", n_chosen);
+    if (n_particles < 0 || n_particles > INT32_MAX) return set_error(IS3D_EINVAL, "n_particles = %lld: 0 .. 2^31 - 1", (long long)n_particles);
+    if (n_particles > 0 && !particles) return set_error(IS3D_EINVAL, "particles is NULL");
+    return IS3D_OK;
+}
+// ... and after it
+int check_list_species(int32_t n_chosen, int64_t n_particles, const is3d_particle *particles)
+{
+    for (int64_t i = 0; i < n_particles; i++)
+        if (particles[i].species < 0 || particles[i].species >= n_chosen)
+            return set_error(IS3D_EINVAL, "particle %lld: species %d outside the chosen list (%d)", (long long)i, particles[i].species, n_chosen);
+    return IS3D_OK;
+}
+
+int no_device() { return set_error(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path"); }
+
+}  // namespace
+
+void is3d::decay_mc_table_stats(const is3d_decay_mc_table *t, is3d_decay_mc_stats *st)
+{
+    st->max_stack = t->H.max_stack;
+    st->max_depth = t->H.max_depth;
+    st->n_closed_channels = t->H.n_closed;
+}
+int32_t is3d::decay_mc_table_entries(const is3d_decay_mc_table *t) { return t->n; }
+int32_t is3d::decay_mc_table_chosen(const is3d_decay_mc_table *t) { return t->n_chosen; }
+int is3d::decay_mc_table_device(const is3d_decay_mc_table *t) { return t->device; }
+
+namespace {
+int table_analyse(is3d_decay_mc_table &t, const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id)
+{
+    if (!table || !chosen_mc_id) return set_error(IS3D_EINVAL, "table and chosen_mc_id are required");
+    if (n_chosen < 1) return set_error(IS3D_EINVAL, "n_chosen = %d: the list's species index a chosen list of at least one", n_chosen);
+    return analyse(*table, n_chosen, chosen_mc_id, t.H);
+}
+}  // namespace
+
+int is3d::decay_mc_table_check(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id)
+{
+    is3d_decay_mc_table t;
+    return table_analyse(t, table, n_chosen, chosen_mc_id);
+}
+
+extern "C" int is3d_decay_mc_table_create(is3d_decay_mc_table **out, const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
+                                          int32_t device)
+{
+    if (!out) return set_error(IS3D_EINVAL, "null argument");
+    *out = nullptr;
+    std::unique_ptr<is3d_decay_mc_table> t(new is3d_decay_mc_table);
+    if (int rc = table_analyse(*t, table, n_chosen, chosen_mc_id)) return rc;
+    t->n = table->n;
+    t->n_chosen = n_chosen;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return no_device();
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    if (int rc = table_upload(*t, *table)) return rc;
+    *out = t.release();
+    return IS3D_OK;
+}
+
+extern "C" void is3d_decay_mc_table_destroy(is3d_decay_mc_table *t)
+{
+    if (!t) return;
+    if (t->device >= 0) (void)hipSetDevice(t->device);
+    delete t;
+}
+
 extern "C" int is3d_decay_particles(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id, const is3d_decay_mc_inputs *in,
                                     int64_t n_particles, const is3d_particle *particles, is3d_particle *out, int64_t *origin, int64_t capacity,
                                     int64_t *n_out, is3d_decay_mc_stats *stats)
 {
     if (!table || !chosen_mc_id || !in || !n_out) return set_error(IS3D_EINVAL, "table, chosen_mc_id, in and n_out are required");
-    if (n_chosen < 1) return set_error(IS3D_EINVAL, "n_chosen = %d: the list's species index a chosen list of at least one", n_chosen);
-    if (n_particles < 0 || n_particles > INT32_MAX) return set_error(IS3D_EINVAL, "n_particles = %lld: 0 .. 2^31 - 1", (long long)n_particles);
-    if (n_particles > 0 && !particles) return set_error(IS3D_EINVAL, "particles is NULL");
+    if (int rc = check_list_head(n_chosen, n_particles, particles)) return rc;
     if (out && capacity < 0) return set_error(IS3D_EINVAL, "capacity = %lld", (long long)capacity);
-    McHostTable H;
-    if (int rc = analyse(*table, n_chosen, chosen_mc_id, H)) return rc;
-    for (int64_t i = 0; i < n_particles; i++)
-        if (particles[i].species < 0 || particles[i].species >= n_chosen)
-            return set_error(IS3D_EINVAL, "particle %lld: species %d outside the chosen list (%d)", (long long)i, particles[i].species, n_chosen);
+    is3d_decay_mc_table tb;
+    if (int rc = analyse(*table, n_chosen, chosen_mc_id, tb.H)) return rc;
+    tb.n = table->n;
+    tb.n_chosen = n_chosen;
+    if (int rc = check_list_species(n_chosen, n_particles, particles)) return rc;
     is3d_decay_mc_stats st{};
     st.n_primaries = n_particles;
-    st.max_stack = H.max_stack;
-    st.max_depth = H.max_depth;
-    st.n_closed_channels = H.n_closed;
+    is3d::decay_mc_table_stats(&tb, &st);
     *n_out = 0;
     if (n_particles == 0) {
         if (stats) *stats = st;
         return IS3D_OK;
     }
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return set_error(IS3D_ENODEVICE, "no HIP device visible; this library has no CPU path");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return no_device();
     if (in->device >= 0) HIP_TRY(hipSetDevice(in->device));
     // ---- upload ----
     const auto t0 = std::chrono::steady_clock::now();
-    DevBuf<double> d_mass, d_width, d_cum;
-    DevBuf<int32_t> d_stable, d_ch0, d_nbody, d_dau, d_chosen, d_counts;
+    DevBuf<int32_t> d_counts;
     DevBuf<int64_t> d_offsets, d_origin;
     DevBuf<is3d_particle> d_in, d_out;
     DevBuf<unsigned long long> d_tally;
     DevBuf<unsigned char> d_tmp;
-    HIP_TRY(d_mass.upload(table->mass, (size_t)table->n));
-    HIP_TRY(d_width.upload(table->width, (size_t)table->n));
-    HIP_TRY(d_stable.upload(table->stable, (size_t)table->n));
-    HIP_TRY(d_ch0.upload(H.ch0));
-    HIP_TRY(d_cum.upload(H.cum));
-    HIP_TRY(d_nbody.upload(H.nbody));
-    HIP_TRY(d_dau.upload(H.dau));
-    HIP_TRY(d_chosen.upload(H.chosen_entry));
+    if (int rc = table_upload(tb, *table)) return rc;
     HIP_TRY(d_in.upload(particles, (size_t)n_particles));
     HIP_TRY(d_counts.alloc((size_t)n_particles));
     HIP_TRY(d_offsets.alloc((size_t)n_particles + 1));
@@ -389,8 +576,8 @@ extern "C" int is3d_decay_particles(const is3d_decay_table *table, int32_t n_cho
     const auto t1 = std::chrono::steady_clock::now();
     // ---- count, scan ----
     McArgs a{};
-    a.t = McTable{d_mass.p, d_width.p, d_stable.p, d_ch0.p, d_cum.p, d_nbody.p, d_dau.p};
-    a.chosen_entry = d_chosen.p;
+    a.t = tb.dev();
+    a.chosen_entry = tb.d_chosen.p;
     a.in = d_in.p;
     a.n = n_particles;
     a.first = in->first_particle;
@@ -444,4 +631,123 @@ extern "C" int is3d_decay_particles(const is3d_decay_table *table, int32_t n_cho
     }
     if (stats) *stats = st;
     return IS3D_OK;
+}
+
+// ---- decayed and binned in one pass ----
+int is3d::decay_mc_check_slots(int32_t n_entries, const int32_t *slot, int32_t n_slots, const is3d_sampler_test_bins *bins)
+{
+    if (n_slots < 1) return set_error(IS3D_EINVAL, "n_slots = %d: the decayed histograms hold at least one species", n_slots);
+    if (!slot) return set_error(IS3D_EINVAL, "slot is NULL");
+    for (int32_t e = 0; e < n_entries; e++)
+        if (slot[e] < -1 || slot[e] >= n_slots) return set_error(IS3D_EINVAL, "slot[%d] = %d: -1 .. %d", e, slot[e], n_slots - 1);
+    const SamplerHistLayout l = sampler_hist_layout(*bins, n_slots);
+    if (bins->kernel_form == 2 && !decay_mc_bins_lds_fits(l))
+        return set_error(IS3D_EINVAL, "kernel_form = 2: %lld histogram words do not fit the LDS", (long long)l.total);
+    return IS3D_OK;
+}
+
+hipError_t is3d::decay_mc_bins_launch(const DecayMcBinRun &r, const is3d_particle *primaries_dev, int64_t n, int64_t first_particle)
+{
+    if (n <= 0) return hipSuccess;
+    const bool fits = decay_mc_bins_lds_fits(r.layout);
+    const int form = r.bins.kernel_form;
+    if (form == 2 && !fits) return hipErrorInvalidValue;
+    const bool priv = form == 2 || (form == 0 && fits);
+    McArgs a{};
+    a.t = r.table->dev();
+    a.chosen_entry = r.table->d_chosen.p;
+    a.in = primaries_dev;
+    a.n = n;
+    a.first = first_particle;
+    a.seed = r.seed;
+    a.lifetime = r.lifetime;
+    McBinArgs b{r.bins, r.widths, r.layout, r.n_slots, r.n_events, r.slot_dev, r.block_dev, r.block_dev + r.layout.total,
+                r.block_dev + r.layout.total + r.n_events};
+    const int64_t trips = (n + kBinThreads - 1) / kBinThreads;
+    if (priv)
+        hipLaunchKernelGGL(cf_decay_mc_bins<true>, dim3((unsigned)std::min<int64_t>(trips, kBinPrivateBlocks)), dim3(kBinThreads),
+                           (size_t)r.layout.total * sizeof(unsigned long long), nullptr, a, b);
+    else
+        hipLaunchKernelGGL(cf_decay_mc_bins<false>, dim3((unsigned)trips), dim3(kBinThreads), 0, nullptr, a, b);
+    return hipGetLastError();
+}
+
+int is3d::decay_mc_bins_tallies(const unsigned long long *tally, is3d_decay_mc_stats *st)
+{
+    st->n_decays = (int64_t)tally[0];
+    st->n_stuck = (int64_t)tally[1];
+    st->n_trials = (int64_t)tally[2];
+    st->n_exhausted = (int64_t)tally[3];
+    st->n_final = (int64_t)tally[5];
+    if (tally[4]) return set_error(IS3D_EINVAL, "the pending stack of %d particles overflowed for %llu primaries", kStack, tally[4]);
+    return IS3D_OK;
+}
+
+extern "C" int is3d_decay_particles_binned(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
+                                           const is3d_decay_mc_inputs *in, int64_t n_particles, const is3d_particle *particles,
+                                           const int32_t *slot, int32_t n_slots, const is3d_sampler_test_bins *bins, int32_t n_events,
+                                           const is3d_sampler_hist *hist, int64_t *n_final, int64_t *n_unbinned, is3d_decay_mc_stats *stats)
+{
+    if (!table || !chosen_mc_id || !in || !n_final || !n_unbinned)
+        return set_error(IS3D_EINVAL, "table, chosen_mc_id, in, n_final and n_unbinned are required");
+    *n_final = *n_unbinned = 0;
+    if (int rc = check_list_head(n_chosen, n_particles, particles)) return rc;
+    is3d_decay_mc_table tb;
+    if (int rc = analyse(*table, n_chosen, chosen_mc_id, tb.H)) return rc;
+    tb.n = table->n;
+    tb.n_chosen = n_chosen;
+    if (int rc = check_list_species(n_chosen, n_particles, particles)) return rc;
+    if (n_slots < 1) return set_error(IS3D_EINVAL, "n_slots = %d: the decayed histograms hold at least one species", n_slots);
+    if (int rc = is3d::sampler_check_bin_args(bins, hist, n_events, n_slots)) return rc;
+    if (int rc = is3d::decay_mc_check_slots(table->n, slot, n_slots, bins)) return rc;
+    for (int64_t i = 0; i < n_particles; i++)
+        if (particles[i].event < 0 || particles[i].event >= n_events)
+            return set_error(IS3D_EINVAL, "particle %lld: event %d outside the %d events", (long long)i, particles[i].event, n_events);
+    is3d_decay_mc_stats st{};
+    st.n_primaries = n_particles;
+    is3d::decay_mc_table_stats(&tb, &st);
+    const is3d::SamplerHistLayout l = is3d::sampler_hist_layout(*bins, n_slots);
+    DevBuf<unsigned char> d_block;
+    if (n_particles == 0) {
+        if (int rc = is3d::sampler_hist_begin(d_block, hist, l, n_events, 0, false)) return rc;
+        if (stats) *stats = st;
+        return IS3D_OK;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return no_device();
+    if (in->device >= 0) HIP_TRY(hipSetDevice(in->device));
+    // ---- upload: the table, the primaries, the slot map; the block of histograms, yields and tallies zeroed ----
+    const auto t0 = std::chrono::steady_clock::now();
+    DevBuf<is3d_particle> d_in;
+    DevBuf<int32_t> d_slot;
+    if (int rc = table_upload(tb, *table)) return rc;
+    HIP_TRY(d_in.upload(particles, (size_t)n_particles));
+    HIP_TRY(d_slot.upload(slot, (size_t)table->n));
+    if (int rc = is3d::sampler_hist_begin(d_block, hist, l, n_events, kBinTallies, true)) return rc;
+    Events ev;
+    for (int k = 0; k < 2; k++) HIP_TRY(hipEventCreate(&ev.e[k]));
+    HIP_TRY(hipDeviceSynchronize());
+    const auto t1 = std::chrono::steady_clock::now();
+    // ---- the one pass ----
+    const is3d::DecayMcBinRun run{&tb,   d_slot.p, n_slots, n_events, in->seed, in->lifetime, *bins, is3d::sampler_bin_widths(*bins),
+                                  l,     d_block.as<unsigned long long>()};
+    HIP_TRY(hipEventRecord(ev.e[0], nullptr));
+    HIP_TRY(is3d::decay_mc_bins_launch(run, d_in.p, n_particles, in->first_particle));
+    HIP_TRY(hipEventRecord(ev.e[1], nullptr));
+    HIP_TRY(hipEventSynchronize(ev.e[1]));
+    st.ms_h2d = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    st.ms_bin = ms_between(ev.e[0], ev.e[1]);
+    const auto t2 = std::chrono::steady_clock::now();
+    unsigned long long tally[kBinTallies];
+    HIP_TRY(hipMemcpy(tally, run.block_dev + l.total + n_events, sizeof tally, hipMemcpyDeviceToHost));
+    if (int rc = is3d::sampler_hist_end(d_block, hist, l, n_events)) return rc;
+    st.ms_d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count();
+    const int rc = is3d::decay_mc_bins_tallies(tally, &st);
+    int64_t binned = 0;
+    for (int32_t e = 0; e < n_events; e++) binned += hist->yield[e];
+    *n_final = st.n_final;
+    *n_unbinned = st.n_final - binned;
+    if (stats) *stats = st;
+    if (rc) return rc;
+    return is3d::sampler_hist_check_counts(hist, l);
 }

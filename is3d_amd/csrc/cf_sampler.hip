@@ -45,6 +45,7 @@
 #include "cf_math.h"
 #include "cf_plan_geometry.h"
 #include "cf_sampler_bins.h"
+#include "cf_decays_mc.h"
 #include "cf_sampler_common.h"
 #include "errors.h"
 #include "jonah.h"
@@ -329,12 +330,13 @@ struct is3d_sampler_plan {
     DevMem d_status, d_GT, d_GT2, d_GT3, d_rec, d_counts, d_offsets, d_scan_tmp;
     DevMem d_drawn, d_emits, d_active, d_nactive, d_cdf;
     DevMem d_particles, d_hist;             // a binned run: one batch of particles (list-and-bin only); the histograms, then the yields
+    DevMem d_hist_decayed, d_slot;          // a decayed-and-binned run: the second block (histograms, yields, tallies) and the slot map
     int64_t cap_cells = 0, cap_bt = 0;      // what the workspaces above were sized for
     int64_t cap_list = 0;                   // ... d_counts and d_offsets, which a fused binned run never has
     size_t tmp_select = 0, tmp_scan = 0;
     int64_t cap_particles = 0;
     size_t tmp_bytes = 0;
-    hipEvent_t ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     is3d::ViscousModel model{};             // the viscous sampler as a variant of its own plan (is3d_sampler_plan_create; unused by other variants)
     is3d::SamplerVariant viscous;
 };
@@ -626,7 +628,8 @@ int bind_cells(is3d_sampler_plan *P, const is3d_cells *cells, int64_t first_cell
 using BinRun = is3d::SamplerBinRun;
 int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t n, const double *x_dev, const double *y_dev, int32_t n_events,
                     uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
-                    bool fuse, int64_t *n_particles, is3d_sampler_stats *stats);
+                    bool fuse, int64_t *n_particles, is3d_sampler_stats *stats, const is3d::DecayMcBinRun *decay = nullptr,
+                    double *ms_decay = nullptr);
 }  // namespace
 
 extern "C" void is3d_sampler_plan_destroy(is3d_sampler_plan *P)
@@ -656,10 +659,11 @@ extern "C" int is3d_sampler_plan_execute(is3d_sampler_plan *P, const is3d_cells 
 namespace {
 // the one batch loop of every variant.  bin == NULL fills the caller's list (or only counts); bin != NULL with fuse samples each batch
 // straight into P->d_hist (cf_sampler_fused); bin != NULL without it fills each batch into the plan's particle workspace at base 0, bins it
-// into P->d_hist (cf_sampler_bins) and drops it
+// into P->d_hist (cf_sampler_bins) and drops it -- after, with decay != NULL, the batch's hadrons as primaries base .. of the whole list have
+// been decayed and binned into decay->block_dev (cf_decay_mc_bins), whose time is added to *ms_decay
 int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t n, const double *x_dev, const double *y_dev, int32_t n_events,
                     uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
-                    bool fuse, int64_t *n_particles, is3d_sampler_stats *stats)
+                    bool fuse, int64_t *n_particles, is3d_sampler_stats *stats, const is3d::DecayMcBinRun *decay, double *ms_decay)
 {
     using is3d::set_error;
     if (particles_dev == nullptr || bin) capacity = 0;
@@ -786,6 +790,14 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t
                                               P->d_hist.as<unsigned long long>(), P->d_hist.as<unsigned long long>() + bin->layout.total,
                                               bin->bins.kernel_form));
         HIP_TRY(hipEventRecord(ev[4], nullptr));
+        if (decay && bin && !fused && batch_total > 0) {
+            HIP_TRY(is3d::decay_mc_bins_launch(*decay, P->d_particles.as<is3d_particle>(), batch_total, base));
+            HIP_TRY(hipEventRecord(ev[9], nullptr));
+            HIP_TRY(hipEventSynchronize(ev[9]));
+            float e_ms = 0;
+            HIP_TRY(hipEventElapsedTime(&e_ms, ev[4], ev[9]));
+            *ms_decay += e_ms;
+        }
         HIP_TRY(hipEventSynchronize(ev[4]));
         float a_ms = 0, b_ms = 0, c_ms = 0, d_ms = 0;
         HIP_TRY(hipEventElapsedTime(&a_ms, ev[5], ev[3]));
@@ -1012,6 +1024,19 @@ int is3d::sampler_check_fused_args(const is3d_sampler_test_bins *bins, const is3
     return check_bin_args_lds(bins, hist, n_events, n_species, true);
 }
 
+int is3d::sampler_hist_begin(DevMem &d_hist, const is3d_sampler_hist *hist, const SamplerHistLayout &l, int32_t n_events, int64_t extra_words,
+                             bool device)
+{
+    return hist_begin(d_hist, hist_parts(*hist, l), hist, n_events, l.total + n_events + extra_words, device);
+}
+
+int is3d::sampler_hist_end(const DevMem &d_hist, const is3d_sampler_hist *hist, const SamplerHistLayout &l, int32_t n_events)
+{
+    return hist_end(d_hist, hist_parts(*hist, l), hist, n_events, l.total + n_events);
+}
+
+int is3d::sampler_hist_check_counts(const is3d_sampler_hist *hist, const SamplerHistLayout &l) { return hist_check_counts(hist_parts(*hist, l), hist); }
+
 int is3d::sampler_variant_execute_binned(is3d_sampler_plan *P, const SamplerVariant &v, int64_t n_cells, const double *x_dev, const double *y_dev,
                                          int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
                                          const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, bool fuse, int64_t *n_particles,
@@ -1107,6 +1132,107 @@ extern "C" int is3d_sample_fused(const is3d_cells *cells, const is3d_species *sp
                                  int64_t *n_particles, is3d_sampler_stats *stats)
 {
     return sample_binned(cells, species, df, in, opts, bins, hist, n_particles, stats, true);
+}
+
+// ------------------------------------------------------------------------------------------------
+// binned twice: the thermal hadrons of each event batch as above and, from the same workspace, their decay products (cf_decays_mc.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" int is3d_sampler_plan_execute_decayed_binned(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev,
+                                                        int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
+                                                        const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist,
+                                                        const is3d_decay_mc_table *table, const int32_t *slot, int32_t n_slots,
+                                                        uint64_t decay_seed, int32_t lifetime, const is3d_sampler_hist *hist_decayed,
+                                                        int64_t *n_particles, int64_t *n_final, int64_t *n_unbinned, is3d_sampler_stats *stats,
+                                                        is3d_decay_mc_stats *decay_stats)
+{
+    using is3d::set_error;
+    if (!P || !cells || !n_particles || !table || !n_final || !n_unbinned) return set_error(IS3D_EINVAL, "null argument");
+    *n_particles = *n_final = *n_unbinned = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (decay_stats) memset(decay_stats, 0, sizeof *decay_stats);
+    if (int rc = check_bin_args_lds(bins, hist, n_events, P->sp.npart, false)) return rc;
+    if (n_slots < 1) return set_error(IS3D_EINVAL, "n_slots = %d: the decayed histograms hold at least one species", n_slots);
+    if (int rc = check_bin_args(bins, hist_decayed, n_events)) return rc;
+    if (int rc = is3d::decay_mc_check_slots(is3d::decay_mc_table_entries(table), slot, n_slots, bins)) return rc;
+    if (is3d::decay_mc_table_chosen(table) != P->sp.npart)
+        return set_error(IS3D_EINVAL, "the decay table was created for %d chosen species, the sampler plan for %d", is3d::decay_mc_table_chosen(table),
+                         P->sp.npart);
+    if (is3d::decay_mc_table_device(table) != P->device)
+        return set_error(IS3D_EINVAL, "the decay table lives on device %d, the sampler plan on device %d", is3d::decay_mc_table_device(table), P->device);
+    if (int rc = bind_cells(P, cells, first_cell)) return rc;
+    const int64_t n_cells = cells->n_cells;
+    const BinRun br{*bins, is3d::sampler_bin_widths(*bins), is3d::sampler_hist_layout(*bins, P->sp.npart)};
+    const is3d::SamplerHistLayout ld = is3d::sampler_hist_layout(*bins, n_slots);
+    const HistParts parts = hist_parts(*hist, br.layout), parts_d = hist_parts(*hist_decayed, ld);
+    const int64_t words = br.layout.total + n_events, words_d = ld.total + n_events;
+    const int32_t n_entries = is3d::decay_mc_table_entries(table);
+    is3d_decay_mc_stats dst{};
+    is3d::decay_mc_table_stats(table, &dst);
+    if (n_cells > 0) HIP_TRY(hipSetDevice(P->device));
+    // the thermal block as in execute_binned; the decayed block (histograms | yields | tallies) and the slot map sized at first use
+    if (int rc = hist_begin(P->d_hist, parts, hist, n_events, words, n_cells > 0)) return rc;
+    if (int rc = hist_begin(P->d_hist_decayed, parts_d, hist_decayed, n_events, words_d + is3d::kDecayMcBinTallies, n_cells > 0)) return rc;
+    if (n_cells > 0) {
+        if ((size_t)n_entries * sizeof(int32_t) > P->d_slot.n) HIP_TRY(P->d_slot.alloc((size_t)n_entries * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(P->d_slot.p, slot, (size_t)n_entries * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    const is3d::DecayMcBinRun run{table, P->d_slot.as<int32_t>(), n_slots, n_events, decay_seed, lifetime, *bins, br.widths, ld,
+                                  P->d_hist_decayed.as<unsigned long long>()};
+    int64_t listed = 0;
+    double ms_decay = 0.0;
+    if (int rc = sampler_batches(P, P->viscous, n_cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, nullptr, 0, &br, false, &listed, stats,
+                                 &run, &ms_decay))
+        return rc;
+    dst.n_primaries = listed;
+    dst.ms_bin = ms_decay;
+    if (n_cells == 0) {
+        if (decay_stats) *decay_stats = dst;
+        return IS3D_OK;
+    }
+    if (int rc = hist_end(P->d_hist, parts, hist, n_events, words)) return rc;
+    if (int rc = hist_end(P->d_hist_decayed, parts_d, hist_decayed, n_events, words_d)) return rc;
+    unsigned long long tally[is3d::kDecayMcBinTallies];
+    HIP_TRY(hipMemcpy(tally, run.block_dev + words_d, sizeof tally, hipMemcpyDeviceToHost));
+    const int rc_t = is3d::decay_mc_bins_tallies(tally, &dst);
+    int64_t binned = 0;
+    for (int32_t e = 0; e < n_events; e++) binned += hist_decayed->yield[e];
+    *n_particles = listed;
+    *n_final = dst.n_final;
+    *n_unbinned = dst.n_final - binned;
+    if (decay_stats) *decay_stats = dst;
+    if (rc_t) return rc_t;
+    if (int rc = hist_check_counts(parts, hist)) return rc;
+    return hist_check_counts(parts_d, hist_decayed);
+}
+
+// host-pointer one-shot: create, upload, execute, destroy (the table included)
+extern "C" int is3d_sample_decayed_binned(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                                          const is3d_options *opts, const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist,
+                                          const is3d_decay_table *table, const int64_t *chosen_mc_id, const int32_t *slot, int32_t n_slots,
+                                          uint64_t decay_seed, int32_t lifetime, const is3d_sampler_hist *hist_decayed, int64_t *n_particles,
+                                          int64_t *n_final, int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats)
+{
+    using is3d::set_error;
+    if (!cells || !species || !df || !in || !opts || !n_particles || !table || !chosen_mc_id || !n_final || !n_unbinned)
+        return set_error(IS3D_EINVAL, "null argument");
+    *n_particles = *n_final = *n_unbinned = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (decay_stats) memset(decay_stats, 0, sizeof *decay_stats);
+    if (int rc = check_bin_args(bins, hist, in->n_events)) return rc;
+    if (n_slots < 1) return set_error(IS3D_EINVAL, "n_slots = %d: the decayed histograms hold at least one species", n_slots);
+    if (int rc = check_bin_args(bins, hist_decayed, in->n_events)) return rc;
+    if (int rc = is3d::decay_mc_check_slots(table->n, slot, n_slots, bins)) return rc;
+    // (the table's refusals on the host first, then the plan's: none of them needs a device)
+    if (int rc = is3d::decay_mc_table_check(table, species->n, chosen_mc_id)) return rc;
+    StagedRun r;
+    if (int rc = stage_run(r, cells, species, df, in, opts)) return rc;
+    struct TableGuard { is3d_decay_mc_table *t = nullptr; ~TableGuard() { is3d_decay_mc_table_destroy(t); } } tg;
+    if (int rc = is3d_decay_mc_table_create(&tg.t, table, species->n, chosen_mc_id, r.P->device)) return rc;
+    const int rc = is3d_sampler_plan_execute_decayed_binned(r.P, &r.dc, r.xy[0], r.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events,
+                                                            bins, hist, tg.t, slot, n_slots, decay_seed, lifetime, hist_decayed, n_particles, n_final,
+                                                            n_unbinned, stats, decay_stats);
+    if (stats) stats->ms_h2d = r.ms_h2d;
+    return rc;
 }
 
 // a caller's list through the same kernel: upload, sampler_bins_launch, download as is3d_sampler_plan_execute_binned does

@@ -115,6 +115,28 @@ IS3D_BINS_HD SamplerBinIndex sampler_bin_particle(const is3d_sampler_test_bins &
 IS3D_BINS_HD long long sampler_vn_fixed(double term) { return llrint(term * IS3D_SAMPLER_VN_SCALE); }
 
 #if defined(__HIP__) || defined(__HIPCC__)
+// The adds of one particle with bins k and species s into the block h (layout l; the workgroup's LDS copy or the global block): five counts
+// and, in a dN_pT bin, the 14 fixed-point harmonic terms -- 64-bit integer atomics.  THE add sequence of cf_sampler_bins, cf_sampler_fused
+// and cf_decay_mc_bins.
+__device__ __forceinline__ void sampler_bin_add(const is3d_sampler_test_bins &b, const SamplerHistLayout &l, int n_species, const SamplerBinIndex &k,
+                                                int64_t s, unsigned long long *h)
+{
+    if (k.iyp >= 0) atomicAdd(&h[l.dy + s * b.y_bins + k.iyp], 1ULL);
+    if (k.ieta >= 0) atomicAdd(&h[l.de + s * b.eta_bins + k.ieta], 1ULL);
+    if (k.itau >= 0) atomicAdd(&h[l.dt + s * b.tau_bins + k.itau], 1ULL);
+    if (k.ir >= 0) atomicAdd(&h[l.dr + s * b.r_bins + k.ir], 1ULL);
+    if (k.ipT >= 0) {
+        const int64_t j = s * b.pT_bins + k.ipT, plane = (int64_t)n_species * b.pT_bins;
+        atomicAdd(&h[l.dp + j], 1ULL);
+        for (int m = 0; m < IS3D_SAMPLER_VN_HARMONICS; m++) {
+            double sn, cs;
+            sincos(((double)m + 1.0) * k.phi, &sn, &cs);
+            atomicAdd(&h[l.vr + m * plane + j], (unsigned long long)sampler_vn_fixed(cs));   // two's complement: signed sums
+            atomicAdd(&h[l.vi + m * plane + j], (unsigned long long)sampler_vn_fixed(sn));
+        }
+    }
+}
+
 // the device side (cf_sampler_bins.hip): one batch of n particles (a DEVICE list, ordered by event as the sampler fills it) added into
 // hist_dev (layout l) and yield_dev (n_events) on the null stream.  form: 0 = the measured choice (workgroup-private histograms where
 // they fit the LDS, global atomics otherwise), 1 = global atomics, 2 = workgroup-private (needs sampler_bins_lds_fits).

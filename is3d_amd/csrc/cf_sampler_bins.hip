@@ -68,21 +68,7 @@ cf_sampler_bins(BinArgs a, const is3d_particle *__restrict__ particles, int64_t 
         }
         if (!ok) continue;
         const SamplerBinIndex k = sampler_bin_particle(a.b, a.w, q);
-        const int64_t s = q.species;
-        if (k.iyp >= 0) atomicAdd(&h[a.l.dy + s * a.b.y_bins + k.iyp], 1ULL);
-        if (k.ieta >= 0) atomicAdd(&h[a.l.de + s * a.b.eta_bins + k.ieta], 1ULL);
-        if (k.itau >= 0) atomicAdd(&h[a.l.dt + s * a.b.tau_bins + k.itau], 1ULL);
-        if (k.ir >= 0) atomicAdd(&h[a.l.dr + s * a.b.r_bins + k.ir], 1ULL);
-        if (k.ipT >= 0) {
-            const int64_t j = s * a.b.pT_bins + k.ipT, plane = (int64_t)a.n_species * a.b.pT_bins;
-            atomicAdd(&h[a.l.dp + j], 1ULL);
-            for (int m = 0; m < IS3D_SAMPLER_VN_HARMONICS; m++) {
-                double sn, cs;
-                sincos(((double)m + 1.0) * k.phi, &sn, &cs);
-                atomicAdd(&h[a.l.vr + m * plane + j], (unsigned long long)sampler_vn_fixed(cs));   // two's complement: signed sums
-                atomicAdd(&h[a.l.vi + m * plane + j], (unsigned long long)sampler_vn_fixed(sn));
-            }
-        }
+        sampler_bin_add(a.b, a.l, a.n_species, k, q.species, h);
     }
     if (PRIVATE) {
         __syncthreads();

@@ -332,21 +332,7 @@ struct SamplerKeepBin {
     __device__ __forceinline__ void operator()(const is3d_particle &q)
     {
         const SamplerBinIndex k = sampler_bin_particle(a.b, a.w, q);
-        const int64_t s = q.species;
-        if (k.iyp >= 0) atomicAdd(&h[a.l.dy + s * a.b.y_bins + k.iyp], 1ULL);
-        if (k.ieta >= 0) atomicAdd(&h[a.l.de + s * a.b.eta_bins + k.ieta], 1ULL);
-        if (k.itau >= 0) atomicAdd(&h[a.l.dt + s * a.b.tau_bins + k.itau], 1ULL);
-        if (k.ir >= 0) atomicAdd(&h[a.l.dr + s * a.b.r_bins + k.ir], 1ULL);
-        if (k.ipT >= 0) {
-            const int64_t j = s * a.b.pT_bins + k.ipT, plane = (int64_t)a.n_species * a.b.pT_bins;
-            atomicAdd(&h[a.l.dp + j], 1ULL);
-            for (int m = 0; m < IS3D_SAMPLER_VN_HARMONICS; m++) {
-                double sn, cs;
-                sincos(((double)m + 1.0) * k.phi, &sn, &cs);
-                atomicAdd(&h[a.l.vr + m * plane + j], (unsigned long long)sampler_vn_fixed(cs));   // two's complement: signed sums
-                atomicAdd(&h[a.l.vi + m * plane + j], (unsigned long long)sampler_vn_fixed(sn));
-            }
-        }
+        sampler_bin_add(a.b, a.l, a.n_species, k, q.species, h);
     }
 };
 
@@ -612,6 +598,15 @@ int sampler_variant_execute_binned(is3d_sampler_plan *P, const SamplerVariant &v
 int sampler_check_bin_args(const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int32_t n_events, int32_t n_species);
 // the same for every fused entry, viscous and anisotropic: kernel_form = 2 needs sampler_fused_lds_fits
 int sampler_check_fused_args(const is3d_sampler_test_bins *bins, const is3d_sampler_hist *hist, int32_t n_events, int32_t n_species);
+// A binned run's histograms for an entry outside cf_sampler.hip (is3d_decay_particles_binned).  begin: the caller's arrays (layout l,
+// n_events yields) zeroed and, with `device`, the block  histograms | yields | extra_words  grown on the current device and zeroed on the
+// null stream; end: the one copy of histograms and yields to the caller's arrays; check_counts: IS3D_EDOMAIN for a dN_pT bin above
+// IS3D_SAMPLER_VN_MAX_COUNT.
+template <class T> struct DevBuf;
+int sampler_hist_begin(DevBuf<unsigned char> &d_hist, const is3d_sampler_hist *hist, const SamplerHistLayout &l, int32_t n_events,
+                       int64_t extra_words, bool device);
+int sampler_hist_end(const DevBuf<unsigned char> &d_hist, const is3d_sampler_hist *hist, const SamplerHistLayout &l, int32_t n_events);
+int sampler_hist_check_counts(const is3d_sampler_hist *hist, const SamplerHistLayout &l);
 
 // is3d_sample_particles_vah's refusals (IS3D_EINVAL), all before any device use: also what is3d_sample_particles_vah_multi checks first
 int sampler_vah_check(const is3d_vah_cells *cells, const is3d_species *species, const is3d_vah_df_tables *tab, const is3d_sampler_inputs *in,

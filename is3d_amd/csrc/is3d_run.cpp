@@ -7,7 +7,8 @@
 //   deltaf_coefficients/vah/c{0..4}_vah1.dat (mode 2); tables/gla_roots_weights_32_points.txt (df_mode 3 / 4, operation 2); its own averages file.
 // Writes: average_thermodynamic_quantities.dat (not in mode 2); input/surface.dat.is3dcache; in results/, which must exist -- operation 1:
 //   dN_pTdpTdphidy*.dat, dN_dpTdphidy.dat, dN_dy_*.dat, vn_continuous/vn_*.dat, *_resonance_decays.dat; operation 0: spacetime_distribution/*.dat;
-//   operation 2: particle_list_osc.dat, particle_list_osc_decayed.dat, or the binned test files (test_sampler = 1); mode 5: S{t,x,y,n}.dat.
+//   operation 2: particle_list_osc.dat, particle_list_osc_decayed.dat, or the binned test files (test_sampler = 1; with test_sampler_decayed = 1
+//   also under results/decayed/); mode 5: S{t,x,y,n}.dat.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -20,6 +21,8 @@
 #include <string>
 #include <thread>
 #include <vector>
+
+#include <sys/stat.h>
 
 #include "../../include/is3d_amd.h"
 #include "errors.h"
@@ -170,7 +173,7 @@ struct MemSurface { const is3d_cells *cells; const double *x, *y; };
 struct RunConfig {
     int operation, mode, hrg_eos, dimension, df_mode, include_baryon, include_bulk, include_shear, include_diff, regulate, outflow;
     // optional keys (absent: 0); an `is set` flag here has passed its checks
-    bool do_decays, decay_sampled, bin_on_device, bin_fused, vah_oversample, vah_bin_on_device, vah_sampler, test_sampler;
+    bool do_decays, decay_sampled, bin_on_device, bin_fused, vah_oversample, vah_bin_on_device, vah_sampler, test_sampler, bin_decayed;
     bool vah;               // mode 2 from files: the anisotropic-hydro surface, tables and routines
     bool feqmod;            // df_mode 3 / 4 of viscous hydro: the modified-equilibrium kernels
     const char *pdg_path;
@@ -193,7 +196,7 @@ static int parse_config(const RunParams &p, const MemSurface *mem, bool wants_re
     const auto is_set = [&p](const char *name) { double key = 0.0; return p.optional(name, &key) && (int)key != 0; };
     c.do_decays = is_set("do_resonance_decays"); c.decay_sampled = is_set("decay_sampled_hadrons"); c.bin_on_device = is_set("test_sampler_on_device");
     c.bin_fused = is_set("test_sampler_fused"); c.vah_sampler = is_set("vah_sampler"); c.vah_oversample = is_set("vah_oversample");
-    c.vah_bin_on_device = is_set("vah_sampler_on_device");
+    c.vah_bin_on_device = is_set("vah_sampler_on_device"); c.bin_decayed = is_set("test_sampler_decayed");
     // test_sampler is a sampler key: optional where a check only looks at it, required (with the missing-key message) where a key depends on it
     const bool has_test_sampler = p.optional("test_sampler", &v);
     c.test_sampler = has_test_sampler && (int)v != 0;
@@ -298,6 +301,27 @@ static int parse_config(const RunParams &p, const MemSurface *mem, bool wants_re
         if (dir.back() != '/') dir += '/';
         c.df_dir = dir;
         printf("df coefficient tables from %s (deltaf_dir)\n", c.df_dir.c_str());
+    }
+    // test_sampler_decayed = 1: beside the thermal distributions of a test_sampler_on_device run, those of the hadrons after their Monte Carlo
+    // decays, binned on the device batch by batch (is3d_sample_decayed_binned).  Behind every other check: no earlier message or order changes.
+    if (c.bin_decayed) {
+        if (operation != 2)
+            DIE("test_sampler_decayed = 1 with operation = %d: it decays and bins the sampler's hadrons (operation = 2); set test_sampler_decayed = 0", operation);
+        if (need_test_sampler()) return IS3D_EINVAL;
+        if (!c.test_sampler)
+            DIE("test_sampler_decayed = 1 with test_sampler = 0: it writes the test_sampler distributions of the decayed hadrons beside the thermal ones; set test_sampler_decayed = 0");
+        if (vah)
+            DIE("test_sampler_decayed = 1 with mode = 2: it decays the viscous-hydro sampler's hadrons; the anisotropic-hydro sampler has no such entry; set test_sampler_decayed = 0");
+        if (wants_result)
+            DIE("test_sampler_decayed = 1: the embedding entry returns the particle list, which this path never holds; set test_sampler_decayed = 0");
+        if (!c.bin_on_device)
+            DIE("test_sampler_decayed = 1 with test_sampler_on_device = 0: the hadrons are decayed where each event batch is binned, on the device "
+                "(test_sampler_on_device = 1); set test_sampler_decayed = 0");
+        if (c.bin_fused)
+            DIE("test_sampler_decayed = 1 with test_sampler_fused = 1: the fused pass never holds the batch of hadrons that is decayed; set test_sampler_decayed = 0");
+        if (hrg_eos != 1 && hrg_eos != 2)
+            DIE("test_sampler_decayed = 1 with hrg_eos = %d: PDG/pdg_box.dat carries no decay data (smash box: no decay info, iS3D_parameters.dat); use hrg_eos = 1 or 2, "
+                "or set test_sampler_decayed = 0", hrg_eos);
     }
     return IS3D_OK;
 }
@@ -710,12 +734,70 @@ static int decay_sampled_list(const RunConfig &cfg, const RunInputs &in, const R
     return IS3D_OK;
 }
 
+// test_sampler_decayed = 1: the run of test_sampler_on_device on the first device of the run's list, every event batch binned as there and then
+// decayed and binned again (is3d_sample_decayed_binned); results/ as without the key, results/decayed/ the same files for the chosen species
+// that are stable in the decay table, in chosen order
+static int run_sampler_decayed_binned(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, SamplerRun &s)
+{
+    static const char *const subdirs[5] = {"dN_dy", "dN_deta", "momentum_distribution", "vn", "spacetime_distribution"};
+    for (const char *d : subdirs) {
+        const std::string path = std::string("results/decayed/") + d;
+        struct stat sb;
+        if (stat(path.c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode))
+            DIE("test_sampler_decayed = 1: the directory %s is missing (results/decayed/ needs the five directories of results/); create it or set test_sampler_decayed = 0",
+                path.c_str());
+    }
+    DecayTable tab;
+    if (int rc = read_decay_table(cfg.pdg_path, tab)) return rc;
+    std::vector<int32_t> slot((size_t)tab.view.n, -1);
+    std::vector<int64_t> slot_id;
+    for (int ip = 0; ip < in.sp.n; ip++)
+        for (int32_t e = 0; e < tab.view.n; e++)
+            if (tab.id[(size_t)e] == in.mcid[(size_t)ip]) {          // first match, as the library's chosen -> entry map
+                if (tab.stable[(size_t)e] && slot[(size_t)e] < 0) { slot[(size_t)e] = (int32_t)slot_id.size(); slot_id.push_back(tab.id[(size_t)e]); }
+                break;
+            }
+    if (slot_id.empty())
+        DIE("test_sampler_decayed = 1: no chosen particle is stable in %s, so nothing would be binned; set test_sampler_decayed = 0", cfg.pdg_path);
+    const is3d_sampler_test_bins &bins = s.bins;
+    const auto sizes = [&bins](size_t S) {
+        return std::vector<size_t>{S * bins.y_bins, S * bins.eta_bins, S * bins.pT_bins, S * bins.tau_bins, S * bins.r_bins,
+                                   (size_t)IS3D_SAMPLER_VN_HARMONICS * S * bins.pT_bins, (size_t)IS3D_SAMPLER_VN_HARMONICS * S * bins.pT_bins};
+    };
+    std::vector<std::vector<int64_t>> ht, hd;
+    for (size_t n : sizes((size_t)in.sp.n)) ht.emplace_back(n);
+    for (size_t n : sizes(slot_id.size())) hd.emplace_back(n);
+    std::vector<int64_t> yt((size_t)s.si.n_events), yd((size_t)s.si.n_events);
+    const is3d_sampler_hist hist{ht[0].data(), ht[1].data(), ht[2].data(), ht[3].data(), ht[4].data(), ht[5].data(), ht[6].data(), yt.data()};
+    const is3d_sampler_hist hist_d{hd[0].data(), hd[1].data(), hd[2].data(), hd[3].data(), hd[4].data(), hd[5].data(), hd[6].data(), yd.data()};
+    is3d_sampler_stats ss{};
+    is3d_decay_mc_stats ms{};
+    int64_t count = 0, n_final = 0, n_unbinned = 0;
+    is3d_options opts = in.opts;
+    opts.device = rd.first();
+    const int rcb = is3d_sample_decayed_binned(&in.cells, &in.sp, &in.df, &s.si, &opts, &bins, &hist, &tab.view, in.mcid.data(), slot.data(),
+                                               (int32_t)slot_id.size(), s.si.seed, 0, &hist_d, &count, &n_final, &n_unbinned, &ss, &ms);
+    if (rcb) DIE("is3d_sample_decayed_binned failed (%d): %s", rcb, is3d_last_error());
+    const double t_sampled = now_s();
+    print_sampling_efficiency(cfg, ss);
+    printf("Writing the binned sampler test distributions...\n");
+    if (is3d_write_sampler_tests_binned("results", &bins, s.si.n_events, in.sp.n, in.mcid.data(), &hist, s.mean_yield)) DIE("%s", is3d_last_error());
+    printf("Writing the binned sampler test distributions of the decayed hadrons (%d species)...\n", (int)slot_id.size());
+    if (is3d_write_sampler_tests_binned("results/decayed", &bins, s.si.n_events, (int32_t)slot_id.size(), slot_id.data(), &hist_d, s.mean_yield))
+        DIE("%s", is3d_last_error());
+    printf("decayed and binned on the device: n_final %lld, n_unbinned %lld, n_decays %lld, n_stuck %lld, n_exhausted %lld, ms_bin %.3f ms\n",
+           (long long)n_final, (long long)n_unbinned, (long long)ms.n_decays, (long long)ms.n_stuck, (long long)ms.n_exhausted, ms.ms_bin);
+    print_sampler_summary(cfg, in, s, ss, count, t_sampled, now_s());
+    return IS3D_OK;
+}
+
 // ---- operation 2 (emissionfunction.cpp:1522-1554): number of events, sampling, the OSCAR list or the binned test distributions ----
 static int run_sampler(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, RunParams &params, is3d_run_result *res)
 {
     SamplerRun s;
     if (int rc = setup_sampler(cfg, in, params, s)) return rc;
     if (int rc = size_sampler_run(cfg, in, s)) return rc;
+    if (cfg.bin_decayed) return run_sampler_decayed_binned(cfg, in, rd, s);
     if (cfg.bin_on_device || cfg.vah_bin_on_device || cfg.bin_fused) return run_sampler_binned(cfg, in, rd, s);
     // count, then fill a list of that size: the viscous-hydro sampler, or (mode 2) the anisotropic-hydro one on the mode-2 cells and tables
     is3d_sampler_stats ss{};
