@@ -1193,6 +1193,117 @@ int is3d_sample_decayed_binned(const is3d_cells *cells, const is3d_species *spec
                                uint64_t decay_seed, int32_t lifetime, const is3d_sampler_hist *hist_decayed, int64_t *n_particles,
                                int64_t *n_final, int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats);
 
+/* Per-event flow vectors and cumulants of a particle list: what varies from event to event and what correlates the
+ * particles of one event, which no event-averaged histogram above holds.  Per (event, slot) a record keeps the multiplicity M and the flow
+ * vectors Q_n = sum e^{i n phi}, n = 1 .. IS3D_FLOW_HARMONICS, in three regions: 0 the full acceptance, 1 sub-event A, 2 sub-event B.
+ * The rule for one particle (csrc/cf_sampler_flow.h, shared by host and device), with ratio = (E + pz) / (E - pz) = e^{2y}:
+ *   accepted   E - pz > 0, exp(-2 y_cut) <= ratio <= exp(2 y_cut) and pT_min <= pT < pT_max, pT = sqrt(px^2 + py^2)
+ *   A          accepted and ratio < exp(-y_gap)   (y < -y_gap / 2)
+ *   B          accepted and ratio > exp(y_gap)    (y > +y_gap / 2): A and B are y_gap apart in rapidity
+ * An accepted particle adds to region 0; one in A or B adds to that region as well.  What it adds: 1 to M, and llrint(cos(n phi) 2^32),
+ * llrint(sin(n phi) 2^32) with phi = atan2(py, px) to Q_re, Q_im -- the fixed point of vn_re / vn_im (IS3D_SAMPLER_VN_SCALE), so every
+ * word is an integer sum: independent of the order of arrival, the kernel form, the launch geometry and the pieces a list is processed in,
+ * bit for bit (records of pieces add).  No region decision goes through log or atan2: host and device agree on M exactly; a Q word of the
+ * device differs from the host's by at most M units (device and host libm).  Eight harmonics serve the two-particle cumulants for n <= 8
+ * and the four-particle ones for n <= 4.  Cuts are valid when y_cut > 0, 0 <= y_gap < 2 y_cut and pT_max > pT_min >= 0.
+ * Records (caller-owned): M [n_events][n_slots][3], Q_re and Q_im [n_events][n_slots][3][8].  M above IS3D_SAMPLER_VN_MAX_COUNT in any
+ * record: IS3D_EDOMAIN from the device entry after the run. */
+#define IS3D_FLOW_HARMONICS 8
+typedef struct {
+    double y_cut, y_gap, pT_min, pT_max;
+    int32_t kernel_form;                /* tuning, device entries only: 0 = the measured choice, 1 = global atomics after a per-wave combine,
+                                           2 = a workgroup-private window of events in LDS (IS3D_EINVAL when the records of one event,
+                                           n_slots * 51 words, do not fit 64 KiB).  The records do not depend on it. */
+} is3d_flow_cuts;
+typedef struct {
+    int64_t *M, *Q_re, *Q_im;
+} is3d_flow_records;
+/* list -> records on the host: THE definition, no device use.  slot: int32[n_species], species -> slot in [0, n_slots), or -1: dropped.
+ * A particle whose species is outside [0, n_species) or whose event is outside [0, n_events) is refused (IS3D_EINVAL), as a NULL, n_events
+ * or n_slots < 1, bad cuts, a slot outside [-1, n_slots) and kernel_form outside 0..2 are.  records is overwritten. */
+int is3d_flow_list(const is3d_flow_cuts *cuts, int32_t n_events, int32_t n_slots, const int32_t *slot, int32_t n_species,
+                   int64_t n_particles, const is3d_particle *particles, const is3d_flow_records *records);
+/* list -> records on the DEVICE: a caller's HOST list (any order, any length) is uploaded and passed through cf_sampler_flow in the form
+ * cuts->kernel_form.  A particle whose species or event is out of range adds nothing and is counted in *n_skipped.  The refusals above
+ * and kernel_form = 2 on records that do not fit come before any device use; a good call without a device is IS3D_ENODEVICE.
+ * n_particles = 0: zero records, no launch.  device < 0: the current device. */
+int is3d_flow_list_device(const is3d_flow_cuts *cuts, int32_t n_events, int32_t n_slots, const int32_t *slot, int32_t n_species,
+                          int64_t n_particles, const is3d_particle *particles, const is3d_flow_records *records, int64_t *n_skipped,
+                          int32_t device);
+/* Integer sums of slots: out (n_groups slots) receives, per event and region, the sums of the records whose slot s has group[s] = g
+ * (group: int32[n_slots], -1: left out).  M and Q are additive, so "all hadrons" is the merge of the identified slots. */
+int is3d_flow_merge(const is3d_flow_records *records, int32_t n_events, int32_t n_slots, const int32_t *group, int32_t n_groups,
+                    const is3d_flow_records *out);
+/* Q-cumulants (Bilandzic, Snellings, Voloshin, Phys. Rev. C 83, 044913) per slot from region 0 and the sub-events, n = 1..8 (index n - 1),
+ * with Q = Q_n / 2^32, all in double from the exact integers, events in order -- deterministic on the host:
+ *   <2>     = (|Q_n|^2 - M) / (M (M - 1)),                                                            event weight M (M - 1)
+ *   <4>     = [|Q_n|^4 + |Q_2n|^2 - 2 Re(Q_2n Q_n*^2) - 4 (M - 2) |Q_n|^2 + 2 M (M - 3)] / W4,  n <= 4,   W4 = M (M - 1)(M - 2)(M - 3)
+ *   <2>_gap = Re(Q_n^A Q_n^B*) / (M_A M_B),                                                           event weight M_A M_B
+ * An event whose weight for a quantity is zero is left out of it; n_used_* count the events that were not.  <<.>> is the weighted event
+ * average (0 when no event was used).
+ *   c2 = <<2>>, avg4 = <<4>>, c4 = <<4>> - 2 <<2>>^2, c2_gap = <<2>_gap>
+ *   v2 = sgn(c2) |c2|^(1/2), v4 = sgn(-c4) |c4|^(1/4), v2_gap = sgn(c2_gap) |c2_gap|^(1/2)
+ *   v_rp = sum Re Q_n / sum M: the flow about the fixed reaction plane (0 when sum M = 0)
+ *   mean_M, var_M: mean and population variance of M over all n_events events */
+typedef struct {
+    double c2[IS3D_FLOW_HARMONICS], c2_gap[IS3D_FLOW_HARMONICS], v2[IS3D_FLOW_HARMONICS], v2_gap[IS3D_FLOW_HARMONICS], v_rp[IS3D_FLOW_HARMONICS];
+    double avg4[4], c4[4], v4[4];
+    double mean_M, var_M;
+    int64_t n_used_2, n_used_4, n_used_gap, n_events;
+} is3d_flow_result;
+int is3d_flow_cumulants(const is3d_flow_records *records, int32_t n_events, int32_t n_slots, is3d_flow_result *out /* [n_slots] */);
+/* Writes, per slot s, <results_dir>/flow/cumulants_<labels[s]>.dat (two comment lines, then a row per n = 1..8: n, c_n{2}, c_n{4}, c_n{2,gap},
+ * v_n{2}, v_n{4}, v_n{2,gap}, reaction-plane v_n, tab separated; the four-particle columns are 0 for n > 4) and
+ * <results_dir>/flow/multiplicity_<labels[s]>.dat (two comment lines, the first with the mean and the variance of M, then a row per event: event, M, M_A, M_B).  Doubles are printed by
+ * std::to_chars(scientific, 8) as the other writers' values.  The flow/ directory must exist (IS3D_EIO otherwise); a NULL, an empty label or
+ * one with a '/', n_events < 1 and n_slots < 1 are IS3D_EINVAL. */
+int is3d_write_flow(const char *results_dir, const is3d_flow_records *records, int32_t n_events, int32_t n_slots, const char *const *labels);
+/* The flow records of a list AFTER its Monte Carlo decays, without the decayed list: the one-pass analogue of is3d_decay_particles_binned.
+ * Definition: the records are those of is3d_flow_list(cuts, n_events, n_slots, slot, table->n, ...) on the list that is3d_decay_particles
+ * returns for the same (table, chosen_mc_id, in, particles), whose species are TABLE entries -- M exactly, every Q word within M units
+ * (device and host libm).  *n_final is the length of that list, *n_unbinned = *n_final - sum of M over region 0: the final particles that
+ * added to no record (slot -1, or outside the cuts).  How: cf_decay_mc_flow, thread <-> primary over the decay loop and stream of
+ * is3d_decay_particles (Rng(seed, 5, first_particle + i)); every final particle's momentum is built in registers and goes to the rule of
+ * csrc/cf_sampler_flow.h at once.  A primary's products share its event, so the workgroup-private form keeps a window of events in LDS
+ * along the primaries' order (kernel_form as for is3d_flow_list_device, the window beside six tally words).  The records do not depend on
+ * kernel_form, on the launch geometry or on the pieces a list is decayed in (first_particle; records added by the caller), bit for bit.
+ * slot: int32[table->n].  All pointers HOST memory; records is overwritten.  stats as for is3d_decay_particles_binned (ms_bin: the pass).
+ * IS3D_EINVAL before any device use: every refusal of is3d_decay_particles; the refusals of is3d_flow_list_device with the table's entries as
+ * species; a primary whose event is outside [0, n_events).  n_particles = 0: zero records, no launch.  M above IS3D_SAMPLER_VN_MAX_COUNT:
+ * IS3D_EDOMAIN.  A good call without a device: IS3D_ENODEVICE. */
+int is3d_decay_particles_flow(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
+                              const is3d_decay_mc_inputs *in, int64_t n_particles, const is3d_particle *particles,
+                              const int32_t *slot, int32_t n_slots, const is3d_flow_cuts *cuts, int32_t n_events,
+                              const is3d_flow_records *records, int64_t *n_final, int64_t *n_unbinned,
+                              is3d_decay_mc_stats *stats /* may be NULL */);
+
+/* is3d_sampler_plan_execute with the list of each event batch turned into flow records on the device and discarded: fill into the plan's
+ * particle workspace, cf_sampler_flow into device-resident records (slot: int32 per species of the plan) and, with table_dev != NULL,
+ * cf_decay_mc_flow of the same batch with first_particle = the number of hadrons of the batches before it (slot_decayed: int32 per table
+ * entry), exactly as is3d_sampler_plan_execute_decayed_binned does; one copy of each block to the caller's HOST arrays after the last batch.
+ *   records          = is3d_flow_list of the list is3d_sampler_plan_execute returns for the same arguments
+ *   records_decayed  = is3d_decay_particles_flow of that list with first_particle = 0, seed = decay_seed
+ * (M exactly, Q within M units), independent of batch_events, kernel_form and launch geometry, bit for bit.  The plan keeps the record
+ * blocks and slot maps (sized at first use) and serves its other entries in any order, as before.  table_dev == NULL: slot_decayed,
+ * records_decayed, n_final, n_unbinned and decay_stats are not used.  *n_particles: thermal hadrons; *n_final, *n_unbinned, decay_stats as
+ * for is3d_decay_particles_flow.  IS3D_EINVAL before any device use: the refusals of is3d_flow_list_device for either set of records, a
+ * table of another chosen count or device.  Not offered: the fused sample-and-bin pass, the anisotropic-hydro sampler, several devices
+ * (thermal records of cell shards may be added by the caller; decayed ones may not, since first_particle depends on the shards before). */
+int is3d_sampler_plan_execute_flow(is3d_sampler_plan *plan, const is3d_cells *cells_dev, const double *x_dev, const double *y_dev,
+                                   int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events, const is3d_flow_cuts *cuts,
+                                   const int32_t *slot, int32_t n_slots, const is3d_flow_records *records_host,
+                                   const is3d_decay_mc_table *table_dev /* may be NULL */, const int32_t *slot_decayed, int32_t n_slots_decayed,
+                                   uint64_t decay_seed, int32_t lifetime, const is3d_flow_records *records_decayed, int64_t *n_particles,
+                                   int64_t *n_final, int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats);
+/* host-pointer one-shot for the viscous sampler: plan and table create, upload, execute, destroy.  table may be NULL; otherwise chosen_mc_id
+ * holds the mc_id of species[0 .. n), which the table must hold.  The cuts' and the table's refusals come first, then the plan's. */
+int is3d_sample_flow(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                     const is3d_options *opts, const is3d_flow_cuts *cuts, const int32_t *slot, int32_t n_slots,
+                     const is3d_flow_records *records, const is3d_decay_table *table /* may be NULL */, const int64_t *chosen_mc_id,
+                     const int32_t *slot_decayed, int32_t n_slots_decayed, uint64_t decay_seed, int32_t lifetime,
+                     const is3d_flow_records *records_decayed, int64_t *n_particles, int64_t *n_final, int64_t *n_unbinned,
+                     is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats);
+
 /* ---------------------------------------------------------------------------------------------
  * Driver: IS3D::run_particlization (src/cpp/iS3D.cpp:74-192; class IS3D, src/cpp/iS3D.h:19-96).  Reads iS3D_parameters.dat,
  * PDG/, tables/, deltaf_coefficients/ from the current directory and writes results/ exactly as the command line tool does

@@ -122,6 +122,8 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_sampler_bin_list", "is3d_write_sampler_tests_binned", "is3d_sampler_plan_execute_binned", "is3d_sample_binned", "is3d_sample_binned_multi",
            "is3d_sampler_plan_execute_fused", "is3d_sample_fused", "is3d_sample_fused_multi",
            "is3d_sampler_bin_list_device", "is3d_df_generate", "is3d_df_tables_write",
+           "is3d_flow_list", "is3d_flow_list_device", "is3d_flow_merge", "is3d_flow_cumulants", "is3d_decay_particles_flow",
+           "is3d_sampler_plan_execute_flow", "is3d_sample_flow", "is3d_write_flow",
            "is3d_smooth_spectra_vah_multi", "is3d_vah_plan_observables",
            "is3d_spacetime_distributions_vah", "is3d_vah_plan_execute_spacetime",
            "is3d_sample_particles_vah", "is3d_sample_particles_vah_multi", "is3d_sample_binned_vah", "is3d_sample_binned_vah_multi",
@@ -1166,6 +1168,27 @@ def decay_particles_binned(table, chosen_mc_id, particles, slot, n_slots, bins, 
     return out, _check_decayed(rc, st, nf, nu, hist=out)
 
 
+def decay_particles_flow(table, chosen_mc_id, particles, slot, n_slots, cuts, n_events, seed=1, first_particle=0, lifetime=0, device=-1):
+    """is3d_decay_particles_flow: a sampled list decayed on the device with every final particle added to the per-event flow records at
+    once -- the records of flow_list on decay_particles' list (species = table entries) with the same slot map.  slot: int32 per table
+    entry.  Returns (records dict, stats dict with n_final, n_unbinned and the tallies of decay_particles)."""
+    L = load()
+    ts, ch, _, keep = _decay_pack(table, chosen_mc_id, dict(pT=[1.0], phi=[0.0], y=[0.0]))
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    slot = _slot_map(table, slot)
+    inp = DecayMcInputs(int(seed), int(first_particle), int(lifetime), int(device))
+    c = _pack_cuts(cuts)
+    r, out = _flow_arrays(n_events, n_slots)
+    st, nf, nu = DecayMcStats(), C.c_int64(0), C.c_int64(0)
+    L.is3d_decay_particles_flow.argtypes = [C.POINTER(DecayTable), C.c_int32, C.POINTER(C.c_int64), C.POINTER(DecayMcInputs), C.c_int64, C.c_void_p,
+                                            C.c_void_p, C.c_int32, C.POINTER(FlowCuts), C.c_int32, C.POINTER(FlowRecords),
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(DecayMcStats)]
+    rc = L.is3d_decay_particles_flow(C.byref(ts), len(ch), ch.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(inp), len(particles),
+                                     particles.ctypes.data, slot.ctypes.data, int(n_slots), C.byref(c), int(n_events), C.byref(r), C.byref(nf),
+                                     C.byref(nu), C.byref(st))
+    return out, _check_decayed(rc, st, nf, nu, records=out)
+
+
 def shard_bounds(n_cells, rank, n_ranks):
     """is3d_shard_bounds: the contiguous cell shard [lo, hi) of `rank` (what is3d_smooth_spectra_multi uses)."""
     lo, hi = C.c_int64(), C.c_int64()
@@ -1867,6 +1890,39 @@ class SamplerPlan:
         dd = _check_decayed(rc, dst, nf, nu, hist=out, hist_decayed=outd, sampler_stats=d)
         return out, outd, d, dd
 
+    def execute_flow(self, n_cells, dev_ptrs, n_events, seed, cuts, slot, n_slots, table=None, slot_decayed=None, n_slots_decayed=0,
+                     decay_seed=None, lifetime=0, x_ptr=0, y_ptr=0, first_cell=0, batch_events=0):
+        """is3d_sampler_plan_execute_flow: the per-event flow records of the list execute returns (slot: int32 per species of the plan) and,
+        with table (a DecayMcTable on the plan's device), of its Monte Carlo decay products (slot_decayed: int32 per table entry).
+        -> (records, sampler stats) | (records, decayed records, sampler stats, decay stats with n_final and n_unbinned)."""
+        cs = Cells()
+        cs.n_cells = int(n_cells)
+        for f in CELL_FIELDS:
+            if dev_ptrs.get(f):
+                setattr(cs, f, int(dev_ptrs[f]))
+        c = _pack_cuts(cuts)
+        slot = np.ascontiguousarray(slot, dtype=np.int32)
+        r, out = _flow_arrays(n_events, n_slots)
+        rd, outd = _flow_arrays(n_events, n_slots_decayed if table is not None else 0)
+        sd = _slot_map(table.table, slot_decayed) if table is not None else None
+        cnt, st, dst, nf, nu = C.c_int64(0), SamplerStats(), DecayMcStats(), C.c_int64(0), C.c_int64(0)
+        fn = load().is3d_sampler_plan_execute_flow
+        fn.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(FlowCuts),
+                       C.c_void_p, C.c_int32, C.POINTER(FlowRecords), C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int32,
+                       C.POINTER(FlowRecords), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(SamplerStats),
+                       C.POINTER(DecayMcStats)]
+        rc = fn(self._h, C.byref(cs), C.c_void_p(int(x_ptr) or None), C.c_void_p(int(y_ptr) or None), int(n_events), int(seed), int(first_cell),
+                int(batch_events), C.byref(c), slot.ctypes.data, int(n_slots), C.byref(r), table._h if table is not None else None,
+                sd.ctypes.data if sd is not None else None, int(n_slots_decayed), int(seed if decay_seed is None else decay_seed), int(lifetime),
+                C.byref(rd) if table is not None else None, C.byref(cnt), C.byref(nf), C.byref(nu), C.byref(st), C.byref(dst))
+        d = st.as_dict()
+        d["n_particles"] = int(cnt.value)
+        if table is None:
+            _check(rc)
+            return out, d
+        dd = _check_decayed(rc, dst, nf, nu, records=out, records_decayed=outd, sampler_stats=d)
+        return out, outd, d, dd
+
     def execute_fused(self, n_cells, dev_ptrs, n_events, seed, bins, n_species, x_ptr=0, y_ptr=0, first_cell=0, batch_events=0):
         """is3d_sampler_plan_execute_fused: execute_binned's arguments and result, every hadron binned where it is sampled (no list, no
         particle workspace: stats["particle_workspace_bytes"] == 0)."""
@@ -2060,6 +2116,112 @@ def sampler_bin_list_device(bins, n_events, n_species, particles, device=0):
     return out, int(skipped.value)
 
 
+FLOW_HARMONICS = 8        # IS3D_FLOW_HARMONICS
+FLOW_CUTS = dict(y_cut=1.0, y_gap=0.5, pT_min=0.2, pT_max=3.0)   # the run driver's defaults
+
+
+class FlowCuts(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ["y_cut", "y_gap", "pT_min", "pT_max"]] + [("kernel_form", C.c_int32)]
+
+
+class FlowRecords(C.Structure):
+    _fields_ = [(n, C.POINTER(C.c_int64)) for n in ["M", "Q_re", "Q_im"]]
+
+
+class FlowResult(C.Structure):
+    _fields_ = [(n, C.c_double * FLOW_HARMONICS) for n in ["c2", "c2_gap", "v2", "v2_gap", "v_rp"]] + \
+               [(n, C.c_double * 4) for n in ["avg4", "c4", "v4"]] + [("mean_M", C.c_double), ("var_M", C.c_double)] + \
+               [(n, C.c_int64) for n in ["n_used_2", "n_used_4", "n_used_gap", "n_events"]]
+
+
+def _pack_cuts(cuts):
+    c = FlowCuts()
+    for k, v in cuts.items():
+        setattr(c, k, v)
+    return c
+
+
+def _flow_arrays(n_events, n_slots, records=None):
+    """is3d_flow_records over numpy int64 arrays: (struct, dict).  records = None: fresh zero arrays M [event][slot][3], Q_re / Q_im
+    [event][slot][3][8] (region 0 full acceptance, 1 sub-event A, 2 sub-event B); otherwise the caller's arrays are checked and used."""
+    E, S = max(int(n_events), 0), max(int(n_slots), 0)
+    shapes = dict(M=(E, S, 3), Q_re=(E, S, 3, FLOW_HARMONICS), Q_im=(E, S, 3, FLOW_HARMONICS))
+    out = {}
+    for k, shp in shapes.items():
+        if records is None:
+            out[k] = np.zeros(shp, dtype=np.int64)
+        else:
+            out[k] = np.ascontiguousarray(records[k], dtype=np.int64)
+            assert out[k].shape == shp, (k, out[k].shape, shp)
+    r = FlowRecords(*[out[k].ctypes.data_as(C.POINTER(C.c_int64)) for k, _ in FlowRecords._fields_])
+    return r, out
+
+
+def flow_list(cuts, n_events, n_slots, slot, particles):
+    """is3d_flow_list: a particle list -> the per-event flow records on the host (the definition; no device use).  slot: int32 per species,
+    -1 drops the species.  Returns a dict of int64 arrays M, Q_re, Q_im."""
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    slot = np.ascontiguousarray(slot, dtype=np.int32)
+    c = _pack_cuts(cuts)
+    r, out = _flow_arrays(n_events, n_slots)
+    L = load()
+    L.is3d_flow_list.argtypes = [C.POINTER(FlowCuts), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(FlowRecords)]
+    _check(L.is3d_flow_list(C.byref(c), int(n_events), int(n_slots), slot.ctypes.data, len(slot), len(particles), particles.ctypes.data, C.byref(r)))
+    return out
+
+
+def flow_list_device(cuts, n_events, n_slots, slot, particles, device=0):
+    """is3d_flow_list_device: a host particle list through the device kernel cf_sampler_flow (form cuts["kernel_form"]).  Returns (records,
+    n_skipped); n_skipped counts the particles whose species or event is out of range, which add nothing."""
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    slot = np.ascontiguousarray(slot, dtype=np.int32)
+    c = _pack_cuts(cuts)
+    r, out = _flow_arrays(n_events, n_slots)
+    skipped = C.c_int64(0)
+    L = load()
+    L.is3d_flow_list_device.argtypes = [C.POINTER(FlowCuts), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(FlowRecords),
+                                        C.POINTER(C.c_int64), C.c_int32]
+    _check(L.is3d_flow_list_device(C.byref(c), int(n_events), int(n_slots), slot.ctypes.data, len(slot), len(particles), particles.ctypes.data,
+                                   C.byref(r), C.byref(skipped), int(device)))
+    return out, int(skipped.value)
+
+
+def flow_merge(records, group, n_groups):
+    """is3d_flow_merge: the integer sums of the slots s with group[s] = g, per event and region (group -1: left out)."""
+    group = np.ascontiguousarray(group, dtype=np.int32)
+    n_events, n_slots = np.shape(records["M"])[:2]
+    r, _keep = _flow_arrays(n_events, n_slots, records)
+    o, out = _flow_arrays(n_events, n_groups)
+    L = load()
+    L.is3d_flow_merge.argtypes = [C.POINTER(FlowRecords), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(FlowRecords)]
+    assert len(group) == n_slots, (len(group), n_slots)
+    _check(L.is3d_flow_merge(C.byref(r), n_events, n_slots, group.ctypes.data, int(n_groups), C.byref(o)))
+    return out
+
+
+def flow_cumulants(records):
+    """is3d_flow_cumulants: the Q-cumulants of every slot.  Returns a dict of arrays with the slot as first axis: c2, c2_gap, v2, v2_gap,
+    v_rp [slot][8]; avg4, c4, v4 [slot][4]; mean_M, var_M, n_used_2, n_used_4, n_used_gap, n_events [slot]."""
+    n_events, n_slots = np.shape(records["M"])[:2]
+    r, _keep = _flow_arrays(n_events, n_slots, records)
+    res = (FlowResult * max(n_slots, 1))()
+    L = load()
+    L.is3d_flow_cumulants.argtypes = [C.POINTER(FlowRecords), C.c_int32, C.c_int32, C.POINTER(FlowResult)]
+    _check(L.is3d_flow_cumulants(C.byref(r), n_events, n_slots, res))
+    return {k: np.array([np.array(getattr(res[s], k)) for s in range(n_slots)]) for k, _ in FlowResult._fields_}
+
+
+def write_flow(results_dir, records, labels):
+    """is3d_write_flow: <results_dir>/flow/cumulants_<label>.dat and multiplicity_<label>.dat for every slot of the records."""
+    n_events, n_slots = np.shape(records["M"])[:2]
+    assert len(labels) == n_slots, (len(labels), n_slots)
+    r, _keep = _flow_arrays(n_events, n_slots, records)
+    names = (C.c_char_p * n_slots)(*[str(x).encode() for x in labels])
+    L = load()
+    L.is3d_write_flow.argtypes = [C.c_char_p, C.POINTER(FlowRecords), C.c_int32, C.c_int32, C.POINTER(C.c_char_p)]
+    _check(L.is3d_write_flow(results_dir.encode(), C.byref(r), n_events, n_slots, names))
+
+
 def write_sampler_tests_binned(results_dir, bins, n_events, mc_id, hist, mean_yield=0.0):
     """is3d_write_sampler_tests_binned: the test_sampler = 1 files from a dict of int64 histograms."""
     ids = np.ascontiguousarray(mc_id, dtype=np.int64)
@@ -2107,6 +2269,43 @@ def sample_decayed_binned(cells, species, df, gla, bins, table, chosen_mc_id, sl
     d = st.as_dict()
     d["n_particles"] = int(cnt.value)
     dd = _check_decayed(rc, dst, nf, nu, hist=out, hist_decayed=outd, sampler_stats=d)
+    return out, outd, d, dd
+
+
+def sample_flow(cells, species, df, gla, cuts, slot, n_slots, opts=None, table=None, chosen_mc_id=None, slot_decayed=None, n_slots_decayed=0,
+                n_events=1, seed=1, decay_seed=None, lifetime=0, y_cut=0.5, first_cell=0, fq=None, fast=0, T_avg=0.0, T_avg_switch=0.0,
+                batch_events=0, muB_avg=0.0):
+    """is3d_sample_flow: the viscous sampler with every event batch turned into per-event flow records on the device (slot: int32 per
+    species) and, with table (pdg_read_decays' dict; chosen_mc_id: the mc_id of the species list), decayed and recorded again by
+    slot_decayed (int32 per table entry).  Returns (records, sampler stats) | (records, decayed records, sampler stats, decay stats)."""
+    cs, sps, ds, si, os_, _held = _pack_sampler(cells, species, df, gla, opts, n_events, seed, y_cut, first_cell, fq, fast, T_avg, T_avg_switch,
+                                                batch_events, muB_avg)
+    c = _pack_cuts(cuts)
+    slot = np.ascontiguousarray(slot, dtype=np.int32)
+    assert len(slot) == sps.n, (len(slot), sps.n)
+    r, out = _flow_arrays(n_events, n_slots)
+    rd, outd = _flow_arrays(n_events, n_slots_decayed if table is not None else 0)
+    ts = ch = sd = None
+    if table is not None:
+        ts, ch, _, keep = _decay_pack(table, chosen_mc_id, dict(pT=[1.0], phi=[0.0], y=[0.0]))
+        assert len(ch) == sps.n, (len(ch), sps.n)
+        sd = _slot_map(table, slot_decayed)
+    cnt, st, dst, nf, nu = C.c_int64(0), SamplerStats(), DecayMcStats(), C.c_int64(0), C.c_int64(0)
+    fn = load().is3d_sample_flow
+    fn.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options), C.POINTER(FlowCuts),
+                   C.c_void_p, C.c_int32, C.POINTER(FlowRecords), C.POINTER(DecayTable), C.POINTER(C.c_int64), C.c_void_p, C.c_int32, C.c_uint64,
+                   C.c_int32, C.POINTER(FlowRecords), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(SamplerStats),
+                   C.POINTER(DecayMcStats)]
+    rc = fn(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), C.byref(c), slot.ctypes.data, int(n_slots), C.byref(r),
+            C.byref(ts) if ts is not None else None, ch.ctypes.data_as(C.POINTER(C.c_int64)) if ch is not None else None,
+            sd.ctypes.data if sd is not None else None, int(n_slots_decayed), int(seed if decay_seed is None else decay_seed), int(lifetime),
+            C.byref(rd) if table is not None else None, C.byref(cnt), C.byref(nf), C.byref(nu), C.byref(st), C.byref(dst))
+    d = st.as_dict()
+    d["n_particles"] = int(cnt.value)
+    if table is None:
+        _check(rc)
+        return out, d
+    dd = _check_decayed(rc, dst, nf, nu, records=out, records_decayed=outd, sampler_stats=d)
     return out, outd, d, dd
 
 

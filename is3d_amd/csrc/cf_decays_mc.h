@@ -6,6 +6,7 @@
 
 #include "../../include/is3d_amd.h"
 #include "cf_sampler_bins.h"
+#include "cf_sampler_flow.h"
 
 namespace is3d {
 
@@ -40,6 +41,20 @@ int decay_mc_table_device(const is3d_decay_mc_table *t);
 // n primaries of a DEVICE list (species indexing the table's chosen list, ordered by event), primary i drawing from stream first_particle + i,
 // decayed and binned into r.block_dev on the null stream in the form r.bins.kernel_form (0 = private where it fits, 1 = global, 2 = private)
 hipError_t decay_mc_bins_launch(const DecayMcBinRun &r, const is3d_particle *primaries_dev, int64_t n, int64_t first_particle);
+// A decayed run into flow records (cf_sampler_flow.h): the slot map as above, the cuts with their thresholds, and the device block
+// records [n_events * n_slots * 51] | tally [kDecayMcBinTallies].  The private form keeps its window beside the static tally words.
+struct DecayMcFlowRun {
+    const is3d_decay_mc_table *table;
+    const int32_t *slot_dev;
+    int32_t n_slots, n_events;
+    uint64_t seed;
+    int32_t lifetime;
+    is3d_flow_cuts cuts;
+    FlowThresholds thresholds;
+    unsigned long long *block_dev;
+};
+// as decay_mc_bins_launch, every final particle going to the rule of cf_sampler_flow.h; form r.cuts.kernel_form
+hipError_t decay_mc_flow_launch(const DecayMcFlowRun &r, const is3d_particle *primaries_dev, int64_t n, int64_t first_particle);
 // the tallies of a finished run (HOST copy of the tally words) into stats; IS3D_EINVAL if a pending stack overflowed
 int decay_mc_bins_tallies(const unsigned long long *tally, is3d_decay_mc_stats *stats);
 // the static part of the stats: what the table analysis found

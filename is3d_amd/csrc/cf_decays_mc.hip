@@ -310,6 +310,72 @@ __global__ void __launch_bounds__(kBinThreads) cf_decay_mc_bins(const McArgs a, 
         }
 }
 
+// the flow pass: the final particle's momentum, built in registers, goes to the rule of cf_sampler_flow.h with slot[entry]; slot -1, a particle
+// outside the cuts or a primary whose event has no record adds nothing
+struct McFlowArgs {
+    is3d_flow_cuts c;
+    is3d::FlowThresholds t;
+    int32_t n_slots, n_events, window;
+    const int32_t *slot;              // [table entries]
+    unsigned long long *records, *tally;   // tally[kBinTallies]
+};
+template <bool PRIVATE>
+struct SinkFlow {
+    static constexpr bool kMomenta = true;
+    const McFlowArgs &f;
+    const is3d::FlowTarget &target;
+    bool live;
+    __device__ __forceinline__ void operator()(int, const Pending &c, const is3d_particle &q)
+    {
+        const int s = f.slot[c.e];
+        if (!live || s < 0 || s >= f.n_slots) return;
+        is3d_particle o;
+        o.E = c.E; o.px = c.px; o.py = c.py; o.pz = c.pz;
+        const int region = is3d::flow_region(f.c, f.t, o);
+        if (region < 0) return;
+        long long re[IS3D_FLOW_HARMONICS], im[IS3D_FLOW_HARMONICS];
+        is3d::flow_terms(o, re, im);
+        is3d::flow_add_particle<PRIVATE>(target, q.event, s, region, re, im);
+    }
+};
+
+// The one-pass flow kernel.  Every workgroup walks a CONTIGUOUS slice of the primaries in trips of kBinThreads (the same trip count for every
+// thread).  A primary's products share its event and the primaries come ordered by event, so the window of cf_sampler_flow applies to the
+// primaries' order: PRIVATE keeps the records of `window` events from the event of the slice's first primary in LDS (dynamic, beside the
+// static tally words) and flushes the non-zero words once; products of a primary outside the window, and every product of the global form,
+// add to global memory.  The threads of a wave reach their final particles at different times, so there is no per-wave combine here.
+template <bool PRIVATE>
+__global__ void __launch_bounds__(kBinThreads) cf_decay_mc_flow(const McArgs a, const McFlowArgs f, const int64_t slice)
+{
+    extern __shared__ unsigned long long priv[];
+    __shared__ unsigned long long blk[kBinTallies];
+    if (threadIdx.x < kBinTallies) blk[threadIdx.x] = 0ULL;
+    const int64_t begin = (int64_t)blockIdx.x * slice, end = begin + slice < a.n ? begin + slice : a.n;
+    is3d::FlowTarget target{priv, f.records, 0, f.window, f.n_slots, f.n_events};
+    if (PRIVATE)
+        target.base = is3d::flow_window_open<kBinThreads>(priv, (int64_t)f.window * f.n_slots * is3d::kFlowRecordWords, begin, end, [&](int64_t i) {
+            const int e = a.in[i].event;
+            return e >= 0 && e < f.n_events ? e : -1;
+        });
+    else
+        __syncthreads();
+    unsigned long long tally[kTallies] = {0ULL, 0ULL, 0ULL, 0ULL, 0ULL}, finals = 0ULL;
+    for (int64_t i0 = begin; i0 < end; i0 += kBinThreads) {
+        const int64_t i = i0 + threadIdx.x;
+        if (i < end) {
+            const int event = a.in[i].event;
+            SinkFlow<PRIVATE> sink{f, target, event >= 0 && event < f.n_events};
+            finals += (unsigned long long)decay_tree(a, i, tally, sink);
+        }
+    }
+    for (int k = 0; k < kTallies; k++)
+        if (tally[k]) atomicAdd(&blk[k], tally[k]);
+    if (finals) atomicAdd(&blk[kTallies], finals);
+    __syncthreads();
+    if (threadIdx.x < kBinTallies && blk[threadIdx.x]) atomicAdd(&f.tally[threadIdx.x], blk[threadIdx.x]);
+    if (PRIVATE) is3d::flow_window_flush<kBinThreads>(target);
+}
+
 struct Widen {
     __host__ __device__ int64_t operator()(int32_t v) const { return (int64_t)v; }
 };
@@ -750,4 +816,103 @@ extern "C" int is3d_decay_particles_binned(const is3d_decay_table *table, int32_
     if (stats) *stats = st;
     if (rc) return rc;
     return is3d::sampler_hist_check_counts(hist, l);
+}
+
+// ---- decayed into flow records in one pass ----
+hipError_t is3d::decay_mc_flow_launch(const DecayMcFlowRun &r, const is3d_particle *primaries_dev, int64_t n, int64_t first_particle)
+{
+    if (n <= 0) return hipSuccess;
+    const int window = flow_window_events(r.n_events, r.n_slots, kBinTallies);
+    const int form = r.cuts.kernel_form;
+    if (form == 2 && window < 1) return hipErrorInvalidValue;
+    const bool priv = form == 2 || (form == 0 && window >= 1);
+    McArgs a{};
+    a.t = r.table->dev();
+    a.chosen_entry = r.table->d_chosen.p;
+    a.in = primaries_dev;
+    a.n = n;
+    a.first = first_particle;
+    a.seed = r.seed;
+    a.lifetime = r.lifetime;
+    const int64_t words = (int64_t)r.n_events * r.n_slots * kFlowRecordWords;
+    const McFlowArgs f{r.cuts, r.thresholds, r.n_slots, r.n_events, window, r.slot_dev, r.block_dev, r.block_dev + words};
+    const int64_t trips = (n + kBinThreads - 1) / kBinThreads;
+    const int64_t blocks0 = priv ? std::min<int64_t>(trips, kBinPrivateBlocks) : trips;
+    const int64_t slice = ((n + blocks0 - 1) / blocks0 + kBinThreads - 1) / kBinThreads * kBinThreads;
+    const unsigned blocks = (unsigned)((n + slice - 1) / slice);
+    if (priv)
+        hipLaunchKernelGGL(cf_decay_mc_flow<true>, dim3(blocks), dim3(kBinThreads),
+                           (size_t)window * r.n_slots * kFlowRecordWords * sizeof(unsigned long long), nullptr, a, f, slice);
+    else
+        hipLaunchKernelGGL(cf_decay_mc_flow<false>, dim3(blocks), dim3(kBinThreads), 0, nullptr, a, f, slice);
+    return hipGetLastError();
+}
+
+extern "C" int is3d_decay_particles_flow(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
+                                         const is3d_decay_mc_inputs *in, int64_t n_particles, const is3d_particle *particles,
+                                         const int32_t *slot, int32_t n_slots, const is3d_flow_cuts *cuts, int32_t n_events,
+                                         const is3d_flow_records *records, int64_t *n_final, int64_t *n_unbinned, is3d_decay_mc_stats *stats)
+{
+    if (!table || !chosen_mc_id || !in || !n_final || !n_unbinned)
+        return set_error(IS3D_EINVAL, "table, chosen_mc_id, in, n_final and n_unbinned are required");
+    *n_final = *n_unbinned = 0;
+    if (int rc = check_list_head(n_chosen, n_particles, particles)) return rc;
+    is3d_decay_mc_table tb;
+    if (int rc = analyse(*table, n_chosen, chosen_mc_id, tb.H)) return rc;
+    tb.n = table->n;
+    tb.n_chosen = n_chosen;
+    if (int rc = check_list_species(n_chosen, n_particles, particles)) return rc;
+    if (table->n < 1) return set_error(IS3D_EINVAL, "decay table: n = %d", table->n);
+    if (int rc = is3d::flow_check_args(cuts, n_events, n_slots, slot, table->n, records, kBinTallies)) return rc;
+    for (int64_t i = 0; i < n_particles; i++)
+        if (particles[i].event < 0 || particles[i].event >= n_events)
+            return set_error(IS3D_EINVAL, "particle %lld: event %d outside the %d events", (long long)i, particles[i].event, n_events);
+    is3d_decay_mc_stats st{};
+    st.n_primaries = n_particles;
+    is3d::decay_mc_table_stats(&tb, &st);
+    if (n_particles == 0) {
+        is3d::flow_records_zero(records, n_events, n_slots);
+        if (stats) *stats = st;
+        return IS3D_OK;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return no_device();
+    is3d::flow_records_zero(records, n_events, n_slots);
+    if (in->device >= 0) HIP_TRY(hipSetDevice(in->device));
+    // ---- upload: the table, the primaries, the slot map; the block of records and tallies zeroed ----
+    const auto t0 = std::chrono::steady_clock::now();
+    DevBuf<is3d_particle> d_in;
+    DevBuf<int32_t> d_slot;
+    DevBuf<unsigned long long> d_block;
+    const size_t words = (size_t)n_events * n_slots * is3d::kFlowRecordWords;
+    if (int rc = table_upload(tb, *table)) return rc;
+    HIP_TRY(d_in.upload(particles, (size_t)n_particles));
+    HIP_TRY(d_slot.upload(slot, (size_t)table->n));
+    HIP_TRY(d_block.alloc(words + kBinTallies));
+    HIP_TRY(hipMemsetAsync(d_block.p, 0, (words + kBinTallies) * sizeof(unsigned long long), nullptr));
+    Events ev;
+    for (int k = 0; k < 2; k++) HIP_TRY(hipEventCreate(&ev.e[k]));
+    HIP_TRY(hipDeviceSynchronize());
+    const auto t1 = std::chrono::steady_clock::now();
+    // ---- the one pass ----
+    const is3d::DecayMcFlowRun run{&tb, d_slot.p, n_slots, n_events, in->seed, in->lifetime, *cuts, is3d::flow_thresholds(*cuts), d_block.p};
+    HIP_TRY(hipEventRecord(ev.e[0], nullptr));
+    HIP_TRY(is3d::decay_mc_flow_launch(run, d_in.p, n_particles, in->first_particle));
+    HIP_TRY(hipEventRecord(ev.e[1], nullptr));
+    HIP_TRY(hipEventSynchronize(ev.e[1]));
+    st.ms_h2d = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    st.ms_bin = ms_between(ev.e[0], ev.e[1]);
+    const auto t2 = std::chrono::steady_clock::now();
+    std::vector<int64_t> h(words + kBinTallies);
+    HIP_TRY(hipMemcpy(h.data(), d_block.p, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    st.ms_d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count();
+    is3d::flow_records_scatter(h.data(), records, n_events, n_slots);
+    const int rc = is3d::decay_mc_bins_tallies((const unsigned long long *)(h.data() + words), &st);
+    int64_t kept = 0;
+    for (size_t j = 0; j < (size_t)n_events * n_slots; j++) kept += records->M[j * is3d::kFlowRegions];
+    *n_final = st.n_final;
+    *n_unbinned = st.n_final - kept;
+    if (stats) *stats = st;
+    if (rc) return rc;
+    return is3d::flow_records_check(records, n_events, n_slots);
 }

@@ -45,6 +45,7 @@
 #include "cf_math.h"
 #include "cf_plan_geometry.h"
 #include "cf_sampler_bins.h"
+#include "cf_sampler_flow.h"
 #include "cf_decays_mc.h"
 #include "cf_sampler_common.h"
 #include "errors.h"
@@ -331,6 +332,7 @@ struct is3d_sampler_plan {
     DevMem d_drawn, d_emits, d_active, d_nactive, d_cdf;
     DevMem d_particles, d_hist;             // a binned run: one batch of particles (list-and-bin only); the histograms, then the yields
     DevMem d_hist_decayed, d_slot;          // a decayed-and-binned run: the second block (histograms, yields, tallies) and the slot map
+    DevMem d_flow, d_flow_decayed, d_flow_slot, d_flow_slot_decayed;   // a flow run: the record blocks (the decayed one with its tallies) and the slot maps
     int64_t cap_cells = 0, cap_bt = 0;      // what the workspaces above were sized for
     int64_t cap_list = 0;                   // ... d_counts and d_offsets, which a fused binned run never has
     size_t tmp_select = 0, tmp_scan = 0;
@@ -626,10 +628,21 @@ int bind_cells(is3d_sampler_plan *P, const is3d_cells *cells, int64_t first_cell
     return IS3D_OK;
 }
 using BinRun = is3d::SamplerBinRun;
+// a flow run of the batch loop: each batch's list in the plan's workspace goes through cf_sampler_flow into records_dev and, with decay,
+// through cf_decay_mc_flow (first_particle = the hadrons of the batches before it), whose time is added to ms_decay
+struct FlowRun {
+    is3d_flow_cuts cuts;
+    is3d::FlowThresholds thresholds;
+    int32_t n_slots;
+    const int32_t *slot_dev;          // [species]
+    unsigned long long *records_dev;
+    const is3d::DecayMcFlowRun *decay;
+    double ms_decay;
+};
 int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t n, const double *x_dev, const double *y_dev, int32_t n_events,
                     uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
                     bool fuse, int64_t *n_particles, is3d_sampler_stats *stats, const is3d::DecayMcBinRun *decay = nullptr,
-                    double *ms_decay = nullptr);
+                    double *ms_decay = nullptr, FlowRun *flow = nullptr);
 }  // namespace
 
 extern "C" void is3d_sampler_plan_destroy(is3d_sampler_plan *P)
@@ -663,10 +676,10 @@ namespace {
 // been decayed and binned into decay->block_dev (cf_decay_mc_bins), whose time is added to *ms_decay
 int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t n, const double *x_dev, const double *y_dev, int32_t n_events,
                     uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
-                    bool fuse, int64_t *n_particles, is3d_sampler_stats *stats, const is3d::DecayMcBinRun *decay, double *ms_decay)
+                    bool fuse, int64_t *n_particles, is3d_sampler_stats *stats, const is3d::DecayMcBinRun *decay, double *ms_decay, FlowRun *flow)
 {
     using is3d::set_error;
-    if (particles_dev == nullptr || bin) capacity = 0;
+    if (particles_dev == nullptr || bin || flow) capacity = 0;
     if (n > P->max_cells) return set_error(IS3D_EINVAL, "%lld cells, the sampler plan was created for %lld", (long long)n, (long long)P->max_cells);
     HIP_TRY(hipSetDevice(P->device));
     if (n == 0) return IS3D_OK;
@@ -770,7 +783,7 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t
             // the list: the caller's buffer at the running base; binned: the plan's workspace, grown to the largest batch seen, at base 0
             a.counts = nullptr; a.offsets = d_offsets.as<int64_t>();
             a.particles = particles_dev; a.base = base; a.capacity = capacity;
-            if (bin && batch_total > 0) {
+            if ((bin || flow) && batch_total > 0) {
                 if (batch_total > P->cap_particles) {
                     HIP_TRY(P->d_particles.alloc((size_t)batch_total * sizeof(is3d_particle)));
                     P->cap_particles = batch_total;
@@ -789,7 +802,18 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t
             HIP_TRY(is3d::sampler_bins_launch(bin->bins, bin->widths, bin->layout, sp.npart, n_events, P->d_particles.as<is3d_particle>(), batch_total,
                                               P->d_hist.as<unsigned long long>(), P->d_hist.as<unsigned long long>() + bin->layout.total,
                                               bin->bins.kernel_form));
+        if (flow && batch_total > 0)
+            HIP_TRY(is3d::flow_launch(flow->cuts, flow->thresholds, n_events, flow->n_slots, flow->slot_dev, sp.npart, P->d_particles.as<is3d_particle>(),
+                                      batch_total, flow->records_dev, flow->cuts.kernel_form));
         HIP_TRY(hipEventRecord(ev[4], nullptr));
+        if (flow && flow->decay && batch_total > 0) {
+            HIP_TRY(is3d::decay_mc_flow_launch(*flow->decay, P->d_particles.as<is3d_particle>(), batch_total, base));
+            HIP_TRY(hipEventRecord(ev[9], nullptr));
+            HIP_TRY(hipEventSynchronize(ev[9]));
+            float e_ms = 0;
+            HIP_TRY(hipEventElapsedTime(&e_ms, ev[4], ev[9]));
+            flow->ms_decay += e_ms;
+        }
         if (decay && bin && !fused && batch_total > 0) {
             HIP_TRY(is3d::decay_mc_bins_launch(*decay, P->d_particles.as<is3d_particle>(), batch_total, base));
             HIP_TRY(hipEventRecord(ev[9], nullptr));
@@ -825,8 +849,8 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t
         stats->n_cells_breakdown = (int64_t)h[5];
         stats->n_classes = ncls;
         stats->ms_count = fused ? 0.0 : ms_count; stats->ms_fill = fused ? 0.0 : ms_fill;
-        if (bin) stats->ms_bin = ms_bin;
-        if (bin && !fused) stats->particle_workspace_bytes = P->cap_particles * (int64_t)sizeof(is3d_particle);
+        if (bin || flow) stats->ms_bin = ms_bin;
+        if ((bin || flow) && !fused) stats->particle_workspace_bytes = P->cap_particles * (int64_t)sizeof(is3d_particle);
     }
     if (h[0] != ~0ULL) return set_error(IS3D_EDOMAIN, "cell %lld: %s", (long long)h[0], v.domain_text.c_str());
     if (particles_dev && base > capacity)
@@ -1231,6 +1255,126 @@ extern "C" int is3d_sample_decayed_binned(const is3d_cells *cells, const is3d_sp
     const int rc = is3d_sampler_plan_execute_decayed_binned(r.P, &r.dc, r.xy[0], r.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events,
                                                             bins, hist, tg.t, slot, n_slots, decay_seed, lifetime, hist_decayed, n_particles, n_final,
                                                             n_unbinned, stats, decay_stats);
+    if (stats) stats->ms_h2d = r.ms_h2d;
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// per-event flow records: each event batch's list, in the plan's workspace, through cf_sampler_flow and (with a table) cf_decay_mc_flow
+// ------------------------------------------------------------------------------------------------
+extern "C" int is3d_sampler_plan_execute_flow(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev,
+                                              int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
+                                              const is3d_flow_cuts *cuts, const int32_t *slot, int32_t n_slots,
+                                              const is3d_flow_records *records, const is3d_decay_mc_table *table, const int32_t *slot_decayed,
+                                              int32_t n_slots_decayed, uint64_t decay_seed, int32_t lifetime,
+                                              const is3d_flow_records *records_decayed, int64_t *n_particles, int64_t *n_final,
+                                              int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats)
+{
+    using is3d::set_error;
+    if (!P || !cells || !n_particles || (table && (!n_final || !n_unbinned))) return set_error(IS3D_EINVAL, "null argument");
+    *n_particles = 0;
+    if (n_final) *n_final = 0;
+    if (n_unbinned) *n_unbinned = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (decay_stats) memset(decay_stats, 0, sizeof *decay_stats);
+    if (int rc = is3d::flow_check_args(cuts, n_events, n_slots, slot, P->sp.npart, records, 0)) return rc;
+    const int32_t n_entries = table ? is3d::decay_mc_table_entries(table) : 0;
+    if (table) {
+        if (int rc = is3d::flow_check_args(cuts, n_events, n_slots_decayed, slot_decayed, n_entries, records_decayed, is3d::kDecayMcBinTallies)) return rc;
+        if (is3d::decay_mc_table_chosen(table) != P->sp.npart)
+            return set_error(IS3D_EINVAL, "the decay table was created for %d chosen species, the sampler plan for %d", is3d::decay_mc_table_chosen(table),
+                             P->sp.npart);
+        if (is3d::decay_mc_table_device(table) != P->device)
+            return set_error(IS3D_EINVAL, "the decay table lives on device %d, the sampler plan on device %d", is3d::decay_mc_table_device(table), P->device);
+    }
+    if (int rc = bind_cells(P, cells, first_cell)) return rc;
+    const int64_t n_cells = cells->n_cells;
+    if (n_cells < 0 || n_cells + first_cell > 0xffffffffLL) return set_error(IS3D_EINVAL, "cell indices must fit 32 bits for the counter-based streams");
+    const size_t words = (size_t)n_events * n_slots * is3d::kFlowRecordWords;
+    const size_t words_d = table ? (size_t)n_events * n_slots_decayed * is3d::kFlowRecordWords : 0;
+    is3d_decay_mc_stats dst{};
+    if (table) is3d::decay_mc_table_stats(table, &dst);
+    is3d::flow_records_zero(records, n_events, n_slots);
+    if (table) is3d::flow_records_zero(records_decayed, n_events, n_slots_decayed);
+    if (n_cells == 0) {
+        if (decay_stats) *decay_stats = dst;
+        return IS3D_OK;
+    }
+    HIP_TRY(hipSetDevice(P->device));
+    // the record blocks and slot maps, sized at first use and kept by the plan
+    const auto grow = [](DevMem &d, size_t bytes) { return bytes > d.n ? d.alloc(bytes) : hipSuccess; };
+    HIP_TRY(grow(P->d_flow, words * sizeof(int64_t)));
+    HIP_TRY(hipMemsetAsync(P->d_flow.p, 0, words * sizeof(int64_t), nullptr));
+    HIP_TRY(grow(P->d_flow_slot, (size_t)P->sp.npart * sizeof(int32_t)));
+    HIP_TRY(hipMemcpy(P->d_flow_slot.p, slot, (size_t)P->sp.npart * sizeof(int32_t), hipMemcpyHostToDevice));
+    const is3d::FlowThresholds th = is3d::flow_thresholds(*cuts);
+    is3d::DecayMcFlowRun drun{};
+    if (table) {
+        HIP_TRY(grow(P->d_flow_decayed, (words_d + is3d::kDecayMcBinTallies) * sizeof(int64_t)));
+        HIP_TRY(hipMemsetAsync(P->d_flow_decayed.p, 0, (words_d + is3d::kDecayMcBinTallies) * sizeof(int64_t), nullptr));
+        HIP_TRY(grow(P->d_flow_slot_decayed, (size_t)n_entries * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(P->d_flow_slot_decayed.p, slot_decayed, (size_t)n_entries * sizeof(int32_t), hipMemcpyHostToDevice));
+        drun = is3d::DecayMcFlowRun{table, P->d_flow_slot_decayed.as<int32_t>(), n_slots_decayed, n_events, decay_seed, lifetime, *cuts, th,
+                                    P->d_flow_decayed.as<unsigned long long>()};
+    }
+    FlowRun run{*cuts, th, n_slots, P->d_flow_slot.as<int32_t>(), P->d_flow.as<unsigned long long>(), table ? &drun : nullptr, 0.0};
+    int64_t listed = 0;
+    if (int rc = sampler_batches(P, P->viscous, n_cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, nullptr, 0, nullptr, false, &listed, stats,
+                                 nullptr, nullptr, &run))
+        return rc;
+    *n_particles = listed;
+    std::vector<int64_t> h(std::max(words, words_d + is3d::kDecayMcBinTallies));
+    HIP_TRY(hipMemcpy(h.data(), P->d_flow.p, words * sizeof(int64_t), hipMemcpyDeviceToHost));
+    is3d::flow_records_scatter(h.data(), records, n_events, n_slots);
+    int rc_t = IS3D_OK;
+    if (table) {
+        HIP_TRY(hipMemcpy(h.data(), P->d_flow_decayed.p, (words_d + is3d::kDecayMcBinTallies) * sizeof(int64_t), hipMemcpyDeviceToHost));
+        is3d::flow_records_scatter(h.data(), records_decayed, n_events, n_slots_decayed);
+        rc_t = is3d::decay_mc_bins_tallies((const unsigned long long *)(h.data() + words_d), &dst);
+        int64_t kept = 0;
+        for (size_t j = 0; j < (size_t)n_events * n_slots_decayed; j++) kept += records_decayed->M[j * is3d::kFlowRegions];
+        dst.n_primaries = listed;
+        dst.ms_bin = run.ms_decay;
+        *n_final = dst.n_final;
+        *n_unbinned = dst.n_final - kept;
+        if (decay_stats) *decay_stats = dst;
+    }
+    if (rc_t) return rc_t;
+    if (int rc = is3d::flow_records_check(records, n_events, n_slots)) return rc;
+    return table ? is3d::flow_records_check(records_decayed, n_events, n_slots_decayed) : IS3D_OK;
+}
+
+// host-pointer one-shot: create, upload, execute, destroy (the table included)
+extern "C" int is3d_sample_flow(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                                const is3d_options *opts, const is3d_flow_cuts *cuts, const int32_t *slot, int32_t n_slots,
+                                const is3d_flow_records *records, const is3d_decay_table *table, const int64_t *chosen_mc_id,
+                                const int32_t *slot_decayed, int32_t n_slots_decayed, uint64_t decay_seed, int32_t lifetime,
+                                const is3d_flow_records *records_decayed, int64_t *n_particles, int64_t *n_final, int64_t *n_unbinned,
+                                is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats)
+{
+    using is3d::set_error;
+    if (!cells || !species || !df || !in || !opts || !n_particles || (table && (!chosen_mc_id || !n_final || !n_unbinned)))
+        return set_error(IS3D_EINVAL, "null argument");
+    *n_particles = 0;
+    if (n_final) *n_final = 0;
+    if (n_unbinned) *n_unbinned = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (decay_stats) memset(decay_stats, 0, sizeof *decay_stats);
+    if (species->n < 1) return set_error(IS3D_EINVAL, "the species list is empty");
+    if (int rc = is3d::flow_check_args(cuts, in->n_events, n_slots, slot, species->n, records, 0)) return rc;
+    if (table) {
+        if (table->n < 1) return set_error(IS3D_EINVAL, "decay table: n = %d", table->n);
+        if (int rc = is3d::flow_check_args(cuts, in->n_events, n_slots_decayed, slot_decayed, table->n, records_decayed, is3d::kDecayMcBinTallies)) return rc;
+        if (int rc = is3d::decay_mc_table_check(table, species->n, chosen_mc_id)) return rc;
+    }
+    StagedRun r;
+    if (int rc = stage_run(r, cells, species, df, in, opts)) return rc;
+    struct TableGuard { is3d_decay_mc_table *t = nullptr; ~TableGuard() { is3d_decay_mc_table_destroy(t); } } tg;
+    if (table)
+        if (int rc = is3d_decay_mc_table_create(&tg.t, table, species->n, chosen_mc_id, r.P->device)) return rc;
+    const int rc = is3d_sampler_plan_execute_flow(r.P, &r.dc, r.xy[0], r.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events, cuts, slot,
+                                                  n_slots, records, tg.t, slot_decayed, n_slots_decayed, decay_seed, lifetime, records_decayed,
+                                                  n_particles, n_final, n_unbinned, stats, decay_stats);
     if (stats) stats->ms_h2d = r.ms_h2d;
     return rc;
 }

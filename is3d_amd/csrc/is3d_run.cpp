@@ -8,7 +8,7 @@
 // Writes: average_thermodynamic_quantities.dat (not in mode 2); input/surface.dat.is3dcache; in results/, which must exist -- operation 1:
 //   dN_pTdpTdphidy*.dat, dN_dpTdphidy.dat, dN_dy_*.dat, vn_continuous/vn_*.dat, *_resonance_decays.dat; operation 0: spacetime_distribution/*.dat;
 //   operation 2: particle_list_osc.dat, particle_list_osc_decayed.dat, or the binned test files (test_sampler = 1; with test_sampler_decayed = 1
-//   also under results/decayed/); mode 5: S{t,x,y,n}.dat.
+//   also under results/decayed/; with test_sampler_flow = 1 the flow cumulants and multiplicities under results/flow/); mode 5: S{t,x,y,n}.dat.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -173,7 +173,8 @@ struct MemSurface { const is3d_cells *cells; const double *x, *y; };
 struct RunConfig {
     int operation, mode, hrg_eos, dimension, df_mode, include_baryon, include_bulk, include_shear, include_diff, regulate, outflow;
     // optional keys (absent: 0); an `is set` flag here has passed its checks
-    bool do_decays, decay_sampled, bin_on_device, bin_fused, vah_oversample, vah_bin_on_device, vah_sampler, test_sampler, bin_decayed;
+    bool do_decays, decay_sampled, bin_on_device, bin_fused, vah_oversample, vah_bin_on_device, vah_sampler, test_sampler, bin_decayed, flow;
+    is3d_flow_cuts flow_cuts;   // test_sampler_flow = 1: flow_y_cut, flow_y_gap, flow_pT_min, flow_pT_max (defaults 1.0, 0.5, 0.2, 3.0)
     bool vah;               // mode 2 from files: the anisotropic-hydro surface, tables and routines
     bool feqmod;            // df_mode 3 / 4 of viscous hydro: the modified-equilibrium kernels
     const char *pdg_path;
@@ -197,6 +198,7 @@ static int parse_config(const RunParams &p, const MemSurface *mem, bool wants_re
     c.do_decays = is_set("do_resonance_decays"); c.decay_sampled = is_set("decay_sampled_hadrons"); c.bin_on_device = is_set("test_sampler_on_device");
     c.bin_fused = is_set("test_sampler_fused"); c.vah_sampler = is_set("vah_sampler"); c.vah_oversample = is_set("vah_oversample");
     c.vah_bin_on_device = is_set("vah_sampler_on_device"); c.bin_decayed = is_set("test_sampler_decayed");
+    c.flow = is_set("test_sampler_flow");
     // test_sampler is a sampler key: optional where a check only looks at it, required (with the missing-key message) where a key depends on it
     const bool has_test_sampler = p.optional("test_sampler", &v);
     c.test_sampler = has_test_sampler && (int)v != 0;
@@ -322,6 +324,37 @@ static int parse_config(const RunParams &p, const MemSurface *mem, bool wants_re
         if (hrg_eos != 1 && hrg_eos != 2)
             DIE("test_sampler_decayed = 1 with hrg_eos = %d: PDG/pdg_box.dat carries no decay data (smash box: no decay info, iS3D_parameters.dat); use hrg_eos = 1 or 2, "
                 "or set test_sampler_decayed = 0", hrg_eos);
+    }
+    // test_sampler_flow = 1: beside the distributions of a test_sampler_on_device run, the per-event flow records of its hadrons (and, with
+    // test_sampler_decayed = 1, of their decay products) as cumulants and multiplicities under results/flow/ (results/decayed/flow/).  Behind
+    // every other check, and the one check here that looks at the file system: the directories must exist before anything is written.
+    if (c.flow) {
+        if (operation != 2)
+            DIE("test_sampler_flow = 1 with operation = %d: it records the flow vectors of the sampler's hadrons (operation = 2); set test_sampler_flow = 0", operation);
+        if (need_test_sampler()) return IS3D_EINVAL;
+        if (!c.test_sampler)
+            DIE("test_sampler_flow = 1 with test_sampler = 0: it writes the flow cumulants beside the test_sampler distributions; set test_sampler_flow = 0");
+        if (vah)
+            DIE("test_sampler_flow = 1 with mode = 2: it records the viscous-hydro sampler's hadrons; the anisotropic-hydro sampler has no such entry; set test_sampler_flow = 0");
+        if (wants_result)
+            DIE("test_sampler_flow = 1: the embedding entry returns the particle list, which this path never holds; set test_sampler_flow = 0");
+        if (!c.bin_on_device)
+            DIE("test_sampler_flow = 1 with test_sampler_on_device = 0: the flow records are made where each event batch is binned, on the device "
+                "(test_sampler_on_device = 1); set test_sampler_flow = 0");
+        if (c.bin_fused)
+            DIE("test_sampler_flow = 1 with test_sampler_fused = 1: the fused pass never holds the batch of hadrons that is recorded; set test_sampler_flow = 0");
+        is3d_flow_cuts &f = c.flow_cuts;
+        f = is3d_flow_cuts{1.0, 0.5, 0.2, 3.0, 0};
+        p.optional("flow_y_cut", &f.y_cut); p.optional("flow_y_gap", &f.y_gap); p.optional("flow_pt_min", &f.pT_min); p.optional("flow_pt_max", &f.pT_max);
+        if (!(f.y_cut > 0.0 && f.y_gap >= 0.0 && f.y_gap < 2.0 * f.y_cut && f.pT_min >= 0.0 && f.pT_max > f.pT_min))
+            DIE("test_sampler_flow = 1 with flow_y_cut = %g, flow_y_gap = %g, flow_pT_min = %g, flow_pT_max = %g: the cuts need flow_y_cut > 0, "
+                "0 <= flow_y_gap < 2 flow_y_cut and flow_pT_max > flow_pT_min >= 0; set test_sampler_flow = 0", f.y_cut, f.y_gap, f.pT_min, f.pT_max);
+        for (const char *dir : {"results/flow", "results/decayed/flow"}) {
+            if (dir[8] == 'd' && !c.bin_decayed) continue;
+            struct stat sb;
+            if (stat(dir, &sb) != 0 || !S_ISDIR(sb.st_mode))
+                DIE("test_sampler_flow = 1: the directory %s is missing; create it or set test_sampler_flow = 0", dir);
+        }
     }
     return IS3D_OK;
 }
@@ -791,14 +824,91 @@ static int run_sampler_decayed_binned(const RunConfig &cfg, RunInputs &in, const
     return IS3D_OK;
 }
 
+// test_sampler_flow = 1: after the binned run has written its files, the sampler runs once more on the first device of the run's list with the
+// same seed (the same hadrons: every stream is counter-based) and each event batch goes through cf_sampler_flow -- and, with
+// test_sampler_decayed = 1, through cf_decay_mc_flow with the decay seed of that run.  Slots: pi+, K+, p (211, 321, 2212) where chosen, everything
+// else in one further slot; "all" is written from the merge.  Decayed: the same rule over the chosen species that are stable in the table.
+static int run_sampler_flow(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, SamplerRun &s)
+{
+    static const int64_t named[3] = {211, 321, 2212};
+    // labels and the slot of an mc_id, in the order the ids come; `others` gets its slot when the first such id comes
+    struct Slots {
+        std::vector<std::string> label;
+        int other = -1;
+        int of(int64_t id)
+        {
+            for (int64_t k : named)
+                if (id == k) {
+                    const std::string l = std::to_string((long long)id);
+                    for (size_t j = 0; j < label.size(); j++)
+                        if (label[j] == l) return (int)j;
+                    label.push_back(l);
+                    return (int)label.size() - 1;
+                }
+            if (other < 0) { other = (int)label.size(); label.push_back("other"); }
+            return other;
+        }
+    } th, de;
+    std::vector<int32_t> slot((size_t)in.sp.n), slot_d;
+    for (int ip = 0; ip < in.sp.n; ip++) slot[(size_t)ip] = th.of(in.mcid[(size_t)ip]);
+    DecayTable tab;
+    if (cfg.bin_decayed) {
+        if (int rc = read_decay_table(cfg.pdg_path, tab)) return rc;
+        slot_d.assign((size_t)tab.view.n, -1);
+        for (int ip = 0; ip < in.sp.n; ip++)
+            for (int32_t e = 0; e < tab.view.n; e++)
+                if (tab.id[(size_t)e] == in.mcid[(size_t)ip]) {          // first match, as the library's chosen -> entry map
+                    if (tab.stable[(size_t)e] && slot_d[(size_t)e] < 0) slot_d[(size_t)e] = de.of(tab.id[(size_t)e]);
+                    break;
+                }
+    }
+    const bool decayed = cfg.bin_decayed && !de.label.empty();
+    const int32_t E = s.si.n_events, S = (int32_t)th.label.size(), Sd = (int32_t)de.label.size();
+    struct Block {
+        std::vector<int64_t> M, re, im;
+        is3d_flow_records view;
+        Block(int32_t events, int32_t slots)
+            : M((size_t)events * slots * 3), re(M.size() * IS3D_FLOW_HARMONICS), im(re.size()), view{M.data(), re.data(), im.data()} {}
+    } rt(E, S), rdec(E, std::max(Sd, 1)), all_t(E, 1), all_d(E, 1);
+    is3d_sampler_stats ss{};
+    is3d_decay_mc_stats ms{};
+    int64_t count = 0, n_final = 0, n_unbinned = 0;
+    is3d_options opts = in.opts;
+    opts.device = rd.first();
+    const int rcf = is3d_sample_flow(&in.cells, &in.sp, &in.df, &s.si, &opts, &cfg.flow_cuts, slot.data(), S, &rt.view, decayed ? &tab.view : nullptr,
+                                     in.mcid.data(), slot_d.data(), Sd, s.si.seed, 0, &rdec.view, &count, &n_final, &n_unbinned, &ss, &ms);
+    if (rcf) DIE("is3d_sample_flow failed (%d): %s", rcf, is3d_last_error());
+    const auto write = [E](const char *dir, Block &b, Block &all, const std::vector<std::string> &label) {
+        std::vector<const char *> names;
+        for (const std::string &l : label) names.push_back(l.c_str());
+        const std::vector<int32_t> group(label.size(), 0);
+        const char *const all_name = "all";
+        if (is3d_write_flow(dir, &b.view, E, (int32_t)label.size(), names.data())) return 1;
+        if (is3d_flow_merge(&b.view, E, (int32_t)label.size(), group.data(), 1, &all.view)) return 1;
+        return is3d_write_flow(dir, &all.view, E, 1, &all_name) ? 1 : 0;
+    };
+    printf("Writing the flow cumulants and multiplicities (%d slots and all)...\n", (int)S);
+    if (write("results", rt, all_t, th.label)) DIE("%s", is3d_last_error());
+    if (decayed) {
+        printf("Writing the flow cumulants and multiplicities of the decayed hadrons (%d slots and all)...\n", (int)Sd);
+        if (write("results/decayed", rdec, all_d, de.label)) DIE("%s", is3d_last_error());
+    }
+    printf("flow records on the device: %lld hadrons, ms_bin %.3f ms", (long long)count, ss.ms_bin);
+    if (decayed) printf("; decayed: n_final %lld, n_unbinned %lld, ms_bin %.3f ms", (long long)n_final, (long long)n_unbinned, ms.ms_bin);
+    printf("\n");
+    return IS3D_OK;
+}
+
 // ---- operation 2 (emissionfunction.cpp:1522-1554): number of events, sampling, the OSCAR list or the binned test distributions ----
 static int run_sampler(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, RunParams &params, is3d_run_result *res)
 {
     SamplerRun s;
     if (int rc = setup_sampler(cfg, in, params, s)) return rc;
     if (int rc = size_sampler_run(cfg, in, s)) return rc;
-    if (cfg.bin_decayed) return run_sampler_decayed_binned(cfg, in, rd, s);
-    if (cfg.bin_on_device || cfg.vah_bin_on_device || cfg.bin_fused) return run_sampler_binned(cfg, in, rd, s);
+    if (cfg.bin_decayed || cfg.bin_on_device || cfg.vah_bin_on_device || cfg.bin_fused) {
+        if (int rc = cfg.bin_decayed ? run_sampler_decayed_binned(cfg, in, rd, s) : run_sampler_binned(cfg, in, rd, s)) return rc;
+        return cfg.flow ? run_sampler_flow(cfg, in, rd, s) : IS3D_OK;
+    }
     // count, then fill a list of that size: the viscous-hydro sampler, or (mode 2) the anisotropic-hydro one on the mode-2 cells and tables
     is3d_sampler_stats ss{};
     int64_t count = 0;
