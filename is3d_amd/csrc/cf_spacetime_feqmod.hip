@@ -111,7 +111,11 @@ __global__ void __launch_bounds__(256) cf_st_fq_cells(const StFqCellArgs a)
                         double rv = 0.0;
 #pragma unroll
                         for (int jj = 0; jj < JT; jj++) {
-                            const double X = sqrt_g1(__builtin_fma(mTpT, row[4 + jj], a2 + pT2g[jj]));
+                            double X = sqrt_g1(__builtin_fma(mTpT, row[4 + jj], a2 + pT2g[jj]));
+                            // 2+1D: the rows sit at eta_scale eta_k with eta_scale = detA and no upper bound (:1847-1849), which the exponent-range
+                            // bound of cf_prep_feqmod (cosh(max |eta_k|), right for the spectra's detA < 1) does not cover: X can pass exp_p9's
+                            // |v| < 1.4e9 on a row that the wave-uniform cull keeps, or with the cull off.  e^-1e9 is the same +0 as e^-X there.
+                            if (!DIM3) X = X > 1.0e9 ? 1.0e9 : X;
                             const double z = exp_p9(BARYON ? cm - X : -X);
                             const double w = z * rcp_nr(__builtin_fma(sign, z, 1.0));
                             double pds = __builtin_fma(pTB[jj], W, mTA);

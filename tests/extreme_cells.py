@@ -4,7 +4,8 @@ viscous stress, rapidity, proper time, the anisotropy variables, mu_B -- that ta
 T in [0.140, 0.160], pi ~ 2 % of E + P, |eta| <= 4, tau in [1, 10], alpha_L in [0.7, 1.2]).  tests/hostile_surfaces.py does the same for dsigma.
 Pure numpy; tests/golden/make_golden_extreme.py evaluates the long-double restatements on every case and commits cells and spectra
 (tests/golden/golden_extreme.npz, .json), tests/test_extreme_cells.py checks table and fixture on the CPU, tests/test_gpu_extreme_cells.py runs
-the device against the fixture.
+the device against the fixture.  Operation 0 runs on the same committed cells (op0_weights, op0_grid, op0_bins, fixture_op0 below;
+tests/extreme_cells_op0.py), and so do mode 5 (tests/test_extreme_polarization.py) and the VAH mean yield (tests/test_extreme_yield_vah.py).
 
 Case            transformation (u = a uniform draw in [0.05, 1), one per cell; dsigma is never touched but where stated)
 fast-flow       transverse rapidity uniform in [1.0, 3.7] (gamma to 20), azimuth uniform and independent of the cell's position; 3+1D:
@@ -205,23 +206,76 @@ def exact_nodes(dim):
     return c
 
 
-# ---- the committed fixture (tests/golden/make_golden_extreme.py) ----
-@lru_cache(maxsize=None)
-def fixture():
-    """(arrays of golden_extreme.npz, read-only; the dict of golden_extreme.json)"""
+# ---- the committed fixtures (tests/golden/make_golden_extreme.py, make_golden_extreme_op0.py) ----
+def _load(stem):
+    """(arrays of tests/golden/<stem>.npz, read-only; the dict of <stem>.json)"""
     import json
     import os
     here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-    with np.load(os.path.join(here, "golden_extreme.npz")) as z:
+    with np.load(os.path.join(here, stem + ".npz")) as z:
         arrays = {k: z[k] for k in z.files}
     for v in arrays.values():
         v.setflags(write=False)
-    with open(os.path.join(here, "golden_extreme.json")) as f:
+    with open(os.path.join(here, stem + ".json")) as f:
         return arrays, json.load(f)
+
+
+@lru_cache(maxsize=None)
+def fixture():
+    """(arrays of golden_extreme.npz, read-only; the dict of golden_extreme.json)"""
+    return _load("golden_extreme")
 
 
 def fixture_cases(family=None):
     return [c for c in fixture()[1]["cases"] if family is None or c["family"] == family]
+
+
+# ---- operation 0 on the same cells (tests/golden/make_golden_extreme_op0.py) ----
+ETA_NODES = (0, 60, 120, 180, 240)        # the 2+1D dN/dy deta partials that are committed
+PT_W_NAMES = ("ones",) + tuple("e%d" % i for i in range(6))
+
+
+@lru_cache(maxsize=None)
+def op0_weights():
+    """(phi_w [9], a seeded positive vector; {name: pT_w [6]}: all ones and the six unit vectors -- with e_i, dN_dy_cell is the (phi, y | eta) sum
+    of a cell at pT node i alone, so that a high node cannot hide behind the low ones; a zero weight is an ordinary input)"""
+    phi_w = np.random.default_rng(6200).uniform(0.5, 1.5, len(grid()["phi"]))
+    pT_w = {"ones": np.ones(6)}
+    pT_w.update({"e%d" % i: np.eye(6)[i] for i in range(6)})
+    for v in (phi_w,) + tuple(pT_w.values()):
+        v.setflags(write=False)
+    return phi_w, pT_w
+
+
+PT_PAD = (0.5, 1.0, 2.0)
+
+
+def op0_grid(name, padded=False):
+    """the grid with the reduction weights of the pT weight vector `name`.  padded: three more pT nodes (PT_PAD) of weight zero behind the six,
+    which leave every dN_dy_cell and dN_dydeta what it is: the 2+1D modified-equilibrium kernel keeps 48 KiB of LDS for its eta rows, [4 waves]
+    [64 / npTp classes][241] doubles, and refuses 6 pT x 241 eta (npTp = 8: 61 KiB; tests/test_spacetime_checks_shared.py pins that refusal),
+    while 9 pT values (npTp = 16: 31 KiB) fit"""
+    g = dict(grid(), phi_w=op0_weights()[0], pT_w=op0_weights()[1][name])
+    if padded:
+        g.update(pT=np.append(g["pT"], PT_PAD), pT_w=np.append(g["pT_w"], np.zeros(len(PT_PAD))))
+    return g
+
+
+def op0_bins(cells_xy):
+    """tau bins that leave the cells of tau-extremes (0.05 / 50) outside on both sides, and the slowest and the fastest of every other case; r
+    bins that end inside the surface"""
+    r = np.sqrt(cells_xy["x"] ** 2 + cells_xy["y"] ** 2)
+    return dict(tau_min=1.5, tau_max=8.0, tau_bins=5, r_min=0.0, r_max=0.8 * float(r.max()), r_bins=4)
+
+
+@lru_cache(maxsize=None)
+def fixture_op0():
+    """(arrays of golden_extreme_op0.npz: per case key D [S][6][36], per 2+1D key also <key>_eta [S][5]; the dict of golden_extreme_op0.json)"""
+    return _load("golden_extreme_op0")
+
+
+def fixture_op0_cases(family=None):
+    return [c for c in fixture_op0()[1]["cases"] if family is None or c["family"] == family]
 
 
 def fixture_cells(tag):

@@ -35,8 +35,9 @@ def coefficients_scipy(tab, Lambda_GeV, aL):
     return out
 
 
-def highprec_vah(c, sp, g, dim, regulate, bulk=True, shear=True):
-    """smooth_kernels.cpp:2208-2346 in long double; returns dN[iy][iphi][ipT][ipart] flattened species-fastest (:2340)."""
+def highprec_vah(c, sp, g, dim, regulate, bulk=True, shear=True, rounded=True):
+    """smooth_kernels.cpp:2208-2346 in long double; returns dN[iy][iphi][ipT][ipart] flattened species-fastest (:2340), rounded to double unless
+    the caller goes on summing (rounded=False)."""
     pT, phi = g["pT"].astype(LD), g["phi"].astype(LD)
     if dim == 3:
         yv = g["y"].astype(LD)
@@ -87,7 +88,7 @@ def highprec_vah(c, sp, g, dim, regulate, bulk=True, shear=True):
                 df = df + (f["c0"] * m * m + f["c1"] * pz * pz + f["c2"] * pu * pu) * f["bulkPi"]
             corr = np.clip(fabar * df, -1, 1) if regulate else fabar * df
             out[:, :, :, ip] += pre * gdeg * np.sum(ws[None, None, None, :] * pds * fa * (1 + corr), axis=3)
-    return out.reshape(-1).astype(np.float64)
+    return out.reshape(-1).astype(np.float64) if rounded else out.reshape(-1)
 
 
 def main():

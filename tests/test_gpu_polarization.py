@@ -16,12 +16,20 @@ pytestmark = pytest.mark.gpu
 OUTS = api.POLARIZATION_OUTPUTS
 
 
-def restate(cells, w, sp, grid, T, dim, chunk_local=False):
+def restate(cells, w, sp, grid, T, dim, chunk_local=False, dtype=np.float64):
     """calculate_spin_polzn in numpy, term by term (polzn_kernels.cpp:117-216).  chunk_local: the reference's indexing of the vorticity by
-    the cell index inside its 10 000-cell chunk (:149-154)."""
+    the cell index inside its 10 000-cell chunk (:149-154).  dtype = np.longdouble: the same text in 80-bit arithmetic (cos / sin of phi stay
+    doubles, as the reference forms them), and the result is (outputs, magnitudes): per output and bin the sum of |summands|, the size a
+    bin of terms of both signs is judged against (tests/test_gpu_extreme_polarization.py)."""
+    ld = np.dtype(dtype) != np.float64
     n = len(cells["tau"])
     idx = np.arange(n) % 10000 if chunk_local else np.arange(n)
     wtx, wty, wtn, wxy, wxn, wyn = (np.asarray(w[f])[idx] for f in synth.VORTICITY_FIELDS)
+    if ld:
+        wtx, wty, wtn, wxy, wxn, wyn = (a.astype(dtype) for a in (wtx, wty, wtn, wxy, wxn, wyn))
+        cells = {k: np.asarray(v).astype(dtype) for k, v in cells.items() if v is not None}
+        grid = {k: np.asarray(v).astype(dtype) for k, v in grid.items()}
+        T = dtype(T)
     tau, ux, uy, un = cells["tau"], cells["ux"], cells["uy"], cells["un"]
     dat, dax, day, dan = cells["dat"], cells["dax"], cells["day"], cells["dan"]
     ut = np.sqrt(np.abs(1.0 + ux * ux + uy * uy + tau * tau * un * un))   # :137
@@ -29,17 +37,18 @@ def restate(cells, w, sp, grid, T, dim, chunk_local=False):
     if dim == 3:
         yv, etav, wk = np.asarray(grid["y"]), None, None
     else:
-        yv = np.zeros(1)
+        yv = np.zeros(1, dtype)
         etav = np.asarray(grid["eta"])
         wk = np.asarray(grid["eta_w"]) * (etav[1] - etav[0])                 # :69-70
     S, npT, J, ny = len(sp["mass"]), len(pTv), len(phiv), len(yv)
-    out = {k: np.zeros((ny, J, npT, S)) for k in OUTS}
-    cp, spn = np.cos(phiv), np.sin(phiv)
+    out = {k: np.zeros((ny, J, npT, S), dtype) for k in OUTS}
+    mag = {k: np.zeros((ny, J, npT, S), dtype) for k in OUTS} if ld else None
+    cp, spn = np.cos(np.asarray(phiv, np.float64)).astype(dtype), np.sin(np.asarray(phiv, np.float64)).astype(dtype)
     # axes: cell, phi, (y | eta)
     C = lambda a: a[:, None, None]                                           # noqa: E731
     with np.errstate(over="ignore", invalid="ignore"):
         for s in range(S):
-            m, sign = float(sp["mass"][s]), float(sp["sign"][s])
+            m, sign = (dtype(sp["mass"][s]), dtype(sp["sign"][s])) if ld else (float(sp["mass"][s]), float(sp["sign"][s]))
             for ip, pT in enumerate(pTv):
                 mT = np.sqrt(m * m + pT * pT)
                 px, py = (pT * cp)[None, :, None], (pT * spn)[None, :, None]
@@ -64,6 +73,10 @@ def restate(cells, w, sp, grid, T, dim, chunk_local=False):
                         out[k][:, :, ip, s] = v.sum(axis=0).T          # [y][phi]
                     else:
                         out[k][0, :, ip, s] = v.sum(axis=(0, 2))
+                    if ld:
+                        mag[k][:, :, ip, s] = np.abs(v).sum(axis=0).T if dim == 3 else np.abs(v).sum(axis=(0, 2))[None, :]
+    if ld:
+        return {k: v.reshape(-1) for k, v in out.items()}, {k: v.reshape(-1) for k, v in mag.items()}
     return {k: v.reshape(-1) for k, v in out.items()}
 
 

@@ -79,21 +79,26 @@ def shear_lrf_diagonal(v):
     return quad(X), quad(Y), quad(Z)
 
 
-def radial_sums(root, weight, mbar, sign):
+def radial_sums(root, weight, mbar, sign, dtype=np.float64):
     """(N0, A0, A2) for an array of mbar"""
-    r, w = np.asarray(root, dtype=np.float64)[None, :], np.asarray(weight, dtype=np.float64)[None, :]
+    r, w = np.asarray(root, dtype=dtype)[None, :], np.asarray(weight, dtype=dtype)[None, :]
     with np.errstate(over="ignore"):
-        e = np.minimum(np.exp(np.sqrt(r * r + np.asarray(mbar, dtype=np.float64)[:, None] ** 2)), 1.0e300)   # held there, as the kernel holds it
+        e = np.minimum(np.exp(np.sqrt(r * r + np.asarray(mbar, dtype=dtype)[:, None] ** 2)), 1.0e300)   # held there, as the kernel holds it
     q = 1.0 / (e + sign)
     eq2 = e * q * q
     base = w * r * np.exp(r)
     return np.sum(base * q, axis=1), np.sum(base * eq2, axis=1), np.sum(base * r * r * eq2, axis=1)
 
 
-def total_yield_vah_ref(v, sp, gla, opts, y_cut=0.5, coef=None):
+def total_yield_vah_ref(v, sp, gla, opts, y_cut=0.5, coef=None, dtype=np.float64):
     """-> (mean_yield, yield_by_species, n_cells_skipped).  v: dict of VAH cell arrays; coef: dict c0..c4 in place of the cells' own; opts:
-    dimension, include_bulk_deltaf, include_shear_deltaf (default 1)."""
+    dimension, include_bulk_deltaf, include_shear_deltaf (default 1).  dtype = np.longdouble: the same text in 80-bit arithmetic, yields
+    returned in that type."""
     bulk, shear = int(opts.get("include_bulk_deltaf", 1)), int(opts.get("include_shear_deltaf", 1))
+    if np.dtype(dtype) != np.float64:
+        v = {k: np.asarray(a).astype(dtype) for k, a in v.items()}
+        coef = None if coef is None else {k: np.asarray(a).astype(dtype) for k, a in coef.items()}
+        sp = {k: np.asarray(sp[k]).astype(dtype) for k in ("mass", "sign", "degeneracy")}
     c = coef if coef is not None else v
     uds, _ = lrf_dsigma(v)
     live = uds > 0.0
@@ -107,13 +112,13 @@ def total_yield_vah_ref(v, sp, gla, opts, y_cut=0.5, coef=None):
         K_p = K_p + c["c4"] * (pXX + pYY + aL ** 2 * pZZ)
     K_p = K_p / 3.0
     w = np.where(live, uds * aL * L ** 3, 0.0)
-    by = np.zeros(len(sp["mass"]))
+    by = np.zeros(len(sp["mass"]), dtype)
     for s, (m, sign, g) in enumerate(zip(sp["mass"], sp["sign"], sp["degeneracy"])):
-        N0, A0, A2 = radial_sums(gla["root1"], gla["weight1"], m / L, sign)
-        by[s] = g / (2.0 * np.pi ** 2 * HBARC ** 3) * np.sum(w * (N0 + K_m * m * m * A0 + K_p * L * L * A2))
+        N0, A0, A2 = radial_sums(gla["root1"], gla["weight1"], m / L, sign, dtype)
+        by[s] = g / dtype(2.0 * np.pi ** 2 * HBARC ** 3) * np.sum(w * (N0 + K_m * m * m * A0 + K_p * L * L * A2))
     if int(opts.get("dimension", 3)) == 2:
         by = by * (2.0 * y_cut)
-    total = 0.0
+    total = dtype(0.0)
     for x in by:
         total += x
-    return float(total), by, int(np.count_nonzero(~live))
+    return (float(total) if np.dtype(dtype) == np.float64 else total), by, int(np.count_nonzero(~live))
