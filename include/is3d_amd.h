@@ -1304,6 +1304,106 @@ int is3d_sample_flow(const is3d_cells *cells, const is3d_species *species, const
                      const is3d_flow_records *records_decayed, int64_t *n_particles, int64_t *n_final, int64_t *n_unbinned,
                      is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats);
 
+/* Two-particle (delta y, delta phi) correlations of a particle list: how the pairs of ONE event are distributed in
+ * relative rapidity and azimuth, beside the same distribution of pairs from neighbouring events.  The flow records above hold the delta phi
+ * harmonics of that and nothing in delta y.  A particle maps to a cell (iy, iphi) of an n_y x n_phi grid or to nothing, by the rule of
+ * csrc/cf_sampler_pairs.h, shared by host and device, with ratio = (E + pz) / (E - pz) = e^{2y} (one division):
+ *   accepted   E - pz > 0, edge[0] <= ratio < edge[n_y], pT_min <= pT < pT_max and pT > 0, pT = sqrt(px^2 + py^2)
+ *   iy         the largest k with edge[k] <= ratio, edge[k] = exp(2 (-y_cut + k (2 y_cut / n_y))), by bisection
+ *   iphi       the quadrant from the signs of px and py; inside it the largest k with dir[k].x py - dir[k].y px >= 0 (two rounded products,
+ *              one subtraction), by bisection, dir[k] = (cos, sin)(2 pi k / n_phi) with the four axis directions exact
+ * The tables are computed once on the host and handed to the kernels as bits; no decision goes through log or atan2, so host and device
+ * reach the same cell from the same particle bits and every count below is equal on both, bit for bit.
+ * Bins are valid when y_cut > 0, pT_max > pT_min >= 0, 1 <= n_y <= 64, n_phi is a multiple of 4 in 4..64 and the edges come out finite and
+ * strictly increasing (NaN: invalid).
+ * Result (caller-owned): same and mixed [n_classes][2 n_y - 1][n_phi], n_classes = n_slots (n_slots + 1) / 2, class (a <= b) at index
+ * a n_slots - a (a - 1) / 2 + (b - a); M [n_events][n_slots], the accepted multiplicities.
+ *   same    every ordered pair (i, j), i != j, of one event, both accepted, slot_i <= slot_j, adds 1 to
+ *           same[class(slot_i, slot_j)][iy_j - iy_i + n_y - 1][(iphi_j - iphi_i) mod n_phi]
+ *   mixed   n_events >= 2: the same with i from event e and j from event (e + 1) mod n_events, without the i != j condition; one event: zero
+ * M[e][s] above IS3D_SAMPLER_VN_MAX_COUNT: IS3D_EDOMAIN from the device entries after the run. */
+typedef struct {
+    double y_cut, pT_min, pT_max;
+    int32_t n_y, n_phi;
+} is3d_pair_bins;
+typedef struct {
+    int64_t *same, *mixed, *M;
+} is3d_pair_hist;
+/* list -> histograms on the host, as the explicit double loop over the pairs: THE definition, no device use, O(M^2) per event.  slot:
+ * int32[n_species], species -> slot in [0, n_slots), or -1: dropped.  IS3D_EINVAL: a NULL, n_events, n_slots or n_species < 1, bad bins, a
+ * slot outside [-1, n_slots), a particle whose species or event is out of range.  hist is overwritten. */
+int is3d_pairs_list(const is3d_pair_bins *bins, int32_t n_events, int32_t n_slots, const int32_t *slot, int32_t n_species,
+                    int64_t n_particles, const is3d_particle *particles, const is3d_pair_hist *hist);
+/* list -> histograms on the DEVICE, without a loop over pairs: a caller's HOST list (any order, any length) is uploaded; cf_pair_cells
+ * (thread <-> particle) adds every accepted particle to a 32-bit occupancy block occ[event][slot][iy][iphi]; cf_pair_correlate (workgroup
+ * <-> (event, class)) forms the cross-correlation of the occupancy grids in 64-bit integers, which IS the pair histogram.  Its cost does
+ * not depend on M^2.  A particle whose species or event is out of range adds nothing and is counted in *n_skipped.  The refusals above
+ * (but that one) come before any device use; a good call without a device is IS3D_ENODEVICE; an occupancy block that cannot be allocated
+ * is IS3D_ENOMEM naming its size.  n_particles = 0: zero histograms, no launch.  device < 0: the current device. */
+int is3d_pairs_list_device(const is3d_pair_bins *bins, int32_t n_events, int32_t n_slots, const int32_t *slot, int32_t n_species,
+                           int64_t n_particles, const is3d_particle *particles, const is3d_pair_hist *hist, int64_t *n_skipped,
+                           int32_t device);
+/* The correlation function of every class from the exact integers, in double, on the host.  Per class c:
+ *   n_same, n_mixed   the totals of same and mixed over all bins
+ *   C[c][dy][dphi]    (same / n_same) / (mixed / n_mixed) where mixed > 0, else 0
+ *   C_phi[c][dphi]    the same ratio of the sums over the rows dy with |dy - (n_y - 1)| >= gap_bins (0 where that sum of mixed is 0):
+ *                     the delta phi projection with a rapidity gap of gap_bins bins
+ *   V[n - 1]          sum C_phi cos(2 pi n dphi / n_phi) / sum C_phi, n = 1..4 (0 when sum C_phi = 0)
+ * hist->M is not read.  IS3D_EINVAL: a NULL (C and C_phi may each be NULL: not returned), bad bins, n_slots < 1, gap_bins outside [0, n_y). */
+typedef struct {
+    int64_t n_same, n_mixed;
+    double V[4];
+} is3d_pair_result;
+int is3d_pairs_correlation(const is3d_pair_bins *bins, const is3d_pair_hist *hist, int32_t n_slots, int32_t gap_bins,
+                           double *C /* [n_classes][2 n_y - 1][n_phi] */, double *C_phi /* [n_classes][n_phi] */,
+                           is3d_pair_result *out /* [n_classes] */);
+/* Writes, per class (a <= b), <results_dir>/pairs/correlation_<labels[a]>_<labels[b]>.dat: two comment lines (the bins; the totals), then a
+ * row per bin: delta y (the centre (dy - (n_y - 1)) 2 y_cut / n_y), delta phi (dphi 2 pi / n_phi), same, mixed, C, tab separated.  Doubles
+ * are printed by std::to_chars(scientific, 8) as the other writers' values, integers in full.  The pairs/ directory must exist (IS3D_EIO
+ * otherwise); a NULL, an empty label or one with a '/', bad bins and n_slots < 1 are IS3D_EINVAL. */
+int is3d_write_pairs(const char *results_dir, const is3d_pair_bins *bins, const is3d_pair_hist *hist, int32_t n_slots,
+                     const char *const *labels);
+/* The pair histograms of a list AFTER its Monte Carlo decays, without the decayed list.  Definition: is3d_pairs_list(bins, n_events,
+ * n_slots, slot, table->n, ...) on the list that is3d_decay_particles returns for the same (table, chosen_mc_id, in, particles), whose
+ * species are TABLE entries -- equal bit for bit.  *n_final is the length of that list, *n_unbinned = *n_final - sum of M.  How:
+ * cf_decay_mc_pairs, thread <-> primary over the decay loop and stream of is3d_decay_particles; every final particle's momentum goes to the
+ * rule at once and makes ONE occupancy add; then cf_pair_correlate.  The occupancies do not depend on the launch geometry or on the pieces a
+ * list is decayed in (first_particle), but the histograms are not additive over pieces of one event: a caller who decays in pieces
+ * passes the whole list's occupancies through one correlate, which this entry does for its list.  slot: int32[table->n].  All pointers
+ * HOST memory; hist is overwritten.  stats as for is3d_decay_particles_binned (ms_bin: the decay pass).  IS3D_EINVAL before any device
+ * use: every refusal of is3d_decay_particles; the refusals of is3d_pairs_list_device with the table's entries as species; a primary whose
+ * event is outside [0, n_events).  n_particles = 0: zero histograms, no launch.  A good call without a device: IS3D_ENODEVICE. */
+int is3d_decay_particles_pairs(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
+                               const is3d_decay_mc_inputs *in, int64_t n_particles, const is3d_particle *particles,
+                               const int32_t *slot, int32_t n_slots, const is3d_pair_bins *bins, int32_t n_events,
+                               const is3d_pair_hist *hist, int64_t *n_final, int64_t *n_unbinned,
+                               is3d_decay_mc_stats *stats /* may be NULL */);
+/* is3d_sampler_plan_execute with the list of each event batch turned into occupancies on the device and discarded: fill into the plan's
+ * particle workspace, cf_pair_cells into a device-resident occupancy block (zeroed once per run, kept across batches; slot: int32 per
+ * species of the plan) and, with table_dev != NULL, cf_decay_mc_pairs of the same batch with first_particle = the number of hadrons of the
+ * batches before it (slot_decayed: int32 per table entry) into a second block; after the last batch cf_pair_correlate for each block and
+ * one copy to the caller's HOST arrays.
+ *   hist          = is3d_pairs_list of the list is3d_sampler_plan_execute returns for the same arguments
+ *   hist_decayed  = is3d_decay_particles_pairs of that list with first_particle = 0, seed = decay_seed
+ * independent of batch_events and launch geometry, bit for bit.  The plan keeps the blocks and slot maps (sized at first use) and serves
+ * its other entries in any order, as before.  table_dev == NULL: slot_decayed, hist_decayed, n_final, n_unbinned and decay_stats are not
+ * used.  IS3D_EINVAL before any device use: the refusals of is3d_pairs_list_device for either result, a table of another chosen count or
+ * device.  Not offered: the fused sample-and-bin pass, the anisotropic-hydro sampler, several devices. */
+int is3d_sampler_plan_execute_pairs(is3d_sampler_plan *plan, const is3d_cells *cells_dev, const double *x_dev, const double *y_dev,
+                                    int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events, const is3d_pair_bins *bins,
+                                    const int32_t *slot, int32_t n_slots, const is3d_pair_hist *hist_host,
+                                    const is3d_decay_mc_table *table_dev /* may be NULL */, const int32_t *slot_decayed, int32_t n_slots_decayed,
+                                    uint64_t decay_seed, int32_t lifetime, const is3d_pair_hist *hist_decayed, int64_t *n_particles,
+                                    int64_t *n_final, int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats);
+/* host-pointer one-shot for the viscous sampler: plan and table create, upload, execute, destroy.  table may be NULL; otherwise chosen_mc_id
+ * holds the mc_id of species[0 .. n), which the table must hold.  The bins' and the table's refusals come first, then the plan's. */
+int is3d_sample_pairs(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                      const is3d_options *opts, const is3d_pair_bins *bins, const int32_t *slot, int32_t n_slots,
+                      const is3d_pair_hist *hist, const is3d_decay_table *table /* may be NULL */, const int64_t *chosen_mc_id,
+                      const int32_t *slot_decayed, int32_t n_slots_decayed, uint64_t decay_seed, int32_t lifetime,
+                      const is3d_pair_hist *hist_decayed, int64_t *n_particles, int64_t *n_final, int64_t *n_unbinned,
+                      is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats);
+
 /* ---------------------------------------------------------------------------------------------
  * Driver: IS3D::run_particlization (src/cpp/iS3D.cpp:74-192; class IS3D, src/cpp/iS3D.h:19-96).  Reads iS3D_parameters.dat,
  * PDG/, tables/, deltaf_coefficients/ from the current directory and writes results/ exactly as the command line tool does

@@ -124,6 +124,8 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_sampler_bin_list_device", "is3d_df_generate", "is3d_df_tables_write",
            "is3d_flow_list", "is3d_flow_list_device", "is3d_flow_merge", "is3d_flow_cumulants", "is3d_decay_particles_flow",
            "is3d_sampler_plan_execute_flow", "is3d_sample_flow", "is3d_write_flow",
+           "is3d_pairs_list", "is3d_pairs_list_device", "is3d_pairs_correlation", "is3d_write_pairs", "is3d_decay_particles_pairs",
+           "is3d_sampler_plan_execute_pairs", "is3d_sample_pairs",
            "is3d_smooth_spectra_vah_multi", "is3d_vah_plan_observables",
            "is3d_spacetime_distributions_vah", "is3d_vah_plan_execute_spacetime",
            "is3d_sample_particles_vah", "is3d_sample_particles_vah_multi", "is3d_sample_binned_vah", "is3d_sample_binned_vah_multi",
@@ -1189,6 +1191,27 @@ def decay_particles_flow(table, chosen_mc_id, particles, slot, n_slots, cuts, n_
     return out, _check_decayed(rc, st, nf, nu, records=out)
 
 
+def decay_particles_pairs(table, chosen_mc_id, particles, slot, n_slots, bins, n_events, seed=1, first_particle=0, lifetime=0, device=-1):
+    """is3d_decay_particles_pairs: a sampled list decayed on the device with every final particle added to the pair occupancies at once,
+    then correlated -- the histograms of pairs_list on decay_particles' list (species = table entries) with the same slot map, bit for bit.
+    slot: int32 per table entry.  Returns (hist dict, stats dict with n_final, n_unbinned and the tallies of decay_particles)."""
+    L = load()
+    ts, ch, _, keep = _decay_pack(table, chosen_mc_id, dict(pT=[1.0], phi=[0.0], y=[0.0]))
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    slot = _slot_map(table, slot)
+    inp = DecayMcInputs(int(seed), int(first_particle), int(lifetime), int(device))
+    b = _pack_pair_bins(bins)
+    h, out = _pair_arrays(b, n_events, n_slots)
+    st, nf, nu = DecayMcStats(), C.c_int64(0), C.c_int64(0)
+    L.is3d_decay_particles_pairs.argtypes = [C.POINTER(DecayTable), C.c_int32, C.POINTER(C.c_int64), C.POINTER(DecayMcInputs), C.c_int64, C.c_void_p,
+                                             C.c_void_p, C.c_int32, C.POINTER(PairBins), C.c_int32, C.POINTER(PairHist),
+                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(DecayMcStats)]
+    rc = L.is3d_decay_particles_pairs(C.byref(ts), len(ch), ch.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(inp), len(particles),
+                                      particles.ctypes.data, slot.ctypes.data, int(n_slots), C.byref(b), int(n_events), C.byref(h), C.byref(nf),
+                                      C.byref(nu), C.byref(st))
+    return out, _check_decayed(rc, st, nf, nu, hist=out)
+
+
 def shard_bounds(n_cells, rank, n_ranks):
     """is3d_shard_bounds: the contiguous cell shard [lo, hi) of `rank` (what is3d_smooth_spectra_multi uses)."""
     lo, hi = C.c_int64(), C.c_int64()
@@ -1923,6 +1946,39 @@ class SamplerPlan:
         dd = _check_decayed(rc, dst, nf, nu, records=out, records_decayed=outd, sampler_stats=d)
         return out, outd, d, dd
 
+    def execute_pairs(self, n_cells, dev_ptrs, n_events, seed, bins, slot, n_slots, table=None, slot_decayed=None, n_slots_decayed=0,
+                      decay_seed=None, lifetime=0, x_ptr=0, y_ptr=0, first_cell=0, batch_events=0):
+        """is3d_sampler_plan_execute_pairs: the pair histograms of the list execute returns (slot: int32 per species of the plan) and, with
+        table (a DecayMcTable on the plan's device), of its Monte Carlo decay products (slot_decayed: int32 per table entry).
+        -> (hist, sampler stats) | (hist, decayed hist, sampler stats, decay stats with n_final and n_unbinned)."""
+        cs = Cells()
+        cs.n_cells = int(n_cells)
+        for f in CELL_FIELDS:
+            if dev_ptrs.get(f):
+                setattr(cs, f, int(dev_ptrs[f]))
+        b = _pack_pair_bins(bins)
+        slot = np.ascontiguousarray(slot, dtype=np.int32)
+        h, out = _pair_arrays(b, n_events, n_slots)
+        hd, outd = _pair_arrays(b, n_events, n_slots_decayed if table is not None else 0)
+        sd = _slot_map(table.table, slot_decayed) if table is not None else None
+        cnt, st, dst, nf, nu = C.c_int64(0), SamplerStats(), DecayMcStats(), C.c_int64(0), C.c_int64(0)
+        fn = load().is3d_sampler_plan_execute_pairs
+        fn.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(PairBins),
+                       C.c_void_p, C.c_int32, C.POINTER(PairHist), C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int32,
+                       C.POINTER(PairHist), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(SamplerStats),
+                       C.POINTER(DecayMcStats)]
+        rc = fn(self._h, C.byref(cs), C.c_void_p(int(x_ptr) or None), C.c_void_p(int(y_ptr) or None), int(n_events), int(seed), int(first_cell),
+                int(batch_events), C.byref(b), slot.ctypes.data, int(n_slots), C.byref(h), table._h if table is not None else None,
+                sd.ctypes.data if sd is not None else None, int(n_slots_decayed), int(seed if decay_seed is None else decay_seed), int(lifetime),
+                C.byref(hd) if table is not None else None, C.byref(cnt), C.byref(nf), C.byref(nu), C.byref(st), C.byref(dst))
+        d = st.as_dict()
+        d["n_particles"] = int(cnt.value)
+        if table is None:
+            _check(rc)
+            return out, d
+        dd = _check_decayed(rc, dst, nf, nu, hist=out, hist_decayed=outd, sampler_stats=d)
+        return out, outd, d, dd
+
     def execute_fused(self, n_cells, dev_ptrs, n_events, seed, bins, n_species, x_ptr=0, y_ptr=0, first_cell=0, batch_events=0):
         """is3d_sampler_plan_execute_fused: execute_binned's arguments and result, every hadron binned where it is sampled (no list, no
         particle workspace: stats["particle_workspace_bytes"] == 0)."""
@@ -2222,6 +2278,120 @@ def write_flow(results_dir, records, labels):
     _check(L.is3d_write_flow(results_dir.encode(), C.byref(r), n_events, n_slots, names))
 
 
+PAIR_BINS = dict(y_cut=2.0, pT_min=0.2, pT_max=3.0, n_y=32, n_phi=32)   # the run driver's defaults
+
+
+class PairBins(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ["y_cut", "pT_min", "pT_max"]] + [("n_y", C.c_int32), ("n_phi", C.c_int32)]
+
+
+class PairHist(C.Structure):
+    _fields_ = [(n, C.POINTER(C.c_int64)) for n in ["same", "mixed", "M"]]
+
+
+class PairResult(C.Structure):
+    _fields_ = [("n_same", C.c_int64), ("n_mixed", C.c_int64), ("V", C.c_double * 4)]
+
+
+def _pack_pair_bins(bins):
+    if isinstance(bins, PairBins):
+        return bins
+    b = PairBins()
+    for k, v in bins.items():
+        setattr(b, k, v)
+    return b
+
+
+def pair_classes(n_slots):
+    """The number of slot pairs (a <= b) of n_slots slots; class (a, b) has index a n_slots - a (a - 1) / 2 + (b - a)."""
+    return n_slots * (n_slots + 1) // 2
+
+
+def pair_class(a, b, n_slots):
+    assert 0 <= a <= b < n_slots, (a, b, n_slots)
+    return a * n_slots - a * (a - 1) // 2 + (b - a)
+
+
+def _pair_arrays(b, n_events, n_slots, hist=None):
+    """is3d_pair_hist over numpy int64 arrays: (struct, dict).  hist = None: fresh zero arrays same and mixed [class][2 n_y - 1][n_phi] and
+    M [event][slot] (shaped for valid bins; a refusal never writes them); otherwise the caller's arrays are checked and used."""
+    E, S = max(int(n_events), 0), max(int(n_slots), 0)
+    ny, nphi = min(max(int(b.n_y), 1), 64), min(max(int(b.n_phi), 1), 64)
+    shapes = dict(same=(pair_classes(S), 2 * ny - 1, nphi), mixed=(pair_classes(S), 2 * ny - 1, nphi), M=(E, S))
+    out = {}
+    for k, shp in shapes.items():
+        if hist is None:
+            out[k] = np.zeros(shp, dtype=np.int64)
+        else:
+            out[k] = np.ascontiguousarray(hist[k], dtype=np.int64)
+            assert out[k].shape == shp, (k, out[k].shape, shp)
+    h = PairHist(*[out[k].ctypes.data_as(C.POINTER(C.c_int64)) for k, _ in PairHist._fields_])
+    return h, out
+
+
+def pairs_list(bins, n_events, n_slots, slot, particles):
+    """is3d_pairs_list: a particle list -> the same-event and mixed-event (delta y, delta phi) pair histograms on the host, as the explicit
+    double loop (the definition; no device use; O(M^2) per event).  slot: int32 per species, -1 drops the species.  Returns a dict of int64
+    arrays same, mixed [class][2 n_y - 1][n_phi] and M [event][slot]."""
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    slot = np.ascontiguousarray(slot, dtype=np.int32)
+    b = _pack_pair_bins(bins)
+    h, out = _pair_arrays(b, n_events, n_slots)
+    L = load()
+    L.is3d_pairs_list.argtypes = [C.POINTER(PairBins), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(PairHist)]
+    _check(L.is3d_pairs_list(C.byref(b), int(n_events), int(n_slots), slot.ctypes.data, len(slot), len(particles), particles.ctypes.data, C.byref(h)))
+    return out
+
+
+def pairs_list_device(bins, n_events, n_slots, slot, particles, device=0):
+    """is3d_pairs_list_device: a host particle list through the device kernels cf_pair_cells and cf_pair_correlate (no loop over pairs).
+    Returns (hist, n_skipped); n_skipped counts the particles whose species or event is out of range, which add nothing."""
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    slot = np.ascontiguousarray(slot, dtype=np.int32)
+    b = _pack_pair_bins(bins)
+    h, out = _pair_arrays(b, n_events, n_slots)
+    skipped = C.c_int64(0)
+    L = load()
+    L.is3d_pairs_list_device.argtypes = [C.POINTER(PairBins), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(PairHist),
+                                         C.POINTER(C.c_int64), C.c_int32]
+    _check(L.is3d_pairs_list_device(C.byref(b), int(n_events), int(n_slots), slot.ctypes.data, len(slot), len(particles), particles.ctypes.data,
+                                    C.byref(h), C.byref(skipped), int(device)))
+    return out, int(skipped.value)
+
+
+def pairs_correlation(bins, hist, gap_bins=0):
+    """is3d_pairs_correlation: per class, C = (same / n_same) / (mixed / n_mixed) (0 where mixed is 0), its delta phi projection over the
+    rows at least gap_bins from delta y = 0 and V_n-delta, n = 1..4.  Returns a dict: C [class][2 n_y - 1][n_phi], C_phi [class][n_phi],
+    V [class][4], n_same, n_mixed [class]."""
+    b = _pack_pair_bins(bins)
+    n_classes = np.shape(hist["same"])[0]
+    n_slots = int(round((np.sqrt(8 * n_classes + 1) - 1) / 2))
+    assert pair_classes(n_slots) == n_classes, n_classes
+    n_events = np.shape(hist["M"])[0]
+    h, _keep = _pair_arrays(b, n_events, n_slots, hist)
+    Cc = np.zeros(np.shape(hist["same"]), dtype=np.float64)
+    Cp = np.zeros((n_classes, int(b.n_phi)), dtype=np.float64)
+    res = (PairResult * max(n_classes, 1))()
+    L = load()
+    L.is3d_pairs_correlation.argtypes = [C.POINTER(PairBins), C.POINTER(PairHist), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(PairResult)]
+    _check(L.is3d_pairs_correlation(C.byref(b), C.byref(h), n_slots, int(gap_bins), Cc.ctypes.data, Cp.ctypes.data, res))
+    return dict(C=Cc, C_phi=Cp, V=np.array([list(res[c].V) for c in range(n_classes)]).reshape(n_classes, 4),
+                n_same=np.array([res[c].n_same for c in range(n_classes)], dtype=np.int64),
+                n_mixed=np.array([res[c].n_mixed for c in range(n_classes)], dtype=np.int64))
+
+
+def write_pairs(results_dir, bins, hist, labels):
+    """is3d_write_pairs: <results_dir>/pairs/correlation_<A>_<B>.dat for every class (A <= B) of the histograms."""
+    b = _pack_pair_bins(bins)
+    n_slots = len(labels)
+    n_events = np.shape(hist["M"])[0]
+    h, _keep = _pair_arrays(b, n_events, n_slots, hist)
+    names = (C.c_char_p * n_slots)(*[str(x).encode() for x in labels])
+    L = load()
+    L.is3d_write_pairs.argtypes = [C.c_char_p, C.POINTER(PairBins), C.POINTER(PairHist), C.c_int32, C.POINTER(C.c_char_p)]
+    _check(L.is3d_write_pairs(results_dir.encode(), C.byref(b), C.byref(h), n_slots, names))
+
+
 def write_sampler_tests_binned(results_dir, bins, n_events, mc_id, hist, mean_yield=0.0):
     """is3d_write_sampler_tests_binned: the test_sampler = 1 files from a dict of int64 histograms."""
     ids = np.ascontiguousarray(mc_id, dtype=np.int64)
@@ -2306,6 +2476,44 @@ def sample_flow(cells, species, df, gla, cuts, slot, n_slots, opts=None, table=N
         _check(rc)
         return out, d
     dd = _check_decayed(rc, dst, nf, nu, records=out, records_decayed=outd, sampler_stats=d)
+    return out, outd, d, dd
+
+
+def sample_pairs(cells, species, df, gla, bins, slot, n_slots, opts=None, table=None, chosen_mc_id=None, slot_decayed=None, n_slots_decayed=0,
+                 n_events=1, seed=1, decay_seed=None, lifetime=0, y_cut=0.5, first_cell=0, fq=None, fast=0, T_avg=0.0, T_avg_switch=0.0,
+                 batch_events=0, muB_avg=0.0):
+    """is3d_sample_pairs: the viscous sampler with every event batch turned into pair occupancies on the device (slot: int32 per species)
+    and, with table (pdg_read_decays' dict; chosen_mc_id: the mc_id of the species list), decayed and counted again by slot_decayed (int32
+    per table entry); the occupancies are correlated after the last batch.  Returns (hist, sampler stats) | (hist, decayed hist, sampler
+    stats, decay stats)."""
+    cs, sps, ds, si, os_, _held = _pack_sampler(cells, species, df, gla, opts, n_events, seed, y_cut, first_cell, fq, fast, T_avg, T_avg_switch,
+                                                batch_events, muB_avg)
+    b = _pack_pair_bins(bins)
+    slot = np.ascontiguousarray(slot, dtype=np.int32)
+    assert len(slot) == sps.n, (len(slot), sps.n)
+    h, out = _pair_arrays(b, n_events, n_slots)
+    hd, outd = _pair_arrays(b, n_events, n_slots_decayed if table is not None else 0)
+    ts = ch = sd = None
+    if table is not None:
+        ts, ch, _, keep = _decay_pack(table, chosen_mc_id, dict(pT=[1.0], phi=[0.0], y=[0.0]))
+        assert len(ch) == sps.n, (len(ch), sps.n)
+        sd = _slot_map(table, slot_decayed)
+    cnt, st, dst, nf, nu = C.c_int64(0), SamplerStats(), DecayMcStats(), C.c_int64(0), C.c_int64(0)
+    fn = load().is3d_sample_pairs
+    fn.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options), C.POINTER(PairBins),
+                   C.c_void_p, C.c_int32, C.POINTER(PairHist), C.POINTER(DecayTable), C.POINTER(C.c_int64), C.c_void_p, C.c_int32, C.c_uint64,
+                   C.c_int32, C.POINTER(PairHist), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(SamplerStats),
+                   C.POINTER(DecayMcStats)]
+    rc = fn(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), C.byref(b), slot.ctypes.data, int(n_slots), C.byref(h),
+            C.byref(ts) if ts is not None else None, ch.ctypes.data_as(C.POINTER(C.c_int64)) if ch is not None else None,
+            sd.ctypes.data if sd is not None else None, int(n_slots_decayed), int(seed if decay_seed is None else decay_seed), int(lifetime),
+            C.byref(hd) if table is not None else None, C.byref(cnt), C.byref(nf), C.byref(nu), C.byref(st), C.byref(dst))
+    d = st.as_dict()
+    d["n_particles"] = int(cnt.value)
+    if table is None:
+        _check(rc)
+        return out, d
+    dd = _check_decayed(rc, dst, nf, nu, hist=out, hist_decayed=outd, sampler_stats=d)
     return out, outd, d, dd
 
 

@@ -7,6 +7,7 @@
 #include "../../include/is3d_amd.h"
 #include "cf_sampler_bins.h"
 #include "cf_sampler_flow.h"
+#include "cf_sampler_pairs.h"
 
 namespace is3d {
 
@@ -55,6 +56,21 @@ struct DecayMcFlowRun {
 };
 // as decay_mc_bins_launch, every final particle going to the rule of cf_sampler_flow.h; form r.cuts.kernel_form
 hipError_t decay_mc_flow_launch(const DecayMcFlowRun &r, const is3d_particle *primaries_dev, int64_t n, int64_t first_particle);
+// A decayed run into pair occupancies (cf_sampler_pairs.h): the slot map as above, the bins with their tables, and the device block
+// tally [kDecayMcBinTallies 64-bit words] | occ [n_events * n_slots * n_y * n_phi 32-bit words]
+struct DecayMcPairRun {
+    const is3d_decay_mc_table *table;
+    const int32_t *slot_dev;
+    int32_t n_slots, n_events;
+    uint64_t seed;
+    int32_t lifetime;
+    is3d_pair_bins bins;
+    PairTables tables;
+    unsigned long long *tally_dev;
+    unsigned *occ_dev;
+};
+// as decay_mc_bins_launch, every final particle going to the rule of cf_sampler_pairs.h and making ONE occupancy add
+hipError_t decay_mc_pairs_launch(const DecayMcPairRun &r, const is3d_particle *primaries_dev, int64_t n, int64_t first_particle);
 // the tallies of a finished run (HOST copy of the tally words) into stats; IS3D_EINVAL if a pending stack overflowed
 int decay_mc_bins_tallies(const unsigned long long *tally, is3d_decay_mc_stats *stats);
 // the static part of the stats: what the table analysis found

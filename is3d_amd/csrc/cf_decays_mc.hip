@@ -376,6 +376,48 @@ __global__ void __launch_bounds__(kBinThreads) cf_decay_mc_flow(const McArgs a, 
     if (PRIVATE) is3d::flow_window_flush<kBinThreads>(target);
 }
 
+// the pair pass: the final particle's momentum, built in registers, goes to the rule of cf_sampler_pairs.h with slot[entry]; an accepted
+// particle makes ONE 32-bit add into the occupancy block; slot -1, a particle outside the bins or a primary whose event has no grid adds nothing
+struct McPairArgs {
+    is3d_pair_bins b;
+    is3d::PairTables t;
+    int32_t n_slots, n_events;
+    const int32_t *slot;              // [table entries]
+    unsigned *occ;
+    unsigned long long *tally;        // tally[kBinTallies]
+};
+struct SinkPairs {
+    static constexpr bool kMomenta = true;
+    const McPairArgs &f;
+    bool live;
+    __device__ __forceinline__ void operator()(int, const Pending &c, const is3d_particle &q)
+    {
+        const int s = f.slot[c.e];
+        if (!live || s < 0 || s >= f.n_slots) return;
+        const int cell = is3d::pair_cell(f.b, f.t, c.E, c.px, c.py, c.pz);
+        if (cell >= 0) is3d::pair_add(f.b, f.occ, f.n_slots, q.event, s, cell);
+    }
+};
+
+// The one-pass pair kernel: thread <-> primary in a grid-stride walk; the tallies go through six static LDS words as in cf_decay_mc_bins.
+__global__ void __launch_bounds__(kBinThreads) cf_decay_mc_pairs(const McArgs a, const McPairArgs f)
+{
+    __shared__ unsigned long long blk[kBinTallies];
+    if (threadIdx.x < kBinTallies) blk[threadIdx.x] = 0ULL;
+    __syncthreads();
+    unsigned long long tally[kTallies] = {0ULL, 0ULL, 0ULL, 0ULL, 0ULL}, finals = 0ULL;
+    for (int64_t i = (int64_t)blockIdx.x * kBinThreads + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kBinThreads) {
+        const int event = a.in[i].event;
+        SinkPairs sink{f, event >= 0 && event < f.n_events};
+        finals += (unsigned long long)decay_tree(a, i, tally, sink);
+    }
+    for (int k = 0; k < kTallies; k++)
+        if (tally[k]) atomicAdd(&blk[k], tally[k]);
+    if (finals) atomicAdd(&blk[kTallies], finals);
+    __syncthreads();
+    if (threadIdx.x < kBinTallies && blk[threadIdx.x]) atomicAdd(&f.tally[threadIdx.x], blk[threadIdx.x]);
+}
+
 struct Widen {
     __host__ __device__ int64_t operator()(int32_t v) const { return (int64_t)v; }
 };
@@ -915,4 +957,96 @@ extern "C" int is3d_decay_particles_flow(const is3d_decay_table *table, int32_t 
     if (stats) *stats = st;
     if (rc) return rc;
     return is3d::flow_records_check(records, n_events, n_slots);
+}
+
+// ---- decayed into pair histograms: one decay pass into the occupancies, then cf_pair_correlate ----
+hipError_t is3d::decay_mc_pairs_launch(const DecayMcPairRun &r, const is3d_particle *primaries_dev, int64_t n, int64_t first_particle)
+{
+    if (n <= 0) return hipSuccess;
+    McArgs a{};
+    a.t = r.table->dev();
+    a.chosen_entry = r.table->d_chosen.p;
+    a.in = primaries_dev;
+    a.n = n;
+    a.first = first_particle;
+    a.seed = r.seed;
+    a.lifetime = r.lifetime;
+    const McPairArgs f{r.bins, r.tables, r.n_slots, r.n_events, r.slot_dev, r.occ_dev, r.tally_dev};
+    const int64_t trips = (n + kBinThreads - 1) / kBinThreads;
+    hipLaunchKernelGGL(cf_decay_mc_pairs, dim3((unsigned)std::min<int64_t>(trips, (int64_t)1 << 20)), dim3(kBinThreads), 0, nullptr, a, f);
+    return hipGetLastError();
+}
+
+extern "C" int is3d_decay_particles_pairs(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
+                                          const is3d_decay_mc_inputs *in, int64_t n_particles, const is3d_particle *particles,
+                                          const int32_t *slot, int32_t n_slots, const is3d_pair_bins *bins, int32_t n_events,
+                                          const is3d_pair_hist *hist, int64_t *n_final, int64_t *n_unbinned, is3d_decay_mc_stats *stats)
+{
+    if (!table || !chosen_mc_id || !in || !n_final || !n_unbinned)
+        return set_error(IS3D_EINVAL, "table, chosen_mc_id, in, n_final and n_unbinned are required");
+    *n_final = *n_unbinned = 0;
+    if (int rc = check_list_head(n_chosen, n_particles, particles)) return rc;
+    is3d_decay_mc_table tb;
+    if (int rc = analyse(*table, n_chosen, chosen_mc_id, tb.H)) return rc;
+    tb.n = table->n;
+    tb.n_chosen = n_chosen;
+    if (int rc = check_list_species(n_chosen, n_particles, particles)) return rc;
+    if (table->n < 1) return set_error(IS3D_EINVAL, "decay table: n = %d", table->n);
+    if (int rc = is3d::pair_check_args(bins, n_events, n_slots, slot, table->n, hist)) return rc;
+    for (int64_t i = 0; i < n_particles; i++)
+        if (particles[i].event < 0 || particles[i].event >= n_events)
+            return set_error(IS3D_EINVAL, "particle %lld: event %d outside the %d events", (long long)i, particles[i].event, n_events);
+    is3d_decay_mc_stats st{};
+    st.n_primaries = n_particles;
+    is3d::decay_mc_table_stats(&tb, &st);
+    if (n_particles == 0) {
+        is3d::pair_hist_zero(*bins, hist, n_events, n_slots);
+        if (stats) *stats = st;
+        return IS3D_OK;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return no_device();
+    is3d::pair_hist_zero(*bins, hist, n_events, n_slots);
+    if (in->device >= 0) HIP_TRY(hipSetDevice(in->device));
+    // ---- upload: the table, the primaries, the slot map; the tallies and the occupancy block zeroed ----
+    const auto t0 = std::chrono::steady_clock::now();
+    DevBuf<is3d_particle> d_in;
+    DevBuf<int32_t> d_slot;
+    DevBuf<unsigned char> d_block, d_out;
+    constexpr size_t head = kBinTallies * sizeof(unsigned long long);
+    const size_t out_words = is3d::pair_out_words(*bins, n_events, n_slots);
+    if (int rc = table_upload(tb, *table)) return rc;
+    HIP_TRY(d_in.upload(particles, (size_t)n_particles));
+    HIP_TRY(d_slot.upload(slot, (size_t)table->n));
+    if (int rc = is3d::pair_occ_begin(d_block, head, is3d::pair_occ_words(*bins, n_events, n_slots))) return rc;
+    HIP_TRY(d_out.alloc(out_words * sizeof(int64_t)));
+    Events ev;
+    for (int k = 0; k < 2; k++) HIP_TRY(hipEventCreate(&ev.e[k]));
+    HIP_TRY(hipDeviceSynchronize());
+    const auto t1 = std::chrono::steady_clock::now();
+    // ---- the decay pass, then the correlation of the occupancies ----
+    const is3d::DecayMcPairRun run{&tb, d_slot.p, n_slots, n_events, in->seed, in->lifetime, *bins, is3d::pair_tables(*bins),
+                                   d_block.as<unsigned long long>(), (unsigned *)(d_block.p + head)};
+    HIP_TRY(hipEventRecord(ev.e[0], nullptr));
+    HIP_TRY(is3d::decay_mc_pairs_launch(run, d_in.p, n_particles, in->first_particle));
+    HIP_TRY(hipEventRecord(ev.e[1], nullptr));
+    HIP_TRY(is3d::pair_correlate_launch(*bins, n_events, n_slots, run.occ_dev, d_out.as<unsigned long long>()));
+    HIP_TRY(hipEventSynchronize(ev.e[1]));
+    st.ms_h2d = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    st.ms_bin = ms_between(ev.e[0], ev.e[1]);
+    const auto t2 = std::chrono::steady_clock::now();
+    std::vector<int64_t> h(out_words);
+    unsigned long long tally[kBinTallies];
+    HIP_TRY(hipMemcpy(h.data(), d_out.p, out_words * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tally, d_block.p, sizeof tally, hipMemcpyDeviceToHost));
+    st.ms_d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count();
+    is3d::pair_hist_scatter(*bins, h.data(), hist, n_events, n_slots);
+    const int rc = is3d::decay_mc_bins_tallies(tally, &st);
+    int64_t kept = 0;
+    for (size_t j = 0; j < (size_t)n_events * n_slots; j++) kept += hist->M[j];
+    *n_final = st.n_final;
+    *n_unbinned = st.n_final - kept;
+    if (stats) *stats = st;
+    if (rc) return rc;
+    return is3d::pair_hist_check(hist, n_events, n_slots);
 }

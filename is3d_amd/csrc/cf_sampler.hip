@@ -46,6 +46,7 @@
 #include "cf_plan_geometry.h"
 #include "cf_sampler_bins.h"
 #include "cf_sampler_flow.h"
+#include "cf_sampler_pairs.h"
 #include "cf_decays_mc.h"
 #include "cf_sampler_common.h"
 #include "errors.h"
@@ -333,6 +334,7 @@ struct is3d_sampler_plan {
     DevMem d_particles, d_hist;             // a binned run: one batch of particles (list-and-bin only); the histograms, then the yields
     DevMem d_hist_decayed, d_slot;          // a decayed-and-binned run: the second block (histograms, yields, tallies) and the slot map
     DevMem d_flow, d_flow_decayed, d_flow_slot, d_flow_slot_decayed;   // a flow run: the record blocks (the decayed one with its tallies) and the slot maps
+    DevMem d_pair_occ, d_pair_occ_decayed, d_pair_out, d_pair_slot, d_pair_slot_decayed;   // a pair run: the occupancy blocks (the decayed one behind its tallies), the histograms, the slot maps
     int64_t cap_cells = 0, cap_bt = 0;      // what the workspaces above were sized for
     int64_t cap_list = 0;                   // ... d_counts and d_offsets, which a fused binned run never has
     size_t tmp_select = 0, tmp_scan = 0;
@@ -638,6 +640,12 @@ struct FlowRun {
     unsigned long long *records_dev;
     const is3d::DecayMcFlowRun *decay;
     double ms_decay;
+    // a pair run instead (records_dev == NULL): the batch's list goes through cf_pair_cells into occ_dev and, with pair_decay, through
+    // cf_decay_mc_pairs; slot_dev and n_slots as above
+    const is3d_pair_bins *pair_bins;
+    const is3d::PairTables *pair_tables;
+    unsigned *occ_dev;
+    const is3d::DecayMcPairRun *pair_decay;
 };
 int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t n, const double *x_dev, const double *y_dev, int32_t n_events,
                     uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
@@ -802,12 +810,23 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t
             HIP_TRY(is3d::sampler_bins_launch(bin->bins, bin->widths, bin->layout, sp.npart, n_events, P->d_particles.as<is3d_particle>(), batch_total,
                                               P->d_hist.as<unsigned long long>(), P->d_hist.as<unsigned long long>() + bin->layout.total,
                                               bin->bins.kernel_form));
-        if (flow && batch_total > 0)
+        if (flow && flow->occ_dev && batch_total > 0)
+            HIP_TRY(is3d::pair_cells_launch(*flow->pair_bins, *flow->pair_tables, n_events, flow->n_slots, flow->slot_dev, sp.npart,
+                                            P->d_particles.as<is3d_particle>(), batch_total, flow->occ_dev));
+        if (flow && flow->records_dev && batch_total > 0)
             HIP_TRY(is3d::flow_launch(flow->cuts, flow->thresholds, n_events, flow->n_slots, flow->slot_dev, sp.npart, P->d_particles.as<is3d_particle>(),
                                       batch_total, flow->records_dev, flow->cuts.kernel_form));
         HIP_TRY(hipEventRecord(ev[4], nullptr));
         if (flow && flow->decay && batch_total > 0) {
             HIP_TRY(is3d::decay_mc_flow_launch(*flow->decay, P->d_particles.as<is3d_particle>(), batch_total, base));
+            HIP_TRY(hipEventRecord(ev[9], nullptr));
+            HIP_TRY(hipEventSynchronize(ev[9]));
+            float e_ms = 0;
+            HIP_TRY(hipEventElapsedTime(&e_ms, ev[4], ev[9]));
+            flow->ms_decay += e_ms;
+        }
+        if (flow && flow->pair_decay && batch_total > 0) {
+            HIP_TRY(is3d::decay_mc_pairs_launch(*flow->pair_decay, P->d_particles.as<is3d_particle>(), batch_total, base));
             HIP_TRY(hipEventRecord(ev[9], nullptr));
             HIP_TRY(hipEventSynchronize(ev[9]));
             float e_ms = 0;
@@ -1317,7 +1336,7 @@ extern "C" int is3d_sampler_plan_execute_flow(is3d_sampler_plan *P, const is3d_c
         drun = is3d::DecayMcFlowRun{table, P->d_flow_slot_decayed.as<int32_t>(), n_slots_decayed, n_events, decay_seed, lifetime, *cuts, th,
                                     P->d_flow_decayed.as<unsigned long long>()};
     }
-    FlowRun run{*cuts, th, n_slots, P->d_flow_slot.as<int32_t>(), P->d_flow.as<unsigned long long>(), table ? &drun : nullptr, 0.0};
+    FlowRun run{*cuts, th, n_slots, P->d_flow_slot.as<int32_t>(), P->d_flow.as<unsigned long long>(), table ? &drun : nullptr, 0.0, nullptr, nullptr, nullptr, nullptr};
     int64_t listed = 0;
     if (int rc = sampler_batches(P, P->viscous, n_cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, nullptr, 0, nullptr, false, &listed, stats,
                                  nullptr, nullptr, &run))
@@ -1375,6 +1394,136 @@ extern "C" int is3d_sample_flow(const is3d_cells *cells, const is3d_species *spe
     const int rc = is3d_sampler_plan_execute_flow(r.P, &r.dc, r.xy[0], r.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events, cuts, slot,
                                                   n_slots, records, tg.t, slot_decayed, n_slots_decayed, decay_seed, lifetime, records_decayed,
                                                   n_particles, n_final, n_unbinned, stats, decay_stats);
+    if (stats) stats->ms_h2d = r.ms_h2d;
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// two-particle (delta y, delta phi) histograms: each event batch's list, in the plan's workspace, through cf_pair_cells and (with a table)
+// cf_decay_mc_pairs into occupancy blocks that live for the whole run; after the last batch cf_pair_correlate for each block
+// ------------------------------------------------------------------------------------------------
+extern "C" int is3d_sampler_plan_execute_pairs(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev,
+                                               int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
+                                               const is3d_pair_bins *bins, const int32_t *slot, int32_t n_slots, const is3d_pair_hist *hist,
+                                               const is3d_decay_mc_table *table, const int32_t *slot_decayed, int32_t n_slots_decayed,
+                                               uint64_t decay_seed, int32_t lifetime, const is3d_pair_hist *hist_decayed, int64_t *n_particles,
+                                               int64_t *n_final, int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats)
+{
+    using is3d::set_error;
+    if (!P || !cells || !n_particles || (table && (!n_final || !n_unbinned))) return set_error(IS3D_EINVAL, "null argument");
+    *n_particles = 0;
+    if (n_final) *n_final = 0;
+    if (n_unbinned) *n_unbinned = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (decay_stats) memset(decay_stats, 0, sizeof *decay_stats);
+    if (int rc = is3d::pair_check_args(bins, n_events, n_slots, slot, P->sp.npart, hist)) return rc;
+    const int32_t n_entries = table ? is3d::decay_mc_table_entries(table) : 0;
+    if (table) {
+        if (int rc = is3d::pair_check_args(bins, n_events, n_slots_decayed, slot_decayed, n_entries, hist_decayed)) return rc;
+        if (is3d::decay_mc_table_chosen(table) != P->sp.npart)
+            return set_error(IS3D_EINVAL, "the decay table was created for %d chosen species, the sampler plan for %d", is3d::decay_mc_table_chosen(table),
+                             P->sp.npart);
+        if (is3d::decay_mc_table_device(table) != P->device)
+            return set_error(IS3D_EINVAL, "the decay table lives on device %d, the sampler plan on device %d", is3d::decay_mc_table_device(table), P->device);
+    }
+    if (int rc = bind_cells(P, cells, first_cell)) return rc;
+    const int64_t n_cells = cells->n_cells;
+    if (n_cells < 0 || n_cells + first_cell > 0xffffffffLL) return set_error(IS3D_EINVAL, "cell indices must fit 32 bits for the counter-based streams");
+    is3d_decay_mc_stats dst{};
+    if (table) is3d::decay_mc_table_stats(table, &dst);
+    is3d::pair_hist_zero(*bins, hist, n_events, n_slots);
+    if (table) is3d::pair_hist_zero(*bins, hist_decayed, n_events, n_slots_decayed);
+    if (n_cells == 0) {
+        if (decay_stats) *decay_stats = dst;
+        return IS3D_OK;
+    }
+    HIP_TRY(hipSetDevice(P->device));
+    // the occupancy blocks, the histogram block and the slot maps, sized at first use and kept by the plan
+    const auto grow = [](DevMem &d, size_t bytes) { return bytes > d.n ? d.alloc(bytes) : hipSuccess; };
+    constexpr size_t head = is3d::kDecayMcBinTallies * sizeof(unsigned long long);
+    const size_t out_words = is3d::pair_out_words(*bins, n_events, n_slots);
+    const size_t out_words_d = table ? is3d::pair_out_words(*bins, n_events, n_slots_decayed) : 0;
+    if (int rc = is3d::pair_occ_begin(P->d_pair_occ, 0, is3d::pair_occ_words(*bins, n_events, n_slots))) return rc;
+    HIP_TRY(grow(P->d_pair_out, std::max(out_words, out_words_d) * sizeof(int64_t)));
+    HIP_TRY(grow(P->d_pair_slot, (size_t)P->sp.npart * sizeof(int32_t)));
+    HIP_TRY(hipMemcpy(P->d_pair_slot.p, slot, (size_t)P->sp.npart * sizeof(int32_t), hipMemcpyHostToDevice));
+    const is3d::PairTables tables = is3d::pair_tables(*bins);
+    is3d::DecayMcPairRun drun{};
+    if (table) {
+        if (int rc = is3d::pair_occ_begin(P->d_pair_occ_decayed, head, is3d::pair_occ_words(*bins, n_events, n_slots_decayed))) return rc;
+        HIP_TRY(grow(P->d_pair_slot_decayed, (size_t)n_entries * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(P->d_pair_slot_decayed.p, slot_decayed, (size_t)n_entries * sizeof(int32_t), hipMemcpyHostToDevice));
+        drun = is3d::DecayMcPairRun{table, P->d_pair_slot_decayed.as<int32_t>(), n_slots_decayed, n_events, decay_seed, lifetime, *bins, tables,
+                                    P->d_pair_occ_decayed.as<unsigned long long>(), (unsigned *)(P->d_pair_occ_decayed.p + head)};
+    }
+    FlowRun run{};
+    run.n_slots = n_slots;
+    run.slot_dev = P->d_pair_slot.as<int32_t>();
+    run.pair_bins = bins;
+    run.pair_tables = &tables;
+    run.occ_dev = P->d_pair_occ.as<unsigned>();
+    run.pair_decay = table ? &drun : nullptr;
+    int64_t listed = 0;
+    if (int rc = sampler_batches(P, P->viscous, n_cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, nullptr, 0, nullptr, false, &listed, stats,
+                                 nullptr, nullptr, &run))
+        return rc;
+    *n_particles = listed;
+    std::vector<int64_t> h(std::max(out_words, out_words_d));
+    HIP_TRY(is3d::pair_correlate_launch(*bins, n_events, n_slots, run.occ_dev, P->d_pair_out.as<unsigned long long>()));
+    HIP_TRY(hipMemcpy(h.data(), P->d_pair_out.p, out_words * sizeof(int64_t), hipMemcpyDeviceToHost));
+    is3d::pair_hist_scatter(*bins, h.data(), hist, n_events, n_slots);
+    int rc_t = IS3D_OK;
+    if (table) {
+        HIP_TRY(is3d::pair_correlate_launch(*bins, n_events, n_slots_decayed, drun.occ_dev, P->d_pair_out.as<unsigned long long>()));
+        HIP_TRY(hipMemcpy(h.data(), P->d_pair_out.p, out_words_d * sizeof(int64_t), hipMemcpyDeviceToHost));
+        is3d::pair_hist_scatter(*bins, h.data(), hist_decayed, n_events, n_slots_decayed);
+        unsigned long long tally[is3d::kDecayMcBinTallies];
+        HIP_TRY(hipMemcpy(tally, P->d_pair_occ_decayed.p, sizeof tally, hipMemcpyDeviceToHost));
+        rc_t = is3d::decay_mc_bins_tallies(tally, &dst);
+        int64_t kept = 0;
+        for (size_t j = 0; j < (size_t)n_events * n_slots_decayed; j++) kept += hist_decayed->M[j];
+        dst.n_primaries = listed;
+        dst.ms_bin = run.ms_decay;
+        *n_final = dst.n_final;
+        *n_unbinned = dst.n_final - kept;
+        if (decay_stats) *decay_stats = dst;
+    }
+    if (rc_t) return rc_t;
+    if (int rc = is3d::pair_hist_check(hist, n_events, n_slots)) return rc;
+    return table ? is3d::pair_hist_check(hist_decayed, n_events, n_slots_decayed) : IS3D_OK;
+}
+
+// host-pointer one-shot: create, upload, execute, destroy (the table included)
+extern "C" int is3d_sample_pairs(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                                 const is3d_options *opts, const is3d_pair_bins *bins, const int32_t *slot, int32_t n_slots,
+                                 const is3d_pair_hist *hist, const is3d_decay_table *table, const int64_t *chosen_mc_id,
+                                 const int32_t *slot_decayed, int32_t n_slots_decayed, uint64_t decay_seed, int32_t lifetime,
+                                 const is3d_pair_hist *hist_decayed, int64_t *n_particles, int64_t *n_final, int64_t *n_unbinned,
+                                 is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats)
+{
+    using is3d::set_error;
+    if (!cells || !species || !df || !in || !opts || !n_particles || (table && (!chosen_mc_id || !n_final || !n_unbinned)))
+        return set_error(IS3D_EINVAL, "null argument");
+    *n_particles = 0;
+    if (n_final) *n_final = 0;
+    if (n_unbinned) *n_unbinned = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (decay_stats) memset(decay_stats, 0, sizeof *decay_stats);
+    if (species->n < 1) return set_error(IS3D_EINVAL, "the species list is empty");
+    if (int rc = is3d::pair_check_args(bins, in->n_events, n_slots, slot, species->n, hist)) return rc;
+    if (table) {
+        if (table->n < 1) return set_error(IS3D_EINVAL, "decay table: n = %d", table->n);
+        if (int rc = is3d::pair_check_args(bins, in->n_events, n_slots_decayed, slot_decayed, table->n, hist_decayed)) return rc;
+        if (int rc = is3d::decay_mc_table_check(table, species->n, chosen_mc_id)) return rc;
+    }
+    StagedRun r;
+    if (int rc = stage_run(r, cells, species, df, in, opts)) return rc;
+    struct TableGuard { is3d_decay_mc_table *t = nullptr; ~TableGuard() { is3d_decay_mc_table_destroy(t); } } tg;
+    if (table)
+        if (int rc = is3d_decay_mc_table_create(&tg.t, table, species->n, chosen_mc_id, r.P->device)) return rc;
+    const int rc = is3d_sampler_plan_execute_pairs(r.P, &r.dc, r.xy[0], r.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events, bins, slot,
+                                                   n_slots, hist, tg.t, slot_decayed, n_slots_decayed, decay_seed, lifetime, hist_decayed,
+                                                   n_particles, n_final, n_unbinned, stats, decay_stats);
     if (stats) stats->ms_h2d = r.ms_h2d;
     return rc;
 }

@@ -8,7 +8,8 @@
 // Writes: average_thermodynamic_quantities.dat (not in mode 2); input/surface.dat.is3dcache; in results/, which must exist -- operation 1:
 //   dN_pTdpTdphidy*.dat, dN_dpTdphidy.dat, dN_dy_*.dat, vn_continuous/vn_*.dat, *_resonance_decays.dat; operation 0: spacetime_distribution/*.dat;
 //   operation 2: particle_list_osc.dat, particle_list_osc_decayed.dat, or the binned test files (test_sampler = 1; with test_sampler_decayed = 1
-//   also under results/decayed/; with test_sampler_flow = 1 the flow cumulants and multiplicities under results/flow/); mode 5: S{t,x,y,n}.dat.
+//   also under results/decayed/; with test_sampler_flow = 1 the flow cumulants and multiplicities under results/flow/; with test_sampler_pairs = 1
+//   the two-particle correlations under results/pairs/); mode 5: S{t,x,y,n}.dat.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -173,7 +174,8 @@ struct MemSurface { const is3d_cells *cells; const double *x, *y; };
 struct RunConfig {
     int operation, mode, hrg_eos, dimension, df_mode, include_baryon, include_bulk, include_shear, include_diff, regulate, outflow;
     // optional keys (absent: 0); an `is set` flag here has passed its checks
-    bool do_decays, decay_sampled, bin_on_device, bin_fused, vah_oversample, vah_bin_on_device, vah_sampler, test_sampler, bin_decayed, flow;
+    bool do_decays, decay_sampled, bin_on_device, bin_fused, vah_oversample, vah_bin_on_device, vah_sampler, test_sampler, bin_decayed, flow, pairs;
+    is3d_pair_bins pair_bins;   // test_sampler_pairs = 1: pairs_y_cut, pairs_pT_min, pairs_pT_max, pairs_y_bins, pairs_phi_bins (defaults 2.0, 0.2, 3.0, 32, 32)
     is3d_flow_cuts flow_cuts;   // test_sampler_flow = 1: flow_y_cut, flow_y_gap, flow_pT_min, flow_pT_max (defaults 1.0, 0.5, 0.2, 3.0)
     bool vah;               // mode 2 from files: the anisotropic-hydro surface, tables and routines
     bool feqmod;            // df_mode 3 / 4 of viscous hydro: the modified-equilibrium kernels
@@ -199,6 +201,7 @@ static int parse_config(const RunParams &p, const MemSurface *mem, bool wants_re
     c.bin_fused = is_set("test_sampler_fused"); c.vah_sampler = is_set("vah_sampler"); c.vah_oversample = is_set("vah_oversample");
     c.vah_bin_on_device = is_set("vah_sampler_on_device"); c.bin_decayed = is_set("test_sampler_decayed");
     c.flow = is_set("test_sampler_flow");
+    c.pairs = is_set("test_sampler_pairs");
     // test_sampler is a sampler key: optional where a check only looks at it, required (with the missing-key message) where a key depends on it
     const bool has_test_sampler = p.optional("test_sampler", &v);
     c.test_sampler = has_test_sampler && (int)v != 0;
@@ -354,6 +357,46 @@ static int parse_config(const RunParams &p, const MemSurface *mem, bool wants_re
             struct stat sb;
             if (stat(dir, &sb) != 0 || !S_ISDIR(sb.st_mode))
                 DIE("test_sampler_flow = 1: the directory %s is missing; create it or set test_sampler_flow = 0", dir);
+        }
+    }
+    // test_sampler_pairs = 1: the two-particle (delta y, delta phi) correlations of the same hadrons under results/pairs/
+    // (results/decayed/pairs/), refused in the situations that refuse test_sampler_flow, and for bad bins and missing directories
+    if (c.pairs) {
+        if (operation != 2)
+            DIE("test_sampler_pairs = 1 with operation = %d: it correlates the sampler's hadrons (operation = 2); set test_sampler_pairs = 0", operation);
+        if (need_test_sampler()) return IS3D_EINVAL;
+        if (!c.test_sampler)
+            DIE("test_sampler_pairs = 1 with test_sampler = 0: it writes the pair correlations beside the test_sampler distributions; set test_sampler_pairs = 0");
+        if (vah)
+            DIE("test_sampler_pairs = 1 with mode = 2: it correlates the viscous-hydro sampler's hadrons; the anisotropic-hydro sampler has no such entry; set test_sampler_pairs = 0");
+        if (wants_result)
+            DIE("test_sampler_pairs = 1: the embedding entry returns the particle list, which this path never holds; set test_sampler_pairs = 0");
+        if (!c.bin_on_device)
+            DIE("test_sampler_pairs = 1 with test_sampler_on_device = 0: the occupancies are made where each event batch is binned, on the device "
+                "(test_sampler_on_device = 1); set test_sampler_pairs = 0");
+        if (c.bin_fused)
+            DIE("test_sampler_pairs = 1 with test_sampler_fused = 1: the fused pass never holds the batch of hadrons that is counted; set test_sampler_pairs = 0");
+        is3d_pair_bins &b = c.pair_bins;
+        b = is3d_pair_bins{2.0, 0.2, 3.0, 32, 32};
+        double ny = 32.0, nphi = 32.0;
+        p.optional("pairs_y_cut", &b.y_cut); p.optional("pairs_pt_min", &b.pT_min); p.optional("pairs_pt_max", &b.pT_max);
+        p.optional("pairs_y_bins", &ny); p.optional("pairs_phi_bins", &nphi);
+        const bool whole = ny >= 1.0 && ny <= 64.0 && ny == (double)(int)ny && nphi >= 4.0 && nphi <= 64.0 && nphi == (double)(int)nphi && (int)nphi % 4 == 0;
+        b.n_y = whole ? (int32_t)ny : 0;
+        b.n_phi = whole ? (int32_t)nphi : 0;
+        // the library's own rule decides (the rapidity edges must come out finite and increasing): an empty list through is3d_pairs_list
+        std::vector<int64_t> w(whole ? (size_t)(2 * (2 * b.n_y - 1) * b.n_phi + 1) : 3);
+        const is3d_pair_hist probe{w.data(), w.data() + (w.size() - 1) / 2, w.data() + w.size() - 1};
+        const int32_t none = -1;
+        if (!whole || is3d_pairs_list(&b, 1, 1, &none, 1, 0, nullptr, &probe) != IS3D_OK)
+            DIE("test_sampler_pairs = 1 with pairs_y_cut = %g, pairs_pT_min = %g, pairs_pT_max = %g, pairs_y_bins = %g, pairs_phi_bins = %g: the bins need "
+                "pairs_y_cut > 0, pairs_pT_max > pairs_pT_min >= 0, 1 <= pairs_y_bins <= 64 and pairs_phi_bins a multiple of 4 in 4..64; set test_sampler_pairs = 0",
+                b.y_cut, b.pT_min, b.pT_max, ny, nphi);
+        for (const char *dir : {"results/pairs", "results/decayed/pairs"}) {
+            if (dir[8] == 'd' && !c.bin_decayed) continue;
+            struct stat sb;
+            if (stat(dir, &sb) != 0 || !S_ISDIR(sb.st_mode))
+                DIE("test_sampler_pairs = 1: the directory %s is missing; create it or set test_sampler_pairs = 0", dir);
         }
     }
     return IS3D_OK;
@@ -824,34 +867,32 @@ static int run_sampler_decayed_binned(const RunConfig &cfg, RunInputs &in, const
     return IS3D_OK;
 }
 
-// test_sampler_flow = 1: after the binned run has written its files, the sampler runs once more on the first device of the run's list with the
-// same seed (the same hadrons: every stream is counter-based) and each event batch goes through cf_sampler_flow -- and, with
-// test_sampler_decayed = 1, through cf_decay_mc_flow with the decay seed of that run.  Slots: pi+, K+, p (211, 321, 2212) where chosen, everything
-// else in one further slot; "all" is written from the merge.  Decayed: the same rule over the chosen species that are stable in the table.
-static int run_sampler_flow(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, SamplerRun &s)
+// labels and the slot of an mc_id, in the order the ids come: a slot of its own for each id of `named`, one further slot "other" for the rest,
+// made when the first such id comes
+struct NamedSlots {
+    std::vector<int64_t> named;
+    std::vector<std::string> label;
+    int other = -1;
+    int of(int64_t id)
+    {
+        for (int64_t k : named)
+            if (id == k) {
+                const std::string l = std::to_string((long long)id);
+                for (size_t j = 0; j < label.size(); j++)
+                    if (label[j] == l) return (int)j;
+                label.push_back(l);
+                return (int)label.size() - 1;
+            }
+        if (other < 0) { other = (int)label.size(); label.push_back("other"); }
+        return other;
+    }
+};
+// the slot maps of a run: thermal over the chosen species; decayed (table read when asked) over the chosen species that are stable in the table
+static int named_slot_maps(const RunConfig &cfg, const RunInputs &in, NamedSlots &th, NamedSlots &de, std::vector<int32_t> &slot,
+                           std::vector<int32_t> &slot_d, DecayTable &tab)
 {
-    static const int64_t named[3] = {211, 321, 2212};
-    // labels and the slot of an mc_id, in the order the ids come; `others` gets its slot when the first such id comes
-    struct Slots {
-        std::vector<std::string> label;
-        int other = -1;
-        int of(int64_t id)
-        {
-            for (int64_t k : named)
-                if (id == k) {
-                    const std::string l = std::to_string((long long)id);
-                    for (size_t j = 0; j < label.size(); j++)
-                        if (label[j] == l) return (int)j;
-                    label.push_back(l);
-                    return (int)label.size() - 1;
-                }
-            if (other < 0) { other = (int)label.size(); label.push_back("other"); }
-            return other;
-        }
-    } th, de;
-    std::vector<int32_t> slot((size_t)in.sp.n), slot_d;
+    slot.assign((size_t)in.sp.n, -1);
     for (int ip = 0; ip < in.sp.n; ip++) slot[(size_t)ip] = th.of(in.mcid[(size_t)ip]);
-    DecayTable tab;
     if (cfg.bin_decayed) {
         if (int rc = read_decay_table(cfg.pdg_path, tab)) return rc;
         slot_d.assign((size_t)tab.view.n, -1);
@@ -862,6 +903,19 @@ static int run_sampler_flow(const RunConfig &cfg, RunInputs &in, const RunDevice
                     break;
                 }
     }
+    return IS3D_OK;
+}
+
+// test_sampler_flow = 1: after the binned run has written its files, the sampler runs once more on the first device of the run's list with the
+// same seed (the same hadrons: every stream is counter-based) and each event batch goes through cf_sampler_flow -- and, with
+// test_sampler_decayed = 1, through cf_decay_mc_flow with the decay seed of that run.  Slots: pi+, K+, p (211, 321, 2212) where chosen, everything
+// else in one further slot; "all" is written from the merge.  Decayed: the same rule over the chosen species that are stable in the table.
+static int run_sampler_flow(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, SamplerRun &s)
+{
+    NamedSlots th{{211, 321, 2212}}, de{{211, 321, 2212}};
+    std::vector<int32_t> slot, slot_d;
+    DecayTable tab;
+    if (int rc = named_slot_maps(cfg, in, th, de, slot, slot_d, tab)) return rc;
     const bool decayed = cfg.bin_decayed && !de.label.empty();
     const int32_t E = s.si.n_events, S = (int32_t)th.label.size(), Sd = (int32_t)de.label.size();
     struct Block {
@@ -899,6 +953,50 @@ static int run_sampler_flow(const RunConfig &cfg, RunInputs &in, const RunDevice
     return IS3D_OK;
 }
 
+// test_sampler_pairs = 1: as run_sampler_flow, the sampler runs once more with the same seed and each event batch goes through cf_pair_cells
+// -- and, with test_sampler_decayed = 1, through cf_decay_mc_pairs -- into occupancies that cf_pair_correlate turns into the same-event and
+// mixed-event histograms after the last batch.  Slots: pi+, pi-, K+, p (211, -211, 321, 2212) where chosen, everything else in one further slot.
+static int run_sampler_pairs(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, SamplerRun &s)
+{
+    NamedSlots th{{211, -211, 321, 2212}}, de{{211, -211, 321, 2212}};
+    std::vector<int32_t> slot, slot_d;
+    DecayTable tab;
+    if (int rc = named_slot_maps(cfg, in, th, de, slot, slot_d, tab)) return rc;
+    const bool decayed = cfg.bin_decayed && !de.label.empty();
+    const int32_t E = s.si.n_events, S = (int32_t)th.label.size(), Sd = (int32_t)de.label.size();
+    const is3d_pair_bins &b = cfg.pair_bins;
+    struct Block {
+        std::vector<int64_t> same, mixed, M;
+        is3d_pair_hist view;
+        Block(const is3d_pair_bins &b, int32_t events, int32_t slots)
+            : same((size_t)slots * (slots + 1) / 2 * (2 * b.n_y - 1) * b.n_phi), mixed(same.size()), M((size_t)events * slots),
+              view{same.data(), mixed.data(), M.data()} {}
+    } ht(b, E, S), hd(b, E, std::max(Sd, 1));
+    is3d_sampler_stats ss{};
+    is3d_decay_mc_stats ms{};
+    int64_t count = 0, n_final = 0, n_unbinned = 0;
+    is3d_options opts = in.opts;
+    opts.device = rd.first();
+    const int rcp = is3d_sample_pairs(&in.cells, &in.sp, &in.df, &s.si, &opts, &b, slot.data(), S, &ht.view, decayed ? &tab.view : nullptr,
+                                      in.mcid.data(), slot_d.data(), Sd, s.si.seed, 0, &hd.view, &count, &n_final, &n_unbinned, &ss, &ms);
+    if (rcp) DIE("is3d_sample_pairs failed (%d): %s", rcp, is3d_last_error());
+    const auto write = [&b](const char *dir, Block &h, const std::vector<std::string> &label) {
+        std::vector<const char *> names;
+        for (const std::string &l : label) names.push_back(l.c_str());
+        return is3d_write_pairs(dir, &b, &h.view, (int32_t)label.size(), names.data());
+    };
+    printf("Writing the pair correlations (%d slots, %d classes)...\n", (int)S, (int)(S * (S + 1) / 2));
+    if (write("results", ht, th.label)) DIE("%s", is3d_last_error());
+    if (decayed) {
+        printf("Writing the pair correlations of the decayed hadrons (%d slots, %d classes)...\n", (int)Sd, (int)(Sd * (Sd + 1) / 2));
+        if (write("results/decayed", hd, de.label)) DIE("%s", is3d_last_error());
+    }
+    printf("pair correlations on the device: %lld hadrons, ms_bin %.3f ms", (long long)count, ss.ms_bin);
+    if (decayed) printf("; decayed: n_final %lld, n_unbinned %lld, ms_bin %.3f ms", (long long)n_final, (long long)n_unbinned, ms.ms_bin);
+    printf("\n");
+    return IS3D_OK;
+}
+
 // ---- operation 2 (emissionfunction.cpp:1522-1554): number of events, sampling, the OSCAR list or the binned test distributions ----
 static int run_sampler(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, RunParams &params, is3d_run_result *res)
 {
@@ -907,7 +1005,9 @@ static int run_sampler(const RunConfig &cfg, RunInputs &in, const RunDevices &rd
     if (int rc = size_sampler_run(cfg, in, s)) return rc;
     if (cfg.bin_decayed || cfg.bin_on_device || cfg.vah_bin_on_device || cfg.bin_fused) {
         if (int rc = cfg.bin_decayed ? run_sampler_decayed_binned(cfg, in, rd, s) : run_sampler_binned(cfg, in, rd, s)) return rc;
-        return cfg.flow ? run_sampler_flow(cfg, in, rd, s) : IS3D_OK;
+        if (cfg.flow)
+            if (int rc = run_sampler_flow(cfg, in, rd, s)) return rc;
+        return cfg.pairs ? run_sampler_pairs(cfg, in, rd, s) : IS3D_OK;
     }
     // count, then fill a list of that size: the viscous-hydro sampler, or (mode 2) the anisotropic-hydro one on the mode-2 cells and tables
     is3d_sampler_stats ss{};
