@@ -1404,6 +1404,108 @@ int is3d_sample_pairs(const is3d_cells *cells, const is3d_species *species, cons
                       const is3d_pair_hist *hist_decayed, int64_t *n_particles, int64_t *n_final, int64_t *n_unbinned,
                       is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats);
 
+/* HBT (femtoscopic) correlation functions of a particle list: the one observable above that reads the freeze-out
+ * POSITIONS (t, x, y, z) of the sampled hadrons.  Identical-particle pairs of ONE event are binned in the pair momentum KT and the
+ * out-side-long components of the relative momentum in the longitudinally comoving frame, and each pair adds cos(q . dx / hbarc) to a
+ * numerator.  This is a true O(M^2) loop per event: the weight depends on both positions.  The rule is csrc/cf_sampler_hbt.h, ONE
+ * statement for host and device, compiled with contraction off; every decision uses only + - * / sqrt and comparisons on numbers the host
+ * computes once (lo = exp(-2 y_cut), hi = exp(2 y_cut), dkT = (kT_max - kT_min) / n_kT, dq = 2 q_max / n_q) and hands over as bits.
+ * Bins are valid when y_cut > 0, pT_max > pT_min >= 0, kT_max > kT_min >= 0, 1 <= n_kT <= 16, q_max > 0, 2 <= n_q <= 64 and lo, hi, dkT,
+ * dq come out finite and positive (NaN: invalid).
+ *   single particle  accepted when E - pz > 0, lo <= (E + pz) / (E - pz) <= hi (one division), pT_min <= sqrt(px^2 + py^2) < pT_max and
+ *                    slot[species] >= 0
+ *   ordered pair     (i, j), i != j, same event, same slot, both accepted; products are rounded one by one, in this order:
+ *     K = (p_i + p_j) / 2, q = p_i - p_j (four components each), KT = sqrt(Kx^2 + Ky^2); rejected unless KT > 0 and kT_min <= KT < kT_max
+ *     ikT = (int)((KT - kT_min) / dkT), clamped to n_kT - 1
+ *     q_o = (qx Kx + qy Ky) / KT, q_s = (qx Ky - qy Kx) / KT
+ *     beta = Kz / K0, g2 = 1 - beta beta; rejected unless g2 > 0; q_l = (qz - beta q0) / sqrt(g2)
+ *     u = (q + q_max) / dq for each of q_o, q_s, q_l; rejected unless 0 <= u < n_q for all three; io, is, il = (int)u
+ *     den[slot][ikT][io][is][il] += 1
+ *     num[slot][ikT][io][is][il] += llrint(cos(phi) 2^32), phi = (((q0 dt - qx dx) - qy dy) - qz dz) / hbarc, dx = x_i - x_j
+ *   M[event][slot]   the accepted single-particle multiplicity
+ * All words are int64, so the sums do not depend on order, batching or kernel form.  cos is the one libm call: it feeds a term, never a
+ * decision, and device and host may differ by one unit per pair there.  A den word above IS3D_SAMPLER_VN_MAX_COUNT is IS3D_EDOMAIN; below
+ * that bound num cannot overflow.  The histograms are NOT additive over pieces of one event (pairs across the pieces are missing).
+ * kernel_form (device entries; the host entries ignore it): 0 the measured choice, 1 global atomics, 2 a workgroup-private histogram of
+ * one slot's n_kT n_q^3 bins in LDS, refused with IS3D_EINVAL naming the word count when it does not fit; every form gives the same bits. */
+typedef struct {
+    double y_cut, pT_min, pT_max, kT_min, kT_max;
+    int32_t n_kT;
+    double q_max;
+    int32_t n_q, kernel_form;
+} is3d_hbt_bins;
+typedef struct {
+    int64_t *num, *den, *M;   /* num, den [n_slots][n_kT][n_q (out)][n_q (side)][n_q (long)]; M [n_events][n_slots] */
+} is3d_hbt_hist;
+/* list -> histograms on the host, as the explicit double loop over the pairs: THE definition, no device use.  slot: int32[n_species],
+ * species -> slot in [0, n_slots), or -1: dropped.  IS3D_EINVAL: a NULL, n_events, n_slots or n_species < 1, bad bins, a slot outside
+ * [-1, n_slots), a particle whose species or event is out of range.  hist is overwritten. */
+int is3d_hbt_list(const is3d_hbt_bins *bins, int32_t n_events, int32_t n_slots, const int32_t *slot, int32_t n_species,
+                  int64_t n_particles, const is3d_particle *particles, const is3d_hbt_hist *hist);
+/* list -> histograms on the DEVICE: a caller's HOST list (any order) is uploaded; cf_hbt_select (thread <-> particle) applies the
+ * single-particle rule and writes the accepted particles as compact 64-byte records (E, px, py, pz, t, x, y, z) into per-(event, slot)
+ * segments (count, scan, fill with a per-segment cursor); cf_hbt_pairs (workgroup <-> (segment, tile of 256 i, run of j tiles); a thread
+ * owns one i, the j tiles are staged in LDS) applies the pair rule.  A particle whose species or event is out of range adds nothing and
+ * is counted in *n_skipped.  The refusals above (but that one) and kernel_form come before any device use; a good call without a device
+ * is IS3D_ENODEVICE; a block that cannot be allocated is IS3D_ENOMEM naming its size.  n_particles = 0: zero histograms, no launch.
+ * device < 0: the current device. */
+int is3d_hbt_list_device(const is3d_hbt_bins *bins, int32_t n_events, int32_t n_slots, const int32_t *slot, int32_t n_species,
+                         int64_t n_particles, const is3d_particle *particles, const is3d_hbt_hist *hist, int64_t *n_skipped,
+                         int32_t device);
+/* Radii from the exact integers, on the host.  Per (slot, kT bin): c = num / (den 2^32) in every q bin with den >= min_pairs and
+ * c >= c_min > 0; a weighted linear least-squares fit (weights den c^2, normal equations in long double) of
+ *   ln c = ln lambda - (R_o^2 q_o^2 + R_s^2 q_s^2 + R_l^2 q_l^2 + 2 R_os^2 q_o q_s + 2 R_ol^2 q_o q_l + 2 R_sl^2 q_s q_l) / hbarc^2
+ * at the bin centres q = -q_max + (k + 1/2) dq.  R2 holds R_o^2, R_s^2, R_l^2, R_os^2, R_ol^2, R_sl^2 in fm^2 (not their roots), n_bins the
+ * number of bins used; singular = 1 (lambda and R2 zero) when the 7 x 7 system has no solution (fewer than 7 bins among them).
+ * hist->M is not read.  IS3D_EINVAL: a NULL, bad bins, n_slots < 1, min_pairs < 1, c_min not > 0. */
+typedef struct {
+    double lambda, R2[6];
+    int32_t n_bins, singular;
+} is3d_hbt_radii_result;
+int is3d_hbt_radii(const is3d_hbt_bins *bins, const is3d_hbt_hist *hist, int32_t n_slots, int64_t min_pairs, double c_min,
+                   is3d_hbt_radii_result *out /* [n_slots][n_kT] */);
+/* Writes, per slot s and kT bin k, <results_dir>/hbt/correlation_<labels[s]>_kT<k>.dat: two comment lines (the bins; the kT range and the
+ * totals), then a row per q bin: the q_o, q_s, q_l centres, den, C = 1 + num / (den 2^32) (1 where den is 0), tab separated; and per slot
+ * <results_dir>/hbt/radii_<labels[s]>.dat: a row per kT bin: the kT centre, lambda, the six R^2, n_bins, singular (the fit of
+ * is3d_hbt_radii with min_pairs and c_min).  Doubles by std::to_chars(scientific, 8), integers in full.  The hbt/ directory must exist
+ * (IS3D_EIO otherwise); a NULL, an empty label or one with a '/', bad bins and n_slots < 1 are IS3D_EINVAL. */
+int is3d_write_hbt(const char *results_dir, const is3d_hbt_bins *bins, const is3d_hbt_hist *hist, int32_t n_slots,
+                   const char *const *labels, int64_t min_pairs, double c_min);
+/* The HBT histograms of a list AFTER its Monte Carlo decays, without the decayed list.  Definition: is3d_hbt_list(bins, n_events, n_slots,
+ * slot, table->n, ...) on the list that is3d_decay_particles returns for the same (table, chosen_mc_id, in, particles): den and M equal,
+ * num within one unit per pair.  How: the decay loop runs twice over the same counter-based stream, first with a sink that counts the
+ * accepted finals per (event, slot), then with a sink that writes their compact records; then cf_hbt_pairs.  Device memory holds the
+ * accepted records, never the decayed list.  With in->lifetime = 1 a parent flies before its daughters are born, which is what the
+ * positions record.  slot: int32[table->n].  *n_final is the length of the decayed list, *n_unbinned = *n_final - sum of M.  IS3D_EINVAL
+ * before any device use: every refusal of is3d_decay_particles; the refusals of is3d_hbt_list_device with the table's entries as species; a
+ * primary whose event is outside [0, n_events).  n_particles = 0: zero histograms, no launch. */
+int is3d_decay_particles_hbt(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
+                             const is3d_decay_mc_inputs *in, int64_t n_particles, const is3d_particle *particles,
+                             const int32_t *slot, int32_t n_slots, const is3d_hbt_bins *bins, int32_t n_events,
+                             const is3d_hbt_hist *hist, int64_t *n_final, int64_t *n_unbinned,
+                             is3d_decay_mc_stats *stats /* may be NULL */);
+/* is3d_sampler_plan_execute with the list of each event batch selected and paired on the device and discarded: an event lies whole in one
+ * batch, so each batch is complete for its events; the histograms stay on the device across batches and are copied once at the end.
+ *   hist          = is3d_hbt_list of the list is3d_sampler_plan_execute returns for the same arguments
+ *   hist_decayed  = is3d_decay_particles_hbt of that list with first_particle = 0, seed = decay_seed
+ * independent of batch_events, bit for bit.  table_dev == NULL: slot_decayed, hist_decayed, n_final, n_unbinned and decay_stats are not
+ * used.  The plan serves its other entries in any order, as before.  IS3D_EINVAL before any device use: the refusals of
+ * is3d_hbt_list_device for either result, a table of another chosen count or device.  Not offered: the fused sample-and-bin pass, the
+ * anisotropic-hydro sampler, several devices. */
+int is3d_sampler_plan_execute_hbt(is3d_sampler_plan *plan, const is3d_cells *cells_dev, const double *x_dev, const double *y_dev,
+                                  int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events, const is3d_hbt_bins *bins,
+                                  const int32_t *slot, int32_t n_slots, const is3d_hbt_hist *hist_host,
+                                  const is3d_decay_mc_table *table_dev /* may be NULL */, const int32_t *slot_decayed, int32_t n_slots_decayed,
+                                  uint64_t decay_seed, int32_t lifetime, const is3d_hbt_hist *hist_decayed, int64_t *n_particles,
+                                  int64_t *n_final, int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats);
+/* host-pointer one-shot for the viscous sampler: plan and table create, upload, execute, destroy.  table may be NULL. */
+int is3d_sample_hbt(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                    const is3d_options *opts, const is3d_hbt_bins *bins, const int32_t *slot, int32_t n_slots,
+                    const is3d_hbt_hist *hist, const is3d_decay_table *table /* may be NULL */, const int64_t *chosen_mc_id,
+                    const int32_t *slot_decayed, int32_t n_slots_decayed, uint64_t decay_seed, int32_t lifetime,
+                    const is3d_hbt_hist *hist_decayed, int64_t *n_particles, int64_t *n_final, int64_t *n_unbinned,
+                    is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats);
+
 /* ---------------------------------------------------------------------------------------------
  * Driver: IS3D::run_particlization (src/cpp/iS3D.cpp:74-192; class IS3D, src/cpp/iS3D.h:19-96).  Reads iS3D_parameters.dat,
  * PDG/, tables/, deltaf_coefficients/ from the current directory and writes results/ exactly as the command line tool does

@@ -126,6 +126,8 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_sampler_plan_execute_flow", "is3d_sample_flow", "is3d_write_flow",
            "is3d_pairs_list", "is3d_pairs_list_device", "is3d_pairs_correlation", "is3d_write_pairs", "is3d_decay_particles_pairs",
            "is3d_sampler_plan_execute_pairs", "is3d_sample_pairs",
+           "is3d_hbt_list", "is3d_hbt_list_device", "is3d_hbt_radii", "is3d_write_hbt", "is3d_decay_particles_hbt",
+           "is3d_sampler_plan_execute_hbt", "is3d_sample_hbt",
            "is3d_smooth_spectra_vah_multi", "is3d_vah_plan_observables",
            "is3d_spacetime_distributions_vah", "is3d_vah_plan_execute_spacetime",
            "is3d_sample_particles_vah", "is3d_sample_particles_vah_multi", "is3d_sample_binned_vah", "is3d_sample_binned_vah_multi",
@@ -1212,6 +1214,28 @@ def decay_particles_pairs(table, chosen_mc_id, particles, slot, n_slots, bins, n
     return out, _check_decayed(rc, st, nf, nu, hist=out)
 
 
+def decay_particles_hbt(table, chosen_mc_id, particles, slot, n_slots, bins, n_events, seed=1, first_particle=0, lifetime=0, device=-1):
+    """is3d_decay_particles_hbt: a sampled list decayed on the device twice over one stream (count, fill) into compact records of the accepted
+    final particles, which are paired -- the histograms of hbt_list on decay_particles' list (species = table entries) with the same slot
+    map: den and M equal, num within one unit per pair.  slot: int32 per table entry.  Returns (hist dict, stats dict with n_final,
+    n_unbinned and the tallies of decay_particles)."""
+    L = load()
+    ts, ch, _, keep = _decay_pack(table, chosen_mc_id, dict(pT=[1.0], phi=[0.0], y=[0.0]))
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    slot = _slot_map(table, slot)
+    inp = DecayMcInputs(int(seed), int(first_particle), int(lifetime), int(device))
+    b = _pack_hbt_bins(bins)
+    h, out = _hbt_arrays(b, n_events, n_slots)
+    st, nf, nu = DecayMcStats(), C.c_int64(0), C.c_int64(0)
+    L.is3d_decay_particles_hbt.argtypes = [C.POINTER(DecayTable), C.c_int32, C.POINTER(C.c_int64), C.POINTER(DecayMcInputs), C.c_int64, C.c_void_p,
+                                           C.c_void_p, C.c_int32, C.POINTER(HbtBins), C.c_int32, C.POINTER(HbtHist),
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(DecayMcStats)]
+    rc = L.is3d_decay_particles_hbt(C.byref(ts), len(ch), ch.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(inp), len(particles),
+                                    particles.ctypes.data, slot.ctypes.data, int(n_slots), C.byref(b), int(n_events), C.byref(h), C.byref(nf),
+                                    C.byref(nu), C.byref(st))
+    return out, _check_decayed(rc, st, nf, nu, hist=out)
+
+
 def shard_bounds(n_cells, rank, n_ranks):
     """is3d_shard_bounds: the contiguous cell shard [lo, hi) of `rank` (what is3d_smooth_spectra_multi uses)."""
     lo, hi = C.c_int64(), C.c_int64()
@@ -1979,6 +2003,39 @@ class SamplerPlan:
         dd = _check_decayed(rc, dst, nf, nu, hist=out, hist_decayed=outd, sampler_stats=d)
         return out, outd, d, dd
 
+    def execute_hbt(self, n_cells, dev_ptrs, n_events, seed, bins, slot, n_slots, table=None, slot_decayed=None, n_slots_decayed=0,
+                    decay_seed=None, lifetime=0, x_ptr=0, y_ptr=0, first_cell=0, batch_events=0):
+        """is3d_sampler_plan_execute_hbt: the HBT histograms of the list execute returns (slot: int32 per species of the plan) and, with
+        table (a DecayMcTable on the plan's device), of its Monte Carlo decay products (slot_decayed: int32 per table entry).
+        -> (hist, sampler stats) | (hist, decayed hist, sampler stats, decay stats with n_final and n_unbinned)."""
+        cs = Cells()
+        cs.n_cells = int(n_cells)
+        for f in CELL_FIELDS:
+            if dev_ptrs.get(f):
+                setattr(cs, f, int(dev_ptrs[f]))
+        b = _pack_hbt_bins(bins)
+        slot = np.ascontiguousarray(slot, dtype=np.int32)
+        h, out = _hbt_arrays(b, n_events, n_slots)
+        hd, outd = _hbt_arrays(b, n_events, n_slots_decayed if table is not None else 0)
+        sd = _slot_map(table.table, slot_decayed) if table is not None else None
+        cnt, st, dst, nf, nu = C.c_int64(0), SamplerStats(), DecayMcStats(), C.c_int64(0), C.c_int64(0)
+        fn = load().is3d_sampler_plan_execute_hbt
+        fn.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(HbtBins),
+                       C.c_void_p, C.c_int32, C.POINTER(HbtHist), C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int32,
+                       C.POINTER(HbtHist), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(SamplerStats),
+                       C.POINTER(DecayMcStats)]
+        rc = fn(self._h, C.byref(cs), C.c_void_p(int(x_ptr) or None), C.c_void_p(int(y_ptr) or None), int(n_events), int(seed), int(first_cell),
+                int(batch_events), C.byref(b), slot.ctypes.data, int(n_slots), C.byref(h), table._h if table is not None else None,
+                sd.ctypes.data if sd is not None else None, int(n_slots_decayed), int(seed if decay_seed is None else decay_seed), int(lifetime),
+                C.byref(hd) if table is not None else None, C.byref(cnt), C.byref(nf), C.byref(nu), C.byref(st), C.byref(dst))
+        d = st.as_dict()
+        d["n_particles"] = int(cnt.value)
+        if table is None:
+            _check(rc)
+            return out, d
+        dd = _check_decayed(rc, dst, nf, nu, hist=out, hist_decayed=outd, sampler_stats=d)
+        return out, outd, d, dd
+
     def execute_fused(self, n_cells, dev_ptrs, n_events, seed, bins, n_species, x_ptr=0, y_ptr=0, first_cell=0, batch_events=0):
         """is3d_sampler_plan_execute_fused: execute_binned's arguments and result, every hadron binned where it is sampled (no list, no
         particle workspace: stats["particle_workspace_bytes"] == 0)."""
@@ -2392,6 +2449,110 @@ def write_pairs(results_dir, bins, hist, labels):
     _check(L.is3d_write_pairs(results_dir.encode(), C.byref(b), C.byref(h), n_slots, names))
 
 
+HBT_BINS = dict(y_cut=0.5, pT_min=0.1, pT_max=1.5, kT_min=0.1, kT_max=0.9, n_kT=4, q_max=0.1, n_q=20, kernel_form=0)   # the run driver's defaults
+
+
+class HbtBins(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ["y_cut", "pT_min", "pT_max", "kT_min", "kT_max"]] + [("n_kT", C.c_int32), ("q_max", C.c_double),
+                                                                                              ("n_q", C.c_int32), ("kernel_form", C.c_int32)]
+
+
+class HbtHist(C.Structure):
+    _fields_ = [(n, C.POINTER(C.c_int64)) for n in ["num", "den", "M"]]
+
+
+class HbtRadii(C.Structure):
+    _fields_ = [("lambda_", C.c_double), ("R2", C.c_double * 6), ("n_bins", C.c_int32), ("singular", C.c_int32)]
+
+
+HBT_R2 = ("oo", "ss", "ll", "os", "ol", "sl")   # the order of R2
+
+
+def _pack_hbt_bins(bins):
+    if isinstance(bins, HbtBins):
+        return bins
+    b = HbtBins()
+    for k, v in bins.items():
+        setattr(b, k, v)
+    return b
+
+
+def _hbt_arrays(b, n_events, n_slots, hist=None):
+    """is3d_hbt_hist over numpy int64 arrays: (struct, dict).  hist = None: fresh zero arrays num and den [slot][n_kT][n_q][n_q][n_q] and
+    M [event][slot] (shaped for valid bins; a refusal never writes them); otherwise the caller's arrays are checked and used."""
+    E, S = max(int(n_events), 0), max(int(n_slots), 0)
+    nk, nq = min(max(int(b.n_kT), 1), 16), min(max(int(b.n_q), 1), 64)
+    shapes = dict(num=(S, nk, nq, nq, nq), den=(S, nk, nq, nq, nq), M=(E, S))
+    out = {}
+    for k, shp in shapes.items():
+        if hist is None:
+            out[k] = np.zeros(shp, dtype=np.int64)
+        else:
+            out[k] = np.ascontiguousarray(hist[k], dtype=np.int64)
+            assert out[k].shape == shp, (k, out[k].shape, shp)
+    h = HbtHist(*[out[k].ctypes.data_as(C.POINTER(C.c_int64)) for k, _ in HbtHist._fields_])
+    return h, out
+
+
+def hbt_list(bins, n_events, n_slots, slot, particles):
+    """is3d_hbt_list: a particle list -> the HBT histograms on the host, as the explicit double loop over the ordered identical-particle
+    pairs of each event (the definition; no device use).  slot: int32 per species, -1 drops the species.  Returns a dict of int64 arrays
+    num, den [slot][n_kT][n_q out][n_q side][n_q long] and M [event][slot]; the correlation is c = num / (den 2^32)."""
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    slot = np.ascontiguousarray(slot, dtype=np.int32)
+    b = _pack_hbt_bins(bins)
+    h, out = _hbt_arrays(b, n_events, n_slots)
+    L = load()
+    L.is3d_hbt_list.argtypes = [C.POINTER(HbtBins), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(HbtHist)]
+    _check(L.is3d_hbt_list(C.byref(b), int(n_events), int(n_slots), slot.ctypes.data, len(slot), len(particles), particles.ctypes.data, C.byref(h)))
+    return out
+
+
+def hbt_list_device(bins, n_events, n_slots, slot, particles, device=0):
+    """is3d_hbt_list_device: a host particle list through the device kernels cf_hbt_select and cf_hbt_pairs (form bins["kernel_form"]).
+    Returns (hist, n_skipped); n_skipped counts the particles whose species or event is out of range, which add nothing."""
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    slot = np.ascontiguousarray(slot, dtype=np.int32)
+    b = _pack_hbt_bins(bins)
+    h, out = _hbt_arrays(b, n_events, n_slots)
+    skipped = C.c_int64(0)
+    L = load()
+    L.is3d_hbt_list_device.argtypes = [C.POINTER(HbtBins), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(HbtHist),
+                                       C.POINTER(C.c_int64), C.c_int32]
+    _check(L.is3d_hbt_list_device(C.byref(b), int(n_events), int(n_slots), slot.ctypes.data, len(slot), len(particles), particles.ctypes.data,
+                                  C.byref(h), C.byref(skipped), int(device)))
+    return out, int(skipped.value)
+
+
+def hbt_radii(bins, hist, min_pairs=1, c_min=1e-3):
+    """is3d_hbt_radii: per (slot, kT bin) the weighted log-linear fit of c = num / (den 2^32) over the bins with den >= min_pairs and
+    c >= c_min.  Returns a dict: lambda [slot][n_kT], R2 [slot][n_kT][6] in fm^2 in the order HBT_R2, n_bins and singular [slot][n_kT]."""
+    b = _pack_hbt_bins(bins)
+    n_slots = np.shape(hist["den"])[0]
+    h, _keep = _hbt_arrays(b, np.shape(hist["M"])[0], n_slots, hist)
+    n = max(n_slots * int(b.n_kT), 1)
+    res = (HbtRadii * n)()
+    L = load()
+    L.is3d_hbt_radii.argtypes = [C.POINTER(HbtBins), C.POINTER(HbtHist), C.c_int32, C.c_int64, C.c_double, C.POINTER(HbtRadii)]
+    _check(L.is3d_hbt_radii(C.byref(b), C.byref(h), n_slots, int(min_pairs), float(c_min), res))
+    shp = (n_slots, int(b.n_kT))
+    return {"lambda": np.array([r.lambda_ for r in res][:shp[0] * shp[1]]).reshape(shp),
+            "R2": np.array([list(r.R2) for r in res][:shp[0] * shp[1]]).reshape(shp + (6,)),
+            "n_bins": np.array([r.n_bins for r in res][:shp[0] * shp[1]], dtype=np.int64).reshape(shp),
+            "singular": np.array([r.singular for r in res][:shp[0] * shp[1]], dtype=np.int64).reshape(shp)}
+
+
+def write_hbt(results_dir, bins, hist, labels, min_pairs=1, c_min=1e-3):
+    """is3d_write_hbt: <results_dir>/hbt/correlation_<label>_kT<k>.dat per slot and kT bin and radii_<label>.dat per slot."""
+    b = _pack_hbt_bins(bins)
+    n_slots = len(labels)
+    h, _keep = _hbt_arrays(b, np.shape(hist["M"])[0], n_slots, hist)
+    names = (C.c_char_p * n_slots)(*[str(x).encode() for x in labels])
+    L = load()
+    L.is3d_write_hbt.argtypes = [C.c_char_p, C.POINTER(HbtBins), C.POINTER(HbtHist), C.c_int32, C.POINTER(C.c_char_p), C.c_int64, C.c_double]
+    _check(L.is3d_write_hbt(results_dir.encode(), C.byref(b), C.byref(h), n_slots, names, int(min_pairs), float(c_min)))
+
+
 def write_sampler_tests_binned(results_dir, bins, n_events, mc_id, hist, mean_yield=0.0):
     """is3d_write_sampler_tests_binned: the test_sampler = 1 files from a dict of int64 histograms."""
     ids = np.ascontiguousarray(mc_id, dtype=np.int64)
@@ -2503,6 +2664,43 @@ def sample_pairs(cells, species, df, gla, bins, slot, n_slots, opts=None, table=
     fn.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options), C.POINTER(PairBins),
                    C.c_void_p, C.c_int32, C.POINTER(PairHist), C.POINTER(DecayTable), C.POINTER(C.c_int64), C.c_void_p, C.c_int32, C.c_uint64,
                    C.c_int32, C.POINTER(PairHist), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(SamplerStats),
+                   C.POINTER(DecayMcStats)]
+    rc = fn(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), C.byref(b), slot.ctypes.data, int(n_slots), C.byref(h),
+            C.byref(ts) if ts is not None else None, ch.ctypes.data_as(C.POINTER(C.c_int64)) if ch is not None else None,
+            sd.ctypes.data if sd is not None else None, int(n_slots_decayed), int(seed if decay_seed is None else decay_seed), int(lifetime),
+            C.byref(hd) if table is not None else None, C.byref(cnt), C.byref(nf), C.byref(nu), C.byref(st), C.byref(dst))
+    d = st.as_dict()
+    d["n_particles"] = int(cnt.value)
+    if table is None:
+        _check(rc)
+        return out, d
+    dd = _check_decayed(rc, dst, nf, nu, hist=out, hist_decayed=outd, sampler_stats=d)
+    return out, outd, d, dd
+
+
+def sample_hbt(cells, species, df, gla, bins, slot, n_slots, opts=None, table=None, chosen_mc_id=None, slot_decayed=None, n_slots_decayed=0,
+               n_events=1, seed=1, decay_seed=None, lifetime=0, y_cut=0.5, first_cell=0, fq=None, fast=0, T_avg=0.0, T_avg_switch=0.0,
+               batch_events=0, muB_avg=0.0):
+    """is3d_sample_hbt: the viscous sampler with every event batch selected and paired on the device (slot: int32 per species) and, with
+    table (pdg_read_decays' dict; chosen_mc_id: the mc_id of the species list), decayed and paired again by slot_decayed (int32 per table
+    entry).  Returns (hist, sampler stats) | (hist, decayed hist, sampler stats, decay stats)."""
+    cs, sps, ds, si, os_, _held = _pack_sampler(cells, species, df, gla, opts, n_events, seed, y_cut, first_cell, fq, fast, T_avg, T_avg_switch,
+                                                batch_events, muB_avg)
+    b = _pack_hbt_bins(bins)
+    slot = np.ascontiguousarray(slot, dtype=np.int32)
+    assert len(slot) == sps.n, (len(slot), sps.n)
+    h, out = _hbt_arrays(b, n_events, n_slots)
+    hd, outd = _hbt_arrays(b, n_events, n_slots_decayed if table is not None else 0)
+    ts = ch = sd = None
+    if table is not None:
+        ts, ch, _, keep = _decay_pack(table, chosen_mc_id, dict(pT=[1.0], phi=[0.0], y=[0.0]))
+        assert len(ch) == sps.n, (len(ch), sps.n)
+        sd = _slot_map(table, slot_decayed)
+    cnt, st, dst, nf, nu = C.c_int64(0), SamplerStats(), DecayMcStats(), C.c_int64(0), C.c_int64(0)
+    fn = load().is3d_sample_hbt
+    fn.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options), C.POINTER(HbtBins),
+                   C.c_void_p, C.c_int32, C.POINTER(HbtHist), C.POINTER(DecayTable), C.POINTER(C.c_int64), C.c_void_p, C.c_int32, C.c_uint64,
+                   C.c_int32, C.POINTER(HbtHist), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(SamplerStats),
                    C.POINTER(DecayMcStats)]
     rc = fn(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), C.byref(b), slot.ctypes.data, int(n_slots), C.byref(h),
             C.byref(ts) if ts is not None else None, ch.ctypes.data_as(C.POINTER(C.c_int64)) if ch is not None else None,

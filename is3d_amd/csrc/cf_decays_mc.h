@@ -8,6 +8,7 @@
 #include "cf_sampler_bins.h"
 #include "cf_sampler_flow.h"
 #include "cf_sampler_pairs.h"
+#include "cf_sampler_hbt.h"
 
 namespace is3d {
 
@@ -71,6 +72,20 @@ struct DecayMcPairRun {
 };
 // as decay_mc_bins_launch, every final particle going to the rule of cf_sampler_pairs.h and making ONE occupancy add
 hipError_t decay_mc_pairs_launch(const DecayMcPairRun &r, const is3d_particle *primaries_dev, int64_t n, int64_t first_particle);
+// A decayed run into HBT records (cf_sampler_hbt.h): the slot map as above; every final particle goes to the single-particle rule and an
+// accepted one to hbt_select_put of `run` -- the count pass (fill = false, which also adds the tallies to tally_dev
+// [kDecayMcBinTallies 64-bit words]) or the fill pass over the same counter-based stream, which sees the same finals
+struct DecayMcHbtRun {
+    const is3d_decay_mc_table *table;
+    const int32_t *slot_dev;
+    uint64_t seed;
+    int32_t lifetime;
+    unsigned long long *tally_dev;
+};
+hipError_t decay_mc_hbt_launch(const DecayMcHbtRun &r, const HbtRun &run, const is3d_particle *primaries_dev, int64_t n, int64_t first_particle,
+                               bool fill);
+// a whole batch: batch_begin, the count pass, batch_plan, the fill pass, batch_pairs
+int decay_mc_hbt_batch(const DecayMcHbtRun &r, HbtRun &run, const is3d_particle *primaries_dev, int64_t n, int64_t first_particle);
 // the tallies of a finished run (HOST copy of the tally words) into stats; IS3D_EINVAL if a pending stack overflowed
 int decay_mc_bins_tallies(const unsigned long long *tally, is3d_decay_mc_stats *stats);
 // the static part of the stats: what the table analysis found

@@ -418,6 +418,47 @@ __global__ void __launch_bounds__(kBinThreads) cf_decay_mc_pairs(const McArgs a,
     if (threadIdx.x < kBinTallies && blk[threadIdx.x]) atomicAdd(&f.tally[threadIdx.x], blk[threadIdx.x]);
 }
 
+// the HBT passes: the final particle's momentum goes to the single-particle rule of cf_sampler_hbt.h with slot[entry]; an accepted one is
+// counted (count pass) or written as a compact record with its position at the cursor of its (event, slot) segment (fill pass)
+struct McHbtArgs {
+    is3d::HbtSelectArgs s;
+    const int32_t *slot;              // [table entries]
+    unsigned long long *tally;        // tally[kBinTallies], count pass
+};
+struct SinkHbt {
+    static constexpr bool kMomenta = true;
+    const McHbtArgs &f;
+    bool live;
+    __device__ __forceinline__ void operator()(int, const Pending &c, const is3d_particle &q)
+    {
+        const int s = f.slot[c.e];
+        if (!live || s < 0 || s >= f.s.n_slots) return;
+        if (!is3d::hbt_accept(f.s.b, f.s.d, c.E, c.px, c.py, c.pz)) return;
+        is3d::hbt_select_put(f.s, q.event, s, is3d::HbtRecord{c.E, c.px, c.py, c.pz, c.t, c.x, c.y, c.z});
+    }
+};
+
+// thread <-> primary in a grid-stride walk; the count pass (FILL = false) adds the tallies through six static LDS words as cf_decay_mc_bins
+template <bool FILL>
+__global__ void __launch_bounds__(kBinThreads) cf_decay_mc_hbt(const McArgs a, const McHbtArgs f)
+{
+    __shared__ unsigned long long blk[kBinTallies];
+    if (threadIdx.x < kBinTallies) blk[threadIdx.x] = 0ULL;
+    __syncthreads();
+    unsigned long long tally[kTallies] = {0ULL, 0ULL, 0ULL, 0ULL, 0ULL}, finals = 0ULL;
+    for (int64_t i = (int64_t)blockIdx.x * kBinThreads + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kBinThreads) {
+        const int event = a.in[i].event;
+        SinkHbt sink{f, event >= 0 && event < f.s.n_events};
+        finals += (unsigned long long)decay_tree(a, i, tally, sink);
+    }
+    if (FILL) return;
+    for (int k = 0; k < kTallies; k++)
+        if (tally[k]) atomicAdd(&blk[k], tally[k]);
+    if (finals) atomicAdd(&blk[kTallies], finals);
+    __syncthreads();
+    if (threadIdx.x < kBinTallies && blk[threadIdx.x]) atomicAdd(&f.tally[threadIdx.x], blk[threadIdx.x]);
+}
+
 struct Widen {
     __host__ __device__ int64_t operator()(int32_t v) const { return (int64_t)v; }
 };
@@ -1049,4 +1090,100 @@ extern "C" int is3d_decay_particles_pairs(const is3d_decay_table *table, int32_t
     if (stats) *stats = st;
     if (rc) return rc;
     return is3d::pair_hist_check(hist, n_events, n_slots);
+}
+
+// ---- decayed into HBT histograms: the decay loop twice (count, fill) into compact records, then cf_hbt_pairs ----
+hipError_t is3d::decay_mc_hbt_launch(const DecayMcHbtRun &r, const HbtRun &run, const is3d_particle *primaries_dev, int64_t n, int64_t first_particle,
+                                     bool fill)
+{
+    if (n <= 0) return hipSuccess;
+    McArgs a{};
+    a.t = r.table->dev();
+    a.chosen_entry = r.table->d_chosen.p;
+    a.in = primaries_dev;
+    a.n = n;
+    a.first = first_particle;
+    a.seed = r.seed;
+    a.lifetime = r.lifetime;
+    const McHbtArgs f{is3d::hbt_select_args(run, fill), r.slot_dev, r.tally_dev};
+    const int64_t trips = (n + kBinThreads - 1) / kBinThreads;
+    const dim3 grid((unsigned)std::min<int64_t>(trips, (int64_t)1 << 20));
+    if (fill)
+        hipLaunchKernelGGL(cf_decay_mc_hbt<true>, grid, dim3(kBinThreads), 0, nullptr, a, f);
+    else
+        hipLaunchKernelGGL(cf_decay_mc_hbt<false>, grid, dim3(kBinThreads), 0, nullptr, a, f);
+    return hipGetLastError();
+}
+
+int is3d::decay_mc_hbt_batch(const DecayMcHbtRun &r, HbtRun &run, const is3d_particle *primaries_dev, int64_t n, int64_t first_particle)
+{
+    if (n <= 0) return IS3D_OK;
+    if (int rc = run.batch_begin()) return rc;
+    HIP_TRY(decay_mc_hbt_launch(r, run, primaries_dev, n, first_particle, false));
+    if (int rc = run.batch_plan()) return rc;
+    HIP_TRY(decay_mc_hbt_launch(r, run, primaries_dev, n, first_particle, true));
+    return run.batch_pairs();
+}
+
+extern "C" int is3d_decay_particles_hbt(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
+                                        const is3d_decay_mc_inputs *in, int64_t n_particles, const is3d_particle *particles,
+                                        const int32_t *slot, int32_t n_slots, const is3d_hbt_bins *bins, int32_t n_events,
+                                        const is3d_hbt_hist *hist, int64_t *n_final, int64_t *n_unbinned, is3d_decay_mc_stats *stats)
+{
+    if (!table || !chosen_mc_id || !in || !n_final || !n_unbinned)
+        return set_error(IS3D_EINVAL, "table, chosen_mc_id, in, n_final and n_unbinned are required");
+    *n_final = *n_unbinned = 0;
+    if (int rc = check_list_head(n_chosen, n_particles, particles)) return rc;
+    is3d_decay_mc_table tb;
+    if (int rc = analyse(*table, n_chosen, chosen_mc_id, tb.H)) return rc;
+    tb.n = table->n;
+    tb.n_chosen = n_chosen;
+    if (int rc = check_list_species(n_chosen, n_particles, particles)) return rc;
+    if (table->n < 1) return set_error(IS3D_EINVAL, "decay table: n = %d", table->n);
+    if (int rc = is3d::hbt_check_args(bins, n_events, n_slots, slot, table->n, hist, true)) return rc;
+    for (int64_t i = 0; i < n_particles; i++)
+        if (particles[i].event < 0 || particles[i].event >= n_events)
+            return set_error(IS3D_EINVAL, "particle %lld: event %d outside the %d events", (long long)i, particles[i].event, n_events);
+    is3d_decay_mc_stats st{};
+    st.n_primaries = n_particles;
+    is3d::decay_mc_table_stats(&tb, &st);
+    if (n_particles == 0) {
+        is3d::hbt_hist_zero(*bins, hist, n_events, n_slots);
+        if (stats) *stats = st;
+        return IS3D_OK;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return no_device();
+    is3d::hbt_hist_zero(*bins, hist, n_events, n_slots);
+    if (in->device >= 0) HIP_TRY(hipSetDevice(in->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    DevBuf<is3d_particle> d_in;
+    DevBuf<int32_t> d_slot;
+    DevBuf<unsigned long long> d_tally;
+    is3d::HbtRun run;
+    if (int rc = table_upload(tb, *table)) return rc;
+    HIP_TRY(d_in.upload(particles, (size_t)n_particles));
+    HIP_TRY(d_slot.upload(slot, (size_t)table->n));
+    HIP_TRY(d_tally.alloc(kBinTallies));
+    HIP_TRY(hipMemsetAsync(d_tally.p, 0, kBinTallies * sizeof(unsigned long long), nullptr));
+    if (int rc = run.begin(*bins, n_events, n_slots)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    const auto t1 = std::chrono::steady_clock::now();
+    const is3d::DecayMcHbtRun drun{&tb, d_slot.p, in->seed, in->lifetime, d_tally.p};
+    if (int rc = is3d::decay_mc_hbt_batch(drun, run, d_in.p, n_particles, in->first_particle)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    const auto t2 = std::chrono::steady_clock::now();
+    st.ms_h2d = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    st.ms_bin = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    unsigned long long tally[kBinTallies];
+    HIP_TRY(hipMemcpy(tally, d_tally.p, sizeof tally, hipMemcpyDeviceToHost));
+    const int rc_h = run.finish(hist);
+    st.ms_d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count();
+    const int rc = is3d::decay_mc_bins_tallies(tally, &st);
+    int64_t kept = 0;
+    for (size_t j = 0; j < (size_t)n_events * n_slots; j++) kept += hist->M[j];
+    *n_final = st.n_final;
+    *n_unbinned = st.n_final - kept;
+    if (stats) *stats = st;
+    return rc ? rc : rc_h;
 }

@@ -47,6 +47,7 @@
 #include "cf_sampler_bins.h"
 #include "cf_sampler_flow.h"
 #include "cf_sampler_pairs.h"
+#include "cf_sampler_hbt.h"
 #include "cf_decays_mc.h"
 #include "cf_sampler_common.h"
 #include "errors.h"
@@ -646,6 +647,10 @@ struct FlowRun {
     const is3d::PairTables *pair_tables;
     unsigned *occ_dev;
     const is3d::DecayMcPairRun *pair_decay;
+    // an HBT run instead (records_dev == NULL, occ_dev == NULL): the batch's list is selected and paired (hbt) and, with hbt_decay, decayed
+    // twice into records that are paired (hbt_decayed); the histograms stay in the two runs
+    is3d::HbtRun *hbt, *hbt_decayed;
+    const is3d::DecayMcHbtRun *hbt_decay;
 };
 int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t n, const double *x_dev, const double *y_dev, int32_t n_events,
                     uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
@@ -816,7 +821,17 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t
         if (flow && flow->records_dev && batch_total > 0)
             HIP_TRY(is3d::flow_launch(flow->cuts, flow->thresholds, n_events, flow->n_slots, flow->slot_dev, sp.npart, P->d_particles.as<is3d_particle>(),
                                       batch_total, flow->records_dev, flow->cuts.kernel_form));
+        if (flow && flow->hbt && batch_total > 0)
+            if (int rc = is3d::hbt_batch_list(*flow->hbt, flow->slot_dev, sp.npart, P->d_particles.as<is3d_particle>(), batch_total)) return rc;
         HIP_TRY(hipEventRecord(ev[4], nullptr));
+        if (flow && flow->hbt_decay && batch_total > 0) {
+            if (int rc = is3d::decay_mc_hbt_batch(*flow->hbt_decay, *flow->hbt_decayed, P->d_particles.as<is3d_particle>(), batch_total, base)) return rc;
+            HIP_TRY(hipEventRecord(ev[9], nullptr));
+            HIP_TRY(hipEventSynchronize(ev[9]));
+            float e_ms = 0;
+            HIP_TRY(hipEventElapsedTime(&e_ms, ev[4], ev[9]));
+            flow->ms_decay += e_ms;
+        }
         if (flow && flow->decay && batch_total > 0) {
             HIP_TRY(is3d::decay_mc_flow_launch(*flow->decay, P->d_particles.as<is3d_particle>(), batch_total, base));
             HIP_TRY(hipEventRecord(ev[9], nullptr));
@@ -1524,6 +1539,126 @@ extern "C" int is3d_sample_pairs(const is3d_cells *cells, const is3d_species *sp
     const int rc = is3d_sampler_plan_execute_pairs(r.P, &r.dc, r.xy[0], r.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events, bins, slot,
                                                    n_slots, hist, tg.t, slot_decayed, n_slots_decayed, decay_seed, lifetime, hist_decayed,
                                                    n_particles, n_final, n_unbinned, stats, decay_stats);
+    if (stats) stats->ms_h2d = r.ms_h2d;
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// HBT correlation histograms: each event batch's list, in the plan's workspace, is selected into compact records and paired (cf_hbt_select,
+// cf_hbt_pairs) and, with a table, decayed twice into records that are paired; an event lies whole in one batch, so the records of a batch
+// are discarded after it and only the histograms live for the whole run
+// ------------------------------------------------------------------------------------------------
+extern "C" int is3d_sampler_plan_execute_hbt(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev,
+                                             int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
+                                             const is3d_hbt_bins *bins, const int32_t *slot, int32_t n_slots, const is3d_hbt_hist *hist,
+                                             const is3d_decay_mc_table *table, const int32_t *slot_decayed, int32_t n_slots_decayed,
+                                             uint64_t decay_seed, int32_t lifetime, const is3d_hbt_hist *hist_decayed, int64_t *n_particles,
+                                             int64_t *n_final, int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats)
+{
+    using is3d::set_error;
+    if (!P || !cells || !n_particles || (table && (!n_final || !n_unbinned))) return set_error(IS3D_EINVAL, "null argument");
+    *n_particles = 0;
+    if (n_final) *n_final = 0;
+    if (n_unbinned) *n_unbinned = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (decay_stats) memset(decay_stats, 0, sizeof *decay_stats);
+    if (int rc = is3d::hbt_check_args(bins, n_events, n_slots, slot, P->sp.npart, hist, true)) return rc;
+    const int32_t n_entries = table ? is3d::decay_mc_table_entries(table) : 0;
+    if (table) {
+        if (int rc = is3d::hbt_check_args(bins, n_events, n_slots_decayed, slot_decayed, n_entries, hist_decayed, true)) return rc;
+        if (is3d::decay_mc_table_chosen(table) != P->sp.npart)
+            return set_error(IS3D_EINVAL, "the decay table was created for %d chosen species, the sampler plan for %d", is3d::decay_mc_table_chosen(table),
+                             P->sp.npart);
+        if (is3d::decay_mc_table_device(table) != P->device)
+            return set_error(IS3D_EINVAL, "the decay table lives on device %d, the sampler plan on device %d", is3d::decay_mc_table_device(table), P->device);
+    }
+    if (int rc = bind_cells(P, cells, first_cell)) return rc;
+    const int64_t n_cells = cells->n_cells;
+    if (n_cells < 0 || n_cells + first_cell > 0xffffffffLL) return set_error(IS3D_EINVAL, "cell indices must fit 32 bits for the counter-based streams");
+    is3d_decay_mc_stats dst{};
+    if (table) is3d::decay_mc_table_stats(table, &dst);
+    is3d::hbt_hist_zero(*bins, hist, n_events, n_slots);
+    if (table) is3d::hbt_hist_zero(*bins, hist_decayed, n_events, n_slots_decayed);
+    if (n_cells == 0) {
+        if (decay_stats) *decay_stats = dst;
+        return IS3D_OK;
+    }
+    HIP_TRY(hipSetDevice(P->device));
+    // the runs own their blocks for this call; the plan keeps nothing of them
+    is3d::HbtRun thermal, decayed;
+    is3d::DevBuf<int32_t> d_slot, d_slot_decayed;
+    is3d::DevBuf<unsigned long long> d_tally;
+    if (int rc = thermal.begin(*bins, n_events, n_slots)) return rc;
+    HIP_TRY(d_slot.upload(slot, (size_t)P->sp.npart));
+    is3d::DecayMcHbtRun drun{};
+    if (table) {
+        if (int rc = decayed.begin(*bins, n_events, n_slots_decayed)) return rc;
+        HIP_TRY(d_slot_decayed.upload(slot_decayed, (size_t)n_entries));
+        HIP_TRY(d_tally.alloc(is3d::kDecayMcBinTallies));
+        HIP_TRY(hipMemsetAsync(d_tally.p, 0, is3d::kDecayMcBinTallies * sizeof(unsigned long long), nullptr));
+        drun = is3d::DecayMcHbtRun{table, d_slot_decayed.p, decay_seed, lifetime, d_tally.p};
+    }
+    FlowRun run{};
+    run.n_slots = n_slots;
+    run.slot_dev = d_slot.p;
+    run.hbt = &thermal;
+    run.hbt_decayed = table ? &decayed : nullptr;
+    run.hbt_decay = table ? &drun : nullptr;
+    int64_t listed = 0;
+    if (int rc = sampler_batches(P, P->viscous, n_cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, nullptr, 0, nullptr, false, &listed, stats,
+                                 nullptr, nullptr, &run))
+        return rc;
+    *n_particles = listed;
+    const int rc_h = thermal.finish(hist);
+    int rc_t = IS3D_OK, rc_d = IS3D_OK;
+    if (table) {
+        rc_d = decayed.finish(hist_decayed);
+        unsigned long long tally[is3d::kDecayMcBinTallies];
+        HIP_TRY(hipMemcpy(tally, d_tally.p, sizeof tally, hipMemcpyDeviceToHost));
+        rc_t = is3d::decay_mc_bins_tallies(tally, &dst);
+        int64_t kept = 0;
+        for (size_t j = 0; j < (size_t)n_events * n_slots_decayed; j++) kept += hist_decayed->M[j];
+        dst.n_primaries = listed;
+        dst.ms_bin = run.ms_decay;
+        *n_final = dst.n_final;
+        *n_unbinned = dst.n_final - kept;
+        if (decay_stats) *decay_stats = dst;
+    }
+    if (rc_t) return rc_t;
+    return rc_h ? rc_h : rc_d;
+}
+
+// host-pointer one-shot: create, upload, execute, destroy (the table included)
+extern "C" int is3d_sample_hbt(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                               const is3d_options *opts, const is3d_hbt_bins *bins, const int32_t *slot, int32_t n_slots,
+                               const is3d_hbt_hist *hist, const is3d_decay_table *table, const int64_t *chosen_mc_id,
+                               const int32_t *slot_decayed, int32_t n_slots_decayed, uint64_t decay_seed, int32_t lifetime,
+                               const is3d_hbt_hist *hist_decayed, int64_t *n_particles, int64_t *n_final, int64_t *n_unbinned,
+                               is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats)
+{
+    using is3d::set_error;
+    if (!cells || !species || !df || !in || !opts || !n_particles || (table && (!chosen_mc_id || !n_final || !n_unbinned)))
+        return set_error(IS3D_EINVAL, "null argument");
+    *n_particles = 0;
+    if (n_final) *n_final = 0;
+    if (n_unbinned) *n_unbinned = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (decay_stats) memset(decay_stats, 0, sizeof *decay_stats);
+    if (species->n < 1) return set_error(IS3D_EINVAL, "the species list is empty");
+    if (int rc = is3d::hbt_check_args(bins, in->n_events, n_slots, slot, species->n, hist, true)) return rc;
+    if (table) {
+        if (table->n < 1) return set_error(IS3D_EINVAL, "decay table: n = %d", table->n);
+        if (int rc = is3d::hbt_check_args(bins, in->n_events, n_slots_decayed, slot_decayed, table->n, hist_decayed, true)) return rc;
+        if (int rc = is3d::decay_mc_table_check(table, species->n, chosen_mc_id)) return rc;
+    }
+    StagedRun r;
+    if (int rc = stage_run(r, cells, species, df, in, opts)) return rc;
+    struct TableGuard { is3d_decay_mc_table *t = nullptr; ~TableGuard() { is3d_decay_mc_table_destroy(t); } } tg;
+    if (table)
+        if (int rc = is3d_decay_mc_table_create(&tg.t, table, species->n, chosen_mc_id, r.P->device)) return rc;
+    const int rc = is3d_sampler_plan_execute_hbt(r.P, &r.dc, r.xy[0], r.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events, bins, slot,
+                                                 n_slots, hist, tg.t, slot_decayed, n_slots_decayed, decay_seed, lifetime, hist_decayed,
+                                                 n_particles, n_final, n_unbinned, stats, decay_stats);
     if (stats) stats->ms_h2d = r.ms_h2d;
     return rc;
 }

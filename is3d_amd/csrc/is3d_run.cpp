@@ -9,7 +9,8 @@
 //   dN_pTdpTdphidy*.dat, dN_dpTdphidy.dat, dN_dy_*.dat, vn_continuous/vn_*.dat, *_resonance_decays.dat; operation 0: spacetime_distribution/*.dat;
 //   operation 2: particle_list_osc.dat, particle_list_osc_decayed.dat, or the binned test files (test_sampler = 1; with test_sampler_decayed = 1
 //   also under results/decayed/; with test_sampler_flow = 1 the flow cumulants and multiplicities under results/flow/; with test_sampler_pairs = 1
-//   the two-particle correlations under results/pairs/); mode 5: S{t,x,y,n}.dat.
+//   the two-particle correlations under results/pairs/; with test_sampler_hbt = 1 the HBT correlation functions and radii under results/hbt/);
+//   mode 5: S{t,x,y,n}.dat.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -174,7 +175,8 @@ struct MemSurface { const is3d_cells *cells; const double *x, *y; };
 struct RunConfig {
     int operation, mode, hrg_eos, dimension, df_mode, include_baryon, include_bulk, include_shear, include_diff, regulate, outflow;
     // optional keys (absent: 0); an `is set` flag here has passed its checks
-    bool do_decays, decay_sampled, bin_on_device, bin_fused, vah_oversample, vah_bin_on_device, vah_sampler, test_sampler, bin_decayed, flow, pairs;
+    bool do_decays, decay_sampled, bin_on_device, bin_fused, vah_oversample, vah_bin_on_device, vah_sampler, test_sampler, bin_decayed, flow, pairs, hbt;
+    is3d_hbt_bins hbt_bins;     // test_sampler_hbt = 1: hbt_y_cut, hbt_pT_min, hbt_pT_max, hbt_kT_min, hbt_kT_max, hbt_kT_bins, hbt_q_max, hbt_q_bins (defaults 0.5, 0.1, 1.5, 0.1, 0.9, 4, 0.1, 20)
     is3d_pair_bins pair_bins;   // test_sampler_pairs = 1: pairs_y_cut, pairs_pT_min, pairs_pT_max, pairs_y_bins, pairs_phi_bins (defaults 2.0, 0.2, 3.0, 32, 32)
     is3d_flow_cuts flow_cuts;   // test_sampler_flow = 1: flow_y_cut, flow_y_gap, flow_pT_min, flow_pT_max (defaults 1.0, 0.5, 0.2, 3.0)
     bool vah;               // mode 2 from files: the anisotropic-hydro surface, tables and routines
@@ -202,6 +204,7 @@ static int parse_config(const RunParams &p, const MemSurface *mem, bool wants_re
     c.vah_bin_on_device = is_set("vah_sampler_on_device"); c.bin_decayed = is_set("test_sampler_decayed");
     c.flow = is_set("test_sampler_flow");
     c.pairs = is_set("test_sampler_pairs");
+    c.hbt = is_set("test_sampler_hbt");
     // test_sampler is a sampler key: optional where a check only looks at it, required (with the missing-key message) where a key depends on it
     const bool has_test_sampler = p.optional("test_sampler", &v);
     c.test_sampler = has_test_sampler && (int)v != 0;
@@ -397,6 +400,48 @@ static int parse_config(const RunParams &p, const MemSurface *mem, bool wants_re
             struct stat sb;
             if (stat(dir, &sb) != 0 || !S_ISDIR(sb.st_mode))
                 DIE("test_sampler_pairs = 1: the directory %s is missing; create it or set test_sampler_pairs = 0", dir);
+        }
+    }
+    // test_sampler_hbt = 1: the HBT correlation functions and radii of the same hadrons under results/hbt/ (results/decayed/hbt/), refused in
+    // the situations that refuse test_sampler_pairs, and for bad bins and missing directories
+    if (c.hbt) {
+        if (operation != 2)
+            DIE("test_sampler_hbt = 1 with operation = %d: it correlates the sampler's hadrons (operation = 2); set test_sampler_hbt = 0", operation);
+        if (need_test_sampler()) return IS3D_EINVAL;
+        if (!c.test_sampler)
+            DIE("test_sampler_hbt = 1 with test_sampler = 0: it writes the HBT correlations beside the test_sampler distributions; set test_sampler_hbt = 0");
+        if (vah)
+            DIE("test_sampler_hbt = 1 with mode = 2: it correlates the viscous-hydro sampler's hadrons; the anisotropic-hydro sampler has no such entry; set test_sampler_hbt = 0");
+        if (wants_result)
+            DIE("test_sampler_hbt = 1: the embedding entry returns the particle list, which this path never holds; set test_sampler_hbt = 0");
+        if (!c.bin_on_device)
+            DIE("test_sampler_hbt = 1 with test_sampler_on_device = 0: the pairs are formed where each event batch is binned, on the device "
+                "(test_sampler_on_device = 1); set test_sampler_hbt = 0");
+        if (c.bin_fused)
+            DIE("test_sampler_hbt = 1 with test_sampler_fused = 1: the fused pass never holds the batch of hadrons that is paired; set test_sampler_hbt = 0");
+        is3d_hbt_bins &b = c.hbt_bins;
+        b = is3d_hbt_bins{0.5, 0.1, 1.5, 0.1, 0.9, 4, 0.1, 20, 0};
+        double nk = 4.0, nq = 20.0;
+        p.optional("hbt_y_cut", &b.y_cut); p.optional("hbt_pt_min", &b.pT_min); p.optional("hbt_pt_max", &b.pT_max);
+        p.optional("hbt_kt_min", &b.kT_min); p.optional("hbt_kt_max", &b.kT_max); p.optional("hbt_q_max", &b.q_max);
+        p.optional("hbt_kt_bins", &nk); p.optional("hbt_q_bins", &nq);
+        const bool whole = nk >= 1.0 && nk <= 16.0 && nk == (double)(int)nk && nq >= 2.0 && nq <= 64.0 && nq == (double)(int)nq;
+        b.n_kT = whole ? (int32_t)nk : 0;
+        b.n_q = whole ? (int32_t)nq : 0;
+        // the library's own rule decides: an empty list through is3d_hbt_list
+        std::vector<int64_t> w(whole ? (size_t)(2 * b.n_kT * b.n_q * b.n_q * b.n_q + 1) : 3);
+        const is3d_hbt_hist probe{w.data(), w.data() + (w.size() - 1) / 2, w.data() + w.size() - 1};
+        const int32_t none = -1;
+        if (!whole || is3d_hbt_list(&b, 1, 1, &none, 1, 0, nullptr, &probe) != IS3D_OK)
+            DIE("test_sampler_hbt = 1 with hbt_y_cut = %g, hbt_pT_min = %g, hbt_pT_max = %g, hbt_kT_min = %g, hbt_kT_max = %g, hbt_kT_bins = %g, hbt_q_max = %g, "
+                "hbt_q_bins = %g: the bins need hbt_y_cut > 0, hbt_pT_max > hbt_pT_min >= 0, hbt_kT_max > hbt_kT_min >= 0, 1 <= hbt_kT_bins <= 16, "
+                "hbt_q_max > 0 and 2 <= hbt_q_bins <= 64; set test_sampler_hbt = 0",
+                b.y_cut, b.pT_min, b.pT_max, b.kT_min, b.kT_max, nk, b.q_max, nq);
+        for (const char *dir : {"results/hbt", "results/decayed/hbt"}) {
+            if (dir[8] == 'd' && !c.bin_decayed) continue;
+            struct stat sb;
+            if (stat(dir, &sb) != 0 || !S_ISDIR(sb.st_mode))
+                DIE("test_sampler_hbt = 1: the directory %s is missing; create it or set test_sampler_hbt = 0", dir);
         }
     }
     return IS3D_OK;
@@ -997,6 +1042,78 @@ static int run_sampler_pairs(const RunConfig &cfg, RunInputs &in, const RunDevic
     return IS3D_OK;
 }
 
+// test_sampler_hbt = 1: as run_sampler_pairs, the sampler runs once more with the same seed and each event batch is selected and paired on
+// the device (cf_hbt_select, cf_hbt_pairs) -- and, with test_sampler_decayed = 1, decayed with lifetimes (the halo of long-lived resonances is
+// what lowers lambda) into records that are paired.  Slots: pi+, pi-, K+, K- (211, -211, 321, -321) where chosen; every other species is dropped.
+static int run_sampler_hbt(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, SamplerRun &s)
+{
+    static const int64_t named[4] = {211, -211, 321, -321};
+    struct Slots {
+        std::vector<std::string> label;
+        int of(int64_t id)
+        {
+            for (int64_t k : named)
+                if (id == k) {
+                    const std::string l = std::to_string((long long)id);
+                    for (size_t j = 0; j < label.size(); j++)
+                        if (label[j] == l) return (int)j;
+                    label.push_back(l);
+                    return (int)label.size() - 1;
+                }
+            return -1;
+        }
+    } th, de;
+    std::vector<int32_t> slot((size_t)in.sp.n), slot_d;
+    for (int ip = 0; ip < in.sp.n; ip++) slot[(size_t)ip] = th.of(in.mcid[(size_t)ip]);
+    DecayTable tab;
+    if (cfg.bin_decayed) {
+        if (int rc = read_decay_table(cfg.pdg_path, tab)) return rc;
+        slot_d.assign((size_t)tab.view.n, -1);
+        for (int ip = 0; ip < in.sp.n; ip++)
+            for (int e = 0; e < tab.view.n; e++)
+                if (tab.view.mc_id[e] == in.mcid[(size_t)ip]) {
+                    if (tab.view.stable[e]) slot_d[(size_t)e] = de.of(in.mcid[(size_t)ip]);
+                    break;
+                }
+    }
+    if (th.label.empty()) {
+        printf("HBT correlations: none of 211, -211, 321, -321 is chosen; nothing written\n");
+        return IS3D_OK;
+    }
+    const bool decayed = cfg.bin_decayed && !de.label.empty();
+    const int32_t E = s.si.n_events, S = (int32_t)th.label.size(), Sd = (int32_t)de.label.size();
+    const is3d_hbt_bins &b = cfg.hbt_bins;
+    struct Block {
+        std::vector<int64_t> num, den, M;
+        is3d_hbt_hist view;
+        Block(const is3d_hbt_bins &b, int32_t events, int32_t slots)
+            : num((size_t)slots * b.n_kT * b.n_q * b.n_q * b.n_q), den(num.size()), M((size_t)events * slots), view{num.data(), den.data(), M.data()} {}
+    } ht(b, E, S), hd(b, E, std::max(Sd, 1));
+    is3d_sampler_stats ss{};
+    is3d_decay_mc_stats ms{};
+    int64_t count = 0, n_final = 0, n_unbinned = 0;
+    is3d_options opts = in.opts;
+    opts.device = rd.first();
+    const int rcp = is3d_sample_hbt(&in.cells, &in.sp, &in.df, &s.si, &opts, &b, slot.data(), S, &ht.view, decayed ? &tab.view : nullptr,
+                                    in.mcid.data(), slot_d.data(), Sd, s.si.seed, 1, &hd.view, &count, &n_final, &n_unbinned, &ss, &ms);
+    if (rcp) DIE("is3d_sample_hbt failed (%d): %s", rcp, is3d_last_error());
+    const auto write = [&b](const char *dir, Block &h, const std::vector<std::string> &label) {
+        std::vector<const char *> names;
+        for (const std::string &l : label) names.push_back(l.c_str());
+        return is3d_write_hbt(dir, &b, &h.view, (int32_t)label.size(), names.data(), 20, 0.05);
+    };
+    printf("Writing the HBT correlations (%d slots, %d kT bins)...\n", (int)S, (int)b.n_kT);
+    if (write("results", ht, th.label)) DIE("%s", is3d_last_error());
+    if (decayed) {
+        printf("Writing the HBT correlations of the decayed hadrons (%d slots, %d kT bins)...\n", (int)Sd, (int)b.n_kT);
+        if (write("results/decayed", hd, de.label)) DIE("%s", is3d_last_error());
+    }
+    printf("HBT correlations on the device: %lld hadrons, ms_bin %.3f ms", (long long)count, ss.ms_bin);
+    if (decayed) printf("; decayed: n_final %lld, n_unbinned %lld, ms_bin %.3f ms", (long long)n_final, (long long)n_unbinned, ms.ms_bin);
+    printf("\n");
+    return IS3D_OK;
+}
+
 // ---- operation 2 (emissionfunction.cpp:1522-1554): number of events, sampling, the OSCAR list or the binned test distributions ----
 static int run_sampler(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, RunParams &params, is3d_run_result *res)
 {
@@ -1007,7 +1124,9 @@ static int run_sampler(const RunConfig &cfg, RunInputs &in, const RunDevices &rd
         if (int rc = cfg.bin_decayed ? run_sampler_decayed_binned(cfg, in, rd, s) : run_sampler_binned(cfg, in, rd, s)) return rc;
         if (cfg.flow)
             if (int rc = run_sampler_flow(cfg, in, rd, s)) return rc;
-        return cfg.pairs ? run_sampler_pairs(cfg, in, rd, s) : IS3D_OK;
+        if (cfg.pairs)
+            if (int rc = run_sampler_pairs(cfg, in, rd, s)) return rc;
+        return cfg.hbt ? run_sampler_hbt(cfg, in, rd, s) : IS3D_OK;
     }
     // count, then fill a list of that size: the viscous-hydro sampler, or (mode 2) the anisotropic-hydro one on the mode-2 cells and tables
     is3d_sampler_stats ss{};
