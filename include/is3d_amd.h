@@ -1304,6 +1304,90 @@ int is3d_sample_flow(const is3d_cells *cells, const is3d_species *species, const
                      const is3d_flow_records *records_decayed, int64_t *n_particles, int64_t *n_final, int64_t *n_unbinned,
                      is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats);
 
+/* Differential flow: the flow records above with a second key, the pT bin, and from them v_n{2}(pT), v_n{4}(pT) and
+ * v_n{2,gap}(pT) against a reference made of the same records.  The pT bins are a caller's edge table pT_edges[n_pT + 1]: HOST doubles,
+ * finite, strictly ascending, pT_edges[0] >= 0, 1 <= n_pT <= IS3D_FLOW_DIFF_MAX_BINS, handed to the kernels as bits.  The table IS the
+ * acceptance in pT: cuts->pT_min and cuts->pT_max must equal pT_edges[0] and pT_edges[n_pT] bit for bit (IS3D_EINVAL otherwise), so the
+ * rule of is3d_flow_list decides acceptance and region unchanged.  An accepted particle's bin is the b with pT_edges[b] <= pT <
+ * pT_edges[b + 1], pT = sqrt(px^2 + py^2) as in that rule, found by bisection with comparisons only (csrc/cf_sampler_flow_diff.h, shared by
+ * host and device: no division by a width, no libm in any decision).  It adds what it adds to a flow record, to region 0 and its
+ * sub-event of (event, slot, bin): m (the count) and p_re, p_im (the fixed-point terms).  So the records summed over the bins ARE the
+ * is3d_flow_list records of the same cuts, word for word, and everything said there about order, pieces, kernel form and the device's
+ * agreement with the host (m exactly, a p word within m units) holds here.
+ * Records (caller-owned): m [n_events][n_slots][n_pT][3], p_re and p_im [n_events][n_slots][n_pT][3][8].  kernel_form = 2 is IS3D_EINVAL
+ * when the records of one event, n_slots * n_pT * 51 words, do not fit 64 KiB beside the IS3D_FLOW_DIFF_MAX_BINS + 2 words kept for the staged
+ * edges (and the six tally words of the decay pass).  m above IS3D_SAMPLER_VN_MAX_COUNT: IS3D_EDOMAIN from a device entry after the run.
+ * Not offered: the fused sample-and-bin pass, the anisotropic-hydro sampler, several devices. */
+#define IS3D_FLOW_DIFF_MAX_BINS 64
+typedef struct {
+    int64_t *m, *p_re, *p_im;
+} is3d_flow_diff_records;
+/* list -> records on the host: THE definition, no device use.  Refusals: those of is3d_flow_list, and the edge-table checks above. */
+int is3d_flow_diff_list(const is3d_flow_cuts *cuts, int32_t n_pT, const double *pT_edges, int32_t n_events, int32_t n_slots, const int32_t *slot,
+                        int32_t n_species, int64_t n_particles, const is3d_particle *particles, const is3d_flow_diff_records *records);
+/* list -> records on the DEVICE through cf_sampler_flow_diff, as is3d_flow_list_device (n_skipped, n_particles = 0, device < 0). */
+int is3d_flow_diff_list_device(const is3d_flow_cuts *cuts, int32_t n_pT, const double *pT_edges, int32_t n_events, int32_t n_slots,
+                               const int32_t *slot, int32_t n_species, int64_t n_particles, const is3d_particle *particles,
+                               const is3d_flow_diff_records *records, int64_t *n_skipped, int32_t device);
+/* The reference flow vectors: out (flow records of ONE slot, n_events events) receives, per event and region, the integer sums of the
+ * differential records over the slots s with ref_slot[s] != 0 (int32[n_slots], 0 or 1) and the bins in [ref_bin_lo, ref_bin_hi).
+ * IS3D_EINVAL: a NULL, sizes < 1, n_pT outside 1..64, ref_slot outside {0, 1}, not 0 <= ref_bin_lo < ref_bin_hi <= n_pT. */
+int is3d_flow_diff_reference(const is3d_flow_diff_records *records, int32_t n_events, int32_t n_slots, int32_t n_pT, const int32_t *ref_slot,
+                             int32_t ref_bin_lo, int32_t ref_bin_hi, const is3d_flow_records *out);
+/* Differential Q-cumulants (Bilandzic, Snellings, Voloshin, Phys. Rev. C 83, 044913, section IV) per (slot, bin), in double from the exact
+ * integers, events in order.  Q, M: the reference of region 0 (is3d_flow_diff_reference); p, m_p: the record of (slot, bin) in region 0;
+ * q, m_q: that record again if the slot and the bin belong to the reference, 0 otherwise; all vectors / 2^32:
+ *   <2'>     = (Re(p_n Q_n*) - m_q) / (m_p M - m_q),                                   event weight the denominator, n = 1..8
+ *   <4'>     = Re[p_n Q_n Q_n* Q_n* - q_2n Q_n* Q_n* - p_n Q_n Q_2n* - 2 M p_n Q_n* - 2 m_q |Q_n|^2 + 7 q_n Q_n* - Q_n q_n* + q_2n Q_2n*
+ *                 + 2 p_n Q_n* + 2 m_q M - 6 m_q] / [(m_p M - 3 m_q)(M - 1)(M - 2)],  event weight the denominator, n = 1..4
+ *   <2'>_gap = [Re(p_n^A Q_n^B*) + Re(p_n^B Q_n^A*)] / (m_p^A M^B + m_p^B M^A),        event weight the denominator
+ * An event whose weight for a quantity is zero is left out of it, and an event with M < 4 out of the four-particle one; n_used_* count
+ * the events that were not.  <<.>> is the weighted event average (0 when no event was used).  With c2 = <<2>>, c4 and c2_gap those of
+ * is3d_flow_cumulants on the reference records:
+ *   d2 = <<2'>>, avg4 = <<4'>>, d4 = <<4'>> - 2 <<2'>> <<2>>, d2_gap = <<2'>_gap>
+ *   v2 = d2 / sqrt(c2) (0 unless c2 > 0), v4 = -d4 / (-c4)^(3/4) (0 unless c4 < 0), v2_gap = d2_gap / sqrt(c2_gap) (0 unless c2_gap > 0)
+ *   v_rp = sum Re p_n / sum m_p (0 when sum m_p = 0); sum_m = sum m_p over the events, mean_m = sum_m / n_events
+ * out: [n_slots][n_pT].  Refusals as for is3d_flow_diff_reference. */
+typedef struct {
+    double d2[IS3D_FLOW_HARMONICS], d2_gap[IS3D_FLOW_HARMONICS], v2[IS3D_FLOW_HARMONICS], v2_gap[IS3D_FLOW_HARMONICS], v_rp[IS3D_FLOW_HARMONICS];
+    double avg4[4], d4[4], v4[4];
+    double mean_m, sum_m;
+    int64_t n_used_2, n_used_4, n_used_gap, n_events;
+} is3d_flow_diff_result;
+int is3d_flow_diff_cumulants(const is3d_flow_diff_records *records, int32_t n_events, int32_t n_slots, int32_t n_pT, const int32_t *ref_slot,
+                             int32_t ref_bin_lo, int32_t ref_bin_hi, is3d_flow_diff_result *out /* [n_slots][n_pT] */);
+/* Writes, per slot s, <results_dir>/flow/differential_<labels[s]>.dat: two comment lines, then a row per (bin, n), n = 1..8: bin, edge_lo,
+ * edge_hi, n, d_n{2}, d_n{4}, d_n{2,gap}, v_n{2}, v_n{4}, v_n{2,gap}, reaction-plane v_n, sum m_p, tab separated (the four-particle
+ * columns are 0 for n > 4); doubles by std::to_chars(scientific, 8), integers in full.  The flow/ directory must exist (IS3D_EIO otherwise);
+ * the refusals of is3d_flow_diff_cumulants and of the edge table, a NULL, an empty label or one with a '/' are IS3D_EINVAL. */
+int is3d_write_flow_diff(const char *results_dir, const is3d_flow_diff_records *records, int32_t n_events, int32_t n_slots, int32_t n_pT,
+                         const double *pT_edges, const int32_t *ref_slot, int32_t ref_bin_lo, int32_t ref_bin_hi, const char *const *labels);
+/* is3d_decay_particles_flow with the pT bin as a second key: the records are those of is3d_flow_diff_list on the list is3d_decay_particles
+ * returns (m exactly, every p word within m units), in one pass of cf_decay_mc_flow on the differential sink; n_final, n_unbinned, stats,
+ * pieces (first_particle) and refusals as there, with the edge-table checks. */
+int is3d_decay_particles_flow_diff(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
+                                   const is3d_decay_mc_inputs *in, int64_t n_particles, const is3d_particle *particles,
+                                   const int32_t *slot, int32_t n_slots, const is3d_flow_cuts *cuts, int32_t n_pT, const double *pT_edges,
+                                   int32_t n_events, const is3d_flow_diff_records *records, int64_t *n_final, int64_t *n_unbinned,
+                                   is3d_decay_mc_stats *stats /* may be NULL */);
+/* is3d_sampler_plan_execute_flow with differential records (both sets on the same edge table): thermal records = is3d_flow_diff_list of
+ * the list is3d_sampler_plan_execute returns, decayed ones = is3d_decay_particles_flow_diff of that list; independent of batch_events,
+ * kernel_form and launch geometry, bit for bit.  The plan serves its other entries afterwards as before. */
+int is3d_sampler_plan_execute_flow_diff(is3d_sampler_plan *plan, const is3d_cells *cells_dev, const double *x_dev, const double *y_dev,
+                                        int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events, const is3d_flow_cuts *cuts,
+                                        int32_t n_pT, const double *pT_edges, const int32_t *slot, int32_t n_slots,
+                                        const is3d_flow_diff_records *records_host, const is3d_decay_mc_table *table_dev /* may be NULL */,
+                                        const int32_t *slot_decayed, int32_t n_slots_decayed, uint64_t decay_seed, int32_t lifetime,
+                                        const is3d_flow_diff_records *records_decayed, int64_t *n_particles, int64_t *n_final,
+                                        int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats);
+/* host-pointer one-shot, as is3d_sample_flow */
+int is3d_sample_flow_diff(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                          const is3d_options *opts, const is3d_flow_cuts *cuts, int32_t n_pT, const double *pT_edges, const int32_t *slot,
+                          int32_t n_slots, const is3d_flow_diff_records *records, const is3d_decay_table *table /* may be NULL */,
+                          const int64_t *chosen_mc_id, const int32_t *slot_decayed, int32_t n_slots_decayed, uint64_t decay_seed,
+                          int32_t lifetime, const is3d_flow_diff_records *records_decayed, int64_t *n_particles, int64_t *n_final,
+                          int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats);
+
 /* Two-particle (delta y, delta phi) correlations of a particle list: how the pairs of ONE event are distributed in
  * relative rapidity and azimuth, beside the same distribution of pairs from neighbouring events.  The flow records above hold the delta phi
  * harmonics of that and nothing in delta y.  A particle maps to a cell (iy, iphi) of an n_y x n_phi grid or to nothing, by the rule of

@@ -124,6 +124,8 @@ EXPORTS = ["is3d_last_error", "is3d_version", "is3d_device_count", "is3d_smooth_
            "is3d_sampler_bin_list_device", "is3d_df_generate", "is3d_df_tables_write",
            "is3d_flow_list", "is3d_flow_list_device", "is3d_flow_merge", "is3d_flow_cumulants", "is3d_decay_particles_flow",
            "is3d_sampler_plan_execute_flow", "is3d_sample_flow", "is3d_write_flow",
+           "is3d_flow_diff_list", "is3d_flow_diff_list_device", "is3d_flow_diff_reference", "is3d_flow_diff_cumulants", "is3d_write_flow_diff",
+           "is3d_decay_particles_flow_diff", "is3d_sampler_plan_execute_flow_diff", "is3d_sample_flow_diff",
            "is3d_pairs_list", "is3d_pairs_list_device", "is3d_pairs_correlation", "is3d_write_pairs", "is3d_decay_particles_pairs",
            "is3d_sampler_plan_execute_pairs", "is3d_sample_pairs",
            "is3d_hbt_list", "is3d_hbt_list_device", "is3d_hbt_radii", "is3d_write_hbt", "is3d_decay_particles_hbt",
@@ -1193,6 +1195,28 @@ def decay_particles_flow(table, chosen_mc_id, particles, slot, n_slots, cuts, n_
     return out, _check_decayed(rc, st, nf, nu, records=out)
 
 
+def decay_particles_flow_diff(table, chosen_mc_id, particles, slot, n_slots, cuts, pT_edges, n_events, seed=1, first_particle=0, lifetime=0,
+                              device=-1):
+    """is3d_decay_particles_flow_diff: decay_particles_flow with the pT bin as a second key -- the records of flow_diff_list on
+    decay_particles' list.  Returns (differential records dict, stats dict with n_final, n_unbinned and the tallies of decay_particles)."""
+    L = load()
+    ts, ch, _, keep = _decay_pack(table, chosen_mc_id, dict(pT=[1.0], phi=[0.0], y=[0.0]))
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    slot = _slot_map(table, slot)
+    inp = DecayMcInputs(int(seed), int(first_particle), int(lifetime), int(device))
+    c = _pack_cuts(cuts)
+    edges = np.ascontiguousarray(pT_edges, dtype=np.float64)
+    r, out = _flow_diff_arrays(n_events, n_slots, len(edges) - 1)
+    st, nf, nu = DecayMcStats(), C.c_int64(0), C.c_int64(0)
+    L.is3d_decay_particles_flow_diff.argtypes = [C.POINTER(DecayTable), C.c_int32, C.POINTER(C.c_int64), C.POINTER(DecayMcInputs), C.c_int64,
+                                                 C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(FlowCuts), C.c_int32, C.c_void_p, C.c_int32,
+                                                 C.POINTER(FlowDiffRecords), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(DecayMcStats)]
+    rc = L.is3d_decay_particles_flow_diff(C.byref(ts), len(ch), ch.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(inp), len(particles),
+                                          particles.ctypes.data, slot.ctypes.data, int(n_slots), C.byref(c), len(edges) - 1, edges.ctypes.data,
+                                          int(n_events), C.byref(r), C.byref(nf), C.byref(nu), C.byref(st))
+    return out, _check_decayed(rc, st, nf, nu, records=out)
+
+
 def decay_particles_pairs(table, chosen_mc_id, particles, slot, n_slots, bins, n_events, seed=1, first_particle=0, lifetime=0, device=-1):
     """is3d_decay_particles_pairs: a sampled list decayed on the device with every final particle added to the pair occupancies at once,
     then correlated -- the histograms of pairs_list on decay_particles' list (species = table entries) with the same slot map, bit for bit.
@@ -1970,6 +1994,40 @@ class SamplerPlan:
         dd = _check_decayed(rc, dst, nf, nu, records=out, records_decayed=outd, sampler_stats=d)
         return out, outd, d, dd
 
+    def execute_flow_diff(self, n_cells, dev_ptrs, n_events, seed, cuts, pT_edges, slot, n_slots, table=None, slot_decayed=None,
+                          n_slots_decayed=0, decay_seed=None, lifetime=0, x_ptr=0, y_ptr=0, first_cell=0, batch_events=0):
+        """is3d_sampler_plan_execute_flow_diff: execute_flow with the pT bin of the edge table pT_edges as a second key of both sets of records.
+        -> (records, sampler stats) | (records, decayed records, sampler stats, decay stats with n_final and n_unbinned)."""
+        cs = Cells()
+        cs.n_cells = int(n_cells)
+        for f in CELL_FIELDS:
+            if dev_ptrs.get(f):
+                setattr(cs, f, int(dev_ptrs[f]))
+        c = _pack_cuts(cuts)
+        edges = np.ascontiguousarray(pT_edges, dtype=np.float64)
+        slot = np.ascontiguousarray(slot, dtype=np.int32)
+        r, out = _flow_diff_arrays(n_events, n_slots, len(edges) - 1)
+        rd, outd = _flow_diff_arrays(n_events, n_slots_decayed if table is not None else 0, len(edges) - 1)
+        sd = _slot_map(table.table, slot_decayed) if table is not None else None
+        cnt, st, dst, nf, nu = C.c_int64(0), SamplerStats(), DecayMcStats(), C.c_int64(0), C.c_int64(0)
+        fn = load().is3d_sampler_plan_execute_flow_diff
+        fn.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(FlowCuts),
+                       C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(FlowDiffRecords), C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64,
+                       C.c_int32, C.POINTER(FlowDiffRecords), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                       C.POINTER(SamplerStats), C.POINTER(DecayMcStats)]
+        rc = fn(self._h, C.byref(cs), C.c_void_p(int(x_ptr) or None), C.c_void_p(int(y_ptr) or None), int(n_events), int(seed), int(first_cell),
+                int(batch_events), C.byref(c), len(edges) - 1, edges.ctypes.data, slot.ctypes.data, int(n_slots), C.byref(r),
+                table._h if table is not None else None, sd.ctypes.data if sd is not None else None, int(n_slots_decayed),
+                int(seed if decay_seed is None else decay_seed), int(lifetime), C.byref(rd) if table is not None else None, C.byref(cnt),
+                C.byref(nf), C.byref(nu), C.byref(st), C.byref(dst))
+        d = st.as_dict()
+        d["n_particles"] = int(cnt.value)
+        if table is None:
+            _check(rc)
+            return out, d
+        dd = _check_decayed(rc, dst, nf, nu, records=out, records_decayed=outd, sampler_stats=d)
+        return out, outd, d, dd
+
     def execute_pairs(self, n_cells, dev_ptrs, n_events, seed, bins, slot, n_slots, table=None, slot_decayed=None, n_slots_decayed=0,
                       decay_seed=None, lifetime=0, x_ptr=0, y_ptr=0, first_cell=0, batch_events=0):
         """is3d_sampler_plan_execute_pairs: the pair histograms of the list execute returns (slot: int32 per species of the plan) and, with
@@ -2335,6 +2393,124 @@ def write_flow(results_dir, records, labels):
     _check(L.is3d_write_flow(results_dir.encode(), C.byref(r), n_events, n_slots, names))
 
 
+FLOW_DIFF_MAX_BINS = 64   # IS3D_FLOW_DIFF_MAX_BINS
+
+
+class FlowDiffRecords(C.Structure):
+    _fields_ = [(n, C.POINTER(C.c_int64)) for n in ["m", "p_re", "p_im"]]
+
+
+class FlowDiffResult(C.Structure):
+    _fields_ = [(n, C.c_double * FLOW_HARMONICS) for n in ["d2", "d2_gap", "v2", "v2_gap", "v_rp"]] + \
+               [(n, C.c_double * 4) for n in ["avg4", "d4", "v4"]] + [("mean_m", C.c_double), ("sum_m", C.c_double)] + \
+               [(n, C.c_int64) for n in ["n_used_2", "n_used_4", "n_used_gap", "n_events"]]
+
+
+def flow_diff_edges(pT_min, pT_max, n_pT):
+    """The run driver's uniform edge table: pT_min + k (pT_max - pT_min) / n_pT, the last edge pT_max exactly."""
+    e = np.array([pT_min + k * (pT_max - pT_min) / n_pT for k in range(n_pT + 1)], dtype=np.float64)
+    e[-1] = pT_max
+    return e
+
+
+def _flow_diff_arrays(n_events, n_slots, n_pT, records=None):
+    """is3d_flow_diff_records over numpy int64 arrays: (struct, dict).  records = None: fresh zero arrays m [event][slot][bin][3], p_re /
+    p_im [event][slot][bin][3][8]; otherwise the caller's arrays are checked and used."""
+    E, S, B = max(int(n_events), 0), max(int(n_slots), 0), max(int(n_pT), 0)
+    shapes = dict(m=(E, S, B, 3), p_re=(E, S, B, 3, FLOW_HARMONICS), p_im=(E, S, B, 3, FLOW_HARMONICS))
+    out = {}
+    for k, shp in shapes.items():
+        if records is None:
+            out[k] = np.zeros(shp, dtype=np.int64)
+        else:
+            out[k] = np.ascontiguousarray(records[k], dtype=np.int64)
+            assert out[k].shape == shp, (k, out[k].shape, shp)
+    r = FlowDiffRecords(*[out[k].ctypes.data_as(C.POINTER(C.c_int64)) for k, _ in FlowDiffRecords._fields_])
+    return r, out
+
+
+def flow_diff_list(cuts, pT_edges, n_events, n_slots, slot, particles):
+    """is3d_flow_diff_list: a particle list -> the differential flow records on the host (the definition; no device use).  pT_edges: the
+    n_pT + 1 bin edges, whose ends must equal cuts pT_min / pT_max bit for bit.  Returns a dict of int64 arrays m, p_re, p_im."""
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    slot = np.ascontiguousarray(slot, dtype=np.int32)
+    edges = np.ascontiguousarray(pT_edges, dtype=np.float64)
+    c = _pack_cuts(cuts)
+    r, out = _flow_diff_arrays(n_events, n_slots, len(edges) - 1)
+    L = load()
+    L.is3d_flow_diff_list.argtypes = [C.POINTER(FlowCuts), C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
+                                      C.POINTER(FlowDiffRecords)]
+    _check(L.is3d_flow_diff_list(C.byref(c), len(edges) - 1, edges.ctypes.data, int(n_events), int(n_slots), slot.ctypes.data, len(slot),
+                                 len(particles), particles.ctypes.data, C.byref(r)))
+    return out
+
+
+def flow_diff_list_device(cuts, pT_edges, n_events, n_slots, slot, particles, device=0):
+    """is3d_flow_diff_list_device: a host particle list through the device kernel cf_sampler_flow_diff (form cuts["kernel_form"]).  Returns
+    (records, n_skipped); n_skipped counts the particles whose species or event is out of range, which add nothing."""
+    particles = np.ascontiguousarray(particles, dtype=PARTICLE_DTYPE)
+    slot = np.ascontiguousarray(slot, dtype=np.int32)
+    edges = np.ascontiguousarray(pT_edges, dtype=np.float64)
+    c = _pack_cuts(cuts)
+    r, out = _flow_diff_arrays(n_events, n_slots, len(edges) - 1)
+    skipped = C.c_int64(0)
+    L = load()
+    L.is3d_flow_diff_list_device.argtypes = [C.POINTER(FlowCuts), C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64,
+                                             C.c_void_p, C.POINTER(FlowDiffRecords), C.POINTER(C.c_int64), C.c_int32]
+    _check(L.is3d_flow_diff_list_device(C.byref(c), len(edges) - 1, edges.ctypes.data, int(n_events), int(n_slots), slot.ctypes.data, len(slot),
+                                        len(particles), particles.ctypes.data, C.byref(r), C.byref(skipped), int(device)))
+    return out, int(skipped.value)
+
+
+def _flow_diff_ref(records, ref_slot, ref_bins):
+    n_events, n_slots, n_pT = np.shape(records["m"])[:3]
+    ref_slot = np.ascontiguousarray(np.ones(n_slots) if ref_slot is None else ref_slot, dtype=np.int32)
+    assert len(ref_slot) == n_slots, (len(ref_slot), n_slots)
+    lo, hi = (0, n_pT) if ref_bins is None else ref_bins
+    return n_events, n_slots, n_pT, ref_slot, int(lo), int(hi)
+
+
+def flow_diff_reference(records, ref_slot=None, ref_bins=None):
+    """is3d_flow_diff_reference: the reference flow records (one slot) of the differential records -- the integer sums over the slots with
+    ref_slot[s] = 1 (None: all) and the bins [ref_bins[0], ref_bins[1]) (None: all).  Returns a dict M, Q_re, Q_im as flow_list's."""
+    n_events, n_slots, n_pT, ref_slot, lo, hi = _flow_diff_ref(records, ref_slot, ref_bins)
+    r, _keep = _flow_diff_arrays(n_events, n_slots, n_pT, records)
+    o, out = _flow_arrays(n_events, 1)
+    L = load()
+    L.is3d_flow_diff_reference.argtypes = [C.POINTER(FlowDiffRecords), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                           C.POINTER(FlowRecords)]
+    _check(L.is3d_flow_diff_reference(C.byref(r), n_events, n_slots, n_pT, ref_slot.ctypes.data, lo, hi, C.byref(o)))
+    return out
+
+
+def flow_diff_cumulants(records, ref_slot=None, ref_bins=None):
+    """is3d_flow_diff_cumulants: the differential Q-cumulants of every (slot, bin) against the reference of flow_diff_reference.  Returns a
+    dict of arrays with (slot, bin) as first axes: d2, d2_gap, v2, v2_gap, v_rp [slot][bin][8]; avg4, d4, v4 [slot][bin][4]; mean_m, sum_m,
+    n_used_2, n_used_4, n_used_gap, n_events [slot][bin]."""
+    n_events, n_slots, n_pT, ref_slot, lo, hi = _flow_diff_ref(records, ref_slot, ref_bins)
+    r, _keep = _flow_diff_arrays(n_events, n_slots, n_pT, records)
+    res = (FlowDiffResult * max(n_slots * n_pT, 1))()
+    L = load()
+    L.is3d_flow_diff_cumulants.argtypes = [C.POINTER(FlowDiffRecords), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                           C.POINTER(FlowDiffResult)]
+    _check(L.is3d_flow_diff_cumulants(C.byref(r), n_events, n_slots, n_pT, ref_slot.ctypes.data, lo, hi, res))
+    return {k: np.array([[np.array(getattr(res[s * n_pT + b], k)) for b in range(n_pT)] for s in range(n_slots)]) for k, _ in FlowDiffResult._fields_}
+
+
+def write_flow_diff(results_dir, records, pT_edges, labels, ref_slot=None, ref_bins=None):
+    """is3d_write_flow_diff: <results_dir>/flow/differential_<label>.dat for every slot of the records."""
+    n_events, n_slots, n_pT, ref_slot, lo, hi = _flow_diff_ref(records, ref_slot, ref_bins)
+    assert len(labels) == n_slots, (len(labels), n_slots)
+    edges = np.ascontiguousarray(pT_edges, dtype=np.float64)
+    assert len(edges) == n_pT + 1, (len(edges), n_pT)
+    r, _keep = _flow_diff_arrays(n_events, n_slots, n_pT, records)
+    names = (C.c_char_p * n_slots)(*[str(x).encode() for x in labels])
+    L = load()
+    L.is3d_write_flow_diff.argtypes = [C.c_char_p, C.POINTER(FlowDiffRecords), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.c_int32, C.POINTER(C.c_char_p)]
+    _check(L.is3d_write_flow_diff(results_dir.encode(), C.byref(r), n_events, n_slots, n_pT, edges.ctypes.data, ref_slot.ctypes.data, lo, hi, names))
+
+
 PAIR_BINS = dict(y_cut=2.0, pT_min=0.2, pT_max=3.0, n_y=32, n_phi=32)   # the run driver's defaults
 
 
@@ -2629,6 +2805,43 @@ def sample_flow(cells, species, df, gla, cuts, slot, n_slots, opts=None, table=N
                    C.POINTER(DecayMcStats)]
     rc = fn(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), C.byref(c), slot.ctypes.data, int(n_slots), C.byref(r),
             C.byref(ts) if ts is not None else None, ch.ctypes.data_as(C.POINTER(C.c_int64)) if ch is not None else None,
+            sd.ctypes.data if sd is not None else None, int(n_slots_decayed), int(seed if decay_seed is None else decay_seed), int(lifetime),
+            C.byref(rd) if table is not None else None, C.byref(cnt), C.byref(nf), C.byref(nu), C.byref(st), C.byref(dst))
+    d = st.as_dict()
+    d["n_particles"] = int(cnt.value)
+    if table is None:
+        _check(rc)
+        return out, d
+    dd = _check_decayed(rc, dst, nf, nu, records=out, records_decayed=outd, sampler_stats=d)
+    return out, outd, d, dd
+
+
+def sample_flow_diff(cells, species, df, gla, cuts, pT_edges, slot, n_slots, opts=None, table=None, chosen_mc_id=None, slot_decayed=None,
+                     n_slots_decayed=0, n_events=1, seed=1, decay_seed=None, lifetime=0, y_cut=0.5, first_cell=0, fq=None, fast=0, T_avg=0.0,
+                     T_avg_switch=0.0, batch_events=0, muB_avg=0.0):
+    """is3d_sample_flow_diff: sample_flow with the pT bin of the edge table pT_edges as a second key of both sets of records.  Returns
+    (records, sampler stats) | (records, decayed records, sampler stats, decay stats)."""
+    cs, sps, ds, si, os_, _held = _pack_sampler(cells, species, df, gla, opts, n_events, seed, y_cut, first_cell, fq, fast, T_avg, T_avg_switch,
+                                                batch_events, muB_avg)
+    c = _pack_cuts(cuts)
+    edges = np.ascontiguousarray(pT_edges, dtype=np.float64)
+    slot = np.ascontiguousarray(slot, dtype=np.int32)
+    assert len(slot) == sps.n, (len(slot), sps.n)
+    r, out = _flow_diff_arrays(n_events, n_slots, len(edges) - 1)
+    rd, outd = _flow_diff_arrays(n_events, n_slots_decayed if table is not None else 0, len(edges) - 1)
+    ts = ch = sd = None
+    if table is not None:
+        ts, ch, _, keep = _decay_pack(table, chosen_mc_id, dict(pT=[1.0], phi=[0.0], y=[0.0]))
+        assert len(ch) == sps.n, (len(ch), sps.n)
+        sd = _slot_map(table, slot_decayed)
+    cnt, st, dst, nf, nu = C.c_int64(0), SamplerStats(), DecayMcStats(), C.c_int64(0), C.c_int64(0)
+    fn = load().is3d_sample_flow_diff
+    fn.argtypes = [C.POINTER(Cells), C.POINTER(Species), C.POINTER(DfTables), C.POINTER(SamplerInputs), C.POINTER(Options), C.POINTER(FlowCuts),
+                   C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(FlowDiffRecords), C.POINTER(DecayTable), C.POINTER(C.c_int64), C.c_void_p,
+                   C.c_int32, C.c_uint64, C.c_int32, C.POINTER(FlowDiffRecords), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                   C.POINTER(SamplerStats), C.POINTER(DecayMcStats)]
+    rc = fn(C.byref(cs), C.byref(sps), C.byref(ds), C.byref(si), C.byref(os_), C.byref(c), len(edges) - 1, edges.ctypes.data, slot.ctypes.data,
+            int(n_slots), C.byref(r), C.byref(ts) if ts is not None else None, ch.ctypes.data_as(C.POINTER(C.c_int64)) if ch is not None else None,
             sd.ctypes.data if sd is not None else None, int(n_slots_decayed), int(seed if decay_seed is None else decay_seed), int(lifetime),
             C.byref(rd) if table is not None else None, C.byref(cnt), C.byref(nf), C.byref(nu), C.byref(st), C.byref(dst))
     d = st.as_dict()

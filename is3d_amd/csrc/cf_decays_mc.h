@@ -7,6 +7,7 @@
 #include "../../include/is3d_amd.h"
 #include "cf_sampler_bins.h"
 #include "cf_sampler_flow.h"
+#include "cf_sampler_flow_diff.h"
 #include "cf_sampler_pairs.h"
 #include "cf_sampler_hbt.h"
 
@@ -54,6 +55,10 @@ struct DecayMcFlowRun {
     is3d_flow_cuts cuts;
     FlowThresholds thresholds;
     unsigned long long *block_dev;
+    // differential records (cf_sampler_flow_diff.h) instead: n_pT > 0 bins on the DEVICE edge table edges_dev[n_pT + 1]; the block then holds
+    // n_events * n_slots * n_pT * 51 words and the window stands beside the staged edges as well
+    int32_t n_pT = 0;
+    const double *edges_dev = nullptr;
 };
 // as decay_mc_bins_launch, every final particle going to the rule of cf_sampler_flow.h; form r.cuts.kernel_form
 hipError_t decay_mc_flow_launch(const DecayMcFlowRun &r, const is3d_particle *primaries_dev, int64_t n, int64_t first_particle);

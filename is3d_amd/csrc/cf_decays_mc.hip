@@ -311,15 +311,18 @@ __global__ void __launch_bounds__(kBinThreads) cf_decay_mc_bins(const McArgs a, 
 }
 
 // the flow pass: the final particle's momentum, built in registers, goes to the rule of cf_sampler_flow.h with slot[entry]; slot -1, a particle
-// outside the cuts or a primary whose event has no record adds nothing
+// outside the cuts or a primary whose event has no record adds nothing.  DIFF: the differential records of cf_sampler_flow_diff.h -- the
+// accepted particle's pT bin, by bisection over the edges the workgroup staged in LDS, makes its record that of the slot  slot * n_pT + bin
 struct McFlowArgs {
     is3d_flow_cuts c;
     is3d::FlowThresholds t;
     int32_t n_slots, n_events, window;
     const int32_t *slot;              // [table entries]
     unsigned long long *records, *tally;   // tally[kBinTallies]
+    int32_t n_pT;                     // DIFF only
+    const double *edges;              // DIFF only: [n_pT + 1]
 };
-template <bool PRIVATE>
+template <bool PRIVATE, bool DIFF>
 struct SinkFlow {
     static constexpr bool kMomenta = true;
     const McFlowArgs &f;
@@ -327,12 +330,13 @@ struct SinkFlow {
     bool live;
     __device__ __forceinline__ void operator()(int, const Pending &c, const is3d_particle &q)
     {
-        const int s = f.slot[c.e];
+        int s = f.slot[c.e];
         if (!live || s < 0 || s >= f.n_slots) return;
         is3d_particle o;
         o.E = c.E; o.px = c.px; o.py = c.py; o.pz = c.pz;
         const int region = is3d::flow_region(f.c, f.t, o);
         if (region < 0) return;
+        if (DIFF) s = is3d::flow_diff_slot(s, f.n_pT, is3d::flow_diff_bin_lds(f.n_pT, o));
         long long re[IS3D_FLOW_HARMONICS], im[IS3D_FLOW_HARMONICS];
         is3d::flow_terms(o, re, im);
         is3d::flow_add_particle<PRIVATE>(target, q.event, s, region, re, im);
@@ -344,16 +348,18 @@ struct SinkFlow {
 // primaries' order: PRIVATE keeps the records of `window` events from the event of the slice's first primary in LDS (dynamic, beside the
 // static tally words) and flushes the non-zero words once; products of a primary outside the window, and every product of the global form,
 // add to global memory.  The threads of a wave reach their final particles at different times, so there is no per-wave combine here.
-template <bool PRIVATE>
+template <bool PRIVATE, bool DIFF>
 __global__ void __launch_bounds__(kBinThreads) cf_decay_mc_flow(const McArgs a, const McFlowArgs f, const int64_t slice)
 {
     extern __shared__ unsigned long long priv[];
     __shared__ unsigned long long blk[kBinTallies];
     if (threadIdx.x < kBinTallies) blk[threadIdx.x] = 0ULL;
     const int64_t begin = (int64_t)blockIdx.x * slice, end = begin + slice < a.n ? begin + slice : a.n;
-    is3d::FlowTarget target{priv, f.records, 0, f.window, f.n_slots, f.n_events};
+    const int n_keys = DIFF ? f.n_slots * f.n_pT : f.n_slots;
+    is3d::FlowTarget target{priv, f.records, 0, f.window, n_keys, f.n_events};
+    if (DIFF) is3d::flow_diff_stage_edges(f.edges, f.n_pT);
     if (PRIVATE)
-        target.base = is3d::flow_window_open<kBinThreads>(priv, (int64_t)f.window * f.n_slots * is3d::kFlowRecordWords, begin, end, [&](int64_t i) {
+        target.base = is3d::flow_window_open<kBinThreads>(priv, (int64_t)f.window * n_keys * is3d::kFlowRecordWords, begin, end, [&](int64_t i) {
             const int e = a.in[i].event;
             return e >= 0 && e < f.n_events ? e : -1;
         });
@@ -364,7 +370,7 @@ __global__ void __launch_bounds__(kBinThreads) cf_decay_mc_flow(const McArgs a, 
         const int64_t i = i0 + threadIdx.x;
         if (i < end) {
             const int event = a.in[i].event;
-            SinkFlow<PRIVATE> sink{f, target, event >= 0 && event < f.n_events};
+            SinkFlow<PRIVATE, DIFF> sink{f, target, event >= 0 && event < f.n_events};
             finals += (unsigned long long)decay_tree(a, i, tally, sink);
         }
     }
@@ -905,7 +911,9 @@ extern "C" int is3d_decay_particles_binned(const is3d_decay_table *table, int32_
 hipError_t is3d::decay_mc_flow_launch(const DecayMcFlowRun &r, const is3d_particle *primaries_dev, int64_t n, int64_t first_particle)
 {
     if (n <= 0) return hipSuccess;
-    const int window = flow_window_events(r.n_events, r.n_slots, kBinTallies);
+    const bool diff = r.n_pT > 0;
+    const int n_keys = diff ? r.n_slots * r.n_pT : r.n_slots;
+    const int window = diff ? flow_diff_window_events(r.n_events, r.n_slots, r.n_pT, kBinTallies) : flow_window_events(r.n_events, r.n_slots, kBinTallies);
     const int form = r.cuts.kernel_form;
     if (form == 2 && window < 1) return hipErrorInvalidValue;
     const bool priv = form == 2 || (form == 0 && window >= 1);
@@ -917,24 +925,29 @@ hipError_t is3d::decay_mc_flow_launch(const DecayMcFlowRun &r, const is3d_partic
     a.first = first_particle;
     a.seed = r.seed;
     a.lifetime = r.lifetime;
-    const int64_t words = (int64_t)r.n_events * r.n_slots * kFlowRecordWords;
-    const McFlowArgs f{r.cuts, r.thresholds, r.n_slots, r.n_events, window, r.slot_dev, r.block_dev, r.block_dev + words};
+    const int64_t words = (int64_t)r.n_events * n_keys * kFlowRecordWords;
+    const McFlowArgs f{r.cuts, r.thresholds, r.n_slots, r.n_events, window, r.slot_dev, r.block_dev, r.block_dev + words, r.n_pT, r.edges_dev};
+    const size_t lds = priv ? (size_t)window * n_keys * kFlowRecordWords * sizeof(unsigned long long) : 0;
     const int64_t trips = (n + kBinThreads - 1) / kBinThreads;
     const int64_t blocks0 = priv ? std::min<int64_t>(trips, kBinPrivateBlocks) : trips;
     const int64_t slice = ((n + blocks0 - 1) / blocks0 + kBinThreads - 1) / kBinThreads * kBinThreads;
     const unsigned blocks = (unsigned)((n + slice - 1) / slice);
-    if (priv)
-        hipLaunchKernelGGL(cf_decay_mc_flow<true>, dim3(blocks), dim3(kBinThreads),
-                           (size_t)window * r.n_slots * kFlowRecordWords * sizeof(unsigned long long), nullptr, a, f, slice);
-    else
-        hipLaunchKernelGGL(cf_decay_mc_flow<false>, dim3(blocks), dim3(kBinThreads), 0, nullptr, a, f, slice);
+    if (diff) {
+        if (priv) hipLaunchKernelGGL((cf_decay_mc_flow<true, true>), dim3(blocks), dim3(kBinThreads), lds, nullptr, a, f, slice);
+        else hipLaunchKernelGGL((cf_decay_mc_flow<false, true>), dim3(blocks), dim3(kBinThreads), 0, nullptr, a, f, slice);
+    } else {
+        if (priv) hipLaunchKernelGGL((cf_decay_mc_flow<true, false>), dim3(blocks), dim3(kBinThreads), lds, nullptr, a, f, slice);
+        else hipLaunchKernelGGL((cf_decay_mc_flow<false, false>), dim3(blocks), dim3(kBinThreads), 0, nullptr, a, f, slice);
+    }
     return hipGetLastError();
 }
 
-extern "C" int is3d_decay_particles_flow(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
-                                         const is3d_decay_mc_inputs *in, int64_t n_particles, const is3d_particle *particles,
-                                         const int32_t *slot, int32_t n_slots, const is3d_flow_cuts *cuts, int32_t n_events,
-                                         const is3d_flow_records *records, int64_t *n_final, int64_t *n_unbinned, is3d_decay_mc_stats *stats)
+// the one body of is3d_decay_particles_flow (diff == NULL: records) and is3d_decay_particles_flow_diff (diff: the differential records on the
+// table pT_edges[n_pT + 1], which are flow records of n_slots * n_pT slots)
+static int decay_particles_flow(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id, const is3d_decay_mc_inputs *in,
+                                int64_t n_particles, const is3d_particle *particles, const int32_t *slot, int32_t n_slots, const is3d_flow_cuts *cuts,
+                                bool differential, int32_t n_pT, const double *pT_edges, int32_t n_events, const is3d_flow_records *plain,
+                                const is3d_flow_diff_records *diff, int64_t *n_final, int64_t *n_unbinned, is3d_decay_mc_stats *stats)
 {
     if (!table || !chosen_mc_id || !in || !n_final || !n_unbinned)
         return set_error(IS3D_EINVAL, "table, chosen_mc_id, in, n_final and n_unbinned are required");
@@ -946,7 +959,13 @@ extern "C" int is3d_decay_particles_flow(const is3d_decay_table *table, int32_t 
     tb.n_chosen = n_chosen;
     if (int rc = check_list_species(n_chosen, n_particles, particles)) return rc;
     if (table->n < 1) return set_error(IS3D_EINVAL, "decay table: n = %d", table->n);
-    if (int rc = is3d::flow_check_args(cuts, n_events, n_slots, slot, table->n, records, kBinTallies)) return rc;
+    if (int rc = differential ? is3d::flow_diff_check_args(cuts, n_pT, pT_edges, n_events, n_slots, slot, table->n, diff, kBinTallies)
+                              : is3d::flow_check_args(cuts, n_events, n_slots, slot, table->n, plain, kBinTallies))
+        return rc;
+    const is3d_flow_records view = differential ? is3d::flow_diff_view(*diff) : *plain;
+    const is3d_flow_records *records = &view;
+    if (differential) n_slots *= n_pT;                 // from here on: the slots of the block
+    else n_pT = 0;
     for (int64_t i = 0; i < n_particles; i++)
         if (particles[i].event < 0 || particles[i].event >= n_events)
             return set_error(IS3D_EINVAL, "particle %lld: event %d outside the %d events", (long long)i, particles[i].event, n_events);
@@ -967,10 +986,12 @@ extern "C" int is3d_decay_particles_flow(const is3d_decay_table *table, int32_t 
     DevBuf<is3d_particle> d_in;
     DevBuf<int32_t> d_slot;
     DevBuf<unsigned long long> d_block;
+    DevBuf<double> d_edges;
     const size_t words = (size_t)n_events * n_slots * is3d::kFlowRecordWords;
     if (int rc = table_upload(tb, *table)) return rc;
     HIP_TRY(d_in.upload(particles, (size_t)n_particles));
     HIP_TRY(d_slot.upload(slot, (size_t)table->n));
+    if (differential) HIP_TRY(d_edges.upload(pT_edges, (size_t)n_pT + 1));
     HIP_TRY(d_block.alloc(words + kBinTallies));
     HIP_TRY(hipMemsetAsync(d_block.p, 0, (words + kBinTallies) * sizeof(unsigned long long), nullptr));
     Events ev;
@@ -978,7 +999,8 @@ extern "C" int is3d_decay_particles_flow(const is3d_decay_table *table, int32_t 
     HIP_TRY(hipDeviceSynchronize());
     const auto t1 = std::chrono::steady_clock::now();
     // ---- the one pass ----
-    const is3d::DecayMcFlowRun run{&tb, d_slot.p, n_slots, n_events, in->seed, in->lifetime, *cuts, is3d::flow_thresholds(*cuts), d_block.p};
+    const is3d::DecayMcFlowRun run{&tb, d_slot.p, differential ? n_slots / n_pT : n_slots, n_events, in->seed, in->lifetime, *cuts,
+                                   is3d::flow_thresholds(*cuts), d_block.p, n_pT, d_edges.p};
     HIP_TRY(hipEventRecord(ev.e[0], nullptr));
     HIP_TRY(is3d::decay_mc_flow_launch(run, d_in.p, n_particles, in->first_particle));
     HIP_TRY(hipEventRecord(ev.e[1], nullptr));
@@ -998,6 +1020,25 @@ extern "C" int is3d_decay_particles_flow(const is3d_decay_table *table, int32_t 
     if (stats) *stats = st;
     if (rc) return rc;
     return is3d::flow_records_check(records, n_events, n_slots);
+}
+
+extern "C" int is3d_decay_particles_flow(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
+                                         const is3d_decay_mc_inputs *in, int64_t n_particles, const is3d_particle *particles,
+                                         const int32_t *slot, int32_t n_slots, const is3d_flow_cuts *cuts, int32_t n_events,
+                                         const is3d_flow_records *records, int64_t *n_final, int64_t *n_unbinned, is3d_decay_mc_stats *stats)
+{
+    return decay_particles_flow(table, n_chosen, chosen_mc_id, in, n_particles, particles, slot, n_slots, cuts, false, 0, nullptr, n_events, records,
+                                nullptr, n_final, n_unbinned, stats);
+}
+
+extern "C" int is3d_decay_particles_flow_diff(const is3d_decay_table *table, int32_t n_chosen, const int64_t *chosen_mc_id,
+                                              const is3d_decay_mc_inputs *in, int64_t n_particles, const is3d_particle *particles,
+                                              const int32_t *slot, int32_t n_slots, const is3d_flow_cuts *cuts, int32_t n_pT,
+                                              const double *pT_edges, int32_t n_events, const is3d_flow_diff_records *records, int64_t *n_final,
+                                              int64_t *n_unbinned, is3d_decay_mc_stats *stats)
+{
+    return decay_particles_flow(table, n_chosen, chosen_mc_id, in, n_particles, particles, slot, n_slots, cuts, true, n_pT, pT_edges, n_events,
+                                nullptr, records, n_final, n_unbinned, stats);
 }
 
 // ---- decayed into pair histograms: one decay pass into the occupancies, then cf_pair_correlate ----

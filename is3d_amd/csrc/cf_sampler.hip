@@ -46,6 +46,7 @@
 #include "cf_plan_geometry.h"
 #include "cf_sampler_bins.h"
 #include "cf_sampler_flow.h"
+#include "cf_sampler_flow_diff.h"
 #include "cf_sampler_pairs.h"
 #include "cf_sampler_hbt.h"
 #include "cf_decays_mc.h"
@@ -334,7 +335,7 @@ struct is3d_sampler_plan {
     DevMem d_drawn, d_emits, d_active, d_nactive, d_cdf;
     DevMem d_particles, d_hist;             // a binned run: one batch of particles (list-and-bin only); the histograms, then the yields
     DevMem d_hist_decayed, d_slot;          // a decayed-and-binned run: the second block (histograms, yields, tallies) and the slot map
-    DevMem d_flow, d_flow_decayed, d_flow_slot, d_flow_slot_decayed;   // a flow run: the record blocks (the decayed one with its tallies) and the slot maps
+    DevMem d_flow, d_flow_decayed, d_flow_slot, d_flow_slot_decayed, d_flow_edges;   // a flow run: the record blocks (the decayed one with its tallies) and the slot maps
     DevMem d_pair_occ, d_pair_occ_decayed, d_pair_out, d_pair_slot, d_pair_slot_decayed;   // a pair run: the occupancy blocks (the decayed one behind its tallies), the histograms, the slot maps
     int64_t cap_cells = 0, cap_bt = 0;      // what the workspaces above were sized for
     int64_t cap_list = 0;                   // ... d_counts and d_offsets, which a fused binned run never has
@@ -651,6 +652,10 @@ struct FlowRun {
     // twice into records that are paired (hbt_decayed); the histograms stay in the two runs
     is3d::HbtRun *hbt, *hbt_decayed;
     const is3d::DecayMcHbtRun *hbt_decay;
+    // a differential flow run (n_pT > 0): records_dev holds n_slots * n_pT records per event and the batch's list goes through
+    // cf_sampler_flow_diff with the DEVICE edge table edges_dev[n_pT + 1]; decay carries the same table
+    int32_t n_pT;
+    const double *edges_dev;
 };
 int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t n, const double *x_dev, const double *y_dev, int32_t n_events,
                     uint64_t seed, int64_t first_cell, int32_t batch_events, is3d_particle *particles_dev, int64_t capacity, const BinRun *bin,
@@ -818,7 +823,10 @@ int sampler_batches(is3d_sampler_plan *P, const is3d::SamplerVariant &v, int64_t
         if (flow && flow->occ_dev && batch_total > 0)
             HIP_TRY(is3d::pair_cells_launch(*flow->pair_bins, *flow->pair_tables, n_events, flow->n_slots, flow->slot_dev, sp.npart,
                                             P->d_particles.as<is3d_particle>(), batch_total, flow->occ_dev));
-        if (flow && flow->records_dev && batch_total > 0)
+        if (flow && flow->records_dev && flow->n_pT > 0 && batch_total > 0)
+            HIP_TRY(is3d::flow_diff_launch(flow->cuts, flow->thresholds, flow->n_pT, flow->edges_dev, n_events, flow->n_slots, flow->slot_dev, sp.npart,
+                                           P->d_particles.as<is3d_particle>(), batch_total, flow->records_dev, flow->cuts.kernel_form));
+        else if (flow && flow->records_dev && batch_total > 0)
             HIP_TRY(is3d::flow_launch(flow->cuts, flow->thresholds, n_events, flow->n_slots, flow->slot_dev, sp.npart, P->d_particles.as<is3d_particle>(),
                                       batch_total, flow->records_dev, flow->cuts.kernel_form));
         if (flow && flow->hbt && batch_total > 0)
@@ -1296,13 +1304,28 @@ extern "C" int is3d_sample_decayed_binned(const is3d_cells *cells, const is3d_sp
 // ------------------------------------------------------------------------------------------------
 // per-event flow records: each event batch's list, in the plan's workspace, through cf_sampler_flow and (with a table) cf_decay_mc_flow
 // ------------------------------------------------------------------------------------------------
-extern "C" int is3d_sampler_plan_execute_flow(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev,
-                                              int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
-                                              const is3d_flow_cuts *cuts, const int32_t *slot, int32_t n_slots,
-                                              const is3d_flow_records *records, const is3d_decay_mc_table *table, const int32_t *slot_decayed,
-                                              int32_t n_slots_decayed, uint64_t decay_seed, int32_t lifetime,
-                                              const is3d_flow_records *records_decayed, int64_t *n_particles, int64_t *n_final,
-                                              int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats)
+namespace {
+// The records of a flow entry, plain or differential: the differential ones on the edge table pT_edges[n_pT + 1] are
+// flow records of n_slots * n_pT slots, so one body serves is3d_sampler_plan_execute_flow and is3d_sampler_plan_execute_flow_diff.
+struct FlowRecordsArg {
+    const is3d_flow_records *plain, *plain_decayed;
+    const is3d_flow_diff_records *diff, *diff_decayed;
+    int32_t n_pT;                     // 0: plain
+    const double *pT_edges;
+    bool differential;
+    int check(const is3d_flow_cuts *cuts, int32_t n_events, int32_t n_slots, const int32_t *slot, int32_t n_species, bool decayed) const
+    {
+        const int static_words = decayed ? is3d::kDecayMcBinTallies : 0;
+        if (differential)
+            return is3d::flow_diff_check_args(cuts, n_pT, pT_edges, n_events, n_slots, slot, n_species, decayed ? diff_decayed : diff, static_words);
+        return is3d::flow_check_args(cuts, n_events, n_slots, slot, n_species, decayed ? plain_decayed : plain, static_words);
+    }
+};
+
+int execute_flow(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev, int32_t n_events, uint64_t seed,
+                 int64_t first_cell, int32_t batch_events, const is3d_flow_cuts *cuts, const FlowRecordsArg &arg, const int32_t *slot, int32_t n_slots,
+                 const is3d_decay_mc_table *table, const int32_t *slot_decayed, int32_t n_slots_decayed, uint64_t decay_seed, int32_t lifetime,
+                 int64_t *n_particles, int64_t *n_final, int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats)
 {
     using is3d::set_error;
     if (!P || !cells || !n_particles || (table && (!n_final || !n_unbinned))) return set_error(IS3D_EINVAL, "null argument");
@@ -1311,10 +1334,10 @@ extern "C" int is3d_sampler_plan_execute_flow(is3d_sampler_plan *P, const is3d_c
     if (n_unbinned) *n_unbinned = 0;
     if (stats) memset(stats, 0, sizeof *stats);
     if (decay_stats) memset(decay_stats, 0, sizeof *decay_stats);
-    if (int rc = is3d::flow_check_args(cuts, n_events, n_slots, slot, P->sp.npart, records, 0)) return rc;
+    if (int rc = arg.check(cuts, n_events, n_slots, slot, P->sp.npart, false)) return rc;
     const int32_t n_entries = table ? is3d::decay_mc_table_entries(table) : 0;
     if (table) {
-        if (int rc = is3d::flow_check_args(cuts, n_events, n_slots_decayed, slot_decayed, n_entries, records_decayed, is3d::kDecayMcBinTallies)) return rc;
+        if (int rc = arg.check(cuts, n_events, n_slots_decayed, slot_decayed, n_entries, true)) return rc;
         if (is3d::decay_mc_table_chosen(table) != P->sp.npart)
             return set_error(IS3D_EINVAL, "the decay table was created for %d chosen species, the sampler plan for %d", is3d::decay_mc_table_chosen(table),
                              P->sp.npart);
@@ -1324,12 +1347,17 @@ extern "C" int is3d_sampler_plan_execute_flow(is3d_sampler_plan *P, const is3d_c
     if (int rc = bind_cells(P, cells, first_cell)) return rc;
     const int64_t n_cells = cells->n_cells;
     if (n_cells < 0 || n_cells + first_cell > 0xffffffffLL) return set_error(IS3D_EINVAL, "cell indices must fit 32 bits for the counter-based streams");
-    const size_t words = (size_t)n_events * n_slots * is3d::kFlowRecordWords;
-    const size_t words_d = table ? (size_t)n_events * n_slots_decayed * is3d::kFlowRecordWords : 0;
+    // the blocks hold n_keys = n_slots (* n_pT) records per event
+    const int32_t n_pT = arg.differential ? arg.n_pT : 0, n_keys = n_pT ? n_slots * n_pT : n_slots, n_keys_decayed = n_pT ? n_slots_decayed * n_pT : n_slots_decayed;
+    const is3d_flow_records view = arg.differential ? is3d::flow_diff_view(*arg.diff) : *arg.plain;
+    const is3d_flow_records view_decayed = !table ? is3d_flow_records{} : (arg.differential ? is3d::flow_diff_view(*arg.diff_decayed) : *arg.plain_decayed);
+    const is3d_flow_records *records = &view, *records_decayed = &view_decayed;
+    const size_t words = (size_t)n_events * n_keys * is3d::kFlowRecordWords;
+    const size_t words_d = table ? (size_t)n_events * n_keys_decayed * is3d::kFlowRecordWords : 0;
     is3d_decay_mc_stats dst{};
     if (table) is3d::decay_mc_table_stats(table, &dst);
-    is3d::flow_records_zero(records, n_events, n_slots);
-    if (table) is3d::flow_records_zero(records_decayed, n_events, n_slots_decayed);
+    is3d::flow_records_zero(records, n_events, n_keys);
+    if (table) is3d::flow_records_zero(records_decayed, n_events, n_keys_decayed);
     if (n_cells == 0) {
         if (decay_stats) *decay_stats = dst;
         return IS3D_OK;
@@ -1342,6 +1370,11 @@ extern "C" int is3d_sampler_plan_execute_flow(is3d_sampler_plan *P, const is3d_c
     HIP_TRY(grow(P->d_flow_slot, (size_t)P->sp.npart * sizeof(int32_t)));
     HIP_TRY(hipMemcpy(P->d_flow_slot.p, slot, (size_t)P->sp.npart * sizeof(int32_t), hipMemcpyHostToDevice));
     const is3d::FlowThresholds th = is3d::flow_thresholds(*cuts);
+    if (n_pT) {
+        HIP_TRY(grow(P->d_flow_edges, ((size_t)n_pT + 1) * sizeof(double)));
+        HIP_TRY(hipMemcpy(P->d_flow_edges.p, arg.pT_edges, ((size_t)n_pT + 1) * sizeof(double), hipMemcpyHostToDevice));
+    }
+    const double *edges_dev = n_pT ? P->d_flow_edges.as<double>() : nullptr;
     is3d::DecayMcFlowRun drun{};
     if (table) {
         HIP_TRY(grow(P->d_flow_decayed, (words_d + is3d::kDecayMcBinTallies) * sizeof(int64_t)));
@@ -1349,9 +1382,11 @@ extern "C" int is3d_sampler_plan_execute_flow(is3d_sampler_plan *P, const is3d_c
         HIP_TRY(grow(P->d_flow_slot_decayed, (size_t)n_entries * sizeof(int32_t)));
         HIP_TRY(hipMemcpy(P->d_flow_slot_decayed.p, slot_decayed, (size_t)n_entries * sizeof(int32_t), hipMemcpyHostToDevice));
         drun = is3d::DecayMcFlowRun{table, P->d_flow_slot_decayed.as<int32_t>(), n_slots_decayed, n_events, decay_seed, lifetime, *cuts, th,
-                                    P->d_flow_decayed.as<unsigned long long>()};
+                                    P->d_flow_decayed.as<unsigned long long>(), n_pT, edges_dev};
     }
     FlowRun run{*cuts, th, n_slots, P->d_flow_slot.as<int32_t>(), P->d_flow.as<unsigned long long>(), table ? &drun : nullptr, 0.0, nullptr, nullptr, nullptr, nullptr};
+    run.n_pT = n_pT;
+    run.edges_dev = edges_dev;
     int64_t listed = 0;
     if (int rc = sampler_batches(P, P->viscous, n_cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, nullptr, 0, nullptr, false, &listed, stats,
                                  nullptr, nullptr, &run))
@@ -1359,14 +1394,14 @@ extern "C" int is3d_sampler_plan_execute_flow(is3d_sampler_plan *P, const is3d_c
     *n_particles = listed;
     std::vector<int64_t> h(std::max(words, words_d + is3d::kDecayMcBinTallies));
     HIP_TRY(hipMemcpy(h.data(), P->d_flow.p, words * sizeof(int64_t), hipMemcpyDeviceToHost));
-    is3d::flow_records_scatter(h.data(), records, n_events, n_slots);
+    is3d::flow_records_scatter(h.data(), records, n_events, n_keys);
     int rc_t = IS3D_OK;
     if (table) {
         HIP_TRY(hipMemcpy(h.data(), P->d_flow_decayed.p, (words_d + is3d::kDecayMcBinTallies) * sizeof(int64_t), hipMemcpyDeviceToHost));
-        is3d::flow_records_scatter(h.data(), records_decayed, n_events, n_slots_decayed);
+        is3d::flow_records_scatter(h.data(), records_decayed, n_events, n_keys_decayed);
         rc_t = is3d::decay_mc_bins_tallies((const unsigned long long *)(h.data() + words_d), &dst);
         int64_t kept = 0;
-        for (size_t j = 0; j < (size_t)n_events * n_slots_decayed; j++) kept += records_decayed->M[j * is3d::kFlowRegions];
+        for (size_t j = 0; j < (size_t)n_events * n_keys_decayed; j++) kept += records_decayed->M[j * is3d::kFlowRegions];
         dst.n_primaries = listed;
         dst.ms_bin = run.ms_decay;
         *n_final = dst.n_final;
@@ -1374,8 +1409,35 @@ extern "C" int is3d_sampler_plan_execute_flow(is3d_sampler_plan *P, const is3d_c
         if (decay_stats) *decay_stats = dst;
     }
     if (rc_t) return rc_t;
-    if (int rc = is3d::flow_records_check(records, n_events, n_slots)) return rc;
-    return table ? is3d::flow_records_check(records_decayed, n_events, n_slots_decayed) : IS3D_OK;
+    if (int rc = is3d::flow_records_check(records, n_events, n_keys)) return rc;
+    return table ? is3d::flow_records_check(records_decayed, n_events, n_keys_decayed) : IS3D_OK;
+}
+}  // namespace
+
+extern "C" int is3d_sampler_plan_execute_flow(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev,
+                                              int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
+                                              const is3d_flow_cuts *cuts, const int32_t *slot, int32_t n_slots,
+                                              const is3d_flow_records *records, const is3d_decay_mc_table *table, const int32_t *slot_decayed,
+                                              int32_t n_slots_decayed, uint64_t decay_seed, int32_t lifetime,
+                                              const is3d_flow_records *records_decayed, int64_t *n_particles, int64_t *n_final,
+                                              int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats)
+{
+    const FlowRecordsArg arg{records, records_decayed, nullptr, nullptr, 0, nullptr, false};
+    return execute_flow(P, cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, cuts, arg, slot, n_slots, table, slot_decayed, n_slots_decayed,
+                        decay_seed, lifetime, n_particles, n_final, n_unbinned, stats, decay_stats);
+}
+
+extern "C" int is3d_sampler_plan_execute_flow_diff(is3d_sampler_plan *P, const is3d_cells *cells, const double *x_dev, const double *y_dev,
+                                                   int32_t n_events, uint64_t seed, int64_t first_cell, int32_t batch_events,
+                                                   const is3d_flow_cuts *cuts, int32_t n_pT, const double *pT_edges, const int32_t *slot,
+                                                   int32_t n_slots, const is3d_flow_diff_records *records, const is3d_decay_mc_table *table,
+                                                   const int32_t *slot_decayed, int32_t n_slots_decayed, uint64_t decay_seed, int32_t lifetime,
+                                                   const is3d_flow_diff_records *records_decayed, int64_t *n_particles, int64_t *n_final,
+                                                   int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats)
+{
+    const FlowRecordsArg arg{nullptr, nullptr, records, records_decayed, n_pT, pT_edges, true};
+    return execute_flow(P, cells, x_dev, y_dev, n_events, seed, first_cell, batch_events, cuts, arg, slot, n_slots, table, slot_decayed, n_slots_decayed,
+                        decay_seed, lifetime, n_particles, n_final, n_unbinned, stats, decay_stats);
 }
 
 // host-pointer one-shot: create, upload, execute, destroy (the table included)
@@ -1409,6 +1471,42 @@ extern "C" int is3d_sample_flow(const is3d_cells *cells, const is3d_species *spe
     const int rc = is3d_sampler_plan_execute_flow(r.P, &r.dc, r.xy[0], r.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events, cuts, slot,
                                                   n_slots, records, tg.t, slot_decayed, n_slots_decayed, decay_seed, lifetime, records_decayed,
                                                   n_particles, n_final, n_unbinned, stats, decay_stats);
+    if (stats) stats->ms_h2d = r.ms_h2d;
+    return rc;
+}
+
+extern "C" int is3d_sample_flow_diff(const is3d_cells *cells, const is3d_species *species, const is3d_df_tables *df, const is3d_sampler_inputs *in,
+                                     const is3d_options *opts, const is3d_flow_cuts *cuts, int32_t n_pT, const double *pT_edges, const int32_t *slot,
+                                     int32_t n_slots, const is3d_flow_diff_records *records, const is3d_decay_table *table,
+                                     const int64_t *chosen_mc_id, const int32_t *slot_decayed, int32_t n_slots_decayed, uint64_t decay_seed,
+                                     int32_t lifetime, const is3d_flow_diff_records *records_decayed, int64_t *n_particles, int64_t *n_final,
+                                     int64_t *n_unbinned, is3d_sampler_stats *stats, is3d_decay_mc_stats *decay_stats)
+{
+    using is3d::set_error;
+    if (!cells || !species || !df || !in || !opts || !n_particles || (table && (!chosen_mc_id || !n_final || !n_unbinned)))
+        return set_error(IS3D_EINVAL, "null argument");
+    *n_particles = 0;
+    if (n_final) *n_final = 0;
+    if (n_unbinned) *n_unbinned = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (decay_stats) memset(decay_stats, 0, sizeof *decay_stats);
+    if (species->n < 1) return set_error(IS3D_EINVAL, "the species list is empty");
+    if (int rc = is3d::flow_diff_check_args(cuts, n_pT, pT_edges, in->n_events, n_slots, slot, species->n, records, 0)) return rc;
+    if (table) {
+        if (table->n < 1) return set_error(IS3D_EINVAL, "decay table: n = %d", table->n);
+        if (int rc = is3d::flow_diff_check_args(cuts, n_pT, pT_edges, in->n_events, n_slots_decayed, slot_decayed, table->n, records_decayed,
+                                                is3d::kDecayMcBinTallies))
+            return rc;
+        if (int rc = is3d::decay_mc_table_check(table, species->n, chosen_mc_id)) return rc;
+    }
+    StagedRun r;
+    if (int rc = stage_run(r, cells, species, df, in, opts)) return rc;
+    struct TableGuard { is3d_decay_mc_table *t = nullptr; ~TableGuard() { is3d_decay_mc_table_destroy(t); } } tg;
+    if (table)
+        if (int rc = is3d_decay_mc_table_create(&tg.t, table, species->n, chosen_mc_id, r.P->device)) return rc;
+    const int rc = is3d_sampler_plan_execute_flow_diff(r.P, &r.dc, r.xy[0], r.xy[1], in->n_events, in->seed, in->first_cell, in->batch_events, cuts, n_pT,
+                                                       pT_edges, slot, n_slots, records, tg.t, slot_decayed, n_slots_decayed, decay_seed, lifetime,
+                                                       records_decayed, n_particles, n_final, n_unbinned, stats, decay_stats);
     if (stats) stats->ms_h2d = r.ms_h2d;
     return rc;
 }

@@ -130,6 +130,70 @@ __device__ __forceinline__ void flow_add_particle(const FlowTarget &t, int ev, i
     }
 }
 
+__device__ __forceinline__ long long flow_wave_sum(long long v)
+{
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// The adds of ONE trip of a list kernel: every lane of every wave calls this, act = the lane holds a particle of region >= 0 for the record
+// (ev, s).  COMBINE: the lanes of a wave that hold the same (event, slot, region) key sum their 17 values with cross-lane adds and ONE lane
+// does the 17 adds (34 with a sub-event) -- a ballot loop over the distinct keys of the wave, which retires its leader's key on every trip.
+template <bool PRIVATE, bool COMBINE>
+__device__ __forceinline__ void flow_add_trip(const FlowTarget &t, int lane, bool act, int ev, int s, int region, const long long *re,
+                                              const long long *im)
+{
+    if (COMBINE) {
+        const long long key = act ? ((long long)ev * t.n_slots + s) * kFlowRegions + region : -1;
+        unsigned long long rem = __ballot(act);
+        while (rem) {                                  // wave-uniform; every trip retires the key of its leader
+            const int leader = __ffsll((long long)rem) - 1;
+            const long long k = __shfl(key, leader);
+            const bool mine = act && key == k;
+            const unsigned long long match = __ballot(mine);
+            rem &= ~match;
+            const bool alone = (match & (match - 1)) == 0;
+            const bool add = lane == leader;
+            const long long cnt = __popcll(match);
+            if (add) {
+                flow_add_word<PRIVATE>(t, ev, s, 0, (unsigned long long)cnt);
+                if (region) flow_add_word<PRIVATE>(t, ev, s, region * kFlowRegionWords, (unsigned long long)cnt);
+            }
+            for (int m = 0; m < IS3D_FLOW_HARMONICS; m++) {
+                long long vr = mine ? re[m] : 0, vi = mine ? im[m] : 0;
+                if (!alone) { vr = flow_wave_sum(vr); vi = flow_wave_sum(vi); }
+                if (add) {
+                    flow_add_word<PRIVATE>(t, ev, s, 1 + m, (unsigned long long)vr);      // two's complement: signed sums
+                    flow_add_word<PRIVATE>(t, ev, s, 1 + IS3D_FLOW_HARMONICS + m, (unsigned long long)vi);
+                    if (region) {
+                        flow_add_word<PRIVATE>(t, ev, s, region * kFlowRegionWords + 1 + m, (unsigned long long)vr);
+                        flow_add_word<PRIVATE>(t, ev, s, region * kFlowRegionWords + 1 + IS3D_FLOW_HARMONICS + m,
+                                               (unsigned long long)vi);
+                    }
+                }
+            }
+        }
+    } else if (act) {
+        flow_add_particle<PRIVATE>(t, ev, s, region, re, im);
+    }
+}
+
+// the launch geometry of a list kernel of `threads` threads over n particles: contiguous slices, a multiple of the trip
+constexpr int kFlowPrivateBlocks = 512;                  // workgroup-private form: at most this many flushes
+constexpr int64_t kFlowPrivateParticles = 4096;          // ... and at least this many particles per workgroup
+constexpr int64_t kFlowGlobalBlocks = (int64_t)1 << 20;
+inline void flow_list_geometry(bool priv, int64_t n, int threads, int64_t *blocks, int64_t *slice)
+{
+    if (priv) {
+        int64_t b = (n + kFlowPrivateParticles - 1) / kFlowPrivateParticles;
+        b = b < 1 ? 1 : (b > kFlowPrivateBlocks ? kFlowPrivateBlocks : b);
+        *slice = ((n + b - 1) / b + threads - 1) / threads * threads;
+    } else {
+        *slice = ((n + kFlowGlobalBlocks - 1) / kFlowGlobalBlocks + threads - 1) / threads * threads;
+    }
+    *blocks = (n + *slice - 1) / *slice;
+}
+
 // The window of a workgroup that walks the slice [begin, end) in trips of THREADS: it starts at the event of the slice's first valid entry
 // (event_of(i) >= 0) -- the lowest thread that holds one names it, through two control words of the block, which is zeroed afterwards.
 // Every thread of the workgroup calls this with the same arguments; all leave the search together.  Returns the base (0: no valid entry).

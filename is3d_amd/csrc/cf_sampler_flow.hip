@@ -28,9 +28,6 @@ namespace is3d {
 namespace {
 
 constexpr int kFlowThreads = 256;
-constexpr int kFlowPrivateBlocks = 512;                  // workgroup-private form: at most this many flushes
-constexpr int64_t kFlowPrivateParticles = 4096;          // ... and at least this many particles per workgroup
-constexpr int64_t kFlowGlobalBlocks = (int64_t)1 << 20;
 constexpr bool kFlowPrivateCombine = false;              // measured: plain ds_add_u64 into the window is 4.6 times faster than combining first
 
 struct FlowArgs {
@@ -38,12 +35,6 @@ struct FlowArgs {
     FlowThresholds t;
     int n_events, n_slots, n_species, window;            // window: events in LDS (private form)
 };
-
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
 
 template <bool PRIVATE, bool COMBINE>
 __global__ void __launch_bounds__(kFlowThreads)
@@ -75,39 +66,7 @@ cf_sampler_flow(FlowArgs a, const int32_t *__restrict__ slot, const is3d_particl
             }
         }
         const bool act = region >= 0;
-        if (COMBINE) {
-            const long long key = act ? ((long long)ev * a.n_slots + s) * kFlowRegions + region : -1;
-            unsigned long long rem = __ballot(act);
-            while (rem) {                                  // wave-uniform; every trip retires the key of its leader
-                const int leader = __ffsll((long long)rem) - 1;
-                const long long k = __shfl(key, leader);
-                const bool mine = act && key == k;
-                const unsigned long long match = __ballot(mine);
-                rem &= ~match;
-                const bool alone = (match & (match - 1)) == 0;
-                const bool add = lane == leader;
-                const long long cnt = __popcll(match);
-                if (add) {
-                    flow_add_word<PRIVATE>(t, ev, s, 0, (unsigned long long)cnt);
-                    if (region) flow_add_word<PRIVATE>(t, ev, s, region * kFlowRegionWords, (unsigned long long)cnt);
-                }
-                for (int m = 0; m < IS3D_FLOW_HARMONICS; m++) {
-                    long long vr = mine ? re[m] : 0, vi = mine ? im[m] : 0;
-                    if (!alone) { vr = wave_sum(vr); vi = wave_sum(vi); }
-                    if (add) {
-                        flow_add_word<PRIVATE>(t, ev, s, 1 + m, (unsigned long long)vr);      // two's complement: signed sums
-                        flow_add_word<PRIVATE>(t, ev, s, 1 + IS3D_FLOW_HARMONICS + m, (unsigned long long)vi);
-                        if (region) {
-                            flow_add_word<PRIVATE>(t, ev, s, region * kFlowRegionWords + 1 + m, (unsigned long long)vr);
-                            flow_add_word<PRIVATE>(t, ev, s, region * kFlowRegionWords + 1 + IS3D_FLOW_HARMONICS + m,
-                                                   (unsigned long long)vi);
-                        }
-                    }
-                }
-            }
-        } else if (act) {
-            flow_add_particle<PRIVATE>(t, ev, s, region, re, im);
-        }
+        flow_add_trip<PRIVATE, COMBINE>(t, lane, act, ev, s, region, re, im);
     }
     if (PRIVATE) flow_window_flush<kFlowThreads>(t);
 }
@@ -116,13 +75,7 @@ template <bool PRIVATE, bool COMBINE>
 void launch(const FlowArgs &a, const int32_t *slot_dev, const is3d_particle *particles_dev, int64_t n, unsigned long long *records_dev)
 {
     int64_t blocks, slice;
-    if (PRIVATE) {
-        blocks = std::max<int64_t>(1, std::min<int64_t>(kFlowPrivateBlocks, (n + kFlowPrivateParticles - 1) / kFlowPrivateParticles));
-        slice = ((n + blocks - 1) / blocks + kFlowThreads - 1) / kFlowThreads * kFlowThreads;
-    } else {
-        slice = ((n + kFlowGlobalBlocks - 1) / kFlowGlobalBlocks + kFlowThreads - 1) / kFlowThreads * kFlowThreads;
-    }
-    blocks = (n + slice - 1) / slice;
+    flow_list_geometry(PRIVATE, n, kFlowThreads, &blocks, &slice);
     const size_t lds = PRIVATE ? (size_t)a.window * a.n_slots * kFlowRecordWords * sizeof(unsigned long long) : 0;
     hipLaunchKernelGGL((cf_sampler_flow<PRIVATE, COMBINE>), dim3((unsigned)blocks), dim3(kFlowThreads), lds, nullptr, a, slot_dev, particles_dev, n, slice,
                        records_dev);

@@ -8,7 +8,8 @@
 // Writes: average_thermodynamic_quantities.dat (not in mode 2); input/surface.dat.is3dcache; in results/, which must exist -- operation 1:
 //   dN_pTdpTdphidy*.dat, dN_dpTdphidy.dat, dN_dy_*.dat, vn_continuous/vn_*.dat, *_resonance_decays.dat; operation 0: spacetime_distribution/*.dat;
 //   operation 2: particle_list_osc.dat, particle_list_osc_decayed.dat, or the binned test files (test_sampler = 1; with test_sampler_decayed = 1
-//   also under results/decayed/; with test_sampler_flow = 1 the flow cumulants and multiplicities under results/flow/; with test_sampler_pairs = 1
+//   also under results/decayed/; with test_sampler_flow = 1 the flow cumulants and multiplicities under results/flow/ (and, with
+//   test_sampler_flow_diff = 1, the differential flow against pT beside them); with test_sampler_pairs = 1
 //   the two-particle correlations under results/pairs/; with test_sampler_hbt = 1 the HBT correlation functions and radii under results/hbt/);
 //   mode 5: S{t,x,y,n}.dat.
 #include <algorithm>
@@ -175,10 +176,12 @@ struct MemSurface { const is3d_cells *cells; const double *x, *y; };
 struct RunConfig {
     int operation, mode, hrg_eos, dimension, df_mode, include_baryon, include_bulk, include_shear, include_diff, regulate, outflow;
     // optional keys (absent: 0); an `is set` flag here has passed its checks
-    bool do_decays, decay_sampled, bin_on_device, bin_fused, vah_oversample, vah_bin_on_device, vah_sampler, test_sampler, bin_decayed, flow, pairs, hbt;
+    bool do_decays, decay_sampled, bin_on_device, bin_fused, vah_oversample, vah_bin_on_device, vah_sampler, test_sampler, bin_decayed, flow, flow_diff, pairs, hbt;
     is3d_hbt_bins hbt_bins;     // test_sampler_hbt = 1: hbt_y_cut, hbt_pT_min, hbt_pT_max, hbt_kT_min, hbt_kT_max, hbt_kT_bins, hbt_q_max, hbt_q_bins (defaults 0.5, 0.1, 1.5, 0.1, 0.9, 4, 0.1, 20)
     is3d_pair_bins pair_bins;   // test_sampler_pairs = 1: pairs_y_cut, pairs_pT_min, pairs_pT_max, pairs_y_bins, pairs_phi_bins (defaults 2.0, 0.2, 3.0, 32, 32)
     is3d_flow_cuts flow_cuts;   // test_sampler_flow = 1: flow_y_cut, flow_y_gap, flow_pT_min, flow_pT_max (defaults 1.0, 0.5, 0.2, 3.0)
+    // test_sampler_flow_diff = 1 (beside test_sampler_flow = 1): flow_diff_pt_bins uniform bins from flow_pT_min to flow_diff_pt_max (defaults 14, 3.0)
+    std::vector<double> flow_diff_edges;
     bool vah;               // mode 2 from files: the anisotropic-hydro surface, tables and routines
     bool feqmod;            // df_mode 3 / 4 of viscous hydro: the modified-equilibrium kernels
     const char *pdg_path;
@@ -203,6 +206,7 @@ static int parse_config(const RunParams &p, const MemSurface *mem, bool wants_re
     c.bin_fused = is_set("test_sampler_fused"); c.vah_sampler = is_set("vah_sampler"); c.vah_oversample = is_set("vah_oversample");
     c.vah_bin_on_device = is_set("vah_sampler_on_device"); c.bin_decayed = is_set("test_sampler_decayed");
     c.flow = is_set("test_sampler_flow");
+    c.flow_diff = is_set("test_sampler_flow_diff");
     c.pairs = is_set("test_sampler_pairs");
     c.hbt = is_set("test_sampler_hbt");
     // test_sampler is a sampler key: optional where a check only looks at it, required (with the missing-key message) where a key depends on it
@@ -361,6 +365,26 @@ static int parse_config(const RunParams &p, const MemSurface *mem, bool wants_re
             if (stat(dir, &sb) != 0 || !S_ISDIR(sb.st_mode))
                 DIE("test_sampler_flow = 1: the directory %s is missing; create it or set test_sampler_flow = 0", dir);
         }
+    }
+    // test_sampler_flow_diff = 1: beside the flow cumulants of a test_sampler_flow = 1 run, v_n{2}, v_n{4} and v_n{2,gap} against pT in
+    // uniform bins from flow_pT_min to flow_diff_pt_max, under the same directories (which the check above has found).  Every edge is
+    // computed here, once: flow_pT_min + k (flow_diff_pt_max - flow_pT_min) / bins, the last one flow_diff_pt_max exactly.
+    if (c.flow_diff) {
+        if (!c.flow)
+            DIE("test_sampler_flow_diff = 1 with test_sampler_flow = 0: it writes the differential flow beside the flow cumulants of test_sampler_flow = 1; "
+                "set test_sampler_flow_diff = 0");
+        double bins = 14.0, top = 3.0;
+        p.optional("flow_diff_pt_bins", &bins); p.optional("flow_diff_pt_max", &top);
+        const double lo = c.flow_cuts.pT_min;
+        const bool whole = bins >= 1.0 && bins <= (double)IS3D_FLOW_DIFF_MAX_BINS && bins == (double)(int)bins;
+        const int n = whole ? (int)bins : 0;
+        c.flow_diff_edges.assign((size_t)n + 1, lo);
+        for (int k = 1; k <= n; k++) c.flow_diff_edges[(size_t)k] = k == n ? top : lo + (double)k * (top - lo) / (double)n;
+        bool rising = whole && top > lo && top <= 1.7976931348623157e308;
+        for (int k = 1; k <= n && rising; k++) rising = c.flow_diff_edges[(size_t)k] > c.flow_diff_edges[(size_t)k - 1];
+        if (!rising)
+            DIE("test_sampler_flow_diff = 1 with flow_diff_pt_bins = %g, flow_diff_pt_max = %g, flow_pT_min = %g: the bins need a whole 1 <= flow_diff_pt_bins <= %d "
+                "and a finite flow_diff_pt_max > flow_pT_min that leaves every bin a width; set test_sampler_flow_diff = 0", bins, top, lo, IS3D_FLOW_DIFF_MAX_BINS);
     }
     // test_sampler_pairs = 1: the two-particle (delta y, delta phi) correlations of the same hadrons under results/pairs/
     // (results/decayed/pairs/), refused in the situations that refuse test_sampler_flow, and for bad bins and missing directories
@@ -998,6 +1022,66 @@ static int run_sampler_flow(const RunConfig &cfg, RunInputs &in, const RunDevice
     return IS3D_OK;
 }
 
+// test_sampler_flow_diff = 1: as run_sampler_flow, once more with the same seed, each event batch through cf_sampler_flow_diff (and
+// cf_decay_mc_flow on the differential sink) with the slots of run_sampler_flow and the pT bins of the config; the cuts are those of the
+// flow run with pT_max = flow_diff_pt_max.  differential_<label>.dat per slot and, from the integer sums over the slots, for "all"; the
+// reference of every file is all slots over all bins.
+static int run_sampler_flow_diff(const RunConfig &cfg, RunInputs &in, const RunDevices &rd, SamplerRun &s)
+{
+    NamedSlots th{{211, 321, 2212}}, de{{211, 321, 2212}};
+    std::vector<int32_t> slot, slot_d;
+    DecayTable tab;
+    if (int rc = named_slot_maps(cfg, in, th, de, slot, slot_d, tab)) return rc;
+    const bool decayed = cfg.bin_decayed && !de.label.empty();
+    const int32_t E = s.si.n_events, S = (int32_t)th.label.size(), Sd = (int32_t)de.label.size(), B = (int32_t)cfg.flow_diff_edges.size() - 1;
+    struct Block {
+        std::vector<int64_t> m, re, im;
+        is3d_flow_diff_records view;
+        Block(int32_t events, int32_t slots, int32_t bins)
+            : m((size_t)events * slots * bins * 3), re(m.size() * IS3D_FLOW_HARMONICS), im(re.size()), view{m.data(), re.data(), im.data()} {}
+    } rt(E, S, B), rdec(E, std::max(Sd, 1), B), all(E, 1, B);
+    is3d_flow_cuts cuts = cfg.flow_cuts;
+    cuts.pT_max = cfg.flow_diff_edges.back();
+    is3d_sampler_stats ss{};
+    is3d_decay_mc_stats ms{};
+    int64_t count = 0, n_final = 0, n_unbinned = 0;
+    is3d_options opts = in.opts;
+    opts.device = rd.first();
+    const int rcf = is3d_sample_flow_diff(&in.cells, &in.sp, &in.df, &s.si, &opts, &cuts, B, cfg.flow_diff_edges.data(), slot.data(), S, &rt.view,
+                                          decayed ? &tab.view : nullptr, in.mcid.data(), slot_d.data(), Sd, s.si.seed, 0, &rdec.view, &count, &n_final,
+                                          &n_unbinned, &ss, &ms);
+    if (rcf) DIE("is3d_sample_flow_diff failed (%d): %s", rcf, is3d_last_error());
+    const auto write = [&](const char *dir, Block &b, const std::vector<std::string> &label) {
+        std::vector<const char *> names;
+        for (const std::string &l : label) names.push_back(l.c_str());
+        const int32_t n = (int32_t)label.size();
+        const std::vector<int32_t> every((size_t)n, 1);
+        if (is3d_write_flow_diff(dir, &b.view, E, n, B, cfg.flow_diff_edges.data(), every.data(), 0, B, names.data())) return 1;
+        // "all": the integer sums over the slots, per (event, bin, region)
+        const size_t rec = (size_t)B * 3;
+        for (std::vector<int64_t> Block::*a : {&Block::m, &Block::re, &Block::im}) {
+            const size_t w = rec * (a == &Block::m ? 1 : IS3D_FLOW_HARMONICS);
+            std::fill((all.*a).begin(), (all.*a).end(), 0);
+            for (int32_t e = 0; e < E; e++)
+                for (int32_t k = 0; k < n; k++)
+                    for (size_t j = 0; j < w; j++) (all.*a)[(size_t)e * w + j] += (b.*a)[((size_t)e * n + (size_t)k) * w + j];
+        }
+        const char *const all_name = "all";
+        const int32_t one = 1;
+        return is3d_write_flow_diff(dir, &all.view, E, 1, B, cfg.flow_diff_edges.data(), &one, 0, B, &all_name) ? 1 : 0;
+    };
+    printf("Writing the differential flow (%d slots and all, %d pT bins)...\n", (int)S, (int)B);
+    if (write("results", rt, th.label)) DIE("%s", is3d_last_error());
+    if (decayed) {
+        printf("Writing the differential flow of the decayed hadrons (%d slots and all, %d pT bins)...\n", (int)Sd, (int)B);
+        if (write("results/decayed", rdec, de.label)) DIE("%s", is3d_last_error());
+    }
+    printf("differential flow records on the device: %lld hadrons, ms_bin %.3f ms", (long long)count, ss.ms_bin);
+    if (decayed) printf("; decayed: n_final %lld, n_unbinned %lld, ms_bin %.3f ms", (long long)n_final, (long long)n_unbinned, ms.ms_bin);
+    printf("\n");
+    return IS3D_OK;
+}
+
 // test_sampler_pairs = 1: as run_sampler_flow, the sampler runs once more with the same seed and each event batch goes through cf_pair_cells
 // -- and, with test_sampler_decayed = 1, through cf_decay_mc_pairs -- into occupancies that cf_pair_correlate turns into the same-event and
 // mixed-event histograms after the last batch.  Slots: pi+, pi-, K+, p (211, -211, 321, 2212) where chosen, everything else in one further slot.
@@ -1124,6 +1208,8 @@ static int run_sampler(const RunConfig &cfg, RunInputs &in, const RunDevices &rd
         if (int rc = cfg.bin_decayed ? run_sampler_decayed_binned(cfg, in, rd, s) : run_sampler_binned(cfg, in, rd, s)) return rc;
         if (cfg.flow)
             if (int rc = run_sampler_flow(cfg, in, rd, s)) return rc;
+        if (cfg.flow_diff)
+            if (int rc = run_sampler_flow_diff(cfg, in, rd, s)) return rc;
         if (cfg.pairs)
             if (int rc = run_sampler_pairs(cfg, in, rd, s)) return rc;
         return cfg.hbt ? run_sampler_hbt(cfg, in, rd, s) : IS3D_OK;

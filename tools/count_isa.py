@@ -28,7 +28,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRCS = [os.path.join(ROOT, "is3d_amd", "csrc", f) for f in ("cf_kernels.hip", "cf_feqmod.hip", "cf_vah.hip")]
-AUDIT_ONLY = [os.path.join(ROOT, "is3d_amd", "csrc", f) for f in ("cf_yield.hip", "cf_sampler.hip", "cf_multi.hip", "cf_sampler_hbt.hip")]
+AUDIT_ONLY = [os.path.join(ROOT, "is3d_amd", "csrc", f) for f in ("cf_yield.hip", "cf_sampler.hip", "cf_multi.hip", "cf_sampler_hbt.hip",
+                                                                    "cf_sampler_flow_diff.hip")]
 OUT = os.path.join(ROOT, "is3d_amd", "csrc", "isa_counts.json")
 
 F64_OPS = ["v_fma_f64", "v_fmac_f64", "v_mul_f64", "v_add_f64", "v_max_f64", "v_min_f64", "v_rcp_f64", "v_ldexp_f64",
